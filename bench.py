@@ -2,8 +2,27 @@
 """Headline benchmark: all-vs-all pairwise LD, variant pairs per second (BASELINE.json).
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
+    python bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line: `value` (pairs/s), `ms_per_step`, the
+`roofline` of the timed launches, `config`, `kernel_ms` and the N > 1 figures below.  Everything that takes work of its own
+after the timed region - `roofline.traffic`, `cpu_baseline`, `e2e`, `extra` (the planted step, the other regimes, the N > 1
+gather check) - runs only with --full; the --no-* options still switch single legs of a --full run off.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes as DIR/<name>.npy (float64):
+  n_pairs, n_records  what the last timed step returned to its caller besides the records: its pair and survivor counts (all
+                      ranks);
+  <field>             the last step's survivors, one array per record field (idxA, idxB, flags, cnt (n x 4), D, Dprime, R, R2,
+                      P, ChiSqFisher, ChiSqModel) in (idxA, idxB) order, beyond DUMP_MAX_RECORDS a fixed, seeded sample of them -
+                      only when the step had survivors: the headline workload's iid genotypes leave no pair at r2 >= 0.1;
+  sample_<field>      the same fields from the same engine call (mode, tile size, engine options) on a seeded block of
+                      DUMP_SAMPLE_ROWS x DUMP_SAMPLE_COLS pairs of the same resident input with the r2 cut-off at 0 (P <= 1), so
+                      that the statistics the headline's cut-off keeps out are compared too (rank 0's rows; slab-local indices
+                      in window runs).
+The input is generated from --seed and the block is drawn from it: the same arguments give the same arrays on every run.
 
 Workload (config.workload): BASELINE.json configs[2] -- 1,000,000 diploid samples x 50,000 biallelic
 variants, all-vs-all *unphased* genotype LD (`calc -u`, default filters r2 >= 0.1), synthetic iid
@@ -79,6 +98,8 @@ MIN_P = {"cfg5": 1e-6}
 HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8.0 TB/s spec
 VALU_LANE_PEAK = 256 * 4 * 32 * 2.4e9         # SIMD-32 lane-ops/s (MI355X_MICROARCH.md: v_fma_f32 wave64 = 2 cycles)
 VALU_PAIR_PEAK = 256 * 4 * 64 / 6.0 * 2.4e9   # and(2 cyc)+bcnt(4 cyc) per wave64 word pair, 2.4 GHz
+DUMP_MAX_RECORDS = 400_000       # --dump-outputs: 14 float64 per record, 45 MB at most ...
+DUMP_SAMPLE_ROWS, DUMP_SAMPLE_COLS = 256, 512    # ... and 15 MB for the sampled block
 
 
 def executed_work(tm):
@@ -432,6 +453,45 @@ def record_hashes(recs):
     return h
 
 
+def sample_block(eng, mode, n_variants, seed, tile_variants=0):
+    """--dump-outputs: one engine call on a seeded off-diagonal block of the resident input (rows [a0, a0 + nA) x columns
+    [b0, b0 + nB), b0 >= a0 + nA), r2 cut-off 0 and P <= 1 -> its records."""
+    import numpy as np
+    import tomahawk_amd as T
+    nA, nB = min(DUMP_SAMPLE_ROWS, n_variants // 4), min(DUMP_SAMPLE_COLS, n_variants // 2)
+    rng = np.random.default_rng(seed)
+    a0 = int(rng.integers(0, n_variants - nA - nB + 1))
+    b0 = int(rng.integers(a0 + nA, n_variants - nB + 1))
+    sink = eng._sink_on
+    eng.set_device_sink(False)              # (N > 1: the timed steps leave the survivors on the device)
+    try:
+        recs, _, _ = eng.ld_region(mode, T.Filters(minR2=0.0), a0, nA, b0, nB, False, tile_variants=tile_variants)
+    finally:
+        eng.set_device_sink(sink)
+    return recs
+
+
+def dump_outputs(path, recs, n_pairs, n_records, sample, seed):
+    """--dump-outputs: the last timed step's pair and record counts, its survivors' records (if any) and the sampled block's records,
+    field by field, as float64 arrays in (idxA, idxB) order, whatever order they were delivered in -> path/<name>.npy."""
+    import numpy as np
+    import tomahawk_amd as T
+
+    def fields(r, prefix):
+        r = np.sort(np.asarray(r, dtype=T.RECORD_DTYPE), order=["idxA", "idxB"])
+        if len(r) > DUMP_MAX_RECORDS:
+            r = r[np.sort(np.random.default_rng(seed).choice(len(r), DUMP_MAX_RECORDS, replace=False))]
+        return {prefix + name: r[name].astype(np.float64) for name in T.RECORD_DTYPE.names if not name.startswith("_")}
+
+    os.makedirs(path, exist_ok=True)
+    out = {"n_pairs": np.array([n_pairs], dtype=np.float64), "n_records": np.array([n_records], dtype=np.float64)}
+    if recs is not None and len(recs):
+        out.update(fields(recs, ""))
+    out.update(fields(sample, "sample_"))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def gather_check(eng, rank, world, xdev, gather_group, collective, seed, log):
     """N > 1, after the timed region: does the gather move records, and the right ones?  The headline workload has no survivors
     (iid genotypes, r2 >= 0.1), so its gather carries one count per rank and nothing else.  Here one step of a small, survivor-rich
@@ -524,7 +584,13 @@ def main():
                     "(twk_hip_set_option, include/twk_hip.h; measurement runs of profiles/collect.sh)")
     ap.add_argument("--emulate-shard", default="", help="K/N: run shard K of N on this one GPU (validation of the "
                     "sharded configs on a single-GPU box; the value then covers that shard only)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run what takes work of its own: counter passes "
+                    "(roofline.traffic), cpu_baseline, e2e, extra (planted step, other regimes, N > 1 gather check)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes the last timed step's counts and survivor "
+                    "records to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # The contract is ONE JSON line on stdout.  Libraries underneath do not know that - RCCL prints a banner of its version, the host name
     # and its own path to stdout the first time a communicator comes up (in every rank of an N > 1 run, and in the native-gather leg at N = 1),
@@ -631,7 +697,7 @@ def main():
                                  n_threads=min(os.cpu_count() or 1, 32))
 
     written = {"records": 0}
-    last = {"recs": None}
+    last = {"recs": None, "npairs": 0}
     phase = {"compute": 0.0, "gather": 0.0, "write": 0.0,       # seconds, this rank, summed over the timed steps
              "xfer": 0.0, "xfer_bytes": 0}                      # rank 0: the transfers alone (after every rank has arrived) and their bytes
 
@@ -668,6 +734,7 @@ def main():
             last["recs"] = recs            # (rank 0: every rank's survivors of this step, as the writer saw them)
         t_d = time.perf_counter()
         phase["compute"] += t_b - t_a; phase["gather"] += t_c - t_b; phase["write"] += t_d - t_c
+        last["npairs"] = npairs
         return npairs, nrec
 
     for i in range(args.warmup):
@@ -693,9 +760,10 @@ def main():
     tm = eng.timing()
     spread = launch_spread(eng)
     written_timed, phase_timed = dict(written), dict(phase)          # the timed region's own figures (the legs below go through the same step())
+    last_recs = last["recs"]                                         # (rank 0: the last timed step's survivors, all ranks')
 
     stats = torch.tensor([elapsed, tm["count_ms"], tm["stats_ms"]], dtype=torch.float64)
-    sums = torch.tensor([my_pairs, my_recs, tm["count_launches"], tm["row_pairs"]], dtype=torch.float64)
+    sums = torch.tensor([my_pairs, my_recs, tm["count_launches"], tm["row_pairs"], last["npairs"]], dtype=torch.float64)
     per_rank_ms, ranks_seen = [phase_timed["compute"] / max(args.steps, 1) * 1e3], [rank]
     if world > 1:
         dist.all_reduce(stats, op=dist.ReduceOp.MAX)
@@ -709,6 +777,9 @@ def main():
         seen = [torch.zeros_like(me) for _ in range(world)]
         dist.all_gather(seen, me, group=gather_group)
         ranks_seen = sorted(int(x.item()) for x in seen)
+    if rank == 0 and args.dump_outputs:
+        sample = sample_block(eng, hip_mode, eng.n_variants, args.seed, tile_variants=args.tile)
+        dump_outputs(args.dump_outputs, last_recs, int(round(float(sums[4]))), 0 if last_recs is None else len(last_recs), sample, args.seed)
 
     def planted_leg():
         """A survivor-bearing step of the SAME problem under the same clock (since round 1 the timed region has had 0 survivors: iid
@@ -825,19 +896,19 @@ def main():
         return res
 
     planted = None
-    if not args.no_planted and args.steps > 0:
+    if args.full and not args.no_planted:
         planted = planted_leg()
     if rank == 0:
         shutil.rmtree(out_dir, ignore_errors=True)
     gcheck = None
-    if world > 1 and not args.no_gather_check:
+    if world > 1 and args.full and not args.no_gather_check:
         try:
             gcheck = gather_check(eng, rank, world, xdev, gather_group, collective, args.seed, log)
         except Exception as e:           # a failed check is reported, on every rank alike, not hidden
             gcheck = {"equal": False, "error": repr(e)[:300]} if rank == 0 else None
             log(f"gather_check failed: {e!r}")
     elapsed_max, count_ms_max, stats_ms_max = (float(x) for x in stats.tolist())
-    pairs_all, recs_all, launches_all, row_pairs_all = (float(x) for x in sums.tolist())
+    pairs_all, recs_all, launches_all, row_pairs_all, _ = (float(x) for x in sums.tolist())
     if not args.emulate_shard:
         assert int(round(pairs_all)) == total_pairs * args.steps, (pairs_all, total_pairs * args.steps)
 
@@ -921,7 +992,7 @@ def main():
             out["extra"] = {"gather_check": gcheck}
         if planted is not None:
             out.setdefault("extra", {})[f"{args.config}_planted"] = planted
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 cb = cpu_baseline(n_samples, mode, args.seed, log)
             except Exception as e:  # the baseline must never take the GPU number down with it
@@ -929,7 +1000,7 @@ def main():
                 cb = None
             if cb:
                 out["cpu_baseline"] = cb
-        if world == 1 and not args.no_traffic and not args.emulate_shard:
+        if world == 1 and args.full and not args.no_traffic and not args.emulate_shard:
             eng.close()                  # the profiled child runs the same workload on the same GPU
             cfg_args = ["--config", args.config, "--seed", str(args.seed)]
             if args.variants:
@@ -954,7 +1025,7 @@ def main():
                                                    "as child processes after the timed region), FETCH_SIZE x2 (gfx950), bytes per launch of "
                                                    "the count kernel; FETCH_SIZE counts the L2s' fabric requests (Infinity-Cache hits "
                                                    "included): an upper bound on HBM reads")
-        if world == 1 and not args.no_e2e and args.config == "cfg3" and not args.emulate_shard:
+        if world == 1 and args.full and not args.no_e2e and args.config == "cfg3" and not args.emulate_shard:
             eng.close()                  # the CLI gets the whole GPU
             try:
                 e2e = e2e_from_disk(n_samples, args.e2e_variants or n_variants, log)
@@ -963,7 +1034,7 @@ def main():
                 e2e = None
             if e2e:
                 out["e2e"] = e2e
-        if world == 1 and not args.no_extra and args.config == "cfg3" and not args.emulate_shard and not args.variants and not args.samples:
+        if world == 1 and args.full and not args.no_extra and args.config == "cfg3" and not args.emulate_shard and not args.variants and not args.samples:
             # Every other regime the repository makes claims about, under the same clock as the headline (after the timed
             # region, like cpu_baseline / e2e): each with its pairs/s, dominant kernel, average launch and roofline fraction.
             eng.close()

@@ -44,7 +44,7 @@ for stage in "$@"; do
 		echo "== per-block finish times of the ticketed kernel (2 rounds of whole-K tiles, N = 1M rows)"
 		FINISH=1 timeout 300 $R/build/count_microbench 4096 31264 3 512 > $OUT/microbench_finish_times.txt 2>&1; head -3 $OUT/microbench_finish_times.txt
 		;;
-	cfg3)  timeout 600 python3 $R/bench.py --steps 2 --warmup 1 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.log; cat $OUT/bench_cfg3.json ;;
+	cfg3)  timeout 600 python3 $R/bench.py --full --steps 2 --warmup 1 > $OUT/bench_cfg3.json 2> $OUT/bench_cfg3.log; cat $OUT/bench_cfg3.json ;;
 	cfg3_stats) stats cfg3 --steps 2 --warmup 1 ;;
 	cfg3_sq)   # the work-is-done check of the headline kernel, every round: VALU instructions issued against the products + v_or the launches stand for
 		pmc cfg3_sq "SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" --steps 1 --warmup 0
@@ -74,12 +74,12 @@ PY
 		done
 		;;
 	cfg2)
-		timeout 600 python3 $R/bench.py --config cfg2 --no-traffic --steps 20 --warmup 3 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.log; cat $OUT/bench_cfg2.json
+		timeout 600 python3 $R/bench.py --full --config cfg2 --no-traffic --steps 20 --warmup 3 > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.log; cat $OUT/bench_cfg2.json
 		stats cfg2 --config cfg2 --steps 20 --warmup 3
 		pmc cfg2_sq "SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" --config cfg2 --steps 5 --warmup 1
 		;;
 	cfg5)
-		timeout 900 python3 $R/bench.py --config cfg5 --no-traffic --emulate-shard 3/8 --steps 1 --warmup 0 > $OUT/bench_cfg5_shard3of8.json 2> $OUT/bench_cfg5_shard3of8.log; cat $OUT/bench_cfg5_shard3of8.json
+		timeout 900 python3 $R/bench.py --full --config cfg5 --no-traffic --emulate-shard 3/8 --steps 1 --warmup 0 > $OUT/bench_cfg5_shard3of8.json 2> $OUT/bench_cfg5_shard3of8.log; cat $OUT/bench_cfg5_shard3of8.json
 		;;
 	cfg5_prof)
 		stats cfg5_shard3of8 --config cfg5 --emulate-shard 3/8 --steps 1 --warmup 0
