@@ -33,6 +33,7 @@ extern "C" {
 /* 5: twk_hip_generate_synthetic_planted / twk_synth_planted_bitvector / twk_synth_plant_source (synthetic input with planted LD pairs);
  *    twk_hip_option_describe; twk_hip_timing grew (finish_ms); twk_hip_gather_records / twk_hip_gather_backend /
  *    twk_hip_drain_device_sink (the RCCL gather of a one-process multi-GPU run). */
+/*    (still 5: twk_hip_ld_score - LD scores - is an entry point more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -272,6 +273,28 @@ int twk_hip_ld_region(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters
                       uint32_t part, uint32_t n_parts, uint32_t tile_variants,
                       int32_t window, uint32_t l_window,
                       twk_hip_record_sink sink, void* user, uint64_t* n_pairs, uint64_t* n_records);
+
+/* LD scores over the same slice of the pair space, with the same arguments: for every variant v of the problem
+ *   n_partners[v] = the number of records twk_hip_ld_region would report with v as idxA or idxB,
+ *   sum_r2[v]     = the sum of their R2 fields
+ * - with filters.minR2 = 0 the LD score of v, with minR2 = 0.8 its number of tagging partners - reduced on the device:
+ * the count matrix of a launch goes through the pair rules and the math of the record path (skips, the default mode's
+ * per-pair choice of math, D = 0, the cubic's roots, window, r2 / D' bounds, option bits: one code, ld_math.hip.h) and the
+ * r2 of the pairs that survive is summed per row and per column (ld_score.hip.h).  No record is formed, sorted or copied:
+ * 16 bytes per variant leave the device.  filters.minP must be >= 1 (TWK_HIP_E_INVALID otherwise): the two-sided P never
+ * exceeds 1, so that bound drops nothing and Fisher's test is not run.  Always the matrix form of the contraction (no r2
+ * band, no fused screen, no carrier lists: a score looks at every pair; TWK_HIP_OPT_R2_SCREEN is ignored).  n_partners /
+ * sum_r2: HOST arrays of n_variants entries each, indexed by variant as uploaded, overwritten (variants outside the slice:
+ * 0 / 0.0).  A shard (part / n_parts: the rows of twk_hip_ld_region's shard) returns partial arrays over all variants; the
+ * shards' arrays add up to the whole.  The sums are formed in a fixed order without floating-point atomics: two calls with
+ * the same arguments return the same bits.  *n_pairs (may be NULL): pairs evaluated.  twk_hip_timing: the score kernels
+ * count as the math stage (stats_ms, stats_launches, variant_pairs).  There is NO reference counterpart: the reference
+ * writes records only, and a score is a sum over its output file. */
+int twk_hip_ld_score(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                     uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                     uint32_t part, uint32_t n_parts, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window,
+                     uint64_t* n_partners, double* sum_r2, uint64_t* n_pairs);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

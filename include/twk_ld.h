@@ -59,6 +59,12 @@ public:
 	// The reference's compile-time-gated micro-benchmark (ld.cpp:878-1057): not
 	// available, returns false like a reference build without TWK_SLAVE_DEBUG_MODE.
 	bool ComputePerformance();
+	// Not in the reference: LD scores.  Loads the .twk exactly as Compute does (-I intervals, -w, -p / -u, -c / -C chunks as regions,
+	// TWK_REF_COMPAT), and instead of records writes one text line per variant of the selection, in file order, to settings.out
+	// ("-" or empty: stdout): contig, position (as `view` prints posA), the number of records Compute would write with the variant at
+	// either end, and the sum of their R2 with 17 significant digits - reduced on one GPU (twk_hip_ld_score), no record is formed.
+	// settings.minP must be 1 (the default).  `tomahawk ldscore` ends here.
+	bool Score(const twk_ld_settings& settings);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

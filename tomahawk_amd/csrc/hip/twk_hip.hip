@@ -5,6 +5,7 @@
 //   count (ld_count.hip.h) LDS-tiled AND+popcount contraction  [dominant kernel]
 //   math  (ld_math.hip.h)  cells -> D/D'/r2/Fisher -> filters -> compaction
 //   (ld_three.hip.h: screen + recount behind the three-product form of the unphased contraction)
+//   score (ld_score.hip.h) cells -> r2 -> per-variant sums, in place of the math stage (twk_hip_ld_score)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -33,6 +34,7 @@
 #include "ld_math.hip.h"
 #include "ld_list.hip.h"
 #include "ld_three.hip.h"
+#include "ld_score.hip.h"
 #include "ld_plan.h"
 #include "twk_delivery.h"
 
@@ -122,6 +124,9 @@ struct Slot {                      // one in-flight tile (double buffered)
 	uint64_t row_pairs = 0, row_pairs_b = 0;
 	// work lists of the (up to two) count launches of the tile: pinned host copy + device copy
 	uint32_t* h_tiles[2] = {nullptr, nullptr}; uint32_t* d_tiles[2] = {nullptr, nullptr}; size_t tiles_cap[2] = {0, 0};
+	// score launches (ld_score.hip.h): the blocks' row and column partials of the launch (grow-only)
+	double* sc_sum = nullptr; uint32_t* sc_n = nullptr; size_t sc_cap = 0;
+	ScoreArgs* h_sc_args = nullptr; ScoreArgs* d_sc_args = nullptr;      // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
 };
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
@@ -246,6 +251,9 @@ struct twk_hip_ctx {
 	uint8_t* d_rle_desc = nullptr; size_t d_rle_desc_cap = 0;
 	int* d_status = nullptr;
 	uint32_t* d_col_hi = nullptr; size_t d_col_hi_cap = 0;   // r2 screen: per-row column limit of the current region
+	// twk_hip_ld_score: the launches of the running call sum r2 per variant (ld_score.hip.h) instead of keeping records
+	bool score_on = false;
+	double* d_score_sum = nullptr; unsigned long long* d_score_n = nullptr;      // [M] accumulators, variant ids in file order
 	char err[512] = {0};
 };
 
@@ -283,6 +291,11 @@ void free_slots(twk_hip_ctx* c) {
 		if (s.vals) (void)hipFree(s.vals);
 		if (s.sorted) (void)hipFree(s.sorted);
 		s.C = nullptr; s.C_words = 0; s.out = nullptr; s.keys = nullptr; s.vals = nullptr; s.capacity = 0; s.sorted = nullptr; s.sorted_cap = 0;
+		if (s.sc_sum) (void)hipFree(s.sc_sum);
+		if (s.sc_n) (void)hipFree(s.sc_n);
+		if (s.h_sc_args) (void)hipHostFree(s.h_sc_args);
+		if (s.d_sc_args) (void)hipFree(s.d_sc_args);
+		s.sc_sum = nullptr; s.sc_n = nullptr; s.sc_cap = 0; s.h_sc_args = nullptr; s.d_sc_args = nullptr;
 		for (int k = 0; k < 2; ++k) {
 			if (s.h_tiles[k]) (void)hipHostFree(s.h_tiles[k]);
 			if (s.d_tiles[k]) (void)hipFree(s.d_tiles[k]);
@@ -293,8 +306,9 @@ void free_slots(twk_hip_ctx* c) {
 void free_problem(twk_hip_ctx* c) {
 	free_planes(c);
 	free_slots(c);
-	void* ptrs[] = {c->raw, c->rawmask, c->d_ac, c->d_an, c->d_pos, c->d_rid, c->d_missing, c->d_hwe, c->d_lfact};
+	void* ptrs[] = {c->raw, c->rawmask, c->d_ac, c->d_an, c->d_pos, c->d_rid, c->d_missing, c->d_hwe, c->d_lfact, c->d_score_sum, c->d_score_n};
 	for (void* p : ptrs) if (p) (void)hipFree(p);
+	c->d_score_sum = nullptr; c->d_score_n = nullptr;
 	c->raw = c->rawmask = nullptr; c->d_lfact = nullptr; c->lfact_n = 0;
 	c->d_ac = c->d_an = c->d_pos = c->d_rid = c->d_missing = nullptr; c->d_hwe = nullptr;
 	c->h_meta.clear();
@@ -783,6 +797,40 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	return TWK_HIP_OK;
 }
 
+// The score epilogue of a launch whose count matrix is in the slot's C (ld_score.hip.h): the pairs' r2 summed per row and per column
+// inside the blocks, the blocks' partials folded into the context's per-variant accumulators - rows, then columns, each in a launch of
+// its own, so that a variant that is both a row and a column of a diagonal launch is added to by one lane at a time.
+int launch_score(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
+	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
+	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
+	if (!t.nA || !t.nB) return TWK_HIP_OK;
+	if (!s.h_sc_args) HIPCHK(c, hipHostMalloc((void**)&s.h_sc_args, 2 * sizeof(ScoreArgs), hipHostMallocDefault));
+	if (!s.d_sc_args) HIPCHK(c, hipMalloc((void**)&s.d_sc_args, 2 * sizeof(ScoreArgs)));
+	ScoreParts sp{};
+	sp.gx = (t.nB + SCORE_THREADS - 1) / SCORE_THREADS; sp.gy = (t.nA + SCORE_ROWS - 1) / SCORE_ROWS;
+	if (sp.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
+	const size_t n_row = (size_t)t.nA * sp.gx, n_col = (size_t)sp.gy * t.nB, need = n_row + n_col;
+	if (s.sc_cap < need) {
+		if (s.sc_sum) c->graveyard.push_back(s.sc_sum);
+		if (s.sc_n) c->graveyard.push_back(s.sc_n);
+		s.sc_sum = nullptr; s.sc_n = nullptr; s.sc_cap = 0;
+		HIPCHK(c, dev_malloc(c, (void**)&s.sc_sum, need * sizeof(double)));
+		HIPCHK(c, dev_malloc(c, (void**)&s.sc_n, need * sizeof(uint32_t)));
+		s.sc_cap = need;
+	}
+	sp.row_sum = s.sc_sum; sp.row_n = s.sc_n; sp.col_sum = s.sc_sum + n_row; sp.col_n = s.sc_n + n_row;
+	const uint32_t* ids = c->planes[set].ids;
+	s.h_sc_args[which].p = p; s.h_sc_args[which].sp = sp;      // (the slot's previous launch has been waited for: its copy is done)
+	HIPCHK(c, hipMemcpyAsync(s.d_sc_args + which, s.h_sc_args + which, sizeof(ScoreArgs), hipMemcpyHostToDevice, c->s_compute));
+	hipLaunchKernelGGL(k_ld_score, dim3(sp.gx, sp.gy), dim3(SCORE_THREADS), 0, c->s_compute, (const ScoreArgs*)(s.d_sc_args + which));
+	hipLaunchKernelGGL(k_ld_score_fold, dim3((t.nA + 255) / 256), dim3(256), 0, c->s_compute, (const double*)sp.row_sum, (const uint32_t*)sp.row_n, t.nA, sp.gx,
+	                   (size_t)sp.gx, (size_t)1, t.rowA0, ids, c->M, c->d_score_sum, c->d_score_n);
+	hipLaunchKernelGGL(k_ld_score_fold, dim3((t.nB + 255) / 256), dim3(256), 0, c->s_compute, (const double*)sp.col_sum, (const uint32_t*)sp.col_n, t.nB, sp.gy,
+	                   (size_t)1, (size_t)t.nB, t.rowB0, ids, c->M, c->d_score_sum, c->d_score_n);
+	HIPCHK(c, hipGetLastError());
+	return TWK_HIP_OK;
+}
+
 // list_words != 0: a band launch (region_impl) - the fused form with a candidate list of that many words and no count
 // matrix at all (its rectangle may be far beyond what a matrix could hold); it is an error if the launch does not fuse.
 int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, Slot& s,
@@ -794,6 +842,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	int rc = ensure_planes(c, kind1); if (rc) return rc;
 	if (two_pass) { rc = ensure_planes(c, kind2); if (rc) return rc; }
 	const Geometry g = tile_geometry(pl.Pmax, t);
+	if (c->score_on) { if (list_words) return TWK_HIP_E_STATE; capacity = 1; }      // a score launch keeps no survivors: always the matrix form
 	if (list_words && !fused_form_applies(c, mode, f)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
@@ -805,7 +854,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	// The fused form: plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
 	// pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.
 	const bool fused_u = !phased && set_kind(kind1) == PK_UNPHASED;
-	const bool want_fused = c->fused_ok && ((phased && set_kind(kind1) == PK_PHASED) || fused_u) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
+	const bool want_fused = !c->score_on && c->fused_ok && ((phased && set_kind(kind1) == PK_PHASED) || fused_u) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
 	FusedArgs fa{};
 	fa.unphased = fused_u ? 1 : 0;
 	ScreenWork& sw = fa.screen;
@@ -882,6 +931,8 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		else if (d_stats)     // (no tiles, no launch, no candidates)
 			hipLaunchKernelGGL(k_ld_stats_list, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, d_stats, (const uint32_t*)s.C,
 			                   (const unsigned long long*)(s.n_out + 2), s.cand_cap);
+	} else if (c->score_on) {
+		rc = launch_score(c, kind1, t, s, 0, phased, pl.select1, f, cr); if (rc) return rc;
 	} else {
 		const StatsParams p = make_stats(c, kind1, t, s, phased, pl.select1, f, cr);
 		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -889,13 +940,17 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	HIPCHK(c, hipGetLastError());
 	if (two_pass) {
 		rc = launch_count(c, kind2, t, s, 1, s.ev_c0b, s.ev_c1b, &s.row_pairs_b, cr); if (rc) return rc;
-		const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
-		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
+		if (c->score_on) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
+		else {
+			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
+			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
+		}
 		HIPCHK(c, hipGetLastError());
 	}
 	// Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is free by now - the math
 	// kernels in front are done with it - and holds the walk-length order)
-	rc = launch_fisher(c, s.out, s.n_out, s.cap_use, f.minP, s.C, s.C_words, s.keys); if (rc) return rc;
+	// (a score launch has none, and no test to run: minP >= 1 drops nothing)
+	if (!c->score_on) { rc = launch_fisher(c, s.out, s.n_out, s.cap_use, f.minP, s.C, s.C_words, s.keys); if (rc) return rc; }
 	HIPCHK(c, hipGetLastError());
 	s.minP = f.minP;
 	HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
@@ -2266,7 +2321,7 @@ static int region_dispatch(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 	if (nA == 0 || nB == 0 || (uint64_t)a0 + nA > c->M || (uint64_t)b0 + nB > c->M) return TWK_HIP_E_INVALID;
 	if (triangle && (a0 != b0 || nB < nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = true; c->three_ok = true;
+	c->fused_ok = c->three_ok = !c->score_on;      // a score looks at every pair: no screen in front of the matrix
 	const bool whole = triangle && a0 == 0 && nA == c->M && nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2338,6 +2393,33 @@ static int region_dispatch(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 	}
 	if (n_pairs) *n_pairs = pairs;          // every pair of the shard is evaluated exactly once
 	if (n_records) *n_records = recs;
+	return rc;
+}
+
+// LD scores: the region call's planner and launch pipeline with the score epilogue in place of math, Fisher, sort and delivery.
+int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                     uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                     uint64_t* n_partners, double* sum_r2, uint64_t* n_pairs) {
+	if (!c || !f || !n_partners || !sum_r2 || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	HIPCHK(c, hipSetDevice(c->device));
+	const size_t M = c->M;
+	if (!c->d_score_sum) HIPCHK(c, hipMalloc((void**)&c->d_score_sum, M * sizeof(double)));
+	if (!c->d_score_n) HIPCHK(c, hipMalloc((void**)&c->d_score_n, M * sizeof(unsigned long long)));
+	HIPCHK(c, hipMemsetAsync(c->d_score_sum, 0, M * sizeof(double), c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_score_n, 0, M * sizeof(unsigned long long), c->s_compute));
+	struct ScoreOn { twk_hip_ctx* c; ~ScoreOn() { c->score_on = false; } } on{c};
+	c->score_on = true;
+	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a score)
+	int rc = region_dispatch(c, mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
+	                         nullptr, nullptr, n_pairs, nullptr);
+	if (rc == TWK_HIP_OK) {
+		hipError_t e = hipMemcpyAsync(sum_r2, c->d_score_sum, M * sizeof(double), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "score arrays: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
+	} else (void)hipDeviceSynchronize();
+	flush_graveyard(c);
 	return rc;
 }
 

@@ -138,6 +138,102 @@ static int calc(int argc, char** argv) {
 	return ld.Compute(settings) ? 0 : 1;
 }
 
+// `tomahawk ldscore` (not in the reference): per-variant sums of r2 over the records `calc` would write, reduced on the GPU.
+static void ldscore_usage() {
+	program_message();
+	std::cerr <<
+	"About:  LD scores: for every variant the number of partners `calc` would report it with\n"
+	"        and the sum of their R-squared values, reduced on the GPU (no .two is written).\n"
+	"        With -r 0 (default) the sum is the LD score; with -r 0.8 the count is the number\n"
+	"        of tagging partners.\n\n"
+	"Usage:  tomahawk ldscore [options] -i <in.twk> [-o <out.tsv>]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o FILE   output text file (- for stdout; default: -)\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -c INT    number of subproblems to split compute into (must be in (c!2 + c))\n"
+	"  -C INT    chosen part to compute (0 < -C < -c)\n"
+	"  -w INT    sliding window width in bases\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value (default: 0)\n"
+	"  -P FLOAT  accepted only as 1: a score sums over every record, Fisher's test is not run\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"Output: '#' header lines, then per variant: contig <TAB> pos <TAB> n_partners <TAB> sum_r2\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int ldscore(int argc, char** argv) {
+	if (argc < 3) { ldscore_usage(); return 1; }
+	static struct option long_options[] = {
+		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
+		{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
+		{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
+		{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
+		{"engine-option", required_argument, 0, 1000}, {0, 0, 0, 0}};
+	tomahawk::twk_ld_settings settings;
+	settings.minR2 = 0;
+	settings.out = "-";
+	int c, option_index = 0;
+	std::vector<std::pair<std::string, long long>> engine_options;
+	while ((c = getopt_long(argc, argv, "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
+		switch (c) {
+		case 'i': settings.in = optarg; break;
+		case 'o': settings.out = optarg; break;
+		case 'I': settings.ival_strings.push_back(optarg); break;
+		case 'p': settings.force_phased = true; settings.forced_unphased = false; break;
+		case 'u': settings.forced_unphased = true; settings.force_phased = false; break;
+		case 't':
+			settings.n_threads = atoi(optarg);
+			if (settings.n_threads <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of worker threads" << std::endl; return 1; }
+			break;
+		case 'c':
+			settings.n_chunks = atoi(optarg);
+			if (settings.n_chunks <= 0) { std::cerr << stamp("ERROR") << "Cannot have a negative or zero amount of partitions" << std::endl; return 1; }
+			break;
+		case 'C':
+			settings.c_chunk = atoi(optarg) - 1;   // 1-based on the command line, as for calc
+			if (settings.c_chunk < 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive start partition" << std::endl; return 1; }
+			break;
+		case 'r':
+			settings.minR2 = atof(optarg);
+			if (settings.minR2 < 0) { std::cerr << stamp("ERROR") << "Cannot have a negative minimum R-squared value" << std::endl; return 1; }
+			if (settings.minR2 > 1) { std::cerr << stamp("ERROR") << "Cannot have minimum R-squared value > 1" << std::endl; return 1; }
+			break;
+		case 'P':
+			settings.minP = atof(optarg);
+			if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run" << std::endl; return 1; }
+			if (settings.minP > 1) { std::cerr << stamp("ERROR") << "Cannot have a cutoff P-value > 1" << std::endl; return 1; }
+			break;
+		case 'w': {
+			settings.window = true;
+			const std::string a(optarg);
+			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << "not an integer" << std::endl; return 1; }
+			settings.l_window = std::regex_match(a, std::regex("^[0-9]+$")) ? atoi(optarg) : (int32_t)atof(optarg);
+			if (settings.l_window <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive window size" << std::endl; return 1; }
+			break;
+		}
+		case 1000: {
+			const std::string a(optarg);
+			const size_t eq = a.find('=');
+			if (eq == std::string::npos || eq == 0 || eq + 1 >= a.size()) { std::cerr << stamp("ERROR") << "--engine-option wants key=value" << std::endl; return 1; }
+			engine_options.emplace_back(a.substr(0, eq), atoll(a.c_str() + eq + 1));
+			break;
+		}
+		default:
+			std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl;
+			return 1;
+		}
+	}
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
+	program_message();
+	std::cerr << stamp("LOG") << "Calling ldscore..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Score(settings) ? 0 : 1;
+}
+
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
 static int concat(int argc, char** argv) {
 	if (argc < 3) {
@@ -428,6 +524,7 @@ static int run_main(int argc, char** argv) {
 		             "  import   convert VCF text (plain / gzip) to .twk\n"
 		             "  calc     calculate linkage disequilibrium: tomahawk calc [options] -i <in.twk> -o <output.two>\n"
 		             "  scalc    linkage disequilibrium of one site against its neighbourhood\n"
+		             "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n"
 		             "  sort     sort a .two file\n"
 		             "  view     convert, filter and slice .two files\n"
 		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
@@ -441,6 +538,7 @@ static int run_main(int argc, char** argv) {
 	tomahawk::LITERAL_COMMAND_LINE = "tomahawk";
 	for (int i = 1; i < argc; ++i) tomahawk::LITERAL_COMMAND_LINE += " " + std::string(argv[i]);
 	if (strcmp(argv[1], "calc") == 0) return calc(argc, argv);
+	if (strcmp(argv[1], "ldscore") == 0) return ldscore(argc, argv);
 	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
 	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
 	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
@@ -449,7 +547,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
 	return 1;
 }
 

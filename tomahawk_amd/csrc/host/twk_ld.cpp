@@ -16,6 +16,7 @@
 #include <ctime>
 #include <iomanip>
 #include <iostream>
+#include <fstream>
 #include <regex>
 #include <sstream>
 #include <thread>
@@ -774,18 +775,31 @@ bool twk_ld::twk_ld_impl::run(twk_ld_settings& settings, const Header& hdr, cons
 	return true;
 }
 
-bool twk_ld::Compute() {
-	using clock = std::chrono::steady_clock;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+// What a run computes on, from the settings: the input file, the blocks the intervals (-I) select, the chunk (-c / -C) of their
+// pair space and the blocks of its row and column ranges.  Shared by Compute and Score.  *nothing_to_do: no valid data (the
+// caller returns true, like the reference).
+namespace {
+struct Selection {
+	TwkReader reader;
+	uint32_t n_samples = 0;
+	Balancer bal;
+	std::vector<uint32_t> sel;       // the L range's blocks, then (square chunk only) the R range's
+	uint32_t nL = 0, nR = 0, M = 0;
+};
+}  // namespace
+static bool select_blocks(twk_ld_settings& settings, Selection& S, bool* nothing_to_do) {
+	*nothing_to_do = false;
+	TwkReader& reader = S.reader;
+	Balancer& bal = S.bal;
+	std::vector<uint32_t>& sel = S.sel;
+	uint32_t& nL = S.nL; uint32_t& nR = S.nR;
 	if (settings.window && settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot use chunking in window mode!" << std::endl; return false; }
 	if (settings.bitmaps || settings.low_memory)
 		std::cerr << stamp("LOG") << "Note: -m/-M are CPU memory-saving modes; the GPU engine keeps dense bit-planes in HBM." << std::endl;
 
 	std::cerr << stamp("LOG", "READER") << "Opening " << settings.in << "..." << std::endl;
-	TwkReader reader;
 	if (!reader.open(settings.in)) { std::cerr << stamp("ERROR") << "Failed to open file: " << settings.in << "... (" << reader.error << ")" << std::endl; return false; }
-	const uint32_t n_samples = (uint32_t)reader.hdr.samples.size();
+	const uint32_t n_samples = S.n_samples = (uint32_t)reader.hdr.samples.size();
 	std::cerr << stamp("LOG") << "Samples: " << pretty(n_samples) << "..." << std::endl;
 
 	// The universe of blocks: all of them, or (-I) those overlapping the intervals
@@ -804,24 +818,37 @@ bool twk_ld::Compute() {
 		if (universe.empty()) { std::cerr << stamp("ERROR", "INTERVAL") << "Found no blocks overlapping the provided range(s)..." << std::endl; return false; }
 	}
 	const uint32_t n_blocks = (uint32_t)universe.size();
-	if (n_blocks == 0 || n_samples == 0) { std::cerr << stamp("ERROR") << "No valid data available..." << std::endl; return true; }
+	if (n_blocks == 0 || n_samples == 0) { std::cerr << stamp("ERROR") << "No valid data available..." << std::endl; *nothing_to_do = true; return true; }
 
 	if (settings.window) settings.c_chunk = 0;
-	Balancer bal;
 	if (!bal.build(n_blocks, (uint32_t)settings.n_chunks, (uint32_t)settings.c_chunk)) return false;
 	std::cerr << stamp("LOG", "BALANCING") << "Using ranges [" << bal.fromL << "-" << bal.toL << "," << bal.fromR << "-" << bal.toR
 	          << "] in " << (settings.window ? "window mode" : "square mode") << "..." << std::endl;
 
 	// Selected blocks: the L range, then (square chunk only) the R range.
-	std::vector<uint32_t> sel;
-	uint32_t nL = 0, nR = 0;
 	for (uint32_t b = bal.fromL; b < bal.toL; ++b) { sel.push_back(universe[b]); nL += reader.index.ent[universe[b]].n; }
 	if (!bal.diag) for (uint32_t b = bal.fromR; b < bal.toR; ++b) { sel.push_back(universe[b]); nR += reader.index.ent[universe[b]].n; }
-	const uint32_t M = nL + nR;
+	const uint32_t M = S.M = nL + nR;
 	const uint64_t n_cmp = bal.diag ? (uint64_t)M * (M - 1) / 2 : (uint64_t)nL * nR;
 	std::cerr << stamp("LOG") << pretty(M) << " variants from " << pretty(sel.size()) << " blocks..." << std::endl;
 	std::cerr << stamp("LOG", "PARAMS") << settings.GetString() << std::endl;
 	std::cerr << stamp("LOG") << "Performing: " << pretty(n_cmp) << " variant comparisons..." << std::endl;
+
+	return true;
+}
+
+bool twk_ld::Compute() {
+	using clock = std::chrono::steady_clock;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+	Selection S;
+	bool nothing_to_do = false;
+	if (!select_blocks(settings, S, &nothing_to_do)) return false;
+	if (nothing_to_do) return true;
+	TwkReader& reader = S.reader;
+	const Balancer& bal = S.bal;
+	const std::vector<uint32_t>& sel = S.sel;
+	const uint32_t n_samples = S.n_samples, nL = S.nL, nR = S.nR, M = S.M;
 
 	const int n_gpus = gpus_from_env();
 	DeviceCtxs dc;
@@ -908,6 +935,77 @@ bool twk_ld::Compute() {
 		if (!cw.forced) spec.options &= ~TWK_HIP_OPT_WINDOW;
 	}
 	if (!mImpl->run(settings, reader.hdr, dc.ctx, n_samples, &spec)) return false;
+	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	return true;
+}
+
+// `tomahawk ldscore`: per variant of the selection the number of records Compute would write with the variant at either end and the
+// sum of their R2 (twk_hip_ld_score: reduced on the GPU, no record is formed), as text.  The input is loaded exactly as Compute loads
+// it; one GPU.  Not in the reference.
+bool twk_ld::Score(const twk_ld_settings& s) {
+	using clock = std::chrono::steady_clock;
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "A score sums over every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
+	Selection S;
+	bool nothing_to_do = false;
+	if (!select_blocks(settings, S, &nothing_to_do)) return false;
+	if (nothing_to_do) return true;
+	const Balancer& bal = S.bal;
+	const uint32_t M = S.M;
+	DeviceCtxs dc;
+	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
+	twk_hip_ctx* ctx = dc.ctx[0];
+	const auto t_load = clock::now();
+	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
+	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
+	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
+	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
+	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
+
+	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
+	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
+	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	std::vector<uint64_t> n_partners(M, 0);
+	std::vector<double> sum_r2(M, 0.0);
+	uint64_t np = 0;
+	const auto t0 = clock::now();
+	int rc = TWK_HIP_OK;
+	if (bal.diag) { if (M > 1) rc = twk_hip_ld_score(ctx, mode, &f, 0, M, 0, M, 1, 0, 1, 0, options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np); }
+	else if (S.nL && S.nR) rc = twk_hip_ld_score(ctx, mode, &f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
+	if (!hip_ok(ctx, rc, "twk_hip_ld_score")) return false;
+	mImpl->n_pairs = np;
+	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+
+	std::ofstream file;
+	const bool to_stdout = settings.out.empty() || settings.out == "-";
+	if (!to_stdout) {
+		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
+		file.open(settings.out, std::ios::out | std::ios::trunc);
+		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return false; }
+	}
+	std::ostream& os = to_stdout ? std::cout : file;
+	os << "##tomahawk_ldscoreVersion=" << TWK_AMD_VERSION << "\n"
+	   << "##tomahawk_ldscoreCommand=" << command_line() << "; Date=" << datetime() << "\n"
+	   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
+	char line[256];
+	snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
+	os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n"
+	   << "#contig\tpos\tn_partners\tsum_r2\n";
+	std::string text;
+	for (uint32_t v = 0; v < M; ++v) {
+		const uint32_t rid = mImpl->rid[v];
+		// (contig and position as `view` prints them for a record's A side: the contig's name, the 1-based position)
+		if (rid < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid].name; else text += '.';
+		snprintf(line, sizeof(line), "\t%u\t%llu\t%.17g\n", mImpl->pos[v] + 1, (unsigned long long)n_partners[v], sum_r2[v]);
+		text += line;
+		if (text.size() > (1u << 20)) { os << text; text.clear(); }
+	}
+	os << text;
+	os.flush();
+	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the scores..." << std::endl; return false; }
+	std::cerr << stamp("LOG") << "Scored " << pretty(M) << " variants over " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
 	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
 	return true;
 }

@@ -185,6 +185,9 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_region.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                       C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, _SINK, p,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_score.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
+                                     C.POINTER(C.c_uint64)]
     lib.twk_hip_shard_rows.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_plan_region.argtypes = [p, p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
@@ -452,6 +455,23 @@ class HipLd:
                                                 C.byref(npairs), C.byref(nrec)), "twk_hip_ld_region")
         recs = np.concatenate(chunks) if chunks else np.zeros(0, dtype=RECORD_DTYPE)
         return recs, npairs.value, nrec.value
+
+    def ld_score(self, mode: int, filters: Filters, a0: int = 0, nA: int | None = None, b0: int = 0, nB: int | None = None,
+                 triangle: bool = True, part: int = 0, n_parts: int = 1, tile_variants: int = 0, window: int = 0, l_window: int = 0):
+        """LD scores (twk_hip_ld_score): per variant the number of records ld_region would report with the variant at either end
+        and the sum of their R2, reduced on the device - no record is formed.  filters.minP must be >= 1.  A shard returns
+        partial arrays over all variants.  -> (n_partners uint64[M], sum_r2 float64[M], n_pairs)."""
+        M = self.n_variants
+        nA = M - a0 if nA is None else nA
+        nB = M - b0 if nB is None else nB
+        n = np.zeros(M, dtype=np.uint64)
+        s = np.zeros(M, dtype=np.float64)
+        npairs = C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_score(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts,
+                                               tile_variants, int(window), l_window, n.ctypes.data, s.ctypes.data,
+                                               C.byref(npairs)), "twk_hip_ld_score")
+        return n, s, npairs.value
 
     def fisher_exact(self, tables: np.ndarray, ordered: bool = True):
         """Two-sided Fisher P of int32 tables [n, 4] = (n11, n12, n21, n22) through the engine's Fisher kernels
