@@ -36,9 +36,17 @@ def _run(hip, opt, lists_env, data, mask, variants, calls):
     for call in calls:
         hip.timing_reset()
         recs = call()
-        out.append((recs, hip.timing()))
+        tm = hip.timing()
+        # list and probe blocks are not count launches: whatever form the slot's previous launch had is none of theirs
+        assert tm["three_launches"] <= tm["count_launches"] and tm["fused_launches"] <= tm["count_launches"], tm
+        out.append((recs, tm))
     opt.unset("lists"); opt.unset("probe_zone")
     return out
+
+
+# every integer field of the timing that is neither a time nor a clock count: what a call did, which a repeat of it must do again
+WORK_FIELDS = ("count_launches", "fused_launches", "three_launches", "list_launches", "probe_launches", "row_pairs", "three_row_pairs",
+               "list_pairs", "probe_pairs", "variant_pairs", "candidates", "recount_candidates", "stats_launches")
 
 
 @pytest.mark.parametrize("N,forced", [(66_000, False), (1500, True)])
@@ -126,12 +134,17 @@ def test_unphased_list_zone_equals_dense_and_oracle(hip, opt, N, forced):
              lambda: hip.ld_all(mode, T.Filters(minR2=0.5), window=T.OPT_R2_SCREEN)[0],
              lambda: hip.ld_all(mode, T.Filters(minR2=0.01), window=T.OPT_R2_SCREEN)[0],
              lambda: np.concatenate([hip.ld_all(mode, T.Filters(minR2=0.1), part=k, n_parts=3, window=T.OPT_R2_SCREEN)[0] for k in range(3)])]
+    calls.append(calls[0])          # the first call once more, behind the others: the same work and the same records
     dense = _run(hip, opt, "0", data, None, variants, calls)
     lists = _run(hip, opt, "2" if forced else "1", data, None, variants, calls)
     for k, ((a, ta), (b, tb)) in enumerate(zip(dense, lists)):
         assert ta["list_launches"] == 0 and tb["list_launches"] > 0 and tb["list_pairs"] > 10_000, (k, tb)
         assert len(a) == len(b) > 20, k
         assert np.sort(a, order=ORDER).tobytes() == np.sort(b, order=ORDER).tobytes(), k
+    for runs in (dense, lists):
+        (first, t_first), (again, t_again) = runs[0], runs[-1]
+        assert {k: t_again[k] for k in WORK_FIELDS} == {k: t_first[k] for k in WORK_FIELDS}
+        assert again.tobytes() == first.tobytes()
     ac = np.minimum(variants["ac"], 2 * N - variants["ac"])
     rare = np.argsort(ac, kind="stable")[:300]
     sub = np.sort(np.concatenate([rare, np.random.default_rng(2).choice(np.setdiff1d(np.arange(M), rare), size=60, replace=False)]))

@@ -90,7 +90,40 @@ constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // until the host had sorted, copied and handed over launch t and come back with launch t + 2 (2,504 x 531,500, all pairs:
 // 39 launches of 13 ms took 1.25 s).  With t + 2 already queued the count kernels run back to back.
 constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
+// The form of a launch, decided once (launch_form) and passed down: which count kernel, which math behind it.
+struct LaunchForm {
+	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
+	bool fused = false;            // the fused count -> screen kernel: no count matrix, C holds the candidate list
+	bool unphased = false;         // plain unphased planes with UnphasedMath: the list math, if there is one, is the unphased kernel
+	bool three = false;            // the three-product form (HH + S; the candidates' four products are recounted): fused, or ...
+	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
+	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
+	bool score = false;            // the score epilogue in place of math, Fisher and records (ld_score.hip.h): always through a matrix
+};
+// What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
+// function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
+struct Launch {
+	LaunchForm form;
+	bool is_list = false;                         // a carrier-list pass (ld_list.hip.h): C holds its candidate list
+	bool is_probe = false;                        // ... of the probe kind (zone rows x columns outside the zone)
+	// a band launch (region_impl): its pair math is enqueued once its candidate count is known (enqueue_band_math)
+	bool deferred = false;
+	bool was_deferred = false;                    // (the launch was one: its math runs between ev_c0b and ev_s1, not right behind the count kernel)
+	const ScreenWork* d_screen_dev = nullptr;     // the parameter blocks of a fused or three-product launch on the device (behind the launch's unit table)
+	StatsParams* d_stats_dev = nullptr;
+	StatsParams stats_host;                       // ... and the host's copy of the second, patched with the survivor buffer before it is sent again
+	bool presorted = false;                       // band launches: the survivors are in Slot::sorted, sorted on the compute stream right behind Fisher's test (close_launch)
+	uint32_t* cand = nullptr;                     // the candidate list of the launch (in C)
+	unsigned long long cand_cap = 0;              // ... of this many entries; n_out[2] counts them
+	bool cand_overflow = false;                   // set by finish_tile: the list did not hold them all
+	bool band_too_big = false;                    // a band launch whose candidates need more survivor / sort buffers than it may have (or could get): finish_tile reports
+	                                              // it as an overflow and the launch's rows are redone as matrix-sized tiles
+	int plane_set = 0;                            // the plane set the launch contracted
+	double minP = 1.0;
+	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
+};
 struct Slot {                      // one in-flight tile (double buffered)
+	Launch l;
 	uint32_t* C = nullptr; size_t C_words = 0;
 	twk_hip_record* out = nullptr; unsigned long long capacity = 0;      // survivor buffer and its size (grow-only)
 	unsigned long long* keys = nullptr; uint32_t* vals = nullptr;        // [capacity]: sort key and position of every survivor, written where it is appended
@@ -101,27 +134,7 @@ struct Slot {                      // one in-flight tile (double buffered)
 	                                              // tick at which the last block on XCD x finished
 	unsigned long long* h_n_out = nullptr;        // pinned host copy of all of them
 	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr, ev_s1 = nullptr, ev_c0b = nullptr, ev_c1b = nullptr;
-	bool two_pass = false;
-	bool is_list = false;                         // the launch was a carrier-list pass (ld_list.hip.h): C holds its candidate list
-	bool is_probe = false;                        // ... of the probe kind (zone rows x columns outside the zone)
-	// a band launch (region_impl): its pair math is enqueued once its candidate count is known (enqueue_band_math)
-	bool deferred = false; bool deferred_unphased = false;
-	bool was_deferred = false;                    // (this slot's launch was one: its math runs between ev_c0b and ev_s1, not right behind the count kernel)
-	StatsParams* d_stats_dev = nullptr;           // the math kernel's parameter block on the device (behind the launch's tile list)
-	StatsParams stats_host;                       // ... and the host's copy, patched with the survivor buffer before it is sent again
-	twk_hip_record* sorted = nullptr; unsigned long long sorted_cap = 0;      // band launches: the survivors in (idxA, idxB) order, sorted on the
-	bool presorted = false;                                                   // compute stream right behind Fisher's test (enqueue_band_math)
-	bool fused = false;                           // first launch ran the fused count -> screen kernel: C holds the candidate list
-	bool three = false;                           // ... in the three-product form (HH + S; the candidates' four products are recounted): fused, or
-	bool three_plain = false;                     // through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
-	uint32_t* cand = nullptr;                     // the candidate list of the launch (in C)
-	int plane_set = 0;                            // the plane set the launch contracted
-	unsigned long long cand_cap = 0;              // ... of this many entries; n_out[2] counts them
-	bool cand_overflow = false;                   // set by finish_tile: the list did not hold them all
-	bool band_too_big = false;                    // a band launch whose candidates need more survivor / sort buffers than it may have (or could get): finish_tile reports
-	                                              // it as an overflow and the launch's rows are redone as matrix-sized tiles
-	double minP = 1.0;
-	uint64_t row_pairs = 0, row_pairs_b = 0;
+	twk_hip_record* sorted = nullptr; unsigned long long sorted_cap = 0;      // band launches: the survivors in (idxA, idxB) order (Launch::presorted)
 	// work lists of the (up to two) count launches of the tile: pinned host copy + device copy
 	uint32_t* h_tiles[2] = {nullptr, nullptr}; uint32_t* d_tiles[2] = {nullptr, nullptr}; size_t tiles_cap[2] = {0, 0};
 	// score launches (ld_score.hip.h): the blocks' row and column partials of the launch (grow-only)
@@ -134,6 +147,10 @@ struct ColRange { const uint32_t* lo = nullptr; const uint32_t* hi = nullptr; ui
                   const uint32_t* d_hi = nullptr; uint32_t n_hi = 0;      // d_hi: device copy of hi, n_hi entries (r2 screen: the math kernel skips what was not contracted)
                   uint32_t list_zone = 0;              // pairs with both set positions below it are intersected as carrier lists (ld_list.hip.h), not contracted
                   uint32_t probe_zone = 0; };          // <= list_zone: every other pair of a row below it is decided by probing the column's row with the row's carriers (k_probe_screen)
+
+// Where a finished launch's sorted survivors go (finish_tile): appended to the device sink (!to_host), or to the host - left whole in
+// c->h_recs (sink == null: the single-tile entry point), or handed to `sink`.
+struct Deliver { bool to_host = true; twk_hip_record_sink sink = nullptr; void* user = nullptr; };
 
 }  // namespace
 
@@ -269,19 +286,16 @@ namespace {
 		}                                                                                         \
 	} while (0)
 
+void free_plane_set(PlaneSet& p) {
+	if (p.owns_rows && p.rows) (void)hipFree(p.rows);
+	void* ptrs[] = {p.rowpop, p.ids, p.lists, p.list_mac, p.list_flip, p.terms};
+	for (void* q : ptrs) if (q) (void)hipFree(q);
+	p = PlaneSet();
+}
 void free_planes(twk_hip_ctx* c) {
 	c->h_popc.clear();
 	c->sorted_keeps_no_lists[0] = c->sorted_keeps_no_lists[1] = false;
-	for (auto& p : c->planes) {
-		if (p.owns_rows && p.rows) (void)hipFree(p.rows);
-		if (p.rowpop) (void)hipFree(p.rowpop);
-		if (p.ids) (void)hipFree(p.ids);
-		if (p.lists) (void)hipFree(p.lists);
-		if (p.list_mac) (void)hipFree(p.list_mac);
-		if (p.list_flip) (void)hipFree(p.list_flip);
-		if (p.terms) (void)hipFree(p.terms);
-		p = PlaneSet();
-	}
+	for (auto& p : c->planes) free_plane_set(p);
 }
 void free_slots(twk_hip_ctx* c) {
 	for (auto& s : c->slot) {
@@ -569,19 +583,18 @@ void build_tile_list(const twk_hip_tile_desc& t, int P, const Geometry& g, bool 
 	out.swap(seq);
 }
 
-// Launch the count kernel for one tile on the compute stream (which: first or second launch of the slot).
-// screen != null: the fused form (k_count_screen_t) if the launch qualifies - rows short enough that no tile's K range
-// is split (or TWK_HIP_FUSED=2: never split) - in which case *fused is set and the slot's C buffer holds the candidate
-// list instead of counts.
-// The two parameter blocks of a fused launch travel to the device behind the tile list and the unit table (one copy
-// per launch as before): the kernels read them from memory where they need them instead of holding ~60 more scalar
-// registers through the contraction loop / the candidate loop.
-// three: the three-product form (fa->unphased) - fused where the launch fuses, else k_count3_list_t into an (HH, S) matrix; the parameter
-// blocks travel in both cases (*d_screen / *d_stats: where they landed).
+// Launch the count kernel for one tile on the compute stream (which: first or second launch of the slot - its event pair, ev_c0 / ev_c1
+// or ev_c0b / ev_c1b, and its row_pairs field follow from it).
+// form.fused: the fused kernels (k_count_screen_t) - no tile's K range is split, and the slot's C buffer holds the candidate list
+// instead of counts.  form.three: the three-product form - fused, or k_count3_list_t into an (HH, S) matrix.
+// The two parameter blocks of a fused or three-product launch (fa) travel to the device behind the tile list and the unit table (one
+// copy per launch): the kernels read them from memory where they need them instead of holding ~60 more scalar registers through the
+// contraction loop / the candidate loop.  Where they landed: Launch::d_screen_dev / d_stats_dev (null: no tiles, nothing was launched).
 struct FusedArgs { ScreenWork screen; StatsParams stats; int unphased; };
-int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, hipEvent_t e0, hipEvent_t e1,
-                 uint64_t* row_pairs, const ColRange* cr = nullptr, const FusedArgs* fa = nullptr, bool* fused = nullptr,
-                 const StatsParams** d_stats = nullptr, bool three = false, const ScreenWork** d_screen = nullptr) {
+int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, const ColRange* cr, const LaunchForm& form, const FusedArgs* fa) {
+	const hipEvent_t e0 = which ? s.ev_c0b : s.ev_c0, e1 = which ? s.ev_c1b : s.ev_c1;
+	const bool fuse = form.fused, three = form.three, with_args = fuse || three;       // with_args: the parameter blocks go to the device behind the unit table
+	if (with_args != (fa != nullptr)) return TWK_HIP_E_STATE;
 	const PlaneSet& ps = c->planes[set];
 	const int P = planes_per_variant(set_kind(set));
 	const Geometry g = tile_geometry(P, t);
@@ -595,14 +608,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	// units of work: see build_count_units (ld_count.hip.h)
 	const uint32_t nchunks = ps.W / KC;
 	uint32_t min_chunks = (uint32_t)c->opt.count_min_chunks;      // (test hook: 1 splits short rows too)
-	bool fuse = false;
-	if (fa) {
-		const int fused_env = (int)c->opt.fused;      // 0: never; 1 (default): rows of <= FUSED_MAX_CHUNKS chunks; 2: always (test hook)
-		fuse = fused_env == 2 || (fused_env == 1 && nchunks <= FUSED_MAX_CHUNKS);
-		if (fuse) min_chunks = nchunks + 1;          // whole tiles only: a block must hold a pair's whole count to screen it
-	}
-	if (fused) *fused = fuse;
-	const bool with_args = fuse || (three && fa);       // the parameter blocks go to the device behind the unit table
+	if (fuse) min_chunks = nchunks + 1;              // whole tiles only: a block must hold a pair's whole count to screen it
 	std::vector<CountUnit> units;
 	uint32_t seg_chunks = (uint32_t)c->opt.seg;    // 0: whole tiles (see build_tile_list for the measurement behind that)
 	if (fuse) seg_chunks = 0;
@@ -673,19 +679,21 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 			HIPCHK(c, hipGetLastError());
 		}
 		const FusedArgs* d_fa = reinterpret_cast<const FusedArgs*>(s.d_tiles[which] + words_units);
-		if (with_args && d_stats) *d_stats = &d_fa->stats;
-		if (with_args && d_screen) *d_screen = &d_fa->screen;
-		if (fuse && fa->unphased && three && c->sampling) hipLaunchKernelGGL((k_count3_screen_unphased_t<COUNT_NW, 1>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w, &d_fa->screen);
-		else if (fuse && fa->unphased && three) hipLaunchKernelGGL((k_count3_screen_unphased_t<COUNT_NW>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w, &d_fa->screen);
-		else if (three && c->sampling) hipLaunchKernelGGL((k_count3_list_t<COUNT_NW, 1>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w);
-		else if (three) hipLaunchKernelGGL((k_count3_list_t<COUNT_NW>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w);
-		else if (fuse && fa->unphased) hipLaunchKernelGGL((k_count_screen_unphased_t<COUNT_NW>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w, &d_fa->screen);
-		else if (fuse) hipLaunchKernelGGL((k_count_screen_t<COUNT_NW>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w, &d_fa->screen);
-		else hipLaunchKernelGGL((k_count_list_t<COUNT_NW>), dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w);
+		if (with_args) { s.l.d_stats_dev = const_cast<StatsParams*>(&d_fa->stats); s.l.d_screen_dev = &d_fa->screen; }
+		// one kernel: into the candidate list (fused) or into a matrix; a density sample's runs under a name of its own (twk_hip_ctx::sampling)
+		void (*k_list)(CountWork, const ScreenWork*) = nullptr;
+		void (*k_matrix)(CountWork) = nullptr;
+		if (fuse && three) k_list = c->sampling ? k_count3_screen_unphased_t<COUNT_NW, 1> : k_count3_screen_unphased_t<COUNT_NW>;
+		else if (three) k_matrix = c->sampling ? k_count3_list_t<COUNT_NW, 1> : k_count3_list_t<COUNT_NW>;
+		else if (fuse) k_list = form.unphased ? k_count_screen_unphased_t<COUNT_NW> : k_count_screen_t<COUNT_NW>;
+		else k_matrix = k_count_list_t<COUNT_NW>;
+		const dim3 grid(std::min(n_blocks, w.n_units)), block(COUNT_THREADS);
+		if (k_list) hipLaunchKernelGGL(k_list, grid, block, 0, c->s_compute, w, &d_fa->screen);
+		else hipLaunchKernelGGL(k_matrix, grid, block, 0, c->s_compute, w);
 		HIPCHK(c, hipGetLastError());
 	}
 	HIPCHK(c, hipEventRecord(e1, c->s_compute));
-	*row_pairs = (uint64_t)T * TILE * TILE;
+	(which ? s.l.row_pairs_b : s.l.row_pairs) = (uint64_t)T * TILE * TILE;
 	return TWK_HIP_OK;
 }
 
@@ -720,7 +728,6 @@ uint64_t pairs_in_tile(const twk_hip_ctx* c, const twk_hip_tile_desc& t) {
 	return nA * nB;
 }
 
-// Enqueue everything for one tile into slot s (count [+ second pass], math, counter copy).
 // What a mode runs on a tile: one or two (plane set, math, pair selection) passes.
 struct TilePlan { int set1, set2; bool phased1; int select1; int Pmax; };
 TilePlan plan_for(const twk_hip_ctx* c, int mode) {
@@ -770,16 +777,29 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 	return TWK_HIP_OK;
 }
 
-// Would a launch of this mode run the fused count -> screen form (and nothing else: one pass)?  The same tests as
-// enqueue_tile / launch_count make, for the callers that size a launch by it.
-bool fused_form_applies(twk_hip_ctx* c, int mode, const twk_hip_filters& f) {
-	const TilePlan pl = plan_for(c, mode);
-	if (pl.set2 >= 0 || !c->fused_ok || c->opt.fused == 0) return false;
+// The form of the (first) launch of a tile of this plan, as the context stands: the one place that reads the options "fused" and "three",
+// FUSED_MAX_CHUNKS, fused_ok, three_ok and score_on for it.
+// A screen in front of the math needs plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
+// pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short
+// enough that no tile's K range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h)
+// on unphased planes.  Row lengths are read last, from planes built here if need be (a set that cannot be built: no screen; enqueue_tile
+// reports why).
+LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
+	LaunchForm lf;
+	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.keep_three = c->opt.three == 2;
 	const int k = set_kind(pl.set1);
-	if (!((pl.phased1 && k == PK_PHASED) || (!pl.phased1 && k == PK_UNPHASED))) return false;
-	if (!(f.minR2 > 1e-6 && f.minR2 <= 1.0)) return false;
-	if (ensure_planes(c, pl.set1) != TWK_HIP_OK) return false;
-	return c->opt.fused == 2 || c->planes[pl.set1].W / KC <= FUSED_MAX_CHUNKS;
+	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
+	const bool screen = !lf.score && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
+	if (!screen) return lf;
+	lf.three = lf.unphased && c->three_ok && c->opt.three != 0;
+	if (c->opt.fused == 0 || ensure_planes(c, pl.set1) != TWK_HIP_OK) return lf;
+	lf.fused = c->opt.fused == 2 || c->planes[pl.set1].W / KC <= FUSED_MAX_CHUNKS;
+	return lf;
+}
+// Would a launch of this mode run the fused count -> screen form and nothing else (one pass)?  For the callers that size a launch by it.
+bool fused_form_applies(twk_hip_ctx* c, int mode, const twk_hip_filters& f) {
+	const LaunchForm lf = launch_form(c, plan_for(c, mode), f);
+	return lf.fused && !lf.two_pass;
 }
 
 // The four products of the candidates of a three-product launch (k_recount_unphased), on the compute stream: a wave per candidate for
@@ -788,11 +808,11 @@ bool fused_form_applies(twk_hip_ctx* c, int mode, const twk_hip_filters& f) {
 int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	const PlaneSet& ps = c->planes[set];
 	if (ps.W_live <= 1024)
-		hipLaunchKernelGGL(k_recount_unphased<16>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.cand_cap, s.n_out + 3);
+		hipLaunchKernelGGL(k_recount_unphased<16>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3);
 	else
-		hipLaunchKernelGGL(k_recount_unphased<64>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.cand_cap, s.n_out + 3);
+		hipLaunchKernelGGL(k_recount_unphased<64>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3);
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -831,133 +851,6 @@ int launch_score(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	return TWK_HIP_OK;
 }
 
-// list_words != 0: a band launch (region_impl) - the fused form with a candidate list of that many words and no count
-// matrix at all (its rectangle may be far beyond what a matrix could hold); it is an error if the launch does not fuse.
-int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, Slot& s,
-                 unsigned long long capacity, const ColRange* cr = nullptr, size_t list_words = 0) {
-	const TilePlan pl = plan_for(c, mode);
-	const bool two_pass = pl.set2 >= 0;
-	const bool phased = pl.phased1;
-	const int kind1 = pl.set1, kind2 = pl.set2;
-	int rc = ensure_planes(c, kind1); if (rc) return rc;
-	if (two_pass) { rc = ensure_planes(c, kind2); if (rc) return rc; }
-	const Geometry g = tile_geometry(pl.Pmax, t);
-	if (c->score_on) { if (list_words) return TWK_HIP_E_STATE; capacity = 1; }      // a score launch keeps no survivors: always the matrix form
-	if (list_words && !fused_form_applies(c, mode, f)) return TWK_HIP_E_STATE;
-	const auto tl0 = std::chrono::steady_clock::now();
-	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
-	rc = ensure_slot(c, s, list_words ? list_words : (size_t)g.rowsA * g.rowsB, capacity); if (rc) return rc;
-	tl("slot buffers");
-	s.two_pass = two_pass;
-
-	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
-	// The fused form: plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
-	// pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.
-	const bool fused_u = !phased && set_kind(kind1) == PK_UNPHASED;
-	const bool want_fused = !c->score_on && c->fused_ok && ((phased && set_kind(kind1) == PK_PHASED) || fused_u) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
-	FusedArgs fa{};
-	fa.unphased = fused_u ? 1 : 0;
-	ScreenWork& sw = fa.screen;
-	s.fused = false; s.is_list = false; s.is_probe = false; s.cand_overflow = false; s.cand_cap = (list_words ? list_words : s.C_words) / (fused_u ? 6 : 3);
-	s.three = false; s.three_plain = false; s.cand = s.C; s.band_too_big = false;
-	// The three-product form (ld_count.hip.h): UnphasedMath on the plain unphased planes with a cut-off the screen can use.  Where the launch
-	// does not fuse (long rows: tiles are split along K) the (HH, S) matrix takes the first half of the slot's count buffer and the candidate
-	// list the room behind it - at most 1/128 of the tile's pairs: a candidate's recount streams its four rows once more, ~25 pairs' worth of
-	// contraction, so a launch with more candidates than that is cheaper in the four-product form (overflow -> three_ok = false -> redone).
-	const bool want_three = want_fused && fused_u && c->three_ok && c->opt.three != 0;
-	const bool fuses = want_fused && (c->opt.fused == 2 || (c->opt.fused == 1 && c->planes[kind1].W / KC <= FUSED_MAX_CHUNKS));      // (launch_count's own test)
-	if (want_three && !fuses) {
-		const size_t c2_words = (size_t)(g.rowsA / 2) * g.rowsB;
-		const unsigned long long room = s.C_words > c2_words ? (s.C_words - c2_words) / 6 : 0;
-		const unsigned long long pairs = (unsigned long long)t.nA * t.nB;
-		s.cand = s.C + c2_words;
-		s.cand_cap = std::min<unsigned long long>(room, c->opt.three == 2 ? room : std::max<unsigned long long>(pairs / 128, 4096));
-	}
-	if (want_fused) {
-		PlaneSet& ps = c->planes[kind1];
-		sw.cut = f.minR2 * (1.0 - 1e-6); sw.two_n = 2.0 * (double)c->N;
-		if (fuses && (!ps.terms || ps.terms_cut != sw.cut)) {      // the prefilter's per-variant terms: once per plane set and cut-off, on the stream the kernels follow
-			const uint32_t P1 = (uint32_t)planes_per_variant(set_kind(kind1)), n_pos = ps.rows_alloc / P1;
-			if (!ps.terms) HIPCHK(c, hipMalloc((void**)&ps.terms, (size_t)n_pos * sizeof(float4)));
-			hipLaunchKernelGGL(k_screen_terms, dim3((n_pos + 255) / 256), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rowpop, n_pos, (int)P1, sw.two_n, sw.cut, ps.terms);
-			HIPCHK(c, hipGetLastError());
-			ps.terms_cut = sw.cut;
-		}
-		sw.terms = ps.terms; sw.slack = 0.5f + (float)sw.two_n * (1.0f / 1048576.0f);
-		fa.stats = make_stats(c, kind1, t, s, phased, pl.select1, f, cr);
-		sw.rowpop = ps.rowpop; sw.a0 = t.rowA0; sw.b0 = t.rowB0; sw.nA = t.nA; sw.nB = t.nB;
-		sw.n_variants = c->M; sw.diag = (t.diag && t.rowA0 == t.rowB0) ? 1 : 0;
-		sw.col_hi = cr ? cr->d_hi : nullptr; sw.hi_a0 = cr ? cr->a0 : 0; sw.hi_b0 = cr ? cr->b0 : 0; sw.hi_n = cr ? cr->n_hi : 0;
-		sw.list_zone = cr ? cr->list_zone : 0; sw.probe_zone = cr ? cr->probe_zone : 0;
-		sw.two_n = 2.0 * (double)c->N; sw.cut = f.minR2 * (1.0 - 1e-6);
-		sw.cand = s.cand; sw.cap = s.cand_cap; sw.n_cand = s.n_out + 2;
-		{	// slots a wave reserves at a time: what it cannot use is lost to the list, so at most an eighth of the list's
-			// capacity may be tied up in the waves' windows (small tiles: 0, i.e. one atomic per wave and tile)
-			const unsigned long long per_wave = s.cand_cap / (8ull * c->resident_blocks * (COUNT_THREADS / 64));
-			sw.chunk = c->opt.cand_chunk >= 0 ? (uint32_t)c->opt.cand_chunk      // measurement hook
-			                                  : (per_wave >= 64 ? (uint32_t)std::min<unsigned long long>(per_wave, 128) : 0u);
-		}
-	}
-	const StatsParams* d_stats = nullptr; const ScreenWork* d_screen = nullptr;
-	s.deferred = false; s.was_deferred = false; s.presorted = false;
-	rc = launch_count(c, kind1, t, s, 0, s.ev_c0, s.ev_c1, &s.row_pairs, cr, want_fused ? &fa : nullptr, &s.fused, &d_stats, want_three, &d_screen); if (rc) return rc;
-	s.three = want_three; s.three_plain = want_three && !s.fused; s.plane_set = kind1;
-	tl("count kernel enqueued");
-	if (list_words) {
-		// A band launch stops here for now: how many survivors it can have is how many candidates it found, and only the count
-		// kernel knows.  The counters travel to the host behind it; enqueue_band_math sizes the survivor buffer by them and
-		// enqueues the rest (sizing it by a guess - 1/32 of the launch's pairs - meant gigabytes of allocation per slot, a
-		// tenth of a second each, for launches that then kept a few thousand records).
-		if (!s.fused) return TWK_HIP_E_STATE;
-		s.deferred = true; s.was_deferred = true; s.deferred_unphased = fused_u; s.d_stats_dev = const_cast<StatsParams*>(d_stats); s.stats_host = fa.stats; s.minP = f.minP;
-		HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
-		HIPCHK(c, hipEventRecord(s.ev_c1b, c->s_compute));
-		return TWK_HIP_OK;
-	}
-	if (s.three_plain && d_stats) {
-		// (HH, S) matrix -> screen -> candidates -> their four products -> the list math
-		hipLaunchKernelGGL(k_screen3_pairs, dim3((t.nB + SCREEN3_THREADS - 1) / SCREEN3_THREADS, t.nA), dim3(SCREEN3_THREADS), 0, c->s_compute, d_screen, d_stats, (const uint32_t*)s.C, g.ldc);
-		HIPCHK(c, hipGetLastError());
-		rc = launch_recount(c, kind1, s); if (rc) return rc;
-		hipLaunchKernelGGL(k_ld_stats_list_unphased, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, d_stats, (const uint32_t*)s.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-	} else if (s.three_plain) {
-		// (no tiles, no launch, no candidates)
-	} else if (s.fused) {
-		if (d_stats && s.three) { rc = launch_recount(c, kind1, s); if (rc) return rc; }
-		if (d_stats && fused_u)
-			hipLaunchKernelGGL(k_ld_stats_list_unphased, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, d_stats, (const uint32_t*)s.C,
-			                   (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		else if (d_stats)     // (no tiles, no launch, no candidates)
-			hipLaunchKernelGGL(k_ld_stats_list, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, d_stats, (const uint32_t*)s.C,
-			                   (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-	} else if (c->score_on) {
-		rc = launch_score(c, kind1, t, s, 0, phased, pl.select1, f, cr); if (rc) return rc;
-	} else {
-		const StatsParams p = make_stats(c, kind1, t, s, phased, pl.select1, f, cr);
-		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
-	}
-	HIPCHK(c, hipGetLastError());
-	if (two_pass) {
-		rc = launch_count(c, kind2, t, s, 1, s.ev_c0b, s.ev_c1b, &s.row_pairs_b, cr); if (rc) return rc;
-		if (c->score_on) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
-		else {
-			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
-			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
-		}
-		HIPCHK(c, hipGetLastError());
-	}
-	// Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is free by now - the math
-	// kernels in front are done with it - and holds the walk-length order)
-	// (a score launch has none, and no test to run: minP >= 1 drops nothing)
-	if (!c->score_on) { rc = launch_fisher(c, s.out, s.n_out, s.cap_use, f.minP, s.C, s.C_words, s.keys); if (rc) return rc; }
-	HIPCHK(c, hipGetLastError());
-	s.minP = f.minP;
-	HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
-	HIPCHK(c, hipEventRecord(s.ev_s1, c->s_compute));
-	return TWK_HIP_OK;
-}
-
 // Survivors are appended with an atomic counter, in no order.  They leave the device in (idxA, idxB) order
 // - the order the writer puts them in the file, which makes a one-GPU run's output deterministic - by a key
 // sort of (idxA << bits | idxB, position) and a gather.  Key and position are written by the math kernels where the
@@ -984,24 +877,160 @@ int regrow(twk_hip_ctx* c, void** p, unsigned long long* cap, unsigned long long
 	return TWK_HIP_OK;
 }
 
+// Every launch of a slot begins here: what the previous one left in the slot's per-launch state cannot reach it.
+Launch& begin_launch(Slot& s, int plane_set, double minP) {
+	s.l = Launch();
+	s.l.plane_set = plane_set; s.l.minP = minP;
+	return s.l;
+}
+
+// The list math over the launch's candidate list (phased or unphased by its form), with the parameter block at d_stats.
+int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
+	hipLaunchKernelGGL(s.l.form.unphased ? k_ld_stats_list_unphased : k_ld_stats_list, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, d_stats,
+	                   (const uint32_t*)s.l.cand, (const unsigned long long*)(s.n_out + 2), s.l.cand_cap);
+	HIPCHK(c, hipGetLastError());
+	return TWK_HIP_OK;
+}
+
+// The end of every launch, on the compute stream: Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is
+// free by now - the math kernels in front are done with it - and holds the walk-length order; a score launch has no survivors, and no
+// test to run: minP >= 1 drops nothing), for a band launch the sort of its survivors (Launch::presorted), the counters' copy to the host
+// and ev_s1.
+// The band launch's sort is over as many slots as there were candidates (unused slots carry the all-ones key, like records the Fisher
+// cut-off drops: they sort behind the survivors): it does not need the survivor count, so it need not wait for the host - on the copy
+// stream (finish_tile's sort_records) it waited for a CU until the *next* launch's persistent count kernel was through, 60 ms per launch
+// of the 2,504 x 531,500 run.
+int close_launch(twk_hip_ctx* c, Slot& s) {
+	if (!s.l.form.score) { const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, s.l.minP, s.C, s.C_words, s.keys); if (rc) return rc; }
+	if (s.l.presorted) {
+		const unsigned long long need = s.cap_use;
+		size_t bytes = c->band_tmp_bytes;
+		HIPCHK(c, rocprim::radix_sort_pairs(c->d_band_tmp, bytes, s.keys, c->d_band_keys, s.vals, c->d_band_vals, (size_t)need, 0u, 64u, c->s_compute));
+		const unsigned long long words = need * (sizeof(twk_hip_record) / 8);
+		hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, (const twk_hip_record*)s.out, (const uint32_t*)c->d_band_vals, need, s.sorted);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
+	HIPCHK(c, hipEventRecord(s.ev_s1, c->s_compute));
+	return TWK_HIP_OK;
+}
+
+// Enqueue everything for one tile into slot s (count [+ second pass], math, counter copy).
+// list_words != 0: a band launch (region_impl) - the fused form with a candidate list of that many words and no count
+// matrix at all (its rectangle may be far beyond what a matrix could hold); it is an error if the launch does not fuse.
+int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, Slot& s,
+                 unsigned long long capacity, const ColRange* cr = nullptr, size_t list_words = 0) {
+	const TilePlan pl = plan_for(c, mode);
+	const int kind1 = pl.set1, kind2 = pl.set2;
+	int rc = ensure_planes(c, kind1); if (rc) return rc;
+	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
+	const LaunchForm form = launch_form(c, pl, f);
+	const Geometry g = tile_geometry(pl.Pmax, t);
+	if (form.score) capacity = 1;                  // a score launch keeps no survivors (and is never a band launch: always the matrix form)
+	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
+	const auto tl0 = std::chrono::steady_clock::now();
+	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
+	rc = ensure_slot(c, s, list_words ? list_words : (size_t)g.rowsA * g.rowsB, capacity); if (rc) return rc;
+	tl("slot buffers");
+	Launch& l = begin_launch(s, kind1, f.minP);
+	l.form = form;
+	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
+	l.cand = s.C; l.cand_cap = (list_words ? list_words : s.C_words) / (form.unphased ? 6 : 3);
+	// The three-product form where the launch does not fuse (long rows: tiles are split along K): the (HH, S) matrix takes the first half of the
+	// slot's count buffer and the candidate list the room behind it - at most 1/128 of the tile's pairs: a candidate's recount streams its four
+	// rows once more, ~25 pairs' worth of contraction, so a launch with more candidates than that is cheaper in the four-product form
+	// (overflow -> three_ok = false -> redone).
+	if (form.three_plain()) {
+		const size_t c2_words = (size_t)(g.rowsA / 2) * g.rowsB;
+		const unsigned long long room = s.C_words > c2_words ? (s.C_words - c2_words) / 6 : 0;
+		const unsigned long long pairs = (unsigned long long)t.nA * t.nB;
+		l.cand = s.C + c2_words;
+		l.cand_cap = std::min<unsigned long long>(room, form.keep_three ? room : std::max<unsigned long long>(pairs / 128, 4096));
+	}
+	FusedArgs fa{};
+	const bool with_args = form.fused || form.three;      // the launch carries the screen's and the list math's parameter blocks
+	if (with_args) {
+		PlaneSet& ps = c->planes[kind1];
+		fa.unphased = form.unphased ? 1 : 0;
+		ScreenWork& sw = fa.screen;
+		sw.cut = f.minR2 * (1.0 - 1e-6); sw.two_n = 2.0 * (double)c->N;
+		if (form.fused && (!ps.terms || ps.terms_cut != sw.cut)) {      // the prefilter's per-variant terms: once per plane set and cut-off, on the stream the kernels follow
+			const uint32_t P1 = (uint32_t)planes_per_variant(set_kind(kind1)), n_pos = ps.rows_alloc / P1;
+			if (!ps.terms) HIPCHK(c, hipMalloc((void**)&ps.terms, (size_t)n_pos * sizeof(float4)));
+			hipLaunchKernelGGL(k_screen_terms, dim3((n_pos + 255) / 256), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rowpop, n_pos, (int)P1, sw.two_n, sw.cut, ps.terms);
+			HIPCHK(c, hipGetLastError());
+			ps.terms_cut = sw.cut;
+		}
+		sw.terms = ps.terms; sw.slack = 0.5f + (float)sw.two_n * (1.0f / 1048576.0f);
+		fa.stats = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
+		sw.rowpop = ps.rowpop; sw.a0 = t.rowA0; sw.b0 = t.rowB0; sw.nA = t.nA; sw.nB = t.nB;
+		sw.n_variants = c->M; sw.diag = (t.diag && t.rowA0 == t.rowB0) ? 1 : 0;
+		sw.col_hi = cr ? cr->d_hi : nullptr; sw.hi_a0 = cr ? cr->a0 : 0; sw.hi_b0 = cr ? cr->b0 : 0; sw.hi_n = cr ? cr->n_hi : 0;
+		sw.list_zone = cr ? cr->list_zone : 0; sw.probe_zone = cr ? cr->probe_zone : 0;
+		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2;
+		{	// slots a wave reserves at a time: what it cannot use is lost to the list, so at most an eighth of the list's
+			// capacity may be tied up in the waves' windows (small tiles: 0, i.e. one atomic per wave and tile)
+			const unsigned long long per_wave = l.cand_cap / (8ull * c->resident_blocks * (COUNT_THREADS / 64));
+			sw.chunk = c->opt.cand_chunk >= 0 ? (uint32_t)c->opt.cand_chunk      // measurement hook
+			                                  : (per_wave >= 64 ? (uint32_t)std::min<unsigned long long>(per_wave, 128) : 0u);
+		}
+	}
+	rc = launch_count(c, kind1, t, s, 0, cr, form, with_args ? &fa : nullptr); if (rc) return rc;
+	tl("count kernel enqueued");
+	if (list_words) {
+		// A band launch stops here for now: how many survivors it can have is how many candidates it found, and only the count
+		// kernel knows.  The counters travel to the host behind it; enqueue_band_math sizes the survivor buffer by them and
+		// enqueues the rest (sizing it by a guess - 1/32 of the launch's pairs - meant gigabytes of allocation per slot, a
+		// tenth of a second each, for launches that then kept a few thousand records).
+		l.deferred = true; l.was_deferred = true; l.stats_host = fa.stats;
+		HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
+		HIPCHK(c, hipEventRecord(s.ev_c1b, c->s_compute));
+		return TWK_HIP_OK;
+	}
+	if (with_args) {
+		if (l.d_stats_dev) {      // (else: no tiles, no launch, no candidates)
+			if (form.three_plain()) {      // (HH, S) matrix -> screen -> candidates -> their four products -> the list math
+				hipLaunchKernelGGL(k_screen3_pairs, dim3((t.nB + SCREEN3_THREADS - 1) / SCREEN3_THREADS, t.nA), dim3(SCREEN3_THREADS), 0, c->s_compute, l.d_screen_dev,
+				                   (const StatsParams*)l.d_stats_dev, (const uint32_t*)s.C, g.ldc);
+				HIPCHK(c, hipGetLastError());
+			}
+			if (form.three) { rc = launch_recount(c, kind1, s); if (rc) return rc; }
+			rc = launch_list_math(c, s, l.d_stats_dev); if (rc) return rc;
+		}
+	} else if (form.score) {
+		rc = launch_score(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
+	} else {
+		const StatsParams p = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
+		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
+	}
+	HIPCHK(c, hipGetLastError());
+	if (form.two_pass) {
+		rc = launch_count(c, kind2, t, s, 1, cr, LaunchForm(), nullptr); if (rc) return rc;
+		if (form.score) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
+		else {
+			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
+			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
+		}
+		HIPCHK(c, hipGetLastError());
+	}
+	return close_launch(c, s);
+}
+
 // The second half of a band launch (see enqueue_tile): wait for its count kernel, size the survivor buffers by the candidates it
-// found (no pair that was not a candidate can survive), enqueue the list math, Fisher's test, the sort of the survivors and the
-// counters' copy - all on the compute stream.  The sort is over as many slots as there were candidates (unused slots carry the
-// all-ones key, like records the Fisher cut-off drops: they sort behind the survivors): it does not need the survivor count, so it
-// need not wait for the host - on the copy stream (finish_tile's sort_records) it waited for a CU until the *next* launch's
-// persistent count kernel was through, 60 ms per launch of the 2,504 x 531,500 run.
+// found (no pair that was not a candidate can survive), enqueue the list math and the launch's end (close_launch: Fisher's test, the
+// sort of the survivors, the counters' copy) - all on the compute stream.
 int enqueue_band_math(twk_hip_ctx* c, Slot& s) {
-	if (!s.deferred) return TWK_HIP_E_STATE;
-	s.deferred = false;
+	Launch& l = s.l;
+	if (!l.deferred) return TWK_HIP_E_STATE;
+	l.deferred = false;
 	HIPCHK(c, hipEventSynchronize(s.ev_c1b));
 	const unsigned long long cand = s.h_n_out[2];
 	// Every candidate may survive: the survivor, key and sort buffers are sized by the candidates (220 bytes each).  Beyond 2^26 of them -
 	// 15 GB per slot - or when the device cannot give the memory, the launch is treated like one whose list overflowed: its rows are redone
 	// as matrix-sized tiles, which split further on their own overflow (the round-4 code returned E_NOMEM and took the run down).
 	constexpr unsigned long long BAND_MAX_SURVIVORS = 1ull << 26;
-	s.band_too_big = false;
-	bool overflow = cand > s.cand_cap;                       // finish_tile reports it; nothing to compute here
-	if (!overflow && cand > BAND_MAX_SURVIVORS) { s.band_too_big = true; overflow = true; }
+	bool overflow = cand > l.cand_cap;                       // finish_tile reports it; nothing to compute here
+	if (!overflow && cand > BAND_MAX_SURVIVORS) { l.band_too_big = true; overflow = true; }
 	unsigned long long need = overflow ? 1 : std::max<unsigned long long>(cand, 1);
 	if (c->opt.record_cap > 0) need = std::min<unsigned long long>(need, (unsigned long long)c->opt.record_cap);      // (test hook: forces the overflow path)
 	auto grow_all = [&]() -> int {
@@ -1032,7 +1061,7 @@ int enqueue_band_math(twk_hip_ctx* c, Slot& s) {
 		int rc = grow_all();
 		if (rc == TWK_HIP_E_NOMEM && !overflow) {            // no room for this many survivors: the fallback's tiles need far less at a time
 			(void)hipGetLastError();
-			s.band_too_big = true; overflow = true; need = 1;
+			l.band_too_big = true; overflow = true; need = 1;
 			rc = grow_all();
 		}
 		if (rc) return rc;
@@ -1043,32 +1072,15 @@ int enqueue_band_math(twk_hip_ctx* c, Slot& s) {
 		HIPCHK(c, hipMemsetAsync(s.keys, 0xFF, (size_t)need * sizeof(unsigned long long), c->s_compute));
 		HIPCHK(c, hipMemsetAsync(s.vals, 0, (size_t)need * sizeof(uint32_t), c->s_compute));
 	}
-	if (s.d_stats_dev && !overflow) {
-		s.stats_host.out = s.out; s.stats_host.capacity = s.cap_use; s.stats_host.n_out = s.n_out;
-		s.stats_host.keys = s.keys; s.stats_host.vals = s.vals;
-		HIPCHK(c, hipMemcpyAsync(s.d_stats_dev, &s.stats_host, sizeof(StatsParams), hipMemcpyHostToDevice, c->s_compute));
-		if (s.three) { const int rc = launch_recount(c, s.plane_set, s); if (rc) return rc; }
-		if (s.deferred_unphased)
-			hipLaunchKernelGGL(k_ld_stats_list_unphased, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const StatsParams*)s.d_stats_dev, (const uint32_t*)s.C,
-			                   (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		else
-			hipLaunchKernelGGL(k_ld_stats_list, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const StatsParams*)s.d_stats_dev, (const uint32_t*)s.C,
-			                   (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		HIPCHK(c, hipGetLastError());
+	if (l.d_stats_dev && !overflow) {
+		l.stats_host.out = s.out; l.stats_host.capacity = s.cap_use; l.stats_host.n_out = s.n_out;
+		l.stats_host.keys = s.keys; l.stats_host.vals = s.vals;
+		HIPCHK(c, hipMemcpyAsync(l.d_stats_dev, &l.stats_host, sizeof(StatsParams), hipMemcpyHostToDevice, c->s_compute));
+		if (l.form.three) { const int rc = launch_recount(c, l.plane_set, s); if (rc) return rc; }
+		{ const int rc = launch_list_math(c, s, l.d_stats_dev); if (rc) return rc; }
 	}
-	{ const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, s.minP, s.C, s.C_words, s.keys); if (rc) return rc; }
-	s.presorted = false;
-	if (!overflow) {
-		size_t bytes = c->band_tmp_bytes;
-		HIPCHK(c, rocprim::radix_sort_pairs(c->d_band_tmp, bytes, s.keys, c->d_band_keys, s.vals, c->d_band_vals, (size_t)need, 0u, 64u, c->s_compute));
-		const unsigned long long words = need * (sizeof(twk_hip_record) / 8);
-		hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, (const twk_hip_record*)s.out, (const uint32_t*)c->d_band_vals, need, s.sorted);
-		HIPCHK(c, hipGetLastError());
-		s.presorted = true;
-	}
-	HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
-	HIPCHK(c, hipEventRecord(s.ev_s1, c->s_compute));
-	return TWK_HIP_OK;
+	l.presorted = !overflow;
+	return close_launch(c, s);
 }
 
 static_assert(sizeof(twk_hip_record) % 8 == 0, "record gather copies 8-byte words");
@@ -1133,10 +1145,10 @@ int ensure_device_keep(twk_hip_ctx* c, unsigned long long n_more) {
 constexpr size_t LAUNCH_RING = 4096;
 void watch_launch(twk_hip_ctx* c, const Slot& s, float ms, const twk_hip_tile_desc& t) {
 	twk_hip_launch_stat st{};
-	st.ms = ms; st.row_pairs = s.row_pairs; st.candidates = (s.fused || s.three) ? s.h_n_out[2] : 0;
+	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three) ? s.h_n_out[2] : 0;
 	st.shader_mhz = s.h_n_out[5] ? (double)s.h_n_out[4] / (double)s.h_n_out[5] * 100.0 : 0.0;
-	st.words_per_row = c->planes[s.plane_set].W_live;
-	st.kind = s.fused ? (s.three ? 4u : (c->planes[s.plane_set].rows && set_kind(s.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.three_plain ? 1u : 0u);
+	st.words_per_row = c->planes[s.l.plane_set].W_live;
+	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.three_plain() ? 1u : 0u);
 	unsigned long long lo = ~0ull, hi = 0;
 	for (int x = 0; x < 8; ++x) if (s.h_n_out[8 + x]) { lo = std::min(lo, s.h_n_out[8 + x]); hi = std::max(hi, s.h_n_out[8 + x]); }
 	st.xcd_finish_spread_us = hi ? (double)(hi - lo) / 100.0 : 0.0;
@@ -1248,8 +1260,7 @@ bool reclaim_device_memory(twk_hip_ctx* c) {
 // (!to_host), or through the pinned staging buffer to the host - left there whole (sink == null: c->h_recs, for the
 // single-tile entry point), or handed to `sink` in pieces of HOST_CHUNK records, each piece while the next is being copied
 // (a launch may hold tens of millions of survivors: page-locking a buffer for all of them would cost more than the copy).
-int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned long long* n_out, bool to_host = true,
-                twk_hip_record_sink sink = nullptr, void* user = nullptr) {
+int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned long long* n_out, const Deliver& to) {
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
 	HIPCHK(c, hipEventSynchronize(s.ev_s1));
@@ -1260,15 +1271,15 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 	} finish_clock{c, std::chrono::steady_clock::now()};
 	float ms = 0;
 	HIPCHK(c, hipEventElapsedTime(&ms, s.ev_c0, s.ev_c1));
-	if (!s.is_list) watch_launch(c, s, ms, t);
-	if (s.is_list && s.is_probe) { c->timing.probe_ms += ms; c->timing.probe_launches += 1; c->timing.probe_pairs += s.row_pairs; c->timing.candidates += s.h_n_out[2]; }
-	else if (s.is_list) { c->timing.list_ms += ms; c->timing.list_launches += 1; c->timing.list_pairs += s.row_pairs; c->timing.candidates += s.h_n_out[2]; }
-	else { c->timing.count_ms += ms; c->timing.count_launches += 1; c->timing.row_pairs += s.row_pairs;
+	if (!s.l.is_list) watch_launch(c, s, ms, t);
+	if (s.l.is_list && s.l.is_probe) { c->timing.probe_ms += ms; c->timing.probe_launches += 1; c->timing.probe_pairs += s.l.row_pairs; c->timing.candidates += s.h_n_out[2]; }
+	else if (s.l.is_list) { c->timing.list_ms += ms; c->timing.list_launches += 1; c->timing.list_pairs += s.l.row_pairs; c->timing.candidates += s.h_n_out[2]; }
+	else { c->timing.count_ms += ms; c->timing.count_launches += 1; c->timing.row_pairs += s.l.row_pairs;
 	       c->timing.count_shader_cycles += s.h_n_out[4]; c->timing.count_wall_ticks += s.h_n_out[5]; }
-	if (s.fused) { c->timing.fused_launches += 1; c->timing.candidates += s.h_n_out[2]; }
-	if (s.three) {
-		c->timing.three_launches += 1; c->timing.three_row_pairs += s.row_pairs; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.cand_cap);
-		if (s.three_plain) c->timing.candidates += s.h_n_out[2];
+	if (s.l.form.fused) { c->timing.fused_launches += 1; c->timing.candidates += s.h_n_out[2]; }
+	if (s.l.form.three) {
+		c->timing.three_launches += 1; c->timing.three_row_pairs += s.l.row_pairs; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap);
+		if (s.l.form.three_plain()) c->timing.candidates += s.h_n_out[2];
 		if (s.h_n_out[3]) {      // the recount disagrees with the contraction: never to be papered over
 			snprintf(c->err, sizeof(c->err), "three-product contraction: %llu candidates whose (HH, S) differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], t.rowA0, t.nA, t.rowB0, t.nB);
 			return TWK_HIP_E_DEVICE;
@@ -1278,101 +1289,115 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		// 0.16 ns each (four 320-byte rows from L2 per candidate: 8 TB/s) add 9.3 ms to the math; the two meet near 1.2 %.
 		// (against the variant pairs of the tiles the launch contracted - four plane-row pairs each - not the launch's rectangle: a window
 		// launch's rectangle is mostly outside the window)
-		if (c->opt.three != 2 && s.h_n_out[2] > std::max<unsigned long long>(s.row_pairs / 4 / 128, 4096)) c->three_ok = false;
+		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) c->three_ok = false;
 	}
 	float ms_all = 0;
-	if (s.two_pass) {
+	if (s.l.form.two_pass) {
 		HIPCHK(c, hipEventElapsedTime(&ms, s.ev_c0b, s.ev_c1b));
-		c->timing.count_ms += ms; c->timing.count_launches += 1; c->timing.row_pairs += s.row_pairs_b;
+		c->timing.count_ms += ms; c->timing.count_launches += 1; c->timing.row_pairs += s.l.row_pairs_b;
 		float m1 = 0, m2 = 0;
 		HIPCHK(c, hipEventElapsedTime(&m1, s.ev_c1, s.ev_c0b));
 		HIPCHK(c, hipEventElapsedTime(&m2, s.ev_c1b, s.ev_s1));
 		ms_all = m1 + m2; c->timing.stats_launches += 2;
 	} else {
-		HIPCHK(c, hipEventElapsedTime(&ms_all, s.was_deferred ? s.ev_c0b : s.ev_c1, s.ev_s1));
+		HIPCHK(c, hipEventElapsedTime(&ms_all, s.l.was_deferred ? s.ev_c0b : s.ev_c1, s.ev_s1));
 		c->timing.stats_launches += 1;
 	}
 	c->timing.stats_ms += ms_all;
-	if (!s.is_list) c->timing.variant_pairs += pairs_in_tile(c, t);      // (the dense tiles that cover the list zone count its pairs)
+	if (!s.l.is_list) c->timing.variant_pairs += pairs_in_tile(c, t);      // (the dense tiles that cover the list zone count its pairs)
 	const unsigned long long n = *s.h_n_out;
 	*n_out = n;
-	if (s.was_deferred && s.band_too_big) {          // (enqueue_band_math: more candidates than a band launch may keep survivors for)
+	if (s.l.was_deferred && s.l.band_too_big) {          // (enqueue_band_math: more candidates than a band launch may keep survivors for)
 		snprintf(c->err, sizeof(c->err), "%llu candidates: beyond the survivor buffers of a band launch (tile rows %u+%u, cols %u+%u)", s.h_n_out[2], t.rowA0, t.nA, t.rowB0, t.nB);
 		return TWK_HIP_E_OVERFLOW;
 	}
-	if ((s.fused || s.is_list || s.three_plain) && s.h_n_out[2] > s.cand_cap) {       // more candidates than the list holds
-		s.cand_overflow = true;
-		snprintf(c->err, sizeof(c->err), "%llu candidates for a list of %llu (tile rows %u+%u, cols %u+%u)", s.h_n_out[2], s.cand_cap, t.rowA0, t.nA, t.rowB0, t.nB);
+	if ((s.l.form.fused || s.l.is_list || s.l.form.three_plain()) && s.h_n_out[2] > s.l.cand_cap) {       // more candidates than the list holds
+		s.l.cand_overflow = true;
+		snprintf(c->err, sizeof(c->err), "%llu candidates for a list of %llu (tile rows %u+%u, cols %u+%u)", s.h_n_out[2], s.l.cand_cap, t.rowA0, t.nA, t.rowB0, t.nB);
 		return TWK_HIP_E_OVERFLOW;
 	}
 	if (n > s.cap_use) {
-		snprintf(c->err, sizeof(c->err), "%llu survivors for a buffer of %llu (tile rows %u+%u, cols %u+%u%s)", n, s.cap_use, t.rowA0, t.nA, t.rowB0, t.nB, s.is_list ? ", list pass" : "");
+		snprintf(c->err, sizeof(c->err), "%llu survivors for a buffer of %llu (tile rows %u+%u, cols %u+%u%s)", n, s.cap_use, t.rowA0, t.nA, t.rowB0, t.nB, s.l.is_list ? ", list pass" : "");
 		return TWK_HIP_E_OVERFLOW;
 	}
 	if (!n) return TWK_HIP_OK;
 	// records that failed the Fisher cut-off were only marked on the device (and counted): they sort behind the rest
 	const unsigned long long dropped = std::min(s.h_n_out[1], n), kept = n - dropped;
 	int rc = TWK_HIP_OK;
-	if (!s.presorted) { rc = sort_records(c, s.out, s.keys, s.vals, n, dropped != 0, c->s_copy); if (rc) return rc; }
-	const twk_hip_record* sorted = s.presorted ? s.sorted : c->d_sorted;      // (a band launch sorted its own behind Fisher's test: enqueue_band_math)
+	if (!s.l.presorted) { rc = sort_records(c, s.out, s.keys, s.vals, n, dropped != 0, c->s_copy); if (rc) return rc; }
+	const twk_hip_record* sorted = s.l.presorted ? s.sorted : c->d_sorted;      // (a band launch sorted its own behind Fisher's test: enqueue_band_math)
 	*n_out = kept;
-	if (to_host && sink && c->dl.active()) {
+	if (to.to_host && to.sink && c->dl.active()) {
 		// many survivors: the delivery thread takes them to the host (deliver_records) while this thread goes on with the launches; few
 		// (a hand-over of a millisecond or two): this thread does, behind whatever is queued
-		if (kept >= HOST_CHUNK / 4 || sink == discard_records) return stage_for_delivery(c, sorted, kept, sink, user);
+		if (kept >= HOST_CHUNK / 4 || to.sink == discard_records) return stage_for_delivery(c, sorted, kept, to.sink, to.user);
 		rc = delivery_drain(c); if (rc) return rc;
 	}
-	if (!to_host) {
+	if (!to.to_host) {
 		rc = ensure_device_keep(c, kept); if (rc) return rc;
 		if (kept) HIPCHK(c, hipMemcpyAsync(c->d_keep + c->d_keep_n, sorted, (size_t)kept * sizeof(twk_hip_record), hipMemcpyDeviceToDevice, c->s_copy));
 		c->d_keep_n += kept;
 		HIPCHK(c, hipStreamSynchronize(c->s_copy));
 		return TWK_HIP_OK;
 	}
-	if (!sink) {
+	if (!to.sink) {
 		rc = ensure_host_records(c, kept); if (rc) return rc;
 		if (kept) HIPCHK(c, hipMemcpyAsync(c->h_recs, sorted, (size_t)kept * sizeof(twk_hip_record), hipMemcpyDeviceToHost, c->s_copy));
 		HIPCHK(c, hipStreamSynchronize(c->s_copy));
 		return TWK_HIP_OK;
 	}
-	return deliver_records(c, sorted, kept, sink, user, c->s_copy, tl_wait);
+	return deliver_records(c, sorted, kept, to.sink, to.user, c->s_copy, tl_wait);
 }
 
-// Rows [row0, row0 + n_rows) of the list zone of the allele-count-sorted phased set, synchronously on the spare slot: every
-// pair (i, j), i < j < zone, inside the r2 band, as an intersection of two carrier lists (ld_list.hip.h) -> candidates ->
-// the list math kernel -> Fisher -> sorted survivors (c->h_recs or the device sink, like a tile).
-int run_list_block(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, uint32_t row0, uint32_t n_rows, uint32_t zone, int32_t window, uint32_t l_window,
-                   const ColRange& cr, unsigned long long capacity, unsigned long long* n_out, bool to_host,
-                   twk_hip_record_sink sink = nullptr, void* user = nullptr) {
+// What a list block and a probe block begin with, on the spare slot: room for a candidate per pair of the block's rectangle t, a fresh
+// launch, the math kernel's parameter block on the device and the ListWork fields the two have in common.
+int begin_list_launch(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, bool probe, const twk_hip_tile_desc& t, uint32_t zone, const ColRange& cr,
+                      unsigned long long capacity, ListWork& w) {
 	const int set = unphased ? PS_SORTED_U : PS_SORTED_P;
 	const PlaneSet& ps = c->planes[set];
 	Slot& s = c->slot[SYNC_SLOT];
-	const uint64_t pairs_max = (uint64_t)n_rows * (zone - row0);
 	const unsigned cand_words = unphased ? 6 : 3;              // (A, B, ALTALT) or (A, B, HH, HQ, QH, QQ)
-	int rc = ensure_slot(c, s, (size_t)std::max<uint64_t>(cand_words * pairs_max, 1024), capacity); if (rc) return rc;
+	int rc = ensure_slot(c, s, (size_t)std::max<uint64_t>(cand_words * (uint64_t)t.nA * t.nB, 1024), capacity); if (rc) return rc;
 	if (!c->d_list_stats) HIPCHK(c, hipMalloc((void**)&c->d_list_stats, sizeof(StatsParams)));
-	s.two_pass = false; s.fused = false; s.is_list = true; s.is_probe = false; s.was_deferred = false; s.presorted = false; s.cand_overflow = false; s.cand_cap = s.C_words / cand_words; s.minP = f.minP;
-	twk_hip_tile_desc t{};
-	t.rowA0 = row0; t.nA = n_rows; t.rowB0 = row0; t.nB = zone - row0; t.diag = 1; t.window = window; t.l_window = l_window;
+	Launch& l = begin_launch(s, set, f.minP);
+	l.is_list = true; l.is_probe = probe; l.form.unphased = unphased; l.cand = s.C; l.cand_cap = s.C_words / cand_words;
 	const StatsParams sp = make_stats(c, set, t, s, !unphased, 0, f, &cr);
 	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
 	HIPCHK(c, hipMemcpyAsync(c->d_list_stats, &sp, sizeof(sp), hipMemcpyHostToDevice, c->s_compute));
-	ListWork w{};
 	w.lists = ps.lists; w.stride = ps.list_max + 1; w.mac = ps.list_mac; w.flip = ps.list_flip; w.rowpop = ps.rowpop;
-	w.n_list = zone; w.row0 = row0; w.n_rows = n_rows;
+	w.n_list = zone; w.row0 = t.rowA0; w.n_rows = t.nA;
 	w.col_hi = cr.d_hi; w.hi_a0 = cr.a0; w.hi_b0 = cr.b0;
 	w.two_n = 2.0 * (double)c->N; w.cut = f.minR2 * (1.0 - 1e-6);
-	w.cand = s.C; w.cap = s.cand_cap; w.n_cand = s.n_out + 2;
+	w.cand = l.cand; w.cap = l.cand_cap; w.n_cand = s.n_out + 2;
+	return TWK_HIP_OK;
+}
+// ... and end with, behind their screen kernel (between ev_c0 and ev_c1): the list math over the candidates (if anything ran), the launch's
+// end, and the survivors' delivery like a tile's.
+int end_list_launch(twk_hip_ctx* c, const twk_hip_tile_desc& t, bool ran, unsigned long long* n_out, const Deliver& to) {
+	Slot& s = c->slot[SYNC_SLOT];
+	HIPCHK(c, hipEventRecord(s.ev_c1, c->s_compute));
+	if (ran) { const int rc = launch_list_math(c, s, c->d_list_stats); if (rc) return rc; }
+	{ const int rc = close_launch(c, s); if (rc) return rc; }
+	return finish_tile(c, s, t, n_out, to);
+}
+
+// Rows [row0, row0 + n_rows) of the list zone of an allele-count-sorted set, synchronously on the spare slot: every
+// pair (i, j), i < j < zone, inside the r2 band, as an intersection of two carrier lists (ld_list.hip.h) -> candidates ->
+// the list math kernel -> Fisher -> sorted survivors (delivered like a tile's).
+int run_list_block(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, uint32_t row0, uint32_t n_rows, uint32_t zone, int32_t window, uint32_t l_window,
+                   const ColRange& cr, unsigned long long capacity, unsigned long long* n_out, const Deliver& to) {
+	twk_hip_tile_desc t{};
+	t.rowA0 = row0; t.nA = n_rows; t.rowB0 = row0; t.nB = zone - row0; t.diag = 1; t.window = window; t.l_window = l_window;
+	ListWork w{};
+	int rc = begin_list_launch(c, f, unphased, false, t, zone, cr, capacity, w); if (rc) return rc;
+	Slot& s = c->slot[SYNC_SLOT];
 	// the widest row of the block decides the grid; lanes beyond a row's own reach leave at once
 	uint32_t width = 0;
 	for (uint32_t i = row0; i < row0 + n_rows; ++i) {
 		const uint32_t lim = std::min<uint32_t>(zone, cr.hi ? cr.b0 + cr.hi[i - cr.a0] : zone);
-		if (lim > i + 1) width = std::max(width, lim - i - 1);
-	}
-	s.row_pairs = 0;
-	for (uint32_t i = row0; i < row0 + n_rows; ++i) {
-		const uint32_t lim = std::min<uint32_t>(zone, cr.hi ? cr.b0 + cr.hi[i - cr.a0] : zone);
-		if (lim > i + 1) s.row_pairs += lim - i - 1;              // pairs intersected (accounting only)
+		if (lim <= i + 1) continue;
+		width = std::max(width, lim - i - 1);
+		s.l.row_pairs += lim - i - 1;              // pairs intersected (accounting only)
 	}
 	HIPCHK(c, hipEventRecord(s.ev_c0, c->s_compute));
 	if (width) {
@@ -1380,62 +1405,35 @@ int run_list_block(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, uint
 		else hipLaunchKernelGGL(k_list_screen, dim3((width + 255) / 256, n_rows), dim3(256), 0, c->s_compute, w);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipEventRecord(s.ev_c1, c->s_compute));
-	if (width) {
-		if (unphased) hipLaunchKernelGGL(k_ld_stats_list_unphased, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const StatsParams*)c->d_list_stats,
-		                                 (const uint32_t*)s.C, (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		else hipLaunchKernelGGL(k_ld_stats_list, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const StatsParams*)c->d_list_stats, (const uint32_t*)s.C,
-		                        (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		HIPCHK(c, hipGetLastError());
-	}
-	{ const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, f.minP, s.C, s.C_words, s.keys); if (rc) return rc; }
-	HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
-	HIPCHK(c, hipEventRecord(s.ev_s1, c->s_compute));
-	return finish_tile(c, s, t, n_out, to_host, sink, user);
+	return end_list_launch(c, t, width != 0, n_out, to);
 }
 
 // Zone rows [row0, row0 + n_rows) against the columns [col0, col0 + n_cols) outside the zone (col0 >= zone): every pair inside the
 // r2 band as a probe of the row variant's carrier list into the column variant's plane row(s) (k_probe_screen, ld_list.hip.h) ->
 // candidates -> the list math kernel -> Fisher -> sorted survivors, like a list block.
 int run_probe_block(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, uint32_t row0, uint32_t n_rows, uint32_t zone, uint32_t col0, uint32_t n_cols,
-                    int32_t window, uint32_t l_window, const ColRange& cr, unsigned long long capacity, unsigned long long* n_out, bool to_host,
-                    twk_hip_record_sink sink, void* user) {
-	const int set = unphased ? PS_SORTED_U : PS_SORTED_P;
-	const PlaneSet& ps = c->planes[set];
-	Slot& s = c->slot[SYNC_SLOT];
-	const uint64_t pairs_max = (uint64_t)n_rows * n_cols;
-	const unsigned cand_words = unphased ? 6 : 3;
-	int rc = ensure_slot(c, s, (size_t)std::max<uint64_t>(cand_words * pairs_max, 1024), capacity); if (rc) return rc;
-	if (!c->d_list_stats) HIPCHK(c, hipMalloc((void**)&c->d_list_stats, sizeof(StatsParams)));
-	s.two_pass = false; s.fused = false; s.is_list = true; s.is_probe = true; s.was_deferred = false; s.presorted = false; s.cand_overflow = false; s.cand_cap = s.C_words / cand_words; s.minP = f.minP;
+                    int32_t window, uint32_t l_window, const ColRange& cr, unsigned long long capacity, unsigned long long* n_out, const Deliver& to) {
 	twk_hip_tile_desc t{};
 	t.rowA0 = row0; t.nA = n_rows; t.rowB0 = col0; t.nB = n_cols; t.diag = 0; t.window = window; t.l_window = l_window;
-	const StatsParams sp = make_stats(c, set, t, s, !unphased, 0, f, &cr);
-	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
-	HIPCHK(c, hipMemcpyAsync(c->d_list_stats, &sp, sizeof(sp), hipMemcpyHostToDevice, c->s_compute));
 	ProbeWork p{};
-	ListWork& w = p.lw;
-	w.lists = ps.lists; w.stride = ps.list_max + 1; w.mac = ps.list_mac; w.flip = ps.list_flip; w.rowpop = ps.rowpop;
-	w.n_list = zone; w.row0 = row0; w.n_rows = n_rows;
-	w.col_hi = cr.d_hi; w.hi_a0 = cr.a0; w.hi_b0 = cr.b0;
-	w.two_n = 2.0 * (double)c->N; w.cut = f.minR2 * (1.0 - 1e-6);
-	w.cand = s.C; w.cap = s.cand_cap; w.n_cand = s.n_out + 2;
+	int rc = begin_list_launch(c, f, unphased, true, t, zone, cr, capacity, p.lw); if (rc) return rc;
+	Slot& s = c->slot[SYNC_SLOT];
+	const PlaneSet& ps = c->planes[s.l.plane_set];
 	// through LDS (k_probe_lds_t: 512 rows x 4 columns a block, 2 columns of unphased planes); option probe_lds = 0: gathers straight from L2, one
 	// column a block (the round-4 kernels: kept as the twin the LDS form is tested against)
 	const bool via_lds = c->opt.probe_lds != 0;
 	p.rows = ps.rows; p.W = ps.W; p.col0 = col0; p.n_cols = n_cols; p.n_row_blocks = via_lds ? (n_rows + PROBE_ROWS - 1) / PROBE_ROWS : (n_rows + 255) / 256;
-	s.row_pairs = 0;
 	for (uint32_t i = row0; i < row0 + n_rows; ++i) {
 		const uint32_t lim = std::min<uint64_t>((uint64_t)col0 + n_cols, cr.hi ? (uint64_t)cr.b0 + cr.hi[i - cr.a0] : (uint64_t)col0 + n_cols);
 		const uint32_t first = std::max(col0, i + 1);             // (columns inside the zone: those behind the row)
-		if (lim > first) s.row_pairs += lim - first;              // pairs probed (accounting only)
+		if (lim > first) s.l.row_pairs += lim - first;              // pairs probed (accounting only)
 	}
 	constexpr uint32_t LDS_COLS_P = 4, LDS_COLS_U = 2;
 	const uint32_t strip_cols = via_lds ? (unphased ? LDS_COLS_U : LDS_COLS_P) : 1;
 	const uint64_t n_blocks = (uint64_t)p.n_row_blocks * ((n_cols + strip_cols - 1) / strip_cols);
 	if (n_blocks > 0x7FFFFFFFull) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipEventRecord(s.ev_c0, c->s_compute));
-	if (s.row_pairs) {
+	if (s.l.row_pairs) {
 		const dim3 grid((uint32_t)n_blocks);
 		if (via_lds && unphased) hipLaunchKernelGGL(k_probe_lds_unphased_t<LDS_COLS_U>, grid, dim3(PROBE_ROWS), 0, c->s_compute, p);
 		else if (via_lds) hipLaunchKernelGGL(k_probe_lds_t<LDS_COLS_P>, grid, dim3(PROBE_ROWS), 0, c->s_compute, p);
@@ -1443,31 +1441,19 @@ int run_probe_block(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, uin
 		else hipLaunchKernelGGL(k_probe_screen, grid, dim3(256), 0, c->s_compute, p);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipEventRecord(s.ev_c1, c->s_compute));
-	if (s.row_pairs) {
-		if (unphased) hipLaunchKernelGGL(k_ld_stats_list_unphased, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const StatsParams*)c->d_list_stats,
-		                                 (const uint32_t*)s.C, (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		else hipLaunchKernelGGL(k_ld_stats_list, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const StatsParams*)c->d_list_stats, (const uint32_t*)s.C,
-		                        (const unsigned long long*)(s.n_out + 2), s.cand_cap);
-		HIPCHK(c, hipGetLastError());
-	}
-	{ const int rc2 = launch_fisher(c, s.out, s.n_out, s.cap_use, f.minP, s.C, s.C_words, s.keys); if (rc2) return rc2; }
-	HIPCHK(c, hipMemcpyAsync(s.h_n_out, s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute));
-	HIPCHK(c, hipEventRecord(s.ev_s1, c->s_compute));
-	return finish_tile(c, s, t, n_out, to_host, sink, user);
+	return end_list_launch(c, t, s.l.row_pairs != 0, n_out, to);
 }
 
-// One tile, synchronously, on the spare slot; survivors end up in c->h_recs (sink == null), with `sink`, or in the device sink.
+// One tile, synchronously, on the spare slot; survivors go where `to` says.
 int run_tile_sync(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f,
-                  unsigned long long capacity, unsigned long long* n_out, bool to_host = true, const ColRange* cr = nullptr,
-                  twk_hip_record_sink sink = nullptr, void* user = nullptr) {
+                  unsigned long long capacity, unsigned long long* n_out, const Deliver& to, const ColRange* cr = nullptr) {
 	Slot& s = c->slot[SYNC_SLOT];
 	int rc = enqueue_tile(c, mode, t, f, s, capacity, cr); if (rc) return rc;
-	rc = finish_tile(c, s, t, n_out, to_host, sink, user);
-	if (rc == TWK_HIP_E_OVERFLOW && s.cand_overflow) {       // too many candidates for the fused / three-product form: through C, four products, for the rest of this call
+	rc = finish_tile(c, s, t, n_out, to);
+	if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow) {       // too many candidates for the fused / three-product form: through C, four products, for the rest of this call
 		c->fused_ok = false; c->three_ok = false;
 		rc = enqueue_tile(c, mode, t, f, s, capacity, cr); if (rc) return rc;
-		rc = finish_tile(c, s, t, n_out, to_host, sink, user);
+		rc = finish_tile(c, s, t, n_out, to);
 	}
 	return rc;
 }
@@ -1478,7 +1464,7 @@ int discard_records(void*, const twk_hip_record*, uint64_t) { return 0; }     //
 // that cannot overflow (strip_rows * cols <= capacity).
 // (cr: the region's column ranges - window, r2 band, list zone - so that a strip decides exactly the pairs its tile would have)
 int redo_tile_in_strips(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f,
-                        unsigned long long capacity, twk_hip_record_sink sink, void* user, uint64_t* n_recs, const ColRange* cr = nullptr) {
+                        unsigned long long capacity, const Deliver& to, uint64_t* n_recs, const ColRange* cr = nullptr) {
 	const uint32_t strip = (uint32_t)std::max<unsigned long long>(1, capacity / std::max<uint32_t>(t.nB, 1));
 	const bool diag = t.diag && t.rowA0 == t.rowB0;
 	for (uint32_t r0 = 0; r0 < t.nA; r0 += strip) {
@@ -1497,7 +1483,7 @@ int redo_tile_in_strips(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, co
 		}
 		for (int k = 0; k < np; ++k) {
 			unsigned long long n = 0;
-			int rc = run_tile_sync(c, mode, parts[k], f, (unsigned long long)parts[k].nA * parts[k].nB, &n, !c->device_sink, cr, sink ? sink : discard_records, user);
+			int rc = run_tile_sync(c, mode, parts[k], f, (unsigned long long)parts[k].nA * parts[k].nB, &n, to, cr);
 			if (rc) return rc;
 			*n_recs += n;
 		}
@@ -1945,8 +1931,8 @@ int twk_hip_count_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc* t, uin
 	Slot& s = c->slot[SYNC_SLOT];
 	const Geometry g = tile_geometry(planes_per_variant(kind), *t);
 	rc = ensure_slot(c, s, (size_t)g.rowsA * g.rowsB, 1); if (rc) return rc;
-	uint64_t rp = 0;
-	rc = launch_count(c, kind, *t, s, 0, s.ev_c0, s.ev_c1, &rp); if (rc) return rc;
+	begin_launch(s, kind, 1.0);
+	rc = launch_count(c, kind, *t, s, 0, nullptr, LaunchForm(), nullptr); if (rc) return rc;
 	const int ncell = phased ? 4 : 9;
 	const size_t n = (size_t)t->nA * t->nB * ncell;
 	unsigned long long* d_cells = nullptr;
@@ -1970,7 +1956,7 @@ int twk_hip_ld_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc* t, const 
 	HIPCHK(c, hipSetDevice(c->device));
 	c->fused_ok = true; c->three_ok = true;
 	unsigned long long n = 0;
-	int rc = run_tile_sync(c, mode, *t, *f, std::max<unsigned long long>(capacity, 1), &n);
+	int rc = run_tile_sync(c, mode, *t, *f, std::max<unsigned long long>(capacity, 1), &n, Deliver());      // (whole, in c->h_recs)
 	flush_graveyard(c);
 	*n_out = n;
 	if (n_pairs) *n_pairs = pairs_in_tile(c, *t);
@@ -1998,7 +1984,7 @@ namespace {
 struct RegionRun {
 	twk_hip_ctx* c; int mode; const twk_hip_filters* f;
 	const PlanGeom& g; const PlanEnv& env; RegionPlan& plan;
-	twk_hip_record_sink sink; void* user;
+	Deliver to;                               // every launch of the region: the device sink, or the caller's sink (none: records are counted and dropped)
 	std::chrono::steady_clock::time_point t_origin = std::chrono::steady_clock::now();
 	ColRange col_range;
 	unsigned long long cap_default = 1ull << 24;
@@ -2006,7 +1992,7 @@ struct RegionRun {
 	std::vector<char> want_three;             // per launch: the three-product form may be used (decide_three_by_samples)
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, twk_hip_record_sink sink_, void* user_)
-		: c(c_), mode(mode_), f(f_), g(g_), env(e_), plan(p_), sink(sink_ ? sink_ : discard_records), user(user_) {}
+		: c(c_), mode(mode_), f(f_), g(g_), env(e_), plan(p_), to{!c_->device_sink, sink_ ? sink_ : discard_records, user_} {}
 
 	void mark(const char* what, size_t i, unsigned long long x = 0) const {       // "timeline" option: where the host's time goes
 		if (!c->opt.timeline) return;
@@ -2054,7 +2040,7 @@ struct RegionRun {
 		for (uint32_t row = lr0; row < lr1;) {
 			const uint32_t nr = std::min(rows_per, lr1 - row);
 			unsigned long long nrec = 0;
-			const int rc = run_list_block(c, *f, unphased, row, nr, zone, g.window, g.l_window, col_range, cap_list, &nrec, !c->device_sink, sink, user);
+			const int rc = run_list_block(c, *f, unphased, row, nr, zone, g.window, g.l_window, col_range, cap_list, &nrec, to);
 			if (rc == TWK_HIP_E_OVERFLOW && nr > 1) { rows_per = std::max<uint32_t>(1, nr / 2); continue; }      // more survivors than the buffer holds: fewer rows
 			if (rc == TWK_HIP_E_OVERFLOW && cap_list < zone) { cap_list = zone; continue; }                      // one row: it cannot have more than `zone` partners
 			if (rc) return rc;
@@ -2081,7 +2067,7 @@ struct RegionRun {
 			const uint32_t lim = reach(row + nr - 1);
 			if (lim <= first) { row += nr; continue; }
 			unsigned long long nrec = 0;
-			const int rc = run_probe_block(c, *f, unphased, row, nr, zone, first, lim - first, g.window, g.l_window, col_range, cap_probe, &nrec, !c->device_sink, sink, user);
+			const int rc = run_probe_block(c, *f, unphased, row, nr, zone, first, lim - first, g.window, g.l_window, col_range, cap_probe, &nrec, to);
 			if (rc == TWK_HIP_E_OVERFLOW && nr > 1) { rows_cap = std::max<uint32_t>(1, nr / 2); continue; }
 			if (rc == TWK_HIP_E_OVERFLOW && cap_probe < (unsigned long long)(lim - first)) { cap_probe = lim - first; continue; }
 			if (rc) return rc;
@@ -2103,10 +2089,7 @@ struct RegionRun {
 		const std::vector<twk_hip_tile_desc>& mine = plan.mine;
 		const size_t n = mine.size();
 		want_three.assign(n, 1);
-		if (mine.empty() || !c->three_ok || c->opt.three != 1) return TWK_HIP_OK;
-		const TilePlan pl = plan_for(c, mode);
-		const bool eligible = !pl.phased1 && pl.set2 < 0 && set_kind(pl.set1) == PK_UNPHASED && f->minR2 > 1e-6 && f->minR2 <= 1.0;
-		if (!eligible) return TWK_HIP_OK;
+		if (mine.empty() || c->opt.three != 1 || !launch_form(c, plan_for(c, mode), *f).three) return TWK_HIP_OK;      // (no launch of this region would take the form)
 		// (fused launches - short rows - are sampled as well: they keep their candidates whatever their number, but past ~1.2 % of the pairs
 		// the recount costs more than the third product saves: 2,504 samples, -u -w 1000000, 2.9 % candidates: 27.4 + 30.3 ms of count kernel and
 		// math with three products in the first of two launches, 30 + 21 ms with four in both)
@@ -2127,7 +2110,7 @@ struct RegionRun {
 			c->sampling = true;
 			int rc = enqueue_tile(c, mode, st, *f, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
 			c->sampling = false;
-			if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, true, discard_records, nullptr);
+			if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
 			const unsigned long long cand = ss.h_n_out[2], sample_pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
 			c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
 			if (c->launch_ring.size() > keep_ring && c->launches_seen == keep_seen + 1 && keep_seen < LAUNCH_RING) c->launch_ring.pop_back();
@@ -2145,10 +2128,10 @@ struct RegionRun {
 	// the rest of the call as well); more survivors than the buffer holds -> row strips.
 	int run_tile_with_fallbacks(const twk_hip_tile_desc& t) {
 		unsigned long long nrec = 0;
-		int r = run_tile_sync(c, mode, t, *f, cap_default, &nrec, !c->device_sink, cr(), sink, user);
+		int r = run_tile_sync(c, mode, t, *f, cap_default, &nrec, to, cr());
 		if (r == TWK_HIP_E_OVERFLOW) {
 			uint64_t nr = 0;
-			r = redo_tile_in_strips(c, mode, t, *f, c->slot[SYNC_SLOT].cap_use, sink, user, &nr, cr());
+			r = redo_tile_in_strips(c, mode, t, *f, c->slot[SYNC_SLOT].cap_use, to, &nr, cr());
 			nrec = nr;
 		}
 		if (r == TWK_HIP_OK) tot_recs += nrec;
@@ -2182,20 +2165,20 @@ struct RegionRun {
 		mark("finish: wait for launch", done);
 		int rc;
 		if (b) {
-			rc = skipped[done] ? TWK_HIP_E_OVERFLOW : finish_tile(c, s, mine[done], &nrec, !c->device_sink, sink, user);
+			rc = skipped[done] ? TWK_HIP_E_OVERFLOW : finish_tile(c, s, mine[done], &nrec, to);
 			mark("finished (records delivered) launch", done, nrec);
 			if (rc == TWK_HIP_E_OVERFLOW) rc = run_band_as_matrix_tiles(*b);      // candidates or survivors beyond the launch's buffers
 			else if (rc == TWK_HIP_OK) tot_recs += nrec;
 			return rc;
 		}
-		rc = finish_tile(c, s, mine[done], &nrec, !c->device_sink, sink, user);
-		if (rc == TWK_HIP_E_OVERFLOW && s.cand_overflow) {     // the fused / three-product form's candidate list overflowed: this tile again through C, four products
+		rc = finish_tile(c, s, mine[done], &nrec, to);
+		if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow) {     // the fused / three-product form's candidate list overflowed: this tile again through C, four products
 			c->fused_ok = false; c->three_ok = false;            // (and the tiles not yet enqueued as well)
-			rc = run_tile_sync(c, mode, mine[done], *f, cap_default, &nrec, !c->device_sink, cr(), sink, user);
+			rc = run_tile_sync(c, mode, mine[done], *f, cap_default, &nrec, to, cr());
 		}
 		if (rc == TWK_HIP_E_OVERFLOW) {
 			uint64_t nr = 0;
-			rc = redo_tile_in_strips(c, mode, mine[done], *f, s.cap_use, sink, user, &nr, cr());
+			rc = redo_tile_in_strips(c, mode, mine[done], *f, s.cap_use, to, &nr, cr());
 			if (rc) return rc;
 			tot_recs += nr;
 		} else if (rc) {
@@ -2270,65 +2253,51 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, PlanEnv& en
 
 }  // namespace
 
-static int region_impl(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA,
-                       uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
-                       uint32_t tile_variants, int32_t window, uint32_t l_window, twk_hip_record_sink sink,
-                       void* user, uint64_t* n_pairs, uint64_t* n_records) {
-	const PlanGeom g{a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window};
+// The arguments of twk_hip_ld_region, as they travel inside the library: region_dispatch edits a copy per stage.
+struct RegionArgs {
+	int mode; const twk_hip_filters* f; uint32_t a0, nA, b0, nB; int32_t triangle; uint32_t part, n_parts, tile_variants; int32_t window; uint32_t l_window;
+	twk_hip_record_sink sink; void* user; uint64_t* n_pairs; uint64_t* n_records;
+	RegionArgs stage(int mode_, uint32_t a0_, uint32_t nA_, uint32_t b0_, uint32_t nB_, int32_t triangle_, uint64_t* n_pairs_, uint64_t* n_records_) const {
+		RegionArgs r = *this;
+		r.mode = mode_; r.a0 = a0_; r.nA = nA_; r.b0 = b0_; r.nB = nB_; r.triangle = triangle_; r.n_pairs = n_pairs_; r.n_records = n_records_;
+		return r;
+	}
+};
+
+static int region_impl(twk_hip_ctx* c, const RegionArgs& a) {
+	const PlanGeom g{a.a0, a.nA, a.b0, a.nB, a.triangle, a.part, a.n_parts, a.tile_variants, a.window, a.l_window};
 	PlanEnv env;
-	int rc = plan_env_for(c, mode, f, env); if (rc) return rc;
+	int rc = plan_env_for(c, a.mode, a.f, env); if (rc) return rc;
 	RegionPlan plan;
 	plan_region(env, g, plan);
-	RegionRun run(c, mode, f, g, env, plan, sink, user);
-	run.mark("region: mode", (size_t)mode, nA);
+	RegionRun run(c, a.mode, a.f, g, env, plan, a.sink, a.user);
+	run.mark("region: mode", (size_t)a.mode, a.nA);
 	rc = run.prepare(); if (rc) return rc;
 	rc = run.run_zone_passes(); if (rc) return rc;
 	run.mark("tiles listed", plan.mine.size());
 	rc = run.decide_three_by_samples(); if (rc) return rc;
 	rc = run.run_pipeline(); if (rc) return rc;
 	if (plan.windowed) run.tot_pairs = plan.pairs;      // screen: every pair of the band is decided; window: the pairs inside it, the ones the math evaluates
-	if (n_pairs) *n_pairs = run.tot_pairs;
-	if (n_records) *n_records = run.tot_recs;
+	if (a.n_pairs) *a.n_pairs = run.tot_pairs;
+	if (a.n_records) *a.n_records = run.tot_recs;
 	return TWK_HIP_OK;
 }
 
-static int region_dispatch(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA,
-                           uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
-                           uint32_t tile_variants, int32_t window, uint32_t l_window, twk_hip_record_sink sink,
-                           void* user, uint64_t* n_pairs, uint64_t* n_records);
-
-int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA,
-                      uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
-                      uint32_t tile_variants, int32_t window, uint32_t l_window, twk_hip_record_sink sink,
-                      void* user, uint64_t* n_pairs, uint64_t* n_records) {
-	if (c) delivery_begin(c, sink);
-	int rc = region_dispatch(c, mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, sink, user, n_pairs, n_records);
-	if (c) {                                // every record staged so far reaches the sink before the call returns, whatever the call's own result
-		(void)hipSetDevice(c->device);
-		const int drc = delivery_end(c);
-		if (rc == TWK_HIP_OK && drc) rc = drc;            // (its text is in c->err: delivery_end)
-	}
-	if (c) flush_graveyard(c);               // buffers outgrown during the call: nothing is in flight any more
-	return rc;
-}
-
-static int region_dispatch(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA,
-                           uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
-                           uint32_t tile_variants, int32_t window, uint32_t l_window, twk_hip_record_sink sink,
-                           void* user, uint64_t* n_pairs, uint64_t* n_records) {
-	if (!c || !f || !valid_mode(mode) || n_parts == 0 || part >= n_parts) return TWK_HIP_E_INVALID;
+static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
+	const int mode = a.mode; const twk_hip_filters* f = a.f;
+	if (!c || !f || !valid_mode(mode) || a.n_parts == 0 || a.part >= a.n_parts) return TWK_HIP_E_INVALID;
 	if (!c->raw) return TWK_HIP_E_STATE;
-	if (nA == 0 || nB == 0 || (uint64_t)a0 + nA > c->M || (uint64_t)b0 + nB > c->M) return TWK_HIP_E_INVALID;
-	if (triangle && (a0 != b0 || nB < nA)) return TWK_HIP_E_INVALID;
+	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
+	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
 	c->fused_ok = c->three_ok = !c->score_on;      // a score looks at every pair: no screen in front of the matrix
-	const bool whole = triangle && a0 == 0 && nA == c->M && nB == c->M;
+	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
 	// ... or, at any cut-off above zero, rows long enough to keep carrier lists: the band is then (nearly) everything, but the
 	// allele-count order still puts the rare variants in a zone whose pairs are list merges and probes instead of contractions
 	const bool lists_pay = f->minR2 > 0 && c->opt.lists != 0 && (c->Wp / 128 >= 32 || c->opt.lists == 2);
-	const bool screen = (window & TWK_HIP_OPT_R2_SCREEN) && whole && !(window & TWK_HIP_OPT_WINDOW) && (f->minR2 >= 1e-3 || lists_pay) && c->M >= 2;
+	const bool screen = (a.window & TWK_HIP_OPT_R2_SCREEN) && whole && !(a.window & TWK_HIP_OPT_WINDOW) && (f->minR2 >= 1e-3 || lists_pay) && c->M >= 2;
 	if (screen && !c->any_missing && (mode == TWK_HIP_MODE_PHASED || mode == TWK_HIP_MODE_AUTO || mode == TWK_HIP_MODE_UNPHASED)) {
 		// Below the cut-off that makes a band worth having the sorted order is only taken for its carrier lists: when the set turns out to
 		// keep none (too few rare variants), the sorted copy of the planes is dropped again and the run goes the file-order way (it used to
@@ -2342,24 +2311,12 @@ static int region_dispatch(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 			if (c->planes[sset].n_list < 2) {
 				keep_sorted = false; known_useless = true;
 				HIPCHK(c, hipDeviceSynchronize());
-				PlaneSet& ps = c->planes[sset];
-				if (ps.owns_rows && ps.rows) (void)hipFree(ps.rows);
-				if (ps.rowpop) (void)hipFree(ps.rowpop);
-				if (ps.ids) (void)hipFree(ps.ids);
-				if (ps.lists) (void)hipFree(ps.lists);
-				if (ps.list_mac) (void)hipFree(ps.list_mac);
-				if (ps.list_flip) (void)hipFree(ps.list_flip);
-				if (ps.terms) (void)hipFree(ps.terms);
-				ps = PlaneSet();
+				free_plane_set(c->planes[sset]);
 			}
 		}
-		if (keep_sorted)
-			return region_impl(c, mode == TWK_HIP_MODE_UNPHASED ? MODE_INT_SORTED_U : MODE_INT_SORTED_P, f, 0, c->M, 0, c->M, 1, part, n_parts,
-			                   tile_variants, window, l_window, sink, user, n_pairs, n_records);
+		if (keep_sorted) return region_impl(c, a.stage(mode == TWK_HIP_MODE_UNPHASED ? MODE_INT_SORTED_U : MODE_INT_SORTED_P, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records));
 	}
-	if (!(mode == TWK_HIP_MODE_AUTO && c->any_missing && whole))
-		return region_impl(c, mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window,
-		                   sink, user, n_pairs, n_records);
+	if (!(mode == TWK_HIP_MODE_AUTO && c->any_missing && whole)) return region_impl(c, a);
 	// Default mode over the whole triangle with missing genotypes somewhere: every pair goes through
 	// the cheap one-plane phased products, and only the pairs that involve a variant with missing
 	// data (the leading group G of the regrouped set) through the 3-plane unphased ones:
@@ -2372,27 +2329,38 @@ static int region_dispatch(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 		// the stages below then cover every pair that involves a variant with missing data
 		rc = ensure_planes(c, PS_SORTED_P); if (rc) return rc;
 		const uint32_t nC = c->planes[PS_SORTED_P].n_front;
-		if (nC >= 2) rc = region_impl(c, MODE_INT_SORTED_P, f, 0, nC, 0, nC, 1, part, n_parts, tile_variants, window, l_window,
-		                              sink, user, &pairs, &recs);
+		if (nC >= 2) rc = region_impl(c, a.stage(MODE_INT_SORTED_P, 0, nC, 0, nC, 1, &pairs, &recs));
 	} else
-	rc = region_impl(c, MODE_INT_AUTO_CLEAN, f, 0, c->M, 0, c->M, 1, part, n_parts, tile_variants, window, l_window,
-	                 sink, user, &pairs, &recs);
+		rc = region_impl(c, a.stage(MODE_INT_AUTO_CLEAN, 0, c->M, 0, c->M, 1, &pairs, &recs));
 	struct Mute { twk_hip_ctx* c; ~Mute() { c->progress_muted = false; } } mute{c};
 	c->progress_muted = true;
 	if (rc == TWK_HIP_OK && nG >= 2) {
-		rc = region_impl(c, MODE_INT_GROUPED, f, 0, nG, 0, nG, 1, part, n_parts, tile_variants, window, l_window,
-		                 sink, user, &p2, &r2);
+		rc = region_impl(c, a.stage(MODE_INT_GROUPED, 0, nG, 0, nG, 1, &p2, &r2));
 		recs += r2;
 		if (screen) pairs += p2;               // the screened stage only counted the pairs without missing data
 	}
 	if (rc == TWK_HIP_OK && nG >= 1 && nG < c->M) {
-		rc = region_impl(c, MODE_INT_GROUPED, f, 0, nG, nG, c->M - nG, 0, part, n_parts, tile_variants, window, l_window,
-		                 sink, user, &p2, &r2);
+		rc = region_impl(c, a.stage(MODE_INT_GROUPED, 0, nG, nG, c->M - nG, 0, &p2, &r2));
 		recs += r2;
 		if (screen) pairs += p2;
 	}
-	if (n_pairs) *n_pairs = pairs;          // every pair of the shard is evaluated exactly once
-	if (n_records) *n_records = recs;
+	if (a.n_pairs) *a.n_pairs = pairs;          // every pair of the shard is evaluated exactly once
+	if (a.n_records) *a.n_records = recs;
+	return rc;
+}
+
+int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA,
+                      uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                      uint32_t tile_variants, int32_t window, uint32_t l_window, twk_hip_record_sink sink,
+                      void* user, uint64_t* n_pairs, uint64_t* n_records) {
+	if (c) delivery_begin(c, sink);
+	int rc = region_dispatch(c, RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, sink, user, n_pairs, n_records});
+	if (c) {                                // every record staged so far reaches the sink before the call returns, whatever the call's own result
+		(void)hipSetDevice(c->device);
+		const int drc = delivery_end(c);
+		if (rc == TWK_HIP_OK && drc) rc = drc;            // (its text is in c->err: delivery_end)
+	}
+	if (c) flush_graveyard(c);               // buffers outgrown during the call: nothing is in flight any more
 	return rc;
 }
 
@@ -2411,8 +2379,8 @@ int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	struct ScoreOn { twk_hip_ctx* c; ~ScoreOn() { c->score_on = false; } } on{c};
 	c->score_on = true;
 	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a score)
-	int rc = region_dispatch(c, mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
-	                         nullptr, nullptr, n_pairs, nullptr);
+	int rc = region_dispatch(c, RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
+	                                       nullptr, nullptr, n_pairs, nullptr});
 	if (rc == TWK_HIP_OK) {
 		hipError_t e = hipMemcpyAsync(sum_r2, c->d_score_sum, M * sizeof(double), hipMemcpyDeviceToHost, c->s_compute);
 		if (e == hipSuccess) e = hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
