@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -81,6 +81,12 @@ tsan:
 	TSAN_OPTIONS=halt_on_error=1 ./build/emitter_tsan
 	$(CXX) -O1 -g -std=c++17 -pthread -fsanitize=thread $(PKG)/csrc/tools/delivery_tsan.cpp -o build/delivery_tsan
 	TSAN_OPTIONS=halt_on_error=1 ./build/delivery_tsan
+
+# The engine's buffer owners (csrc/hip/twk_buffers.h) with the allocator stubbed (csrc/tools/buffers_check.cpp): what is freed, when, and once
+buffers-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/buffers_check.cpp -o build/buffers_check
+	./build/buffers_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -37,6 +37,7 @@
 #include "ld_score.hip.h"
 #include "ld_plan.h"
 #include "twk_delivery.h"
+#include "twk_buffers.h"
 
 using namespace twk;
 
@@ -44,26 +45,38 @@ namespace {
 
 inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
+// Every device and page-locked buffer of the engine is one of these (twk_buffers.h): the runtime's allocator behind the owner types.
+struct HipMemOps {
+	typedef hipError_t error;
+	static constexpr hipError_t ok = hipSuccess, out_of_memory = hipErrorOutOfMemory;
+	static hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+	static void device_free(void* p) { (void)hipFree(p); }
+	static hipError_t host_alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+	static void host_free(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = Buffer<T, HipMemOps>;
+template <class T> using PinnedBuf = Buffer<T, HipMemOps, true>;
+
 struct PlaneSet {
-	uint32_t* rows = nullptr;     // [rows_alloc][W]
-	uint32_t* rowpop = nullptr;   // [rows_alloc]
+	uint32_t* rows = nullptr;     // [rows_alloc][W]: own_rows, or the context's raw layout (which *is* the phased plane)
+	DevBuf<uint32_t> own_rows;
+	DevBuf<uint32_t> rowpop;      // [rows_alloc]
 	uint32_t  W = 0;              // words per row (padded to KC)
 	uint32_t  W_live = 0;         // words per row that carry data
 	uint32_t  rows_alloc = 0;
 	bool      built = false;
-	bool      owns_rows = false;
 	// regrouped set only: position in the set -> variant id (device + host), and how many
 	// variants with missing genotypes lead the set
-	uint32_t* ids = nullptr;
+	DevBuf<uint32_t> ids;
 	std::vector<uint32_t> h_ids;
 	uint32_t  n_front = 0;
 	// allele-count-sorted phased set only (ld_list.hip.h): carrier lists of the variants that lead the set with at most
 	// list_max carriers of their minor allele - positions [0, n_list), n_list a multiple of the tile edge
-	uint32_t* lists = nullptr; uint32_t* list_mac = nullptr; uint32_t* list_flip = nullptr;
+	DevBuf<uint32_t> lists, list_mac, list_flip;
 	uint32_t  n_list = 0, list_max = 0;
 	uint32_t  n_probe = 0;         // <= n_list: the leading variants whose lists are short enough for probing to beat the dense pair (ld_list.hip.h)
 	// fused screen kernels: the prefilter's per-variant terms at the cut-off of the run that built them (ScreenWork::terms, k_screen_terms)
-	float4*   terms = nullptr; double terms_cut = -1.0;
+	DevBuf<float4> terms; double terms_cut = -1.0;
 };
 
 // Plane sets a context can hold: one per PlaneKind in file order, plus the masked unphased planes
@@ -124,22 +137,23 @@ struct Launch {
 };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
-	uint32_t* C = nullptr; size_t C_words = 0;
-	twk_hip_record* out = nullptr; unsigned long long capacity = 0;      // survivor buffer and its size (grow-only)
-	unsigned long long* keys = nullptr; uint32_t* vals = nullptr;        // [capacity]: sort key and position of every survivor, written where it is appended
+	DevBuf<uint32_t> C;
+	DevBuf<twk_hip_record> out;                   // survivor buffer (grow-only)
+	DevBuf<unsigned long long> keys; DevBuf<uint32_t> vals;              // [capacity()]: sort key and position of every survivor, written where it is appended
+	unsigned long long capacity() const { return shared_capacity(out, keys, vals); }
 	unsigned long long cap_use = 0;               // ... of which the current launch may use this many (what the caller asked for)
-	unsigned long long* n_out = nullptr;          // device counters: [0] survivors appended, [1] of those dropped by the Fisher cut-off,
+	DevBuf<unsigned long long> n_out;             // device counters: [0] survivors appended, [1] of those dropped by the Fisher cut-off,
 	                                              // [2] candidates of the fused count kernel, [3] three-product candidates whose recount disagrees, [4] shader cycles and
 	                                              // [5] 100 MHz ticks the count kernel's blocks lived for (summed over the blocks), [6], [7] spare, [8 + x] the 100 MHz
 	                                              // tick at which the last block on XCD x finished
-	unsigned long long* h_n_out = nullptr;        // pinned host copy of all of them
+	PinnedBuf<unsigned long long> h_n_out;        // pinned host copy of all of them (both live as long as the context)
 	hipEvent_t ev_c0 = nullptr, ev_c1 = nullptr, ev_s1 = nullptr, ev_c0b = nullptr, ev_c1b = nullptr;
-	twk_hip_record* sorted = nullptr; unsigned long long sorted_cap = 0;      // band launches: the survivors in (idxA, idxB) order (Launch::presorted)
+	DevBuf<twk_hip_record> sorted;                // band launches: the survivors in (idxA, idxB) order (Launch::presorted)
 	// work lists of the (up to two) count launches of the tile: pinned host copy + device copy
-	uint32_t* h_tiles[2] = {nullptr, nullptr}; uint32_t* d_tiles[2] = {nullptr, nullptr}; size_t tiles_cap[2] = {0, 0};
+	PinnedBuf<uint32_t> h_tiles[2]; DevBuf<uint32_t> d_tiles[2];
 	// score launches (ld_score.hip.h): the blocks' row and column partials of the launch (grow-only)
-	double* sc_sum = nullptr; uint32_t* sc_n = nullptr; size_t sc_cap = 0;
-	ScoreArgs* h_sc_args = nullptr; ScoreArgs* d_sc_args = nullptr;      // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
+	DevBuf<double> sc_sum; DevBuf<uint32_t> sc_n;
+	PinnedBuf<ScoreArgs> h_sc_args; DevBuf<ScoreArgs> d_sc_args;         // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
 };
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
@@ -223,21 +237,21 @@ struct twk_hip_ctx {
 	bool deliver_warm = false;       // s_deliver has carried a copy (HipDeliveryOps::thread_begin)
 	uint32_t N = 0, M = 0, M_alloc = 0;
 	uint32_t Wp = 0, Wu = 0;       // padded words per row: raw (2N bits) / unphased planes (N bits)
-	uint32_t* raw = nullptr;       // [M_alloc][Wp]
-	uint32_t* rawmask = nullptr;   // [M_alloc][Wp] or null
+	DevBuf<uint32_t> raw;          // [M_alloc][Wp]
+	DevBuf<uint32_t> rawmask;      // [M_alloc][Wp] or null
 	bool any_missing = false;
 	// metadata (device SoA) + host mirror
-	uint32_t *d_ac = nullptr, *d_an = nullptr, *d_pos = nullptr, *d_rid = nullptr, *d_missing = nullptr;
-	double* d_hwe = nullptr;
-	double* d_lfact = nullptr; int lfact_n = 0;    // lgamma(i + 1), i <= 2N: Fisher's log-binomials (ld_math.hip.h)
-	uint32_t* d_fisher_bins = nullptr;             // [2 * FISHER_BINS]: bin sizes and fill cursors of the walk-length order (s_compute only)
+	DevBuf<uint32_t> d_ac, d_an, d_pos, d_rid, d_missing;
+	DevBuf<double> d_hwe;
+	DevBuf<double> d_lfact; int lfact_n = 0;       // lgamma(i + 1), i <= 2N: Fisher's log-binomials (ld_math.hip.h)
+	DevBuf<uint32_t> d_fisher_bins;                // [2 * FISHER_BINS]: bin sizes and fill cursors of the walk-length order (s_compute only)
 	std::vector<twk_hip_variant_meta> h_meta;
 	std::vector<uint32_t> h_popc;  // ALT alleles per variant as counted on the device (r2 screen; empty until needed, dropped on upload)
 	PlaneSet planes[N_PLANE_SETS];
 	Slot slot[PIPE_SLOTS + 1];     // [0 .. PIPE_SLOTS): the pipeline of region calls; [SYNC_SLOT]: synchronous single-tile calls
-	twk_hip_record* h_recs = nullptr; unsigned long long h_recs_cap = 0;   // pinned staging
+	PinnedBuf<twk_hip_record> h_recs;   // pinned staging
 	// twk_hip_set_device_sink: the survivors of region calls stay on the device, appended here tile by tile
-	StatsParams* d_list_stats = nullptr;          // parameter block of the list pass's math kernel (device copy)
+	DevBuf<StatsParams> d_list_stats;             // parameter block of the list pass's math kernel (device copy)
 	bool fused_ok = true;           // cleared for the rest of a call when a fused tile's candidate list overflowed
 	bool three_ok = true;           // cleared for the rest of a call when a three-product launch had too many candidates for the recount to stay cheap
 	bool sampling = false;          // the launch being enqueued is a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name
@@ -245,36 +259,38 @@ struct twk_hip_ctx {
 	bool sorted_keeps_no_lists[2] = {false, false};      // [phased, unphased]: the allele-count-sorted set was built once for a run below the band's cut-off and
 	                                                     // kept no carrier lists: such runs go the file-order way without building it again (cleared with the planes)
 	bool device_sink = false;
-	twk_hip_record* d_keep = nullptr; unsigned long long d_keep_n = 0, d_keep_cap = 0;
+	DevBuf<twk_hip_record> d_keep; unsigned long long d_keep_n = 0;
 	// the survivors of a tile leave in (idxA, idxB) order: sort keys / permutation (double-buffered), the
 	// reordered records, rocprim's scratch (grow-only)
-	unsigned long long* d_sort_keys = nullptr; uint32_t* d_sort_vals = nullptr; twk_hip_record* d_sorted = nullptr;
-	unsigned long long sort_cap = 0;
-	void* d_sort_tmp = nullptr; size_t sort_tmp_bytes = 0;
+	DevBuf<unsigned long long> d_sort_keys; DevBuf<uint32_t> d_sort_vals; DevBuf<twk_hip_record> d_sorted;      // (one capacity)
+	DevBuf<char> d_sort_tmp;
 	// the same for the sorts of band launches, which run on the compute stream (one at a time, in stream order) while a sort of
 	// the other kind may be running on the copy stream
-	unsigned long long* d_band_keys = nullptr; uint32_t* d_band_vals = nullptr; unsigned long long band_sort_cap = 0;
-	void* d_band_tmp = nullptr; size_t band_tmp_bytes = 0;
-	std::vector<void*> host_graveyard; // the same for page-locked host buffers
-	std::vector<void*> graveyard;      // device buffers outgrown while launches were in flight: hipFree waits for the device, so they are freed when the call ends
+	DevBuf<unsigned long long> d_band_keys; DevBuf<uint32_t> d_band_vals;      // (one capacity)
+	DevBuf<char> d_band_tmp;
+	Graveyard<HipMemOps> graveyard;    // buffers outgrown while launches were in flight: freed when the call ends (flush_graveyard)
 	twk_hip_timing timing{};
 	std::vector<twk_hip_launch_stat> launch_ring; uint64_t launches_seen = 0;      // the outlier watch's log (twk_hip_launch_log): the last LAUNCH_RING count launches
 	twk_hip_progress_cb progress_cb = nullptr; void* progress_user = nullptr;
 	bool progress_muted = false;       // second stage of a default-mode run: its pairs were already counted
 	uint32_t resident_blocks = 512;   // count-kernel blocks the chip holds at once (2 per CU)
-	uint32_t* tickets = nullptr;      // [2 * (PIPE_SLOTS + 1)][8] work tickets of the count launches: one set of queues per (slot, launch)
+	DevBuf<uint32_t> tickets;         // [2 * (PIPE_SLOTS + 1)][8] work tickets of the count launches: one set of queues per (slot, launch)
 	// staging of twk_hip_upload_rle (grow-only): run bytes, descriptors, status word
-	uint8_t* d_rle = nullptr; size_t d_rle_cap = 0;
-	uint8_t* d_rle_desc = nullptr; size_t d_rle_desc_cap = 0;
-	int* d_status = nullptr;
-	uint32_t* d_col_hi = nullptr; size_t d_col_hi_cap = 0;   // r2 screen: per-row column limit of the current region
+	DevBuf<uint8_t> d_rle, d_rle_desc;
+	DevBuf<int> d_status;
+	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
 	// twk_hip_ld_score: the launches of the running call sum r2 per variant (ld_score.hip.h) instead of keeping records
 	bool score_on = false;
-	double* d_score_sum = nullptr; unsigned long long* d_score_n = nullptr;      // [M] accumulators, variant ids in file order
+	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
 	char err[512] = {0};
 };
 
 namespace {
+
+struct Event {                     // a local event, destroyed on every way out
+	hipEvent_t e = nullptr;
+	~Event() { if (e) (void)hipEventDestroy(e); }
+};
 
 #define HIPCHK(ctx, call)                                                                         \
 	do {                                                                                          \
@@ -286,45 +302,25 @@ namespace {
 		}                                                                                         \
 	} while (0)
 
-void free_plane_set(PlaneSet& p) {
-	if (p.owns_rows && p.rows) (void)hipFree(p.rows);
-	void* ptrs[] = {p.rowpop, p.ids, p.lists, p.list_mac, p.list_flip, p.terms};
-	for (void* q : ptrs) if (q) (void)hipFree(q);
-	p = PlaneSet();
-}
 void free_planes(twk_hip_ctx* c) {
 	c->h_popc.clear();
 	c->sorted_keeps_no_lists[0] = c->sorted_keeps_no_lists[1] = false;
-	for (auto& p : c->planes) free_plane_set(p);
+	for (auto& p : c->planes) p = PlaneSet();
 }
+// (the slots' counters and the work tickets live as long as the context)
 void free_slots(twk_hip_ctx* c) {
 	for (auto& s : c->slot) {
-		if (s.C) (void)hipFree(s.C);
-		if (s.out) (void)hipFree(s.out);
-		if (s.keys) (void)hipFree(s.keys);
-		if (s.vals) (void)hipFree(s.vals);
-		if (s.sorted) (void)hipFree(s.sorted);
-		s.C = nullptr; s.C_words = 0; s.out = nullptr; s.keys = nullptr; s.vals = nullptr; s.capacity = 0; s.sorted = nullptr; s.sorted_cap = 0;
-		if (s.sc_sum) (void)hipFree(s.sc_sum);
-		if (s.sc_n) (void)hipFree(s.sc_n);
-		if (s.h_sc_args) (void)hipHostFree(s.h_sc_args);
-		if (s.d_sc_args) (void)hipFree(s.d_sc_args);
-		s.sc_sum = nullptr; s.sc_n = nullptr; s.sc_cap = 0; s.h_sc_args = nullptr; s.d_sc_args = nullptr;
-		for (int k = 0; k < 2; ++k) {
-			if (s.h_tiles[k]) (void)hipHostFree(s.h_tiles[k]);
-			if (s.d_tiles[k]) (void)hipFree(s.d_tiles[k]);
-			s.h_tiles[k] = s.d_tiles[k] = nullptr; s.tiles_cap[k] = 0;
-		}
+		s.C.reset(); s.out.reset(); s.keys.reset(); s.vals.reset(); s.sorted.reset();
+		s.sc_sum.reset(); s.sc_n.reset(); s.h_sc_args.reset(); s.d_sc_args.reset();
+		for (int k = 0; k < 2; ++k) { s.h_tiles[k].reset(); s.d_tiles[k].reset(); }
 	}
 }
 void free_problem(twk_hip_ctx* c) {
 	free_planes(c);
 	free_slots(c);
-	void* ptrs[] = {c->raw, c->rawmask, c->d_ac, c->d_an, c->d_pos, c->d_rid, c->d_missing, c->d_hwe, c->d_lfact, c->d_score_sum, c->d_score_n};
-	for (void* p : ptrs) if (p) (void)hipFree(p);
-	c->d_score_sum = nullptr; c->d_score_n = nullptr;
-	c->raw = c->rawmask = nullptr; c->d_lfact = nullptr; c->lfact_n = 0;
-	c->d_ac = c->d_an = c->d_pos = c->d_rid = c->d_missing = nullptr; c->d_hwe = nullptr;
+	c->raw.reset(); c->rawmask.reset(); c->d_lfact.reset(); c->lfact_n = 0;
+	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
+	c->d_score_sum.reset(); c->d_score_n.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -339,22 +335,20 @@ int plane_kind_for(const twk_hip_ctx* c, bool phased) {
 // disagrees with its genotypes must not lose records to the screen).
 int ensure_popcounts(twk_hip_ctx* c) {
 	if (c->h_popc.size() == c->M) return TWK_HIP_OK;
-	uint32_t* d = nullptr;
-	HIPCHK(c, hipMalloc((void**)&d, (size_t)c->M * 4));
+	DevBuf<uint32_t> d;
+	HIPCHK(c, d.reserve(c->M, c->M, nullptr));
 	hipLaunchKernelGGL(k_row_popcount, dim3((c->M + 3) / 4), dim3(256), 0, c->s_compute, c->raw, c->Wp, c->M, d);
 	hipError_t e = hipGetLastError();
 	c->h_popc.assign(c->M, 0);
 	if (e == hipSuccess) e = hipMemcpyAsync(c->h_popc.data(), d, (size_t)c->M * 4, hipMemcpyDeviceToHost, c->s_compute);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-	(void)hipFree(d);
 	if (e != hipSuccess) c->h_popc.clear();
 	HIPCHK(c, e);
 	return TWK_HIP_OK;
 }
 
-int ensure_planes(twk_hip_ctx* c, int set) {
+int build_planes(twk_hip_ctx* c, int set) {
 	PlaneSet& ps = c->planes[set];
-	if (ps.built) return TWK_HIP_OK;
 	const int kind = set_kind(set);
 	const int P = planes_per_variant(kind);
 	const bool wide = (kind == PK_PHASED || kind == PK_PHASED_MASKED);
@@ -380,14 +374,14 @@ int ensure_planes(twk_hip_ctx* c, int set) {
 		for (uint32_t v = 0; v < c->M; ++v) if (key(ps.h_ids[v]) != ~0ull) ++ps.n_front;
 	}
 	if (kind == PK_PHASED && !sorted) {
-		ps.rows = c->raw; ps.owns_rows = false;       // the raw layout *is* the phased plane
+		ps.rows = c->raw;                             // the raw layout *is* the phased plane
 	} else {
-		const size_t bytes = (size_t)ps.rows_alloc * ps.W * 4;
-		HIPCHK(c, hipMalloc((void**)&ps.rows, bytes));
-		ps.owns_rows = true;
-		HIPCHK(c, hipMemsetAsync(ps.rows, 0, bytes, c->s_compute));
+		const size_t words = (size_t)ps.rows_alloc * ps.W;
+		HIPCHK(c, ps.own_rows.reserve(words, words, nullptr));
+		ps.rows = ps.own_rows;
+		HIPCHK(c, hipMemsetAsync(ps.rows, 0, words * 4, c->s_compute));
 		if (sorted) {
-			HIPCHK(c, hipMalloc((void**)&ps.ids, (size_t)c->M * 4));
+			HIPCHK(c, ps.ids.reserve(c->M, c->M, nullptr));
 			HIPCHK(c, hipMemcpyAsync(ps.ids, ps.h_ids.data(), (size_t)c->M * 4, hipMemcpyHostToDevice, c->s_compute));
 		}
 		if (set == PS_GROUPED) {
@@ -395,7 +389,7 @@ int ensure_planes(twk_hip_ctx* c, int set) {
 			for (uint32_t v = 0; v < c->M; ++v) if (c->h_meta[v].an) ps.h_ids.push_back(v);
 			ps.n_front = (uint32_t)ps.h_ids.size();
 			for (uint32_t v = 0; v < c->M; ++v) if (!c->h_meta[v].an) ps.h_ids.push_back(v);
-			HIPCHK(c, hipMalloc((void**)&ps.ids, (size_t)c->M * 4));
+			HIPCHK(c, ps.ids.reserve(c->M, c->M, nullptr));
 			HIPCHK(c, hipMemcpyAsync(ps.ids, ps.h_ids.data(), (size_t)c->M * 4, hipMemcpyHostToDevice, c->s_compute));
 		}
 		const dim3 blk(256), grd((ps.W + 255) / 256, std::min<uint32_t>(c->M, 65535u));
@@ -409,7 +403,7 @@ int ensure_planes(twk_hip_ctx* c, int set) {
 			                   c->Wp, c->N, c->M, ps.rows, ps.W, P, (const uint32_t*)ps.ids);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipMalloc((void**)&ps.rowpop, (size_t)ps.rows_alloc * 4));
+	HIPCHK(c, ps.rowpop.reserve(ps.rows_alloc, ps.rows_alloc, nullptr));
 	HIPCHK(c, hipMemsetAsync(ps.rowpop, 0, (size_t)ps.rows_alloc * 4, c->s_compute));
 	const uint32_t live_rows = c->M * P;
 	hipLaunchKernelGGL(k_row_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, ps.rows, ps.W, live_rows, ps.rowpop);
@@ -449,9 +443,9 @@ int ensure_planes(twk_hip_ctx* c, int set) {
 					++np;
 				}
 				ps.n_probe = np / TILE * TILE;
-				HIPCHK(c, hipMalloc((void**)&ps.lists, (size_t)n * (lmax + 1) * 4));
-				HIPCHK(c, hipMalloc((void**)&ps.list_mac, (size_t)n * 4));
-				HIPCHK(c, hipMalloc((void**)&ps.list_flip, (size_t)n * 4));
+				HIPCHK(c, ps.lists.reserve((size_t)n * (lmax + 1), (size_t)n * (lmax + 1), nullptr));
+				HIPCHK(c, ps.list_mac.reserve(n, n, nullptr));
+				HIPCHK(c, ps.list_flip.reserve(n, n, nullptr));
 				if (set == PS_SORTED_P)
 					hipLaunchKernelGGL(k_build_lists, dim3((n + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, (uint64_t)T2,
 					                   (const uint32_t*)ps.rowpop, n, lmax + 1, ps.lists, ps.list_mac, ps.list_flip);
@@ -466,34 +460,18 @@ int ensure_planes(twk_hip_ctx* c, int set) {
 	ps.built = true;
 	return TWK_HIP_OK;
 }
-
-// (Outgrown buffers go to the graveyard - freed when the region call ends, or with the context: hipFree waits for the whole device,
-// every stream, and in the middle of a region's pipeline that was a stall of 50-250 ms a time: profiles/r05_delivery_thread.txt.)
-// hipMalloc for the buffers of a running call: out of memory -> what the delivery queue holds idle and what the call has outgrown is
-// given back (reclaim_device_memory, below) and the allocation tried once more, before the call fails.
-bool reclaim_device_memory(twk_hip_ctx* c);
-hipError_t dev_malloc(twk_hip_ctx* c, void** p, size_t bytes) {
-	hipError_t e = hipMalloc(p, bytes);
-	if (e == hipErrorOutOfMemory && reclaim_device_memory(c)) e = hipMalloc(p, bytes);
-	return e;
+// (a set whose build failed is left empty, not half-built)
+int ensure_planes(twk_hip_ctx* c, int set) {
+	if (c->planes[set].built) return TWK_HIP_OK;
+	const int rc = build_planes(c, set);
+	if (rc) c->planes[set] = PlaneSet();
+	return rc;
 }
+
+// C_words words of count matrix / candidate list and `capacity` survivors for the slot's next launch.
 int ensure_slot(twk_hip_ctx* c, Slot& s, size_t C_words, unsigned long long capacity) {
-	if (s.C_words < C_words) {
-		if (s.C) c->graveyard.push_back(s.C);
-		s.C = nullptr; s.C_words = 0;
-		HIPCHK(c, dev_malloc(c, (void**)&s.C, C_words * 4));
-		s.C_words = C_words;
-	}
-	if (s.capacity < capacity) {
-		if (s.out) c->graveyard.push_back(s.out);
-		if (s.keys) c->graveyard.push_back(s.keys);
-		if (s.vals) c->graveyard.push_back(s.vals);
-		s.out = nullptr; s.keys = nullptr; s.vals = nullptr; s.capacity = 0;
-		HIPCHK(c, dev_malloc(c, (void**)&s.out, (size_t)capacity * sizeof(twk_hip_record)));
-		HIPCHK(c, dev_malloc(c, (void**)&s.keys, (size_t)capacity * sizeof(unsigned long long)));
-		HIPCHK(c, dev_malloc(c, (void**)&s.vals, (size_t)capacity * sizeof(uint32_t)));
-		s.capacity = capacity;
-	}
+	HIPCHK(c, s.C.reserve(C_words, C_words, &c->graveyard));
+	HIPCHK(c, reserve_together(capacity, capacity, &c->graveyard, s.out, s.keys, s.vals));
 	s.cap_use = capacity;
 	return TWK_HIP_OK;
 }
@@ -510,12 +488,7 @@ int ensure_slot(twk_hip_ctx* c, Slot& s, size_t C_words, unsigned long long capa
 
 int ensure_host_records(twk_hip_ctx* c, unsigned long long n, char* err = nullptr, size_t err_len = 0) {
 	if (!err) { err = c->err; err_len = sizeof(c->err); }
-	if (c->h_recs_cap >= n) return TWK_HIP_OK;
-	if (c->h_recs) (void)hipHostFree(c->h_recs);
-	c->h_recs = nullptr; c->h_recs_cap = 0;
-	const unsigned long long cap = std::max<unsigned long long>(n, 1ull << 16);
-	HIPCHK_E(err, err_len, hipHostMalloc((void**)&c->h_recs, (size_t)cap * sizeof(twk_hip_record), hipHostMallocDefault));
-	c->h_recs_cap = cap;
+	HIPCHK_E(err, err_len, c->h_recs.reserve(n, std::max<unsigned long long>(n, 1ull << 16), nullptr));      // (freed at once: also called on the delivery thread)
 	return TWK_HIP_OK;
 }
 
@@ -638,15 +611,8 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	const size_t T4 = (T + 3) / 4 * 4, words_units = T4 + units.size() * 4;       // [tiles | pad | units], units 16-byte aligned
 	const size_t fa_words = (sizeof(FusedArgs) + 15) / 16 * 4;
 	const size_t words = words_units + (with_args ? fa_words : 0);               // [... | FusedArgs] for a fused or three-product launch
-	if (s.tiles_cap[which] < words) {
-		if (s.h_tiles[which]) c->host_graveyard.push_back(s.h_tiles[which]);      // (the device copy of the previous launch's table may still be travelling)
-		if (s.d_tiles[which]) c->graveyard.push_back(s.d_tiles[which]);
-		s.h_tiles[which] = s.d_tiles[which] = nullptr; s.tiles_cap[which] = 0;
-		const size_t cap = std::max<size_t>(words, 16384);
-		HIPCHK(c, hipHostMalloc((void**)&s.h_tiles[which], cap * 4, hipHostMallocDefault));
-		HIPCHK(c, hipMalloc((void**)&s.d_tiles[which], cap * 4));
-		s.tiles_cap[which] = cap;
-	}
+	// (parked, the pinned one too: the device copy of the previous launch's table may still be travelling)
+	HIPCHK(c, reserve_together(words, std::max<size_t>(words, 16384), &c->graveyard, s.h_tiles[which], s.d_tiles[which]));
 	if (T) {
 		std::memcpy(s.h_tiles[which], list.data(), T * 4);
 		std::memcpy(s.h_tiles[which] + T4, units.data(), units.size() * sizeof(CountUnit));
@@ -759,7 +725,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 	const bool ordered = c->opt.fisher_order != 0, lds_ok = c->opt.fisher_lds != 0;
 	const bool lds_table = lds_ok && c->lfact_n <= FISHER_LDS_TABLE_MAX;
 	const size_t lds_bytes = lds_table ? (size_t)c->lfact_n * sizeof(double) : 0;
-	if (!c->d_fisher_bins) HIPCHK(c, hipMalloc((void**)&c->d_fisher_bins, 2 * FISHER_BINS * sizeof(uint32_t)));
+	HIPCHK(c, c->d_fisher_bins.reserve(2 * FISHER_BINS, 2 * FISHER_BINS, nullptr));
 	const unsigned long long limit = (ordered && scratch && scratch_words >= 4096) ? std::min<unsigned long long>(scratch_words, 0xFFFFFFFFull) : 0;
 	HIPCHK(c, hipMemsetAsync(c->d_fisher_bins, 0, 2 * FISHER_BINS * sizeof(uint32_t), c->s_compute));
 	if (lds_table) hipLaunchKernelGGL(k_fisher_prepare<true>, dim3(c->resident_blocks), dim3(1024), lds_bytes, c->s_compute, recs, (const unsigned long long*)n_out, cap, lf, limit, c->d_fisher_bins);
@@ -824,20 +790,13 @@ int launch_score(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
 	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
 	if (!t.nA || !t.nB) return TWK_HIP_OK;
-	if (!s.h_sc_args) HIPCHK(c, hipHostMalloc((void**)&s.h_sc_args, 2 * sizeof(ScoreArgs), hipHostMallocDefault));
-	if (!s.d_sc_args) HIPCHK(c, hipMalloc((void**)&s.d_sc_args, 2 * sizeof(ScoreArgs)));
+	HIPCHK(c, s.h_sc_args.reserve(2, 2, nullptr));
+	HIPCHK(c, s.d_sc_args.reserve(2, 2, nullptr));
 	ScoreParts sp{};
 	sp.gx = (t.nB + SCORE_THREADS - 1) / SCORE_THREADS; sp.gy = (t.nA + SCORE_ROWS - 1) / SCORE_ROWS;
 	if (sp.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
 	const size_t n_row = (size_t)t.nA * sp.gx, n_col = (size_t)sp.gy * t.nB, need = n_row + n_col;
-	if (s.sc_cap < need) {
-		if (s.sc_sum) c->graveyard.push_back(s.sc_sum);
-		if (s.sc_n) c->graveyard.push_back(s.sc_n);
-		s.sc_sum = nullptr; s.sc_n = nullptr; s.sc_cap = 0;
-		HIPCHK(c, dev_malloc(c, (void**)&s.sc_sum, need * sizeof(double)));
-		HIPCHK(c, dev_malloc(c, (void**)&s.sc_n, need * sizeof(uint32_t)));
-		s.sc_cap = need;
-	}
+	HIPCHK(c, reserve_together(need, need, &c->graveyard, s.sc_sum, s.sc_n));
 	sp.row_sum = s.sc_sum; sp.row_n = s.sc_n; sp.col_sum = s.sc_sum + n_row; sp.col_n = s.sc_n + n_row;
 	const uint32_t* ids = c->planes[set].ids;
 	s.h_sc_args[which].p = p; s.h_sc_args[which].sp = sp;      // (the slot's previous launch has been waited for: its copy is done)
@@ -865,18 +824,6 @@ __global__ void k_gather_records(const twk_hip_record* __restrict__ recs, const 
 	reinterpret_cast<unsigned long long*>(out)[i] = reinterpret_cast<const unsigned long long*>(recs + order[r])[w];
 }
 
-// Replace *p (cap items of `item` bytes) by a buffer of at least `need` items without waiting for the device: the old buffer goes to
-// the graveyard (freed when the call ends).  Contents are not kept.
-int regrow(twk_hip_ctx* c, void** p, unsigned long long* cap, unsigned long long need, size_t item) {
-	if (*cap >= need) return TWK_HIP_OK;
-	const unsigned long long want = need + need / 4;
-	void* q = nullptr;
-	HIPCHK(c, dev_malloc(c, &q, (size_t)want * item));
-	if (*p) c->graveyard.push_back(*p);
-	*p = q; *cap = want;
-	return TWK_HIP_OK;
-}
-
 // Every launch of a slot begins here: what the previous one left in the slot's per-launch state cannot reach it.
 Launch& begin_launch(Slot& s, int plane_set, double minP) {
 	s.l = Launch();
@@ -901,11 +848,11 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 // stream (finish_tile's sort_records) it waited for a CU until the *next* launch's persistent count kernel was through, 60 ms per launch
 // of the 2,504 x 531,500 run.
 int close_launch(twk_hip_ctx* c, Slot& s) {
-	if (!s.l.form.score) { const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, s.l.minP, s.C, s.C_words, s.keys); if (rc) return rc; }
+	if (!s.l.form.score) { const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, s.l.minP, s.C, s.C.capacity(), s.keys); if (rc) return rc; }
 	if (s.l.presorted) {
 		const unsigned long long need = s.cap_use;
-		size_t bytes = c->band_tmp_bytes;
-		HIPCHK(c, rocprim::radix_sort_pairs(c->d_band_tmp, bytes, s.keys, c->d_band_keys, s.vals, c->d_band_vals, (size_t)need, 0u, 64u, c->s_compute));
+		size_t bytes = c->d_band_tmp.capacity();
+		HIPCHK(c, rocprim::radix_sort_pairs(c->d_band_tmp.get(), bytes, s.keys.get(), c->d_band_keys.get(), s.vals.get(), c->d_band_vals.get(), (size_t)need, 0u, 64u, c->s_compute));
 		const unsigned long long words = need * (sizeof(twk_hip_record) / 8);
 		hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, (const twk_hip_record*)s.out, (const uint32_t*)c->d_band_vals, need, s.sorted);
 		HIPCHK(c, hipGetLastError());
@@ -935,14 +882,14 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	Launch& l = begin_launch(s, kind1, f.minP);
 	l.form = form;
 	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
-	l.cand = s.C; l.cand_cap = (list_words ? list_words : s.C_words) / (form.unphased ? 6 : 3);
+	l.cand = s.C; l.cand_cap = (list_words ? list_words : s.C.capacity()) / (form.unphased ? 6 : 3);
 	// The three-product form where the launch does not fuse (long rows: tiles are split along K): the (HH, S) matrix takes the first half of the
 	// slot's count buffer and the candidate list the room behind it - at most 1/128 of the tile's pairs: a candidate's recount streams its four
 	// rows once more, ~25 pairs' worth of contraction, so a launch with more candidates than that is cheaper in the four-product form
 	// (overflow -> three_ok = false -> redone).
 	if (form.three_plain()) {
 		const size_t c2_words = (size_t)(g.rowsA / 2) * g.rowsB;
-		const unsigned long long room = s.C_words > c2_words ? (s.C_words - c2_words) / 6 : 0;
+		const unsigned long long room = s.C.capacity() > c2_words ? (s.C.capacity() - c2_words) / 6 : 0;
 		const unsigned long long pairs = (unsigned long long)t.nA * t.nB;
 		l.cand = s.C + c2_words;
 		l.cand_cap = std::min<unsigned long long>(room, form.keep_three ? room : std::max<unsigned long long>(pairs / 128, 4096));
@@ -956,7 +903,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		sw.cut = f.minR2 * (1.0 - 1e-6); sw.two_n = 2.0 * (double)c->N;
 		if (form.fused && (!ps.terms || ps.terms_cut != sw.cut)) {      // the prefilter's per-variant terms: once per plane set and cut-off, on the stream the kernels follow
 			const uint32_t P1 = (uint32_t)planes_per_variant(set_kind(kind1)), n_pos = ps.rows_alloc / P1;
-			if (!ps.terms) HIPCHK(c, hipMalloc((void**)&ps.terms, (size_t)n_pos * sizeof(float4)));
+			HIPCHK(c, ps.terms.reserve(n_pos, n_pos, nullptr));
 			hipLaunchKernelGGL(k_screen_terms, dim3((n_pos + 255) / 256), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rowpop, n_pos, (int)P1, sw.two_n, sw.cut, ps.terms);
 			HIPCHK(c, hipGetLastError());
 			ps.terms_cut = sw.cut;
@@ -1034,27 +981,14 @@ int enqueue_band_math(twk_hip_ctx* c, Slot& s) {
 	unsigned long long need = overflow ? 1 : std::max<unsigned long long>(cand, 1);
 	if (c->opt.record_cap > 0) need = std::min<unsigned long long>(need, (unsigned long long)c->opt.record_cap);      // (test hook: forces the overflow path)
 	auto grow_all = [&]() -> int {
-		if (s.capacity < need) {       // (with some room: the next launch of the region will be about as rich)
-			unsigned long long c1 = s.capacity, c2 = s.capacity, c3 = s.capacity;
-			int rc = regrow(c, (void**)&s.out, &c1, need, sizeof(twk_hip_record)); if (rc) return rc;
-			rc = regrow(c, (void**)&s.keys, &c2, need, sizeof(unsigned long long)); if (rc) return rc;
-			rc = regrow(c, (void**)&s.vals, &c3, need, sizeof(uint32_t)); if (rc) return rc;
-			s.capacity = std::min(c1, std::min(c2, c3));
-		}
-		{ const int rc = regrow(c, (void**)&s.sorted, &s.sorted_cap, need, sizeof(twk_hip_record)); if (rc) return rc; }
-		if (c->band_sort_cap < need) {
-			unsigned long long c1 = c->band_sort_cap, c2 = c->band_sort_cap;
-			int rc = regrow(c, (void**)&c->d_band_keys, &c1, need, sizeof(unsigned long long)); if (rc) return rc;
-			rc = regrow(c, (void**)&c->d_band_vals, &c2, need, sizeof(uint32_t)); if (rc) return rc;
-			c->band_sort_cap = std::min(c1, c2);
-		}
+		const size_t roomy = (size_t)(need + need / 4);      // (with some room: the next launch of the region will be about as rich)
+		HIPCHK(c, reserve_together(need, roomy, &c->graveyard, s.out, s.keys, s.vals));
+		HIPCHK(c, s.sorted.reserve(need, roomy, &c->graveyard));
+		HIPCHK(c, reserve_together(need, roomy, &c->graveyard, c->d_band_keys, c->d_band_vals));
 		size_t tmp = 0;
-		HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp, s.keys, c->d_band_keys, s.vals, c->d_band_vals, (size_t)need, 0u, 64u, c->s_compute));
-		if (!c->d_band_tmp || tmp > c->band_tmp_bytes) {
-			unsigned long long cap = c->band_tmp_bytes;
-			const int rc = regrow(c, &c->d_band_tmp, &cap, std::max<size_t>(tmp, 4096), 1); if (rc) return rc;
-			c->band_tmp_bytes = (size_t)cap;
-		}
+		HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp, s.keys.get(), c->d_band_keys.get(), s.vals.get(), c->d_band_vals.get(), (size_t)need, 0u, 64u, c->s_compute));
+		tmp = std::max<size_t>(tmp, 4096);                   // (never empty: a null scratch pointer would turn the sort into another size query)
+		HIPCHK(c, c->d_band_tmp.reserve(tmp, tmp + tmp / 4, &c->graveyard));
 		return TWK_HIP_OK;
 	};
 	{
@@ -1088,17 +1022,7 @@ static_assert(sizeof(twk_hip_record) % 8 == 0, "record gather copies 8-byte word
 // recs[0..n) on the device, with their keys and positions -> c->d_sorted in (idxA, idxB) order, on stream st.
 int sort_records(twk_hip_ctx* c, const twk_hip_record* recs, unsigned long long* keys_in, uint32_t* vals_in, unsigned long long n, bool any_dropped, hipStream_t st) {
 	if (n > 0xFFFFFFFFull) return TWK_HIP_E_INVALID;
-	if (c->sort_cap < n) {
-		if (c->d_sort_keys) c->graveyard.push_back(c->d_sort_keys);       // (not hipFree: it waits for every stream of the device)
-		if (c->d_sort_vals) c->graveyard.push_back(c->d_sort_vals);
-		if (c->d_sorted) c->graveyard.push_back(c->d_sorted);
-		c->d_sort_keys = nullptr; c->d_sort_vals = nullptr; c->d_sorted = nullptr; c->sort_cap = 0;
-		const unsigned long long cap = std::max<unsigned long long>(n + n / 4, 1ull << 16);
-		HIPCHK(c, dev_malloc(c, (void**)&c->d_sort_keys, (size_t)cap * sizeof(unsigned long long)));
-		HIPCHK(c, dev_malloc(c, (void**)&c->d_sort_vals, (size_t)cap * sizeof(uint32_t)));
-		HIPCHK(c, dev_malloc(c, (void**)&c->d_sorted, (size_t)cap * sizeof(twk_hip_record)));
-		c->sort_cap = cap;
-	}
+	HIPCHK(c, reserve_together(n, std::max<unsigned long long>(n + n / 4, 1ull << 16), &c->graveyard, c->d_sort_keys, c->d_sort_vals, c->d_sorted));
 	unsigned long long* keys_out = c->d_sort_keys;
 	uint32_t* vals_out = c->d_sort_vals;
 	const uint32_t bits_b = key_shift_for(c->M);
@@ -1107,15 +1031,9 @@ int sort_records(twk_hip_ctx* c, const twk_hip_record* recs, unsigned long long*
 	const unsigned end_bit = any_dropped ? 64u : 2u * bits_b;
 	size_t tmp = 0;
 	HIPCHK(c, rocprim::radix_sort_pairs(nullptr, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, end_bit, st));
-	if (!c->d_sort_tmp || tmp > c->sort_tmp_bytes) {          // (a null scratch pointer would turn the sort into another size query)
-		if (c->d_sort_tmp) c->graveyard.push_back(c->d_sort_tmp);
-		c->d_sort_tmp = nullptr; c->sort_tmp_bytes = 0;
-		const size_t want = std::max<size_t>(tmp + tmp / 4, 4096);
-		HIPCHK(c, dev_malloc(c, &c->d_sort_tmp, want));
-		c->sort_tmp_bytes = want;
-	}
-	tmp = c->sort_tmp_bytes;
-	HIPCHK(c, rocprim::radix_sort_pairs(c->d_sort_tmp, tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, end_bit, st));
+	HIPCHK(c, c->d_sort_tmp.reserve(std::max<size_t>(tmp, 1), std::max<size_t>(tmp + tmp / 4, 4096), &c->graveyard));      // (never empty: a null scratch pointer would turn the sort into another size query)
+	tmp = c->d_sort_tmp.capacity();
+	HIPCHK(c, rocprim::radix_sort_pairs(c->d_sort_tmp.get(), tmp, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0u, end_bit, st));
 	const unsigned long long words = n * (sizeof(twk_hip_record) / 8);
 	hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, recs, vals_out, n, c->d_sorted);
 	HIPCHK(c, hipGetLastError());
@@ -1125,17 +1043,14 @@ int sort_records(twk_hip_ctx* c, const twk_hip_record* recs, unsigned long long*
 // Room for n more records behind the ones the device sink holds (grow-only, contents kept).
 int ensure_device_keep(twk_hip_ctx* c, unsigned long long n_more) {
 	const unsigned long long need = c->d_keep_n + n_more;
-	if (need <= c->d_keep_cap) return TWK_HIP_OK;
-	const unsigned long long cap = std::max<unsigned long long>(need + need / 2, 1ull << 16);
-	twk_hip_record* p = nullptr;
-	HIPCHK(c, dev_malloc(c, (void**)&p, (size_t)cap * sizeof(twk_hip_record)));
+	if (need <= c->d_keep.capacity()) return TWK_HIP_OK;
+	DevBuf<twk_hip_record> p;
+	HIPCHK(c, p.reserve(need, std::max<unsigned long long>(need + need / 2, 1ull << 16), &c->graveyard));      // (the graveyard: for its reclaim - p has nothing to park)
 	if (c->d_keep_n) {
-		const hipError_t e = hipMemcpyAsync(p, c->d_keep, (size_t)c->d_keep_n * sizeof(twk_hip_record), hipMemcpyDeviceToDevice, c->s_copy);
-		if (e != hipSuccess) { (void)hipFree(p); HIPCHK(c, e); }
+		HIPCHK(c, hipMemcpyAsync(p, c->d_keep, (size_t)c->d_keep_n * sizeof(twk_hip_record), hipMemcpyDeviceToDevice, c->s_copy));
 		HIPCHK(c, hipStreamSynchronize(c->s_copy));
 	}
-	if (c->d_keep) (void)hipFree(c->d_keep);
-	c->d_keep = p; c->d_keep_cap = cap;
+	c->d_keep = std::move(p);
 	return TWK_HIP_OK;
 }
 
@@ -1243,15 +1158,15 @@ int stage_for_delivery(twk_hip_ctx* c, const twk_hip_record* sorted, unsigned lo
 	}
 	return rc;
 }
-// The calling thread is out of device memory (ensure_slot, regrow, sort_records): everything queued goes to the sink, the idle staging
+// The calling thread is out of device memory (the graveyard's reclaim: twk_buffers.h): everything queued goes to the sink, the idle staging
 // buffers and what the call has outgrown so far are freed -> true when anything was given back (the allocation is then tried once more).
 bool reclaim_device_memory(twk_hip_ctx* c) {
 	(void)hipGetLastError();
 	size_t bytes = c->dl.active() ? c->dl.reclaim() : 0;
 	if (!c->graveyard.empty()) {
 		(void)hipDeviceSynchronize();            // (outgrown buffers may still be read by launches in flight)
-		for (void* p : c->graveyard) { (void)hipFree(p); ++bytes; }
-		c->graveyard.clear();
+		c->graveyard.flush();
+		++bytes;
 	}
 	return bytes != 0;
 }
@@ -1358,9 +1273,9 @@ int begin_list_launch(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, b
 	Slot& s = c->slot[SYNC_SLOT];
 	const unsigned cand_words = unphased ? 6 : 3;              // (A, B, ALTALT) or (A, B, HH, HQ, QH, QQ)
 	int rc = ensure_slot(c, s, (size_t)std::max<uint64_t>(cand_words * (uint64_t)t.nA * t.nB, 1024), capacity); if (rc) return rc;
-	if (!c->d_list_stats) HIPCHK(c, hipMalloc((void**)&c->d_list_stats, sizeof(StatsParams)));
+	HIPCHK(c, c->d_list_stats.reserve(1, 1, nullptr));
 	Launch& l = begin_launch(s, set, f.minP);
-	l.is_list = true; l.is_probe = probe; l.form.unphased = unphased; l.cand = s.C; l.cand_cap = s.C_words / cand_words;
+	l.is_list = true; l.is_probe = probe; l.form.unphased = unphased; l.cand = s.C; l.cand_cap = s.C.capacity() / cand_words;
 	const StatsParams sp = make_stats(c, set, t, s, !unphased, 0, f, &cr);
 	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
 	HIPCHK(c, hipMemcpyAsync(c->d_list_stats, &sp, sizeof(sp), hipMemcpyHostToDevice, c->s_compute));
@@ -1598,12 +1513,13 @@ int twk_hip_ctx_create(int device, twk_hip_ctx** out) {
 		if (hipStreamCreateWithPriority(&c->s_copy, hipStreamNonBlocking, hi) != hipSuccess) return fail(TWK_HIP_E_DEVICE);
 		if (hipStreamCreateWithPriority(&c->s_deliver, hipStreamNonBlocking, hi) != hipSuccess) return fail(TWK_HIP_E_DEVICE);
 	}
-	if (hipMalloc((void**)&c->tickets, 2 * (PIPE_SLOTS + 1) * 8 * sizeof(uint32_t)) != hipSuccess) return fail(TWK_HIP_E_NOMEM);
+	c->graveyard.reclaim = [c] { return reclaim_device_memory(c); };
+	if (c->tickets.reserve(2 * (PIPE_SLOTS + 1) * 8, 2 * (PIPE_SLOTS + 1) * 8, nullptr) != hipSuccess) return fail(TWK_HIP_E_NOMEM);
 	for (auto& s : c->slot) {
 		hipEvent_t* evs[] = {&s.ev_c0, &s.ev_c1, &s.ev_s1, &s.ev_c0b, &s.ev_c1b};
 		for (auto* e : evs) if (hipEventCreate(e) != hipSuccess) return fail(TWK_HIP_E_DEVICE);
-		if (hipMalloc((void**)&s.n_out, N_SLOT_COUNTERS * sizeof(unsigned long long)) != hipSuccess) return fail(TWK_HIP_E_NOMEM);
-		if (hipHostMalloc((void**)&s.h_n_out, N_SLOT_COUNTERS * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) return fail(TWK_HIP_E_NOMEM);
+		if (s.n_out.reserve(N_SLOT_COUNTERS, N_SLOT_COUNTERS, nullptr) != hipSuccess) return fail(TWK_HIP_E_NOMEM);
+		if (s.h_n_out.reserve(N_SLOT_COUNTERS, N_SLOT_COUNTERS, nullptr) != hipSuccess) return fail(TWK_HIP_E_NOMEM);
 		std::memset(s.h_n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long));
 	}
 	*out = c;
@@ -1614,33 +1530,11 @@ int twk_hip_ctx_destroy(twk_hip_ctx* c) {
 	if (!c) return TWK_HIP_OK;
 	(void)hipSetDevice(c->device);
 	(void)hipDeviceSynchronize();
-	free_problem(c);
+	(void)c->dl.end();                       // (before the buffers it may be copying from go)
 	for (auto& s : c->slot) {
 		hipEvent_t evs[] = {s.ev_c0, s.ev_c1, s.ev_s1, s.ev_c0b, s.ev_c1b};
 		for (auto e : evs) if (e) (void)hipEventDestroy(e);
-		if (s.n_out) (void)hipFree(s.n_out);
-		if (s.h_n_out) (void)hipHostFree(s.h_n_out);
 	}
-	if (c->h_recs) (void)hipHostFree(c->h_recs);
-	if (c->d_keep) (void)hipFree(c->d_keep);
-	if (c->d_list_stats) (void)hipFree(c->d_list_stats);
-	if (c->d_fisher_bins) (void)hipFree(c->d_fisher_bins);
-	if (c->d_sort_keys) (void)hipFree(c->d_sort_keys);
-	if (c->d_sort_vals) (void)hipFree(c->d_sort_vals);
-	if (c->d_sorted) (void)hipFree(c->d_sorted);
-	if (c->d_sort_tmp) (void)hipFree(c->d_sort_tmp);
-	if (c->d_band_keys) (void)hipFree(c->d_band_keys);
-	if (c->d_band_vals) (void)hipFree(c->d_band_vals);
-	if (c->d_band_tmp) (void)hipFree(c->d_band_tmp);
-	for (void* p : c->graveyard) (void)hipFree(p);
-	c->graveyard.clear();
-	for (void* p : c->host_graveyard) (void)hipHostFree(p);
-	c->host_graveyard.clear();
-	if (c->tickets) (void)hipFree(c->tickets);
-	if (c->d_rle) (void)hipFree(c->d_rle);
-	if (c->d_rle_desc) (void)hipFree(c->d_rle_desc);
-	if (c->d_status) (void)hipFree(c->d_status);
-	if (c->d_col_hi) (void)hipFree(c->d_col_hi);
 	if (c->s_compute) (void)hipStreamDestroy(c->s_compute);
 	if (c->s_copy) (void)hipStreamDestroy(c->s_copy);
 	if (c->s_deliver) (void)hipStreamDestroy(c->s_deliver);
@@ -1668,19 +1562,18 @@ int twk_hip_set_problem(twk_hip_ctx* c, uint32_t n_samples, uint32_t n_variants)
 	c->Wp = round_up((uint32_t)((2ull * n_samples + 31) / 32), KC);
 	c->Wu = round_up((n_samples + 31) / 32, KC);
 	const size_t raw_bytes = (size_t)c->M_alloc * c->Wp * 4;
-	HIPCHK(c, hipMalloc((void**)&c->raw, raw_bytes));
+	HIPCHK(c, c->raw.reserve(raw_bytes / 4, raw_bytes / 4, nullptr));
 	HIPCHK(c, hipMemset(c->raw, 0, raw_bytes));
 	const size_t m4 = (size_t)c->M_alloc * 4;
-	HIPCHK(c, hipMalloc((void**)&c->d_ac, m4)); HIPCHK(c, hipMalloc((void**)&c->d_an, m4));
-	HIPCHK(c, hipMalloc((void**)&c->d_pos, m4)); HIPCHK(c, hipMalloc((void**)&c->d_rid, m4));
-	HIPCHK(c, hipMalloc((void**)&c->d_missing, m4)); HIPCHK(c, hipMalloc((void**)&c->d_hwe, (size_t)c->M_alloc * 8));
+	for (DevBuf<uint32_t>* b : {&c->d_ac, &c->d_an, &c->d_pos, &c->d_rid, &c->d_missing}) HIPCHK(c, b->reserve(c->M_alloc, c->M_alloc, nullptr));
+	HIPCHK(c, c->d_hwe.reserve(c->M_alloc, c->M_alloc, nullptr));
 	HIPCHK(c, hipMemset(c->d_ac, 0, m4)); HIPCHK(c, hipMemset(c->d_an, 0, m4)); HIPCHK(c, hipMemset(c->d_pos, 0, m4));
 	HIPCHK(c, hipMemset(c->d_rid, 0, m4)); HIPCHK(c, hipMemset(c->d_missing, 0, m4)); HIPCHK(c, hipMemset(c->d_hwe, 0, (size_t)c->M_alloc * 8));
 	c->h_meta.assign(n_variants, twk_hip_variant_meta{});
 	c->timing.words_per_row = 0;
 	{	// every count Fisher's test sees is <= 2N (+ rounding of the unphased expected counts); beyond 2^26 entries lgamma itself is used
 		const unsigned long long want = std::min<unsigned long long>(2ull * n_samples + 16, 1ull << 26);
-		HIPCHK(c, hipMalloc((void**)&c->d_lfact, (size_t)want * sizeof(double)));
+		HIPCHK(c, c->d_lfact.reserve(want, want, nullptr));
 		c->lfact_n = (int)want;
 		hipLaunchKernelGGL(k_build_lfact, dim3((unsigned)((want + 255) / 256)), dim3(256), 0, c->s_compute, c->d_lfact, c->lfact_n);
 		HIPCHK(c, hipGetLastError());
@@ -1712,7 +1605,7 @@ int twk_hip_upload_bitvectors(twk_hip_ctx* c, uint32_t first, uint32_t count, co
 	if (mask) {
 		if (!c->rawmask) {
 			const size_t raw_bytes = (size_t)c->M_alloc * c->Wp * 4;
-			HIPCHK(c, hipMalloc((void**)&c->rawmask, raw_bytes));
+			HIPCHK(c, c->rawmask.reserve(raw_bytes / 4, raw_bytes / 4, nullptr));
 			HIPCHK(c, hipMemset(c->rawmask, 0, raw_bytes));
 		}
 		HIPCHK(c, hipMemcpy2D(c->rawmask + (size_t)first * c->Wp, (size_t)c->Wp * 4, mask, stride64 * 8, w64 * 8, count, hipMemcpyHostToDevice));
@@ -1750,26 +1643,18 @@ int twk_hip_upload_rle(twk_hip_ctx* c, uint32_t first, uint32_t count, const voi
 	chunk_base[count] = (uint32_t)n_chunks;
 	HIPCHK(c, hipSetDevice(c->device));
 	free_planes(c);                                             // derived planes are stale now
-	auto grow = [&](void** p, size_t* cap, size_t need) -> hipError_t {
-		if (*cap >= need) return hipSuccess;
-		if (*p) (void)hipFree(*p);
-		*p = nullptr; *cap = 0;
-		const size_t want = need + need / 4;
-		const hipError_t e = hipMalloc(p, want);
-		if (e == hipSuccess) *cap = want;
-		return e;
-	};
 	// descriptors | chunk sums (u64 per block) | first block of every variant
 	const size_t desc_bytes = (size_t)count * sizeof(RleDesc) + (size_t)n_chunks * 8 + ((size_t)count + 1) * 4;
-	HIPCHK(c, grow((void**)&c->d_rle, &c->d_rle_cap, n_bytes + 32));        // the kernel's dword loads run up to 19 bytes past the last run
-	HIPCHK(c, grow((void**)&c->d_rle_desc, &c->d_rle_desc_cap, desc_bytes));
-	if (!c->d_status) HIPCHK(c, hipMalloc((void**)&c->d_status, sizeof(int)));
+	const size_t run_bytes = n_bytes + 32;                                  // the kernel's dword loads run up to 19 bytes past the last run
+	HIPCHK(c, c->d_rle.reserve(run_bytes, run_bytes + run_bytes / 4, nullptr));
+	HIPCHK(c, c->d_rle_desc.reserve(desc_bytes, desc_bytes + desc_bytes / 4, nullptr));
+	HIPCHK(c, c->d_status.reserve(1, 1, nullptr));
 	if (any_mask && !c->rawmask) {
 		const size_t raw_bytes = (size_t)c->M_alloc * c->Wp * 4;
-		HIPCHK(c, hipMalloc((void**)&c->rawmask, raw_bytes));
+		HIPCHK(c, c->rawmask.reserve(raw_bytes / 4, raw_bytes / 4, nullptr));
 		HIPCHK(c, hipMemsetAsync(c->rawmask, 0, raw_bytes, c->s_compute));
 	}
-	RleDesc* d_desc = reinterpret_cast<RleDesc*>(c->d_rle_desc);
+	RleDesc* d_desc = reinterpret_cast<RleDesc*>(c->d_rle_desc.get());
 	unsigned long long* d_chunk_sum = reinterpret_cast<unsigned long long*>(c->d_rle_desc + (size_t)count * sizeof(RleDesc));
 	uint32_t* d_chunk_base = reinterpret_cast<uint32_t*>(c->d_rle_desc + (size_t)count * sizeof(RleDesc) + (size_t)n_chunks * 8);
 	HIPCHK(c, hipMemsetAsync(c->d_status, 0, sizeof(int), c->s_compute));
@@ -1828,7 +1713,7 @@ int twk_hip_generate_synthetic_planted(twk_hip_ctx* c, uint64_t seed, uint32_t f
 	if (!c->raw) return TWK_HIP_E_STATE;
 	HIPCHK(c, hipSetDevice(c->device));
 	free_planes(c);
-	if (c->rawmask) { (void)hipFree(c->rawmask); c->rawmask = nullptr; }
+	c->rawmask.reset();
 	c->any_missing = false;
 	hipLaunchKernelGGL(k_synth, dim3((c->Wp + 255) / 256, std::min<uint32_t>(c->M, 65535u)), dim3(256), 0, c->s_compute, c->raw, c->Wp, c->N, c->M, seed, first_variant, pl);
 	HIPCHK(c, hipGetLastError());
@@ -1909,15 +1794,12 @@ int twk_hip_get_marginals(twk_hip_ctx* c, uint32_t* ac, uint32_t* n_het, uint32_
 	return TWK_HIP_OK;
 }
 
-// Buffers outgrown during a call (regrow, ensure_slot, sort_records): freed once nothing is in flight any more.
+// Buffers outgrown during a call: freed once nothing is in flight any more.
 static void flush_graveyard(twk_hip_ctx* c) {
-	if (c->graveyard.empty() && c->host_graveyard.empty()) return;
+	if (c->graveyard.empty()) return;
 	(void)hipSetDevice(c->device);
 	(void)hipDeviceSynchronize();
-	for (void* p : c->graveyard) (void)hipFree(p);
-	c->graveyard.clear();
-	for (void* p : c->host_graveyard) (void)hipHostFree(p);
-	c->host_graveyard.clear();
+	c->graveyard.flush();
 }
 
 int twk_hip_count_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc* t, uint64_t* out) {
@@ -1935,14 +1817,13 @@ int twk_hip_count_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc* t, uin
 	rc = launch_count(c, kind, *t, s, 0, nullptr, LaunchForm(), nullptr); if (rc) return rc;
 	const int ncell = phased ? 4 : 9;
 	const size_t n = (size_t)t->nA * t->nB * ncell;
-	unsigned long long* d_cells = nullptr;
-	HIPCHK(c, hipMalloc((void**)&d_cells, n * 8));
+	DevBuf<unsigned long long> d_cells;
+	HIPCHK(c, d_cells.reserve(n, n, nullptr));
 	StatsParams p = make_stats(c, kind, *t, s, phased, 0, twk_hip_filters{});
 	hipLaunchKernelGGL(k_ld_cells, dim3((t->nB + 255) / 256, t->nA), dim3(256), 0, c->s_compute, p.tv, t->nA, t->nB, c->M, p.diag, phased ? 1 : 0, d_cells);
 	hipError_t e = hipGetLastError();
 	if (e == hipSuccess) e = hipMemcpyAsync(out, d_cells, n * 8, hipMemcpyDeviceToHost, c->s_compute);
 	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-	(void)hipFree(d_cells);
 	flush_graveyard(c);
 	HIPCHK(c, e);
 	return TWK_HIP_OK;
@@ -2008,12 +1889,7 @@ struct RegionRun {
 		if (c->opt.record_cap > 0) cap_default = std::min<unsigned long long>(cap_default, (unsigned long long)c->opt.record_cap);   // test hook: force the overflow / strip path
 		if (plan.windowed) { col_range.lo = plan.lo.data(); col_range.hi = plan.hi.data(); col_range.a0 = g.a0; col_range.b0 = g.b0; }
 		if (env.screen && g.nA) {
-			if (c->d_col_hi_cap < g.nA) {
-				if (c->d_col_hi) (void)hipFree(c->d_col_hi);
-				c->d_col_hi = nullptr; c->d_col_hi_cap = 0;
-				HIPCHK(c, hipMalloc((void**)&c->d_col_hi, (size_t)g.nA * 4));
-				c->d_col_hi_cap = g.nA;
-			}
+			HIPCHK(c, c->d_col_hi.reserve(g.nA, g.nA, nullptr));
 			HIPCHK(c, hipMemcpy(c->d_col_hi, plan.hi.data(), (size_t)g.nA * 4, hipMemcpyHostToDevice));
 			col_range.d_hi = c->d_col_hi; col_range.n_hi = g.nA;
 		}
@@ -2311,7 +2187,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 			if (c->planes[sset].n_list < 2) {
 				keep_sorted = false; known_useless = true;
 				HIPCHK(c, hipDeviceSynchronize());
-				free_plane_set(c->planes[sset]);
+				c->planes[sset] = PlaneSet();
 			}
 		}
 		if (keep_sorted) return region_impl(c, a.stage(mode == TWK_HIP_MODE_UNPHASED ? MODE_INT_SORTED_U : MODE_INT_SORTED_P, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records));
@@ -2372,8 +2248,8 @@ int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	if (!c->raw) return TWK_HIP_E_STATE;
 	HIPCHK(c, hipSetDevice(c->device));
 	const size_t M = c->M;
-	if (!c->d_score_sum) HIPCHK(c, hipMalloc((void**)&c->d_score_sum, M * sizeof(double)));
-	if (!c->d_score_n) HIPCHK(c, hipMalloc((void**)&c->d_score_n, M * sizeof(unsigned long long)));
+	HIPCHK(c, c->d_score_sum.reserve(M, M, nullptr));
+	HIPCHK(c, c->d_score_n.reserve(M, M, nullptr));
 	HIPCHK(c, hipMemsetAsync(c->d_score_sum, 0, M * sizeof(double), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(c->d_score_n, 0, M * sizeof(unsigned long long), c->s_compute));
 	struct ScoreOn { twk_hip_ctx* c; ~ScoreOn() { c->score_on = false; } } on{c};
@@ -2452,34 +2328,26 @@ int twk_hip_fisher_exact(twk_hip_ctx* c, const int32_t* tables, uint64_t n, doub
 	if (!c || !tables || !p_two_sided || n == 0 || n > (1ull << 28)) return TWK_HIP_E_INVALID;
 	if (!c->d_lfact) return TWK_HIP_E_STATE;
 	HIPCHK(c, hipSetDevice(c->device));
-	int32_t* d_t = nullptr; twk_hip_record* d_r = nullptr; double* d_p = nullptr; unsigned long long* d_n = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	auto cleanup = [&] {
-		if (d_t) (void)hipFree(d_t);
-		if (d_r) (void)hipFree(d_r);
-		if (d_p) (void)hipFree(d_p);
-		if (d_n) (void)hipFree(d_n);
-		if (e0) (void)hipEventDestroy(e0);
-		if (e1) (void)hipEventDestroy(e1);
-	};
-	hipError_t e = hipMalloc((void**)&d_t, (size_t)n * 16);
-	if (e == hipSuccess) e = hipMalloc((void**)&d_r, (size_t)n * sizeof(twk_hip_record));
-	if (e == hipSuccess) e = hipMalloc((void**)&d_p, (size_t)n * 8);
-	if (e == hipSuccess) e = hipMalloc((void**)&d_n, 4 * sizeof(unsigned long long));
-	if (e == hipSuccess) e = hipEventCreate(&e0);
-	if (e == hipSuccess) e = hipEventCreate(&e1);
+	DevBuf<int32_t> d_t; DevBuf<twk_hip_record> d_r; DevBuf<double> d_p; DevBuf<unsigned long long> d_n;
+	Event e0, e1;
+	hipError_t e = d_t.reserve((size_t)n * 4, (size_t)n * 4, nullptr);
+	if (e == hipSuccess) e = d_r.reserve(n, n, nullptr);
+	if (e == hipSuccess) e = d_p.reserve(n, n, nullptr);
+	if (e == hipSuccess) e = d_n.reserve(4, 4, nullptr);
+	if (e == hipSuccess) e = hipEventCreate(&e0.e);
+	if (e == hipSuccess) e = hipEventCreate(&e1.e);
 	const unsigned long long counters[4] = {n, 0, 0, 0};
 	if (e == hipSuccess) e = hipMemcpyAsync(d_t, tables, (size_t)n * 16, hipMemcpyHostToDevice, c->s_compute);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_n, counters, sizeof(counters), hipMemcpyHostToDevice, c->s_compute);
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(k_tables_to_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->s_compute, d_t, (unsigned long long)n, d_r);
-		e = hipEventRecord(e0, c->s_compute);
+		e = hipEventRecord(e0.e, c->s_compute);
 	}
 	if (e == hipSuccess) {
 		// as the engine runs it (walk-length order; the table buffer is free: the tables are in the records by now), or in the order given
-		const int rc = launch_fisher(c, d_r, d_n, (unsigned long long)n, 2.0, in_given_order ? nullptr : (uint32_t*)d_t, (size_t)n * 4);
-		if (rc) { cleanup(); return rc; }
-		e = hipEventRecord(e1, c->s_compute);
+		const int rc = launch_fisher(c, d_r, d_n, (unsigned long long)n, 2.0, in_given_order ? nullptr : (uint32_t*)d_t.get(), (size_t)n * 4);
+		if (rc) return rc;
+		e = hipEventRecord(e1.e, c->s_compute);
 	}
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(k_records_to_p, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->s_compute, d_r, (unsigned long long)n, d_p);
@@ -2487,8 +2355,7 @@ int twk_hip_fisher_exact(twk_hip_ctx* c, const int32_t* tables, uint64_t n, doub
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
 	if (e == hipSuccess) e = hipGetLastError();
-	if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, e0, e1);
-	cleanup();
+	if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, e0.e, e1.e);
 	HIPCHK(c, e);
 	return TWK_HIP_OK;
 }
@@ -2595,49 +2462,40 @@ int twk_hip_gather_records(twk_hip_ctx* const* ctxs, uint32_t n, uint32_t dst, i
 	off[dst] = 0; total = cnt[dst];
 	for (uint32_t r = 0; r < n; ++r) if (r != dst) { off[r] = total; total += cnt[r]; }
 	HIPCHK(d, hipSetDevice(d->device));
-	twk_hip_record* loop_buf = nullptr;
+	DevBuf<twk_hip_record> loop_buf;          // (freed on every way out, unless it became the sink)
 	if (loop) {          // one GPU: the same group of ncclSend / ncclRecv, from the sink to itself through a second buffer (what a one-GPU box can show of the path)
-		if (cnt[0]) HIPCHK(d, hipMalloc((void**)&loop_buf, (size_t)cnt[0] * sizeof(twk_hip_record)));
+		HIPCHK(d, loop_buf.reserve(cnt[0], cnt[0], nullptr));
 	} else {
 		const unsigned long long own = d->d_keep_n;
 		d->d_keep_n = own;
 		const int e = ensure_device_keep(d, total - own); if (e) return e;         // (keeps the destination's own records, at the front)
 	}
-	struct Events {          // (destroyed on every way out)
-		hipEvent_t e0 = nullptr, e1 = nullptr;
-		~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-	} ev;
-	hipEvent_t& e0 = ev.e0; hipEvent_t& e1 = ev.e1;
-	struct LoopBuf { twk_hip_record** p; ~LoopBuf() { if (*p) (void)hipFree(*p); } } loop_guard{&loop_buf};      // (freed unless it became the sink)
-	HIPCHK(d, hipEventCreate(&e0)); HIPCHK(d, hipEventCreate(&e1));
-	HIPCHK(d, hipEventRecord(e0, d->s_copy));
+	Event e0, e1;
+	HIPCHK(d, hipEventCreate(&e0.e)); HIPCHK(d, hipEventCreate(&e1.e));
+	HIPCHK(d, hipEventRecord(e0.e, d->s_copy));
 	int rcode = NCHK(rc.GroupStart(), "ncclGroupStart");
 	for (uint32_t r = 0; r < n && !rcode; ++r) {
 		if (!loop && r == dst) continue;
 		const size_t bytes = (size_t)cnt[r] * sizeof(twk_hip_record);
 		if (!bytes) continue;
 		if (hipSetDevice(ctxs[r]->device) != hipSuccess) { rcode = TWK_HIP_E_DEVICE; break; }
-		rcode = NCHK(rc.Send(ctxs[r]->d_keep, bytes, ncclUint8, (int)dst, comm[r], ctxs[r]->s_copy), "ncclSend");
+		rcode = NCHK(rc.Send(ctxs[r]->d_keep.get(), bytes, ncclUint8, (int)dst, comm[r], ctxs[r]->s_copy), "ncclSend");
 		if (rcode) break;
 		if (hipSetDevice(d->device) != hipSuccess) { rcode = TWK_HIP_E_DEVICE; break; }
-		rcode = NCHK(rc.Recv(loop ? loop_buf : d->d_keep + off[r], bytes, ncclUint8, (int)r, comm[dst], d->s_copy), "ncclRecv");
+		rcode = NCHK(rc.Recv(loop ? loop_buf.get() : d->d_keep + off[r], bytes, ncclUint8, (int)r, comm[dst], d->s_copy), "ncclRecv");
 	}
 	{ const int e = NCHK(rc.GroupEnd(), "ncclGroupEnd"); if (!rcode) rcode = e; }
 	(void)hipSetDevice(d->device);
-	if (!rcode && hipEventRecord(e1, d->s_copy) != hipSuccess) rcode = TWK_HIP_E_DEVICE;
+	if (!rcode && hipEventRecord(e1.e, d->s_copy) != hipSuccess) rcode = TWK_HIP_E_DEVICE;
 	for (uint32_t r = 0; r < n && !rcode; ++r) {
 		if (hipSetDevice(ctxs[r]->device) != hipSuccess || hipStreamSynchronize(ctxs[r]->s_copy) != hipSuccess) rcode = TWK_HIP_E_DEVICE;
 	}
 	(void)hipSetDevice(d->device);
 	float ms = 0;
-	if (!rcode && hipEventElapsedTime(&ms, e0, e1) == hipSuccess && transfer_ms) *transfer_ms = ms;
+	if (!rcode && hipEventElapsedTime(&ms, e0.e, e1.e) == hipSuccess && transfer_ms) *transfer_ms = ms;
 	if (rcode) { if (!d->err[0]) snprintf(d->err, sizeof(d->err), "RCCL gather: a HIP call failed"); return rcode; }
 	if (loop) {
-		if (loop_buf) {        // the records that went round are the sink's content from here on
-			if (d->d_keep) (void)hipFree(d->d_keep);
-			d->d_keep = loop_buf; d->d_keep_cap = cnt[0];
-			loop_buf = nullptr;
-		}
+		if (loop_buf) d->d_keep = std::move(loop_buf);        // the records that went round are the sink's content from here on
 	} else {
 		d->d_keep_n = total;
 		for (uint32_t r = 0; r < n; ++r) if (r != dst) ctxs[r]->d_keep_n = 0;
