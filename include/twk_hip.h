@@ -34,6 +34,7 @@ extern "C" {
  *    twk_hip_option_describe; twk_hip_timing grew (finish_ms); twk_hip_gather_records / twk_hip_gather_backend /
  *    twk_hip_drain_device_sink (the RCCL gather of a one-process multi-GPU run). */
 /*    (still 5: twk_hip_ld_score - LD scores - is an entry point more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_prune / twk_hip_prune_last - LD pruning - are two entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -295,6 +296,29 @@ int twk_hip_ld_score(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
                      uint32_t part, uint32_t n_parts, uint32_t tile_variants,
                      int32_t window, uint32_t l_window,
                      uint64_t* n_partners, double* sum_r2, uint64_t* n_pairs);
+
+/* LD pruning (PLINK's --indep-pairwise, greedy in file order) of the contiguous triangle of variants [a0, a0 + n), with the mode,
+ * filters, tile_variants, window bits and l_window of twk_hip_ld_region:
+ *   a pair (u, v), u < v, is an EDGE if twk_hip_ld_region over that triangle would report a record with those two variants;
+ *   walking v = a0 .. a0 + n - 1 upwards, v is KEPT if and only if no kept u < v has an edge (u, v).
+ * A variant the pair rules never report (the low-allele-count rule, say) has no edge and is kept.  Decided on the device: the count
+ * matrix of a launch goes through the pair rules and the math of the record path (one code, ld_math.hip.h), `keep` of every pair is
+ * balloted into an adjacency bitmap, and one sequential kernel walks the bitmap (ld_prune.hip.h).  No record is formed, sorted or
+ * copied: one byte per variant leaves the device.
+ *   keep     HOST array of n_variants bytes, indexed by variant as uploaded, overwritten: 1 kept, 0 dropped or outside the slice
+ *   *n_kept  (may be NULL) the number of 1s;  *n_edges (may be NULL) the number of records twk_hip_ld_region would have reported;
+ *   *n_pairs (may be NULL) pairs evaluated.
+ * The result is a function of the edge set alone and bitwise OR has no order: two calls with the same arguments return the same bytes.
+ * Always the whole triangle on one device (the walk needs every edge: there is no part / n_parts and no rectangle here), always the
+ * matrix form of the contraction (TWK_HIP_OPT_R2_SCREEN is ignored, as for a score).  filters.minP must be >= 1 (TWK_HIP_E_INVALID
+ * otherwise, before any launch): Fisher's test is not run.  Device memory: n * ceil(n / 64) * 8 bytes for the bitmap for the length of
+ * the call (0.31 GB at 50,000 variants, 35 GB at 531,500), whatever the window; TWK_HIP_E_NOMEM with the size in twk_hip_last_error
+ * when the device cannot give it.  twk_hip_timing: the mask kernels count as the math stage (stats_ms, stats_launches,
+ * variant_pairs); the walk is reported by twk_hip_prune_last.  There is NO reference counterpart. */
+int twk_hip_ld_prune(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters, uint32_t a0, uint32_t n, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window, uint8_t* keep, uint64_t* n_kept, uint64_t* n_edges, uint64_t* n_pairs);
+/* Of the context's last twk_hip_ld_prune call: the device time of its walk kernel in ms and the size of its bitmap (either may be NULL). */
+int twk_hip_prune_last(const twk_hip_ctx* ctx, double* walk_ms, uint64_t* bitmap_bytes);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

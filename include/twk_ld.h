@@ -65,6 +65,12 @@ public:
 	// either end, and the sum of their R2 with 17 significant digits - reduced on one GPU (twk_hip_ld_score), no record is formed.
 	// settings.minP must be 1 (the default).  `tomahawk ldscore` ends here.
 	bool Score(const twk_ld_settings& settings);
+	// Not in the reference: greedy LD pruning in file order (PLINK's --indep-pairwise).  Loads the .twk exactly as Compute does (-I intervals,
+	// -w, -p / -u, TWK_REF_COMPAT; the whole pair space: -c / -C are refused, the walk needs every pair) and writes one text line per
+	// variant of the selection, in file order, to settings.out ("-" or empty: stdout): contig, position (as Score prints them) and keep,
+	// 1 if no kept variant before it forms a record Compute would write with it, else 0 - decided and walked on one GPU
+	// (twk_hip_ld_prune), no record is formed.  settings.minP must be 1 (the default).  `tomahawk prune` ends here.
+	bool Prune(const twk_ld_settings& settings);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

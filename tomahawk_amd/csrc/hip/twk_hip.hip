@@ -6,6 +6,7 @@
 //   math  (ld_math.hip.h)  cells -> D/D'/r2/Fisher -> filters -> compaction
 //   (ld_three.hip.h: screen + recount behind the three-product form of the unphased contraction)
 //   score (ld_score.hip.h) cells -> r2 -> per-variant sums, in place of the math stage (twk_hip_ld_score)
+//   prune (ld_prune.hip.h) cells -> keep -> adjacency bitmap, in place of the math stage, and the greedy walk over it (twk_hip_ld_prune)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "ld_list.hip.h"
 #include "ld_three.hip.h"
 #include "ld_score.hip.h"
+#include "ld_prune.hip.h"
 #include "ld_plan.h"
 #include "twk_delivery.h"
 #include "twk_buffers.h"
@@ -112,6 +114,8 @@ struct LaunchForm {
 	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
 	bool score = false;            // the score epilogue in place of math, Fisher and records (ld_score.hip.h): always through a matrix
+	bool prune = false;            // the prune epilogue in their place (ld_prune.hip.h): likewise
+	bool reduces() const { return score || prune; }      // ... either way the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
@@ -154,6 +158,7 @@ struct Slot {                      // one in-flight tile (double buffered)
 	// score launches (ld_score.hip.h): the blocks' row and column partials of the launch (grow-only)
 	DevBuf<double> sc_sum; DevBuf<uint32_t> sc_n;
 	PinnedBuf<ScoreArgs> h_sc_args; DevBuf<ScoreArgs> d_sc_args;         // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
+	PinnedBuf<PruneArgs> h_pr_args; DevBuf<PruneArgs> d_pr_args;         // prune launches (ld_prune.hip.h): the same two blocks
 };
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
@@ -282,6 +287,13 @@ struct twk_hip_ctx {
 	// twk_hip_ld_score: the launches of the running call sum r2 per variant (ld_score.hip.h) instead of keeping records
 	bool score_on = false;
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
+	// twk_hip_ld_prune: the launches of the running call ballot `keep` into the adjacency bitmap of the call's triangle (ld_prune.hip.h)
+	bool prune_on = false;
+	bool reduce_on() const { return score_on || prune_on; }
+	PruneMap prune_map{};
+	DevBuf<unsigned long long> d_prune_adj, d_prune_removed, d_prune_counts;     // the bitmap (lives for the call), `removed` beyond LDS, [0] edges [1] kept
+	DevBuf<uint8_t> d_prune_keep;                                                // [M]
+	double prune_walk_ms = 0; uint64_t prune_bitmap_bytes = 0;                   // of the last call (twk_hip_prune_last)
 	char err[512] = {0};
 };
 
@@ -311,7 +323,7 @@ void free_planes(twk_hip_ctx* c) {
 void free_slots(twk_hip_ctx* c) {
 	for (auto& s : c->slot) {
 		s.C.reset(); s.out.reset(); s.keys.reset(); s.vals.reset(); s.sorted.reset();
-		s.sc_sum.reset(); s.sc_n.reset(); s.h_sc_args.reset(); s.d_sc_args.reset();
+		s.sc_sum.reset(); s.sc_n.reset(); s.h_sc_args.reset(); s.d_sc_args.reset(); s.h_pr_args.reset(); s.d_pr_args.reset();
 		for (int k = 0; k < 2; ++k) { s.h_tiles[k].reset(); s.d_tiles[k].reset(); }
 	}
 }
@@ -321,6 +333,7 @@ void free_problem(twk_hip_ctx* c) {
 	c->raw.reset(); c->rawmask.reset(); c->d_lfact.reset(); c->lfact_n = 0;
 	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
 	c->d_score_sum.reset(); c->d_score_n.reset();
+	c->d_prune_adj.reset(); c->d_prune_removed.reset(); c->d_prune_counts.reset(); c->d_prune_keep.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -744,7 +757,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 }
 
 // The form of the (first) launch of a tile of this plan, as the context stands: the one place that reads the options "fused" and "three",
-// FUSED_MAX_CHUNKS, fused_ok, three_ok and score_on for it.
+// FUSED_MAX_CHUNKS, fused_ok, three_ok, score_on and prune_on for it.
 // A screen in front of the math needs plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
 // pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short
 // enough that no tile's K range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h)
@@ -752,10 +765,10 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 // reports why).
 LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
 	LaunchForm lf;
-	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.keep_three = c->opt.three == 2;
+	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.prune = c->prune_on; lf.keep_three = c->opt.three == 2;
 	const int k = set_kind(pl.set1);
 	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
-	const bool screen = !lf.score && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
+	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
 	if (!screen) return lf;
 	lf.three = lf.unphased && c->three_ok && c->opt.three != 0;
 	if (c->opt.fused == 0 || ensure_planes(c, pl.set1) != TWK_HIP_OK) return lf;
@@ -810,6 +823,23 @@ int launch_score(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	return TWK_HIP_OK;
 }
 
+// The prune epilogue of a launch whose count matrix is in the slot's C (ld_prune.hip.h): `keep` of every pair balloted into the call's
+// adjacency bitmap.  The walk over the bitmap follows the call's last launch (twk_hip_ld_prune).
+int launch_prune(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
+	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
+	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
+	if (!t.nA || !t.nB) return TWK_HIP_OK;
+	HIPCHK(c, s.h_pr_args.reserve(2, 2, nullptr));
+	HIPCHK(c, s.d_pr_args.reserve(2, 2, nullptr));
+	const uint32_t gx = (t.nB + PRUNE_THREADS - 1) / PRUNE_THREADS, gy = (t.nA + PRUNE_ROWS - 1) / PRUNE_ROWS;
+	if (gy > 0xFFFFu) return TWK_HIP_E_INVALID;
+	s.h_pr_args[which].p = p; s.h_pr_args[which].pm = c->prune_map;      // (the slot's previous launch has been waited for: its copy is done)
+	HIPCHK(c, hipMemcpyAsync(s.d_pr_args + which, s.h_pr_args + which, sizeof(PruneArgs), hipMemcpyHostToDevice, c->s_compute));
+	hipLaunchKernelGGL(k_ld_prune_mask, dim3(gx, gy), dim3(PRUNE_THREADS), 0, c->s_compute, (const PruneArgs*)(s.d_pr_args + which));
+	HIPCHK(c, hipGetLastError());
+	return TWK_HIP_OK;
+}
+
 // Survivors are appended with an atomic counter, in no order.  They leave the device in (idxA, idxB) order
 // - the order the writer puts them in the file, which makes a one-GPU run's output deterministic - by a key
 // sort of (idxA << bits | idxB, position) and a gather.  Key and position are written by the math kernels where the
@@ -840,7 +870,7 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 }
 
 // The end of every launch, on the compute stream: Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is
-// free by now - the math kernels in front are done with it - and holds the walk-length order; a score launch has no survivors, and no
+// free by now - the math kernels in front are done with it - and holds the walk-length order; a score or prune launch has no survivors, and no
 // test to run: minP >= 1 drops nothing), for a band launch the sort of its survivors (Launch::presorted), the counters' copy to the host
 // and ev_s1.
 // The band launch's sort is over as many slots as there were candidates (unused slots carry the all-ones key, like records the Fisher
@@ -848,7 +878,7 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 // stream (finish_tile's sort_records) it waited for a CU until the *next* launch's persistent count kernel was through, 60 ms per launch
 // of the 2,504 x 531,500 run.
 int close_launch(twk_hip_ctx* c, Slot& s) {
-	if (!s.l.form.score) { const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, s.l.minP, s.C, s.C.capacity(), s.keys); if (rc) return rc; }
+	if (!s.l.form.reduces()) { const int rc = launch_fisher(c, s.out, s.n_out, s.cap_use, s.l.minP, s.C, s.C.capacity(), s.keys); if (rc) return rc; }
 	if (s.l.presorted) {
 		const unsigned long long need = s.cap_use;
 		size_t bytes = c->d_band_tmp.capacity();
@@ -873,7 +903,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
 	const LaunchForm form = launch_form(c, pl, f);
 	const Geometry g = tile_geometry(pl.Pmax, t);
-	if (form.score) capacity = 1;                  // a score launch keeps no survivors (and is never a band launch: always the matrix form)
+	if (form.reduces()) capacity = 1;              // a score or prune launch keeps no survivors (and is never a band launch: always the matrix form)
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
@@ -946,6 +976,8 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		}
 	} else if (form.score) {
 		rc = launch_score(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
+	} else if (form.prune) {
+		rc = launch_prune(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
 	} else {
 		const StatsParams p = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
 		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -954,6 +986,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (form.two_pass) {
 		rc = launch_count(c, kind2, t, s, 1, cr, LaunchForm(), nullptr); if (rc) return rc;
 		if (form.score) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
+		else if (form.prune) { rc = launch_prune(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else {
 			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
 			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -2166,7 +2199,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = !c->score_on;      // a score looks at every pair: no screen in front of the matrix
+	c->fused_ok = c->three_ok = !c->reduce_on();      // a score or a prune looks at every pair: no screen in front of the matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2265,6 +2298,75 @@ int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	} else (void)hipDeviceSynchronize();
 	flush_graveyard(c);
 	return rc;
+}
+
+// LD pruning: the same planner and pipeline with the prune epilogue, then the greedy walk over the bitmap the launches filled.
+int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window, uint8_t* keep, uint64_t* n_kept, uint64_t* n_edges, uint64_t* n_pairs) {
+	if (!c || !f || !keep || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M) return TWK_HIP_E_INVALID;
+	HIPCHK(c, hipSetDevice(c->device));
+	const size_t M = c->M;
+	const uint32_t stride = (n + 63) / 64;
+	const size_t words = (size_t)n * stride;
+	{	// the adjacency bitmap: n * ceil(n / 64) words, whatever the window (ld_prune.hip.h)
+		const hipError_t e = c->d_prune_adj.reserve(words, words, nullptr);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			snprintf(c->err, sizeof(c->err), "LD pruning of %u variants needs an adjacency bitmap of %zu bytes: %s", n, words * sizeof(unsigned long long), hipGetErrorString(e));
+			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+		}
+	}
+	// (the bitmap goes back when the call ends, whichever way: gigabytes that a record run behind this call may need)
+	struct PruneOn { twk_hip_ctx* c; ~PruneOn() { c->prune_on = false; c->prune_map = PruneMap{}; (void)hipDeviceSynchronize(); c->d_prune_adj.reset(); } } on{c};
+	const bool in_lds = stride <= WALK_LDS_WORDS;
+	HIPCHK(c, c->d_prune_keep.reserve(M, M, nullptr));
+	HIPCHK(c, c->d_prune_counts.reserve(2, 2, nullptr));
+	if (!in_lds) HIPCHK(c, c->d_prune_removed.reserve(stride, stride, nullptr));
+	HIPCHK(c, hipMemsetAsync(c->d_prune_adj, 0, words * sizeof(unsigned long long), c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_prune_keep, 0, M, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_prune_counts, 0, 2 * sizeof(unsigned long long), c->s_compute));
+	if (!in_lds) HIPCHK(c, hipMemsetAsync(c->d_prune_removed, 0, (size_t)stride * sizeof(unsigned long long), c->s_compute));
+	c->prune_map = PruneMap{c->d_prune_adj, c->d_prune_counts, a0, n, stride};
+	c->prune_walk_ms = 0; c->prune_bitmap_bytes = words * sizeof(unsigned long long);
+	c->prune_on = true;
+	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a prune.  A single variant has no pair.)
+	int rc = n < 2 ? TWK_HIP_OK
+	               : region_dispatch(c, RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
+	                                               nullptr, nullptr, n_pairs, nullptr});
+	if (n < 2 && n_pairs) *n_pairs = 0;
+	if (rc == TWK_HIP_OK) {
+		unsigned long long counts[2] = {0, 0};
+		Event w0, w1;
+		HIPCHK(c, hipEventCreate(&w0.e)); HIPCHK(c, hipEventCreate(&w1.e));
+		HIPCHK(c, hipEventRecord(w0.e, c->s_compute));
+		if (in_lds) hipLaunchKernelGGL(k_ld_prune_walk<true>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_prune_adj, a0, n, stride,
+		                               (unsigned long long*)nullptr, c->d_prune_keep.get(), c->d_prune_counts + 1);
+		else hipLaunchKernelGGL(k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_prune_adj, a0, n, stride,
+		                        c->d_prune_removed.get(), c->d_prune_keep.get(), c->d_prune_counts + 1);
+		hipError_t e = hipGetLastError();
+		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(keep, c->d_prune_keep, M, hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(counts, c->d_prune_counts, sizeof(counts), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "prune walk: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
+		else {
+			if (n_edges) *n_edges = counts[0];
+			if (n_kept) *n_kept = counts[1];
+			float ms = 0;
+			if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->prune_walk_ms = ms;
+		}
+	}
+	flush_graveyard(c);
+	return rc;
+}
+
+int twk_hip_prune_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (walk_ms) *walk_ms = c->prune_walk_ms;
+	if (bitmap_bytes) *bitmap_bytes = c->prune_bitmap_bytes;
+	return TWK_HIP_OK;
 }
 
 int twk_hip_shard_rows(uint32_t n_rows, uint32_t n_cols, int32_t triangle, uint32_t part, uint32_t n_parts,

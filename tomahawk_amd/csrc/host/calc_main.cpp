@@ -164,20 +164,17 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int ldscore(int argc, char** argv) {
-	if (argc < 3) { ldscore_usage(); return 1; }
+// The options `ldscore` and `prune` share (-P is accepted only as 1 by both; `prune` has no -c / -C).  -> 0, or 1 after an error message.
+static int reduce_options(int argc, char** argv, bool prune, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options) {
 	static struct option long_options[] = {
 		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
 		{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
 		{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 		{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
 		{"engine-option", required_argument, 0, 1000}, {0, 0, 0, 0}};
-	tomahawk::twk_ld_settings settings;
-	settings.minR2 = 0;
-	settings.out = "-";
 	int c, option_index = 0;
-	std::vector<std::pair<std::string, long long>> engine_options;
 	while ((c = getopt_long(argc, argv, "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
+		if (prune && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
 		switch (c) {
 		case 'i': settings.in = optarg; break;
 		case 'o': settings.out = optarg; break;
@@ -203,7 +200,11 @@ static int ldscore(int argc, char** argv) {
 			break;
 		case 'P':
 			settings.minP = atof(optarg);
-			if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run" << std::endl; return 1; }
+			if (!(settings.minP >= 1)) {
+				std::cerr << stamp("ERROR") << (prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
+				                                      : "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run") << std::endl;
+				return 1;
+			}
 			if (settings.minP > 1) { std::cerr << stamp("ERROR") << "Cannot have a cutoff P-value > 1" << std::endl; return 1; }
 			break;
 		case 'w': {
@@ -227,11 +228,59 @@ static int ldscore(int argc, char** argv) {
 		}
 	}
 	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
+	return 0;
+}
+
+static int ldscore(int argc, char** argv) {
+	if (argc < 3) { ldscore_usage(); return 1; }
+	tomahawk::twk_ld_settings settings;
+	settings.minR2 = 0;
+	settings.out = "-";
+	std::vector<std::pair<std::string, long long>> engine_options;
+	if (reduce_options(argc, argv, false, settings, engine_options)) return 1;
 	program_message();
 	std::cerr << stamp("LOG") << "Calling ldscore..." << std::endl;
 	tomahawk::twk_ld ld;
 	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
 	return ld.Score(settings) ? 0 : 1;
+}
+
+// `tomahawk prune` (not in the reference): greedy LD pruning in file order over the records `calc` would write, decided on the GPU.
+static void prune_usage() {
+	program_message();
+	std::cerr <<
+	"About:  LD pruning: walking the variants in file order, a variant is kept if and only if no\n"
+	"        variant kept before it forms a pair with it that `calc` would report under the same\n"
+	"        options (greedy pruning, like PLINK's --indep-pairwise); decided on the GPU (no .two\n"
+	"        is written).\n\n"
+	"Usage:  tomahawk prune [options] -i <in.twk> [-o <out.tsv>]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o FILE   output text file (- for stdout; default: -)\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -w INT    sliding window width in bases\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value: pairs at or above it are in LD (default: 0.1)\n"
+	"  -P FLOAT  accepted only as 1: pruning looks at every record, Fisher's test is not run\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"  (-c / -C are refused: the walk needs every pair)\n"
+	"Output: '#' header lines, then per variant: contig <TAB> pos <TAB> keep (1 kept, 0 pruned)\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int prune(int argc, char** argv) {
+	if (argc < 3) { prune_usage(); return 1; }
+	tomahawk::twk_ld_settings settings;      // (-r: calc's default)
+	settings.out = "-";
+	std::vector<std::pair<std::string, long long>> engine_options;
+	if (reduce_options(argc, argv, true, settings, engine_options)) return 1;
+	program_message();
+	std::cerr << stamp("LOG") << "Calling prune..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Prune(settings) ? 0 : 1;
 }
 
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
@@ -525,6 +574,7 @@ static int run_main(int argc, char** argv) {
 		             "  calc     calculate linkage disequilibrium: tomahawk calc [options] -i <in.twk> -o <output.two>\n"
 		             "  scalc    linkage disequilibrium of one site against its neighbourhood\n"
 		             "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n"
+		             "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n"
 		             "  sort     sort a .two file\n"
 		             "  view     convert, filter and slice .two files\n"
 		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
@@ -539,6 +589,7 @@ static int run_main(int argc, char** argv) {
 	for (int i = 1; i < argc; ++i) tomahawk::LITERAL_COMMAND_LINE += " " + std::string(argv[i]);
 	if (strcmp(argv[1], "calc") == 0) return calc(argc, argv);
 	if (strcmp(argv[1], "ldscore") == 0) return ldscore(argc, argv);
+	if (strcmp(argv[1], "prune") == 0) return prune(argc, argv);
 	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
 	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
 	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
@@ -547,7 +598,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
 	return 1;
 }
 

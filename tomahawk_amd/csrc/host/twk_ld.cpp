@@ -1010,6 +1010,76 @@ bool twk_ld::Score(const twk_ld_settings& s) {
 	return true;
 }
 
+// `tomahawk prune`: greedy LD pruning of the selection in file order (twk_hip_ld_prune: the edges are the records Compute would write,
+// decided and walked on the GPU, no record is formed), as text: one line per variant with its keep flag.  The input is loaded exactly
+// as Compute loads it; one GPU; the whole triangle (the walk needs every pair: no -c / -C).  Not in the reference.
+bool twk_ld::Prune(const twk_ld_settings& s) {
+	using clock = std::chrono::steady_clock;
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "Pruning looks at every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
+	if (settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space: the walk needs every pair (no -c / -C)..." << std::endl; return false; }
+	Selection S;
+	bool nothing_to_do = false;
+	if (!select_blocks(settings, S, &nothing_to_do)) return false;
+	if (nothing_to_do) return true;
+	const uint32_t M = S.M;
+	DeviceCtxs dc;
+	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
+	twk_hip_ctx* ctx = dc.ctx[0];
+	const auto t_load = clock::now();
+	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
+	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
+	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
+	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
+	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
+
+	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
+	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
+	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	std::vector<uint8_t> keep(M, 0);
+	uint64_t np = 0, n_kept = 0, n_edges = 0;
+	const auto t0 = clock::now();
+	const int rc = twk_hip_ld_prune(ctx, mode, &f, 0, M, 0, options, (uint32_t)settings.l_window, keep.data(), &n_kept, &n_edges, &np);
+	if (!hip_ok(ctx, rc, "twk_hip_ld_prune")) return false;
+	mImpl->n_pairs = np;
+	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+
+	std::ofstream file;
+	const bool to_stdout = settings.out.empty() || settings.out == "-";
+	if (!to_stdout) {
+		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
+		file.open(settings.out, std::ios::out | std::ios::trunc);
+		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return false; }
+	}
+	std::ostream& os = to_stdout ? std::cout : file;
+	os << "##tomahawk_pruneVersion=" << TWK_AMD_VERSION << "\n"
+	   << "##tomahawk_pruneCommand=" << command_line() << "; Date=" << datetime() << "\n"
+	   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
+	char line[256];
+	snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
+	os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n";
+	snprintf(line, sizeof(line), "##kept=%llu,total=%u,edges=%llu\n", (unsigned long long)n_kept, M, (unsigned long long)n_edges);
+	os << line << "#contig\tpos\tkeep\n";
+	std::string text;
+	for (uint32_t v = 0; v < M; ++v) {
+		const uint32_t rid = mImpl->rid[v];
+		// (contig and position as `ldscore` prints them: the contig's name, the 1-based position)
+		if (rid < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid].name; else text += '.';
+		snprintf(line, sizeof(line), "\t%u\t%u\n", mImpl->pos[v] + 1, keep[v] ? 1u : 0u);
+		text += line;
+		if (text.size() > (1u << 20)) { os << text; text.clear(); }
+	}
+	os << text;
+	os.flush();
+	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the keep flags..." << std::endl; return false; }
+	std::cerr << stamp("LOG") << "Pruned: kept " << pretty(n_kept) << " of " << pretty(M) << " variants; " << pretty(n_edges) << " pairs in LD among "
+	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	return true;
+}
+
 // scalc: one target site against its neighbourhood (ld.cpp:673-876, LoadTargetSingle :123-255,
 // CalculateSingle ld_engine.cpp:2226-2332).
 bool twk_ld::ComputeSingle(bool verbose, bool) {

@@ -188,6 +188,9 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_score.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
                                      C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_prune.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_prune_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_shard_rows.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_plan_region.argtypes = [p, p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
@@ -472,6 +475,26 @@ class HipLd:
                                                tile_variants, int(window), l_window, n.ctypes.data, s.ctypes.data,
                                                C.byref(npairs)), "twk_hip_ld_score")
         return n, s, npairs.value
+
+    def ld_prune(self, mode: int, filters: Filters, a0: int = 0, n: int | None = None, tile_variants: int = 0, window: int = 0,
+                 l_window: int = 0):
+        """Greedy LD pruning in file order (twk_hip_ld_prune) of the triangle of variants [a0, a0 + n): a variant is kept if and
+        only if no variant kept before it forms a record with it that ld_region would report; decided and walked on the device -
+        no record is formed.  filters.minP must be >= 1.  -> (keep uint8[M], n_kept, n_edges, n_pairs)."""
+        M = self.n_variants
+        n = M - a0 if n is None else n
+        keep = np.zeros(M, dtype=np.uint8)
+        n_kept, n_edges, npairs = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_prune(self._ctx, mode, C.byref(f), a0, n, tile_variants, int(window), l_window,
+                                               keep.ctypes.data, C.byref(n_kept), C.byref(n_edges), C.byref(npairs)), "twk_hip_ld_prune")
+        return keep, n_kept.value, n_edges.value, npairs.value
+
+    def prune_last(self) -> dict:
+        """Of the last ld_prune call (twk_hip_prune_last): the walk kernel's device time and the adjacency bitmap's size."""
+        ms, b = C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_prune_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_prune_last")
+        return {"walk_ms": ms.value, "bitmap_bytes": b.value}
 
     def fisher_exact(self, tables: np.ndarray, ordered: bool = True):
         """Two-sided Fisher P of int32 tables [n, 4] = (n11, n12, n21, n22) through the engine's Fisher kernels
