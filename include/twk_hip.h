@@ -35,6 +35,7 @@ extern "C" {
  *    twk_hip_drain_device_sink (the RCCL gather of a one-process multi-GPU run). */
 /*    (still 5: twk_hip_ld_score - LD scores - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_prune / twk_hip_prune_last - LD pruning - are two entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_clump / twk_hip_clump_last - LD clumping - are two entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -319,6 +320,37 @@ int twk_hip_ld_prune(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
                      int32_t window, uint32_t l_window, uint8_t* keep, uint64_t* n_kept, uint64_t* n_edges, uint64_t* n_pairs);
 /* Of the context's last twk_hip_ld_prune call: the device time of its walk kernel in ms and the size of its bitmap (either may be NULL). */
 int twk_hip_prune_last(const twk_hip_ctx* ctx, double* walk_ms, uint64_t* bitmap_bytes);
+
+/* LD clumping (PLINK's --clump) of the triangle of variants [a0, a0 + n) in file order, without records.  mode, filters, tile_variants,
+ * window (the option bits) and l_window are those of twk_hip_ld_region.
+ *   {u, v} is an EDGE if twk_hip_ld_region over that triangle would report a record with those two variants (prune's edge, seen from
+ *   both ends);  v is ELIGIBLE if p[v] is not NaN and p[v] <= p2;
+ *   the variants of the slice whose p is not NaN are visited in ascending p, ties in file order, up to the first with p > p1.  A visited
+ *   variant that already belongs to a clump is skipped; otherwise it becomes an INDEX variant, index_of[v] = v, and every eligible w
+ *   with an edge to v that belongs to no clump yet gets index_of[w] = v.
+ * Decided on the device: `keep` of every pair of a launch's count matrix - the pair rules and the math of the record path, one code
+ * (ld_math.hip.h) - is set in an adjacency bitmap at (u, v) and at (v, u), and one sequential kernel walks the bitmap in P order
+ * (ld_clump.hip.h).  No record is formed, sorted or copied: four bytes per variant leave the device.
+ *   p          HOST array of n_variants doubles, indexed by variant as uploaded: the association P value, NaN for none
+ *   p1, p2     the index and the secondary threshold, 0 <= p1 <= p2 <= 1
+ *   index_of   HOST array of n_variants uint32, overwritten: the variant's index variant (itself for an index variant), or
+ *              TWK_HIP_NO_CLUMP - unclaimed, no P value, or outside the slice
+ *   *n_clumps  (may be NULL) the number of index variants;  *n_members (may be NULL) the number of claimed variants that are not
+ *   index variants;  *n_edges (may be NULL) the records twk_hip_ld_region would have reported, each pair once;  *n_pairs (may be NULL)
+ * The result is a function of the edge set and p alone: two calls return the same bytes.  With p increasing in file order and
+ * p1 = p2 = 1 the index variants are exactly twk_hip_ld_prune's kept set.
+ * TWK_HIP_E_INVALID before any launch: filters->minP < 1 (Fisher's test is not run), p or index_of NULL, a threshold that is NaN, out
+ * of order or outside [0, 1], a non-NaN p[v] of the slice outside [0, 1], n == 0 or a slice that reaches beyond the last variant.
+ * Device memory: n * ceil(n / 64) * 8 bytes for the bitmap for the length of the call, as for twk_hip_ld_prune (the mirrored bits
+ * take the half prune leaves empty); TWK_HIP_E_NOMEM with the size in twk_hip_last_error when the device cannot give it.
+ * twk_hip_timing: the mask kernels count as the math stage (stats_ms, stats_launches, variant_pairs); the walk is reported by
+ * twk_hip_clump_last.  There is NO reference counterpart. */
+#define TWK_HIP_NO_CLUMP 0xFFFFFFFFu
+int twk_hip_ld_clump(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters, uint32_t a0, uint32_t n, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window, const double* p, double p1, double p2,
+                     uint32_t* index_of, uint64_t* n_clumps, uint64_t* n_members, uint64_t* n_edges, uint64_t* n_pairs);
+/* Of the context's last twk_hip_ld_clump call: the device time of its walk kernel in ms and the size of its bitmap (either may be NULL). */
+int twk_hip_clump_last(const twk_hip_ctx* ctx, double* walk_ms, uint64_t* bitmap_bytes);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

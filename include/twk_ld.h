@@ -42,6 +42,13 @@ struct twk_ld_settings {
 	std::vector<std::string> ival_strings;
 };
 
+// What Clump needs beyond twk_ld_settings.
+struct twk_clump_settings {
+	std::string assoc;          // the association file
+	double p1 = 1e-4;           // index threshold: a variant with P <= p1 may start a clump
+	double p2 = 1e-2;           // secondary threshold: a variant with P <= p2 may be claimed
+};
+
 class twk_ld {
 public:
 	twk_ld();
@@ -71,6 +78,16 @@ public:
 	// 1 if no kept variant before it forms a record Compute would write with it, else 0 - decided and walked on one GPU
 	// (twk_hip_ld_prune), no record is formed.  settings.minP must be 1 (the default).  `tomahawk prune` ends here.
 	bool Prune(const twk_ld_settings& settings);
+	// Not in the reference: LD clumping (PLINK's --clump).  Loads the .twk exactly as Prune does (-I intervals, -w, -p / -u, TWK_REF_COMPAT;
+	// -c / -C are refused) and reads one association P value per variant from clump.assoc - text, split on tabs or spaces, lines that
+	// start with '#' ignored: contig name, position (1-based, as Score and Prune print it), P (NA / nan: none), further columns ignored;
+	// every variant of the selection at a (contig, position) gets that P, variants the file does not name get none; the same key twice,
+	// a P outside [0, 1] or an unreadable file is an error before any device is touched.  The variants are visited in ascending P up to
+	// clump.p1; one that belongs to no clump yet becomes an index variant and claims every free variant with P <= clump.p2 that forms a
+	// record Compute would write with it - decided and walked on one GPU (twk_hip_ld_clump), no record is formed.  Writes one text line
+	// per variant of the selection, in file order, to settings.out: contig, position, P, and contig and position of its index variant.
+	// settings.minP must be 1 (the default).  `tomahawk clump` ends here.
+	bool Clump(const twk_ld_settings& settings, const twk_clump_settings& clump);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

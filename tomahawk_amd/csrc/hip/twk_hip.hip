@@ -7,6 +7,7 @@
 //   (ld_three.hip.h: screen + recount behind the three-product form of the unphased contraction)
 //   score (ld_score.hip.h) cells -> r2 -> per-variant sums, in place of the math stage (twk_hip_ld_score)
 //   prune (ld_prune.hip.h) cells -> keep -> adjacency bitmap, in place of the math stage, and the greedy walk over it (twk_hip_ld_prune)
+//   clump (ld_clump.hip.h) cells -> keep -> the bitmap's bits (u, v) and (v, u), likewise, and the walk over it in P order (twk_hip_ld_clump)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -37,6 +38,7 @@
 #include "ld_three.hip.h"
 #include "ld_score.hip.h"
 #include "ld_prune.hip.h"
+#include "ld_clump.hip.h"
 #include "ld_plan.h"
 #include "twk_delivery.h"
 #include "twk_buffers.h"
@@ -115,7 +117,8 @@ struct LaunchForm {
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
 	bool score = false;            // the score epilogue in place of math, Fisher and records (ld_score.hip.h): always through a matrix
 	bool prune = false;            // the prune epilogue in their place (ld_prune.hip.h): likewise
-	bool reduces() const { return score || prune; }      // ... either way the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
+	bool clump = false;            // the clump epilogue (ld_clump.hip.h): the prune epilogue with both bits of an edge
+	bool reduces() const { return score || prune || clump; }      // ... either way the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
@@ -159,6 +162,7 @@ struct Slot {                      // one in-flight tile (double buffered)
 	DevBuf<double> sc_sum; DevBuf<uint32_t> sc_n;
 	PinnedBuf<ScoreArgs> h_sc_args; DevBuf<ScoreArgs> d_sc_args;         // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
 	PinnedBuf<PruneArgs> h_pr_args; DevBuf<PruneArgs> d_pr_args;         // prune launches (ld_prune.hip.h): the same two blocks
+	PinnedBuf<ClumpArgs> h_cl_args; DevBuf<ClumpArgs> d_cl_args;         // clump launches (ld_clump.hip.h): likewise
 };
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
@@ -289,11 +293,17 @@ struct twk_hip_ctx {
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
 	// twk_hip_ld_prune: the launches of the running call ballot `keep` into the adjacency bitmap of the call's triangle (ld_prune.hip.h)
 	bool prune_on = false;
-	bool reduce_on() const { return score_on || prune_on; }
+	bool reduce_on() const { return score_on || prune_on || clump_on; }
 	PruneMap prune_map{};
 	DevBuf<unsigned long long> d_prune_adj, d_prune_removed, d_prune_counts;     // the bitmap (lives for the call), `removed` beyond LDS, [0] edges [1] kept
 	DevBuf<uint8_t> d_prune_keep;                                                // [M]
 	double prune_walk_ms = 0; uint64_t prune_bitmap_bytes = 0;                   // of the last call (twk_hip_prune_last)
+	// twk_hip_ld_clump: the launches of the running call ballot `keep` into the call's bitmap from both ends of a pair (ld_clump.hip.h)
+	bool clump_on = false;
+	PruneMap clump_map{};
+	DevBuf<unsigned long long> d_clump_adj, d_clump_taken, d_clump_counts;       // the bitmap (lives for the call), taken0 / `taken` beyond LDS, [0] edges [1] clumps [2] members
+	DevBuf<uint32_t> d_clump_order, d_clump_index;                               // the candidates in visiting order; index_of [M]
+	double clump_walk_ms = 0; uint64_t clump_bitmap_bytes = 0;                   // of the last call (twk_hip_clump_last)
 	char err[512] = {0};
 };
 
@@ -324,6 +334,7 @@ void free_slots(twk_hip_ctx* c) {
 	for (auto& s : c->slot) {
 		s.C.reset(); s.out.reset(); s.keys.reset(); s.vals.reset(); s.sorted.reset();
 		s.sc_sum.reset(); s.sc_n.reset(); s.h_sc_args.reset(); s.d_sc_args.reset(); s.h_pr_args.reset(); s.d_pr_args.reset();
+		s.h_cl_args.reset(); s.d_cl_args.reset();
 		for (int k = 0; k < 2; ++k) { s.h_tiles[k].reset(); s.d_tiles[k].reset(); }
 	}
 }
@@ -334,6 +345,7 @@ void free_problem(twk_hip_ctx* c) {
 	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
 	c->d_score_sum.reset(); c->d_score_n.reset();
 	c->d_prune_adj.reset(); c->d_prune_removed.reset(); c->d_prune_counts.reset(); c->d_prune_keep.reset();
+	c->d_clump_adj.reset(); c->d_clump_taken.reset(); c->d_clump_counts.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -757,7 +769,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 }
 
 // The form of the (first) launch of a tile of this plan, as the context stands: the one place that reads the options "fused" and "three",
-// FUSED_MAX_CHUNKS, fused_ok, three_ok, score_on and prune_on for it.
+// FUSED_MAX_CHUNKS, fused_ok, three_ok, score_on, prune_on and clump_on for it.
 // A screen in front of the math needs plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
 // pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short
 // enough that no tile's K range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h)
@@ -765,7 +777,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 // reports why).
 LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
 	LaunchForm lf;
-	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.prune = c->prune_on; lf.keep_three = c->opt.three == 2;
+	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.prune = c->prune_on; lf.clump = c->clump_on; lf.keep_three = c->opt.three == 2;
 	const int k = set_kind(pl.set1);
 	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
 	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
@@ -840,6 +852,23 @@ int launch_prune(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	return TWK_HIP_OK;
 }
 
+// The clump epilogue of a launch whose count matrix is in the slot's C (ld_clump.hip.h): `keep` of every pair set in the call's bitmap at
+// (u, v) and at (v, u).  The walk in P order follows the call's last launch (twk_hip_ld_clump).
+int launch_clump(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
+	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
+	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
+	if (!t.nA || !t.nB) return TWK_HIP_OK;
+	HIPCHK(c, s.h_cl_args.reserve(2, 2, nullptr));
+	HIPCHK(c, s.d_cl_args.reserve(2, 2, nullptr));
+	const uint32_t gx = (t.nB + CLUMP_THREADS - 1) / CLUMP_THREADS, gy = (t.nA + CLUMP_ROWS - 1) / CLUMP_ROWS;
+	if (gy > 0xFFFFu) return TWK_HIP_E_INVALID;
+	s.h_cl_args[which].p = p; s.h_cl_args[which].pm = c->clump_map;      // (the slot's previous launch has been waited for: its copy is done)
+	HIPCHK(c, hipMemcpyAsync(s.d_cl_args + which, s.h_cl_args + which, sizeof(ClumpArgs), hipMemcpyHostToDevice, c->s_compute));
+	hipLaunchKernelGGL(k_ld_clump_mask, dim3(gx, gy), dim3(CLUMP_THREADS), 0, c->s_compute, (const ClumpArgs*)(s.d_cl_args + which));
+	HIPCHK(c, hipGetLastError());
+	return TWK_HIP_OK;
+}
+
 // Survivors are appended with an atomic counter, in no order.  They leave the device in (idxA, idxB) order
 // - the order the writer puts them in the file, which makes a one-GPU run's output deterministic - by a key
 // sort of (idxA << bits | idxB, position) and a gather.  Key and position are written by the math kernels where the
@@ -870,7 +899,7 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 }
 
 // The end of every launch, on the compute stream: Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is
-// free by now - the math kernels in front are done with it - and holds the walk-length order; a score or prune launch has no survivors, and no
+// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune or clump launch has no survivors, and no
 // test to run: minP >= 1 drops nothing), for a band launch the sort of its survivors (Launch::presorted), the counters' copy to the host
 // and ev_s1.
 // The band launch's sort is over as many slots as there were candidates (unused slots carry the all-ones key, like records the Fisher
@@ -903,7 +932,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
 	const LaunchForm form = launch_form(c, pl, f);
 	const Geometry g = tile_geometry(pl.Pmax, t);
-	if (form.reduces()) capacity = 1;              // a score or prune launch keeps no survivors (and is never a band launch: always the matrix form)
+	if (form.reduces()) capacity = 1;              // a score, prune or clump launch keeps no survivors (and is never a band launch: always the matrix form)
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
@@ -978,6 +1007,8 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		rc = launch_score(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
 	} else if (form.prune) {
 		rc = launch_prune(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
+	} else if (form.clump) {
+		rc = launch_clump(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
 	} else {
 		const StatsParams p = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
 		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -987,6 +1018,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		rc = launch_count(c, kind2, t, s, 1, cr, LaunchForm(), nullptr); if (rc) return rc;
 		if (form.score) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else if (form.prune) { rc = launch_prune(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
+		else if (form.clump) { rc = launch_clump(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else {
 			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
 			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -2199,7 +2231,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = !c->reduce_on();      // a score or a prune looks at every pair: no screen in front of the matrix
+	c->fused_ok = c->three_ok = !c->reduce_on();      // a score, a prune or a clump looks at every pair: no screen in front of the matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2366,6 +2398,96 @@ int twk_hip_prune_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_b
 	if (!c) return TWK_HIP_E_INVALID;
 	if (walk_ms) *walk_ms = c->prune_walk_ms;
 	if (bitmap_bytes) *bitmap_bytes = c->prune_bitmap_bytes;
+	return TWK_HIP_OK;
+}
+
+// LD clumping: the same planner and pipeline with the clump epilogue, then the walk in P order over the bitmap the launches filled.
+int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window, const double* p, double p1, double p2,
+                     uint32_t* index_of, uint64_t* n_clumps, uint64_t* n_members, uint64_t* n_edges, uint64_t* n_pairs) {
+	if (!c || !f || !p || !index_of || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
+	if (!(p1 >= 0.0 && p1 <= p2 && p2 <= 1.0)) return TWK_HIP_E_INVALID;          // (a NaN fails every comparison)
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M) return TWK_HIP_E_INVALID;
+	const size_t M = c->M;
+	const uint32_t stride = (n + 63) / 64;
+	const size_t words = (size_t)n * stride;
+	// the candidates (P <= p1) in visiting order - ascending P, ties in file order - and the variants that can belong to no clump
+	std::vector<uint32_t> order;
+	std::vector<unsigned long long> taken0(stride, 0ull);
+	if (n & 63) taken0[stride - 1] = ~0ull << (n & 63);                            // (beyond the slice: nobody's)
+	for (uint32_t v = 0; v < n; ++v) {
+		const double pv = p[a0 + v];
+		if (pv != pv) { taken0[v >> 6] |= 1ull << (v & 63); continue; }
+		if (!(pv >= 0.0 && pv <= 1.0)) return TWK_HIP_E_INVALID;
+		if (pv > p2) taken0[v >> 6] |= 1ull << (v & 63);
+		if (pv <= p1) order.push_back(v);
+	}
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return p[a0 + x] < p[a0 + y]; });
+	// (p1 <= p2: every candidate is eligible - an index variant that may not be in a clump cannot arise)
+	for (const uint32_t v : order) if (taken0[v >> 6] >> (v & 63) & 1) return TWK_HIP_E_INVALID;
+	const uint32_t m = (uint32_t)order.size();
+	HIPCHK(c, hipSetDevice(c->device));
+	{	// the adjacency bitmap: n * ceil(n / 64) words, whatever the window (ld_prune.hip.h), both triangles used
+		const hipError_t e = c->d_clump_adj.reserve(words, words, nullptr);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			snprintf(c->err, sizeof(c->err), "LD clumping of %u variants needs an adjacency bitmap of %zu bytes: %s", n, words * sizeof(unsigned long long), hipGetErrorString(e));
+			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+		}
+	}
+	// (the bitmap goes back when the call ends, whichever way: gigabytes that a record run behind this call may need)
+	struct ClumpOn { twk_hip_ctx* c; ~ClumpOn() { c->clump_on = false; c->clump_map = PruneMap{}; (void)hipDeviceSynchronize(); c->d_clump_adj.reset(); } } on{c};
+	const bool in_lds = stride <= CLUMP_LDS_WORDS;
+	HIPCHK(c, c->d_clump_index.reserve(M, M, nullptr));
+	HIPCHK(c, c->d_clump_counts.reserve(3, 3, nullptr));
+	HIPCHK(c, c->d_clump_taken.reserve(stride, stride, nullptr));
+	HIPCHK(c, c->d_clump_order.reserve(m ? m : 1, m ? m : 1, nullptr));
+	HIPCHK(c, hipMemsetAsync(c->d_clump_adj, 0, words * sizeof(unsigned long long), c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_clump_index, 0xFF, M * sizeof(uint32_t), c->s_compute));          // TWK_HIP_NO_CLUMP
+	HIPCHK(c, hipMemsetAsync(c->d_clump_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
+	// (from pageable memory: the copies have left `order` and `taken0` when they return; both live to the end of the call anyway)
+	HIPCHK(c, hipMemcpyAsync(c->d_clump_taken, taken0.data(), (size_t)stride * sizeof(unsigned long long), hipMemcpyHostToDevice, c->s_compute));
+	if (m) HIPCHK(c, hipMemcpyAsync(c->d_clump_order, order.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
+	c->clump_map = PruneMap{c->d_clump_adj, c->d_clump_counts, a0, n, stride};
+	c->clump_walk_ms = 0; c->clump_bitmap_bytes = words * sizeof(unsigned long long);
+	c->clump_on = true;
+	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a clump.  A single variant has no pair.)
+	int rc = n < 2 ? TWK_HIP_OK
+	               : region_dispatch(c, RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
+	                                               nullptr, nullptr, n_pairs, nullptr});
+	if (n < 2 && n_pairs) *n_pairs = 0;
+	if (rc == TWK_HIP_OK) {
+		unsigned long long counts[3] = {0, 0, 0};
+		Event w0, w1;
+		HIPCHK(c, hipEventCreate(&w0.e)); HIPCHK(c, hipEventCreate(&w1.e));
+		HIPCHK(c, hipEventRecord(w0.e, c->s_compute));
+		if (in_lds) hipLaunchKernelGGL(k_ld_clump_walk<true>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_clump_adj, a0, n, stride,
+		                               (const uint32_t*)c->d_clump_order, m, c->d_clump_taken.get(), c->d_clump_index.get(), c->d_clump_counts + 1);
+		else hipLaunchKernelGGL(k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_clump_adj, a0, n, stride,
+		                        (const uint32_t*)c->d_clump_order, m, c->d_clump_taken.get(), c->d_clump_index.get(), c->d_clump_counts + 1);
+		hipError_t e = hipGetLastError();
+		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(index_of, c->d_clump_index, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(counts, c->d_clump_counts, sizeof(counts), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "clump walk: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
+		else {
+			if (n_edges) *n_edges = counts[0];
+			if (n_clumps) *n_clumps = counts[1];
+			if (n_members) *n_members = counts[2];
+			float ms = 0;
+			if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->clump_walk_ms = ms;
+		}
+	}
+	flush_graveyard(c);
+	return rc;
+}
+
+int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (walk_ms) *walk_ms = c->clump_walk_ms;
+	if (bitmap_bytes) *bitmap_bytes = c->clump_bitmap_bytes;
 	return TWK_HIP_OK;
 }
 

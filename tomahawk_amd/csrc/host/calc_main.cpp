@@ -164,18 +164,33 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-// The options `ldscore` and `prune` share (-P is accepted only as 1 by both; `prune` has no -c / -C).  -> 0, or 1 after an error message.
-static int reduce_options(int argc, char** argv, bool prune, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options) {
+// The options `ldscore`, `prune` and `clump` share (-P is accepted only as 1 by all; `prune` and `clump` have no -c / -C; `clump` adds its
+// association file and thresholds).  -> 0, or 1 after an error message.
+enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP };
+static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options,
+                          tomahawk::twk_clump_settings* clump = nullptr) {
+	const bool prune = cmd == REDUCE_PRUNE;
 	static struct option long_options[] = {
 		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
 		{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
 		{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 		{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
-		{"engine-option", required_argument, 0, 1000}, {0, 0, 0, 0}};
+		{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
+		{0, 0, 0, 0}};
 	int c, option_index = 0;
-	while ((c = getopt_long(argc, argv, "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
+	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
 		if (prune && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
+		if (cmd == REDUCE_CLUMP && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
+		if (!clump && (c == 'a' || c == '1' || c == '2')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
 		switch (c) {
+		case 'a': clump->assoc = optarg; break;
+		case '1': case '2': {
+			char* end = nullptr;
+			const double t = strtod(optarg, &end);
+			if (end == optarg || *end || !(t >= 0 && t <= 1)) { std::cerr << stamp("ERROR") << "A clumping threshold (-" << (char)c << ") must be a P-value in [0, 1]" << std::endl; return 1; }
+			(c == '1' ? clump->p1 : clump->p2) = t;
+			break;
+		}
 		case 'i': settings.in = optarg; break;
 		case 'o': settings.out = optarg; break;
 		case 'I': settings.ival_strings.push_back(optarg); break;
@@ -201,7 +216,8 @@ static int reduce_options(int argc, char** argv, bool prune, tomahawk::twk_ld_se
 		case 'P':
 			settings.minP = atof(optarg);
 			if (!(settings.minP >= 1)) {
-				std::cerr << stamp("ERROR") << (prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
+				std::cerr << stamp("ERROR") << (cmd == REDUCE_CLUMP ? "Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run" :
+				                                prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
 				                                      : "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run") << std::endl;
 				return 1;
 			}
@@ -228,6 +244,8 @@ static int reduce_options(int argc, char** argv, bool prune, tomahawk::twk_ld_se
 		}
 	}
 	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
+	if (clump && clump->assoc.empty()) { std::cerr << stamp("ERROR") << "No association file specified (-a)..." << std::endl; return 1; }
+	if (clump && clump->p1 > clump->p2) { std::cerr << stamp("ERROR") << "The index threshold (-1) cannot be above the secondary threshold (-2)" << std::endl; return 1; }
 	return 0;
 }
 
@@ -237,7 +255,7 @@ static int ldscore(int argc, char** argv) {
 	settings.minR2 = 0;
 	settings.out = "-";
 	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, false, settings, engine_options)) return 1;
+	if (reduce_options(argc, argv, REDUCE_SCORE, settings, engine_options)) return 1;
 	program_message();
 	std::cerr << stamp("LOG") << "Calling ldscore..." << std::endl;
 	tomahawk::twk_ld ld;
@@ -275,12 +293,63 @@ static int prune(int argc, char** argv) {
 	tomahawk::twk_ld_settings settings;      // (-r: calc's default)
 	settings.out = "-";
 	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, true, settings, engine_options)) return 1;
+	if (reduce_options(argc, argv, REDUCE_PRUNE, settings, engine_options)) return 1;
 	program_message();
 	std::cerr << stamp("LOG") << "Calling prune..." << std::endl;
 	tomahawk::twk_ld ld;
 	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
 	return ld.Prune(settings) ? 0 : 1;
+}
+
+// `tomahawk clump` (not in the reference): LD clumping (PLINK's --clump) over the records `calc` would write, decided on the GPU.
+static void clump_usage() {
+	program_message();
+	std::cerr <<
+	"About:  LD clumping: the variants are visited from the smallest association P-value upwards, up\n"
+	"        to the index threshold; a visited variant that belongs to no clump yet becomes an index\n"
+	"        variant and claims every variant that belongs to no clump, passes the secondary threshold\n"
+	"        and forms a pair with it that `calc` would report under the same options (like PLINK's\n"
+	"        --clump); decided on the GPU (no .two is written).\n\n"
+	"Usage:  tomahawk clump [options] -i <in.twk> -a <assoc.txt> [-o <out.tsv>]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -a FILE   association file (required): text, split on tabs or spaces, '#' lines ignored;\n"
+	"            columns contig, pos (1-based, as `ldscore` / `prune` / `view` print it), P (NA / nan:\n"
+	"            none); further columns are ignored.  Every selected variant at a (contig, pos) gets\n"
+	"            that P; variants the file does not name get none.  The same (contig, pos) twice or a\n"
+	"            P outside [0, 1] is an error\n"
+	"  -1 FLOAT  index threshold: a variant with P at or below it may start a clump (default: 1e-4)\n"
+	"  -2 FLOAT  secondary threshold: a variant with P at or below it may be claimed (default: 1e-2)\n"
+	"  -o FILE   output text file (- for stdout; default: -)\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -w INT    sliding window width in bases\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value: pairs at or above it are in LD (default: 0.1)\n"
+	"  -P FLOAT  accepted only as 1: clumping looks at every record, Fisher's test is not run\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"  (-c / -C are refused: the walk needs every pair)\n"
+	"  (-r and -w keep calc's defaults: the same flags as calc mean the same pairs in LD)\n"
+	"Output: '#' header lines, among them ##clumps=<index variants>,members=<claimed>,total=<variants>,edges=<pairs in LD>,\n"
+	"        then per variant: contig <TAB> pos <TAB> P <TAB> index_contig <TAB> index_pos\n"
+	"        (P: NA where the variant has none; index_contig, index_pos: . where it is in no clump;\n"
+	"        an index variant names itself)\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int clump(int argc, char** argv) {
+	if (argc < 3) { clump_usage(); return 1; }
+	tomahawk::twk_ld_settings settings;      // (-r, -w: calc's defaults)
+	settings.out = "-";
+	tomahawk::twk_clump_settings cs;
+	std::vector<std::pair<std::string, long long>> engine_options;
+	if (reduce_options(argc, argv, REDUCE_CLUMP, settings, engine_options, &cs)) return 1;
+	program_message();
+	std::cerr << stamp("LOG") << "Calling clump..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Clump(settings, cs) ? 0 : 1;
 }
 
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
@@ -575,6 +644,7 @@ static int run_main(int argc, char** argv) {
 		             "  scalc    linkage disequilibrium of one site against its neighbourhood\n"
 		             "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n"
 		             "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n"
+		             "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n"
 		             "  sort     sort a .two file\n"
 		             "  view     convert, filter and slice .two files\n"
 		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
@@ -590,6 +660,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "calc") == 0) return calc(argc, argv);
 	if (strcmp(argv[1], "ldscore") == 0) return ldscore(argc, argv);
 	if (strcmp(argv[1], "prune") == 0) return prune(argc, argv);
+	if (strcmp(argv[1], "clump") == 0) return clump(argc, argv);
 	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
 	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
 	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
@@ -598,7 +669,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
 	return 1;
 }
 

@@ -16,6 +16,8 @@
 #include <ctime>
 #include <iomanip>
 #include <iostream>
+#include <limits>
+#include <map>
 #include <fstream>
 #include <regex>
 #include <sstream>
@@ -1076,6 +1078,145 @@ bool twk_ld::Prune(const twk_ld_settings& s) {
 	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the keep flags..." << std::endl; return false; }
 	std::cerr << stamp("LOG") << "Pruned: kept " << pretty(n_kept) << " of " << pretty(M) << " variants; " << pretty(n_edges) << " pairs in LD among "
 	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	return true;
+}
+
+// The association file of `tomahawk clump` (include/twk_ld.h): (contig name, 1-based position) -> P, NaN for "no P value".  -> false
+// after an error message: unreadable, a malformed line, a P outside [0, 1], the same key twice.
+namespace {
+struct AssocEntry { double p; bool used; };
+using AssocMap = std::map<std::pair<std::string, uint64_t>, AssocEntry>;
+bool read_assoc(const std::string& path, AssocMap& out) {
+	std::ifstream in(path);
+	if (!in.good()) { std::cerr << stamp("ERROR") << "Failed to open the association file: " << path << "..." << std::endl; return false; }
+	std::string text;
+	for (uint64_t n_line = 1; std::getline(in, text); ++n_line) {
+		if (!text.empty() && text.back() == '\r') text.pop_back();
+		if (text.empty() || text[0] == '#') continue;
+		std::vector<std::string> col;
+		for (size_t at = 0; at < text.size() && col.size() < 3;) {
+			const size_t from = text.find_first_not_of(" \t", at);
+			if (from == std::string::npos) break;
+			const size_t to = text.find_first_of(" \t", from);
+			col.push_back(text.substr(from, to == std::string::npos ? std::string::npos : to - from));
+			at = to == std::string::npos ? text.size() : to;
+		}
+		if (col.empty()) continue;
+		if (col.size() < 3) { std::cerr << stamp("ERROR") << path << ":" << n_line << ": expected contig, position and P..." << std::endl; return false; }
+		char* end = nullptr;
+		const unsigned long long pos = strtoull(col[1].c_str(), &end, 10);
+		if (col[1].empty() || *end || col[1][0] == '-' || pos == 0) { std::cerr << stamp("ERROR") << path << ":" << n_line << ": not a 1-based position: " << col[1] << std::endl; return false; }
+		std::string low = col[2];
+		for (char& ch : low) ch = (char)tolower((unsigned char)ch);
+		double pv = std::numeric_limits<double>::quiet_NaN();
+		if (low != "na" && low != "nan" && low != ".") {
+			pv = strtod(col[2].c_str(), &end);
+			if (*end || !(pv >= 0.0 && pv <= 1.0)) { std::cerr << stamp("ERROR") << path << ":" << n_line << ": not a P value in [0, 1]: " << col[2] << std::endl; return false; }
+		}
+		if (!out.emplace(std::make_pair(col[0], (uint64_t)pos), AssocEntry{pv, false}).second) {
+			std::cerr << stamp("ERROR") << path << ":" << n_line << ": " << col[0] << ":" << pos << " is named twice..." << std::endl; return false;
+		}
+	}
+	return true;
+}
+}  // namespace
+
+// `tomahawk clump`: LD clumping of the selection (twk_hip_ld_clump: the edges are the records Compute would write, seen from both ends,
+// decided on the GPU and walked there in P order, no record is formed), as text: one line per variant with its index variant.  The
+// association file is read and checked before the input is opened or a device touched; the input is then loaded exactly as Prune
+// loads it; one GPU; the whole triangle (no -c / -C).  Not in the reference.
+bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
+	using clock = std::chrono::steady_clock;
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "Clumping looks at every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
+	if (settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space: the walk needs every pair (no -c / -C)..." << std::endl; return false; }
+	if (!(cs.p1 >= 0 && cs.p1 <= cs.p2 && cs.p2 <= 1)) { std::cerr << stamp("ERROR") << "The clumping thresholds must satisfy 0 <= p1 <= p2 <= 1..." << std::endl; return false; }
+	if (cs.assoc.empty()) { std::cerr << stamp("ERROR") << "No association file provided..." << std::endl; return false; }
+	AssocMap assoc;
+	if (!read_assoc(cs.assoc, assoc)) return false;
+	Selection S;
+	bool nothing_to_do = false;
+	if (!select_blocks(settings, S, &nothing_to_do)) return false;
+	if (nothing_to_do) return true;
+	const uint32_t M = S.M;
+	DeviceCtxs dc;
+	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
+	twk_hip_ctx* ctx = dc.ctx[0];
+	const auto t_load = clock::now();
+	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
+	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
+	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
+	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
+	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
+
+	// every variant of the selection at a (contig, position) the file names gets that P
+	const auto& contigs = S.reader.hdr.contigs;
+	std::vector<double> p(M, std::numeric_limits<double>::quiet_NaN());
+	uint64_t n_with_p = 0;
+	for (uint32_t v = 0; v < M; ++v) {
+		const uint32_t rid = mImpl->rid[v];
+		if (rid >= contigs.size()) continue;
+		const auto it = assoc.find(std::make_pair(contigs[rid].name, (uint64_t)mImpl->pos[v] + 1));
+		if (it == assoc.end()) continue;
+		it->second.used = true;
+		p[v] = it->second.p;
+		if (p[v] == p[v]) ++n_with_p;
+	}
+	uint64_t n_unmatched = 0;
+	for (const auto& kv : assoc) if (!kv.second.used) ++n_unmatched;
+	std::cerr << stamp("LOG") << "Association file: " << pretty(assoc.size()) << " lines, " << pretty(n_unmatched) << " name no selected variant; "
+	          << pretty(n_with_p) << " of " << pretty(M) << " variants have a P value." << std::endl;
+
+	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
+	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
+	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	std::vector<uint32_t> index_of(M, TWK_HIP_NO_CLUMP);
+	uint64_t np = 0, n_clumps = 0, n_members = 0, n_edges = 0;
+	const auto t0 = clock::now();
+	const int rc = twk_hip_ld_clump(ctx, mode, &f, 0, M, 0, options, (uint32_t)settings.l_window, p.data(), cs.p1, cs.p2, index_of.data(), &n_clumps, &n_members, &n_edges, &np);
+	if (!hip_ok(ctx, rc, "twk_hip_ld_clump")) return false;
+	mImpl->n_pairs = np;
+	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+
+	std::ofstream file;
+	const bool to_stdout = settings.out.empty() || settings.out == "-";
+	if (!to_stdout) {
+		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
+		file.open(settings.out, std::ios::out | std::ios::trunc);
+		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return false; }
+	}
+	std::ostream& os = to_stdout ? std::cout : file;
+	os << "##tomahawk_clumpVersion=" << TWK_AMD_VERSION << "\n"
+	   << "##tomahawk_clumpCommand=" << command_line() << "; Date=" << datetime() << "\n"
+	   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
+	char line[256];
+	snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
+	os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n";
+	snprintf(line, sizeof(line), "##thresholds=p1=%.17g,p2=%.17g\n", cs.p1, cs.p2);
+	os << line;
+	snprintf(line, sizeof(line), "##clumps=%llu,members=%llu,total=%u,edges=%llu\n", (unsigned long long)n_clumps, (unsigned long long)n_members, M, (unsigned long long)n_edges);
+	os << line << "#contig\tpos\tP\tindex_contig\tindex_pos\n";
+	std::string text;
+	auto contig_name = [&](uint32_t v) -> std::string { const uint32_t rid = mImpl->rid[v]; return rid < contigs.size() ? contigs[rid].name : std::string("."); };
+	for (uint32_t v = 0; v < M; ++v) {
+		// (contig and position as `ldscore` prints them: the contig's name, the 1-based position)
+		text += contig_name(v);
+		if (p[v] == p[v]) snprintf(line, sizeof(line), "\t%u\t%.17g\t", mImpl->pos[v] + 1, p[v]);
+		else snprintf(line, sizeof(line), "\t%u\tNA\t", mImpl->pos[v] + 1);
+		text += line;
+		const uint32_t ix = index_of[v];
+		if (ix < M) { text += contig_name(ix); snprintf(line, sizeof(line), "\t%u\n", mImpl->pos[ix] + 1); text += line; }
+		else text += ".\t.\n";
+		if (text.size() > (1u << 20)) { os << text; text.clear(); }
+	}
+	os << text;
+	os.flush();
+	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the clumps..." << std::endl; return false; }
+	std::cerr << stamp("LOG") << "Clumped: " << pretty(n_clumps) << " index variants claimed " << pretty(n_members) << " of " << pretty(M) << " variants; " << pretty(n_edges)
+	          << " pairs in LD among " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
 	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
 	return true;
 }

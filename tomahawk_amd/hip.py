@@ -18,6 +18,7 @@ ABI_VERSION = 5                 # TWK_HIP_ABI_VERSION of include/twk_hip.h (stru
 MODE_PHASED, MODE_UNPHASED, MODE_AUTO = 1, 2, 3
 # option bits of twk_hip_tile_desc.window / the `window` argument of ld_all / ld_region (TWK_HIP_OPT_*)
 OPT_WINDOW, OPT_KEEP_LOW_AC, OPT_REF_COMPAT, OPT_R2_SCREEN = 1, 2, 4, 8
+NO_CLUMP = 0xFFFFFFFF      # TWK_HIP_NO_CLUMP: ld_clump's index_of for a variant in no clump
 E_OVERFLOW = -4
 
 # twk_hip_record (include/twk_hip.h): 104 bytes
@@ -191,6 +192,10 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_prune.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_prune_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_clump.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p,
+                                     C.c_double, C.c_double, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)]
+    lib.twk_hip_clump_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_shard_rows.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_plan_region.argtypes = [p, p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
@@ -494,6 +499,32 @@ class HipLd:
         """Of the last ld_prune call (twk_hip_prune_last): the walk kernel's device time and the adjacency bitmap's size."""
         ms, b = C.c_double(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_prune_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_prune_last")
+        return {"walk_ms": ms.value, "bitmap_bytes": b.value}
+
+    def ld_clump(self, mode: int, filters: Filters, p, p1: float = 1e-4, p2: float = 1e-2, a0: int = 0, n: int | None = None,
+                 tile_variants: int = 0, window: int = 0, l_window: int = 0):
+        """LD clumping (twk_hip_ld_clump) of the triangle of variants [a0, a0 + n): the variants are visited in ascending P (p: one
+        float64 per variant, NaN for none) up to p1; a visited variant that belongs to no clump becomes an index variant and claims
+        every free variant with P <= p2 that forms a record with it that ld_region would report; decided and walked on the device -
+        no record is formed.  filters.minP must be >= 1.  -> (index_of uint32[M], n_clumps, n_members, n_edges, n_pairs);
+        index_of is NO_CLUMP where a variant belongs to no clump."""
+        M = self.n_variants
+        n = M - a0 if n is None else n
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if p.shape != (M,):
+            raise ValueError(f"p must hold one value per variant ({M}), not {p.shape}")
+        index_of = np.full(M, NO_CLUMP, dtype=np.uint32)
+        n_clumps, n_members, n_edges, npairs = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_clump(self._ctx, mode, C.byref(f), a0, n, tile_variants, int(window), l_window, p.ctypes.data,
+                                               float(p1), float(p2), index_of.ctypes.data, C.byref(n_clumps), C.byref(n_members),
+                                               C.byref(n_edges), C.byref(npairs)), "twk_hip_ld_clump")
+        return index_of, n_clumps.value, n_members.value, n_edges.value, npairs.value
+
+    def clump_last(self) -> dict:
+        """Of the last ld_clump call (twk_hip_clump_last): the walk kernel's device time and the adjacency bitmap's size."""
+        ms, b = C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_clump_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_clump_last")
         return {"walk_ms": ms.value, "bitmap_bytes": b.value}
 
     def fisher_exact(self, tables: np.ndarray, ordered: bool = True):
