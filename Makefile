@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -87,6 +87,12 @@ buffers-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/buffers_check.cpp -o build/buffers_check
 	./build/buffers_check
+
+# The LD matrix fill's slot arithmetic and guards (csrc/hip/ld_matrix_index.h) played lane by lane on the host (csrc/tools/matrix_index_check.cpp)
+matrix-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/matrix_index_check.cpp -o build/matrix_index_check
+	./build/matrix_index_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

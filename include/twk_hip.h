@@ -36,6 +36,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_score - LD scores - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_prune / twk_hip_prune_last - LD pruning - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_clump / twk_hip_clump_last - LD clumping - are two entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_matrix / twk_hip_matrix_last - the dense LD matrix - are two entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -351,6 +352,37 @@ int twk_hip_ld_clump(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
                      uint32_t* index_of, uint64_t* n_clumps, uint64_t* n_members, uint64_t* n_edges, uint64_t* n_pairs);
 /* Of the context's last twk_hip_ld_clump call: the device time of its walk kernel in ms and the size of its bitmap (either may be NULL). */
 int twk_hip_clump_last(const twk_hip_ctx* ctx, double* walk_ms, uint64_t* bitmap_bytes);
+
+/* The dense LD matrix of the triangle of variants [a0, a0 + n) in file order, without records: the input of fine-mapping and of
+ * Bayesian polygenic scores.  mode, filters, tile_variants, window (the option bits) and l_window are those of twk_hip_ld_region.
+ *   stat   TWK_HIP_STAT_R: copysign(rec.R, rec.D) - the record's R is sqrt(R2) and never negative, the matrix's r carries D's sign;
+ *          TWK_HIP_STAT_R2: rec.R2;  TWK_HIP_STAT_D: rec.D;  TWK_HIP_STAT_DPRIME: rec.Dprime
+ *   out    HOST array of n rows of ld >= n floats.  For u != v relative to a0: if twk_hip_ld_region over that triangle would report a
+ *          record for the two variants, out[u * ld + v] is that record's statistic, computed in double and rounded once to float32
+ *          ((float)x, to nearest); otherwise it is `fill`, bit for bit (any pattern, NaN included) - the low-allele-count skip,
+ *          D == 0, outside the window, below a cut-off.  All four statistics are symmetric in the two variants: out[u * ld + v] and
+ *          out[v * ld + u] hold the same bits.  With fill = 0 and minR2 = 0 this is the matrix a fine-mapper expects; with minR2 > 0
+ *          the sparsified one.
+ *          THE DIAGONAL is 1.0f for R, R2 and DPRIME, whatever the variant's allele count, and `fill` for D: no record pins a
+ *          variant's variance under missing data, and the function invents none.
+ *          The columns n .. ld - 1 of every row are not written.
+ *   *n_records  (may be NULL) the off-diagonal pairs that received a value, each pair once: the records `calc` would have written;
+ *   *n_pairs    (may be NULL) the pairs evaluated.
+ * Always the whole triangle on one device and always the matrix form of the contraction: TWK_HIP_OPT_R2_SCREEN is ignored, as for a
+ * score; there is no part / n_parts and no rectangle.  Every entry is written by plain stores, by exactly one lane of exactly one
+ * launch (in the default mode the two passes select disjoint pairs) or by the preset: no atomics, two calls return the same bytes.
+ * TWK_HIP_E_INVALID before any launch: minP < 1, out NULL, ld < n, n == 0, a slice beyond the last variant, an unknown stat.
+ * Device memory: n * n * 4 bytes for the length of the call; TWK_HIP_E_NOMEM with the size in twk_hip_last_error when the device
+ * cannot give it.  The matrix leaves the device in one 2-D copy that honours ld.
+ * twk_hip_timing: the fill kernels count as the math stage (stats_ms, stats_launches, variant_pairs); the copy is reported by
+ * twk_hip_matrix_last.  There is NO reference counterpart. */
+enum { TWK_HIP_STAT_R = 0, TWK_HIP_STAT_R2 = 1, TWK_HIP_STAT_D = 2, TWK_HIP_STAT_DPRIME = 3 };
+int twk_hip_ld_matrix(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                      uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                      int32_t stat, float fill, float* out, uint64_t ld,
+                      uint64_t* n_records, uint64_t* n_pairs);
+/* Of the context's last twk_hip_ld_matrix call: the time of its device-to-host copy in ms and the matrix's bytes (either may be NULL). */
+int twk_hip_matrix_last(const twk_hip_ctx* ctx, double* copy_ms, uint64_t* matrix_bytes);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

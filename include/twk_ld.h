@@ -49,6 +49,13 @@ struct twk_clump_settings {
 	double p2 = 1e-2;           // secondary threshold: a variant with P <= p2 may be claimed
 };
 
+// What Matrix needs beyond twk_ld_settings.
+struct twk_matrix_settings {
+	int stat = 0;               // TWK_HIP_STAT_R (signed r), _R2, _D or _DPRIME (include/twk_hip.h)
+	float fill = 0.0f;          // the entry of a pair Compute would write no record for
+	bool text = false;          // PREFIX.ld (space-separated text, as FINEMAP reads it) instead of PREFIX.npy
+};
+
 class twk_ld {
 public:
 	twk_ld();
@@ -88,6 +95,14 @@ public:
 	// per variant of the selection, in file order, to settings.out: contig, position, P, and contig and position of its index variant.
 	// settings.minP must be 1 (the default).  `tomahawk clump` ends here.
 	bool Clump(const twk_ld_settings& settings, const twk_clump_settings& clump);
+	// Not in the reference: the dense LD matrix of the selection, the input of fine-mapping and of Bayesian polygenic scores.  Loads the
+	// .twk exactly as Prune does (-I intervals, -w, -p / -u, TWK_REF_COMPAT; -c / -C are refused) and fills an n x n float32 matrix on one
+	// GPU (twk_hip_ld_matrix): entry (u, v) is matrix.stat of the record Compute would write for the two variants - r carries D's sign -
+	// and matrix.fill where it would write none; the diagonal is 1 (for D: the fill).  No record is formed.  settings.out is a PREFIX:
+	// PREFIX.npy (NumPy format 1.0, '<f4', C order, shape (n, n)) or, with matrix.text, PREFIX.ld (one row per line, space-separated,
+	// 9 significant digits), and always PREFIX.variants.tsv: one "contig <TAB> pos" line per row, as Score prints them.
+	// settings.minP must be 1 (the default).  `tomahawk ldmatrix` ends here.
+	bool Matrix(const twk_ld_settings& settings, const twk_matrix_settings& matrix);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

@@ -8,6 +8,7 @@
 //   score (ld_score.hip.h) cells -> r2 -> per-variant sums, in place of the math stage (twk_hip_ld_score)
 //   prune (ld_prune.hip.h) cells -> keep -> adjacency bitmap, in place of the math stage, and the greedy walk over it (twk_hip_ld_prune)
 //   clump (ld_clump.hip.h) cells -> keep -> the bitmap's bits (u, v) and (v, u), likewise, and the walk over it in P order (twk_hip_ld_clump)
+//   matrix (ld_matrix.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a dense float32 matrix (twk_hip_ld_matrix)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -39,6 +40,7 @@
 #include "ld_score.hip.h"
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
+#include "ld_matrix.hip.h"
 #include "ld_plan.h"
 #include "twk_delivery.h"
 #include "twk_buffers.h"
@@ -118,7 +120,8 @@ struct LaunchForm {
 	bool score = false;            // the score epilogue in place of math, Fisher and records (ld_score.hip.h): always through a matrix
 	bool prune = false;            // the prune epilogue in their place (ld_prune.hip.h): likewise
 	bool clump = false;            // the clump epilogue (ld_clump.hip.h): the prune epilogue with both bits of an edge
-	bool reduces() const { return score || prune || clump; }      // ... either way the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
+	bool matrix = false;           // the matrix epilogue (ld_matrix.hip.h): one statistic of every record stored into the call's dense matrix
+	bool reduces() const { return score || prune || clump || matrix; }      // ... either way the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
@@ -163,6 +166,7 @@ struct Slot {                      // one in-flight tile (double buffered)
 	PinnedBuf<ScoreArgs> h_sc_args; DevBuf<ScoreArgs> d_sc_args;         // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
 	PinnedBuf<PruneArgs> h_pr_args; DevBuf<PruneArgs> d_pr_args;         // prune launches (ld_prune.hip.h): the same two blocks
 	PinnedBuf<ClumpArgs> h_cl_args; DevBuf<ClumpArgs> d_cl_args;         // clump launches (ld_clump.hip.h): likewise
+	PinnedBuf<MatrixArgs> h_mx_args; DevBuf<MatrixArgs> d_mx_args;       // matrix launches (ld_matrix.hip.h): likewise
 };
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
@@ -293,7 +297,7 @@ struct twk_hip_ctx {
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
 	// twk_hip_ld_prune: the launches of the running call ballot `keep` into the adjacency bitmap of the call's triangle (ld_prune.hip.h)
 	bool prune_on = false;
-	bool reduce_on() const { return score_on || prune_on || clump_on; }
+	bool reduce_on() const { return score_on || prune_on || clump_on || matrix_on; }
 	PruneMap prune_map{};
 	DevBuf<unsigned long long> d_prune_adj, d_prune_removed, d_prune_counts;     // the bitmap (lives for the call), `removed` beyond LDS, [0] edges [1] kept
 	DevBuf<uint8_t> d_prune_keep;                                                // [M]
@@ -304,6 +308,11 @@ struct twk_hip_ctx {
 	DevBuf<unsigned long long> d_clump_adj, d_clump_taken, d_clump_counts;       // the bitmap (lives for the call), taken0 / `taken` beyond LDS, [0] edges [1] clumps [2] members
 	DevBuf<uint32_t> d_clump_order, d_clump_index;                               // the candidates in visiting order; index_of [M]
 	double clump_walk_ms = 0; uint64_t clump_bitmap_bytes = 0;                   // of the last call (twk_hip_clump_last)
+	// twk_hip_ld_matrix: the launches of the running call store one statistic per record into the call's dense matrix (ld_matrix.hip.h)
+	bool matrix_on = false;
+	MatrixMap matrix_map{};
+	DevBuf<float> d_matrix; DevBuf<unsigned long long> d_matrix_count;           // the n x n matrix (lives for the call); [0] records
+	double matrix_copy_ms = 0; uint64_t matrix_bytes = 0;                        // of the last call (twk_hip_matrix_last)
 	char err[512] = {0};
 };
 
@@ -334,7 +343,7 @@ void free_slots(twk_hip_ctx* c) {
 	for (auto& s : c->slot) {
 		s.C.reset(); s.out.reset(); s.keys.reset(); s.vals.reset(); s.sorted.reset();
 		s.sc_sum.reset(); s.sc_n.reset(); s.h_sc_args.reset(); s.d_sc_args.reset(); s.h_pr_args.reset(); s.d_pr_args.reset();
-		s.h_cl_args.reset(); s.d_cl_args.reset();
+		s.h_cl_args.reset(); s.d_cl_args.reset(); s.h_mx_args.reset(); s.d_mx_args.reset();
 		for (int k = 0; k < 2; ++k) { s.h_tiles[k].reset(); s.d_tiles[k].reset(); }
 	}
 }
@@ -346,6 +355,7 @@ void free_problem(twk_hip_ctx* c) {
 	c->d_score_sum.reset(); c->d_score_n.reset();
 	c->d_prune_adj.reset(); c->d_prune_removed.reset(); c->d_prune_counts.reset(); c->d_prune_keep.reset();
 	c->d_clump_adj.reset(); c->d_clump_taken.reset(); c->d_clump_counts.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
+	c->d_matrix.reset(); c->d_matrix_count.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -769,7 +779,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 }
 
 // The form of the (first) launch of a tile of this plan, as the context stands: the one place that reads the options "fused" and "three",
-// FUSED_MAX_CHUNKS, fused_ok, three_ok, score_on, prune_on and clump_on for it.
+// FUSED_MAX_CHUNKS, fused_ok, three_ok, score_on, prune_on, clump_on and matrix_on for it.
 // A screen in front of the math needs plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
 // pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short
 // enough that no tile's K range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h)
@@ -777,7 +787,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 // reports why).
 LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
 	LaunchForm lf;
-	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.prune = c->prune_on; lf.clump = c->clump_on; lf.keep_three = c->opt.three == 2;
+	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.prune = c->prune_on; lf.clump = c->clump_on; lf.matrix = c->matrix_on; lf.keep_three = c->opt.three == 2;
 	const int k = set_kind(pl.set1);
 	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
 	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
@@ -869,6 +879,24 @@ int launch_clump(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	return TWK_HIP_OK;
 }
 
+// The matrix epilogue of a launch whose count matrix is in the slot's C (ld_matrix.hip.h): the chosen statistic of every pair with a
+// record stored at (u, v) and at (v, u) of the call's matrix.  The diagonal and the copy to the host follow the call's last launch
+// (twk_hip_ld_matrix).
+int launch_matrix(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
+	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
+	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
+	if (!t.nA || !t.nB) return TWK_HIP_OK;
+	HIPCHK(c, s.h_mx_args.reserve(2, 2, nullptr));
+	HIPCHK(c, s.d_mx_args.reserve(2, 2, nullptr));
+	const uint32_t gx = (t.nB + MATRIX_THREADS - 1) / MATRIX_THREADS, gy = (t.nA + MATRIX_ROWS - 1) / MATRIX_ROWS;
+	if (gy > 0xFFFFu) return TWK_HIP_E_INVALID;
+	s.h_mx_args[which].p = p; s.h_mx_args[which].mm = c->matrix_map;      // (the slot's previous launch has been waited for: its copy is done)
+	HIPCHK(c, hipMemcpyAsync(s.d_mx_args + which, s.h_mx_args + which, sizeof(MatrixArgs), hipMemcpyHostToDevice, c->s_compute));
+	hipLaunchKernelGGL(k_ld_matrix_fill, dim3(gx, gy), dim3(MATRIX_THREADS), 0, c->s_compute, (const MatrixArgs*)(s.d_mx_args + which));
+	HIPCHK(c, hipGetLastError());
+	return TWK_HIP_OK;
+}
+
 // Survivors are appended with an atomic counter, in no order.  They leave the device in (idxA, idxB) order
 // - the order the writer puts them in the file, which makes a one-GPU run's output deterministic - by a key
 // sort of (idxA << bits | idxB, position) and a gather.  Key and position are written by the math kernels where the
@@ -899,7 +927,7 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 }
 
 // The end of every launch, on the compute stream: Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is
-// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune or clump launch has no survivors, and no
+// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune, clump or matrix launch has no survivors, and no
 // test to run: minP >= 1 drops nothing), for a band launch the sort of its survivors (Launch::presorted), the counters' copy to the host
 // and ev_s1.
 // The band launch's sort is over as many slots as there were candidates (unused slots carry the all-ones key, like records the Fisher
@@ -932,7 +960,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
 	const LaunchForm form = launch_form(c, pl, f);
 	const Geometry g = tile_geometry(pl.Pmax, t);
-	if (form.reduces()) capacity = 1;              // a score, prune or clump launch keeps no survivors (and is never a band launch: always the matrix form)
+	if (form.reduces()) capacity = 1;              // a score, prune, clump or matrix launch keeps no survivors (and is never a band launch: always the matrix form)
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
@@ -1009,6 +1037,8 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		rc = launch_prune(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
 	} else if (form.clump) {
 		rc = launch_clump(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
+	} else if (form.matrix) {
+		rc = launch_matrix(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
 	} else {
 		const StatsParams p = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
 		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -1019,6 +1049,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		if (form.score) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else if (form.prune) { rc = launch_prune(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else if (form.clump) { rc = launch_clump(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
+		else if (form.matrix) { rc = launch_matrix(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else {
 			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
 			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -2231,7 +2262,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = !c->reduce_on();      // a score, a prune or a clump looks at every pair: no screen in front of the matrix
+	c->fused_ok = c->three_ok = !c->reduce_on();      // a score, a prune, a clump or a matrix looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2488,6 +2519,68 @@ int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_b
 	if (!c) return TWK_HIP_E_INVALID;
 	if (walk_ms) *walk_ms = c->clump_walk_ms;
 	if (bitmap_bytes) *bitmap_bytes = c->clump_bitmap_bytes;
+	return TWK_HIP_OK;
+}
+
+// LD matrix: the same planner and pipeline with the matrix epilogue; the matrix is preset to the fill in front of the launches, gets
+// its diagonal behind the last of them and leaves in one 2-D copy that honours the caller's row pitch.
+int twk_hip_ld_matrix(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                      int32_t stat, float fill, float* out, uint64_t ld, uint64_t* n_records, uint64_t* n_pairs) {
+	if (!c || !f || !out || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
+	if (stat != TWK_HIP_STAT_R && stat != TWK_HIP_STAT_R2 && stat != TWK_HIP_STAT_D && stat != TWK_HIP_STAT_DPRIME) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M || ld < n) return TWK_HIP_E_INVALID;
+	HIPCHK(c, hipSetDevice(c->device));
+	const size_t cells = (size_t)n * n;
+	{	// the dense matrix: n * n floats, whatever the window
+		const hipError_t e = c->d_matrix.reserve(cells, cells, nullptr);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			snprintf(c->err, sizeof(c->err), "the LD matrix of %u variants needs %zu bytes of device memory: %s", n, cells * sizeof(float), hipGetErrorString(e));
+			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+		}
+	}
+	// (the matrix goes back when the call ends, whichever way: gigabytes that a record run behind this call may need)
+	struct MatrixOn { twk_hip_ctx* c; ~MatrixOn() { c->matrix_on = false; c->matrix_map = MatrixMap{}; (void)hipDeviceSynchronize(); c->d_matrix.reset(); } } on{c};
+	HIPCHK(c, c->d_matrix_count.reserve(1, 1, nullptr));
+	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
+	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_matrix.get(), (int)fill_bits, cells, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_matrix_count, 0, sizeof(unsigned long long), c->s_compute));
+	c->matrix_map = MatrixMap{c->d_matrix, c->d_matrix_count, a0, n, stat};
+	c->matrix_copy_ms = 0; c->matrix_bytes = cells * sizeof(float);
+	c->matrix_on = true;
+	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a matrix.  A single variant has no pair.)
+	int rc = n < 2 ? TWK_HIP_OK
+	               : region_dispatch(c, RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
+	                                               nullptr, nullptr, n_pairs, nullptr});
+	if (n < 2 && n_pairs) *n_pairs = 0;
+	if (rc == TWK_HIP_OK) {
+		unsigned long long count = 0;
+		Event w0, w1;
+		HIPCHK(c, hipEventCreate(&w0.e)); HIPCHK(c, hipEventCreate(&w1.e));
+		if (stat != TWK_HIP_STAT_D)      // (D: the diagonal keeps the preset fill - no launch stores on it)
+			hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, c->d_matrix.get(), n, 1.0f);
+		hipError_t e = hipGetLastError();
+		if (e == hipSuccess) e = hipEventRecord(w0.e, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), c->d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(&count, c->d_matrix_count, sizeof(count), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "LD matrix: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
+		else {
+			if (n_records) *n_records = count;
+			float ms = 0;
+			if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->matrix_copy_ms = ms;
+		}
+	}
+	flush_graveyard(c);
+	return rc;
+}
+
+int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (copy_ms) *copy_ms = c->matrix_copy_ms;
+	if (matrix_bytes) *matrix_bytes = c->matrix_bytes;
 	return TWK_HIP_OK;
 }
 

@@ -164,11 +164,11 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-// The options `ldscore`, `prune` and `clump` share (-P is accepted only as 1 by all; `prune` and `clump` have no -c / -C; `clump` adds its
-// association file and thresholds).  -> 0, or 1 after an error message.
-enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP };
+// The options `ldscore`, `prune`, `clump` and `ldmatrix` share (-P is accepted only as 1 by all; `prune`, `clump` and `ldmatrix` have no
+// -c / -C; `clump` adds its association file and thresholds, `ldmatrix` its statistic, fill and text switch).  -> 0, or 1 after an error message.
+enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP, REDUCE_MATRIX };
 static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options,
-                          tomahawk::twk_clump_settings* clump = nullptr) {
+                          tomahawk::twk_clump_settings* clump = nullptr, tomahawk::twk_matrix_settings* matrix = nullptr) {
 	const bool prune = cmd == REDUCE_PRUNE;
 	static struct option long_options[] = {
 		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
@@ -176,13 +176,33 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 		{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 		{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
 		{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
+		{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
 		{0, 0, 0, 0}};
 	int c, option_index = 0;
-	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
+	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : matrix ? "i:o:t:puP:r:w:I:c:C:s:f:T?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
 		if (prune && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
 		if (cmd == REDUCE_CLUMP && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
+		if (cmd == REDUCE_MATRIX && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot fill a part of the pair space (-c / -C): the matrix needs every pair" << std::endl; return 1; }
 		if (!clump && (c == 'a' || c == '1' || c == '2')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
+		if (!matrix && (c == 's' || c == 'f' || c == 'T')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
 		switch (c) {
+		case 's': {
+			const std::string a(optarg);
+			if (a == "r") matrix->stat = TWK_HIP_STAT_R;
+			else if (a == "r2") matrix->stat = TWK_HIP_STAT_R2;
+			else if (a == "D") matrix->stat = TWK_HIP_STAT_D;
+			else if (a == "Dprime") matrix->stat = TWK_HIP_STAT_DPRIME;
+			else { std::cerr << stamp("ERROR") << "Unknown statistic (-s): " << a << " - one of r, r2, D, Dprime" << std::endl; return 1; }
+			break;
+		}
+		case 'f': {
+			char* end = nullptr;
+			const float v = strtof(optarg, &end);      // (nan and inf are numbers here: a fill may be either)
+			if (end == optarg || *end) { std::cerr << stamp("ERROR") << "The fill value (-f) must be a number: " << optarg << std::endl; return 1; }
+			matrix->fill = v;
+			break;
+		}
+		case 'T': matrix->text = true; break;
 		case 'a': clump->assoc = optarg; break;
 		case '1': case '2': {
 			char* end = nullptr;
@@ -216,7 +236,8 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 		case 'P':
 			settings.minP = atof(optarg);
 			if (!(settings.minP >= 1)) {
-				std::cerr << stamp("ERROR") << (cmd == REDUCE_CLUMP ? "Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run" :
+				std::cerr << stamp("ERROR") << (cmd == REDUCE_MATRIX ? "Cannot fill a matrix with a cutoff P-value below 1: the matrix holds every record and Fisher's exact test is not run" :
+				                                cmd == REDUCE_CLUMP ? "Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run" :
 				                                prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
 				                                      : "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run") << std::endl;
 				return 1;
@@ -245,6 +266,7 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 	}
 	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
 	if (clump && clump->assoc.empty()) { std::cerr << stamp("ERROR") << "No association file specified (-a)..." << std::endl; return 1; }
+	if (matrix && (settings.out.empty() || settings.out == "-")) { std::cerr << stamp("ERROR") << "No output prefix specified (-o)..." << std::endl; return 1; }
 	if (clump && clump->p1 > clump->p2) { std::cerr << stamp("ERROR") << "The index threshold (-1) cannot be above the secondary threshold (-2)" << std::endl; return 1; }
 	return 0;
 }
@@ -350,6 +372,52 @@ static int clump(int argc, char** argv) {
 	tomahawk::twk_ld ld;
 	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
 	return ld.Clump(settings, cs) ? 0 : 1;
+}
+
+// `tomahawk ldmatrix` (not in the reference): the dense LD matrix of a region, filled on the GPU from the records `calc` would write.
+static void ldmatrix_usage() {
+	program_message();
+	std::cerr <<
+	"About:  The dense LD matrix of the selected variants - the input of fine-mapping (SuSiE, FINEMAP)\n"
+	"        and of Bayesian polygenic scores (LDpred, PRS-CS): entry (u, v) is the chosen statistic of\n"
+	"        the pair `calc` would report under the same options, and the fill value where it would\n"
+	"        report none; r carries the sign of D.  The diagonal is 1 (for D: the fill value).  Filled\n"
+	"        on the GPU (no .two is written); n x n x 4 bytes on the device and on the host.\n\n"
+	"Usage:  tomahawk ldmatrix [options] -i <in.twk> -o <PREFIX>\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o PREFIX output prefix (required)\n"
+	"  -s STRING statistic: r, r2, D or Dprime (default: r)\n"
+	"  -f FLOAT  fill value of a pair without a record, nan allowed (default: 0)\n"
+	"  -T        write PREFIX.ld (text) instead of PREFIX.npy\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -w INT    sliding window width in bases: entries outside it are the fill value\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value: entries below it are the fill value (default: 0)\n"
+	"  -P FLOAT  accepted only as 1: the matrix holds every record, Fisher's test is not run\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"  (-c / -C are refused: the matrix needs every pair)\n"
+	"  (-r defaults to 0, as for ldscore: calc's 0.1 would punch holes into a matrix meant for fine-mapping)\n"
+	"Output: PREFIX.npy           the matrix as a NumPy file: float32, C order, shape (n, n); or, with -T,\n"
+	"        PREFIX.ld            the matrix as text: one row per line, space-separated, 9 significant digits\n"
+	"        PREFIX.variants.tsv  per row of the matrix: contig <TAB> pos\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int ldmatrix(int argc, char** argv) {
+	if (argc < 3) { ldmatrix_usage(); return 1; }
+	tomahawk::twk_ld_settings settings;
+	settings.minR2 = 0;
+	tomahawk::twk_matrix_settings ms;
+	std::vector<std::pair<std::string, long long>> engine_options;
+	if (reduce_options(argc, argv, REDUCE_MATRIX, settings, engine_options, nullptr, &ms)) return 1;
+	program_message();
+	std::cerr << stamp("LOG") << "Calling ldmatrix..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Matrix(settings, ms) ? 0 : 1;
 }
 
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
@@ -645,6 +713,7 @@ static int run_main(int argc, char** argv) {
 		             "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n"
 		             "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n"
 		             "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n"
+		             "  ldmatrix dense LD matrix of a region (signed r, r2, D or D'), filled on the GPU\n"
 		             "  sort     sort a .two file\n"
 		             "  view     convert, filter and slice .two files\n"
 		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
@@ -661,6 +730,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "ldscore") == 0) return ldscore(argc, argv);
 	if (strcmp(argv[1], "prune") == 0) return prune(argc, argv);
 	if (strcmp(argv[1], "clump") == 0) return clump(argc, argv);
+	if (strcmp(argv[1], "ldmatrix") == 0) return ldmatrix(argc, argv);
 	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
 	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
 	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
@@ -669,7 +739,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `ldmatrix`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
 	return 1;
 }
 

@@ -1221,6 +1221,105 @@ bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
 	return true;
 }
 
+// `tomahawk ldmatrix`: the dense LD matrix of the selection (twk_hip_ld_matrix: one statistic of every record Compute would write, stored
+// on the GPU at (u, v) and (v, u), no record is formed), as a NumPy file or as text, with the rows' variants next to it.  The input is
+// loaded exactly as Prune loads it; one GPU; the whole triangle (no -c / -C).  Not in the reference.
+bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
+	using clock = std::chrono::steady_clock;
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "The matrix holds every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
+	if (settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot fill a part of the pair space: the matrix needs every pair (no -c / -C)..." << std::endl; return false; }
+	if (ms.stat != TWK_HIP_STAT_R && ms.stat != TWK_HIP_STAT_R2 && ms.stat != TWK_HIP_STAT_D && ms.stat != TWK_HIP_STAT_DPRIME) {
+		std::cerr << stamp("ERROR") << "Unknown statistic: one of r, r2, D, Dprime..." << std::endl; return false;
+	}
+	if (settings.out.empty() || settings.out == "-") { std::cerr << stamp("ERROR") << "No output prefix provided: the matrix and its variant list are files..." << std::endl; return false; }
+	Selection S;
+	bool nothing_to_do = false;
+	if (!select_blocks(settings, S, &nothing_to_do)) return false;
+	if (nothing_to_do) return true;
+	const uint32_t M = S.M;
+	DeviceCtxs dc;
+	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
+	twk_hip_ctx* ctx = dc.ctx[0];
+	const auto t_load = clock::now();
+	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
+	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
+	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
+	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
+	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
+
+	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
+	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
+	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	std::vector<float> m((size_t)M * M);
+	uint64_t np = 0, n_recs = 0;
+	const auto t0 = clock::now();
+	const int rc = twk_hip_ld_matrix(ctx, mode, &f, 0, M, 0, options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np);
+	if (!hip_ok(ctx, rc, "twk_hip_ld_matrix")) return false;
+	mImpl->n_pairs = np; mImpl->n_records = n_recs;
+	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+
+	const std::string path = settings.out + (ms.text ? ".ld" : ".npy");
+	std::cerr << stamp("LOG", "WRITER") << "Opening " << path << "..." << std::endl;
+	std::ofstream file(path, std::ios::out | std::ios::trunc | std::ios::binary);
+	if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << path << "..." << std::endl; return false; }
+	if (!ms.text) {
+		// NumPy format 1.0: magic, version, a little-endian uint16 header length, the dictionary padded with spaces and ended by a
+		// newline so that the data begins on a multiple of 64 bytes
+		std::string dict = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(M) + ", " + std::to_string(M) + "), }";
+		const size_t fixed = 6 + 2 + 2;
+		const size_t total = (fixed + dict.size() + 1 + 63) / 64 * 64;
+		dict.append(total - fixed - dict.size() - 1, ' ');
+		dict += '\n';
+		const char head[fixed] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(dict.size() & 0xFF), (char)(dict.size() >> 8 & 0xFF)};
+		file.write(head, fixed);
+		file.write(dict.data(), (std::streamsize)dict.size());
+		file.write(reinterpret_cast<const char*>(m.data()), (std::streamsize)(m.size() * sizeof(float)));      // (the hosts this runs on are little-endian)
+	} else {
+		std::string text;
+		char num[32];
+		for (uint32_t u = 0; u < M; ++u) {
+			for (uint32_t v = 0; v < M; ++v) {
+				snprintf(num, sizeof(num), v ? " %.9g" : "%.9g", (double)m[(size_t)u * M + v]);
+				text += num;
+			}
+			text += '\n';
+			if (text.size() > (1u << 20)) { file << text; text.clear(); }
+		}
+		file << text;
+	}
+	file.flush();
+	if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the matrix..." << std::endl; return false; }
+	file.close();
+
+	const std::string vpath = settings.out + ".variants.tsv";
+	std::cerr << stamp("LOG", "WRITER") << "Opening " << vpath << "..." << std::endl;
+	std::ofstream vfile(vpath, std::ios::out | std::ios::trunc);
+	if (!vfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << vpath << "..." << std::endl; return false; }
+	{
+		std::string text;
+		char line[64];
+		for (uint32_t v = 0; v < M; ++v) {
+			const uint32_t rid = mImpl->rid[v];
+			// (contig and position as `ldscore` prints them: the contig's name, the 1-based position)
+			if (rid < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid].name; else text += '.';
+			snprintf(line, sizeof(line), "\t%u\n", mImpl->pos[v] + 1);
+			text += line;
+			if (text.size() > (1u << 20)) { vfile << text; text.clear(); }
+		}
+		vfile << text;
+	}
+	vfile.flush();
+	if (!vfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the variant list..." << std::endl; return false; }
+	static const char* const stat_names[] = {"r", "r2", "D", "Dprime"};
+	std::cerr << stamp("LOG") << "Matrix of " << stat_names[ms.stat] << ": " << pretty(M) << " x " << pretty(M) << ", " << pretty(n_recs) << " pairs with a value among "
+	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	return true;
+}
+
 // scalc: one target site against its neighbourhood (ld.cpp:673-876, LoadTargetSingle :123-255,
 // CalculateSingle ld_engine.cpp:2226-2332).
 bool twk_ld::ComputeSingle(bool verbose, bool) {

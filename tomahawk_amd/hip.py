@@ -19,6 +19,7 @@ MODE_PHASED, MODE_UNPHASED, MODE_AUTO = 1, 2, 3
 # option bits of twk_hip_tile_desc.window / the `window` argument of ld_all / ld_region (TWK_HIP_OPT_*)
 OPT_WINDOW, OPT_KEEP_LOW_AC, OPT_REF_COMPAT, OPT_R2_SCREEN = 1, 2, 4, 8
 NO_CLUMP = 0xFFFFFFFF      # TWK_HIP_NO_CLUMP: ld_clump's index_of for a variant in no clump
+STAT_R, STAT_R2, STAT_D, STAT_DPRIME = 0, 1, 2, 3      # TWK_HIP_STAT_*: the statistic ld_matrix fills in
 E_OVERFLOW = -4
 
 # twk_hip_record (include/twk_hip.h): 104 bytes
@@ -196,6 +197,9 @@ def load_library() -> C.CDLL:
                                      C.c_double, C.c_double, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                      C.POINTER(C.c_uint64)]
     lib.twk_hip_clump_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_matrix.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
+                                      C.c_int32, C.c_float, p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_matrix_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_shard_rows.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_plan_region.argtypes = [p, p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
@@ -526,6 +530,28 @@ class HipLd:
         ms, b = C.c_double(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_clump_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_clump_last")
         return {"walk_ms": ms.value, "bitmap_bytes": b.value}
+
+    def ld_matrix(self, mode: int, filters: Filters, stat: int = STAT_R, fill: float = 0.0, a0: int = 0, n: int | None = None,
+                  tile_variants: int = 0, window: int = 0, l_window: int = 0):
+        """The dense LD matrix (twk_hip_ld_matrix) of the triangle of variants [a0, a0 + n): entry (u, v) is the statistic - STAT_R
+        (signed: copysign(R, D)), STAT_R2, STAT_D or STAT_DPRIME - of the record ld_region would report for the two variants, rounded
+        once to float32, and `fill` (bit for bit) where it would report none; the diagonal is 1 (for STAT_D: fill).  Filled on the
+        device - no record is formed.  filters.minP must be >= 1.  -> (float32 ndarray (n, n), n_records, n_pairs)."""
+        M = self.n_variants
+        n = M - a0 if n is None else n
+        out = np.empty((max(n, 0), max(n, 0)), dtype=np.float32)
+        nrec, npairs = C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        # (the fill travels as a C float: a NaN's payload is kept as far as the platform's float conversions keep it)
+        self._check(self._lib.twk_hip_ld_matrix(self._ctx, mode, C.byref(f), a0, n, tile_variants, int(window), l_window, int(stat),
+                                                C.c_float(fill), out.ctypes.data, n, C.byref(nrec), C.byref(npairs)), "twk_hip_ld_matrix")
+        return out, nrec.value, npairs.value
+
+    def matrix_last(self) -> dict:
+        """Of the last ld_matrix call (twk_hip_matrix_last): the device-to-host copy's time and the matrix's size."""
+        ms, b = C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_matrix_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_matrix_last")
+        return {"copy_ms": ms.value, "matrix_bytes": b.value}
 
     def fisher_exact(self, tables: np.ndarray, ordered: bool = True):
         """Two-sided Fisher P of int32 tables [n, 4] = (n11, n12, n21, n22) through the engine's Fisher kernels
