@@ -55,6 +55,7 @@ def lib() -> C.CDLL:
         L.orc_fisher_exact.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_double)] * 3
         L.orc_phased_math.argtypes = [p, p, p, C.POINTER(Settings), p]
         L.orc_unphased_math.argtypes = [p, p, p, C.POINTER(Settings), p]
+        L.orc_pair.argtypes = [p, p, p, p, p, p, C.c_uint32, C.POINTER(Settings), C.c_int, p]
         L.orc_all_pairs.restype = C.c_uint64
         L.orc_all_pairs.argtypes = [p, p, p, C.c_uint32, C.c_uint32, C.POINTER(Settings), C.c_int, p]
         L.orc_all_pairs_rows.restype = C.c_uint64
@@ -138,6 +139,17 @@ def unphased_math(c9, A, B, st):
     c9 = np.ascontiguousarray(c9, dtype=np.uint64)
     A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
     ok = lib().orc_unphased_math(c9.ctypes.data, A.ctypes.data, B.ctypes.data, C.byref(st), rec.ctypes.data)
+    return (rec[0] if ok else None)
+
+
+def pair(a, ma, A, b, mb, B, n_samples, st, vector_only=False):
+    """One pair as all_pairs treats it (orc_pair: the low-AC skip, the mode, the slot mirror of sparse pairs with missing
+    data, then the math) -> record or None.  a / b: the variants' bitvectors, ma / mb: their masks or None."""
+    rec = np.zeros(1, dtype=RECORD_DTYPE)
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
+    ok = lib().orc_pair(a.ctypes.data, None if ma is None else ma.ctypes.data, A.ctypes.data,
+                        b.ctypes.data, None if mb is None else mb.ctypes.data, B.ctypes.data,
+                        n_samples, C.byref(st), int(vector_only), rec.ctypes.data)
     return (rec[0] if ok else None)
 
 

@@ -218,3 +218,44 @@ def test_three_product_rows_that_end_inside_their_last_chunk(hip, opt, N):
     opt.set("skip_pad", 0)
     r, _, _ = hip.ld_all(T.MODE_UNPHASED, f)
     assert _same(p, r)
+
+
+def test_forced_fused_screen_with_a_column_dosage_beyond_float(hip, opt):
+    """N = 10,000,000 (the sample count of test_gpu_configs.ten_million), a dozen variants, `-u`: the last two have an ALT
+    frequency near 0.999 and an odd dosage h + 2q above 2^24, which no float holds - and ScreenCountsUnphased's exact test takes
+    the column variant's dosage from the prefilter's float terms where k_screen3_pairs reads the integers.  fused = 2 (test hook)
+    fuses rows this long.  The last variant is a noisy copy of the one before (r2 near 0.5): with the cut-off on that pair's r2,
+    one ulp below and one ulp above it, the plain path, the forced fused forms and the three-product forms give the same records."""
+    N, M = 10_000_000, 12
+    rng = np.random.default_rng(44)
+    al = np.empty((M, N, 2), dtype=np.int8)
+    for v in range(M - 2):
+        al[v] = (rng.random(2 * N, dtype=np.float32) < rng.uniform(0.1, 0.5)).reshape(N, 2)
+    hap = rng.random(2 * N, dtype=np.float32) < 0.999
+    al[M - 2] = hap.reshape(N, 2)
+    al[M - 1] = (hap ^ (rng.random(2 * N, dtype=np.float32) < 0.001)).reshape(N, 2)
+    for v in (M - 2, M - 1):                             # an odd dosage: one more ALT allele where there is room
+        if int(al[v].sum(dtype=np.int64)) % 2 == 0:
+            al[v].reshape(-1)[np.flatnonzero(al[v].reshape(-1) == 0)[0]] = 1
+    data, mask, variants = util.upload(hip, al)
+    del al, hap
+    for v in (M - 2, M - 1):
+        ac = int(variants["ac"][v])
+        assert ac > 1 << 24 and ac % 2 == 1 and float(np.float32(ac)) != ac and 0.997 < ac / (2 * N) < 0.9995
+    mode = T.MODE_UNPHASED
+    opt.set("fused", 0); opt.set("three", 0)
+    base, _, _ = hip.ld_all(mode, T.Filters(minR2=0.0))
+    pair = base[(base["idxA"] == M - 2) & (base["idxB"] == M - 1)]
+    assert len(pair) == 1 and not (int(pair["flags"][0]) & 1) and 0.4 < pair["R2"][0] < 0.6, pair
+    x = float(pair["R2"][0])
+    for cut in (float(np.nextafter(x, 0.0)), x, float(np.nextafter(x, 1.0))):
+        want = base[base["R2"] >= cut]
+        assert len(want) == (1 if cut <= x else 0)
+        for fused in (0, 2):
+            for three in (0, 2):
+                opt.set("fused", fused); opt.set("three", three)
+                hip.timing_reset()
+                got, _, _ = hip.ld_all(mode, T.Filters(minR2=cut))
+                tm = hip.timing()
+                assert (tm["fused_launches"] > 0) == (fused == 2) and (tm["three_launches"] > 0) == (three == 2), (fused, three, tm)
+                assert _same(got, want), (cut, fused, three, len(got), len(want))

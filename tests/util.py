@@ -129,6 +129,152 @@ def extreme_alleles(M, N, seed, miss=False):
     return al
 
 
+def compositions(n, k):
+    """Every way to write n as an ordered sum of k non-negative cells -> int64 [C(n + k - 1, k - 1), k], lexicographic
+    from (0, .., 0, n) to (n, 0, .., 0) (stars and bars: the cells are the gaps between k - 1 bars among n + k - 1 places)."""
+    from itertools import combinations
+    bars = np.array(list(combinations(range(n + k - 1), k - 1)), dtype=np.int64).reshape(-1, k - 1)
+    edge = np.concatenate([np.full((len(bars), 1), -1), bars, np.full((len(bars), 1), n + k - 1)], axis=1)
+    return np.diff(edge, axis=1) - 1
+
+
+def small_table_alleles(kind, n, seed=None, missing=False):
+    """Every genotype table of a small sample count, one variant pair per table -> (alleles int8 [2T, N, 2], variants, tables).
+
+    kind = "unphased": every composition of n samples into the 9 genotype cells in the oracle's order (O.count_unphased: A's
+    genotype major - (0/0,0/0), (0/0,het), (0/0,hom), (het,0/0), ..); N = n.  kind = "phased": every composition of n = 2N
+    haplotypes into (n00, n01, n10, n11), first digit A's allele (O.count_phased returns [n00, n10, n01, n11]).
+    Table k (row k of `tables`) is variants 2k (A) and 2k + 1 (B), all on one contig, pos[2k] = 1000 + 10k, pos[2k + 1] =
+    pos[2k] + 1: a window of 1 bp holds exactly the T partner pairs.
+    seed: permutes the tables and, per table, its samples (both variants alike: the table stays, its bits move).
+    missing: two more samples per table, one missing in A only and one in B only, the other variant's genotype there cycling
+    0/0, 0/1, 1/1 with the table's number in the unpermuted order; neither sample is counted in the pair's table (N = n + 2)."""
+    if kind == "unphased":
+        tables = compositions(n, 9)
+        T = len(tables)
+        cell = np.repeat(np.tile(np.arange(9), T), tables.ravel()).reshape(T, n)
+        g = np.stack([cell // 3, cell % 3], axis=1)                       # [T, 2 (A, B), n] genotypes 0, 1, 2
+        al = np.stack([g == 2, g >= 1], axis=-1).astype(np.int8)          # 0/0, 0/1, 1/1
+    elif kind == "phased":
+        assert n % 2 == 0
+        tables = compositions(n, 4)
+        T = len(tables)
+        cell = np.repeat(np.tile(np.arange(4), T), tables.ravel()).reshape(T, n)
+        al = np.stack([cell >> 1, cell & 1], axis=1).astype(np.int8).reshape(T, 2, n // 2, 2)
+    else:
+        raise ValueError(kind)
+    if missing:
+        k = np.arange(T) % 3
+        other = np.stack([k == 2, k >= 1], axis=-1).astype(np.int8)      # [T, 2]: the called variant's genotype
+        extra = np.empty((T, 2, 2, 2), dtype=np.int8)                     # [T, variant, the two samples, allele]
+        extra[:, 0, 0] = 2; extra[:, 1, 0] = other                        # missing in A only
+        extra[:, 0, 1] = other; extra[:, 1, 1] = 2                        # missing in B only
+        al = np.concatenate([al, extra], axis=2)
+    if seed is not None:
+        rng = np.random.default_rng(seed)
+        order = rng.permutation(T)
+        al, tables = al[order], tables[order]
+        by = np.argsort(rng.random((T, al.shape[2])), axis=1)
+        al = np.take_along_axis(al, by[:, None, :, None], axis=2)
+    alleles = np.ascontiguousarray(al.reshape(2 * T, al.shape[2], 2))
+    pos = 1000 + 10 * np.repeat(np.arange(T), 2) + np.tile([0, 1], T)
+    return alleles, O.variants_from_alleles(alleles, pos=pos), tables
+
+
+def small_table_ill_conditioned(tables, variants, vet):
+    """Which unphased tables of small_table_alleles sit where the cubic's root is not determined to parity's bar, from the tables
+    alone (the oracle's own record supplies the root): a double root (`vet`, a double_root_vetter of the set), a root whose
+    uncertainty root_error() cannot bound (dx infinite), or one whose floor 4 dx would pass DX_CEILING -> bool [T]."""
+    st = O.settings(minR2=0.0, unphased=True, keep_low_ac=True)
+    ill = np.zeros(len(tables), dtype=bool)
+    for k in np.nonzero(tables[:, 4] > 0)[0]:                     # (no double hets: PhasedMath, no cubic)
+        ill[k] = vet(2 * k, 2 * k + 1)
+        r = O.unphased_math(tables[k], variants[2 * k], variants[2 * k + 1], st)
+        if r is not None and not ill[k]:
+            dx = vet.root_error(2 * k, 2 * k + 1, float(r["cnt"][0]) / float(np.sum(r["cnt"])))[0]
+            ill[k] = not np.isfinite(dx) or ROOT_ERROR_FACTOR * dx > DX_CEILING
+    return ill
+
+
+def small_table_exact_root(table, f11):
+    """Is the root `f11` (the oracle's, as a frequency) of an unphased table's cubic one that rational arithmetic knows exactly,
+    at a place where parity's relative bar has nothing to hold on to?  Decided in fractions from the table alone:
+      "zero-D": pA pB is a root of the cubic and f11 is that root - D is 0 exactly, what a record carries as D, D', r, r2 and
+                chi2 is the rounding noise of f11 - pA pB, different noise on every libm;
+      "half":   an odd multiple of 1 / (4 total) is a root and f11 is that root - every expected count f * 2 total ends in .5
+                exactly (the margins are integers), and the last bit of the root decides which way round() sends it in front
+                of Fisher's test.
+    -> "zero-D", "half", "zero-D+half" or None.  (The cubic is ld_engine.cpp:1363-1428's, as in double_root_vetter.)"""
+    from fractions import Fraction as F
+    a0, a14, a5, a1664, hets, a2169, a80, a8184, a85 = (int(x) for x in table)
+    total = a0 + a14 + a5 + a1664 + hets + a2169 + a80 + a8184 + a85
+    if total == 0 or hets == 0:
+        return None
+    P = F(2 * (a0 + a14 + a5) + a1664 + hets + a2169, 2 * total)
+    Q = F(2 * (a0 + a1664 + a80) + a14 + hets + a8184, 2 * total)
+    n11 = 2 * a0 + a14 + a1664
+    dee = -n11 * P * Q
+    cc = -n11 * (1 - 2 * P - 2 * Q) - hets * (1 - P - Q) + 2 * total * P * Q
+    b = 2 * total * (1 - 2 * P - 2 * Q) - 2 * n11 - hets
+    a = 4 * total
+    g = lambda x: a * x ** 3 + b * x * x + cc * x + dee
+    kinds = []
+    if g(P * Q) == 0 and abs(float(f11) - float(P * Q)) <= D_FLOOR:
+        kinds.append("zero-D")
+    m = int(round(float(f11) * 4 * total))
+    if m % 2 == 1 and g(F(m, 4 * total)) == 0 and abs(float(f11) - m / (4.0 * total)) <= DX_CEILING:
+        kinds.append("half")
+    return "+".join(kinds) or None
+
+
+def small_table_exact_class(tables, variants):
+    """small_table_exact_root of every unphased table of small_table_alleles whose pair gets a record out of the cubic
+    -> {k: kind}."""
+    st = O.settings(minR2=0.0, unphased=True, keep_low_ac=True)
+    out = {}
+    for k in np.nonzero(tables[:, 4] > 0)[0]:
+        r = O.unphased_math(tables[k], variants[2 * k], variants[2 * k + 1], st)
+        if r is not None:
+            kind = small_table_exact_root(tables[k], float(r["cnt"][0]) / float(np.sum(r["cnt"])))
+            if kind:
+                out[int(k)] = kind
+    return out
+
+
+def assert_exact_root_record(g, w, kind, dx, rtol=1e-6):
+    """The bar for the record `g` of a table of small_table_exact_class against the oracle's `w`: flags but bit 5 equal; every
+    statistic within `rtol` or within what an error `dx` of the root leaves of it (cubic_floors: for a zero-D table that is
+    |D| <= dx on both sides, asserted as such); Fisher's P is the oracle's if both round the expected counts to the same table -
+    they must, unless the counts end in .5 exactly ("half"), where either neighbour is a correct rounding of a root that is
+    right to dx and P must be Fisher's P of the record's own rounded table."""
+    assert not ((int(g["flags"]) ^ int(w["controller"])) & ~(1 << 5)), (hex(int(g["flags"])), hex(int(w["controller"])))
+    cf = cubic_floors([float(x) for x in w["cnt"]], w["R"], dx)
+    assert np.allclose(g["cnt"], w["cnt"], rtol=rtol, atol=cf["cnt"]), (g["cnt"], w["cnt"])
+    for f in ("D", "Dprime", "R", "R2", "ChiSqFisher"):
+        assert np.isclose(g[f], w[f], rtol=rtol, atol=cf[f]), (f, float(g[f]), float(w[f]), cf[f])
+    assert np.isclose(g["ChiSqModel"], w["ChiSqModel"], rtol=rtol, atol=0.0)
+    if "zero-D" in kind:
+        assert abs(float(g["D"])) <= dx and abs(float(w["D"])) <= dx and g["R2"] <= cf["R2"], (float(g["D"]), float(w["D"]))
+    gt = [int(np.floor(float(x) + 0.5)) for x in g["cnt"]]
+    wt = [int(np.floor(float(x) + 0.5)) for x in w["cnt"]]
+    if gt != wt:
+        assert "half" in kind and max(abs(x - y) for x, y in zip(gt, wt)) <= 1, (kind, gt, wt)
+        assert np.isclose(g["P"], O.fisher(gt[0], gt[2], gt[1], gt[3])[2], rtol=rtol, atol=0.0), (gt, float(g["P"]))
+    else:
+        assert np.isclose(g["P"], w["P"], rtol=rtol, atol=0.0), (float(g["P"]), float(w["P"]))
+    return gt != wt
+
+
+def exact_fisher_p(n11, n12, n21, n22):
+    """Two-sided Fisher P in rational arithmetic: given the margins, the probabilities of every table that is at most as
+    likely as the observed one, added up -> Fraction."""
+    from fractions import Fraction
+    from math import comb
+    r1, c1, n = n11 + n12, n11 + n21, n11 + n12 + n21 + n22
+    w = {x: comb(r1, x) * comb(n - r1, c1 - x) for x in range(max(0, r1 + c1 - n), min(r1, c1) + 1)}
+    return Fraction(sum(v for v in w.values() if v <= w[n11]), comb(n, c1))
+
+
 def to_hip_meta(variants):
     m = np.zeros(len(variants), dtype=META_DTYPE)
     for k in ("ac", "an", "pos", "rid", "hwe"):

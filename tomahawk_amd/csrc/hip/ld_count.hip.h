@@ -1272,6 +1272,13 @@ struct ScreenCountsUnphased {
 					const uint32_t hh = acc[2 * sI][2 * v];
 					const uint32_t s_sum = THREE ? acc[2 * sI + 1][2 * v + 1] : acc[2 * sI + 1][2 * v] + acc[2 * sI][2 * v + 1] + 2u * acc[2 * sI + 1][2 * v + 1];
 					// n11 = ra - b + (QH + HQ + 2 QQ): the (REF, REF) haplotypes that are certain
+					// (b comes from the prefilter's float term, not from the integers staged at U_COLS as k_screen3_pairs reads them: the
+					// integer itself below 2^24 alleles; above that the float is the nearest multiple of 2 (of 4 from 2^25 on), and this is
+					// no longer the exact test k_screen3_pairs makes.  The default policy never fuses rows that long, only the test hook
+					// fused = 2 does.  A candidate is decided again from exact counts by the list math, so a rounded b can only lose a pair at
+					// the cut-off, not admit a wrong record.  No bound on that loss is claimed here; what is shown is one column with an odd
+					// dosage above 2^24 (N = 10,000,000, r2 near 0.5, cut-offs on and one ulp beside it) on which the forced form gives the plain
+					// path's records: tests/test_gpu_three.py, test_forced_fused_screen_with_a_column_dosage_beyond_float.)
 					const double dbv = (double)fb[v].x, rbv = T2n - dbv;
 					const double n11 = (ra - dbv) + (double)s_sum;
 					const double e_lo = (n11 * T2n - ra * rbv) - eps;

@@ -13,7 +13,8 @@ namespace twk {
 
 // ---- the three-product form's screen over a count matrix (long rows: tiles split along K, counts added into C) ----
 // One thread per variant pair of the super-tile: (HH, S) from the matrix StoreCounts3 wrote, the row margins, and the test of
-// ScreenCountsUnphased word for word (same doubles, same order); a pair that passes becomes a candidate (A, B, HH, S, -, -) in the
+// ScreenCountsUnphased (same doubles, same order - but for the column variant's dosage, which is read here as the integer it is and
+// there from the prefilter's float term: the same number below 2^24 alleles); a pair that passes becomes a candidate (A, B, HH, S, -, -) in the
 // launch's list, appended with one atomic per block.  Structural tests as in the fused epilogue (the list math checks them again).
 constexpr int SCREEN3_THREADS = 256;
 __global__ __launch_bounds__(SCREEN3_THREADS)
