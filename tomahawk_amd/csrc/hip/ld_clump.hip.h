@@ -49,23 +49,8 @@ constexpr int CLUMP_WALK_THREADS = 1024;
 constexpr uint32_t CLUMP_LDS_WORDS = WALK_LDS_WORDS;      // `taken` in LDS: up to 520,192 variants, as prune's `removed`
 constexpr uint32_t CLUMP_NONE = 0xFFFFFFFFu;              // TWK_HIP_NO_CLUMP
 
-// The parameter block of a mask launch, in device memory (read inside the row loop: ld_score.hip.h on why).  The map is prune's.
+// The parameter block of a mask launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).  The map is prune's.
 struct ClumpArgs { StatsParams p; PruneMap pm; };
-
-// One pair of the launch's matrix: would `calc` report it?  Out of line, as d_prune_pair and for its reason.
-__device__ __noinline__ bool d_clump_pair(const StatsParams* pp, uint32_t i, uint32_t j) {
-	const StatsParams& p = *pp;
-	twk_hip_record rec;
-	return d_pair<SRC_MATRIX>(p, p.tv.a0 + i, p.tv.b0 + j, i, j, 0, &rec);
-}
-
-// ORs the 64 bits `bits`, the first of them bit `bit0` of the row, into the one or two words of the row they straddle.
-__device__ __forceinline__ void d_clump_or(unsigned long long* row, uint32_t stride, uint32_t bit0, unsigned long long bits) {
-	const uint32_t at = bit0 >> 6, sh = bit0 & 63;
-	const unsigned long long lo = bits << sh, hi = sh ? bits >> (64 - sh) : 0ull;
-	if (lo && at < stride) atomicOr(row + at, lo);
-	if (hi && at + 1 < stride) atomicOr(row + at + 1, hi);
-}
 
 __global__ __launch_bounds__(CLUMP_THREADS)
 void k_ld_clump_mask(const ClumpArgs* __restrict__ args) {
@@ -76,8 +61,7 @@ void k_ld_clump_mask(const ClumpArgs* __restrict__ args) {
 	const uint32_t j = blockIdx.x * CLUMP_THREADS + threadIdx.x;
 	const uint32_t i0 = blockIdx.y * CLUMP_ROWS;
 	const int lane = threadIdx.x & 63;
-	// a block that lies wholly on or below the diagonal of a diagonal launch has no pair
-	if (args->p.diag && a0 == b0 && blockIdx.x * CLUMP_THREADS + (CLUMP_THREADS - 1) <= i0) return;
+	if (d_block_dead(args->p, blockIdx.x, CLUMP_THREADS, i0)) return;
 	// the wave's first column as a bit of the bitmap (plain sets: its 64 columns are the bits from there on)
 	const uint32_t bit0 = b0 + (j - lane) - pm.a0;
 	uint32_t edges = 0;
@@ -86,7 +70,7 @@ void k_ld_clump_mask(const ClumpArgs* __restrict__ args) {
 	for (uint32_t r = 0; r < CLUMP_ROWS; ++r) {
 		const uint32_t i = i0 + r;
 		bool keep = false;
-		if (i < nA && j < nB) keep = d_clump_pair(&args->p, i, j);
+		if (i < nA && j < nB) keep = d_reduce_keeps(&args->p, i, j);
 		const unsigned long long ballot = __ballot(keep);
 		if (!ballot) continue;                               // (uniform over the wave)
 		edges += (uint32_t)__popcll(ballot);
@@ -94,7 +78,7 @@ void k_ld_clump_mask(const ClumpArgs* __restrict__ args) {
 			// keep implies both variants inside the triangle (its launches lie on or above its diagonal)
 			col |= (unsigned long long)keep << r;
 			const uint32_t row = a0 + i - pm.a0;
-			if (lane == 0 && row < pm.n) d_clump_or(pm.adj + (size_t)row * pm.stride, pm.stride, bit0, ballot);
+			if (lane == 0 && row < pm.n) d_or_bits(pm.adj + (size_t)row * pm.stride, pm.stride, bit0, ballot);
 		} else if (keep) {
 			const uint32_t u = ids[a0 + i] - pm.a0, v = ids[b0 + j] - pm.a0;
 			if (u < pm.n && v < pm.n) {
@@ -106,7 +90,7 @@ void k_ld_clump_mask(const ClumpArgs* __restrict__ args) {
 	// the mirrored bits: the column's variant is the bitmap row, the block's rows are its bits from a0 + i0 on
 	if (col) {
 		const uint32_t row = b0 + j - pm.a0;
-		if (row < pm.n) d_clump_or(pm.adj + (size_t)row * pm.stride, pm.stride, a0 + i0 - pm.a0, col);
+		if (row < pm.n) d_or_bits(pm.adj + (size_t)row * pm.stride, pm.stride, a0 + i0 - pm.a0, col);
 	}
 	if (lane == 0 && edges) atomicAdd(pm.n_edges, (unsigned long long)edges);
 }

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ld_math.hip.h"
+#include "ld_reduce.hip.h"
 #include "ld_matrix_index.h"
 
 namespace twk {
@@ -40,7 +41,7 @@ struct MatrixMap {
 	uint32_t a0, n;                     // the triangle's first variant, its size
 	int32_t stat;                       // TWK_HIP_STAT_*
 };
-// The parameter block of a fill launch, in device memory (read inside the row loop: ld_score.hip.h on why).
+// The parameter block of a fill launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
 struct MatrixArgs { StatsParams p; MatrixMap mm; };
 
 // One pair of the launch's matrix: bit 32 set if `calc` would report it, and then its statistic as a float32 in the low word (the

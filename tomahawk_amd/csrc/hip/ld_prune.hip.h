@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ld_math.hip.h"
+#include "ld_reduce.hip.h"
 
 namespace twk {
 
@@ -40,16 +41,8 @@ struct PruneMap {
 	unsigned long long* n_edges;
 	uint32_t a0, n, stride;             // the triangle's first variant, its size, words per row
 };
-// The parameter block of a mask launch, in device memory (read inside the row loop: ld_score.hip.h on why).
+// The parameter block of a mask launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
 struct PruneArgs { StatsParams p; PruneMap pm; };
-
-// One pair of the launch's matrix: would `calc` report it?  Out of line, so that the registers of the two maths are the callee's and
-// not held across the row loop (the finding noted at d_score_pair).
-__device__ __noinline__ bool d_prune_pair(const StatsParams* pp, uint32_t i, uint32_t j) {
-	const StatsParams& p = *pp;
-	twk_hip_record rec;
-	return d_pair<SRC_MATRIX>(p, p.tv.a0 + i, p.tv.b0 + j, i, j, 0, &rec);
-}
 
 __global__ __launch_bounds__(PRUNE_THREADS)
 void k_ld_prune_mask(const PruneArgs* __restrict__ args) {
@@ -60,8 +53,7 @@ void k_ld_prune_mask(const PruneArgs* __restrict__ args) {
 	const uint32_t j = blockIdx.x * PRUNE_THREADS + threadIdx.x;
 	const uint32_t i0 = blockIdx.y * PRUNE_ROWS;
 	const int lane = threadIdx.x & 63;
-	// a block that lies wholly on or below the diagonal of a diagonal launch has no pair
-	if (args->p.diag && a0 == b0 && blockIdx.x * PRUNE_THREADS + (PRUNE_THREADS - 1) <= i0) return;
+	if (d_block_dead(args->p, blockIdx.x, PRUNE_THREADS, i0)) return;
 	// the wave's first column as a bit of the bitmap (plain sets: its 64 columns are the bits from there on)
 	const uint32_t bit0 = b0 + (j - lane) - pm.a0;
 	uint32_t edges = 0;
@@ -69,20 +61,14 @@ void k_ld_prune_mask(const PruneArgs* __restrict__ args) {
 	for (uint32_t r = 0; r < PRUNE_ROWS; ++r) {
 		const uint32_t i = i0 + r;
 		bool keep = false;
-		if (i < nA && j < nB) keep = d_prune_pair(&args->p, i, j);
+		if (i < nA && j < nB) keep = d_reduce_keeps(&args->p, i, j);
 		const unsigned long long ballot = __ballot(keep);
 		if (!ballot) continue;                               // (uniform over the wave)
 		edges += (uint32_t)__popcll(ballot);
 		if (!ids) {
 			// keep implies column variant > row variant (a triangle's launches lie on or above its diagonal) and both inside it
 			const uint32_t row = a0 + i - pm.a0;
-			if (lane == 0 && row < pm.n) {
-				unsigned long long* w = pm.adj + (size_t)row * pm.stride;
-				const uint32_t at = bit0 >> 6, sh = bit0 & 63;
-				const unsigned long long lo = ballot << sh, hi = sh ? ballot >> (64 - sh) : 0ull;
-				if (lo && at < pm.stride) atomicOr(w + at, lo);
-				if (hi && at + 1 < pm.stride) atomicOr(w + at + 1, hi);
-			}
+			if (lane == 0 && row < pm.n) d_or_bits(pm.adj + (size_t)row * pm.stride, pm.stride, bit0, ballot);
 		} else if (keep) {
 			uint32_t u = ids[a0 + i] - pm.a0, v = ids[b0 + j] - pm.a0;
 			if (u > v) { const uint32_t x = u; u = v; v = x; }

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ld_math.hip.h"
+#include "ld_reduce.hip.h"
 
 namespace twk {
 
@@ -30,9 +31,7 @@ struct ScoreParts {
 	double* col_sum; uint32_t* col_n;   // [gy][nB]: column j's partial from row block by at by * nB + j
 	uint32_t gx, gy;
 };
-// The parameter block of a score launch, in device memory: the kernel reads the pair's parameters from it inside its row loop (held in
-// scalar registers across the loop they are ~170 registers, spilled into vector registers: 206 VGPRs, two waves a SIMD - the same
-// finding as k_ld_stats_list's, ld_math.hip.h).
+// The parameter block of a score launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
 struct ScoreArgs { StatsParams p; ScoreParts sp; };
 
 // Sum over the wave's 64 lanes, the same value in every lane: a butterfly whose pairing does not depend on the data.
@@ -59,8 +58,7 @@ void k_ld_score(const ScoreArgs* __restrict__ args) {
 	const uint32_t j = blockIdx.x * SCORE_THREADS + threadIdx.x;
 	const uint32_t i0 = blockIdx.y * SCORE_ROWS;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	// a block that lies wholly on or below the diagonal of a diagonal launch has no pair: zero partials
-	const bool dead = args->p.diag && args->p.tv.a0 == args->p.tv.b0 && blockIdx.x * SCORE_THREADS + (SCORE_THREADS - 1) <= i0;
+	const bool dead = d_block_dead(args->p, blockIdx.x, SCORE_THREADS, i0);      // (such a block still writes its partials: zeros)
 	double csum = 0.0; uint32_t cn = 0;
 #pragma unroll 1
 	for (uint32_t r = 0; r < SCORE_ROWS; ++r) {

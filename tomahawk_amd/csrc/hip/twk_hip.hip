@@ -9,6 +9,7 @@
 //   prune (ld_prune.hip.h) cells -> keep -> adjacency bitmap, in place of the math stage, and the greedy walk over it (twk_hip_ld_prune)
 //   clump (ld_clump.hip.h) cells -> keep -> the bitmap's bits (u, v) and (v, u), likewise, and the walk over it in P order (twk_hip_ld_clump)
 //   matrix (ld_matrix.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a dense float32 matrix (twk_hip_ld_matrix)
+//   (score, prune, clump and matrix are the four kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include <rccl/rccl.h>          // types only: the library is opened on first use (twk_hip_gather_records), never linked
 #include <dlfcn.h>
 #include <map>
+#include <type_traits>
 
 #include "../../../include/twk_hip.h"
 #include "ld_count.hip.h"
@@ -37,6 +39,7 @@
 #include "ld_math.hip.h"
 #include "ld_list.hip.h"
 #include "ld_three.hip.h"
+#include "ld_reduce.hip.h"
 #include "ld_score.hip.h"
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
@@ -109,6 +112,10 @@ constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // until the host had sorted, copied and handed over launch t and come back with launch t + 2 (2,504 x 531,500, all pairs:
 // 39 launches of 13 ms took 1.25 s).  With t + 2 already queued the count kernels run back to back.
 constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
+// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump or _matrix runs: it looks at
+// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the four kernels share).
+enum class Reduce { none, score, prune, clump, matrix };
+constexpr int N_REDUCE = (int)Reduce::matrix + 1;
 // The form of a launch, decided once (launch_form) and passed down: which count kernel, which math behind it.
 struct LaunchForm {
 	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
@@ -117,11 +124,8 @@ struct LaunchForm {
 	bool three = false;            // the three-product form (HH + S; the candidates' four products are recounted): fused, or ...
 	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
-	bool score = false;            // the score epilogue in place of math, Fisher and records (ld_score.hip.h): always through a matrix
-	bool prune = false;            // the prune epilogue in their place (ld_prune.hip.h): likewise
-	bool clump = false;            // the clump epilogue (ld_clump.hip.h): the prune epilogue with both bits of an edge
-	bool matrix = false;           // the matrix epilogue (ld_matrix.hip.h): one statistic of every record stored into the call's dense matrix
-	bool reduces() const { return score || prune || clump || matrix; }      // ... either way the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
+	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
+	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
@@ -145,6 +149,8 @@ struct Launch {
 	double minP = 1.0;
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
 };
+// Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -163,10 +169,8 @@ struct Slot {                      // one in-flight tile (double buffered)
 	PinnedBuf<uint32_t> h_tiles[2]; DevBuf<uint32_t> d_tiles[2];
 	// score launches (ld_score.hip.h): the blocks' row and column partials of the launch (grow-only)
 	DevBuf<double> sc_sum; DevBuf<uint32_t> sc_n;
-	PinnedBuf<ScoreArgs> h_sc_args; DevBuf<ScoreArgs> d_sc_args;         // ... and the parameter blocks of its (up to two) passes: pinned host copy + device copy
-	PinnedBuf<PruneArgs> h_pr_args; DevBuf<PruneArgs> d_pr_args;         // prune launches (ld_prune.hip.h): the same two blocks
-	PinnedBuf<ClumpArgs> h_cl_args; DevBuf<ClumpArgs> d_cl_args;         // clump launches (ld_clump.hip.h): likewise
-	PinnedBuf<MatrixArgs> h_mx_args; DevBuf<MatrixArgs> d_mx_args;       // matrix launches (ld_matrix.hip.h): likewise
+	// reduce launches (launch_reduce): the parameter blocks of the (up to two) passes, whatever the kind: pinned host copy + device copy
+	PinnedBuf<ReduceArgs> h_args; DevBuf<ReduceArgs> d_args;
 };
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
@@ -292,27 +296,21 @@ struct twk_hip_ctx {
 	DevBuf<uint8_t> d_rle, d_rle_desc;
 	DevBuf<int> d_status;
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
-	// twk_hip_ld_score: the launches of the running call sum r2 per variant (ld_score.hip.h) instead of keeping records
-	bool score_on = false;
+	// twk_hip_ld_score, _prune, _clump, _matrix: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
+	Reduce reduce = Reduce::none;                                                // which way, for the length of the call (ReduceCall)
+	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
+	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last)
+	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
+	// score: sums of r2 per variant (ld_score.hip.h)
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
-	// twk_hip_ld_prune: the launches of the running call ballot `keep` into the adjacency bitmap of the call's triangle (ld_prune.hip.h)
-	bool prune_on = false;
-	bool reduce_on() const { return score_on || prune_on || clump_on || matrix_on; }
-	PruneMap prune_map{};
-	DevBuf<unsigned long long> d_prune_adj, d_prune_removed, d_prune_counts;     // the bitmap (lives for the call), `removed` beyond LDS, [0] edges [1] kept
+	// prune and clump: `keep` balloted into the adjacency bitmap of the call's triangle (ld_prune.hip.h; clump from both ends of a pair, ld_clump.hip.h)
+	PruneMap map{};
+	DevBuf<unsigned long long> d_adj, d_walk;                                    // the bitmap (lives for the call); prune's `removed` beyond LDS, clump's taken0 / `taken`
 	DevBuf<uint8_t> d_prune_keep;                                                // [M]
-	double prune_walk_ms = 0; uint64_t prune_bitmap_bytes = 0;                   // of the last call (twk_hip_prune_last)
-	// twk_hip_ld_clump: the launches of the running call ballot `keep` into the call's bitmap from both ends of a pair (ld_clump.hip.h)
-	bool clump_on = false;
-	PruneMap clump_map{};
-	DevBuf<unsigned long long> d_clump_adj, d_clump_taken, d_clump_counts;       // the bitmap (lives for the call), taken0 / `taken` beyond LDS, [0] edges [1] clumps [2] members
 	DevBuf<uint32_t> d_clump_order, d_clump_index;                               // the candidates in visiting order; index_of [M]
-	double clump_walk_ms = 0; uint64_t clump_bitmap_bytes = 0;                   // of the last call (twk_hip_clump_last)
-	// twk_hip_ld_matrix: the launches of the running call store one statistic per record into the call's dense matrix (ld_matrix.hip.h)
-	bool matrix_on = false;
+	// matrix: one statistic per record stored into the call's dense matrix (ld_matrix.hip.h)
 	MatrixMap matrix_map{};
-	DevBuf<float> d_matrix; DevBuf<unsigned long long> d_matrix_count;           // the n x n matrix (lives for the call); [0] records
-	double matrix_copy_ms = 0; uint64_t matrix_bytes = 0;                        // of the last call (twk_hip_matrix_last)
+	DevBuf<float> d_matrix;                                                      // the n x n matrix (lives for the call)
 	char err[512] = {0};
 };
 
@@ -342,8 +340,7 @@ void free_planes(twk_hip_ctx* c) {
 void free_slots(twk_hip_ctx* c) {
 	for (auto& s : c->slot) {
 		s.C.reset(); s.out.reset(); s.keys.reset(); s.vals.reset(); s.sorted.reset();
-		s.sc_sum.reset(); s.sc_n.reset(); s.h_sc_args.reset(); s.d_sc_args.reset(); s.h_pr_args.reset(); s.d_pr_args.reset();
-		s.h_cl_args.reset(); s.d_cl_args.reset(); s.h_mx_args.reset(); s.d_mx_args.reset();
+		s.sc_sum.reset(); s.sc_n.reset(); s.h_args.reset(); s.d_args.reset();
 		for (int k = 0; k < 2; ++k) { s.h_tiles[k].reset(); s.d_tiles[k].reset(); }
 	}
 }
@@ -353,9 +350,8 @@ void free_problem(twk_hip_ctx* c) {
 	c->raw.reset(); c->rawmask.reset(); c->d_lfact.reset(); c->lfact_n = 0;
 	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
 	c->d_score_sum.reset(); c->d_score_n.reset();
-	c->d_prune_adj.reset(); c->d_prune_removed.reset(); c->d_prune_counts.reset(); c->d_prune_keep.reset();
-	c->d_clump_adj.reset(); c->d_clump_taken.reset(); c->d_clump_counts.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
-	c->d_matrix.reset(); c->d_matrix_count.reset();
+	c->d_counts.reset(); c->d_adj.reset(); c->d_walk.reset(); c->d_prune_keep.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
+	c->d_matrix.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -779,7 +775,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 }
 
 // The form of the (first) launch of a tile of this plan, as the context stands: the one place that reads the options "fused" and "three",
-// FUSED_MAX_CHUNKS, fused_ok, three_ok, score_on, prune_on, clump_on and matrix_on for it.
+// FUSED_MAX_CHUNKS, fused_ok, three_ok and reduce for it.
 // A screen in front of the math needs plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
 // pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short
 // enough that no tile's K range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h)
@@ -787,7 +783,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 // reports why).
 LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
 	LaunchForm lf;
-	lf.two_pass = pl.set2 >= 0; lf.score = c->score_on; lf.prune = c->prune_on; lf.clump = c->clump_on; lf.matrix = c->matrix_on; lf.keep_three = c->opt.three == 2;
+	lf.two_pass = pl.set2 >= 0; lf.reduce = c->reduce; lf.keep_three = c->opt.three == 2;
 	const int k = set_kind(pl.set1);
 	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
 	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
@@ -818,15 +814,37 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	return TWK_HIP_OK;
 }
 
-// The score epilogue of a launch whose count matrix is in the slot's C (ld_score.hip.h): the pairs' r2 summed per row and per column
-// inside the blocks, the blocks' partials folded into the context's per-variant accumulators - rows, then columns, each in a launch of
-// its own, so that a variant that is both a row and a column of a diagonal launch is added to by one lane at a time.
-int launch_score(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
+// The end of every reduce launch: the parameter block `a` of pass `which` into the slot's pinned block and from there to the device, on the stream of
+// `kernel`, which then reads it there while it walks the tile in blocks of cols x rows.
+template <class A>
+int run_reduce_kernel(twk_hip_ctx* c, const twk_hip_tile_desc& t, Slot& s, int which, void (*kernel)(const A*), uint32_t cols, uint32_t rows, const A& a) {
+	static_assert(sizeof(A) <= sizeof(ReduceArgs) && alignof(A) <= alignof(ReduceArgs) && std::is_trivially_copyable<A>::value, "a parameter block the slot has room for");
+	const dim3 grid((t.nB + cols - 1) / cols, (t.nA + rows - 1) / rows);
+	if (grid.y > 0xFFFFu) return TWK_HIP_E_INVALID;
+	memcpy(s.h_args + which, &a, sizeof(A));      // (the slot's previous launch has been waited for: its copy is done)
+	HIPCHK(c, hipMemcpyAsync(s.d_args + which, s.h_args + which, sizeof(A), hipMemcpyHostToDevice, c->s_compute));
+	hipLaunchKernelGGL(kernel, grid, dim3(cols), 0, c->s_compute, reinterpret_cast<const A*>(s.d_args + which));
+	HIPCHK(c, hipGetLastError());
+	return TWK_HIP_OK;
+}
+
+// The epilogue of a reduce launch whose count matrix is in the slot's C, by the launch's kind: what follows the call's last launch - prune's and clump's
+// walks, the matrix's diagonal and copy - is the entry point's (twk_hip_ld_prune, _clump, _matrix).
+int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
 	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
 	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
 	if (!t.nA || !t.nB) return TWK_HIP_OK;
-	HIPCHK(c, s.h_sc_args.reserve(2, 2, nullptr));
-	HIPCHK(c, s.d_sc_args.reserve(2, 2, nullptr));
+	HIPCHK(c, s.h_args.reserve(2, 2, nullptr));
+	HIPCHK(c, s.d_args.reserve(2, 2, nullptr));
+	switch (s.l.form.reduce) {
+	case Reduce::prune:  return run_reduce_kernel(c, t, s, which, k_ld_prune_mask, PRUNE_THREADS, PRUNE_ROWS, PruneArgs{p, c->map});
+	case Reduce::clump:  return run_reduce_kernel(c, t, s, which, k_ld_clump_mask, CLUMP_THREADS, CLUMP_ROWS, ClumpArgs{p, c->map});
+	case Reduce::matrix: return run_reduce_kernel(c, t, s, which, k_ld_matrix_fill, MATRIX_THREADS, MATRIX_ROWS, MatrixArgs{p, c->matrix_map});
+	case Reduce::score: break;
+	case Reduce::none: return TWK_HIP_E_STATE;
+	}
+	// score: the pairs' r2 summed per row and per column inside the blocks, the blocks' partials folded into the context's per-variant accumulators - rows,
+	// then columns, each in a launch of its own, so that a variant that is both a row and a column of a diagonal launch is added to by one lane at a time
 	ScoreParts sp{};
 	sp.gx = (t.nB + SCORE_THREADS - 1) / SCORE_THREADS; sp.gy = (t.nA + SCORE_ROWS - 1) / SCORE_ROWS;
 	if (sp.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
@@ -834,65 +852,11 @@ int launch_score(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	HIPCHK(c, reserve_together(need, need, &c->graveyard, s.sc_sum, s.sc_n));
 	sp.row_sum = s.sc_sum; sp.row_n = s.sc_n; sp.col_sum = s.sc_sum + n_row; sp.col_n = s.sc_n + n_row;
 	const uint32_t* ids = c->planes[set].ids;
-	s.h_sc_args[which].p = p; s.h_sc_args[which].sp = sp;      // (the slot's previous launch has been waited for: its copy is done)
-	HIPCHK(c, hipMemcpyAsync(s.d_sc_args + which, s.h_sc_args + which, sizeof(ScoreArgs), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(k_ld_score, dim3(sp.gx, sp.gy), dim3(SCORE_THREADS), 0, c->s_compute, (const ScoreArgs*)(s.d_sc_args + which));
+	const int rc = run_reduce_kernel(c, t, s, which, k_ld_score, SCORE_THREADS, SCORE_ROWS, ScoreArgs{p, sp}); if (rc) return rc;
 	hipLaunchKernelGGL(k_ld_score_fold, dim3((t.nA + 255) / 256), dim3(256), 0, c->s_compute, (const double*)sp.row_sum, (const uint32_t*)sp.row_n, t.nA, sp.gx,
 	                   (size_t)sp.gx, (size_t)1, t.rowA0, ids, c->M, c->d_score_sum, c->d_score_n);
 	hipLaunchKernelGGL(k_ld_score_fold, dim3((t.nB + 255) / 256), dim3(256), 0, c->s_compute, (const double*)sp.col_sum, (const uint32_t*)sp.col_n, t.nB, sp.gy,
 	                   (size_t)1, (size_t)t.nB, t.rowB0, ids, c->M, c->d_score_sum, c->d_score_n);
-	HIPCHK(c, hipGetLastError());
-	return TWK_HIP_OK;
-}
-
-// The prune epilogue of a launch whose count matrix is in the slot's C (ld_prune.hip.h): `keep` of every pair balloted into the call's
-// adjacency bitmap.  The walk over the bitmap follows the call's last launch (twk_hip_ld_prune).
-int launch_prune(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
-	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
-	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
-	if (!t.nA || !t.nB) return TWK_HIP_OK;
-	HIPCHK(c, s.h_pr_args.reserve(2, 2, nullptr));
-	HIPCHK(c, s.d_pr_args.reserve(2, 2, nullptr));
-	const uint32_t gx = (t.nB + PRUNE_THREADS - 1) / PRUNE_THREADS, gy = (t.nA + PRUNE_ROWS - 1) / PRUNE_ROWS;
-	if (gy > 0xFFFFu) return TWK_HIP_E_INVALID;
-	s.h_pr_args[which].p = p; s.h_pr_args[which].pm = c->prune_map;      // (the slot's previous launch has been waited for: its copy is done)
-	HIPCHK(c, hipMemcpyAsync(s.d_pr_args + which, s.h_pr_args + which, sizeof(PruneArgs), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(k_ld_prune_mask, dim3(gx, gy), dim3(PRUNE_THREADS), 0, c->s_compute, (const PruneArgs*)(s.d_pr_args + which));
-	HIPCHK(c, hipGetLastError());
-	return TWK_HIP_OK;
-}
-
-// The clump epilogue of a launch whose count matrix is in the slot's C (ld_clump.hip.h): `keep` of every pair set in the call's bitmap at
-// (u, v) and at (v, u).  The walk in P order follows the call's last launch (twk_hip_ld_clump).
-int launch_clump(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
-	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
-	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
-	if (!t.nA || !t.nB) return TWK_HIP_OK;
-	HIPCHK(c, s.h_cl_args.reserve(2, 2, nullptr));
-	HIPCHK(c, s.d_cl_args.reserve(2, 2, nullptr));
-	const uint32_t gx = (t.nB + CLUMP_THREADS - 1) / CLUMP_THREADS, gy = (t.nA + CLUMP_ROWS - 1) / CLUMP_ROWS;
-	if (gy > 0xFFFFu) return TWK_HIP_E_INVALID;
-	s.h_cl_args[which].p = p; s.h_cl_args[which].pm = c->clump_map;      // (the slot's previous launch has been waited for: its copy is done)
-	HIPCHK(c, hipMemcpyAsync(s.d_cl_args + which, s.h_cl_args + which, sizeof(ClumpArgs), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(k_ld_clump_mask, dim3(gx, gy), dim3(CLUMP_THREADS), 0, c->s_compute, (const ClumpArgs*)(s.d_cl_args + which));
-	HIPCHK(c, hipGetLastError());
-	return TWK_HIP_OK;
-}
-
-// The matrix epilogue of a launch whose count matrix is in the slot's C (ld_matrix.hip.h): the chosen statistic of every pair with a
-// record stored at (u, v) and at (v, u) of the call's matrix.  The diagonal and the copy to the host follow the call's last launch
-// (twk_hip_ld_matrix).
-int launch_matrix(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
-	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
-	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
-	if (!t.nA || !t.nB) return TWK_HIP_OK;
-	HIPCHK(c, s.h_mx_args.reserve(2, 2, nullptr));
-	HIPCHK(c, s.d_mx_args.reserve(2, 2, nullptr));
-	const uint32_t gx = (t.nB + MATRIX_THREADS - 1) / MATRIX_THREADS, gy = (t.nA + MATRIX_ROWS - 1) / MATRIX_ROWS;
-	if (gy > 0xFFFFu) return TWK_HIP_E_INVALID;
-	s.h_mx_args[which].p = p; s.h_mx_args[which].mm = c->matrix_map;      // (the slot's previous launch has been waited for: its copy is done)
-	HIPCHK(c, hipMemcpyAsync(s.d_mx_args + which, s.h_mx_args + which, sizeof(MatrixArgs), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(k_ld_matrix_fill, dim3(gx, gy), dim3(MATRIX_THREADS), 0, c->s_compute, (const MatrixArgs*)(s.d_mx_args + which));
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -1031,14 +995,8 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 			if (form.three) { rc = launch_recount(c, kind1, s); if (rc) return rc; }
 			rc = launch_list_math(c, s, l.d_stats_dev); if (rc) return rc;
 		}
-	} else if (form.score) {
-		rc = launch_score(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
-	} else if (form.prune) {
-		rc = launch_prune(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
-	} else if (form.clump) {
-		rc = launch_clump(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
-	} else if (form.matrix) {
-		rc = launch_matrix(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
+	} else if (form.reduces()) {
+		rc = launch_reduce(c, kind1, t, s, 0, pl.phased1, pl.select1, f, cr); if (rc) return rc;
 	} else {
 		const StatsParams p = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
 		hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -1046,10 +1004,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	HIPCHK(c, hipGetLastError());
 	if (form.two_pass) {
 		rc = launch_count(c, kind2, t, s, 1, cr, LaunchForm(), nullptr); if (rc) return rc;
-		if (form.score) { rc = launch_score(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
-		else if (form.prune) { rc = launch_prune(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
-		else if (form.clump) { rc = launch_clump(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
-		else if (form.matrix) { rc = launch_matrix(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
+		if (form.reduces()) { rc = launch_reduce(c, kind2, t, s, 1, false, 2, f, nullptr); if (rc) return rc; }
 		else {
 			const StatsParams p = make_stats(c, kind2, t, s, false, 2, f);
 			hipLaunchKernelGGL(k_ld_stats, dim3((t.nB + 255) / 256, t.nA), dim3(256), 0, c->s_compute, p);
@@ -2262,7 +2217,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = !c->reduce_on();      // a score, a prune, a clump or a matrix looks at every pair: no screen in front of the count matrix
+	c->fused_ok = c->three_ok = c->reduce == Reduce::none;      // a score, a prune, a clump or a matrix looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2336,113 +2291,160 @@ int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 	return rc;
 }
 
-// LD scores: the region call's planner and launch pipeline with the score epilogue in place of math, Fisher, sort and delivery.
+extern "C++" {      // (member templates)
+namespace {
+// One call of twk_hip_ld_score, _prune, _clump or _matrix: the region call's planner and launch pipeline with the kind's epilogue in place of
+// math, Fisher, sort and delivery (launch_reduce).  Constructed at the top of the entry point, which returns `bad` if the shared checks found
+// something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the buffer
+// that lived for the call released, the graveyard flushed.
+struct ReduceCall {
+	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
+	int bad;
+	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
+	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
+		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
+	ReduceCall(const ReduceCall&) = delete;
+	int check(bool own_args_ok, int mode, uint32_t a0, uint32_t n) {
+		if (!c || !f || !own_args_ok || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
+		if (!c->raw) return TWK_HIP_E_STATE;
+		if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M) return TWK_HIP_E_INVALID;
+		HIPCHK(c, hipSetDevice(c->device));
+		return TWK_HIP_OK;
+	}
+	~ReduceCall() {
+		if (bad) return;
+		c->reduce = Reduce::none; c->map = PruneMap{}; c->matrix_map = MatrixMap{};
+		(void)hipDeviceSynchronize();
+		c->d_adj.reset(); c->d_matrix.reset();      // what lived for the call (hold)
+		flush_graveyard(c);                 // buffers outgrown during the call: nothing is in flight any more
+	}
+	// The buffer that lives as long as the call - gigabytes that a record run behind this call may need, so it goes back when the call ends,
+	// whichever way - or the call fails with `what`: a format of the variant count, the bytes wanted and the runtime's reason.  With it the
+	// call's three counters, zeroed.
+	template <class T>
+	int hold(DevBuf<T>& b, size_t items, const char* what, uint32_t n) {
+		const hipError_t e = b.reserve(items, items, nullptr);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			snprintf(c->err, sizeof(c->err), what, n, items * sizeof(T), hipGetErrorString(e));
+			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+		}
+		HIPCHK(c, c->d_counts.reserve(3, 3, nullptr));
+		HIPCHK(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
+		return TWK_HIP_OK;
+	}
+	// prune, clump: the adjacency bitmap of the slice [a0, a0 + n), n * ceil(n / 64) words whatever the window (ld_prune.hip.h), held, cleared
+	// and armed
+	int bitmap(uint32_t a0, uint32_t n, const char* what) {
+		const uint32_t stride = (n + 63) / 64;
+		const size_t words = (size_t)n * stride;
+		const int rc = hold(c->d_adj, words, what, n); if (rc) return rc;
+		HIPCHK(c, hipMemsetAsync(c->d_adj, 0, words * sizeof(unsigned long long), c->s_compute));
+		c->map = PruneMap{c->d_adj, c->d_counts, a0, n, stride};
+		arm(words * sizeof(unsigned long long));
+		return TWK_HIP_OK;
+	}
+	// From here on the call's launches take the kind's epilogue.  bytes: what twk_hip_*_last reports of this call.
+	void arm(uint64_t bytes) { c->reduce_last[(int)kind].ms = 0; c->reduce_last[(int)kind].bytes = bytes; c->reduce = kind; }
+	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a reduce call)
+	int dispatch(RegionArgs a) {
+		a.window &= ~(int32_t)TWK_HIP_OPT_R2_SCREEN;
+		return region_dispatch(c, a);
+	}
+	// ... over the triangle of the slice [a0, a0 + n).  A single variant has no pair.
+	int dispatch(int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window, uint64_t* n_pairs) {
+		if (n < 2) { if (n_pairs) *n_pairs = 0; return TWK_HIP_OK; }
+		return dispatch(RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	}
+	// What follows the call's last launch on its stream: `timed` between two events - their distance is the call's `ms` of twk_hip_*_last -
+	// then `rest`, then one wait for the stream.  Both enqueue and return the runtime's verdict.
+	template <class Timed, class Rest>
+	int tail(const char* what, Timed&& timed, Rest&& rest) {
+		Event w0, w1;
+		hipError_t e = hipEventCreate(&w0.e);
+		if (e == hipSuccess) e = hipEventCreate(&w1.e);
+		if (e == hipSuccess) e = hipEventRecord(w0.e, c->s_compute);
+		if (e == hipSuccess) e = timed();
+		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
+		if (e == hipSuccess) e = rest();
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->reduce_last[(int)kind].ms = ms;
+		return TWK_HIP_OK;
+	}
+};
+
+int last_of(const twk_hip_ctx* c, Reduce kind, double* ms, uint64_t* bytes) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (ms) *ms = c->reduce_last[(int)kind].ms;
+	if (bytes) *bytes = c->reduce_last[(int)kind].bytes;
+	return TWK_HIP_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+// LD scores: per-variant sums over the records of the region (a rectangle or a triangle, a shard of it: the region call's geometry).
 int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
                      uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
                      uint64_t* n_partners, double* sum_r2, uint64_t* n_pairs) {
-	if (!c || !f || !n_partners || !sum_r2 || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
-	if (!c->raw) return TWK_HIP_E_STATE;
-	HIPCHK(c, hipSetDevice(c->device));
+	ReduceCall call(c, Reduce::score, f, n_partners && sum_r2, mode, a0, nA);
+	if (call.bad) return call.bad;
 	const size_t M = c->M;
 	HIPCHK(c, c->d_score_sum.reserve(M, M, nullptr));
 	HIPCHK(c, c->d_score_n.reserve(M, M, nullptr));
 	HIPCHK(c, hipMemsetAsync(c->d_score_sum, 0, M * sizeof(double), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(c->d_score_n, 0, M * sizeof(unsigned long long), c->s_compute));
-	struct ScoreOn { twk_hip_ctx* c; ~ScoreOn() { c->score_on = false; } } on{c};
-	c->score_on = true;
-	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a score)
-	int rc = region_dispatch(c, RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
-	                                       nullptr, nullptr, n_pairs, nullptr});
-	if (rc == TWK_HIP_OK) {
-		hipError_t e = hipMemcpyAsync(sum_r2, c->d_score_sum, M * sizeof(double), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "score arrays: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
-	} else (void)hipDeviceSynchronize();
-	flush_graveyard(c);
-	return rc;
-}
-
-// LD pruning: the same planner and pipeline with the prune epilogue, then the greedy walk over the bitmap the launches filled.
-int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
-                     int32_t window, uint32_t l_window, uint8_t* keep, uint64_t* n_kept, uint64_t* n_edges, uint64_t* n_pairs) {
-	if (!c || !f || !keep || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
-	if (!c->raw) return TWK_HIP_E_STATE;
-	if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M) return TWK_HIP_E_INVALID;
-	HIPCHK(c, hipSetDevice(c->device));
-	const size_t M = c->M;
-	const uint32_t stride = (n + 63) / 64;
-	const size_t words = (size_t)n * stride;
-	{	// the adjacency bitmap: n * ceil(n / 64) words, whatever the window (ld_prune.hip.h)
-		const hipError_t e = c->d_prune_adj.reserve(words, words, nullptr);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			snprintf(c->err, sizeof(c->err), "LD pruning of %u variants needs an adjacency bitmap of %zu bytes: %s", n, words * sizeof(unsigned long long), hipGetErrorString(e));
-			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
-		}
-	}
-	// (the bitmap goes back when the call ends, whichever way: gigabytes that a record run behind this call may need)
-	struct PruneOn { twk_hip_ctx* c; ~PruneOn() { c->prune_on = false; c->prune_map = PruneMap{}; (void)hipDeviceSynchronize(); c->d_prune_adj.reset(); } } on{c};
-	const bool in_lds = stride <= WALK_LDS_WORDS;
-	HIPCHK(c, c->d_prune_keep.reserve(M, M, nullptr));
-	HIPCHK(c, c->d_prune_counts.reserve(2, 2, nullptr));
-	if (!in_lds) HIPCHK(c, c->d_prune_removed.reserve(stride, stride, nullptr));
-	HIPCHK(c, hipMemsetAsync(c->d_prune_adj, 0, words * sizeof(unsigned long long), c->s_compute));
-	HIPCHK(c, hipMemsetAsync(c->d_prune_keep, 0, M, c->s_compute));
-	HIPCHK(c, hipMemsetAsync(c->d_prune_counts, 0, 2 * sizeof(unsigned long long), c->s_compute));
-	if (!in_lds) HIPCHK(c, hipMemsetAsync(c->d_prune_removed, 0, (size_t)stride * sizeof(unsigned long long), c->s_compute));
-	c->prune_map = PruneMap{c->d_prune_adj, c->d_prune_counts, a0, n, stride};
-	c->prune_walk_ms = 0; c->prune_bitmap_bytes = words * sizeof(unsigned long long);
-	c->prune_on = true;
-	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a prune.  A single variant has no pair.)
-	int rc = n < 2 ? TWK_HIP_OK
-	               : region_dispatch(c, RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
-	                                               nullptr, nullptr, n_pairs, nullptr});
-	if (n < 2 && n_pairs) *n_pairs = 0;
-	if (rc == TWK_HIP_OK) {
-		unsigned long long counts[2] = {0, 0};
-		Event w0, w1;
-		HIPCHK(c, hipEventCreate(&w0.e)); HIPCHK(c, hipEventCreate(&w1.e));
-		HIPCHK(c, hipEventRecord(w0.e, c->s_compute));
-		if (in_lds) hipLaunchKernelGGL(k_ld_prune_walk<true>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_prune_adj, a0, n, stride,
-		                               (unsigned long long*)nullptr, c->d_prune_keep.get(), c->d_prune_counts + 1);
-		else hipLaunchKernelGGL(k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_prune_adj, a0, n, stride,
-		                        c->d_prune_removed.get(), c->d_prune_keep.get(), c->d_prune_counts + 1);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpyAsync(keep, c->d_prune_keep, M, hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpyAsync(counts, c->d_prune_counts, sizeof(counts), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "prune walk: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
-		else {
-			if (n_edges) *n_edges = counts[0];
-			if (n_kept) *n_kept = counts[1];
-			float ms = 0;
-			if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->prune_walk_ms = ms;
-		}
-	}
-	flush_graveyard(c);
-	return rc;
-}
-
-int twk_hip_prune_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) {
-	if (!c) return TWK_HIP_E_INVALID;
-	if (walk_ms) *walk_ms = c->prune_walk_ms;
-	if (bitmap_bytes) *bitmap_bytes = c->prune_bitmap_bytes;
+	call.arm(0);
+	const int rc = call.dispatch(RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	if (rc) return rc;
+	hipError_t e = hipMemcpyAsync(sum_r2, c->d_score_sum, M * sizeof(double), hipMemcpyDeviceToHost, c->s_compute);
+	if (e == hipSuccess) e = hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+	if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "score arrays: %s", hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
 	return TWK_HIP_OK;
 }
 
-// LD clumping: the same planner and pipeline with the clump epilogue, then the walk in P order over the bitmap the launches filled.
+// LD pruning: the greedy walk over the bitmap the launches filled.
+int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window, uint8_t* keep, uint64_t* n_kept, uint64_t* n_edges, uint64_t* n_pairs) {
+	ReduceCall call(c, Reduce::prune, f, keep != nullptr, mode, a0, n);
+	if (call.bad) return call.bad;
+	const size_t M = c->M;
+	const uint32_t stride = (n + 63) / 64;
+	int rc = call.bitmap(a0, n, "LD pruning of %u variants needs an adjacency bitmap of %zu bytes: %s"); if (rc) return rc;
+	const bool in_lds = stride <= WALK_LDS_WORDS;
+	HIPCHK(c, c->d_prune_keep.reserve(M, M, nullptr));
+	if (!in_lds) HIPCHK(c, c->d_walk.reserve(stride, stride, nullptr));
+	HIPCHK(c, hipMemsetAsync(c->d_prune_keep, 0, M, c->s_compute));
+	if (!in_lds) HIPCHK(c, hipMemsetAsync(c->d_walk, 0, (size_t)stride * sizeof(unsigned long long), c->s_compute));
+	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
+	unsigned long long counts[2] = {0, 0};
+	rc = call.tail("prune walk", [&] {
+		hipLaunchKernelGGL(in_lds ? k_ld_prune_walk<true> : k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_adj,
+		                   a0, n, stride, in_lds ? nullptr : c->d_walk.get(), c->d_prune_keep.get(), c->d_counts + 1);
+		return hipGetLastError();
+	}, [&] {
+		const hipError_t e = hipMemcpyAsync(keep, c->d_prune_keep, M, hipMemcpyDeviceToHost, c->s_compute);
+		return e != hipSuccess ? e : hipMemcpyAsync(counts, c->d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->s_compute);
+	});
+	if (rc) return rc;
+	if (n_edges) *n_edges = counts[0];
+	if (n_kept) *n_kept = counts[1];
+	return TWK_HIP_OK;
+}
+
+int twk_hip_prune_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) { return last_of(c, Reduce::prune, walk_ms, bitmap_bytes); }
+
+// LD clumping: the walk in P order over the bitmap the launches filled from both ends of a pair.
 int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
                      int32_t window, uint32_t l_window, const double* p, double p1, double p2,
                      uint32_t* index_of, uint64_t* n_clumps, uint64_t* n_members, uint64_t* n_edges, uint64_t* n_pairs) {
-	if (!c || !f || !p || !index_of || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
-	if (!(p1 >= 0.0 && p1 <= p2 && p2 <= 1.0)) return TWK_HIP_E_INVALID;          // (a NaN fails every comparison)
-	if (!c->raw) return TWK_HIP_E_STATE;
-	if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M) return TWK_HIP_E_INVALID;
+	ReduceCall call(c, Reduce::clump, f, p && index_of && p1 >= 0.0 && p1 <= p2 && p2 <= 1.0, mode, a0, n);      // (a NaN fails every comparison)
+	if (call.bad) return call.bad;
 	const size_t M = c->M;
 	const uint32_t stride = (n + 63) / 64;
-	const size_t words = (size_t)n * stride;
 	// the candidates (P <= p1) in visiting order - ascending P, ties in file order - and the variants that can belong to no clump
 	std::vector<uint32_t> order;
 	std::vector<unsigned long long> taken0(stride, 0ull);
@@ -2458,131 +2460,64 @@ int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	// (p1 <= p2: every candidate is eligible - an index variant that may not be in a clump cannot arise)
 	for (const uint32_t v : order) if (taken0[v >> 6] >> (v & 63) & 1) return TWK_HIP_E_INVALID;
 	const uint32_t m = (uint32_t)order.size();
-	HIPCHK(c, hipSetDevice(c->device));
-	{	// the adjacency bitmap: n * ceil(n / 64) words, whatever the window (ld_prune.hip.h), both triangles used
-		const hipError_t e = c->d_clump_adj.reserve(words, words, nullptr);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			snprintf(c->err, sizeof(c->err), "LD clumping of %u variants needs an adjacency bitmap of %zu bytes: %s", n, words * sizeof(unsigned long long), hipGetErrorString(e));
-			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
-		}
-	}
-	// (the bitmap goes back when the call ends, whichever way: gigabytes that a record run behind this call may need)
-	struct ClumpOn { twk_hip_ctx* c; ~ClumpOn() { c->clump_on = false; c->clump_map = PruneMap{}; (void)hipDeviceSynchronize(); c->d_clump_adj.reset(); } } on{c};
+	int rc = call.bitmap(a0, n, "LD clumping of %u variants needs an adjacency bitmap of %zu bytes: %s"); if (rc) return rc;      // (both triangles used)
 	const bool in_lds = stride <= CLUMP_LDS_WORDS;
 	HIPCHK(c, c->d_clump_index.reserve(M, M, nullptr));
-	HIPCHK(c, c->d_clump_counts.reserve(3, 3, nullptr));
-	HIPCHK(c, c->d_clump_taken.reserve(stride, stride, nullptr));
+	HIPCHK(c, c->d_walk.reserve(stride, stride, nullptr));
 	HIPCHK(c, c->d_clump_order.reserve(m ? m : 1, m ? m : 1, nullptr));
-	HIPCHK(c, hipMemsetAsync(c->d_clump_adj, 0, words * sizeof(unsigned long long), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(c->d_clump_index, 0xFF, M * sizeof(uint32_t), c->s_compute));          // TWK_HIP_NO_CLUMP
-	HIPCHK(c, hipMemsetAsync(c->d_clump_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
 	// (from pageable memory: the copies have left `order` and `taken0` when they return; both live to the end of the call anyway)
-	HIPCHK(c, hipMemcpyAsync(c->d_clump_taken, taken0.data(), (size_t)stride * sizeof(unsigned long long), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemcpyAsync(c->d_walk, taken0.data(), (size_t)stride * sizeof(unsigned long long), hipMemcpyHostToDevice, c->s_compute));
 	if (m) HIPCHK(c, hipMemcpyAsync(c->d_clump_order, order.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
-	c->clump_map = PruneMap{c->d_clump_adj, c->d_clump_counts, a0, n, stride};
-	c->clump_walk_ms = 0; c->clump_bitmap_bytes = words * sizeof(unsigned long long);
-	c->clump_on = true;
-	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a clump.  A single variant has no pair.)
-	int rc = n < 2 ? TWK_HIP_OK
-	               : region_dispatch(c, RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
-	                                               nullptr, nullptr, n_pairs, nullptr});
-	if (n < 2 && n_pairs) *n_pairs = 0;
-	if (rc == TWK_HIP_OK) {
-		unsigned long long counts[3] = {0, 0, 0};
-		Event w0, w1;
-		HIPCHK(c, hipEventCreate(&w0.e)); HIPCHK(c, hipEventCreate(&w1.e));
-		HIPCHK(c, hipEventRecord(w0.e, c->s_compute));
-		if (in_lds) hipLaunchKernelGGL(k_ld_clump_walk<true>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_clump_adj, a0, n, stride,
-		                               (const uint32_t*)c->d_clump_order, m, c->d_clump_taken.get(), c->d_clump_index.get(), c->d_clump_counts + 1);
-		else hipLaunchKernelGGL(k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_clump_adj, a0, n, stride,
-		                        (const uint32_t*)c->d_clump_order, m, c->d_clump_taken.get(), c->d_clump_index.get(), c->d_clump_counts + 1);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpyAsync(index_of, c->d_clump_index, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpyAsync(counts, c->d_clump_counts, sizeof(counts), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "clump walk: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
-		else {
-			if (n_edges) *n_edges = counts[0];
-			if (n_clumps) *n_clumps = counts[1];
-			if (n_members) *n_members = counts[2];
-			float ms = 0;
-			if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->clump_walk_ms = ms;
-		}
-	}
-	flush_graveyard(c);
-	return rc;
-}
-
-int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) {
-	if (!c) return TWK_HIP_E_INVALID;
-	if (walk_ms) *walk_ms = c->clump_walk_ms;
-	if (bitmap_bytes) *bitmap_bytes = c->clump_bitmap_bytes;
+	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
+	unsigned long long counts[3] = {0, 0, 0};
+	rc = call.tail("clump walk", [&] {
+		hipLaunchKernelGGL(in_lds ? k_ld_clump_walk<true> : k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_adj,
+		                   a0, n, stride, (const uint32_t*)c->d_clump_order, m, c->d_walk.get(), c->d_clump_index.get(), c->d_counts + 1);
+		return hipGetLastError();
+	}, [&] {
+		const hipError_t e = hipMemcpyAsync(index_of, c->d_clump_index, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
+		return e != hipSuccess ? e : hipMemcpyAsync(counts, c->d_counts, sizeof(counts), hipMemcpyDeviceToHost, c->s_compute);
+	});
+	if (rc) return rc;
+	if (n_edges) *n_edges = counts[0];
+	if (n_clumps) *n_clumps = counts[1];
+	if (n_members) *n_members = counts[2];
 	return TWK_HIP_OK;
 }
 
-// LD matrix: the same planner and pipeline with the matrix epilogue; the matrix is preset to the fill in front of the launches, gets
-// its diagonal behind the last of them and leaves in one 2-D copy that honours the caller's row pitch.
+int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) { return last_of(c, Reduce::clump, walk_ms, bitmap_bytes); }
+
+// LD matrix: the matrix is preset to the fill in front of the launches, gets its diagonal behind the last of them and leaves in one 2-D
+// copy that honours the caller's row pitch.
 int twk_hip_ld_matrix(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
                       int32_t stat, float fill, float* out, uint64_t ld, uint64_t* n_records, uint64_t* n_pairs) {
-	if (!c || !f || !out || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
-	if (stat != TWK_HIP_STAT_R && stat != TWK_HIP_STAT_R2 && stat != TWK_HIP_STAT_D && stat != TWK_HIP_STAT_DPRIME) return TWK_HIP_E_INVALID;
-	if (!c->raw) return TWK_HIP_E_STATE;
-	if (!valid_mode(mode) || n == 0 || (uint64_t)a0 + n > c->M || ld < n) return TWK_HIP_E_INVALID;
-	HIPCHK(c, hipSetDevice(c->device));
+	const bool stat_ok = stat == TWK_HIP_STAT_R || stat == TWK_HIP_STAT_R2 || stat == TWK_HIP_STAT_D || stat == TWK_HIP_STAT_DPRIME;
+	ReduceCall call(c, Reduce::matrix, f, out && stat_ok, mode, a0, n);
+	if (call.bad) return call.bad;
+	if (ld < n) return TWK_HIP_E_INVALID;
 	const size_t cells = (size_t)n * n;
-	{	// the dense matrix: n * n floats, whatever the window
-		const hipError_t e = c->d_matrix.reserve(cells, cells, nullptr);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			snprintf(c->err, sizeof(c->err), "the LD matrix of %u variants needs %zu bytes of device memory: %s", n, cells * sizeof(float), hipGetErrorString(e));
-			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
-		}
-	}
-	// (the matrix goes back when the call ends, whichever way: gigabytes that a record run behind this call may need)
-	struct MatrixOn { twk_hip_ctx* c; ~MatrixOn() { c->matrix_on = false; c->matrix_map = MatrixMap{}; (void)hipDeviceSynchronize(); c->d_matrix.reset(); } } on{c};
-	HIPCHK(c, c->d_matrix_count.reserve(1, 1, nullptr));
+	// the dense matrix: n * n floats, whatever the window
+	int rc = call.hold(c->d_matrix, cells, "the LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
 	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
 	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_matrix.get(), (int)fill_bits, cells, c->s_compute));
-	HIPCHK(c, hipMemsetAsync(c->d_matrix_count, 0, sizeof(unsigned long long), c->s_compute));
-	c->matrix_map = MatrixMap{c->d_matrix, c->d_matrix_count, a0, n, stat};
-	c->matrix_copy_ms = 0; c->matrix_bytes = cells * sizeof(float);
-	c->matrix_on = true;
-	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a matrix.  A single variant has no pair.)
-	int rc = n < 2 ? TWK_HIP_OK
-	               : region_dispatch(c, RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window & ~(int32_t)TWK_HIP_OPT_R2_SCREEN, l_window,
-	                                               nullptr, nullptr, n_pairs, nullptr});
-	if (n < 2 && n_pairs) *n_pairs = 0;
-	if (rc == TWK_HIP_OK) {
-		unsigned long long count = 0;
-		Event w0, w1;
-		HIPCHK(c, hipEventCreate(&w0.e)); HIPCHK(c, hipEventCreate(&w1.e));
-		if (stat != TWK_HIP_STAT_D)      // (D: the diagonal keeps the preset fill - no launch stores on it)
-			hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, c->d_matrix.get(), n, 1.0f);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess) e = hipEventRecord(w0.e, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), c->d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
-		if (e == hipSuccess) e = hipMemcpyAsync(&count, c->d_matrix_count, sizeof(count), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "LD matrix: %s", hipGetErrorString(e)); rc = TWK_HIP_E_DEVICE; }
-		else {
-			if (n_records) *n_records = count;
-			float ms = 0;
-			if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->matrix_copy_ms = ms;
-		}
+	c->matrix_map = MatrixMap{c->d_matrix, c->d_counts, a0, n, stat};
+	call.arm(cells * sizeof(float));
+	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
+	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
+		hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, c->d_matrix.get(), n, 1.0f);
+		HIPCHK(c, hipGetLastError());
 	}
-	flush_graveyard(c);
-	return rc;
-}
-
-int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) {
-	if (!c) return TWK_HIP_E_INVALID;
-	if (copy_ms) *copy_ms = c->matrix_copy_ms;
-	if (matrix_bytes) *matrix_bytes = c->matrix_bytes;
+	unsigned long long count = 0;
+	rc = call.tail("LD matrix", [&] {
+		return hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), c->d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
+	}, [&] { return hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute); });
+	if (rc) return rc;
+	if (n_records) *n_records = count;
 	return TWK_HIP_OK;
 }
+
+int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) { return last_of(c, Reduce::matrix, copy_ms, matrix_bytes); }
 
 int twk_hip_shard_rows(uint32_t n_rows, uint32_t n_cols, int32_t triangle, uint32_t part, uint32_t n_parts,
                        uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs) {

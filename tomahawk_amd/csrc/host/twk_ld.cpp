@@ -941,74 +941,125 @@ bool twk_ld::Compute() {
 	return true;
 }
 
+// What `ldscore`, `prune`, `clump` and `ldmatrix` share around their one engine call: the checks common to all, the input loaded exactly as
+// Compute loads it onto one GPU, the text output with its `##` header, the `contig \t pos` that begins a variant's line, the closing lines.
+namespace {
+struct ReduceCommand {
+	using clock = std::chrono::steady_clock;
+	twk_ld_settings& settings;
+	std::vector<uint32_t>& rid; std::vector<uint32_t>& pos;      // per variant of the uploaded selection (twk_ld_impl)
+	Selection S;
+	DeviceCtxs dc;
+	twk_hip_ctx* ctx = nullptr;
+	uint32_t M = 0;
+	int mode = TWK_HIP_MODE_AUTO, options = 0;
+	twk_hip_filters f{};
+	clock::time_point t_load;
+	std::ofstream file;
+
+	// The input's name; the P cut-off (every: why the command cannot have one, "A score sums over every record"); -c / -C (partial: why
+	// not, "Cannot prune a part of the pair space: the walk needs every pair"; null: the command takes a part)
+	bool check(const char* every, const char* partial) const {
+		if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
+		if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << every << ": a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
+		if (partial && settings.n_chunks != 1) { std::cerr << stamp("ERROR") << partial << " (no -c / -C)..." << std::endl; return false; }
+		return true;
+	}
+	// Selection, device, upload; mode, filters and options of the engine call.  Unless `ready` the command ends: `empty` - the selection
+	// holds nothing, nothing to do - is its success, `failed` an error, reported
+	enum Loaded { failed, empty, ready };
+	Loaded load(const std::vector<std::pair<std::string, int64_t>>& engine_options) {
+		bool nothing_to_do = false;
+		if (!select_blocks(settings, S, &nothing_to_do)) return failed;
+		if (nothing_to_do) return empty;
+		M = S.M;
+		if (!create_devices(dc, 1, engine_options)) return failed;
+		ctx = dc.ctx[0];
+		t_load = clock::now();
+		const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
+		std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
+		if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, rid, pos)) return failed;
+		std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
+		          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
+		mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
+		f = twk_hip_filters{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
+		options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+		return ready;
+	}
+	// The text output: -o, or stdout.  -> null after an error message
+	std::ostream* open_text() {
+		if (settings.out.empty() || settings.out == "-") return &std::cout;
+		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
+		file.open(settings.out, std::ios::out | std::ios::trunc);
+		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return nullptr; }
+		return &file;
+	}
+	// The `##` lines every command's text begins with (name: "ldscore", "prune", ...); the command's own lines follow
+	void header(std::ostream& os, const char* name) const {
+		os << "##tomahawk_" << name << "Version=" << TWK_AMD_VERSION << "\n"
+		   << "##tomahawk_" << name << "Command=" << command_line() << "; Date=" << datetime() << "\n"
+		   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
+		char line[256];
+		snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
+		os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n";
+	}
+	// Contig and position of variant v as `view` prints them for a record's A side: the contig's name, a tab, the 1-based position
+	void place(std::string& text, uint32_t v) const {
+		if (rid[v] < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid[v]].name; else text += '.';
+		text += '\t'; text += std::to_string(pos[v] + 1);
+	}
+	// (a variant's line is complete: the text goes out a megabyte at a time)
+	static void spill(std::ostream& os, std::string& text) { if (text.size() > (1u << 20)) { os << text; text.clear(); } }
+	// The rest of the text; -> false after "Failed to write <what>..."
+	static bool finish(std::ostream& os, std::string& text, const char* what) {
+		os << text;
+		os.flush();
+		if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write " << what << "..." << std::endl; return false; }
+		return true;
+	}
+	void all_done() const {
+		std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	}
+};
+}  // namespace
+
 // `tomahawk ldscore`: per variant of the selection the number of records Compute would write with the variant at either end and the
 // sum of their R2 (twk_hip_ld_score: reduced on the GPU, no record is formed), as text.  The input is loaded exactly as Compute loads
 // it; one GPU.  Not in the reference.
 bool twk_ld::Score(const twk_ld_settings& s) {
-	using clock = std::chrono::steady_clock;
 	settings = s;
 	mImpl->n_pairs = mImpl->n_records = 0;
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
-	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "A score sums over every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
-	Selection S;
-	bool nothing_to_do = false;
-	if (!select_blocks(settings, S, &nothing_to_do)) return false;
-	if (nothing_to_do) return true;
-	const Balancer& bal = S.bal;
-	const uint32_t M = S.M;
-	DeviceCtxs dc;
-	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
-	twk_hip_ctx* ctx = dc.ctx[0];
-	const auto t_load = clock::now();
-	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
-	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
-	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
-	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
-	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
-
-	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
-	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
-	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("A score sums over every record", nullptr)) return false;
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const Selection& S = cmd.S;
+	const uint32_t M = cmd.M;
 	std::vector<uint64_t> n_partners(M, 0);
 	std::vector<double> sum_r2(M, 0.0);
 	uint64_t np = 0;
-	const auto t0 = clock::now();
+	const auto t0 = ReduceCommand::clock::now();
 	int rc = TWK_HIP_OK;
-	if (bal.diag) { if (M > 1) rc = twk_hip_ld_score(ctx, mode, &f, 0, M, 0, M, 1, 0, 1, 0, options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np); }
-	else if (S.nL && S.nR) rc = twk_hip_ld_score(ctx, mode, &f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
-	if (!hip_ok(ctx, rc, "twk_hip_ld_score")) return false;
+	if (S.bal.diag) { if (M > 1) rc = twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, M, 1, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np); }
+	else if (S.nL && S.nR) rc = twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_score")) return false;
 	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
 
-	std::ofstream file;
-	const bool to_stdout = settings.out.empty() || settings.out == "-";
-	if (!to_stdout) {
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
-		file.open(settings.out, std::ios::out | std::ios::trunc);
-		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return false; }
-	}
-	std::ostream& os = to_stdout ? std::cout : file;
-	os << "##tomahawk_ldscoreVersion=" << TWK_AMD_VERSION << "\n"
-	   << "##tomahawk_ldscoreCommand=" << command_line() << "; Date=" << datetime() << "\n"
-	   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
-	char line[256];
-	snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
-	os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n"
-	   << "#contig\tpos\tn_partners\tsum_r2\n";
+	std::ostream* const os = cmd.open_text();
+	if (!os) return false;
+	cmd.header(*os, "ldscore");
+	*os << "#contig\tpos\tn_partners\tsum_r2\n";
 	std::string text;
+	char line[256];
 	for (uint32_t v = 0; v < M; ++v) {
-		const uint32_t rid = mImpl->rid[v];
-		// (contig and position as `view` prints them for a record's A side: the contig's name, the 1-based position)
-		if (rid < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid].name; else text += '.';
-		snprintf(line, sizeof(line), "\t%u\t%llu\t%.17g\n", mImpl->pos[v] + 1, (unsigned long long)n_partners[v], sum_r2[v]);
+		cmd.place(text, v);
+		snprintf(line, sizeof(line), "\t%llu\t%.17g\n", (unsigned long long)n_partners[v], sum_r2[v]);
 		text += line;
-		if (text.size() > (1u << 20)) { os << text; text.clear(); }
+		cmd.spill(*os, text);
 	}
-	os << text;
-	os.flush();
-	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the scores..." << std::endl; return false; }
+	if (!cmd.finish(*os, text, "the scores")) return false;
 	std::cerr << stamp("LOG") << "Scored " << pretty(M) << " variants over " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
-	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	cmd.all_done();
 	return true;
 }
 
@@ -1016,69 +1067,36 @@ bool twk_ld::Score(const twk_ld_settings& s) {
 // decided and walked on the GPU, no record is formed), as text: one line per variant with its keep flag.  The input is loaded exactly
 // as Compute loads it; one GPU; the whole triangle (the walk needs every pair: no -c / -C).  Not in the reference.
 bool twk_ld::Prune(const twk_ld_settings& s) {
-	using clock = std::chrono::steady_clock;
 	settings = s;
 	mImpl->n_pairs = mImpl->n_records = 0;
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
-	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "Pruning looks at every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
-	if (settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space: the walk needs every pair (no -c / -C)..." << std::endl; return false; }
-	Selection S;
-	bool nothing_to_do = false;
-	if (!select_blocks(settings, S, &nothing_to_do)) return false;
-	if (nothing_to_do) return true;
-	const uint32_t M = S.M;
-	DeviceCtxs dc;
-	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
-	twk_hip_ctx* ctx = dc.ctx[0];
-	const auto t_load = clock::now();
-	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
-	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
-	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
-	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
-	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
-
-	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
-	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
-	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("Pruning looks at every record", "Cannot prune a part of the pair space: the walk needs every pair")) return false;
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const uint32_t M = cmd.M;
 	std::vector<uint8_t> keep(M, 0);
 	uint64_t np = 0, n_kept = 0, n_edges = 0;
-	const auto t0 = clock::now();
-	const int rc = twk_hip_ld_prune(ctx, mode, &f, 0, M, 0, options, (uint32_t)settings.l_window, keep.data(), &n_kept, &n_edges, &np);
-	if (!hip_ok(ctx, rc, "twk_hip_ld_prune")) return false;
+	const auto t0 = ReduceCommand::clock::now();
+	const int rc = twk_hip_ld_prune(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, keep.data(), &n_kept, &n_edges, &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_prune")) return false;
 	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
 
-	std::ofstream file;
-	const bool to_stdout = settings.out.empty() || settings.out == "-";
-	if (!to_stdout) {
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
-		file.open(settings.out, std::ios::out | std::ios::trunc);
-		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return false; }
-	}
-	std::ostream& os = to_stdout ? std::cout : file;
-	os << "##tomahawk_pruneVersion=" << TWK_AMD_VERSION << "\n"
-	   << "##tomahawk_pruneCommand=" << command_line() << "; Date=" << datetime() << "\n"
-	   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
+	std::ostream* const os = cmd.open_text();
+	if (!os) return false;
+	cmd.header(*os, "prune");
 	char line[256];
-	snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
-	os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n";
 	snprintf(line, sizeof(line), "##kept=%llu,total=%u,edges=%llu\n", (unsigned long long)n_kept, M, (unsigned long long)n_edges);
-	os << line << "#contig\tpos\tkeep\n";
+	*os << line << "#contig\tpos\tkeep\n";
 	std::string text;
 	for (uint32_t v = 0; v < M; ++v) {
-		const uint32_t rid = mImpl->rid[v];
-		// (contig and position as `ldscore` prints them: the contig's name, the 1-based position)
-		if (rid < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid].name; else text += '.';
-		snprintf(line, sizeof(line), "\t%u\t%u\n", mImpl->pos[v] + 1, keep[v] ? 1u : 0u);
-		text += line;
-		if (text.size() > (1u << 20)) { os << text; text.clear(); }
+		cmd.place(text, v);
+		text += keep[v] ? "\t1\n" : "\t0\n";
+		cmd.spill(*os, text);
 	}
-	os << text;
-	os.flush();
-	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the keep flags..." << std::endl; return false; }
+	if (!cmd.finish(*os, text, "the keep flags")) return false;
 	std::cerr << stamp("LOG") << "Pruned: kept " << pretty(n_kept) << " of " << pretty(M) << " variants; " << pretty(n_edges) << " pairs in LD among "
 	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
-	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	cmd.all_done();
 	return true;
 }
 
@@ -1127,33 +1145,19 @@ bool read_assoc(const std::string& path, AssocMap& out) {
 // association file is read and checked before the input is opened or a device touched; the input is then loaded exactly as Prune
 // loads it; one GPU; the whole triangle (no -c / -C).  Not in the reference.
 bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
-	using clock = std::chrono::steady_clock;
 	settings = s;
 	mImpl->n_pairs = mImpl->n_records = 0;
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
-	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "Clumping looks at every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
-	if (settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space: the walk needs every pair (no -c / -C)..." << std::endl; return false; }
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("Clumping looks at every record", "Cannot clump a part of the pair space: the walk needs every pair")) return false;
 	if (!(cs.p1 >= 0 && cs.p1 <= cs.p2 && cs.p2 <= 1)) { std::cerr << stamp("ERROR") << "The clumping thresholds must satisfy 0 <= p1 <= p2 <= 1..." << std::endl; return false; }
 	if (cs.assoc.empty()) { std::cerr << stamp("ERROR") << "No association file provided..." << std::endl; return false; }
 	AssocMap assoc;
 	if (!read_assoc(cs.assoc, assoc)) return false;
-	Selection S;
-	bool nothing_to_do = false;
-	if (!select_blocks(settings, S, &nothing_to_do)) return false;
-	if (nothing_to_do) return true;
-	const uint32_t M = S.M;
-	DeviceCtxs dc;
-	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
-	twk_hip_ctx* ctx = dc.ctx[0];
-	const auto t_load = clock::now();
-	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
-	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
-	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
-	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
-	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const uint32_t M = cmd.M;
 
 	// every variant of the selection at a (contig, position) the file names gets that P
-	const auto& contigs = S.reader.hdr.contigs;
+	const auto& contigs = cmd.S.reader.hdr.contigs;
 	std::vector<double> p(M, std::numeric_limits<double>::quiet_NaN());
 	uint64_t n_with_p = 0;
 	for (uint32_t v = 0; v < M; ++v) {
@@ -1170,54 +1174,36 @@ bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
 	std::cerr << stamp("LOG") << "Association file: " << pretty(assoc.size()) << " lines, " << pretty(n_unmatched) << " name no selected variant; "
 	          << pretty(n_with_p) << " of " << pretty(M) << " variants have a P value." << std::endl;
 
-	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
-	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
-	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
 	std::vector<uint32_t> index_of(M, TWK_HIP_NO_CLUMP);
 	uint64_t np = 0, n_clumps = 0, n_members = 0, n_edges = 0;
-	const auto t0 = clock::now();
-	const int rc = twk_hip_ld_clump(ctx, mode, &f, 0, M, 0, options, (uint32_t)settings.l_window, p.data(), cs.p1, cs.p2, index_of.data(), &n_clumps, &n_members, &n_edges, &np);
-	if (!hip_ok(ctx, rc, "twk_hip_ld_clump")) return false;
+	const auto t0 = ReduceCommand::clock::now();
+	const int rc = twk_hip_ld_clump(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, p.data(), cs.p1, cs.p2, index_of.data(), &n_clumps, &n_members, &n_edges, &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_clump")) return false;
 	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
 
-	std::ofstream file;
-	const bool to_stdout = settings.out.empty() || settings.out == "-";
-	if (!to_stdout) {
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
-		file.open(settings.out, std::ios::out | std::ios::trunc);
-		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return false; }
-	}
-	std::ostream& os = to_stdout ? std::cout : file;
-	os << "##tomahawk_clumpVersion=" << TWK_AMD_VERSION << "\n"
-	   << "##tomahawk_clumpCommand=" << command_line() << "; Date=" << datetime() << "\n"
-	   << "##mode=" << (mode == TWK_HIP_MODE_PHASED ? "phased" : mode == TWK_HIP_MODE_UNPHASED ? "unphased" : "per-pair (unphased where either variant has missing genotypes)") << "\n";
+	std::ostream* const os = cmd.open_text();
+	if (!os) return false;
+	cmd.header(*os, "clump");
 	char line[256];
-	snprintf(line, sizeof(line), "##filters=minR2=%.17g,maxR2=%.17g,minDprime=%.17g,maxDprime=%.17g,minP=%.17g\n", f.minR2, f.maxR2, f.minDprime, f.maxDprime, f.minP);
-	os << line << "##window=" << (settings.window ? std::to_string(settings.l_window) + " bases" : std::string("none")) << "\n";
 	snprintf(line, sizeof(line), "##thresholds=p1=%.17g,p2=%.17g\n", cs.p1, cs.p2);
-	os << line;
+	*os << line;
 	snprintf(line, sizeof(line), "##clumps=%llu,members=%llu,total=%u,edges=%llu\n", (unsigned long long)n_clumps, (unsigned long long)n_members, M, (unsigned long long)n_edges);
-	os << line << "#contig\tpos\tP\tindex_contig\tindex_pos\n";
+	*os << line << "#contig\tpos\tP\tindex_contig\tindex_pos\n";
 	std::string text;
-	auto contig_name = [&](uint32_t v) -> std::string { const uint32_t rid = mImpl->rid[v]; return rid < contigs.size() ? contigs[rid].name : std::string("."); };
 	for (uint32_t v = 0; v < M; ++v) {
-		// (contig and position as `ldscore` prints them: the contig's name, the 1-based position)
-		text += contig_name(v);
-		if (p[v] == p[v]) snprintf(line, sizeof(line), "\t%u\t%.17g\t", mImpl->pos[v] + 1, p[v]);
-		else snprintf(line, sizeof(line), "\t%u\tNA\t", mImpl->pos[v] + 1);
-		text += line;
+		cmd.place(text, v);
+		if (p[v] == p[v]) { snprintf(line, sizeof(line), "\t%.17g\t", p[v]); text += line; }
+		else text += "\tNA\t";
 		const uint32_t ix = index_of[v];
-		if (ix < M) { text += contig_name(ix); snprintf(line, sizeof(line), "\t%u\n", mImpl->pos[ix] + 1); text += line; }
+		if (ix < M) { cmd.place(text, ix); text += '\n'; }
 		else text += ".\t.\n";
-		if (text.size() > (1u << 20)) { os << text; text.clear(); }
+		cmd.spill(*os, text);
 	}
-	os << text;
-	os.flush();
-	if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the clumps..." << std::endl; return false; }
+	if (!cmd.finish(*os, text, "the clumps")) return false;
 	std::cerr << stamp("LOG") << "Clumped: " << pretty(n_clumps) << " index variants claimed " << pretty(n_members) << " of " << pretty(M) << " variants; " << pretty(n_edges)
 	          << " pairs in LD among " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
-	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	cmd.all_done();
 	return true;
 }
 
@@ -1225,41 +1211,23 @@ bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
 // on the GPU at (u, v) and (v, u), no record is formed), as a NumPy file or as text, with the rows' variants next to it.  The input is
 // loaded exactly as Prune loads it; one GPU; the whole triangle (no -c / -C).  Not in the reference.
 bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
-	using clock = std::chrono::steady_clock;
 	settings = s;
 	mImpl->n_pairs = mImpl->n_records = 0;
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
-	if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << "The matrix holds every record: a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
-	if (settings.n_chunks != 1) { std::cerr << stamp("ERROR") << "Cannot fill a part of the pair space: the matrix needs every pair (no -c / -C)..." << std::endl; return false; }
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("The matrix holds every record", "Cannot fill a part of the pair space: the matrix needs every pair")) return false;
 	if (ms.stat != TWK_HIP_STAT_R && ms.stat != TWK_HIP_STAT_R2 && ms.stat != TWK_HIP_STAT_D && ms.stat != TWK_HIP_STAT_DPRIME) {
 		std::cerr << stamp("ERROR") << "Unknown statistic: one of r, r2, D, Dprime..." << std::endl; return false;
 	}
 	if (settings.out.empty() || settings.out == "-") { std::cerr << stamp("ERROR") << "No output prefix provided: the matrix and its variant list are files..." << std::endl; return false; }
-	Selection S;
-	bool nothing_to_do = false;
-	if (!select_blocks(settings, S, &nothing_to_do)) return false;
-	if (nothing_to_do) return true;
-	const uint32_t M = S.M;
-	DeviceCtxs dc;
-	if (!create_devices(dc, 1, mImpl->engine_options)) return false;
-	twk_hip_ctx* ctx = dc.ctx[0];
-	const auto t_load = clock::now();
-	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
-	std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
-	if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, mImpl->rid, mImpl->pos)) return false;
-	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
-	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
-
-	const int mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
-	const twk_hip_filters f{settings.minR2, settings.maxR2, settings.minDprime, settings.maxDprime, settings.minP};
-	const int options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const uint32_t M = cmd.M;
 	std::vector<float> m((size_t)M * M);
 	uint64_t np = 0, n_recs = 0;
-	const auto t0 = clock::now();
-	const int rc = twk_hip_ld_matrix(ctx, mode, &f, 0, M, 0, options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np);
-	if (!hip_ok(ctx, rc, "twk_hip_ld_matrix")) return false;
+	const auto t0 = ReduceCommand::clock::now();
+	const int rc = twk_hip_ld_matrix(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_matrix")) return false;
 	mImpl->n_pairs = np; mImpl->n_records = n_recs;
-	const double sec = std::chrono::duration<double>(clock::now() - t0).count();
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
 
 	const std::string path = settings.out + (ms.text ? ".ld" : ".npy");
 	std::cerr << stamp("LOG", "WRITER") << "Opening " << path << "..." << std::endl;
@@ -1286,7 +1254,7 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 				text += num;
 			}
 			text += '\n';
-			if (text.size() > (1u << 20)) { file << text; text.clear(); }
+			cmd.spill(file, text);
 		}
 		file << text;
 	}
@@ -1298,25 +1266,17 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 	std::cerr << stamp("LOG", "WRITER") << "Opening " << vpath << "..." << std::endl;
 	std::ofstream vfile(vpath, std::ios::out | std::ios::trunc);
 	if (!vfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << vpath << "..." << std::endl; return false; }
-	{
-		std::string text;
-		char line[64];
-		for (uint32_t v = 0; v < M; ++v) {
-			const uint32_t rid = mImpl->rid[v];
-			// (contig and position as `ldscore` prints them: the contig's name, the 1-based position)
-			if (rid < S.reader.hdr.contigs.size()) text += S.reader.hdr.contigs[rid].name; else text += '.';
-			snprintf(line, sizeof(line), "\t%u\n", mImpl->pos[v] + 1);
-			text += line;
-			if (text.size() > (1u << 20)) { vfile << text; text.clear(); }
-		}
-		vfile << text;
+	std::string text;
+	for (uint32_t v = 0; v < M; ++v) {
+		cmd.place(text, v);
+		text += '\n';
+		cmd.spill(vfile, text);
 	}
-	vfile.flush();
-	if (!vfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the variant list..." << std::endl; return false; }
+	if (!cmd.finish(vfile, text, "the variant list")) return false;
 	static const char* const stat_names[] = {"r", "r2", "D", "Dprime"};
 	std::cerr << stamp("LOG") << "Matrix of " << stat_names[ms.stat] << ": " << pretty(M) << " x " << pretty(M) << ", " << pretty(n_recs) << " pairs with a value among "
 	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
-	std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
+	cmd.all_done();
 	return true;
 }
 
