@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -93,6 +93,12 @@ matrix-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/matrix_index_check.cpp -o build/matrix_index_check
 	./build/matrix_index_check
+
+# LD decay's bin index, quantisation and host conversion (csrc/hip/ld_decay_bin.h) against a naive restatement (csrc/tools/decay_bin_check.cpp)
+decay-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/decay_bin_check.cpp -o build/decay_bin_check
+	./build/decay_bin_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -37,6 +37,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_prune / twk_hip_prune_last - LD pruning - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_clump / twk_hip_clump_last - LD clumping - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_matrix / twk_hip_matrix_last - the dense LD matrix - are two entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_decay - LD decay - is an entry point more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -383,6 +384,34 @@ int twk_hip_ld_matrix(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters
                       uint64_t* n_records, uint64_t* n_pairs);
 /* Of the context's last twk_hip_ld_matrix call: the time of its device-to-host copy in ms and the matrix's bytes (either may be NULL). */
 int twk_hip_matrix_last(const twk_hip_ctx* ctx, double* copy_ms, uint64_t* matrix_bytes);
+
+/* LD decay over the same slice of the pair space as twk_hip_ld_score, with the same arguments: r2 as a function of the distance
+ * between two variants.  A pair COUNTS when twk_hip_ld_region with these arguments would report a record for it, both variants lie on
+ * the same contig and their positions differ; its distance is d = |posA - posB| (on a position-sorted file the reference's rule,
+ * ridA == ridB && Apos < Bpos: two_reader::Decay).  With width = range_bp / n_bins (integer division) its bin is
+ * min(d / width, n_bins - 1): the last bin also collects everything beyond the range, as in the reference.  For every bin
+ *   n[bin]      = the number of counting pairs,
+ *   sum_r2[bin] = the sum of their R2 fields
+ * (the mean is the caller's division) - reduced on the device: the count matrix of a launch goes through the pair rules and the
+ * math of the record path (one code, ld_math.hip.h) and the r2 of a counting pair is added to its bin as the integer
+ * rint(r2 * 2^32) (ld_decay.hip.h, ld_decay_bin.h).  No record is formed, sorted or copied: 24 bytes per bin leave the device.
+ * THE SUMS ARE EXACT IN INTEGERS AND HAVE NO ORDER: sum_r2[bin] is the sum of the pairs' r2, each rounded once to a multiple of
+ * 2^-32 (off by at most 2^-33 a pair), converted to double once; two calls, any tile_variants and any launch order return the same
+ * bits, and no floating-point atomic is used.  filters.minP must be >= 1: Fisher's test is not run.  Always the matrix form of the
+ * contraction (TWK_HIP_OPT_R2_SCREEN is ignored, as for a score).  n / sum_r2: HOST arrays of n_bins entries each, overwritten.  A
+ * shard (part / n_parts) returns partial arrays; the shards' n add up exactly, their sums to within double rounding.
+ * *n_pairs (may be NULL): pairs evaluated.
+ * TWK_HIP_E_INVALID before any launch: minP < 1, n or sum_r2 NULL, n_bins == 0 or n_bins > 4096 (the block's histogram lives in
+ * LDS), range_bp < n_bins (a width of 0), and the region call's own argument errors; TWK_HIP_E_STATE before upload.  A call of more
+ * than 2^32 kernel blocks - at least 2^32 blocks of up to 8192 pairs: beyond the accumulators' proven room - ends with
+ * TWK_HIP_E_INVALID at the launch that would pass it.  twk_hip_timing: the decay kernels count as the math stage (stats_ms,
+ * stats_launches, variant_pairs).  The reference's counterpart bins the records of a sorted .two file on the host. */
+int twk_hip_ld_decay(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                     uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                     uint32_t part, uint32_t n_parts, uint32_t tile_variants,
+                     int32_t window, uint32_t l_window,
+                     uint32_t range_bp, uint32_t n_bins,
+                     uint64_t* n /*[n_bins]*/, double* sum_r2 /*[n_bins]*/, uint64_t* n_pairs);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

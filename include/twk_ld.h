@@ -56,6 +56,12 @@ struct twk_matrix_settings {
 	bool text = false;          // PREFIX.ld (space-separated text, as FINEMAP reads it) instead of PREFIX.npy
 };
 
+// What Decay needs beyond twk_ld_settings.
+struct twk_decay_settings {
+	int64_t range_bp = 10000000; // the distance the bins cover (the reference's default); the last bin also takes everything beyond it
+	int32_t n_bins = 1000;       // the number of bins (the reference's default), at most 4096; range_bp / n_bins bases each
+};
+
 class twk_ld {
 public:
 	twk_ld();
@@ -103,6 +109,14 @@ public:
 	// 9 significant digits), and always PREFIX.variants.tsv: one "contig <TAB> pos" line per row, as Score prints them.
 	// settings.minP must be 1 (the default).  `tomahawk ldmatrix` ends here.
 	bool Matrix(const twk_ld_settings& settings, const twk_matrix_settings& matrix);
+	// LD decay: mean r2 by the distance between two variants (the reference's two_reader::Decay reads a .two file; here no record is
+	// formed).  Loads the .twk exactly as Score does (-I intervals, -w, -p / -u, -c / -C chunks as regions, TWK_REF_COMPAT).  A pair counts
+	// when Compute would write a record for it, both variants lie on one contig and their positions differ; its bin is
+	// min(|posA - posB| / (decay.range_bp / decay.n_bins), decay.n_bins - 1).  Per bin the pairs are counted and their R2 summed on one GPU
+	// (twk_hip_ld_decay: exact integer sums, the same bits from run to run).  Writes the `##` header lines and then the reference's
+	// columns From, To, Mean, Frequency plus Sum (17 significant digits; Mean = Sum / Frequency, 0 for an empty bin), one line per bin,
+	// to settings.out ("-" or empty: stdout).  settings.minP must be 1 (the default).  `tomahawk lddecay` ends here.
+	bool Decay(const twk_ld_settings& settings, const twk_decay_settings& decay);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

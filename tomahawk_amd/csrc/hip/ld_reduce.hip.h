@@ -1,5 +1,5 @@
-// What the four epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
-// ld_matrix.hip.h; launch_reduce in twk_hip.hip).
+// What the five epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
+// ld_matrix.hip.h, ld_decay.hip.h; launch_reduce in twk_hip.hip).
 //
 // THE SHAPE.  A block is 256 lanes = 256 columns of the launch and walks a fixed number of its rows (32; clump 64) in a loop that is not
 // unrolled.  A lane's pair goes through d_pair<SRC_MATRIX> (ld_math.hip.h) with the launch's StatsParams - the pair rules, the regrouped
@@ -7,7 +7,7 @@
 // the two maths are then the callee's and are not held across the row loop (inlined, k_ld_score needs 191 VGPRs: two waves a SIMD).
 // The PARAMETER BLOCK lives in device memory and the kernel takes a pointer to it: as a kernel argument it is held in ~170 scalar
 // registers across the loop and spilled into vector registers (206 VGPRs; the same finding as k_ld_stats_list's).  A block that lies
-// wholly on or below the diagonal of a diagonal launch has no pair.  What a kernel does with `keep` - sum, ballot, store - is its own.
+// wholly on or below the diagonal of a diagonal launch has no pair.  What a kernel does with `keep` - sum, ballot, store, bin - is its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,7 +9,8 @@
 //   prune (ld_prune.hip.h) cells -> keep -> adjacency bitmap, in place of the math stage, and the greedy walk over it (twk_hip_ld_prune)
 //   clump (ld_clump.hip.h) cells -> keep -> the bitmap's bits (u, v) and (v, u), likewise, and the walk over it in P order (twk_hip_ld_clump)
 //   matrix (ld_matrix.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a dense float32 matrix (twk_hip_ld_matrix)
-//   (score, prune, clump and matrix are the four kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
+//   decay (ld_decay.hip.h) cells -> r2 -> exact integer sums per distance bin, in place of the math stage (twk_hip_ld_decay)
+//   (score, prune, clump, matrix and decay are the five kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -41,6 +42,7 @@
 #include "ld_three.hip.h"
 #include "ld_reduce.hip.h"
 #include "ld_score.hip.h"
+#include "ld_decay.hip.h"
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
@@ -112,10 +114,10 @@ constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // until the host had sorted, copied and handed over launch t and come back with launch t + 2 (2,504 x 531,500, all pairs:
 // 39 launches of 13 ms took 1.25 s).  With t + 2 already queued the count kernels run back to back.
 constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
-// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump or _matrix runs: it looks at
-// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the four kernels share).
-enum class Reduce { none, score, prune, clump, matrix };
-constexpr int N_REDUCE = (int)Reduce::matrix + 1;
+// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix or _decay runs: it looks at
+// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the five kernels share).
+enum class Reduce { none, score, prune, clump, matrix, decay };
+constexpr int N_REDUCE = (int)Reduce::decay + 1;
 // The form of a launch, decided once (launch_form) and passed down: which count kernel, which math behind it.
 struct LaunchForm {
 	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
@@ -150,7 +152,7 @@ struct Launch {
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
-union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; };
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -311,6 +313,10 @@ struct twk_hip_ctx {
 	// matrix: one statistic per record stored into the call's dense matrix (ld_matrix.hip.h)
 	MatrixMap matrix_map{};
 	DevBuf<float> d_matrix;                                                      // the n x n matrix (lives for the call)
+	// decay: exact sums of quantised r2 and counts per distance bin (ld_decay.hip.h)
+	DecayMap decay_map{};
+	DevBuf<unsigned long long> d_decay;                                          // [3][n_bins] accumulators: acc_int, acc_frac, acc_n
+	uint64_t decay_blocks = 0;                                                   // blocks launched for the running call: each flushes a bin at most once
 	char err[512] = {0};
 };
 
@@ -351,7 +357,7 @@ void free_problem(twk_hip_ctx* c) {
 	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
 	c->d_score_sum.reset(); c->d_score_n.reset();
 	c->d_counts.reset(); c->d_adj.reset(); c->d_walk.reset(); c->d_prune_keep.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
-	c->d_matrix.reset();
+	c->d_matrix.reset(); c->d_decay.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -815,15 +821,15 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 }
 
 // The end of every reduce launch: the parameter block `a` of pass `which` into the slot's pinned block and from there to the device, on the stream of
-// `kernel`, which then reads it there while it walks the tile in blocks of cols x rows.
+// `kernel`, which then reads it there while it walks the tile in blocks of cols x rows (with lds_bytes of dynamic LDS a block).
 template <class A>
-int run_reduce_kernel(twk_hip_ctx* c, const twk_hip_tile_desc& t, Slot& s, int which, void (*kernel)(const A*), uint32_t cols, uint32_t rows, const A& a) {
+int run_reduce_kernel(twk_hip_ctx* c, const twk_hip_tile_desc& t, Slot& s, int which, void (*kernel)(const A*), uint32_t cols, uint32_t rows, const A& a, size_t lds_bytes = 0) {
 	static_assert(sizeof(A) <= sizeof(ReduceArgs) && alignof(A) <= alignof(ReduceArgs) && std::is_trivially_copyable<A>::value, "a parameter block the slot has room for");
 	const dim3 grid((t.nB + cols - 1) / cols, (t.nA + rows - 1) / rows);
 	if (grid.y > 0xFFFFu) return TWK_HIP_E_INVALID;
 	memcpy(s.h_args + which, &a, sizeof(A));      // (the slot's previous launch has been waited for: its copy is done)
 	HIPCHK(c, hipMemcpyAsync(s.d_args + which, s.h_args + which, sizeof(A), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(kernel, grid, dim3(cols), 0, c->s_compute, reinterpret_cast<const A*>(s.d_args + which));
+	hipLaunchKernelGGL(kernel, grid, dim3(cols), lds_bytes, c->s_compute, reinterpret_cast<const A*>(s.d_args + which));
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -840,6 +846,12 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	case Reduce::prune:  return run_reduce_kernel(c, t, s, which, k_ld_prune_mask, PRUNE_THREADS, PRUNE_ROWS, PruneArgs{p, c->map});
 	case Reduce::clump:  return run_reduce_kernel(c, t, s, which, k_ld_clump_mask, CLUMP_THREADS, CLUMP_ROWS, ClumpArgs{p, c->map});
 	case Reduce::matrix: return run_reduce_kernel(c, t, s, which, k_ld_matrix_fill, MATRIX_THREADS, MATRIX_ROWS, MatrixArgs{p, c->matrix_map});
+	case Reduce::decay: {
+		// a block adds less than 2^32 to a bin's acc_frac, once: 2^32 blocks a call are its room (ld_decay.hip.h)
+		c->decay_blocks += (uint64_t)((t.nB + DECAY_THREADS - 1) / DECAY_THREADS) * ((t.nA + DECAY_ROWS - 1) / DECAY_ROWS);
+		if (c->decay_blocks > 0xFFFFFFFFull) { snprintf(c->err, sizeof(c->err), "LD decay: more than 2^32 blocks in one call; split it into shards"); return TWK_HIP_E_INVALID; }
+		return run_reduce_kernel(c, t, s, which, k_ld_decay, DECAY_THREADS, DECAY_ROWS, DecayArgs{p, c->decay_map}, decay_lds_bytes(c->decay_map.n_bins));
+	}
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -891,7 +903,7 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 }
 
 // The end of every launch, on the compute stream: Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is
-// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune, clump or matrix launch has no survivors, and no
+// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune, clump, matrix or decay launch has no survivors, and no
 // test to run: minP >= 1 drops nothing), for a band launch the sort of its survivors (Launch::presorted), the counters' copy to the host
 // and ev_s1.
 // The band launch's sort is over as many slots as there were candidates (unused slots carry the all-ones key, like records the Fisher
@@ -924,7 +936,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
 	const LaunchForm form = launch_form(c, pl, f);
 	const Geometry g = tile_geometry(pl.Pmax, t);
-	if (form.reduces()) capacity = 1;              // a score, prune, clump or matrix launch keeps no survivors (and is never a band launch: always the matrix form)
+	if (form.reduces()) capacity = 1;              // a score, prune, clump, matrix or decay launch keeps no survivors (and is never a band launch: always the matrix form)
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
@@ -2217,7 +2229,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = c->reduce == Reduce::none;      // a score, a prune, a clump or a matrix looks at every pair: no screen in front of the count matrix
+	c->fused_ok = c->three_ok = c->reduce == Reduce::none;      // a score, a prune, a clump, a matrix or a decay looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2293,7 +2305,7 @@ int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 
 extern "C++" {      // (member templates)
 namespace {
-// One call of twk_hip_ld_score, _prune, _clump or _matrix: the region call's planner and launch pipeline with the kind's epilogue in place of
+// One call of twk_hip_ld_score, _prune, _clump, _matrix or _decay: the region call's planner and launch pipeline with the kind's epilogue in place of
 // math, Fisher, sort and delivery (launch_reduce).  Constructed at the top of the entry point, which returns `bad` if the shared checks found
 // something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the buffer
 // that lived for the call released, the graveyard flushed.
@@ -2313,7 +2325,7 @@ struct ReduceCall {
 	}
 	~ReduceCall() {
 		if (bad) return;
-		c->reduce = Reduce::none; c->map = PruneMap{}; c->matrix_map = MatrixMap{};
+		c->reduce = Reduce::none; c->map = PruneMap{}; c->matrix_map = MatrixMap{}; c->decay_map = DecayMap{}; c->decay_blocks = 0;
 		(void)hipDeviceSynchronize();
 		c->d_adj.reset(); c->d_matrix.reset();      // what lived for the call (hold)
 		flush_graveyard(c);                 // buffers outgrown during the call: nothing is in flight any more
@@ -2518,6 +2530,32 @@ int twk_hip_ld_matrix(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 }
 
 int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) { return last_of(c, Reduce::matrix, copy_ms, matrix_bytes); }
+
+// LD decay: the bins' integer accumulators are zeroed in front of the launches and converted behind the last of them.
+int twk_hip_ld_decay(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                     uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                     uint32_t range_bp, uint32_t n_bins, uint64_t* n, double* sum_r2, uint64_t* n_pairs) {
+	const bool bins_ok = n_bins >= 1 && n_bins <= DECAY_MAX_BINS && range_bp >= n_bins;      // (range_bp < n_bins: a width of 0)
+	ReduceCall call(c, Reduce::decay, f, n && sum_r2 && bins_ok, mode, a0, nA);
+	if (call.bad) return call.bad;
+	const size_t B = n_bins;
+	HIPCHK(c, c->d_decay.reserve(3 * B, 3 * B, nullptr));
+	HIPCHK(c, hipMemsetAsync(c->d_decay, 0, 3 * B * sizeof(unsigned long long), c->s_compute));
+	c->decay_map = DecayMap{c->d_decay, c->d_decay + B, c->d_decay + 2 * B, dk_width(range_bp, n_bins), n_bins};
+	c->decay_blocks = 0;
+	call.arm(3 * B * sizeof(unsigned long long));
+	const int rc = call.dispatch(RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	if (rc) return rc;
+	std::vector<unsigned long long> acc(3 * B);
+	hipError_t e = hipMemcpyAsync(acc.data(), c->d_decay, 3 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+	if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decay arrays: %s", hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
+	for (size_t b = 0; b < B; ++b) {
+		sum_r2[b] = dk_sum_to_double(acc[b], acc[B + b]);      // (exact in 128 bits, one conversion: ld_decay_bin.h)
+		n[b] = acc[2 * B + b];
+	}
+	return TWK_HIP_OK;
+}
 
 int twk_hip_shard_rows(uint32_t n_rows, uint32_t n_cols, int32_t triangle, uint32_t part, uint32_t n_parts,
                        uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs) {

@@ -164,11 +164,12 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-// The options `ldscore`, `prune`, `clump` and `ldmatrix` share (-P is accepted only as 1 by all; `prune`, `clump` and `ldmatrix` have no
-// -c / -C; `clump` adds its association file and thresholds, `ldmatrix` its statistic, fill and text switch).  -> 0, or 1 after an error message.
-enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP, REDUCE_MATRIX };
+// The options `ldscore`, `prune`, `clump`, `ldmatrix` and `lddecay` share (-P is accepted only as 1 by all; `prune`, `clump` and `ldmatrix` have no
+// -c / -C; `clump` adds its association file and thresholds, `ldmatrix` its statistic, fill and text switch, `lddecay` its range and number of
+// bins).  -> 0, or 1 after an error message.
+enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP, REDUCE_MATRIX, REDUCE_DECAY };
 static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options,
-                          tomahawk::twk_clump_settings* clump = nullptr, tomahawk::twk_matrix_settings* matrix = nullptr) {
+                          tomahawk::twk_clump_settings* clump = nullptr, tomahawk::twk_matrix_settings* matrix = nullptr, tomahawk::twk_decay_settings* decay = nullptr) {
 	const bool prune = cmd == REDUCE_PRUNE;
 	static struct option long_options[] = {
 		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
@@ -177,15 +178,31 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 		{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
 		{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
 		{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
+		{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
 		{0, 0, 0, 0}};
+	bool range_given = false;
 	int c, option_index = 0;
-	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : matrix ? "i:o:t:puP:r:w:I:c:C:s:f:T?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
+	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : matrix ? "i:o:t:puP:r:w:I:c:C:s:f:T?" : decay ? "i:o:t:puP:r:w:I:c:C:d:b:?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
 		if (prune && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
 		if (cmd == REDUCE_CLUMP && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
 		if (cmd == REDUCE_MATRIX && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot fill a part of the pair space (-c / -C): the matrix needs every pair" << std::endl; return 1; }
 		if (!clump && (c == 'a' || c == '1' || c == '2')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
 		if (!matrix && (c == 's' || c == 'f' || c == 'T')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
+		if (!decay && (c == 'd' || c == 'b')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
 		switch (c) {
+		case 'd': case 'b': {
+			const std::string a(optarg);
+			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << stamp("ERROR") << "The " << (c == 'd' ? "range (-d)" : "number of bins (-b)") << " must be a non-negative integer: " << a << std::endl; return 1; }
+			const double v = atof(optarg);
+			if (c == 'd') {
+				if (!(v >= 1 && v <= 4294967295.0)) { std::cerr << stamp("ERROR") << "The range (-d) must be between 1 and 4294967295 bases" << std::endl; return 1; }
+				decay->range_bp = (int64_t)v; range_given = true;
+			} else {
+				if (!(v >= 1 && v <= 4096)) { std::cerr << stamp("ERROR") << "The number of bins (-b) must be between 1 and 4096" << std::endl; return 1; }
+				decay->n_bins = (int32_t)v;
+			}
+			break;
+		}
 		case 's': {
 			const std::string a(optarg);
 			if (a == "r") matrix->stat = TWK_HIP_STAT_R;
@@ -237,6 +254,7 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 			settings.minP = atof(optarg);
 			if (!(settings.minP >= 1)) {
 				std::cerr << stamp("ERROR") << (cmd == REDUCE_MATRIX ? "Cannot fill a matrix with a cutoff P-value below 1: the matrix holds every record and Fisher's exact test is not run" :
+				                                cmd == REDUCE_DECAY ? "Cannot bin with a cutoff P-value below 1: a decay curve averages over every record and Fisher's exact test is not run" :
 				                                cmd == REDUCE_CLUMP ? "Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run" :
 				                                prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
 				                                      : "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run") << std::endl;
@@ -267,6 +285,8 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
 	if (clump && clump->assoc.empty()) { std::cerr << stamp("ERROR") << "No association file specified (-a)..." << std::endl; return 1; }
 	if (matrix && (settings.out.empty() || settings.out == "-")) { std::cerr << stamp("ERROR") << "No output prefix specified (-o)..." << std::endl; return 1; }
+	if (decay && !range_given && settings.window) decay->range_bp = settings.l_window;      // (only -w given: no pair lies further apart)
+	if (decay && decay->range_bp < decay->n_bins) { std::cerr << stamp("ERROR") << "The range (-d, or -w without -d: " << decay->range_bp << ") cannot be smaller than the number of bins (-b: " << decay->n_bins << "): a bin would be 0 bases wide" << std::endl; return 1; }
 	if (clump && clump->p1 > clump->p2) { std::cerr << stamp("ERROR") << "The index threshold (-1) cannot be above the secondary threshold (-2)" << std::endl; return 1; }
 	return 0;
 }
@@ -418,6 +438,52 @@ static int ldmatrix(int argc, char** argv) {
 	tomahawk::twk_ld ld;
 	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
 	return ld.Matrix(settings, ms) ? 0 : 1;
+}
+
+// `tomahawk lddecay`: mean r2 by the distance between two variants over the records `calc` would write, binned and summed on the GPU.  (The
+// reference's `decay` reads a .two file, and its range is -w; here -w keeps calc's meaning, the window of the computation.)
+static void lddecay_usage() {
+	program_message();
+	std::cerr <<
+	"About:  LD decay: R-squared as a function of the distance between two variants.  Every pair `calc`\n"
+	"        would report under the same options, with both variants on one contig at different\n"
+	"        positions, falls into the bin of its distance; per bin the pairs are counted and their\n"
+	"        R-squared summed exactly on the GPU (no .two is written).  The last bin also takes every\n"
+	"        pair beyond the range.\n\n"
+	"Usage:  tomahawk lddecay [options] -i <in.twk> [-o <out.tsv>]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o FILE   output text file (- for stdout; default: -)\n"
+	"  -d INT    range in bases the bins cover (default: 10000000, or the -w window when only -w is given)\n"
+	"  -b INT    number of bins, 1 to 4096 (default: 1000); a bin is -d / -b bases wide\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -c INT    number of subproblems to split compute into (must be in (c!2 + c))\n"
+	"  -C INT    chosen part to compute (0 < -C < -c)\n"
+	"  -w INT    sliding window width in bases: pairs further apart are not computed\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value (default: 0)\n"
+	"  -P FLOAT  accepted only as 1: a decay curve averages over every record, Fisher's test is not run\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"Output: '#' header lines, then per bin: From <TAB> To <TAB> Mean <TAB> Frequency <TAB> Sum\n"
+	"        (Mean = Sum / Frequency, 0 for an empty bin)\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int lddecay(int argc, char** argv) {
+	if (argc < 3) { lddecay_usage(); return 1; }
+	tomahawk::twk_ld_settings settings;
+	settings.minR2 = 0;
+	settings.out = "-";
+	tomahawk::twk_decay_settings ds;
+	std::vector<std::pair<std::string, long long>> engine_options;
+	if (reduce_options(argc, argv, REDUCE_DECAY, settings, engine_options, nullptr, nullptr, &ds)) return 1;
+	program_message();
+	std::cerr << stamp("LOG") << "Calling lddecay..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Decay(settings, ds) ? 0 : 1;
 }
 
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
@@ -714,6 +780,7 @@ static int run_main(int argc, char** argv) {
 		             "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n"
 		             "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n"
 		             "  ldmatrix dense LD matrix of a region (signed r, r2, D or D'), filled on the GPU\n"
+		             "  lddecay  LD decay: R-squared by the distance between two variants, binned and summed on the GPU\n"
 		             "  sort     sort a .two file\n"
 		             "  view     convert, filter and slice .two files\n"
 		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
@@ -731,6 +798,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "prune") == 0) return prune(argc, argv);
 	if (strcmp(argv[1], "clump") == 0) return clump(argc, argv);
 	if (strcmp(argv[1], "ldmatrix") == 0) return ldmatrix(argc, argv);
+	if (strcmp(argv[1], "lddecay") == 0) return lddecay(argc, argv);
 	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
 	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
 	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
@@ -739,7 +807,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `ldmatrix`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance without a .two)" << std::endl;
 	return 1;
 }
 

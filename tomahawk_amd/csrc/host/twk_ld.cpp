@@ -941,7 +941,7 @@ bool twk_ld::Compute() {
 	return true;
 }
 
-// What `ldscore`, `prune`, `clump` and `ldmatrix` share around their one engine call: the checks common to all, the input loaded exactly as
+// What `ldscore`, `prune`, `clump`, `ldmatrix` and `lddecay` share around their one engine call: the checks common to all, the input loaded exactly as
 // Compute loads it onto one GPU, the text output with its `##` header, the `contig \t pos` that begins a variant's line, the closing lines.
 namespace {
 struct ReduceCommand {
@@ -1059,6 +1059,52 @@ bool twk_ld::Score(const twk_ld_settings& s) {
 	}
 	if (!cmd.finish(*os, text, "the scores")) return false;
 	std::cerr << stamp("LOG") << "Scored " << pretty(M) << " variants over " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+	cmd.all_done();
+	return true;
+}
+
+// `tomahawk lddecay`: r2 by the distance between two variants, over the records Compute would write (twk_hip_ld_decay: binned and summed
+// exactly on the GPU, no record is formed), as text: one line per bin.  The input is loaded exactly as Compute loads it; one GPU.  The
+// reference's two_reader::Decay bins the records of a .two file; its columns are kept and `Sum` is added.
+bool twk_ld::Decay(const twk_ld_settings& s, const twk_decay_settings& ds) {
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("A decay curve averages over every record", nullptr)) return false;
+	if (ds.n_bins < 1 || ds.n_bins > 4096) { std::cerr << stamp("ERROR") << "The number of bins must be between 1 and 4096..." << std::endl; return false; }
+	if (ds.range_bp < ds.n_bins || ds.range_bp > 0xFFFFFFFFll) { std::cerr << stamp("ERROR") << "The range in bases must be at least the number of bins and below 2^32..." << std::endl; return false; }
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const Selection& S = cmd.S;
+	const uint32_t M = cmd.M, B = (uint32_t)ds.n_bins, range = (uint32_t)ds.range_bp;
+	std::vector<uint64_t> n(B, 0);
+	std::vector<double> sum_r2(B, 0.0);
+	uint64_t np = 0;
+	const auto t0 = ReduceCommand::clock::now();
+	int rc = TWK_HIP_OK;
+	if (S.bal.diag) { if (M > 1) rc = twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, M, 1, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np); }
+	else if (S.nL && S.nR) rc = twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_decay")) return false;
+	mImpl->n_pairs = np;
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+
+	std::ostream* const os = cmd.open_text();
+	if (!os) return false;
+	cmd.header(*os, "lddecay");
+	const uint32_t width = range / B;
+	uint64_t counted = 0;
+	for (uint32_t b = 0; b < B; ++b) counted += n[b];
+	*os << "##range=" << range << ",bins=" << B << ",width=" << width << ",pairs=" << counted << "\n"
+	    << "From\tTo\tMean\tFrequency\tSum\n";
+	std::string text;
+	char line[256];
+	for (uint32_t b = 0; b < B; ++b) {
+		snprintf(line, sizeof(line), "%llu\t%llu\t%.17g\t%llu\t%.17g\n", (unsigned long long)b * width, (unsigned long long)(b + 1) * width,
+		         n[b] ? sum_r2[b] / (double)n[b] : 0.0, (unsigned long long)n[b], sum_r2[b]);
+		text += line;
+		cmd.spill(*os, text);
+	}
+	if (!cmd.finish(*os, text, "the decay table")) return false;
+	std::cerr << stamp("LOG") << "Binned " << pretty(counted) << " records of " << pretty(np) << " variant comparisons into " << pretty(B) << " bins. " << elapsed_string(sec) << std::endl;
 	cmd.all_done();
 	return true;
 }

@@ -190,6 +190,9 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_score.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
                                      C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_decay.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, p, p,
+                                     C.POINTER(C.c_uint64)]
     lib.twk_hip_ld_prune.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_prune_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
@@ -483,6 +486,27 @@ class HipLd:
         self._check(self._lib.twk_hip_ld_score(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts,
                                                tile_variants, int(window), l_window, n.ctypes.data, s.ctypes.data,
                                                C.byref(npairs)), "twk_hip_ld_score")
+        return n, s, npairs.value
+
+    def ld_decay(self, mode: int, filters: Filters, range_bp: int = 10_000_000, n_bins: int = 1000, a0: int = 0, nA: int | None = None,
+                 b0: int = 0, nB: int | None = None, triangle: bool = True, part: int = 0, n_parts: int = 1, tile_variants: int = 0,
+                 window: int = 0, l_window: int = 0):
+        """LD decay (twk_hip_ld_decay): r2 by distance.  A pair counts when ld_region would report a record for it, both variants
+        lie on one contig and their positions differ; its bin is min(|posA - posB| // (range_bp // n_bins), n_bins - 1).  Per bin the
+        number of counting pairs and the sum of their R2, each rounded once to a multiple of 2^-32 and summed exactly in integers on
+        the device: the same bits for any tiling, order or repeat.  No record is formed.  filters.minP must be >= 1; n_bins <= 4096;
+        range_bp >= n_bins.  A shard returns partial arrays.  -> (n uint64[n_bins], sum_r2 float64[n_bins], n_pairs)."""
+        M = self.n_variants
+        nA = M - a0 if nA is None else nA
+        nB = M - b0 if nB is None else nB
+        size = max(int(n_bins), 1) if 0 <= int(n_bins) <= 4096 else 1          # (a refused n_bins is the engine's to refuse)
+        n = np.zeros(size, dtype=np.uint64)
+        s = np.zeros(size, dtype=np.float64)
+        npairs = C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_decay(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts,
+                                               tile_variants, int(window), l_window, int(range_bp), int(n_bins), n.ctypes.data,
+                                               s.ctypes.data, C.byref(npairs)), "twk_hip_ld_decay")
         return n, s, npairs.value
 
     def ld_prune(self, mode: int, filters: Filters, a0: int = 0, n: int | None = None, tile_variants: int = 0, window: int = 0,
