@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -99,6 +99,13 @@ decay-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/decay_bin_check.cpp -o build/decay_bin_check
 	./build/decay_bin_check
+
+# LD aggregate's packing, quantisation, split and host conversion (csrc/hip/ld_aggregate_bin.h) and ldaggregate's landscape
+# (csrc/host/twk_aggregate_landscape.h) against a naive restatement (csrc/tools/aggregate_bin_check.cpp)
+aggregate-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/aggregate_bin_check.cpp -o build/aggregate_bin_check
+	./build/aggregate_bin_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -38,6 +38,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_clump / twk_hip_clump_last - LD clumping - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_matrix / twk_hip_matrix_last - the dense LD matrix - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_decay - LD decay - is an entry point more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_aggregate - the LD aggregate - is an entry point more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -412,6 +413,38 @@ int twk_hip_ld_decay(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
                      int32_t window, uint32_t l_window,
                      uint32_t range_bp, uint32_t n_bins,
                      uint64_t* n /*[n_bins]*/, double* sum_r2 /*[n_bins]*/, uint64_t* n_pairs);
+
+/* LD aggregate over the same slice of the pair space as twk_hip_ld_score, with the same arguments: the pairwise LD of a region
+ * rasterised into x_bins * y_bins cells (the reference's two_reader::Aggregate reads the records of a .two file; here no record is
+ * formed).  stat: TWK_HIP_STAT_R (signed: copysign(R, D), as in twk_hip_ld_matrix), _R2, _D or _DPRIME - the pair's value v.
+ * bin_x / bin_y: HOST arrays of n_variants uint16_t, indexed by variant as uploaded: the variant's bin on that axis, 0xFFFF for a
+ * variant that is off the landscape on it.  The engine never sees positions: what a bin is - a stretch of bases, of genetic distance,
+ * an allele-frequency class - is the caller's.  For every pair (A, B) for which twk_hip_ld_region with these arguments would report a
+ * record, v is added to cell (bin_x[A], bin_y[B]) and to cell (bin_x[B], bin_y[A]), each orientation if both of its bins are valid
+ * (the reference's writer emits every record in both orientations and its aggregator indexes mat[x(A)][y(B)]; when both land in one
+ * cell its n grows by 2; no same-contig and no distinct-position rule, as in the reference).  HOST arrays of x_bins * y_bins entries
+ * each, cell (x, y) at x * y_bins + y, overwritten:
+ *   n       contributions to the cell
+ *   sum     the sum of q / 2^32 over the cell, q = rint(v * 2^32) as a signed 64-bit integer
+ *   sum_sq  the same with q2 = rint((v * v) * 2^32) - the square is one double multiplication
+ *   min/max the smallest and the largest q / 2^32; both 0.0 where n == 0
+ * THE SUMS ARE EXACT IN INTEGERS AND HAVE NO ORDER (ld_aggregate.hip.h, ld_aggregate_bin.h): summed in 64-bit integer atomics,
+ * converted once from 128 bits; all five arrays are the same bits for any tile_variants, any launch order and any repeat, and no
+ * floating-point atomic is used.  A shard (part / n_parts) returns partial arrays: n and the sums add, min / max combine by min /
+ * max over the cells with n != 0.  filters.minP must be >= 1: Fisher's test is not run.  Always the matrix form of the contraction
+ * (TWK_HIP_OPT_R2_SCREEN is ignored, as for a score).  *n_pairs (may be NULL): pairs evaluated.  64 bytes of device memory a cell
+ * for the length of the call.
+ * TWK_HIP_E_INVALID before any launch: minP < 1, a NULL array, x_bins or y_bins 0 or above 4096, a bin entry >= its axis' count
+ * that is not 0xFFFF, an unknown stat, and the region call's own argument errors; TWK_HIP_E_STATE before upload.  A call whose
+ * launches can evaluate more than 2^42 pairs - beyond the accumulators' proven room - ends with TWK_HIP_E_INVALID at the launch that
+ * would pass it.  twk_hip_timing: the aggregate kernels count as the math stage (stats_ms, stats_launches, variant_pairs). */
+int twk_hip_ld_aggregate(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                         uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                         uint32_t part, uint32_t n_parts, uint32_t tile_variants,
+                         int32_t window, uint32_t l_window,
+                         int32_t stat, const uint16_t* bin_x /*[n_variants]*/, const uint16_t* bin_y /*[n_variants]*/,
+                         uint32_t x_bins, uint32_t y_bins,
+                         uint64_t* n, double* sum, double* sum_sq, double* min, double* max /*[x_bins * y_bins] each*/, uint64_t* n_pairs);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

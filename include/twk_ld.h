@@ -62,6 +62,14 @@ struct twk_decay_settings {
 	int32_t n_bins = 1000;       // the number of bins (the reference's default), at most 4096; range_bp / n_bins bases each
 };
 
+// What Aggregate needs beyond twk_ld_settings.
+struct twk_aggregate_settings {
+	int32_t x_bins = 1000, y_bins = 1000;  // bins per axis (the reference's defaults), 1 to 4096 each
+	int32_t stat = 1;                      // TWK_HIP_STAT_R2; or _R (signed), _D, _DPRIME
+	int32_t reduce = 0;                    // what is printed per cell: 0 mean, 1 count, 2 min, 3 max, 4 sd, 5 total
+	int64_t min_count = 5;                 // a cell with fewer contributions prints 0 (the reference's -c)
+};
+
 class twk_ld {
 public:
 	twk_ld();
@@ -117,6 +125,15 @@ public:
 	// columns From, To, Mean, Frequency plus Sum (17 significant digits; Mean = Sum / Frequency, 0 for an empty bin), one line per bin,
 	// to settings.out ("-" or empty: stdout).  settings.minP must be 1 (the default).  `tomahawk lddecay` ends here.
 	bool Decay(const twk_ld_settings& settings, const twk_decay_settings& decay);
+	// LD aggregate: the pairwise LD of the selection rasterised into x_bins * y_bins cells (the reference's two_reader::Aggregate reads a
+	// .two file; here no record is formed).  Loads the .twk exactly as Score does (-I intervals, -w, -p / -u, -c / -C chunks as regions,
+	// TWK_REF_COMPAT).  The landscape is the reference's rule applied to the loaded variants (csrc/host/twk_aggregate_landscape.h): one
+	// contig - the data's range; several - every contig present at its header length; ceil((float)range / bins) bases a bin.  Every
+	// record Compute would write adds its statistic to cell (x(A), y(B)) and to cell (x(B), y(A)) on one GPU (twk_hip_ld_aggregate: exact
+	// integer sums, the same bits from run to run).  Writes `#` comment lines (x, y, bases per bin, range, every contig's offset) and
+	// then x_bins rows of y_bins tab-separated values at 17 significant digits - the reduction of the cell, 0 below min_count - to
+	// settings.out ("-" or empty: stdout).  settings.minP must be 1 (the default).  `tomahawk ldaggregate` ends here.
+	bool Aggregate(const twk_ld_settings& settings, const twk_aggregate_settings& aggregate);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

@@ -1,5 +1,5 @@
-// What the five epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
-// ld_matrix.hip.h, ld_decay.hip.h; launch_reduce in twk_hip.hip).
+// What the six epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
+// ld_matrix.hip.h, ld_decay.hip.h, ld_aggregate.hip.h; launch_reduce in twk_hip.hip).
 //
 // THE SHAPE.  A block is 256 lanes = 256 columns of the launch and walks a fixed number of its rows (32; clump 64) in a loop that is not
 // unrolled.  A lane's pair goes through d_pair<SRC_MATRIX> (ld_math.hip.h) with the launch's StatsParams - the pair rules, the regrouped

@@ -10,7 +10,8 @@
 //   clump (ld_clump.hip.h) cells -> keep -> the bitmap's bits (u, v) and (v, u), likewise, and the walk over it in P order (twk_hip_ld_clump)
 //   matrix (ld_matrix.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a dense float32 matrix (twk_hip_ld_matrix)
 //   decay (ld_decay.hip.h) cells -> r2 -> exact integer sums per distance bin, in place of the math stage (twk_hip_ld_decay)
-//   (score, prune, clump, matrix and decay are the five kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
+//   aggregate (ld_aggregate.hip.h) cells -> one statistic -> exact integer sums, counts and extremes per cell of an x-by-y landscape, likewise (twk_hip_ld_aggregate)
+//   (score, prune, clump, matrix, decay and aggregate are the six kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -43,6 +44,7 @@
 #include "ld_reduce.hip.h"
 #include "ld_score.hip.h"
 #include "ld_decay.hip.h"
+#include "ld_aggregate.hip.h"
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
@@ -114,10 +116,10 @@ constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // until the host had sorted, copied and handed over launch t and come back with launch t + 2 (2,504 x 531,500, all pairs:
 // 39 launches of 13 ms took 1.25 s).  With t + 2 already queued the count kernels run back to back.
 constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
-// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix or _decay runs: it looks at
-// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the five kernels share).
-enum class Reduce { none, score, prune, clump, matrix, decay };
-constexpr int N_REDUCE = (int)Reduce::decay + 1;
+// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay or _aggregate runs: it looks at
+// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the six kernels share).
+enum class Reduce { none, score, prune, clump, matrix, decay, aggregate };
+constexpr int N_REDUCE = (int)Reduce::aggregate + 1;
 // The form of a launch, decided once (launch_form) and passed down: which count kernel, which math behind it.
 struct LaunchForm {
 	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
@@ -152,7 +154,7 @@ struct Launch {
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
-union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; };
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -298,7 +300,7 @@ struct twk_hip_ctx {
 	DevBuf<uint8_t> d_rle, d_rle_desc;
 	DevBuf<int> d_status;
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
-	// twk_hip_ld_score, _prune, _clump, _matrix: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
+	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	Reduce reduce = Reduce::none;                                                // which way, for the length of the call (ReduceCall)
 	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
 	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last)
@@ -317,6 +319,11 @@ struct twk_hip_ctx {
 	DecayMap decay_map{};
 	DevBuf<unsigned long long> d_decay;                                          // [3][n_bins] accumulators: acc_int, acc_frac, acc_n
 	uint64_t decay_blocks = 0;                                                   // blocks launched for the running call: each flushes a bin at most once
+	// aggregate: exact sums, counts and extremes per cell of an x-by-y landscape (ld_aggregate.hip.h)
+	AggMap agg_map{};
+	DevBuf<uint32_t> d_agg_key;                                                  // [M] the two bins of every variant, packed
+	DevBuf<unsigned long long> d_agg;                                            // [x_bins * y_bins][AGG_CELL_WORDS] accumulators (lives for the call)
+	uint64_t agg_slots = 0;                                                      // pairs the running call's launches can evaluate: two contributions each
 	char err[512] = {0};
 };
 
@@ -357,7 +364,7 @@ void free_problem(twk_hip_ctx* c) {
 	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
 	c->d_score_sum.reset(); c->d_score_n.reset();
 	c->d_counts.reset(); c->d_adj.reset(); c->d_walk.reset(); c->d_prune_keep.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
-	c->d_matrix.reset(); c->d_decay.reset();
+	c->d_matrix.reset(); c->d_decay.reset(); c->d_agg_key.reset(); c->d_agg.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -852,6 +859,13 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 		if (c->decay_blocks > 0xFFFFFFFFull) { snprintf(c->err, sizeof(c->err), "LD decay: more than 2^32 blocks in one call; split it into shards"); return TWK_HIP_E_INVALID; }
 		return run_reduce_kernel(c, t, s, which, k_ld_decay, DECAY_THREADS, DECAY_ROWS, DecayArgs{p, c->decay_map}, decay_lds_bytes(c->decay_map.n_bins));
 	}
+	case Reduce::aggregate: {
+		// two contributions a pair and 2^43 of them to one cell are the accumulators' proven room (ld_aggregate.hip.h)
+		const bool square_diag = t.diag && t.rowA0 == t.rowB0 && t.nA == t.nB;
+		c->agg_slots += square_diag ? (uint64_t)t.nA * (t.nA - 1) / 2 : (uint64_t)t.nA * t.nB;
+		if (c->agg_slots > 1ull << 42) { snprintf(c->err, sizeof(c->err), "LD aggregate: more than 2^42 pairs in one call; split it into shards"); return TWK_HIP_E_INVALID; }
+		return run_reduce_kernel(c, t, s, which, k_ld_aggregate, AGG_THREADS, AGG_ROWS, AggArgs{p, c->agg_map});
+	}
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -903,7 +917,7 @@ int launch_list_math(twk_hip_ctx* c, Slot& s, const StatsParams* d_stats) {
 }
 
 // The end of every launch, on the compute stream: Fisher's exact test on the compacted survivors (the slot's count / candidate buffer is
-// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune, clump, matrix or decay launch has no survivors, and no
+// free by now - the math kernels in front are done with it - and holds the walk-length order; a score, prune, clump, matrix, decay or aggregate launch has no survivors, and no
 // test to run: minP >= 1 drops nothing), for a band launch the sort of its survivors (Launch::presorted), the counters' copy to the host
 // and ev_s1.
 // The band launch's sort is over as many slots as there were candidates (unused slots carry the all-ones key, like records the Fisher
@@ -936,7 +950,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
 	const LaunchForm form = launch_form(c, pl, f);
 	const Geometry g = tile_geometry(pl.Pmax, t);
-	if (form.reduces()) capacity = 1;              // a score, prune, clump, matrix or decay launch keeps no survivors (and is never a band launch: always the matrix form)
+	if (form.reduces()) capacity = 1;              // a score, prune, clump, matrix, decay or aggregate launch keeps no survivors (and is never a band launch: always the matrix form)
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
@@ -2229,7 +2243,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = c->reduce == Reduce::none;      // a score, a prune, a clump, a matrix or a decay looks at every pair: no screen in front of the count matrix
+	c->fused_ok = c->three_ok = c->reduce == Reduce::none;      // a score, a prune, a clump, a matrix, a decay or an aggregate looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2305,7 +2319,7 @@ int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 
 extern "C++" {      // (member templates)
 namespace {
-// One call of twk_hip_ld_score, _prune, _clump, _matrix or _decay: the region call's planner and launch pipeline with the kind's epilogue in place of
+// One call of twk_hip_ld_score, _prune, _clump, _matrix, _decay or _aggregate: the region call's planner and launch pipeline with the kind's epilogue in place of
 // math, Fisher, sort and delivery (launch_reduce).  Constructed at the top of the entry point, which returns `bad` if the shared checks found
 // something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the buffer
 // that lived for the call released, the graveyard flushed.
@@ -2326,8 +2340,9 @@ struct ReduceCall {
 	~ReduceCall() {
 		if (bad) return;
 		c->reduce = Reduce::none; c->map = PruneMap{}; c->matrix_map = MatrixMap{}; c->decay_map = DecayMap{}; c->decay_blocks = 0;
+		c->agg_map = AggMap{}; c->agg_slots = 0;
 		(void)hipDeviceSynchronize();
-		c->d_adj.reset(); c->d_matrix.reset();      // what lived for the call (hold)
+		c->d_adj.reset(); c->d_matrix.reset(); c->d_agg.reset();      // what lived for the call (hold)
 		flush_graveyard(c);                 // buffers outgrown during the call: nothing is in flight any more
 	}
 	// The buffer that lives as long as the call - gigabytes that a record run behind this call may need, so it goes back when the call ends,
@@ -2553,6 +2568,52 @@ int twk_hip_ld_decay(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	for (size_t b = 0; b < B; ++b) {
 		sum_r2[b] = dk_sum_to_double(acc[b], acc[B + b]);      // (exact in 128 bits, one conversion: ld_decay_bin.h)
 		n[b] = acc[2 * B + b];
+	}
+	return TWK_HIP_OK;
+}
+
+// LD aggregate: the variants' bins are packed and uploaded and the cells' integer accumulators preset in front of the launches, and
+// converted behind the last of them, a slab of cells at a time.
+int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                         uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                         int32_t stat, const uint16_t* bin_x, const uint16_t* bin_y, uint32_t x_bins, uint32_t y_bins,
+                         uint64_t* n, double* sum, double* sum_sq, double* min, double* max, uint64_t* n_pairs) {
+	const bool stat_ok = stat == TWK_HIP_STAT_R || stat == TWK_HIP_STAT_R2 || stat == TWK_HIP_STAT_D || stat == TWK_HIP_STAT_DPRIME;
+	const bool bins_ok = x_bins >= 1 && x_bins <= AGG_MAX_BINS && y_bins >= 1 && y_bins <= AGG_MAX_BINS;
+	ReduceCall call(c, Reduce::aggregate, f, bin_x && bin_y && n && sum && sum_sq && min && max && stat_ok && bins_ok, mode, a0, nA);
+	if (call.bad) return call.bad;
+	const size_t M = c->M, cells = (size_t)x_bins * y_bins, words = cells * AGG_CELL_WORDS;
+	std::vector<uint32_t> key(M);
+	for (size_t v = 0; v < M; ++v) {
+		if ((bin_x[v] != AGG_OFF && bin_x[v] >= x_bins) || (bin_y[v] != AGG_OFF && bin_y[v] >= y_bins)) return TWK_HIP_E_INVALID;
+		key[v] = ag_pack(bin_x[v], bin_y[v]);
+	}
+	HIPCHK(c, c->d_agg_key.reserve(M, M, nullptr));
+	int rc = call.hold(c->d_agg, words, "the LD aggregate of %u variants needs %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	// (from pageable memory: the copy has left `key` when it returns)
+	HIPCHK(c, hipMemcpyAsync(c->d_agg_key, key.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
+	hipLaunchKernelGGL(k_ld_aggregate_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, c->d_agg.get(), (unsigned long long)words);
+	HIPCHK(c, hipGetLastError());
+	c->agg_map = AggMap{c->d_agg_key, c->d_agg, x_bins, y_bins, stat};
+	c->agg_slots = 0;
+	call.arm(words * sizeof(unsigned long long));
+	rc = call.dispatch(RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	if (rc) return rc;
+	const size_t slab = std::min<size_t>(cells, (size_t)1 << 18);      // 16 MiB of accumulators at a time
+	std::vector<unsigned long long> acc(slab * AGG_CELL_WORDS);
+	for (size_t at = 0; at < cells; at += slab) {
+		const size_t m = std::min(slab, cells - at);
+		hipError_t e = hipMemcpyAsync(acc.data(), c->d_agg + at * AGG_CELL_WORDS, m * AGG_CELL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "aggregate arrays: %s", hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
+		for (size_t k = 0; k < m; ++k) {
+			const unsigned long long* w = acc.data() + k * AGG_CELL_WORDS;
+			n[at + k] = w[AGG_W_N];
+			sum[at + k] = ag_sum_to_double_signed(w[AGG_W_Q_HI], w[AGG_W_Q_LO]);      // (exact in 128 bits, one conversion: ld_aggregate_bin.h)
+			sum_sq[at + k] = ag_sum_to_double_unsigned(w[AGG_W_Q2_HI], w[AGG_W_Q2_LO]);
+			min[at + k] = w[AGG_W_N] ? ag_value_to_double((long long)w[AGG_W_MIN]) : 0.0;
+			max[at + k] = w[AGG_W_N] ? ag_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
+		}
 	}
 	return TWK_HIP_OK;
 }

@@ -164,12 +164,13 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-// The options `ldscore`, `prune`, `clump`, `ldmatrix` and `lddecay` share (-P is accepted only as 1 by all; `prune`, `clump` and `ldmatrix` have no
+// The options `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay` and `ldaggregate` share (-P is accepted only as 1 by all; `prune`, `clump` and `ldmatrix` have no
 // -c / -C; `clump` adds its association file and thresholds, `ldmatrix` its statistic, fill and text switch, `lddecay` its range and number of
-// bins).  -> 0, or 1 after an error message.
-enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP, REDUCE_MATRIX, REDUCE_DECAY };
+// bins, `ldaggregate` its bins per axis, statistic, reduction and minimum count).  -> 0, or 1 after an error message.
+enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP, REDUCE_MATRIX, REDUCE_DECAY, REDUCE_AGGREGATE };
 static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options,
-                          tomahawk::twk_clump_settings* clump = nullptr, tomahawk::twk_matrix_settings* matrix = nullptr, tomahawk::twk_decay_settings* decay = nullptr) {
+                          tomahawk::twk_clump_settings* clump = nullptr, tomahawk::twk_matrix_settings* matrix = nullptr, tomahawk::twk_decay_settings* decay = nullptr,
+                          tomahawk::twk_aggregate_settings* aggregate = nullptr) {
 	const bool prune = cmd == REDUCE_PRUNE;
 	static struct option long_options[] = {
 		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
@@ -179,17 +180,44 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 		{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
 		{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
 		{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
+		{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
 		{0, 0, 0, 0}};
 	bool range_given = false;
 	int c, option_index = 0;
-	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : matrix ? "i:o:t:puP:r:w:I:c:C:s:f:T?" : decay ? "i:o:t:puP:r:w:I:c:C:d:b:?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
+	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : matrix ? "i:o:t:puP:r:w:I:c:C:s:f:T?" : decay ? "i:o:t:puP:r:w:I:c:C:d:b:?" : aggregate ? "i:o:t:puP:r:w:I:c:C:x:y:s:R:m:?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
 		if (prune && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
 		if (cmd == REDUCE_CLUMP && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
 		if (cmd == REDUCE_MATRIX && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot fill a part of the pair space (-c / -C): the matrix needs every pair" << std::endl; return 1; }
 		if (!clump && (c == 'a' || c == '1' || c == '2')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
-		if (!matrix && (c == 's' || c == 'f' || c == 'T')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
+		if (!matrix && (c == 'f' || c == 'T' || (c == 's' && !aggregate))) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
 		if (!decay && (c == 'd' || c == 'b')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
+		if (!aggregate && (c == 'x' || c == 'y' || c == 'R' || c == 'm')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
 		switch (c) {
+		case 'x': case 'y': case 'm': {
+			const std::string a(optarg);
+			const char* const what = c == 'x' ? "number of x bins (-x)" : c == 'y' ? "number of y bins (-y)" : "minimum count (-m)";
+			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << stamp("ERROR") << "The " << what << " must be a non-negative integer: " << a << std::endl; return 1; }
+			const double v = atof(optarg);
+			if (c == 'm') {
+				if (!(v <= 9007199254740992.0)) { std::cerr << stamp("ERROR") << "The minimum count (-m) must be at most 2^53" << std::endl; return 1; }
+				aggregate->min_count = (int64_t)v;
+			} else {
+				if (!(v >= 1 && v <= 4096)) { std::cerr << stamp("ERROR") << "The " << what << " must be between 1 and 4096" << std::endl; return 1; }
+				(c == 'x' ? aggregate->x_bins : aggregate->y_bins) = (int32_t)v;
+			}
+			break;
+		}
+		case 'R': {
+			const std::string a(optarg);
+			if (a == "mean") aggregate->reduce = 0;
+			else if (a == "count" || a == "n") aggregate->reduce = 1;
+			else if (a == "min") aggregate->reduce = 2;
+			else if (a == "max") aggregate->reduce = 3;
+			else if (a == "sd") aggregate->reduce = 4;
+			else if (a == "total") aggregate->reduce = 5;
+			else { std::cerr << stamp("ERROR") << "Unknown reduction (-R): " << a << " - one of mean, count, n, min, max, sd, total" << std::endl; return 1; }
+			break;
+		}
 		case 'd': case 'b': {
 			const std::string a(optarg);
 			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << stamp("ERROR") << "The " << (c == 'd' ? "range (-d)" : "number of bins (-b)") << " must be a non-negative integer: " << a << std::endl; return 1; }
@@ -205,10 +233,11 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 		}
 		case 's': {
 			const std::string a(optarg);
-			if (a == "r") matrix->stat = TWK_HIP_STAT_R;
-			else if (a == "r2") matrix->stat = TWK_HIP_STAT_R2;
-			else if (a == "D") matrix->stat = TWK_HIP_STAT_D;
-			else if (a == "Dprime") matrix->stat = TWK_HIP_STAT_DPRIME;
+			int32_t& stat = aggregate ? aggregate->stat : matrix->stat;
+			if (a == "r") stat = TWK_HIP_STAT_R;
+			else if (a == "r2") stat = TWK_HIP_STAT_R2;
+			else if (a == "D") stat = TWK_HIP_STAT_D;
+			else if (a == "Dprime") stat = TWK_HIP_STAT_DPRIME;
 			else { std::cerr << stamp("ERROR") << "Unknown statistic (-s): " << a << " - one of r, r2, D, Dprime" << std::endl; return 1; }
 			break;
 		}
@@ -254,6 +283,7 @@ static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::tw
 			settings.minP = atof(optarg);
 			if (!(settings.minP >= 1)) {
 				std::cerr << stamp("ERROR") << (cmd == REDUCE_MATRIX ? "Cannot fill a matrix with a cutoff P-value below 1: the matrix holds every record and Fisher's exact test is not run" :
+				                                cmd == REDUCE_AGGREGATE ? "Cannot aggregate with a cutoff P-value below 1: an aggregate takes in every record and Fisher's exact test is not run" :
 				                                cmd == REDUCE_DECAY ? "Cannot bin with a cutoff P-value below 1: a decay curve averages over every record and Fisher's exact test is not run" :
 				                                cmd == REDUCE_CLUMP ? "Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run" :
 				                                prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
@@ -484,6 +514,55 @@ static int lddecay(int argc, char** argv) {
 	tomahawk::twk_ld ld;
 	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
 	return ld.Decay(settings, ds) ? 0 : 1;
+}
+
+// `tomahawk ldaggregate`: the LD of every record `calc` would write rasterised into x-by-y cells, binned and summed on the GPU.  (The
+// reference's `aggregate` reads a .two file and writes a binary .twa; its -c, the minimum count, is -m here: -c is the chunk flag.)
+static void ldaggregate_usage() {
+	program_message();
+	std::cerr <<
+	"About:  LD aggregate: the pairwise LD of a region rasterised into an x-by-y heat map.  Every pair\n"
+	"        `calc` would report under the same options adds its statistic to cell (x(A), y(B)) and to\n"
+	"        cell (x(B), y(A)); per cell the contributions are counted and summed exactly on the GPU\n"
+	"        (no .two is written).  One contig: the axes span the data's range; several: every contig\n"
+	"        present at its whole length, one after the other.\n\n"
+	"Usage:  tomahawk ldaggregate [options] -i <in.twk> [-o <out.tsv>]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o FILE   output text file (- for stdout; default: -)\n"
+	"  -x INT    number of bins on the x axis, 1 to 4096 (default: 1000)\n"
+	"  -y INT    number of bins on the y axis, 1 to 4096 (default: 1000)\n"
+	"  -s STRING statistic: r2, r (signed), D or Dprime (default: r2)\n"
+	"  -R STRING reduction of a cell: mean, count (or n), min, max, sd or total (default: mean)\n"
+	"  -m INT    minimum count of a cell: a cell with fewer contributions prints 0 (default: 5)\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -c INT    number of subproblems to split compute into (must be in (c!2 + c))\n"
+	"  -C INT    chosen part to compute (0 < -C < -c)\n"
+	"  -w INT    sliding window width in bases: pairs further apart are not computed\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value (default: 0)\n"
+	"  -P FLOAT  accepted only as 1: an aggregate takes in every record, Fisher's test is not run\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"Output: '#' comment lines (x, y, bases per bin, range, each contig's offset), then x rows of y\n"
+	"        tab-separated values (mean = sum / n; sd = sqrt(sum_sq / n - mean^2), at least 0)\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int ldaggregate(int argc, char** argv) {
+	if (argc < 3) { ldaggregate_usage(); return 1; }
+	tomahawk::twk_ld_settings settings;
+	settings.minR2 = 0;
+	settings.out = "-";
+	tomahawk::twk_aggregate_settings as;
+	std::vector<std::pair<std::string, long long>> engine_options;
+	if (reduce_options(argc, argv, REDUCE_AGGREGATE, settings, engine_options, nullptr, nullptr, nullptr, &as)) return 1;
+	program_message();
+	std::cerr << stamp("LOG") << "Calling ldaggregate..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Aggregate(settings, as) ? 0 : 1;
 }
 
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
@@ -781,6 +860,7 @@ static int run_main(int argc, char** argv) {
 		             "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n"
 		             "  ldmatrix dense LD matrix of a region (signed r, r2, D or D'), filled on the GPU\n"
 		             "  lddecay  LD decay: R-squared by the distance between two variants, binned and summed on the GPU\n"
+		             "  ldaggregate  LD aggregate: r2, r, D or D' rasterised into x-by-y bins, summed exactly on the GPU\n"
 		             "  sort     sort a .two file\n"
 		             "  view     convert, filter and slice .two files\n"
 		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
@@ -799,6 +879,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "clump") == 0) return clump(argc, argv);
 	if (strcmp(argv[1], "ldmatrix") == 0) return ldmatrix(argc, argv);
 	if (strcmp(argv[1], "lddecay") == 0) return lddecay(argc, argv);
+	if (strcmp(argv[1], "ldaggregate") == 0) return ldaggregate(argc, argv);
 	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
 	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
 	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
@@ -807,7 +888,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance without a .two)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay`, `ldaggregate`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance and `ldaggregate` into x-by-y cells without a .two)" << std::endl;
 	return 1;
 }
 

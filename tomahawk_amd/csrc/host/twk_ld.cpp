@@ -31,6 +31,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include "twk_aggregate_landscape.h"
 #include "twk_format.h"
 #include "twk_hip.h"
 #include "twk_parallel.h"
@@ -941,7 +942,7 @@ bool twk_ld::Compute() {
 	return true;
 }
 
-// What `ldscore`, `prune`, `clump`, `ldmatrix` and `lddecay` share around their one engine call: the checks common to all, the input loaded exactly as
+// What `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay` and `ldaggregate` share around their one engine call: the checks common to all, the input loaded exactly as
 // Compute loads it onto one GPU, the text output with its `##` header, the `contig \t pos` that begins a variant's line, the closing lines.
 namespace {
 struct ReduceCommand {
@@ -1105,6 +1106,83 @@ bool twk_ld::Decay(const twk_ld_settings& s, const twk_decay_settings& ds) {
 	}
 	if (!cmd.finish(*os, text, "the decay table")) return false;
 	std::cerr << stamp("LOG") << "Binned " << pretty(counted) << " records of " << pretty(np) << " variant comparisons into " << pretty(B) << " bins. " << elapsed_string(sec) << std::endl;
+	cmd.all_done();
+	return true;
+}
+
+// `tomahawk ldaggregate`: the statistic of every record Compute would write, rasterised into x-by-y cells of the landscape the loaded
+// variants span (twk_hip_ld_aggregate: binned and summed exactly on the GPU, no record is formed), as text: one line per x bin.  The
+// input is loaded exactly as Compute loads it; one GPU.  The reference's two_reader::Aggregate rasterises the records of a .two file
+// into a binary .twa; its coordinate rule is kept (twk_aggregate_landscape.h), its file format is not provided.
+bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& as) {
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("An aggregate takes in every record", nullptr)) return false;
+	if (as.x_bins < 1 || as.x_bins > 4096 || as.y_bins < 1 || as.y_bins > 4096) { std::cerr << stamp("ERROR") << "The number of bins per axis must be between 1 and 4096..." << std::endl; return false; }
+	if (as.stat != TWK_HIP_STAT_R && as.stat != TWK_HIP_STAT_R2 && as.stat != TWK_HIP_STAT_D && as.stat != TWK_HIP_STAT_DPRIME) { std::cerr << stamp("ERROR") << "Unknown statistic..." << std::endl; return false; }
+	if (as.reduce < 0 || as.reduce > 5 || as.min_count < 0) { std::cerr << stamp("ERROR") << "Unknown reduction or a negative minimum count..." << std::endl; return false; }
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const Selection& S = cmd.S;
+	const uint32_t M = cmd.M, X = (uint32_t)as.x_bins, Y = (uint32_t)as.y_bins;
+	std::vector<int64_t> contig_bases;
+	for (const auto& ctg : S.reader.hdr.contigs) contig_bases.push_back(ctg.n_bases);
+	twk_aggregate_landscape land;
+	std::vector<uint16_t> bin_x, bin_y;
+	if (!agl_build(mImpl->rid.data(), mImpl->pos.data(), M, contig_bases, X, Y, land, bin_x, bin_y)) {
+		std::cerr << stamp("ERROR") << "Cannot lay out the landscape: a variant on a contig the header does not have, or a range of 0 or of 2^32 bases and more..." << std::endl;
+		return false;
+	}
+	const size_t cells = (size_t)X * Y;
+	std::vector<uint64_t> n(cells, 0);
+	std::vector<double> sum(cells, 0.0), sum_sq(cells, 0.0), mn(cells, 0.0), mx(cells, 0.0);
+	uint64_t np = 0;
+	const auto t0 = ReduceCommand::clock::now();
+	int rc = TWK_HIP_OK;
+	if (S.bal.diag) { if (M > 1) rc = twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, M, 1, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np); }
+	else if (S.nL && S.nR) rc = twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_aggregate")) return false;
+	mImpl->n_pairs = np;
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+
+	std::ostream* const os = cmd.open_text();
+	if (!os) return false;
+	cmd.header(*os, "ldaggregate");
+	static const char* const stat_names[] = {"r", "r2", "D", "Dprime"};
+	static const char* const reduce_names[] = {"mean", "count", "min", "max", "sd", "total"};
+	uint64_t contributions = 0;
+	for (size_t k = 0; k < cells; ++k) contributions += n[k];
+	*os << "#x=" << X << ",y=" << Y << ",bpx=" << land.bpx << ",bpy=" << land.bpy << ",range=" << land.range
+	    << ",stat=" << stat_names[as.stat] << ",reduce=" << reduce_names[as.reduce] << ",min_count=" << as.min_count << ",contributions=" << contributions << "\n";
+	if (land.single) *os << "#landscape=one contig,min_pos=" << land.min_pos << "\n";
+	else *os << "#landscape=whole contigs\n";
+	for (size_t k = 0; k < contig_bases.size(); ++k)
+		if (land.present[k]) *os << "#contig=" << S.reader.hdr.contigs[k].name << ",rid=" << k << ",offset=" << (land.single ? 0 : land.offset[k]) << "\n";
+	std::string text;
+	char cell[64];
+	for (uint32_t x = 0; x < X; ++x) {
+		for (uint32_t y = 0; y < Y; ++y) {
+			const size_t k = (size_t)x * Y + y;
+			double v = 0.0;
+			if (n[k] && n[k] >= (uint64_t)as.min_count) {
+				const double cnt = (double)n[k], mean = sum[k] / cnt;
+				switch (as.reduce) {
+				case 0: v = mean; break;
+				case 1: v = cnt; break;
+				case 2: v = mn[k]; break;
+				case 3: v = mx[k]; break;
+				case 4: { const double var = sum_sq[k] / cnt - mean * mean; v = var > 0 ? sqrt(var) : 0.0; break; }
+				default: v = sum[k]; break;
+				}
+			}
+			snprintf(cell, sizeof(cell), y ? "\t%.17g" : "%.17g", v);
+			text += cell;
+		}
+		text += '\n';
+		cmd.spill(*os, text);
+	}
+	if (!cmd.finish(*os, text, "the aggregate")) return false;
+	std::cerr << stamp("LOG") << "Aggregated " << pretty(contributions) << " contributions of " << pretty(np) << " variant comparisons into " << pretty(cells) << " cells. " << elapsed_string(sec) << std::endl;
 	cmd.all_done();
 	return true;
 }

@@ -193,6 +193,9 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_decay.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, p, p,
                                      C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_aggregate.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, p, p,
+                                         C.c_uint32, C.c_uint32, p, p, p, p, p, C.POINTER(C.c_uint64)]
     lib.twk_hip_ld_prune.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_prune_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
@@ -508,6 +511,35 @@ class HipLd:
                                                tile_variants, int(window), l_window, int(range_bp), int(n_bins), n.ctypes.data,
                                                s.ctypes.data, C.byref(npairs)), "twk_hip_ld_decay")
         return n, s, npairs.value
+
+    def ld_aggregate(self, mode: int, filters: Filters, bin_x, bin_y, x_bins: int, y_bins: int, stat: int = STAT_R2, a0: int = 0,
+                     nA: int | None = None, b0: int = 0, nB: int | None = None, triangle: bool = True, part: int = 0, n_parts: int = 1,
+                     tile_variants: int = 0, window: int = 0, l_window: int = 0):
+        """LD aggregate (twk_hip_ld_aggregate): the pairs' LD rasterised into x_bins x y_bins cells.  bin_x / bin_y: one uint16 per
+        uploaded variant, its bin on that axis, 0xFFFF for off the landscape.  For every pair (A, B) ld_region would report a record
+        for, v (stat: STAT_R signed, STAT_R2, STAT_D, STAT_DPRIME) is added to cell (bin_x[A], bin_y[B]) and to cell (bin_x[B],
+        bin_y[A]), each if both bins are valid.  Per cell the contributions, the sums of rint(v * 2^32) / 2^32 and of
+        rint((v * v) * 2^32) / 2^32, summed exactly in integers on the device, and the extremes of rint(v * 2^32) / 2^32 (0 in an
+        empty cell): the same bits for any tiling, order or repeat.  No record is formed.  filters.minP must be >= 1; 1 <= x_bins,
+        y_bins <= 4096.  A shard returns partial arrays.  -> (n uint64, sum, sum_sq, min, max float64, each (x_bins, y_bins), n_pairs)."""
+        M = self.n_variants
+        nA = M - a0 if nA is None else nA
+        nB = M - b0 if nB is None else nB
+        bx = np.ascontiguousarray(bin_x, dtype=np.uint16)
+        by = np.ascontiguousarray(bin_y, dtype=np.uint16)
+        if M and (bx.shape != (M,) or by.shape != (M,)):          # (before upload the engine refuses the call itself)
+            raise ValueError(f"bin_x and bin_y hold one bin per uploaded variant ({M}): got {bx.shape} and {by.shape}")
+        ok = 1 <= int(x_bins) <= 4096 and 1 <= int(y_bins) <= 4096          # (refused bin counts are the engine's to refuse)
+        shape = (int(x_bins), int(y_bins)) if ok else (1, 1)
+        n = np.zeros(shape, dtype=np.uint64)
+        out = [np.zeros(shape, dtype=np.float64) for _ in range(4)]
+        npairs = C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_aggregate(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts,
+                                                   tile_variants, int(window), l_window, int(stat), bx.ctypes.data, by.ctypes.data,
+                                                   int(x_bins), int(y_bins), n.ctypes.data, *(a.ctypes.data for a in out),
+                                                   C.byref(npairs)), "twk_hip_ld_aggregate")
+        return (n, *out, npairs.value)
 
     def ld_prune(self, mode: int, filters: Filters, a0: int = 0, n: int | None = None, tile_variants: int = 0, window: int = 0,
                  l_window: int = 0):
