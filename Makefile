@@ -94,14 +94,15 @@ matrix-check:
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/matrix_index_check.cpp -o build/matrix_index_check
 	./build/matrix_index_check
 
-# LD decay's bin index, quantisation and host conversion (csrc/hip/ld_decay_bin.h) against a naive restatement (csrc/tools/decay_bin_check.cpp)
+# LD decay's bin index (csrc/hip/ld_decay_bin.h) against a naive restatement (csrc/tools/decay_bin_check.cpp), and the exact sums'
+# quantisation, split and host conversion (csrc/hip/ld_exact_sum.h) for both split widths in use (csrc/tools/exact_sum_check.h)
 decay-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/decay_bin_check.cpp -o build/decay_bin_check
 	./build/decay_bin_check
 
-# LD aggregate's packing, quantisation, split and host conversion (csrc/hip/ld_aggregate_bin.h) and ldaggregate's landscape
-# (csrc/host/twk_aggregate_landscape.h) against a naive restatement (csrc/tools/aggregate_bin_check.cpp)
+# LD aggregate's packing (csrc/hip/ld_aggregate_bin.h) and ldaggregate's landscape (csrc/host/twk_aggregate_landscape.h) against a naive
+# restatement (csrc/tools/aggregate_bin_check.cpp), and the same checks of the exact sums as decay-check (csrc/tools/exact_sum_check.h)
 aggregate-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/aggregate_bin_check.cpp -o build/aggregate_bin_check

@@ -395,7 +395,7 @@ int twk_hip_matrix_last(const twk_hip_ctx* ctx, double* copy_ms, uint64_t* matri
  *   sum_r2[bin] = the sum of their R2 fields
  * (the mean is the caller's division) - reduced on the device: the count matrix of a launch goes through the pair rules and the
  * math of the record path (one code, ld_math.hip.h) and the r2 of a counting pair is added to its bin as the integer
- * rint(r2 * 2^32) (ld_decay.hip.h, ld_decay_bin.h).  No record is formed, sorted or copied: 24 bytes per bin leave the device.
+ * rint(r2 * 2^32) (ld_decay.hip.h, ld_exact_sum.h).  No record is formed, sorted or copied: 24 bytes per bin leave the device.
  * THE SUMS ARE EXACT IN INTEGERS AND HAVE NO ORDER: sum_r2[bin] is the sum of the pairs' r2, each rounded once to a multiple of
  * 2^-32 (off by at most 2^-33 a pair), converted to double once; two calls, any tile_variants and any launch order return the same
  * bits, and no floating-point atomic is used.  filters.minP must be >= 1: Fisher's test is not run.  Always the matrix form of the
@@ -428,7 +428,7 @@ int twk_hip_ld_decay(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
  *   sum     the sum of q / 2^32 over the cell, q = rint(v * 2^32) as a signed 64-bit integer
  *   sum_sq  the same with q2 = rint((v * v) * 2^32) - the square is one double multiplication
  *   min/max the smallest and the largest q / 2^32; both 0.0 where n == 0
- * THE SUMS ARE EXACT IN INTEGERS AND HAVE NO ORDER (ld_aggregate.hip.h, ld_aggregate_bin.h): summed in 64-bit integer atomics,
+ * THE SUMS ARE EXACT IN INTEGERS AND HAVE NO ORDER (ld_aggregate.hip.h, ld_exact_sum.h): summed in 64-bit integer atomics,
  * converted once from 128 bits; all five arrays are the same bits for any tile_variants, any launch order and any repeat, and no
  * floating-point atomic is used.  A shard (part / n_parts) returns partial arrays: n and the sums add, min / max combine by min /
  * max over the cells with n != 0.  filters.minP must be >= 1: Fisher's test is not run.  Always the matrix form of the contraction

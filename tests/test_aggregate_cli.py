@@ -3,6 +3,9 @@ import os
 import re
 import subprocess
 
+import pytest
+
+from tests import util
 from tomahawk_amd import hostlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,3 +86,10 @@ def test_make_aggregate_check_passes():
                        env={k: v for k, v in os.environ.items() if k not in ("LD_PRELOAD", "ASAN_OPTIONS", "UBSAN_OPTIONS")})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "aggregate_bin_check: ok" in r.stdout
+
+
+@pytest.mark.skipif(not os.path.exists(util.HIPCC), reason="hipcc not installed")
+def test_aggregate_kernels_use_no_scratch_memory_and_run_three_waves_a_simd():
+    """The aggregate kernels as `make hip` compiles them, by their metadata alone: what DESIGN 3.11 states."""
+    names = util.reduce_kernels_fit("k_ld_aggregate")
+    assert len(names) == 2 and any("k_ld_aggregate_init" in n for n in names), names

@@ -5,10 +5,10 @@ import subprocess
 
 import pytest
 
+from tests import util
 from tomahawk_amd import hostlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _run(*args):
@@ -119,28 +119,18 @@ def test_header_declares_the_entry_points_and_the_abi_version_is_unchanged():
     assert "bool Clump(const twk_ld_settings& settings, const twk_clump_settings& clump);" in twk_ld and "struct twk_clump_settings {" in twk_ld
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_clump_kernels_use_no_scratch_memory(tmp_path):
+@pytest.mark.skipif(not os.path.exists(util.HIPCC), reason="hipcc not installed")
+def test_clump_kernels_use_no_scratch_memory():
     """The clump kernels as `make hip` compiles them: the record d_pair fills is never stored (only `keep` is used) and the mask
     kernel carries one more word than prune's across its row loop, so no kernel of the clump path may have a private segment or
     spill a vector register.  Only the kernels' metadata is read."""
-    out = str(tmp_path / "twk_hip.s")
-    make = open(os.path.join(ROOT, "Makefile")).read()
-    flags = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", make, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    flags = [f for f in flags if f not in ("-fPIC",)]
-    r = subprocess.run([HIPCC] + flags + ["-Iinclude", "-S", "--cuda-device-only", "-o", out, "tomahawk_amd/csrc/hip/twk_hip.hip"],
-                       cwd=ROOT, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(out).read()
     seen = []
-    for name, body in re.findall(r"\.name:\s+(\S+)\n((?:(?!\s*\.name:).*\n)*)", asm):
+    for name, body in util.engine_kernels().items():
         if "k_ld_clump" not in name:
             continue
         assert "k_ld_prune" not in name
         seen.append(name)
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-        spills = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
-        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", body).group(1))
+        vgprs, scratch, spills = util.kernel_resources(body)
         print(name, "vgprs", vgprs, "scratch", scratch, "spills", spills)
         assert scratch == 0 and spills == 0, (name, scratch, spills)
     assert sum("mask" in n for n in seen) == 1 and sum("walk" in n for n in seen) == 2, seen

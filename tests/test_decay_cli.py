@@ -3,6 +3,9 @@ import os
 import re
 import subprocess
 
+import pytest
+
+from tests import util
 from tomahawk_amd import hostlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,3 +72,11 @@ def test_make_decay_check_passes():
                        env={k: v for k, v in os.environ.items() if k not in ("LD_PRELOAD", "ASAN_OPTIONS", "UBSAN_OPTIONS")})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "decay_bin_check: ok" in r.stdout
+
+
+
+@pytest.mark.skipif(not os.path.exists(util.HIPCC), reason="hipcc not installed")
+def test_decay_kernels_use_no_scratch_memory_and_run_three_waves_a_simd():
+    """The decay kernels as `make hip` compiles them, by their metadata alone: what DESIGN 3.10 states."""
+    names = util.reduce_kernels_fit("k_ld_decay")
+    assert len(names) == 1, names

@@ -37,10 +37,8 @@ import pytest
 import tomahawk_amd as T
 from oracle import oracle as O
 from tests import util
-from tests.test_gpu_clump import data_set as big_data_set
-from tests.test_gpu_decay import alleles, blob, positions
-from tests.test_gpu_ldscore import MODES, RTOL, oracle_records
-from tests.test_gpu_matrix import FIELD, STATS, stat_of
+from tests.reduce_cases import FIELD, MODES, RTOL, STATS, alleles, bins_every_seventh_random, bins_monotone, blob, monotone, oracle_records, positions, stat_of
+from tests.reduce_cases import data_set as big_data_set
 from tomahawk_amd import hostlib
 
 pytestmark = pytest.mark.gpu
@@ -52,27 +50,10 @@ I64_MAX, I64_MIN = np.iinfo(np.int64).max, np.iinfo(np.int64).min
 STAT_IDS = {T.STAT_R: "r", T.STAT_R2: "r2", T.STAT_D: "D", T.STAT_DPRIME: "Dprime"}
 
 
-# ---- bin assignments -------------------------------------------------------------------------------------------------------------------
-def monotone(M, bins):
-    return (np.arange(M, dtype=np.int64) * bins // M).astype(np.uint16)
-
-
-def bins_monotone(M, X, Y):
-    return monotone(M, X), monotone(M, Y)
-
-
+# ---- bin assignments (monotone and every-seventh-random: reduce_cases) -------------------------------------------------------------------------------------------------------------------
 def bins_permuted(M, X, Y, seed=11):
     rng = np.random.default_rng(seed)
     return monotone(M, X)[rng.permutation(M)], monotone(M, Y)[rng.permutation(M)]
-
-
-def bins_every_seventh_random(M, X, Y, seed=12):
-    rng = np.random.default_rng(seed)
-    bx, by = bins_monotone(M, X, Y)
-    sel = np.arange(M) % 7 == 3
-    bx[sel] = rng.integers(0, X, int(sel.sum()))
-    by[sel] = rng.integers(0, Y, int(sel.sum()))
-    return bx, by
 
 
 def bins_some_off(M, X, Y):

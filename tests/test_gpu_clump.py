@@ -23,17 +23,13 @@ import pytest
 import tomahawk_amd as T
 from oracle import oracle as O
 from tests import util
-from tests.test_gpu_prune import MODES, big_missing, big_plain, margin_holds, mosaic140, oracle_records
+from tests.reduce_cases import MODES, data_set, margin_holds, mosaic140, oracle_records, standard_p
 from tomahawk_amd import hostlib
 
 pytestmark = pytest.mark.gpu
 
 NO = 0xFFFFFFFF
 P1, P2 = 1e-4, 1e-2
-
-
-def standard_p(M):
-    return 10.0 ** (-8.0 * np.random.default_rng(77).random(M))
 
 
 def clump(ia, ib, M, p, p1, p2, a0=0, n=None):
@@ -67,24 +63,14 @@ def tally(index_of):
     return int((inside & (ix == at)).sum()), int((inside & (ix != at)).sum()), int((inside & (at < ix)).sum())
 
 
-# ---- the data sets and their oracle records: computed once per (data set, mode, window), never changed -----------------------------
-DATA = {"mosaic250": lambda: mosaic140(250), "mosaic128": lambda: mosaic140(128), "mosaic64": lambda: mosaic140(64),
-        "plain": big_plain, "missing": big_missing}
-
-
-@functools.lru_cache(maxsize=None)
-def data_set(name):
-    al = DATA[name]()
-    al.setflags(write=False)
-    return al
-
-
+# ---- the data sets (reduce_cases.data_set) and their oracle records: computed once per (data set, mode, window), never changed -----------------------------
 @functools.lru_cache(maxsize=None)
 def oracle_edges(name, mode_key, window=None):
     al = data_set(name)
     data, mask = O.bitvectors_from_alleles(al)
     variants = O.variants_from_alleles(al)
-    ia, ib, r2 = oracle_records(data, mask, variants, al.shape[1], mode_key, window)
+    ia, ib, recs = oracle_records(data, mask, variants, al.shape[1], mode_key, window=window)
+    r2 = recs["R2"].astype(np.float64)
     for a in (ia, ib, r2):
         a.setflags(write=False)
     return ia, ib, r2
@@ -268,7 +254,8 @@ def test_clump_long_rows(hip):
     ia, ib = recs["idxA"].astype(np.int64), recs["idxB"].astype(np.int64)
     want = clump(ia, ib, M, p, P1, P2)
     assert n_edges == len(recs) and index_of.tobytes() == want.tobytes() and (n_clumps, n_members) == tally(want)[:2] and n_clumps > 0
-    oa, ob, r2 = oracle_records(data, mask, variants, N, "p")
+    oa, ob, recs = oracle_records(data, mask, variants, N, "p")
+    r2 = recs["R2"].astype(np.float64)
     if margin_holds(r2, thr):
         sel = r2 >= thr
         assert n_edges == int(sel.sum()) and index_of.tobytes() == clump(oa[sel], ob[sel], M, p, P1, P2).tobytes()
@@ -326,7 +313,8 @@ def test_clump_cli(hip, tmp_path, flags, mode_key, thr, window):
     hostlib.write_twk(twk, al, pos, rid, phased=np.ones(M, np.uint8), n_contigs=2, block_size=50)
     data, mask = O.bitvectors_from_alleles(al)
     variants = O.variants_from_alleles(al, pos=pos, rid=rid, phase=1)
-    ia, ib, r2 = oracle_records(data, mask, variants, N, mode_key, window)
+    ia, ib, recs = oracle_records(data, mask, variants, N, mode_key, window=window)
+    r2 = recs["R2"].astype(np.float64)
     assert margin_holds(r2, thr)
     sel = r2 >= thr
     # the association file: every variant but number 5 (not named: no P), number 9 as NA, one line that names no variant, one

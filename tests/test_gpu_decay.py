@@ -27,8 +27,8 @@ import pytest
 import tomahawk_amd as T
 from oracle import oracle as O
 from tests import util
-from tests.test_gpu_clump import data_set as big_data_set
-from tests.test_gpu_ldscore import MODES, RTOL, mosaic140, oracle_records
+from tests.reduce_cases import MODES, RTOL, alleles, blob, oracle_records, positions
+from tests.reduce_cases import data_set as big_data_set
 from tomahawk_amd import hostlib
 
 pytestmark = pytest.mark.gpu
@@ -36,19 +36,6 @@ pytestmark = pytest.mark.gpu
 E_INVALID, E_STATE = -1, -5
 Q_STEP = 2.0 ** -33                 # |rint(R2 * 2^32) / 2^32 - R2| of one pair
 RANGE = 30000                       # the 300 variants at the default spacing of 100 span 29,900 bases
-
-DATA = {"random": lambda: util.random_alleles(300, 1000, seed=2024, low_ac=4),
-        "missing": lambda: util.random_alleles(120, 128, 31, miss_rate=0.08, miss_variants=0.3, low_ac=4),
-        "mosaic64": lambda: mosaic140(64), "mosaic250": lambda: mosaic140(250), "mosaic128": lambda: mosaic140(128),
-        "mosaic1000": lambda: mosaic140(1000)}
-
-
-@functools.lru_cache(maxsize=None)
-def alleles(name):
-    al = DATA[name]()
-    al.setflags(write=False)
-    return al
-
 
 @functools.lru_cache(maxsize=None)
 def oracle(name, mode_key, minR2=0.0):
@@ -71,12 +58,6 @@ def oracle(name, mode_key, minR2=0.0):
     for a in out:
         a.setflags(write=False)
     return out
-
-
-def positions(M, pos=None, rid=None):
-    pos = np.arange(M, dtype=np.int64) * 100 + 1000 if pos is None else np.asarray(pos, dtype=np.int64)
-    rid = np.zeros(M, dtype=np.int64) if rid is None else np.asarray(rid, dtype=np.int64)
-    return pos, rid
 
 
 def bins_of(ia, ib, pos, rid, range_bp, n_bins):
@@ -321,10 +302,6 @@ def test_decay_refuses_bad_arguments_and_leaves_the_engine_usable(hip):
 
 
 # ---- 8: decay among the other kinds of the reduce path, on one context ----------------------------------------------------------------
-def blob(result):
-    return b"".join(np.asarray(x).tobytes() for x in result)
-
-
 def test_decay_between_calls_of_other_kinds_on_one_context(hip):
     """The order decay, region, score, decay, matrix, decay with tile_variants = 128 - more launches a call than the pipeline has slots,
     so every slot's argument block is reused by kinds whose parameter blocks differ in size: each call returns the bytes it returns alone."""

@@ -19,36 +19,10 @@ import pytest
 import tomahawk_amd as T
 from oracle import oracle as O
 from tests import util
+from tests.reduce_cases import MODES, RTOL, mosaic140, oracle_records
 from tomahawk_amd import hostlib
 
 pytestmark = pytest.mark.gpu
-
-MODES = {"p": (T.MODE_PHASED, True, False), "u": (T.MODE_UNPHASED, False, True), "auto": (T.MODE_AUTO, False, False)}
-RTOL = 1e-6
-MOSAICS = {64: (5001, 4, 0.02, 0.002, False), 250: (5004, 7, 0.02, 0.002, False), 128: (5003, 6, 0.005, 0.0, True),
-           1000: (5006, 3, 0.005, 0.0, False)}          # N -> seed, founders, switch, mut, miss (test_haplotype_block_data_all_modes)
-
-
-def mosaic140(N):
-    seed, founders, switch, mut, miss = MOSAICS[N]
-    return util.mosaic_alleles(140, N, seed, n_founders=founders, switch=switch, mut=mut,
-                               miss_rate=0.05 if miss else 0.0, miss_variants=0.3 if miss else 0.0)
-
-
-def oracle_records(data, mask, variants, N, mode_key, minR2=0.0, window=None):
-    """-> (idxA, idxB, records) of the oracle for the mode, each pair once (A < B in file order)."""
-    _, ph, un = MODES[mode_key]
-    want = O.all_pairs(data, mask, variants, N, O.settings(minR2=minR2, minP=1, phased=ph, unphased=un), vector_only=False)
-    index = {(int(v["rid"]), int(v["pos"])): i for i, v in enumerate(variants)}
-    ia = np.array([index[(int(r), int(p))] for r, p in zip(want["ridA"], want["Apos"])], dtype=np.int64)
-    ib = np.array([index[(int(r), int(p))] for r, p in zip(want["ridB"], want["Bpos"])], dtype=np.int64)
-    assert (ia < ib).all()
-    if window is not None:
-        pos, rid = variants["pos"].astype(np.int64), variants["rid"].astype(np.int64)
-        keep = (rid[ia] == rid[ib]) & (np.abs(pos[ia] - pos[ib]) <= window)
-        ia, ib, want = ia[keep], ib[keep], want[keep]
-    return ia, ib, want
-
 
 def oracle_score(ia, ib, recs, M, root_error=None):
     """-> (n uint64[M], sum float64[M], floor float64[M]) from records: the definition, plus the floor term of the bar."""

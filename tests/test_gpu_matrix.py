@@ -23,24 +23,16 @@ import pytest
 import tomahawk_amd as T
 from oracle import oracle as O
 from tests import util
-from tests.test_gpu_ldscore import MODES, mosaic140, oracle_records
+from tests.reduce_cases import FIELD, MODES, RTOL, STATS, mosaic140, oracle_records, stat_of
 from tomahawk_amd import hostlib
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-6
 FILL = -2.0
-FIELD = {T.STAT_R: "R", T.STAT_R2: "R2", T.STAT_D: "D", T.STAT_DPRIME: "Dprime"}
-STATS = [T.STAT_R, T.STAT_R2, T.STAT_D, T.STAT_DPRIME]
 
 
 def u32(m):
     return np.ascontiguousarray(m).view(np.uint32)
-
-
-def stat_of(recs, stat):
-    """The statistic of records, in float64: r carries D's sign."""
-    return np.copysign(recs["R"], recs["D"]) if stat == T.STAT_R else recs[FIELD[stat]].astype(np.float64)
 
 
 def oracle_matrix(ia, ib, recs, n, stat, fill, root_error=None, a0=0):

@@ -19,48 +19,10 @@ import pytest
 import tomahawk_amd as T
 from oracle import oracle as O
 from tests import util
+from tests.reduce_cases import MODES, big_missing, big_plain, margin_holds, mosaic140, oracle_records
 from tomahawk_amd import hostlib
 
 pytestmark = pytest.mark.gpu
-
-MODES = {"p": (T.MODE_PHASED, True, False), "u": (T.MODE_UNPHASED, False, True), "auto": (T.MODE_AUTO, False, False)}
-MOSAICS = {64: (5001, 4, 0.02, 0.002, False), 250: (5004, 7, 0.02, 0.002, False), 128: (5003, 6, 0.005, 0.0, True),
-           1000: (5006, 3, 0.005, 0.0, False)}          # N -> seed, founders, switch, mut, miss (test_gpu_ldscore.MOSAICS)
-
-
-def mosaic140(N):
-    seed, founders, switch, mut, miss = MOSAICS[N]
-    return util.mosaic_alleles(140, N, seed, n_founders=founders, switch=switch, mut=mut,
-                               miss_rate=0.05 if miss else 0.0, miss_variants=0.3 if miss else 0.0)
-
-
-def big_plain():
-    return util.mosaic_alleles(700, 250, 5004, n_founders=7, switch=0.02, mut=0.002)
-
-
-def big_missing():
-    return util.mosaic_alleles(600, 128, 5003, n_founders=6, switch=0.005, mut=0.0, miss_rate=0.05, miss_variants=0.3)
-
-
-def oracle_records(data, mask, variants, N, mode_key, window=None):
-    """-> (idxA, idxB, R2) of the oracle's unthresholded records for the mode, each pair once (A < B in file order)."""
-    _, ph, un = MODES[mode_key]
-    want = O.all_pairs(data, mask, variants, N, O.settings(minR2=0.0, minP=1, phased=ph, unphased=un), vector_only=False)
-    index = {(int(v["rid"]), int(v["pos"])): i for i, v in enumerate(variants)}
-    ia = np.array([index[(int(r), int(p))] for r, p in zip(want["ridA"], want["Apos"])], dtype=np.int64)
-    ib = np.array([index[(int(r), int(p))] for r, p in zip(want["ridB"], want["Bpos"])], dtype=np.int64)
-    assert (ia < ib).all()
-    r2 = np.asarray(want["R2"], dtype=np.float64)
-    if window is not None:
-        pos, rid = variants["pos"].astype(np.int64), variants["rid"].astype(np.int64)
-        inside = (rid[ia] == rid[ib]) & (np.abs(pos[ia] - pos[ib]) <= window)
-        ia, ib, r2 = ia[inside], ib[inside], r2[inside]
-    return ia, ib, r2
-
-
-def margin_holds(r2, thr):
-    return not (np.abs(r2 - thr) <= 1e-6 * thr).any()
-
 
 def greedy_walk(ia, ib, M, a0=0, n=None):
     """The definition: edges (ia[k], ib[k]), ia < ib, inside [a0, a0 + n) -> keep uint8[M]."""
@@ -76,7 +38,8 @@ def greedy_walk(ia, ib, M, a0=0, n=None):
 
 
 def oracle_prune(data, mask, variants, N, mode_key, thr, window=None, a0=0, n=None):
-    ia, ib, r2 = oracle_records(data, mask, variants, N, mode_key, window)
+    ia, ib, recs = oracle_records(data, mask, variants, N, mode_key, window=window)
+    r2 = recs["R2"].astype(np.float64)
     assert margin_holds(r2, thr), f"an oracle R2 within 1e-6 relative of the cut-off {thr}: the input does not qualify"
     sel = r2 >= thr
     return greedy_walk(ia[sel], ib[sel], len(variants), a0, n)
@@ -188,7 +151,8 @@ def test_prune_long_rows(hip):
     assert hip.timing()["count_launches"] >= 3
     want, n_recs, _ = walk_of_own_records(hip, T.MODE_PHASED, thr, M, tile_variants=512)
     assert n_edges == n_recs and keep.tobytes() == want.tobytes() and 0 < n_kept == int(want.sum()) < M
-    ia, ib, r2 = oracle_records(data, mask, variants, N, "p")
+    ia, ib, recs = oracle_records(data, mask, variants, N, "p")
+    r2 = recs["R2"].astype(np.float64)
     if margin_holds(r2, thr):
         sel = r2 >= thr
         o_keep, o_edges = greedy_walk(ia[sel], ib[sel], M)
@@ -243,7 +207,8 @@ def test_prune_cli(hip, tmp_path, flags, mode_key, thr, window):
     hostlib.write_twk(twk, al, pos, rid, phased=np.ones(M, np.uint8), n_contigs=2, block_size=50)
     data, mask = O.bitvectors_from_alleles(al)
     variants = O.variants_from_alleles(al, pos=pos, rid=rid, phase=1)
-    ia, ib, r2 = oracle_records(data, mask, variants, N, mode_key, window)
+    ia, ib, recs = oracle_records(data, mask, variants, N, mode_key, window=window)
+    r2 = recs["R2"].astype(np.float64)
     assert margin_holds(r2, thr)
     sel = r2 >= thr
     if window is not None:

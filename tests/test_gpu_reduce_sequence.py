@@ -1,6 +1,6 @@
-"""Score, prune, clump and matrix calls share one reduce path in the engine: one kind, one pair of argument buffers per pipeline slot,
-one adjacency bitmap, one counters buffer.  What four separate sets of state gave for free is checked here: calls of different kinds
-on ONE context, in any order and around failed calls, return what they return alone.
+"""Score, prune, clump, matrix, decay and aggregate calls share one reduce path in the engine: one kind, one pair of argument buffers per
+pipeline slot, one state block, one counters buffer.  What six separate sets of state gave for free is checked here: calls of different
+kinds on ONE context, in any order and around failed calls, return what they return alone.
 
 Both inputs run with tile_variants = 128, so that a call has more launches than the pipeline has slots: every slot's argument buffer
 is then reused by kinds whose parameter blocks differ in size.  Equality is of bytes; nothing here is compared with a tolerance.
@@ -10,19 +10,16 @@ import pytest
 
 import tomahawk_amd as T
 from tests import util
-from tests.test_gpu_clump import data_set, standard_p
+from tests.reduce_cases import bins_every_seventh_random, blob, data_set, standard_p
 
 pytestmark = pytest.mark.gpu
 
 TILE = 128
 F = dict(minR2=0.2)
-KINDS = ("region", "score", "prune", "clump", "matrix")
+KINDS = ("region", "score", "prune", "clump", "matrix", "decay", "aggregate")
 A0, N_SUB = 37, 203
-
-
-def blob(result):
-    """Everything a call returned, as bytes."""
-    return b"".join(np.asarray(x).tobytes() for x in result)
+RANGE_BP, N_BINS = 50000, 500          # decay
+X_BINS, Y_BINS = 50, 31                # aggregate, bins_every_seventh_random
 
 
 def call(eng, kind, p, **kw):
@@ -35,6 +32,11 @@ def call(eng, kind, p, **kw):
         return eng.ld_prune(T.MODE_AUTO, f, tile_variants=TILE, **kw)
     if kind == "clump":
         return eng.ld_clump(T.MODE_AUTO, f, p, 1e-4, 1e-2, tile_variants=TILE, **kw)
+    if kind == "decay":
+        return eng.ld_decay(T.MODE_AUTO, f, RANGE_BP, N_BINS, tile_variants=TILE)
+    if kind == "aggregate":
+        bx, by = bins_every_seventh_random(eng.n_variants, X_BINS, Y_BINS)
+        return eng.ld_aggregate(T.MODE_AUTO, f, bx, by, X_BINS, Y_BINS, T.STAT_R, tile_variants=TILE)
     return eng.ld_matrix(T.MODE_AUTO, f, T.STAT_R, -2.0, tile_variants=TILE, **kw)
 
 
@@ -72,7 +74,9 @@ def test_kinds_in_any_order_on_one_context(hip, name):
     # one failed call of every reduce kind (minP < 1: TWK_HIP_E_INVALID) leaves nothing behind
     bad = T.Filters(minR2=0.2, minP=0.5)
     for failing in (lambda: hip.ld_score(T.MODE_AUTO, bad), lambda: hip.ld_prune(T.MODE_AUTO, bad),
-                    lambda: hip.ld_clump(T.MODE_AUTO, bad, p), lambda: hip.ld_matrix(T.MODE_AUTO, bad)):
+                    lambda: hip.ld_clump(T.MODE_AUTO, bad, p), lambda: hip.ld_matrix(T.MODE_AUTO, bad),
+                    lambda: hip.ld_decay(T.MODE_AUTO, bad, RANGE_BP, N_BINS),
+                    lambda: hip.ld_aggregate(T.MODE_AUTO, bad, *bins_every_seventh_random(M, X_BINS, Y_BINS), X_BINS, Y_BINS, T.STAT_R)):
         with pytest.raises(T.HipError) as ei:
             failing()
         assert ei.value.code == -1

@@ -6,10 +6,10 @@ import subprocess
 
 import pytest
 
+from tests import util
 from tomahawk_amd import hostlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _run(*args):
@@ -122,30 +122,20 @@ def test_index_arithmetic_of_the_fill_played_on_the_host():
     assert '#include "../hip/ld_matrix_index.h"' in open(os.path.join(ROOT, "tomahawk_amd", "csrc", "tools", "matrix_index_check.cpp")).read()
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_matrix_kernels_use_no_scratch_memory(tmp_path):
+@pytest.mark.skipif(not os.path.exists(util.HIPCC), reason="hipcc not installed")
+def test_matrix_kernels_use_no_scratch_memory():
     """The matrix kernels as `make hip` compiles them: the pair runs out of line and returns its statistic in two registers, so no
     kernel of the matrix path may have a private segment or spill a vector register; there is one fill kernel; and the score, prune
     and clump kernels are still there under their names.  Only the kernels' metadata is read."""
-    out = str(tmp_path / "twk_hip.s")
-    make = open(os.path.join(ROOT, "Makefile")).read()
-    flags = re.search(r"^HIPFLAGS\s*:=\s*(.*)$", make, re.M).group(1).replace("$(ARCH)", "gfx950").split()
-    flags = [f for f in flags if f not in ("-fPIC",)]
-    r = subprocess.run([HIPCC] + flags + ["-Iinclude", "-S", "--cuda-device-only", "-o", out, "tomahawk_amd/csrc/hip/twk_hip.hip"],
-                       cwd=ROOT, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    asm = open(out).read()
     seen, others = [], set()
-    for name, body in re.findall(r"\.name:\s+(\S+)\n((?:(?!\s*\.name:).*\n)*)", asm):
+    for name, body in util.engine_kernels().items():
         for k in ("k_ld_score", "k_ld_prune", "k_ld_clump"):
             if k in name:
                 others.add(name)
         if "k_ld_matrix" not in name:
             continue
         seen.append(name)
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", body).group(1))
-        spills = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", body).group(1))
-        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", body).group(1))
+        vgprs, scratch, spills = util.kernel_resources(body)
         print(name, "vgprs", vgprs, "scratch", scratch, "spills", spills)
         assert scratch == 0 and spills == 0, (name, scratch, spills)
     assert sum("k_ld_matrix_fill" in n for n in seen) == 1 and sum("k_ld_matrix_diag" in n for n in seen) == 1 and len(seen) == 2, seen

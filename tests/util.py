@@ -6,7 +6,11 @@ import tomahawk_amd as T
 from tomahawk_amd.hip import META_DTYPE
 
 import collections as _collections
+import functools as _functools
 import os as _os
+import re as _re
+import subprocess as _subprocess
+import tempfile as _tempfile
 _STATS_PATH = _os.environ.get("TWK_PARITY_STATS", "")     # tests/sweeps: record the observed deviations
 
 # ---- bookkeeping of every exemption assert_records_match grants (reported at session end, tests/conftest.py) -------
@@ -594,3 +598,44 @@ def assert_records_match(gpu_recs, orc_recs, variants, n_samples=None, rtol=1e-6
         EXEMPTIONS.update(used)
         COMPARED.update({"records": len(want), "cubic": n_cubic, "calls": 1})
     return {"records": len(want), "cubic": n_cubic, **{k: v for k, v in used.items() if v}}
+
+
+# ---- the engine's device code as `make hip` compiles it ------------------------------------------------------------------------------------
+_REPO = _os.path.dirname(_os.path.dirname(_os.path.abspath(__file__)))
+HIPCC = _os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+@_functools.lru_cache(maxsize=None)
+def engine_assembly():
+    """The gfx950 assembly of csrc/hip/twk_hip.hip, compiled with the Makefile's HIPFLAGS: once per test session."""
+    make = open(_os.path.join(_REPO, "Makefile")).read()
+    flags = _re.search(r"^HIPFLAGS\s*:=\s*(.*)$", make, _re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    flags = [f for f in flags if f not in ("-fPIC",)]
+    with _tempfile.TemporaryDirectory() as tmp:
+        out = _os.path.join(tmp, "twk_hip.s")
+        r = _subprocess.run([HIPCC] + flags + ["-Iinclude", "-S", "--cuda-device-only", "-o", out, "tomahawk_amd/csrc/hip/twk_hip.hip"],
+                            cwd=_REPO, capture_output=True, text=True, timeout=900,
+                            env={k: v for k, v in _os.environ.items() if k not in ("LD_PRELOAD", "ASAN_OPTIONS", "UBSAN_OPTIONS")})
+        assert r.returncode == 0, r.stderr[-2000:]
+        return open(out).read()
+
+
+@_functools.lru_cache(maxsize=None)
+def engine_kernels():
+    """-> {kernel name: the body of its metadata entry behind the name} of engine_assembly()."""
+    return dict(_re.findall(r"\.name:\s+(\S+)\n((?:(?!\s*\.name:).*\n)*)", engine_assembly()))
+
+
+def kernel_resources(body):
+    """-> (VGPRs, bytes of private segment, spilled VGPRs) of one body of engine_kernels()."""
+    return tuple(int(_re.search(r"\.%s:\s+(\d+)" % k, body).group(1)) for k in ("vgpr_count", "private_segment_fixed_size", "vgpr_spill_count"))
+
+
+def reduce_kernels_fit(prefix):
+    """The engine's kernels whose name holds `prefix` have no private segment and spill no VGPR, and the one of them that is no "init"
+    is given at most 168 VGPRs (in granules of 8): the largest allocation of which a SIMD's 512 hold three.  -> their names"""
+    seen = {n: kernel_resources(b) for n, b in engine_kernels().items() if prefix in n}
+    assert all(scratch == 0 and spills == 0 for _, scratch, spills in seen.values()), seen
+    (vgprs, _, _), = (v for n, v in seen.items() if "init" not in n)
+    assert -(-vgprs // 8) * 8 <= 168, seen
+    return sorted(seen)

@@ -12,12 +12,12 @@
 //                   chosen statistic are used.  The shape is ld_reduce.hip.h's: 256 lanes = 256 columns, AGG_ROWS rows in a loop that
 //                   is not unrolled, the parameter block in device memory, the pair out of line, blocks below the diagonal skipped.
 // THE SUMS ARE EXACT AND HAVE NO ORDER.  A contribution adds the integers q = rint(v * 2^32) and q2 = rint((v * v) * 2^32)
-// (ld_aggregate_bin.h), and takes part in an integer minimum and maximum of q: integers add up and compare the same in any order, so two
+// (ld_exact_sum.h), and takes part in an integer minimum and maximum of q: integers add up and compare the same in any order, so two
 // runs, any tiling and any launch order return the same bits, and no floating-point atomic is used anywhere.
 //   in the wave  the row's variant is the same in all 64 lanes; lanes whose column variants share a packed key share both cells.
-//                While lanes are left: take the first one's key, ballot the lanes with that key, reduce their q, q2, minimum and maximum
-//                over the wave (butterflies over 64-bit integers; a key with one lane skips them), and the first lane adds the result
-//                and the ballot's popcount to both cells.  Right for any distribution of keys over the lanes.
+//                The lanes are grouped by key (d_key_groups, ld_reduce.hip.h): per key present their q, q2, minimum and maximum are
+//                reduced over the wave (d_wave_reduce over 64-bit integers; a key with one lane skips it), and the first lane adds the
+//                result and the ballot's popcount to both cells.  Right for any distribution of keys over the lanes.
 //   in the block two dense windows of cells in LDS, one per orientation, AGG_WIN_A bins of the row side by AGG_WIN_B bins of the column
 //                side, anchored at the bins of the block's first row and first column.  A contribution inside its window goes to LDS
 //                integer atomics (a uint32 count, 64-bit q and q2 sums, 64-bit minimum and maximum per cell); one outside goes straight
@@ -29,7 +29,7 @@
 // HEADROOM.  Let Q = 2^33 bound |q| and q2 (v is a correlation, a D or a D': |v| <= 1 up to rounding).  A window cell takes at most
 // one contribution a pair of the block and orientation, 8192: its count stays below 2^32 and its sums below 2^13 * Q = 2^46 in
 // magnitude.  A wave's group holds at most 64 contributions.  Every global add - a flush or a direct one - carries c >= 1
-// contributions with a partial sum |S| <= c * Q and adds, with k = AGG_SPLIT = 20,
+// contributions with a partial sum |S| <= c * Q and adds, with k = AGG_SPLIT = 20 (ld_exact_sum.h's split),
 //   lo = S & (2^k - 1) < 2^20           to an unsigned word: after T contributions to the cell at most T adds, less than T * 2^20;
 //   hi = S >> k (arithmetic), |hi| <= |S| / 2^k + 1 <= c * (2^13 + 1)
 //                                        to a signed word: after T contributions at most T * (2^13 + 1) in magnitude;
@@ -64,8 +64,7 @@ struct AggMap {
 	uint32_t x_bins, y_bins;
 	int32_t stat;                       // TWK_HIP_STAT_*
 };
-// The parameter block of an aggregate launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
-struct AggArgs { StatsParams p; AggMap am; };
+struct AggArgs : ReduceParams<AggMap> {};
 
 struct AggPair { long long q; unsigned long long q2; uint32_t key; };
 
@@ -80,46 +79,23 @@ __device__ __noinline__ AggPair d_agg_pair(const AggArgs* args, uint32_t i, uint
 	if (!d_pair<SRC_MATRIX>(p, sA, sB, i, j, 0, &rec)) return out;
 	// (keep implies both set positions below n_variants: the id is there)
 	const uint32_t B = p.tv.ids ? p.tv.ids[sB] : sB;
-	const uint32_t key = args->am.key[B];
+	const uint32_t key = args->m.key[B];
 	if (key == AGG_NO_KEY) return out;
-	double v;
-	switch (args->am.stat) {
-	case TWK_HIP_STAT_R:  v = copysign(rec.R, rec.D); break;
-	case TWK_HIP_STAT_R2: v = rec.R2; break;
-	case TWK_HIP_STAT_D:  v = rec.D; break;
-	default:              v = rec.Dprime; break;
-	}
-	out.q = ag_quantise(v);
-	out.q2 = ag_quantise_sq(v);
+	const double v = d_stat_value(rec, args->m.stat);
+	out.q = xs_quantise(v);
+	out.q2 = xs_quantise_sq(v);
 	out.key = key;
 	return out;
-}
-
-// The same value in every lane: sum, minimum, maximum over the wave's 64 lanes.
-__device__ __forceinline__ long long d_wave_sum_i64(long long x) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-	return x;
-}
-__device__ __forceinline__ long long d_wave_min_i64(long long x) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) { const long long y = __shfl_xor(x, m, 64); x = y < x ? y : x; }
-	return x;
-}
-__device__ __forceinline__ long long d_wave_max_i64(long long x) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) { const long long y = __shfl_xor(x, m, 64); x = y > x ? y : x; }
-	return x;
 }
 
 // A partial result of n contributions into the global accumulators of `cell` (< x_bins * y_bins: the entry point checked every bin).
 __device__ __forceinline__ void d_agg_global(const AggMap& am, uint32_t cell, uint32_t n, long long q, unsigned long long q2, long long mn, long long mx) {
 	unsigned long long* const w = am.acc + (size_t)cell * AGG_CELL_WORDS;
 	atomicAdd(w + AGG_W_N, (unsigned long long)n);
-	atomicAdd(w + AGG_W_Q_HI, (unsigned long long)ag_split_hi(q));      // (two's complement: the word is read as signed)
-	atomicAdd(w + AGG_W_Q_LO, ag_split_lo(q));
-	atomicAdd(w + AGG_W_Q2_HI, ag_split_hi_u(q2));
-	atomicAdd(w + AGG_W_Q2_LO, ag_split_lo_u(q2));
+	atomicAdd(w + AGG_W_Q_HI, (unsigned long long)xs_split_hi<AGG_SPLIT>(q));      // (two's complement: the word is read as signed)
+	atomicAdd(w + AGG_W_Q_LO, xs_split_lo<AGG_SPLIT>(q));
+	atomicAdd(w + AGG_W_Q2_HI, xs_split_hi_u<AGG_SPLIT>(q2));
+	atomicAdd(w + AGG_W_Q2_LO, xs_split_lo_u<AGG_SPLIT>(q2));
 	atomicMin(reinterpret_cast<long long*>(w + AGG_W_MIN), mn);
 	atomicMax(reinterpret_cast<long long*>(w + AGG_W_MAX), mx);
 }
@@ -151,13 +127,13 @@ __device__ __forceinline__ void d_agg_add(const AggMap& am, AggWindows& w, uint3
 __device__ __forceinline__ uint32_t d_agg_key_at(const AggArgs* args, uint32_t s) {
 	if (s >= args->p.n_variants) return AGG_NO_KEY;
 	const uint32_t* ids = args->p.tv.ids;
-	return args->am.key[ids ? ids[s] : s];
+	return args->m.key[ids ? ids[s] : s];
 }
 
 __global__ __launch_bounds__(AGG_THREADS)
 void k_ld_aggregate(const AggArgs* __restrict__ args) {
 	__shared__ AggWindows win;
-	const AggMap am = args->am;
+	const AggMap am = args->m;
 	const uint32_t nA = args->p.nA, nB = args->p.nB;
 	const uint32_t j = blockIdx.x * AGG_THREADS + threadIdx.x;
 	const uint32_t i0 = blockIdx.y * AGG_ROWS;
@@ -175,31 +151,25 @@ void k_ld_aggregate(const AggArgs* __restrict__ args) {
 		const uint32_t i = i0 + r;
 		AggPair pr{0ll, 0ull, AGG_NO_KEY};
 		if (i < nA && j < nB) pr = d_agg_pair(args, i, j);
-		// every lane stays in the loop (its condition is the wave's): the lanes of one key leave `todo` together
-		unsigned long long todo = __ballot(pr.key != AGG_NO_KEY);
+		const unsigned long long todo = __ballot(pr.key != AGG_NO_KEY);
 		if (!todo) continue;                                         // (uniform over the wave)
 		const uint32_t keyA = d_agg_key_at(args, args->p.tv.a0 + i);  // (the row's variant: the same in every lane)
 		const uint32_t xa = ag_x(keyA), ya = ag_y(keyA);
-		while (todo) {
-			const int first = __ffsll((long long)todo) - 1;
-			const uint32_t kb = (uint32_t)__builtin_amdgcn_readlane((int)pr.key, first);
-			const bool mine = pr.key == kb;                          // (a lane without a pair holds AGG_NO_KEY, which is no key)
-			const unsigned long long same = __ballot(mine);
+		d_key_groups(pr.key, todo, [&](int first, uint32_t kb, bool mine, unsigned long long same) {
 			long long q = mine ? pr.q : 0ll, mn = mine ? pr.q : AGG_I64_MAX, mx = mine ? pr.q : AGG_I64_MIN;
 			unsigned long long q2 = mine ? pr.q2 : 0ull;
 			if (same & (same - 1)) {                                 // (uniform: more than one lane with the key)
-				q = d_wave_sum_i64(q);
-				q2 = (unsigned long long)d_wave_sum_i64((long long)q2);
-				mn = d_wave_min_i64(mn);
-				mx = d_wave_max_i64(mx);
+				q = d_wave_reduce(q, WaveSum());
+				q2 = d_wave_reduce(q2, WaveSum());
+				mn = d_wave_reduce(mn, WaveMin());
+				mx = d_wave_reduce(mx, WaveMax());
 			}
 			if (lane == first) {
 				const uint32_t n = (uint32_t)__popcll(same), xb = ag_x(kb), yb = ag_y(kb);
 				if (xa != AGG_OFF && yb != AGG_OFF) d_agg_add(am, win, 0, xa - ax0, yb - by0, xa * am.y_bins + yb, n, q, q2, mn, mx);
 				if (xb != AGG_OFF && ya != AGG_OFF) d_agg_add(am, win, 1, ya - ay0, xb - bx0, xb * am.y_bins + ya, n, q, q2, mn, mx);
 			}
-			todo &= ~same;
-		}
+		});
 	}
 	__syncthreads();
 	// (a touched window cell was reached from its anchors by valid bins: its cell exists)

@@ -49,12 +49,11 @@ constexpr int CLUMP_WALK_THREADS = 1024;
 constexpr uint32_t CLUMP_LDS_WORDS = WALK_LDS_WORDS;      // `taken` in LDS: up to 520,192 variants, as prune's `removed`
 constexpr uint32_t CLUMP_NONE = 0xFFFFFFFFu;              // TWK_HIP_NO_CLUMP
 
-// The parameter block of a mask launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).  The map is prune's.
-struct ClumpArgs { StatsParams p; PruneMap pm; };
+struct ClumpArgs : ReduceParams<PruneMap> {};      // (the map is prune's)
 
 __global__ __launch_bounds__(CLUMP_THREADS)
 void k_ld_clump_mask(const ClumpArgs* __restrict__ args) {
-	const PruneMap pm = args->pm;
+	const PruneMap pm = args->m;
 	const uint32_t nA = args->p.nA, nB = args->p.nB;
 	const uint32_t a0 = args->p.tv.a0, b0 = args->p.tv.b0;
 	const uint32_t* ids = args->p.tv.ids;

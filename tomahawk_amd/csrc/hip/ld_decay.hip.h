@@ -9,17 +9,17 @@
 //                used; positions and contigs are p.vm.pos / p.vm.rid of the two variant ids, as d_pair resolves them.  The shape is
 //                ld_reduce.hip.h's: 256 lanes = 256 columns, DECAY_ROWS rows in a loop that is not unrolled, the parameter block in
 //                device memory, the pair out of line, blocks below the diagonal skipped.
-// THE SUMS ARE EXACT AND HAVE NO ORDER.  A counting pair adds the integer q = rint(R2 * 2^32) (ld_decay_bin.h: one rounding, at most
+// THE SUMS ARE EXACT AND HAVE NO ORDER.  A counting pair adds the integer q = rint(R2 * 2^32) (ld_exact_sum.h: one rounding, at most
 // 2^-33 from R2), and integers add up the same in any order: two runs, any tiling and any launch order return the same bits, and no
 // floating-point atomic is used anywhere.
-//   in the wave  adjacent columns of a row mostly share a bin, so 64 lanes adding to one LDS word would serialise.  While lanes are
-//                left: take the first one's bin, ballot the lanes with that bin, add up their q over the wave (a butterfly over
+//   in the wave  adjacent columns of a row mostly share a bin, so 64 lanes adding to one LDS word would serialise.  The lanes are
+//                grouped by bin (d_key_groups, ld_reduce.hip.h): per bin present their q are added up over the wave (d_wave_reduce over
 //                64-bit integers; a bin with one lane skips it), and the first lane adds the sum and the ballot's popcount to the
 //                block's histogram.  Right for any distribution of bins over the lanes: a regrouped set is not in position order.
 //   in the block the histogram lives in dynamic LDS - a uint64 sum and a uint32 count per bin, 12 bytes x n_bins, n_bins <= 4096
 //                (48 KiB) - zeroed at block start, added to with LDS integer atomics (the block's four waves share it).
-//   at the end   for every bin the block counted a pair in, three global 64-bit integer atomic adds: S >> 32 into acc_int[bin],
-//                S & 0xffffffff into acc_frac[bin], the count into acc_n[bin].  No carry between the words and no branch on the data:
+//   at the end   for every bin the block counted a pair in, three global 64-bit integer atomic adds, with K = DECAY_SPLIT = 32
+//                (ld_exact_sum.h's split): S >> 32 into acc_int[bin], S & 0xffffffff into acc_frac[bin], the count into acc_n[bin].  No carry between the words and no branch on the data:
 //                every path runs on every input.  The host forms (acc_int << 32) + acc_frac in 128 bits and converts once.
 // HEADROOM.  A block holds DECAY_THREADS * DECAY_ROWS = 8192 pairs and q <= 2^32 (+ a few ulps of R2), so a block's S < 2^46.
 // acc_frac takes less than 2^32 a flush: room for 2^32 flushes a bin; acc_int takes S >> 32 < 2^14 a flush and less than one a
@@ -46,8 +46,7 @@ struct DecayMap {
 	unsigned long long* acc_n;          // [n_bins] counting pairs
 	uint32_t width, n_bins;
 };
-// The parameter block of a decay launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
-struct DecayArgs { StatsParams p; DecayMap dm; };
+struct DecayArgs : ReduceParams<DecayMap> {};
 // LDS of a block: the sums, then the counts.
 inline size_t decay_lds_bytes(uint32_t n_bins) { return (size_t)n_bins * (sizeof(unsigned long long) + sizeof(uint32_t)); }
 
@@ -65,22 +64,15 @@ __device__ __noinline__ DecayPair d_decay_pair(const DecayArgs* args, uint32_t i
 	const uint32_t A = p.tv.ids ? p.tv.ids[sA] : sA, B = p.tv.ids ? p.tv.ids[sB] : sB;
 	const uint32_t pa = p.vm.pos[A], pb = p.vm.pos[B];
 	if (p.vm.rid[A] != p.vm.rid[B] || pa == pb) return out;
-	out.bin = dk_bin(dk_distance(pa, pb), args->dm.width, args->dm.n_bins);
-	out.q = dk_quantise(rec.R2);
+	out.bin = dk_bin(dk_distance(pa, pb), args->m.width, args->m.n_bins);
+	out.q = (unsigned long long)xs_quantise(rec.R2);
 	return out;
-}
-
-// Sum over the wave's 64 lanes, the same value in every lane.
-__device__ __forceinline__ unsigned long long d_wave_sum_u64(unsigned long long x) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-	return x;
 }
 
 __global__ __launch_bounds__(DECAY_THREADS)
 void k_ld_decay(const DecayArgs* __restrict__ args) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char decay_lds[];
-	const DecayMap dm = args->dm;
+	const DecayMap dm = args->m;
 	unsigned long long* const h_sum = reinterpret_cast<unsigned long long*>(decay_lds);
 	uint32_t* const h_n = reinterpret_cast<uint32_t*>(h_sum + dm.n_bins);
 	const uint32_t nA = args->p.nA, nB = args->p.nB;
@@ -95,29 +87,22 @@ void k_ld_decay(const DecayArgs* __restrict__ args) {
 		const uint32_t i = i0 + r;
 		DecayPair pr{0ull, DECAY_NO_BIN};
 		if (i < nA && j < nB) pr = d_decay_pair(args, i, j);
-		// every lane stays in the loop (its condition is the wave's): the lanes of one bin leave `todo` together
-		unsigned long long todo = __ballot(pr.bin != DECAY_NO_BIN);
-		while (todo) {
-			const int first = __ffsll((long long)todo) - 1;
-			const uint32_t bin = (uint32_t)__builtin_amdgcn_readlane((int)pr.bin, first);
-			const bool mine = pr.bin == bin;                     // (a lane without a pair holds DECAY_NO_BIN, which is no bin)
-			const unsigned long long same = __ballot(mine);
+		d_key_groups(pr.bin, DECAY_NO_BIN, [&](int first, uint32_t bin, bool mine, unsigned long long same) {
 			unsigned long long s = mine ? pr.q : 0ull;
-			if (same & (same - 1)) s = d_wave_sum_u64(s);        // (uniform: more than one lane in the bin)
+			if (same & (same - 1)) s = d_wave_reduce(s, WaveSum());      // (uniform: more than one lane in the bin)
 			if (lane == first) {
 				atomicAdd(h_sum + bin, s);
 				atomicAdd(h_n + bin, (uint32_t)__popcll(same));
 			}
-			todo &= ~same;
-		}
+		});
 	}
 	__syncthreads();
 	for (uint32_t b = threadIdx.x; b < dm.n_bins; b += DECAY_THREADS) {
 		const uint32_t n = h_n[b];
 		if (!n) continue;
 		const unsigned long long s = h_sum[b];
-		atomicAdd(dm.acc_int + b, s >> 32);
-		atomicAdd(dm.acc_frac + b, s & 0xFFFFFFFFull);
+		atomicAdd(dm.acc_int + b, xs_split_hi_u<DECAY_SPLIT>(s));
+		atomicAdd(dm.acc_frac + b, xs_split_lo_u<DECAY_SPLIT>(s));
 		atomicAdd(dm.acc_n + b, (unsigned long long)n);
 	}
 }

@@ -41,8 +41,7 @@ struct MatrixMap {
 	uint32_t a0, n;                     // the triangle's first variant, its size
 	int32_t stat;                       // TWK_HIP_STAT_*
 };
-// The parameter block of a fill launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
-struct MatrixArgs { StatsParams p; MatrixMap mm; };
+struct MatrixArgs : ReduceParams<MatrixMap> {};
 
 // One pair of the launch's matrix: bit 32 set if `calc` would report it, and then its statistic as a float32 in the low word (the
 // double rounded once, to nearest).  Out of line, so that the registers of the two maths are the callee's and not held across the
@@ -51,21 +50,14 @@ __device__ __noinline__ unsigned long long d_matrix_pair(const MatrixArgs* args,
 	const StatsParams& p = args->p;
 	twk_hip_record rec;
 	if (!d_pair<SRC_MATRIX>(p, p.tv.a0 + i, p.tv.b0 + j, i, j, 0, &rec)) return 0ull;
-	double x;
-	switch (args->mm.stat) {
-	case TWK_HIP_STAT_R:  x = copysign(rec.R, rec.D); break;
-	case TWK_HIP_STAT_R2: x = rec.R2; break;
-	case TWK_HIP_STAT_D:  x = rec.D; break;
-	default:              x = rec.Dprime; break;
-	}
-	return 1ull << 32 | (unsigned long long)__float_as_uint((float)x);
+	return 1ull << 32 | (unsigned long long)__float_as_uint((float)d_stat_value(rec, args->m.stat));
 }
 
 __global__ __launch_bounds__(MATRIX_THREADS)
 void k_ld_matrix_fill(const MatrixArgs* __restrict__ args) {
 	__shared__ float stage[MX_STAGE_WORDS];
 	__shared__ uint32_t kept[MX_COLS];
-	const MatrixMap mm = args->mm;
+	const MatrixMap mm = args->m;
 	const uint32_t nA = args->p.nA, nB = args->p.nB;
 	const uint32_t a0 = args->p.tv.a0, b0 = args->p.tv.b0;
 	const uint32_t* ids = args->p.tv.ids;

@@ -41,12 +41,11 @@ struct PruneMap {
 	unsigned long long* n_edges;
 	uint32_t a0, n, stride;             // the triangle's first variant, its size, words per row
 };
-// The parameter block of a mask launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
-struct PruneArgs { StatsParams p; PruneMap pm; };
+struct PruneArgs : ReduceParams<PruneMap> {};
 
 __global__ __launch_bounds__(PRUNE_THREADS)
 void k_ld_prune_mask(const PruneArgs* __restrict__ args) {
-	const PruneMap pm = args->pm;
+	const PruneMap pm = args->m;
 	const uint32_t nA = args->p.nA, nB = args->p.nB;
 	const uint32_t a0 = args->p.tv.a0, b0 = args->p.tv.b0;
 	const uint32_t* ids = args->p.tv.ids;

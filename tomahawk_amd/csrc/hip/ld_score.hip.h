@@ -31,15 +31,7 @@ struct ScoreParts {
 	double* col_sum; uint32_t* col_n;   // [gy][nB]: column j's partial from row block by at by * nB + j
 	uint32_t gx, gy;
 };
-// The parameter block of a score launch, in device memory (read inside the row loop: ld_reduce.hip.h on why).
-struct ScoreArgs { StatsParams p; ScoreParts sp; };
-
-// Sum over the wave's 64 lanes, the same value in every lane: a butterfly whose pairing does not depend on the data.
-__device__ __forceinline__ double d_wave_sum(double x) {
-#pragma unroll
-	for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);
-	return x;
-}
+struct ScoreArgs : ReduceParams<ScoreParts> {};
 
 // One pair of the launch's matrix: its r2 if `calc` would report it, a negative number if not.  Out of line, so that the registers of
 // the two maths are the callee's and not held across the row loop (inlined into it the kernel needs 191 VGPRs: two waves a SIMD).
@@ -53,7 +45,7 @@ __global__ __launch_bounds__(SCORE_THREADS)
 void k_ld_score(const ScoreArgs* __restrict__ args) {
 	__shared__ double wave_sum[SCORE_ROWS][SCORE_THREADS / 64];
 	__shared__ uint32_t wave_n[SCORE_ROWS][SCORE_THREADS / 64];
-	const ScoreParts sp = args->sp;
+	const ScoreParts sp = args->m;
 	const uint32_t nA = args->p.nA, nB = args->p.nB;
 	const uint32_t j = blockIdx.x * SCORE_THREADS + threadIdx.x;
 	const uint32_t i0 = blockIdx.y * SCORE_ROWS;
@@ -69,7 +61,7 @@ void k_ld_score(const ScoreArgs* __restrict__ args) {
 		if (!keep) r2 = 0.0;
 		csum += r2; cn += keep ? 1u : 0u;
 		const unsigned long long ballot = __ballot(keep);
-		const double ws = ballot ? d_wave_sum(r2) : 0.0;      // (uniform over the wave)
+		const double ws = ballot ? d_wave_reduce(r2, WaveSum()) : 0.0;      // (uniform over the wave)
 		if (lane == 0) { wave_sum[r][wave] = ws; wave_n[r][wave] = (uint32_t)__popcll(ballot); }
 	}
 	if (j < nB) {

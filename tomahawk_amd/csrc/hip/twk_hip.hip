@@ -131,6 +131,12 @@ struct LaunchForm {
 	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
+// What the running call of one of them sets, for its length: ~ReduceCall puts a default-constructed one back.
+struct ReduceState {
+	Reduce kind = Reduce::none;
+	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; } map{};      // where the running kind's launches put their results (prune and clump: bits)
+	uint64_t work = 0;                            // what the call's launches used up of the room of the kind's accumulators (launch_reduce holds it to the kind's limit)
+};
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
 struct Launch {
@@ -301,29 +307,20 @@ struct twk_hip_ctx {
 	DevBuf<int> d_status;
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
 	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
-	Reduce reduce = Reduce::none;                                                // which way, for the length of the call (ReduceCall)
+	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
 	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
 	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last)
 	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
 	// score: sums of r2 per variant (ld_score.hip.h)
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
-	// prune and clump: `keep` balloted into the adjacency bitmap of the call's triangle (ld_prune.hip.h; clump from both ends of a pair, ld_clump.hip.h)
-	PruneMap map{};
-	DevBuf<unsigned long long> d_adj, d_walk;                                    // the bitmap (lives for the call); prune's `removed` beyond LDS, clump's taken0 / `taken`
+	// prune and clump: what their walks over the call's adjacency bitmap read and write (ld_prune.hip.h, ld_clump.hip.h; the bitmap is the ReduceCall's)
+	DevBuf<unsigned long long> d_walk;                                           // prune's `removed` beyond LDS, clump's taken0 / `taken`
 	DevBuf<uint8_t> d_prune_keep;                                                // [M]
 	DevBuf<uint32_t> d_clump_order, d_clump_index;                               // the candidates in visiting order; index_of [M]
-	// matrix: one statistic per record stored into the call's dense matrix (ld_matrix.hip.h)
-	MatrixMap matrix_map{};
-	DevBuf<float> d_matrix;                                                      // the n x n matrix (lives for the call)
 	// decay: exact sums of quantised r2 and counts per distance bin (ld_decay.hip.h)
-	DecayMap decay_map{};
 	DevBuf<unsigned long long> d_decay;                                          // [3][n_bins] accumulators: acc_int, acc_frac, acc_n
-	uint64_t decay_blocks = 0;                                                   // blocks launched for the running call: each flushes a bin at most once
-	// aggregate: exact sums, counts and extremes per cell of an x-by-y landscape (ld_aggregate.hip.h)
-	AggMap agg_map{};
-	DevBuf<uint32_t> d_agg_key;                                                  // [M] the two bins of every variant, packed
-	DevBuf<unsigned long long> d_agg;                                            // [x_bins * y_bins][AGG_CELL_WORDS] accumulators (lives for the call)
-	uint64_t agg_slots = 0;                                                      // pairs the running call's launches can evaluate: two contributions each
+	// aggregate: the two bins of every variant, packed (ld_aggregate.hip.h; the cells' accumulators are the ReduceCall's)
+	DevBuf<uint32_t> d_agg_key;                                                  // [M]
 	char err[512] = {0};
 };
 
@@ -363,8 +360,8 @@ void free_problem(twk_hip_ctx* c) {
 	c->raw.reset(); c->rawmask.reset(); c->d_lfact.reset(); c->lfact_n = 0;
 	c->d_ac.reset(); c->d_an.reset(); c->d_pos.reset(); c->d_rid.reset(); c->d_missing.reset(); c->d_hwe.reset();
 	c->d_score_sum.reset(); c->d_score_n.reset();
-	c->d_counts.reset(); c->d_adj.reset(); c->d_walk.reset(); c->d_prune_keep.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
-	c->d_matrix.reset(); c->d_decay.reset(); c->d_agg_key.reset(); c->d_agg.reset();
+	c->d_counts.reset(); c->d_walk.reset(); c->d_prune_keep.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
+	c->d_decay.reset(); c->d_agg_key.reset();
 	c->h_meta.clear();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
 }
@@ -796,7 +793,7 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 // reports why).
 LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
 	LaunchForm lf;
-	lf.two_pass = pl.set2 >= 0; lf.reduce = c->reduce; lf.keep_three = c->opt.three == 2;
+	lf.two_pass = pl.set2 >= 0; lf.reduce = c->reduce.kind; lf.keep_three = c->opt.three == 2;
 	const int k = set_kind(pl.set1);
 	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
 	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
@@ -849,23 +846,26 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	if (!t.nA || !t.nB) return TWK_HIP_OK;
 	HIPCHK(c, s.h_args.reserve(2, 2, nullptr));
 	HIPCHK(c, s.d_args.reserve(2, 2, nullptr));
+	ReduceState& rs = c->reduce;
+	// the launch's share of the accumulators' proven room: decay's blocks (ld_decay.hip.h), the pairs an aggregate launch can evaluate (ld_aggregate.hip.h)
+	const bool square_diag = t.diag && t.rowA0 == t.rowB0 && t.nA == t.nB;
+	uint64_t limit = ~0ull; const char* over = "";
 	switch (s.l.form.reduce) {
-	case Reduce::prune:  return run_reduce_kernel(c, t, s, which, k_ld_prune_mask, PRUNE_THREADS, PRUNE_ROWS, PruneArgs{p, c->map});
-	case Reduce::clump:  return run_reduce_kernel(c, t, s, which, k_ld_clump_mask, CLUMP_THREADS, CLUMP_ROWS, ClumpArgs{p, c->map});
-	case Reduce::matrix: return run_reduce_kernel(c, t, s, which, k_ld_matrix_fill, MATRIX_THREADS, MATRIX_ROWS, MatrixArgs{p, c->matrix_map});
-	case Reduce::decay: {
-		// a block adds less than 2^32 to a bin's acc_frac, once: 2^32 blocks a call are its room (ld_decay.hip.h)
-		c->decay_blocks += (uint64_t)((t.nB + DECAY_THREADS - 1) / DECAY_THREADS) * ((t.nA + DECAY_ROWS - 1) / DECAY_ROWS);
-		if (c->decay_blocks > 0xFFFFFFFFull) { snprintf(c->err, sizeof(c->err), "LD decay: more than 2^32 blocks in one call; split it into shards"); return TWK_HIP_E_INVALID; }
-		return run_reduce_kernel(c, t, s, which, k_ld_decay, DECAY_THREADS, DECAY_ROWS, DecayArgs{p, c->decay_map}, decay_lds_bytes(c->decay_map.n_bins));
+	case Reduce::decay:
+		rs.work += (uint64_t)((t.nB + DECAY_THREADS - 1) / DECAY_THREADS) * ((t.nA + DECAY_ROWS - 1) / DECAY_ROWS);
+		limit = 0xFFFFFFFFull; over = "LD decay: more than 2^32 blocks in one call; split it into shards"; break;
+	case Reduce::aggregate:
+		rs.work += square_diag ? (uint64_t)t.nA * (t.nA - 1) / 2 : (uint64_t)t.nA * t.nB;
+		limit = 1ull << 42; over = "LD aggregate: more than 2^42 pairs in one call; split it into shards"; break;
+	default: break;
 	}
-	case Reduce::aggregate: {
-		// two contributions a pair and 2^43 of them to one cell are the accumulators' proven room (ld_aggregate.hip.h)
-		const bool square_diag = t.diag && t.rowA0 == t.rowB0 && t.nA == t.nB;
-		c->agg_slots += square_diag ? (uint64_t)t.nA * (t.nA - 1) / 2 : (uint64_t)t.nA * t.nB;
-		if (c->agg_slots > 1ull << 42) { snprintf(c->err, sizeof(c->err), "LD aggregate: more than 2^42 pairs in one call; split it into shards"); return TWK_HIP_E_INVALID; }
-		return run_reduce_kernel(c, t, s, which, k_ld_aggregate, AGG_THREADS, AGG_ROWS, AggArgs{p, c->agg_map});
-	}
+	if (rs.work > limit) { snprintf(c->err, sizeof(c->err), "%s", over); return TWK_HIP_E_INVALID; }
+	switch (s.l.form.reduce) {
+	case Reduce::prune:     return run_reduce_kernel(c, t, s, which, k_ld_prune_mask, PRUNE_THREADS, PRUNE_ROWS, PruneArgs{{p, rs.map.bits}});
+	case Reduce::clump:     return run_reduce_kernel(c, t, s, which, k_ld_clump_mask, CLUMP_THREADS, CLUMP_ROWS, ClumpArgs{{p, rs.map.bits}});
+	case Reduce::matrix:    return run_reduce_kernel(c, t, s, which, k_ld_matrix_fill, MATRIX_THREADS, MATRIX_ROWS, MatrixArgs{{p, rs.map.matrix}});
+	case Reduce::decay:     return run_reduce_kernel(c, t, s, which, k_ld_decay, DECAY_THREADS, DECAY_ROWS, DecayArgs{{p, rs.map.decay}}, decay_lds_bytes(rs.map.decay.n_bins));
+	case Reduce::aggregate: return run_reduce_kernel(c, t, s, which, k_ld_aggregate, AGG_THREADS, AGG_ROWS, AggArgs{{p, rs.map.agg}});
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -878,7 +878,7 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	HIPCHK(c, reserve_together(need, need, &c->graveyard, s.sc_sum, s.sc_n));
 	sp.row_sum = s.sc_sum; sp.row_n = s.sc_n; sp.col_sum = s.sc_sum + n_row; sp.col_n = s.sc_n + n_row;
 	const uint32_t* ids = c->planes[set].ids;
-	const int rc = run_reduce_kernel(c, t, s, which, k_ld_score, SCORE_THREADS, SCORE_ROWS, ScoreArgs{p, sp}); if (rc) return rc;
+	const int rc = run_reduce_kernel(c, t, s, which, k_ld_score, SCORE_THREADS, SCORE_ROWS, ScoreArgs{{p, sp}}); if (rc) return rc;
 	hipLaunchKernelGGL(k_ld_score_fold, dim3((t.nA + 255) / 256), dim3(256), 0, c->s_compute, (const double*)sp.row_sum, (const uint32_t*)sp.row_n, t.nA, sp.gx,
 	                   (size_t)sp.gx, (size_t)1, t.rowA0, ids, c->M, c->d_score_sum, c->d_score_n);
 	hipLaunchKernelGGL(k_ld_score_fold, dim3((t.nB + 255) / 256), dim3(256), 0, c->s_compute, (const double*)sp.col_sum, (const uint32_t*)sp.col_n, t.nB, sp.gy,
@@ -2243,7 +2243,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = c->three_ok = c->reduce == Reduce::none;      // a score, a prune, a clump, a matrix, a decay or an aggregate looks at every pair: no screen in front of the count matrix
+	c->fused_ok = c->three_ok = c->reduce.kind == Reduce::none;      // a score, a prune, a clump, a matrix, a decay or an aggregate looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2321,11 +2321,13 @@ extern "C++" {      // (member templates)
 namespace {
 // One call of twk_hip_ld_score, _prune, _clump, _matrix, _decay or _aggregate: the region call's planner and launch pipeline with the kind's epilogue in place of
 // math, Fisher, sort and delivery (launch_reduce).  Constructed at the top of the entry point, which returns `bad` if the shared checks found
-// something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the buffer
-// that lived for the call released, the graveyard flushed.
+// something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the
+// graveyard flushed - and the buffer that lived for the call, a member, is released behind it.
 struct ReduceCall {
 	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
 	int bad;
+	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells.  Freed behind the destructor's body, which waits for the device.
+	DevBuf<unsigned long long> d_adj, d_agg; DevBuf<float> d_matrix;
 	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
 	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
 		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
@@ -2339,10 +2341,8 @@ struct ReduceCall {
 	}
 	~ReduceCall() {
 		if (bad) return;
-		c->reduce = Reduce::none; c->map = PruneMap{}; c->matrix_map = MatrixMap{}; c->decay_map = DecayMap{}; c->decay_blocks = 0;
-		c->agg_map = AggMap{}; c->agg_slots = 0;
+		c->reduce = ReduceState();
 		(void)hipDeviceSynchronize();
-		c->d_adj.reset(); c->d_matrix.reset(); c->d_agg.reset();      // what lived for the call (hold)
 		flush_graveyard(c);                 // buffers outgrown during the call: nothing is in flight any more
 	}
 	// The buffer that lives as long as the call - gigabytes that a record run behind this call may need, so it goes back when the call ends,
@@ -2365,23 +2365,32 @@ struct ReduceCall {
 	int bitmap(uint32_t a0, uint32_t n, const char* what) {
 		const uint32_t stride = (n + 63) / 64;
 		const size_t words = (size_t)n * stride;
-		const int rc = hold(c->d_adj, words, what, n); if (rc) return rc;
-		HIPCHK(c, hipMemsetAsync(c->d_adj, 0, words * sizeof(unsigned long long), c->s_compute));
-		c->map = PruneMap{c->d_adj, c->d_counts, a0, n, stride};
+		const int rc = hold(d_adj, words, what, n); if (rc) return rc;
+		HIPCHK(c, hipMemsetAsync(d_adj, 0, words * sizeof(unsigned long long), c->s_compute));
+		c->reduce.map.bits = PruneMap{d_adj, c->d_counts, a0, n, stride};
 		arm(words * sizeof(unsigned long long));
 		return TWK_HIP_OK;
 	}
 	// From here on the call's launches take the kind's epilogue.  bytes: what twk_hip_*_last reports of this call.
-	void arm(uint64_t bytes) { c->reduce_last[(int)kind].ms = 0; c->reduce_last[(int)kind].bytes = bytes; c->reduce = kind; }
-	// (the r2 band and the carrier-list zones exist to avoid looking at pairs: never for a reduce call)
-	int dispatch(RegionArgs a) {
-		a.window &= ~(int32_t)TWK_HIP_OPT_R2_SCREEN;
-		return region_dispatch(c, a);
+	void arm(uint64_t bytes) { c->reduce_last[(int)kind].ms = 0; c->reduce_last[(int)kind].bytes = bytes; c->reduce.work = 0; c->reduce.kind = kind; }
+	// The region call's geometry.  (The r2 band and the carrier-list zones exist to avoid looking at pairs: never for a reduce call.)
+	int dispatch(int mode, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts, uint32_t tile_variants,
+	             int32_t window, uint32_t l_window, uint64_t* n_pairs) {
+		window &= ~(int32_t)TWK_HIP_OPT_R2_SCREEN;
+		return region_dispatch(c, RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
 	}
 	// ... over the triangle of the slice [a0, a0 + n).  A single variant has no pair.
 	int dispatch(int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window, uint64_t* n_pairs) {
 		if (n < 2) { if (n_pairs) *n_pairs = 0; return TWK_HIP_OK; }
-		return dispatch(RegionArgs{mode, f, a0, n, a0, n, 1, 0, 1, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+		return dispatch(mode, a0, n, a0, n, 1, 0, 1, tile_variants, window, l_window, n_pairs);
+	}
+	// Behind the last launch: the device-to-host copies `copies` enqueues and one wait for the stream, or "<what>: <the runtime's reason>".
+	template <class Copies>
+	int download(const char* what, Copies&& copies) {
+		hipError_t e = copies();
+		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
+		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
+		return TWK_HIP_OK;
 	}
 	// What follows the call's last launch on its stream: `timed` between two events - their distance is the call's `ms` of twk_hip_*_last -
 	// then `rest`, then one wait for the stream.  Both enqueue and return the runtime's verdict.
@@ -2401,6 +2410,8 @@ struct ReduceCall {
 		return TWK_HIP_OK;
 	}
 };
+
+bool valid_stat(int32_t stat) { return stat == TWK_HIP_STAT_R || stat == TWK_HIP_STAT_R2 || stat == TWK_HIP_STAT_D || stat == TWK_HIP_STAT_DPRIME; }
 
 int last_of(const twk_hip_ctx* c, Reduce kind, double* ms, uint64_t* bytes) {
 	if (!c) return TWK_HIP_E_INVALID;
@@ -2424,13 +2435,12 @@ int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	HIPCHK(c, hipMemsetAsync(c->d_score_sum, 0, M * sizeof(double), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(c->d_score_n, 0, M * sizeof(unsigned long long), c->s_compute));
 	call.arm(0);
-	const int rc = call.dispatch(RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	const int rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
 	if (rc) return rc;
-	hipError_t e = hipMemcpyAsync(sum_r2, c->d_score_sum, M * sizeof(double), hipMemcpyDeviceToHost, c->s_compute);
-	if (e == hipSuccess) e = hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
-	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-	if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "score arrays: %s", hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
-	return TWK_HIP_OK;
+	return call.download("score arrays", [&] {
+		const hipError_t e = hipMemcpyAsync(sum_r2, c->d_score_sum, M * sizeof(double), hipMemcpyDeviceToHost, c->s_compute);
+		return e != hipSuccess ? e : hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+	});
 }
 
 // LD pruning: the greedy walk over the bitmap the launches filled.
@@ -2449,7 +2459,7 @@ int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
 	unsigned long long counts[2] = {0, 0};
 	rc = call.tail("prune walk", [&] {
-		hipLaunchKernelGGL(in_lds ? k_ld_prune_walk<true> : k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_adj,
+		hipLaunchKernelGGL(in_lds ? k_ld_prune_walk<true> : k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)call.d_adj,
 		                   a0, n, stride, in_lds ? nullptr : c->d_walk.get(), c->d_prune_keep.get(), c->d_counts + 1);
 		return hipGetLastError();
 	}, [&] {
@@ -2499,7 +2509,7 @@ int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
 	unsigned long long counts[3] = {0, 0, 0};
 	rc = call.tail("clump walk", [&] {
-		hipLaunchKernelGGL(in_lds ? k_ld_clump_walk<true> : k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->d_adj,
+		hipLaunchKernelGGL(in_lds ? k_ld_clump_walk<true> : k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)call.d_adj,
 		                   a0, n, stride, (const uint32_t*)c->d_clump_order, m, c->d_walk.get(), c->d_clump_index.get(), c->d_counts + 1);
 		return hipGetLastError();
 	}, [&] {
@@ -2519,25 +2529,24 @@ int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_b
 // copy that honours the caller's row pitch.
 int twk_hip_ld_matrix(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
                       int32_t stat, float fill, float* out, uint64_t ld, uint64_t* n_records, uint64_t* n_pairs) {
-	const bool stat_ok = stat == TWK_HIP_STAT_R || stat == TWK_HIP_STAT_R2 || stat == TWK_HIP_STAT_D || stat == TWK_HIP_STAT_DPRIME;
-	ReduceCall call(c, Reduce::matrix, f, out && stat_ok, mode, a0, n);
+	ReduceCall call(c, Reduce::matrix, f, out && valid_stat(stat), mode, a0, n);
 	if (call.bad) return call.bad;
 	if (ld < n) return TWK_HIP_E_INVALID;
 	const size_t cells = (size_t)n * n;
 	// the dense matrix: n * n floats, whatever the window
-	int rc = call.hold(c->d_matrix, cells, "the LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	int rc = call.hold(call.d_matrix, cells, "the LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
 	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
-	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_matrix.get(), (int)fill_bits, cells, c->s_compute));
-	c->matrix_map = MatrixMap{c->d_matrix, c->d_counts, a0, n, stat};
+	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)call.d_matrix.get(), (int)fill_bits, cells, c->s_compute));
+	c->reduce.map.matrix = MatrixMap{call.d_matrix, c->d_counts, a0, n, stat};
 	call.arm(cells * sizeof(float));
 	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
 	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
-		hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, c->d_matrix.get(), n, 1.0f);
+		hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, call.d_matrix.get(), n, 1.0f);
 		HIPCHK(c, hipGetLastError());
 	}
 	unsigned long long count = 0;
 	rc = call.tail("LD matrix", [&] {
-		return hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), c->d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
+		return hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), call.d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
 	}, [&] { return hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute); });
 	if (rc) return rc;
 	if (n_records) *n_records = count;
@@ -2556,17 +2565,15 @@ int twk_hip_ld_decay(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	const size_t B = n_bins;
 	HIPCHK(c, c->d_decay.reserve(3 * B, 3 * B, nullptr));
 	HIPCHK(c, hipMemsetAsync(c->d_decay, 0, 3 * B * sizeof(unsigned long long), c->s_compute));
-	c->decay_map = DecayMap{c->d_decay, c->d_decay + B, c->d_decay + 2 * B, dk_width(range_bp, n_bins), n_bins};
-	c->decay_blocks = 0;
+	c->reduce.map.decay = DecayMap{c->d_decay, c->d_decay + B, c->d_decay + 2 * B, dk_width(range_bp, n_bins), n_bins};
 	call.arm(3 * B * sizeof(unsigned long long));
-	const int rc = call.dispatch(RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	int rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
 	if (rc) return rc;
 	std::vector<unsigned long long> acc(3 * B);
-	hipError_t e = hipMemcpyAsync(acc.data(), c->d_decay, 3 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
-	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-	if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "decay arrays: %s", hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
+	rc = call.download("decay arrays", [&] { return hipMemcpyAsync(acc.data(), c->d_decay, 3 * B * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute); });
+	if (rc) return rc;
 	for (size_t b = 0; b < B; ++b) {
-		sum_r2[b] = dk_sum_to_double(acc[b], acc[B + b]);      // (exact in 128 bits, one conversion: ld_decay_bin.h)
+		sum_r2[b] = xs_sum_to_double_unsigned<DECAY_SPLIT>(acc[b], acc[B + b]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
 		n[b] = acc[2 * B + b];
 	}
 	return TWK_HIP_OK;
@@ -2578,9 +2585,8 @@ int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uin
                          uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
                          int32_t stat, const uint16_t* bin_x, const uint16_t* bin_y, uint32_t x_bins, uint32_t y_bins,
                          uint64_t* n, double* sum, double* sum_sq, double* min, double* max, uint64_t* n_pairs) {
-	const bool stat_ok = stat == TWK_HIP_STAT_R || stat == TWK_HIP_STAT_R2 || stat == TWK_HIP_STAT_D || stat == TWK_HIP_STAT_DPRIME;
 	const bool bins_ok = x_bins >= 1 && x_bins <= AGG_MAX_BINS && y_bins >= 1 && y_bins <= AGG_MAX_BINS;
-	ReduceCall call(c, Reduce::aggregate, f, bin_x && bin_y && n && sum && sum_sq && min && max && stat_ok && bins_ok, mode, a0, nA);
+	ReduceCall call(c, Reduce::aggregate, f, bin_x && bin_y && n && sum && sum_sq && min && max && valid_stat(stat) && bins_ok, mode, a0, nA);
 	if (call.bad) return call.bad;
 	const size_t M = c->M, cells = (size_t)x_bins * y_bins, words = cells * AGG_CELL_WORDS;
 	std::vector<uint32_t> key(M);
@@ -2589,30 +2595,30 @@ int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uin
 		key[v] = ag_pack(bin_x[v], bin_y[v]);
 	}
 	HIPCHK(c, c->d_agg_key.reserve(M, M, nullptr));
-	int rc = call.hold(c->d_agg, words, "the LD aggregate of %u variants needs %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	int rc = call.hold(call.d_agg, words, "the LD aggregate of %u variants needs %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
 	// (from pageable memory: the copy has left `key` when it returns)
 	HIPCHK(c, hipMemcpyAsync(c->d_agg_key, key.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(k_ld_aggregate_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, c->d_agg.get(), (unsigned long long)words);
+	hipLaunchKernelGGL(k_ld_aggregate_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, call.d_agg.get(), (unsigned long long)words);
 	HIPCHK(c, hipGetLastError());
-	c->agg_map = AggMap{c->d_agg_key, c->d_agg, x_bins, y_bins, stat};
-	c->agg_slots = 0;
+	c->reduce.map.agg = AggMap{c->d_agg_key, call.d_agg, x_bins, y_bins, stat};
 	call.arm(words * sizeof(unsigned long long));
-	rc = call.dispatch(RegionArgs{mode, f, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, nullptr, nullptr, n_pairs, nullptr});
+	rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
 	if (rc) return rc;
 	const size_t slab = std::min<size_t>(cells, (size_t)1 << 18);      // 16 MiB of accumulators at a time
 	std::vector<unsigned long long> acc(slab * AGG_CELL_WORDS);
 	for (size_t at = 0; at < cells; at += slab) {
 		const size_t m = std::min(slab, cells - at);
-		hipError_t e = hipMemcpyAsync(acc.data(), c->d_agg + at * AGG_CELL_WORDS, m * AGG_CELL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
-		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
-		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "aggregate arrays: %s", hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
+		rc = call.download("aggregate arrays", [&] {
+			return hipMemcpyAsync(acc.data(), call.d_agg + at * AGG_CELL_WORDS, m * AGG_CELL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+		});
+		if (rc) return rc;
 		for (size_t k = 0; k < m; ++k) {
 			const unsigned long long* w = acc.data() + k * AGG_CELL_WORDS;
 			n[at + k] = w[AGG_W_N];
-			sum[at + k] = ag_sum_to_double_signed(w[AGG_W_Q_HI], w[AGG_W_Q_LO]);      // (exact in 128 bits, one conversion: ld_aggregate_bin.h)
-			sum_sq[at + k] = ag_sum_to_double_unsigned(w[AGG_W_Q2_HI], w[AGG_W_Q2_LO]);
-			min[at + k] = w[AGG_W_N] ? ag_value_to_double((long long)w[AGG_W_MIN]) : 0.0;
-			max[at + k] = w[AGG_W_N] ? ag_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
+			sum[at + k] = xs_sum_to_double_signed<AGG_SPLIT>(w[AGG_W_Q_HI], w[AGG_W_Q_LO]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
+			sum_sq[at + k] = xs_sum_to_double_unsigned<AGG_SPLIT>(w[AGG_W_Q2_HI], w[AGG_W_Q2_LO]);
+			min[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MIN]) : 0.0;
+			max[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
 		}
 	}
 	return TWK_HIP_OK;

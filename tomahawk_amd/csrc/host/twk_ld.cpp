@@ -987,6 +987,13 @@ struct ReduceCommand {
 		options = (settings.window ? TWK_HIP_OPT_WINDOW : 0) | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);
 		return ready;
 	}
+	// The selection's pairs as the geometry of one engine call (`ldscore`, `lddecay`, `ldaggregate`): the whole triangle if the selection
+	// is diagonal, else left x right.  pairs false: the selection holds no pair and the command makes no engine call
+	struct Geometry { bool pairs; uint32_t a0, nA, b0, nB; int32_t triangle; };
+	Geometry geometry() const {
+		if (S.bal.diag) return Geometry{M > 1, 0, M, 0, M, 1};
+		return Geometry{S.nL && S.nR, 0, (uint32_t)S.nL, (uint32_t)S.nL, (uint32_t)S.nR, 0};
+	}
 	// The text output: -o, or stdout.  -> null after an error message
 	std::ostream* open_text() {
 		if (settings.out.empty() || settings.out == "-") return &std::cout;
@@ -1033,15 +1040,14 @@ bool twk_ld::Score(const twk_ld_settings& s) {
 	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
 	if (!cmd.check("A score sums over every record", nullptr)) return false;
 	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
-	const Selection& S = cmd.S;
 	const uint32_t M = cmd.M;
 	std::vector<uint64_t> n_partners(M, 0);
 	std::vector<double> sum_r2(M, 0.0);
 	uint64_t np = 0;
 	const auto t0 = ReduceCommand::clock::now();
 	int rc = TWK_HIP_OK;
-	if (S.bal.diag) { if (M > 1) rc = twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, M, 1, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np); }
-	else if (S.nL && S.nR) rc = twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
+	const auto g = cmd.geometry();
+	if (g.pairs) rc = twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
 	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_score")) return false;
 	mImpl->n_pairs = np;
 	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
@@ -1075,15 +1081,14 @@ bool twk_ld::Decay(const twk_ld_settings& s, const twk_decay_settings& ds) {
 	if (ds.n_bins < 1 || ds.n_bins > 4096) { std::cerr << stamp("ERROR") << "The number of bins must be between 1 and 4096..." << std::endl; return false; }
 	if (ds.range_bp < ds.n_bins || ds.range_bp > 0xFFFFFFFFll) { std::cerr << stamp("ERROR") << "The range in bases must be at least the number of bins and below 2^32..." << std::endl; return false; }
 	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
-	const Selection& S = cmd.S;
-	const uint32_t M = cmd.M, B = (uint32_t)ds.n_bins, range = (uint32_t)ds.range_bp;
+	const uint32_t B = (uint32_t)ds.n_bins, range = (uint32_t)ds.range_bp;
 	std::vector<uint64_t> n(B, 0);
 	std::vector<double> sum_r2(B, 0.0);
 	uint64_t np = 0;
 	const auto t0 = ReduceCommand::clock::now();
 	int rc = TWK_HIP_OK;
-	if (S.bal.diag) { if (M > 1) rc = twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, M, 1, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np); }
-	else if (S.nL && S.nR) rc = twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np);
+	const auto g = cmd.geometry();
+	if (g.pairs) rc = twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np);
 	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_decay")) return false;
 	mImpl->n_pairs = np;
 	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
@@ -1139,8 +1144,8 @@ bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& a
 	uint64_t np = 0;
 	const auto t0 = ReduceCommand::clock::now();
 	int rc = TWK_HIP_OK;
-	if (S.bal.diag) { if (M > 1) rc = twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, M, 1, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np); }
-	else if (S.nL && S.nR) rc = twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, 0, S.nL, S.nL, S.nR, 0, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np);
+	const auto g = cmd.geometry();
+	if (g.pairs) rc = twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np);
 	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_aggregate")) return false;
 	mImpl->n_pairs = np;
 	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
