@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -107,6 +107,13 @@ aggregate-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall $(PKG)/csrc/tools/aggregate_bin_check.cpp -o build/aggregate_bin_check
 	./build/aggregate_bin_check
+
+# The sample relationship's layout, transposition, count formulas and epilogue lanes (csrc/hip/ld_relate_index.h) against a naive
+# restatement (csrc/tools/relate_index_check.cpp): host code only, under AddressSanitizer and UBSan
+relate-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/relate_index_check.cpp -o build/relate_index_check
+	./build/relate_index_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

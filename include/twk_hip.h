@@ -39,6 +39,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_matrix / twk_hip_matrix_last - the dense LD matrix - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_decay - LD decay - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_aggregate - the LD aggregate - is an entry point more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_relationship / twk_hip_relationship_last - the sample relationship matrix - are two entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -445,6 +446,55 @@ int twk_hip_ld_aggregate(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filt
                          int32_t stat, const uint16_t* bin_x /*[n_variants]*/, const uint16_t* bin_y /*[n_variants]*/,
                          uint32_t x_bins, uint32_t y_bins,
                          uint64_t* n, double* sum, double* sum_sq, double* min, double* max /*[x_bins * y_bins] each*/, uint64_t* n_pairs);
+
+/* The sample relationship matrix: sample by sample instead of variant by variant - what a cohort user computes before any LD, to find
+ * duplicates and relatives.  The same AND + popcount contraction with the reduced axis turned round: the genotype matrix is transposed
+ * on the device into bit planes of the SAMPLES over the variants in use, the count kernel contracts them, and an epilogue turns the plane
+ * products of a sample pair into exact integer counts and one statistic.
+ *   variants, n_use   the variants in use, indices as uploaded, strictly ascending; NULL: all of them (n_use is ignored)
+ *   sA0, nSA, sB0, nSB  the sample rows [sA0, sA0 + nSA) and columns [sB0, sB0 + nSB) of the matrix
+ * For two samples a, b let g be a sample's ALT-allele count at a variant (0, 1, 2; phase is ignored); a sample is missing at a variant
+ * when its mask bits are set.  Over the variants in use at which BOTH samples are non-missing:
+ *   n       the number of such variants            ibs0    the number with {g_a, g_b} = {0, 2}
+ *   ibs2    the number with g_a == g_b             hethet  the number with g_a == g_b == 1
+ *   het_a   the number with g_a == 1               het_b   the number with g_b == 1          (ibs1 = n - ibs0 - ibs2)
+ * The diagonal is a pair like any other: ibs2 = n, ibs0 = 0, hethet = het_a = het_b.  A statistic is ONE double division of integers
+ * formed in 64 bits (the build has no fast-math: IEEE division, the bits numpy's division of the same integers gives):
+ *   TWK_HIP_REL_IBS   (n + ibs2 - ibs0) / (2 n)                mean allele sharing: PLINK's 2 - |g_a - g_b|, averaged and halved
+ *   TWK_HIP_REL_IBS0  ibs0 / n
+ *   TWK_HIP_REL_KING  (hethet - 2 ibs0) / (het_a + het_b)      the KING-robust kinship as PLINK 2's --make-king forms it; signed numerator
+ * and an entry whose denominator is 0 is `fill`, bit for bit.
+ *   out     HOST array of nSA rows of ld >= nSB doubles, or NULL;  counts  HOST array of nSA rows of ld_counts >= nSB entries, or NULL
+ *           (not both NULL).  Columns beyond nSB are not written.  A caller with more samples than one output fits asks for rectangles;
+ *           several GPUs are the caller's rectangles on several contexts.
+ *   *n_sample_pairs (may be NULL)  the pairs evaluated: nSA * nSB, or nSA (nSA + 1) / 2 when the call is a square on the diagonal
+ *           (sA0 == sB0 and nSA == nSB) - then only the tiles on or above the diagonal are contracted and every pair fills (a, b) and
+ *           (b, a), het_a and het_b swapped.
+ * The planes are two a sample (het, hom-alt) when no variant in use has missing genotypes and three (het, hom-alt, non-missing) when one
+ * has; they live for the length of the call (re-transposing reads the raw matrix once, little next to the contraction), and the sample
+ * pair space is walked in super-tiles, so the count matrix stays bounded whatever the sample count.  Plain stores, every entry by
+ * exactly one lane of one launch, no atomics: two calls return the same bytes.  The context is afterwards as it was: no option, no
+ * variant plane set and no record-path state changes.
+ * TWK_HIP_E_INVALID before any launch: both outputs NULL, ld or ld_counts below nSB, an empty sample slice or one beyond the last sample,
+ * n_use == 0 with a list, a list that is not strictly ascending or reaches beyond the last variant, an unknown stat; TWK_HIP_E_STATE
+ * before twk_hip_set_problem; TWK_HIP_E_NOMEM with the size in twk_hip_last_error when the planes, the count matrix or the output do
+ * not fit the device.  twk_hip_timing: the count launches count as count_ms, count_launches and row_pairs, the epilogue as stats_ms and
+ * stats_launches; the transposition is reported by twk_hip_relationship_last.
+ * The reference's `relationship` (lib/relationship.h) is NOT reproduced: its inner loop skips the first sample of every run, it scores
+ * het / het as 2 inside a run and 1 across runs, its mirroring leaves column 0 empty and it divides by the number of variants whatever
+ * is missing.  The statistics here are defined from the integer counts above. */
+enum { TWK_HIP_REL_IBS = 0, TWK_HIP_REL_IBS0 = 1, TWK_HIP_REL_KING = 2 };
+typedef struct { uint32_t n, ibs0, ibs2, hethet, het_a, het_b; } twk_hip_rel_counts;
+int twk_hip_relationship(twk_hip_ctx* ctx,
+        const uint32_t* variants, uint32_t n_use,          /* variants in use, strictly ascending; NULL: all (n_use ignored) */
+        uint32_t sA0, uint32_t nSA, uint32_t sB0, uint32_t nSB,  /* sample rows x sample columns */
+        int32_t stat, double fill,
+        double* out, uint64_t ld,                          /* nSA rows of ld >= nSB doubles; may be NULL */
+        twk_hip_rel_counts* counts, uint64_t ld_counts,    /* likewise; may be NULL (not both) */
+        uint64_t* n_sample_pairs);
+/* Of the context's last twk_hip_relationship call: planes a sample (2 or 3), the device time of the transposition in ms and the bytes of
+ * the plane set (any may be NULL). */
+int twk_hip_relationship_last(const twk_hip_ctx* ctx, int32_t* planes_per_sample, double* transpose_ms, uint64_t* plane_bytes);
 
 /* Multi-GPU runs: keep the survivors of twk_hip_ld_all / twk_hip_ld_region on the device.  With on != 0 the
  * record sink of those calls is not invoked; the survivors of every tile are appended (each tile in (idxA, idxB)

@@ -7,6 +7,7 @@
 #define TWK_LD_H_
 
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -68,6 +69,13 @@ struct twk_aggregate_settings {
 	int32_t stat = 1;                      // TWK_HIP_STAT_R2; or _R (signed), _D, _DPRIME
 	int32_t reduce = 0;                    // what is printed per cell: 0 mean, 1 count, 2 min, 3 max, 4 sd, 5 total
 	int64_t min_count = 5;                 // a cell with fewer contributions prints 0 (the reference's -c)
+};
+
+// What Relationship needs beyond twk_ld_settings.
+struct twk_relationship_settings {
+	int32_t stat = 2;           // TWK_HIP_REL_KING; or _IBS (0), _IBS0 (1) (include/twk_hip.h)
+	double fill = std::numeric_limits<double>::quiet_NaN();      // the entry of a sample pair whose denominator is 0
+	bool text = false;          // with an output prefix: PREFIX.tsv (tab-separated text) instead of PREFIX.npy
 };
 
 class twk_ld {
@@ -134,6 +142,14 @@ public:
 	// then x_bins rows of y_bins tab-separated values at 17 significant digits - the reduction of the cell, 0 below min_count - to
 	// settings.out ("-" or empty: stdout).  settings.minP must be 1 (the default).  `tomahawk ldaggregate` ends here.
 	bool Aggregate(const twk_ld_settings& settings, const twk_aggregate_settings& aggregate);
+	// The sample relationship matrix: sample by sample over the variants of the selection (the reference's `relationship` walks the runs of a
+	// .twk on the host; its numbers are not reproduced - include/twk_hip.h, twk_hip_relationship, says which of its quirks and why).  Loads the
+	// .twk exactly as Prune does (-I intervals select whole blocks; no -c / -C) and fills an n x n float64 matrix over the header's samples on
+	// one GPU: IBS (mean allele sharing), IBS0 or the KING-robust kinship, one IEEE division of exact integer counts per pair, rel.fill where
+	// the denominator is 0.  settings.out empty or "-": the matrix as tab-separated text on stdout, one row per sample, 17 significant digits.
+	// Else settings.out is a PREFIX: PREFIX.npy (NumPy format 1.0, '<f8', C order, shape (n, n)) or, with rel.text, PREFIX.tsv (the same text),
+	// and always PREFIX.samples.tsv: one sample name per row, from the header.  `tomahawk relationship` ends here.
+	bool Relationship(const twk_ld_settings& settings, const twk_relationship_settings& rel);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

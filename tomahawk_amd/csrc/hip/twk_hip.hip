@@ -11,6 +11,8 @@
 //   matrix (ld_matrix.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a dense float32 matrix (twk_hip_ld_matrix)
 //   decay (ld_decay.hip.h) cells -> r2 -> exact integer sums per distance bin, in place of the math stage (twk_hip_ld_decay)
 //   aggregate (ld_aggregate.hip.h) cells -> one statistic -> exact integer sums, counts and extremes per cell of an x-by-y landscape, likewise (twk_hip_ld_aggregate)
+//   relate (ld_relate.hip.h) the raw layout transposed into planes of the samples -> count -> genotype-sharing counts and one statistic per sample pair
+//                          (twk_hip_relationship: its own launches, beside the variant launch path)
 //   (score, prune, clump, matrix, decay and aggregate are the six kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
@@ -48,6 +50,7 @@
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
+#include "ld_relate.hip.h"
 #include "ld_plan.h"
 #include "twk_delivery.h"
 #include "twk_buffers.h"
@@ -321,6 +324,8 @@ struct twk_hip_ctx {
 	DevBuf<unsigned long long> d_decay;                                          // [3][n_bins] accumulators: acc_int, acc_frac, acc_n
 	// aggregate: the two bins of every variant, packed (ld_aggregate.hip.h; the cells' accumulators are the ReduceCall's)
 	DevBuf<uint32_t> d_agg_key;                                                  // [M]
+	// relationship: of the last call (twk_hip_relationship_last) - its planes, row lists and outputs live for the length of the call
+	struct { int32_t planes = 0; double transpose_ms = 0; uint64_t plane_bytes = 0; } relate_last;
 	char err[512] = {0};
 };
 
@@ -2621,6 +2626,176 @@ int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uin
 			max[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
 		}
 	}
+	return TWK_HIP_OK;
+}
+
+// ---- sample relationship (ld_relate.hip.h): its own plane set, tile lists, count launches and epilogue, beside the variant launch path ----
+extern "C++" {
+namespace {
+static_assert(sizeof(RelCounts) == sizeof(twk_hip_rel_counts) && sizeof(RelCounts) == 24, "the epilogue stores twk_hip_rel_counts");
+
+struct EventList {                  // the events of one call, destroyed on every way out
+	std::vector<hipEvent_t> v;
+	~EventList() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
+	hipError_t add(size_t n) {
+		for (size_t k = 0; k < n; ++k) { hipEvent_t e = nullptr; const hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; v.push_back(e); }
+		return hipSuccess;
+	}
+};
+
+// Device memory of the call: TWK_HIP_E_NOMEM with the size in the context's error text when the device cannot give it.
+template <class T>
+int relate_hold(twk_hip_ctx* c, DevBuf<T>& buf, size_t items, const char* what) {
+	const hipError_t e = buf.reserve(items, items, nullptr);
+	if (e == hipSuccess) return TWK_HIP_OK;
+	snprintf(c->err, sizeof(c->err), "sample relationship: %s needs %zu bytes of device memory: %s", what, items * sizeof(T), hipGetErrorString(e));
+	return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+}
+
+struct RelateSuper { uint32_t sa, na, sb, nb; bool diag; size_t list_at = 0, units_at = 0; uint32_t n_tiles = 0, n_units = 0, first_split = 0, ldc = 0; };
+}  // namespace
+}  // extern "C++"
+
+int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_use, uint32_t sA0, uint32_t nSA, uint32_t sB0, uint32_t nSB,
+                         int32_t stat, double fill, double* out, uint64_t ld, twk_hip_rel_counts* counts, uint64_t ld_counts, uint64_t* n_sample_pairs) {
+	if (!c || (!out && !counts) || !rl_valid_stat(stat)) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (nSA == 0 || nSB == 0 || (uint64_t)sA0 + nSA > c->N || (uint64_t)sB0 + nSB > c->N) return TWK_HIP_E_INVALID;
+	if ((out && ld < nSB) || (counts && ld_counts < nSB)) return TWK_HIP_E_INVALID;
+	if (variants) {
+		if (n_use == 0) return TWK_HIP_E_INVALID;
+		for (uint32_t k = 0; k < n_use; ++k)
+			if (variants[k] >= c->M || (k && variants[k] <= variants[k - 1])) return TWK_HIP_E_INVALID;
+	} else n_use = c->M;
+	bool any_missing = false;
+	for (uint32_t k = 0; k < n_use && !any_missing; ++k) any_missing = c->h_meta[variants ? variants[k] : k].missing != 0;
+	if (any_missing && !c->rawmask) return TWK_HIP_E_STATE;
+	HIPCHK(c, hipSetDevice(c->device));
+
+	// the plane set: P rows a sample over the variants in use (ld_relate_index.h)
+	const uint32_t P = rl_planes(any_missing), W = rl_words(n_use), N = c->N;
+	const uint64_t rows_alloc = rl_rows_alloc(N, P), live_rows = (uint64_t)N * P;
+	DevBuf<uint32_t> d_rows, d_rowpop, d_ids, d_C, d_lists, d_tickets;
+	DevBuf<unsigned long long> d_out;
+	DevBuf<RelCounts> d_counts;
+	DevBuf<RelateArgs> d_args;
+	int rc = relate_hold(c, d_rows, (size_t)rows_alloc * W, "the planes of the samples"); if (rc) return rc;
+	rc = relate_hold(c, d_rowpop, (size_t)rows_alloc, "the planes' popcounts"); if (rc) return rc;
+	if (variants) {
+		rc = relate_hold(c, d_ids, n_use, "the variant list"); if (rc) return rc;
+		HIPCHK(c, hipMemcpyAsync(d_ids, variants, (size_t)n_use * 4, hipMemcpyHostToDevice, c->s_compute));
+	}
+	// (the transposition writes every word of the live rows; the zero rows behind them are set here)
+	HIPCHK(c, hipMemsetAsync(d_rows + live_rows * W, 0, (size_t)(rows_alloc - live_rows) * W * 4, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d_rowpop, 0, (size_t)rows_alloc * 4, c->s_compute));
+	EventList ev;
+	HIPCHK(c, ev.add(2));
+	HIPCHK(c, hipEventRecord(ev.v[0], c->s_compute));
+	{
+		const dim3 grid((N + RL_BLOCK_SAMPLES - 1) / RL_BLOCK_SAMPLES, std::min<uint32_t>(W / RL_KC, 65535u)), block(RL_THREADS);
+		hipLaunchKernelGGL(k_relate_transpose, grid, block, 0, c->s_compute, (const uint32_t*)c->raw, (const uint32_t*)(any_missing ? c->rawmask.get() : nullptr), c->Wp,
+		                   (const uint32_t*)(variants ? d_ids.get() : nullptr), n_use, N, P, d_rows.get(), W);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipEventRecord(ev.v[1], c->s_compute));
+	hipLaunchKernelGGL(k_row_popcount, dim3((unsigned)((live_rows + 3) / 4)), dim3(256), 0, c->s_compute, (const uint32_t*)d_rows, W, (uint32_t)live_rows, d_rowpop.get());
+	HIPCHK(c, hipGetLastError());
+
+	// the super-tiles of the sample-pair space, each with its tile list and unit table (one copy to the device for all of them)
+	const bool square = sA0 == sB0 && nSA == nSB;
+	const uint32_t S = rl_super_samples(P), nchunks = W / KC, n_blocks = c->resident_blocks;
+	std::vector<RelateSuper> supers;
+	std::vector<uint32_t> blob;               // per super-tile: [tiles | pad to 16 bytes | units]
+	size_t c_words = 0;
+	for (uint32_t ia = 0; ia < nSA; ia += S)
+		for (uint32_t ib = 0; ib < nSB; ib += S) {
+			if (square && ib < ia) continue;
+			RelateSuper st{sA0 + ia, std::min(S, nSA - ia), sB0 + ib, std::min(S, nSB - ib), square && ia == ib};
+			const twk_hip_tile_desc t{st.sa, st.na, st.sb, st.nb, st.diag ? 1 : 0, 0, 0, 0};
+			const Geometry g = tile_geometry((int)P, t);
+			std::vector<uint32_t> list, patch_end;
+			build_tile_list(t, (int)P, g, st.diag, nullptr, list, &patch_end, (uint32_t)c->opt.patch_rows, (uint32_t)c->opt.patch_cols);
+			std::vector<CountUnit> units;
+			st.n_tiles = (uint32_t)list.size();
+			st.first_split = build_count_units(st.n_tiles, nchunks, n_blocks, (uint32_t)c->opt.count_min_chunks, units, 8, 8);
+			fill_unit_tiles(units, list.data());
+			st.n_units = (uint32_t)units.size(); st.ldc = g.ldc;
+			st.list_at = blob.size();
+			blob.insert(blob.end(), list.begin(), list.end());
+			blob.resize((blob.size() + 3) / 4 * 4);
+			st.units_at = blob.size();
+			blob.resize(blob.size() + units.size() * 4);
+			std::memcpy(blob.data() + st.units_at, units.data(), units.size() * sizeof(CountUnit));
+			c_words = std::max(c_words, (size_t)g.rowsA * g.rowsB);
+			supers.push_back(st);
+		}
+	const size_t cells = (size_t)nSA * nSB;
+	rc = relate_hold(c, d_C, c_words, "the count matrix of a super-tile"); if (rc) return rc;
+	rc = relate_hold(c, d_lists, blob.size(), "the tile lists"); if (rc) return rc;
+	rc = relate_hold(c, d_tickets, supers.size() * 8, "the work tickets"); if (rc) return rc;
+	rc = relate_hold(c, d_args, supers.size(), "the epilogue's parameter blocks"); if (rc) return rc;
+	if (out) { rc = relate_hold(c, d_out, cells, "the matrix"); if (rc) return rc; }
+	if (counts) { rc = relate_hold(c, d_counts, cells, "the counts"); if (rc) return rc; }
+	unsigned long long fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));          // any pattern, NaNs included
+	std::vector<RelateArgs> args(supers.size());
+	for (size_t k = 0; k < supers.size(); ++k) {
+		const RelateSuper& st = supers[k];
+		RelateArgs& a = args[k];
+		a.C = d_C; a.ldc = st.ldc; a.P = P; a.n_use = n_use; a.rowpop = d_rowpop;
+		a.sa = st.sa; a.na = st.na; a.sb = st.sb; a.nb = st.nb;
+		a.out_a0 = sA0; a.out_b0 = sB0; a.out_ld = nSB;
+		a.diag = st.diag ? 1 : 0; a.mirror = square ? 1 : 0; a.stat = stat; a.fill_bits = fill_bits;
+		a.out = out ? d_out.get() : nullptr; a.counts = counts ? d_counts.get() : nullptr;
+	}
+	// (from pageable memory: the copies have left `blob` and `args` when they return)
+	HIPCHK(c, hipMemcpyAsync(d_lists, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemcpyAsync(d_args, args.data(), args.size() * sizeof(RelateArgs), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d_tickets, 0, supers.size() * 8 * 4, c->s_compute));
+	HIPCHK(c, ev.add(3 * supers.size()));
+	for (size_t k = 0; k < supers.size(); ++k) {
+		const RelateSuper& st = supers[k];
+		CountWork w{};
+		w.rows = d_rows; w.W = W; w.rowA0 = st.sa * P; w.rowB0 = st.sb * P;
+		w.tiles = d_lists + st.list_at;
+		w.units = reinterpret_cast<const CountUnit*>(d_lists + st.units_at); w.n_units = st.n_units;
+		w.C = d_C; w.ldc = st.ldc;
+		w.ticket = d_tickets + k * 8;
+		w.n_queues = 1; w.queue_begin[0] = 0; w.queue_begin[1] = st.n_units;
+		w.last_halves = c->opt.skip_pad ? rl_last_halves(n_use) : 0;
+		w.clocks = nullptr;
+		if (st.first_split < st.n_tiles) {
+			hipLaunchKernelGGL(k_zero_tiles, dim3(st.n_tiles - st.first_split), dim3(256), 0, c->s_compute, w.tiles, st.first_split, w.C, w.ldc, (uint32_t)TILE);
+			HIPCHK(c, hipGetLastError());
+		}
+		HIPCHK(c, hipEventRecord(ev.v[2 + 3 * k], c->s_compute));
+		hipLaunchKernelGGL(k_count_list_t<COUNT_NW>, dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w);
+		HIPCHK(c, hipGetLastError());
+		HIPCHK(c, hipEventRecord(ev.v[3 + 3 * k], c->s_compute));
+		hipLaunchKernelGGL(k_relate_epilogue, dim3((st.nb + RL_EP - 1) / RL_EP, (st.na + RL_EP - 1) / RL_EP), dim3(RL_THREADS), 0, c->s_compute, (const RelateArgs*)(d_args + k));
+		HIPCHK(c, hipGetLastError());
+		HIPCHK(c, hipEventRecord(ev.v[4 + 3 * k], c->s_compute));
+	}
+	if (out) HIPCHK(c, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), d_out, (size_t)nSB * sizeof(double), (size_t)nSB * sizeof(double), nSA, hipMemcpyDeviceToHost, c->s_compute));
+	if (counts) HIPCHK(c, hipMemcpy2DAsync(counts, (size_t)ld_counts * sizeof(RelCounts), d_counts, (size_t)nSB * sizeof(RelCounts), (size_t)nSB * sizeof(RelCounts), nSA, hipMemcpyDeviceToHost, c->s_compute));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	float ms = 0;
+	c->relate_last.planes = (int32_t)P; c->relate_last.plane_bytes = (uint64_t)rows_alloc * W * 4;
+	c->relate_last.transpose_ms = hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess ? ms : 0.0;
+	for (size_t k = 0; k < supers.size(); ++k) {
+		if (hipEventElapsedTime(&ms, ev.v[2 + 3 * k], ev.v[3 + 3 * k]) == hipSuccess) c->timing.count_ms += ms;
+		if (hipEventElapsedTime(&ms, ev.v[3 + 3 * k], ev.v[4 + 3 * k]) == hipSuccess) c->timing.stats_ms += ms;
+		c->timing.count_launches += 1; c->timing.stats_launches += 1;
+		c->timing.row_pairs += (uint64_t)supers[k].n_tiles * TILE * TILE;
+	}
+	if (n_sample_pairs) *n_sample_pairs = square ? (uint64_t)nSA * (nSA + 1) / 2 : (uint64_t)nSA * nSB;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_relationship_last(const twk_hip_ctx* c, int32_t* planes_per_sample, double* transpose_ms, uint64_t* plane_bytes) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (planes_per_sample) *planes_per_sample = c->relate_last.planes;
+	if (transpose_ms) *transpose_ms = c->relate_last.transpose_ms;
+	if (plane_bytes) *plane_bytes = c->relate_last.plane_bytes;
 	return TWK_HIP_OK;
 }
 

@@ -470,6 +470,101 @@ static int ldmatrix(int argc, char** argv) {
 	return ld.Matrix(settings, ms) ? 0 : 1;
 }
 
+// `tomahawk relationship`: the sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU.  The reference's name and its -i / -I;
+// its numbers are not reproduced (include/twk_hip.h, twk_hip_relationship).
+static void relationship_usage() {
+	program_message();
+	std::cerr <<
+	"About:  The sample relationship matrix - what a cohort is checked with for duplicates and relatives\n"
+	"        before any LD: per pair of samples, over the selected variants at which both are non-missing,\n"
+	"        n, IBS0 (opposite homozygotes), IBS2 (same genotype) and the heterozygote counts, exact\n"
+	"        integers counted on the GPU, and one statistic of them:\n"
+	"          ibs   (n + ibs2 - ibs0) / (2 n)                mean allele sharing\n"
+	"          ibs0  ibs0 / n\n"
+	"          king  (hethet - 2 ibs0) / (het_a + het_b)      KING-robust kinship (0.5 duplicate, 0.25 first degree)\n"
+	"        The reference's `relationship` is not reproduced: it skips the first sample of every run,\n"
+	"        scores het/het differently inside and across runs, leaves column 0 empty and divides by the\n"
+	"        number of variants whatever is missing.\n\n"
+	"Usage:  tomahawk relationship -i <in.twk> [-I interval ...] [-s ibs|ibs0|king] [-f fill] [-o PREFIX [-T]]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -I STRING filter interval <contig>:pos-pos (repeatable; default: every variant)\n"
+	"  -s STRING statistic: ibs, ibs0 or king (default: king)\n"
+	"  -f FLOAT  fill value of a pair whose denominator is 0, nan allowed (default: nan)\n"
+	"  -o PREFIX output prefix (default: the matrix as text on stdout)\n"
+	"  -T        with -o: write PREFIX.tsv (text) instead of PREFIX.npy\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"  (-p, -u, -r, -w, -c, -C and -P are refused: samples are compared genotype by genotype over every selected variant)\n"
+	"Output: without -o       the matrix on stdout: one row per sample, tab-separated, 17 significant digits\n"
+	"        PREFIX.npy          the matrix as a NumPy file: float64, C order, shape (n, n); or, with -T,\n"
+	"        PREFIX.tsv          the matrix as text, as on stdout\n"
+	"        PREFIX.samples.tsv  one sample name per row of the matrix, from the input's header\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+
+static int relationship(int argc, char** argv) {
+	if (argc < 3) { relationship_usage(); return 1; }
+	static struct option long_options[] = {
+		{"input", required_argument, 0, 'i'}, {"interval", required_argument, 0, 'I'}, {"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'},
+		{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000},
+		{"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'}, {"minR2", required_argument, 0, 'r'}, {"windowBases", required_argument, 0, 'w'},
+		{"parts", required_argument, 0, 'c'}, {"partStart", required_argument, 0, 'C'}, {"minP", required_argument, 0, 'P'}, {0, 0, 0, 0}};
+	tomahawk::twk_ld_settings settings;
+	tomahawk::twk_relationship_settings rs;
+	std::vector<std::pair<std::string, long long>> engine_options;
+	int c, option_index = 0;
+	while ((c = getopt_long(argc, argv, "i:I:s:f:o:Tt:pur:w:c:C:P:?", long_options, &option_index)) != -1) {
+		switch (c) {
+		case 'p': case 'u': std::cerr << stamp("ERROR") << "Cannot force a phasing (-" << (char)c << "): samples are compared by genotype, phase is ignored" << std::endl; return 1;
+		case 'r': std::cerr << stamp("ERROR") << "Cannot apply an R-squared cut-off (-r): no variant pair is formed" << std::endl; return 1;
+		case 'w': std::cerr << stamp("ERROR") << "Cannot apply a window (-w): samples are compared over every selected variant" << std::endl; return 1;
+		case 'c': case 'C': std::cerr << stamp("ERROR") << "Cannot relate over a part of the pair space (-" << (char)c << "): samples are compared over every selected variant" << std::endl; return 1;
+		case 'P': std::cerr << stamp("ERROR") << "Cannot apply a cutoff P-value (-P): the matrix is counted, no test is run" << std::endl; return 1;
+		case 'i': settings.in = optarg; break;
+		case 'I': settings.ival_strings.push_back(optarg); break;
+		case 'o': settings.out = optarg; break;
+		case 'T': rs.text = true; break;
+		case 't':
+			settings.n_threads = atoi(optarg);
+			if (settings.n_threads <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of worker threads" << std::endl; return 1; }
+			break;
+		case 's': {
+			const std::string a(optarg);
+			if (a == "ibs") rs.stat = TWK_HIP_REL_IBS;
+			else if (a == "ibs0") rs.stat = TWK_HIP_REL_IBS0;
+			else if (a == "king") rs.stat = TWK_HIP_REL_KING;
+			else { std::cerr << stamp("ERROR") << "Unknown statistic (-s): " << a << " - one of ibs, ibs0, king" << std::endl; return 1; }
+			break;
+		}
+		case 'f': {
+			char* end = nullptr;
+			const double v = strtod(optarg, &end);      // (nan and inf are numbers here: a fill may be either)
+			if (end == optarg || *end) { std::cerr << stamp("ERROR") << "The fill value (-f) must be a number: " << optarg << std::endl; return 1; }
+			rs.fill = v;
+			break;
+		}
+		case 1000: {
+			const std::string a(optarg);
+			const size_t eq = a.find('=');
+			if (eq == std::string::npos || eq == 0 || eq + 1 >= a.size()) { std::cerr << stamp("ERROR") << "--engine-option wants key=value" << std::endl; return 1; }
+			engine_options.emplace_back(a.substr(0, eq), atoll(a.c_str() + eq + 1));
+			break;
+		}
+		default:
+			std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl;
+			return 1;
+		}
+	}
+	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
+	if (rs.text && (settings.out.empty() || settings.out == "-")) { std::cerr << stamp("ERROR") << "-T names the file written for -o PREFIX: without -o the text goes to stdout anyway" << std::endl; return 1; }
+	program_message();
+	std::cerr << stamp("LOG") << "Calling relationship..." << std::endl;
+	tomahawk::twk_ld ld;
+	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
+	return ld.Relationship(settings, rs) ? 0 : 1;
+}
+
 // `tomahawk lddecay`: mean r2 by the distance between two variants over the records `calc` would write, binned and summed on the GPU.  (The
 // reference's `decay` reads a .two file, and its range is -w; here -w keeps calc's meaning, the window of the computation.)
 static void lddecay_usage() {
@@ -855,6 +950,7 @@ static int run_main(int argc, char** argv) {
 		             "  import   convert VCF text (plain / gzip) to .twk\n"
 		             "  calc     calculate linkage disequilibrium: tomahawk calc [options] -i <in.twk> -o <output.two>\n"
 		             "  scalc    linkage disequilibrium of one site against its neighbourhood\n"
+	             "  relationship  sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU\n"
 		             "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n"
 		             "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n"
 		             "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n"
@@ -874,6 +970,7 @@ static int run_main(int argc, char** argv) {
 	tomahawk::LITERAL_COMMAND_LINE = "tomahawk";
 	for (int i = 1; i < argc; ++i) tomahawk::LITERAL_COMMAND_LINE += " " + std::string(argv[i]);
 	if (strcmp(argv[1], "calc") == 0) return calc(argc, argv);
+	if (strcmp(argv[1], "relationship") == 0) return relationship(argc, argv);
 	if (strcmp(argv[1], "ldscore") == 0) return ldscore(argc, argv);
 	if (strcmp(argv[1], "prune") == 0) return prune(argc, argv);
 	if (strcmp(argv[1], "clump") == 0) return clump(argc, argv);
@@ -888,7 +985,7 @@ static int run_main(int argc, char** argv) {
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay`, `ldaggregate`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance and `ldaggregate` into x-by-y cells without a .two)" << std::endl;
+	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `relationship`, `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay`, `ldaggregate`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance and `ldaggregate` into x-by-y cells without a .two; `relationship` keeps the reference's name, not its numbers)" << std::endl;
 	return 1;
 }
 

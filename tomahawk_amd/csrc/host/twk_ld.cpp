@@ -1409,6 +1409,82 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 	return true;
 }
 
+// `tomahawk relationship`: the sample-by-sample matrix over the variants of the selection (twk_hip_relationship: transposed, contracted and
+// divided on the GPU), as text on stdout or as a NumPy file or text file with the samples' names next to it.  The input is loaded exactly as
+// Prune loads it; one GPU.  The reference's command of the same name is not reproduced (include/twk_hip.h says why).
+bool twk_ld::Relationship(const twk_ld_settings& s, const twk_relationship_settings& rs) {
+	settings = s;
+	mImpl->n_pairs = mImpl->n_records = 0;
+	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
+	if (!cmd.check("The matrix is counted, not tested", "Cannot relate over a part of the pair space: the samples are compared over every selected variant")) return false;
+	if (rs.stat != TWK_HIP_REL_IBS && rs.stat != TWK_HIP_REL_IBS0 && rs.stat != TWK_HIP_REL_KING) {
+		std::cerr << stamp("ERROR") << "Unknown statistic: one of ibs, ibs0, king..." << std::endl; return false;
+	}
+	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	const uint32_t n = cmd.S.n_samples;
+	std::vector<double> m((size_t)n * n);
+	uint64_t np = 0;
+	const auto t0 = ReduceCommand::clock::now();
+	const int rc = twk_hip_relationship(cmd.ctx, nullptr, 0, 0, n, 0, n, rs.stat, rs.fill, m.data(), n, nullptr, 0, &np);
+	if (!hip_ok(cmd.ctx, rc, "twk_hip_relationship")) return false;
+	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+
+	// one row per sample, tab-separated, 17 significant digits (a NaN prints as nan whatever its bits: the .npy keeps them)
+	auto write_text = [&](std::ostream& os) {
+		std::string text;
+		char num[40];
+		for (uint32_t a = 0; a < n; ++a) {
+			for (uint32_t b = 0; b < n; ++b) {
+				const double v = m[(size_t)a * n + b];
+				if (v != v) snprintf(num, sizeof(num), b ? "\tnan" : "nan");
+				else snprintf(num, sizeof(num), b ? "\t%.17g" : "%.17g", v);
+				text += num;
+			}
+			text += '\n';
+			cmd.spill(os, text);
+		}
+		return cmd.finish(os, text, "the matrix");
+	};
+	const bool to_stdout = settings.out.empty() || settings.out == "-";
+	if (to_stdout) {
+		if (!write_text(std::cout)) return false;
+	} else {
+		const std::string path = settings.out + (rs.text ? ".tsv" : ".npy");
+		std::cerr << stamp("LOG", "WRITER") << "Opening " << path << "..." << std::endl;
+		std::ofstream file(path, std::ios::out | std::ios::trunc | std::ios::binary);
+		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << path << "..." << std::endl; return false; }
+		if (rs.text) {
+			if (!write_text(file)) return false;
+		} else {
+			// NumPy format 1.0, as Matrix writes it, with eight-byte floats
+			std::string dict = "{'descr': '<f8', 'fortran_order': False, 'shape': (" + std::to_string(n) + ", " + std::to_string(n) + "), }";
+			const size_t fixed = 6 + 2 + 2;
+			const size_t total = (fixed + dict.size() + 1 + 63) / 64 * 64;
+			dict.append(total - fixed - dict.size() - 1, ' ');
+			dict += '\n';
+			const char head[fixed] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(dict.size() & 0xFF), (char)(dict.size() >> 8 & 0xFF)};
+			file.write(head, fixed);
+			file.write(dict.data(), (std::streamsize)dict.size());
+			file.write(reinterpret_cast<const char*>(m.data()), (std::streamsize)(m.size() * sizeof(double)));      // (the hosts this runs on are little-endian)
+			file.flush();
+			if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the matrix..." << std::endl; return false; }
+		}
+		file.close();
+		const std::string spath = settings.out + ".samples.tsv";
+		std::cerr << stamp("LOG", "WRITER") << "Opening " << spath << "..." << std::endl;
+		std::ofstream sfile(spath, std::ios::out | std::ios::trunc);
+		if (!sfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << spath << "..." << std::endl; return false; }
+		std::string text;
+		for (const std::string& name : cmd.S.reader.hdr.samples) { text += name; text += '\n'; }
+		if (!cmd.finish(sfile, text, "the sample list")) return false;
+	}
+	static const char* const stat_names[] = {"ibs", "ibs0", "king"};
+	std::cerr << stamp("LOG") << "Relationship (" << stat_names[rs.stat] << "): " << pretty(n) << " x " << pretty(n) << " samples over " << pretty(cmd.M) << " variants, "
+	          << pretty(np) << " sample pairs. " << elapsed_string(sec) << std::endl;
+	cmd.all_done();
+	return true;
+}
+
 // scalc: one target site against its neighbourhood (ld.cpp:673-876, LoadTargetSingle :123-255,
 // CalculateSingle ld_engine.cpp:2226-2332).
 bool twk_ld::ComputeSingle(bool verbose, bool) {

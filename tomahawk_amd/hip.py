@@ -20,6 +20,7 @@ MODE_PHASED, MODE_UNPHASED, MODE_AUTO = 1, 2, 3
 OPT_WINDOW, OPT_KEEP_LOW_AC, OPT_REF_COMPAT, OPT_R2_SCREEN = 1, 2, 4, 8
 NO_CLUMP = 0xFFFFFFFF      # TWK_HIP_NO_CLUMP: ld_clump's index_of for a variant in no clump
 STAT_R, STAT_R2, STAT_D, STAT_DPRIME = 0, 1, 2, 3      # TWK_HIP_STAT_*: the statistic ld_matrix fills in
+REL_IBS, REL_IBS0, REL_KING = 0, 1, 2      # TWK_HIP_REL_*: the statistic relationship fills in
 E_OVERFLOW = -4
 
 # twk_hip_record (include/twk_hip.h): 104 bytes
@@ -36,6 +37,10 @@ assert RLE_DESC_DTYPE.itemsize == 16
 META_DTYPE = np.dtype([("ac", "<u4"), ("an", "<u4"), ("pos", "<u4"), ("rid", "<u4"),
                        ("missing", "<u4"), ("_pad", "<u4"), ("hwe", "<f8")])
 assert META_DTYPE.itemsize == 32
+
+# twk_hip_rel_counts: 24 bytes
+REL_COUNTS_DTYPE = np.dtype([("n", "<u4"), ("ibs0", "<u4"), ("ibs2", "<u4"), ("hethet", "<u4"), ("het_a", "<u4"), ("het_b", "<u4")])
+assert REL_COUNTS_DTYPE.itemsize == 24
 
 
 class _Filters(C.Structure):
@@ -206,6 +211,9 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_matrix.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                       C.c_int32, C.c_float, p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_matrix_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_relationship.argtypes = [p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_double,
+                                         p, C.c_uint64, p, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.twk_hip_relationship_last.argtypes = [p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_shard_rows.argtypes = [C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_plan_region.argtypes = [p, p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32,
@@ -608,6 +616,34 @@ class HipLd:
         ms, b = C.c_double(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_matrix_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_matrix_last")
         return {"copy_ms": ms.value, "matrix_bytes": b.value}
+
+    def relationship(self, stat: int = REL_KING, fill: float = float("nan"), variants=None, sA0: int = 0, nSA: int | None = None,
+                     sB0: int = 0, nSB: int | None = None, want_counts: bool = False):
+        """The sample relationship matrix (twk_hip_relationship) of the sample rows [sA0, sA0 + nSA) x columns [sB0, sB0 + nSB) over
+        `variants` (indices as uploaded, strictly ascending; None: all): per pair, over the variants at which both samples are
+        non-missing, the exact counts n, ibs0, ibs2, hethet, het_a, het_b and one statistic - REL_IBS (n + ibs2 - ibs0) / (2 n),
+        REL_IBS0 ibs0 / n, REL_KING (hethet - 2 ibs0) / (het_a + het_b) - as one IEEE double division; `fill` (bit for bit) where
+        the denominator is 0.  Transposed, contracted and divided on the device.
+        -> float64 ndarray (nSA, nSB), or (that, REL_COUNTS_DTYPE ndarray (nSA, nSB)) with want_counts."""
+        N = self.n_samples
+        nSA = N - sA0 if nSA is None else nSA
+        nSB = N - sB0 if nSB is None else nSB
+        shape = (max(int(nSA), 0), max(int(nSB), 0))
+        out = np.empty(shape, dtype=np.float64)
+        cnt = np.zeros(shape, dtype=REL_COUNTS_DTYPE) if want_counts else None
+        ids = None if variants is None else np.ascontiguousarray(variants, dtype=np.uint32)
+        npairs = C.c_uint64(0)
+        self._check(self._lib.twk_hip_relationship(self._ctx, None if ids is None else ids.ctypes.data, 0 if ids is None else len(ids),
+                                                   sA0, nSA, sB0, nSB, int(stat), C.c_double(fill), out.ctypes.data, shape[1],
+                                                   None if cnt is None else cnt.ctypes.data, shape[1], C.byref(npairs)), "twk_hip_relationship")
+        return (out, cnt) if want_counts else out
+
+    def relationship_last(self) -> dict:
+        """Of the last relationship call (twk_hip_relationship_last): planes a sample (2: no variant in use had missing genotypes,
+        3: one had), the transposition's device time and the plane set's size."""
+        planes, ms, b = C.c_int32(0), C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_relationship_last(self._ctx, C.byref(planes), C.byref(ms), C.byref(b)), "twk_hip_relationship_last")
+        return {"planes_per_sample": planes.value, "transpose_ms": ms.value, "plane_bytes": b.value}
 
     def fisher_exact(self, tables: np.ndarray, ordered: bool = True):
         """Two-sided Fisher P of int32 tables [n, 4] = (n11, n12, n21, n22) through the engine's Fisher kernels
