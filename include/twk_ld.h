@@ -63,6 +63,9 @@ struct twk_decay_settings {
 	int32_t n_bins = 1000;       // the number of bins (the reference's default), at most 4096; range_bp / n_bins bases each
 };
 
+// What Aggregate prints per cell: the values of twk_aggregate_settings::reduce.
+enum { TWK_AGGREGATE_MEAN = 0, TWK_AGGREGATE_COUNT = 1, TWK_AGGREGATE_MIN = 2, TWK_AGGREGATE_MAX = 3, TWK_AGGREGATE_SD = 4, TWK_AGGREGATE_TOTAL = 5 };
+
 // What Aggregate needs beyond twk_ld_settings.
 struct twk_aggregate_settings {
 	int32_t x_bins = 1000, y_bins = 1000;  // bins per axis (the reference's defaults), 1 to 4096 each

@@ -1,5 +1,8 @@
 // `tomahawk calc` on the MI355X engine: same flags, defaults, messages-on-stderr
-// and exit codes as the reference CLI (lib/main.cpp:19-93, lib/calc.h:28-240).
+// and exit codes as the reference CLI (lib/main.cpp:19-93, lib/calc.h:28-240); the engine's other commands; the reference's host tools.
+// An engine command is one row (Command): its usage text, a verbatim literal, is followed by its own options and its row; run_command()
+// parses the shared options, and run_main() reads the rows for dispatch, help and the "Illegal command" sentence.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <getopt.h>
@@ -14,6 +17,7 @@
 #include <malloc.h>
 
 #include "twk_ld.h"
+#include "twk_ld_names.h"
 #include "twk_format.h"
 #include "twk_hip.h"
 #include "twk_two_tools.h"
@@ -26,8 +30,6 @@ static void program_message() {
 	          << "Libraries: tomahawk_amd; ZSTD-" << tomahawk::zstd_version() << "; twk_hip ABI " << twk_hip_abi_version() << "\n"
 	          << "----------" << std::endl;
 }
-
-static std::vector<std::string> g_argv;     // argv as given (getopt_long permutes the live one)
 
 static void calc_usage() {
 	program_message();
@@ -59,84 +61,185 @@ static void calc_usage() {
 
 static std::string stamp(const char* t) { return std::string("[") + t + "] "; }
 
-static int calc(int argc, char** argv) {
-	if (argc < 3) { calc_usage(); return 1; }
-	static struct option long_options[] = {
-		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
-		{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
-		{"low-memory", optional_argument, 0, 'm'}, {"block-size", optional_argument, 0, 'b'}, {"bitmaps", optional_argument, 0, 'M'},
-		{"compression-level", optional_argument, 0, 'k'}, {"cross-chr-only", no_argument, 0, 'X'}, {"no-cross-chr", no_argument, 0, 'x'},
-		{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
-		{"samples", optional_argument, 0, 'S'}, {"minR2", optional_argument, 0, 'r'}, {"detailedProgress", no_argument, 0, 'd'},
-		{"silent", no_argument, 0, 's'}, {"windowBases", optional_argument, 0, 'w'},
-		{"engine-option", required_argument, 0, 1000}, {0, 0, 0, 0}};
-	tomahawk::twk_ld_settings settings;
-	int c, option_index = 0;
+static bool fail(const std::string& what) { std::cerr << stamp("ERROR") << what << std::endl; return false; }
+
+// ---- What is parsed more than once, parsed here.  Each -> false after its error message ----
+using tomahawk::twk_ld_settings;
+
+static bool thread_option(const char* arg, int32_t& n_threads) {
+	n_threads = atoi(arg);
+	return n_threads > 0 || fail("Cannot have a non-positive number of worker threads");
+}
+
+// A non-negative integer, maybe with an exponent (5000, 1e6)?  (Says nothing: -w answers in the reference's words.)
+static bool integer_form(const std::string& arg) {
+	static const std::regex form("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$");
+	return std::regex_match(arg, form);
+}
+// Such an integer in [lo, hi] -> v.  subject: "range (-d)"; bounds: the words after "must be"
+static bool integer_option(const std::string& arg, const char* subject, double lo, double hi, const std::string& bounds, double& v) {
+	if (!integer_form(arg)) return fail(std::string("The ") + subject + " must be a non-negative integer: " + arg);
+	v = atof(arg.c_str());
+	return (v >= lo && v <= hi) || fail(std::string("The ") + subject + " must be " + bounds);
+}
+
+// -f: a fill value (nan and inf are numbers here: a fill may be either)
+template <typename T>
+static bool fill_option(const char* arg, T& fill) {
+	char* end = nullptr;
+	T v;
+	if constexpr (sizeof(T) == sizeof(float)) v = strtof(arg, &end); else v = strtod(arg, &end);
+	if (end == arg || *end) return fail(std::string("The fill value (-f) must be a number: ") + arg);
+	fill = v;
+	return true;
+}
+
+// -s: a statistic by its name in `names` (twk_ld_names.h)
+template <int N>
+static bool stat_option(const char* arg, const tomahawk::NameTable<N>& names, int32_t& stat) {
+	const int32_t v = names.value(arg);
+	if (v < 0) return fail(std::string("Unknown statistic (-s): ") + arg + " - one of " + names.list());
+	stat = v;
+	return true;
+}
+
+// ---- An engine command is a row: what the one parser and the one tail below need to know about it ----
+enum Took { took, failed, declined };
+struct Refusal { const char* flags; const char* why; };      // a shared option the command refuses: its letters, and the sentence (%c: the letter met)
+struct NoOptions {};
+template <class Own>                      // Own: the settings the command's own options fill in; run_command() holds them by value
+struct Command {
+	const char* name;
+	const char* summary;                  // its line of `tomahawk` without arguments
+	void (*usage)();
+	const char* short_options;            // getopt's string, as the command has always had it
+	const struct option* long_options;
+	double minR2;                         // the default of -r (every other default is twk_ld_settings' own)
+	Refusal refusals[5];
+	const char* only_P1;                  // -P below 1 is refused with this sentence; null: calc, which applies -P
+	Took (*option)(int c, const char* arg, twk_ld_settings& settings, Own& own);      // the command's own options; null: it has none
+	bool (*check)(twk_ld_settings& settings, Own& own);                               // after the options and the input's name; null: nothing more
+	bool (*run)(tomahawk::twk_ld& ld, const twk_ld_settings& settings, const Own& own);
+};
+
+// The shared options once (-i -o -I -p -u -t -c -C -r -P -w --engine-option), anything else to the command's own handler; then the checks
+// after the options, the banner, and the call.
+template <class Own>
+static int run_command(const Command<Own>& cmd, int argc, char** argv) {
+	if (argc < 3) { cmd.usage(); return 1; }
+	twk_ld_settings settings;
+	settings.minR2 = cmd.minR2;
+	Own own{};
 	std::vector<std::pair<std::string, long long>> engine_options;
-	while ((c = getopt_long(argc, argv, "i:o:t:puP:a:A:r:w:S:I:sdc:C:mMb:xXk:?", long_options, &option_index)) != -1) {
+	int c, option_index = 0;
+	while ((c = getopt_long(argc, argv, cmd.short_options, cmd.long_options, &option_index)) != -1) {
+		for (const Refusal& r : cmd.refusals) {
+			if (!r.flags || c <= 0 || c > 127 || !strchr(r.flags, c)) continue;
+			char why[256];
+			snprintf(why, sizeof(why), r.why, c);
+			return !fail(why);
+		}
 		switch (c) {
 		case 'i': settings.in = optarg; break;
 		case 'o': settings.out = optarg; break;
 		case 'I': settings.ival_strings.push_back(optarg); break;
-		case 'm': settings.low_memory = true; break;
 		case 'p': settings.force_phased = true; settings.forced_unphased = false; break;
 		case 'u': settings.forced_unphased = true; settings.force_phased = false; break;
-		case 'M': settings.force_phased = true; settings.low_memory = true; settings.bitmaps = true; break;
-		case 't':
-			settings.n_threads = atoi(optarg);
-			if (settings.n_threads <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of worker threads" << std::endl; return 1; }
-			break;
-		case 'b':
-			settings.bl_size = atoi(optarg);
-			if (settings.bl_size <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of entries in a block!" << std::endl; return 1; }
-			break;
+		case 't': if (!thread_option(optarg, settings.n_threads)) return 1; break;
 		case 'c':
 			settings.n_chunks = atoi(optarg);
-			if (settings.n_chunks <= 0) { std::cerr << stamp("ERROR") << "Cannot have a negative or zero amount of partitions" << std::endl; return 1; }
+			if (settings.n_chunks <= 0) return !fail("Cannot have a negative or zero amount of partitions");
 			break;
 		case 'C':
 			settings.c_chunk = atoi(optarg) - 1;   // 1-based on the command line (calc.h:152-153)
-			if (settings.c_chunk < 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive start partition" << std::endl; return 1; }
+			if (settings.c_chunk < 0) return !fail("Cannot have a non-positive start partition");
 			break;
 		case 'r':
 			settings.minR2 = atof(optarg);
-			if (settings.minR2 < 0) { std::cerr << stamp("ERROR") << "Cannot have a negative minimum R-squared value" << std::endl; return 1; }
-			if (settings.minR2 > 1) { std::cerr << stamp("ERROR") << "Cannot have minimum R-squared value > 1" << std::endl; return 1; }
+			if (settings.minR2 < 0) return !fail("Cannot have a negative minimum R-squared value");
+			if (settings.minR2 > 1) return !fail("Cannot have minimum R-squared value > 1");
 			break;
 		case 'P':
 			settings.minP = atof(optarg);
-			if (settings.minP < 0) { std::cerr << stamp("ERROR") << "Cannot have a negative cutoff P-value" << std::endl; return 1; }
-			if (settings.minP > 1) { std::cerr << stamp("ERROR") << "Cannot have a cutoff P-value > 1" << std::endl; return 1; }
+			if (cmd.only_P1) { if (!(settings.minP >= 1)) return !fail(cmd.only_P1); }
+			else if (settings.minP < 0) return !fail("Cannot have a negative cutoff P-value");
+			if (settings.minP > 1) return !fail("Cannot have a cutoff P-value > 1");
 			break;
 		case 'w': {
 			settings.window = true;
-			const std::string a(optarg);
-			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << "not an integer" << std::endl; return 1; }
-			settings.l_window = std::regex_match(a, std::regex("^[0-9]+$")) ? atoi(optarg) : (int32_t)atof(optarg);
-			if (settings.l_window <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive window size" << std::endl; return 1; }
+			const std::string a(optarg);           // (--windowBases without =: no argument, and std::string says so)
+			if (!integer_form(a)) { std::cerr << "not an integer" << std::endl; return 1; }
+			settings.l_window = a.find_first_of("eE") == std::string::npos ? atoi(optarg) : (int32_t)atof(optarg);
+			if (settings.l_window <= 0) return !fail("Cannot have a non-positive window size");
 			break;
 		}
-		case 'k': settings.c_level = atoi(optarg); break;
 		case 1000: {      // --engine-option key=value (not in the reference): twk_ld::SetEngineOption
 			const std::string a(optarg);
 			const size_t eq = a.find('=');
-			if (eq == std::string::npos || eq == 0 || eq + 1 >= a.size()) { std::cerr << stamp("ERROR") << "--engine-option wants key=value" << std::endl; return 1; }
+			if (eq == std::string::npos || eq == 0 || eq + 1 >= a.size()) return !fail("--engine-option wants key=value");
 			engine_options.emplace_back(a.substr(0, eq), atoll(a.c_str() + eq + 1));
 			break;
 		}
 		default:
-			std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl;
-			return 1;
+			switch (cmd.option ? cmd.option(c, optarg, settings, own) : declined) {
+			case took: break;
+			case failed: return 1;
+			case declined: return !fail(std::string("Unrecognized option: ") + (char)c);
+			}
 		}
 	}
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
-	if (settings.out.empty()) { std::cerr << stamp("ERROR") << "No output value specified..." << std::endl; return 1; }
+	if (settings.in.empty()) return !fail("No input value specified...");
+	if (cmd.check && !cmd.check(settings, own)) return 1;
 	program_message();
-	std::cerr << stamp("LOG") << "Calling calc..." << std::endl;
+	std::cerr << stamp("LOG") << "Calling " << cmd.name << "..." << std::endl;
 	tomahawk::twk_ld ld;
 	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Compute(settings) ? 0 : 1;
+	return cmd.run(ld, settings, own) ? 0 : 1;
 }
+
+// The long names of `calc` (the reference's), of the six commands that reduce calc's records, and of `relationship`
+static const struct option CALC_LONG_OPTIONS[] = {
+	{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
+	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
+	{"low-memory", optional_argument, 0, 'm'}, {"block-size", optional_argument, 0, 'b'}, {"bitmaps", optional_argument, 0, 'M'},
+	{"compression-level", optional_argument, 0, 'k'}, {"cross-chr-only", no_argument, 0, 'X'}, {"no-cross-chr", no_argument, 0, 'x'},
+	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
+	{"samples", optional_argument, 0, 'S'}, {"minR2", optional_argument, 0, 'r'}, {"detailedProgress", no_argument, 0, 'd'},
+	{"silent", no_argument, 0, 's'}, {"windowBases", optional_argument, 0, 'w'},
+	{"engine-option", required_argument, 0, 1000}, {0, 0, 0, 0}};
+static const struct option REDUCE_LONG_OPTIONS[] = {
+	{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
+	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
+	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
+	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
+	{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
+	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
+	{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
+	{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
+	{0, 0, 0, 0}};
+static const struct option RELATIONSHIP_LONG_OPTIONS[] = {
+	{"input", required_argument, 0, 'i'}, {"interval", required_argument, 0, 'I'}, {"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'},
+	{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000},
+	{"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'}, {"minR2", required_argument, 0, 'r'}, {"windowBases", required_argument, 0, 'w'},
+	{"parts", required_argument, 0, 'c'}, {"partStart", required_argument, 0, 'C'}, {"minP", required_argument, 0, 'P'}, {0, 0, 0, 0}};
+
+// `calc`'s own options: the reference's low-memory modes and block size (accepted, unused here) and the compression level
+static Took calc_option(int c, const char* arg, twk_ld_settings& settings, NoOptions&) {
+	switch (c) {
+	case 'm': settings.low_memory = true; return took;
+	case 'M': settings.force_phased = true; settings.low_memory = true; settings.bitmaps = true; return took;
+	case 'b':
+		settings.bl_size = atoi(arg);
+		return settings.bl_size > 0 || fail("Cannot have a non-positive number of entries in a block!") ? took : failed;
+	case 'k': settings.c_level = atoi(arg); return took;
+	}
+	return declined;
+}
+static const Command<NoOptions> CALC = {
+	"calc", "  calc     calculate linkage disequilibrium: tomahawk calc [options] -i <in.twk> -o <output.two>\n", calc_usage,
+	"i:o:t:puP:a:A:r:w:S:I:sdc:C:mMb:xXk:?", CALC_LONG_OPTIONS, 0.1, {}, nullptr, calc_option,
+	[](twk_ld_settings& settings, NoOptions&) { return !settings.out.empty() || fail("No output value specified..."); },
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const NoOptions&) { return ld.Compute(settings); }};
 
 // `tomahawk ldscore` (not in the reference): per-variant sums of r2 over the records `calc` would write, reduced on the GPU.
 static void ldscore_usage() {
@@ -164,176 +267,11 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-// The options `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay` and `ldaggregate` share (-P is accepted only as 1 by all; `prune`, `clump` and `ldmatrix` have no
-// -c / -C; `clump` adds its association file and thresholds, `ldmatrix` its statistic, fill and text switch, `lddecay` its range and number of
-// bins, `ldaggregate` its bins per axis, statistic, reduction and minimum count).  -> 0, or 1 after an error message.
-enum ReduceCommand { REDUCE_SCORE, REDUCE_PRUNE, REDUCE_CLUMP, REDUCE_MATRIX, REDUCE_DECAY, REDUCE_AGGREGATE };
-static int reduce_options(int argc, char** argv, ReduceCommand cmd, tomahawk::twk_ld_settings& settings, std::vector<std::pair<std::string, long long>>& engine_options,
-                          tomahawk::twk_clump_settings* clump = nullptr, tomahawk::twk_matrix_settings* matrix = nullptr, tomahawk::twk_decay_settings* decay = nullptr,
-                          tomahawk::twk_aggregate_settings* aggregate = nullptr) {
-	const bool prune = cmd == REDUCE_PRUNE;
-	static struct option long_options[] = {
-		{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
-		{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
-		{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
-		{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
-		{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
-		{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
-		{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
-		{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
-		{0, 0, 0, 0}};
-	bool range_given = false;
-	int c, option_index = 0;
-	while ((c = getopt_long(argc, argv, clump ? "i:o:t:puP:r:w:I:c:C:a:1:2:?" : matrix ? "i:o:t:puP:r:w:I:c:C:s:f:T?" : decay ? "i:o:t:puP:r:w:I:c:C:d:b:?" : aggregate ? "i:o:t:puP:r:w:I:c:C:x:y:s:R:m:?" : "i:o:t:puP:r:w:I:c:C:?", long_options, &option_index)) != -1) {
-		if (prune && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot prune a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
-		if (cmd == REDUCE_CLUMP && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot clump a part of the pair space (-c / -C): the walk needs every pair" << std::endl; return 1; }
-		if (cmd == REDUCE_MATRIX && (c == 'c' || c == 'C')) { std::cerr << stamp("ERROR") << "Cannot fill a part of the pair space (-c / -C): the matrix needs every pair" << std::endl; return 1; }
-		if (!clump && (c == 'a' || c == '1' || c == '2')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
-		if (!matrix && (c == 'f' || c == 'T' || (c == 's' && !aggregate))) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
-		if (!decay && (c == 'd' || c == 'b')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
-		if (!aggregate && (c == 'x' || c == 'y' || c == 'R' || c == 'm')) { std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl; return 1; }
-		switch (c) {
-		case 'x': case 'y': case 'm': {
-			const std::string a(optarg);
-			const char* const what = c == 'x' ? "number of x bins (-x)" : c == 'y' ? "number of y bins (-y)" : "minimum count (-m)";
-			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << stamp("ERROR") << "The " << what << " must be a non-negative integer: " << a << std::endl; return 1; }
-			const double v = atof(optarg);
-			if (c == 'm') {
-				if (!(v <= 9007199254740992.0)) { std::cerr << stamp("ERROR") << "The minimum count (-m) must be at most 2^53" << std::endl; return 1; }
-				aggregate->min_count = (int64_t)v;
-			} else {
-				if (!(v >= 1 && v <= 4096)) { std::cerr << stamp("ERROR") << "The " << what << " must be between 1 and 4096" << std::endl; return 1; }
-				(c == 'x' ? aggregate->x_bins : aggregate->y_bins) = (int32_t)v;
-			}
-			break;
-		}
-		case 'R': {
-			const std::string a(optarg);
-			if (a == "mean") aggregate->reduce = 0;
-			else if (a == "count" || a == "n") aggregate->reduce = 1;
-			else if (a == "min") aggregate->reduce = 2;
-			else if (a == "max") aggregate->reduce = 3;
-			else if (a == "sd") aggregate->reduce = 4;
-			else if (a == "total") aggregate->reduce = 5;
-			else { std::cerr << stamp("ERROR") << "Unknown reduction (-R): " << a << " - one of mean, count, n, min, max, sd, total" << std::endl; return 1; }
-			break;
-		}
-		case 'd': case 'b': {
-			const std::string a(optarg);
-			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << stamp("ERROR") << "The " << (c == 'd' ? "range (-d)" : "number of bins (-b)") << " must be a non-negative integer: " << a << std::endl; return 1; }
-			const double v = atof(optarg);
-			if (c == 'd') {
-				if (!(v >= 1 && v <= 4294967295.0)) { std::cerr << stamp("ERROR") << "The range (-d) must be between 1 and 4294967295 bases" << std::endl; return 1; }
-				decay->range_bp = (int64_t)v; range_given = true;
-			} else {
-				if (!(v >= 1 && v <= 4096)) { std::cerr << stamp("ERROR") << "The number of bins (-b) must be between 1 and 4096" << std::endl; return 1; }
-				decay->n_bins = (int32_t)v;
-			}
-			break;
-		}
-		case 's': {
-			const std::string a(optarg);
-			int32_t& stat = aggregate ? aggregate->stat : matrix->stat;
-			if (a == "r") stat = TWK_HIP_STAT_R;
-			else if (a == "r2") stat = TWK_HIP_STAT_R2;
-			else if (a == "D") stat = TWK_HIP_STAT_D;
-			else if (a == "Dprime") stat = TWK_HIP_STAT_DPRIME;
-			else { std::cerr << stamp("ERROR") << "Unknown statistic (-s): " << a << " - one of r, r2, D, Dprime" << std::endl; return 1; }
-			break;
-		}
-		case 'f': {
-			char* end = nullptr;
-			const float v = strtof(optarg, &end);      // (nan and inf are numbers here: a fill may be either)
-			if (end == optarg || *end) { std::cerr << stamp("ERROR") << "The fill value (-f) must be a number: " << optarg << std::endl; return 1; }
-			matrix->fill = v;
-			break;
-		}
-		case 'T': matrix->text = true; break;
-		case 'a': clump->assoc = optarg; break;
-		case '1': case '2': {
-			char* end = nullptr;
-			const double t = strtod(optarg, &end);
-			if (end == optarg || *end || !(t >= 0 && t <= 1)) { std::cerr << stamp("ERROR") << "A clumping threshold (-" << (char)c << ") must be a P-value in [0, 1]" << std::endl; return 1; }
-			(c == '1' ? clump->p1 : clump->p2) = t;
-			break;
-		}
-		case 'i': settings.in = optarg; break;
-		case 'o': settings.out = optarg; break;
-		case 'I': settings.ival_strings.push_back(optarg); break;
-		case 'p': settings.force_phased = true; settings.forced_unphased = false; break;
-		case 'u': settings.forced_unphased = true; settings.force_phased = false; break;
-		case 't':
-			settings.n_threads = atoi(optarg);
-			if (settings.n_threads <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of worker threads" << std::endl; return 1; }
-			break;
-		case 'c':
-			settings.n_chunks = atoi(optarg);
-			if (settings.n_chunks <= 0) { std::cerr << stamp("ERROR") << "Cannot have a negative or zero amount of partitions" << std::endl; return 1; }
-			break;
-		case 'C':
-			settings.c_chunk = atoi(optarg) - 1;   // 1-based on the command line, as for calc
-			if (settings.c_chunk < 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive start partition" << std::endl; return 1; }
-			break;
-		case 'r':
-			settings.minR2 = atof(optarg);
-			if (settings.minR2 < 0) { std::cerr << stamp("ERROR") << "Cannot have a negative minimum R-squared value" << std::endl; return 1; }
-			if (settings.minR2 > 1) { std::cerr << stamp("ERROR") << "Cannot have minimum R-squared value > 1" << std::endl; return 1; }
-			break;
-		case 'P':
-			settings.minP = atof(optarg);
-			if (!(settings.minP >= 1)) {
-				std::cerr << stamp("ERROR") << (cmd == REDUCE_MATRIX ? "Cannot fill a matrix with a cutoff P-value below 1: the matrix holds every record and Fisher's exact test is not run" :
-				                                cmd == REDUCE_AGGREGATE ? "Cannot aggregate with a cutoff P-value below 1: an aggregate takes in every record and Fisher's exact test is not run" :
-				                                cmd == REDUCE_DECAY ? "Cannot bin with a cutoff P-value below 1: a decay curve averages over every record and Fisher's exact test is not run" :
-				                                cmd == REDUCE_CLUMP ? "Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run" :
-				                                prune ? "Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run"
-				                                      : "Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run") << std::endl;
-				return 1;
-			}
-			if (settings.minP > 1) { std::cerr << stamp("ERROR") << "Cannot have a cutoff P-value > 1" << std::endl; return 1; }
-			break;
-		case 'w': {
-			settings.window = true;
-			const std::string a(optarg);
-			if (!std::regex_match(a, std::regex("^(([0-9]+)|([0-9]+[eE]{1}[0-9]+))$"))) { std::cerr << "not an integer" << std::endl; return 1; }
-			settings.l_window = std::regex_match(a, std::regex("^[0-9]+$")) ? atoi(optarg) : (int32_t)atof(optarg);
-			if (settings.l_window <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive window size" << std::endl; return 1; }
-			break;
-		}
-		case 1000: {
-			const std::string a(optarg);
-			const size_t eq = a.find('=');
-			if (eq == std::string::npos || eq == 0 || eq + 1 >= a.size()) { std::cerr << stamp("ERROR") << "--engine-option wants key=value" << std::endl; return 1; }
-			engine_options.emplace_back(a.substr(0, eq), atoll(a.c_str() + eq + 1));
-			break;
-		}
-		default:
-			std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl;
-			return 1;
-		}
-	}
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
-	if (clump && clump->assoc.empty()) { std::cerr << stamp("ERROR") << "No association file specified (-a)..." << std::endl; return 1; }
-	if (matrix && (settings.out.empty() || settings.out == "-")) { std::cerr << stamp("ERROR") << "No output prefix specified (-o)..." << std::endl; return 1; }
-	if (decay && !range_given && settings.window) decay->range_bp = settings.l_window;      // (only -w given: no pair lies further apart)
-	if (decay && decay->range_bp < decay->n_bins) { std::cerr << stamp("ERROR") << "The range (-d, or -w without -d: " << decay->range_bp << ") cannot be smaller than the number of bins (-b: " << decay->n_bins << "): a bin would be 0 bases wide" << std::endl; return 1; }
-	if (clump && clump->p1 > clump->p2) { std::cerr << stamp("ERROR") << "The index threshold (-1) cannot be above the secondary threshold (-2)" << std::endl; return 1; }
-	return 0;
-}
-
-static int ldscore(int argc, char** argv) {
-	if (argc < 3) { ldscore_usage(); return 1; }
-	tomahawk::twk_ld_settings settings;
-	settings.minR2 = 0;
-	settings.out = "-";
-	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, REDUCE_SCORE, settings, engine_options)) return 1;
-	program_message();
-	std::cerr << stamp("LOG") << "Calling ldscore..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Score(settings) ? 0 : 1;
-}
+static const Command<NoOptions> LDSCORE = {
+	"ldscore", "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n", ldscore_usage,
+	"i:o:t:puP:r:w:I:c:C:?", REDUCE_LONG_OPTIONS, 0, {},
+	"Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run", nullptr, nullptr,
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const NoOptions&) { return ld.Score(settings); }};
 
 // `tomahawk prune` (not in the reference): greedy LD pruning in file order over the records `calc` would write, decided on the GPU.
 static void prune_usage() {
@@ -360,18 +298,11 @@ static void prune_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int prune(int argc, char** argv) {
-	if (argc < 3) { prune_usage(); return 1; }
-	tomahawk::twk_ld_settings settings;      // (-r: calc's default)
-	settings.out = "-";
-	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, REDUCE_PRUNE, settings, engine_options)) return 1;
-	program_message();
-	std::cerr << stamp("LOG") << "Calling prune..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Prune(settings) ? 0 : 1;
-}
+static const Command<NoOptions> PRUNE = {      // (-r: calc's default)
+	"prune", "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n", prune_usage,
+	"i:o:t:puP:r:w:I:c:C:?", REDUCE_LONG_OPTIONS, 0.1, {{"cC", "Cannot prune a part of the pair space (-c / -C): the walk needs every pair"}},
+	"Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run", nullptr, nullptr,
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const NoOptions&) { return ld.Prune(settings); }};
 
 // `tomahawk clump` (not in the reference): LD clumping (PLINK's --clump) over the records `calc` would write, decided on the GPU.
 static void clump_usage() {
@@ -410,19 +341,24 @@ static void clump_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int clump(int argc, char** argv) {
-	if (argc < 3) { clump_usage(); return 1; }
-	tomahawk::twk_ld_settings settings;      // (-r, -w: calc's defaults)
-	settings.out = "-";
-	tomahawk::twk_clump_settings cs;
-	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, REDUCE_CLUMP, settings, engine_options, &cs)) return 1;
-	program_message();
-	std::cerr << stamp("LOG") << "Calling clump..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Clump(settings, cs) ? 0 : 1;
+static Took clump_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_clump_settings& clump) {
+	if (c == 'a') { clump.assoc = arg; return took; }
+	if (c != '1' && c != '2') return declined;
+	char* end = nullptr;
+	const double t = strtod(arg, &end);
+	if (end == arg || *end || !(t >= 0 && t <= 1)) { fail(std::string("A clumping threshold (-") + (char)c + ") must be a P-value in [0, 1]"); return failed; }
+	(c == '1' ? clump.p1 : clump.p2) = t;
+	return took;
 }
+static const Command<tomahawk::twk_clump_settings> CLUMP = {      // (-r, -w: calc's defaults)
+	"clump", "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n", clump_usage,
+	"i:o:t:puP:r:w:I:c:C:a:1:2:?", REDUCE_LONG_OPTIONS, 0.1, {{"cC", "Cannot clump a part of the pair space (-c / -C): the walk needs every pair"}},
+	"Cannot clump with a cutoff P-value below 1: clumping looks at every record and Fisher's exact test is not run", clump_option,
+	[](twk_ld_settings&, tomahawk::twk_clump_settings& clump) {
+		if (clump.assoc.empty()) return fail("No association file specified (-a)...");
+		return !(clump.p1 > clump.p2) || fail("The index threshold (-1) cannot be above the secondary threshold (-2)");
+	},
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_clump_settings& clump) { return ld.Clump(settings, clump); }};
 
 // `tomahawk ldmatrix` (not in the reference): the dense LD matrix of a region, filled on the GPU from the records `calc` would write.
 static void ldmatrix_usage() {
@@ -456,19 +392,20 @@ static void ldmatrix_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int ldmatrix(int argc, char** argv) {
-	if (argc < 3) { ldmatrix_usage(); return 1; }
-	tomahawk::twk_ld_settings settings;
-	settings.minR2 = 0;
-	tomahawk::twk_matrix_settings ms;
-	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, REDUCE_MATRIX, settings, engine_options, nullptr, &ms)) return 1;
-	program_message();
-	std::cerr << stamp("LOG") << "Calling ldmatrix..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Matrix(settings, ms) ? 0 : 1;
+static Took matrix_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_matrix_settings& matrix) {
+	switch (c) {
+	case 's': return stat_option(arg, tomahawk::LD_STATS, matrix.stat) ? took : failed;
+	case 'f': return fill_option(arg, matrix.fill) ? took : failed;
+	case 'T': matrix.text = true; return took;
+	}
+	return declined;
 }
+static const Command<tomahawk::twk_matrix_settings> LDMATRIX = {
+	"ldmatrix", "  ldmatrix dense LD matrix of a region (signed r, r2, D or D'), filled on the GPU\n", ldmatrix_usage,
+	"i:o:t:puP:r:w:I:c:C:s:f:T?", REDUCE_LONG_OPTIONS, 0, {{"cC", "Cannot fill a part of the pair space (-c / -C): the matrix needs every pair"}},
+	"Cannot fill a matrix with a cutoff P-value below 1: the matrix holds every record and Fisher's exact test is not run", matrix_option,
+	[](twk_ld_settings& settings, tomahawk::twk_matrix_settings&) { return !(settings.out.empty() || settings.out == "-") || fail("No output prefix specified (-o)..."); },
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_matrix_settings& matrix) { return ld.Matrix(settings, matrix); }};
 
 // `tomahawk relationship`: the sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU.  The reference's name and its -i / -I;
 // its numbers are not reproduced (include/twk_hip.h, twk_hip_relationship).
@@ -503,67 +440,27 @@ static void relationship_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int relationship(int argc, char** argv) {
-	if (argc < 3) { relationship_usage(); return 1; }
-	static struct option long_options[] = {
-		{"input", required_argument, 0, 'i'}, {"interval", required_argument, 0, 'I'}, {"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'},
-		{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000},
-		{"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'}, {"minR2", required_argument, 0, 'r'}, {"windowBases", required_argument, 0, 'w'},
-		{"parts", required_argument, 0, 'c'}, {"partStart", required_argument, 0, 'C'}, {"minP", required_argument, 0, 'P'}, {0, 0, 0, 0}};
-	tomahawk::twk_ld_settings settings;
-	tomahawk::twk_relationship_settings rs;
-	std::vector<std::pair<std::string, long long>> engine_options;
-	int c, option_index = 0;
-	while ((c = getopt_long(argc, argv, "i:I:s:f:o:Tt:pur:w:c:C:P:?", long_options, &option_index)) != -1) {
-		switch (c) {
-		case 'p': case 'u': std::cerr << stamp("ERROR") << "Cannot force a phasing (-" << (char)c << "): samples are compared by genotype, phase is ignored" << std::endl; return 1;
-		case 'r': std::cerr << stamp("ERROR") << "Cannot apply an R-squared cut-off (-r): no variant pair is formed" << std::endl; return 1;
-		case 'w': std::cerr << stamp("ERROR") << "Cannot apply a window (-w): samples are compared over every selected variant" << std::endl; return 1;
-		case 'c': case 'C': std::cerr << stamp("ERROR") << "Cannot relate over a part of the pair space (-" << (char)c << "): samples are compared over every selected variant" << std::endl; return 1;
-		case 'P': std::cerr << stamp("ERROR") << "Cannot apply a cutoff P-value (-P): the matrix is counted, no test is run" << std::endl; return 1;
-		case 'i': settings.in = optarg; break;
-		case 'I': settings.ival_strings.push_back(optarg); break;
-		case 'o': settings.out = optarg; break;
-		case 'T': rs.text = true; break;
-		case 't':
-			settings.n_threads = atoi(optarg);
-			if (settings.n_threads <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of worker threads" << std::endl; return 1; }
-			break;
-		case 's': {
-			const std::string a(optarg);
-			if (a == "ibs") rs.stat = TWK_HIP_REL_IBS;
-			else if (a == "ibs0") rs.stat = TWK_HIP_REL_IBS0;
-			else if (a == "king") rs.stat = TWK_HIP_REL_KING;
-			else { std::cerr << stamp("ERROR") << "Unknown statistic (-s): " << a << " - one of ibs, ibs0, king" << std::endl; return 1; }
-			break;
-		}
-		case 'f': {
-			char* end = nullptr;
-			const double v = strtod(optarg, &end);      // (nan and inf are numbers here: a fill may be either)
-			if (end == optarg || *end) { std::cerr << stamp("ERROR") << "The fill value (-f) must be a number: " << optarg << std::endl; return 1; }
-			rs.fill = v;
-			break;
-		}
-		case 1000: {
-			const std::string a(optarg);
-			const size_t eq = a.find('=');
-			if (eq == std::string::npos || eq == 0 || eq + 1 >= a.size()) { std::cerr << stamp("ERROR") << "--engine-option wants key=value" << std::endl; return 1; }
-			engine_options.emplace_back(a.substr(0, eq), atoll(a.c_str() + eq + 1));
-			break;
-		}
-		default:
-			std::cerr << stamp("ERROR") << "Unrecognized option: " << (char)c << std::endl;
-			return 1;
-		}
+static Took relationship_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_relationship_settings& rel) {
+	switch (c) {
+	case 's': return stat_option(arg, tomahawk::REL_STATS, rel.stat) ? took : failed;
+	case 'f': return fill_option(arg, rel.fill) ? took : failed;
+	case 'T': rel.text = true; return took;
 	}
-	if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No input value specified..." << std::endl; return 1; }
-	if (rs.text && (settings.out.empty() || settings.out == "-")) { std::cerr << stamp("ERROR") << "-T names the file written for -o PREFIX: without -o the text goes to stdout anyway" << std::endl; return 1; }
-	program_message();
-	std::cerr << stamp("LOG") << "Calling relationship..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Relationship(settings, rs) ? 0 : 1;
+	return declined;
 }
+static const Command<tomahawk::twk_relationship_settings> RELATIONSHIP = {
+	"relationship", "  relationship  sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU\n", relationship_usage,
+	"i:I:s:f:o:Tt:pur:w:c:C:P:?", RELATIONSHIP_LONG_OPTIONS, 0.1,
+	{{"pu", "Cannot force a phasing (-%c): samples are compared by genotype, phase is ignored"},
+	 {"r", "Cannot apply an R-squared cut-off (-r): no variant pair is formed"},
+	 {"w", "Cannot apply a window (-w): samples are compared over every selected variant"},
+	 {"cC", "Cannot relate over a part of the pair space (-%c): samples are compared over every selected variant"},
+	 {"P", "Cannot apply a cutoff P-value (-P): the matrix is counted, no test is run"}},
+	nullptr, relationship_option,
+	[](twk_ld_settings& settings, tomahawk::twk_relationship_settings& rel) {
+		return !(rel.text && (settings.out.empty() || settings.out == "-")) || fail("-T names the file written for -o PREFIX: without -o the text goes to stdout anyway");
+	},
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_relationship_settings& rel) { return ld.Relationship(settings, rel); }};
 
 // `tomahawk lddecay`: mean r2 by the distance between two variants over the records `calc` would write, binned and summed on the GPU.  (The
 // reference's `decay` reads a .two file, and its range is -w; here -w keeps calc's meaning, the window of the computation.)
@@ -596,20 +493,30 @@ static void lddecay_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int lddecay(int argc, char** argv) {
-	if (argc < 3) { lddecay_usage(); return 1; }
-	tomahawk::twk_ld_settings settings;
-	settings.minR2 = 0;
-	settings.out = "-";
-	tomahawk::twk_decay_settings ds;
-	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, REDUCE_DECAY, settings, engine_options, nullptr, nullptr, &ds)) return 1;
-	program_message();
-	std::cerr << stamp("LOG") << "Calling lddecay..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Decay(settings, ds) ? 0 : 1;
+static const std::string ONE_TO_MAX_BINS = "between 1 and " + std::to_string(tomahawk::MAX_BINS);
+struct DecayOptions { tomahawk::twk_decay_settings decay; bool range_given = false; };
+static Took decay_option(int c, const char* arg, twk_ld_settings&, DecayOptions& own) {
+	double v = 0;
+	if (c == 'd') {
+		if (!integer_option(arg, "range (-d)", 1, (double)tomahawk::MAX_RANGE_BP, "between 1 and " + std::to_string(tomahawk::MAX_RANGE_BP) + " bases", v)) return failed;
+		own.decay.range_bp = (int64_t)v; own.range_given = true;
+		return took;
+	}
+	if (c != 'b') return declined;
+	if (!integer_option(arg, "number of bins (-b)", 1, tomahawk::MAX_BINS, ONE_TO_MAX_BINS, v)) return failed;
+	own.decay.n_bins = (int32_t)v;
+	return took;
 }
+static const Command<DecayOptions> LDDECAY = {
+	"lddecay", "  lddecay  LD decay: R-squared by the distance between two variants, binned and summed on the GPU\n", lddecay_usage,
+	"i:o:t:puP:r:w:I:c:C:d:b:?", REDUCE_LONG_OPTIONS, 0, {},
+	"Cannot bin with a cutoff P-value below 1: a decay curve averages over every record and Fisher's exact test is not run", decay_option,
+	[](twk_ld_settings& settings, DecayOptions& own) {
+		tomahawk::twk_decay_settings& d = own.decay;
+		if (!own.range_given && settings.window) d.range_bp = settings.l_window;      // (only -w given: no pair lies further apart)
+		return d.range_bp >= d.n_bins || fail("The range (-d, or -w without -d: " + std::to_string(d.range_bp) + ") cannot be smaller than the number of bins (-b: " + std::to_string(d.n_bins) + "): a bin would be 0 bases wide");
+	},
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const DecayOptions& own) { return ld.Decay(settings, own.decay); }};
 
 // `tomahawk ldaggregate`: the LD of every record `calc` would write rasterised into x-by-y cells, binned and summed on the GPU.  (The
 // reference's `aggregate` reads a .two file and writes a binary .twa; its -c, the minimum count, is -m here: -c is the chunk flag.)
@@ -645,20 +552,30 @@ static void ldaggregate_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static int ldaggregate(int argc, char** argv) {
-	if (argc < 3) { ldaggregate_usage(); return 1; }
-	tomahawk::twk_ld_settings settings;
-	settings.minR2 = 0;
-	settings.out = "-";
-	tomahawk::twk_aggregate_settings as;
-	std::vector<std::pair<std::string, long long>> engine_options;
-	if (reduce_options(argc, argv, REDUCE_AGGREGATE, settings, engine_options, nullptr, nullptr, nullptr, &as)) return 1;
-	program_message();
-	std::cerr << stamp("LOG") << "Calling ldaggregate..." << std::endl;
-	tomahawk::twk_ld ld;
-	for (const auto& kv : engine_options) ld.SetEngineOption(kv.first, kv.second);
-	return ld.Aggregate(settings, as) ? 0 : 1;
+static Took aggregate_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_aggregate_settings& a) {
+	double v = 0;
+	switch (c) {
+	case 'x': case 'y':
+		if (!integer_option(arg, c == 'x' ? "number of x bins (-x)" : "number of y bins (-y)", 1, tomahawk::MAX_BINS, ONE_TO_MAX_BINS, v)) return failed;
+		(c == 'x' ? a.x_bins : a.y_bins) = (int32_t)v;
+		return took;
+	case 'm':
+		if (!integer_option(arg, "minimum count (-m)", 0, 9007199254740992.0, "at most 2^53", v)) return failed;
+		a.min_count = (int64_t)v;
+		return took;
+	case 'R':
+		a.reduce = strcmp(arg, "n") == 0 ? (int32_t)tomahawk::TWK_AGGREGATE_COUNT : tomahawk::AGGREGATE_REDUCTIONS.value(arg);
+		if (a.reduce < 0) { fail(std::string("Unknown reduction (-R): ") + arg + " - one of mean, count, n, min, max, sd, total"); return failed; }
+		return took;
+	case 's': return stat_option(arg, tomahawk::LD_STATS, a.stat) ? took : failed;
+	}
+	return declined;
 }
+static const Command<tomahawk::twk_aggregate_settings> LDAGGREGATE = {
+	"ldaggregate", "  ldaggregate  LD aggregate: r2, r, D or D' rasterised into x-by-y bins, summed exactly on the GPU\n", ldaggregate_usage,
+	"i:o:t:puP:r:w:I:c:C:x:y:s:R:m:?", REDUCE_LONG_OPTIONS, 0, {},
+	"Cannot aggregate with a cutoff P-value below 1: an aggregate takes in every record and Fisher's exact test is not run", aggregate_option, nullptr,
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_aggregate_settings& a) { return ld.Aggregate(settings, a); }};
 
 // `tomahawk concat` (lib/concat.h:63-251): copy the compressed blocks of several .two files into one.
 static int concat(int argc, char** argv) {
@@ -902,10 +819,7 @@ static int scalc(int argc, char** argv) {
 		case 'I': settings.ival_strings.push_back(optarg); break;
 		case 'm': settings.low_memory = true; break;
 		case 'M': settings.force_phased = true; settings.low_memory = true; settings.bitmaps = true; break;
-		case 't':
-			settings.n_threads = atoi(optarg);
-			if (settings.n_threads <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of worker threads" << std::endl; return 1; }
-			break;
+		case 't': if (!thread_option(optarg, settings.n_threads)) return 1; break;
 		case 'b':
 			settings.bl_size = atoi(optarg);
 			if (settings.bl_size <= 0) { std::cerr << stamp("ERROR") << "Cannot have a non-positive number of entries in a block!" << std::endl; return 1; }
@@ -942,50 +856,55 @@ static int scalc(int argc, char** argv) {
 	return ld.ComputeSingle(settings, true, true) ? 0 : 1;
 }
 
+// Every command, in the order `tomahawk` without arguments lists them: an engine command's row, or a host tool that parses for itself
+// (the reference's parsers, with the reference's words) with its name, its line of that list and, for two, what else selects it.
+struct Entry {
+	const char* name; const char* summary;      // summary: its line of `tomahawk` without arguments
+	int (*main)(int, char**);
+	int said;                                   // its place in the "Illegal command" sentence, which ends with the .two tools in another order
+	const char* alias; bool by_prefix;          // what else selects it: another name; any word that begins with its name
+};
+template <const auto& CMD> static int engine(int argc, char** argv) { return run_command(CMD, argc, argv); }
+static const Entry ENTRIES[] = {
+	{"import", "  import   convert VCF text (plain / gzip) to .twk\n", import_cmd, 0},
+	{CALC.name, CALC.summary, engine<CALC>, 1},
+	{"scalc", "  scalc    linkage disequilibrium of one site against its neighbourhood\n", scalc, 2, "calc-single"},
+	{RELATIONSHIP.name, RELATIONSHIP.summary, engine<RELATIONSHIP>, 3},
+	{LDSCORE.name, LDSCORE.summary, engine<LDSCORE>, 4},
+	{PRUNE.name, PRUNE.summary, engine<PRUNE>, 5},
+	{CLUMP.name, CLUMP.summary, engine<CLUMP>, 6},
+	{LDMATRIX.name, LDMATRIX.summary, engine<LDMATRIX>, 7},
+	{LDDECAY.name, LDDECAY.summary, engine<LDDECAY>, 8},
+	{LDAGGREGATE.name, LDAGGREGATE.summary, engine<LDAGGREGATE>, 9},
+	{"sort", "  sort     sort a .two file\n", sort_cmd, 12},
+	{"view", "  view     convert, filter and slice .two files\n", view, 11},
+	{"concat", "  concat   concatenate .two files from the same set of samples\n", concat, 10, nullptr, true}};
+static const size_t N_ENTRIES = sizeof(ENTRIES) / sizeof(ENTRIES[0]);
+
 static int run_main(int argc, char** argv) {
 	if (argc == 1) {           // reference: lib/main.cpp:28-60 lists its commands
 		program_message();
-		std::cerr << "Usage: tomahawk <command> [options]\n\n"
-		             "Commands:\n"
-		             "  import   convert VCF text (plain / gzip) to .twk\n"
-		             "  calc     calculate linkage disequilibrium: tomahawk calc [options] -i <in.twk> -o <output.two>\n"
-		             "  scalc    linkage disequilibrium of one site against its neighbourhood\n"
-	             "  relationship  sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU\n"
-		             "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n"
-		             "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n"
-		             "  clump    LD clumping by association P-value (an index variant per variant), decided on the GPU\n"
-		             "  ldmatrix dense LD matrix of a region (signed r, r2, D or D'), filled on the GPU\n"
-		             "  lddecay  LD decay: R-squared by the distance between two variants, binned and summed on the GPU\n"
-		             "  ldaggregate  LD aggregate: r2, r, D or D' rasterised into x-by-y bins, summed exactly on the GPU\n"
-		             "  sort     sort a .two file\n"
-		             "  view     convert, filter and slice .two files\n"
-		             "  concat   concatenate .two files from the same set of samples\n" << std::endl;
+		std::cerr << "Usage: tomahawk <command> [options]\n\nCommands:\n";
+		for (const Entry& e : ENTRIES) std::cerr << e.summary;
+		std::cerr << std::endl;
 		return 1;
 	}
 	// The host tools allocate and free MB-sized block buffers on hundreds of threads; served by
 	// mmap/munmap (glibc's default above 128 KiB) that serialises on the address-space lock.
 	mallopt(M_MMAP_THRESHOLD, 1 << 30);
 	mallopt(M_TRIM_THRESHOLD, 1 << 30);
-	g_argv.assign(argv, argv + argc);
 	tomahawk::LITERAL_COMMAND_LINE = "tomahawk";
 	for (int i = 1; i < argc; ++i) tomahawk::LITERAL_COMMAND_LINE += " " + std::string(argv[i]);
-	if (strcmp(argv[1], "calc") == 0) return calc(argc, argv);
-	if (strcmp(argv[1], "relationship") == 0) return relationship(argc, argv);
-	if (strcmp(argv[1], "ldscore") == 0) return ldscore(argc, argv);
-	if (strcmp(argv[1], "prune") == 0) return prune(argc, argv);
-	if (strcmp(argv[1], "clump") == 0) return clump(argc, argv);
-	if (strcmp(argv[1], "ldmatrix") == 0) return ldmatrix(argc, argv);
-	if (strcmp(argv[1], "lddecay") == 0) return lddecay(argc, argv);
-	if (strcmp(argv[1], "ldaggregate") == 0) return ldaggregate(argc, argv);
-	if (strncmp(argv[1], "concat", 6) == 0) return concat(argc, argv);
-	if (strcmp(argv[1], "calc-single") == 0 || strcmp(argv[1], "scalc") == 0) return scalc(argc, argv);
-	if (strcmp(argv[1], "view") == 0) return view(argc, argv);
-	if (strcmp(argv[1], "sort") == 0) return sort_cmd(argc, argv);
-	if (strcmp(argv[1], "import") == 0) return import_cmd(argc, argv);
+	for (const Entry& e : ENTRIES)
+		if (strcmp(argv[1], e.name) == 0 || (e.alias && strcmp(argv[1], e.alias) == 0) || (e.by_prefix && strncmp(argv[1], e.name, strlen(e.name)) == 0)) return e.main(argc, argv);
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }
 	if (strcmp(argv[1], "--help") == 0 || strcmp(argv[1], "help") == 0) { calc_usage(); return 0; }
 	program_message();
-	std::cerr << stamp("ERROR") << "Illegal command: only `import`, `calc`, `scalc`, `relationship`, `ldscore`, `prune`, `clump`, `ldmatrix`, `lddecay`, `ldaggregate`, `concat`, `view` and `sort` are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance and `ldaggregate` into x-by-y cells without a .two; `relationship` keeps the reference's name, not its numbers)" << std::endl;
+	const char* said[N_ENTRIES] = {};
+	for (const Entry& e : ENTRIES) said[e.said] = e.name;
+	std::string names;
+	for (size_t k = 0; k < N_ENTRIES; ++k) names += std::string(k == 0 ? "`" : k + 1 < N_ENTRIES ? ", `" : " and `") + said[k] + "`";
+	std::cerr << stamp("ERROR") << "Illegal command: only " << names << " are provided by the MI355X engine (aggregate/decay/... are the reference's; `lddecay` bins by distance and `ldaggregate` into x-by-y cells without a .two; `relationship` keeps the reference's name, not its numbers)" << std::endl;
 	return 1;
 }
 

@@ -34,6 +34,7 @@
 #include "twk_aggregate_landscape.h"
 #include "twk_format.h"
 #include "twk_hip.h"
+#include "twk_ld_names.h"
 #include "twk_parallel.h"
 #include "twk_record_sink.h"
 #include "twk_util.h"
@@ -227,6 +228,19 @@ struct RunSpec {
 };
 }  // namespace
 
+// What is said before an output file is opened and after it did not open; the same for the input
+static void opening(const std::string& path) { std::cerr << stamp("LOG", "WRITER") << "Opening " << path << "..." << std::endl; }
+static bool opened(bool ok, const std::string& path) {
+	if (!ok) std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << path << "..." << std::endl;
+	return ok;
+}
+static bool open_input(TwkReader& reader, const std::string& path, bool announce) {
+	if (announce) std::cerr << stamp("LOG", "READER") << "Opening " << path << "..." << std::endl;
+	if (reader.open(path)) return true;
+	std::cerr << stamp("ERROR") << "Failed to open file: " << path << "... (" << reader.error << ")" << std::endl;
+	return false;
+}
+
 static bool open_output(twk_ld_settings& settings, const Header& in_hdr, TwoWriter& writer) {   // ld.cpp:583-618
 	std::string out = settings.out;
 	if (out.empty() || out == "-") {
@@ -238,14 +252,13 @@ static bool open_output(twk_ld_settings& settings, const Header& in_hdr, TwoWrit
 			const std::string bp = base_path(out);
 			out = (bp.size() ? bp + "/" : "") + base_name(out) + ".two";
 		}
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << out << "..." << std::endl;
+		opening(out);
 	}
 	settings.out = out;
 	Header hdr = in_hdr;
 	hdr.literals += "\n##tomahawk_calcVersion=" + std::string(TWK_AMD_VERSION) + "\n";
 	hdr.literals += "##tomahawk_calcCommand=" + command_line() + "; Date=" + datetime() + "\n";
-	if (!writer.open(out, hdr, settings.c_level)) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << out << "..." << std::endl; return false; }
-	return true;
+	return opened(writer.open(out, hdr, settings.c_level), out);
 }
 
 // ---- input: .twk blocks -> HBM (ld.cpp:370-465, ld_unpacker.h:44-123) ------------------------------------
@@ -800,8 +813,7 @@ static bool select_blocks(twk_ld_settings& settings, Selection& S, bool* nothing
 	if (settings.bitmaps || settings.low_memory)
 		std::cerr << stamp("LOG") << "Note: -m/-M are CPU memory-saving modes; the GPU engine keeps dense bit-planes in HBM." << std::endl;
 
-	std::cerr << stamp("LOG", "READER") << "Opening " << settings.in << "..." << std::endl;
-	if (!reader.open(settings.in)) { std::cerr << stamp("ERROR") << "Failed to open file: " << settings.in << "... (" << reader.error << ")" << std::endl; return false; }
+	if (!open_input(reader, settings.in, true)) return false;
 	const uint32_t n_samples = S.n_samples = (uint32_t)reader.hdr.samples.size();
 	std::cerr << stamp("LOG") << "Samples: " << pretty(n_samples) << "..." << std::endl;
 
@@ -949,6 +961,8 @@ struct ReduceCommand {
 	using clock = std::chrono::steady_clock;
 	twk_ld_settings& settings;
 	std::vector<uint32_t>& rid; std::vector<uint32_t>& pos;      // per variant of the uploaded selection (twk_ld_impl)
+	uint64_t& n_pairs; uint64_t& n_records;                      // the object's results (twk_ld_impl)
+	const std::vector<std::pair<std::string, int64_t>>& engine_options;
 	Selection S;
 	DeviceCtxs dc;
 	twk_hip_ctx* ctx = nullptr;
@@ -958,9 +972,16 @@ struct ReduceCommand {
 	clock::time_point t_load;
 	std::ofstream file;
 
-	// The input's name; the P cut-off (every: why the command cannot have one, "A score sums over every record"); -c / -C (partial: why
-	// not, "Cannot prune a part of the pair space: the walk needs every pair"; null: the command takes a part)
-	bool check(const char* every, const char* partial) const {
+	// (Impl is twk_ld::twk_ld_impl: private to twk_ld, so a struct out here cannot name it, only take it as a template's argument)
+	template <class Impl>
+	ReduceCommand(twk_ld_settings& settings_, Impl& impl) : settings(settings_), rid(impl.rid), pos(impl.pos), n_pairs(impl.n_pairs), n_records(impl.n_records), engine_options(impl.engine_options) {}
+
+	// How every method begins: the caller's settings taken, the results zeroed, and the checks common to all - the input's name; the P
+	// cut-off (every: why the command cannot have one, "A score sums over every record"); -c / -C (partial: why not, "Cannot prune a part
+	// of the pair space: the walk needs every pair"; null: the command takes a part)
+	bool begin(const twk_ld_settings& s, const char* every, const char* partial) {
+		settings = s;
+		n_pairs = n_records = 0;
 		if (settings.in.empty()) { std::cerr << stamp("ERROR") << "No file-name provided..." << std::endl; return false; }
 		if (!(settings.minP >= 1)) { std::cerr << stamp("ERROR") << every << ": a cutoff P-value below 1 is not supported (Fisher's test is not run)..." << std::endl; return false; }
 		if (partial && settings.n_chunks != 1) { std::cerr << stamp("ERROR") << partial << " (no -c / -C)..." << std::endl; return false; }
@@ -969,7 +990,7 @@ struct ReduceCommand {
 	// Selection, device, upload; mode, filters and options of the engine call.  Unless `ready` the command ends: `empty` - the selection
 	// holds nothing, nothing to do - is its success, `failed` an error, reported
 	enum Loaded { failed, empty, ready };
-	Loaded load(const std::vector<std::pair<std::string, int64_t>>& engine_options) {
+	Loaded load() {
 		bool nothing_to_do = false;
 		if (!select_blocks(settings, S, &nothing_to_do)) return failed;
 		if (nothing_to_do) return empty;
@@ -994,13 +1015,26 @@ struct ReduceCommand {
 		if (S.bal.diag) return Geometry{M > 1, 0, M, 0, M, 1};
 		return Geometry{S.nL && S.nR, 0, (uint32_t)S.nL, (uint32_t)S.nL, (uint32_t)S.nR, 0};
 	}
+	// The one engine call, timed: -> its seconds, or a negative number after the error message.  np: where the call leaves the pairs it
+	// compared, kept as the object's result (null: the call compares none)
+	template <class Call>
+	double call(const char* what, Call&& engine, const uint64_t* np) {
+		const auto t0 = clock::now();
+		if (!hip_ok(ctx, engine(), what)) return -1;
+		if (np) n_pairs = *np;
+		return std::chrono::duration<double>(clock::now() - t0).count();
+	}
+	// An output file, announced; -> false after an error message
+	static bool open(std::ofstream& f, const std::string& path, std::ios::openmode mode = std::ios::out) {
+		opening(path);
+		f.open(path, std::ios::out | std::ios::trunc | mode);
+		return opened(f.good(), path);
+	}
+	bool to_stdout() const { return settings.out.empty() || settings.out == "-"; }
 	// The text output: -o, or stdout.  -> null after an error message
 	std::ostream* open_text() {
-		if (settings.out.empty() || settings.out == "-") return &std::cout;
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << settings.out << "..." << std::endl;
-		file.open(settings.out, std::ios::out | std::ios::trunc);
-		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << settings.out << "..." << std::endl; return nullptr; }
-		return &file;
+		if (to_stdout()) return &std::cout;
+		return open(file, settings.out) ? &file : nullptr;
 	}
 	// The `##` lines every command's text begins with (name: "ldscore", "prune", ...); the command's own lines follow
 	void header(std::ostream& os, const char* name) const {
@@ -1025,6 +1059,40 @@ struct ReduceCommand {
 		if (!os.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write " << what << "..." << std::endl; return false; }
 		return true;
 	}
+	// A dense n x n matrix as text, a row per line: `digits` significant digits, `sep` between two values; plain_nan: every NaN is spelled
+	// nan (else as printf spells it, sign included).  -> finish()
+	template <class T>
+	static bool dense_text(std::ostream& os, const T* m, uint32_t n, char sep, int digits, bool plain_nan) {
+		std::string text;
+		char num[40];
+		for (uint32_t a = 0; a < n; ++a) {
+			for (uint32_t b = 0; b < n; ++b) {
+				const double v = (double)m[(size_t)a * n + b];
+				if (b) text += sep;
+				if (plain_nan && v != v) text += "nan";
+				else { snprintf(num, sizeof(num), "%.*g", digits, v); text += num; }
+			}
+			text += '\n';
+			spill(os, text);
+		}
+		return finish(os, text, "the matrix");
+	}
+	// A dense n x n matrix as a NumPy file, format 1.0: magic, version, a little-endian uint16 header length, the dictionary padded with
+	// spaces and ended by a newline so that the data begins on a multiple of 64 bytes; C order (the hosts this runs on are little-endian).
+	// descr: "<f4", "<f8".  -> finish()
+	static bool npy(std::ostream& os, const char* descr, uint32_t n, const void* data, size_t bytes) {
+		std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" + std::to_string(n) + ", " + std::to_string(n) + "), }";
+		const size_t fixed = 6 + 2 + 2;
+		const size_t total = (fixed + dict.size() + 1 + 63) / 64 * 64;
+		dict.append(total - fixed - dict.size() - 1, ' ');
+		dict += '\n';
+		const char head[fixed] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(dict.size() & 0xFF), (char)(dict.size() >> 8 & 0xFF)};
+		os.write(head, fixed);
+		os.write(dict.data(), (std::streamsize)dict.size());
+		os.write(static_cast<const char*>(data), (std::streamsize)bytes);
+		std::string nothing;
+		return finish(os, nothing, "the matrix");
+	}
 	void all_done() const {
 		std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
 	}
@@ -1035,22 +1103,18 @@ struct ReduceCommand {
 // sum of their R2 (twk_hip_ld_score: reduced on the GPU, no record is formed), as text.  The input is loaded exactly as Compute loads
 // it; one GPU.  Not in the reference.
 bool twk_ld::Score(const twk_ld_settings& s) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("A score sums over every record", nullptr)) return false;
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "A score sums over every record", nullptr)) return false;
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t M = cmd.M;
 	std::vector<uint64_t> n_partners(M, 0);
 	std::vector<double> sum_r2(M, 0.0);
 	uint64_t np = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	int rc = TWK_HIP_OK;
 	const auto g = cmd.geometry();
-	if (g.pairs) rc = twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_score")) return false;
-	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_ld_score", [&] {
+		return !g.pairs ? TWK_HIP_OK : twk_hip_ld_score(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, n_partners.data(), sum_r2.data(), &np);
+	}, &np);
+	if (sec < 0) return false;
 
 	std::ostream* const os = cmd.open_text();
 	if (!os) return false;
@@ -1074,24 +1138,20 @@ bool twk_ld::Score(const twk_ld_settings& s) {
 // exactly on the GPU, no record is formed), as text: one line per bin.  The input is loaded exactly as Compute loads it; one GPU.  The
 // reference's two_reader::Decay bins the records of a .two file; its columns are kept and `Sum` is added.
 bool twk_ld::Decay(const twk_ld_settings& s, const twk_decay_settings& ds) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("A decay curve averages over every record", nullptr)) return false;
-	if (ds.n_bins < 1 || ds.n_bins > 4096) { std::cerr << stamp("ERROR") << "The number of bins must be between 1 and 4096..." << std::endl; return false; }
-	if (ds.range_bp < ds.n_bins || ds.range_bp > 0xFFFFFFFFll) { std::cerr << stamp("ERROR") << "The range in bases must be at least the number of bins and below 2^32..." << std::endl; return false; }
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "A decay curve averages over every record", nullptr)) return false;
+	if (ds.n_bins < 1 || ds.n_bins > MAX_BINS) { std::cerr << stamp("ERROR") << "The number of bins must be between 1 and " << MAX_BINS << "..." << std::endl; return false; }
+	if (ds.range_bp < ds.n_bins || ds.range_bp > MAX_RANGE_BP) { std::cerr << stamp("ERROR") << "The range in bases must be at least the number of bins and below 2^32..." << std::endl; return false; }
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t B = (uint32_t)ds.n_bins, range = (uint32_t)ds.range_bp;
 	std::vector<uint64_t> n(B, 0);
 	std::vector<double> sum_r2(B, 0.0);
 	uint64_t np = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	int rc = TWK_HIP_OK;
 	const auto g = cmd.geometry();
-	if (g.pairs) rc = twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_decay")) return false;
-	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_ld_decay", [&] {
+		return !g.pairs ? TWK_HIP_OK : twk_hip_ld_decay(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, range, B, n.data(), sum_r2.data(), &np);
+	}, &np);
+	if (sec < 0) return false;
 
 	std::ostream* const os = cmd.open_text();
 	if (!os) return false;
@@ -1120,14 +1180,12 @@ bool twk_ld::Decay(const twk_ld_settings& s, const twk_decay_settings& ds) {
 // input is loaded exactly as Compute loads it; one GPU.  The reference's two_reader::Aggregate rasterises the records of a .two file
 // into a binary .twa; its coordinate rule is kept (twk_aggregate_landscape.h), its file format is not provided.
 bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& as) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("An aggregate takes in every record", nullptr)) return false;
-	if (as.x_bins < 1 || as.x_bins > 4096 || as.y_bins < 1 || as.y_bins > 4096) { std::cerr << stamp("ERROR") << "The number of bins per axis must be between 1 and 4096..." << std::endl; return false; }
-	if (as.stat != TWK_HIP_STAT_R && as.stat != TWK_HIP_STAT_R2 && as.stat != TWK_HIP_STAT_D && as.stat != TWK_HIP_STAT_DPRIME) { std::cerr << stamp("ERROR") << "Unknown statistic..." << std::endl; return false; }
-	if (as.reduce < 0 || as.reduce > 5 || as.min_count < 0) { std::cerr << stamp("ERROR") << "Unknown reduction or a negative minimum count..." << std::endl; return false; }
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "An aggregate takes in every record", nullptr)) return false;
+	if (as.x_bins < 1 || as.x_bins > MAX_BINS || as.y_bins < 1 || as.y_bins > MAX_BINS) { std::cerr << stamp("ERROR") << "The number of bins per axis must be between 1 and " << MAX_BINS << "..." << std::endl; return false; }
+	if (!LD_STATS.valid(as.stat)) { std::cerr << stamp("ERROR") << "Unknown statistic..." << std::endl; return false; }
+	if (!AGGREGATE_REDUCTIONS.valid(as.reduce) || as.min_count < 0) { std::cerr << stamp("ERROR") << "Unknown reduction or a negative minimum count..." << std::endl; return false; }
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const Selection& S = cmd.S;
 	const uint32_t M = cmd.M, X = (uint32_t)as.x_bins, Y = (uint32_t)as.y_bins;
 	std::vector<int64_t> contig_bases;
@@ -1142,23 +1200,19 @@ bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& a
 	std::vector<uint64_t> n(cells, 0);
 	std::vector<double> sum(cells, 0.0), sum_sq(cells, 0.0), mn(cells, 0.0), mx(cells, 0.0);
 	uint64_t np = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	int rc = TWK_HIP_OK;
 	const auto g = cmd.geometry();
-	if (g.pairs) rc = twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_aggregate")) return false;
-	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_ld_aggregate", [&] {
+		return !g.pairs ? TWK_HIP_OK : twk_hip_ld_aggregate(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window, as.stat, bin_x.data(), bin_y.data(), X, Y, n.data(), sum.data(), sum_sq.data(), mn.data(), mx.data(), &np);
+	}, &np);
+	if (sec < 0) return false;
 
 	std::ostream* const os = cmd.open_text();
 	if (!os) return false;
 	cmd.header(*os, "ldaggregate");
-	static const char* const stat_names[] = {"r", "r2", "D", "Dprime"};
-	static const char* const reduce_names[] = {"mean", "count", "min", "max", "sd", "total"};
 	uint64_t contributions = 0;
 	for (size_t k = 0; k < cells; ++k) contributions += n[k];
 	*os << "#x=" << X << ",y=" << Y << ",bpx=" << land.bpx << ",bpy=" << land.bpy << ",range=" << land.range
-	    << ",stat=" << stat_names[as.stat] << ",reduce=" << reduce_names[as.reduce] << ",min_count=" << as.min_count << ",contributions=" << contributions << "\n";
+	    << ",stat=" << LD_STATS.name(as.stat) << ",reduce=" << AGGREGATE_REDUCTIONS.name(as.reduce) << ",min_count=" << as.min_count << ",contributions=" << contributions << "\n";
 	if (land.single) *os << "#landscape=one contig,min_pos=" << land.min_pos << "\n";
 	else *os << "#landscape=whole contigs\n";
 	for (size_t k = 0; k < contig_bases.size(); ++k)
@@ -1172,12 +1226,12 @@ bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& a
 			if (n[k] && n[k] >= (uint64_t)as.min_count) {
 				const double cnt = (double)n[k], mean = sum[k] / cnt;
 				switch (as.reduce) {
-				case 0: v = mean; break;
-				case 1: v = cnt; break;
-				case 2: v = mn[k]; break;
-				case 3: v = mx[k]; break;
-				case 4: { const double var = sum_sq[k] / cnt - mean * mean; v = var > 0 ? sqrt(var) : 0.0; break; }
-				default: v = sum[k]; break;
+				case TWK_AGGREGATE_MEAN: v = mean; break;
+				case TWK_AGGREGATE_COUNT: v = cnt; break;
+				case TWK_AGGREGATE_MIN: v = mn[k]; break;
+				case TWK_AGGREGATE_MAX: v = mx[k]; break;
+				case TWK_AGGREGATE_SD: { const double var = sum_sq[k] / cnt - mean * mean; v = var > 0 ? sqrt(var) : 0.0; break; }
+				default: v = sum[k]; break;      // TWK_AGGREGATE_TOTAL
 				}
 			}
 			snprintf(cell, sizeof(cell), y ? "\t%.17g" : "%.17g", v);
@@ -1196,19 +1250,14 @@ bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& a
 // decided and walked on the GPU, no record is formed), as text: one line per variant with its keep flag.  The input is loaded exactly
 // as Compute loads it; one GPU; the whole triangle (the walk needs every pair: no -c / -C).  Not in the reference.
 bool twk_ld::Prune(const twk_ld_settings& s) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("Pruning looks at every record", "Cannot prune a part of the pair space: the walk needs every pair")) return false;
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "Pruning looks at every record", "Cannot prune a part of the pair space: the walk needs every pair")) return false;
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t M = cmd.M;
 	std::vector<uint8_t> keep(M, 0);
 	uint64_t np = 0, n_kept = 0, n_edges = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	const int rc = twk_hip_ld_prune(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, keep.data(), &n_kept, &n_edges, &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_prune")) return false;
-	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_ld_prune", [&] { return twk_hip_ld_prune(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, keep.data(), &n_kept, &n_edges, &np); }, &np);
+	if (sec < 0) return false;
 
 	std::ostream* const os = cmd.open_text();
 	if (!os) return false;
@@ -1274,15 +1323,13 @@ bool read_assoc(const std::string& path, AssocMap& out) {
 // association file is read and checked before the input is opened or a device touched; the input is then loaded exactly as Prune
 // loads it; one GPU; the whole triangle (no -c / -C).  Not in the reference.
 bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("Clumping looks at every record", "Cannot clump a part of the pair space: the walk needs every pair")) return false;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "Clumping looks at every record", "Cannot clump a part of the pair space: the walk needs every pair")) return false;
 	if (!(cs.p1 >= 0 && cs.p1 <= cs.p2 && cs.p2 <= 1)) { std::cerr << stamp("ERROR") << "The clumping thresholds must satisfy 0 <= p1 <= p2 <= 1..." << std::endl; return false; }
 	if (cs.assoc.empty()) { std::cerr << stamp("ERROR") << "No association file provided..." << std::endl; return false; }
 	AssocMap assoc;
 	if (!read_assoc(cs.assoc, assoc)) return false;
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t M = cmd.M;
 
 	// every variant of the selection at a (contig, position) the file names gets that P
@@ -1305,11 +1352,10 @@ bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
 
 	std::vector<uint32_t> index_of(M, TWK_HIP_NO_CLUMP);
 	uint64_t np = 0, n_clumps = 0, n_members = 0, n_edges = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	const int rc = twk_hip_ld_clump(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, p.data(), cs.p1, cs.p2, index_of.data(), &n_clumps, &n_members, &n_edges, &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_clump")) return false;
-	mImpl->n_pairs = np;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_ld_clump", [&] {
+		return twk_hip_ld_clump(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, p.data(), cs.p1, cs.p2, index_of.data(), &n_clumps, &n_members, &n_edges, &np);
+	}, &np);
+	if (sec < 0) return false;
 
 	std::ostream* const os = cmd.open_text();
 	if (!os) return false;
@@ -1340,61 +1386,23 @@ bool twk_ld::Clump(const twk_ld_settings& s, const twk_clump_settings& cs) {
 // on the GPU at (u, v) and (v, u), no record is formed), as a NumPy file or as text, with the rows' variants next to it.  The input is
 // loaded exactly as Prune loads it; one GPU; the whole triangle (no -c / -C).  Not in the reference.
 bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("The matrix holds every record", "Cannot fill a part of the pair space: the matrix needs every pair")) return false;
-	if (ms.stat != TWK_HIP_STAT_R && ms.stat != TWK_HIP_STAT_R2 && ms.stat != TWK_HIP_STAT_D && ms.stat != TWK_HIP_STAT_DPRIME) {
-		std::cerr << stamp("ERROR") << "Unknown statistic: one of r, r2, D, Dprime..." << std::endl; return false;
-	}
-	if (settings.out.empty() || settings.out == "-") { std::cerr << stamp("ERROR") << "No output prefix provided: the matrix and its variant list are files..." << std::endl; return false; }
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "The matrix holds every record", "Cannot fill a part of the pair space: the matrix needs every pair")) return false;
+	if (!LD_STATS.valid(ms.stat)) { std::cerr << stamp("ERROR") << "Unknown statistic: one of " << LD_STATS.list() << "..." << std::endl; return false; }
+	if (cmd.to_stdout()) { std::cerr << stamp("ERROR") << "No output prefix provided: the matrix and its variant list are files..." << std::endl; return false; }
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t M = cmd.M;
 	std::vector<float> m((size_t)M * M);
 	uint64_t np = 0, n_recs = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	const int rc = twk_hip_ld_matrix(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_ld_matrix")) return false;
-	mImpl->n_pairs = np; mImpl->n_records = n_recs;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_ld_matrix", [&] { return twk_hip_ld_matrix(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np); }, &np);
+	if (sec < 0) return false;
+	mImpl->n_records = n_recs;
 
-	const std::string path = settings.out + (ms.text ? ".ld" : ".npy");
-	std::cerr << stamp("LOG", "WRITER") << "Opening " << path << "..." << std::endl;
-	std::ofstream file(path, std::ios::out | std::ios::trunc | std::ios::binary);
-	if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << path << "..." << std::endl; return false; }
-	if (!ms.text) {
-		// NumPy format 1.0: magic, version, a little-endian uint16 header length, the dictionary padded with spaces and ended by a
-		// newline so that the data begins on a multiple of 64 bytes
-		std::string dict = "{'descr': '<f4', 'fortran_order': False, 'shape': (" + std::to_string(M) + ", " + std::to_string(M) + "), }";
-		const size_t fixed = 6 + 2 + 2;
-		const size_t total = (fixed + dict.size() + 1 + 63) / 64 * 64;
-		dict.append(total - fixed - dict.size() - 1, ' ');
-		dict += '\n';
-		const char head[fixed] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(dict.size() & 0xFF), (char)(dict.size() >> 8 & 0xFF)};
-		file.write(head, fixed);
-		file.write(dict.data(), (std::streamsize)dict.size());
-		file.write(reinterpret_cast<const char*>(m.data()), (std::streamsize)(m.size() * sizeof(float)));      // (the hosts this runs on are little-endian)
-	} else {
-		std::string text;
-		char num[32];
-		for (uint32_t u = 0; u < M; ++u) {
-			for (uint32_t v = 0; v < M; ++v) {
-				snprintf(num, sizeof(num), v ? " %.9g" : "%.9g", (double)m[(size_t)u * M + v]);
-				text += num;
-			}
-			text += '\n';
-			cmd.spill(file, text);
-		}
-		file << text;
-	}
-	file.flush();
-	if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the matrix..." << std::endl; return false; }
+	std::ofstream file, vfile;
+	if (!cmd.open(file, settings.out + (ms.text ? ".ld" : ".npy"), std::ios::binary)) return false;
+	if (!(ms.text ? cmd.dense_text(file, m.data(), M, ' ', 9, false) : cmd.npy(file, "<f4", M, m.data(), m.size() * sizeof(float)))) return false;
 	file.close();
-
-	const std::string vpath = settings.out + ".variants.tsv";
-	std::cerr << stamp("LOG", "WRITER") << "Opening " << vpath << "..." << std::endl;
-	std::ofstream vfile(vpath, std::ios::out | std::ios::trunc);
-	if (!vfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << vpath << "..." << std::endl; return false; }
+	if (!cmd.open(vfile, settings.out + ".variants.tsv")) return false;
 	std::string text;
 	for (uint32_t v = 0; v < M; ++v) {
 		cmd.place(text, v);
@@ -1402,8 +1410,7 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 		cmd.spill(vfile, text);
 	}
 	if (!cmd.finish(vfile, text, "the variant list")) return false;
-	static const char* const stat_names[] = {"r", "r2", "D", "Dprime"};
-	std::cerr << stamp("LOG") << "Matrix of " << stat_names[ms.stat] << ": " << pretty(M) << " x " << pretty(M) << ", " << pretty(n_recs) << " pairs with a value among "
+	std::cerr << stamp("LOG") << "Matrix of " << LD_STATS.name(ms.stat) << ": " << pretty(M) << " x " << pretty(M) << ", " << pretty(n_recs) << " pairs with a value among "
 	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
 	cmd.all_done();
 	return true;
@@ -1413,73 +1420,30 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 // divided on the GPU), as text on stdout or as a NumPy file or text file with the samples' names next to it.  The input is loaded exactly as
 // Prune loads it; one GPU.  The reference's command of the same name is not reproduced (include/twk_hip.h says why).
 bool twk_ld::Relationship(const twk_ld_settings& s, const twk_relationship_settings& rs) {
-	settings = s;
-	mImpl->n_pairs = mImpl->n_records = 0;
-	ReduceCommand cmd{settings, mImpl->rid, mImpl->pos};
-	if (!cmd.check("The matrix is counted, not tested", "Cannot relate over a part of the pair space: the samples are compared over every selected variant")) return false;
-	if (rs.stat != TWK_HIP_REL_IBS && rs.stat != TWK_HIP_REL_IBS0 && rs.stat != TWK_HIP_REL_KING) {
-		std::cerr << stamp("ERROR") << "Unknown statistic: one of ibs, ibs0, king..." << std::endl; return false;
-	}
-	if (const auto l = cmd.load(mImpl->engine_options); l != cmd.ready) return l == cmd.empty;
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "The matrix is counted, not tested", "Cannot relate over a part of the pair space: the samples are compared over every selected variant")) return false;
+	if (!REL_STATS.valid(rs.stat)) { std::cerr << stamp("ERROR") << "Unknown statistic: one of " << REL_STATS.list() << "..." << std::endl; return false; }
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t n = cmd.S.n_samples;
 	std::vector<double> m((size_t)n * n);
 	uint64_t np = 0;
-	const auto t0 = ReduceCommand::clock::now();
-	const int rc = twk_hip_relationship(cmd.ctx, nullptr, 0, 0, n, 0, n, rs.stat, rs.fill, m.data(), n, nullptr, 0, &np);
-	if (!hip_ok(cmd.ctx, rc, "twk_hip_relationship")) return false;
-	const double sec = std::chrono::duration<double>(ReduceCommand::clock::now() - t0).count();
+	const double sec = cmd.call("twk_hip_relationship", [&] { return twk_hip_relationship(cmd.ctx, nullptr, 0, 0, n, 0, n, rs.stat, rs.fill, m.data(), n, nullptr, 0, &np); }, nullptr);
+	if (sec < 0) return false;
 
-	// one row per sample, tab-separated, 17 significant digits (a NaN prints as nan whatever its bits: the .npy keeps them)
-	auto write_text = [&](std::ostream& os) {
-		std::string text;
-		char num[40];
-		for (uint32_t a = 0; a < n; ++a) {
-			for (uint32_t b = 0; b < n; ++b) {
-				const double v = m[(size_t)a * n + b];
-				if (v != v) snprintf(num, sizeof(num), b ? "\tnan" : "nan");
-				else snprintf(num, sizeof(num), b ? "\t%.17g" : "%.17g", v);
-				text += num;
-			}
-			text += '\n';
-			cmd.spill(os, text);
-		}
-		return cmd.finish(os, text, "the matrix");
-	};
-	const bool to_stdout = settings.out.empty() || settings.out == "-";
-	if (to_stdout) {
-		if (!write_text(std::cout)) return false;
+	// as text: one row per sample, tab-separated, 17 significant digits (a NaN prints as nan whatever its bits: the .npy keeps them)
+	if (cmd.to_stdout()) {
+		if (!cmd.dense_text(std::cout, m.data(), n, '\t', 17, true)) return false;
 	} else {
-		const std::string path = settings.out + (rs.text ? ".tsv" : ".npy");
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << path << "..." << std::endl;
-		std::ofstream file(path, std::ios::out | std::ios::trunc | std::ios::binary);
-		if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << path << "..." << std::endl; return false; }
-		if (rs.text) {
-			if (!write_text(file)) return false;
-		} else {
-			// NumPy format 1.0, as Matrix writes it, with eight-byte floats
-			std::string dict = "{'descr': '<f8', 'fortran_order': False, 'shape': (" + std::to_string(n) + ", " + std::to_string(n) + "), }";
-			const size_t fixed = 6 + 2 + 2;
-			const size_t total = (fixed + dict.size() + 1 + 63) / 64 * 64;
-			dict.append(total - fixed - dict.size() - 1, ' ');
-			dict += '\n';
-			const char head[fixed] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0, (char)(dict.size() & 0xFF), (char)(dict.size() >> 8 & 0xFF)};
-			file.write(head, fixed);
-			file.write(dict.data(), (std::streamsize)dict.size());
-			file.write(reinterpret_cast<const char*>(m.data()), (std::streamsize)(m.size() * sizeof(double)));      // (the hosts this runs on are little-endian)
-			file.flush();
-			if (!file.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to write the matrix..." << std::endl; return false; }
-		}
+		std::ofstream file, sfile;
+		if (!cmd.open(file, settings.out + (rs.text ? ".tsv" : ".npy"), std::ios::binary)) return false;
+		if (!(rs.text ? cmd.dense_text(file, m.data(), n, '\t', 17, true) : cmd.npy(file, "<f8", n, m.data(), m.size() * sizeof(double)))) return false;
 		file.close();
-		const std::string spath = settings.out + ".samples.tsv";
-		std::cerr << stamp("LOG", "WRITER") << "Opening " << spath << "..." << std::endl;
-		std::ofstream sfile(spath, std::ios::out | std::ios::trunc);
-		if (!sfile.good()) { std::cerr << stamp("ERROR", "WRITER") << "Failed to open file: " << spath << "..." << std::endl; return false; }
+		if (!cmd.open(sfile, settings.out + ".samples.tsv")) return false;
 		std::string text;
 		for (const std::string& name : cmd.S.reader.hdr.samples) { text += name; text += '\n'; }
 		if (!cmd.finish(sfile, text, "the sample list")) return false;
 	}
-	static const char* const stat_names[] = {"ibs", "ibs0", "king"};
-	std::cerr << stamp("LOG") << "Relationship (" << stat_names[rs.stat] << "): " << pretty(n) << " x " << pretty(n) << " samples over " << pretty(cmd.M) << " variants, "
+	std::cerr << stamp("LOG") << "Relationship (" << REL_STATS.name(rs.stat) << "): " << pretty(n) << " x " << pretty(n) << " samples over " << pretty(cmd.M) << " variants, "
 	          << pretty(np) << " sample pairs. " << elapsed_string(sec) << std::endl;
 	cmd.all_done();
 	return true;
@@ -1494,9 +1458,8 @@ bool twk_ld::ComputeSingle(bool verbose, bool) {
 	if (settings.window) { std::cerr << stamp("ERROR") << "Cannot use window mode when running in single mode!" << std::endl; return false; }
 	if (settings.ival_strings.size() != 1) { std::cerr << stamp("ERROR") << "Single mode requires exactly one target interval (-I)..." << std::endl; return false; }
 	settings.single = true;
-	if (verbose) std::cerr << stamp("LOG", "READER") << "Opening " << settings.in << "..." << std::endl;
 	TwkReader reader;
-	if (!reader.open(settings.in)) { std::cerr << stamp("ERROR") << "Failed to open file: " << settings.in << "... (" << reader.error << ")" << std::endl; return false; }
+	if (!open_input(reader, settings.in, verbose)) return false;
 	const uint32_t n_samples = (uint32_t)reader.hdr.samples.size();
 	Interval tgt;
 	if (!parse_interval(settings.ival_strings[0], reader.hdr, tgt)) return false;
