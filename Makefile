@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -114,6 +114,14 @@ relate-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/relate_index_check.cpp -o build/relate_index_check
 	./build/relate_index_check
+
+# The count launches' work table - tiles in patch order, units, queues, the packed layout - and the last-chunk rule (csrc/hip/ld_count_table.h)
+# against a naive restatement and against the recorded order of tests/golden/count_tables.json (csrc/tools/count_table_check.cpp): host code
+# only, under AddressSanitizer and UBSan
+count-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/count_table_check.cpp -o build/count_table_check
+	./build/count_table_check tests/golden/count_tables.json
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -88,3 +88,15 @@ def test_buffer_owners_free_what_they_hold_once():
     r = subprocess.run(["make", "-C", ROOT, "buffers-check"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
     assert "7 cases, 0 bad" in r.stdout
+
+
+def test_count_tables_keep_their_invariants_and_their_recorded_order():
+    """`make count-check`: the count launches' work table (csrc/hip/ld_count_table.h) built on the CPU, under AddressSanitizer and UBSan,
+    for grids of 1 to 17 tiles an axis, every tile kind and every setting of the work order - the listed tiles are the wanted ones in
+    patch order, the units partition every tile's K range, the queues hold every unit once, the packed image reads back - and hashed
+    against tests/golden/count_tables.json: the order in which the blocks walk the tiles was tuned, and no result test sees it.  With
+    it the one statement of the last-chunk rule against the rule spelled out."""
+    r = subprocess.run(["make", "-C", ROOT, "count-check"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+    m = re.search(r"count-check: (\d+) cases, (\d+) bad", r.stdout)
+    assert m and int(m.group(1)) >= 1 and int(m.group(2)) == 0, r.stdout[-2000:]

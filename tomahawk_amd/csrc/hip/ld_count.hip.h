@@ -30,11 +30,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ld_count_table.h"
 
 namespace twk {
 
-constexpr int TILE = 128;       // rows per block tile edge
-constexpr int KC   = 32;        // 32-bit words of K per chunk (128 B per row)
 constexpr int LDS_TILE_BYTES = TILE * KC * 4;   // 16 KiB: one operand, one chunk
 
 typedef __attribute__((address_space(1))) const void gptr_t;
@@ -438,7 +437,7 @@ __device__ __forceinline__ void contract3_slot(uint32_t (&acc)[8][4], uint32_t a
 // of blocks the chip holds at once (2 per CU), which pull *units* of work from an atomic ticket:
 //   * a unit is a K-range [c0, c1) of one tile; whole tiles (full K range) are stored plainly, parts
 //     of a tile are added with atomics into a tile that a small kernel zeroed beforehand;
-//   * the host (build_count_units) hands out whole tiles while more than ~2 rounds of work remain
+//   * the host (build_count_units, ld_count_table.h) hands out whole tiles while more than ~2 rounds of work remain
 //     and ever shorter K-ranges after that, so the launch ends within a few short units of balance.
 // Why not a plain 2-D grid: T tiles take ceil(T / P) rounds and the partial last round is pure loss
 // (12 % of a configs[1]-sized launch, more for thin window-mode row blocks).  Why not a static equal
@@ -450,8 +449,6 @@ __device__ __forceinline__ void contract3_slot(uint32_t (&acc)[8][4], uint32_t a
 // the next unit's ticket is drawn by thread 0 at the first chunk of a unit and handed to the other
 // waves through a two-slot LDS mailbox behind the next chunk barrier, so no extra synchronisation
 // is paid (units of a single chunk excepted).
-struct CountUnit { uint32_t tile, c0, c1, yx; };       // chunks [c0, c1) of tiles[tile]; yx = tiles[tile], so that a block learns everything about its
-                                                       // next unit from one 16-byte scalar load (fill_unit_tiles) instead of two dependent ones
 struct CountWork {
 	const uint32_t* rows; uint32_t W;      // plane rows, row pitch in words (multiple of KC)
 	uint32_t rowA0, rowB0;                 // first plane row of the super-tile's row / column axis
@@ -475,60 +472,6 @@ struct CountWork {
 	// profiles/r04_clock_probe.txt), which is most of what short-row runs lose against long ones.
 	unsigned long long* clocks;
 };
-
-// The unit table of a launch (host side; shared by the engine and the dev tools).  Guided self-scheduling:
-// a unit is never longer than 1/share_div of an even share of the work still to be handed out, so whole
-// tiles go out only while more than tail_rounds (= share_div) rounds of work remain, and after that
-// K-ranges that shrink with the remainder down to `min_chunks` chunks.  The launch then ends within a few
-// of the shortest units of perfect balance however unequal the blocks' speeds are (measured: finish
-// times of the 512 blocks within 0.14 ms of each other on a 21 ms launch).  Returns the index of the
-// first tile that is split (tiles from there on must be zeroed before the launch); n_tiles if none.
-// Long rows, segmented walk (seg_chunks != 0, rows of at least two segments, patch_end = the list index where each
-// patch of tiles ends): the tiles of a patch - which share their row and column tiles - are not contracted one whole
-// tile per block, each block at its own pace, but K segment by K segment: all tiles of the patch over chunks
-// [0, seg), then all over [seg, 2 seg), ...  The blocks working on a patch are then always within a segment of each
-// other, so a chunk of a row tile fetched for one block is still in the MALL (and often in L2) when the other blocks
-// that need it come by: HBM sees every (row tile, segment) about once per patch instead of once per tile.  The price:
-// every unit is a part of its tile's K range (counts added with atomics into zeroed tiles - 32 adds per lane per
-// segment, nothing next to the segment's 2048 x seg VALU ops).
-template <class Vec>
-inline uint32_t build_count_units(uint32_t n_tiles, uint32_t nchunks, uint32_t n_blocks, uint32_t min_chunks, Vec& units,
-                                  uint32_t share_div = 8, uint32_t tail_rounds = 8,
-                                  const uint32_t* patch_end = nullptr, uint32_t n_patches = 0, uint32_t seg_chunks = 0) {
-	units.clear();
-	const uint32_t tail = (uint32_t)(n_tiles < (unsigned long long)tail_rounds * n_blocks ? n_tiles : (unsigned long long)tail_rounds * n_blocks);
-	uint32_t first_split = n_tiles - tail;
-	if (nchunks < 2 * min_chunks) first_split = n_tiles;             // rows too short to be worth splitting
-	const bool segmented = seg_chunks && patch_end && n_patches && nchunks >= 2 * seg_chunks && nchunks >= 2 * min_chunks;
-	if (segmented) {
-		const uint32_t nseg = (nchunks + seg_chunks - 1) / seg_chunks;
-		uint32_t p0 = 0;
-		for (uint32_t p = 0; p < n_patches && p0 < first_split; ++p) {
-			const uint32_t p1 = patch_end[p] < first_split ? patch_end[p] : first_split;
-			for (uint32_t sgm = 0; sgm < nseg; ++sgm)
-				for (uint32_t t = p0; t < p1; ++t)
-					units.push_back(CountUnit{t, (uint32_t)((unsigned long long)nchunks * sgm / nseg), (uint32_t)((unsigned long long)nchunks * (sgm + 1) / nseg), 0});
-			p0 = p1;
-		}
-	} else {
-		for (uint32_t t = 0; t < first_split; ++t) units.push_back(CountUnit{t, 0, nchunks, 0});
-	}
-	for (uint32_t t = first_split; t < n_tiles; ++t) {
-		const unsigned long long rem = (unsigned long long)(n_tiles - t) * nchunks;      // chunks left, this tile included
-		unsigned long long target = rem / ((unsigned long long)share_div * n_blocks);
-		if (target < min_chunks) target = min_chunks;
-		if (segmented && target > seg_chunks) target = seg_chunks;
-		uint32_t S = (uint32_t)((nchunks + target - 1) / target);
-		if (S < 1) S = 1;
-		if (S > nchunks) S = nchunks;
-		for (uint32_t k = 0; k < S; ++k)
-			units.push_back(CountUnit{t, (uint32_t)((unsigned long long)nchunks * k / S), (uint32_t)((unsigned long long)nchunks * (k + 1) / S), 0});
-	}
-	return segmented ? 0 : first_split;
-}
-
-template <class Vec>
-inline void fill_unit_tiles(Vec& units, const uint32_t* tiles) { for (auto& u : units) u.yx = tiles[u.tile]; }
 
 // What a block does with the 8 x TB counts each of its lanes holds when a unit ends.  StoreCounts is the plain form:
 // the counts go to the super-tile's C matrix (stored for a whole tile, added for a part of its K range).
@@ -1364,5 +1307,38 @@ void k_zero_tiles(const uint32_t* __restrict__ tiles, uint32_t first, uint32_t* 
 #endif
 constexpr int COUNT_NW = TWK_COUNT_NW;
 constexpr int COUNT_THREADS = COUNT_NW * 64;
+
+// The parameter block of a launch over table tb, whose packed image (CountTable::pack) lies at d_table on the device.  ticket: tb.n_queues
+// words, zeroed by the caller before the launch; last_halves: count_last_halves of the rows, or 0; clocks: CountWork::clocks, may be null.
+inline CountWork count_work(const uint32_t* rows, uint32_t W, uint32_t rowA0, uint32_t rowB0, const uint32_t* d_table, const CountTable& tb,
+                            uint32_t* C, uint32_t ldc, uint32_t* ticket, uint32_t last_halves, unsigned long long* clocks) {
+	CountWork w{};
+	w.rows = rows; w.W = W; w.rowA0 = rowA0; w.rowB0 = rowB0;
+	w.tiles = d_table;
+	w.units = reinterpret_cast<const CountUnit*>(d_table + tb.units_at()); w.n_units = tb.n_units();
+	w.C = C; w.ldc = ldc;
+	w.ticket = ticket;
+	w.n_queues = tb.n_queues;
+	for (int q = 0; q < 9; ++q) w.queue_begin[q] = tb.queue_begin[q];
+	w.last_halves = last_halves;
+	w.clocks = clocks;
+	return w;
+}
+
+// A launch on `stream`: the split tiles of the table zeroed (tile_rows: TILE, or TILE / 2 for the three-product matrix), then `kernel`
+// (w, more...) on as many blocks as the chip holds at once, or fewer when there are fewer units.  between: an event of the caller's
+// recorded after the zeroing and before the kernel, or null.  Returns the runtime's verdict.
+template <class Kernel, class... More>
+inline hipError_t enqueue_count(hipStream_t stream, const CountWork& w, const CountTable& tb, uint32_t n_blocks, uint32_t tile_rows, hipEvent_t between,
+                                Kernel kernel, More... more) {
+	if (tb.first_split < tb.n_tiles()) {
+		hipLaunchKernelGGL(k_zero_tiles, dim3(tb.n_tiles() - tb.first_split), dim3(256), 0, stream, w.tiles, tb.first_split, w.C, w.ldc, tile_rows);
+		const hipError_t e = hipGetLastError();
+		if (e != hipSuccess) return e;
+	}
+	if (between) { const hipError_t e = hipEventRecord(between, stream); if (e != hipSuccess) return e; }
+	hipLaunchKernelGGL(kernel, dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, stream, w, more...);
+	return hipGetLastError();
+}
 
 }  // namespace twk

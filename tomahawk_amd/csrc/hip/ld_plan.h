@@ -133,7 +133,7 @@ inline void plan_shard(const PlanGeom& g, RegionPlan& p) {
 	p.r1 = p.windowed ? window_boundary(g.part + 1) : band_boundary(g.part + 1, g.n_parts, g.nA, g.nB, g.triangle != 0);
 }
 
-// The block tiles build_tile_list (twk_hip.hip) will list for rows [x, x + h) over all the columns they reach.
+// The block tiles build_tile_list (ld_count_table.h) will list for rows [x, x + h) over all the columns they reach.
 inline uint64_t plan_tiles_of_rows(const PlanEnv& e, const PlanGeom& g, const RegionPlan& p, uint32_t x, uint32_t h) {
 	const uint64_t P = (uint64_t)e.Pmax;
 	const uint32_t col0 = g.triangle ? x : (p.windowed ? p.lo[x] : 0);

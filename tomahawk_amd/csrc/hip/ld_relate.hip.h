@@ -22,8 +22,6 @@
 
 namespace twk {
 
-static_assert(RL_KC == KC && RL_TILE == TILE, "ld_relate_index.h restates the count kernel's chunk and tile");
-
 __global__ __launch_bounds__(RL_THREADS)
 void k_relate_transpose(const uint32_t* __restrict__ raw, const uint32_t* __restrict__ rawmask, uint32_t Wp,
                         const uint32_t* __restrict__ ids, uint32_t n_use, uint32_t n_samples, uint32_t P,

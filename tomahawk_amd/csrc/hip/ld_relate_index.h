@@ -2,6 +2,8 @@
 // the six counts and the statistic of a sample pair follow from plane products (twk_hip_relationship, include/twk_hip.h).  Plain C++ with no
 // HIP in it: ld_relate.hip.h includes it, the engine's host code includes it, and so does csrc/tools/relate_index_check.cpp
 // (`make relate-check`), which plays the transposition lane by lane against a naive one and the count formulas against counted genotypes.
+// The count launches behind the transposition are not this file's: their tiles, units and the rule for a row's last K chunk are
+// ld_count_table.h's (build_count_table, count_last_halves), whose chunk and tile RL_KC and RL_TILE name.
 //
 // The plane set is sample-major: P rows a sample, one bit per variant IN USE, in the order of the call's variant list.
 //   P = 2 (no variant in use has missing genotypes): H (heterozygous), Q (homozygous ALT);
@@ -20,6 +22,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "ld_count_table.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define TWK_RL_FN __host__ __device__ inline
@@ -29,8 +32,8 @@
 
 namespace twk {
 
-constexpr uint32_t RL_KC = 32;                       // words of a K chunk of the count kernel (ld_count.hip.h: KC)
-constexpr uint32_t RL_TILE = 128;                    // rows of a tile of the count kernel (TILE)
+constexpr uint32_t RL_KC = KC;                       // words of a K chunk of the count kernel
+constexpr uint32_t RL_TILE = TILE;                   // rows of a tile of the count kernel
 constexpr uint32_t RL_THREADS = 256;                 // lanes of a transposition block: 4 waves
 constexpr uint32_t RL_CHUNK = 1024;                  // list positions a block takes: RL_KC words of every output row
 constexpr uint32_t RL_PASS_SAMPLES = 64;             // samples of a pass: 4 raw words (16 samples a word), one 16-byte load a lane
@@ -51,13 +54,6 @@ TWK_RL_FN uint64_t rl_rows_alloc(uint32_t n_samples, uint32_t P) { return ((uint
 TWK_RL_FN uint64_t rl_row(uint32_t sample, uint32_t plane, uint32_t P) { return (uint64_t)sample * P + plane; }
 TWK_RL_FN uint32_t rl_word(uint32_t position) { return position >> 5; }
 TWK_RL_FN uint32_t rl_bit(uint32_t position) { return position & 31u; }
-// Half-slots (8 bytes) of a row's last K chunk that carry data: CountWork::last_halves by the engine's own rule (0: all sixteen).
-TWK_RL_FN uint32_t rl_last_halves(uint32_t n_use) {
-	const uint32_t live = rl_words_live(n_use), W = rl_words(n_use);
-	if (!live || W - live >= RL_KC) return 0;
-	const uint32_t live_last = live - (W / RL_KC - 1) * RL_KC, halves = (live_last + 1) / 2;
-	return halves > 12 ? 0 : halves;
-}
 // Samples per axis of a super-tile.
 TWK_RL_FN uint32_t rl_super_samples(uint32_t P) { return RL_SUPER_ROWS / P; }
 

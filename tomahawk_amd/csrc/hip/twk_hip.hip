@@ -59,7 +59,6 @@ using namespace twk;
 
 namespace {
 
-inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
 // Every device and page-locked buffer of the engine is one of these (twk_buffers.h): the runtime's allocator behind the owner types.
 struct HipMemOps {
@@ -185,12 +184,6 @@ struct Slot {                      // one in-flight tile (double buffered)
 	// reduce launches (launch_reduce): the parameter blocks of the (up to two) passes, whatever the kind: pinned host copy + device copy
 	PinnedBuf<ReduceArgs> h_args; DevBuf<ReduceArgs> d_args;
 };
-
-// Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
-struct ColRange { const uint32_t* lo = nullptr; const uint32_t* hi = nullptr; uint32_t a0 = 0, b0 = 0;
-                  const uint32_t* d_hi = nullptr; uint32_t n_hi = 0;      // d_hi: device copy of hi, n_hi entries (r2 screen: the math kernel skips what was not contracted)
-                  uint32_t list_zone = 0;              // pairs with both set positions below it are intersected as carrier lists (ld_list.hip.h), not contracted
-                  uint32_t probe_zone = 0; };          // <= list_zone: every other pair of a row below it is decided by probing the column's row with the row's carriers (k_probe_screen)
 
 // Where a finished launch's sorted survivors go (finish_tile): appended to the device sink (!to_host), or to the host - left whole in
 // c->h_recs (sink == null: the single-tile entry point), or handed to `sink`.
@@ -331,9 +324,16 @@ struct twk_hip_ctx {
 
 namespace {
 
-struct Event {                     // a local event, destroyed on every way out
-	hipEvent_t e = nullptr;
-	~Event() { if (e) (void)hipEventDestroy(e); }
+struct Events {                    // the events of one call, destroyed on every way out
+	std::vector<hipEvent_t> v;
+	Events() = default;
+	Events(const Events&) = delete;
+	~Events() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
+	hipError_t add(size_t n) {
+		for (size_t k = 0; k < n; ++k) { hipEvent_t e = nullptr; const hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; v.push_back(e); }
+		return hipSuccess;
+	}
+	hipEvent_t operator[](size_t k) const { return v[k]; }
 };
 
 #define HIPCHK(ctx, call)                                                                         \
@@ -546,62 +546,6 @@ int ensure_host_records(twk_hip_ctx* c, unsigned long long n, char* err = nullpt
 // profiles/r03_fused_mid_n.txt: N = 60,000 -p, 4e4 variants: 46 + 15 ms -> 49 + 2.5 ms); the two meet near 220 chunks.
 constexpr uint32_t FUSED_MAX_CHUNKS = 128;
 
-struct Geometry { uint32_t rowsA, rowsB, gx, gy, ldc; };
-Geometry tile_geometry(int P, const twk_hip_tile_desc& t) {
-	Geometry g;
-	g.rowsA = round_up(t.nA * P, TILE); g.rowsB = round_up(t.nB * P, TILE);
-	g.gy = g.rowsA / TILE; g.gx = g.rowsB / TILE; g.ldc = g.rowsB;
-	return g;
-}
-
-// The 128 x 128 tiles of a super-tile that hold wanted pairs, as (tile row << 16 | tile column):
-// on or above the diagonal (diag), and in window mode only those some row of the tile can reach.
-// Order: 8 x 8 patches of tiles, patch by patch - the blocks pull consecutive tickets, so the ~P tiles in
-// flight at any time are a few neighbouring patches (shared row / column tiles meet in L2 and the MALL).
-void build_tile_list(const twk_hip_tile_desc& t, int P, const Geometry& g, bool diag, const ColRange* cr,
-                     std::vector<uint32_t>& out, std::vector<uint32_t>* patch_end = nullptr, uint32_t PR = 8, uint32_t PC = 8) {
-	std::vector<uint32_t> x0(g.gy, 0), x1(g.gy, g.gx);
-	for (uint32_t by = 0; by < g.gy; ++by) {
-		if (diag) x0[by] = by;
-		if (cr && cr->lo) {
-			const uint32_t v0 = t.rowA0 + (by * TILE) / P;
-			const uint32_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + P - 1) / P);   // exclusive
-			if (v0 >= v1) { x1[by] = x0[by]; continue; }
-			const uint64_t c_lo = (uint64_t)cr->b0 + cr->lo[v0 - cr->a0], c_hi = (uint64_t)cr->b0 + cr->hi[v1 - 1 - cr->a0];   // variants [c_lo, c_hi)
-			const uint64_t lo = std::max<uint64_t>(c_lo, t.rowB0), hi = std::min<uint64_t>(c_hi, (uint64_t)t.rowB0 + t.nB);
-			if (hi <= lo) { x1[by] = x0[by]; continue; }
-			x0[by] = std::max<uint32_t>(x0[by], (uint32_t)(((lo - t.rowB0) * P) / TILE));
-			x1[by] = std::min<uint32_t>(x1[by], (uint32_t)(((hi - t.rowB0) * P + TILE - 1) / TILE));
-			if (x1[by] < x0[by]) x1[by] = x0[by];
-		}
-		if (cr && cr->list_zone) {      // a row of tiles that lies wholly inside the list zone starts at the zone's last column tile
-			const uint64_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + P - 1) / P);
-			if (v1 <= cr->probe_zone) x1[by] = x0[by];                    // every pair of these rows is a list merge or a probe
-			else if (v1 <= cr->list_zone && cr->list_zone > t.rowB0) {
-				x0[by] = std::max<uint32_t>(x0[by], (uint32_t)((((uint64_t)cr->list_zone - t.rowB0) * P) / TILE));
-				if (x1[by] < x0[by]) x1[by] = x0[by];
-			}
-		}
-	}
-	std::vector<uint32_t> seq;
-	seq.reserve((size_t)g.gx * g.gy);
-	// Patch shape 8 x 8.  Measured (profiles/r03_patch_pmc.txt, FETCH_SIZE = what the L2s ask the fabric for, 16,384 variants
-	// at N = 1 M, 1.05 TB of tile-level demand per launch): 8 x 8 patches 258 GB per launch; wider patches are *worse*
-	// (16 x 32: 309 GB), and so is walking a patch K segment by K segment (TWK_HIP_SEG=64: 306 GB) - the tiles in flight
-	// are spread over eight L2s by the dispatcher, so fewer distinct row tiles in flight buys nothing per L2.  What does
-	// help is giving each XCD its own patches (TWK_HIP_XCD_QUEUES=8 with 64-chunk segments: 149 GB, -42 %), at +0.5 % kernel
-	// time for the adds into C; since the kernel is VALU-bound and the fabric sees < 10 % of its rate either way, that
-	// trade is not taken by default.  (Options "patch_rows" / "patch_cols" / "seg" / "xcd_queues" are the hooks of that measurement.)
-	if (patch_end) patch_end->clear();
-	for (uint32_t py = 0; py < g.gy; py += PR)
-		for (uint32_t px = 0; px < g.gx; px += PC) {
-			for (uint32_t y = py; y < std::min(py + PR, g.gy); ++y)
-				for (uint32_t x = std::max(px, x0[y]); x < std::min(px + PC, x1[y]); ++x) seq.push_back(y << 16 | x);
-			if (patch_end && (patch_end->empty() ? !seq.empty() : seq.size() > patch_end->back())) patch_end->push_back((uint32_t)seq.size());
-		}
-	out.swap(seq);
-}
-
 // Launch the count kernel for one tile on the compute stream (which: first or second launch of the slot - its event pair, ev_c0 / ev_c1
 // or ev_c0b / ev_c1b, and its row_pairs field follow from it).
 // form.fused: the fused kernels (k_count_screen_t) - no tile's K range is split, and the slot's C buffer holds the candidate list
@@ -620,76 +564,28 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	if ((uint64_t)t.rowA0 * P + g.rowsA > ps.rows_alloc || (uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
 	if (g.gx > 0xFFFFu || g.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
 	const bool diag = t.diag && t.rowA0 == t.rowB0;
-	const uint32_t n_blocks = c->resident_blocks;
-	std::vector<uint32_t> list, patch_end;
-	build_tile_list(t, P, g, diag, cr, list, &patch_end, (uint32_t)c->opt.patch_rows, (uint32_t)c->opt.patch_cols);
-	const size_t T = list.size();
-	// units of work: see build_count_units (ld_count.hip.h)
-	const uint32_t nchunks = ps.W / KC;
-	uint32_t min_chunks = (uint32_t)c->opt.count_min_chunks;      // (test hook: 1 splits short rows too)
-	if (fuse) min_chunks = nchunks + 1;              // whole tiles only: a block must hold a pair's whole count to screen it
-	std::vector<CountUnit> units;
-	uint32_t seg_chunks = (uint32_t)c->opt.seg;    // 0: whole tiles (see build_tile_list for the measurement behind that)
-	if (fuse) seg_chunks = 0;
-	uint32_t first_split = 0, n_queues = 1, queue_begin[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-	const uint32_t xcd_queues = (uint32_t)c->opt.xcd_queues;    // measurement hook (profiles/): one unit queue per XCD
-	if (T && !fuse && xcd_queues > 1 && xcd_queues <= 8 && nchunks >= 128 && !patch_end.empty()) {
-		// patches dealt round robin to the queues; within a queue patch after patch, each K segment by K segment
-		const uint32_t nseg = seg_chunks ? (nchunks + seg_chunks - 1) / seg_chunks : 1;
-		std::vector<std::vector<CountUnit>> qs(xcd_queues);
-		uint32_t p0 = 0;
-		for (size_t pi = 0; pi < patch_end.size(); ++pi) {
-			auto& qv = qs[pi % xcd_queues];
-			for (uint32_t sgm = 0; sgm < nseg; ++sgm)
-				for (uint32_t tl = p0; tl < patch_end[pi]; ++tl)
-					qv.push_back(CountUnit{tl, (uint32_t)((unsigned long long)nchunks * sgm / nseg), (uint32_t)((unsigned long long)nchunks * (sgm + 1) / nseg), 0});
-			p0 = patch_end[pi];
-		}
-		n_queues = xcd_queues;
-		for (uint32_t q = 0; q < n_queues; ++q) { queue_begin[q] = (uint32_t)units.size(); units.insert(units.end(), qs[q].begin(), qs[q].end()); }
-		for (uint32_t q = n_queues; q <= 8; ++q) queue_begin[q] = (uint32_t)units.size();
-		first_split = nseg > 1 ? 0 : (uint32_t)T;
-	} else {
-		first_split = T ? build_count_units((uint32_t)T, nchunks, n_blocks, min_chunks, units, 8, 8, patch_end.data(), (uint32_t)patch_end.size(), seg_chunks) : 0;
-		queue_begin[1] = (uint32_t)units.size();
-	}
-	fill_unit_tiles(units, list.data());
-	const size_t T4 = (T + 3) / 4 * 4, words_units = T4 + units.size() * 4;       // [tiles | pad | units], units 16-byte aligned
-	const size_t fa_words = (sizeof(FusedArgs) + 15) / 16 * 4;
-	const size_t words = words_units + (with_args ? fa_words : 0);               // [... | FusedArgs] for a fused or three-product launch
+	// the tiles and the units of work (ld_count_table.h; "count_min_chunks" is a test hook: 1 splits short rows too; "seg" 0: whole tiles and
+	// "xcd_queues": see build_tile_list for the measurement behind them)
+	CountSettings cs;
+	cs.patch_rows = (uint32_t)c->opt.patch_rows; cs.patch_cols = (uint32_t)c->opt.patch_cols; cs.min_chunks = (uint32_t)c->opt.count_min_chunks;
+	cs.seg_chunks = (uint32_t)c->opt.seg; cs.xcd_queues = (uint32_t)c->opt.xcd_queues; cs.n_blocks = c->resident_blocks; cs.fused = fuse;
+	const CountTable tb = build_count_table(t, P, diag, cr, ps.W / KC, cs);
+	const size_t T = tb.n_tiles();
+	const size_t words_units = tb.words(), fa_words = (sizeof(FusedArgs) + 15) / 16 * 4;
+	const size_t words = words_units + (with_args ? fa_words : 0);               // [tiles | pad | units | FusedArgs] for a fused or three-product launch
 	// (parked, the pinned one too: the device copy of the previous launch's table may still be travelling)
 	HIPCHK(c, reserve_together(words, std::max<size_t>(words, 16384), &c->graveyard, s.h_tiles[which], s.d_tiles[which]));
 	if (T) {
-		std::memcpy(s.h_tiles[which], list.data(), T * 4);
-		std::memcpy(s.h_tiles[which] + T4, units.data(), units.size() * sizeof(CountUnit));
+		tb.pack(s.h_tiles[which]);
 		if (with_args) std::memcpy(s.h_tiles[which] + words_units, fa, sizeof(FusedArgs));
 		HIPCHK(c, hipMemcpyAsync(s.d_tiles[which], s.h_tiles[which], words * 4, hipMemcpyHostToDevice, c->s_compute));
 	}
 	HIPCHK(c, hipEventRecord(e0, c->s_compute));
 	if (T) {
-		CountWork w{};
-		w.rows = ps.rows; w.W = ps.W; w.rowA0 = t.rowA0 * P; w.rowB0 = t.rowB0 * P;
-		w.tiles = s.d_tiles[which];
-		w.units = reinterpret_cast<const CountUnit*>(s.d_tiles[which] + T4); w.n_units = (uint32_t)units.size();
-		w.C = s.C; w.ldc = g.ldc;
-		w.ticket = c->tickets + ((&s - c->slot) * 2 + which) * 8;
-		w.n_queues = n_queues;
-		w.clocks = s.n_out + 4;
-		for (int q = 0; q < 9; ++q) w.queue_begin[q] = queue_begin[q];
-		{
-			const bool skip_pad = c->opt.skip_pad != 0;      // measurement hook: 0 = contract the zero padding too
-			const uint32_t live_last = ps.W_live - (ps.W / KC - 1) * KC;      // live words of the last chunk, 1..KC (W = W_live rounded up to KC)
-			w.last_halves = (skip_pad && ps.W_live && ps.W_live <= ps.W && ps.W - ps.W_live < KC) ? (live_last + 1) / 2 : 0;
-			// The shortened chunk runs a plain rolled loop (no reads in flight behind the contraction): worth it when it drops a
-			// quarter of the chunk or more, not for a half-slot or two (2,504 samples phased: 157 live words of 160, 15 half-slots
-			// of the fifth chunk - there the pipelined loop over all 16 is the faster one).
-			if (w.last_halves > 12) w.last_halves = 0;
-		}
+		const uint32_t last_halves = c->opt.skip_pad ? count_last_halves(ps.W_live, ps.W) : 0;      // (measurement hook: 0 = contract the zero padding too)
+		const CountWork w = count_work(ps.rows, ps.W, t.rowA0 * P, t.rowB0 * P, s.d_tiles[which], tb, s.C, g.ldc,
+		                               c->tickets + ((&s - c->slot) * 2 + which) * 8, last_halves, s.n_out + 4);
 		HIPCHK(c, hipMemsetAsync(w.ticket, 0, 8 * 4, c->s_compute));
-		if (first_split < T) {
-			hipLaunchKernelGGL(k_zero_tiles, dim3((uint32_t)T - first_split), dim3(256), 0, c->s_compute, w.tiles, first_split, w.C, w.ldc, (uint32_t)(three ? TILE / 2 : TILE));
-			HIPCHK(c, hipGetLastError());
-		}
 		const FusedArgs* d_fa = reinterpret_cast<const FusedArgs*>(s.d_tiles[which] + words_units);
 		if (with_args) { s.l.d_stats_dev = const_cast<StatsParams*>(&d_fa->stats); s.l.d_screen_dev = &d_fa->screen; }
 		// one kernel: into the candidate list (fused) or into a matrix; a density sample's runs under a name of its own (twk_hip_ctx::sampling)
@@ -699,10 +595,9 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		else if (three) k_matrix = c->sampling ? k_count3_list_t<COUNT_NW, 1> : k_count3_list_t<COUNT_NW>;
 		else if (fuse) k_list = form.unphased ? k_count_screen_unphased_t<COUNT_NW> : k_count_screen_t<COUNT_NW>;
 		else k_matrix = k_count_list_t<COUNT_NW>;
-		const dim3 grid(std::min(n_blocks, w.n_units)), block(COUNT_THREADS);
-		if (k_list) hipLaunchKernelGGL(k_list, grid, block, 0, c->s_compute, w, &d_fa->screen);
-		else hipLaunchKernelGGL(k_matrix, grid, block, 0, c->s_compute, w);
-		HIPCHK(c, hipGetLastError());
+		const uint32_t tile_rows = three ? TILE / 2 : TILE;
+		if (k_list) HIPCHK(c, enqueue_count(c->s_compute, w, tb, cs.n_blocks, tile_rows, nullptr, k_list, &d_fa->screen));
+		else HIPCHK(c, enqueue_count(c->s_compute, w, tb, cs.n_blocks, tile_rows, nullptr, k_matrix));
 	}
 	HIPCHK(c, hipEventRecord(e1, c->s_compute));
 	(which ? s.l.row_pairs_b : s.l.row_pairs) = (uint64_t)T * TILE * TILE;
@@ -2324,6 +2219,17 @@ int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 
 extern "C++" {      // (member templates)
 namespace {
+// Device memory that lives as long as one call: reserved, or the call fails with `what` - a format of `lead` (a count, or a name), the bytes
+// wanted and the runtime's reason - as TWK_HIP_E_NOMEM when the device cannot give it.
+template <class T, class Lead>
+int hold_for_call(twk_hip_ctx* c, DevBuf<T>& b, size_t items, const char* what, Lead lead) {
+	const hipError_t e = b.reserve(items, items, nullptr);
+	if (e == hipSuccess) return TWK_HIP_OK;
+	(void)hipGetLastError();
+	snprintf(c->err, sizeof(c->err), what, lead, items * sizeof(T), hipGetErrorString(e));
+	return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+}
+
 // One call of twk_hip_ld_score, _prune, _clump, _matrix, _decay or _aggregate: the region call's planner and launch pipeline with the kind's epilogue in place of
 // math, Fisher, sort and delivery (launch_reduce).  Constructed at the top of the entry point, which returns `bad` if the shared checks found
 // something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the
@@ -2355,12 +2261,7 @@ struct ReduceCall {
 	// call's three counters, zeroed.
 	template <class T>
 	int hold(DevBuf<T>& b, size_t items, const char* what, uint32_t n) {
-		const hipError_t e = b.reserve(items, items, nullptr);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			snprintf(c->err, sizeof(c->err), what, n, items * sizeof(T), hipGetErrorString(e));
-			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
-		}
+		const int rc = hold_for_call(c, b, items, what, n); if (rc) return rc;
 		HIPCHK(c, c->d_counts.reserve(3, 3, nullptr));
 		HIPCHK(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
 		return TWK_HIP_OK;
@@ -2401,17 +2302,16 @@ struct ReduceCall {
 	// then `rest`, then one wait for the stream.  Both enqueue and return the runtime's verdict.
 	template <class Timed, class Rest>
 	int tail(const char* what, Timed&& timed, Rest&& rest) {
-		Event w0, w1;
-		hipError_t e = hipEventCreate(&w0.e);
-		if (e == hipSuccess) e = hipEventCreate(&w1.e);
-		if (e == hipSuccess) e = hipEventRecord(w0.e, c->s_compute);
+		Events w;
+		hipError_t e = w.add(2);
+		if (e == hipSuccess) e = hipEventRecord(w[0], c->s_compute);
 		if (e == hipSuccess) e = timed();
-		if (e == hipSuccess) e = hipEventRecord(w1.e, c->s_compute);
+		if (e == hipSuccess) e = hipEventRecord(w[1], c->s_compute);
 		if (e == hipSuccess) e = rest();
 		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
 		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
 		float ms = 0;
-		if (hipEventElapsedTime(&ms, w0.e, w1.e) == hipSuccess) c->reduce_last[(int)kind].ms = ms;
+		if (hipEventElapsedTime(&ms, w[0], w[1]) == hipSuccess) c->reduce_last[(int)kind].ms = ms;
 		return TWK_HIP_OK;
 	}
 };
@@ -2634,25 +2534,13 @@ extern "C++" {
 namespace {
 static_assert(sizeof(RelCounts) == sizeof(twk_hip_rel_counts) && sizeof(RelCounts) == 24, "the epilogue stores twk_hip_rel_counts");
 
-struct EventList {                  // the events of one call, destroyed on every way out
-	std::vector<hipEvent_t> v;
-	~EventList() { for (hipEvent_t e : v) if (e) (void)hipEventDestroy(e); }
-	hipError_t add(size_t n) {
-		for (size_t k = 0; k < n; ++k) { hipEvent_t e = nullptr; const hipError_t rc = hipEventCreate(&e); if (rc != hipSuccess) return rc; v.push_back(e); }
-		return hipSuccess;
-	}
-};
-
-// Device memory of the call: TWK_HIP_E_NOMEM with the size in the context's error text when the device cannot give it.
+// Device memory of the call (hold_for_call), named in the error text.
 template <class T>
 int relate_hold(twk_hip_ctx* c, DevBuf<T>& buf, size_t items, const char* what) {
-	const hipError_t e = buf.reserve(items, items, nullptr);
-	if (e == hipSuccess) return TWK_HIP_OK;
-	snprintf(c->err, sizeof(c->err), "sample relationship: %s needs %zu bytes of device memory: %s", what, items * sizeof(T), hipGetErrorString(e));
-	return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+	return hold_for_call(c, buf, items, "sample relationship: %s needs %zu bytes of device memory: %s", what);
 }
 
-struct RelateSuper { uint32_t sa, na, sb, nb; bool diag; size_t list_at = 0, units_at = 0; uint32_t n_tiles = 0, n_units = 0, first_split = 0, ldc = 0; };
+struct RelateSuper { uint32_t sa, na, sb, nb; bool diag; CountTable table; size_t table_at = 0; };      // table_at: where the packed table lies in the call's one copy
 }  // namespace
 }  // extern "C++"
 
@@ -2688,16 +2576,16 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 	// (the transposition writes every word of the live rows; the zero rows behind them are set here)
 	HIPCHK(c, hipMemsetAsync(d_rows + live_rows * W, 0, (size_t)(rows_alloc - live_rows) * W * 4, c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_rowpop, 0, (size_t)rows_alloc * 4, c->s_compute));
-	EventList ev;
+	Events ev;
 	HIPCHK(c, ev.add(2));
-	HIPCHK(c, hipEventRecord(ev.v[0], c->s_compute));
+	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
 	{
 		const dim3 grid((N + RL_BLOCK_SAMPLES - 1) / RL_BLOCK_SAMPLES, std::min<uint32_t>(W / RL_KC, 65535u)), block(RL_THREADS);
 		hipLaunchKernelGGL(k_relate_transpose, grid, block, 0, c->s_compute, (const uint32_t*)c->raw, (const uint32_t*)(any_missing ? c->rawmask.get() : nullptr), c->Wp,
 		                   (const uint32_t*)(variants ? d_ids.get() : nullptr), n_use, N, P, d_rows.get(), W);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipEventRecord(ev.v[1], c->s_compute));
+	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
 	hipLaunchKernelGGL(k_row_popcount, dim3((unsigned)((live_rows + 3) / 4)), dim3(256), 0, c->s_compute, (const uint32_t*)d_rows, W, (uint32_t)live_rows, d_rowpop.get());
 	HIPCHK(c, hipGetLastError());
 
@@ -2705,29 +2593,21 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 	const bool square = sA0 == sB0 && nSA == nSB;
 	const uint32_t S = rl_super_samples(P), nchunks = W / KC, n_blocks = c->resident_blocks;
 	std::vector<RelateSuper> supers;
-	std::vector<uint32_t> blob;               // per super-tile: [tiles | pad to 16 bytes | units]
+	std::vector<uint32_t> blob;               // per super-tile: its packed table (CountTable::pack)
+	CountSettings cs;                         // (one queue of whole-tile units and a guided tail: "seg" and "xcd_queues" are the variant path's)
+	cs.patch_rows = (uint32_t)c->opt.patch_rows; cs.patch_cols = (uint32_t)c->opt.patch_cols; cs.min_chunks = (uint32_t)c->opt.count_min_chunks; cs.n_blocks = n_blocks;
 	size_t c_words = 0;
 	for (uint32_t ia = 0; ia < nSA; ia += S)
 		for (uint32_t ib = 0; ib < nSB; ib += S) {
 			if (square && ib < ia) continue;
 			RelateSuper st{sA0 + ia, std::min(S, nSA - ia), sB0 + ib, std::min(S, nSB - ib), square && ia == ib};
 			const twk_hip_tile_desc t{st.sa, st.na, st.sb, st.nb, st.diag ? 1 : 0, 0, 0, 0};
-			const Geometry g = tile_geometry((int)P, t);
-			std::vector<uint32_t> list, patch_end;
-			build_tile_list(t, (int)P, g, st.diag, nullptr, list, &patch_end, (uint32_t)c->opt.patch_rows, (uint32_t)c->opt.patch_cols);
-			std::vector<CountUnit> units;
-			st.n_tiles = (uint32_t)list.size();
-			st.first_split = build_count_units(st.n_tiles, nchunks, n_blocks, (uint32_t)c->opt.count_min_chunks, units, 8, 8);
-			fill_unit_tiles(units, list.data());
-			st.n_units = (uint32_t)units.size(); st.ldc = g.ldc;
-			st.list_at = blob.size();
-			blob.insert(blob.end(), list.begin(), list.end());
-			blob.resize((blob.size() + 3) / 4 * 4);
-			st.units_at = blob.size();
-			blob.resize(blob.size() + units.size() * 4);
-			std::memcpy(blob.data() + st.units_at, units.data(), units.size() * sizeof(CountUnit));
-			c_words = std::max(c_words, (size_t)g.rowsA * g.rowsB);
-			supers.push_back(st);
+			st.table = build_count_table(t, (int)P, st.diag, nullptr, nchunks, cs);
+			st.table_at = blob.size();
+			blob.resize(blob.size() + st.table.words());
+			st.table.pack(blob.data() + st.table_at);
+			c_words = std::max(c_words, (size_t)st.table.g.rowsA * st.table.g.rowsB);
+			supers.push_back(std::move(st));
 		}
 	const size_t cells = (size_t)nSA * nSB;
 	rc = relate_hold(c, d_C, c_words, "the count matrix of a super-tile"); if (rc) return rc;
@@ -2741,7 +2621,7 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 	for (size_t k = 0; k < supers.size(); ++k) {
 		const RelateSuper& st = supers[k];
 		RelateArgs& a = args[k];
-		a.C = d_C; a.ldc = st.ldc; a.P = P; a.n_use = n_use; a.rowpop = d_rowpop;
+		a.C = d_C; a.ldc = st.table.g.ldc; a.P = P; a.n_use = n_use; a.rowpop = d_rowpop;
 		a.sa = st.sa; a.na = st.na; a.sb = st.sb; a.nb = st.nb;
 		a.out_a0 = sA0; a.out_b0 = sB0; a.out_ld = nSB;
 		a.diag = st.diag ? 1 : 0; a.mirror = square ? 1 : 0; a.stat = stat; a.fill_bits = fill_bits;
@@ -2752,40 +2632,27 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 	HIPCHK(c, hipMemcpyAsync(d_args, args.data(), args.size() * sizeof(RelateArgs), hipMemcpyHostToDevice, c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_tickets, 0, supers.size() * 8 * 4, c->s_compute));
 	HIPCHK(c, ev.add(3 * supers.size()));
+	const uint32_t last_halves = c->opt.skip_pad ? count_last_halves(rl_words_live(n_use), W) : 0;
 	for (size_t k = 0; k < supers.size(); ++k) {
 		const RelateSuper& st = supers[k];
-		CountWork w{};
-		w.rows = d_rows; w.W = W; w.rowA0 = st.sa * P; w.rowB0 = st.sb * P;
-		w.tiles = d_lists + st.list_at;
-		w.units = reinterpret_cast<const CountUnit*>(d_lists + st.units_at); w.n_units = st.n_units;
-		w.C = d_C; w.ldc = st.ldc;
-		w.ticket = d_tickets + k * 8;
-		w.n_queues = 1; w.queue_begin[0] = 0; w.queue_begin[1] = st.n_units;
-		w.last_halves = c->opt.skip_pad ? rl_last_halves(n_use) : 0;
-		w.clocks = nullptr;
-		if (st.first_split < st.n_tiles) {
-			hipLaunchKernelGGL(k_zero_tiles, dim3(st.n_tiles - st.first_split), dim3(256), 0, c->s_compute, w.tiles, st.first_split, w.C, w.ldc, (uint32_t)TILE);
-			HIPCHK(c, hipGetLastError());
-		}
-		HIPCHK(c, hipEventRecord(ev.v[2 + 3 * k], c->s_compute));
-		hipLaunchKernelGGL(k_count_list_t<COUNT_NW>, dim3(std::min(n_blocks, w.n_units)), dim3(COUNT_THREADS), 0, c->s_compute, w);
-		HIPCHK(c, hipGetLastError());
-		HIPCHK(c, hipEventRecord(ev.v[3 + 3 * k], c->s_compute));
+		const CountWork w = count_work(d_rows, W, st.sa * P, st.sb * P, d_lists + st.table_at, st.table, d_C, st.table.g.ldc, d_tickets + k * 8, last_halves, nullptr);
+		HIPCHK(c, enqueue_count(c->s_compute, w, st.table, n_blocks, (uint32_t)TILE, ev[2 + 3 * k], k_count_list_t<COUNT_NW>));      // (the count's time starts behind the zeroing)
+		HIPCHK(c, hipEventRecord(ev[3 + 3 * k], c->s_compute));
 		hipLaunchKernelGGL(k_relate_epilogue, dim3((st.nb + RL_EP - 1) / RL_EP, (st.na + RL_EP - 1) / RL_EP), dim3(RL_THREADS), 0, c->s_compute, (const RelateArgs*)(d_args + k));
 		HIPCHK(c, hipGetLastError());
-		HIPCHK(c, hipEventRecord(ev.v[4 + 3 * k], c->s_compute));
+		HIPCHK(c, hipEventRecord(ev[4 + 3 * k], c->s_compute));
 	}
 	if (out) HIPCHK(c, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), d_out, (size_t)nSB * sizeof(double), (size_t)nSB * sizeof(double), nSA, hipMemcpyDeviceToHost, c->s_compute));
 	if (counts) HIPCHK(c, hipMemcpy2DAsync(counts, (size_t)ld_counts * sizeof(RelCounts), d_counts, (size_t)nSB * sizeof(RelCounts), (size_t)nSB * sizeof(RelCounts), nSA, hipMemcpyDeviceToHost, c->s_compute));
 	HIPCHK(c, hipStreamSynchronize(c->s_compute));
 	float ms = 0;
 	c->relate_last.planes = (int32_t)P; c->relate_last.plane_bytes = (uint64_t)rows_alloc * W * 4;
-	c->relate_last.transpose_ms = hipEventElapsedTime(&ms, ev.v[0], ev.v[1]) == hipSuccess ? ms : 0.0;
+	c->relate_last.transpose_ms = hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0.0;
 	for (size_t k = 0; k < supers.size(); ++k) {
-		if (hipEventElapsedTime(&ms, ev.v[2 + 3 * k], ev.v[3 + 3 * k]) == hipSuccess) c->timing.count_ms += ms;
-		if (hipEventElapsedTime(&ms, ev.v[3 + 3 * k], ev.v[4 + 3 * k]) == hipSuccess) c->timing.stats_ms += ms;
+		if (hipEventElapsedTime(&ms, ev[2 + 3 * k], ev[3 + 3 * k]) == hipSuccess) c->timing.count_ms += ms;
+		if (hipEventElapsedTime(&ms, ev[3 + 3 * k], ev[4 + 3 * k]) == hipSuccess) c->timing.stats_ms += ms;
 		c->timing.count_launches += 1; c->timing.stats_launches += 1;
-		c->timing.row_pairs += (uint64_t)supers[k].n_tiles * TILE * TILE;
+		c->timing.row_pairs += (uint64_t)supers[k].table.n_tiles() * TILE * TILE;
 	}
 	if (n_sample_pairs) *n_sample_pairs = square ? (uint64_t)nSA * (nSA + 1) / 2 : (uint64_t)nSA * nSB;
 	return TWK_HIP_OK;
@@ -2861,25 +2728,24 @@ int twk_hip_fisher_exact(twk_hip_ctx* c, const int32_t* tables, uint64_t n, doub
 	if (!c->d_lfact) return TWK_HIP_E_STATE;
 	HIPCHK(c, hipSetDevice(c->device));
 	DevBuf<int32_t> d_t; DevBuf<twk_hip_record> d_r; DevBuf<double> d_p; DevBuf<unsigned long long> d_n;
-	Event e0, e1;
+	Events ev;
 	hipError_t e = d_t.reserve((size_t)n * 4, (size_t)n * 4, nullptr);
 	if (e == hipSuccess) e = d_r.reserve(n, n, nullptr);
 	if (e == hipSuccess) e = d_p.reserve(n, n, nullptr);
 	if (e == hipSuccess) e = d_n.reserve(4, 4, nullptr);
-	if (e == hipSuccess) e = hipEventCreate(&e0.e);
-	if (e == hipSuccess) e = hipEventCreate(&e1.e);
+	if (e == hipSuccess) e = ev.add(2);
 	const unsigned long long counters[4] = {n, 0, 0, 0};
 	if (e == hipSuccess) e = hipMemcpyAsync(d_t, tables, (size_t)n * 16, hipMemcpyHostToDevice, c->s_compute);
 	if (e == hipSuccess) e = hipMemcpyAsync(d_n, counters, sizeof(counters), hipMemcpyHostToDevice, c->s_compute);
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(k_tables_to_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->s_compute, d_t, (unsigned long long)n, d_r);
-		e = hipEventRecord(e0.e, c->s_compute);
+		e = hipEventRecord(ev[0], c->s_compute);
 	}
 	if (e == hipSuccess) {
 		// as the engine runs it (walk-length order; the table buffer is free: the tables are in the records by now), or in the order given
 		const int rc = launch_fisher(c, d_r, d_n, (unsigned long long)n, 2.0, in_given_order ? nullptr : (uint32_t*)d_t.get(), (size_t)n * 4);
 		if (rc) return rc;
-		e = hipEventRecord(e1.e, c->s_compute);
+		e = hipEventRecord(ev[1], c->s_compute);
 	}
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(k_records_to_p, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->s_compute, d_r, (unsigned long long)n, d_p);
@@ -2887,7 +2753,7 @@ int twk_hip_fisher_exact(twk_hip_ctx* c, const int32_t* tables, uint64_t n, doub
 	}
 	if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
 	if (e == hipSuccess) e = hipGetLastError();
-	if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, e0.e, e1.e);
+	if (e == hipSuccess && kernel_ms) e = hipEventElapsedTime(kernel_ms, ev[0], ev[1]);
 	HIPCHK(c, e);
 	return TWK_HIP_OK;
 }
@@ -3002,9 +2868,9 @@ int twk_hip_gather_records(twk_hip_ctx* const* ctxs, uint32_t n, uint32_t dst, i
 		d->d_keep_n = own;
 		const int e = ensure_device_keep(d, total - own); if (e) return e;         // (keeps the destination's own records, at the front)
 	}
-	Event e0, e1;
-	HIPCHK(d, hipEventCreate(&e0.e)); HIPCHK(d, hipEventCreate(&e1.e));
-	HIPCHK(d, hipEventRecord(e0.e, d->s_copy));
+	Events ev;
+	HIPCHK(d, ev.add(2));
+	HIPCHK(d, hipEventRecord(ev[0], d->s_copy));
 	int rcode = NCHK(rc.GroupStart(), "ncclGroupStart");
 	for (uint32_t r = 0; r < n && !rcode; ++r) {
 		if (!loop && r == dst) continue;
@@ -3018,13 +2884,13 @@ int twk_hip_gather_records(twk_hip_ctx* const* ctxs, uint32_t n, uint32_t dst, i
 	}
 	{ const int e = NCHK(rc.GroupEnd(), "ncclGroupEnd"); if (!rcode) rcode = e; }
 	(void)hipSetDevice(d->device);
-	if (!rcode && hipEventRecord(e1.e, d->s_copy) != hipSuccess) rcode = TWK_HIP_E_DEVICE;
+	if (!rcode && hipEventRecord(ev[1], d->s_copy) != hipSuccess) rcode = TWK_HIP_E_DEVICE;
 	for (uint32_t r = 0; r < n && !rcode; ++r) {
 		if (hipSetDevice(ctxs[r]->device) != hipSuccess || hipStreamSynchronize(ctxs[r]->s_copy) != hipSuccess) rcode = TWK_HIP_E_DEVICE;
 	}
 	(void)hipSetDevice(d->device);
 	float ms = 0;
-	if (!rcode && hipEventElapsedTime(&ms, e0.e, e1.e) == hipSuccess && transfer_ms) *transfer_ms = ms;
+	if (!rcode && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess && transfer_ms) *transfer_ms = ms;
 	if (rcode) { if (!d->err[0]) snprintf(d->err, sizeof(d->err), "RCCL gather: a HIP call failed"); return rcode; }
 	if (loop) {
 		if (loop_buf) d->d_keep = std::move(loop_buf);        // the records that went round are the sink's content from here on

@@ -13,12 +13,19 @@
 #include "../hip/ld_count.hip.h"
 #define CK(x) do{hipError_t e=(x); if(e!=hipSuccess){fprintf(stderr,"HIP %s @%d: %s\n",#x,__LINE__,hipGetErrorString(e)); exit(1);} }while(0)
 
-static std::vector<uint32_t> make_list(uint32_t g, int diag, bool patch) {
-	std::vector<uint32_t> seq;
-	if (!patch) { for (uint32_t y = 0; y < g; ++y) for (uint32_t x = diag ? y : 0; x < g; ++x) seq.push_back(y << 16 | x); return seq; }
-	for (uint32_t py = 0; py < g; py += 8) for (uint32_t px = 0; px < g; px += 8)
-		for (uint32_t y = py; y < std::min(py + 8, g); ++y) for (uint32_t x = std::max(px, diag ? y : 0u); x < std::min(px + 8, g); ++x) seq.push_back(y << 16 | x);
-	return seq;
+// The table of the R x R rows (ld_count_table.h), on the device at dt.  patch: 8 x 8 patches as the engine walks them, else row by row (patches of one
+// row of tiles); knobs: SHAREDIV / TAILROUNDS of the guided tail from the environment; fused: whole tiles only.
+static twk::CountTable make_table(uint32_t R, uint32_t W, int diag, bool patch, uint32_t blocks, uint32_t min_chunks, uint32_t* dt, bool knobs = false, bool fused = false) {
+	twk::CountSettings cs; cs.n_blocks = blocks; cs.min_chunks = min_chunks; cs.fused = fused;
+	if (!patch) { cs.patch_rows = 1; cs.patch_cols = std::max(R / 128, 1u); }
+	if (knobs && getenv("SHAREDIV")) cs.share_div = atoi(getenv("SHAREDIV"));
+	if (knobs && getenv("TAILROUNDS")) cs.tail_rounds = atoi(getenv("TAILROUNDS"));
+	const twk_hip_tile_desc t{0, R, 0, R, diag, 0, 0, 0};
+	const twk::CountTable tb = twk::build_count_table(t, 1, diag != 0, nullptr, W / twk::KC, cs);
+	std::vector<uint32_t> image(tb.words());
+	tb.pack(image.data());
+	CK(hipMemcpy(dt, image.data(), image.size() * 4, hipMemcpyHostToDevice));
+	return tb;
 }
 int main(int argc,char**argv){
   uint32_t R = argc>1? atoi(argv[1]) : 4096;     // rows (multiple of 128)
@@ -29,8 +36,8 @@ int main(int argc,char**argv){
   std::vector<uint32_t> h(nw); std::mt19937 rng(1); for(auto&x:h) x=rng();
   if(getenv("FUSED") && getenv("LIVE")) for(uint32_t r=0;r<R;++r) for(uint32_t k=atoi(getenv("LIVE"));k<W;++k) h[(size_t)r*W+k]=0;      // zero padding behind the live words
   if(getenv("FUSED")) for(uint32_t r=1;r<R;r+=2) for(uint32_t k=0;k<W;++k) h[(size_t)r*W+k] &= ~h[(size_t)(r-1)*W+k];   // rows 2v / 2v + 1 as a variant's H / Q planes: disjoint
-  uint32_t *d,*C,*dl; twk::CountUnit* du; CK(hipMalloc(&d,nw*4)); CK(hipMalloc(&C,(size_t)R*R*4)); CK(hipMalloc(&dl,(size_t)(R/128)*(R/128)*4)); CK(hipMalloc(&du,(size_t)(R/128)*(R/128)*64*16+65536));
-  const uint32_t min_chunks = getenv("MINCHUNKS")? atoi(getenv("MINCHUNKS")) : 8; uint32_t first_split=0; std::vector<twk::CountUnit> units;
+  uint32_t *d,*C,*dt; CK(hipMalloc(&d,nw*4)); CK(hipMalloc(&C,(size_t)R*R*4)); CK(hipMalloc(&dt,(size_t)(R/128)*(R/128)*(4+(size_t)(W/twk::KC)*16)+65536));      // dt: room for every tile in units of one chunk
+  const uint32_t min_chunks = getenv("MINCHUNKS")? atoi(getenv("MINCHUNKS")) : 8;
   CK(hipMemcpy(d,h.data(),nw*4,hipMemcpyHostToDevice)); CK(hipMemset(C,0xff,(size_t)R*R*4));
   dim3 grid(R/128,R/128), block(twk::COUNT_THREADS);
   hipEvent_t e0,e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
@@ -56,17 +63,15 @@ int main(int argc,char**argv){
     // buffer; 3 warm launches, then the best of `reps`, per offset.
     const int n=atoi(bs); const size_t step=getenv("STEP")? strtoull(getenv("STEP"),nullptr,10) : (2ull<<20);
     uint8_t* big; CK(hipMalloc(&big,nw*4+(size_t)n*step));
-    std::vector<uint32_t> list=make_list(R/128,0,true); CK(hipMemcpy(dl,list.data(),list.size()*4,hipMemcpyHostToDevice));
-    twk::CountWork w{}; w.W=W; w.tiles=dl; w.C=C; w.ldc=R; w.ticket=tick;
-    first_split=twk::build_count_units((uint32_t)list.size(),W/twk::KC,P,min_chunks,units,8,8); twk::fill_unit_tiles(units,list.data());
-    CK(hipMemcpy(du,units.data(),units.size()*16,hipMemcpyHostToDevice)); w.units=du; w.n_units=(uint32_t)units.size(); w.n_queues=1; w.queue_begin[0]=0; w.queue_begin[1]=w.n_units;
+    const twk::CountTable tb=make_table(R,W,0,true,P,min_chunks,dt);
+    twk::CountWork w=twk::count_work(nullptr,W,0,0,dt,tb,C,R,tick,0,nullptr);
     std::vector<float> ms_all;
     for(int o=0;o<n;++o){
       uint32_t* base=reinterpret_cast<uint32_t*>(big+(size_t)o*step);
       CK(hipMemcpy(base,d,nw*4,hipMemcpyDeviceToDevice)); w.rows=base;
       float best=1e30f;
-      for(int i=0;i<3+reps;++i){ CK(hipMemsetAsync(tick,0,4,0)); if(first_split<list.size()) hipLaunchKernelGGL(twk::k_zero_tiles,dim3((uint32_t)list.size()-first_split),dim3(256),0,0,w.tiles,first_split,C,R);
-        CK(hipEventRecord(e0)); hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW>),dim3(P),block,0,0,w); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms,e0,e1)); if(i>=3&&ms<best)best=ms; }
+      for(int i=0;i<3+reps;++i){ CK(hipMemsetAsync(tick,0,4,0));
+        CK(twk::enqueue_count(0,w,tb,P,128u,e0,twk::k_count_list_t<twk::COUNT_NW>)); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms,e0,e1)); if(i>=3&&ms<best)best=ms; }
       ms_all.push_back(best);
     }
     float mn=1e30f,mx=0; for(float x:ms_all){ mn=std::min(mn,x); mx=std::max(mx,x); }
@@ -75,10 +80,10 @@ int main(int argc,char**argv){
     return 0;
   }
   if(getenv("FINISH")){   // probe: per-block finish times of the static list kernel (2 full rounds), by XCD
-    std::vector<uint32_t> list=make_list(R/128,0,true); CK(hipMemcpy(dl,list.data(),list.size()*4,hipMemcpyHostToDevice));
-    twk::CountWork w{}; w.rows=d; w.W=W; w.tiles=dl; w.C=C; w.ldc=R; w.ticket=tick; first_split=twk::build_count_units((uint32_t)list.size(),W/twk::KC,P,min_chunks,units,getenv("SHAREDIV")?atoi(getenv("SHAREDIV")):8,getenv("TAILROUNDS")?atoi(getenv("TAILROUNDS")):8); twk::fill_unit_tiles(units,list.data()); CK(hipMemcpy(du,units.data(),units.size()*16,hipMemcpyHostToDevice)); w.units=du; w.n_units=(uint32_t)units.size(); w.n_queues=1; w.queue_begin[0]=0; w.queue_begin[1]=w.n_units;
+    const twk::CountTable tb=make_table(R,W,0,true,P,min_chunks,dt,true);
+    const twk::CountWork w=twk::count_work(d,W,0,0,dt,tb,C,R,tick,0,nullptr);
     const int probe_reps = getenv("FINISH_REPS")? atoi(getenv("FINISH_REPS")) : 2;       // launches back to back; the last one is reported
-    for(int rep=0;rep<probe_reps;++rep){ CK(hipMemset(tick,0,4)); if(first_split<list.size()) hipLaunchKernelGGL(twk::k_zero_tiles,dim3((uint32_t)list.size()-first_split),dim3(256),0,0,w.tiles,first_split,C,R); hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW,5>),dim3(P),block,0,0,w); }
+    for(int rep=0;rep<probe_reps;++rep){ CK(hipMemset(tick,0,4)); CK(twk::enqueue_count(0,w,tb,P,128u,nullptr,twk::k_count_list_t<twk::COUNT_NW,5>)); }
     CK(hipDeviceSynchronize());
     std::vector<unsigned long long> o4(4*P); CK(hipMemcpy(o4.data(),C,o4.size()*8,hipMemcpyDeviceToHost));
     std::vector<unsigned long long> o(2*P); for(uint32_t b=0;b<P;++b){ o[2*b]=o4[4*b]; o[2*b+1]=o4[4*b+1]; }
@@ -95,12 +100,9 @@ int main(int argc,char**argv){
   }
   if(getenv("FUSED")){   // the fused count -> screen kernels on whole tiles (short rows), with their epilogue and without it (EXPERIMENT 6):
     // what does the screen cost next to the K loop?  Random rows, so nothing passes the screen.  LIVE=<words>: the row's live words (last chunk cut short)
-    std::vector<uint32_t> list=make_list(R/128,0,true); CK(hipMemcpy(dl,list.data(),list.size()*4,hipMemcpyHostToDevice));
     const uint32_t live = getenv("LIVE")? atoi(getenv("LIVE")) : W;
-    twk::CountWork w{}; w.rows=d; w.W=W; w.tiles=dl; w.C=C; w.ldc=R; w.ticket=tick;
-    { const uint32_t live_last = live - (W/twk::KC - 1)*twk::KC; w.last_halves = (live<W && W-live<twk::KC) ? (live_last+1)/2 : 0; if(w.last_halves>12) w.last_halves=0; }
-    twk::build_count_units((uint32_t)list.size(),W/twk::KC,P,W/twk::KC+1,units,8,8); twk::fill_unit_tiles(units,list.data());
-    CK(hipMemcpy(du,units.data(),units.size()*16,hipMemcpyHostToDevice)); w.units=du; w.n_units=(uint32_t)units.size(); w.n_queues=1; w.queue_begin[0]=0; w.queue_begin[1]=w.n_units;
+    const twk::CountTable tb=make_table(R,W,0,true,P,min_chunks,dt,false,true);
+    const twk::CountWork w=twk::count_work(d,W,0,0,dt,tb,C,R,tick,twk::count_last_halves(live,W),nullptr);
     std::vector<uint32_t> pop(R+256); for(uint32_t r=0;r<R;++r){ uint32_t c=0; for(uint32_t k=0;k<W;++k) c+=__builtin_popcount(h[(size_t)r*W+k]); pop[r]=c; }
     uint32_t* dpop; CK(hipMalloc(&dpop,pop.size()*4)); CK(hipMemcpy(dpop,pop.data(),pop.size()*4,hipMemcpyHostToDevice));
     unsigned long long* dn; CK(hipMalloc(&dn,64)); CK(hipMemset(dn,0,64));
@@ -108,7 +110,7 @@ int main(int argc,char**argv){
     sw.cand=C; sw.cap=(unsigned long long)R*R/8; sw.n_cand=dn; sw.chunk=64;
     twk::ScreenWork* dsw; CK(hipMalloc(&dsw,sizeof(sw)));
     float4* dterms; CK(hipMalloc(&dterms,(size_t)(R+256)*sizeof(float4)));
-    const double tiles=(double)list.size();
+    const double tiles=(double)tb.n_tiles();
     for(int form=0; form<3; ++form){   // 0 phased (rows = variants), 1 unphased four products, 2 unphased three products (rows 2v, 2v+1 = H, Q)
       sw.nA=sw.nB= form? R/2 : R; sw.n_variants=sw.nA; sw.two_n = form? 2.0*W*32 : 1.0*W*32;
       hipLaunchKernelGGL(twk::k_screen_terms,dim3((sw.nA+255)/256),dim3(256),0,0,(const uint32_t*)dpop,sw.nA,form?2:1,sw.two_n,sw.cut,dterms);
@@ -116,9 +118,11 @@ int main(int argc,char**argv){
       CK(hipMemcpy(dsw,&sw,sizeof(sw),hipMemcpyHostToDevice));
       for(int noepi=0; noepi<2; ++noepi){
         auto launch=[&](){ CK(hipMemsetAsync(tick,0,4,0)); CK(hipMemsetAsync(dn,0,8,0));
-          if(form==0){ if(noepi) hipLaunchKernelGGL((twk::k_count_screen_t<twk::COUNT_NW,6>),dim3(P),block,0,0,w,dsw); else hipLaunchKernelGGL((twk::k_count_screen_t<twk::COUNT_NW,0>),dim3(P),block,0,0,w,dsw); }
-          else if(form==1){ if(noepi) hipLaunchKernelGGL((twk::k_count_screen_unphased_t<twk::COUNT_NW,6>),dim3(P),block,0,0,w,dsw); else hipLaunchKernelGGL((twk::k_count_screen_unphased_t<twk::COUNT_NW,0>),dim3(P),block,0,0,w,dsw); }
-          else { if(noepi) hipLaunchKernelGGL((twk::k_count3_screen_unphased_t<twk::COUNT_NW,6>),dim3(P),block,0,0,w,dsw); else hipLaunchKernelGGL((twk::k_count3_screen_unphased_t<twk::COUNT_NW,0>),dim3(P),block,0,0,w,dsw); } };
+          void (*k)(twk::CountWork,const twk::ScreenWork*) =
+            form==0? (noepi? twk::k_count_screen_t<twk::COUNT_NW,6> : twk::k_count_screen_t<twk::COUNT_NW,0>) :
+            form==1? (noepi? twk::k_count_screen_unphased_t<twk::COUNT_NW,6> : twk::k_count_screen_unphased_t<twk::COUNT_NW,0>) :
+                     (noepi? twk::k_count3_screen_unphased_t<twk::COUNT_NW,6> : twk::k_count3_screen_unphased_t<twk::COUNT_NW,0>);
+          CK(twk::enqueue_count(0,w,tb,P,128u,nullptr,k,(const twk::ScreenWork*)dsw)); };
         launch(); launch(); CK(hipDeviceSynchronize());
         float best=1e30f;
         for(int i=0;i<reps;++i){ CK(hipEventRecord(e0)); launch(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms,e0,e1)); if(ms<best)best=ms; }
@@ -133,17 +137,15 @@ int main(int argc,char**argv){
   }
   if(getenv("THREE")){   // the three-product form of the unphased planes (rows 2v / 2v + 1 = H / Q of variant v): k_count3_list_t against k_count_list_t on
     // the same rows, patch order, rectangle; checked against the host on sampled variant pairs
-    std::vector<uint32_t> list=make_list(R/128,0,true); CK(hipMemcpy(dl,list.data(),list.size()*4,hipMemcpyHostToDevice));
-    twk::CountWork w{}; w.rows=d; w.W=W; w.tiles=dl; w.C=C; w.ldc=R; w.ticket=tick;
-    first_split=twk::build_count_units((uint32_t)list.size(),W/twk::KC,P,min_chunks,units,8,8); twk::fill_unit_tiles(units,list.data());
-    CK(hipMemcpy(du,units.data(),units.size()*16,hipMemcpyHostToDevice)); w.units=du; w.n_units=(uint32_t)units.size(); w.n_queues=1; w.queue_begin[0]=0; w.queue_begin[1]=w.n_units;
-    const double tiles=(double)list.size(), wordops=tiles*128*128*W;
+    const twk::CountTable tb=make_table(R,W,0,true,P,min_chunks,dt);
+    const twk::CountWork w=twk::count_work(d,W,0,0,dt,tb,C,R,tick,0,nullptr);
+    const double tiles=(double)tb.n_tiles(), wordops=tiles*128*128*W;
     if(const char* ex=getenv("EXPER")){   // timing only (wrong counts): the three- and four-product list kernels without the chunk barrier (7) / without the operand staging (8)
       const int which=atoi(ex);
       for(int three=0; three<2; ++three){
         auto launch=[&](){ CK(hipMemsetAsync(tick,0,4,0));
-          if(which==7){ if(three) hipLaunchKernelGGL((twk::k_count3_list_t<twk::COUNT_NW,7>),dim3(P),block,0,0,w); else hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW,7>),dim3(P),block,0,0,w); }
-          else { if(three) hipLaunchKernelGGL((twk::k_count3_list_t<twk::COUNT_NW,8>),dim3(P),block,0,0,w); else hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW,8>),dim3(P),block,0,0,w); } };
+          void (*k)(twk::CountWork) = which==7? (three? twk::k_count3_list_t<twk::COUNT_NW,7> : twk::k_count_list_t<twk::COUNT_NW,7>) : (three? twk::k_count3_list_t<twk::COUNT_NW,8> : twk::k_count_list_t<twk::COUNT_NW,8>);
+          CK(twk::enqueue_count(0,w,tb,P,three?64u:128u,nullptr,k)); };
         launch(); CK(hipDeviceSynchronize()); float best=1e30f;
         for(int i=0;i<reps;++i){ CK(hipEventRecord(e0)); launch(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms,e0,e1)); if(ms<best)best=ms; }
         const double exec=three? wordops*0.75 : wordops;
@@ -153,9 +155,8 @@ int main(int argc,char**argv){
     }
     for(int three=0; three<2; ++three){
       auto launch=[&](){ CK(hipMemsetAsync(tick,0,4,0));
-        const uint32_t fs = first_split;
-        if(fs<list.size()) hipLaunchKernelGGL(twk::k_zero_tiles,dim3((uint32_t)list.size()-fs),dim3(256),0,0,w.tiles,fs,C,R,three?64u:128u);
-        if(three) hipLaunchKernelGGL((twk::k_count3_list_t<twk::COUNT_NW>),dim3(P),block,0,0,w); else hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW>),dim3(P),block,0,0,w); };
+        void (*k)(twk::CountWork) = three? twk::k_count3_list_t<twk::COUNT_NW> : twk::k_count_list_t<twk::COUNT_NW>;
+        CK(twk::enqueue_count(0,w,tb,P,three?64u:128u,nullptr,k)); };
       CK(hipMemset(C,0xff,(size_t)R*R*4)); launch(); CK(hipDeviceSynchronize());
       if(three){ std::vector<uint32_t> hc((size_t)R*R/2); CK(hipMemcpy(hc.data(),C,hc.size()*4,hipMemcpyDeviceToHost)); int bad=0; std::mt19937 r2(7);
         for(int s=0;s<2000;++s){ const uint32_t a=r2()%(R/2), b=r2()%(R/2); uint32_t hh=0, ss=0;
@@ -169,7 +170,7 @@ int main(int argc,char**argv){
       for(int i=0;i<reps;++i){ CK(hipEventRecord(e0)); launch(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms,e0,e1)); if(ms<best)best=ms; }
       const double exec=three? wordops*0.75 : wordops;
       printf("%-13s R=%u W=%u P=%u tiles=%.0f whole=%u units=%u best %.3f ms  variant pairs/s %.4e  executed word-pairs/s %.3e (%.1f%% of the and+bcnt ceiling 2.62e13)\n",
-             three?"three-product":"four-product",R,W,P,tiles,first_split,w.n_units,best,tiles*64*64/best*1e3,exec/best*1e3,exec/best*1e3/2.6214e13*100);
+             three?"three-product":"four-product",R,W,P,tiles,tb.first_split,w.n_units,best,tiles*64*64/best*1e3,exec/best*1e3,exec/best*1e3/2.6214e13*100);
     }
     return bad_total!=0;
   }
@@ -179,15 +180,12 @@ int main(int argc,char**argv){
     double wordops = tiles*128*128*W;
     for(int mode=0; mode<3; ++mode){     // 0 grid, 1 list row-major, 2 list patch order, 3.. timing probes
       if(only_mode>=0 && mode!=only_mode) continue;
-      std::vector<uint32_t> list; twk::CountWork w{};
-      if(mode){ list=make_list(R/128,diag,mode>=2); CK(hipMemcpy(dl,list.data(),list.size()*4,hipMemcpyHostToDevice));
-        w.rows=d; w.W=W; w.rowA0=0; w.rowB0=0; w.tiles=dl; w.C=C; w.ldc=R; w.ticket=tick; first_split=twk::build_count_units((uint32_t)list.size(),W/twk::KC,P,min_chunks,units,getenv("SHAREDIV")?atoi(getenv("SHAREDIV")):8,getenv("TAILROUNDS")?atoi(getenv("TAILROUNDS")):8); twk::fill_unit_tiles(units,list.data()); CK(hipMemcpy(du,units.data(),units.size()*16,hipMemcpyHostToDevice)); w.units=du; w.n_units=(uint32_t)units.size(); w.n_queues=1; w.queue_begin[0]=0; w.queue_begin[1]=w.n_units; }
+      const twk::CountTable tb = mode? make_table(R,W,diag,mode>=2,P,min_chunks,dt,true) : twk::CountTable();
+      const twk::CountWork w=twk::count_work(d,W,0,0,dt,tb,C,R,tick,0,nullptr);
       auto launch=[&](){
         if(!mode){ hipLaunchKernelGGL((twk::k_count_tile_t<twk::COUNT_NW>),grid,block,0,0,d,W,0u,0u,diag,C,R); return; }
         CK(hipMemsetAsync(tick,0,4,0));
-        if(first_split<list.size()) hipLaunchKernelGGL(twk::k_zero_tiles,dim3((uint32_t)list.size()-first_split),dim3(256),0,0,w.tiles,first_split,C,R);
-        if(getenv("NOSTORE")) hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW,6>),dim3(P),block,0,0,w);
-        else hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW>),dim3(P),block,0,0,w);
+        CK(twk::enqueue_count(0,w,tb,P,128u,nullptr,getenv("NOSTORE")? twk::k_count_list_t<twk::COUNT_NW,6> : twk::k_count_list_t<twk::COUNT_NW>));
       };
       static const char* names[]={"grid","list","list/patch"};
       CK(hipMemset(C,0xff,(size_t)R*R*4));
@@ -196,7 +194,7 @@ int main(int argc,char**argv){
       float best=1e30f;
       for(int i=0;i<reps;++i){ CK(hipEventRecord(e0)); launch(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms,e0,e1)); if(ms<best)best=ms; }
       printf("%-10s diag=%d R=%u W=%u P=%u tiles=%.0f whole=%u units=%u best %.3f ms  word-pairs/s %.3e  VALU lane-ops/s %.3e (%.1f%% of 7.86e13; %.1f%% of the and+bcnt ceiling 2.62e13)\n",
-             names[mode],diag,R,W,P,tiles,mode?first_split:0u,mode?w.n_units:0u,best,wordops/best*1e3,2*wordops/best*1e3,2*wordops/best*1e3/7.864e13*100,wordops/best*1e3/2.6214e13*100);
+             names[mode],diag,R,W,P,tiles,mode?tb.first_split:0u,mode?w.n_units:0u,best,wordops/best*1e3,2*wordops/best*1e3,2*wordops/best*1e3/7.864e13*100,wordops/best*1e3/2.6214e13*100);
     }
   }
   return bad_total!=0;

@@ -60,37 +60,33 @@ int main(int argc, char** argv) {
 		for (uint32_t k = 0; k < AC; ++k) { lists[(size_t)v * stride + k] = cur[k]; rows[(size_t)v * W + cur[k] / 32] |= 1u << (cur[k] % 32); }
 		lists[(size_t)v * stride + AC] = 0xFFFFFFFFu;
 	}
-	uint32_t *d_lists, *d_rows, *d_out, *d_C, *d_tiles, *tick; twk::CountUnit* d_units;
+	uint32_t *d_lists, *d_rows, *d_out, *d_C, *d_table, *tick;
 	CK(hipMalloc(&d_lists, lists.size() * 4)); CK(hipMalloc(&d_rows, rows.size() * 4));
 	CK(hipMalloc(&d_out, (size_t)M * M * 4)); CK(hipMalloc(&d_C, (size_t)M * M * 4)); CK(hipMalloc(&tick, 32));
 	CK(hipMemcpy(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
 	CK(hipMemcpy(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
 	CK(hipMemset(d_out, 0, (size_t)M * M * 4)); CK(hipMemset(d_C, 0, (size_t)M * M * 4));
-	// dense: the tiles on and above the diagonal, whole-K units, 512 persistent blocks (as the engine launches it)
-	std::vector<uint32_t> tl; const uint32_t g = M / 128;
-	for (uint32_t y = 0; y < g; ++y) for (uint32_t x = y; x < g; ++x) tl.push_back(y << 16 | x);
-	std::vector<twk::CountUnit> units;
-	const uint32_t first_split = twk::build_count_units((uint32_t)tl.size(), W / twk::KC, 512, 8, units);
-	twk::fill_unit_tiles(units, tl.data());
-	CK(hipMalloc(&d_tiles, tl.size() * 4)); CK(hipMalloc(&d_units, units.size() * sizeof(twk::CountUnit)));
-	CK(hipMemcpy(d_tiles, tl.data(), tl.size() * 4, hipMemcpyHostToDevice));
-	CK(hipMemcpy(d_units, units.data(), units.size() * sizeof(twk::CountUnit), hipMemcpyHostToDevice));
-	twk::CountWork w{}; w.rows = d_rows; w.W = W; w.tiles = d_tiles; w.units = d_units; w.n_units = (uint32_t)units.size(); w.C = d_C; w.ldc = M;
-	w.ticket = tick; w.n_queues = 1; w.queue_begin[0] = 0; w.queue_begin[1] = w.n_units;
+	// dense: the tiles on and above the diagonal row by row, 512 persistent blocks (the engine's table: ld_count_table.h)
+	twk::CountSettings cs; cs.patch_rows = 1; cs.patch_cols = M / 128;
+	const twk_hip_tile_desc t{0, M, 0, M, 1, 0, 0, 0};
+	const twk::CountTable tb = twk::build_count_table(t, 1, true, nullptr, W / twk::KC, cs);
+	std::vector<uint32_t> image(tb.words());
+	tb.pack(image.data());
+	CK(hipMalloc(&d_table, image.size() * 4)); CK(hipMemcpy(d_table, image.data(), image.size() * 4, hipMemcpyHostToDevice));
+	const twk::CountWork w = twk::count_work(d_rows, W, 0, 0, d_table, tb, d_C, M, tick, 0, nullptr);
 	hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
 	auto time_it = [&](auto&& launch) { float best = 1e30f; for (int r = 0; r <= reps; ++r) { CK(hipEventRecord(e0)); launch(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1)); if (r && ms < best) best = ms; } return best; };
 	const float ms_list = time_it([&] { hipLaunchKernelGGL(k_list_pairs, dim3((M + 255) / 256, M), dim3(256), 0, 0, d_lists, stride, AC, M, d_out); });
 	const float ms_dense = time_it([&] {
 		CK(hipMemsetAsync(tick, 0, 32, 0));
-		if (first_split < tl.size()) hipLaunchKernelGGL(twk::k_zero_tiles, dim3((uint32_t)tl.size() - first_split), dim3(256), 0, 0, w.tiles, first_split, d_C, M);
-		hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW>), dim3(std::min<uint32_t>(512, w.n_units)), dim3(twk::COUNT_THREADS), 0, 0, w);
+		CK(twk::enqueue_count(0, w, tb, cs.n_blocks, (uint32_t)twk::TILE, nullptr, twk::k_count_list_t<twk::COUNT_NW>));
 	});
 	CK(hipDeviceSynchronize());
 	std::vector<uint32_t> a((size_t)M * M), b((size_t)M * M);
 	CK(hipMemcpy(a.data(), d_out, a.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(b.data(), d_C, b.size() * 4, hipMemcpyDeviceToHost));
 	size_t bad = 0; uint64_t sum = 0;
 	for (uint32_t i = 0; i < M; ++i) for (uint32_t j = i + 1; j < M; ++j) { bad += a[(size_t)i * M + j] != b[(size_t)i * M + j]; sum += a[(size_t)i * M + j]; }
-	const double pairs = (double)M * (M - 1) / 2, dense_pairs = (double)tl.size() * 128 * 128;
+	const double pairs = (double)M * (M - 1) / 2, dense_pairs = (double)tb.n_tiles() * 128 * 128;
 	printf("2N=%llu AC=%u M=%u (W=%u words/row): list merge %9.3f ms = %9.1f ps/pair (%.2e merge steps/s) | dense %9.3f ms = %9.1f ps/pair (%4.1f %% of the and+bcnt ceiling) | list/dense %7.3f | mismatches %zu, mean ALTALT %.2f\n",
 	       (unsigned long long)H, AC, M, W, ms_list, ms_list * 1e9 / pairs, pairs * 2.0 * AC / (ms_list * 1e-3), ms_dense, ms_dense * 1e9 / dense_pairs,
 	       dense_pairs * W / (ms_dense * 1e-3) / 2.6214e13 * 100, (ms_list / pairs) / (ms_dense / dense_pairs), bad, (double)sum / pairs);

@@ -69,21 +69,19 @@ int main(int argc, char** argv) {
 			rows[(size_t)v * W + k] = x;
 		}
 	}
-	uint32_t *d_lists, *d_rows, *d_out, *d_out2, *d_C, *d_tiles, *tick; twk::CountUnit* d_units;
+	uint32_t *d_lists, *d_rows, *d_out, *d_out2, *d_C, *d_table, *tick;
 	CK(hipMalloc(&d_lists, lists.size() * 4)); CK(hipMalloc(&d_rows, rows.size() * 4));
 	CK(hipMalloc(&d_out, (size_t)Mr * Mc * 4)); CK(hipMalloc(&d_out2, (size_t)Mr * Mc * 4)); CK(hipMalloc(&d_C, (size_t)Mr * Mc * 4)); CK(hipMalloc(&tick, 32));
 	CK(hipMemcpy(d_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
 	CK(hipMemcpy(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-	std::vector<uint32_t> tl;
-	for (uint32_t y = 0; y < Mr / 128; ++y) for (uint32_t x = 0; x < Mc / 128; ++x) tl.push_back(y << 16 | x);
-	std::vector<twk::CountUnit> units;
-	const uint32_t first_split = twk::build_count_units((uint32_t)tl.size(), W / twk::KC, 512, 8, units);
-	twk::fill_unit_tiles(units, tl.data());
-	CK(hipMalloc(&d_tiles, tl.size() * 4)); CK(hipMalloc(&d_units, units.size() * sizeof(twk::CountUnit)));
-	CK(hipMemcpy(d_tiles, tl.data(), tl.size() * 4, hipMemcpyHostToDevice));
-	CK(hipMemcpy(d_units, units.data(), units.size() * sizeof(twk::CountUnit), hipMemcpyHostToDevice));
-	twk::CountWork w{}; w.rows = d_rows; w.W = W; w.rowA0 = 0; w.rowB0 = Mr; w.tiles = d_tiles; w.units = d_units; w.n_units = (uint32_t)units.size(); w.C = d_C; w.ldc = Mc;
-	w.ticket = tick; w.n_queues = 1; w.queue_begin[0] = 0; w.queue_begin[1] = w.n_units;
+	// dense: the rare x common rectangle row by row, 512 persistent blocks (the engine's table: ld_count_table.h)
+	twk::CountSettings cs; cs.patch_rows = 1; cs.patch_cols = Mc / 128;
+	const twk_hip_tile_desc t{0, Mr, Mr, Mc, 0, 0, 0, 0};
+	const twk::CountTable tb = twk::build_count_table(t, 1, false, nullptr, W / twk::KC, cs);
+	std::vector<uint32_t> image(tb.words());
+	tb.pack(image.data());
+	CK(hipMalloc(&d_table, image.size() * 4)); CK(hipMemcpy(d_table, image.data(), image.size() * 4, hipMemcpyHostToDevice));
+	const twk::CountWork w = twk::count_work(d_rows, W, 0, Mr, d_table, tb, d_C, Mc, tick, 0, nullptr);
 	hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
 	auto time_it = [&](auto&& launch) { float best = 1e30f; for (int r = 0; r <= reps; ++r) { CK(hipEventRecord(e0)); launch(); CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); float ms; CK(hipEventElapsedTime(&ms, e0, e1)); if (r && ms < best) best = ms; } return best; };
 	const uint32_t* d_common = d_rows + (size_t)Mr * W;
@@ -91,8 +89,7 @@ int main(int argc, char** argv) {
 	const float ms_pairs = time_it([&] { hipLaunchKernelGGL(k_probe_pairs, dim3((Mc + 255) / 256, Mr), dim3(256), 0, 0, d_lists, stride, AC, d_common, W, Mc, d_out2); });
 	const float ms_dense = time_it([&] {
 		CK(hipMemsetAsync(tick, 0, 32, 0));
-		if (first_split < tl.size()) hipLaunchKernelGGL(twk::k_zero_tiles, dim3((uint32_t)tl.size() - first_split), dim3(256), 0, 0, w.tiles, first_split, d_C, Mc);
-		hipLaunchKernelGGL((twk::k_count_list_t<twk::COUNT_NW>), dim3(std::min<uint32_t>(512, w.n_units)), dim3(twk::COUNT_THREADS), 0, 0, w);
+		CK(twk::enqueue_count(0, w, tb, cs.n_blocks, (uint32_t)twk::TILE, nullptr, twk::k_count_list_t<twk::COUNT_NW>));
 	});
 	CK(hipDeviceSynchronize());
 	std::vector<uint32_t> a((size_t)Mr * Mc), a2((size_t)Mr * Mc), b((size_t)Mr * Mc);

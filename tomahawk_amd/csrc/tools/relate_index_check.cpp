@@ -162,8 +162,6 @@ void check_case(uint32_t N, uint32_t M, bool missing, const char* name, uint32_t
 			CHECK(rows[rl_row(0, plane, P) * W + rl_words_live(L) - 1] == w, "last partial word of plane %u", plane);
 		}
 	}
-	const uint32_t lh = rl_last_halves(L);
-	if (lh) CHECK(2 * lh >= rl_words_live(L) - (W - RL_KC) && lh <= 12, "last_halves %u for %u live words of %u", lh, rl_words_live(L), W);
 
 	// the epilogue over a square call: one diagonal super-tile (N <= the super-tile's edge here), only the tiles on or above the diagonal hold values
 	const uint32_t rows_pad = (N * P + RL_TILE - 1) / RL_TILE * RL_TILE, ldc = rows_pad;
