@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -122,6 +122,14 @@ count-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/count_table_check.cpp -o build/count_table_check
 	./build/count_table_check tests/golden/count_tables.json
+
+# The two-product form's host side (csrc/tools/two_check.cpp): its screen (csrc/hip/ld_two_screen.h) over every small genotype table, and the
+# work table of a launch with one plane row per row variant and two per column variant against a naive restatement and the recorded order of
+# tests/golden/count_tables_two.json: host code only, under AddressSanitizer and UBSan
+two-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/two_check.cpp -o build/two_check
+	./build/two_check tests/golden/count_tables_two.json
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -264,7 +264,16 @@ int twk_hip_ld_tile(twk_hip_ctx* ctx, int mode, const twk_hip_tile_desc* tile,
  * records of one sink call are in (idxA, idxB) order (sorted on the device), the
  * pieces of a launch follow each other in that order, and a piece stays valid
  * until the sink returns.  *n_pairs / *n_records (may be NULL)
- * receive totals for this shard. */
+ * receive totals for this shard.
+ * The order of the launches is the engine's.  TWK_HIP_MODE_UNPHASED over the whole triangle,
+ * without a window, on planes without missing genotypes, with rows too long for the
+ * fused form, an r2 cut-off above 1e-6, option "three" = 1 and tile_variants = 0 walks
+ * the variants in order of minor allele count (a second, sorted copy of the planes; if it
+ * cannot be allocated the call walks the file order): the launches over the rows with few
+ * hom-alt carriers then contract two products a pair instead of three (option "two",
+ * DESIGN 3.1b).  Every pair is still contracted - no band, no carrier lists - and part /
+ * n_parts shard the sorted triangle, the same for every rank; the records are those of the
+ * file-order walk, idxA < idxB in file order as always. */
 typedef int (*twk_hip_record_sink)(void* user, const twk_hip_record* recs, uint64_t n);
 int twk_hip_ld_all(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
                    uint32_t part, uint32_t n_parts, uint32_t tile_variants,
@@ -559,6 +568,16 @@ int twk_hip_plan_region(const twk_hip_plan_env* env, const twk_hip_variant_meta*
                         uint32_t tile_variants, int32_t window, uint32_t l_window,
                         twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                         uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi);
+/* The same for the two-product walk of an unscreened UnphasedMath call (screen = 0, planes_per_variant = 2, a triangle): het /
+ * hom = het and hom-alt carriers per position of the index space, which is in order of minor allele count; two_margin: what the square
+ * root of the screen's bound is shrunk to when the planner asks which rows can take two products (0: the engine's 0.95).  *two_end
+ * (may be NULL): the row, a multiple of 128, the triangle is cut at - no launch straddles it, launches in front of it may take two
+ * products.  het == hom == NULL: twk_hip_plan_region. */
+int twk_hip_plan_region_two(const twk_hip_plan_env* env, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                            uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                            uint32_t tile_variants, int32_t window, uint32_t l_window,
+                            twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                            uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end);
 
 /* Fisher's exact test on n caller-supplied 2x2 tables (tables[4*i + {0,1,2,3}] = n11, n12, n21, n22), two-sided P
  * into p_two_sided[i]: kt_fisher_exact (lib/fisher_math.cpp:231-267) as the pair math calls it
@@ -631,6 +650,13 @@ typedef struct {
 	double   finish_ms;           /* (ABI 5) the calling thread's wall time between a launch's last kernel and the hand-over of its
 	                                 records: device sort, copy to the host, the sink (launches the delivery thread takes: up to
 	                                 their copy aside on the device) - summed over the launches                              */
+	uint64_t two_launches;        /* Appended behind the ABI 5 layout, and TWK_HIP_ABI_VERSION stays 5: twk_hip_timing_get writes sizeof(twk_hip_timing) of THIS
+	                                 header, so a caller compiled against an older one must be rebuilt - the version check does not catch it
+	                                 (nothing but this library's own binding and host code, built with it, reads the struct).
+	                                 Count launches that ran the two-product form: HH and HQ of the row variants' H planes
+	                                 against the column variants' H and Q rows.  Their row_pairs are the plane-row pairs they really
+	                                 contracted - one row x two rows per variant pair - and they are no part of three_launches /
+	                                 three_row_pairs                                                                          */
 } twk_hip_timing;
 /* Progress of twk_hip_ld_all / twk_hip_ld_region: `cb` runs on the calling thread after every tile
  * with the variant pairs finished so far in the current call and the tile counts.  Replaces the
@@ -652,7 +678,8 @@ typedef struct {
 	uint64_t candidates;          /* fused / three-product launches: pairs that passed the screen              */
 	uint32_t words_per_row;
 	uint32_t kind;                /* 0 four products -> matrix, 1 three products -> matrix, 2 fused PhasedMath,
-	                                 3 fused UnphasedMath four products, 4 fused UnphasedMath three products   */
+	                                 3 fused UnphasedMath four products, 4 fused UnphasedMath three products,
+	                                 5 two products -> matrix (row variants' H planes x column variants' H, Q) */
 	uint32_t outlier;             /* != 0: flagged by the watch                                                */
 	uint32_t _pad;
 } twk_hip_launch_stat;

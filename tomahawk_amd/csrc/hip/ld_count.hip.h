@@ -452,6 +452,8 @@ __device__ __forceinline__ void contract3_slot(uint32_t (&acc)[8][4], uint32_t a
 struct CountWork {
 	const uint32_t* rows; uint32_t W;      // plane rows, row pitch in words (multiple of KC)
 	uint32_t rowA0, rowB0;                 // first plane row of the super-tile's row / column axis
+	uint32_t stepA;                        // row r of the row axis is plane row stepA * (rowA0 + r).  1: consecutive rows; 2: every other one - the H planes
+	                                       // of unphased variants, the two-product form's row operand (ld_two_screen.h; rowA0 is then a variant)
 	const uint32_t* tiles;                 // [n_tiles]: (tile row << 16) | tile column, within the super-tile
 	const CountUnit* units;                // [n_units], in the order they are handed out
 	uint32_t n_units;
@@ -624,8 +626,9 @@ __device__ __forceinline__ void count_list_body(const CountWork& w, const Epilog
 			offB = (uint32_t)(LDS_TILE_BYTES + (wc * 8 * TB + lj_) * (KC * 4) + ((lj_ >> 1) << 4));
 		}
 		// DMA source offsets: lane's row within an 8-row segment and its (swizzled) 16-byte slot, see stage_rows_s
-		voff_even = (li_ * w.W + ((lj_ ^ (li_ >> 1)) << 2)) << 2;
-		voff_odd  = (li_ * w.W + ((lj_ ^ (li_ >> 1) ^ 4u) << 2)) << 2;
+		const uint32_t pitch = __builtin_amdgcn_readfirstlane(wave) >= NW / 2 ? w.W : w.W * w.stepA;      // (of the rows this wave stages: st_pitch below)
+		voff_even = (li_ * pitch + ((lj_ ^ (li_ >> 1)) << 2)) << 2;
+		voff_odd  = (li_ * pitch + ((lj_ ^ (li_ >> 1) ^ 4u) << 2)) << 2;
 	};
 	lane_offsets(false);
 	constexpr int ODD = PAIRED ? 0 : 4;          // what the slot index of an odd t / u is XORed with (see the offA table)
@@ -638,13 +641,15 @@ __device__ __forceinline__ void count_list_body(const CountWork& w, const Epilog
 	const int st_seg0 = (wave_u % (NW / 2)) * NSEG;
 	const uint32_t lds_base = (uint32_t)(uintptr_t)(lptr_t*)lds;
 	const uint32_t st_lds = lds_base + (st_isB ? (uint32_t)LDS_TILE_BYTES : 0u);
-	// first plane row this wave stages for a tile: the A rows (first half of the waves) or the B rows
+	// first row this wave stages for a tile, in rows of its pitch: the A rows (first half of the waves; every stepA-th plane row from rowA0 on, so
+	// rows of stepA * W words) or the B rows
+	const size_t st_pitch = st_isB ? (size_t)w.W : (size_t)w.W * w.stepA;
 	auto stage_row0 = [&](uint32_t yx) -> uint32_t {       // (yx: wave-uniform, lives in an SGPR)
 		return st_isB ? w.rowB0 + (yx & 0xFFFFu) * TILE : w.rowA0 + (yx >> 16) * TILE;
 	};
 
 	uint32_t st_row0 = stage_row0(tile_yx);
-	stage_rows_s(w.rows, w.W, st_row0, c, st_lds, st_seg0, NSEG, voff_even, voff_odd);
+	stage_rows_s(w.rows, st_pitch, st_row0, c, st_lds, st_seg0, NSEG, voff_even, voff_odd);
 	uint32_t seg_c0 = c;
 	__shared__ uint32_t window_words[NW][8];
 	constexpr bool QUEUED = Epilogue::QUEUED;
@@ -701,7 +706,7 @@ __device__ __forceinline__ void count_list_body(const CountWork& w, const Epilog
 		}
 		// (issued here, in front of the chunk's LDS reads; behind the first or the third half-slot's contraction it is neither faster nor
 		// slower - 18.31 / 18.31 / 18.26 ms on the 1 M-sample microbenchmark, round 5)
-		if (more && (EXPERIMENT != 8 || n_c == 0 || n_c + 1 >= n_end)) stage_rows_s(w.rows, w.W, st_row0, n_c, st_lds + (buf ^ 1) * (2 * LDS_TILE_BYTES), st_seg0, NSEG, voff_even, voff_odd);      // (8: the dev tool's timing WITHOUT the operand staging)
+		if (more && (EXPERIMENT != 8 || n_c == 0 || n_c + 1 >= n_end)) stage_rows_s(w.rows, st_pitch, st_row0, n_c, st_lds + (buf ^ 1) * (2 * LDS_TILE_BYTES), st_seg0, NSEG, voff_even, voff_odd);      // (8: the dev tool's timing WITHOUT the operand staging)
 		// The chunk in 16 half-slots of 8 bytes per row.  The 12 LDS reads of half-slot h + 1 (8 A rows,
 		// TB B rows, ds_read_b64) are issued before the contraction of half-slot h, into the other
 		// register set, so the contraction never waits for LDS except at the first half-slot of a chunk.
@@ -1310,10 +1315,11 @@ constexpr int COUNT_THREADS = COUNT_NW * 64;
 
 // The parameter block of a launch over table tb, whose packed image (CountTable::pack) lies at d_table on the device.  ticket: tb.n_queues
 // words, zeroed by the caller before the launch; last_halves: count_last_halves of the rows, or 0; clocks: CountWork::clocks, may be null.
+// stepA: CountWork::stepA - rowA0 is then counted in rows of stepA plane rows, and the table was built with PA = P / stepA (ld_count_table.h).
 inline CountWork count_work(const uint32_t* rows, uint32_t W, uint32_t rowA0, uint32_t rowB0, const uint32_t* d_table, const CountTable& tb,
-                            uint32_t* C, uint32_t ldc, uint32_t* ticket, uint32_t last_halves, unsigned long long* clocks) {
+                            uint32_t* C, uint32_t ldc, uint32_t* ticket, uint32_t last_halves, unsigned long long* clocks, uint32_t stepA = 1) {
 	CountWork w{};
-	w.rows = rows; w.W = W; w.rowA0 = rowA0; w.rowB0 = rowB0;
+	w.rows = rows; w.W = W; w.rowA0 = rowA0; w.rowB0 = rowB0; w.stepA = stepA ? stepA : 1;
 	w.tiles = d_table;
 	w.units = reinterpret_cast<const CountUnit*>(d_table + tb.units_at()); w.n_units = tb.n_units();
 	w.C = C; w.ldc = ldc;

@@ -83,9 +83,12 @@ struct ColRange { const uint32_t* lo = nullptr; const uint32_t* hi = nullptr; ui
                   uint32_t probe_zone = 0; };          // <= list_zone: every other pair of a row below it is decided by probing the column's row with the row's carriers (k_probe_screen)
 
 struct Geometry { uint32_t rowsA, rowsB, gx, gy, ldc; };
-inline Geometry tile_geometry(int P, const twk_hip_tile_desc& t) {
+// PA: plane rows a variant takes on the row axis when that differs from the column axis' P (0: the same).  The two-product form of
+// UnphasedMath's contraction (ld_two_screen.h) stages one plane row - the H plane - per row variant against the H and Q rows of the
+// column variants: PA = 1, P = 2, a tile of 128 row variants x 64 column variants.
+inline Geometry tile_geometry(int P, const twk_hip_tile_desc& t, int PA = 0) {
 	Geometry g;
-	g.rowsA = round_up(t.nA * P, TILE); g.rowsB = round_up(t.nB * P, TILE);
+	g.rowsA = round_up(t.nA * (PA ? PA : P), TILE); g.rowsB = round_up(t.nB * P, TILE);
 	g.gy = g.rowsA / TILE; g.gx = g.rowsB / TILE; g.ldc = g.rowsB;
 	return g;
 }
@@ -94,14 +97,17 @@ inline Geometry tile_geometry(int P, const twk_hip_tile_desc& t) {
 // on or above the diagonal (diag), and in window mode only those some row of the tile can reach.
 // Order: 8 x 8 patches of tiles, patch by patch - the blocks pull consecutive tickets, so the ~P tiles in
 // flight at any time are a few neighbouring patches (shared row / column tiles meet in L2 and the MALL).
+// PA (0: P): plane rows per variant on the row axis (tile_geometry).  A tile row then starts at variant by * TILE / PA, and a tile of the
+// diagonal super-tile is wanted when its last column variant lies behind that one: from column tile by * P / PA on.
 inline void build_tile_list(const twk_hip_tile_desc& t, int P, const Geometry& g, bool diag, const ColRange* cr,
-                     std::vector<uint32_t>& out, std::vector<uint32_t>* patch_end = nullptr, uint32_t PR = 8, uint32_t PC = 8) {
+                     std::vector<uint32_t>& out, std::vector<uint32_t>* patch_end = nullptr, uint32_t PR = 8, uint32_t PC = 8, int PA_ = 0) {
+	const int PA = PA_ ? PA_ : P;
 	std::vector<uint32_t> x0(g.gy, 0), x1(g.gy, g.gx);
 	for (uint32_t by = 0; by < g.gy; ++by) {
-		if (diag) x0[by] = by;
+		if (diag) x0[by] = std::min<uint32_t>((uint32_t)((uint64_t)by * P / PA), g.gx);
 		if (cr && cr->lo) {
-			const uint32_t v0 = t.rowA0 + (by * TILE) / P;
-			const uint32_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + P - 1) / P);   // exclusive
+			const uint32_t v0 = t.rowA0 + (by * TILE) / PA;
+			const uint32_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + PA - 1) / PA);   // exclusive
 			if (v0 >= v1) { x1[by] = x0[by]; continue; }
 			const uint64_t c_lo = (uint64_t)cr->b0 + cr->lo[v0 - cr->a0], c_hi = (uint64_t)cr->b0 + cr->hi[v1 - 1 - cr->a0];   // variants [c_lo, c_hi)
 			const uint64_t lo = std::max<uint64_t>(c_lo, t.rowB0), hi = std::min<uint64_t>(c_hi, (uint64_t)t.rowB0 + t.nB);
@@ -111,7 +117,7 @@ inline void build_tile_list(const twk_hip_tile_desc& t, int P, const Geometry& g
 			if (x1[by] < x0[by]) x1[by] = x0[by];
 		}
 		if (cr && cr->list_zone) {      // a row of tiles that lies wholly inside the list zone starts at the zone's last column tile
-			const uint64_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + P - 1) / P);
+			const uint64_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + PA - 1) / PA);
 			if (v1 <= cr->probe_zone) x1[by] = x0[by];                    // every pair of these rows is a list merge or a probe
 			else if (v1 <= cr->list_zone && cr->list_zone > t.rowB0) {
 				x0[by] = std::max<uint32_t>(x0[by], (uint32_t)((((uint64_t)cr->list_zone - t.rowB0) * P) / TILE));
@@ -181,10 +187,11 @@ struct CountTable {
 // The table for the P-plane rows of tile t (diag: only the tiles on or above the diagonal; cr: window mode's column ranges and zones, or
 // null) over rows of nchunks K chunks.  One queue in the order of build_count_units, or - the measurement hook "xcd_queues" on rows of at
 // least 128 chunks - the patches dealt round robin to one queue per XCD; within a queue patch after patch, each K segment by K segment.
-inline CountTable build_count_table(const twk_hip_tile_desc& t, int P, bool diag, const ColRange* cr, uint32_t nchunks, const CountSettings& s) {
+// PA (0: P): plane rows per variant on the row axis, see tile_geometry.
+inline CountTable build_count_table(const twk_hip_tile_desc& t, int P, bool diag, const ColRange* cr, uint32_t nchunks, const CountSettings& s, int PA = 0) {
 	CountTable tb;
-	tb.g = tile_geometry(P, t);
-	build_tile_list(t, P, tb.g, diag, cr, tb.tiles, &tb.patch_end, s.patch_rows, s.patch_cols);
+	tb.g = tile_geometry(P, t, PA);
+	build_tile_list(t, P, tb.g, diag, cr, tb.tiles, &tb.patch_end, s.patch_rows, s.patch_cols, PA);
 	const uint32_t T = tb.n_tiles();
 	const uint32_t min_chunks = s.fused ? nchunks + 1 : s.min_chunks, seg_chunks = s.fused ? 0 : s.seg_chunks;
 	if (T && !s.fused && s.xcd_queues > 1 && s.xcd_queues <= 8 && nchunks >= 128 && !tb.patch_end.empty()) {

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <vector>
 #include "../../../include/twk_hip.h"
+#include "ld_two_screen.h"
 
 namespace twk {
 
@@ -29,6 +30,9 @@ struct PlanEnv {                                    // what the planner needs to
 	bool phased_math = true;                        // (candidate entries: 3 words, else 6)
 	// per position of the region's index space (file order, or a regrouped / sorted set through `ids`)
 	const twk_hip_variant_meta* meta = nullptr; const uint32_t* ids = nullptr; const uint32_t* popc = nullptr;
+	// the two-product walk (an unscreened UnphasedMath call over the allele-count-sorted set, twk_hip.hip region_dispatch): het / hom = carriers
+	// of either kind per position of the index space; the triangle is then cut at RegionPlan::two_end (plan_two_end)
+	const uint32_t* het = nullptr; const uint32_t* hom = nullptr; double two_margin = 0.95;
 	// options
 	bool band_launch = true, band_reverse = true; long long band_work_log2 = 19, band_max_launches = 8, band_list_entries = 0;
 	const twk_hip_variant_meta& at(uint32_t i) const { return meta[ids ? ids[i] : i]; }
@@ -43,6 +47,7 @@ struct RegionPlan {
 	std::vector<twk_hip_tile_desc> mine;            // the launches, in order; the first bands.size() of them are band launches
 	std::vector<BandLaunch> bands;
 	uint64_t pairs = 0;                             // pairs the shard decides
+	uint32_t two_end = 0;                           // the two-product walk: launches over rows below it (a multiple of the tile edge) lie wholly in front of r*
 };
 
 inline uint32_t plan_round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
@@ -309,6 +314,35 @@ inline void plan_band_launches(const PlanEnv& e, const PlanGeom& g, RegionPlan& 
 	}
 }
 
+// ---- the two-product walk's cut -------------------------------------------------------------------------------------------
+// r*: the first row of the region at which the two-product screen (ld_two_screen.h), asked at the independence expectation of a pair and
+// with the square root of its bound shrunk to two_margin of it, keeps a pair with some column behind the row.  From there on a two-product
+// launch would list a large part of its pairs as candidates (in allele-count order: rows with p above ~0.17 at r2 >= 0.1), so launches
+// behind r* keep the three-product form; the rows in front of it are cut off at the A tile edge below r*, and which form their launches
+// really take is still decided by a sample of each (RegionRun::decide_three_by_samples).  The margin keeps the rows next to the edge -
+// where sampling noise decides - out: 0.95 moves the edge from p = 0.172 to 0.160 at r2 >= 0.1.
+// Every rank of a sharded run finds the same r*: it is a property of the region, asked from row 0 on whatever the shard.  Each row is asked
+// against at most 256 columns spread evenly over those behind it, the last one included (the predicate is no guarantee, only a guide: the
+// sample decides, and an overflowing list is redone).
+inline uint32_t plan_two_end(const PlanEnv& e, const PlanGeom& g) {
+	if (!e.het || !e.hom || !g.triangle || g.nA == 0) return 0;
+	const double two_n = 2.0 * (double)e.n_samples, cut = e.minR2 * (1.0 - 1e-6);
+	uint32_t r = 0;
+	for (; r < g.nA; ++r) {
+		const uint32_t first = r + 1, n_behind = g.nB > first ? g.nB - first : 0;
+		if (!n_behind) continue;
+		const uint32_t n_ask = std::min<uint32_t>(n_behind, 256);
+		bool kept = false;
+		for (uint32_t k = 0; k < n_ask && !kept; ++k) {
+			const uint32_t j = first + (uint32_t)(((uint64_t)(k + 1) * n_behind) / n_ask) - 1;
+			const ScreenMargins m{e.het[g.a0 + r], e.hom[g.a0 + r], e.het[g.b0 + j], e.hom[g.b0 + j]};
+			kept = screen2_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin);
+		}
+		if (kept) break;
+	}
+	return r / PLAN_TILE * PLAN_TILE;
+}
+
 // The whole plan of a region call.
 inline void plan_region(const PlanEnv& e, const PlanGeom& g, RegionPlan& p) {
 	p = RegionPlan();
@@ -318,7 +352,12 @@ inline void plan_region(const PlanEnv& e, const PlanGeom& g, RegionPlan& p) {
 	plan_shard(g, p);
 	p.S = plan_tile_edge(e, g, p);
 	if (!g.tile_variants && e.band_launch && p.r1 > p.r0 && e.fused) plan_band_launches(e, g, p);
-	if (p.bands.empty()) plan_matrix_tiles(e, g, p, p.r0, p.r1, p.mine);
+	if (e.het && !p.windowed && p.bands.empty()) p.two_end = plan_two_end(e, g);
+	if (p.bands.empty()) {       // (the two-product walk: no launch straddles two_end)
+		const uint32_t cut = std::min(std::max(p.two_end, p.r0), p.r1);
+		plan_matrix_tiles(e, g, p, p.r0, cut, p.mine);
+		plan_matrix_tiles(e, g, p, cut, p.r1, p.mine);
+	}
 	if (e.screen) p.pairs = band_pairs_before(p.r1, g.nA, g.nB, true) - band_pairs_before(p.r0, g.nA, g.nB, true);   // every pair of the band is decided
 	else if (p.windowed) p.pairs = p.cum[p.r1] - p.cum[p.r0];       // pairs inside the window: the ones the math evaluates
 	else p.pairs = band_pairs_before(p.r1, g.nA, g.nB, g.triangle != 0) - band_pairs_before(p.r0, g.nA, g.nB, g.triangle != 0);

@@ -1,6 +1,7 @@
 // The three-product form of UnphasedMath's contraction (ld_count.hip.h: contract3_half, StoreCounts3, ScreenCountsUnphased<TB, true>)
 // leaves (HH, S) per variant pair.  This header holds what follows it:
-//   k_screen3_pairs     the r2 screen over an (HH, S) count matrix (long rows, where tiles are split along K)
+//   k_screen3_pairs     the r2 screen over an (HH, S) count matrix (long rows, where tiles are split along K), or over the (HH, HQ) matrix
+//                       of the two-product form (k_screen2_pairs; rows whose hom-alt carriers are few: ld_two_screen.h)
 //   k_recount_unphased  the four products HH, HQ, QH, QQ of the pairs that passed, counted afresh from their plane rows
 // The candidates then go through k_ld_stats_list_unphased (ld_math.hip.h) like those of the four-product fused form.
 // Reference shape: UnphasedMath reads the 3 x 3 table only through n11, the double hets and the margins before its cubic
@@ -8,6 +9,7 @@
 #pragma once
 #include "ld_count.hip.h"
 #include "ld_math.hip.h"
+#include "ld_two_screen.h"
 
 namespace twk {
 
@@ -16,9 +18,12 @@ namespace twk {
 // ScreenCountsUnphased (same doubles, same order - but for the column variant's dosage, which is read here as the integer it is and
 // there from the prefilter's float term: the same number below 2^24 alleles); a pair that passes becomes a candidate (A, B, HH, S, -, -) in the
 // launch's list, appended with one atomic per block.  Structural tests as in the fused epilogue (the list math checks them again).
+// TWO: the matrix is that of a two-product launch (k_count_list_t over the row variants' H planes against the column variants' H and Q
+// rows: (HH, HQ) where the three-product form leaves (HH, S), same layout), the test screen2_keeps - the same doubles with S_lo = HQ and
+// S_hi = HQ + qA + min(qA, qB) in S's place (ld_two_screen.h) - and a candidate is (A, B, HH, HQ, -, -).
 constexpr int SCREEN3_THREADS = 256;
-__global__ __launch_bounds__(SCREEN3_THREADS)
-void k_screen3_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) {
+template <bool TWO>
+__device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) {
 	const ScreenWork& s = *sp;
 	const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
 	const uint32_t vA = s.a0 + i, vB = s.b0 + j;
@@ -35,15 +40,8 @@ void k_screen3_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 	if (ok) {
 		const uint2 hs = *reinterpret_cast<const uint2*>(C + (size_t)i * ldc + 2 * j);
 		hh = hs.x; s_sum = hs.y;
-		const uint32_t hA = s.rowpop[2 * vA], qA = s.rowpop[2 * vA + 1], hB = s.rowpop[2 * vB], qB = s.rowpop[2 * vB + 1];
-		const double T2n = s.two_n, eps = 1e-5 * (T2n * T2n);
-		const double da = (double)(hA + 2u * qA), ra = T2n - da, fA = s.cut * (da * ra);
-		const double db = (double)(hB + 2u * qB), rb = T2n - db, fB = db * rb;
-		const double n11 = (ra - db) + (double)s_sum;
-		const double e_lo = (n11 * T2n - ra * rb) - eps;
-		const double e_hi = ((n11 + (double)hh) * T2n - ra * rb) + eps;
-		const double bound = fA * fB;
-		ok = !(e_lo * e_lo < bound && e_hi * e_hi < bound);
+		const ScreenMargins m{s.rowpop[2 * vA], s.rowpop[2 * vA + 1], s.rowpop[2 * vB], s.rowpop[2 * vB + 1]};
+		ok = TWO ? screen2_keeps(m, hh, s_sum, s.two_n, s.cut) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
 	}
 	__shared__ uint32_t wave_n[SCREEN3_THREADS / 64];
 	__shared__ unsigned long long block_base;
@@ -63,10 +61,15 @@ void k_screen3_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 		slot += (unsigned long long)__popcll(ballot & ((1ull << lane) - 1));
 		if (slot < s.cap) {
 			uint32_t* e = s.cand + slot * 6;
-			e[0] = vA; e[1] = vB; e[2] = hh; e[3] = 0; e[4] = 0; e[5] = s_sum;
+			e[0] = vA; e[1] = vB; e[2] = hh; e[3] = TWO ? s_sum : 0; e[4] = 0; e[5] = TWO ? 0 : s_sum;
 		}
 	}
 }
+
+__global__ __launch_bounds__(SCREEN3_THREADS)
+void k_screen3_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) { screen_pairs_body<false>(sp, pp, C, ldc); }
+__global__ __launch_bounds__(SCREEN3_THREADS)
+void k_screen2_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) { screen_pairs_body<true>(sp, pp, C, ldc); }
 
 // ---- the candidates' four products --------------------------------------------------------------------------------------
 // The three-product forms hand over (A, B, HH, S); UnphasedMath needs HH, HQ, QH and QQ.  LANES lanes per candidate (64 for
@@ -75,11 +78,12 @@ void k_screen3_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 // the four-product form would have made it.  The few candidates of a default run (r2 >= 0.1: pairs in real LD) cost nothing
 // next to the contraction; the host stops using the three-product forms when a launch's candidates are too many for that to
 // hold (twk_hip.hip: three_ok).  The recount also proves the contraction, always: a candidate whose (HH, S) disagree with its
-// own four products is counted in *mismatches, and the host fails the call on it.
+// own four products is counted in *mismatches, and the host fails the call on it.  two != 0: the candidates are a two-product launch's,
+// (A, B, HH, HQ) - the proof is then that both products equal their recount.
 template <int LANES>
 __global__ __launch_bounds__(256)
 void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t W_live, uint32_t* __restrict__ cand,
-                        const unsigned long long* __restrict__ n_cand, unsigned long long cap, unsigned long long* __restrict__ mismatches) {
+                        const unsigned long long* __restrict__ n_cand, unsigned long long cap, unsigned long long* __restrict__ mismatches, int two) {
 	static_assert(LANES == 64 || LANES == 16, "a wave or a DPP row per candidate");
 	const unsigned long long n = *n_cand;
 	if (n > cap) return;                                    // the list overflowed: the host redoes the launch with four products, nothing of this one is kept
@@ -108,7 +112,7 @@ void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t 
 			hh += __shfl_xor(hh, d, LANES); hq += __shfl_xor(hq, d, LANES); qh += __shfl_xor(qh, d, LANES); qq += __shfl_xor(qq, d, LANES);
 		}
 		if (lane == 0) {
-			if (mismatches && (e[2] != hh || e[5] != qh + hq + 2u * qq)) atomicAdd(mismatches, 1ull);      // the contraction's (HH, S) against the recount
+			if (mismatches && (e[2] != hh || (two ? e[3] != hq : e[5] != qh + hq + 2u * qq))) atomicAdd(mismatches, 1ull);      // the contraction's (HH, S) - (HH, HQ) - against the recount
 			e[2] = hh; e[3] = hq; e[4] = qh; e[5] = qq;
 		}
 	}

@@ -89,9 +89,12 @@ struct PlaneSet {
 	// list_max carriers of their minor allele - positions [0, n_list), n_list a multiple of the tile edge
 	DevBuf<uint32_t> lists, list_mac, list_flip;
 	uint32_t  n_list = 0, list_max = 0;
+	bool      lists_done = false;  // the lists have been built (or found not worth keeping): ensure_lists
 	uint32_t  n_probe = 0;         // <= n_list: the leading variants whose lists are short enough for probing to beat the dense pair (ld_list.hip.h)
 	// fused screen kernels: the prefilter's per-variant terms at the cut-off of the run that built them (ScreenWork::terms, k_screen_terms)
 	DevBuf<float4> terms; double terms_cut = -1.0;
+	// the two-product walk's planner (ld_plan.h plan_two_end): het and hom-alt carriers per position, copied from rowpop when first asked for
+	std::vector<uint32_t> h_het, h_hom;
 };
 
 // Plane sets a context can hold: one per PlaneKind in file order, plus the masked unphased planes
@@ -110,7 +113,8 @@ inline int set_kind(int set) {
 enum { MODE_INT_AUTO_CLEAN = 0x10,     // phased math on the plain planes; pairs without missing data only
        MODE_INT_GROUPED    = 0x11,     // unphased math on the regrouped planes; every pair of the tile
        MODE_INT_SORTED_P   = 0x12,     // phased math on the allele-count-sorted planes (variants without missing data)
-       MODE_INT_SORTED_U   = 0x13 };   // unphased math on the allele-count-sorted planes
+       MODE_INT_SORTED_U   = 0x13,     // unphased math on the allele-count-sorted planes
+       MODE_INT_SORTED_U_ALL = 0x14 }; // ... without the r2 band, the list zone and the probe zone: every pair is contracted (the two-product walk)
 
 constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // Launches of a region call in flight.  Three, not two: the survivors of launch t are sorted on the copy stream, where they
@@ -129,6 +133,7 @@ struct LaunchForm {
 	bool unphased = false;         // plain unphased planes with UnphasedMath: the list math, if there is one, is the unphased kernel
 	bool three = false;            // the three-product form (HH + S; the candidates' four products are recounted): fused, or ...
 	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
+	bool two = false;              // the two-product form (HH + HQ through a count matrix, S bounded from the margins): never fused, never with `three`
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
 	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
@@ -200,6 +205,7 @@ namespace {
 #define TWK_HIP_OPTIONS(X) \
 	X(fused, 1, 0, 2, false, "fused count -> r2 screen kernel (no count matrix; DESIGN 3.2a): 0 never, 1 rows of <= 128 K chunks, 2 always") \
 	X(three, 1, 0, 2, false, "UnphasedMath on planes without missing genotypes, r2 cut-off > 1e-6: contract three products a pair (HH and S = QH + HQ + 2 QQ: all the screen reads) and recount the four products of the pairs that pass (DESIGN 3.1a); 0: four products for every pair; 2: keep to three whatever a launch's candidate density (1 samples every launch first)") \
+	X(two, 1, 0, 2, false, "UnphasedMath, whole triangle without a window, rows too long to fuse, three = 1 and no tile edge given: walk the allele-count-sorted planes and contract two products a pair (HH and HQ of the row variant's H plane; S bounded from the margins) in the launches whose rows have few hom-alt carriers (DESIGN 3.1b); 0: never (the call walks the file order); 2: in every launch of that walk, whatever the predicate and the samples say") \
 	X(count_min_chunks, 8, 1, 1 << 20, false, "shortest K range a tile of the count kernel is split into at the end of a launch (test hook: 1 splits short rows too)") \
 	X(patch_rows, 8, 1, 4096, false, "rows of a patch of tiles in the count kernel's work order (DESIGN 3.1, profiles/r03_patch_pmc.txt)") \
 	X(patch_cols, 8, 1, 4096, false, "... and its columns") \
@@ -277,6 +283,8 @@ struct twk_hip_ctx {
 	DevBuf<StatsParams> d_list_stats;             // parameter block of the list pass's math kernel (device copy)
 	bool fused_ok = true;           // cleared for the rest of a call when a fused tile's candidate list overflowed
 	bool three_ok = true;           // cleared for the rest of a call when a three-product launch had too many candidates for the recount to stay cheap
+	bool two_ok = true;             // cleared for the rest of a call when a two-product launch's candidate list overflowed
+	bool two_now = false;           // the launch being enqueued lies in front of the two-product walk's cut and its sample was poor in candidates (RegionRun)
 	bool sampling = false;          // the launch being enqueued is a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name
 	                                // (k_count3_list_t<.., 1>), so that a kernel trace's statistics of the real launches are not diluted by half-millisecond ones
 	bool sorted_keeps_no_lists[2] = {false, false};      // [phased, unphased]: the allele-count-sorted set was built once for a run below the band's cut-off and
@@ -393,6 +401,61 @@ int ensure_popcounts(twk_hip_ctx* c) {
 	return TWK_HIP_OK;
 }
 
+// The carrier lists of a sorted set (ld_list.hip.h), built when a run first wants them (ensure_lists: the r2-screen runs; the two-product walk
+// over the same planes uses none and does not pay for them).
+int build_lists(twk_hip_ctx* c, int set) {
+	PlaneSet& ps = c->planes[set];
+	{ const int rc = ensure_popcounts(c); if (rc) return rc; }
+	// Carrier lists for the head of the set (ld_list.hip.h): worth it where a dense pair costs more than a merge of
+	// two lists, i.e. for long rows only.  list_max = (phased row words) / 128 carriers for PhasedMath (the measured
+	// break-even is ~W / 150 merge steps per side, profiles/r03_t2_list_vs_dense.txt) and twice that for UnphasedMath (a
+	// dense unphased pair costs twice a phased one, a merge over samples about the same), and not below 32 - rows
+	// shorter than 4096 words (N < 65,536) keep no lists.  Option "lists" = 0: never; 2: always, with at least 8 carriers
+	// (test hook); "list_max" = n: the limit itself (measurement hook).
+	const int lists_env = (int)c->opt.lists;
+	uint32_t lmax = c->Wp / (set == PS_SORTED_U ? 64 : 128);      // measured optimum at N = 1 M: 488 / 976 carriers (profiles/r03_list_max_sweep.txt)
+	if (lists_env == 2) lmax = std::max<uint32_t>(lmax, 8);
+	if (c->opt.list_max >= 8) lmax = (uint32_t)c->opt.list_max;      // measurement hook (<= 60000: the unphased merge counts in 16 bits)
+	if (lists_env != 0 && (c->Wp / 128 >= 32 || lists_env == 2)) {
+		const uint64_t T2 = 2ull * c->N;
+		uint32_t n = 0;                                  // variants of the missing-free head with a minor allele count <= lmax
+		while (n < ps.n_front) {
+			const uint64_t ac = std::min<uint64_t>(c->h_popc[ps.h_ids[n]], T2);
+			if (std::min(ac, T2 - ac) > lmax) break;
+			++n;
+		}
+		n = n / TILE * TILE;                             // whole tiles: a tile is either intersected or contracted
+		if (n >= 2 * TILE) {
+			ps.n_list = n; ps.list_max = lmax;
+			// Probing (k_probe_screen) beats the dense pair up to ~W / 114 carriers in isolation (csrc/tools/probe_vs_dense.hip) and
+			// up to about half that in a whole run, where the rows that reach beyond the zone are the ones with the longest lists and
+			// the columns are thousands of 250 KB rows (1 M x 50,000: 10-11 ps per carrier against 5; with every list probing, the
+			// default-cut-off run was 23 ms slower than without probes): PhasedMath probes lists of up to W / 256 carriers,
+			// UnphasedMath - two reads per listed sample, a dense pair of twice the cost - of up to W / 160 entries.
+			const uint32_t pmax = set == PS_SORTED_U ? std::max<uint32_t>(c->Wp / 160, 8) : std::max<uint32_t>(c->Wp / 256, 8);
+			uint32_t np = 0;
+			while (np < n) {
+				const uint64_t ac = std::min<uint64_t>(c->h_popc[ps.h_ids[np]], T2);
+				if (std::min(ac, T2 - ac) > pmax) break;
+				++np;
+			}
+			ps.n_probe = np / TILE * TILE;
+			HIPCHK(c, ps.lists.reserve((size_t)n * (lmax + 1), (size_t)n * (lmax + 1), nullptr));
+			HIPCHK(c, ps.list_mac.reserve(n, n, nullptr));
+			HIPCHK(c, ps.list_flip.reserve(n, n, nullptr));
+			if (set == PS_SORTED_P)
+				hipLaunchKernelGGL(k_build_lists, dim3((n + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, (uint64_t)T2,
+				                   (const uint32_t*)ps.rowpop, n, lmax + 1, ps.lists, ps.list_mac, ps.list_flip);
+			else
+				hipLaunchKernelGGL(k_build_lists_unphased, dim3((n + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, c->N,
+				                   (const uint32_t*)ps.rowpop, n, lmax + 1, ps.lists, ps.list_mac, ps.list_flip);
+			HIPCHK(c, hipGetLastError());
+		}
+	}
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	return TWK_HIP_OK;
+}
+
 int build_planes(twk_hip_ctx* c, int set) {
 	PlaneSet& ps = c->planes[set];
 	const int kind = set_kind(set);
@@ -400,7 +463,8 @@ int build_planes(twk_hip_ctx* c, int set) {
 	const bool wide = (kind == PK_PHASED || kind == PK_PHASED_MASKED);
 	ps.W = wide ? c->Wp : c->Wu;
 	ps.W_live = wide ? (uint32_t)((2ull * c->N + 31) / 32) : (c->N + 31) / 32;
-	ps.rows_alloc = round_up(c->M * P, TILE) + TILE;
+	// (the sorted unphased set: a tile more - a two-product launch stages every other row of 128 variants, 256 plane rows from its last tile's first)
+	ps.rows_alloc = round_up(c->M * P, TILE) + (set == PS_SORTED_U ? 2 * TILE : TILE);
 	if ((kind == PK_PHASED_MASKED || kind == PK_UNPHASED_MASKED) && !c->rawmask) return TWK_HIP_E_STATE;
 	const bool sorted = set == PS_SORTED_P || set == PS_SORTED_U;
 	if (sorted) {
@@ -454,54 +518,6 @@ int build_planes(twk_hip_ctx* c, int set) {
 	const uint32_t live_rows = c->M * P;
 	hipLaunchKernelGGL(k_row_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, ps.rows, ps.W, live_rows, ps.rowpop);
 	HIPCHK(c, hipGetLastError());
-	if (set == PS_SORTED_P || set == PS_SORTED_U) {
-		// Carrier lists for the head of the set (ld_list.hip.h): worth it where a dense pair costs more than a merge of
-		// two lists, i.e. for long rows only.  list_max = (phased row words) / 128 carriers for PhasedMath (the measured
-		// break-even is ~W / 150 merge steps per side, profiles/r03_t2_list_vs_dense.txt) and twice that for UnphasedMath (a
-		// dense unphased pair costs twice a phased one, a merge over samples about the same), and not below 32 - rows
-		// shorter than 4096 words (N < 65,536) keep no lists.  Option "lists" = 0: never; 2: always, with at least 8 carriers
-		// (test hook); "list_max" = n: the limit itself (measurement hook).
-		const int lists_env = (int)c->opt.lists;
-		uint32_t lmax = c->Wp / (set == PS_SORTED_U ? 64 : 128);      // measured optimum at N = 1 M: 488 / 976 carriers (profiles/r03_list_max_sweep.txt)
-		if (lists_env == 2) lmax = std::max<uint32_t>(lmax, 8);
-		if (c->opt.list_max >= 8) lmax = (uint32_t)c->opt.list_max;      // measurement hook (<= 60000: the unphased merge counts in 16 bits)
-		if (lists_env != 0 && (c->Wp / 128 >= 32 || lists_env == 2)) {
-			const uint64_t T2 = 2ull * c->N;
-			uint32_t n = 0;                                  // variants of the missing-free head with a minor allele count <= lmax
-			while (n < ps.n_front) {
-				const uint64_t ac = std::min<uint64_t>(c->h_popc[ps.h_ids[n]], T2);
-				if (std::min(ac, T2 - ac) > lmax) break;
-				++n;
-			}
-			n = n / TILE * TILE;                             // whole tiles: a tile is either intersected or contracted
-			if (n >= 2 * TILE) {
-				ps.n_list = n; ps.list_max = lmax;
-				// Probing (k_probe_screen) beats the dense pair up to ~W / 114 carriers in isolation (csrc/tools/probe_vs_dense.hip) and
-				// up to about half that in a whole run, where the rows that reach beyond the zone are the ones with the longest lists and
-				// the columns are thousands of 250 KB rows (1 M x 50,000: 10-11 ps per carrier against 5; with every list probing, the
-				// default-cut-off run was 23 ms slower than without probes): PhasedMath probes lists of up to W / 256 carriers,
-				// UnphasedMath - two reads per listed sample, a dense pair of twice the cost - of up to W / 160 entries.
-				const uint32_t pmax = set == PS_SORTED_U ? std::max<uint32_t>(c->Wp / 160, 8) : std::max<uint32_t>(c->Wp / 256, 8);
-				uint32_t np = 0;
-				while (np < n) {
-					const uint64_t ac = std::min<uint64_t>(c->h_popc[ps.h_ids[np]], T2);
-					if (std::min(ac, T2 - ac) > pmax) break;
-					++np;
-				}
-				ps.n_probe = np / TILE * TILE;
-				HIPCHK(c, ps.lists.reserve((size_t)n * (lmax + 1), (size_t)n * (lmax + 1), nullptr));
-				HIPCHK(c, ps.list_mac.reserve(n, n, nullptr));
-				HIPCHK(c, ps.list_flip.reserve(n, n, nullptr));
-				if (set == PS_SORTED_P)
-					hipLaunchKernelGGL(k_build_lists, dim3((n + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, (uint64_t)T2,
-					                   (const uint32_t*)ps.rowpop, n, lmax + 1, ps.lists, ps.list_mac, ps.list_flip);
-				else
-					hipLaunchKernelGGL(k_build_lists_unphased, dim3((n + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, c->N,
-					                   (const uint32_t*)ps.rowpop, n, lmax + 1, ps.lists, ps.list_mac, ps.list_flip);
-				HIPCHK(c, hipGetLastError());
-			}
-		}
-	}
 	HIPCHK(c, hipStreamSynchronize(c->s_compute));
 	ps.built = true;
 	return TWK_HIP_OK;
@@ -512,6 +528,16 @@ int ensure_planes(twk_hip_ctx* c, int set) {
 	const int rc = build_planes(c, set);
 	if (rc) c->planes[set] = PlaneSet();
 	return rc;
+}
+// ... with its carrier lists, where the set keeps any (sorted sets only)
+int ensure_lists(twk_hip_ctx* c, int set) {
+	int rc = ensure_planes(c, set); if (rc) return rc;
+	PlaneSet& ps = c->planes[set];
+	if (ps.lists_done || !(set == PS_SORTED_P || set == PS_SORTED_U)) return TWK_HIP_OK;
+	rc = build_lists(c, set);
+	if (rc) { c->planes[set] = PlaneSet(); return rc; }
+	ps.lists_done = true;
+	return TWK_HIP_OK;
 }
 
 // C_words words of count matrix / candidate list and `capacity` survivors for the slot's next launch.
@@ -556,12 +582,16 @@ constexpr uint32_t FUSED_MAX_CHUNKS = 128;
 struct FusedArgs { ScreenWork screen; StatsParams stats; int unphased; };
 int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, const ColRange* cr, const LaunchForm& form, const FusedArgs* fa) {
 	const hipEvent_t e0 = which ? s.ev_c0b : s.ev_c0, e1 = which ? s.ev_c1b : s.ev_c1;
-	const bool fuse = form.fused, three = form.three, with_args = fuse || three;       // with_args: the parameter blocks go to the device behind the unit table
+	const bool fuse = form.fused, three = form.three, two = form.two, with_args = fuse || three || two;       // with_args: the parameter blocks go to the device behind the unit table
 	if (with_args != (fa != nullptr)) return TWK_HIP_E_STATE;
 	const PlaneSet& ps = c->planes[set];
 	const int P = planes_per_variant(set_kind(set));
-	const Geometry g = tile_geometry(P, t);
-	if ((uint64_t)t.rowA0 * P + g.rowsA > ps.rows_alloc || (uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
+	// two products: one plane row - the H plane, every other row - per row variant, so tiles of 128 row variants x 64 column variants
+	const int PA = two ? 1 : P;
+	const uint32_t stepA = (uint32_t)(P / PA);
+	if (two && (P != 2 || fuse || which != 0)) return TWK_HIP_E_STATE;
+	const Geometry g = tile_geometry(P, t, PA);
+	if (((uint64_t)t.rowA0 * PA + g.rowsA) * stepA > ps.rows_alloc || (uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
 	if (g.gx > 0xFFFFu || g.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
 	const bool diag = t.diag && t.rowA0 == t.rowB0;
 	// the tiles and the units of work (ld_count_table.h; "count_min_chunks" is a test hook: 1 splits short rows too; "seg" 0: whole tiles and
@@ -569,7 +599,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	CountSettings cs;
 	cs.patch_rows = (uint32_t)c->opt.patch_rows; cs.patch_cols = (uint32_t)c->opt.patch_cols; cs.min_chunks = (uint32_t)c->opt.count_min_chunks;
 	cs.seg_chunks = (uint32_t)c->opt.seg; cs.xcd_queues = (uint32_t)c->opt.xcd_queues; cs.n_blocks = c->resident_blocks; cs.fused = fuse;
-	const CountTable tb = build_count_table(t, P, diag, cr, ps.W / KC, cs);
+	const CountTable tb = build_count_table(t, P, diag, cr, ps.W / KC, cs, PA);
 	const size_t T = tb.n_tiles();
 	const size_t words_units = tb.words(), fa_words = (sizeof(FusedArgs) + 15) / 16 * 4;
 	const size_t words = words_units + (with_args ? fa_words : 0);               // [tiles | pad | units | FusedArgs] for a fused or three-product launch
@@ -583,8 +613,8 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	HIPCHK(c, hipEventRecord(e0, c->s_compute));
 	if (T) {
 		const uint32_t last_halves = c->opt.skip_pad ? count_last_halves(ps.W_live, ps.W) : 0;      // (measurement hook: 0 = contract the zero padding too)
-		const CountWork w = count_work(ps.rows, ps.W, t.rowA0 * P, t.rowB0 * P, s.d_tiles[which], tb, s.C, g.ldc,
-		                               c->tickets + ((&s - c->slot) * 2 + which) * 8, last_halves, s.n_out + 4);
+		const CountWork w = count_work(ps.rows, ps.W, t.rowA0 * PA, t.rowB0 * P, s.d_tiles[which], tb, s.C, g.ldc,
+		                               c->tickets + ((&s - c->slot) * 2 + which) * 8, last_halves, s.n_out + 4, stepA);
 		HIPCHK(c, hipMemsetAsync(w.ticket, 0, 8 * 4, c->s_compute));
 		const FusedArgs* d_fa = reinterpret_cast<const FusedArgs*>(s.d_tiles[which] + words_units);
 		if (with_args) { s.l.d_stats_dev = const_cast<StatsParams*>(&d_fa->stats); s.l.d_screen_dev = &d_fa->screen; }
@@ -594,7 +624,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		if (fuse && three) k_list = c->sampling ? k_count3_screen_unphased_t<COUNT_NW, 1> : k_count3_screen_unphased_t<COUNT_NW>;
 		else if (three) k_matrix = c->sampling ? k_count3_list_t<COUNT_NW, 1> : k_count3_list_t<COUNT_NW>;
 		else if (fuse) k_list = form.unphased ? k_count_screen_unphased_t<COUNT_NW> : k_count_screen_t<COUNT_NW>;
-		else k_matrix = k_count_list_t<COUNT_NW>;
+		else k_matrix = (two && c->sampling) ? k_count_list_t<COUNT_NW, 1> : k_count_list_t<COUNT_NW>;
 		const uint32_t tile_rows = three ? TILE / 2 : TILE;
 		if (k_list) HIPCHK(c, enqueue_count(c->s_compute, w, tb, cs.n_blocks, tile_rows, nullptr, k_list, &d_fa->screen));
 		else HIPCHK(c, enqueue_count(c->s_compute, w, tb, cs.n_blocks, tile_rows, nullptr, k_matrix));
@@ -645,7 +675,7 @@ TilePlan plan_for(const twk_hip_ctx* c, int mode) {
 	case MODE_INT_AUTO_CLEAN:   p.select1 = 1; break;
 	case MODE_INT_GROUPED:      p.set1 = PS_GROUPED; p.phased1 = false; break;
 	case MODE_INT_SORTED_P:     p.set1 = PS_SORTED_P; break;
-	case MODE_INT_SORTED_U:     p.set1 = PS_SORTED_U; p.phased1 = false; break;
+	case MODE_INT_SORTED_U: case MODE_INT_SORTED_U_ALL: p.set1 = PS_SORTED_U; p.phased1 = false; break;
 	default:                    // AUTO on one tile: plain phased (pairs without missing) then masked unphased
 		if (c->any_missing) { p.select1 = 1; p.set2 = PK_UNPHASED_MASKED; }
 		break;
@@ -699,8 +729,9 @@ LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters
 	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
 	if (!screen) return lf;
 	lf.three = lf.unphased && c->three_ok && c->opt.three != 0;
-	if (c->opt.fused == 0 || ensure_planes(c, pl.set1) != TWK_HIP_OK) return lf;
-	lf.fused = c->opt.fused == 2 || c->planes[pl.set1].W / KC <= FUSED_MAX_CHUNKS;
+	if (c->opt.fused != 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK) lf.fused = c->opt.fused == 2 || c->planes[pl.set1].W / KC <= FUSED_MAX_CHUNKS;
+	// two products: only where the walk's owner says so for this launch (two_now: RegionRun, on the sorted set), and only in place of three through a matrix
+	if (lf.three && !lf.fused && !lf.two_pass && pl.set1 == PS_SORTED_U && c->two_now && c->two_ok && c->opt.two != 0) { lf.two = true; lf.three = false; }
 	return lf;
 }
 // Would a launch of this mode run the fused count -> screen form and nothing else (one pass)?  For the callers that size a launch by it.
@@ -716,10 +747,10 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	const PlaneSet& ps = c->planes[set];
 	if (ps.W_live <= 1024)
 		hipLaunchKernelGGL(k_recount_unphased<16>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0);
 	else
 		hipLaunchKernelGGL(k_recount_unphased<64>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0);
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -854,7 +885,10 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
-	rc = ensure_slot(c, s, list_words ? list_words : (size_t)g.rowsA * g.rowsB, capacity); if (rc) return rc;
+	// (two products: the (HH, HQ) matrix has a row per row variant, whole tiles of 128 of them, and the candidate list lies behind it)
+	const size_t c_two_words = form.two ? (size_t)round_up(t.nA, TILE) * g.rowsB : 0;
+	const size_t two_list_words = form.two ? 6 * (size_t)std::max<unsigned long long>((unsigned long long)t.nA * t.nB / 128, 4096) : 0;
+	rc = ensure_slot(c, s, list_words ? list_words : std::max((size_t)g.rowsA * g.rowsB, c_two_words + two_list_words), capacity); if (rc) return rc;
 	tl("slot buffers");
 	Launch& l = begin_launch(s, kind1, f.minP);
 	l.form = form;
@@ -864,15 +898,15 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	// slot's count buffer and the candidate list the room behind it - at most 1/128 of the tile's pairs: a candidate's recount streams its four
 	// rows once more, ~25 pairs' worth of contraction, so a launch with more candidates than that is cheaper in the four-product form
 	// (overflow -> three_ok = false -> redone).
-	if (form.three_plain()) {
-		const size_t c2_words = (size_t)(g.rowsA / 2) * g.rowsB;
+	if (form.three_plain() || form.two) {
+		const size_t c2_words = form.two ? c_two_words : (size_t)(g.rowsA / 2) * g.rowsB;
 		const unsigned long long room = s.C.capacity() > c2_words ? (s.C.capacity() - c2_words) / 6 : 0;
 		const unsigned long long pairs = (unsigned long long)t.nA * t.nB;
 		l.cand = s.C + c2_words;
 		l.cand_cap = std::min<unsigned long long>(room, form.keep_three ? room : std::max<unsigned long long>(pairs / 128, 4096));
 	}
 	FusedArgs fa{};
-	const bool with_args = form.fused || form.three;      // the launch carries the screen's and the list math's parameter blocks
+	const bool with_args = form.fused || form.three || form.two;      // the launch carries the screen's and the list math's parameter blocks
 	if (with_args) {
 		PlaneSet& ps = c->planes[kind1];
 		fa.unphased = form.unphased ? 1 : 0;
@@ -913,12 +947,17 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	}
 	if (with_args) {
 		if (l.d_stats_dev) {      // (else: no tiles, no launch, no candidates)
+			if (form.two) {                // (HH, HQ) matrix -> screen with S bounded from the margins -> candidates -> their four products -> the list math
+				hipLaunchKernelGGL(k_screen2_pairs, dim3((t.nB + SCREEN3_THREADS - 1) / SCREEN3_THREADS, t.nA), dim3(SCREEN3_THREADS), 0, c->s_compute, l.d_screen_dev,
+				                   (const StatsParams*)l.d_stats_dev, (const uint32_t*)s.C, g.ldc);
+				HIPCHK(c, hipGetLastError());
+			}
 			if (form.three_plain()) {      // (HH, S) matrix -> screen -> candidates -> their four products -> the list math
 				hipLaunchKernelGGL(k_screen3_pairs, dim3((t.nB + SCREEN3_THREADS - 1) / SCREEN3_THREADS, t.nA), dim3(SCREEN3_THREADS), 0, c->s_compute, l.d_screen_dev,
 				                   (const StatsParams*)l.d_stats_dev, (const uint32_t*)s.C, g.ldc);
 				HIPCHK(c, hipGetLastError());
 			}
-			if (form.three) { rc = launch_recount(c, kind1, s); if (rc) return rc; }
+			if (form.three || form.two) { rc = launch_recount(c, kind1, s); if (rc) return rc; }
 			rc = launch_list_math(c, s, l.d_stats_dev); if (rc) return rc;
 		}
 	} else if (form.reduces()) {
@@ -1037,10 +1076,10 @@ int ensure_device_keep(twk_hip_ctx* c, unsigned long long n_more) {
 constexpr size_t LAUNCH_RING = 4096;
 void watch_launch(twk_hip_ctx* c, const Slot& s, float ms, const twk_hip_tile_desc& t) {
 	twk_hip_launch_stat st{};
-	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three) ? s.h_n_out[2] : 0;
+	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three || s.l.form.two) ? s.h_n_out[2] : 0;
 	st.shader_mhz = s.h_n_out[5] ? (double)s.h_n_out[4] / (double)s.h_n_out[5] * 100.0 : 0.0;
 	st.words_per_row = c->planes[s.l.plane_set].W_live;
-	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.three_plain() ? 1u : 0u);
+	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.two ? 5u : s.l.form.three_plain() ? 1u : 0u);
 	unsigned long long lo = ~0ull, hi = 0;
 	for (int x = 0; x < 8; ++x) if (s.h_n_out[8 + x]) { lo = std::min(lo, s.h_n_out[8 + x]); hi = std::max(hi, s.h_n_out[8 + x]); }
 	st.xcd_finish_spread_us = hi ? (double)(hi - lo) / 100.0 : 0.0;
@@ -1183,6 +1222,13 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		// launch's rectangle is mostly outside the window)
 		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) c->three_ok = false;
 	}
+	if (s.l.form.two) {
+		c->timing.two_launches += 1; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
+		if (s.h_n_out[3]) {      // as above: the recount is the contraction's proof
+			snprintf(c->err, sizeof(c->err), "two-product contraction: %llu candidates whose (HH, HQ) differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], t.rowA0, t.nA, t.rowB0, t.nB);
+			return TWK_HIP_E_DEVICE;
+		}
+	}
 	float ms_all = 0;
 	if (s.l.form.two_pass) {
 		HIPCHK(c, hipEventElapsedTime(&ms, s.ev_c0b, s.ev_c1b));
@@ -1203,7 +1249,7 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		snprintf(c->err, sizeof(c->err), "%llu candidates: beyond the survivor buffers of a band launch (tile rows %u+%u, cols %u+%u)", s.h_n_out[2], t.rowA0, t.nA, t.rowB0, t.nB);
 		return TWK_HIP_E_OVERFLOW;
 	}
-	if ((s.l.form.fused || s.l.is_list || s.l.form.three_plain()) && s.h_n_out[2] > s.l.cand_cap) {       // more candidates than the list holds
+	if ((s.l.form.fused || s.l.is_list || s.l.form.three_plain() || s.l.form.two) && s.h_n_out[2] > s.l.cand_cap) {       // more candidates than the list holds
 		s.l.cand_overflow = true;
 		snprintf(c->err, sizeof(c->err), "%llu candidates for a list of %llu (tile rows %u+%u, cols %u+%u)", s.h_n_out[2], s.l.cand_cap, t.rowA0, t.nA, t.rowB0, t.nB);
 		return TWK_HIP_E_OVERFLOW;
@@ -1848,6 +1894,10 @@ struct RegionRun {
 	unsigned long long cap_default = 1ull << 24;
 	uint64_t tot_pairs = 0, tot_recs = 0;
 	std::vector<char> want_three;             // per launch: the three-product form may be used (decide_three_by_samples)
+	std::vector<char> want_two;               // ... and the two-product form (the two-product walk: launches in front of plan.two_end whose sample was poor in candidates)
+	bool two_walk() const { return mode == MODE_INT_SORTED_U_ALL; }
+	// (option two = 2, the test hook: every launch of the walk, whatever the predicate says)
+	bool two_eligible(const twk_hip_tile_desc& t) const { return two_walk() && c->opt.two != 0 && (c->opt.two == 2 || t.rowA0 + t.nA <= g.a0 + plan.two_end); }
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, twk_hip_record_sink sink_, void* user_)
 		: c(c_), mode(mode_), f(f_), g(g_), env(e_), plan(p_), to{!c_->device_sink, sink_ ? sink_ : discard_records, user_} {}
@@ -1938,17 +1988,25 @@ struct RegionRun {
 	// pipeline starts: a sub-tile of at most 384 x 384 variants from its middle through the same kernels (half a millisecond), three
 	// products if at most 1 pair in 256 of the sample is a candidate (1 in 128 for fused launches, whose recount reads short rows from L2).  (Regions of more than 64 launches sample every k-th one; the others
 	// follow their nearest sampled neighbour.)
+	// The two-product walk: a launch in front of the planner's cut is sampled in the two-product form first - two products if at most 1 pair
+	// in 256 of that sample is a candidate - and only if that fails in the three-product form (those launches are sampled one by one: the
+	// neighbour across the cut says nothing).
 	int decide_three_by_samples() {
 		const std::vector<twk_hip_tile_desc>& mine = plan.mine;
 		const size_t n = mine.size();
-		want_three.assign(n, 1);
+		want_three.assign(n, 1); want_two.assign(n, 0);
+		if (c->opt.two == 2) for (size_t i = 0; i < n; ++i) want_two[i] = two_eligible(mine[i]) ? 1 : 0;
 		if (mine.empty() || c->opt.three != 1 || !launch_form(c, plan_for(c, mode), *f).three) return TWK_HIP_OK;      // (no launch of this region would take the form)
 		// (fused launches - short rows - are sampled as well: they keep their candidates whatever their number, but past ~1.2 % of the pairs
 		// the recount costs more than the third product saves: 2,504 samples, -u -w 1000000, 2.9 % candidates: 27.4 + 30.3 ms of count kernel and
 		// math with three products in the first of two launches, 30 + 21 ms with four in both)
 		const unsigned long long dense_one_in = env.fused ? 128 : 256;
-		const size_t step = (n + 63) / 64;
-		for (size_t i0 = 0; i0 < n; i0 += step) {
+		// (the launches in front of the two-product walk's cut lead the plan and are sampled one by one; the others every k-th as ever)
+		size_t n_front = 0;
+		if (c->opt.two == 1) while (n_front < n && two_eligible(mine[n_front])) ++n_front;
+		const size_t step_behind = std::max<size_t>(1, (n - n_front + 63) / 64);
+		for (size_t i0 = 0, step = 1; i0 < n; i0 += step) {
+			step = i0 < n_front ? 1 : step_behind;
 			const size_t pick = std::min(n - 1, i0 + step / 2);
 			const twk_hip_tile_desc& t0 = mine[pick];
 			twk_hip_tile_desc st = t0;
@@ -1956,19 +2014,31 @@ struct RegionRun {
 			st.rowA0 = row_c; st.nA = h;
 			if (t0.diag && t0.rowA0 == t0.rowB0) { st.rowB0 = row_c; st.nB = std::min<uint32_t>(h, t0.rowB0 + t0.nB - row_c); st.diag = 1; }
 			else { const uint32_t wv = std::min<uint32_t>(384, t0.nB); st.rowB0 = t0.rowB0 + (t0.nB - wv) / 2; st.nB = wv; st.diag = 0; }
-			const twk_hip_timing keep_timing = c->timing;
-			const size_t keep_ring = c->launch_ring.size(); const uint64_t keep_seen = c->launches_seen;
-			Slot& ss = c->slot[SYNC_SLOT];
-			unsigned long long nrec = 0;
-			c->sampling = true;
-			int rc = enqueue_tile(c, mode, st, *f, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
-			c->sampling = false;
-			if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
-			const unsigned long long cand = ss.h_n_out[2], sample_pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
-			c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
-			if (c->launch_ring.size() > keep_ring && c->launches_seen == keep_seen + 1 && keep_seen < LAUNCH_RING) c->launch_ring.pop_back();
-			c->launches_seen = keep_seen;
-			c->three_ok = true;                      // (a sample's own overflow decides its launch, not the call)
+			unsigned long long cand = 0;
+			const unsigned long long sample_pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
+			auto sample = [&](bool two) -> int {
+				const twk_hip_timing keep_timing = c->timing;
+				const size_t keep_ring = c->launch_ring.size(); const uint64_t keep_seen = c->launches_seen;
+				Slot& ss = c->slot[SYNC_SLOT];
+				unsigned long long nrec = 0;
+				c->sampling = true; c->two_now = two;
+				int rc = enqueue_tile(c, mode, st, *f, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
+				c->sampling = false; c->two_now = false;
+				if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
+				cand = ss.h_n_out[2];
+				c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
+				if (c->launch_ring.size() > keep_ring && c->launches_seen == keep_seen + 1 && keep_seen < LAUNCH_RING) c->launch_ring.pop_back();
+				c->launches_seen = keep_seen;
+				c->three_ok = true;                      // (a sample's own overflow decides its launch, not the call)
+				return rc;
+			};
+			if (c->opt.two == 1 && two_eligible(t0)) {
+				const int rc2 = sample(true);
+				if (rc2 != TWK_HIP_OK && rc2 != TWK_HIP_E_OVERFLOW) return rc2;
+				mark("two-product sample of launch: candidates", pick, cand);
+				if (rc2 == TWK_HIP_OK && cand * 256 <= sample_pairs) { want_two[pick] = 1; continue; }      // (three products stay wanted: what a launch falls back to)
+			}
+			const int rc = sample(false);
 			const bool dense = rc == TWK_HIP_E_OVERFLOW || (rc == TWK_HIP_OK && cand * dense_one_in > sample_pairs);
 			if (rc != TWK_HIP_OK && rc != TWK_HIP_E_OVERFLOW) return rc;
 			for (size_t i = i0; i < std::min(n, i0 + step); ++i) want_three[i] = dense ? 0 : 1;
@@ -2025,7 +2095,15 @@ struct RegionRun {
 			return rc;
 		}
 		rc = finish_tile(c, s, mine[done], &nrec, to);
-		if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow) {     // the fused / three-product form's candidate list overflowed: this tile again through C, four products
+		if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow && s.l.form.two) {
+			// a two-product launch's list overflowed: this tile again with three products (run_tile_sync goes on to four if that list overflows too), and
+			// no two-product launches for the rest of the call; nothing of the overflowed launch was kept (its recount and its list math left at once)
+			c->two_ok = false;
+			const bool three_was = c->three_ok, three_given = three_was && want_three[done] != 0;
+			c->three_ok = three_given;
+			rc = run_tile_sync(c, mode, mine[done], *f, cap_default, &nrec, to, cr());
+			c->three_ok = (three_given && !c->three_ok) ? false : three_was;       // (cleared inside: the three-product redo overflowed as well)
+		} else if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow) {     // the fused / three-product form's candidate list overflowed: this tile again through C, four products
 			c->fused_ok = false; c->three_ok = false;            // (and the tiles not yet enqueued as well)
 			rc = run_tile_sync(c, mode, mine[done], *f, cap_default, &nrec, to, cr());
 		}
@@ -2059,8 +2137,9 @@ struct RegionRun {
 				mark("enqueue launch", issued);
 				const bool three_was = c->three_ok;
 				c->three_ok = three_was && want_three[issued] != 0;       // (the launch's own sample)
+				c->two_now = want_two[issued] != 0;
 				const int r = enqueue_tile(c, mode, mine[issued], *f, c->slot[issued % PIPE_SLOTS], b ? 1 : cap_default, cr(), b ? b->list_words : 0);
-				c->three_ok = three_was;
+				c->three_ok = three_was; c->two_now = false;
 				if (r) return r;
 				mark("enqueued launch", issued);
 			}
@@ -2086,10 +2165,20 @@ struct RegionRun {
 // What the planner needs to know of the context for this mode.
 int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, PlanEnv& env) {
 	env = PlanEnv();
-	if (mode == MODE_INT_GROUPED || mode == MODE_INT_SORTED_P || mode == MODE_INT_SORTED_U) {
+	if (mode == MODE_INT_GROUPED || mode == MODE_INT_SORTED_P || mode == MODE_INT_SORTED_U || mode == MODE_INT_SORTED_U_ALL) {
 		const int set = mode == MODE_INT_GROUPED ? PS_GROUPED : mode == MODE_INT_SORTED_P ? PS_SORTED_P : PS_SORTED_U;
-		const int rc = ensure_planes(c, set); if (rc) return rc;
+		const int rc = mode == MODE_INT_SORTED_U_ALL ? ensure_planes(c, set) : ensure_lists(c, set); if (rc) return rc;      // (the two-product walk keeps no zones)
 		env.ids = c->planes[set].h_ids.data();
+	}
+	if (mode == MODE_INT_SORTED_U_ALL && c->opt.two != 0) {      // the two-product walk: the planner cuts the triangle where the rows' hom-alt carriers become too many
+		PlaneSet& ps = c->planes[PS_SORTED_U];
+		if (ps.h_het.size() != c->M) {
+			std::vector<uint32_t> pop((size_t)2 * c->M);
+			HIPCHK(c, hipMemcpy(pop.data(), ps.rowpop, pop.size() * 4, hipMemcpyDeviceToHost));
+			ps.h_het.resize(c->M); ps.h_hom.resize(c->M);
+			for (uint32_t v = 0; v < c->M; ++v) { ps.h_het[v] = pop[2 * (size_t)v]; ps.h_hom[v] = pop[2 * (size_t)v + 1]; }
+		}
+		env.het = ps.h_het.data(); env.hom = ps.h_hom.data();
 	}
 	// r2 screen (TWK_HIP_OPT_R2_SCREEN): the region is a triangle over the leading, missing-free part of an allele-count-sorted set
 	env.screen = (mode == MODE_INT_SORTED_P) ? 1 : (mode == MODE_INT_SORTED_U) ? 2 : 0;
@@ -2143,6 +2232,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
+	c->two_ok = true; c->two_now = false;
 	c->fused_ok = c->three_ok = c->reduce.kind == Reduce::none;      // a score, a prune, a clump, a matrix, a decay or an aggregate looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
@@ -2160,7 +2250,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 		bool& known_useless = c->sorted_keeps_no_lists[sset == PS_SORTED_U ? 1 : 0];      // (every region call of a multi-step run used to build and drop the set again)
 		if (f->minR2 < 1e-3 && known_useless) keep_sorted = false;
 		else if (f->minR2 < 1e-3) {
-			const int rc = ensure_planes(c, sset); if (rc) return rc;
+			const int rc = ensure_lists(c, sset); if (rc) return rc;
 			if (c->planes[sset].n_list < 2) {
 				keep_sorted = false; known_useless = true;
 				HIPCHK(c, hipDeviceSynchronize());
@@ -2168,6 +2258,19 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 			}
 		}
 		if (keep_sorted) return region_impl(c, a.stage(mode == TWK_HIP_MODE_UNPHASED ? MODE_INT_SORTED_U : MODE_INT_SORTED_P, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records));
+	}
+	// The two-product walk: an unscreened UnphasedMath call over the whole triangle walks the allele-count-sorted set as well - every
+	// pair is still contracted (no band, no list or probe zone), but the launches over the rows with few hom-alt carriers take two products a pair.
+	// Only where the tile edge is the engine's (an explicit one pins the launch geometry in file order) and option three = 1 (2: three products
+	// whatever); rows short enough to fuse, masked planes and a window keep the file order.  part / n_parts shard the sorted triangle.  A second
+	// plane set that cannot be allocated: the call runs in file order.
+	if (mode == TWK_HIP_MODE_UNPHASED && whole && !(a.window & (TWK_HIP_OPT_WINDOW | TWK_HIP_OPT_R2_SCREEN)) && !c->any_missing && c->reduce.kind == Reduce::none &&
+	    a.tile_variants == 0 && c->opt.two != 0 && c->opt.three == 1 && f->minR2 > 1e-6 && f->minR2 <= 1.0 && c->M >= 2 &&
+	    (c->opt.fused == 0 || (c->opt.fused == 1 && c->Wu / KC > FUSED_MAX_CHUNKS))) {
+		const int prc = ensure_planes(c, PS_SORTED_U);
+		if (prc == TWK_HIP_OK) return region_impl(c, a.stage(MODE_INT_SORTED_U_ALL, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records));
+		if (prc != TWK_HIP_E_NOMEM) return prc;
+		(void)hipGetLastError(); c->err[0] = 0;
 	}
 	if (!(mode == TWK_HIP_MODE_AUTO && c->any_missing && whole)) return region_impl(c, a);
 	// Default mode over the whole triangle with missing genotypes somewhere: every pair goes through
@@ -2682,6 +2785,15 @@ int twk_hip_plan_region(const twk_hip_plan_env* pe, const twk_hip_variant_meta* 
                         uint32_t tile_variants, int32_t window, uint32_t l_window,
                         twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                         uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi) {
+	return twk_hip_plan_region_two(pe, meta, popc, nullptr, nullptr, 0.0, n_variants, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window,
+	                               tiles, capacity, n_tiles, n_band_launches, row_begin, row_end, n_pairs, lo, hi, nullptr);
+}
+int twk_hip_plan_region_two(const twk_hip_plan_env* pe, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                            uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                            uint32_t tile_variants, int32_t window, uint32_t l_window,
+                            twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                            uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end) {
+	if ((het != nullptr) != (hom != nullptr)) return TWK_HIP_E_INVALID;
 	if (!pe || !meta || !n_tiles || (capacity && !tiles) || n_parts == 0 || part >= n_parts) return TWK_HIP_E_INVALID;
 	if (nA == 0 || nB == 0 || (uint64_t)a0 + nA > n_variants || (uint64_t)b0 + nB > n_variants) return TWK_HIP_E_INVALID;
 	if (triangle && (a0 != b0 || nB < nA)) return TWK_HIP_E_INVALID;
@@ -2691,6 +2803,7 @@ int twk_hip_plan_region(const twk_hip_plan_env* pe, const twk_hip_variant_meta* 
 	env.n_samples = pe->n_samples; env.Pmax = pe->planes_per_variant; env.nchunks = std::max<uint32_t>(pe->k_chunks, 1); env.resident_blocks = std::max<uint32_t>(pe->resident_blocks, 1);
 	env.screen = pe->screen; env.minR2 = pe->minR2; env.fused = pe->fused != 0; env.phased_math = pe->phased_math != 0;
 	env.meta = meta; env.ids = nullptr; env.popc = popc;
+	env.het = het; env.hom = hom; if (two_margin > 0) env.two_margin = two_margin;
 	env.band_launch = pe->band_launch != 0; env.band_reverse = pe->band_reverse != 0; env.band_work_log2 = pe->band_work_log2; env.band_max_launches = std::max<long long>(pe->band_max_launches, 1);
 	const PlanGeom g{a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window};
 	RegionPlan plan;
@@ -2700,6 +2813,7 @@ int twk_hip_plan_region(const twk_hip_plan_env* pe, const twk_hip_variant_meta* 
 	if (row_begin) *row_begin = plan.r0;
 	if (row_end) *row_end = plan.r1;
 	if (n_pairs) *n_pairs = plan.pairs;
+	if (two_end) *two_end = plan.two_end;
 	if (plan.windowed) {
 		if (lo) std::copy(plan.lo.begin(), plan.lo.end(), lo);
 		if (hi) std::copy(plan.hi.begin(), plan.hi.end(), hi);
