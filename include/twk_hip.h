@@ -40,6 +40,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_decay - LD decay - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_aggregate - the LD aggregate - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_relationship / twk_hip_relationship_last - the sample relationship matrix - are two entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_score_annot - partitioned LD scores - is an entry point more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -455,6 +456,39 @@ int twk_hip_ld_aggregate(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filt
                          int32_t stat, const uint16_t* bin_x /*[n_variants]*/, const uint16_t* bin_y /*[n_variants]*/,
                          uint32_t x_bins, uint32_t y_bins,
                          uint64_t* n, double* sum, double* sum_sq, double* min, double* max /*[x_bins * y_bins] each*/, uint64_t* n_pairs);
+
+/* Partitioned LD scores over the same slice of the pair space as twk_hip_ld_score, with the same arguments and the same pair set: what
+ * stratified LD-score regression reads, l(v, c) = the sum over v's partners w of a[w][c] * r2(v, w).  annot: HOST array of n_variants
+ * rows of ld_annot >= n_annot doubles, indexed by variant as uploaded - binary categories, real-valued ones, anything finite with
+ * |a| <= TWK_HIP_ANNOT_MAX_ABS.  A pair COUNTS exactly when twk_hip_ld_region with these arguments would report a record for it.  For
+ * each counting pair (A, B) and each category c the integer rint((R2 * a[B][c]) * 2^32) is added to (A, c) and the integer
+ * rint((R2 * a[A][c]) * 2^32) to (B, c): one double multiplication, an exact scaling, rounding to nearest with ties to even.
+ *   score       HOST array of n_variants * n_annot doubles, row v at v * n_annot, overwritten: the exact integer sum of (v, c),
+ *               converted to double once and divided by 2^32
+ *   n_partners  HOST array of n_variants entries, overwritten: twk_hip_ld_score's count
+ * An annotation of 0 (or -0.0) adds nothing; an annotation of 1 adds rint(R2 * 2^32), the quantum of twk_hip_ld_decay; variants
+ * outside the slice get 0.  THE VARIANT ITSELF IS NOT A PARTNER, as in twk_hip_ld_score: a caller that wants LDSC's convention
+ * (r2(v, v) = 1) adds a[v][c].
+ * THE SUMS ARE EXACT IN INTEGERS AND HAVE NO ORDER (ld_score_annot.hip.h, ld_annot_term.h, ld_exact_sum.h): summed in 64-bit integer
+ * atomics, converted once from 128 bits; the same bits for any tile_variants, any launch order and any repeat, and no floating-point
+ * atomic is used.  A shard (part / n_parts) returns partial arrays: n_partners adds exactly, the scores to within double rounding.
+ * filters.minP must be >= 1: Fisher's test is not run.  Always the matrix form of the contraction (TWK_HIP_OPT_R2_SCREEN is ignored, as
+ * for a score).  *n_pairs (may be NULL): pairs evaluated.  The context is left as it was.
+ * TWK_HIP_E_INVALID before any launch: minP < 1, a NULL array, n_annot == 0 or above TWK_HIP_ANNOT_MAX_CATEGORIES, ld_annot < n_annot,
+ * an annotation of any variant of the problem that is not finite or beyond TWK_HIP_ANNOT_MAX_ABS in magnitude (twk_hip_last_error
+ * names the variant and the column), and the region call's own argument errors; TWK_HIP_E_STATE before upload.  Device memory:
+ * 24 bytes per variant and category for the length of the call; TWK_HIP_E_NOMEM with the size in twk_hip_last_error when the device
+ * cannot give it.  twk_hip_timing: the kernels count as the math stage (stats_ms, stats_launches, variant_pairs).  There is NO
+ * reference counterpart. */
+#define TWK_HIP_ANNOT_MAX_CATEGORIES 256
+#define TWK_HIP_ANNOT_MAX_ABS 65536.0     /* 2^16 */
+int twk_hip_ld_score_annot(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                           uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                           uint32_t part, uint32_t n_parts, uint32_t tile_variants,
+                           int32_t window, uint32_t l_window,
+                           const double* annot, uint32_t n_annot, uint64_t ld_annot,
+                           uint64_t* n_partners /*[n_variants]*/, double* score /*[n_variants * n_annot], row v at v * n_annot*/,
+                           uint64_t* n_pairs);
 
 /* The sample relationship matrix: sample by sample instead of variant by variant - what a cohort user computes before any LD, to find
  * duplicates and relatives.  The same AND + popcount contraction with the reduced axis turned round: the genotype matrix is transposed

@@ -43,6 +43,12 @@ struct twk_ld_settings {
 	std::vector<std::string> ival_strings;
 };
 
+// What Score takes beyond twk_ld_settings.
+struct twk_score_settings {
+	std::string annot;          // the annotation file: with it the scores are partitioned, one column per category; empty: the plain score
+	bool self = false;          // add the variant's own annotation to its partitioned scores (LDSC's convention, r2(v, v) = 1)
+};
+
 // What Clump needs beyond twk_ld_settings.
 struct twk_clump_settings {
 	std::string assoc;          // the association file
@@ -104,6 +110,17 @@ public:
 	// either end, and the sum of their R2 with 17 significant digits - reduced on one GPU (twk_hip_ld_score), no record is formed.
 	// settings.minP must be 1 (the default).  `tomahawk ldscore` ends here.
 	bool Score(const twk_ld_settings& settings);
+	// ... and partitioned by the categories of score.annot, what stratified LD-score regression reads (LDSC's --l2 --annot): text, split on
+	// tabs or spaces, `##` lines ignored; the first other line is the header, contig pos name1 .. nameC (a leading '#' is allowed; columns 3
+	// and 4 named SNP and CM, as in LDSC's .annot, are skipped in every row), then one row per variant: contig name, position (1-based, as
+	// Score prints it), C numbers, finite and at most 65536 in magnitude, 1 <= C <= 256.  Every variant of the selection at a (contig,
+	// position) gets that row, variants the file does not name get zeros; the same key or name twice, a row of another length, a number that
+	// is none or an unreadable file is an error, with file and line, before the input is opened or a device touched.  Per variant v and
+	// category c the sum over v's partners w of a[w][c] * R2(v, w) is formed on one GPU (twk_hip_ld_score_annot: exact integer sums, the
+	// same bits from run to run); score.self adds a[v][c] on the host.  Writes the `##` lines of Score, then ##annotations=C, ##M= and
+	// ##M_5_50= (the categories' sums over the selection, and over its variants with a minor allele frequency above 0.05), ##self=1 with
+	// score.self, and per variant contig, position, n_partners and the C scores with 17 significant digits.
+	bool Score(const twk_ld_settings& settings, const twk_score_settings& score);
 	// Not in the reference: greedy LD pruning in file order (PLINK's --indep-pairwise).  Loads the .twk exactly as Compute does (-I intervals,
 	// -w, -p / -u, TWK_REF_COMPAT; the whole pair space: -c / -C are refused, the walk needs every pair) and writes one text line per
 	// variant of the selection, in file order, to settings.out ("-" or empty: stdout): contig, position (as Score prints them) and keep,

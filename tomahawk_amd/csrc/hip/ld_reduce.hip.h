@@ -1,7 +1,7 @@
-// What the six epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
-// ld_matrix.hip.h, ld_decay.hip.h, ld_aggregate.hip.h; launch_reduce in twk_hip.hip): the shape of a kernel and the toolkit it is built from.
+// What the seven epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
+// ld_matrix.hip.h, ld_decay.hip.h, ld_aggregate.hip.h, ld_score_annot.hip.h; launch_reduce in twk_hip.hip): the shape of a kernel and the toolkit it is built from.
 //
-// THE SHAPE.  A block is 256 lanes = 256 columns of the launch and walks a fixed number of its rows (32; clump 64) in a loop that is not
+// THE SHAPE.  A block is 256 lanes = 256 columns of the launch and walks a fixed number of its rows (32; clump 64; annot 16) in a loop that is not
 // unrolled.  A lane's pair goes through d_pair<SRC_MATRIX> (ld_math.hip.h) with the launch's StatsParams - the pair rules, the regrouped
 // sets' ids, auto_select, window and option bits are the record path's own code - in a function that is OUT OF LINE: the registers of
 // the two maths are then the callee's and are not held across the row loop (inlined, k_ld_score needs 191 VGPRs: two waves a SIMD).
@@ -18,7 +18,7 @@
 //   d_or_bits, d_block_dead
 // WHAT STAYS PER KIND.  The pair function: each returns its own small result in registers and the record stays local to the callee (a
 // shared one that returned the record would pass 104 bytes through memory), so d_stat_value is inlined INTO those out-of-line bodies.
-// The row loop: the six carry different state across rows (clump's column word, the matrix's LDS stage, score's partials).
+// The row loop: the seven carry different state across rows (clump's column word, the matrix's LDS stage, score's partials, annot's parked r2).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

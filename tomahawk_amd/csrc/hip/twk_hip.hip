@@ -11,9 +11,10 @@
 //   matrix (ld_matrix.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a dense float32 matrix (twk_hip_ld_matrix)
 //   decay (ld_decay.hip.h) cells -> r2 -> exact integer sums per distance bin, in place of the math stage (twk_hip_ld_decay)
 //   aggregate (ld_aggregate.hip.h) cells -> one statistic -> exact integer sums, counts and extremes per cell of an x-by-y landscape, likewise (twk_hip_ld_aggregate)
+//   annot (ld_score_annot.hip.h) cells -> r2 -> times the partner's annotations -> exact integer sums per (variant, category), likewise (twk_hip_ld_score_annot)
 //   relate (ld_relate.hip.h) the raw layout transposed into planes of the samples -> count -> genotype-sharing counts and one statistic per sample pair
 //                          (twk_hip_relationship: its own launches, beside the variant launch path)
-//   (score, prune, clump, matrix, decay and aggregate are the six kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
+//   (score, prune, clump, matrix, decay, aggregate and annot are the seven kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -47,6 +48,7 @@
 #include "ld_score.hip.h"
 #include "ld_decay.hip.h"
 #include "ld_aggregate.hip.h"
+#include "ld_score_annot.hip.h"
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
@@ -122,10 +124,10 @@ constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // until the host had sorted, copied and handed over launch t and come back with launch t + 2 (2,504 x 531,500, all pairs:
 // 39 launches of 13 ms took 1.25 s).  With t + 2 already queued the count kernels run back to back.
 constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
-// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay or _aggregate runs: it looks at
-// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the six kernels share).
-enum class Reduce { none, score, prune, clump, matrix, decay, aggregate };
-constexpr int N_REDUCE = (int)Reduce::aggregate + 1;
+// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate or _score_annot runs: it looks at
+// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the seven kernels share).
+enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot };
+constexpr int N_REDUCE = (int)Reduce::annot + 1;
 // The form of a launch, decided once (launch_form) and passed down: which count kernel, which math behind it.
 struct LaunchForm {
 	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
@@ -141,7 +143,7 @@ struct LaunchForm {
 // What the running call of one of them sets, for its length: ~ReduceCall puts a default-constructed one back.
 struct ReduceState {
 	Reduce kind = Reduce::none;
-	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; } map{};      // where the running kind's launches put their results (prune and clump: bits)
+	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; } map{};      // where the running kind's launches put their results (prune and clump: bits)
 	uint64_t work = 0;                            // what the call's launches used up of the room of the kind's accumulators (launch_reduce holds it to the kind's limit)
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
@@ -167,7 +169,7 @@ struct Launch {
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
-union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; };
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -797,6 +799,7 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	case Reduce::matrix:    return run_reduce_kernel(c, t, s, which, k_ld_matrix_fill, MATRIX_THREADS, MATRIX_ROWS, MatrixArgs{{p, rs.map.matrix}});
 	case Reduce::decay:     return run_reduce_kernel(c, t, s, which, k_ld_decay, DECAY_THREADS, DECAY_ROWS, DecayArgs{{p, rs.map.decay}}, decay_lds_bytes(rs.map.decay.n_bins));
 	case Reduce::aggregate: return run_reduce_kernel(c, t, s, which, k_ld_aggregate, AGG_THREADS, AGG_ROWS, AggArgs{{p, rs.map.agg}});
+	case Reduce::annot:     return run_reduce_kernel(c, t, s, which, k_ld_annot, ANNOT_THREADS, ANNOT_ROWS, AnnotArgs{{p, rs.map.annot}});      // (no work limit: ld_score_annot.hip.h)
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -2340,8 +2343,8 @@ int hold_for_call(twk_hip_ctx* c, DevBuf<T>& b, size_t items, const char* what, 
 struct ReduceCall {
 	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
 	int bad;
-	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells.  Freed behind the destructor's body, which waits for the device.
-	DevBuf<unsigned long long> d_adj, d_agg; DevBuf<float> d_matrix;
+	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums.  Freed behind the destructor's body, which waits for the device.
+	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc; DevBuf<float> d_matrix; DevBuf<double> d_annot;
 	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
 	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
 		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
@@ -2628,6 +2631,51 @@ int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uin
 			min[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MIN]) : 0.0;
 			max[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
 		}
+	}
+	return TWK_HIP_OK;
+}
+
+// Partitioned LD scores: the annotations are checked, packed to n_annot columns and uploaded, the integer accumulators of every
+// (variant, category) zeroed in front of the launches, and converted behind the last of them, a slab of variants at a time.
+int twk_hip_ld_score_annot(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                           uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                           const double* annot, uint32_t n_annot, uint64_t ld_annot, uint64_t* n_partners, double* score, uint64_t* n_pairs) {
+	const bool shape_ok = n_annot >= 1 && n_annot <= ANNOT_MAX_CATEGORIES && ld_annot >= n_annot;
+	ReduceCall call(c, Reduce::annot, f, annot && n_partners && score && shape_ok, mode, a0, nA);
+	if (call.bad) return call.bad;
+	const size_t M = c->M, C = n_annot, cells = M * C;
+	std::vector<double> packed(cells);
+	for (size_t v = 0; v < M; ++v)
+		for (size_t k = 0; k < C; ++k) {
+			const double a = annot[v * ld_annot + k];
+			if (!at_valid(a)) {
+				snprintf(c->err, sizeof(c->err), "partitioned LD scores: the annotation of variant %zu in column %zu is %g: not finite or beyond 65536 in magnitude", v, k, a);
+				return TWK_HIP_E_INVALID;
+			}
+			packed[v * C + k] = a;
+		}
+	int rc = hold_for_call(c, call.d_annot, cells, "the annotations of %u variants need %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	rc = hold_for_call(c, call.d_annot_acc, 2 * cells, "the partitioned LD scores of %u variants need %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	HIPCHK(c, c->d_score_n.reserve(M, M, nullptr));
+	// (from pageable memory: the copy has left `packed` when it returns)
+	HIPCHK(c, hipMemcpyAsync(call.d_annot, packed.data(), cells * sizeof(double), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(call.d_annot_acc, 0, 2 * cells * sizeof(unsigned long long), c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_score_n, 0, M * sizeof(unsigned long long), c->s_compute));
+	c->reduce.map.annot = AnnotMap{call.d_annot, call.d_annot_acc, c->d_score_n, n_annot};
+	call.arm(2 * cells * sizeof(unsigned long long));
+	rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
+	if (rc) return rc;
+	rc = call.download("partner counts", [&] { return hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute); });
+	if (rc) return rc;
+	const size_t slab = std::min<size_t>(cells, (size_t)1 << 20);      // 16 MiB of accumulators at a time
+	std::vector<unsigned long long> acc(2 * slab);
+	for (size_t at = 0; at < cells; at += slab) {
+		const size_t m = std::min(slab, cells - at);
+		rc = call.download("partitioned score arrays", [&] {
+			return hipMemcpyAsync(acc.data(), call.d_annot_acc + 2 * at, 2 * m * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+		});
+		if (rc) return rc;
+		for (size_t k = 0; k < m; ++k) score[at + k] = xs_sum_to_double_signed<ANNOT_SPLIT>(acc[2 * k], acc[2 * k + 1]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
 	}
 	return TWK_HIP_OK;
 }

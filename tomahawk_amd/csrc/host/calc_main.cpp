@@ -184,7 +184,8 @@ static int run_command(const Command<Own>& cmd, int argc, char** argv) {
 			switch (cmd.option ? cmd.option(c, optarg, settings, own) : declined) {
 			case took: break;
 			case failed: return 1;
-			case declined: return !fail(std::string("Unrecognized option: ") + (char)c);
+			case declined:      // (a long option without a letter - another command's --annot, --self - by its name)
+				return !fail(std::string("Unrecognized option: ") + (c > 127 ? std::string("--") + cmd.long_options[option_index].name : std::string(1, (char)c)));
 			}
 		}
 	}
@@ -212,7 +213,7 @@ static const struct option REDUCE_LONG_OPTIONS[] = {
 	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
 	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
-	{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
+	{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
 	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
 	{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
 	{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
@@ -267,11 +268,20 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static const Command<NoOptions> LDSCORE = {
+// ... and `ldscore --annot FILE [--self]`: the scores partitioned by annotation category.  Long names only, and not in
+// the usage text above: `ldscore -a`, `ldscore --assoc` and the usage itself answer as they always have (tests/golden/cli_transcript.json).
+static Took ldscore_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_score_settings& score) {
+	if (c == 1002) { score.annot = arg; return took; }
+	if (c == 1001) { score.self = true; return took; }
+	return declined;
+}
+
+static const Command<tomahawk::twk_score_settings> LDSCORE = {
 	"ldscore", "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n", ldscore_usage,
 	"i:o:t:puP:r:w:I:c:C:?", REDUCE_LONG_OPTIONS, 0, {},
-	"Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run", nullptr, nullptr,
-	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const NoOptions&) { return ld.Score(settings); }};
+	"Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run", ldscore_option,
+	[](twk_ld_settings&, tomahawk::twk_score_settings& score) { return !score.self || !score.annot.empty() || fail("--self needs an annotation file (--annot)"); },
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_score_settings& score) { return ld.Score(settings, score); }};
 
 // `tomahawk prune` (not in the reference): greedy LD pruning in file order over the records `calc` would write, decided on the GPU.
 static void prune_usage() {

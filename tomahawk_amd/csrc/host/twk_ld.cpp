@@ -18,6 +18,7 @@
 #include <iostream>
 #include <limits>
 #include <map>
+#include <set>
 #include <fstream>
 #include <regex>
 #include <sstream>
@@ -330,12 +331,14 @@ bool index_block(const uint8_t* base, size_t block_off, size_t block_len, uint32
 }  // namespace
 
 static bool load_blocks(const std::string& path, const TwkReader& reader, const std::vector<uint32_t>& sel,
-                        uint32_t T, const std::vector<twk_hip_ctx*>& ctxs, uint32_t n_samples, std::vector<uint32_t>& rid, std::vector<uint32_t>& pos) {
+                        uint32_t T, const std::vector<twk_hip_ctx*>& ctxs, uint32_t n_samples, std::vector<uint32_t>& rid, std::vector<uint32_t>& pos,
+                        std::vector<twk_hip_variant_meta>* meta_out = nullptr) {      // meta_out: the caller also wants the variants' allele counts
 	using lclock = std::chrono::steady_clock;
 	const auto t_begin = lclock::now();
 	std::vector<uint32_t> first(sel.size() + 1, 0);
 	for (size_t k = 0; k < sel.size(); ++k) first[k + 1] = first[k] + reader.index.ent[sel[k]].n;
 	rid.assign(first.back(), 0); pos.assign(first.back(), 0);
+	if (meta_out) meta_out->assign(first.back(), twk_hip_variant_meta{});
 	if (sel.empty()) {
 		for (auto* c : ctxs) if (!hip_ok(c, twk_hip_set_problem(c, n_samples, 0), "twk_hip_set_problem")) return false;
 		return true;
@@ -416,6 +419,7 @@ static bool load_blocks(const std::string& path, const TwkReader& reader, const 
 			if (!index_block(buf, b.boff[k - b.k0], unc, e.n, &b.desc[v0], &b.meta[v0])) return false;
 		}
 		for (uint32_t i = 0; i < b.nv; ++i) { rid[b.first + i] = b.meta[i].rid; pos[b.first + i] = b.meta[i].pos; }
+		if (meta_out) for (uint32_t i = 0; i < b.nv; ++i) (*meta_out)[b.first + i] = b.meta[i];
 		return true;
 	};
 	auto decoder = [&](uint32_t w) {
@@ -971,6 +975,7 @@ struct ReduceCommand {
 	twk_hip_filters f{};
 	clock::time_point t_load;
 	std::ofstream file;
+	std::vector<twk_hip_variant_meta>* meta = nullptr;           // set before load(): filled with the selection's per-variant metadata (`ldscore --annot`: allele counts)
 
 	// (Impl is twk_ld::twk_ld_impl: private to twk_ld, so a struct out here cannot name it, only take it as a template's argument)
 	template <class Impl>
@@ -1000,7 +1005,7 @@ struct ReduceCommand {
 		t_load = clock::now();
 		const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
 		std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
-		if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, rid, pos)) return failed;
+		if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, rid, pos, meta)) return failed;
 		std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
 		          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
 		mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
@@ -1102,11 +1107,154 @@ struct ReduceCommand {
 // `tomahawk ldscore`: per variant of the selection the number of records Compute would write with the variant at either end and the
 // sum of their R2 (twk_hip_ld_score: reduced on the GPU, no record is formed), as text.  The input is loaded exactly as Compute loads
 // it; one GPU.  Not in the reference.
-bool twk_ld::Score(const twk_ld_settings& s) {
+bool twk_ld::Score(const twk_ld_settings& s) { return Score(s, twk_score_settings()); }
+
+// The annotation file of `tomahawk ldscore --annot` (include/twk_ld.h): the categories' names and (contig name, 1-based position) -> a row of
+// numbers.  -> false after an error message with file and line: unreadable, no header, no or too many columns, a name twice, a row of
+// another length, a position or a number that is none, not finite or beyond 65536 in magnitude, the same key twice.
+namespace {
+struct AnnotFile {
+	std::vector<std::string> names;
+	std::map<std::pair<std::string, uint64_t>, size_t> row;      // -> the row's first number in `values`
+	std::vector<double> values;
+	std::vector<bool> used;
+};
+bool read_annot(const std::string& path, AnnotFile& out) {
+	std::ifstream in(path);
+	if (!in.good()) { std::cerr << stamp("ERROR") << "Failed to open the annotation file: " << path << "..." << std::endl; return false; }
+	std::string text;
+	size_t skip = 0, C = 0;               // the SNP and CM columns of an LDSC .annot; the categories
+	bool have_header = false;
+	for (uint64_t n_line = 1; std::getline(in, text); ++n_line) {
+		if (!text.empty() && text.back() == '\r') text.pop_back();
+		if (text.compare(0, 2, "##") == 0) continue;
+		std::vector<std::string> col;
+		for (size_t at = 0; at < text.size();) {
+			const size_t from = text.find_first_not_of(" \t", at);
+			if (from == std::string::npos) break;
+			const size_t to = text.find_first_of(" \t", from);
+			col.push_back(text.substr(from, to == std::string::npos ? std::string::npos : to - from));
+			at = to == std::string::npos ? text.size() : to;
+		}
+		if (col.empty()) continue;
+		const auto bad = [&]() -> std::ostream& { return std::cerr << stamp("ERROR") << path << ":" << n_line << ": "; };
+		if (!have_header) {
+			have_header = true;
+			if (col[0] == "#" && col.size() > 1) col.erase(col.begin());      // ("# contig pos ...")
+			if (col.size() >= 4 && col[2] == "SNP" && col[3] == "CM") skip = 2;
+			if (col.size() < 2 + skip + 1 || col.size() - 2 - skip > TWK_HIP_ANNOT_MAX_CATEGORIES) {
+				bad() << "the number of annotation columns must be between 1 and " << TWK_HIP_ANNOT_MAX_CATEGORIES << ", not " << (col.size() < 2 + skip ? 0 : col.size() - 2 - skip) << "..." << std::endl;
+				return false;
+			}
+			out.names.assign(col.begin() + 2 + skip, col.end());
+			C = out.names.size();
+			std::set<std::string> seen;
+			for (const std::string& name : out.names)
+				if (!seen.insert(name).second) { bad() << "the annotation " << name << " is named twice..." << std::endl; return false; }
+			continue;
+		}
+		if (col.size() != 2 + skip + C) { bad() << "expected " << 2 + skip + C << " columns, found " << col.size() << "..." << std::endl; return false; }
+		char* end = nullptr;
+		const unsigned long long pos = strtoull(col[1].c_str(), &end, 10);
+		if (*end || col[1][0] == '-' || pos == 0) { bad() << "not a 1-based position: " << col[1] << std::endl; return false; }
+		if (!out.row.emplace(std::make_pair(col[0], (uint64_t)pos), out.values.size()).second) { bad() << col[0] << ":" << pos << " is named twice..." << std::endl; return false; }
+		for (size_t k = 0; k < C; ++k) {
+			const std::string& word = col[2 + skip + k];
+			const double a = strtod(word.c_str(), &end);
+			if (end == word.c_str() || *end || !(a >= -TWK_HIP_ANNOT_MAX_ABS && a <= TWK_HIP_ANNOT_MAX_ABS)) {
+				bad() << "not a finite annotation of at most " << (long long)TWK_HIP_ANNOT_MAX_ABS << " in magnitude: " << word << std::endl;
+				return false;
+			}
+			out.values.push_back(a);
+		}
+	}
+	if (!have_header) { std::cerr << stamp("ERROR") << path << ": no header line (contig pos name1 ...)..." << std::endl; return false; }
+	out.used.assign(out.row.size(), false);
+	return true;
+}
+}  // namespace
+
+// ... and with ss.annot partitioned LD scores (twk_hip_ld_score_annot): per variant and annotation column the sum over the variant's
+// partners of annotation * R2, summed exactly on the GPU.  The annotation file is read and checked before the input is opened or a
+// device touched, as Clump reads its association file.
+bool twk_ld::Score(const twk_ld_settings& s, const twk_score_settings& ss) {
 	ReduceCommand cmd(settings, *mImpl);
 	if (!cmd.begin(s, "A score sums over every record", nullptr)) return false;
+	const bool annotated = !ss.annot.empty();
+	if (ss.self && !annotated) { std::cerr << stamp("ERROR") << "--self adds a variant's own annotation to its partitioned scores: it needs an annotation file (--annot)..." << std::endl; return false; }
+	AnnotFile af;
+	std::vector<twk_hip_variant_meta> meta;
+	if (annotated) {
+		if (!read_annot(ss.annot, af)) return false;
+		cmd.meta = &meta;
+	}
 	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t M = cmd.M;
+	if (annotated) {
+		const size_t C = af.names.size();
+		// every variant of the selection at a (contig, position) the file names gets that row; the others zeros
+		const auto& contigs = cmd.S.reader.hdr.contigs;
+		std::vector<double> annot((size_t)M * C, 0.0);
+		uint64_t n_named = 0;
+		for (uint32_t v = 0; v < M; ++v) {
+			const uint32_t rid = mImpl->rid[v];
+			if (rid >= contigs.size()) continue;
+			const auto it = af.row.find(std::make_pair(contigs[rid].name, (uint64_t)mImpl->pos[v] + 1));
+			if (it == af.row.end()) continue;
+			af.used[it->second / C] = true;
+			std::copy(af.values.begin() + it->second, af.values.begin() + it->second + C, annot.begin() + (size_t)v * C);
+			++n_named;
+		}
+		const uint64_t n_unmatched = (uint64_t)std::count(af.used.begin(), af.used.end(), false);
+		std::cerr << stamp("LOG") << "Annotation file: " << pretty(C) << " categories, " << pretty(af.row.size()) << " rows, " << pretty(n_unmatched) << " name no selected variant; "
+		          << pretty(n_named) << " of " << pretty(M) << " variants are annotated." << std::endl;
+		// the regression's M and M_5_50: the categories' sums over the selection, and over its variants with a minor allele frequency above 0.05
+		std::vector<double> sum_all(C, 0.0), sum_common(C, 0.0);
+		for (uint32_t v = 0; v < M; ++v) {
+			const int64_t called = 2 * (int64_t)cmd.S.n_samples - (int64_t)meta[v].an, ac = meta[v].ac;
+			const bool common = called > 0 && (double)std::min(ac, called - ac) / (double)called > 0.05;
+			for (size_t k = 0; k < C; ++k) {
+				sum_all[k] += annot[(size_t)v * C + k];
+				if (common) sum_common[k] += annot[(size_t)v * C + k];
+			}
+		}
+		std::vector<uint64_t> n_partners(M, 0);
+		std::vector<double> score((size_t)M * C, 0.0);
+		uint64_t np = 0;
+		const auto g = cmd.geometry();
+		const double sec = cmd.call("twk_hip_ld_score_annot", [&] {
+			return !g.pairs ? TWK_HIP_OK : twk_hip_ld_score_annot(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window,
+			                                                       annot.data(), (uint32_t)C, C, n_partners.data(), score.data(), &np);
+		}, &np);
+		if (sec < 0) return false;
+		if (ss.self) for (size_t k = 0; k < score.size(); ++k) score[k] += annot[k];      // (LDSC's convention: r2(v, v) = 1)
+
+		std::ostream* const os = cmd.open_text();
+		if (!os) return false;
+		cmd.header(*os, "ldscore");
+		std::string text = "##annotations=" + std::to_string(C) + "\n";
+		char num[64];
+		for (const auto* sums : {&sum_all, &sum_common}) {
+			text += sums == &sum_all ? "##M=" : "##M_5_50=";
+			for (size_t k = 0; k < C; ++k) { snprintf(num, sizeof(num), k ? ",%.17g" : "%.17g", (*sums)[k]); text += num; }
+			text += '\n';
+		}
+		if (ss.self) text += "##self=1\n";
+		text += "#contig\tpos\tn_partners";
+		for (const std::string& name : af.names) { text += '\t'; text += name; }
+		text += '\n';
+		for (uint32_t v = 0; v < M; ++v) {
+			cmd.place(text, v);
+			snprintf(num, sizeof(num), "\t%llu", (unsigned long long)n_partners[v]); text += num;
+			for (size_t k = 0; k < C; ++k) { snprintf(num, sizeof(num), "\t%.17g", score[(size_t)v * C + k]); text += num; }
+			text += '\n';
+			cmd.spill(*os, text);
+		}
+		if (!cmd.finish(*os, text, "the scores")) return false;
+		std::cerr << stamp("LOG") << "Scored " << pretty(M) << " variants in " << pretty(C) << " categories over " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+		cmd.all_done();
+		return true;
+	}
 	std::vector<uint64_t> n_partners(M, 0);
 	std::vector<double> sum_r2(M, 0.0);
 	uint64_t np = 0;

@@ -203,6 +203,9 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_score.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
                                      C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_score_annot.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32,
+                                           C.c_uint64, p, p, C.POINTER(C.c_uint64)]
     lib.twk_hip_ld_decay.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, p, p,
                                      C.POINTER(C.c_uint64)]
@@ -507,6 +510,34 @@ class HipLd:
         self._check(self._lib.twk_hip_ld_score(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts,
                                                tile_variants, int(window), l_window, n.ctypes.data, s.ctypes.data,
                                                C.byref(npairs)), "twk_hip_ld_score")
+        return n, s, npairs.value
+
+    def ld_score_annot(self, mode: int, filters: Filters, annot, a0: int = 0, nA: int | None = None, b0: int = 0, nB: int | None = None,
+                       triangle: bool = True, part: int = 0, n_parts: int = 1, tile_variants: int = 0, window: int = 0,
+                       l_window: int = 0):
+        """Partitioned LD scores (twk_hip_ld_score_annot): for every variant v and annotation column c the sum over the records
+        ld_region would report with v at either end of rint((R2 * annot[w][c]) * 2^32), w the variant at the other end - summed
+        exactly in integers on the device, converted once and divided by 2^32: the same bits for any tiling, order or repeat.  The
+        variant itself is no partner.  annot: (M, C) float64, one row per uploaded variant (1-D: one column); finite, |a| <= 65536,
+        1 <= C <= 256.  filters.minP must be >= 1.  A shard returns partial arrays.
+        -> (n_partners uint64[M], score float64[M, C], n_pairs)."""
+        M = self.n_variants
+        a = np.ascontiguousarray(annot, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if a.ndim != 2 or a.shape[0] != M:
+            raise ValueError(f"annot must have one row per uploaded variant: {M}, not shape {a.shape}")
+        ncat = a.shape[1]
+        nA = M - a0 if nA is None else nA
+        nB = M - b0 if nB is None else nB
+        n = np.zeros(M, dtype=np.uint64)
+        s = np.zeros((M, ncat), dtype=np.float64)
+        npairs = C.c_uint64(0)
+        f = filters._c()
+        # (a column count the engine refuses is the engine's to refuse: it reads nothing before it has)
+        self._check(self._lib.twk_hip_ld_score_annot(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts,
+                                                     tile_variants, int(window), l_window, a.ctypes.data, ncat, max(ncat, 1),
+                                                     n.ctypes.data, s.ctypes.data, C.byref(npairs)), "twk_hip_ld_score_annot")
         return n, s, npairs.value
 
     def ld_decay(self, mode: int, filters: Filters, range_bp: int = 10_000_000, n_bins: int = 1000, a0: int = 0, nA: int | None = None,
