@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check form-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -138,6 +138,13 @@ annot-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/annot_term_check.cpp -o build/annot_term_check
 	./build/annot_term_check
+
+# Who may take which form of a count launch (csrc/hip/ld_form.h): decide_form over every combination of facts and grants, the transitions of
+# CallForms::gave_up and the ladder a redone tile descends (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
+form-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/form_check.cpp -o build/form_check
+	./build/form_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -1,0 +1,85 @@
+// The form of a count launch - which contraction, which math behind it - and who may take which: what a launch is (LaunchForm), what its
+// owner allows it (FormGrant), what the plan, the filters and the options fix (FormFacts), what the running call has not yet given up
+// (CallForms).  Host-only, no HIP: twk_hip.hip's launch_form gathers the facts and calls decide_form(); csrc/tools/form_check.cpp plays every
+// combination on the host (make form-check, tests/test_form_cpu.py).
+#pragma once
+#include <stdint.h>
+
+namespace twk {
+
+// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate or _score_annot runs: it looks at
+// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the seven kernels share).
+enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot };
+constexpr int N_REDUCE = (int)Reduce::annot + 1;
+// The form of a launch, decided once (decide_form) and passed down: which count kernel, which math behind it.
+struct LaunchForm {
+	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
+	bool fused = false;            // the fused count -> screen kernel: no count matrix, C holds the candidate list
+	bool unphased = false;         // plain unphased planes with UnphasedMath: the list math, if there is one, is the unphased kernel
+	bool three = false;            // the three-product form (HH + S; the candidates' four products are recounted): fused, or ...
+	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
+	bool two = false;              // the two-product form (HH + HQ through a count matrix, S bounded from the margins): never fused, never with `three`
+	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
+	bool sample = false;           // a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name (k_count3_list_t<.., 1>), so that a
+	                               // kernel trace's statistics of the real launches are not diluted by half-millisecond ones
+	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
+	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
+};
+
+// Rows of at most this many K chunks (32 words each: N <= 65,536 phased, N <= 131,072 unphased) take the fused
+// count -> screen kernel.  Up to 16 chunks a tile is never worth splitting, and the C round trip plus the
+// one-thread-per-pair math front end cost as much as the counting itself.  Beyond that a fused launch ends less evenly
+// (a block must hold a pair's whole count to screen it, so the last tiles cannot be cut along K: +2..6 % count kernel at
+// 40-118 chunks) but still saves several times that in the math kernel (tests/sweeps/fused_mid_n.sh,
+// profiles/r03_fused_mid_n.txt: N = 60,000 -p, 4e4 variants: 46 + 15 ms -> 49 + 2.5 ms); the two meet near 220 chunks.
+constexpr uint32_t FUSED_MAX_CHUNKS = 128;
+
+// What the owner of a launch allows it: `two` only where the two-product walk's owner says so for this launch (RegionRun, on the sorted set).
+struct FormGrant { bool fused = true, three = true, two = false, sample = false; };
+// What the tile plan, the filters and the options fix, whoever grants what.
+struct FormFacts {
+	bool two_pass = false;
+	bool phased_plain = false, unphased_plain = false;      // PhasedMath on plain phased planes (one count per pair) / UnphasedMath on plain unphased planes
+	Reduce reduce = Reduce::none;
+	bool cut_screens = false;                               // an r2 cut-off a screen can use: minR2 > 1e-6 && minR2 <= 1
+	uint32_t chunks = 0;                                    // K chunks of a row (read only where a launch may fuse)
+	bool sorted_u = false;                                  // the set is PS_SORTED_U
+	long long opt_fused = 1, opt_three = 1, opt_two = 1;
+};
+// A screen in front of the math needs plain phased planes with PhasedMath, or plain unphased planes (four products per pair, gathered in the
+// epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short enough that no tile's K
+// range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h) on unphased planes - or,
+// where it is granted, two products in place of three through a matrix.
+inline bool may_screen(const FormFacts& x, const FormGrant& g) { return x.reduce == Reduce::none && g.fused && (x.phased_plain || x.unphased_plain) && x.cut_screens; }
+inline LaunchForm decide_form(const FormFacts& x, const FormGrant& g) {
+	LaunchForm lf;
+	lf.two_pass = x.two_pass; lf.reduce = x.reduce; lf.keep_three = x.opt_three == 2; lf.unphased = x.unphased_plain; lf.sample = g.sample;
+	if (!may_screen(x, g)) return lf;
+	lf.three = lf.unphased && g.three && x.opt_three != 0;
+	lf.fused = x.opt_fused != 0 && (x.opt_fused == 2 || x.chunks <= FUSED_MAX_CHUNKS);
+	if (lf.three && !lf.fused && !lf.two_pass && x.sorted_u && g.two && x.opt_two != 0) { lf.two = true; lf.three = false; }
+	return lf;
+}
+// The ladder: what the tile of a launch whose candidate list overflowed may be when it is redone - a two-product launch's with three products
+// (if it was granted them), a fused or three-product launch's with four products through a matrix.
+inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
+	if (!was.two) given.fused = given.three = false;
+	given.two = false;
+	return given;
+}
+
+// What the running call has not yet given up: a region call owns one for all its stages, the single-tile entry a fresh one.
+struct CallForms {
+	bool fused = true, three = true, two = true;
+	// ... and allows a launch, whose owner wants three / two products for it
+	FormGrant grant(bool want_three, bool want_two) const { return FormGrant{fused, three && want_three, two && want_two, false}; }
+	// A launch of form `was`, given `given`, is through: a list that overflowed (cand_overflow) or held more candidates than the recount is worth
+	// (too_rich) ends the form for the rest of the call - but a form the launch was not given is not taken from the call on its account.
+	void gave_up(const LaunchForm& was, const FormGrant& given, bool cand_overflow, bool too_rich) {
+		if (cand_overflow && was.two) two = two && !given.two;
+		if (cand_overflow && (was.fused || was.three)) { fused = fused && !given.fused; three = three && !given.three; }
+		if (too_rich && was.three && !was.keep_three) three = three && !given.three;
+	}
+};
+
+}  // namespace twk

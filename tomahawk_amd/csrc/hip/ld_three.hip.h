@@ -77,7 +77,7 @@ void k_screen2_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 // and count all four products afresh - nothing of the three-product contraction is reused, so a record is exactly what
 // the four-product form would have made it.  The few candidates of a default run (r2 >= 0.1: pairs in real LD) cost nothing
 // next to the contraction; the host stops using the three-product forms when a launch's candidates are too many for that to
-// hold (twk_hip.hip: three_ok).  The recount also proves the contraction, always: a candidate whose (HH, S) disagree with its
+// hold (Launch::too_rich -> ld_form.h: CallForms::gave_up).  The recount also proves the contraction, always: a candidate whose (HH, S) disagree with its
 // own four products is counted in *mismatches, and the host fails the call on it.  two != 0: the candidates are a two-product launch's,
 // (A, B, HH, HQ) - the proof is then that both products equal their recount.
 template <int LANES>

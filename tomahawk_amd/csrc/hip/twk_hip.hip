@@ -54,6 +54,7 @@
 #include "ld_matrix.hip.h"
 #include "ld_relate.hip.h"
 #include "ld_plan.h"
+#include "ld_form.h"
 #include "twk_delivery.h"
 #include "twk_buffers.h"
 
@@ -124,22 +125,6 @@ constexpr int N_SLOT_COUNTERS = 16;      // (see Slot::n_out)
 // until the host had sorted, copied and handed over launch t and come back with launch t + 2 (2,504 x 531,500, all pairs:
 // 39 launches of 13 ms took 1.25 s).  With t + 2 already queued the count kernels run back to back.
 constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
-// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate or _score_annot runs: it looks at
-// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the seven kernels share).
-enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot };
-constexpr int N_REDUCE = (int)Reduce::annot + 1;
-// The form of a launch, decided once (launch_form) and passed down: which count kernel, which math behind it.
-struct LaunchForm {
-	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first
-	bool fused = false;            // the fused count -> screen kernel: no count matrix, C holds the candidate list
-	bool unphased = false;         // plain unphased planes with UnphasedMath: the list math, if there is one, is the unphased kernel
-	bool three = false;            // the three-product form (HH + S; the candidates' four products are recounted): fused, or ...
-	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
-	bool two = false;              // the two-product form (HH + HQ through a count matrix, S bounded from the margins): never fused, never with `three`
-	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
-	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
-	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
-};
 // What the running call of one of them sets, for its length: ~ReduceCall puts a default-constructed one back.
 struct ReduceState {
 	Reduce kind = Reduce::none;
@@ -150,6 +135,7 @@ struct ReduceState {
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
 struct Launch {
 	LaunchForm form;
+	FormGrant given;                              // ... decided under this grant (enqueue_tile): what CallForms::gave_up reads when the launch is through
 	bool is_list = false;                         // a carrier-list pass (ld_list.hip.h): C holds its candidate list
 	bool is_probe = false;                        // ... of the probe kind (zone rows x columns outside the zone)
 	// a band launch (region_impl): its pair math is enqueued once its candidate count is known (enqueue_band_math)
@@ -162,6 +148,7 @@ struct Launch {
 	uint32_t* cand = nullptr;                     // the candidate list of the launch (in C)
 	unsigned long long cand_cap = 0;              // ... of this many entries; n_out[2] counts them
 	bool cand_overflow = false;                   // set by finish_tile: the list did not hold them all
+	bool too_rich = false;                        // set by finish_tile: a three-product launch with more candidates than their recount is worth
 	bool band_too_big = false;                    // a band launch whose candidates need more survivor / sort buffers than it may have (or could get): finish_tile reports
 	                                              // it as an overflow and the launch's rows are redone as matrix-sized tiles
 	int plane_set = 0;                            // the plane set the launch contracted
@@ -283,12 +270,6 @@ struct twk_hip_ctx {
 	PinnedBuf<twk_hip_record> h_recs;   // pinned staging
 	// twk_hip_set_device_sink: the survivors of region calls stay on the device, appended here tile by tile
 	DevBuf<StatsParams> d_list_stats;             // parameter block of the list pass's math kernel (device copy)
-	bool fused_ok = true;           // cleared for the rest of a call when a fused tile's candidate list overflowed
-	bool three_ok = true;           // cleared for the rest of a call when a three-product launch had too many candidates for the recount to stay cheap
-	bool two_ok = true;             // cleared for the rest of a call when a two-product launch's candidate list overflowed
-	bool two_now = false;           // the launch being enqueued lies in front of the two-product walk's cut and its sample was poor in candidates (RegionRun)
-	bool sampling = false;          // the launch being enqueued is a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name
-	                                // (k_count3_list_t<.., 1>), so that a kernel trace's statistics of the real launches are not diluted by half-millisecond ones
 	bool sorted_keeps_no_lists[2] = {false, false};      // [phased, unphased]: the allele-count-sorted set was built once for a run below the band's cut-off and
 	                                                     // kept no carrier lists: such runs go the file-order way without building it again (cleared with the planes)
 	bool device_sink = false;
@@ -566,14 +547,6 @@ int ensure_host_records(twk_hip_ctx* c, unsigned long long n, char* err = nullpt
 	return TWK_HIP_OK;
 }
 
-// Rows of at most this many K chunks (32 words each: N <= 65,536 phased, N <= 131,072 unphased) take the fused
-// count -> screen kernel.  Up to 16 chunks a tile is never worth splitting, and the C round trip plus the
-// one-thread-per-pair math front end cost as much as the counting itself.  Beyond that a fused launch ends less evenly
-// (a block must hold a pair's whole count to screen it, so the last tiles cannot be cut along K: +2..6 % count kernel at
-// 40-118 chunks) but still saves several times that in the math kernel (tests/sweeps/fused_mid_n.sh,
-// profiles/r03_fused_mid_n.txt: N = 60,000 -p, 4e4 variants: 46 + 15 ms -> 49 + 2.5 ms); the two meet near 220 chunks.
-constexpr uint32_t FUSED_MAX_CHUNKS = 128;
-
 // Launch the count kernel for one tile on the compute stream (which: first or second launch of the slot - its event pair, ev_c0 / ev_c1
 // or ev_c0b / ev_c1b, and its row_pairs field follow from it).
 // form.fused: the fused kernels (k_count_screen_t) - no tile's K range is split, and the slot's C buffer holds the candidate list
@@ -620,13 +593,13 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		HIPCHK(c, hipMemsetAsync(w.ticket, 0, 8 * 4, c->s_compute));
 		const FusedArgs* d_fa = reinterpret_cast<const FusedArgs*>(s.d_tiles[which] + words_units);
 		if (with_args) { s.l.d_stats_dev = const_cast<StatsParams*>(&d_fa->stats); s.l.d_screen_dev = &d_fa->screen; }
-		// one kernel: into the candidate list (fused) or into a matrix; a density sample's runs under a name of its own (twk_hip_ctx::sampling)
+		// one kernel: into the candidate list (fused) or into a matrix; a density sample's runs under a name of its own (LaunchForm::sample)
 		void (*k_list)(CountWork, const ScreenWork*) = nullptr;
 		void (*k_matrix)(CountWork) = nullptr;
-		if (fuse && three) k_list = c->sampling ? k_count3_screen_unphased_t<COUNT_NW, 1> : k_count3_screen_unphased_t<COUNT_NW>;
-		else if (three) k_matrix = c->sampling ? k_count3_list_t<COUNT_NW, 1> : k_count3_list_t<COUNT_NW>;
+		if (fuse && three) k_list = form.sample ? k_count3_screen_unphased_t<COUNT_NW, 1> : k_count3_screen_unphased_t<COUNT_NW>;
+		else if (three) k_matrix = form.sample ? k_count3_list_t<COUNT_NW, 1> : k_count3_list_t<COUNT_NW>;
 		else if (fuse) k_list = form.unphased ? k_count_screen_unphased_t<COUNT_NW> : k_count_screen_t<COUNT_NW>;
-		else k_matrix = (two && c->sampling) ? k_count_list_t<COUNT_NW, 1> : k_count_list_t<COUNT_NW>;
+		else k_matrix = (two && form.sample) ? k_count_list_t<COUNT_NW, 1> : k_count_list_t<COUNT_NW>;
 		const uint32_t tile_rows = three ? TILE / 2 : TILE;
 		if (k_list) HIPCHK(c, enqueue_count(c->s_compute, w, tb, cs.n_blocks, tile_rows, nullptr, k_list, &d_fa->screen));
 		else HIPCHK(c, enqueue_count(c->s_compute, w, tb, cs.n_blocks, tile_rows, nullptr, k_matrix));
@@ -716,29 +689,26 @@ int launch_fisher(twk_hip_ctx* c, twk_hip_record* recs, unsigned long long* n_ou
 	return TWK_HIP_OK;
 }
 
-// The form of the (first) launch of a tile of this plan, as the context stands: the one place that reads the options "fused" and "three",
-// FUSED_MAX_CHUNKS, fused_ok, three_ok and reduce for it.
-// A screen in front of the math needs plain phased planes (one count per pair) with PhasedMath, or plain unphased planes (four products per
-// pair, gathered in the epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short
-// enough that no tile's K range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h)
-// on unphased planes.  Row lengths are read last, from planes built here if need be (a set that cannot be built: no screen; enqueue_tile
-// reports why).
-LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f) {
-	LaunchForm lf;
-	lf.two_pass = pl.set2 >= 0; lf.reduce = c->reduce.kind; lf.keep_three = c->opt.three == 2;
+// The form of the (first) launch of a tile of this plan under the grant of the launch's owner: the facts - the plan, the cut-off, the options "fused",
+// "three" and "two", the running reduce kind - gathered for decide_form (ld_form.h), which is the one place that weighs them.  Row lengths are read
+// last and only where a launch may fuse, from planes built here if need be (a set that cannot be built: no fused form; enqueue_tile reports why).
+LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters& f, const FormGrant& grant) {
+	FormFacts x;
 	const int k = set_kind(pl.set1);
-	lf.unphased = !pl.phased1 && k == PK_UNPHASED;
-	const bool screen = !lf.reduces() && c->fused_ok && ((pl.phased1 && k == PK_PHASED) || lf.unphased) && f.minR2 > 1e-6 && f.minR2 <= 1.0;
-	if (!screen) return lf;
-	lf.three = lf.unphased && c->three_ok && c->opt.three != 0;
-	if (c->opt.fused != 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK) lf.fused = c->opt.fused == 2 || c->planes[pl.set1].W / KC <= FUSED_MAX_CHUNKS;
-	// two products: only where the walk's owner says so for this launch (two_now: RegionRun, on the sorted set), and only in place of three through a matrix
-	if (lf.three && !lf.fused && !lf.two_pass && pl.set1 == PS_SORTED_U && c->two_now && c->two_ok && c->opt.two != 0) { lf.two = true; lf.three = false; }
-	return lf;
+	x.two_pass = pl.set2 >= 0; x.reduce = c->reduce.kind; x.sorted_u = pl.set1 == PS_SORTED_U;
+	x.phased_plain = pl.phased1 && k == PK_PHASED; x.unphased_plain = !pl.phased1 && k == PK_UNPHASED;
+	x.cut_screens = f.minR2 > 1e-6 && f.minR2 <= 1.0;
+	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two;
+	if (may_screen(x, grant) && x.opt_fused != 0) {
+		if (ensure_planes(c, pl.set1) == TWK_HIP_OK) x.chunks = c->planes[pl.set1].W / KC;
+		else x.opt_fused = 0;
+	}
+	return decide_form(x, grant);
 }
-// Would a launch of this mode run the fused count -> screen form and nothing else (one pass)?  For the callers that size a launch by it.
-bool fused_form_applies(twk_hip_ctx* c, int mode, const twk_hip_filters& f) {
-	const LaunchForm lf = launch_form(c, plan_for(c, mode), f);
+// Would a launch of this mode run the fused count -> screen form and nothing else (one pass), as far as the call still allows it?  For the callers
+// that size a launch by it.
+bool fused_form_applies(twk_hip_ctx* c, int mode, const twk_hip_filters& f, const CallForms& calls) {
+	const LaunchForm lf = launch_form(c, plan_for(c, mode), f, calls.grant(true, false));
 	return lf.fused && !lf.two_pass;
 }
 
@@ -873,16 +843,16 @@ int close_launch(twk_hip_ctx* c, Slot& s) {
 	return TWK_HIP_OK;
 }
 
-// Enqueue everything for one tile into slot s (count [+ second pass], math, counter copy).
+// Enqueue everything for one tile into slot s (count [+ second pass], math, counter copy), in the form its owner's grant allows (launch_form).
 // list_words != 0: a band launch (region_impl) - the fused form with a candidate list of that many words and no count
 // matrix at all (its rectangle may be far beyond what a matrix could hold); it is an error if the launch does not fuse.
-int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, Slot& s,
+int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, const FormGrant& grant, Slot& s,
                  unsigned long long capacity, const ColRange* cr = nullptr, size_t list_words = 0) {
 	const TilePlan pl = plan_for(c, mode);
 	const int kind1 = pl.set1, kind2 = pl.set2;
 	int rc = ensure_planes(c, kind1); if (rc) return rc;
 	if (kind2 >= 0) { rc = ensure_planes(c, kind2); if (rc) return rc; }
-	const LaunchForm form = launch_form(c, pl, f);
+	const LaunchForm form = launch_form(c, pl, f, grant);
 	const Geometry g = tile_geometry(pl.Pmax, t);
 	if (form.reduces()) capacity = 1;              // a score, prune, clump, matrix, decay or aggregate launch keeps no survivors (and is never a band launch: always the matrix form)
 	if (list_words && !(form.fused && !form.two_pass)) return TWK_HIP_E_STATE;
@@ -894,13 +864,13 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	rc = ensure_slot(c, s, list_words ? list_words : std::max((size_t)g.rowsA * g.rowsB, c_two_words + two_list_words), capacity); if (rc) return rc;
 	tl("slot buffers");
 	Launch& l = begin_launch(s, kind1, f.minP);
-	l.form = form;
+	l.form = form; l.given = grant;
 	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
 	l.cand = s.C; l.cand_cap = (list_words ? list_words : s.C.capacity()) / (form.unphased ? 6 : 3);
 	// The three-product form where the launch does not fuse (long rows: tiles are split along K): the (HH, S) matrix takes the first half of the
 	// slot's count buffer and the candidate list the room behind it - at most 1/128 of the tile's pairs: a candidate's recount streams its four
 	// rows once more, ~25 pairs' worth of contraction, so a launch with more candidates than that is cheaper in the four-product form
-	// (overflow -> three_ok = false -> redone).
+	// (overflow -> CallForms::gave_up -> redone).
 	if (form.three_plain() || form.two) {
 		const size_t c2_words = form.two ? c_two_words : (size_t)(g.rowsA / 2) * g.rowsB;
 		const unsigned long long room = s.C.capacity() > c2_words ? (s.C.capacity() - c2_words) / 6 : 0;
@@ -1223,7 +1193,7 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		// 0.16 ns each (four 320-byte rows from L2 per candidate: 8 TB/s) add 9.3 ms to the math; the two meet near 1.2 %.
 		// (against the variant pairs of the tiles the launch contracted - four plane-row pairs each - not the launch's rectangle: a window
 		// launch's rectangle is mostly outside the window)
-		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) c->three_ok = false;
+		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) s.l.too_rich = true;      // (the launch's owner folds it into the call: CallForms::gave_up)
 	}
 	if (s.l.form.two) {
 		c->timing.two_launches += 1; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
@@ -1385,18 +1355,22 @@ int run_probe_block(twk_hip_ctx* c, const twk_hip_filters& f, bool unphased, uin
 	return end_list_launch(c, t, s.l.row_pairs != 0, n_out, to);
 }
 
-// One tile, synchronously, on the spare slot; survivors go where `to` says.
-int run_tile_sync(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f,
+// One tile, synchronously, on the spare slot; survivors go where `to` says.  `given` is what the caller allows the tile, narrowed here by what the
+// call has given up since, and this is the one place that redoes a tile whose candidate list overflowed: down the ladder (step_down: two products ->
+// three -> four through the matrix; fused -> the matrix), each launch's outcome folded into the call.  Nothing of an overflowed launch was kept (its
+// recount and its list math left at once).
+int run_tile_sync(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, FormGrant given, CallForms& calls,
                   unsigned long long capacity, unsigned long long* n_out, const Deliver& to, const ColRange* cr = nullptr) {
 	Slot& s = c->slot[SYNC_SLOT];
-	int rc = enqueue_tile(c, mode, t, f, s, capacity, cr); if (rc) return rc;
-	rc = finish_tile(c, s, t, n_out, to);
-	if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow) {       // too many candidates for the fused / three-product form: through C, four products, for the rest of this call
-		c->fused_ok = false; c->three_ok = false;
-		rc = enqueue_tile(c, mode, t, f, s, capacity, cr); if (rc) return rc;
+	for (;;) {
+		FormGrant grant = calls.grant(given.three, given.two);
+		grant.fused = grant.fused && given.fused; grant.sample = given.sample;
+		int rc = enqueue_tile(c, mode, t, f, grant, s, capacity, cr); if (rc) return rc;
 		rc = finish_tile(c, s, t, n_out, to);
+		calls.gave_up(s.l.form, grant, s.l.cand_overflow, s.l.too_rich);
+		if (!(rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow)) return rc;
+		given = step_down(s.l.form, grant);
 	}
-	return rc;
 }
 
 int discard_records(void*, const twk_hip_record*, uint64_t) { return 0; }     // the sink of a caller that passed none
@@ -1404,7 +1378,7 @@ int discard_records(void*, const twk_hip_record*, uint64_t) { return 0; }     //
 // A tile whose survivors overflowed the device buffer: redo it in row strips
 // that cannot overflow (strip_rows * cols <= capacity).
 // (cr: the region's column ranges - window, r2 band, list zone - so that a strip decides exactly the pairs its tile would have)
-int redo_tile_in_strips(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f,
+int redo_tile_in_strips(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk_hip_filters& f, const FormGrant& given, CallForms& calls,
                         unsigned long long capacity, const Deliver& to, uint64_t* n_recs, const ColRange* cr = nullptr) {
 	const uint32_t strip = (uint32_t)std::max<unsigned long long>(1, capacity / std::max<uint32_t>(t.nB, 1));
 	const bool diag = t.diag && t.rowA0 == t.rowB0;
@@ -1424,7 +1398,7 @@ int redo_tile_in_strips(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, co
 		}
 		for (int k = 0; k < np; ++k) {
 			unsigned long long n = 0;
-			int rc = run_tile_sync(c, mode, parts[k], f, (unsigned long long)parts[k].nA * parts[k].nB, &n, to, cr);
+			int rc = run_tile_sync(c, mode, parts[k], f, given, calls, (unsigned long long)parts[k].nA * parts[k].nB, &n, to, cr);
 			if (rc) return rc;
 			*n_recs += n;
 		}
@@ -1861,9 +1835,9 @@ int twk_hip_ld_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc* t, const 
 	if (!c->raw) return TWK_HIP_E_STATE;
 	if (!valid_tile(c, t)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->fused_ok = true; c->three_ok = true;
+	CallForms calls;                 // (a call of its own: what a region call gave up does not reach it)
 	unsigned long long n = 0;
-	int rc = run_tile_sync(c, mode, *t, *f, std::max<unsigned long long>(capacity, 1), &n, Deliver());      // (whole, in c->h_recs)
+	int rc = run_tile_sync(c, mode, *t, *f, calls.grant(true, false), calls, std::max<unsigned long long>(capacity, 1), &n, Deliver());      // (whole, in c->h_recs)
 	flush_graveyard(c);
 	*n_out = n;
 	if (n_pairs) *n_pairs = pairs_in_tile(c, *t);
@@ -1891,6 +1865,7 @@ namespace {
 struct RegionRun {
 	twk_hip_ctx* c; int mode; const twk_hip_filters* f;
 	const PlanGeom& g; const PlanEnv& env; RegionPlan& plan;
+	CallForms& calls;                         // what the call - all its stages - has not yet given up (region_dispatch owns it)
 	Deliver to;                               // every launch of the region: the device sink, or the caller's sink (none: records are counted and dropped)
 	std::chrono::steady_clock::time_point t_origin = std::chrono::steady_clock::now();
 	ColRange col_range;
@@ -1902,8 +1877,13 @@ struct RegionRun {
 	// (option two = 2, the test hook: every launch of the walk, whatever the predicate says)
 	bool two_eligible(const twk_hip_tile_desc& t) const { return two_walk() && c->opt.two != 0 && (c->opt.two == 2 || t.rowA0 + t.nA <= g.a0 + plan.two_end); }
 
-	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, twk_hip_record_sink sink_, void* user_)
-		: c(c_), mode(mode_), f(f_), g(g_), env(e_), plan(p_), to{!c_->device_sink, sink_ ? sink_ : discard_records, user_} {}
+	// What launch i of the plan may be: the call's forms, three and two products as the launch's own sample decided.  A tile redone synchronously is not
+	// bound by a sample: it may be whatever the call still allows but two products (redo_grant).
+	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0); }
+	FormGrant redo_grant() const { return calls.grant(true, false); }
+
+	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, CallForms& calls_, twk_hip_record_sink sink_, void* user_)
+		: c(c_), mode(mode_), f(f_), g(g_), env(e_), plan(p_), calls(calls_), to{!c_->device_sink, sink_ ? sink_ : discard_records, user_} {}
 
 	void mark(const char* what, size_t i, unsigned long long x = 0) const {       // "timeline" option: where the host's time goes
 		if (!c->opt.timeline) return;
@@ -1999,7 +1979,7 @@ struct RegionRun {
 		const size_t n = mine.size();
 		want_three.assign(n, 1); want_two.assign(n, 0);
 		if (c->opt.two == 2) for (size_t i = 0; i < n; ++i) want_two[i] = two_eligible(mine[i]) ? 1 : 0;
-		if (mine.empty() || c->opt.three != 1 || !launch_form(c, plan_for(c, mode), *f).three) return TWK_HIP_OK;      // (no launch of this region would take the form)
+		if (mine.empty() || c->opt.three != 1 || !launch_form(c, plan_for(c, mode), *f, redo_grant()).three) return TWK_HIP_OK;     // (no launch of this region would take the form)
 		// (fused launches - short rows - are sampled as well: they keep their candidates whatever their number, but past ~1.2 % of the pairs
 		// the recount costs more than the third product saves: 2,504 samples, -u -w 1000000, 2.9 % candidates: 27.4 + 30.3 ms of count kernel and
 		// math with three products in the first of two launches, 30 + 21 ms with four in both)
@@ -2024,15 +2004,13 @@ struct RegionRun {
 				const size_t keep_ring = c->launch_ring.size(); const uint64_t keep_seen = c->launches_seen;
 				Slot& ss = c->slot[SYNC_SLOT];
 				unsigned long long nrec = 0;
-				c->sampling = true; c->two_now = two;
-				int rc = enqueue_tile(c, mode, st, *f, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
-				c->sampling = false; c->two_now = false;
+				// (three products granted: a sample is only taken where the call allows them; and its own overflow or richness decides its launch, not the call)
+				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
 				if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
 				cand = ss.h_n_out[2];
 				c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
 				if (c->launch_ring.size() > keep_ring && c->launches_seen == keep_seen + 1 && keep_seen < LAUNCH_RING) c->launch_ring.pop_back();
 				c->launches_seen = keep_seen;
-				c->three_ok = true;                      // (a sample's own overflow decides its launch, not the call)
 				return rc;
 			};
 			if (c->opt.two == 1 && two_eligible(t0)) {
@@ -2050,18 +2028,22 @@ struct RegionRun {
 		return TWK_HIP_OK;
 	}
 
-	// One matrix-sized tile, synchronously, with its fallbacks: the fused form's candidate list overflowed -> through C (and
-	// the rest of the call as well); more survivors than the buffer holds -> row strips.
-	int run_tile_with_fallbacks(const twk_hip_tile_desc& t) {
-		unsigned long long nrec = 0;
-		int r = run_tile_sync(c, mode, t, *f, cap_default, &nrec, to, cr());
-		if (r == TWK_HIP_E_OVERFLOW) {
+	// What every tile ends with once its launch, or the ladder below it (run_tile_sync), is through with rc: more survivors than the buffer holds -> the
+	// tile again in row strips that cannot overflow; its records into the total.
+	int strips_if_overflowed(int rc, const twk_hip_tile_desc& t, unsigned long long nrec) {
+		if (rc == TWK_HIP_E_OVERFLOW) {
 			uint64_t nr = 0;
-			r = redo_tile_in_strips(c, mode, t, *f, c->slot[SYNC_SLOT].cap_use, to, &nr, cr());
+			rc = redo_tile_in_strips(c, mode, t, *f, redo_grant(), calls, cap_default, to, &nr, cr());
 			nrec = nr;
 		}
-		if (r == TWK_HIP_OK) tot_recs += nrec;
-		return r;
+		if (rc == TWK_HIP_OK) tot_recs += nrec;
+		return rc;
+	}
+	// One matrix-sized tile, synchronously, with its fallbacks.
+	int run_tile_with_fallbacks(const twk_hip_tile_desc& t) {
+		unsigned long long nrec = 0;
+		const int rc = run_tile_sync(c, mode, t, *f, redo_grant(), calls, cap_default, &nrec, to, cr());
+		return strips_if_overflowed(rc, t, nrec);
 	}
 	// a band launch that cannot run (or has overflowed) as the matrix-sized tiles of its rows
 	int run_band_as_matrix_tiles(const BandLaunch& b) {
@@ -2092,36 +2074,20 @@ struct RegionRun {
 		int rc;
 		if (b) {
 			rc = skipped[done] ? TWK_HIP_E_OVERFLOW : finish_tile(c, s, mine[done], &nrec, to);
+			// (a band launch's list is the planner's guess for a whole band: its overflow ends no form - the matrix-sized tiles that redo it try theirs)
+			if (!skipped[done]) calls.gave_up(s.l.form, s.l.given, false, s.l.too_rich);
 			mark("finished (records delivered) launch", done, nrec);
 			if (rc == TWK_HIP_E_OVERFLOW) rc = run_band_as_matrix_tiles(*b);      // candidates or survivors beyond the launch's buffers
 			else if (rc == TWK_HIP_OK) tot_recs += nrec;
 			return rc;
 		}
 		rc = finish_tile(c, s, mine[done], &nrec, to);
-		if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow && s.l.form.two) {
-			// a two-product launch's list overflowed: this tile again with three products (run_tile_sync goes on to four if that list overflows too), and
-			// no two-product launches for the rest of the call; nothing of the overflowed launch was kept (its recount and its list math left at once)
-			c->two_ok = false;
-			const bool three_was = c->three_ok, three_given = three_was && want_three[done] != 0;
-			c->three_ok = three_given;
-			rc = run_tile_sync(c, mode, mine[done], *f, cap_default, &nrec, to, cr());
-			c->three_ok = (three_given && !c->three_ok) ? false : three_was;       // (cleared inside: the three-product redo overflowed as well)
-		} else if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow) {     // the fused / three-product form's candidate list overflowed: this tile again through C, four products
-			c->fused_ok = false; c->three_ok = false;            // (and the tiles not yet enqueued as well)
-			rc = run_tile_sync(c, mode, mine[done], *f, cap_default, &nrec, to, cr());
-		}
-		if (rc == TWK_HIP_E_OVERFLOW) {
-			uint64_t nr = 0;
-			rc = redo_tile_in_strips(c, mode, mine[done], *f, s.cap_use, to, &nr, cr());
-			if (rc) return rc;
-			tot_recs += nr;
-		} else if (rc) {
-			return rc;
-		} else {
-			tot_recs += nrec;
-		}
-		mark("finished (records delivered) launch", done, tot_recs);
-		return TWK_HIP_OK;
+		calls.gave_up(s.l.form, s.l.given, s.l.cand_overflow, s.l.too_rich);      // (the launches not yet enqueued see it; those in flight keep their grant)
+		if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow)                        // the candidate list overflowed: this tile again, one step down the ladder
+			rc = run_tile_sync(c, mode, mine[done], *f, step_down(s.l.form, s.l.given), calls, cap_default, &nrec, to, cr());
+		rc = strips_if_overflowed(rc, mine[done], nrec);
+		if (rc == TWK_HIP_OK) mark("finished (records delivered) launch", done, tot_recs);
+		return rc;
 	}
 
 	// Software pipeline over the launches of this shard, PIPE_SLOTS deep.  The pair math of a band launch follows once its count kernel is
@@ -2135,14 +2101,10 @@ struct RegionRun {
 		int rc = TWK_HIP_OK;
 		auto issue_next = [&]() -> int {
 			const BandLaunch* b = issued < plan.bands.size() ? &plan.bands[issued] : nullptr;
-			if (b && !c->fused_ok) skipped[issued] = 1;                 // an earlier launch gave the fused form up: this one goes the matrix way when its turn comes
+			if (b && !calls.fused) skipped[issued] = 1;                 // an earlier launch gave the fused form up: this one goes the matrix way when its turn comes
 			else {
 				mark("enqueue launch", issued);
-				const bool three_was = c->three_ok;
-				c->three_ok = three_was && want_three[issued] != 0;       // (the launch's own sample)
-				c->two_now = want_two[issued] != 0;
-				const int r = enqueue_tile(c, mode, mine[issued], *f, c->slot[issued % PIPE_SLOTS], b ? 1 : cap_default, cr(), b ? b->list_words : 0);
-				c->three_ok = three_was; c->two_now = false;
+				const int r = enqueue_tile(c, mode, mine[issued], *f, grant_of(issued), c->slot[issued % PIPE_SLOTS], b ? 1 : cap_default, cr(), b ? b->list_words : 0);
 				if (r) return r;
 				mark("enqueued launch", issued);
 			}
@@ -2166,7 +2128,7 @@ struct RegionRun {
 };
 
 // What the planner needs to know of the context for this mode.
-int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, PlanEnv& env) {
+int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, const CallForms& calls, PlanEnv& env) {
 	env = PlanEnv();
 	if (mode == MODE_INT_GROUPED || mode == MODE_INT_SORTED_P || mode == MODE_INT_SORTED_U || mode == MODE_INT_SORTED_U_ALL) {
 		const int set = mode == MODE_INT_GROUPED ? PS_GROUPED : mode == MODE_INT_SORTED_P ? PS_SORTED_P : PS_SORTED_U;
@@ -2189,7 +2151,7 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, PlanEnv& en
 	const TilePlan pl = plan_for(c, mode);
 	env.n_samples = c->N; env.Pmax = pl.Pmax; env.resident_blocks = c->resident_blocks; env.minR2 = f->minR2; env.phased_math = pl.phased1;
 	env.meta = c->h_meta.data();
-	env.fused = fused_form_applies(c, mode, *f);
+	env.fused = fused_form_applies(c, mode, *f, calls);
 	if (env.fused) env.nchunks = c->planes[pl.set1].W / KC;
 	env.band_launch = c->opt.band_launch != 0; env.band_reverse = c->opt.band_reverse != 0;
 	env.band_work_log2 = c->opt.band_work_log2; env.band_max_launches = c->opt.band_max_launches; env.band_list_entries = c->opt.band_list_entries;
@@ -2209,13 +2171,13 @@ struct RegionArgs {
 	}
 };
 
-static int region_impl(twk_hip_ctx* c, const RegionArgs& a) {
+static int region_impl(twk_hip_ctx* c, const RegionArgs& a, CallForms& calls) {
 	const PlanGeom g{a.a0, a.nA, a.b0, a.nB, a.triangle, a.part, a.n_parts, a.tile_variants, a.window, a.l_window};
 	PlanEnv env;
-	int rc = plan_env_for(c, a.mode, a.f, env); if (rc) return rc;
+	int rc = plan_env_for(c, a.mode, a.f, calls, env); if (rc) return rc;
 	RegionPlan plan;
 	plan_region(env, g, plan);
-	RegionRun run(c, a.mode, a.f, g, env, plan, a.sink, a.user);
+	RegionRun run(c, a.mode, a.f, g, env, plan, calls, a.sink, a.user);
 	run.mark("region: mode", (size_t)a.mode, a.nA);
 	rc = run.prepare(); if (rc) return rc;
 	rc = run.run_zone_passes(); if (rc) return rc;
@@ -2235,8 +2197,8 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	if (a.nA == 0 || a.nB == 0 || (uint64_t)a.a0 + a.nA > c->M || (uint64_t)a.b0 + a.nB > c->M) return TWK_HIP_E_INVALID;
 	if (a.triangle && (a.a0 != a.b0 || a.nB < a.nA)) return TWK_HIP_E_INVALID;
 	HIPCHK(c, hipSetDevice(c->device));
-	c->two_ok = true; c->two_now = false;
-	c->fused_ok = c->three_ok = c->reduce.kind == Reduce::none;      // a score, a prune, a clump, a matrix, a decay or an aggregate looks at every pair: no screen in front of the count matrix
+	CallForms calls;                 // of this call, all its stages: a later stage sees what an earlier one gave up
+	calls.fused = calls.three = calls.two = c->reduce.kind == Reduce::none;      // a score, a prune, a clump, a matrix, a decay or an aggregate looks at every pair: no screen in front of the count matrix
 	const bool whole = a.triangle && a.a0 == 0 && a.nA == c->M && a.nB == c->M;
 	// TWK_HIP_OPT_R2_SCREEN: whole-triangle runs with an r2 cut-off worth the name, outside window mode (which
 	// already prunes by position, in an order the allele-count sort would destroy)
@@ -2260,7 +2222,7 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 				c->planes[sset] = PlaneSet();
 			}
 		}
-		if (keep_sorted) return region_impl(c, a.stage(mode == TWK_HIP_MODE_UNPHASED ? MODE_INT_SORTED_U : MODE_INT_SORTED_P, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records));
+		if (keep_sorted) return region_impl(c, a.stage(mode == TWK_HIP_MODE_UNPHASED ? MODE_INT_SORTED_U : MODE_INT_SORTED_P, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records), calls);
 	}
 	// The two-product walk: an unscreened UnphasedMath call over the whole triangle walks the allele-count-sorted set as well - every
 	// pair is still contracted (no band, no list or probe zone), but the launches over the rows with few hom-alt carriers take two products a pair.
@@ -2271,11 +2233,11 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 	    a.tile_variants == 0 && c->opt.two != 0 && c->opt.three == 1 && f->minR2 > 1e-6 && f->minR2 <= 1.0 && c->M >= 2 &&
 	    (c->opt.fused == 0 || (c->opt.fused == 1 && c->Wu / KC > FUSED_MAX_CHUNKS))) {
 		const int prc = ensure_planes(c, PS_SORTED_U);
-		if (prc == TWK_HIP_OK) return region_impl(c, a.stage(MODE_INT_SORTED_U_ALL, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records));
+		if (prc == TWK_HIP_OK) return region_impl(c, a.stage(MODE_INT_SORTED_U_ALL, 0, c->M, 0, c->M, 1, a.n_pairs, a.n_records), calls);
 		if (prc != TWK_HIP_E_NOMEM) return prc;
 		(void)hipGetLastError(); c->err[0] = 0;
 	}
-	if (!(mode == TWK_HIP_MODE_AUTO && c->any_missing && whole)) return region_impl(c, a);
+	if (!(mode == TWK_HIP_MODE_AUTO && c->any_missing && whole)) return region_impl(c, a, calls);
 	// Default mode over the whole triangle with missing genotypes somewhere: every pair goes through
 	// the cheap one-plane phased products, and only the pairs that involve a variant with missing
 	// data (the leading group G of the regrouped set) through the 3-plane unphased ones:
@@ -2288,18 +2250,18 @@ static int region_dispatch(twk_hip_ctx* c, const RegionArgs& a) {
 		// the stages below then cover every pair that involves a variant with missing data
 		rc = ensure_planes(c, PS_SORTED_P); if (rc) return rc;
 		const uint32_t nC = c->planes[PS_SORTED_P].n_front;
-		if (nC >= 2) rc = region_impl(c, a.stage(MODE_INT_SORTED_P, 0, nC, 0, nC, 1, &pairs, &recs));
+		if (nC >= 2) rc = region_impl(c, a.stage(MODE_INT_SORTED_P, 0, nC, 0, nC, 1, &pairs, &recs), calls);
 	} else
-		rc = region_impl(c, a.stage(MODE_INT_AUTO_CLEAN, 0, c->M, 0, c->M, 1, &pairs, &recs));
+		rc = region_impl(c, a.stage(MODE_INT_AUTO_CLEAN, 0, c->M, 0, c->M, 1, &pairs, &recs), calls);
 	struct Mute { twk_hip_ctx* c; ~Mute() { c->progress_muted = false; } } mute{c};
 	c->progress_muted = true;
 	if (rc == TWK_HIP_OK && nG >= 2) {
-		rc = region_impl(c, a.stage(MODE_INT_GROUPED, 0, nG, 0, nG, 1, &p2, &r2));
+		rc = region_impl(c, a.stage(MODE_INT_GROUPED, 0, nG, 0, nG, 1, &p2, &r2), calls);
 		recs += r2;
 		if (screen) pairs += p2;               // the screened stage only counted the pairs without missing data
 	}
 	if (rc == TWK_HIP_OK && nG >= 1 && nG < c->M) {
-		rc = region_impl(c, a.stage(MODE_INT_GROUPED, 0, nG, nG, c->M - nG, 0, &p2, &r2));
+		rc = region_impl(c, a.stage(MODE_INT_GROUPED, 0, nG, nG, c->M - nG, 0, &p2, &r2), calls);
 		recs += r2;
 		if (screen) pairs += p2;
 	}

@@ -1,0 +1,115 @@
+// `make form-check`: who may take which form of a count launch (csrc/hip/ld_form.h), on the CPU under AddressSanitizer and UBSan.
+//   1. decide_form over every combination of FormFacts x FormGrant: no two forms that exclude each other, a reducing launch in no form but
+//      four products through a matrix, every form only on the planes, under the grants and with the options it needs, and no grant whose
+//      withdrawal adds a form - but grant.two, which turns two products into three.
+//   2. CallForms::gave_up: the transitions a launch's outcome makes in what the call still allows, one by one, that a form the launch was not
+//      granted is never taken from the call, and that a second telling changes nothing; step_down, the ladder a redone tile descends.
+#include <cstdio>
+#include <initializer_list>
+#include <vector>
+#include "../hip/ld_form.h"
+
+using namespace twk;
+
+namespace {
+
+int g_bad_checks = 0;
+long g_cases = 0;
+#define CHECK(cond, ...) do { if (!(cond)) { if (g_bad_checks < 40) { fprintf(stderr, "    FAILED %s: ", #cond); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } ++g_bad_checks; } } while (0)
+
+bool same(const LaunchForm& a, const LaunchForm& b) {
+	return a.two_pass == b.two_pass && a.fused == b.fused && a.unphased == b.unphased && a.three == b.three && a.two == b.two && a.keep_three == b.keep_three &&
+	       a.sample == b.sample && a.reduce == b.reduce;
+}
+FormGrant grant_of(int bits) { return FormGrant{(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0}; }
+
+std::vector<FormFacts> all_facts() {
+	std::vector<FormFacts> out;
+	for (int two_pass = 0; two_pass < 2; ++two_pass)
+	for (int planes = 0; planes < 3; ++planes)                        // neither, phased math on plain phased planes, unphased math on plain unphased planes
+	for (const Reduce reduce : {Reduce::none, Reduce::score, Reduce::annot})
+	for (int cut = 0; cut < 2; ++cut)
+	for (const uint32_t chunks : {0u, 1u, FUSED_MAX_CHUNKS, FUSED_MAX_CHUNKS + 1, 4000u})
+	for (int sorted_u = 0; sorted_u < 2; ++sorted_u)
+	for (int f = 0; f < 3; ++f) for (int t3 = 0; t3 < 3; ++t3) for (int t2 = 0; t2 < 3; ++t2) {
+		FormFacts x;
+		x.two_pass = two_pass != 0; x.phased_plain = planes == 1; x.unphased_plain = planes == 2; x.reduce = reduce; x.cut_screens = cut != 0;
+		x.chunks = chunks; x.sorted_u = sorted_u != 0; x.opt_fused = f; x.opt_three = t3; x.opt_two = t2;
+		out.push_back(x);
+	}
+	return out;
+}
+
+void check_decide_form() {
+	for (const FormFacts& x : all_facts()) for (int gb = 0; gb < 16; ++gb) {
+		const FormGrant g = grant_of(gb);
+		const LaunchForm lf = decide_form(x, g);
+		++g_cases;
+		CHECK(!(lf.two && (lf.three || lf.fused || lf.two_pass)), "two products with another form (grant %d)", gb);
+		CHECK(!(lf.reduces() && (lf.fused || lf.three || lf.two)), "a reducing launch in a screened form (grant %d)", gb);
+		CHECK(lf.reduce == x.reduce && lf.two_pass == x.two_pass && lf.unphased == x.unphased_plain && lf.keep_three == (x.opt_three == 2), "a fact not carried over");
+		CHECK(!(lf.three || lf.two) || x.unphased_plain, "three or two products off the plain unphased planes");
+		CHECK(!lf.three || (g.three && g.fused && x.opt_three != 0), "three products without their grants or with the option off");
+		CHECK(!lf.two || (x.sorted_u && g.two && g.three && g.fused && x.opt_two != 0 && x.opt_three != 0), "two products without the sorted set, their grants or their options");
+		CHECK(!lf.fused || (g.fused && x.opt_fused != 0 && (x.opt_fused == 2 || x.chunks <= FUSED_MAX_CHUNKS)), "fused against the option or on rows too long");
+		CHECK(!(lf.fused || lf.three || lf.two) || (x.cut_screens && (x.phased_plain || x.unphased_plain)), "a screen without a cut-off or planes it can use");
+		CHECK(lf.sample == g.sample, "the sample mark");
+		// withdrawing a grant adds no form (two -> three excepted), and grant.sample changes nothing but the mark
+		for (int bit = 0; bit < 4; ++bit) {
+			if (!(gb & (1 << bit))) continue;
+			const LaunchForm less = decide_form(x, grant_of(gb & ~(1 << bit)));
+			if (bit == 3) { LaunchForm marked = less; marked.sample = true; CHECK(same(marked, lf), "grant.sample changed the form"); continue; }
+			CHECK(!(less.fused && !lf.fused), "withdrawing grant %d added the fused form", bit);
+			CHECK(!(less.two && !lf.two), "withdrawing grant %d added two products", bit);
+			if (less.three && !lf.three) CHECK(bit == 2 && lf.two && !less.two, "withdrawing grant %d added three products", bit);
+			if (bit == 2 && !same(less, lf)) CHECK(lf.two && !less.two && less.three && !lf.three && less.fused == lf.fused, "withdrawing grant.two did more than turn two products into three");
+		}
+	}
+}
+
+LaunchForm form_of(bool fused, bool three, bool two, bool keep_three = false) { LaunchForm lf; lf.unphased = three || two; lf.fused = fused; lf.three = three; lf.two = two; lf.keep_three = keep_three; return lf; }
+bool is(const CallForms& c, bool fused, bool three, bool two) { return c.fused == fused && c.three == three && c.two == two; }
+
+void check_gave_up() {
+	const FormGrant all{true, true, true, false};
+	const LaunchForm two = form_of(false, false, true), fused4 = form_of(true, false, false), fused3 = form_of(true, true, false), three = form_of(false, true, false),
+	                 four = form_of(false, false, false), kept3 = form_of(true, true, false, true);
+	{ CallForms c; c.gave_up(two, all, true, false); CHECK(is(c, true, true, false), "a two-product list overflowed"); }
+	for (const LaunchForm& lf : {fused4, fused3, three}) { CallForms c; c.gave_up(lf, all, true, false); CHECK(is(c, false, false, true), "a fused or three-product list overflowed"); }
+	for (const LaunchForm& lf : {fused3, three}) { CallForms c; c.gave_up(lf, all, false, true); CHECK(is(c, true, false, true), "a launch too rich in candidates"); }
+	{ CallForms c; c.gave_up(kept3, all, false, true); CHECK(is(c, true, true, true), "option three = 2 keeps the form"); }
+	{ CallForms c; c.gave_up(four, all, false, false); c.gave_up(fused3, all, false, false); c.gave_up(two, all, false, false); CHECK(is(c, true, true, true), "nothing happened"); }
+	// every outcome of every form under every grant, from every state of the call: nothing comes back, nothing not granted is taken, twice is once
+	for (int fb = 0; fb < 16; ++fb) for (int gb = 0; gb < 8; ++gb) for (int ob = 0; ob < 4; ++ob) for (int cb = 0; cb < 8; ++cb) {
+		const LaunchForm lf = form_of((fb & 1) != 0, (fb & 2) != 0, (fb & 4) != 0, (fb & 8) != 0);
+		if (lf.two && (lf.three || lf.fused)) continue;
+		const FormGrant g = grant_of(gb);
+		CallForms before; before.fused = (cb & 1) != 0; before.three = (cb & 2) != 0; before.two = (cb & 4) != 0;
+		CallForms c = before;
+		c.gave_up(lf, g, (ob & 1) != 0, (ob & 2) != 0);
+		++g_cases;
+		CHECK((!c.fused || before.fused) && (!c.three || before.three) && (!c.two || before.two), "a form came back");
+		CHECK((c.fused == before.fused || g.fused) && (c.three == before.three || g.three) && (c.two == before.two || g.two), "a form that was not granted was taken from the call");
+		if (!ob) CHECK(is(c, before.fused, before.three, before.two), "a launch that went well changed the call");
+		CallForms again = c;
+		again.gave_up(lf, g, (ob & 1) != 0, (ob & 2) != 0);
+		CHECK(is(again, c.fused, c.three, c.two), "not idempotent");
+		// what the call then grants a launch is no more than it still holds
+		const FormGrant next = c.grant(true, true);
+		CHECK(next.fused == c.fused && next.three == c.three && next.two == c.two && !next.sample, "grant");
+		CHECK(!c.grant(false, true).three && !c.grant(true, false).two, "grant beyond what the owner wants");
+	}
+	// the ladder: two -> three (if granted) -> four through the matrix; fused or three -> four through the matrix
+	{ const FormGrant g = step_down(two, all); CHECK(g.fused && g.three && !g.two, "below two products"); }
+	for (const LaunchForm& lf : {fused4, fused3, three}) { const FormGrant g = step_down(lf, all); CHECK(!g.fused && !g.three && !g.two, "below a fused or three-product launch"); }
+	{ FormGrant s = all; s.sample = true; CHECK(step_down(three, s).sample, "the sample mark stays"); }
+}
+
+}  // namespace
+
+int main() {
+	check_decide_form();
+	check_gave_up();
+	printf("form-check: %ld cases, %d bad\n", g_cases, g_bad_checks);
+	return g_bad_checks ? 1 : 0;
+}
