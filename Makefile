@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check form-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check form-check bandmat-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -145,6 +145,14 @@ form-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/form_check.cpp -o build/form_check
 	./build/form_check
+
+# The banded LD matrix's layout against its O(n^2) definition, and the fill's slot arithmetic, guards and dead-block test
+# (csrc/hip/ld_bandmat_index.h) played lane by lane against an array of write counts with a border (csrc/tools/bandmat_index_check.cpp):
+# host code only, under AddressSanitizer and UBSan
+bandmat-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/bandmat_index_check.cpp -o build/bandmat_index_check
+	./build/bandmat_index_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -41,6 +41,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_aggregate - the LD aggregate - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_relationship / twk_hip_relationship_last - the sample relationship matrix - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_score_annot - partitioned LD scores - is an entry point more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_bandmat_layout / twk_hip_ld_matrix_band / twk_hip_bandmat_last - the banded LD matrix - are three entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -396,6 +397,40 @@ int twk_hip_ld_matrix(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters
                       uint64_t* n_records, uint64_t* n_pairs);
 /* Of the context's last twk_hip_ld_matrix call: the time of its device-to-host copy in ms and the matrix's bytes (either may be NULL). */
 int twk_hip_matrix_last(const twk_hip_ctx* ctx, double* copy_ms, uint64_t* matrix_bytes);
+
+/* The banded LD matrix: twk_hip_ld_matrix's values of a WINDOWED run in band storage - per row only the columns inside the window - so
+ * that a chromosome-wide LD reference panel (what LDpred2, PRS-CS, SBayesR and summary-statistics imputation read) fits where the dense
+ * n * n * 4 bytes do not.  The variants of the slice [a0, a0 + n) must be sorted by (rid, pos), as in every .twk.
+ * THE LAYOUT, for a window of l_window base pairs: the band of row u is the contiguous column range [first[u], first[u] + len[u]),
+ * relative to the slice: the variants v of the slice on u's contig with |pos[u] - pos[v]| <= l_window - exactly the rule of the window
+ * test of twk_hip_ld_region.  It is symmetric, includes the diagonal, and is clipped at contig and slice borders.  row_ptr[u] is the sum
+ * of len[0 .. u), row_ptr[n] the number of stored floats; len[u] = row_ptr[u + 1] - row_ptr[u].
+ *   twk_hip_bandmat_layout  first (HOST, n entries) and row_ptr (HOST, n + 1 entries) from the uploaded metadata, on the host, so that
+ *          a caller can size `values`.  TWK_HIP_E_INVALID: a NULL argument, n == 0, a slice beyond the last variant, a slice that is not
+ *          sorted by (rid, pos); TWK_HIP_E_STATE before upload.
+ *   twk_hip_ld_matrix_band  mode, filters, a0, n, tile_variants, l_window, stat, fill, n_records and n_pairs are twk_hip_ld_matrix's;
+ *          `window` holds the option bits and TWK_HIP_OPT_WINDOW must be set.
+ *          values  HOST array of `capacity` >= row_ptr[n] floats.  For every in-band (u, v), values[row_ptr[u] + (v - first[u])] holds,
+ *                  bit for bit, what twk_hip_ld_matrix with the same arguments puts in out[u * n + v]: the statistic rounded once to
+ *                  float32 where twk_hip_ld_region would report a record, `fill` where it would not, and on the diagonal 1.0f for R,
+ *                  R2 and DPRIME and `fill` for D.  Nothing beyond values[row_ptr[n] - 1] is written.  Both orientations are stored:
+ *                  (values, the columns first[u] .. first[u] + len[u] - 1 of every row, row_ptr) is a CSR matrix as it stands.
+ *          first, row_ptr  HOST arrays of n and n + 1 entries, overwritten with the layout.
+ *          TWK_HIP_E_INVALID before any launch, with nothing written to values, first or row_ptr: twk_hip_ld_matrix's own refusals
+ *          (minP < 1, n == 0, a slice beyond the last variant, an unknown stat), TWK_HIP_OPT_WINDOW not set, a NULL values, first or
+ *          row_ptr, capacity < row_ptr[n], a slice that is not sorted.  Device memory: row_ptr[n] * 4 + n * 16 bytes for the length of
+ *          the call; TWK_HIP_E_NOMEM with the byte count in twk_hip_last_error when the device cannot give it.  Plain stores, every
+ *          entry by exactly one lane of one launch or by the preset: two calls return the same bytes, whatever tile_variants.  The band
+ *          leaves the device in one contiguous copy.  twk_hip_timing: the fill kernels count as the math stage.
+ *   twk_hip_bandmat_last  of the context's last twk_hip_ld_matrix_band call: the time of its device-to-host copy in ms and the band's
+ *          bytes, row_ptr[n] * 4 (either may be NULL).
+ * There is NO reference counterpart. */
+int twk_hip_bandmat_layout(twk_hip_ctx* ctx, uint32_t a0, uint32_t n, uint32_t l_window, uint32_t* first, uint64_t* row_ptr);
+int twk_hip_ld_matrix_band(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                           uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                           int32_t stat, float fill, float* values, uint64_t capacity, uint32_t* first, uint64_t* row_ptr,
+                           uint64_t* n_records, uint64_t* n_pairs);
+int twk_hip_bandmat_last(const twk_hip_ctx* ctx, double* copy_ms, uint64_t* band_bytes);
 
 /* LD decay over the same slice of the pair space as twk_hip_ld_score, with the same arguments: r2 as a function of the distance
  * between two variants.  A pair COUNTS when twk_hip_ld_region with these arguments would report a record for it, both variants lie on

@@ -61,6 +61,7 @@ struct twk_matrix_settings {
 	int stat = 0;               // TWK_HIP_STAT_R (signed r), _R2, _D or _DPRIME (include/twk_hip.h)
 	float fill = 0.0f;          // the entry of a pair Compute would write no record for
 	bool text = false;          // PREFIX.ld (space-separated text, as FINEMAP reads it) instead of PREFIX.npy
+	bool band = false;          // band storage: per row only the columns inside the window (needs settings.window; no text form)
 };
 
 // What Decay needs beyond twk_ld_settings.
@@ -144,6 +145,11 @@ public:
 	// PREFIX.npy (NumPy format 1.0, '<f4', C order, shape (n, n)) or, with matrix.text, PREFIX.ld (one row per line, space-separated,
 	// 9 significant digits), and always PREFIX.variants.tsv: one "contig <TAB> pos" line per row, as Score prints them.
 	// settings.minP must be 1 (the default).  `tomahawk ldmatrix` ends here.
+	// With matrix.band (settings.window must be set; matrix.text is refused) the same values leave in band storage
+	// (twk_hip_ld_matrix_band): per row only the variants on its contig within settings.l_window bases, row_ptr[n] floats in place of
+	// n * n - a chromosome-wide panel fits.  PREFIX.values.npy ('<f4', shape (nnz,)), PREFIX.indptr.npy ('<i8', shape (n + 1,)) and
+	// PREFIX.first.npy ('<i4', shape (n,)): entry (u, v), first[u] <= v < first[u] + indptr[u + 1] - indptr[u], is
+	// values[indptr[u] + v - first[u]]; both orientations are stored, so the three are a CSR matrix.  PREFIX.variants.tsv as above.
 	bool Matrix(const twk_ld_settings& settings, const twk_matrix_settings& matrix);
 	// LD decay: mean r2 by the distance between two variants (the reference's two_reader::Decay reads a .two file; here no record is
 	// formed).  Loads the .twk exactly as Score does (-I intervals, -w, -p / -u, -c / -C chunks as regions, TWK_REF_COMPAT).  A pair counts

@@ -12,9 +12,10 @@
 //   decay (ld_decay.hip.h) cells -> r2 -> exact integer sums per distance bin, in place of the math stage (twk_hip_ld_decay)
 //   aggregate (ld_aggregate.hip.h) cells -> one statistic -> exact integer sums, counts and extremes per cell of an x-by-y landscape, likewise (twk_hip_ld_aggregate)
 //   annot (ld_score_annot.hip.h) cells -> r2 -> times the partner's annotations -> exact integer sums per (variant, category), likewise (twk_hip_ld_score_annot)
+//   bandmat (ld_bandmat.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a banded float32 matrix: per row only the columns inside the window (twk_hip_ld_matrix_band)
 //   relate (ld_relate.hip.h) the raw layout transposed into planes of the samples -> count -> genotype-sharing counts and one statistic per sample pair
 //                          (twk_hip_relationship: its own launches, beside the variant launch path)
-//   (score, prune, clump, matrix, decay, aggregate and annot are the seven kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
+//   (score, prune, clump, matrix, decay, aggregate, annot and bandmat are the eight kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -52,6 +53,7 @@
 #include "ld_prune.hip.h"
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
+#include "ld_bandmat.hip.h"
 #include "ld_relate.hip.h"
 #include "ld_plan.h"
 #include "ld_form.h"
@@ -128,7 +130,7 @@ constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
 // What the running call of one of them sets, for its length: ~ReduceCall puts a default-constructed one back.
 struct ReduceState {
 	Reduce kind = Reduce::none;
-	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; } map{};      // where the running kind's launches put their results (prune and clump: bits)
+	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; BandMap band; } map{};      // where the running kind's launches put their results (prune and clump: bits)
 	uint64_t work = 0;                            // what the call's launches used up of the room of the kind's accumulators (launch_reduce holds it to the kind's limit)
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
@@ -156,7 +158,7 @@ struct Launch {
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
-union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; };
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; BandArgs bandmat; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -293,10 +295,10 @@ struct twk_hip_ctx {
 	DevBuf<uint8_t> d_rle, d_rle_desc;
 	DevBuf<int> d_status;
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
-	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
+	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
 	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
-	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last)
+	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last, twk_hip_bandmat_last)
 	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
 	// score: sums of r2 per variant (ld_score.hip.h)
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
@@ -742,7 +744,7 @@ int run_reduce_kernel(twk_hip_ctx* c, const twk_hip_tile_desc& t, Slot& s, int w
 }
 
 // The epilogue of a reduce launch whose count matrix is in the slot's C, by the launch's kind: what follows the call's last launch - prune's and clump's
-// walks, the matrix's diagonal and copy - is the entry point's (twk_hip_ld_prune, _clump, _matrix).
+// walks, the matrix's and the band's diagonal and copy - is the entry point's (twk_hip_ld_prune, _clump, _matrix, _matrix_band).
 int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, int which, bool phased_math, int auto_select, const twk_hip_filters& f, const ColRange* cr) {
 	StatsParams p = make_stats(c, set, t, s, phased_math, auto_select, f, cr);
 	p.out = nullptr; p.capacity = 0; p.n_out = nullptr; p.keys = nullptr; p.vals = nullptr;
@@ -770,6 +772,7 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	case Reduce::decay:     return run_reduce_kernel(c, t, s, which, k_ld_decay, DECAY_THREADS, DECAY_ROWS, DecayArgs{{p, rs.map.decay}}, decay_lds_bytes(rs.map.decay.n_bins));
 	case Reduce::aggregate: return run_reduce_kernel(c, t, s, which, k_ld_aggregate, AGG_THREADS, AGG_ROWS, AggArgs{{p, rs.map.agg}});
 	case Reduce::annot:     return run_reduce_kernel(c, t, s, which, k_ld_annot, ANNOT_THREADS, ANNOT_ROWS, AnnotArgs{{p, rs.map.annot}});      // (no work limit: ld_score_annot.hip.h)
+	case Reduce::bandmat:   return run_reduce_kernel(c, t, s, which, k_ld_bandmat_fill, BANDMAT_THREADS, BANDMAT_ROWS, BandArgs{{p, rs.map.band}});
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -2305,8 +2308,8 @@ int hold_for_call(twk_hip_ctx* c, DevBuf<T>& b, size_t items, const char* what, 
 struct ReduceCall {
 	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
 	int bad;
-	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums.  Freed behind the destructor's body, which waits for the device.
-	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc; DevBuf<float> d_matrix; DevBuf<double> d_annot;
+	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums, the band and its map.  Freed behind the destructor's body, which waits for the device.
+	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc; DevBuf<float> d_matrix, d_band; DevBuf<double> d_annot; DevBuf<BandRow> d_band_rows;
 	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
 	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
 		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
@@ -2527,6 +2530,69 @@ int twk_hip_ld_matrix(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 }
 
 int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) { return last_of(c, Reduce::matrix, copy_ms, matrix_bytes); }
+
+// Banded LD matrix: the band's layout of the slice [a0, a0 + n) from the uploaded metadata (ld_bandmat_index.h), on the host.
+extern "C++" {
+namespace {
+int bandmat_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, uint32_t* first, uint64_t* row_ptr) {
+	const twk_hip_variant_meta* meta = c->h_meta.data() + a0;
+	if (bm_layout(n, [&](uint32_t k) { return meta[k].pos; }, [&](uint32_t k) { return meta[k].rid; }, l_window, first, row_ptr)) return TWK_HIP_OK;
+	snprintf(c->err, sizeof(c->err), "banded LD matrix: the variants [%u, %u) are not sorted by (contig, position): a row's window is then no contiguous band", a0, a0 + n);
+	return TWK_HIP_E_INVALID;
+}
+}  // namespace
+}  // extern "C++"
+
+int twk_hip_bandmat_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, uint32_t* first, uint64_t* row_ptr) {
+	if (!c || !first || !row_ptr) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (n == 0 || (uint64_t)a0 + n > c->M || c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
+	return bandmat_layout(c, a0, n, l_window, first, row_ptr);
+}
+
+// ... and the band itself: preset to the fill in front of the launches, its diagonal behind the last of them, one contiguous copy of
+// row_ptr[n] floats; first and row_ptr are the host layout's.
+int twk_hip_ld_matrix_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                           int32_t stat, float fill, float* values, uint64_t capacity, uint32_t* first, uint64_t* row_ptr, uint64_t* n_records, uint64_t* n_pairs) {
+	ReduceCall call(c, Reduce::bandmat, f, values && first && row_ptr && valid_stat(stat) && (window & TWK_HIP_OPT_WINDOW), mode, a0, n);
+	if (call.bad) return call.bad;
+	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
+	std::vector<uint32_t> h_first(n);
+	std::vector<uint64_t> h_ptr((size_t)n + 1);
+	int rc = bandmat_layout(c, a0, n, l_window, h_first.data(), h_ptr.data()); if (rc) return rc;
+	const size_t cells = (size_t)h_ptr[n];
+	if (capacity < cells) {
+		snprintf(c->err, sizeof(c->err), "banded LD matrix: the band of %u variants holds %zu floats, the caller's array %llu", n, cells, (unsigned long long)capacity);
+		return TWK_HIP_E_INVALID;
+	}
+	std::vector<BandRow> rows(n);
+	for (uint32_t u = 0; u < n; ++u) rows[u] = BandRow{h_ptr[u], h_first[u], (uint32_t)(h_ptr[u + 1] - h_ptr[u])};
+	// the band: row_ptr[n] floats, and a BandRow per variant
+	rc = hold_for_call(c, call.d_band_rows, (size_t)n, "the band map of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	rc = call.hold(call.d_band, cells, "the banded LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
+	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)call.d_band.get(), (int)fill_bits, cells, c->s_compute));
+	// (from pageable memory: the copy has left `rows` when it returns; it lives to the end of the call anyway)
+	HIPCHK(c, hipMemcpyAsync(call.d_band_rows, rows.data(), (size_t)n * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
+	c->reduce.map.band = BandMap{call.d_band, call.d_band_rows, c->d_counts, a0, n, stat};
+	call.arm(cells * sizeof(float));
+	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
+	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
+		hipLaunchKernelGGL(k_ld_bandmat_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, call.d_band.get(), (const BandRow*)call.d_band_rows.get(), n, 1.0f);
+		HIPCHK(c, hipGetLastError());
+	}
+	unsigned long long count = 0;
+	rc = call.tail("banded LD matrix", [&] {
+		return hipMemcpyAsync(values, call.d_band, cells * sizeof(float), hipMemcpyDeviceToHost, c->s_compute);
+	}, [&] { return hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute); });
+	if (rc) return rc;
+	memcpy(first, h_first.data(), (size_t)n * sizeof(uint32_t));
+	memcpy(row_ptr, h_ptr.data(), ((size_t)n + 1) * sizeof(uint64_t));
+	if (n_records) *n_records = count;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_bandmat_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* band_bytes) { return last_of(c, Reduce::bandmat, copy_ms, band_bytes); }
 
 // LD decay: the bins' integer accumulators are zeroed in front of the launches and converted behind the last of them.
 int twk_hip_ld_decay(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,

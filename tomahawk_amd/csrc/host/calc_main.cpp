@@ -184,7 +184,7 @@ static int run_command(const Command<Own>& cmd, int argc, char** argv) {
 			switch (cmd.option ? cmd.option(c, optarg, settings, own) : declined) {
 			case took: break;
 			case failed: return 1;
-			case declined:      // (a long option without a letter - another command's --annot, --self - by its name)
+			case declined:      // (a long option without a letter - another command's --annot, --self, --band - by its name)
 				return !fail(std::string("Unrecognized option: ") + (c > 127 ? std::string("--") + cmd.long_options[option_index].name : std::string(1, (char)c)));
 			}
 		}
@@ -214,7 +214,7 @@ static const struct option REDUCE_LONG_OPTIONS[] = {
 	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
 	{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
-	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'},
+	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'}, {"band", no_argument, 0, 1003},
 	{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
 	{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
 	{0, 0, 0, 0}};
@@ -407,14 +407,21 @@ static Took matrix_option(int c, const char* arg, twk_ld_settings&, tomahawk::tw
 	case 's': return stat_option(arg, tomahawk::LD_STATS, matrix.stat) ? took : failed;
 	case 'f': return fill_option(arg, matrix.fill) ? took : failed;
 	case 'T': matrix.text = true; return took;
+	case 1003: matrix.band = true; return took;
 	}
 	return declined;
 }
+// (`ldmatrix --band -w INT`: the matrix in band storage, INTEGRATION section 1.  A long name only, and not in the usage text above: the usage and
+// every recorded invocation answer as they always have, tests/golden/cli_transcript.json.)
 static const Command<tomahawk::twk_matrix_settings> LDMATRIX = {
 	"ldmatrix", "  ldmatrix dense LD matrix of a region (signed r, r2, D or D'), filled on the GPU\n", ldmatrix_usage,
 	"i:o:t:puP:r:w:I:c:C:s:f:T?", REDUCE_LONG_OPTIONS, 0, {{"cC", "Cannot fill a part of the pair space (-c / -C): the matrix needs every pair"}},
 	"Cannot fill a matrix with a cutoff P-value below 1: the matrix holds every record and Fisher's exact test is not run", matrix_option,
-	[](twk_ld_settings& settings, tomahawk::twk_matrix_settings&) { return !(settings.out.empty() || settings.out == "-") || fail("No output prefix specified (-o)..."); },
+	[](twk_ld_settings& settings, tomahawk::twk_matrix_settings& matrix) {
+		if (matrix.band && !settings.window) return fail("--band stores the columns inside the window: it needs one (-w)");
+		if (matrix.band && matrix.text) return fail("--band has no text form (-T): it writes PREFIX.values.npy, PREFIX.indptr.npy and PREFIX.first.npy");
+		return !(settings.out.empty() || settings.out == "-") || fail("No output prefix specified (-o)...");
+	},
 	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_matrix_settings& matrix) { return ld.Matrix(settings, matrix); }};
 
 // `tomahawk relationship`: the sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU.  The reference's name and its -i / -I;

@@ -1082,11 +1082,12 @@ struct ReduceCommand {
 		}
 		return finish(os, text, "the matrix");
 	}
-	// A dense n x n matrix as a NumPy file, format 1.0: magic, version, a little-endian uint16 header length, the dictionary padded with
+	// An array as a NumPy file, format 1.0: magic, version, a little-endian uint16 header length, the dictionary padded with
 	// spaces and ended by a newline so that the data begins on a multiple of 64 bytes; C order (the hosts this runs on are little-endian).
-	// descr: "<f4", "<f8".  -> finish()
-	static bool npy(std::ostream& os, const char* descr, uint32_t n, const void* data, size_t bytes) {
-		std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" + std::to_string(n) + ", " + std::to_string(n) + "), }";
+	// descr: "<f4", "<f8", "<i4", "<i8".  rows x cols: a dense matrix, shape (rows, cols); cols == 0: a 1-D array, shape (rows,).
+	// -> finish()
+	static bool npy(std::ostream& os, const char* descr, uint64_t rows, uint64_t cols, const void* data, size_t bytes) {
+		std::string dict = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': (" + std::to_string(rows) + "," + (cols ? " " + std::to_string(cols) : std::string()) + "), }";
 		const size_t fixed = 6 + 2 + 2;
 		const size_t total = (fixed + dict.size() + 1 + 63) / 64 * 64;
 		dict.append(total - fixed - dict.size() - 1, ' ');
@@ -1538,18 +1539,43 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 	if (!cmd.begin(s, "The matrix holds every record", "Cannot fill a part of the pair space: the matrix needs every pair")) return false;
 	if (!LD_STATS.valid(ms.stat)) { std::cerr << stamp("ERROR") << "Unknown statistic: one of " << LD_STATS.list() << "..." << std::endl; return false; }
 	if (cmd.to_stdout()) { std::cerr << stamp("ERROR") << "No output prefix provided: the matrix and its variant list are files..." << std::endl; return false; }
+	if (ms.band && !settings.window) { std::cerr << stamp("ERROR") << "A banded matrix stores the columns inside the window: it needs one (-w)..." << std::endl; return false; }
+	if (ms.band && ms.text) { std::cerr << stamp("ERROR") << "A banded matrix has no text form..." << std::endl; return false; }
 	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
 	const uint32_t M = cmd.M;
-	std::vector<float> m((size_t)M * M);
-	uint64_t np = 0, n_recs = 0;
-	const double sec = cmd.call("twk_hip_ld_matrix", [&] { return twk_hip_ld_matrix(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np); }, &np);
-	if (sec < 0) return false;
-	mImpl->n_records = n_recs;
-
+	uint64_t np = 0, n_recs = 0, nnz = 0;
+	double sec = 0;
 	std::ofstream file, vfile;
-	if (!cmd.open(file, settings.out + (ms.text ? ".ld" : ".npy"), std::ios::binary)) return false;
-	if (!(ms.text ? cmd.dense_text(file, m.data(), M, ' ', 9, false) : cmd.npy(file, "<f4", M, m.data(), m.size() * sizeof(float)))) return false;
-	file.close();
+	if (ms.band) {
+		// the band: its layout first, which sizes the values; then the three arrays of a CSR matrix, each a NumPy file
+		if (M > 0x7FFFFFFFu) { std::cerr << stamp("ERROR") << "Too many variants for PREFIX.first.npy (int32)..." << std::endl; return false; }
+		std::vector<uint32_t> first(M);
+		std::vector<uint64_t> indptr((size_t)M + 1);
+		if (!hip_ok(cmd.ctx, twk_hip_bandmat_layout(cmd.ctx, 0, M, (uint32_t)settings.l_window, first.data(), indptr.data()), "twk_hip_bandmat_layout")) return false;
+		nnz = indptr[M];
+		std::vector<float> values((size_t)nnz);
+		sec = cmd.call("twk_hip_ld_matrix_band", [&] {
+			return twk_hip_ld_matrix_band(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, values.data(), nnz, first.data(), indptr.data(), &n_recs, &np);
+		}, &np);
+		if (sec < 0) return false;
+		const struct { const char* suffix; const char* descr; uint64_t items; const void* data; size_t bytes; } arrays[3] = {
+			{".values.npy", "<f4", nnz, values.data(), values.size() * sizeof(float)},
+			{".indptr.npy", "<i8", (uint64_t)M + 1, indptr.data(), indptr.size() * sizeof(uint64_t)},      // (below 2^63: the same bits)
+			{".first.npy", "<i4", M, first.data(), first.size() * sizeof(uint32_t)}};                       // (below 2^31)
+		for (const auto& a : arrays) {
+			if (!cmd.open(file, settings.out + a.suffix, std::ios::binary)) return false;
+			if (!cmd.npy(file, a.descr, a.items, 0, a.data, a.bytes)) return false;
+			file.close();
+		}
+	} else {
+		std::vector<float> m((size_t)M * M);
+		sec = cmd.call("twk_hip_ld_matrix", [&] { return twk_hip_ld_matrix(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np); }, &np);
+		if (sec < 0) return false;
+		if (!cmd.open(file, settings.out + (ms.text ? ".ld" : ".npy"), std::ios::binary)) return false;
+		if (!(ms.text ? cmd.dense_text(file, m.data(), M, ' ', 9, false) : cmd.npy(file, "<f4", M, M, m.data(), m.size() * sizeof(float)))) return false;
+		file.close();
+	}
+	mImpl->n_records = n_recs;
 	if (!cmd.open(vfile, settings.out + ".variants.tsv")) return false;
 	std::string text;
 	for (uint32_t v = 0; v < M; ++v) {
@@ -1558,7 +1584,7 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 		cmd.spill(vfile, text);
 	}
 	if (!cmd.finish(vfile, text, "the variant list")) return false;
-	std::cerr << stamp("LOG") << "Matrix of " << LD_STATS.name(ms.stat) << ": " << pretty(M) << " x " << pretty(M) << ", " << pretty(n_recs) << " pairs with a value among "
+	std::cerr << stamp("LOG") << "Matrix of " << LD_STATS.name(ms.stat) << ": " << pretty(M) << " x " << pretty(M) << (ms.band ? ", a band of " + pretty(nnz) + " entries" : std::string()) << ", " << pretty(n_recs) << " pairs with a value among "
 	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
 	cmd.all_done();
 	return true;
@@ -1584,7 +1610,7 @@ bool twk_ld::Relationship(const twk_ld_settings& s, const twk_relationship_setti
 	} else {
 		std::ofstream file, sfile;
 		if (!cmd.open(file, settings.out + (rs.text ? ".tsv" : ".npy"), std::ios::binary)) return false;
-		if (!(rs.text ? cmd.dense_text(file, m.data(), n, '\t', 17, true) : cmd.npy(file, "<f8", n, m.data(), m.size() * sizeof(double)))) return false;
+		if (!(rs.text ? cmd.dense_text(file, m.data(), n, '\t', 17, true) : cmd.npy(file, "<f8", n, n, m.data(), m.size() * sizeof(double)))) return false;
 		file.close();
 		if (!cmd.open(sfile, settings.out + ".samples.tsv")) return false;
 		std::string text;

@@ -222,6 +222,10 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_matrix.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                       C.c_int32, C.c_float, p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_matrix_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_bandmat_layout.argtypes = [p, C.c_uint32, C.c_uint32, C.c_uint32, p, p]
+    lib.twk_hip_ld_matrix_band.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
+                                           C.c_int32, C.c_float, p, C.c_uint64, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_bandmat_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_relationship.argtypes = [p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_double,
                                          p, C.c_uint64, p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.twk_hip_relationship_last.argtypes = [p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
@@ -303,6 +307,35 @@ def shard_rows(n_variants: int, part: int, n_parts: int, n_cols: int | None = No
     if rc != 0:
         raise HipError(rc, "twk_hip_shard_rows")
     return r0.value, r1.value, n.value
+
+
+def band_to_csr(values, first, indptr):
+    """The banded LD matrix (HipLd.ld_matrix_band, or `ldmatrix --band`'s three files) as the arrays of a CSR matrix of shape (n, n):
+    -> (data, indices int64[nnz], indptr int64[n + 1]); data is `values` itself - the band stores both orientations, row by row - and
+    row u's indices are first[u], first[u] + 1, ...  scipy.sparse.csr_matrix((data, indices, indptr), shape=(n, n)) takes them as
+    they are.  Plain NumPy."""
+    indptr = np.asarray(indptr).astype(np.int64)
+    first = np.asarray(first).astype(np.int64)
+    values = np.asarray(values)
+    n = len(first)
+    if len(indptr) != n + 1 or (n and indptr[0] != 0) or (np.diff(indptr) < 0).any() or int(indptr[-1]) != len(values):
+        raise ValueError("band_to_csr: first, indptr and values do not describe one band")
+    lens = np.diff(indptr)
+    row = np.repeat(np.arange(n, dtype=np.int64), lens)
+    indices = np.arange(len(values), dtype=np.int64) - indptr[:-1][row] + first[row]
+    return values, indices, indptr
+
+
+def band_to_dense(values, first, indptr, fill=0.0):
+    """The banded LD matrix scattered into a dense (n, n) array of values' dtype preset to `fill`: what HipLd.ld_matrix returns for the
+    same window and fill.  Plain NumPy; for tests and small regions - the band exists because the dense matrix does not fit."""
+    data, indices, indptr = band_to_csr(values, first, indptr)
+    n = len(indptr) - 1
+    if len(indices) and (indices.min() < 0 or indices.max() >= n):
+        raise ValueError("band_to_dense: a band reaches beyond the matrix")
+    out = np.full((n, n), fill, dtype=data.dtype)
+    out[np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr)), indices] = data
+    return out
 
 
 def words64(n_samples: int) -> int:
@@ -657,6 +690,42 @@ class HipLd:
         ms, b = C.c_double(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_matrix_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_matrix_last")
         return {"copy_ms": ms.value, "matrix_bytes": b.value}
+
+    def bandmat_layout(self, l_window: int, a0: int = 0, n: int | None = None):
+        """The banded LD matrix's layout (twk_hip_bandmat_layout) of the slice [a0, a0 + n) for a window of l_window base pairs, from
+        the uploaded metadata, on the host: row u stores the columns [first[u], first[u] + indptr[u + 1] - indptr[u]) - the variants
+        on u's contig within the window - from slot indptr[u] on; indptr[n] floats in all.
+        -> (first uint32[n], indptr uint64[n + 1])."""
+        n = self.n_variants - a0 if n is None else n
+        first = np.zeros(max(n, 0), dtype=np.uint32)
+        indptr = np.zeros(max(n, 0) + 1, dtype=np.uint64)
+        self._check(self._lib.twk_hip_bandmat_layout(self._ctx, a0, n, l_window, first.ctypes.data, indptr.ctypes.data), "twk_hip_bandmat_layout")
+        return first, indptr
+
+    def ld_matrix_band(self, mode: int, filters: Filters, l_window: int, stat: int = STAT_R, fill: float = 0.0, a0: int = 0,
+                       n: int | None = None, tile_variants: int = 0):
+        """The banded LD matrix (twk_hip_ld_matrix_band): ld_matrix with window=OPT_WINDOW and this l_window, in band storage - for
+        every in-band (u, v), values[indptr[u] + (v - first[u])] holds the bits of the dense matrix's entry (u, v); what the band does
+        not store is the dense matrix's fill.  Both orientations are stored (band_to_csr, band_to_dense).  filters.minP must be >= 1.
+        -> (values float32[indptr[n]], first uint32[n], indptr uint64[n + 1], n_records, n_pairs)."""
+        n = self.n_variants - a0 if n is None else n
+        _, layout_ptr = self.bandmat_layout(l_window, a0, n)          # (sizes `values`; refuses what the call would refuse about the slice)
+        nnz = int(layout_ptr[-1])
+        values = np.empty(nnz, dtype=np.float32)
+        first = np.zeros(n, dtype=np.uint32)
+        indptr = np.zeros(n + 1, dtype=np.uint64)
+        nrec, npairs = C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_matrix_band(self._ctx, mode, C.byref(f), a0, n, tile_variants, int(OPT_WINDOW), l_window, int(stat),
+                                                     C.c_float(fill), values.ctypes.data, nnz, first.ctypes.data, indptr.ctypes.data,
+                                                     C.byref(nrec), C.byref(npairs)), "twk_hip_ld_matrix_band")
+        return values, first, indptr, nrec.value, npairs.value
+
+    def bandmat_last(self) -> dict:
+        """Of the last ld_matrix_band call (twk_hip_bandmat_last): the device-to-host copy's time and the band's size."""
+        ms, b = C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_bandmat_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_bandmat_last")
+        return {"copy_ms": ms.value, "band_bytes": b.value}
 
     def relationship(self, stat: int = REL_KING, fill: float = float("nan"), variants=None, sA0: int = 0, nSA: int | None = None,
                      sB0: int = 0, nSB: int | None = None, want_counts: bool = False):
