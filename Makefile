@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check form-check bandmat-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check form-check bandmat-check topk-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -153,6 +153,14 @@ bandmat-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/bandmat_index_check.cpp -o build/bandmat_index_check
 	./build/bandmat_index_check
+
+# The top-k partners' key against the comparator of its definition, the cascade played step by step under random interleavings with stale
+# threshold reads, and the kernel's two levels (csrc/hip/ld_topk_key.h) against a sort (csrc/tools/topk_key_check.cpp): host code only,
+# under AddressSanitizer and UBSan
+topk-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/topk_key_check.cpp -o build/topk_key_check
+	./build/topk_key_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -42,6 +42,7 @@ extern "C" {
 /*    (still 5: twk_hip_relationship / twk_hip_relationship_last - the sample relationship matrix - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_score_annot - partitioned LD scores - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_bandmat_layout / twk_hip_ld_matrix_band / twk_hip_bandmat_last - the banded LD matrix - are three entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_topk / twk_hip_topk_last - top-k LD partners - are two entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -524,6 +525,40 @@ int twk_hip_ld_score_annot(twk_hip_ctx* ctx, int mode, const twk_hip_filters* fi
                            const double* annot, uint32_t n_annot, uint64_t ld_annot,
                            uint64_t* n_partners /*[n_variants]*/, double* score /*[n_variants * n_annot], row v at v * n_annot*/,
                            uint64_t* n_pairs);
+
+/* Top-k LD partners over the same slice of the pair space as twk_hip_ld_score, with the same arguments and the same pair set: for every
+ * variant its k strongest proxies - what LDlink's LDproxy, PLINK's --show-tags and --ld-snp, and proxy substitution for a variant missing
+ * from a summary-statistics file ask for.  With stat one of TWK_HIP_STAT_* and 1 <= k <= TWK_HIP_TOPK_MAX:
+ *   the PARTNERS of variant v are the variants w for which twk_hip_ld_region with these arguments would report a record for {v, w}: both
+ *                ends of a record count, as in the score, and the variant itself is no partner;
+ *   the VALUE of a partner is that record's statistic - signed r (R with D's sign), r2, D or D' - computed in double and rounded once to
+ *                float32: the bits twk_hip_ld_matrix writes at (v, w);
+ *   the LIST of v is its partners ordered by |value| descending, compared as float32; of two partners with the same |value| the one
+ *                with the smaller index in file order comes first (+x and -x tie); the list is cut at k.
+ *   idx          HOST array of n_variants * k entries, overwritten: row v at v * k, the partners' indices as uploaded
+ *   val          HOST array of n_variants * k floats, overwritten: their signed values
+ * Slots that are not used - fewer than k partners, a variant outside the slice - hold TWK_HIP_NO_PARTNER and +0.0f, behind the used ones.
+ * THE SELECTION IS EXACT AND HAS NO ORDER (ld_topk.hip.h, ld_topk_key.h): a candidate is one 64-bit integer key whose order is the
+ * list's, selected with integer atomic maxima; the same bytes for any tile_variants, any launch order and any repeat, and no
+ * floating-point atomic is used.  A shard (part / n_parts) returns the lists over its own pairs: the shards' lists merged under the
+ * same order and cut at k are the lists of the whole.
+ * filters.minP must be >= 1: Fisher's test is not run.  Always the matrix form of the contraction (TWK_HIP_OPT_R2_SCREEN is ignored, as
+ * for a score).  *n_pairs (may be NULL): pairs evaluated.  The context is left as it was.
+ * TWK_HIP_E_INVALID before any launch, with nothing written: minP < 1, a NULL array, k == 0 or k > TWK_HIP_TOPK_MAX, an unknown stat, and
+ * the region call's own argument errors; TWK_HIP_E_STATE before upload.  Device memory: k * 8 bytes per variant for the length of the
+ * call (531,500 variants at k = 16: 68 MB, where the dense matrix would need 1.13 TB); TWK_HIP_E_NOMEM with the size in
+ * twk_hip_last_error when the device cannot give it.  twk_hip_timing: the kernels count as the math stage (stats_ms, stats_launches,
+ * variant_pairs).  twk_hip_topk_last: the time from the last launch's end to the unpacked lists (the copy of the keys and their
+ * unpacking on the host) and the lists' bytes on the device, of the context's last twk_hip_ld_topk call.  There is NO reference
+ * counterpart. */
+#define TWK_HIP_TOPK_MAX 32
+#define TWK_HIP_NO_PARTNER 0xFFFFFFFFu
+int twk_hip_ld_topk(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                    uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                    uint32_t part, uint32_t n_parts, uint32_t tile_variants,
+                    int32_t window, uint32_t l_window,
+                    int32_t stat, uint32_t k, uint32_t* idx /*[n_variants * k]*/, float* val /*[n_variants * k]*/, uint64_t* n_pairs);
+int twk_hip_topk_last(const twk_hip_ctx* ctx, double* unpack_ms, uint64_t* list_bytes);
 
 /* The sample relationship matrix: sample by sample instead of variant by variant - what a cohort user computes before any LD, to find
  * duplicates and relatives.  The same AND + popcount contraction with the reduced axis turned round: the genotype matrix is transposed

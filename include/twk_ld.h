@@ -47,6 +47,8 @@ struct twk_ld_settings {
 struct twk_score_settings {
 	std::string annot;          // the annotation file: with it the scores are partitioned, one column per category; empty: the plain score
 	bool self = false;          // add the variant's own annotation to its partitioned scores (LDSC's convention, r2(v, v) = 1)
+	int32_t top = 0;            // > 0: in place of the scores, every variant's `top` strongest partners (1 .. TWK_HIP_TOPK_MAX; not with annot)
+	int32_t top_stat = -1;      // ... by the magnitude of this statistic (TWK_HIP_STAT_*; -1, not stated: r2)
 };
 
 // What Clump needs beyond twk_ld_settings.
@@ -121,6 +123,10 @@ public:
 	// same bits from run to run); score.self adds a[v][c] on the host.  Writes the `##` lines of Score, then ##annotations=C, ##M= and
 	// ##M_5_50= (the categories' sums over the selection, and over its variants with a minor allele frequency above 0.05), ##self=1 with
 	// score.self, and per variant contig, position, n_partners and the C scores with 17 significant digits.
+	// With score.top = K > 0 (and no score.annot) the output is instead every variant's K strongest partners - proxy lookup - selected on one
+	// GPU (twk_hip_ld_topk: |score.top_stat| descending as float32, ties to the partner earlier in the file): the `##` lines of Score, ##top=K,
+	// ##stat=, with -c / -C a ##shard= line (the lists then hold the partners among that part's pairs only), and per variant and rank
+	// contig, position, rank (from 1), the partner's contig and position, and the signed value with 9 significant digits.
 	bool Score(const twk_ld_settings& settings, const twk_score_settings& score);
 	// Not in the reference: greedy LD pruning in file order (PLINK's --indep-pairwise).  Loads the .twk exactly as Compute does (-I intervals,
 	// -w, -p / -u, TWK_REF_COMPAT; the whole pair space: -c / -C are refused, the walk needs every pair) and writes one text line per

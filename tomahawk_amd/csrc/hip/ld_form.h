@@ -7,10 +7,10 @@
 
 namespace twk {
 
-// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot or _matrix_band runs: it looks at
-// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the eight kernels share).
-enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot, bandmat };
-constexpr int N_REDUCE = (int)Reduce::bandmat + 1;
+// The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band or _topk runs: it looks at
+// every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the nine kernels share).
+enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot, bandmat, topk };
+constexpr int N_REDUCE = (int)Reduce::topk + 1;
 // The form of a launch, decided once (decide_form) and passed down: which count kernel, which math behind it.
 struct LaunchForm {
 	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first

@@ -1,5 +1,5 @@
-// What the eight epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
-// ld_matrix.hip.h, ld_decay.hip.h, ld_aggregate.hip.h, ld_score_annot.hip.h, ld_bandmat.hip.h; launch_reduce in twk_hip.hip): the shape of a kernel and the toolkit it is built from.
+// What the nine epilogues that reduce a count matrix instead of keeping records share (ld_score.hip.h, ld_prune.hip.h, ld_clump.hip.h,
+// ld_matrix.hip.h, ld_decay.hip.h, ld_aggregate.hip.h, ld_score_annot.hip.h, ld_bandmat.hip.h, ld_topk.hip.h; launch_reduce in twk_hip.hip): the shape of a kernel and the toolkit it is built from.
 //
 // THE SHAPE.  A block is 256 lanes = 256 columns of the launch and walks a fixed number of its rows (32; clump 64; annot 16) in a loop that is not
 // unrolled.  A lane's pair goes through d_pair<SRC_MATRIX> (ld_math.hip.h) with the launch's StatsParams - the pair rules, the regrouped
@@ -7,7 +7,7 @@
 // the two maths are then the callee's and are not held across the row loop (inlined, k_ld_score needs 191 VGPRs: two waves a SIMD).
 // The PARAMETER BLOCK lives in device memory and the kernel takes a pointer to it: as a kernel argument it is held in ~170 scalar
 // registers across the loop and spilled into vector registers (206 VGPRs; the same finding as k_ld_stats_list's).  A block that lies
-// wholly on or below the diagonal of a diagonal launch has no pair (the banded matrix also knows the blocks wholly outside its band).  What a kernel does with `keep` - sum, ballot, store, bin - is its own.
+// wholly on or below the diagonal of a diagonal launch has no pair (the banded matrix also knows the blocks wholly outside its band).  What a kernel does with `keep` - sum, ballot, store, bin, select - is its own.
 //
 // THE TOOLKIT.  A new kind is one kernel file built from these, plus one entry point:
 //   ReduceParams<Map>  the parameter block {p, m}: the launch's StatsParams and the kind's map.  Every kind derives its own, by name.
@@ -18,7 +18,8 @@
 //   d_or_bits, d_block_dead
 // WHAT STAYS PER KIND.  The pair function: each returns its own small result in registers and the record stays local to the callee (a
 // shared one that returned the record would pass 104 bytes through memory), so d_stat_value is inlined INTO those out-of-line bodies.
-// The row loop: the eight carry different state across rows (clump's column word, the matrix's and the band's LDS stage, score's partials, annot's parked r2).
+// The row loop: the nine carry different state across rows (clump's column word, the matrix's and the band's LDS stage, score's partials, annot's parked r2,
+// top-k's LDS lists).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

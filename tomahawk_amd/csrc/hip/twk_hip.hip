@@ -15,7 +15,8 @@
 //   bandmat (ld_bandmat.hip.h) cells -> one statistic of the pair's record -> the entries (u, v) and (v, u) of a banded float32 matrix: per row only the columns inside the window (twk_hip_ld_matrix_band)
 //   relate (ld_relate.hip.h) the raw layout transposed into planes of the samples -> count -> genotype-sharing counts and one statistic per sample pair
 //                          (twk_hip_relationship: its own launches, beside the variant launch path)
-//   (score, prune, clump, matrix, decay, aggregate, annot and bandmat are the eight kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
+//   topk (ld_topk.hip.h) cells -> one statistic of the pair's record -> a 64-bit key -> the k largest per variant, selected with integer atomic maxima (twk_hip_ld_topk)
+//   (score, prune, clump, matrix, decay, aggregate, annot, bandmat and topk are the nine kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -54,6 +55,7 @@
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
 #include "ld_bandmat.hip.h"
+#include "ld_topk.hip.h"
 #include "ld_relate.hip.h"
 #include "ld_plan.h"
 #include "ld_form.h"
@@ -130,7 +132,7 @@ constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
 // What the running call of one of them sets, for its length: ~ReduceCall puts a default-constructed one back.
 struct ReduceState {
 	Reduce kind = Reduce::none;
-	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; BandMap band; } map{};      // where the running kind's launches put their results (prune and clump: bits)
+	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; BandMap band; TopkMap topk; } map{};      // where the running kind's launches put their results (prune and clump: bits)
 	uint64_t work = 0;                            // what the call's launches used up of the room of the kind's accumulators (launch_reduce holds it to the kind's limit)
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
@@ -158,7 +160,7 @@ struct Launch {
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
-union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; BandArgs bandmat; };
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; BandArgs bandmat; TopkArgs topk; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -298,7 +300,7 @@ struct twk_hip_ctx {
 	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
 	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
-	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last, twk_hip_bandmat_last)
+	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last, twk_hip_bandmat_last, twk_hip_topk_last)
 	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
 	// score: sums of r2 per variant (ld_score.hip.h)
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
@@ -773,6 +775,7 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	case Reduce::aggregate: return run_reduce_kernel(c, t, s, which, k_ld_aggregate, AGG_THREADS, AGG_ROWS, AggArgs{{p, rs.map.agg}});
 	case Reduce::annot:     return run_reduce_kernel(c, t, s, which, k_ld_annot, ANNOT_THREADS, ANNOT_ROWS, AnnotArgs{{p, rs.map.annot}});      // (no work limit: ld_score_annot.hip.h)
 	case Reduce::bandmat:   return run_reduce_kernel(c, t, s, which, k_ld_bandmat_fill, BANDMAT_THREADS, BANDMAT_ROWS, BandArgs{{p, rs.map.band}});
+	case Reduce::topk:      return run_reduce_kernel(c, t, s, which, k_ld_topk, TOPK_THREADS, TOPK_BLOCK_ROWS, TopkArgs{{p, rs.map.topk}}, tk_lds_bytes(rs.map.topk.k));      // (no work limit: a selection has no headroom to use up)
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -2308,8 +2311,8 @@ int hold_for_call(twk_hip_ctx* c, DevBuf<T>& b, size_t items, const char* what, 
 struct ReduceCall {
 	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
 	int bad;
-	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums, the band and its map.  Freed behind the destructor's body, which waits for the device.
-	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc; DevBuf<float> d_matrix, d_band; DevBuf<double> d_annot; DevBuf<BandRow> d_band_rows;
+	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums, the band and its map, the top-k lists.  Freed behind the destructor's body, which waits for the device.
+	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc, d_topk; DevBuf<float> d_matrix, d_band; DevBuf<double> d_annot; DevBuf<BandRow> d_band_rows;
 	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
 	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
 		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
@@ -2593,6 +2596,37 @@ int twk_hip_ld_matrix_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 }
 
 int twk_hip_bandmat_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* band_bytes) { return last_of(c, Reduce::bandmat, copy_ms, band_bytes); }
+
+// Top-k LD partners: the lists' slots are zeroed in front of the launches; behind the last of them the keys are copied out and unpacked
+// on the host, a slab of variants at a time - 8 bytes per slot leave the device whoever unpacks.
+int twk_hip_ld_topk(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
+                    uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
+                    int32_t stat, uint32_t k, uint32_t* idx, float* val, uint64_t* n_pairs) {
+	ReduceCall call(c, Reduce::topk, f, idx && val && k >= 1 && k <= TOPK_MAX && valid_stat(stat), mode, a0, nA);
+	if (call.bad) return call.bad;
+	const size_t M = c->M, slots = M * k;
+	int rc = hold_for_call(c, call.d_topk, slots, "the top-k lists of %u variants need %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	// (beyond 64 KiB of dynamic LDS a kernel has to be told so; k = 32 asks for 72 KiB)
+	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ld_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tk_lds_bytes(TOPK_MAX)));
+	HIPCHK(c, hipMemsetAsync(call.d_topk, 0, slots * sizeof(unsigned long long), c->s_compute));
+	c->reduce.map.topk = TopkMap{call.d_topk, k, stat};
+	call.arm(slots * sizeof(unsigned long long));
+	if (triangle && nA < 2) { if (n_pairs) *n_pairs = 0; }      // (a single variant has no pair)
+	else { rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs); if (rc) return rc; }
+	const auto t0 = std::chrono::steady_clock::now();
+	const size_t slab = std::min<size_t>(slots, (size_t)1 << 21);      // 16 MiB of keys at a time
+	std::vector<unsigned long long> keys(slab);
+	for (size_t at = 0; at < slots; at += slab) {
+		const size_t m = std::min(slab, slots - at);
+		rc = call.download("top-k lists", [&] { return hipMemcpyAsync(keys.data(), call.d_topk + at, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute); });
+		if (rc) return rc;
+		for (size_t e = 0; e < m; ++e) tk_unpack(keys[e], idx + at + e, val + at + e);
+	}
+	c->reduce_last[(int)Reduce::topk].ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	return TWK_HIP_OK;
+}
+
+int twk_hip_topk_last(const twk_hip_ctx* c, double* unpack_ms, uint64_t* list_bytes) { return last_of(c, Reduce::topk, unpack_ms, list_bytes); }
 
 // LD decay: the bins' integer accumulators are zeroed in front of the launches and converted behind the last of them.
 int twk_hip_ld_decay(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,

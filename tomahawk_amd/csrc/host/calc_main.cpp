@@ -184,7 +184,7 @@ static int run_command(const Command<Own>& cmd, int argc, char** argv) {
 			switch (cmd.option ? cmd.option(c, optarg, settings, own) : declined) {
 			case took: break;
 			case failed: return 1;
-			case declined:      // (a long option without a letter - another command's --annot, --self, --band - by its name)
+			case declined:      // (a long option without a letter - another command's --annot, --self, --band, --top - by its name)
 				return !fail(std::string("Unrecognized option: ") + (c > 127 ? std::string("--") + cmd.long_options[option_index].name : std::string(1, (char)c)));
 			}
 		}
@@ -215,6 +215,7 @@ static const struct option REDUCE_LONG_OPTIONS[] = {
 	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
 	{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
 	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'}, {"band", no_argument, 0, 1003},
+	{"top", required_argument, 0, 1004}, {"top-stat", required_argument, 0, 1005},
 	{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
 	{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
 	{0, 0, 0, 0}};
@@ -268,11 +269,26 @@ static void ldscore_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
+// (`ldscore --top K [--top-stat r2|r|D|Dprime]`, likewise long names only and not in the usage text: every variant's K strongest partners,
+// INTEGRATION section 1)
 // ... and `ldscore --annot FILE [--self]`: the scores partitioned by annotation category.  Long names only, and not in
 // the usage text above: `ldscore -a`, `ldscore --assoc` and the usage itself answer as they always have (tests/golden/cli_transcript.json).
 static Took ldscore_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_score_settings& score) {
 	if (c == 1002) { score.annot = arg; return took; }
 	if (c == 1001) { score.self = true; return took; }
+	if (c == 1004) {      // --top K: the K strongest partners of every variant in place of the scores
+		char* end = nullptr;
+		const long k = strtol(arg, &end, 10);
+		if (end == arg || *end || k < 1 || k > TWK_HIP_TOPK_MAX) return fail(std::string("The number of partners to list (--top) must be an integer between 1 and ") + std::to_string(TWK_HIP_TOPK_MAX) + ": " + arg) ? took : failed;
+		score.top = (int32_t)k;
+		return took;
+	}
+	if (c == 1005) {      // --top-stat: what the partners are ranked by
+		const int32_t v = tomahawk::LD_STATS.value(arg);
+		if (v < 0) return fail(std::string("Unknown statistic (--top-stat): ") + arg + " - one of " + tomahawk::LD_STATS.list()) ? took : failed;
+		score.top_stat = v;
+		return took;
+	}
 	return declined;
 }
 
@@ -280,7 +296,11 @@ static const Command<tomahawk::twk_score_settings> LDSCORE = {
 	"ldscore", "  ldscore  per-variant LD scores (sums of r2 over a variant's partners), reduced on the GPU\n", ldscore_usage,
 	"i:o:t:puP:r:w:I:c:C:?", REDUCE_LONG_OPTIONS, 0, {},
 	"Cannot score with a cutoff P-value below 1: a score sums over every record and Fisher's exact test is not run", ldscore_option,
-	[](twk_ld_settings&, tomahawk::twk_score_settings& score) { return !score.self || !score.annot.empty() || fail("--self needs an annotation file (--annot)"); },
+	[](twk_ld_settings&, tomahawk::twk_score_settings& score) {
+		if (score.top_stat >= 0 && !score.top) return fail("--top-stat needs a number of partners to list (--top)");
+		if (score.top && !score.annot.empty()) return fail("--top lists partners and takes no annotation file (--annot)");
+		return !score.self || !score.annot.empty() || fail("--self needs an annotation file (--annot)");
+	},
 	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_score_settings& score) { return ld.Score(settings, score); }};
 
 // `tomahawk prune` (not in the reference): greedy LD pruning in file order over the records `calc` would write, decided on the GPU.

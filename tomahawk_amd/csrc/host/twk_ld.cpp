@@ -1182,6 +1182,9 @@ bool twk_ld::Score(const twk_ld_settings& s, const twk_score_settings& ss) {
 	ReduceCommand cmd(settings, *mImpl);
 	if (!cmd.begin(s, "A score sums over every record", nullptr)) return false;
 	const bool annotated = !ss.annot.empty();
+	if (ss.top < 0 || ss.top > TWK_HIP_TOPK_MAX) { std::cerr << stamp("ERROR") << "The number of partners to list (--top) must be between 1 and " << TWK_HIP_TOPK_MAX << "..." << std::endl; return false; }
+	const int32_t top_stat = ss.top_stat < 0 ? (int32_t)TWK_HIP_STAT_R2 : ss.top_stat;
+	if (ss.top > 0 && (annotated || !LD_STATS.valid(top_stat))) { std::cerr << stamp("ERROR") << "--top lists partners by one of " << LD_STATS.list() << " and takes no annotation file..." << std::endl; return false; }
 	if (ss.self && !annotated) { std::cerr << stamp("ERROR") << "--self adds a variant's own annotation to its partitioned scores: it needs an annotation file (--annot)..." << std::endl; return false; }
 	AnnotFile af;
 	std::vector<twk_hip_variant_meta> meta;
@@ -1253,6 +1256,40 @@ bool twk_ld::Score(const twk_ld_settings& s, const twk_score_settings& ss) {
 		}
 		if (!cmd.finish(*os, text, "the scores")) return false;
 		std::cerr << stamp("LOG") << "Scored " << pretty(M) << " variants in " << pretty(C) << " categories over " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+		cmd.all_done();
+		return true;
+	}
+	if (ss.top > 0) {
+		// the k strongest partners of every variant (twk_hip_ld_topk): selected on the GPU, one line per variant and rank
+		const uint32_t K = (uint32_t)ss.top;
+		std::vector<uint32_t> idx((size_t)M * K, TWK_HIP_NO_PARTNER);
+		std::vector<float> val((size_t)M * K, 0.0f);
+		uint64_t np = 0;
+		const auto g = cmd.geometry();
+		const double sec = cmd.call("twk_hip_ld_topk", [&] {
+			return !g.pairs ? TWK_HIP_OK : twk_hip_ld_topk(cmd.ctx, cmd.mode, &cmd.f, g.a0, g.nA, g.b0, g.nB, g.triangle, 0, 1, 0, cmd.options, (uint32_t)settings.l_window,
+			                                                top_stat, K, idx.data(), val.data(), &np);
+		}, &np);
+		if (sec < 0) return false;
+		std::ostream* const os = cmd.open_text();
+		if (!os) return false;
+		cmd.header(*os, "ldscore");
+		std::string text = "##top=" + std::to_string(K) + "\n##stat=" + LD_STATS.name(top_stat) + "\n";
+		if (settings.n_chunks != 1)
+			text += "##shard=" + std::to_string(settings.c_chunk + 1) + "/" + std::to_string(settings.n_chunks) + ": the lists hold the partners among this part's pairs only; the parts' lists merge into the whole's\n";
+		text += "#contig\tpos\trank\tpartner_contig\tpartner_pos\tvalue\n";
+		char num[64];
+		uint64_t n_listed = 0;
+		for (uint32_t v = 0; v < M; ++v)
+			for (uint32_t r = 0; r < K && idx[(size_t)v * K + r] != TWK_HIP_NO_PARTNER; ++r, ++n_listed) {
+				cmd.place(text, v);
+				snprintf(num, sizeof(num), "\t%u\t", r + 1); text += num;
+				cmd.place(text, idx[(size_t)v * K + r]);
+				snprintf(num, sizeof(num), "\t%.9g\n", (double)val[(size_t)v * K + r]); text += num;
+				cmd.spill(*os, text);
+			}
+		if (!cmd.finish(*os, text, "the partner lists")) return false;
+		std::cerr << stamp("LOG") << "Listed " << pretty(n_listed) << " partners of " << pretty(M) << " variants over " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
 		cmd.all_done();
 		return true;
 	}

@@ -19,6 +19,8 @@ MODE_PHASED, MODE_UNPHASED, MODE_AUTO = 1, 2, 3
 # option bits of twk_hip_tile_desc.window / the `window` argument of ld_all / ld_region (TWK_HIP_OPT_*)
 OPT_WINDOW, OPT_KEEP_LOW_AC, OPT_REF_COMPAT, OPT_R2_SCREEN = 1, 2, 4, 8
 NO_CLUMP = 0xFFFFFFFF      # TWK_HIP_NO_CLUMP: ld_clump's index_of for a variant in no clump
+NO_PARTNER = 0xFFFFFFFF    # TWK_HIP_NO_PARTNER: ld_topk's idx for a slot that is not used
+TOPK_MAX = 32              # TWK_HIP_TOPK_MAX
 STAT_R, STAT_R2, STAT_D, STAT_DPRIME = 0, 1, 2, 3      # TWK_HIP_STAT_*: the statistic ld_matrix fills in
 REL_IBS, REL_IBS0, REL_KING = 0, 1, 2      # TWK_HIP_REL_*: the statistic relationship fills in
 E_OVERFLOW = -4
@@ -226,6 +228,10 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_matrix_band.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                            C.c_int32, C.c_float, p, C.c_uint64, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_bandmat_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_topk.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                    C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
+                                    C.POINTER(C.c_uint64)]
+    lib.twk_hip_topk_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_relationship.argtypes = [p, p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_double,
                                          p, C.c_uint64, p, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.twk_hip_relationship_last.argtypes = [p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
@@ -336,6 +342,31 @@ def band_to_dense(values, first, indptr, fill=0.0):
     out = np.full((n, n), fill, dtype=data.dtype)
     out[np.repeat(np.arange(n, dtype=np.int64), np.diff(indptr)), indices] = data
     return out
+
+
+def _topk_keys(idx, val):
+    """ld_topk's lists as the 64-bit keys whose unsigned order is the lists' order (csrc/hip/ld_topk_key.h); 0 for a slot not used."""
+    idx = np.ascontiguousarray(idx, dtype=np.uint32)
+    bits = np.ascontiguousarray(val, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    key = (bits & np.uint64(0x7FFFFFFF)) << np.uint64(33) | (~idx).astype(np.uint64) << np.uint64(1) | bits >> np.uint64(31)
+    return np.where(idx == np.uint32(NO_PARTNER), np.uint64(0), key)
+
+
+def topk_merge(lists, k: int):
+    """The lists of several ld_topk calls over disjoint pair sets - shards (part / n_parts), regions - merged into the lists of their
+    union: per variant the entries of all of them under ld_topk's order (|value| as float32 descending, ties to the smaller partner
+    index), cut at k, padded with (NO_PARTNER, +0.0).  lists: (idx, val) pairs, each (M, k_i).  Plain NumPy.
+    -> (idx uint32[M, k], val float32[M, k])."""
+    keys = np.concatenate([_topk_keys(i, v) for i, v in lists], axis=1)
+    keys = np.sort(keys, axis=1)[:, ::-1]
+    if keys.shape[1] < k:
+        keys = np.concatenate([keys, np.zeros((keys.shape[0], k - keys.shape[1]), dtype=np.uint64)], axis=1)
+    keys = np.ascontiguousarray(keys[:, :k])
+    used = keys != 0
+    idx = np.where(used, ~(keys >> np.uint64(1)).astype(np.uint32), np.uint32(NO_PARTNER)).astype(np.uint32)
+    bits = ((keys >> np.uint64(33)).astype(np.uint32) | ((keys & np.uint64(1)).astype(np.uint32) << np.uint32(31)))
+    val = np.where(used, bits, np.uint32(0)).astype(np.uint32).view(np.float32)
+    return idx, val
 
 
 def words64(n_samples: int) -> int:
@@ -726,6 +757,35 @@ class HipLd:
         ms, b = C.c_double(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_bandmat_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_bandmat_last")
         return {"copy_ms": ms.value, "band_bytes": b.value}
+
+    def ld_topk(self, mode: int, filters: Filters, k: int, stat: int = STAT_R2, a0: int = 0, nA: int | None = None, b0: int = 0,
+                nB: int | None = None, triangle: bool = True, part: int = 0, n_parts: int = 1, tile_variants: int = 0, window: int = 0,
+                l_window: int = 0):
+        """Top-k LD partners (twk_hip_ld_topk): for every variant the k partners with the largest |stat| among the records ld_region
+        would report with the variant at either end - the value a float32 (the double rounded once: ld_matrix's bits), the order
+        |value| descending, ties to the smaller partner index - selected on the device with integer atomic maxima: the same bytes for
+        any tiling, order or repeat.  Slots not used hold (NO_PARTNER, +0.0).  1 <= k <= 32; filters.minP must be >= 1.  A shard
+        returns the lists over its own pairs (topk_merge joins them).
+        -> (idx uint32[M, k], val float32[M, k], n_pairs)."""
+        M = self.n_variants
+        nA = M - a0 if nA is None else nA
+        nB = M - b0 if nB is None else nB
+        kk = max(int(k), 0)
+        idx = np.full((M, kk), NO_PARTNER, dtype=np.uint32)
+        val = np.zeros((M, kk), dtype=np.float32)
+        npairs = C.c_uint64(0)
+        f = filters._c()
+        # (a k the engine refuses is the engine's to refuse: it writes nothing before it has)
+        self._check(self._lib.twk_hip_ld_topk(self._ctx, mode, C.byref(f), a0, nA, b0, nB, int(bool(triangle)), part, n_parts, tile_variants,
+                                              int(window), l_window, int(stat), int(k), idx.ctypes.data, val.ctypes.data, C.byref(npairs)),
+                    "twk_hip_ld_topk")
+        return idx, val, npairs.value
+
+    def topk_last(self) -> dict:
+        """Of the last ld_topk call (twk_hip_topk_last): the time from the last launch's end to the unpacked lists, and the lists' size on the device."""
+        ms, b = C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_topk_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_topk_last")
+        return {"unpack_ms": ms.value, "list_bytes": b.value}
 
     def relationship(self, stat: int = REL_KING, fill: float = float("nan"), variants=None, sA0: int = 0, nSA: int | None = None,
                      sB0: int = 0, nSB: int | None = None, want_counts: bool = False):
