@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check annot-check form-check bandmat-check topk-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -130,6 +130,15 @@ two-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/two_check.cpp -o build/two_check
 	./build/two_check tests/golden/count_tables_two.json
+
+# The prefix contraction's host side (csrc/tools/prefix_check.cpp): its screens (csrc/hip/ld_two_screen.h) over every pair of a small prefix and a
+# small suffix genotype table, the work table with per-tile stops (csrc/hip/ld_count_table.h) against a naive restatement and against the table
+# built without stops, and the planner's stops (csrc/hip/ld_plan.h) on the headline's frequency law: host code only, under AddressSanitizer
+# and UBSan
+prefix-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/prefix_check.cpp -o build/prefix_check
+	./build/prefix_check
 
 # The partitioned LD score's term, its split width and the block's index arithmetic (csrc/hip/ld_annot_term.h) against llrint, the exact
 # sums' checks (csrc/tools/exact_sum_check.h) and a whole block played on the host (csrc/tools/annot_term_check.cpp): host code only,

@@ -761,6 +761,12 @@ typedef struct {
 	                                 against the column variants' H and Q rows.  Their row_pairs are the plane-row pairs they really
 	                                 contracted - one row x two rows per variant pair - and they are no part of three_launches /
 	                                 three_row_pairs                                                                          */
+	uint64_t prefix_launches;     /* (appended likewise) Two- and three-product launches that contracted their tiles over a prefix of the rows
+	                                  and whose candidate list held - one that flooded and was redone over whole rows is not counted.  They stay part of two_launches / three_launches, and their row_pairs / three_row_pairs
+	                                 count full-row equivalents: plane-row pairs x chunks contracted / chunks per row, summed over the
+	                                 tiles and rounded down once per launch - so that row_pairs x words_per_row stays the work executed */
+	uint64_t prefix_chunks;       /* K chunks those launches' tiles were contracted over ...                                   */
+	uint64_t prefix_chunks_full;  /* ... and what whole rows would have been                                                   */
 } twk_hip_timing;
 /* Progress of twk_hip_ld_all / twk_hip_ld_region: `cb` runs on the calling thread after every tile
  * with the variant pairs finished so far in the current call and the tile counts.  Replaces the
@@ -786,6 +792,11 @@ typedef struct {
 	                                 5 two products -> matrix (row variants' H planes x column variants' H, Q) */
 	uint32_t outlier;             /* != 0: flagged by the watch                                                */
 	uint32_t _pad;
+	/* Appended behind the ABI 5 layout with TWK_HIP_ABI_VERSION still 5 (existing callers' checks pin it): the entry grew, so the stride of the
+	 * array twk_hip_launch_log fills changed - a caller compiled against the older header would misread every entry after the first and must be
+	 * rebuilt; the version check does not catch it (only this library's own binding, built with it, reads the log). */
+	uint64_t prefix_chunks;       /* a prefix launch: K chunks its tiles were contracted over ... (else 0)      */
+	uint64_t prefix_chunks_full;  /* ... and what whole rows would have been; row_pairs is scaled by their ratio            */
 } twk_hip_launch_stat;
 /* Copies the most recent min(capacity, launches kept) entries, oldest first; *n_total: launches seen since the reset. */
 int twk_hip_launch_log(twk_hip_ctx* ctx, twk_hip_launch_stat* out, uint32_t capacity, uint32_t* n_copied, uint64_t* n_total);

@@ -765,7 +765,9 @@ __device__ __forceinline__ void count_list_body(const CountWork& w, const Epilog
 			const uint32_t yx = tile_yx;
 			if (EXPERIMENT != 6) {      // (6: the dev tool's no-epilogue timing)
 				const uint32_t ln = META ? fresh_lane() : (uint32_t)lane;
-				epilogue(acc, yx, wr, wc, (int)(ln >> 3), (int)(ln & 7u), (int)ln, seg_c0 == 0 && c_end == nchunks, meta, window);
+				// the unit holds the tile's whole count: all of the row, or all of the range a stopped tile is contracted over (UNIT_WHOLE, ld_count_table.h)
+				const bool whole = (seg_c0 == 0 && c_end == nchunks) || (tile & UNIT_WHOLE) != 0;
+				epilogue(acc, yx, wr, wc, (int)(ln >> 3), (int)(ln & 7u), (int)ln, whole, meta, window);
 			}
 			if (META) lane_offsets(true);
 			if (!more) {
@@ -856,6 +858,11 @@ struct ScreenWork {
 	// a padding row: no pair of it can pass the exact test (its D is exactly 0), and +inf keeps it from passing this one.
 	const float4* terms;
 	float slack;                       // 0.5 + T 2^-20 counts: four times the worst rounding of the prefilter's left side
+	// A prefix launch (the matrix screens of ld_three.hip.h only): pre_stops[ty * pre_gx + tx] = the grid index (ld_two_screen.h
+	// prefix_stop_chunks) of the stop of the tile that holds row variant i = ty * pre_tvA + .. and column variant j = tx * 64 + ..; pre_suffix
+	// [plane row][PREFIX_GRID]: the rows' suffix popcounts (k_row_suffix_popcount).  pre_stops == null: every tile over its whole rows.
+	const uint8_t* pre_stops; const uint32_t* pre_suffix;
+	uint32_t pre_gx, pre_tvA, pre_nchunks;
 };
 // -> terms[] of ScreenWork for n_pos set positions (P = 1: rowpop[pos]; P = 2: rowpop[2 pos] + 2 rowpop[2 pos + 1])
 __global__ void k_screen_terms(const uint32_t* __restrict__ rowpop, uint32_t n_pos, int P, double two_n, double cut, float4* __restrict__ terms) {

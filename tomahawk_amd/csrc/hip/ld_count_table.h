@@ -21,6 +21,10 @@ inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
 struct CountUnit { uint32_t tile, c0, c1, yx; };       // chunks [c0, c1) of tiles[tile]; yx = tiles[tile], so that a block learns everything about its
                                                        // next unit from one 16-byte scalar load (fill_unit_tiles) instead of two dependent ones
+// Set in CountUnit::tile of a unit that holds the whole count of a tile whose contraction stops short of the row's end (per-tile stops, the
+// prefix contraction of DESIGN 3.1c): the kernel's epilogue stores such a unit's counts like those of a unit over [0, nchunks).  Never set
+// in a table built without stops.
+constexpr uint32_t UNIT_WHOLE = 0x80000000u;
 
 // The unit table of a launch (host side; shared by the engine and the dev tools).  Guided self-scheduling:
 // a unit is never longer than 1/share_div of an even share of the work still to be handed out, so whole
@@ -40,12 +44,17 @@ struct CountUnit { uint32_t tile, c0, c1, yx; };       // chunks [c0, c1) of til
 template <class Vec>
 inline uint32_t build_count_units(uint32_t n_tiles, uint32_t nchunks, uint32_t n_blocks, uint32_t min_chunks, Vec& units,
                                   uint32_t share_div = 8, uint32_t tail_rounds = 8,
-                                  const uint32_t* patch_end = nullptr, uint32_t n_patches = 0, uint32_t seg_chunks = 0) {
+                                  const uint32_t* patch_end = nullptr, uint32_t n_patches = 0, uint32_t seg_chunks = 0, const uint32_t* stops = nullptr) {
 	units.clear();
+	// stops (may be null; the segmented walk is not taken with them): tile t of the list is contracted over the chunks [0, stops[t]) only,
+	// 1 <= stops[t] <= nchunks - without stops every tile's stop is nchunks.  Whole-tile units cover [0, stop), the guided tail sizes its
+	// units by the chunks really left - the sum of the stops - and a split tile's units partition [0, stop).
+	auto stop_of = [&](uint32_t t) -> uint32_t { return !stops ? nchunks : stops[t] < 1 ? 1 : (stops[t] > nchunks ? nchunks : stops[t]); };
+	auto flag_of = [&](uint32_t stop) -> uint32_t { return stop < nchunks ? UNIT_WHOLE : 0u; };      // (a unit that holds a stopped tile's whole count)
 	const uint32_t tail = (uint32_t)(n_tiles < (unsigned long long)tail_rounds * n_blocks ? n_tiles : (unsigned long long)tail_rounds * n_blocks);
 	uint32_t first_split = n_tiles - tail;
 	if (nchunks < 2 * min_chunks) first_split = n_tiles;             // rows too short to be worth splitting
-	const bool segmented = seg_chunks && patch_end && n_patches && nchunks >= 2 * seg_chunks && nchunks >= 2 * min_chunks;
+	const bool segmented = !stops && seg_chunks && patch_end && n_patches && nchunks >= 2 * seg_chunks && nchunks >= 2 * min_chunks;
 	if (segmented) {
 		const uint32_t nseg = (nchunks + seg_chunks - 1) / seg_chunks;
 		uint32_t p0 = 0;
@@ -57,24 +66,27 @@ inline uint32_t build_count_units(uint32_t n_tiles, uint32_t nchunks, uint32_t n
 			p0 = p1;
 		}
 	} else {
-		for (uint32_t t = 0; t < first_split; ++t) units.push_back(CountUnit{t, 0, nchunks, 0});
+		for (uint32_t t = 0; t < first_split; ++t) units.push_back(CountUnit{t | flag_of(stop_of(t)), 0, stop_of(t), 0});
 	}
+	unsigned long long rem = 0;                                      // chunks left, from the tile at hand on
+	for (uint32_t t = first_split; t < n_tiles; ++t) rem += stop_of(t);
 	for (uint32_t t = first_split; t < n_tiles; ++t) {
-		const unsigned long long rem = (unsigned long long)(n_tiles - t) * nchunks;      // chunks left, this tile included
+		const uint32_t stop = stop_of(t);
 		unsigned long long target = rem / ((unsigned long long)share_div * n_blocks);
 		if (target < min_chunks) target = min_chunks;
 		if (segmented && target > seg_chunks) target = seg_chunks;
-		uint32_t S = (uint32_t)((nchunks + target - 1) / target);
+		uint32_t S = (uint32_t)((stop + target - 1) / target);
 		if (S < 1) S = 1;
-		if (S > nchunks) S = nchunks;
+		if (S > stop) S = stop;
 		for (uint32_t k = 0; k < S; ++k)
-			units.push_back(CountUnit{t, (uint32_t)((unsigned long long)nchunks * k / S), (uint32_t)((unsigned long long)nchunks * (k + 1) / S), 0});
+			units.push_back(CountUnit{t | (S == 1 ? flag_of(stop) : 0u), (uint32_t)((unsigned long long)stop * k / S), (uint32_t)((unsigned long long)stop * (k + 1) / S), 0});
+		rem -= stop;
 	}
 	return segmented ? 0 : first_split;
 }
 
 template <class Vec>
-inline void fill_unit_tiles(Vec& units, const uint32_t* tiles) { for (auto& u : units) u.yx = tiles[u.tile]; }
+inline void fill_unit_tiles(Vec& units, const uint32_t* tiles) { for (auto& u : units) u.yx = tiles[u.tile & ~UNIT_WHOLE]; }
 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
 struct ColRange { const uint32_t* lo = nullptr; const uint32_t* hi = nullptr; uint32_t a0 = 0, b0 = 0;
@@ -188,13 +200,26 @@ struct CountTable {
 // null) over rows of nchunks K chunks.  One queue in the order of build_count_units, or - the measurement hook "xcd_queues" on rows of at
 // least 128 chunks - the patches dealt round robin to one queue per XCD; within a queue patch after patch, each K segment by K segment.
 // PA (0: P): plane rows per variant on the row axis, see tile_geometry.
-inline CountTable build_count_table(const twk_hip_tile_desc& t, int P, bool diag, const ColRange* cr, uint32_t nchunks, const CountSettings& s, int PA = 0) {
+// stop_of (may be empty): the per-tile stop in chunks, asked with a tile's (tile row << 16 | tile column) once the list is known - the prefix
+// contraction's planner (ld_plan.h plan_prefix_stop).  Not combined with K segments or XCD queues (the caller asks for neither then).
+// chunks_done / chunks_full (may be null): the chunks the table's tiles are contracted over, and what whole rows would have been.
+struct NoStops { uint32_t operator()(uint32_t) const { return 0; } };
+template <class StopOf = NoStops>
+inline CountTable build_count_table(const twk_hip_tile_desc& t, int P, bool diag, const ColRange* cr, uint32_t nchunks, const CountSettings& s, int PA = 0,
+                                    const StopOf* stop_of = nullptr, std::vector<uint32_t>* stops_out = nullptr) {
 	CountTable tb;
 	tb.g = tile_geometry(P, t, PA);
 	build_tile_list(t, P, tb.g, diag, cr, tb.tiles, &tb.patch_end, s.patch_rows, s.patch_cols, PA);
 	const uint32_t T = tb.n_tiles();
 	const uint32_t min_chunks = s.fused ? nchunks + 1 : s.min_chunks, seg_chunks = s.fused ? 0 : s.seg_chunks;
-	if (T && !s.fused && s.xcd_queues > 1 && s.xcd_queues <= 8 && nchunks >= 128 && !tb.patch_end.empty()) {
+	if (T && stop_of && !s.fused) {
+		std::vector<uint32_t> local;
+		std::vector<uint32_t>& stops = stops_out ? *stops_out : local;
+		stops.resize(T);
+		for (uint32_t i = 0; i < T; ++i) { const uint32_t st = (*stop_of)(tb.tiles[i]); stops[i] = st < 1 ? 1 : (st > nchunks ? nchunks : st); }
+		tb.first_split = build_count_units(T, nchunks, s.n_blocks, min_chunks, tb.units, s.share_div, s.tail_rounds, nullptr, 0, 0, stops.data());
+		for (uint32_t q = 1; q <= 8; ++q) tb.queue_begin[q] = tb.n_units();
+	} else if (T && !s.fused && s.xcd_queues > 1 && s.xcd_queues <= 8 && nchunks >= 128 && !tb.patch_end.empty()) {
 		const uint32_t nseg = seg_chunks ? (nchunks + seg_chunks - 1) / seg_chunks : 1;
 		std::vector<std::vector<CountUnit>> qs(s.xcd_queues);
 		uint32_t p0 = 0;

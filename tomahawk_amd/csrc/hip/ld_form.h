@@ -22,6 +22,7 @@ struct LaunchForm {
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
 	bool sample = false;           // a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name (k_count3_list_t<.., 1>), so that a
 	                               // kernel trace's statistics of the real launches are not diluted by half-millisecond ones
+	bool prefix = false;           // a two- or three-product launch through a matrix whose tiles are contracted over a prefix of their rows (per-tile stops)
 	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
@@ -35,7 +36,8 @@ struct LaunchForm {
 constexpr uint32_t FUSED_MAX_CHUNKS = 128;
 
 // What the owner of a launch allows it: `two` only where the two-product walk's owner says so for this launch (RegionRun, on the sorted set).
-struct FormGrant { bool fused = true, three = true, two = false, sample = false; };
+// `prefix`: an attribute of such a launch's two- or three-product form, not a form of its own - stops for its tiles, where the owner's sample allows them.
+struct FormGrant { bool fused = true, three = true, two = false, sample = false, prefix = false; };
 // What the tile plan, the filters and the options fix, whoever grants what.
 struct FormFacts {
 	bool two_pass = false;
@@ -44,7 +46,8 @@ struct FormFacts {
 	bool cut_screens = false;                               // an r2 cut-off a screen can use: minR2 > 1e-6 && minR2 <= 1
 	uint32_t chunks = 0;                                    // K chunks of a row (read only where a launch may fuse)
 	bool sorted_u = false;                                  // the set is PS_SORTED_U
-	long long opt_fused = 1, opt_three = 1, opt_two = 1;
+	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1;
+	uint32_t row_chunks = 0;                                // K chunks of a row (read only where a launch is granted the prefix)
 };
 // A screen in front of the math needs plain phased planes with PhasedMath, or plain unphased planes (four products per pair, gathered in the
 // epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short enough that no tile's K
@@ -58,11 +61,15 @@ inline LaunchForm decide_form(const FormFacts& x, const FormGrant& g) {
 	lf.three = lf.unphased && g.three && x.opt_three != 0;
 	lf.fused = x.opt_fused != 0 && (x.opt_fused == 2 || x.chunks <= FUSED_MAX_CHUNKS);
 	if (lf.three && !lf.fused && !lf.two_pass && x.sorted_u && g.two && x.opt_two != 0) { lf.two = true; lf.three = false; }
+	// the prefix: only the matrix forms of the sorted walk, and only on rows the fused form never takes by policy - whatever "fused" is set to
+	lf.prefix = g.prefix && x.opt_prefix != 0 && (lf.two || lf.three_plain()) && !lf.two_pass && x.sorted_u && x.row_chunks > FUSED_MAX_CHUNKS;
 	return lf;
 }
 // The ladder: what the tile of a launch whose candidate list overflowed may be when it is redone - a two-product launch's with three products
 // (if it was granted them), a fused or three-product launch's with four products through a matrix.
+// A prefix launch's is redone over whole rows in the same product form.
 inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
+	if (was.prefix) { given.prefix = false; return given; }
 	if (!was.two) given.fused = given.three = false;
 	given.two = false;
 	return given;
@@ -70,12 +77,15 @@ inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
 
 // What the running call has not yet given up: a region call owns one for all its stages, the single-tile entry a fresh one.
 struct CallForms {
-	bool fused = true, three = true, two = true;
-	// ... and allows a launch, whose owner wants three / two products for it
-	FormGrant grant(bool want_three, bool want_two) const { return FormGrant{fused, three && want_three, two && want_two, false}; }
+	bool fused = true, three = true, two = true, prefix = true;
+	// ... and allows a launch, whose owner wants three / two products for it (and stops for its tiles)
+	FormGrant grant(bool want_three, bool want_two, bool want_prefix = false) const { return FormGrant{fused, three && want_three, two && want_two, false, prefix && want_prefix}; }
 	// A launch of form `was`, given `given`, is through: a list that overflowed (cand_overflow) or held more candidates than the recount is worth
 	// (too_rich) ends the form for the rest of the call - but a form the launch was not given is not taken from the call on its account.
 	void gave_up(const LaunchForm& was, const FormGrant& given, bool cand_overflow, bool too_rich) {
+		// (a prefix launch's overflow - and its richness in candidates, which the wider screen of its stops makes - is the stops' doing: either ends
+		// the prefix for the call, the two-product rule, and no product form: the launches behind it are judged over whole rows again)
+		if (was.prefix) { if (cand_overflow || too_rich) prefix = false; return; }
 		if (cand_overflow && was.two) two = two && !given.two;
 		if (cand_overflow && (was.fused || was.three)) { fused = fused && !given.fused; three = three && !given.three; }
 		if (too_rich && was.three && !was.keep_three) three = three && !given.three;

@@ -343,6 +343,65 @@ inline uint32_t plan_two_end(const PlanEnv& e, const PlanGeom& g) {
 	return r / PLAN_TILE * PLAN_TILE;
 }
 
+// ---- the prefix contraction's stops ---------------------------------------------------------------------------
+// A tile of a two- or three-product launch of the two-product walk is contracted over the chunks [0, stop) only; the screen bounds what it did
+// not read by the rows' suffix margins (ld_two_screen.h).  The stop of a tile: for a small fixed set of its variant pairs - the four corners
+// and the middle - the smallest grid point at which the pair, at its independence expectation and with the square root of the screen's bound
+// shrunk to `margin` of it, is dropped; the largest of those, plus one grid step.  Expected prefix counts come from the real prefix margins
+// and the suffix term from the real suffix margins, so a file whose carriers crowd its last samples gets later stops by itself.  A guide
+// and no guarantee: the launch's sample decides whether the stops are taken, and what the wider screen keeps is recounted.
+struct PrefixEnv {
+	const uint32_t* het = nullptr; const uint32_t* hom = nullptr;      // per position of the sorted set
+	const uint32_t* suffix = nullptr;                                  // [2 x position + plane][PREFIX_GRID]: suffix popcounts of the H and Q rows
+	uint32_t n_variants = 0, n_samples = 0, nchunks = 0;
+	double cut = 0, margin = 0.95;
+	uint32_t fixed_grid = 0;                                           // test hook "prefix_stop": this grid index for every tile (0: the planner's)
+	uint64_t samples_before(uint32_t g) const { return std::min<uint64_t>((uint64_t)prefix_stop_chunks(g, nchunks) * 32u * 32u, n_samples); }
+	bool dropped(bool two, uint32_t vA, uint32_t vB, uint32_t g) const {
+		if (g >= PREFIX_GRID) return true;       // (whole rows: the screen itself decides)
+		const ScreenMargins m{het[vA], hom[vA], het[vB], hom[vB]};
+		const SuffixMargins x{suffix[(size_t)(2 * vA) * PREFIX_GRID + g], suffix[(size_t)(2 * vA + 1) * PREFIX_GRID + g],
+		                      suffix[(size_t)(2 * vB) * PREFIX_GRID + g], suffix[(size_t)(2 * vB + 1) * PREFIX_GRID + g]};
+		return !prefix_expected_keeps(m, x, two, (double)samples_before(g), 2.0 * (double)n_samples, cut, margin);
+	}
+	// smallest grid index in [1, PREFIX_GRID] at which the pair is dropped, walked from `hint` (the answer of a neighbouring tile: one or two
+	// questions instead of a search - both inequalities move one way along the row)
+	uint32_t pair_need(bool two, uint32_t vA, uint32_t vB, uint32_t hint) const {
+		uint32_t g = std::min<uint32_t>(std::max<uint32_t>(hint, 1), PREFIX_GRID);
+		while (g > 1 && dropped(two, vA, vB, g - 1)) --g;
+		while (g < PREFIX_GRID && !dropped(two, vA, vB, g)) ++g;
+		return g;
+	}
+};
+// Grid index of the stop of the tile over row variants [a_lo, a_hi] x column variants [b_lo, b_hi] (inclusive; a tile that reaches the
+// diagonal holds pairs of neighbours in allele-count order and is few: whole rows).  hint[5]: the caller's, carried from tile to tile.
+inline uint32_t plan_prefix_tile_grid(const PrefixEnv& e, bool two, uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, uint32_t b_hi, uint32_t* hint) {
+	if (e.fixed_grid) return std::min<uint32_t>(e.fixed_grid, PREFIX_GRID);
+	if (a_hi >= e.n_variants) a_hi = e.n_variants - 1;
+	if (b_hi >= e.n_variants) b_hi = e.n_variants - 1;
+	if (a_lo > a_hi || b_lo > b_hi || b_lo <= a_hi) return PREFIX_GRID;
+	const uint32_t pa[5] = {a_lo, a_lo, a_hi, a_hi, a_lo + (a_hi - a_lo) / 2}, pb[5] = {b_lo, b_hi, b_lo, b_hi, b_lo + (b_hi - b_lo) / 2};
+	uint32_t need = 1;
+	for (int k = 0; k < 5; ++k) { hint[k] = e.pair_need(two, pa[k], pb[k], hint[k]); need = std::max(need, hint[k]); }
+	return std::min<uint32_t>(need + 1, PREFIX_GRID);
+}
+
+// The stops of a launch's tiles as build_count_table (ld_count_table.h) asks for them: called with a tile's (tile row << 16 | tile column) in
+// the order of the list, -> its stop in chunks; the grid index goes into grid[tile row * gx + tile column] for the screen.  A tile holds
+// 64 x 64 variants in the three-product form and 128 row variants x 64 column variants in the two-product form.
+struct PrefixTileStops {
+	const PrefixEnv* e; bool two; uint32_t a0, b0, nA, nB, gx; std::vector<uint8_t>* grid; mutable uint32_t hint[5];
+	uint32_t tvA() const { return two ? PLAN_TILE : PLAN_TILE / 2; }
+	uint32_t operator()(uint32_t yx) const {
+		const uint32_t y = yx >> 16, x = yx & 0xFFFFu, ta = tvA(), tb = PLAN_TILE / 2;
+		uint32_t g = PREFIX_GRID;
+		if (y * ta < nA && x * tb < nB)
+			g = plan_prefix_tile_grid(*e, two, a0 + y * ta, a0 + std::min(nA, (y + 1) * ta) - 1, b0 + x * tb, b0 + std::min(nB, (x + 1) * tb) - 1, hint);
+		(*grid)[(size_t)y * gx + x] = (uint8_t)g;
+		return prefix_stop_chunks(g, e->nchunks);
+	}
+};
+
 // The whole plan of a region call.
 inline void plan_region(const PlanEnv& e, const PlanGeom& g, RegionPlan& p) {
 	p = RegionPlan();

@@ -99,6 +99,36 @@ __global__ void k_row_popcount(const uint32_t* __restrict__ rows, uint32_t W, ui
 	if (lane == 0) out[r] = c;
 }
 
+// Suffix popcounts of every row on a grid of 32 points (the prefix contraction's margins, ld_two_screen.h): out[r * 32 + g] = popcount of the
+// words [g * seg_words, W) of row r, zero where the grid point lies behind the row's end.  seg_words is a multiple of 4 (a grid step is whole
+// K chunks of 32 words).  One wave per row, one pass over the planes: the wave sums a segment at a time, lane g keeps segment g's count, and
+// the suffix sums are a 32-term loop per lane at the end.
+__global__ void k_row_suffix_popcount(const uint32_t* __restrict__ rows, uint32_t W, uint32_t n_rows, uint32_t seg_words,
+                                      uint32_t* __restrict__ out) {
+	const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	if (r >= n_rows) return;
+	const int lane = threadIdx.x & 63;
+	const uint4* p = reinterpret_cast<const uint4*>(rows + (size_t)r * W);
+	const uint32_t W4 = W / 4, seg4 = seg_words / 4;
+	uint32_t mine = 0;                      // lane g < 32: the count of segment g
+	for (uint32_t g = 0; g < 32; ++g) {
+		const uint32_t k0 = g * seg4, k1 = k0 + seg4 < W4 ? k0 + seg4 : W4;
+		uint32_t c = 0;
+		for (uint32_t k = k0 + lane; k < k1; k += 64) {
+			const uint4 x = p[k];
+			c += __builtin_popcount(x.x) + __builtin_popcount(x.y) + __builtin_popcount(x.z) + __builtin_popcount(x.w);
+		}
+		for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+		if (lane == (int)g) mine = c;
+	}
+	uint32_t suffix = 0;
+	for (int g = 31; g >= 0; --g) {
+		const uint32_t s = __shfl(mine, g);
+		if (g >= lane) suffix += s;
+	}
+	if (lane < 32) out[(size_t)r * 32 + lane] = suffix;
+}
+
 // Keep the even bits of a 64-bit word, packed into 32 bits.
 __device__ __forceinline__ uint32_t compress_even(uint64_t x) {
 	x &= 0x5555555555555555ull;

@@ -36,12 +36,25 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 		const int64_t d = (int64_t)p.vm.pos[A] - (int64_t)p.vm.pos[B];
 		if (p.vm.rid[A] != p.vm.rid[B] || (d < 0 ? -d : d) > (int64_t)p.l_window) ok = false;
 	}
-	uint32_t hh = 0, s_sum = 0;
+	uint32_t hh = 0, s_sum = 0, stop = 0;      // stop: the chunks the pair's counts cover (0: the whole rows)
 	if (ok) {
 		const uint2 hs = *reinterpret_cast<const uint2*>(C + (size_t)i * ldc + 2 * j);
 		hh = hs.x; s_sum = hs.y;
 		const ScreenMargins m{s.rowpop[2 * vA], s.rowpop[2 * vA + 1], s.rowpop[2 * vB], s.rowpop[2 * vB + 1]};
-		ok = TWO ? screen2_keeps(m, hh, s_sum, s.two_n, s.cut) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
+		// a prefix launch: the pair's tile was contracted over the chunks [0, stop) only - the counts are the prefix's, and the
+		// unread part of the two rows is bounded by its margins (ld_two_screen.h)
+		if (s.pre_stops) {
+			const uint32_t g = s.pre_stops[(size_t)(i / s.pre_tvA) * s.pre_gx + j / (TILE / 2)];
+			const uint32_t st = prefix_stop_chunks(g, s.pre_nchunks);
+			if (st < s.pre_nchunks) {
+				stop = st;
+				const uint32_t* fA = s.pre_suffix + (size_t)(2 * vA) * PREFIX_GRID + g;
+				const uint32_t* fB = s.pre_suffix + (size_t)(2 * vB) * PREFIX_GRID + g;
+				const SuffixMargins x{fA[0], fA[PREFIX_GRID], fB[0], fB[PREFIX_GRID]};
+				ok = TWO ? screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut) : screen3_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut);
+			}
+		}
+		if (!stop) ok = TWO ? screen2_keeps(m, hh, s_sum, s.two_n, s.cut) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
 	}
 	__shared__ uint32_t wave_n[SCREEN3_THREADS / 64];
 	__shared__ unsigned long long block_base;
@@ -61,7 +74,7 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 		slot += (unsigned long long)__popcll(ballot & ((1ull << lane) - 1));
 		if (slot < s.cap) {
 			uint32_t* e = s.cand + slot * 6;
-			e[0] = vA; e[1] = vB; e[2] = hh; e[3] = TWO ? s_sum : 0; e[4] = 0; e[5] = TWO ? 0 : s_sum;
+			e[0] = vA; e[1] = vB; e[2] = hh; e[3] = TWO ? s_sum : 0; e[4] = stop; e[5] = TWO ? 0 : s_sum;
 		}
 	}
 }
@@ -83,7 +96,7 @@ void k_screen2_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 template <int LANES>
 __global__ __launch_bounds__(256)
 void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t W_live, uint32_t* __restrict__ cand,
-                        const unsigned long long* __restrict__ n_cand, unsigned long long cap, unsigned long long* __restrict__ mismatches, int two) {
+                        const unsigned long long* __restrict__ n_cand, unsigned long long cap, unsigned long long* __restrict__ mismatches, int two, int prefix) {
 	static_assert(LANES == 64 || LANES == 16, "a wave or a DPP row per candidate");
 	const unsigned long long n = *n_cand;
 	if (n > cap) return;                                    // the list overflowed: the host redoes the launch with four products, nothing of this one is kept
@@ -100,19 +113,26 @@ void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t 
 		const uint4* hB = reinterpret_cast<const uint4*>(rows + (size_t)(2 * sB) * W);
 		const uint4* qB = reinterpret_cast<const uint4*>(rows + (size_t)(2 * sB + 1) * W);
 		uint32_t hh = 0, hq = 0, qh = 0, qq = 0;
+		// a prefix launch's candidate carries the stop of its tile in e[4] (0: whole rows): the contraction counted the 16-byte pieces [0, pre4) only,
+		// and it is their sums the proof below compares - the records come from the totals
+		const uint32_t pre4 = (prefix && e[4]) ? (e[4] * (uint32_t)(KC / 4) < W4 ? e[4] * (uint32_t)(KC / 4) : W4) : W4;
+		uint32_t p_hh = 0, p_s = 0;             // the prefix's HH, and its S (HQ of a two-product launch)
 		for (uint32_t p = lane; p < W4; p += LANES) {
 			const uint4 a = hA[p], b = qA[p], x = hB[p], y = qB[p];
-			hh += __popc(a.x & x.x) + __popc(a.y & x.y) + __popc(a.z & x.z) + __popc(a.w & x.w);
-			hq += __popc(a.x & y.x) + __popc(a.y & y.y) + __popc(a.z & y.z) + __popc(a.w & y.w);
-			qh += __popc(b.x & x.x) + __popc(b.y & x.y) + __popc(b.z & x.z) + __popc(b.w & x.w);
-			qq += __popc(b.x & y.x) + __popc(b.y & y.y) + __popc(b.z & y.z) + __popc(b.w & y.w);
+			const uint32_t d_hh = __popc(a.x & x.x) + __popc(a.y & x.y) + __popc(a.z & x.z) + __popc(a.w & x.w);
+			const uint32_t d_hq = __popc(a.x & y.x) + __popc(a.y & y.y) + __popc(a.z & y.z) + __popc(a.w & y.w);
+			const uint32_t d_qh = __popc(b.x & x.x) + __popc(b.y & x.y) + __popc(b.z & x.z) + __popc(b.w & x.w);
+			const uint32_t d_qq = __popc(b.x & y.x) + __popc(b.y & y.y) + __popc(b.z & y.z) + __popc(b.w & y.w);
+			hh += d_hh; hq += d_hq; qh += d_qh; qq += d_qq;
+			if (p < pre4) { p_hh += d_hh; p_s += two ? d_hq : d_qh + d_hq + 2u * d_qq; }
 		}
 #pragma unroll
 		for (int d = 1; d < LANES; d <<= 1) {
 			hh += __shfl_xor(hh, d, LANES); hq += __shfl_xor(hq, d, LANES); qh += __shfl_xor(qh, d, LANES); qq += __shfl_xor(qq, d, LANES);
+			p_hh += __shfl_xor(p_hh, d, LANES); p_s += __shfl_xor(p_s, d, LANES);
 		}
 		if (lane == 0) {
-			if (mismatches && (e[2] != hh || (two ? e[3] != hq : e[5] != qh + hq + 2u * qq))) atomicAdd(mismatches, 1ull);      // the contraction's (HH, S) - (HH, HQ) - against the recount
+			if (mismatches && (e[2] != p_hh || (two ? e[3] != p_s : e[5] != p_s))) atomicAdd(mismatches, 1ull);      // the contraction's (HH, S) - (HH, HQ) - against the recount
 			e[2] = hh; e[3] = hq; e[4] = qh; e[5] = qq;
 		}
 	}

@@ -53,4 +53,47 @@ TWK_SCREEN_FN bool screen2_expected_keeps(const ScreenMargins& m, double n_sampl
 	return screen_keeps_between(m, hh, hq, hq + screen2_slack(m), two_n, cut, margin * margin);
 }
 
+// ---- the prefix contraction ------------------------------------------------------------------------------------------
+// A launch may contract only the first K chunks [0, stop) of a tile's rows.  Per sample, with g = 0 / 1 / 2 alt alleles, the contribution to
+// S = QH + HQ + 2 QQ is >= 0 and the contribution to S + HH is exactly min(gA, gB); summed over the unread suffix, whose margins are the
+// popcounts h', q' of the row suffixes (dosage d' = h' + 2 q'):
+//     S_suffix >= 0,     (S + HH)_suffix <= min(dA', dB').
+// e_lo is tested at s_lo and e_hi at s_hi + hh, and both rise with their argument, so with the prefix counts in the totals' place and
+// min(dA', dB') added to s_hi the two outer values again enclose the ones the full three-product screen would test: a prefix screen keeps
+// every pair screen3_keeps keeps on the whole rows.  What it keeps is recounted over the whole rows (k_recount_unphased).
+struct SuffixMargins { uint32_t hA, qA, hB, qB; };       // het and hom-alt carriers among the samples behind the stop
+TWK_SCREEN_FN double prefix_slack(const SuffixMargins& x) {
+	const double da = (double)x.hA + 2.0 * (double)x.qA, db = (double)x.hB + 2.0 * (double)x.qB;
+	return da < db ? da : db;
+}
+// Three products over the prefix: hh = HH_pre, s_sum = S_pre.
+TWK_SCREEN_FN bool screen3_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t hh, uint32_t s_sum, double two_n, double cut) {
+	return screen_keeps_between(m, (double)hh, (double)s_sum, (double)s_sum + prefix_slack(x), two_n, cut);
+}
+// Two products over the prefix: hh = HH_pre, hq = HQ_pre; the prefix's own S is bounded by the prefix margins (total minus suffix).
+TWK_SCREEN_FN bool screen2_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t hh, uint32_t hq, double two_n, double cut) {
+	const double qa = (double)(m.qA - x.qA), qb = (double)(m.qB - x.qB);
+	return screen_keeps_between(m, (double)hh, (double)hq, (double)hq + qa + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut);
+}
+// The planner's question for a stop (ld_plan.h plan_prefix_stop): would a pair of independent variants with these margins, n_pre samples in
+// front of the stop, be kept by the prefix screen if the cut-off's square root were `margin` of what it is?  The expected prefix counts come
+// from the prefix margins themselves (HH_pre = hA_pre hB_pre / n_pre, ...), the suffix term from the suffix margins.
+TWK_SCREEN_FN bool prefix_expected_keeps(const ScreenMargins& m, const SuffixMargins& x, bool two, double n_pre, double two_n, double cut, double margin) {
+	if (n_pre <= 0) return true;
+	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
+	const double hh = ha * hb / n_pre, hq = ha * qb / n_pre;
+	if (two) return screen_keeps_between(m, hh, hq, hq + qa + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut, margin * margin);
+	const double s = (qa * hb + ha * qb + 2.0 * qa * qb) / n_pre;
+	return screen_keeps_between(m, hh, s, s + prefix_slack(x), two_n, cut, margin * margin);
+}
+
+// The grid of stops: PREFIX_GRID points along a row of nchunks K chunks, prefix_step chunks apart; grid index g stands for the stop
+// min(g * step, nchunks), and PREFIX_GRID (or any stop of nchunks) for the whole row.
+constexpr uint32_t PREFIX_GRID = 32;
+TWK_SCREEN_FN uint32_t prefix_step(uint32_t nchunks) { return (nchunks + PREFIX_GRID - 1) / PREFIX_GRID; }
+TWK_SCREEN_FN uint32_t prefix_stop_chunks(uint32_t g, uint32_t nchunks) {
+	const unsigned long long s = (unsigned long long)g * prefix_step(nchunks);
+	return g >= PREFIX_GRID || s >= nchunks ? nchunks : (uint32_t)s;
+}
+
 }  // namespace twk

@@ -102,6 +102,9 @@ struct PlaneSet {
 	DevBuf<float4> terms; double terms_cut = -1.0;
 	// the two-product walk's planner (ld_plan.h plan_two_end): het and hom-alt carriers per position, copied from rowpop when first asked for
 	std::vector<uint32_t> h_het, h_hom;
+	// the prefix contraction: suffix popcounts of every plane row on the grid of stops, [rows_alloc][PREFIX_GRID], built the first time a
+	// call may take the form (ensure_suffix) and kept with the set - on the device for the screens, on the host for the planner
+	DevBuf<uint32_t> suffix; std::vector<uint32_t> h_suffix;
 };
 
 // Plane sets a context can hold: one per PlaneKind in file order, plus the masked unphased planes
@@ -157,7 +160,9 @@ struct Launch {
 	                                              // it as an overflow and the launch's rows are redone as matrix-sized tiles
 	int plane_set = 0;                            // the plane set the launch contracted
 	double minP = 1.0;
-	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted
+	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted - a prefix launch's in full-row
+	                                              // equivalents: x chunks contracted / chunks per row, summed over its tiles and rounded down once
+	uint64_t prefix_chunks = 0, prefix_chunks_full = 0;      // a prefix launch: chunks its tiles were contracted over, and what whole rows would have been
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
 union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; BandArgs bandmat; TopkArgs topk; };
@@ -199,6 +204,9 @@ namespace {
 	X(fused, 1, 0, 2, false, "fused count -> r2 screen kernel (no count matrix; DESIGN 3.2a): 0 never, 1 rows of <= 128 K chunks, 2 always") \
 	X(three, 1, 0, 2, false, "UnphasedMath on planes without missing genotypes, r2 cut-off > 1e-6: contract three products a pair (HH and S = QH + HQ + 2 QQ: all the screen reads) and recount the four products of the pairs that pass (DESIGN 3.1a); 0: four products for every pair; 2: keep to three whatever a launch's candidate density (1 samples every launch first)") \
 	X(two, 1, 0, 2, false, "UnphasedMath, whole triangle without a window, rows too long to fuse, three = 1 and no tile edge given: walk the allele-count-sorted planes and contract two products a pair (HH and HQ of the row variant's H plane; S bounded from the margins) in the launches whose rows have few hom-alt carriers (DESIGN 3.1b); 0: never (the call walks the file order); 2: in every launch of that walk, whatever the predicate and the samples say") \
+	X(prefix, 1, 0, 2, false, "the two-product walk on rows of more than 128 K chunks: a launch contracts each tile over a prefix of its rows, up to a stop the planner chooses per tile, and its screen bounds the unread samples by the rows' suffix margins; what it keeps is recounted over the whole rows (DESIGN 3.1c); 0: never; 1: launches whose sample with stops is poor in candidates; 2: every eligible launch whatever its sample") \
+	X(prefix_margin, 950, 1, 1000, false, "... the planner asks with the square root of the screen's bound shrunk to this many thousandths of it (950 as the two-product planner's two_margin = 0.95)") \
+	X(prefix_stop, 0, 0, 32, false, "test hook: this point of the 32-point grid of stops for every tile of a prefix launch (0: the planner's stops)") \
 	X(count_min_chunks, 8, 1, 1 << 20, false, "shortest K range a tile of the count kernel is split into at the end of a launch (test hook: 1 splits short rows too)") \
 	X(patch_rows, 8, 1, 4096, false, "rows of a patch of tiles in the count kernel's work order (DESIGN 3.1, profiles/r03_patch_pmc.txt)") \
 	X(patch_cols, 8, 1, 4096, false, "... and its columns") \
@@ -506,6 +514,7 @@ int build_planes(twk_hip_ctx* c, int set) {
 	hipLaunchKernelGGL(k_row_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, ps.rows, ps.W, live_rows, ps.rowpop);
 	HIPCHK(c, hipGetLastError());
 	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	ps.h_suffix.clear();
 	ps.built = true;
 	return TWK_HIP_OK;
 }
@@ -524,6 +533,25 @@ int ensure_lists(twk_hip_ctx* c, int set) {
 	rc = build_lists(c, set);
 	if (rc) { c->planes[set] = PlaneSet(); return rc; }
 	ps.lists_done = true;
+	return TWK_HIP_OK;
+}
+
+// ... with the suffix popcounts of its rows on the grid of stops (the prefix contraction): one pass over the planes and one copy to the
+// host, the first time a call may take the form; kept with the set.  -> TWK_HIP_E_NOMEM leaves the set as it was (the call then takes no stops).
+int ensure_suffix(twk_hip_ctx* c, int set) {
+	int rc = ensure_planes(c, set); if (rc) return rc;
+	PlaneSet& ps = c->planes[set];
+	const size_t n = (size_t)ps.rows_alloc * PREFIX_GRID;
+	if (ps.h_suffix.size() == n && ps.suffix) return TWK_HIP_OK;
+	const uint32_t nchunks = ps.W / KC, seg_words = prefix_step(nchunks) * KC;
+	HIPCHK(c, ps.suffix.reserve(n, n, nullptr));
+	HIPCHK(c, hipMemsetAsync(ps.suffix, 0, n * 4, c->s_compute));
+	const uint32_t live_rows = c->M * (uint32_t)planes_per_variant(set_kind(set));
+	hipLaunchKernelGGL(k_row_suffix_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, live_rows, seg_words, ps.suffix.get());
+	HIPCHK(c, hipGetLastError());
+	ps.h_suffix.resize(n);
+	HIPCHK(c, hipMemcpyAsync(ps.h_suffix.data(), ps.suffix, n * 4, hipMemcpyDeviceToHost, c->s_compute));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
 	return TWK_HIP_OK;
 }
 
@@ -578,15 +606,38 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	CountSettings cs;
 	cs.patch_rows = (uint32_t)c->opt.patch_rows; cs.patch_cols = (uint32_t)c->opt.patch_cols; cs.min_chunks = (uint32_t)c->opt.count_min_chunks;
 	cs.seg_chunks = (uint32_t)c->opt.seg; cs.xcd_queues = (uint32_t)c->opt.xcd_queues; cs.n_blocks = c->resident_blocks; cs.fused = fuse;
-	const CountTable tb = build_count_table(t, P, diag, cr, ps.W / KC, cs, PA);
+	// A prefix launch: every tile gets a stop from the planner (ld_plan.h plan_prefix_tile_grid: the tile's variants on both axes,
+	// asked in the order of the list, each question starting from its neighbour's answer); the grid indices travel to the device behind the
+	// parameter blocks, one byte per tile of the super-tile's grid, for the screen.
+	const uint32_t nchunks = ps.W / KC;
+	std::vector<uint8_t> pre_grid;
+	PrefixEnv pe;
+	PrefixTileStops stop_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, g.gx, &pre_grid, {PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID}};
+	if (form.prefix) {
+		if (!(two || three) || fuse || which != 0 || P != 2 || ps.h_suffix.size() != (size_t)ps.rows_alloc * PREFIX_GRID || ps.h_het.size() != c->M) return TWK_HIP_E_STATE;
+		pe.het = ps.h_het.data(); pe.hom = ps.h_hom.data(); pe.suffix = ps.h_suffix.data();
+		pe.n_variants = c->M; pe.n_samples = c->N; pe.nchunks = nchunks;
+		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.fixed_grid = (uint32_t)c->opt.prefix_stop;
+		pre_grid.assign((size_t)g.gy * g.gx, (uint8_t)PREFIX_GRID);
+	}
+	std::vector<uint32_t> stops;
+	const CountTable tb = form.prefix ? build_count_table(t, P, diag, cr, nchunks, cs, PA, &stop_of, &stops) : build_count_table(t, P, diag, cr, nchunks, cs, PA);
 	const size_t T = tb.n_tiles();
-	const size_t words_units = tb.words(), fa_words = (sizeof(FusedArgs) + 15) / 16 * 4;
-	const size_t words = words_units + (with_args ? fa_words : 0);               // [tiles | pad | units | FusedArgs] for a fused or three-product launch
+	const size_t words_units = tb.words(), fa_words = (sizeof(FusedArgs) + 15) / 16 * 4, pre_words = (pre_grid.size() + 3) / 4;
+	const size_t words = words_units + (with_args ? fa_words : 0) + pre_words;   // [tiles | pad | units | FusedArgs | a prefix launch's stops] for a fused or three-product launch
 	// (parked, the pinned one too: the device copy of the previous launch's table may still be travelling)
 	HIPCHK(c, reserve_together(words, std::max<size_t>(words, 16384), &c->graveyard, s.h_tiles[which], s.d_tiles[which]));
 	if (T) {
 		tb.pack(s.h_tiles[which]);
 		if (with_args) std::memcpy(s.h_tiles[which] + words_units, fa, sizeof(FusedArgs));
+		if (form.prefix) {
+			uint32_t* at = s.h_tiles[which] + words_units + fa_words;
+			at[pre_words - 1] = 0;
+			std::memcpy(at, pre_grid.data(), pre_grid.size());
+			ScreenWork& sw = reinterpret_cast<FusedArgs*>(s.h_tiles[which] + words_units)->screen;
+			sw.pre_stops = reinterpret_cast<const uint8_t*>(s.d_tiles[which] + words_units + fa_words); sw.pre_suffix = ps.suffix;
+			sw.pre_gx = g.gx; sw.pre_tvA = stop_of.tvA(); sw.pre_nchunks = nchunks;
+		}
 		HIPCHK(c, hipMemcpyAsync(s.d_tiles[which], s.h_tiles[which], words * 4, hipMemcpyHostToDevice, c->s_compute));
 	}
 	HIPCHK(c, hipEventRecord(e0, c->s_compute));
@@ -610,6 +661,12 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	}
 	HIPCHK(c, hipEventRecord(e1, c->s_compute));
 	(which ? s.l.row_pairs_b : s.l.row_pairs) = (uint64_t)T * TILE * TILE;
+	if (form.prefix) {      // full-row equivalents: what the launch's time is set against (bench.py's roofline, the outlier watch)
+		uint64_t done = 0;
+		for (uint32_t st : stops) done += st;
+		s.l.prefix_chunks = done; s.l.prefix_chunks_full = (uint64_t)T * nchunks;
+		s.l.row_pairs = (uint64_t)TILE * TILE * done / nchunks;
+	}
 	return TWK_HIP_OK;
 }
 
@@ -702,7 +759,9 @@ LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters
 	x.two_pass = pl.set2 >= 0; x.reduce = c->reduce.kind; x.sorted_u = pl.set1 == PS_SORTED_U;
 	x.phased_plain = pl.phased1 && k == PK_PHASED; x.unphased_plain = !pl.phased1 && k == PK_UNPHASED;
 	x.cut_screens = f.minR2 > 1e-6 && f.minR2 <= 1.0;
-	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two;
+	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix;
+	// (stops are not combined with the measurement hooks that walk a tile's K range their own way)
+	if (grant.prefix && c->opt.prefix != 0 && c->opt.seg == 0 && c->opt.xcd_queues == 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK) x.row_chunks = c->planes[pl.set1].W / KC;
 	if (may_screen(x, grant) && x.opt_fused != 0) {
 		if (ensure_planes(c, pl.set1) == TWK_HIP_OK) x.chunks = c->planes[pl.set1].W / KC;
 		else x.opt_fused = 0;
@@ -723,10 +782,10 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	const PlaneSet& ps = c->planes[set];
 	if (ps.W_live <= 1024)
 		hipLaunchKernelGGL(k_recount_unphased<16>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
 	else
 		hipLaunchKernelGGL(k_recount_unphased<64>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -1058,6 +1117,7 @@ void watch_launch(twk_hip_ctx* c, const Slot& s, float ms, const twk_hip_tile_de
 	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three || s.l.form.two) ? s.h_n_out[2] : 0;
 	st.shader_mhz = s.h_n_out[5] ? (double)s.h_n_out[4] / (double)s.h_n_out[5] * 100.0 : 0.0;
 	st.words_per_row = c->planes[s.l.plane_set].W_live;
+	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full;
 	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.two ? 5u : s.l.form.three_plain() ? 1u : 0u);
 	unsigned long long lo = ~0ull, hi = 0;
 	for (int x = 0; x < 8; ++x) if (s.h_n_out[8 + x]) { lo = std::min(lo, s.h_n_out[8 + x]); hi = std::max(hi, s.h_n_out[8 + x]); }
@@ -1233,6 +1293,8 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		snprintf(c->err, sizeof(c->err), "%llu candidates for a list of %llu (tile rows %u+%u, cols %u+%u)", s.h_n_out[2], s.l.cand_cap, t.rowA0, t.nA, t.rowB0, t.nB);
 		return TWK_HIP_E_OVERFLOW;
 	}
+	// (behind the overflow check: a prefix launch whose list flooded is redone over whole rows and has taken no stop that counted; the launch log keeps its entry)
+	if (s.l.form.prefix) { c->timing.prefix_launches += 1; c->timing.prefix_chunks += s.l.prefix_chunks; c->timing.prefix_chunks_full += s.l.prefix_chunks_full; }
 	if (n > s.cap_use) {
 		snprintf(c->err, sizeof(c->err), "%llu survivors for a buffer of %llu (tile rows %u+%u, cols %u+%u%s)", n, s.cap_use, t.rowA0, t.nA, t.rowB0, t.nB, s.l.is_list ? ", list pass" : "");
 		return TWK_HIP_E_OVERFLOW;
@@ -1879,13 +1941,16 @@ struct RegionRun {
 	uint64_t tot_pairs = 0, tot_recs = 0;
 	std::vector<char> want_three;             // per launch: the three-product form may be used (decide_three_by_samples)
 	std::vector<char> want_two;               // ... and the two-product form (the two-product walk: launches in front of plan.two_end whose sample was poor in candidates)
+	std::vector<char> want_prefix;            // ... and stops for its tiles (the prefix contraction, DESIGN 3.1c: the launch's sample ran with them and was poor in candidates)
+	// the prefix applies to the launches of the two-product walk on rows of more than FUSED_MAX_CHUNKS chunks (ld_form.h decide_form holds the rest)
+	bool prefix_eligible() const { return two_walk() && c->opt.prefix != 0 && calls.prefix && c->planes[PS_SORTED_U].W / KC > FUSED_MAX_CHUNKS && !c->planes[PS_SORTED_U].h_suffix.empty(); }
 	bool two_walk() const { return mode == MODE_INT_SORTED_U_ALL; }
 	// (option two = 2, the test hook: every launch of the walk, whatever the predicate says)
 	bool two_eligible(const twk_hip_tile_desc& t) const { return two_walk() && c->opt.two != 0 && (c->opt.two == 2 || t.rowA0 + t.nA <= g.a0 + plan.two_end); }
 
 	// What launch i of the plan may be: the call's forms, three and two products as the launch's own sample decided.  A tile redone synchronously is not
 	// bound by a sample: it may be whatever the call still allows but two products (redo_grant).
-	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0); }
+	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0, want_prefix[i] != 0); }
 	FormGrant redo_grant() const { return calls.grant(true, false); }
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, CallForms& calls_, twk_hip_record_sink sink_, void* user_)
@@ -1983,8 +2048,10 @@ struct RegionRun {
 	int decide_three_by_samples() {
 		const std::vector<twk_hip_tile_desc>& mine = plan.mine;
 		const size_t n = mine.size();
-		want_three.assign(n, 1); want_two.assign(n, 0);
+		want_three.assign(n, 1); want_two.assign(n, 0); want_prefix.assign(n, 0);
 		if (c->opt.two == 2) for (size_t i = 0; i < n; ++i) want_two[i] = two_eligible(mine[i]) ? 1 : 0;
+		const bool prefix_ok = prefix_eligible();
+		if (prefix_ok && c->opt.prefix == 2) want_prefix.assign(n, 1);
 		if (mine.empty() || c->opt.three != 1 || !launch_form(c, plan_for(c, mode), *f, redo_grant()).three) return TWK_HIP_OK;     // (no launch of this region would take the form)
 		// (fused launches - short rows - are sampled as well: they keep their candidates whatever their number, but past ~1.2 % of the pairs
 		// the recount costs more than the third product saves: 2,504 samples, -u -w 1000000, 2.9 % candidates: 27.4 + 30.3 ms of count kernel and
@@ -2005,13 +2072,13 @@ struct RegionRun {
 			else { const uint32_t wv = std::min<uint32_t>(384, t0.nB); st.rowB0 = t0.rowB0 + (t0.nB - wv) / 2; st.nB = wv; st.diag = 0; }
 			unsigned long long cand = 0;
 			const unsigned long long sample_pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
-			auto sample = [&](bool two) -> int {
+			auto sample = [&](bool two, bool prefix = false) -> int {
 				const twk_hip_timing keep_timing = c->timing;
 				const size_t keep_ring = c->launch_ring.size(); const uint64_t keep_seen = c->launches_seen;
 				Slot& ss = c->slot[SYNC_SLOT];
 				unsigned long long nrec = 0;
 				// (three products granted: a sample is only taken where the call allows them; and its own overflow or richness decides its launch, not the call)
-				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
+				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true, prefix && calls.prefix}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
 				if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
 				cand = ss.h_n_out[2];
 				c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
@@ -2019,6 +2086,18 @@ struct RegionRun {
 				c->launches_seen = keep_seen;
 				return rc;
 			};
+			// The prefix: the same samples, first with the stops the launch would use - at most 1 candidate in 256 and the launch takes the form with
+			// its stops; otherwise the ladder below decides without them.
+			const bool try_two = (c->opt.two == 1 && two_eligible(t0)) || (c->opt.two == 2 && want_two[pick]);
+			if (prefix_ok && c->opt.prefix == 1) {
+				const int rcp = sample(try_two, true);
+				if (rcp != TWK_HIP_OK && rcp != TWK_HIP_E_OVERFLOW) return rcp;
+				mark("prefix sample of launch: candidates", pick, cand);
+				if (rcp == TWK_HIP_OK && cand * 256 <= sample_pairs) {
+					for (size_t i = i0; i < std::min(n, i0 + step); ++i) { want_prefix[i] = 1; if (try_two && two_eligible(mine[i])) want_two[i] = 1; }
+					continue;
+				}
+			}
 			if (c->opt.two == 1 && two_eligible(t0)) {
 				const int rc2 = sample(true);
 				if (rc2 != TWK_HIP_OK && rc2 != TWK_HIP_E_OVERFLOW) return rc2;
@@ -2150,6 +2229,12 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, const CallF
 			for (uint32_t v = 0; v < c->M; ++v) { ps.h_het[v] = pop[2 * (size_t)v]; ps.h_hom[v] = pop[2 * (size_t)v + 1]; }
 		}
 		env.het = ps.h_het.data(); env.hom = ps.h_hom.data();
+		// the prefix contraction: the rows' suffix margins, the first time a call may take the form (no room for the table: the call takes no stops)
+		if (c->opt.prefix != 0 && calls.prefix && f->minR2 > 1e-6 && f->minR2 <= 1.0 && ps.W / KC > FUSED_MAX_CHUNKS) {
+			const int rc = ensure_suffix(c, PS_SORTED_U);
+			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.suffix = DevBuf<uint32_t>(); ps.h_suffix.clear(); }
+			else if (rc) return rc;
+		}
 	}
 	// r2 screen (TWK_HIP_OPT_R2_SCREEN): the region is a triangle over the leading, missing-free part of an allele-count-sorted set
 	env.screen = (mode == MODE_INT_SORTED_P) ? 1 : (mode == MODE_INT_SORTED_U) ? 2 : 0;

@@ -103,6 +103,33 @@ void check_gave_up() {
 	{ const FormGrant g = step_down(two, all); CHECK(g.fused && g.three && !g.two, "below two products"); }
 	for (const LaunchForm& lf : {fused4, fused3, three}) { const FormGrant g = step_down(lf, all); CHECK(!g.fused && !g.three && !g.two, "below a fused or three-product launch"); }
 	{ FormGrant s = all; s.sample = true; CHECK(step_down(three, s).sample, "the sample mark stays"); }
+	// the prefix: an attribute of a two- or three-product launch through a matrix.  Its overflow ends the prefix for the call and
+	// no product form, and the tile is redone over whole rows in the same product form; a launch without it never touches it.
+	FormGrant with_prefix = all; with_prefix.prefix = true;
+	for (LaunchForm lf : {two, three}) {
+		lf.prefix = true;
+		{ CallForms c; c.gave_up(lf, with_prefix, true, false); CHECK(is(c, true, true, true) && !c.prefix, "a prefix launch's list overflowed"); }
+		{ CallForms c; c.gave_up(lf, with_prefix, false, false); CHECK(is(c, true, true, true) && c.prefix, "a prefix launch went well"); }
+		const FormGrant g = step_down(lf, with_prefix);
+		CHECK(!g.prefix && g.fused == with_prefix.fused && g.three == with_prefix.three && g.two == with_prefix.two, "below a prefix launch: the same product form over whole rows");
+		CallForms gone; gone.prefix = false;
+		CHECK(!gone.grant(true, true, true).prefix && CallForms().grant(true, true, true).prefix && !CallForms().grant(true, true).prefix, "prefix grants");
+	}
+	{ LaunchForm lf = three; lf.prefix = true; CallForms c; c.gave_up(lf, with_prefix, false, true); CHECK(is(c, true, true, true) && !c.prefix, "a three-product prefix launch too rich in candidates: the stops go, the form stays"); }
+	{ LaunchForm lf = three; lf.prefix = true; CallForms c; c.gave_up(lf, with_prefix, true, true); CHECK(is(c, true, true, true) && !c.prefix, "a flooded prefix launch is rich by its stops: the form stays"); }
+	for (const LaunchForm& lf : {two, fused4, fused3, three, four}) for (int ob = 0; ob < 4; ++ob) { CallForms c; c.gave_up(lf, all, (ob & 1) != 0, (ob & 2) != 0); CHECK(c.prefix, "a launch without stops took the prefix from the call"); }
+	// decide_form: only with the grant, the option, the sorted set, a matrix form of two or three products and rows beyond the fused form's policy
+	for (const FormFacts& x0 : all_facts()) for (const uint32_t rc : {0u, FUSED_MAX_CHUNKS, FUSED_MAX_CHUNKS + 1}) for (int op = 0; op < 3; ++op) for (int gp = 0; gp < 2; ++gp) for (int gt = 0; gt < 2; ++gt) {
+		FormFacts x = x0; x.row_chunks = rc; x.opt_prefix = op;
+		FormGrant g; g.two = gt != 0; g.prefix = gp != 0;
+		const LaunchForm lf = decide_form(x, g);
+		FormGrant g0 = g; g0.prefix = false;
+		const LaunchForm base = decide_form(x, g0);
+		++g_cases;
+		CHECK(lf.fused == base.fused && lf.three == base.three && lf.two == base.two && lf.two_pass == base.two_pass, "the prefix grant changed the product form");
+		CHECK(!base.prefix, "a prefix without its grant");
+		CHECK(lf.prefix == (gp && op != 0 && rc > FUSED_MAX_CHUNKS && x.sorted_u && !lf.two_pass && (lf.two || lf.three_plain())), "prefix: grant %d option %d chunks %u", gp, op, rc);
+	}
 }
 
 }  // namespace

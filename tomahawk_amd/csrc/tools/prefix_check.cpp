@@ -1,0 +1,233 @@
+// `make prefix-check`: the host side of the prefix contraction, on the CPU under AddressSanitizer and UBSan.
+//   1. Soundness of the prefix screens (csrc/hip/ld_two_screen.h): every (prefix 3 x 3 genotype table, suffix 3 x 3 genotype table) of up to
+//      4 + 4 samples, at the cut-offs 0.1, 0.5, 0.8 and at cut-offs on, one ulp below and one ulp above the values at which the three-product
+//      screen's decision on the summed table turns.  Every pair screen3_keeps keeps on the summed table must be kept by
+//      screen3_prefix_keeps and by screen2_prefix_keeps on the prefix counts with the suffix margins.
+//   2. The table builder with per-tile stops (csrc/hip/ld_count_table.h) against a naive restatement: every tile's units partition
+//      [0, stop) exactly, every split tile lies in the zeroed range, a unit that holds a stopped tile's whole count says so (UNIT_WHOLE) and
+//      no other does, and with no stops - or every stop at the row's end - the packed image is the one built without them.
+//   3. The planner (csrc/hip/ld_plan.h) on the headline's law: p evenly spread over (0.05, 0.5), 1,000,000 samples, 50,000 variants in
+//      allele-count order, margins and suffix margins at their expectation: the launches of the two-product walk, the stop of every tile
+//      of every launch, the mean contracted fraction per launch and overall (two-product pairs at 0.66 of a three-product pair's cost).
+// usage: prefix_check [--no-planner]
+#include <cinttypes>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <chrono>
+#include <vector>
+#include "../hip/ld_count_table.h"
+#include "../hip/ld_plan.h"
+#include "../hip/ld_two_screen.h"
+
+using namespace twk;
+
+namespace {
+
+int g_bad_checks = 0;
+#define CHECK(cond, ...) do { if (!(cond)) { if (g_bad_checks < 40) { fprintf(stderr, "    FAILED %s: ", #cond); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } ++g_bad_checks; } } while (0)
+
+// ---- 1. the screens ----------------------------------------------------------------------------------------------------------
+constexpr uint32_t MAX_PART = 4;
+uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_violations = 0;
+std::vector<std::vector<uint32_t>> g_tables;          // every 3 x 3 table of 0 .. MAX_PART samples: c[3 a + b]
+
+void each_table(uint32_t c[9], int cell, uint32_t left) {
+	if (cell == 8) { c[8] = left; g_tables.push_back(std::vector<uint32_t>(c, c + 9)); return; }
+	for (uint32_t k = 0; k <= left; ++k) { c[cell] = k; each_table(c, cell + 1, left - k); }
+}
+void check_pair(const uint32_t* p, const uint32_t* x) {
+	uint32_t c[9], n = 0;
+	for (int k = 0; k < 9; ++k) { c[k] = p[k] + x[k]; n += c[k]; }
+	if (!n) return;
+	const ScreenMargins m{c[3] + c[4] + c[5], c[6] + c[7] + c[8], c[1] + c[4] + c[7], c[2] + c[5] + c[8]};
+	const SuffixMargins sx{x[3] + x[4] + x[5], x[6] + x[7] + x[8], x[1] + x[4] + x[7], x[2] + x[5] + x[8]};
+	const uint32_t hh = c[4], s = c[7] + c[5] + 2 * c[8];
+	const uint32_t hh_pre = p[4], hq_pre = p[5], s_pre = p[7] + p[5] + 2 * p[8];
+	const double two_n = 2.0 * n;
+	// the facts the bound rests on: the suffix's S is >= 0 (unsigned), and its S + HH is at most min(dA', dB')
+	const uint32_t s_suf = x[7] + x[5] + 2 * x[8], hh_suf = x[4];
+	CHECK((double)(s_suf + hh_suf) <= prefix_slack(sx), "suffix S + HH = %u above min(dA', dB') = %g", s_suf + hh_suf, prefix_slack(sx));
+	double cuts[3 + 6]; int n_cuts = 3;
+	cuts[0] = 0.1; cuts[1] = 0.5; cuts[2] = 0.8;
+	const double da = m.hA + 2.0 * m.qA, ra = two_n - da, db = m.hB + 2.0 * m.qB, rb = two_n - db, denom = da * ra * db * rb;
+	if (denom > 0) {
+		const double n11 = (ra - db) + s;
+		for (const double e : {n11 * two_n - ra * rb, (n11 + hh) * two_n - ra * rb}) {
+			const double v = e * e / denom;
+			if (v > 1e-6 && v <= 1.0) { cuts[n_cuts++] = std::nextafter(v, 0.0); cuts[n_cuts++] = v; cuts[n_cuts++] = std::nextafter(v, 2.0); }
+		}
+	}
+	for (int k = 0; k < n_cuts; ++k) {
+		if (cuts[k] > 1.0) continue;
+		const double cut = cuts[k] * (1.0 - 1e-6);
+		const bool k3 = screen3_keeps(m, hh, s, two_n, cut);
+		const bool k3p = screen3_prefix_keeps(m, sx, hh_pre, s_pre, two_n, cut), k2p = screen2_prefix_keeps(m, sx, hh_pre, hq_pre, two_n, cut);
+		if (k3 && !(k3p && k2p)) {
+			++g_violations;
+			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: kept by three products on the whole rows, prefix three %d, prefix two %d",
+			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3p, (int)k2p);
+		}
+		++g_tests; g_kept3 += k3; g_kept3p += k3p; g_kept2p += k2p;
+	}
+}
+int check_screens() {
+	const int before = g_bad_checks;
+	for (uint32_t n = 0; n <= MAX_PART; ++n) { uint32_t c[9]; each_table(c, 0, n); }
+	for (const auto& p : g_tables) for (const auto& x : g_tables) check_pair(p.data(), x.data());
+	// a stop at the row's end is the screen itself
+	for (const auto& p : g_tables) {
+		const uint32_t* c = p.data();
+		uint32_t n = 0; for (int k = 0; k < 9; ++k) n += c[k];
+		if (!n) continue;
+		const ScreenMargins m{c[3] + c[4] + c[5], c[6] + c[7] + c[8], c[1] + c[4] + c[7], c[2] + c[5] + c[8]};
+		const SuffixMargins none{0, 0, 0, 0};
+		for (const double r2 : {0.1, 0.5, 0.8}) {
+			const double cut = r2 * (1.0 - 1e-6);
+			CHECK(screen3_prefix_keeps(m, none, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut) == screen3_keeps(m, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut), "empty suffix, three");
+			CHECK(screen2_prefix_keeps(m, none, c[4], c[5], 2.0 * n, cut) == screen2_keeps(m, c[4], c[5], 2.0 * n, cut), "empty suffix, two");
+		}
+	}
+	return g_bad_checks != before;
+}
+
+// ---- 2. the table builder with stops -----------------------------------------------------------------------------------------
+struct Case { uint32_t nA, nB; bool diag; uint32_t nchunks; int PA; CountSettings s; };
+struct HashStops {       // a stop per tile from its coordinates: 1 .. nchunks, a fifth of the tiles at the row's end
+	uint32_t nchunks;
+	uint32_t operator()(uint32_t yx) const {
+		uint32_t h = yx * 2654435761u; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+		return h % 5 == 0 ? nchunks : 1 + h % nchunks;
+	}
+};
+struct FullStops { uint32_t nchunks; uint32_t operator()(uint32_t) const { return nchunks; } };
+int check_table_case(const Case& c) {
+	const int before = g_bad_checks;
+	twk_hip_tile_desc t{};
+	t.rowA0 = 384; t.rowB0 = c.diag ? 384 : 1000; t.nA = c.nA; t.nB = c.nB; t.diag = c.diag ? 1 : 0;
+	const HashStops hs{c.nchunks};
+	std::vector<uint32_t> stops;
+	const CountTable tb = build_count_table(t, 2, c.diag, nullptr, c.nchunks, c.s, c.PA, &hs, &stops);
+	const CountTable plain = build_count_table(t, 2, c.diag, nullptr, c.nchunks, c.s, c.PA);
+	const uint32_t T = tb.n_tiles(), U = tb.n_units();
+	CHECK(tb.tiles == plain.tiles && stops.size() == T, "the tile list does not depend on the stops");
+	std::vector<std::vector<std::pair<uint32_t, uint32_t>>> of(T);
+	std::vector<int> flagged(T, 0);
+	for (uint32_t u = 0; u < U; ++u) {
+		const CountUnit& cu = tb.units[u];
+		const uint32_t tile = cu.tile & ~UNIT_WHOLE;
+		CHECK(tile < T && cu.c0 < cu.c1 && cu.c1 <= c.nchunks, "unit %u = tile %u [%u, %u)", u, tile, cu.c0, cu.c1);
+		if (tile >= T) continue;
+		CHECK(cu.yx == tb.tiles[tile], "unit %u yx", u);
+		of[tile].push_back({cu.c0, cu.c1});
+		if (cu.tile & UNIT_WHOLE) ++flagged[tile];
+	}
+	for (uint32_t k = 0; k < T; ++k) {
+		const uint32_t stop = hs(tb.tiles[k]);
+		CHECK(stops[k] == stop, "tile %u: stop %u recorded as %u", k, stop, stops[k]);
+		std::sort(of[k].begin(), of[k].end());
+		uint32_t at = 0;
+		for (const auto& r : of[k]) { CHECK(r.first == at, "tile %u: [%u, %u) after %u", k, r.first, r.second, at); at = r.second; }
+		CHECK(at == stop, "tile %u covered to %u, stop %u of %u", k, at, stop, c.nchunks);
+		if (of[k].size() > 1) CHECK(k >= tb.first_split, "tile %u split before first_split %u", k, tb.first_split);
+		// the kernel stores a unit's counts when it is flagged or covers [0, nchunks), and adds them otherwise: stored exactly when the unit is the tile's only one
+		const bool stored = of[k].size() == 1 && (flagged[k] || of[k][0].second == c.nchunks);
+		CHECK(stored == (of[k].size() == 1) && flagged[k] == ((of[k].size() == 1 && stop < c.nchunks) ? 1 : 0), "tile %u: %zu units, stop %u, %d flagged", k, of[k].size(), stop, flagged[k]);
+	}
+	// every stop at the row's end: the image of the table built without stops
+	const FullStops fs{c.nchunks};
+	const CountTable full = build_count_table(t, 2, c.diag, nullptr, c.nchunks, c.s, c.PA, &fs);
+	std::vector<uint32_t> a(full.words() + 1, 0), b(plain.words() + 1, 0);
+	full.pack(a.data()); plain.pack(b.data());
+	CHECK(full.words() == plain.words() && a == b && full.first_split == plain.first_split && full.n_queues == plain.n_queues, "stops at the row's end change the table");
+	for (int q = 0; q <= 8; ++q) CHECK(full.queue_begin[q] == plain.queue_begin[q], "queue %d", q);
+	return g_bad_checks != before;
+}
+int check_tables(int& n_cases) {
+	auto settings = [](uint32_t nb, uint32_t mc, uint32_t pr, uint32_t pc) { CountSettings s; s.n_blocks = nb; s.min_chunks = mc; s.patch_rows = pr; s.patch_cols = pc; return s; };
+	static const uint32_t SHAPES[7][2] = {{5, 9}, {100, 30}, {130, 130}, {200, 200}, {256, 256}, {700, 700}, {1100, 2300}};
+	int bad = 0;
+	for (const int PA : {0, 1}) for (const auto& sh : SHAPES) for (const bool diag : {false, true}) {
+		if (diag && sh[1] < sh[0]) continue;
+		bad += check_table_case(Case{sh[0], sh[1], diag, 137, PA, settings(512, 8, 8, 8)});      // whole tiles mostly
+		bad += check_table_case(Case{sh[0], sh[1], diag, 300, PA, settings(4, 8, 8, 8)});        // a guided tail of K-split units
+		bad += check_table_case(Case{sh[0], sh[1], diag, 137, PA, settings(4, 1, 8, 8)});        // ... down to single chunks
+		bad += check_table_case(Case{sh[0], sh[1], diag, 17, PA, settings(1, 1, 16, 32)});       // one block: every tile split
+		n_cases += 4;
+	}
+	return bad;
+}
+
+// ---- 3. the planner on the headline's law --------------------------------------------------------------------------------------
+int play_planner() {
+	const uint32_t M = 50000, N = 1000000, nchunks = (N + 1023) / 1024;
+	const double minR2 = 0.1, cut = minR2 * (1.0 - 1e-6), two_cost = 0.66;
+	std::vector<uint32_t> het(M), hom(M), suffix((size_t)2 * M * PREFIX_GRID);
+	for (uint32_t v = 0; v < M; ++v) {
+		const double p = 0.05 + 0.45 * (v + 0.5) / M;
+		het[v] = (uint32_t)std::llround(2 * p * (1 - p) * N); hom[v] = (uint32_t)std::llround(p * p * N);
+		for (uint32_t g = 0; g < PREFIX_GRID; ++g) {
+			const double behind = 1.0 - std::min<double>((double)prefix_stop_chunks(g, nchunks) * 1024.0, N) / N;
+			suffix[(size_t)(2 * v) * PREFIX_GRID + g] = (uint32_t)std::llround(het[v] * behind);
+			suffix[(size_t)(2 * v + 1) * PREFIX_GRID + g] = (uint32_t)std::llround(hom[v] * behind);
+		}
+	}
+	PlanEnv env; env.n_samples = N; env.Pmax = 2; env.nchunks = nchunks; env.minR2 = minR2; env.phased_math = false; env.het = het.data(); env.hom = hom.data();
+	const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
+	RegionPlan plan;
+	plan_region(env, g, plan);
+	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = 0.95;
+	printf("planner: %u variants x %u samples, r2 >= %g, rows of %u chunks, grid step %u chunks; two-product cut at sorted row %u (p = %.3f); %zu launches\n",
+	       M, N, minR2, nchunks, prefix_step(nchunks), plan.two_end, 0.05 + 0.45 * plan.two_end / M, plan.mine.size());
+	CountSettings cs;
+	double work_full = 0, work_done = 0, sum2_full = 0, sum2_done = 0, sum3_full = 0, sum3_done = 0, host_ms = 0;
+	uint64_t n_tiles = 0;
+	for (size_t i = 0; i < plan.mine.size(); ++i) {
+		const twk_hip_tile_desc& t = plan.mine[i];
+		const bool two = t.rowA0 + t.nA <= plan.two_end, diag = t.diag && t.rowA0 == t.rowB0;
+		const Geometry geo = tile_geometry(2, t, two ? 1 : 0);
+		std::vector<uint8_t> grid((size_t)geo.gy * geo.gx, (uint8_t)PREFIX_GRID);
+		std::vector<uint32_t> stops;
+		const PrefixTileStops stop_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, geo.gx, &grid, {PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID}};
+		const auto t0 = std::chrono::steady_clock::now();
+		const CountTable tb = build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &stop_of, &stops);
+		const auto t1 = std::chrono::steady_clock::now();
+		const CountTable plain = build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0);
+		const auto t2 = std::chrono::steady_clock::now();
+		host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count() - std::chrono::duration<double, std::milli>(t2 - t1).count();
+		uint64_t done = 0; uint32_t lo = nchunks, hi = 0;
+		for (const uint32_t s : stops) { done += s; lo = std::min(lo, s); hi = std::max(hi, s); }
+		const uint64_t full = (uint64_t)tb.n_tiles() * nchunks;
+		n_tiles += tb.n_tiles();
+		printf("  launch %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n", i, two ? "two  " : "three", t.rowA0, t.nA, t.rowB0, t.nB,
+		       tb.n_tiles(), lo, hi, full ? (double)done / (double)full : 0.0);
+		// (a two-product tile holds 128 x 64 variant pairs, a three-product tile 64 x 64: per tile and chunk twice the pairs at two_cost each)
+		const double w = two ? 2.0 * two_cost : 1.0;
+		work_full += w * (double)full; work_done += w * (double)done;
+		(two ? sum2_full : sum3_full) += (double)full; (two ? sum2_done : sum3_done) += (double)done;
+	}
+	const double all_full = sum2_full * 2.0 * two_cost + sum3_full, all_pairs = 2.0 * sum2_full + sum3_full;
+	printf("planner: two-product launches %.1f %% of the pairs (%.1f %% of today's count work), mean fraction of the row contracted %.4f; three-product launches %.1f %% of the pairs (%.1f %%), mean fraction %.4f\n",
+	       100.0 * 2.0 * sum2_full / all_pairs, 100.0 * sum2_full * 2.0 * two_cost / all_full, sum2_full ? sum2_done / sum2_full : 0.0,
+	       100.0 * sum3_full / all_pairs, 100.0 * sum3_full / all_full, sum3_full ? sum3_done / sum3_full : 0.0);
+	printf("planner: count work %.4f of today's (two-product pairs at %.2f of a three-product pair); %" PRIu64 " tiles, the stops cost %.1f ms of host time a call on this machine\n",
+	       work_full ? work_done / work_full : 0.0, two_cost, n_tiles, host_ms);
+	return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+	const bool planner = !(argc > 1 && std::strcmp(argv[1], "--no-planner") == 0);
+	const int bad_screen = check_screens();
+	printf("prefix-check: screens: %zu tables of up to %u samples, %" PRIu64 " (prefix table, suffix table, cut-off) tests; three products on the whole rows keep %" PRIu64
+	       ", the three-product prefix screen %" PRIu64 ", the two-product prefix screen %" PRIu64 "; violations %" PRIu64 "\n",
+	       g_tables.size(), MAX_PART, g_tests, g_kept3, g_kept3p, g_kept2p, g_violations);
+	int n_cases = 0;
+	const int bad_tables = check_tables(n_cases);
+	printf("prefix-check: table builder with stops: %d cases, %d bad\n", n_cases, bad_tables);
+	if (planner) play_planner();
+	printf("prefix-check: %s\n", (bad_screen || bad_tables || g_bad_checks) ? "FAILED" : "ok");
+	return (bad_screen || bad_tables || g_bad_checks) ? 1 : 0;
+}
