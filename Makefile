@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -170,6 +170,14 @@ topk-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/topk_key_check.cpp -o build/topk_key_check
 	./build/topk_key_check
+
+# The sample selection's table, compress and split by output words (csrc/hip/ld_subset_index.h) played block by block and lane by lane
+# against a field-by-field gather and an array of write counts with a border (csrc/tools/subset_index_check.cpp): host code only, under
+# AddressSanitizer and UBSan
+subset-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/subset_index_check.cpp -o build/subset_index_check
+	./build/subset_index_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -43,6 +43,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_score_annot - partitioned LD scores - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_bandmat_layout / twk_hip_ld_matrix_band / twk_hip_bandmat_last - the banded LD matrix - are three entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_topk / twk_hip_topk_last - top-k LD partners - are two entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_select_samples / twk_hip_selection / twk_hip_get_meta / twk_hip_set_hwe / twk_hip_select_last - sample subsets - are five entry points more; no struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -231,6 +232,52 @@ int twk_synth_plant_source(uint64_t seed, const twk_hip_plant* plant, uint32_t v
  * NULL. */
 int twk_hip_get_marginals(twk_hip_ctx* ctx, uint32_t* ac, uint32_t* n_het, uint32_t* n_hom,
                           uint32_t* n_miss_samples);
+
+/* ---- sample subsets ---------------------------------------------------- */
+/* LD over a chosen set of samples - one population of a cohort, PLINK's --keep - selected on the device from the data that is already
+ * there.  keep: n_keep sample indices into the data AS UPLOADED (the SOURCE), strictly ascending.  After the call the context is a
+ * problem of n_keep samples and the same variants, the WORKING SET, and that problem is indistinguishable from a context that received
+ * the subset through twk_hip_set_problem + twk_hip_upload_bitvectors: twk_hip_download_bitvectors returns the same data and mask words,
+ * padding bits zero; twk_hip_get_marginals and twk_hip_get_meta return the same numbers; every compute entry point returns the same
+ * bytes.  Sample k of the working set is source sample keep[k]; variant indices, pos and rid are untouched, and a variant that is
+ * monomorphic in the subset stays (the pair rules deal with ac = 0), so that indices stay comparable between subsets.
+ * THE SOURCE STAYS ON THE DEVICE: a second call selects from the source again, not from the previous selection - population after
+ * population from one upload - and twk_hip_select_samples(ctx, NULL, 0) drops the selection: the context is the source again, bit for
+ * bit, without a re-upload.  A list of all the samples is a selection like any other.
+ * MEMORY: the working set's rows live beside the source's: M_alloc * Wp' * 4 bytes, twice that while the source holds mask rows, where
+ * M_alloc = n_variants rounded up to a multiple of 128, plus 128, and Wp' = ceil(2 n_keep / 32) rounded up to a multiple of 32; the
+ * working mask rows are freed again when no working variant has missing data.  During the call 32 bytes per source word with a kept
+ * sample (the table) and 8 bytes per variant on top.  TWK_HIP_E_NOMEM with the byte count in twk_hip_last_error.
+ * RECOMPUTED ON THE DEVICE for the working set, from its rows: ac[v] = the ALT alleles of the kept samples (popcount of the data row);
+ * an[v] = the popcount of the mask row: two per kept sample with a missing genotype; missing[v] = an[v] != 0.  The mask rows are kept
+ * only while some working variant is missing, and a variant whose missing samples were all dropped is a variant without missing data:
+ * TWK_HIP_MODE_AUTO takes the phased math for it, as it would after a re-import.  `an` equals the importer's count except where a kept
+ * sample misses exactly ONE allele: the raw layout marks the whole sample and does not record that case (the importer counts 1, this
+ * counts 2), and the device reads `an` only as zero / non-zero.
+ * hwe IS LEFT AS UPLOADED: it only sets two flag bits of a record and its exact test lives in the host library; a caller that wants the
+ * subset's own Hardy-Weinberg P writes it with twk_hip_set_hwe, which changes the working set only - the next selection, and dropping
+ * the selection, bring the uploaded values back.
+ * All derived state - contraction planes, sorted plane sets, carrier lists, cached popcounts - is dropped as after an upload and
+ * rebuilt on next use; the log-factorial table sized for the source covers every subset.
+ * REFUSALS, on each of which nothing changes and a selection that was active stays active: TWK_HIP_E_INVALID for keep == NULL with
+ * n_keep != 0, an empty list, a list that is not strictly ascending or holds an index >= the source's sample count (twk_hip_last_error
+ * names the position); TWK_HIP_E_STATE before the first upload (or generator call).  WHILE A SELECTION IS ACTIVE twk_hip_upload_bitvectors,
+ * twk_hip_upload_rle and the synthetic generators return TWK_HIP_E_STATE: the caller drops it first.  twk_hip_set_problem discards
+ * source and selection alike.  A caller that never selects sees no change anywhere.
+ * The kernel (csrc/hip/ld_subset.hip.h) reads, per variant, the source words that hold a kept sample - once - and writes the compacted
+ * rows with plain stores, every word by one block: two calls give the same bytes.  There is NO reference counterpart (the reference
+ * computes over all samples of its input). */
+int twk_hip_select_samples(twk_hip_ctx* ctx, const uint32_t* keep, uint32_t n_keep);
+/* The sample count of the source and of the working set (either may be NULL); equal when no selection is active (or all are kept). */
+int twk_hip_selection(const twk_hip_ctx* ctx, uint32_t* n_source, uint32_t* n_selected);
+/* The metadata of variants [first, first + count) of the working set, as the engine holds it: what was uploaded, or what a selection
+ * recomputed (ac, an, missing) beside what it left alone (pos, rid, hwe). */
+int twk_hip_get_meta(twk_hip_ctx* ctx, uint32_t first, uint32_t count, twk_hip_variant_meta* out);
+/* Overwrite the hwe of variants [first, first + count) of the working set. */
+int twk_hip_set_hwe(twk_hip_ctx* ctx, uint32_t first, uint32_t count, const double* hwe);
+/* Of the context's last selection that ran the kernel: its device time in ms, the bytes of source rows it read (the words with a kept
+ * sample, of every variant, data and mask rows) and the bytes of working rows it wrote (any may be NULL). */
+int twk_hip_select_last(const twk_hip_ctx* ctx, double* select_ms, uint64_t* bytes_read, uint64_t* bytes_written);
 
 /* ---- compute ---------------------------------------------------------- */
 /* Raw contingency counts for one tile (debug/parity entry point; replaces the

@@ -41,6 +41,13 @@ struct twk_ld_settings {
 	double minP, minR2, maxR2, minDprime, maxDprime;
 	int32_t n_chunks, c_chunk;
 	std::vector<std::string> ival_strings;
+	// Not in the reference: LD over a subset of the input's samples (`--keep FILE`, `--remove FILE`: one sample name per line, blank lines
+	// and lines that start with '#' skipped; both: keep, then remove).  Every method that loads a .twk resolves the list against the
+	// header before any device work (csrc/host/twk_sample_list.h: a name that is not in the header, a name twice in one file, an unreadable
+	// file and an empty result are errors), loads the input as always and selects the samples on the GPU (twk_hip_select_samples); the
+	// variants' Hardy-Weinberg P is recomputed over the kept samples, as a re-import of the subset would carry it.  The sample count and
+	// the sample names of every output (.two header, PREFIX.samples.tsv, ##M_5_50) are then the kept samples', in header order.  Empty: all.
+	std::string keep_file, remove_file;
 };
 
 // What Score takes beyond twk_ld_settings.

@@ -16,6 +16,7 @@
 //   relate (ld_relate.hip.h) the raw layout transposed into planes of the samples -> count -> genotype-sharing counts and one statistic per sample pair
 //                          (twk_hip_relationship: its own launches, beside the variant launch path)
 //   topk (ld_topk.hip.h) cells -> one statistic of the pair's record -> a 64-bit key -> the k largest per variant, selected with integer atomic maxima (twk_hip_ld_topk)
+//   subset (ld_subset.hip.h) the raw rows compacted to a list of samples: a working copy beside the rows as uploaded (twk_hip_select_samples)
 //   (score, prune, clump, matrix, decay, aggregate, annot, bandmat and topk are the nine kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
@@ -57,6 +58,7 @@
 #include "ld_bandmat.hip.h"
 #include "ld_topk.hip.h"
 #include "ld_relate.hip.h"
+#include "ld_subset.hip.h"
 #include "ld_plan.h"
 #include "ld_form.h"
 #include "twk_delivery.h"
@@ -270,6 +272,16 @@ struct twk_hip_ctx {
 	DevBuf<uint32_t> raw;          // [M_alloc][Wp]
 	DevBuf<uint32_t> rawmask;      // [M_alloc][Wp] or null
 	bool any_missing = false;
+	bool has_data = false;         // an upload or a generator has filled rows since twk_hip_set_problem
+	// twk_hip_select_samples: while a selection is active the rows and the metadata as uploaded - the source - wait here, and raw, rawmask,
+	// N, Wp, Wu, any_missing, the metadata and everything derived from them describe the working set
+	struct Source {
+		bool active = false;
+		uint32_t N = 0, Wp = 0, Wu = 0;
+		DevBuf<uint32_t> raw, rawmask;
+		std::vector<twk_hip_variant_meta> h_meta;
+	} source;
+	struct { double ms = 0; uint64_t bytes_read = 0, bytes_written = 0; } select_last;      // of the last selection that ran the kernel
 	// metadata (device SoA) + host mirror
 	DevBuf<uint32_t> d_ac, d_an, d_pos, d_rid, d_missing;
 	DevBuf<double> d_hwe;
@@ -371,7 +383,8 @@ void free_problem(twk_hip_ctx* c) {
 	c->d_counts.reset(); c->d_walk.reset(); c->d_prune_keep.reset(); c->d_clump_order.reset(); c->d_clump_index.reset();
 	c->d_decay.reset(); c->d_agg_key.reset();
 	c->h_meta.clear();
-	c->N = c->M = c->M_alloc = 0; c->any_missing = false;
+	c->source.raw.reset(); c->source.rawmask.reset(); c->source.h_meta.clear(); c->source.active = false;
+	c->N = c->M = c->M_alloc = 0; c->any_missing = false; c->has_data = false;
 }
 
 int plane_kind_for(const twk_hip_ctx* c, bool phased) {
@@ -1653,7 +1666,7 @@ int twk_hip_set_problem(twk_hip_ctx* c, uint32_t n_samples, uint32_t n_variants)
 int twk_hip_upload_bitvectors(twk_hip_ctx* c, uint32_t first, uint32_t count, const uint64_t* data,
                               const uint64_t* mask, size_t stride64, const twk_hip_variant_meta* meta) {
 	if (!c || !data || !meta || count == 0) return TWK_HIP_E_INVALID;
-	if (!c->raw) return TWK_HIP_E_STATE;
+	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;      // (a selection is dropped first: twk_hip_select_samples)
 	const size_t w64 = ((size_t)2 * c->N + 63) / 64;
 	if (stride64 < w64 || (uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
 	// Validate everything before any device or context state changes.  A variant's missing-data
@@ -1666,6 +1679,7 @@ int twk_hip_upload_bitvectors(twk_hip_ctx* c, uint32_t first, uint32_t count, co
 	}
 	HIPCHK(c, hipSetDevice(c->device));
 	free_planes(c);                                             // derived planes are stale now
+	c->has_data = true;
 	HIPCHK(c, hipMemcpy2D(c->raw + (size_t)first * c->Wp, (size_t)c->Wp * 4, data, stride64 * 8, w64 * 8, count, hipMemcpyHostToDevice));
 	hipLaunchKernelGGL(k_clear_tail, dim3((c->Wp + 255) / 256, std::min<uint32_t>(count, 65535u)), dim3(256), 0, c->s_compute,
 	                   c->raw + (size_t)first * c->Wp, c->Wp, c->N, count);
@@ -1689,7 +1703,7 @@ int twk_hip_upload_bitvectors(twk_hip_ctx* c, uint32_t first, uint32_t count, co
 int twk_hip_upload_rle(twk_hip_ctx* c, uint32_t first, uint32_t count, const void* bytes, size_t n_bytes,
                        const twk_hip_rle_desc* desc, const twk_hip_variant_meta* meta) {
 	if (!c || !bytes || !desc || !meta || count == 0) return TWK_HIP_E_INVALID;
-	if (!c->raw) return TWK_HIP_E_STATE;
+	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;
 	if ((uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
 	// validate before anything changes (same rules as twk_hip_upload_bitvectors)
 	bool any_mask = false;
@@ -1711,6 +1725,7 @@ int twk_hip_upload_rle(twk_hip_ctx* c, uint32_t first, uint32_t count, const voi
 	chunk_base[count] = (uint32_t)n_chunks;
 	HIPCHK(c, hipSetDevice(c->device));
 	free_planes(c);                                             // derived planes are stale now
+	c->has_data = true;
 	// descriptors | chunk sums (u64 per block) | first block of every variant
 	const size_t desc_bytes = (size_t)count * sizeof(RleDesc) + (size_t)n_chunks * 8 + ((size_t)count + 1) * 4;
 	const size_t run_bytes = n_bytes + 32;                                  // the kernel's dword loads run up to 19 bytes past the last run
@@ -1778,9 +1793,10 @@ int twk_hip_generate_synthetic_planted(twk_hip_ctx* c, uint64_t seed, uint32_t f
 	if ((uint64_t)first_variant + (c ? c->M : 0) > 0xFFFFFFFFull) return TWK_HIP_E_INVALID;
 	SynthPlant pl;
 	if (!plant_of(plant, pl)) return TWK_HIP_E_INVALID;
-	if (!c->raw) return TWK_HIP_E_STATE;
+	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;
 	HIPCHK(c, hipSetDevice(c->device));
 	free_planes(c);
+	c->has_data = true;
 	c->rawmask.reset();
 	c->any_missing = false;
 	hipLaunchKernelGGL(k_synth, dim3((c->Wp + 255) / 256, std::min<uint32_t>(c->M, 65535u)), dim3(256), 0, c->s_compute, c->raw, c->Wp, c->N, c->M, seed, first_variant, pl);
@@ -1859,6 +1875,149 @@ int twk_hip_get_marginals(twk_hip_ctx* c, uint32_t* ac, uint32_t* n_het, uint32_
 			if (n_miss) n_miss[v] = P == 3 ? rp[(size_t)v * P + 2] : 0;
 		}
 	}
+	return TWK_HIP_OK;
+}
+
+extern "C++" {
+namespace {
+// The selection goes: the rows and the metadata as uploaded are the context's again, bit for bit (nothing is copied but the metadata).
+int drop_selection(twk_hip_ctx* c) {
+	if (!c->source.active) return TWK_HIP_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	free_planes(c);
+	c->raw = std::move(c->source.raw); c->rawmask = std::move(c->source.rawmask);
+	c->N = c->source.N; c->Wp = c->source.Wp; c->Wu = c->source.Wu;
+	c->h_meta = std::move(c->source.h_meta); c->source.h_meta.clear();
+	c->source.active = false;
+	c->any_missing = false;                                     // (upload_meta sets it from the metadata)
+	const std::vector<twk_hip_variant_meta> meta = c->h_meta;
+	return upload_meta(c, 0, c->M, meta.data());
+}
+}  // namespace
+}
+
+int twk_hip_select_samples(twk_hip_ctx* c, const uint32_t* keep, uint32_t n_keep) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (!keep && n_keep != 0) { snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: no list, but a count of %u", n_keep); return TWK_HIP_E_INVALID; }
+	if (!c->raw || !c->has_data) return TWK_HIP_E_STATE;
+	if (!keep) return drop_selection(c);
+	const uint32_t n_src = c->source.active ? c->source.N : c->N, w_src = c->source.active ? c->source.Wp : c->Wp;
+	if (n_keep == 0) { snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: an empty list"); return TWK_HIP_E_INVALID; }
+	const uint32_t Wp = round_up((uint32_t)((2ull * n_keep + 31) / 32), KC), Wu = round_up((n_keep + 31) / 32, KC);
+	std::vector<SubsetEntry> table; std::vector<SubsetChunk> chunks;
+	uint32_t bad_at = 0;
+	if (n_keep > n_src || !build_subset_table(keep, n_keep, n_src, Wp, table, chunks, &bad_at)) {
+		if (n_keep > n_src) snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: %u samples listed, the source has %u", n_keep, n_src);
+		else snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: keep[%u] = %u is not above its predecessor and below the source's %u samples", bad_at, keep[bad_at], n_src);
+		return TWK_HIP_E_INVALID;
+	}
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	const uint32_t* src_raw = c->source.active ? c->source.raw.get() : c->raw.get();
+	const uint32_t* src_mask = c->source.active ? c->source.rawmask.get() : c->rawmask.get();
+	const std::vector<twk_hip_variant_meta>& src_meta = c->source.active ? c->source.h_meta : c->h_meta;
+	const int n_planes = src_mask ? 2 : 1;
+	// everything new is built beside what the context holds, and nothing of the context changes until all of it stands
+	const size_t row_words = (size_t)c->M_alloc * Wp;
+	DevBuf<uint32_t> rows[2], d_pop[2];
+	DevBuf<SubsetEntry> d_table; DevBuf<SubsetChunk> d_chunks;
+	{
+		hipError_t e = hipSuccess;
+		for (int p = 0; p < n_planes && e == hipSuccess; ++p) e = rows[p].reserve(row_words, row_words, nullptr);
+		for (int p = 0; p < n_planes && e == hipSuccess; ++p) e = d_pop[p].reserve(c->M, c->M, nullptr);
+		if (e == hipSuccess) e = d_table.reserve(table.size(), table.size(), nullptr);
+		if (e == hipSuccess) e = d_chunks.reserve(chunks.size(), chunks.size(), nullptr);
+		if (e != hipSuccess) {
+			(void)hipGetLastError();
+			snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: the working copy of %u variants x %u samples needs %llu bytes of device memory beside the source: %s",
+			         c->M, n_keep, (unsigned long long)(row_words * 4 * n_planes), hipGetErrorString(e));
+			return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+		}
+	}
+	Events ev;
+	HIPCHK(c, ev.add(2));
+	HIPCHK(c, hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(SubsetEntry), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(SubsetChunk), hipMemcpyHostToDevice, c->s_compute));
+	// (the rows behind the last variant are padding of the count kernel's tiles: zeros, as twk_hip_set_problem leaves them)
+	for (int p = 0; p < n_planes; ++p) HIPCHK(c, hipMemsetAsync(rows[p] + (size_t)c->M * Wp, 0, (size_t)(c->M_alloc - c->M) * Wp * 4, c->s_compute));
+	SubsetArgs a{};
+	a.src[0] = src_raw; a.src[1] = src_mask; a.dst[0] = rows[0]; a.dst[1] = rows[1];
+	a.table = d_table; a.chunks = d_chunks; a.w_src = w_src; a.w_dst = Wp; a.n_rows = c->M;
+	const uint32_t row_groups = (c->M + SUBSET_ROWS - 1) / SUBSET_ROWS;
+	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
+	hipLaunchKernelGGL(k_subset_rows, dim3((unsigned)chunks.size(), std::min<uint32_t>(row_groups, 65535u), n_planes), dim3(256), 0, c->s_compute, a);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
+	// ac = ALT alleles of the kept samples, an = two per kept sample with a missing genotype: popcounts of the new rows
+	std::vector<uint32_t> pop[2];
+	for (int p = 0; p < n_planes; ++p) {
+		hipLaunchKernelGGL(k_row_popcount, dim3((c->M + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)rows[p], Wp, c->M, d_pop[p].get());
+		HIPCHK(c, hipGetLastError());
+		pop[p].resize(c->M);
+		HIPCHK(c, hipMemcpyAsync(pop[p].data(), d_pop[p], (size_t)c->M * 4, hipMemcpyDeviceToHost, c->s_compute));
+	}
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	float ms = 0.f;
+	HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+	std::vector<twk_hip_variant_meta> meta = src_meta;
+	bool any_missing = false;
+	for (uint32_t v = 0; v < c->M; ++v) {
+		meta[v].ac = pop[0][v];
+		meta[v].an = n_planes == 2 ? pop[1][v] : 0;
+		meta[v].missing = meta[v].an != 0;
+		any_missing = any_missing || meta[v].missing;
+	}
+	// ... and now the context changes hands
+	free_planes(c);
+	if (!c->source.active) {
+		c->source.raw = std::move(c->raw); c->source.rawmask = std::move(c->rawmask);
+		c->source.N = c->N; c->source.Wp = c->Wp; c->source.Wu = c->Wu;
+		c->source.h_meta = c->h_meta;
+		c->source.active = true;
+	}
+	c->raw = std::move(rows[0]);
+	if (any_missing) c->rawmask = std::move(rows[1]); else c->rawmask.reset();      // the mask rows are kept only while a working variant has missing data
+	c->N = n_keep; c->Wp = Wp; c->Wu = Wu;
+	c->any_missing = false;                                                         // (upload_meta sets it from the metadata)
+	c->select_last.ms = ms;
+	c->select_last.bytes_read = (uint64_t)c->M * table.size() * 4 * n_planes;
+	c->select_last.bytes_written = (uint64_t)c->M * Wp * 4 * n_planes;
+	return upload_meta(c, 0, c->M, meta.data());
+}
+
+int twk_hip_selection(const twk_hip_ctx* c, uint32_t* n_source, uint32_t* n_selected) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (n_source) *n_source = c->source.active ? c->source.N : c->N;
+	if (n_selected) *n_selected = c->N;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_get_meta(twk_hip_ctx* c, uint32_t first, uint32_t count, twk_hip_variant_meta* out) {
+	if (!c || !out || count == 0) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if ((uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
+	std::copy(c->h_meta.begin() + first, c->h_meta.begin() + first + count, out);
+	return TWK_HIP_OK;
+}
+
+int twk_hip_set_hwe(twk_hip_ctx* c, uint32_t first, uint32_t count, const double* hwe) {
+	if (!c || !hwe || count == 0) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if ((uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	HIPCHK(c, hipMemcpy(c->d_hwe + first, hwe, (size_t)count * 8, hipMemcpyHostToDevice));
+	for (uint32_t i = 0; i < count; ++i) c->h_meta[first + i].hwe = hwe[i];
+	return TWK_HIP_OK;
+}
+
+int twk_hip_select_last(const twk_hip_ctx* c, double* select_ms, uint64_t* bytes_read, uint64_t* bytes_written) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (select_ms) *select_ms = c->select_last.ms;
+	if (bytes_read) *bytes_read = c->select_last.bytes_read;
+	if (bytes_written) *bytes_written = c->select_last.bytes_written;
 	return TWK_HIP_OK;
 }
 

@@ -173,6 +173,8 @@ static int run_command(const Command<Own>& cmd, int argc, char** argv) {
 			if (settings.l_window <= 0) return !fail("Cannot have a non-positive window size");
 			break;
 		}
+		case 1006: settings.keep_file = optarg; break;        // --keep FILE / --remove FILE (not in the reference): LD over a subset of the samples,
+		case 1007: settings.remove_file = optarg; break;      // twk_ld_settings::keep_file.  Long names only, as --annot: the usage texts answer as they always have
 		case 1000: {      // --engine-option key=value (not in the reference): twk_ld::SetEngineOption
 			const std::string a(optarg);
 			const size_t eq = a.find('=');
@@ -207,13 +209,13 @@ static const struct option CALC_LONG_OPTIONS[] = {
 	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 	{"samples", optional_argument, 0, 'S'}, {"minR2", optional_argument, 0, 'r'}, {"detailedProgress", no_argument, 0, 'd'},
 	{"silent", no_argument, 0, 's'}, {"windowBases", optional_argument, 0, 'w'},
-	{"engine-option", required_argument, 0, 1000}, {0, 0, 0, 0}};
+	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, {0, 0, 0, 0}};
 static const struct option REDUCE_LONG_OPTIONS[] = {
 	{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
 	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
 	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
-	{"engine-option", required_argument, 0, 1000}, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
+	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
 	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'}, {"band", no_argument, 0, 1003},
 	{"top", required_argument, 0, 1004}, {"top-stat", required_argument, 0, 1005},
 	{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
@@ -221,7 +223,7 @@ static const struct option REDUCE_LONG_OPTIONS[] = {
 	{0, 0, 0, 0}};
 static const struct option RELATIONSHIP_LONG_OPTIONS[] = {
 	{"input", required_argument, 0, 'i'}, {"interval", required_argument, 0, 'I'}, {"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'},
-	{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000},
+	{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007},
 	{"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'}, {"minR2", required_argument, 0, 'r'}, {"windowBases", required_argument, 0, 'w'},
 	{"parts", required_argument, 0, 'c'}, {"partStart", required_argument, 0, 'C'}, {"minP", required_argument, 0, 'P'}, {0, 0, 0, 0}};
 
@@ -849,8 +851,11 @@ static int scalc(int argc, char** argv) {
 	}
 	tomahawk::twk_ld_settings settings;
 	int c;
-	while ((c = getopt(argc, argv, "i:o:t:I:mMb:r:R:P:k:w:?")) != -1) {
+	static const struct option long_options[] = {{"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, {0, 0, 0, 0}};
+	while ((c = getopt_long(argc, argv, "i:o:t:I:mMb:r:R:P:k:w:?", long_options, nullptr)) != -1) {
 		switch (c) {
+		case 1006: settings.keep_file = optarg; break;
+		case 1007: settings.remove_file = optarg; break;
 		case 'i': settings.in = optarg; break;
 		case 'o': settings.out = optarg; break;
 		case 'I': settings.ival_strings.push_back(optarg); break;

@@ -1,5 +1,6 @@
 // Small C API over the host library for tests, tools and the benchmark harness
 // (ctypes-friendly; plain pointers and sizes).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include "twk_import.h"
 #include "twk_record_sink.h"
 #include "twk_repcodec.h"
+#include "twk_sample_list.h"
 
 using namespace tomahawk;
 
@@ -309,12 +311,39 @@ int twk_import_vcf(const char* in, const char* out, double threshold_miss, doubl
 
 double twk_hwe_exact(uint64_t hom1, uint64_t het, uint64_t hom2) { return hardy_weinberg_exact(hom1, het, hom2); }
 
+// resolve_sample_list (twk_sample_list.h) on `n_names` header names: keep / remove are paths, NULL or "" for "not given".  -> 0 with the
+// kept indices, ascending, in out[0 .. *n_out) (at most cap of them are written; *n_out is the count in any case); 1 with the message in
+// err (NUL terminated, truncated to err_cap).
+int twk_resolve_samples(const char* const* names, uint32_t n_names, const char* keep, const char* remove, uint32_t* out, uint32_t cap,
+                        uint32_t* n_out, char* err, size_t err_cap) try {
+	std::vector<std::string> header;
+	for (uint32_t s = 0; s < n_names; ++s) header.emplace_back(names[s] ? names[s] : "");
+	std::vector<uint32_t> ids; std::string msg;
+	const bool ok = resolve_sample_list(header, keep ? keep : "", remove ? remove : "", ids, msg);
+	if (err && err_cap) { std::strncpy(err, msg.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+	if (n_out) *n_out = (uint32_t)ids.size();
+	if (ok && out) std::copy(ids.begin(), ids.begin() + std::min<size_t>(cap, ids.size()), out);
+	return ok ? 0 : 1;
+} catch (...) { return -9; }
+
 // Header literals of a .two / .twk (NUL terminated, truncated to cap).
 int twk_file_header_literals(const char* path, int is_two, char* out, size_t cap) try {
 	Header h;
 	if (is_two) { TwoReader r; if (!r.open(path)) return -2; h = r.hdr; }
 	else { TwkReader r; if (!r.open(path)) return -2; h = r.hdr; }
 	if (out && cap) { std::strncpy(out, h.literals.c_str(), cap - 1); out[cap - 1] = 0; }
+	return 0;
+} catch (...) { return -9; }
+
+// The sample names of a .two / .twk header, one per line (NUL terminated, truncated to cap); *n_samples (may be NULL): their number.
+int twk_file_sample_names(const char* path, int is_two, char* out, size_t cap, uint32_t* n_samples) try {
+	Header h;
+	if (is_two) { TwoReader r; if (!r.open(path)) return -2; h = r.hdr; }
+	else { TwkReader r; if (!r.open(path)) return -2; h = r.hdr; }
+	std::string text;
+	for (const std::string& name : h.samples) { text += name; text += '\n'; }
+	if (out && cap) { std::strncpy(out, text.c_str(), cap - 1); out[cap - 1] = 0; }
+	if (n_samples) *n_samples = (uint32_t)h.samples.size();
 	return 0;
 } catch (...) { return -9; }
 

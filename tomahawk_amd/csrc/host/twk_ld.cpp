@@ -35,9 +35,11 @@
 #include "twk_aggregate_landscape.h"
 #include "twk_format.h"
 #include "twk_hip.h"
+#include "twk_import.h"
 #include "twk_ld_names.h"
 #include "twk_parallel.h"
 #include "twk_record_sink.h"
+#include "twk_sample_list.h"
 #include "twk_util.h"
 
 #ifndef TWK_AMD_VERSION
@@ -531,6 +533,35 @@ static bool create_devices(DeviceCtxs& dc, int n_gpus, const std::vector<std::pa
 	}
 	return true;
 }
+// `--keep` / `--remove`: the context, loaded with every sample of the input, becomes the problem of the kept samples (twk_hip_select_samples:
+// selected on the device, ac / an / missing recomputed there), and every variant's Hardy-Weinberg P is recomputed over them - the genotype
+// counts from the device's marginals, the importer's exact test on T host threads - so that the context holds what a re-import of the
+// subset would have uploaded.  meta_out (may be null): the caller's copy of the metadata follows.
+static bool apply_sample_selection(twk_hip_ctx* ctx, const std::vector<uint32_t>& keep, uint32_t M, uint32_t T, std::vector<twk_hip_variant_meta>* meta_out) {
+	if (keep.empty() || M == 0) return true;
+	if (!hip_ok(ctx, twk_hip_select_samples(ctx, keep.data(), (uint32_t)keep.size()), "twk_hip_select_samples")) return false;
+	std::vector<uint32_t> het(M), hom(M), miss(M);
+	if (!hip_ok(ctx, twk_hip_get_marginals(ctx, nullptr, het.data(), hom.data(), miss.data()), "twk_hip_get_marginals")) return false;
+	std::vector<double> hwe(M);
+	const uint64_t n = keep.size();
+	const size_t piece = 4096, n_pieces = (M + piece - 1) / piece;
+	struct None {};
+	const bool ok = par::ordered_parallel<None>(n_pieces, (int)T,
+		[&](size_t i, None&) {
+			for (size_t v = i * piece; v < std::min<size_t>(M, (i + 1) * piece); ++v)
+				hwe[v] = hardy_weinberg_exact(n - het[v] - hom[v] - miss[v], het[v], hom[v]);      // over the complete genotypes, as the importer counts them
+			return true;
+		},
+		[](size_t, None&) { return true; });
+	if (!ok) return false;
+	if (!hip_ok(ctx, twk_hip_set_hwe(ctx, 0, M, hwe.data()), "twk_hip_set_hwe")) return false;
+	if (meta_out) {
+		meta_out->resize(M);
+		if (!hip_ok(ctx, twk_hip_get_meta(ctx, 0, M, meta_out->data()), "twk_hip_get_meta")) return false;
+	}
+	return true;
+}
+
 static int gpus_from_env() {
 	if (const char* g = std::getenv("TWK_HIP_GPUS")) { const int n = std::atoi(g); if (n >= 1) return std::min(n, 64); }
 	return 1;
@@ -803,12 +834,30 @@ bool twk_ld::twk_ld_impl::run(twk_ld_settings& settings, const Header& hdr, cons
 namespace {
 struct Selection {
 	TwkReader reader;
-	uint32_t n_samples = 0;
+	uint32_t n_samples = 0;          // the samples the run computes over: the header's, or (--keep / --remove) the kept ones - reader.hdr.samples names exactly these
+	uint32_t n_source = 0;           // the samples of the input: what is uploaded
+	std::vector<uint32_t> keep;      // --keep / --remove: the kept samples' indices in the input, ascending; empty: no selection
 	Balancer bal;
 	std::vector<uint32_t> sel;       // the L range's blocks, then (square chunk only) the R range's
 	uint32_t nL = 0, nR = 0, M = 0;
 };
 }  // namespace
+// --keep / --remove resolved against the header, before any device work: keep = the kept samples' indices in the input, and the header's
+// sample list becomes the kept names, so that whatever writes a sample count or sample names writes the kept ones.  Neither option:
+// nothing changes and keep stays empty.
+static bool select_samples(const twk_ld_settings& settings, Header& hdr, std::vector<uint32_t>& keep) {
+	keep.clear();
+	if (settings.keep_file.empty() && settings.remove_file.empty()) return true;
+	std::string err;
+	if (!resolve_sample_list(hdr.samples, settings.keep_file, settings.remove_file, keep, err)) { std::cerr << stamp("ERROR") << err << "..." << std::endl; return false; }
+	std::vector<std::string> names;
+	names.reserve(keep.size());
+	for (uint32_t s : keep) names.push_back(hdr.samples[s]);
+	std::cerr << stamp("LOG") << "Keeping " << pretty(keep.size()) << " of " << pretty(hdr.samples.size()) << " samples..." << std::endl;
+	hdr.samples.swap(names);
+	return true;
+}
+
 static bool select_blocks(twk_ld_settings& settings, Selection& S, bool* nothing_to_do) {
 	*nothing_to_do = false;
 	TwkReader& reader = S.reader;
@@ -820,6 +869,8 @@ static bool select_blocks(twk_ld_settings& settings, Selection& S, bool* nothing
 		std::cerr << stamp("LOG") << "Note: -m/-M are CPU memory-saving modes; the GPU engine keeps dense bit-planes in HBM." << std::endl;
 
 	if (!open_input(reader, settings.in, true)) return false;
+	S.n_source = (uint32_t)reader.hdr.samples.size();
+	if (!select_samples(settings, reader.hdr, S.keep)) return false;
 	const uint32_t n_samples = S.n_samples = (uint32_t)reader.hdr.samples.size();
 	std::cerr << stamp("LOG") << "Samples: " << pretty(n_samples) << "..." << std::endl;
 
@@ -925,7 +976,9 @@ bool twk_ld::Compute() {
 		std::vector<std::thread> th;
 		for (int g = 0; g < n_gpus; ++g) th.emplace_back([&, g] {
 			if (sel_g[g].empty()) return;
-			if (!load_blocks(settings.in, reader, sel_g[g], std::max<uint32_t>(1, T / (uint32_t)n_gpus), {dc.ctx[g]}, n_samples, rid_g[g], pos_g[g])) ok[g] = 0;
+			const uint32_t Tg = std::max<uint32_t>(1, T / (uint32_t)n_gpus);
+			if (!load_blocks(settings.in, reader, sel_g[g], Tg, {dc.ctx[g]}, S.n_source, rid_g[g], pos_g[g])) ok[g] = 0;
+			else if (!apply_sample_selection(dc.ctx[g], S.keep, (uint32_t)rid_g[g].size(), Tg, nullptr)) ok[g] = 0;
 		});
 		for (auto& t : th) t.join();
 		for (int g = 0; g < n_gpus; ++g) {
@@ -934,7 +987,8 @@ bool twk_ld::Compute() {
 			std::copy(pos_g[g].begin(), pos_g[g].end(), mImpl->pos.begin() + spec.slabs[g].first);
 		}
 	} else {
-		if (!load_blocks(settings.in, reader, sel, T, dc.ctx, n_samples, mImpl->rid, mImpl->pos)) return false;
+		if (!load_blocks(settings.in, reader, sel, T, dc.ctx, S.n_source, mImpl->rid, mImpl->pos)) return false;
+		for (twk_hip_ctx* c : dc.ctx) if (!apply_sample_selection(c, S.keep, M, T, nullptr)) return false;
 	}
 	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
 	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
@@ -1007,7 +1061,8 @@ struct ReduceCommand {
 		t_load = clock::now();
 		const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
 		std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
-		if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_samples, rid, pos, meta)) return failed;
+		if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_source, rid, pos, meta)) return failed;
+		if (!apply_sample_selection(ctx, S.keep, M, T, meta)) return failed;
 		std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
 		          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
 		mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
@@ -1673,7 +1728,9 @@ bool twk_ld::ComputeSingle(bool verbose, bool) {
 	settings.single = true;
 	TwkReader reader;
 	if (!open_input(reader, settings.in, verbose)) return false;
-	const uint32_t n_samples = (uint32_t)reader.hdr.samples.size();
+	const uint32_t n_samples = (uint32_t)reader.hdr.samples.size();      // (of the input: what is uploaded)
+	std::vector<uint32_t> keep;
+	if (!select_samples(settings, reader.hdr, keep)) return false;
 	Interval tgt;
 	if (!parse_interval(settings.ival_strings[0], reader.hdr, tgt)) return false;
 	// Flanks (ld.cpp:145-153), 1-based inclusive matching of pos+1 (ld.cpp:192):
@@ -1725,10 +1782,11 @@ bool twk_ld::ComputeSingle(bool verbose, bool) {
 	}
 	if (!hip_ok(ctx, twk_hip_upload_bitvectors(ctx, 0, M, data.data(), any_mask ? mask.data() : nullptr, w64, meta.data()),
 	            "twk_hip_upload_bitvectors")) return false;
+	if (!apply_sample_selection(ctx, keep, M, (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus())), nullptr)) return false;
 	RunSpec spec;
 	spec.nA = nT; spec.nB = nO; spec.triangleA = true; spec.rectAB = true;
 	spec.options = TWK_HIP_OPT_KEEP_LOW_AC | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);      // the skip is commented out in CalculateSingle (:2267-2269)
-	return mImpl->run(settings, reader.hdr, dc.ctx, n_samples, &spec);
+	return mImpl->run(settings, reader.hdr, dc.ctx, (uint32_t)reader.hdr.samples.size(), &spec);
 }
 
 }  // namespace tomahawk

@@ -23,7 +23,7 @@ NO_PARTNER = 0xFFFFFFFF    # TWK_HIP_NO_PARTNER: ld_topk's idx for a slot that i
 TOPK_MAX = 32              # TWK_HIP_TOPK_MAX
 STAT_R, STAT_R2, STAT_D, STAT_DPRIME = 0, 1, 2, 3      # TWK_HIP_STAT_*: the statistic ld_matrix fills in
 REL_IBS, REL_IBS0, REL_KING = 0, 1, 2      # TWK_HIP_REL_*: the statistic relationship fills in
-E_OVERFLOW = -4
+E_INVALID, E_OVERFLOW, E_STATE = -1, -4, -5      # TWK_HIP_E_*
 
 # twk_hip_record (include/twk_hip.h): 104 bytes
 RECORD_DTYPE = np.dtype([("idxA", "<u4"), ("idxB", "<u4"), ("flags", "<u4"), ("_pad", "<u4"),
@@ -196,6 +196,11 @@ def load_library() -> C.CDLL:
     lib.twk_synth_planted_bitvector.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(Plant), p]
     lib.twk_synth_plant_source.argtypes = [C.c_uint64, C.POINTER(Plant), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
     lib.twk_hip_get_marginals.argtypes = [p, p, p, p, p]
+    lib.twk_hip_select_samples.argtypes = [p, p, C.c_uint32]
+    lib.twk_hip_selection.argtypes = [p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.twk_hip_get_meta.argtypes = [p, C.c_uint32, C.c_uint32, p]
+    lib.twk_hip_set_hwe.argtypes = [p, C.c_uint32, C.c_uint32, p]
+    lib.twk_hip_select_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_count_tile.argtypes = [p, C.c_int, C.POINTER(_Tile), p]
     lib.twk_hip_ld_tile.argtypes = [p, C.c_int, C.POINTER(_Tile), C.POINTER(_Filters), p, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -491,6 +496,48 @@ class HipLd:
         self._check(self._lib.twk_hip_get_marginals(self._ctx, ac.ctypes.data, het.ctypes.data, hom.ctypes.data,
                                                     miss.ctypes.data), "twk_hip_get_marginals")
         return ac, het, hom, miss
+
+    # ---- sample subsets (twk_hip_select_samples: the data stays on the device as uploaded, the context works on the kept samples) ----
+    def select_samples(self, keep):
+        """keep: strictly ascending sample indices into the data as uploaded (any integer array-like), or None to drop the selection.
+        Afterwards the context is a problem of len(keep) samples: n_samples, download(), marginals(), meta() and every compute call
+        are those of the subset.  A second call selects from the uploaded data again."""
+        if keep is None:
+            self._check(self._lib.twk_hip_select_samples(self._ctx, None, 0), "twk_hip_select_samples")
+        else:
+            k = np.asarray(keep)
+            if k.size and not np.issubdtype(k.dtype, np.integer):
+                raise TypeError("select_samples: sample indices must be integers")
+            if k.size and (k.min() < 0 or k.max() > 0xFFFFFFFF):
+                raise HipError(E_INVALID, "twk_hip_select_samples", "a sample index outside 0 .. 2^32 - 1")
+            k = np.ascontiguousarray(k.reshape(-1), dtype=np.uint32)
+            buf = k if k.size else np.zeros(1, dtype=np.uint32)          # (an empty list is the engine's to refuse: not NULL, which drops)
+            self._check(self._lib.twk_hip_select_samples(self._ctx, buf.ctypes.data, k.size), "twk_hip_select_samples")
+        self.n_samples = self.selection()[1]
+
+    def selection(self):
+        """-> (samples of the data as uploaded, samples of the working set); equal when no selection is active."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.twk_hip_selection(self._ctx, C.byref(a), C.byref(b)), "twk_hip_selection")
+        return int(a.value), int(b.value)
+
+    def meta(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """-> META_DTYPE[count]: the working set's metadata as the engine holds it (after a selection: ac, an, missing recomputed)."""
+        count = self.n_variants - first if count is None else count
+        out = np.zeros(count, dtype=META_DTYPE)
+        self._check(self._lib.twk_hip_get_meta(self._ctx, first, count, out.ctypes.data), "twk_hip_get_meta")
+        return out
+
+    def set_hwe(self, hwe, first: int = 0):
+        """Overwrite the Hardy-Weinberg P of variants [first, first + len(hwe)) of the working set."""
+        h = np.ascontiguousarray(hwe, dtype=np.float64).reshape(-1)
+        self._check(self._lib.twk_hip_set_hwe(self._ctx, first, h.size, h.ctypes.data), "twk_hip_set_hwe")
+
+    def select_last(self) -> dict:
+        """Of the last selection: the kernel's time and the bytes of genotype rows it read and wrote."""
+        ms, r, w = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_select_last(self._ctx, C.byref(ms), C.byref(r), C.byref(w)), "twk_hip_select_last")
+        return {"select_ms": ms.value, "bytes_read": int(r.value), "bytes_written": int(w.value)}
 
     # ---- compute ----
     @staticmethod

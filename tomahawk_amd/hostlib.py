@@ -43,6 +43,8 @@ def lib():
         L.twk_import_vcf.argtypes = [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.c_int, C.c_uint32, C.c_int, C.c_int, p]
         L.twk_hwe_exact.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
         L.twk_hwe_exact.restype = C.c_double
+        L.twk_file_sample_names.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.twk_resolve_samples.argtypes = [p, C.c_uint32, C.c_char_p, C.c_char_p, p, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
         L.twk_record_codec_bound.restype = C.c_uint64
         L.twk_record_codec_bound.argtypes = [C.c_uint64]
         L.twk_record_codec_compress.restype = C.c_uint64
@@ -185,6 +187,33 @@ def record_codec_compress(data: bytes, stride: int = 106) -> bytes:
 
 def hwe_exact(hom1, het, hom2):
     return float(lib().twk_hwe_exact(hom1, het, hom2))
+
+
+def resolve_samples(names, keep=None, remove=None):
+    """`--keep` / `--remove` (csrc/host/twk_sample_list.h): the header's sample names and the two list files (paths, or None) -> the kept
+    samples' indices, ascending (uint32).  ValueError with the command's message for a name that is not in the header, a name twice in
+    one file, an unreadable file or an empty result."""
+    enc = [str(n).encode() for n in names]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    out = np.zeros(max(len(enc), 1), dtype=np.uint32)
+    n = C.c_uint32(0)
+    err = C.create_string_buffer(1024)
+    rc = lib().twk_resolve_samples(C.cast(arr, C.c_void_p), len(enc), None if keep is None else str(keep).encode(),
+                                   None if remove is None else str(remove).encode(), out.ctypes.data, len(out), C.byref(n), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode() or f"twk_resolve_samples failed: {rc}")
+    return out[:n.value].copy()
+
+
+def sample_names(path, is_two=True):
+    """The sample names of a .two / .twk header, in order."""
+    n = C.c_uint32(0)
+    if lib().twk_file_sample_names(path.encode(), int(is_two), None, 0, C.byref(n)) != 0:
+        raise RuntimeError(f"cannot read the header of {path}")
+    buf = C.create_string_buffer(64 * (n.value + 1) + 4096)
+    if lib().twk_file_sample_names(path.encode(), int(is_two), buf, len(buf), None) != 0:
+        raise RuntimeError(f"cannot read the header of {path}")
+    return buf.value.decode().splitlines()
 
 
 def header_literals(path, is_two=True):
