@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check varsel-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -178,6 +178,14 @@ subset-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/subset_index_check.cpp -o build/subset_index_check
 	./build/subset_index_check
+
+# The variant selection's predicate, word counts and gather walk (csrc/hip/ld_varsel_index.h): the predicate with its equality boundaries
+# against a restatement, every block and lane of the row gather against a row-by-row copy and an array of write counts with a border
+# (csrc/tools/varsel_index_check.cpp): host code only, under AddressSanitizer and UBSan
+varsel-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/varsel_index_check.cpp -o build/varsel_index_check
+	./build/varsel_index_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

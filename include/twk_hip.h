@@ -44,6 +44,7 @@ extern "C" {
 /*    (still 5: twk_hip_bandmat_layout / twk_hip_ld_matrix_band / twk_hip_bandmat_last - the banded LD matrix - are three entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_topk / twk_hip_topk_last - top-k LD partners - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_select_samples / twk_hip_selection / twk_hip_get_meta / twk_hip_set_hwe / twk_hip_select_last - sample subsets - are five entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_select_variants / twk_hip_variant_selection / twk_hip_variant_map / twk_hip_select_variants_last - variant subsets - are four entry points more; no existing struct and no existing entry point changed) */
 #define TWK_HIP_ABI_VERSION 5
 
 enum {
@@ -278,6 +279,60 @@ int twk_hip_set_hwe(twk_hip_ctx* ctx, uint32_t first, uint32_t count, const doub
 /* Of the context's last selection that ran the kernel: its device time in ms, the bytes of source rows it read (the words with a kept
  * sample, of every variant, data and mask rows) and the bytes of working rows it wrote (any may be NULL). */
 int twk_hip_select_last(const twk_hip_ctx* ctx, double* select_ms, uint64_t* bytes_read, uint64_t* bytes_written);
+
+/* ---- variant subsets --------------------------------------------------- */
+/* The other axis: LD over the variants that pass a list and frequency / missingness / Hardy-Weinberg thresholds - PLINK's --extract,
+ * --exclude, --maf, --max-maf, --mac, --geno and --hwe - decided on the device from the data that is already there.
+ * THE BASE is the context as it stands when no variant selection is active: the data as uploaded, or the working set of an active sample
+ * selection, its hwe including what twk_hip_set_hwe wrote.  So the order is PLINK's: samples first, then the variants on the kept
+ * samples' own counts.
+ * THE RULE: variant v of the base is KEPT iff it passes the list and every threshold.  list: n_list base indices, strictly ascending;
+ * exclude == 0: v must be in the list, exclude != 0: v must not be; list == NULL with n_list == 0: no list test.  The thresholds are a pure
+ * function of what twk_hip_get_marginals and twk_hip_get_meta return for the base: with N the base's sample count, called = N - n_miss,
+ * obs = 2 called, alt = n_het + 2 n_hom, minor = min(alt, obs - alt), v passes iff
+ *     (double)minor >= min_maf * (double)obs   and   (double)minor <= max_maf * (double)obs   and   minor >= min_mac
+ *     and   (double)n_miss <= max_missing * (double)N   and   !(hwe < min_hwe)
+ * - each one IEEE double multiplication and one comparison, so equality with a threshold keeps the variant and a NumPy restatement gives
+ * the same answer on every input.  filter == NULL: every threshold off (min_maf 0, max_maf 0.5, min_mac 0, max_missing 1, min_hwe 0).
+ * THE CONTRACT is the sample subsets': after the call the context is a problem of *n_kept variants and the same samples, in base order,
+ * indistinguishable from a context that received exactly those rows and that metadata (the base's hwe included) through
+ * twk_hip_set_problem + twk_hip_upload_bitvectors: the downloads, the marginals, the metadata and every compute entry point return the
+ * same bytes.  Variant indices everywhere - slices, idxA / idxB, per-variant outputs and per-variant inputs (clump's p, annotations,
+ * aggregate's bins) - are WORKING indices 0 .. *n_kept - 1; twk_hip_variant_map gives working -> base.  File order is preserved.  The
+ * mask rows are dropped when no kept variant has missing data, and TWK_HIP_MODE_AUTO then takes the phased math, as after a re-import.
+ * STATE: a second call selects from the base again ("A then B" equals "B").  twk_hip_select_variants(ctx, NULL, NULL, 0, 0, ..) drops the
+ * selection: the context is the base again bit for bit - rows, metadata, an active sample selection.  WHILE A VARIANT SELECTION IS ACTIVE
+ * twk_hip_select_samples, the uploads and the generators return TWK_HIP_E_STATE: the caller drops it first.  twk_hip_set_hwe writes the
+ * working set only.  twk_hip_set_problem discards everything.
+ * MEMORY: THE BASE STAYS ON THE DEVICE, untouched, and the working set lives beside it: M_alloc' * Wp * 4 bytes of rows, twice that while
+ * a kept variant has missing data, plus 28 bytes of metadata per row, where M_alloc' = *n_kept rounded up to a multiple of 128, plus 128,
+ * and Wp the base's row pitch in words.  During the call 16 bytes per base variant on top (list flags, kept flags, scan, map) and the
+ * scan's scratch.  Dropping the selection copies nothing: the base's buffers become the context's again.
+ * REFUSALS, on each of which nothing changes and a selection that was active stays active: TWK_HIP_E_INVALID for a list that is not
+ * strictly ascending or holds an index >= the base's variant count (twk_hip_last_error names the position), list == NULL with
+ * n_list != 0, a threshold that is NaN or outside its range (min_maf, max_maf in [0, 0.5] with min_maf <= max_maf; max_missing, min_hwe
+ * in [0, 1]), a selection that keeps no variant; TWK_HIP_E_STATE before the first upload (or generator call); TWK_HIP_E_NOMEM with the
+ * byte count.
+ * The kernels (csrc/hip/ld_varsel.hip.h): one wave per base variant counts het / hom / missing from its raw rows in one pass and applies
+ * the rule; an exclusive scan of the flags gives the map; the rows and the metadata SoA are gathered through it with 16-byte accesses,
+ * every output word written once by a plain store, the padding rows as zeros: two calls give the same bytes.  There is NO reference
+ * counterpart. */
+typedef struct {
+    double   min_maf, max_maf;   /* off: 0, 0.5 */
+    uint32_t min_mac, _pad;      /* off: 0      */
+    double   max_missing;        /* off: 1      */
+    double   min_hwe;            /* off: 0      */
+} twk_hip_variant_filter;
+int twk_hip_select_variants(twk_hip_ctx* ctx, const twk_hip_variant_filter* filter /* NULL: all off */,
+                            const uint32_t* list, uint32_t n_list, int32_t exclude, uint32_t* n_kept /* may be NULL */);
+/* The variant count of the base and of the working set (either may be NULL); equal when no selection is active (or all are kept). */
+int twk_hip_variant_selection(const twk_hip_ctx* ctx, uint32_t* n_before, uint32_t* n_selected);
+/* index_before[i] = the base index of working variant first + i (the identity while no selection is active). */
+int twk_hip_variant_map(const twk_hip_ctx* ctx, uint32_t first, uint32_t count, uint32_t* index_before);
+/* Of the context's last variant selection that ran the kernels: their device time in ms (predicate, scan and map; row and metadata
+ * gather), the bytes of rows read (the base's rows once for the predicate, the kept rows once for the gather) and the bytes of working
+ * rows written, padding rows included (any may be NULL). */
+int twk_hip_select_variants_last(const twk_hip_ctx* ctx, double* select_ms, uint64_t* bytes_read, uint64_t* bytes_written);
 
 /* ---- compute ---------------------------------------------------------- */
 /* Raw contingency counts for one tile (debug/parity entry point; replaces the

@@ -48,6 +48,20 @@ struct twk_ld_settings {
 	// variants' Hardy-Weinberg P is recomputed over the kept samples, as a re-import of the subset would carry it.  The sample count and
 	// the sample names of every output (.two header, PREFIX.samples.tsv, ##M_5_50) are then the kept samples', in header order.  Empty: all.
 	std::string keep_file, remove_file;
+	// Not in the reference: LD over a subset of the input's variants, PLINK's options in PLINK's order - samples first, then the
+	// Hardy-Weinberg P over the kept samples, then the variants on those counts, then the compute.  `--extract FILE` / `--exclude FILE`: a
+	// list of positions (csrc/host/twk_variant_list.h: CONTIG:POS or CONTIG<whitespace>POS per line, further columns ignored, positions
+	// as the commands print them; every variant at a listed position matches; listed positions the input does not have are counted on
+	// stderr; both: extract, then exclude).  `--maf` / `--max-maf` (minor allele frequency among the called alleles, bounds included),
+	// `--mac` (minor allele count), `--geno` (the largest fraction of samples with a missing genotype), `--hwe` (the smallest
+	// Hardy-Weinberg P): twk_hip_variant_filter's fields and rule.  The files are read before any device work; the variants are selected on
+	// the GPU (twk_hip_select_variants), and the positions, per-variant side inputs (--assoc, --annot, the landscape) and the L / R split of
+	// a -c / -C chunk follow the kept variants.  Refused where no one context holds the command's whole variant set (window mode over
+	// several GPUs or processes) and in window mode under TWK_REF_COMPAT.  At their defaults: all variants.
+	std::string extract_file, exclude_file;
+	double min_maf = 0.0, max_maf = 0.5, max_missing = 1.0, min_hwe = 0.0;
+	uint32_t min_mac = 0;
+	bool selects_variants() const { return !extract_file.empty() || !exclude_file.empty() || min_maf != 0.0 || max_maf != 0.5 || min_mac != 0 || max_missing != 1.0 || min_hwe != 0.0; }
 };
 
 // What Score takes beyond twk_ld_settings.
@@ -56,6 +70,11 @@ struct twk_score_settings {
 	bool self = false;          // add the variant's own annotation to its partitioned scores (LDSC's convention, r2(v, v) = 1)
 	int32_t top = 0;            // > 0: in place of the scores, every variant's `top` strongest partners (1 .. TWK_HIP_TOPK_MAX; not with annot)
 	int32_t top_stat = -1;      // ... by the magnitude of this statistic (TWK_HIP_STAT_*; -1, not stated: r2)
+};
+
+// What Prune takes beyond twk_ld_settings.
+struct twk_prune_settings {
+	bool kept_only = false;     // write the kept variants' lines only (`prune --kept-only`): a list `--extract` reads back, PLINK's prune.in
 };
 
 // What Clump needs beyond twk_ld_settings.
@@ -141,6 +160,9 @@ public:
 	// 1 if no kept variant before it forms a record Compute would write with it, else 0 - decided and walked on one GPU
 	// (twk_hip_ld_prune), no record is formed.  settings.minP must be 1 (the default).  `tomahawk prune` ends here.
 	bool Prune(const twk_ld_settings& settings);
+	// ... with prune.kept_only only the lines of the kept variants are written (the `##kept=` line stays): the file is a variant list that
+	// `--extract` of any command reads back - PLINK's --indep-pairwise followed by --extract.
+	bool Prune(const twk_ld_settings& settings, const twk_prune_settings& prune);
 	// Not in the reference: LD clumping (PLINK's --clump).  Loads the .twk exactly as Prune does (-I intervals, -w, -p / -u, TWK_REF_COMPAT;
 	// -c / -C are refused) and reads one association P value per variant from clump.assoc - text, split on tabs or spaces, lines that
 	// start with '#' ignored: contig name, position (1-based, as Score and Prune print it), P (NA / nan: none), further columns ignored;

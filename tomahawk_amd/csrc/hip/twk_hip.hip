@@ -17,6 +17,7 @@
 //                          (twk_hip_relationship: its own launches, beside the variant launch path)
 //   topk (ld_topk.hip.h) cells -> one statistic of the pair's record -> a 64-bit key -> the k largest per variant, selected with integer atomic maxima (twk_hip_ld_topk)
 //   subset (ld_subset.hip.h) the raw rows compacted to a list of samples: a working copy beside the rows as uploaded (twk_hip_select_samples)
+//   varsel (ld_varsel.hip.h) a predicate per variant -> scan -> the rows and the metadata of the kept variants gathered beside the base (twk_hip_select_variants)
 //   (score, prune, clump, matrix, decay, aggregate, annot, bandmat and topk are the nine kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
@@ -36,6 +37,7 @@
 #include <chrono>
 #include <string.h>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rccl/rccl.h>          // types only: the library is opened on first use (twk_hip_gather_records), never linked
 #include <dlfcn.h>
 #include <map>
@@ -59,6 +61,7 @@
 #include "ld_topk.hip.h"
 #include "ld_relate.hip.h"
 #include "ld_subset.hip.h"
+#include "ld_varsel.hip.h"
 #include "ld_plan.h"
 #include "ld_form.h"
 #include "twk_delivery.h"
@@ -282,6 +285,19 @@ struct twk_hip_ctx {
 		std::vector<twk_hip_variant_meta> h_meta;
 	} source;
 	struct { double ms = 0; uint64_t bytes_read = 0, bytes_written = 0; } select_last;      // of the last selection that ran the kernel
+	// twk_hip_select_variants: while a variant selection is active the rows and the metadata it selected from - the base: the data as uploaded,
+	// or the working set of an active sample selection - wait here, and raw, rawmask, M, M_alloc, any_missing, the metadata (device SoA and
+	// h_meta) and everything derived from them describe the working set.  Nothing is copied when the selection is dropped: the buffers move back.
+	struct VarBase {
+		bool active = false;
+		uint32_t M = 0, M_alloc = 0;
+		bool any_missing = false;
+		DevBuf<uint32_t> raw, rawmask, d_ac, d_an, d_pos, d_rid, d_missing;
+		DevBuf<double> d_hwe;
+		std::vector<twk_hip_variant_meta> h_meta;
+		std::vector<uint32_t> h_map;       // working -> base
+	} varbase;
+	struct { double ms = 0; uint64_t bytes_read = 0, bytes_written = 0; } varsel_last;      // of the last variant selection that ran the kernels
 	// metadata (device SoA) + host mirror
 	DevBuf<uint32_t> d_ac, d_an, d_pos, d_rid, d_missing;
 	DevBuf<double> d_hwe;
@@ -384,6 +400,7 @@ void free_problem(twk_hip_ctx* c) {
 	c->d_decay.reset(); c->d_agg_key.reset();
 	c->h_meta.clear();
 	c->source.raw.reset(); c->source.rawmask.reset(); c->source.h_meta.clear(); c->source.active = false;
+	c->varbase = twk_hip_ctx::VarBase();
 	c->N = c->M = c->M_alloc = 0; c->any_missing = false; c->has_data = false;
 }
 
@@ -1666,7 +1683,8 @@ int twk_hip_set_problem(twk_hip_ctx* c, uint32_t n_samples, uint32_t n_variants)
 int twk_hip_upload_bitvectors(twk_hip_ctx* c, uint32_t first, uint32_t count, const uint64_t* data,
                               const uint64_t* mask, size_t stride64, const twk_hip_variant_meta* meta) {
 	if (!c || !data || !meta || count == 0) return TWK_HIP_E_INVALID;
-	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;      // (a selection is dropped first: twk_hip_select_samples)
+	if (c->raw && c->varbase.active) { snprintf(c->err, sizeof(c->err), "%s: a variant selection is active (twk_hip_select_variants(ctx, NULL, NULL, 0, 0, ..) drops it)", "twk_hip_upload_bitvectors"); return TWK_HIP_E_STATE; }
+	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;      // (a selection is dropped first: twk_hip_select_samples, twk_hip_select_variants)
 	const size_t w64 = ((size_t)2 * c->N + 63) / 64;
 	if (stride64 < w64 || (uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
 	// Validate everything before any device or context state changes.  A variant's missing-data
@@ -1703,6 +1721,7 @@ int twk_hip_upload_bitvectors(twk_hip_ctx* c, uint32_t first, uint32_t count, co
 int twk_hip_upload_rle(twk_hip_ctx* c, uint32_t first, uint32_t count, const void* bytes, size_t n_bytes,
                        const twk_hip_rle_desc* desc, const twk_hip_variant_meta* meta) {
 	if (!c || !bytes || !desc || !meta || count == 0) return TWK_HIP_E_INVALID;
+	if (c->raw && c->varbase.active) { snprintf(c->err, sizeof(c->err), "twk_hip_upload_rle: a variant selection is active (twk_hip_select_variants(ctx, NULL, NULL, 0, 0, ..) drops it)"); return TWK_HIP_E_STATE; }
 	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;
 	if ((uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
 	// validate before anything changes (same rules as twk_hip_upload_bitvectors)
@@ -1793,6 +1812,7 @@ int twk_hip_generate_synthetic_planted(twk_hip_ctx* c, uint64_t seed, uint32_t f
 	if ((uint64_t)first_variant + (c ? c->M : 0) > 0xFFFFFFFFull) return TWK_HIP_E_INVALID;
 	SynthPlant pl;
 	if (!plant_of(plant, pl)) return TWK_HIP_E_INVALID;
+	if (c->raw && c->varbase.active) { snprintf(c->err, sizeof(c->err), "twk_hip_generate_synthetic: a variant selection is active (twk_hip_select_variants(ctx, NULL, NULL, 0, 0, ..) drops it)"); return TWK_HIP_E_STATE; }
 	if (!c->raw || c->source.active) return TWK_HIP_E_STATE;
 	HIPCHK(c, hipSetDevice(c->device));
 	free_planes(c);
@@ -1901,6 +1921,7 @@ int twk_hip_select_samples(twk_hip_ctx* c, const uint32_t* keep, uint32_t n_keep
 	if (!c) return TWK_HIP_E_INVALID;
 	if (!keep && n_keep != 0) { snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: no list, but a count of %u", n_keep); return TWK_HIP_E_INVALID; }
 	if (!c->raw || !c->has_data) return TWK_HIP_E_STATE;
+	if (c->varbase.active) { snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: a variant selection is active (twk_hip_select_variants drops it)"); return TWK_HIP_E_STATE; }
 	if (!keep) return drop_selection(c);
 	const uint32_t n_src = c->source.active ? c->source.N : c->N, w_src = c->source.active ? c->source.Wp : c->Wp;
 	if (n_keep == 0) { snprintf(c->err, sizeof(c->err), "twk_hip_select_samples: an empty list"); return TWK_HIP_E_INVALID; }
@@ -2018,6 +2039,197 @@ int twk_hip_select_last(const twk_hip_ctx* c, double* select_ms, uint64_t* bytes
 	if (select_ms) *select_ms = c->select_last.ms;
 	if (bytes_read) *bytes_read = c->select_last.bytes_read;
 	if (bytes_written) *bytes_written = c->select_last.bytes_written;
+	return TWK_HIP_OK;
+}
+
+extern "C++" {
+namespace {
+// The variant selection goes: the base's rows and metadata are the context's again, bit for bit.  Nothing is copied; the buffers move back.
+int drop_variant_selection(twk_hip_ctx* c) {
+	if (!c->varbase.active) return TWK_HIP_OK;
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	free_planes(c);
+	twk_hip_ctx::VarBase& b = c->varbase;
+	c->raw = std::move(b.raw); c->rawmask = std::move(b.rawmask);
+	c->d_ac = std::move(b.d_ac); c->d_an = std::move(b.d_an); c->d_pos = std::move(b.d_pos); c->d_rid = std::move(b.d_rid);
+	c->d_missing = std::move(b.d_missing); c->d_hwe = std::move(b.d_hwe);
+	c->h_meta = std::move(b.h_meta);
+	c->M = b.M; c->M_alloc = b.M_alloc; c->any_missing = b.any_missing;
+	b = twk_hip_ctx::VarBase();
+	return TWK_HIP_OK;
+}
+}  // namespace
+}
+
+int twk_hip_select_variants(twk_hip_ctx* c, const twk_hip_variant_filter* filter, const uint32_t* list, uint32_t n_list, int32_t exclude, uint32_t* n_kept_out) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (!list && n_list != 0) { snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: no list, but a count of %u", n_list); return TWK_HIP_E_INVALID; }
+	VarselFilter f{0.0, 0.5, 0u, 1.0, 0.0};
+	if (filter) {
+		f = VarselFilter{filter->min_maf, filter->max_maf, filter->min_mac, filter->max_missing, filter->min_hwe};
+		if (const char* fault = varsel_filter_fault(f)) {
+			snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: threshold %s is NaN or outside its range (min_maf %g, max_maf %g in [0, 0.5], max_missing %g, min_hwe %g in [0, 1])",
+			         fault, f.min_maf, f.max_maf, f.max_missing, f.min_hwe);
+			return TWK_HIP_E_INVALID;
+		}
+	}
+	if (!c->raw || !c->has_data) { snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: the context holds no data yet (%s): upload or generate first", c->raw ? "twk_hip_set_problem was called, nothing was uploaded" : "no twk_hip_set_problem"); return TWK_HIP_E_STATE; }
+	if (!filter && !list) {
+		const int rc = drop_variant_selection(c);
+		if (rc == TWK_HIP_OK && n_kept_out) *n_kept_out = c->M;
+		return rc;
+	}
+	twk_hip_ctx::VarBase& vb = c->varbase;
+	const bool was = vb.active;
+	const uint32_t Mb = was ? vb.M : c->M;
+	for (uint32_t k = 0; k < n_list; ++k)
+		if (list[k] >= Mb || (k && list[k] <= list[k - 1])) {
+			snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: list[%u] = %u is not above its predecessor and below the base's %u variants", k, list[k], Mb);
+			return TWK_HIP_E_INVALID;
+		}
+	HIPCHK(c, hipSetDevice(c->device));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	const uint32_t* b_raw = was ? vb.raw.get() : c->raw.get();
+	const bool b_missing = was ? vb.any_missing : c->any_missing;
+	const uint32_t* b_mask = b_missing ? (was ? vb.rawmask.get() : c->rawmask.get()) : nullptr;      // (mask rows count only while a variant is flagged missing: plane_kind_for)
+	const uint32_t* b32[5] = {was ? vb.d_ac.get() : c->d_ac.get(), was ? vb.d_an.get() : c->d_an.get(), was ? vb.d_pos.get() : c->d_pos.get(),
+	                          was ? vb.d_rid.get() : c->d_rid.get(), was ? vb.d_missing.get() : c->d_missing.get()};
+	const double* b_hwe = was ? vb.d_hwe.get() : c->d_hwe.get();
+	const std::vector<twk_hip_variant_meta>& b_meta = was ? vb.h_meta : c->h_meta;
+	const uint32_t Wp = c->Wp;
+	auto nomem = [c](hipError_t e, unsigned long long bytes, const char* what) {
+		(void)hipGetLastError();
+		snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: %s needs %llu bytes of device memory beside the base: %s", what, bytes, hipGetErrorString(e));
+		return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+	};
+	// everything new is built beside what the context holds, and nothing of the context changes until all of it stands
+	// (a) the predicate, (b) the scan and the map
+	DevBuf<uint32_t> d_listed, d_flag, d_off, d_map, d_n;
+	DevBuf<char> d_tmp;
+	size_t tmp_bytes = 0;
+	HIPCHK(c, rocprim::exclusive_scan(nullptr, tmp_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)Mb, rocprim::plus<uint32_t>(), c->s_compute));
+	{
+		hipError_t e = hipSuccess;
+		if (list) e = d_listed.reserve(Mb, Mb, nullptr);
+		for (DevBuf<uint32_t>* b : {&d_flag, &d_off, &d_map}) if (e == hipSuccess) e = b->reserve(Mb, Mb, nullptr);
+		if (e == hipSuccess) e = d_n.reserve(1, 1, nullptr);
+		if (e == hipSuccess) e = d_tmp.reserve(std::max<size_t>(tmp_bytes, 16), std::max<size_t>(tmp_bytes, 16), nullptr);
+		if (e != hipSuccess) return nomem(e, (unsigned long long)Mb * 16 + tmp_bytes, "the flags, the scan and the map");
+	}
+	Events ev;
+	HIPCHK(c, ev.add(4));
+	DevBuf<uint32_t> d_list;
+	if (list) {
+		HIPCHK(c, hipMemsetAsync(d_listed, 0, (size_t)Mb * 4, c->s_compute));
+		if (n_list) {
+			HIPCHK(c, d_list.reserve(n_list, n_list, nullptr));
+			HIPCHK(c, hipMemcpyAsync(d_list, list, (size_t)n_list * 4, hipMemcpyHostToDevice, c->s_compute));
+			hipLaunchKernelGGL(k_varsel_list_flags, dim3((n_list + 255) / 256), dim3(256), 0, c->s_compute, (const uint32_t*)d_list, n_list, d_listed.get());
+			HIPCHK(c, hipGetLastError());
+		}
+	}
+	VarselPredArgs pa{};
+	pa.raw = b_raw; pa.rawmask = b_mask; pa.listed = list ? d_listed.get() : nullptr; pa.hwe = b_hwe; pa.flag = d_flag;
+	pa.Wp = Wp; pa.n_variants = Mb; pa.n_samples = c->N; pa.exclude = exclude ? 1u : 0u; pa.f = f;
+	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
+	hipLaunchKernelGGL(k_varsel_predicate, dim3((Mb + 3) / 4), dim3(256), 0, c->s_compute, pa);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, rocprim::exclusive_scan(d_tmp.get(), tmp_bytes, d_flag.get(), d_off.get(), 0u, (size_t)Mb, rocprim::plus<uint32_t>(), c->s_compute));
+	hipLaunchKernelGGL(k_varsel_map, dim3((Mb + 255) / 256), dim3(256), 0, c->s_compute, (const uint32_t*)d_flag, (const uint32_t*)d_off, Mb, d_map.get(), d_n.get());
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
+	uint32_t n_kept = 0;
+	HIPCHK(c, hipMemcpyAsync(&n_kept, d_n, 4, hipMemcpyDeviceToHost, c->s_compute));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	if (n_kept == 0 || n_kept > Mb) {
+		snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: the selection keeps none of the base's %u variants", Mb);
+		return TWK_HIP_E_INVALID;
+	}
+	// the map comes to the host once: for h_meta and twk_hip_variant_map
+	std::vector<uint32_t> h_map(n_kept);
+	HIPCHK(c, hipMemcpy(h_map.data(), d_map, (size_t)n_kept * 4, hipMemcpyDeviceToHost));
+	std::vector<twk_hip_variant_meta> meta(n_kept);
+	bool any_missing = false;
+	for (uint32_t r = 0; r < n_kept; ++r) {
+		if (h_map[r] >= Mb) { snprintf(c->err, sizeof(c->err), "twk_hip_select_variants: the map's entry %u is %u, beyond the base", r, h_map[r]); return TWK_HIP_E_DEVICE; }
+		meta[r] = b_meta[h_map[r]];
+		any_missing = any_missing || meta[r].missing;
+	}
+	// (c) the rows and the metadata SoA through the map
+	const uint32_t M_alloc = round_up(n_kept, TILE) + TILE;
+	const int n_planes = any_missing && b_mask ? 2 : 1;                // the mask rows are kept only while a working variant has missing data
+	const size_t row_words = (size_t)M_alloc * Wp;
+	DevBuf<uint32_t> rows[2], n32[5];
+	DevBuf<double> n_hwe;
+	{
+		hipError_t e = hipSuccess;
+		for (int p = 0; p < n_planes && e == hipSuccess; ++p) e = rows[p].reserve(row_words, row_words, nullptr);
+		for (int k = 0; k < 5 && e == hipSuccess; ++k) e = n32[k].reserve(M_alloc, M_alloc, nullptr);
+		if (e == hipSuccess) e = n_hwe.reserve(M_alloc, M_alloc, nullptr);
+		if (e != hipSuccess) return nomem(e, (unsigned long long)row_words * 4 * n_planes + (unsigned long long)M_alloc * 28, "the working set");
+	}
+	VarselRowArgs ra{};
+	ra.src[0] = b_raw; ra.src[1] = b_mask; ra.dst[0] = rows[0]; ra.dst[1] = rows[1]; ra.map = d_map;
+	ra.g = varsel_gather_geometry(M_alloc, n_kept, Wp / 4);
+	VarselMetaArgs ma{};
+	for (int k = 0; k < 5; ++k) { ma.src32[k] = b32[k]; ma.dst32[k] = n32[k]; }
+	ma.src_hwe = b_hwe; ma.dst_hwe = n_hwe; ma.map = d_map; ma.n_kept = n_kept; ma.n_out = M_alloc;
+	HIPCHK(c, hipEventRecord(ev[2], c->s_compute));
+	hipLaunchKernelGGL(k_varsel_rows, dim3(ra.g.n_blocks, 1, n_planes), dim3(VARSEL_BLOCK), 0, c->s_compute, ra);
+	HIPCHK(c, hipGetLastError());
+	hipLaunchKernelGGL(k_varsel_meta, dim3((M_alloc + 255) / 256), dim3(256), 0, c->s_compute, ma);
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(ev[3], c->s_compute));
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	float ms_a = 0.f, ms_c = 0.f;
+	HIPCHK(c, hipEventElapsedTime(&ms_a, ev[0], ev[1]));
+	HIPCHK(c, hipEventElapsedTime(&ms_c, ev[2], ev[3]));
+	// ... and now the context changes hands
+	free_planes(c);
+	if (!was) {
+		vb.raw = std::move(c->raw); vb.rawmask = std::move(c->rawmask);
+		vb.d_ac = std::move(c->d_ac); vb.d_an = std::move(c->d_an); vb.d_pos = std::move(c->d_pos); vb.d_rid = std::move(c->d_rid);
+		vb.d_missing = std::move(c->d_missing); vb.d_hwe = std::move(c->d_hwe);
+		vb.h_meta = std::move(c->h_meta);
+		vb.M = c->M; vb.M_alloc = c->M_alloc; vb.any_missing = c->any_missing;
+		vb.active = true;
+	}
+	vb.h_map = std::move(h_map);
+	c->raw = std::move(rows[0]);
+	if (n_planes == 2) c->rawmask = std::move(rows[1]); else c->rawmask.reset();
+	c->d_ac = std::move(n32[0]); c->d_an = std::move(n32[1]); c->d_pos = std::move(n32[2]); c->d_rid = std::move(n32[3]); c->d_missing = std::move(n32[4]);
+	c->d_hwe = std::move(n_hwe);
+	c->h_meta = std::move(meta);
+	c->M = n_kept; c->M_alloc = M_alloc; c->any_missing = any_missing;
+	c->varsel_last.ms = (double)ms_a + (double)ms_c;
+	c->varsel_last.bytes_read = (uint64_t)Mb * Wp * 4 * (b_mask ? 2 : 1) + (uint64_t)n_kept * Wp * 4 * n_planes;
+	c->varsel_last.bytes_written = (uint64_t)M_alloc * Wp * 4 * n_planes;
+	if (n_kept_out) *n_kept_out = n_kept;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_variant_selection(const twk_hip_ctx* c, uint32_t* n_before, uint32_t* n_selected) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if (n_before) *n_before = c->varbase.active ? c->varbase.M : c->M;
+	if (n_selected) *n_selected = c->M;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_variant_map(const twk_hip_ctx* c, uint32_t first, uint32_t count, uint32_t* index_before) {
+	if (!c || !index_before || count == 0) return TWK_HIP_E_INVALID;
+	if (!c->raw) return TWK_HIP_E_STATE;
+	if ((uint64_t)first + count > c->M) return TWK_HIP_E_INVALID;
+	for (uint32_t i = 0; i < count; ++i) index_before[i] = c->varbase.active ? c->varbase.h_map[first + i] : first + i;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_select_variants_last(const twk_hip_ctx* c, double* select_ms, uint64_t* bytes_read, uint64_t* bytes_written) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (select_ms) *select_ms = c->varsel_last.ms;
+	if (bytes_read) *bytes_read = c->varsel_last.bytes_read;
+	if (bytes_written) *bytes_written = c->varsel_last.bytes_written;
 	return TWK_HIP_OK;
 }
 

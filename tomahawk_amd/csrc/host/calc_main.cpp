@@ -122,7 +122,37 @@ struct Command {
 	bool (*run)(tomahawk::twk_ld& ld, const twk_ld_settings& settings, const Own& own);
 };
 
-// The shared options once (-i -o -I -p -u -t -c -C -r -P -w --engine-option), anything else to the command's own handler; then the checks
+// --extract FILE / --exclude FILE / --maf X / --max-maf X / --mac N / --geno X / --hwe P (not in the reference): LD over a subset of the
+// variants, twk_ld_settings::extract_file.  Long names only, as --keep; one table entry list and one handler for every command that
+// takes --keep / --remove.  The ranges are the engine's (twk_hip_select_variants), checked here so that the error names the option.
+#define VARIANT_SELECTION_LONG_OPTIONS \
+	{"extract", required_argument, 0, 1010}, {"exclude", required_argument, 0, 1011}, {"maf", required_argument, 0, 1012}, {"max-maf", required_argument, 0, 1013}, {"mac", required_argument, 0, 1014}, {"geno", required_argument, 0, 1015}, {"hwe", required_argument, 0, 1016}
+static Took variant_selection_option(int c, const char* arg, twk_ld_settings& settings) {
+	auto number = [&](const char* name, double lo, double hi, double& out) {
+		char* end = nullptr;
+		const double x = strtod(arg, &end);
+		if (end == arg || *end || !(x >= lo && x <= hi)) { char why[160]; snprintf(why, sizeof(why), "%s wants a number between %g and %g", name, lo, hi); fail(why); return failed; }
+		out = x;
+		return took;
+	};
+	switch (c) {
+	case 1010: settings.extract_file = arg; return took;
+	case 1011: settings.exclude_file = arg; return took;
+	case 1012: return number("--maf", 0.0, 0.5, settings.min_maf);
+	case 1013: return number("--max-maf", 0.0, 0.5, settings.max_maf);
+	case 1014: {      // an unsigned integer, digits only
+		const std::string a(arg);
+		if (a.empty() || a.size() > 10 || a.find_first_not_of("0123456789") != std::string::npos || strtoull(arg, nullptr, 10) > 4294967295ull) { fail("--mac wants an integer between 0 and 4294967295"); return failed; }
+		settings.min_mac = (uint32_t)strtoull(arg, nullptr, 10);
+		return took;
+	}
+	case 1015: return number("--geno", 0.0, 1.0, settings.max_missing);
+	case 1016: return number("--hwe", 0.0, 1.0, settings.min_hwe);
+	}
+	return declined;
+}
+
+// The shared options once (-i -o -I -p -u -t -c -C -r -P -w --engine-option, the sample and variant selections), anything else to the command's own handler; then the checks
 // after the options, the banner, and the call.
 template <class Own>
 static int run_command(const Command<Own>& cmd, int argc, char** argv) {
@@ -183,6 +213,7 @@ static int run_command(const Command<Own>& cmd, int argc, char** argv) {
 			break;
 		}
 		default:
+			if (const Took v = variant_selection_option(c, optarg, settings); v != declined) { if (v == failed) return 1; break; }
 			switch (cmd.option ? cmd.option(c, optarg, settings, own) : declined) {
 			case took: break;
 			case failed: return 1;
@@ -209,21 +240,21 @@ static const struct option CALC_LONG_OPTIONS[] = {
 	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 	{"samples", optional_argument, 0, 'S'}, {"minR2", optional_argument, 0, 'r'}, {"detailedProgress", no_argument, 0, 'd'},
 	{"silent", no_argument, 0, 's'}, {"windowBases", optional_argument, 0, 'w'},
-	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, {0, 0, 0, 0}};
+	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, VARIANT_SELECTION_LONG_OPTIONS, {0, 0, 0, 0}};
 static const struct option REDUCE_LONG_OPTIONS[] = {
 	{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
 	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
 	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
 	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
-	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
+	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, VARIANT_SELECTION_LONG_OPTIONS, {"assoc", required_argument, 0, 'a'}, {"annot", required_argument, 0, 1002}, {"self", no_argument, 0, 1001}, {"p1", required_argument, 0, '1'}, {"p2", required_argument, 0, '2'},
 	{"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'}, {"text", no_argument, 0, 'T'}, {"band", no_argument, 0, 1003},
-	{"top", required_argument, 0, 1004}, {"top-stat", required_argument, 0, 1005},
+	{"top", required_argument, 0, 1004}, {"top-stat", required_argument, 0, 1005}, {"kept-only", no_argument, 0, 1017},
 	{"range", required_argument, 0, 'd'}, {"bins", required_argument, 0, 'b'},
 	{"xbins", required_argument, 0, 'x'}, {"ybins", required_argument, 0, 'y'}, {"reduce", required_argument, 0, 'R'}, {"minCount", required_argument, 0, 'm'},
 	{0, 0, 0, 0}};
 static const struct option RELATIONSHIP_LONG_OPTIONS[] = {
 	{"input", required_argument, 0, 'i'}, {"interval", required_argument, 0, 'I'}, {"stat", required_argument, 0, 's'}, {"fill", required_argument, 0, 'f'},
-	{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007},
+	{"output", required_argument, 0, 'o'}, {"text", no_argument, 0, 'T'}, {"threads", required_argument, 0, 't'}, {"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, VARIANT_SELECTION_LONG_OPTIONS,
 	{"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'}, {"minR2", required_argument, 0, 'r'}, {"windowBases", required_argument, 0, 'w'},
 	{"parts", required_argument, 0, 'c'}, {"partStart", required_argument, 0, 'C'}, {"minP", required_argument, 0, 'P'}, {0, 0, 0, 0}};
 
@@ -330,11 +361,16 @@ static void prune_usage() {
 	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
 }
 
-static const Command<NoOptions> PRUNE = {      // (-r: calc's default)
+// (`prune --kept-only`, long name only and not in the usage text: the kept variants' lines alone, a list that --extract reads back)
+static Took prune_option(int c, const char*, twk_ld_settings&, tomahawk::twk_prune_settings& prune) {
+	if (c == 1017) { prune.kept_only = true; return took; }
+	return declined;
+}
+static const Command<tomahawk::twk_prune_settings> PRUNE = {      // (-r: calc's default)
 	"prune", "  prune    greedy LD pruning in file order (a keep flag per variant), decided on the GPU\n", prune_usage,
 	"i:o:t:puP:r:w:I:c:C:?", REDUCE_LONG_OPTIONS, 0.1, {{"cC", "Cannot prune a part of the pair space (-c / -C): the walk needs every pair"}},
-	"Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run", nullptr, nullptr,
-	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const NoOptions&) { return ld.Prune(settings); }};
+	"Cannot prune with a cutoff P-value below 1: pruning looks at every record and Fisher's exact test is not run", prune_option, nullptr,
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_prune_settings& prune) { return ld.Prune(settings, prune); }};
 
 // `tomahawk clump` (not in the reference): LD clumping (PLINK's --clump) over the records `calc` would write, decided on the GPU.
 static void clump_usage() {
@@ -851,11 +887,14 @@ static int scalc(int argc, char** argv) {
 	}
 	tomahawk::twk_ld_settings settings;
 	int c;
-	static const struct option long_options[] = {{"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, {0, 0, 0, 0}};
+	static const struct option long_options[] = {{"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, VARIANT_SELECTION_LONG_OPTIONS, {0, 0, 0, 0}};
 	while ((c = getopt_long(argc, argv, "i:o:t:I:mMb:r:R:P:k:w:?", long_options, nullptr)) != -1) {
 		switch (c) {
 		case 1006: settings.keep_file = optarg; break;
 		case 1007: settings.remove_file = optarg; break;
+		case 1010: case 1011: case 1012: case 1013: case 1014: case 1015: case 1016:
+			if (variant_selection_option(c, optarg, settings) != took) return 1;
+			break;
 		case 'i': settings.in = optarg; break;
 		case 'o': settings.out = optarg; break;
 		case 'I': settings.ival_strings.push_back(optarg); break;

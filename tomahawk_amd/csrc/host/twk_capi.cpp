@@ -17,6 +17,7 @@
 #include "twk_record_sink.h"
 #include "twk_repcodec.h"
 #include "twk_sample_list.h"
+#include "twk_variant_list.h"
 
 using namespace tomahawk;
 
@@ -322,6 +323,23 @@ int twk_resolve_samples(const char* const* names, uint32_t n_names, const char* 
 	const bool ok = resolve_sample_list(header, keep ? keep : "", remove ? remove : "", ids, msg);
 	if (err && err_cap) { std::strncpy(err, msg.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
 	if (n_out) *n_out = (uint32_t)ids.size();
+	if (ok && out) std::copy(ids.begin(), ids.begin() + std::min<size_t>(cap, ids.size()), out);
+	return ok ? 0 : 1;
+} catch (...) { return -9; }
+
+// resolve_variant_list (twk_variant_list.h): the list file `path` against M variants given by their contig (rid[v], an index into the
+// n_contigs names) and stored position (pos[v]: the commands print pos[v] + 1, and that is what the file holds).  -> 0 with the matching
+// variants, ascending, in out[0 .. *n_out) (at most cap of them are written; *n_out is the count in any case) and the listed positions no
+// variant has in *n_absent; 1 with the message in err (NUL terminated, truncated to err_cap).
+int twk_resolve_variants(const char* const* contigs, uint32_t n_contigs, const uint32_t* rid, const uint32_t* pos, uint32_t M, const char* path,
+                         uint32_t* out, uint32_t cap, uint32_t* n_out, uint64_t* n_absent, char* err, size_t err_cap) try {
+	std::vector<std::string> names;
+	for (uint32_t k = 0; k < n_contigs; ++k) names.emplace_back(contigs[k] ? contigs[k] : "");
+	std::vector<uint32_t> ids; std::string msg; uint64_t absent = 0;
+	const bool ok = resolve_variant_list(names, rid, pos, M, path ? path : "", "list", ids, &absent, msg);
+	if (err && err_cap) { std::strncpy(err, msg.c_str(), err_cap - 1); err[err_cap - 1] = 0; }
+	if (n_out) *n_out = (uint32_t)ids.size();
+	if (n_absent) *n_absent = absent;
 	if (ok && out) std::copy(ids.begin(), ids.begin() + std::min<size_t>(cap, ids.size()), out);
 	return ok ? 0 : 1;
 } catch (...) { return -9; }

@@ -8,6 +8,7 @@
 #include "twk_ld.h"
 
 #include <algorithm>
+#include <iterator>
 #include <memory>
 #include <atomic>
 #include <chrono>
@@ -40,6 +41,7 @@
 #include "twk_parallel.h"
 #include "twk_record_sink.h"
 #include "twk_sample_list.h"
+#include "twk_variant_list.h"
 #include "twk_util.h"
 
 #ifndef TWK_AMD_VERSION
@@ -562,6 +564,71 @@ static bool apply_sample_selection(twk_hip_ctx* ctx, const std::vector<uint32_t>
 	return true;
 }
 
+// `--extract` / `--exclude` / `--maf` / `--max-maf` / `--mac` / `--geno` / `--hwe`.  The list files are read before any device work
+// (read_variant_lists: an unreadable file or a line that does not parse ends the command there); after the upload, the sample selection and
+// its Hardy-Weinberg P, the lists are matched against the loaded variants' positions and every context - each holds the same M variants -
+// becomes the problem of the kept variants (twk_hip_select_variants: the rule is the engine's).  The host's tables follow the map: rid and
+// pos are compacted, nL / nR - the variants of the L range and of the R range of a chunk, or scalc's targets and neighbours - become the
+// kept ones among them, and meta_out (may be null) is read back.  Every per-variant side input is matched against rid / pos after this.
+namespace {
+struct VariantLists { std::vector<VariantListEntry> extract, exclude; };
+}
+static bool read_variant_lists(const twk_ld_settings& settings, VariantLists& lists) {
+	std::string err;
+	if (!settings.extract_file.empty() && !read_variant_file(settings.extract_file, "--extract", lists.extract, err)) { std::cerr << stamp("ERROR") << err << "..." << std::endl; return false; }
+	if (!settings.exclude_file.empty() && !read_variant_file(settings.exclude_file, "--exclude", lists.exclude, err)) { std::cerr << stamp("ERROR") << err << "..." << std::endl; return false; }
+	return true;
+}
+static bool apply_variant_selection(const std::vector<twk_hip_ctx*>& ctxs, const twk_ld_settings& settings, const VariantLists& lists, const Header& hdr,
+                                    std::vector<uint32_t>& rid, std::vector<uint32_t>& pos, uint32_t& nL, uint32_t& nR, std::vector<twk_hip_variant_meta>* meta_out) {
+	if (!settings.selects_variants() || ctxs.empty()) return true;
+	const uint32_t M = (uint32_t)rid.size();
+	std::vector<std::string> contigs;
+	for (const auto& c : hdr.contigs) contigs.push_back(c.name);
+	std::vector<uint32_t> list;
+	bool have_list = false; int32_t exclude = 0;
+	if (!settings.extract_file.empty()) {
+		uint64_t absent = 0;
+		match_variant_list(contigs, rid.data(), pos.data(), M, lists.extract, list, &absent);
+		std::cerr << stamp("LOG") << "--extract: " << pretty(list.size()) << " variants at the listed positions" << (absent ? "; " + pretty(absent) + " listed positions are not among the loaded variants" : std::string()) << "..." << std::endl;
+		have_list = true;
+	}
+	if (!settings.exclude_file.empty()) {
+		uint64_t absent = 0;
+		std::vector<uint32_t> out;
+		match_variant_list(contigs, rid.data(), pos.data(), M, lists.exclude, out, &absent);
+		std::cerr << stamp("LOG") << "--exclude: " << pretty(out.size()) << " variants at the listed positions" << (absent ? "; " + pretty(absent) + " listed positions are not among the loaded variants" : std::string()) << "..." << std::endl;
+		if (have_list) {          // both: extract, then exclude
+			std::vector<uint32_t> rest;
+			std::set_difference(list.begin(), list.end(), out.begin(), out.end(), std::back_inserter(rest));
+			list.swap(rest);
+		} else { list.swap(out); exclude = 1; have_list = true; }
+	}
+	if (have_list && !exclude && list.empty()) { std::cerr << stamp("ERROR") << "No variant is left after --extract / --exclude..." << std::endl; return false; }
+	twk_hip_variant_filter f{};
+	f.min_maf = settings.min_maf; f.max_maf = settings.max_maf; f.min_mac = settings.min_mac; f.max_missing = settings.max_missing; f.min_hwe = settings.min_hwe;
+	const uint32_t none = 0;
+	uint32_t n_kept = 0;
+	for (twk_hip_ctx* ctx : ctxs) {
+		if (!hip_ok(ctx, twk_hip_select_variants(ctx, &f, have_list ? (list.empty() ? &none : list.data()) : nullptr, (uint32_t)list.size(), exclude, &n_kept), "twk_hip_select_variants")) return false;
+	}
+	std::vector<uint32_t> map(n_kept);
+	if (!hip_ok(ctxs[0], twk_hip_variant_map(ctxs[0], 0, n_kept, map.data()), "twk_hip_variant_map")) return false;
+	std::cerr << stamp("LOG") << "Keeping " << pretty(n_kept) << " of " << pretty(M) << " variants..." << std::endl;
+	uint32_t kL = 0;
+	for (uint32_t k = 0; k < n_kept; ++k) {
+		if (map[k] < nL) ++kL;
+		rid[k] = rid[map[k]]; pos[k] = pos[map[k]];          // (the map ascends: map[k] >= k)
+	}
+	rid.resize(n_kept); pos.resize(n_kept);
+	nR = nR ? n_kept - kL : 0; nL = kL;
+	if (meta_out) {
+		meta_out->resize(n_kept);
+		if (!hip_ok(ctxs[0], twk_hip_get_meta(ctxs[0], 0, n_kept, meta_out->data()), "twk_hip_get_meta")) return false;
+	}
+	return true;
+}
+
 static int gpus_from_env() {
 	if (const char* g = std::getenv("TWK_HIP_GPUS")) { const int n = std::atoi(g); if (n >= 1) return std::min(n, 64); }
 	return 1;
@@ -837,6 +904,7 @@ struct Selection {
 	uint32_t n_samples = 0;          // the samples the run computes over: the header's, or (--keep / --remove) the kept ones - reader.hdr.samples names exactly these
 	uint32_t n_source = 0;           // the samples of the input: what is uploaded
 	std::vector<uint32_t> keep;      // --keep / --remove: the kept samples' indices in the input, ascending; empty: no selection
+	VariantLists lists;              // --extract / --exclude: the files' positions, matched against the loaded variants after the upload
 	Balancer bal;
 	std::vector<uint32_t> sel;       // the L range's blocks, then (square chunk only) the R range's
 	uint32_t nL = 0, nR = 0, M = 0;
@@ -871,6 +939,7 @@ static bool select_blocks(twk_ld_settings& settings, Selection& S, bool* nothing
 	if (!open_input(reader, settings.in, true)) return false;
 	S.n_source = (uint32_t)reader.hdr.samples.size();
 	if (!select_samples(settings, reader.hdr, S.keep)) return false;
+	if (!read_variant_lists(settings, S.lists)) return false;
 	const uint32_t n_samples = S.n_samples = (uint32_t)reader.hdr.samples.size();
 	std::cerr << stamp("LOG") << "Samples: " << pretty(n_samples) << "..." << std::endl;
 
@@ -920,15 +989,24 @@ bool twk_ld::Compute() {
 	TwkReader& reader = S.reader;
 	const Balancer& bal = S.bal;
 	const std::vector<uint32_t>& sel = S.sel;
-	const uint32_t n_samples = S.n_samples, nL = S.nL, nR = S.nR, M = S.M;
+	const uint32_t n_samples = S.n_samples;
+	uint32_t nL = S.nL, nR = S.nR, M = S.M;      // (a variant selection shrinks them after the upload)
 
 	const int n_gpus = gpus_from_env();
-	DeviceCtxs dc;
-	if (!create_devices(dc, n_gpus, mImpl->engine_options)) return false;
-	if (n_gpus > 1) std::cerr << stamp("LOG", "HIP") << "Using " << n_gpus << " GPUs: one driver thread each, equal-area row bands of the pair space..." << std::endl;
 	uint32_t part0 = 0, n_procs = 1;
 	if (!part_from_env(part0, n_procs)) return false;
 	const uint32_t n_parts = n_procs * (uint32_t)n_gpus;
+	// (window mode on several GPUs or processes: every GPU loads its own band and halo, below)
+	const bool slabs = settings.window && bal.diag && n_parts > 1 && !(ref_compat() && !(settings.force_phased || settings.forced_unphased));
+	// a variant selection needs one context that holds the command's whole variant set: refused before any device is touched
+	if (settings.selects_variants() && (slabs || (ref_compat() && settings.window))) {
+		std::cerr << stamp("ERROR") << "--extract / --exclude / --maf / --max-maf / --mac / --geno / --hwe need one context that holds the command's whole variant set: not in window mode over "
+		          << "several GPUs or processes (every GPU holds its own band and halo), and not in window mode under TWK_REF_COMPAT (its windows follow the input's blocks)..." << std::endl;
+		return false;
+	}
+	DeviceCtxs dc;
+	if (!create_devices(dc, n_gpus, mImpl->engine_options)) return false;
+	if (n_gpus > 1) std::cerr << stamp("LOG", "HIP") << "Using " << n_gpus << " GPUs: one driver thread each, equal-area row bands of the pair space..." << std::endl;
 	RunSpec spec;
 	const auto t_load = clock::now();
 	const uint32_t T = (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus()));
@@ -938,7 +1016,7 @@ bool twk_ld::Compute() {
 	// window reaches beyond it (the reference's ticker prunes block pairs the same way, ld_balancing.h:176-203) -
 	// for BASELINE configs[4] that is 75 GB per GPU instead of 500 GB.  Bands are cut at block boundaries with equal
 	// estimated in-window pairs, from the index alone (block span and size), identically in every process.
-	if (settings.window && bal.diag && n_parts > 1 && !(ref_compat() && !(settings.force_phased || settings.forced_unphased))) {
+	if (slabs) {
 		const uint64_t w = (uint64_t)std::max(0, settings.l_window);
 		const size_t nb = sel.size();
 		auto ent = [&](size_t k) -> const IndexEntry& { return reader.index.ent[sel[k]]; };
@@ -989,6 +1067,8 @@ bool twk_ld::Compute() {
 	} else {
 		if (!load_blocks(settings.in, reader, sel, T, dc.ctx, S.n_source, mImpl->rid, mImpl->pos)) return false;
 		for (twk_hip_ctx* c : dc.ctx) if (!apply_sample_selection(c, S.keep, M, T, nullptr)) return false;
+		if (!apply_variant_selection(dc.ctx, settings, S.lists, reader.hdr, mImpl->rid, mImpl->pos, nL, nR, nullptr)) return false;
+		if (settings.selects_variants()) M = (uint32_t)mImpl->rid.size();
 	}
 	std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
 	          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
@@ -1063,6 +1143,10 @@ struct ReduceCommand {
 		std::cerr << stamp("LOG", "THREAD") << "Unpacking using " << T << " threads..." << std::endl;
 		if (!load_blocks(settings.in, S.reader, S.sel, T, dc.ctx, S.n_source, rid, pos, meta)) return failed;
 		if (!apply_sample_selection(ctx, S.keep, M, T, meta)) return failed;
+		if (settings.selects_variants()) {
+			if (!apply_variant_selection(dc.ctx, settings, S.lists, S.reader.hdr, rid, pos, S.nL, S.nR, meta)) return failed;
+			M = S.M = (uint32_t)rid.size();
+		}
 		std::cerr << stamp("LOG") << "Unpacked and uploaded " << pretty(M) << " variants. "
 		          << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << std::endl;
 		mode = settings.force_phased ? TWK_HIP_MODE_PHASED : (settings.forced_unphased ? TWK_HIP_MODE_UNPHASED : TWK_HIP_MODE_AUTO);
@@ -1492,7 +1576,8 @@ bool twk_ld::Aggregate(const twk_ld_settings& s, const twk_aggregate_settings& a
 // `tomahawk prune`: greedy LD pruning of the selection in file order (twk_hip_ld_prune: the edges are the records Compute would write,
 // decided and walked on the GPU, no record is formed), as text: one line per variant with its keep flag.  The input is loaded exactly
 // as Compute loads it; one GPU; the whole triangle (the walk needs every pair: no -c / -C).  Not in the reference.
-bool twk_ld::Prune(const twk_ld_settings& s) {
+bool twk_ld::Prune(const twk_ld_settings& s) { return Prune(s, twk_prune_settings()); }
+bool twk_ld::Prune(const twk_ld_settings& s, const twk_prune_settings& ps) {
 	ReduceCommand cmd(settings, *mImpl);
 	if (!cmd.begin(s, "Pruning looks at every record", "Cannot prune a part of the pair space: the walk needs every pair")) return false;
 	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
@@ -1510,6 +1595,7 @@ bool twk_ld::Prune(const twk_ld_settings& s) {
 	*os << line << "#contig\tpos\tkeep\n";
 	std::string text;
 	for (uint32_t v = 0; v < M; ++v) {
+		if (ps.kept_only && !keep[v]) continue;
 		cmd.place(text, v);
 		text += keep[v] ? "\t1\n" : "\t0\n";
 		cmd.spill(*os, text);
@@ -1731,6 +1817,8 @@ bool twk_ld::ComputeSingle(bool verbose, bool) {
 	const uint32_t n_samples = (uint32_t)reader.hdr.samples.size();      // (of the input: what is uploaded)
 	std::vector<uint32_t> keep;
 	if (!select_samples(settings, reader.hdr, keep)) return false;
+	VariantLists lists;
+	if (!read_variant_lists(settings, lists)) return false;
 	Interval tgt;
 	if (!parse_interval(settings.ival_strings[0], reader.hdr, tgt)) return false;
 	// Flanks (ld.cpp:145-153), 1-based inclusive matching of pos+1 (ld.cpp:192):
@@ -1757,7 +1845,8 @@ bool twk_ld::ComputeSingle(bool verbose, bool) {
 	if (targets.empty()) { std::cerr << "no data found for reference" << std::endl; return false; }
 	if (ref_compat()) others.resize(others.size() / 100 * 100);      // the reference keeps the neighbours in full groups of 100 only (ld.cpp:203-205, 239-244)
 	if (others.empty()) { std::cerr << "no surrounding variants" << std::endl; return false; }
-	const uint32_t nT = (uint32_t)targets.size(), nO = (uint32_t)others.size(), M = nT + nO;
+	uint32_t nT = (uint32_t)targets.size(), nO = (uint32_t)others.size();
+	const uint32_t M = nT + nO;
 	if (verbose) std::cerr << stamp("LOG") << pretty(nT) << " target and " << pretty(nO) << " surrounding variants..." << std::endl;
 
 	DeviceCtxs dc;
@@ -1783,6 +1872,9 @@ bool twk_ld::ComputeSingle(bool verbose, bool) {
 	if (!hip_ok(ctx, twk_hip_upload_bitvectors(ctx, 0, M, data.data(), any_mask ? mask.data() : nullptr, w64, meta.data()),
 	            "twk_hip_upload_bitvectors")) return false;
 	if (!apply_sample_selection(ctx, keep, M, (uint32_t)std::max(1, std::min(settings.n_threads, util::usable_cpus())), nullptr)) return false;
+	if (!apply_variant_selection(dc.ctx, settings, lists, reader.hdr, mImpl->rid, mImpl->pos, nT, nO, nullptr)) return false;      // (targets first, then the neighbours: the order is kept)
+	if (nT == 0) { std::cerr << "no data found for reference" << std::endl; return false; }
+	if (nO == 0) { std::cerr << "no surrounding variants" << std::endl; return false; }
 	RunSpec spec;
 	spec.nA = nT; spec.nB = nO; spec.triangleA = true; spec.rectAB = true;
 	spec.options = TWK_HIP_OPT_KEEP_LOW_AC | (ref_compat() ? TWK_HIP_OPT_REF_COMPAT : 0);      // the skip is commented out in CalculateSingle (:2267-2269)

@@ -55,6 +55,11 @@ class _Tile(C.Structure):
                 ("diag", C.c_int32), ("window", C.c_int32), ("l_window", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class _VariantFilter(C.Structure):      # twk_hip_variant_filter
+    _fields_ = [("min_maf", C.c_double), ("max_maf", C.c_double), ("min_mac", C.c_uint32), ("_pad", C.c_uint32),
+                ("max_missing", C.c_double), ("min_hwe", C.c_double)]
+
+
 class _Timing(C.Structure):
     _fields_ = [("count_ms", C.c_double), ("stats_ms", C.c_double), ("count_launches", C.c_uint64),
                 ("stats_launches", C.c_uint64), ("row_pairs", C.c_uint64), ("variant_pairs", C.c_uint64),
@@ -201,6 +206,10 @@ def load_library() -> C.CDLL:
     lib.twk_hip_get_meta.argtypes = [p, C.c_uint32, C.c_uint32, p]
     lib.twk_hip_set_hwe.argtypes = [p, C.c_uint32, C.c_uint32, p]
     lib.twk_hip_select_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_select_variants.argtypes = [p, C.POINTER(_VariantFilter), p, C.c_uint32, C.c_int32, C.POINTER(C.c_uint32)]
+    lib.twk_hip_variant_selection.argtypes = [p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.twk_hip_variant_map.argtypes = [p, C.c_uint32, C.c_uint32, p]
+    lib.twk_hip_select_variants_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_count_tile.argtypes = [p, C.c_int, C.POINTER(_Tile), p]
     lib.twk_hip_ld_tile.argtypes = [p, C.c_int, C.POINTER(_Tile), C.POINTER(_Filters), p, C.c_uint64,
                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -537,6 +546,57 @@ class HipLd:
         """Of the last selection: the kernel's time and the bytes of genotype rows it read and wrote."""
         ms, r, w = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_select_last(self._ctx, C.byref(ms), C.byref(r), C.byref(w)), "twk_hip_select_last")
+        return {"select_ms": ms.value, "bytes_read": int(r.value), "bytes_written": int(w.value)}
+
+    # ---- variant subsets (twk_hip_select_variants: the base stays on the device, the context works on the kept variants) ----
+    def select_variants(self, list=None, exclude=False, min_maf=0.0, max_maf=0.5, min_mac=0, max_missing=1.0, min_hwe=0.0) -> int:
+        """Keep the variants of the base - the data as uploaded, or the working set of a sample selection - that pass the list (strictly
+        ascending base indices; exclude: the list names the variants to drop) and every threshold.  -> n_kept.  Afterwards n_variants,
+        download(), marginals(), meta() and every compute call are those of the kept variants, indexed 0 .. n_kept - 1; variant_map()
+        gives their base indices.  A second call selects from the base again; select_variants(None) with every threshold off drops
+        the selection."""
+        off = (min_maf, max_maf, min_mac, max_missing, min_hwe) == (0.0, 0.5, 0, 1.0, 0.0)
+        n = C.c_uint32(0)
+        if list is None and off:
+            self._check(self._lib.twk_hip_select_variants(self._ctx, None, None, 0, 0, C.byref(n)), "twk_hip_select_variants")
+        else:
+            if not 0 <= int(min_mac) <= 0xFFFFFFFF:
+                raise HipError(E_INVALID, "twk_hip_select_variants", "min_mac outside 0 .. 2^32 - 1")
+            f = _VariantFilter(float(min_maf), float(max_maf), int(min_mac), 0, float(max_missing), float(min_hwe))
+            if list is None:
+                ptr, count = None, 0
+            else:
+                k = np.asarray(list)
+                if k.size and not np.issubdtype(k.dtype, np.integer):
+                    raise TypeError("select_variants: variant indices must be integers")
+                if k.size and (k.min() < 0 or k.max() > 0xFFFFFFFF):
+                    raise HipError(E_INVALID, "twk_hip_select_variants", "a variant index outside 0 .. 2^32 - 1")
+                k = np.ascontiguousarray(k.reshape(-1), dtype=np.uint32)
+                buf = k if k.size else np.zeros(1, dtype=np.uint32)          # (an empty list is a list: not NULL, which means "no list test")
+                ptr, count = buf.ctypes.data, k.size
+            self._check(self._lib.twk_hip_select_variants(self._ctx, C.byref(f), ptr, count, int(bool(exclude)), C.byref(n)), "twk_hip_select_variants")
+        self.n_variants = self.variant_selection()[1]
+        return int(n.value)
+
+    def variant_selection(self):
+        """-> (variants of the base, variants of the working set); equal when no selection is active."""
+        a, b = C.c_uint32(0), C.c_uint32(0)
+        self._check(self._lib.twk_hip_variant_selection(self._ctx, C.byref(a), C.byref(b)), "twk_hip_variant_selection")
+        return int(a.value), int(b.value)
+
+    def variant_map(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """-> uint32[count]: the base index of every working variant (the identity while no selection is active)."""
+        count = self.n_variants - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=np.uint32)
+        if count == 0 and 0 <= first <= self.n_variants:
+            return out                                                   # (an empty slice: the engine takes no zero count)
+        self._check(self._lib.twk_hip_variant_map(self._ctx, first, count, out.ctypes.data), "twk_hip_variant_map")
+        return out
+
+    def select_variants_last(self) -> dict:
+        """Of the last variant selection: the kernels' time and the bytes of genotype rows they read and wrote."""
+        ms, r, w = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_select_variants_last(self._ctx, C.byref(ms), C.byref(r), C.byref(w)), "twk_hip_select_variants_last")
         return {"select_ms": ms.value, "bytes_read": int(r.value), "bytes_written": int(w.value)}
 
     # ---- compute ----

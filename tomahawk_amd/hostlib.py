@@ -45,6 +45,8 @@ def lib():
         L.twk_hwe_exact.restype = C.c_double
         L.twk_file_sample_names.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.twk_resolve_samples.argtypes = [p, C.c_uint32, C.c_char_p, C.c_char_p, p, C.c_uint32, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
+        L.twk_resolve_variants.argtypes = [p, C.c_uint32, p, p, C.c_uint32, C.c_char_p, p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                           C.c_char_p, C.c_size_t]
         L.twk_record_codec_bound.restype = C.c_uint64
         L.twk_record_codec_bound.argtypes = [C.c_uint64]
         L.twk_record_codec_compress.restype = C.c_uint64
@@ -203,6 +205,27 @@ def resolve_samples(names, keep=None, remove=None):
     if rc != 0:
         raise ValueError(err.value.decode() or f"twk_resolve_samples failed: {rc}")
     return out[:n.value].copy()
+
+
+def resolve_variants(contigs, rid, pos, path):
+    """`--extract` / `--exclude` (csrc/host/twk_variant_list.h): the list file `path` - lines CONTIG:POS or CONTIG<whitespace>POS, further
+    columns ignored, '#' lines and empty lines skipped, POS as the commands print it (the stored position + 1) - against the variants
+    given by rid (an index into `contigs`) and the stored pos.  -> (the indices of every variant at a listed position, ascending (uint32),
+    the number of listed positions no variant has).  ValueError with the command's message for an unreadable file or a line that does
+    not parse (the line is named)."""
+    enc = [str(n).encode() for n in contigs]
+    arr = (C.c_char_p * max(len(enc), 1))(*enc)
+    rid = np.ascontiguousarray(rid, dtype=np.uint32)
+    pos = np.ascontiguousarray(pos, dtype=np.uint32)
+    assert rid.shape == pos.shape and rid.ndim == 1
+    out = np.zeros(max(len(rid), 1), dtype=np.uint32)
+    n, absent = C.c_uint32(0), C.c_uint64(0)
+    err = C.create_string_buffer(1024)
+    rc = lib().twk_resolve_variants(C.cast(arr, C.c_void_p), len(enc), rid.ctypes.data, pos.ctypes.data, len(rid), str(path).encode(),
+                                    out.ctypes.data, len(out), C.byref(n), C.byref(absent), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode() or f"twk_resolve_variants failed: {rc}")
+    return out[:n.value].copy(), int(absent.value)
 
 
 def sample_names(path, is_two=True):
