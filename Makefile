@@ -123,7 +123,8 @@ count-check:
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/count_table_check.cpp -o build/count_table_check
 	./build/count_table_check tests/golden/count_tables.json
 
-# The two-product form's host side (csrc/tools/two_check.cpp): its screen (csrc/hip/ld_two_screen.h) over every small genotype table, and the
+# The two-product form's host side (csrc/tools/two_check.cpp): its screens (csrc/hip/ld_two_screen.h: the H plane or the carrier plane H | Q as the
+# row operand) over every small genotype table, and the
 # work table of a launch with one plane row per row variant and two per column variant against a naive restatement and the recorded order of
 # tests/golden/count_tables_two.json: host code only, under AddressSanitizer and UBSan
 two-check:
@@ -133,8 +134,8 @@ two-check:
 
 # The prefix contraction's host side (csrc/tools/prefix_check.cpp): its screens (csrc/hip/ld_two_screen.h) over every pair of a small prefix and a
 # small suffix genotype table, the work table with per-tile stops (csrc/hip/ld_count_table.h) against a naive restatement and against the table
-# built without stops, and the planner's stops (csrc/hip/ld_plan.h) on the headline's frequency law: host code only, under AddressSanitizer
-# and UBSan
+# built without stops, and the planner's stops (csrc/hip/ld_plan.h) on the headline's frequency law - once with the H plane and once with the
+# carrier plane as the two-product launches' row operand: host code only, under AddressSanitizer and UBSan
 prefix-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/prefix_check.cpp -o build/prefix_check
@@ -149,7 +150,7 @@ annot-check:
 	./build/annot_term_check
 
 # Who may take which form of a count launch (csrc/hip/ld_form.h): decide_form over every combination of facts and grants, the transitions of
-# CallForms::gave_up and the ladder a redone tile descends (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
+# CallForms::gave_up, the ladder a redone tile descends and the choice of the two-product launches' row operand (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
 form-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/form_check.cpp -o build/form_check

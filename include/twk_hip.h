@@ -784,6 +784,14 @@ int twk_hip_plan_region_two(const twk_hip_plan_env* env, const twk_hip_variant_m
                             uint32_t tile_variants, int32_t window, uint32_t l_window,
                             twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                             uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end);
+/* ... with the row operand of the walk's two-product launches named: carrier == 0: the row variants' H planes (twk_hip_plan_region_two); != 0: their
+ * carrier planes H | Q, as the engine's launches take them on rows of more than 128 K chunks (option "carrier") - the cut is then asked of the carrier
+ * screen (csrc/hip/ld_two_screen.h: screen2c_expected_keeps) and lies further on. */
+int twk_hip_plan_region_two_operand(const twk_hip_plan_env* env, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                                    int32_t carrier, uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                                    uint32_t tile_variants, int32_t window, uint32_t l_window,
+                                    twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                                    uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end);
 
 /* Fisher's exact test on n caller-supplied 2x2 tables (tables[4*i + {0,1,2,3}] = n11, n12, n21, n22), two-sided P
  * into p_two_sided[i]: kt_fisher_exact (lib/fisher_math.cpp:231-267) as the pair math calls it
@@ -869,6 +877,9 @@ typedef struct {
 	                                 tiles and rounded down once per launch - so that row_pairs x words_per_row stays the work executed */
 	uint64_t prefix_chunks;       /* K chunks those launches' tiles were contracted over ...                                   */
 	uint64_t prefix_chunks_full;  /* ... and what whole rows would have been                                                   */
+	uint64_t carrier_launches;    /* (appended likewise) Two-product launches whose row operand was the row variants' carrier plane H | Q
+	                                 in the H plane's place (CH and CQ for HH and HQ).  They stay part of two_launches, with
+	                                 the same row_pairs accounting: one row x two rows per variant pair                        */
 } twk_hip_timing;
 /* Progress of twk_hip_ld_all / twk_hip_ld_region: `cb` runs on the calling thread after every tile
  * with the variant pairs finished so far in the current call and the tile counts.  Replaces the
@@ -899,6 +910,8 @@ typedef struct {
 	 * rebuilt; the version check does not catch it (only this library's own binding, built with it, reads the log). */
 	uint64_t prefix_chunks;       /* a prefix launch: K chunks its tiles were contracted over ... (else 0)      */
 	uint64_t prefix_chunks_full;  /* ... and what whole rows would have been; row_pairs is scaled by their ratio            */
+	uint32_t carrier;             /* (appended likewise) != 0: a kind-5 launch whose row operand was the carrier plane H | Q   */
+	uint32_t _pad2;
 } twk_hip_launch_stat;
 /* Copies the most recent min(capacity, launches kept) entries, oldest first; *n_total: launches seen since the reset. */
 int twk_hip_launch_log(twk_hip_ctx* ctx, twk_hip_launch_stat* out, uint32_t capacity, uint32_t* n_copied, uint64_t* n_total);

@@ -863,6 +863,7 @@ struct ScreenWork {
 	// [plane row][PREFIX_GRID]: the rows' suffix popcounts (k_row_suffix_popcount).  pre_stops == null: every tile over its whole rows.
 	const uint8_t* pre_stops; const uint32_t* pre_suffix;
 	uint32_t pre_gx, pre_tvA, pre_nchunks;
+	uint32_t carrier;                  // k_screen2_pairs: the matrix is (CH, CQ) of a launch whose row operand was the carrier plane (ld_two_screen.h: screen2c_*)
 };
 // -> terms[] of ScreenWork for n_pos set positions (P = 1: rowpop[pos]; P = 2: rowpop[2 pos] + 2 rowpop[2 pos + 1])
 __global__ void k_screen_terms(const uint32_t* __restrict__ rowpop, uint32_t n_pos, int P, double two_n, double cut, float4* __restrict__ terms) {

@@ -22,6 +22,8 @@ struct LaunchForm {
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
 	bool sample = false;           // a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name (k_count3_list_t<.., 1>), so that a
 	                               // kernel trace's statistics of the real launches are not diluted by half-millisecond ones
+	bool carrier = false;          // a two-product launch whose row operand is the carrier plane H | Q (CH + CQ in place of HH + HQ; ld_two_screen.h): an attribute of
+	                               // `two`, never set without it
 	bool prefix = false;           // a two- or three-product launch through a matrix whose tiles are contracted over a prefix of their rows (per-tile stops)
 	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
@@ -37,7 +39,8 @@ constexpr uint32_t FUSED_MAX_CHUNKS = 128;
 
 // What the owner of a launch allows it: `two` only where the two-product walk's owner says so for this launch (RegionRun, on the sorted set).
 // `prefix`: an attribute of such a launch's two- or three-product form, not a form of its own - stops for its tiles, where the owner's sample allows them.
-struct FormGrant { bool fused = true, three = true, two = false, sample = false, prefix = false; };
+// `carrier`: the owner holds carrier rows for this launch's row variants (carrier_operand below) - the row operand of its two-product form, if it takes it.
+struct FormGrant { bool fused = true, three = true, two = false, sample = false, prefix = false, carrier = false; };
 // What the tile plan, the filters and the options fix, whoever grants what.
 struct FormFacts {
 	bool two_pass = false;
@@ -46,9 +49,16 @@ struct FormFacts {
 	bool cut_screens = false;                               // an r2 cut-off a screen can use: minR2 > 1e-6 && minR2 <= 1
 	uint32_t chunks = 0;                                    // K chunks of a row (read only where a launch may fuse)
 	bool sorted_u = false;                                  // the set is PS_SORTED_U
-	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1;
+	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1, opt_carrier = 1;
 	uint32_t row_chunks = 0;                                // K chunks of a row (read only where a launch is granted the prefix)
+	uint32_t carrier_chunks = 0;                            // K chunks of a row (read only where a launch is granted the carrier plane)
 };
+// The row operand of a call's two-product launches: the carrier plane where option "carrier" allows it, the rows are longer than the fused form
+// ever takes - shorter ones gain little and the third plane is not worth its memory - and carrier rows for the row variants [0, rows_need) of the
+// walk are there.  rows_have < rows_need: they could not be allocated - the H plane as before, and no error.
+inline bool carrier_operand(long long opt_carrier, uint32_t row_chunks, uint32_t rows_have, uint32_t rows_need) {
+	return opt_carrier != 0 && row_chunks > FUSED_MAX_CHUNKS && rows_need > 0 && rows_have >= rows_need;
+}
 // A screen in front of the math needs plain phased planes with PhasedMath, or plain unphased planes (four products per pair, gathered in the
 // epilogue) with UnphasedMath, and an r2 cut-off the screen can use.  Such a launch fuses when its rows are short enough that no tile's K
 // range is split (option fused = 2: never split; 0: never fuse), and takes the three-product form (ld_count.hip.h) on unphased planes - or,
@@ -61,6 +71,7 @@ inline LaunchForm decide_form(const FormFacts& x, const FormGrant& g) {
 	lf.three = lf.unphased && g.three && x.opt_three != 0;
 	lf.fused = x.opt_fused != 0 && (x.opt_fused == 2 || x.chunks <= FUSED_MAX_CHUNKS);
 	if (lf.three && !lf.fused && !lf.two_pass && x.sorted_u && g.two && x.opt_two != 0) { lf.two = true; lf.three = false; }
+	lf.carrier = lf.two && g.carrier && x.opt_carrier != 0 && x.carrier_chunks > FUSED_MAX_CHUNKS;
 	// the prefix: only the matrix forms of the sorted walk, and only on rows the fused form never takes by policy - whatever "fused" is set to
 	lf.prefix = g.prefix && x.opt_prefix != 0 && (lf.two || lf.three_plain()) && !lf.two_pass && x.sorted_u && x.row_chunks > FUSED_MAX_CHUNKS;
 	return lf;
@@ -71,7 +82,7 @@ inline LaunchForm decide_form(const FormFacts& x, const FormGrant& g) {
 inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
 	if (was.prefix) { given.prefix = false; return given; }
 	if (!was.two) given.fused = given.three = false;
-	given.two = false;
+	given.two = given.carrier = false;
 	return given;
 }
 
@@ -79,7 +90,10 @@ inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
 struct CallForms {
 	bool fused = true, three = true, two = true, prefix = true;
 	// ... and allows a launch, whose owner wants three / two products for it (and stops for its tiles)
-	FormGrant grant(bool want_three, bool want_two, bool want_prefix = false) const { return FormGrant{fused, three && want_three, two && want_two, false, prefix && want_prefix}; }
+	// (the carrier plane is no form of the call's to give up: it goes where the two-product form goes)
+	FormGrant grant(bool want_three, bool want_two, bool want_prefix = false, bool want_carrier = false) const {
+		return FormGrant{fused, three && want_three, two && want_two, false, prefix && want_prefix, two && want_two && want_carrier};
+	}
 	// A launch of form `was`, given `given`, is through: a list that overflowed (cand_overflow) or held more candidates than the recount is worth
 	// (too_rich) ends the form for the rest of the call - but a form the launch was not given is not taken from the call on its account.
 	void gave_up(const LaunchForm& was, const FormGrant& given, bool cand_overflow, bool too_rich) {

@@ -33,6 +33,9 @@ struct PlanEnv {                                    // what the planner needs to
 	// the two-product walk (an unscreened UnphasedMath call over the allele-count-sorted set, twk_hip.hip region_dispatch): het / hom = carriers
 	// of either kind per position of the index space; the triangle is then cut at RegionPlan::two_end (plan_two_end)
 	const uint32_t* het = nullptr; const uint32_t* hom = nullptr; double two_margin = 0.95;
+	// ... the form of its launches' row operand: the carrier plane H | Q in the H plane's place (ld_two_screen.h: screen2c_*) - the cut is then asked of
+	// the carrier screen and lies further on (r2 >= 0.1: p ~ 0.21 for ~ 0.16)
+	bool carrier = false;
 	// options
 	bool band_launch = true, band_reverse = true; long long band_work_log2 = 19, band_max_launches = 8, band_list_entries = 0;
 	const twk_hip_variant_meta& at(uint32_t i) const { return meta[ids ? ids[i] : i]; }
@@ -336,7 +339,8 @@ inline uint32_t plan_two_end(const PlanEnv& e, const PlanGeom& g) {
 		for (uint32_t k = 0; k < n_ask && !kept; ++k) {
 			const uint32_t j = first + (uint32_t)(((uint64_t)(k + 1) * n_behind) / n_ask) - 1;
 			const ScreenMargins m{e.het[g.a0 + r], e.hom[g.a0 + r], e.het[g.b0 + j], e.hom[g.b0 + j]};
-			kept = screen2_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin);
+			kept = e.carrier ? screen2c_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin)
+			                 : screen2_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin);
 		}
 		if (kept) break;
 	}
@@ -356,12 +360,14 @@ struct PrefixEnv {
 	uint32_t n_variants = 0, n_samples = 0, nchunks = 0;
 	double cut = 0, margin = 0.95;
 	uint32_t fixed_grid = 0;                                           // test hook "prefix_stop": this grid index for every tile (0: the planner's)
+	bool carrier = false;                                              // a two-product launch's row operand is the carrier plane (PlanEnv::carrier)
 	uint64_t samples_before(uint32_t g) const { return std::min<uint64_t>((uint64_t)prefix_stop_chunks(g, nchunks) * 32u * 32u, n_samples); }
 	bool dropped(bool two, uint32_t vA, uint32_t vB, uint32_t g) const {
 		if (g >= PREFIX_GRID) return true;       // (whole rows: the screen itself decides)
 		const ScreenMargins m{het[vA], hom[vA], het[vB], hom[vB]};
 		const SuffixMargins x{suffix[(size_t)(2 * vA) * PREFIX_GRID + g], suffix[(size_t)(2 * vA + 1) * PREFIX_GRID + g],
 		                      suffix[(size_t)(2 * vB) * PREFIX_GRID + g], suffix[(size_t)(2 * vB + 1) * PREFIX_GRID + g]};
+		if (two && carrier) return !prefix_expected_keeps_carrier(m, x, (double)samples_before(g), 2.0 * (double)n_samples, cut, margin);
 		return !prefix_expected_keeps(m, x, two, (double)samples_before(g), 2.0 * (double)n_samples, cut, margin);
 	}
 	// smallest grid index in [1, PREFIX_GRID] at which the pair is dropped, walked from `hint` (the answer of a neighbouring tile: one or two

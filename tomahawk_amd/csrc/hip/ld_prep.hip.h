@@ -129,6 +129,18 @@ __global__ void k_row_suffix_popcount(const uint32_t* __restrict__ rows, uint32_
 	if (lane < 32) out[(size_t)r * 32 + lane] = suffix;
 }
 
+// Carrier rows of the first n variants of an unphased plane set (the two-product form's row operand, ld_two_screen.h): out[v][k] = H | Q of
+// variant v - plane rows 2v and 2v + 1 - one row of W words per variant.  W is a multiple of 4; grid.y walks the variants, 16 bytes per thread:
+// one streaming pass.  Rows behind n are the caller's to zero.
+__global__ void k_build_carrier(const uint32_t* __restrict__ rows, uint32_t W, uint32_t n, uint32_t* __restrict__ out) {
+	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x, W4 = W / 4;
+	if (k >= W4) return;
+	for (uint32_t v = blockIdx.y; v < n; v += gridDim.y) {
+		const uint4 h = reinterpret_cast<const uint4*>(rows + (size_t)(2 * v) * W)[k], q = reinterpret_cast<const uint4*>(rows + (size_t)(2 * v + 1) * W)[k];
+		reinterpret_cast<uint4*>(out + (size_t)v * W)[k] = make_uint4(h.x | q.x, h.y | q.y, h.z | q.z, h.w | q.w);
+	}
+}
+
 // Keep the even bits of a 64-bit word, packed into 32 bits.
 __device__ __forceinline__ uint32_t compress_even(uint64_t x) {
 	x &= 0x5555555555555555ull;

@@ -20,7 +20,8 @@ namespace twk {
 // launch's list, appended with one atomic per block.  Structural tests as in the fused epilogue (the list math checks them again).
 // TWO: the matrix is that of a two-product launch (k_count_list_t over the row variants' H planes against the column variants' H and Q
 // rows: (HH, HQ) where the three-product form leaves (HH, S), same layout), the test screen2_keeps - the same doubles with S_lo = HQ and
-// S_hi = HQ + qA + min(qA, qB) in S's place (ld_two_screen.h) - and a candidate is (A, B, HH, HQ, -, -).
+// S_hi = HQ + qA + min(qA, qB) in S's place (ld_two_screen.h) - and a candidate is (A, B, HH, HQ, -, -).  ScreenWork::carrier: the row operand was
+// the carrier plane H | Q, the matrix holds (CH, CQ) in the same layout and the test is screen2c_keeps; a candidate is (A, B, CH, CQ, -, -).
 constexpr int SCREEN3_THREADS = 256;
 template <bool TWO>
 __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) {
@@ -51,10 +52,11 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 				const uint32_t* fA = s.pre_suffix + (size_t)(2 * vA) * PREFIX_GRID + g;
 				const uint32_t* fB = s.pre_suffix + (size_t)(2 * vB) * PREFIX_GRID + g;
 				const SuffixMargins x{fA[0], fA[PREFIX_GRID], fB[0], fB[PREFIX_GRID]};
-				ok = TWO ? screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut) : screen3_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut);
+				ok = TWO ? (s.carrier ? screen2c_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut) : screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut))
+				         : screen3_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut);
 			}
 		}
-		if (!stop) ok = TWO ? screen2_keeps(m, hh, s_sum, s.two_n, s.cut) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
+		if (!stop) ok = TWO ? (s.carrier ? screen2c_keeps(m, hh, s_sum, s.two_n, s.cut) : screen2_keeps(m, hh, s_sum, s.two_n, s.cut)) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
 	}
 	__shared__ uint32_t wave_n[SCREEN3_THREADS / 64];
 	__shared__ unsigned long long block_base;
@@ -92,7 +94,8 @@ void k_screen2_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 // next to the contraction; the host stops using the three-product forms when a launch's candidates are too many for that to
 // hold (Launch::too_rich -> ld_form.h: CallForms::gave_up).  The recount also proves the contraction, always: a candidate whose (HH, S) disagree with its
 // own four products is counted in *mismatches, and the host fails the call on it.  two != 0: the candidates are a two-product launch's,
-// (A, B, HH, HQ) - the proof is then that both products equal their recount.
+// (A, B, HH, HQ) - the proof is then that both products equal their recount.  two == 2: the launch's row operand was the carrier plane, the
+// candidates are (A, B, CH, CQ), and the proof compares them with HH + QH and HQ + QQ of the recount; the records are the four products' as ever.
 template <int LANES>
 __global__ __launch_bounds__(256)
 void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t W_live, uint32_t* __restrict__ cand,
@@ -124,7 +127,10 @@ void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t 
 			const uint32_t d_qh = __popc(b.x & x.x) + __popc(b.y & x.y) + __popc(b.z & x.z) + __popc(b.w & x.w);
 			const uint32_t d_qq = __popc(b.x & y.x) + __popc(b.y & y.y) + __popc(b.z & y.z) + __popc(b.w & y.w);
 			hh += d_hh; hq += d_hq; qh += d_qh; qq += d_qq;
-			if (p < pre4) { p_hh += d_hh; p_s += two ? d_hq : d_qh + d_hq + 2u * d_qq; }
+			if (p < pre4) {
+				if (two == 2) { p_hh += d_hh + d_qh; p_s += d_hq + d_qq; }      // the carrier plane's products: CH = HH + QH, CQ = HQ + QQ
+				else { p_hh += d_hh; p_s += two ? d_hq : d_qh + d_hq + 2u * d_qq; }
+			}
 		}
 #pragma unroll
 		for (int d = 1; d < LANES; d <<= 1) {

@@ -11,6 +11,7 @@
 // Both of the screen's test values rise with S and e_lo <= e_hi at every S, so e_lo(S_lo) <= e_lo(S) <= e_hi(S) <= e_hi(S_hi): when the two
 // outer ones lie inside (-sqrt(bound), sqrt(bound)), so do the two the three-product screen would have tested.  screen2_keeps therefore keeps
 // every pair screen3_keeps keeps - and, for a row variant with few hom-alt carriers (qA ~ p^2 N), hardly any other.
+// (Further down: the same two products of the row variant's carrier plane H | Q, whose interval is narrower - screen2c_*.)
 #pragma once
 #include <stdint.h>
 
@@ -53,6 +54,23 @@ TWK_SCREEN_FN bool screen2_expected_keeps(const ScreenMargins& m, double n_sampl
 	return screen_keeps_between(m, hh, hq, hq + screen2_slack(m), two_n, cut, margin * margin);
 }
 
+// ---- the carrier plane as the row operand ------------------------------------------------------------------------------
+// A two-product launch may contract the row variant's carrier plane C_A = H_A | Q_A in the H plane's place.  It leaves
+//     CH = popc(C_A & H_B) = HH + QH,     CQ = popc(C_A & Q_B) = HQ + QQ,
+// and with S = QH + HQ + 2 QQ = CQ + popc(Q_A & C_B) and T = S + HH = CH + CQ + QQ (e_lo is tested at S, e_hi at T):
+//     S >= CQ,     T <= CH + CQ + min(qA, qB).
+// Both ends lie inside the H form's - CQ >= HQ, and CH + CQ + min = HH + HQ + (QH + QQ) + min <= HH + HQ + qA + min - so screen2c_keeps keeps
+// every pair screen3_keeps keeps and none that screen2_keeps drops; the gap above T falls from about 2 qA to min(qA, qB).
+TWK_SCREEN_FN double screen2c_slack(const ScreenMargins& m) { return (double)(m.qA < m.qB ? m.qA : m.qB); }       // (T's upper end) - CH - CQ
+TWK_SCREEN_FN bool screen2c_keeps(const ScreenMargins& m, uint32_t ch, uint32_t cq, double two_n, double cut) {
+	return screen_keeps_between(m, (double)ch, (double)cq, (double)cq + screen2c_slack(m), two_n, cut);
+}
+// The planner's question of the carrier form: under independence CH = cA hB / N and CQ = cA qB / N with cA = hA + qA.
+TWK_SCREEN_FN bool screen2c_expected_keeps(const ScreenMargins& m, double n_samples, double two_n, double cut, double margin) {
+	const double ca = (double)m.hA + (double)m.qA, ch = ca * (double)m.hB / n_samples, cq = ca * (double)m.qB / n_samples;
+	return screen_keeps_between(m, ch, cq, cq + screen2c_slack(m), two_n, cut, margin * margin);
+}
+
 // ---- the prefix contraction ------------------------------------------------------------------------------------------
 // A launch may contract only the first K chunks [0, stop) of a tile's rows.  Per sample, with g = 0 / 1 / 2 alt alleles, the contribution to
 // S = QH + HQ + 2 QQ is >= 0 and the contribution to S + HH is exactly min(gA, gB); summed over the unread suffix, whose margins are the
@@ -85,6 +103,20 @@ TWK_SCREEN_FN bool prefix_expected_keeps(const ScreenMargins& m, const SuffixMar
 	if (two) return screen_keeps_between(m, hh, hq, hq + qa + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut, margin * margin);
 	const double s = (qa * hb + ha * qb + 2.0 * qa * qb) / n_pre;
 	return screen_keeps_between(m, hh, s, s + prefix_slack(x), two_n, cut, margin * margin);
+}
+
+// The carrier form over the prefix: ch = CH_pre, cq = CQ_pre.  S_pre >= CQ_pre and T_pre <= CH_pre + CQ_pre + min(qa_pre, qb_pre) as over whole
+// rows, with the prefix margins (total minus suffix); the unread suffix adds prefix_slack(x) to the upper end as in the other prefix screens.
+TWK_SCREEN_FN bool screen2c_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t ch, uint32_t cq, double two_n, double cut) {
+	const double qa = (double)(m.qA - x.qA), qb = (double)(m.qB - x.qB);
+	return screen_keeps_between(m, (double)ch, (double)cq, (double)cq + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut);
+}
+// ... and the planner's question for a stop of a carrier launch (prefix_expected_keeps with two = true, in the carrier form).
+TWK_SCREEN_FN bool prefix_expected_keeps_carrier(const ScreenMargins& m, const SuffixMargins& x, double n_pre, double two_n, double cut, double margin) {
+	if (n_pre <= 0) return true;
+	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
+	const double ch = (ha + qa) * hb / n_pre, cq = (ha + qa) * qb / n_pre;
+	return screen_keeps_between(m, ch, cq, cq + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut, margin * margin);
 }
 
 // The grid of stops: PREFIX_GRID points along a row of nchunks K chunks, prefix_step chunks apart; grid index g stands for the stop

@@ -110,6 +110,12 @@ struct PlaneSet {
 	// the prefix contraction: suffix popcounts of every plane row on the grid of stops, [rows_alloc][PREFIX_GRID], built the first time a
 	// call may take the form (ensure_suffix) and kept with the set - on the device for the screens, on the host for the planner
 	DevBuf<uint32_t> suffix; std::vector<uint32_t> h_suffix;
+	// the carrier plane: H | Q of the variants [0, carrier_n) of the sorted unphased set, one row of W words each and a zeroed pad of one
+	// tile of rows behind them (a tile stages 128 rows from its first) - the row operand of the two-product launches on long rows.  Built the first
+	// time a call's cut needs it, grown when a later cut needs more rows (ensure_carrier), kept and dropped with the set.  carrier_rows: its first row,
+	// placed inside carrier_buf so that it lies a whole number of rows from `rows` - CountWork addresses every row as rows + row x W, so a count launch
+	// reaches both through one base and a row offset (carrier_operand_rows)
+	DevBuf<uint32_t> carrier_buf; uint32_t* carrier_rows = nullptr; uint32_t carrier_n = 0;
 };
 
 // Plane sets a context can hold: one per PlaneKind in file order, plus the masked unphased planes
@@ -209,6 +215,7 @@ namespace {
 	X(fused, 1, 0, 2, false, "fused count -> r2 screen kernel (no count matrix; DESIGN 3.2a): 0 never, 1 rows of <= 128 K chunks, 2 always") \
 	X(three, 1, 0, 2, false, "UnphasedMath on planes without missing genotypes, r2 cut-off > 1e-6: contract three products a pair (HH and S = QH + HQ + 2 QQ: all the screen reads) and recount the four products of the pairs that pass (DESIGN 3.1a); 0: four products for every pair; 2: keep to three whatever a launch's candidate density (1 samples every launch first)") \
 	X(two, 1, 0, 2, false, "UnphasedMath, whole triangle without a window, rows too long to fuse, three = 1 and no tile edge given: walk the allele-count-sorted planes and contract two products a pair (HH and HQ of the row variant's H plane; S bounded from the margins) in the launches whose rows have few hom-alt carriers (DESIGN 3.1b); 0: never (the call walks the file order); 2: in every launch of that walk, whatever the predicate and the samples say") \
+	X(carrier, 1, 0, 1, false, "the two-product walk on rows of more than 128 K chunks: its two-product launches contract the row variant's carrier plane (H or Q, bit by bit) in the H plane's place (CH = HH + QH and CQ = HQ + QQ: S >= CQ and S + HH <= CH + CQ + min(qA, qB)), which moves the walk's cut from p ~ 0.16 to ~ 0.21 at r2 >= 0.1; one more plane row per row variant in front of the cut, built on first use and kept with the planes (DESIGN 3.1b); 0: always the H plane") \
 	X(prefix, 1, 0, 2, false, "the two-product walk on rows of more than 128 K chunks: a launch contracts each tile over a prefix of its rows, up to a stop the planner chooses per tile, and its screen bounds the unread samples by the rows' suffix margins; what it keeps is recounted over the whole rows (DESIGN 3.1c); 0: never; 1: launches whose sample with stops is poor in candidates; 2: every eligible launch whatever its sample") \
 	X(prefix_margin, 950, 1, 1000, false, "... the planner asks with the square root of the screen's bound shrunk to this many thousandths of it (950 as the two-product planner's two_margin = 0.95)") \
 	X(prefix_stop, 0, 0, 32, false, "test hook: this point of the 32-point grid of stops for every tile of a prefix launch (0: the planner's stops)") \
@@ -585,6 +592,48 @@ int ensure_suffix(twk_hip_ctx* c, int set) {
 	return TWK_HIP_OK;
 }
 
+// ... with the carrier rows H | Q of its variants [0, n) (the two-product form's row operand on long rows): one streaming pass over those
+// variants' planes, the first time a call's cut needs them and again when a later cut needs more; kept with the set.  -> TWK_HIP_E_NOMEM leaves the
+// set without carrier rows (the call's two-product launches then contract the H planes as before).
+int ensure_carrier(twk_hip_ctx* c, int set, uint32_t n) {
+	int rc = ensure_planes(c, set); if (rc) return rc;
+	PlaneSet& ps = c->planes[set];
+	if (planes_per_variant(set_kind(set)) != 2) return TWK_HIP_E_STATE;
+	n = std::min(n, c->M);
+	if (ps.carrier_rows && ps.carrier_n >= n) return TWK_HIP_OK;
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));      // (nothing reads the rows that are replaced)
+	ps.carrier_rows = nullptr; ps.carrier_n = 0;
+	// a zeroed pad of one tile of rows behind the last, and one row of slack to place the first row in
+	const size_t n_rows = (size_t)round_up(n, TILE) + TILE, words = (n_rows + 1) * ps.W;
+	HIPCHK(c, ps.carrier_buf.reserve(words, words, nullptr));
+	// the first row: the first address of the buffer that lies a whole number of rows from the set's planes, in front of them or behind (byte
+	// distances: a row is W words, a multiple of 128 bytes, so the rows stay aligned like the planes')
+	const intptr_t pitch = (intptr_t)ps.W * 4, d = (intptr_t)reinterpret_cast<uintptr_t>(ps.rows) - (intptr_t)reinterpret_cast<uintptr_t>(ps.carrier_buf.get());
+	const intptr_t off = ((d % pitch) + pitch) % pitch, dist = (d - off) / pitch;      // rows from the first carrier row to the planes' first (negative: the planes lie in front)
+	// (both operands of a launch are addressed from the lower of the two bases in 32-bit row numbers: CountWork::rowA0 / rowB0)
+	if ((dist < 0 ? -dist : dist) + (intptr_t)std::max<size_t>(n_rows, ps.rows_alloc) >= (intptr_t)1 << 31) { ps.carrier_buf.reset(); return TWK_HIP_E_NOMEM; }
+	uint32_t* first = ps.carrier_buf.get() + off / 4;
+	// zeroed: the slack in front of the first row and everything behind row n - the pad; the kernel writes the rows [0, n) whole
+	if (off) HIPCHK(c, hipMemsetAsync(ps.carrier_buf.get(), 0, (size_t)off, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(first + (size_t)n * ps.W, 0, (words - (size_t)off / 4 - (size_t)n * ps.W) * 4, c->s_compute));
+	if (n) {
+		hipLaunchKernelGGL(k_build_carrier, dim3((ps.W / 4 + 255) / 256, std::min<uint32_t>(n, 65535u)), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, n, first);
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	ps.carrier_rows = first; ps.carrier_n = n;
+	return TWK_HIP_OK;
+}
+// The two operands of a count launch whose row axis walks the carrier rows from variant rowA0 on and whose column axis the planes from plane row rowB0 on,
+// as CountWork addresses them: one base and two row numbers (ensure_carrier placed the carrier rows a whole number of rows from the planes).
+struct OperandRows { const uint32_t* base; uint32_t rowA0, rowB0; };
+OperandRows carrier_operand_rows(const PlaneSet& ps, uint32_t rowA0, uint32_t rowB0) {
+	const intptr_t pitch = (intptr_t)ps.W * 4;
+	const intptr_t dist = ((intptr_t)reinterpret_cast<uintptr_t>(ps.carrier_rows) - (intptr_t)reinterpret_cast<uintptr_t>(ps.rows)) / pitch;
+	if (dist >= 0) return OperandRows{ps.rows, (uint32_t)dist + rowA0, rowB0};
+	return OperandRows{ps.carrier_rows, rowA0, (uint32_t)(-dist) + rowB0};
+}
+
 // C_words words of count matrix / candidate list and `capacity` survivors for the slot's next launch.
 int ensure_slot(twk_hip_ctx* c, Slot& s, size_t C_words, unsigned long long capacity) {
 	HIPCHK(c, s.C.reserve(C_words, C_words, &c->graveyard));
@@ -624,11 +673,16 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	const PlaneSet& ps = c->planes[set];
 	const int P = planes_per_variant(set_kind(set));
 	// two products: one plane row - the H plane, every other row - per row variant, so tiles of 128 row variants x 64 column variants
+	// ... or, a carrier launch, consecutive rows of the set's carrier plane (ensure_carrier): same tiles, same table, rows of their own
 	const int PA = two ? 1 : P;
-	const uint32_t stepA = (uint32_t)(P / PA);
+	const uint32_t stepA = form.carrier ? 1u : (uint32_t)(P / PA);
 	if (two && (P != 2 || fuse || which != 0)) return TWK_HIP_E_STATE;
+	if (form.carrier && !two) return TWK_HIP_E_STATE;
 	const Geometry g = tile_geometry(P, t, PA);
-	if (((uint64_t)t.rowA0 * PA + g.rowsA) * stepA > ps.rows_alloc || (uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
+	if (form.carrier) {      // every row variant has its carrier row, and a tile's 128 rows end inside the zeroed pad
+		if (!ps.carrier_rows || (uint64_t)t.rowA0 + t.nA > ps.carrier_n || (uint64_t)t.rowA0 + g.rowsA > (uint64_t)round_up(ps.carrier_n, TILE) + TILE) return TWK_HIP_E_STATE;
+		if ((uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
+	} else if (((uint64_t)t.rowA0 * PA + g.rowsA) * stepA > ps.rows_alloc || (uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
 	if (g.gx > 0xFFFFu || g.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
 	const bool diag = t.diag && t.rowA0 == t.rowB0;
 	// the tiles and the units of work (ld_count_table.h; "count_min_chunks" is a test hook: 1 splits short rows too; "seg" 0: whole tiles and
@@ -647,7 +701,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		if (!(two || three) || fuse || which != 0 || P != 2 || ps.h_suffix.size() != (size_t)ps.rows_alloc * PREFIX_GRID || ps.h_het.size() != c->M) return TWK_HIP_E_STATE;
 		pe.het = ps.h_het.data(); pe.hom = ps.h_hom.data(); pe.suffix = ps.h_suffix.data();
 		pe.n_variants = c->M; pe.n_samples = c->N; pe.nchunks = nchunks;
-		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.fixed_grid = (uint32_t)c->opt.prefix_stop;
+		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.fixed_grid = (uint32_t)c->opt.prefix_stop; pe.carrier = form.carrier;
 		pre_grid.assign((size_t)g.gy * g.gx, (uint8_t)PREFIX_GRID);
 	}
 	std::vector<uint32_t> stops;
@@ -673,7 +727,8 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	HIPCHK(c, hipEventRecord(e0, c->s_compute));
 	if (T) {
 		const uint32_t last_halves = c->opt.skip_pad ? count_last_halves(ps.W_live, ps.W) : 0;      // (measurement hook: 0 = contract the zero padding too)
-		const CountWork w = count_work(ps.rows, ps.W, t.rowA0 * PA, t.rowB0 * P, s.d_tiles[which], tb, s.C, g.ldc,
+		const OperandRows op = form.carrier ? carrier_operand_rows(ps, t.rowA0, t.rowB0 * P) : OperandRows{ps.rows, t.rowA0 * PA, t.rowB0 * P};
+		const CountWork w = count_work(op.base, ps.W, op.rowA0, op.rowB0, s.d_tiles[which], tb, s.C, g.ldc,
 		                               c->tickets + ((&s - c->slot) * 2 + which) * 8, last_halves, s.n_out + 4, stepA);
 		HIPCHK(c, hipMemsetAsync(w.ticket, 0, 8 * 4, c->s_compute));
 		const FusedArgs* d_fa = reinterpret_cast<const FusedArgs*>(s.d_tiles[which] + words_units);
@@ -789,7 +844,8 @@ LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters
 	x.two_pass = pl.set2 >= 0; x.reduce = c->reduce.kind; x.sorted_u = pl.set1 == PS_SORTED_U;
 	x.phased_plain = pl.phased1 && k == PK_PHASED; x.unphased_plain = !pl.phased1 && k == PK_UNPHASED;
 	x.cut_screens = f.minR2 > 1e-6 && f.minR2 <= 1.0;
-	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix;
+	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix; x.opt_carrier = c->opt.carrier;
+	if (grant.carrier && c->opt.carrier != 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK && c->planes[pl.set1].carrier_rows) x.carrier_chunks = c->planes[pl.set1].W / KC;
 	// (stops are not combined with the measurement hooks that walk a tile's K range their own way)
 	if (grant.prefix && c->opt.prefix != 0 && c->opt.seg == 0 && c->opt.xcd_queues == 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK) x.row_chunks = c->planes[pl.set1].W / KC;
 	if (may_screen(x, grant) && x.opt_fused != 0) {
@@ -812,10 +868,10 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	const PlaneSet& ps = c->planes[set];
 	if (ps.W_live <= 1024)
 		hipLaunchKernelGGL(k_recount_unphased<16>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.carrier ? 2 : s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
 	else
 		hipLaunchKernelGGL(k_recount_unphased<64>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.carrier ? 2 : s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -993,7 +1049,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		sw.n_variants = c->M; sw.diag = (t.diag && t.rowA0 == t.rowB0) ? 1 : 0;
 		sw.col_hi = cr ? cr->d_hi : nullptr; sw.hi_a0 = cr ? cr->a0 : 0; sw.hi_b0 = cr ? cr->b0 : 0; sw.hi_n = cr ? cr->n_hi : 0;
 		sw.list_zone = cr ? cr->list_zone : 0; sw.probe_zone = cr ? cr->probe_zone : 0;
-		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2;
+		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2; sw.carrier = form.carrier ? 1u : 0u;
 		{	// slots a wave reserves at a time: what it cannot use is lost to the list, so at most an eighth of the list's
 			// capacity may be tied up in the waves' windows (small tiles: 0, i.e. one atomic per wave and tile)
 			const unsigned long long per_wave = l.cand_cap / (8ull * c->resident_blocks * (COUNT_THREADS / 64));
@@ -1147,7 +1203,7 @@ void watch_launch(twk_hip_ctx* c, const Slot& s, float ms, const twk_hip_tile_de
 	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three || s.l.form.two) ? s.h_n_out[2] : 0;
 	st.shader_mhz = s.h_n_out[5] ? (double)s.h_n_out[4] / (double)s.h_n_out[5] * 100.0 : 0.0;
 	st.words_per_row = c->planes[s.l.plane_set].W_live;
-	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full;
+	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full; st.carrier = s.l.form.carrier ? 1u : 0u;
 	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.two ? 5u : s.l.form.three_plain() ? 1u : 0u);
 	unsigned long long lo = ~0ull, hi = 0;
 	for (int x = 0; x < 8; ++x) if (s.h_n_out[8 + x]) { lo = std::min(lo, s.h_n_out[8 + x]); hi = std::max(hi, s.h_n_out[8 + x]); }
@@ -1292,9 +1348,9 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) s.l.too_rich = true;      // (the launch's owner folds it into the call: CallForms::gave_up)
 	}
 	if (s.l.form.two) {
-		c->timing.two_launches += 1; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
+		c->timing.two_launches += 1; c->timing.carrier_launches += s.l.form.carrier ? 1 : 0; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
 		if (s.h_n_out[3]) {      // as above: the recount is the contraction's proof
-			snprintf(c->err, sizeof(c->err), "two-product contraction: %llu candidates whose (HH, HQ) differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], t.rowA0, t.nA, t.rowB0, t.nB);
+			snprintf(c->err, sizeof(c->err), "two-product contraction: %llu candidates whose %s differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], s.l.form.carrier ? "(CH, CQ)" : "(HH, HQ)", t.rowA0, t.nA, t.rowB0, t.nB);
 			return TWK_HIP_E_DEVICE;
 		}
 	}
@@ -1461,7 +1517,7 @@ int run_tile_sync(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const tw
                   unsigned long long capacity, unsigned long long* n_out, const Deliver& to, const ColRange* cr = nullptr) {
 	Slot& s = c->slot[SYNC_SLOT];
 	for (;;) {
-		FormGrant grant = calls.grant(given.three, given.two);
+		FormGrant grant = calls.grant(given.three, given.two, false, given.carrier);      // (a two-product tile redone over whole rows keeps its row operand)
 		grant.fused = grant.fused && given.fused; grant.sample = given.sample;
 		int rc = enqueue_tile(c, mode, t, f, grant, s, capacity, cr); if (rc) return rc;
 		rc = finish_tile(c, s, t, n_out, to);
@@ -2321,7 +2377,8 @@ struct RegionRun {
 
 	// What launch i of the plan may be: the call's forms, three and two products as the launch's own sample decided.  A tile redone synchronously is not
 	// bound by a sample: it may be whatever the call still allows but two products (redo_grant).
-	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0, want_prefix[i] != 0); }
+	// (env.carrier: the region's two-product launches contract the carrier plane - region_impl holds carrier rows for every row in front of the cut)
+	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0, want_prefix[i] != 0, env.carrier); }
 	FormGrant redo_grant() const { return calls.grant(true, false); }
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, CallForms& calls_, twk_hip_record_sink sink_, void* user_)
@@ -2449,7 +2506,7 @@ struct RegionRun {
 				Slot& ss = c->slot[SYNC_SLOT];
 				unsigned long long nrec = 0;
 				// (three products granted: a sample is only taken where the call allows them; and its own overflow or richness decides its launch, not the call)
-				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true, prefix && calls.prefix}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
+				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true, prefix && calls.prefix, two && calls.two && env.carrier}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
 				if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
 				cand = ss.h_n_out[2];
 				c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
@@ -2600,6 +2657,8 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, const CallF
 			for (uint32_t v = 0; v < c->M; ++v) { ps.h_het[v] = pop[2 * (size_t)v]; ps.h_hom[v] = pop[2 * (size_t)v + 1]; }
 		}
 		env.het = ps.h_het.data(); env.hom = ps.h_hom.data();
+		// the carrier plane as the row operand: asked for here, granted by region_impl once the rows in front of the cut it gives are there
+		env.carrier = c->opt.carrier != 0 && ps.W / KC > FUSED_MAX_CHUNKS;
 		// the prefix contraction: the rows' suffix margins, the first time a call may take the form (no room for the table: the call takes no stops)
 		if (c->opt.prefix != 0 && calls.prefix && f->minR2 > 1e-6 && f->minR2 <= 1.0 && ps.W / KC > FUSED_MAX_CHUNKS) {
 			const int rc = ensure_suffix(c, PS_SORTED_U);
@@ -2639,6 +2698,21 @@ static int region_impl(twk_hip_ctx* c, const RegionArgs& a, CallForms& calls) {
 	int rc = plan_env_for(c, a.mode, a.f, calls, env); if (rc) return rc;
 	RegionPlan plan;
 	plan_region(env, g, plan);
+	if (env.carrier) {
+		// The carrier form's cut lies behind the H form's: carrier rows for every row variant of this shard's two-product launches (option two = 2: every
+		// launch of the walk), built now if they are not there.  No room for them: the plan of the H form, as before.
+		PlaneSet& ps = c->planes[PS_SORTED_U];
+		const uint32_t walk_end = c->opt.two == 2 ? g.nA : plan.two_end, need = plan.r0 < std::min(walk_end, plan.r1) ? g.a0 + std::min(walk_end, plan.r1) : 0;
+		if (need) {
+			rc = ensure_carrier(c, PS_SORTED_U, need);
+			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; }
+			else if (rc) return rc;
+		}
+		if (!carrier_operand(c->opt.carrier, ps.W / KC, ps.carrier_rows ? ps.carrier_n : 0, need)) {
+			env.carrier = false;
+			plan_region(env, g, plan);
+		}
+	}
 	RegionRun run(c, a.mode, a.f, g, env, plan, calls, a.sink, a.user);
 	run.mark("region: mode", (size_t)a.mode, a.nA);
 	rc = run.prepare(); if (rc) return rc;
@@ -3359,6 +3433,14 @@ int twk_hip_plan_region_two(const twk_hip_plan_env* pe, const twk_hip_variant_me
                             uint32_t tile_variants, int32_t window, uint32_t l_window,
                             twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                             uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end) {
+	return twk_hip_plan_region_two_operand(pe, meta, popc, het, hom, two_margin, 0, n_variants, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window,
+	                                       tiles, capacity, n_tiles, n_band_launches, row_begin, row_end, n_pairs, lo, hi, two_end);
+}
+int twk_hip_plan_region_two_operand(const twk_hip_plan_env* pe, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                                    int32_t carrier, uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                                    uint32_t tile_variants, int32_t window, uint32_t l_window,
+                                    twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                                    uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end) {
 	if ((het != nullptr) != (hom != nullptr)) return TWK_HIP_E_INVALID;
 	if (!pe || !meta || !n_tiles || (capacity && !tiles) || n_parts == 0 || part >= n_parts) return TWK_HIP_E_INVALID;
 	if (nA == 0 || nB == 0 || (uint64_t)a0 + nA > n_variants || (uint64_t)b0 + nB > n_variants) return TWK_HIP_E_INVALID;
@@ -3370,6 +3452,7 @@ int twk_hip_plan_region_two(const twk_hip_plan_env* pe, const twk_hip_variant_me
 	env.screen = pe->screen; env.minR2 = pe->minR2; env.fused = pe->fused != 0; env.phased_math = pe->phased_math != 0;
 	env.meta = meta; env.ids = nullptr; env.popc = popc;
 	env.het = het; env.hom = hom; if (two_margin > 0) env.two_margin = two_margin;
+	env.carrier = carrier != 0 && het != nullptr;
 	env.band_launch = pe->band_launch != 0; env.band_reverse = pe->band_reverse != 0; env.band_work_log2 = pe->band_work_log2; env.band_max_launches = std::max<long long>(pe->band_max_launches, 1);
 	const PlanGeom g{a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window};
 	RegionPlan plan;

@@ -132,11 +132,59 @@ void check_gave_up() {
 	}
 }
 
+// The carrier plane as the row operand of a two-product launch: an attribute of `two` - the rung of the ladder where the two-product
+// form sits, with rows of its own.
+void check_carrier() {
+	// decide_form: only with the grant, the option, rows beyond the fused form's policy and a launch that takes two products; it changes nothing else
+	for (const FormFacts& x0 : all_facts()) for (const uint32_t cc : {0u, FUSED_MAX_CHUNKS, FUSED_MAX_CHUNKS + 1}) for (int oc = 0; oc < 2; ++oc) for (int gc = 0; gc < 2; ++gc) for (int gt = 0; gt < 2; ++gt)
+	for (int gp = 0; gp < 2; ++gp) {
+		FormFacts x = x0; x.carrier_chunks = cc; x.row_chunks = cc; x.opt_carrier = oc;
+		FormGrant g; g.two = gt != 0; g.carrier = gc != 0; g.prefix = gp != 0;
+		const LaunchForm lf = decide_form(x, g);
+		FormGrant g0 = g; g0.carrier = false;
+		const LaunchForm base = decide_form(x, g0);
+		++g_cases;
+		CHECK(same(lf, base) && lf.prefix == base.prefix, "the carrier grant changed the form");
+		CHECK(!base.carrier, "a carrier launch without its grant");
+		CHECK(lf.carrier == (gc && oc != 0 && cc > FUSED_MAX_CHUNKS && lf.two), "carrier: grant %d option %d chunks %u two %d", gc, oc, cc, (int)lf.two);
+		CHECK(!lf.carrier || (lf.two && !lf.three && !lf.fused && !lf.two_pass && x.sorted_u), "a carrier launch that is no two-product launch of the sorted walk");
+	}
+	// the ladder: a carrier launch whose list overflowed is redone with three products, and the call's two-product launches end - as the H form's;
+	// a prefix launch on carrier rows is redone over whole rows on the same rows
+	FormGrant all{true, true, true, false}; all.carrier = true;
+	LaunchForm two; two.unphased = true; two.two = true; two.carrier = true;
+	{ const FormGrant g = step_down(two, all); CHECK(g.fused && g.three && !g.two && !g.carrier, "below a carrier launch: three products"); }
+	{ CallForms c; c.gave_up(two, all, true, false); CHECK(c.fused && c.three && !c.two && c.prefix, "a carrier launch's list overflowed: no more two-product launches"); CHECK(!c.grant(true, true, false, true).carrier && !c.grant(true, true, false, true).two, "... and none on carrier rows"); }
+	{ CallForms c; c.gave_up(two, all, false, false); CHECK(c.two && c.grant(true, true, false, true).carrier, "a carrier launch went well"); }
+	{ LaunchForm lf = two; lf.prefix = true; FormGrant wp = all; wp.prefix = true; const FormGrant g = step_down(lf, wp); CHECK(!g.prefix && g.two && g.carrier, "below a carrier prefix launch: whole rows, same operand");
+	  CallForms c; c.gave_up(lf, wp, true, false); CHECK(c.two && !c.prefix, "a carrier prefix launch's list overflowed: the stops go"); }
+	CHECK(!CallForms().grant(true, false, false, true).carrier && !CallForms().grant(true, true).carrier && CallForms().grant(true, true, false, true).carrier, "carrier grants follow the two-product grant");
+	g_cases += 6;
+	// the row operand of a call (carrier_operand): the option, rows beyond the fused form's, and carrier rows for every row in front of the cut - rows that
+	// could not be allocated (have 0 < need) leave the H plane, and a call with nothing in front of its cut asks for none
+	// (the answers are written out, not restated: option, chunks of a row, rows held, rows needed -> carrier plane?)
+	static const struct { long long opt; uint32_t chunks, have, need; bool carrier; const char* what; } CASES[] = {
+		{1, 977, 18304, 18304, true,  "the headline: every row in front of the cut has its carrier row"},
+		{1, 977, 50000, 18304, true,  "rows left by an earlier call with a later cut"},
+		{1, 129, 128, 128, true,      "the shortest rows that take the form"},
+		{1, 977, 0, 18304, false,     "an allocation that failed: the H plane"},
+		{1, 977, 12544, 18304, false, "rows for an earlier cut only: the H plane"},
+		{1, 977, 18304, 0, false,     "a shard with no row in front of the cut asks for none"},
+		{1, 977, 0, 0, false,         "nothing held, nothing needed"},
+		{0, 977, 18304, 18304, false, "option carrier = 0"},
+		{1, 128, 18304, 18304, false, "rows of 128 chunks keep the H plane"},
+		{1, 40, 18304, 18304, false,  "rows of 40 chunks keep the H plane"},
+		{1, 1, 128, 128, false,       "rows of one chunk keep the H plane"},
+	};
+	for (const auto& k : CASES) { ++g_cases; CHECK(carrier_operand(k.opt, k.chunks, k.have, k.need) == k.carrier, "carrier_operand(%lld, %u, %u, %u): %s", k.opt, k.chunks, k.have, k.need, k.what); }
+}
+
 }  // namespace
 
 int main() {
 	check_decide_form();
 	check_gave_up();
+	check_carrier();
 	printf("form-check: %ld cases, %d bad\n", g_cases, g_bad_checks);
 	return g_bad_checks ? 1 : 0;
 }

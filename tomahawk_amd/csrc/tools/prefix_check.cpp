@@ -2,13 +2,16 @@
 //   1. Soundness of the prefix screens (csrc/hip/ld_two_screen.h): every (prefix 3 x 3 genotype table, suffix 3 x 3 genotype table) of up to
 //      4 + 4 samples, at the cut-offs 0.1, 0.5, 0.8 and at cut-offs on, one ulp below and one ulp above the values at which the three-product
 //      screen's decision on the summed table turns.  Every pair screen3_keeps keeps on the summed table must be kept by
-//      screen3_prefix_keeps and by screen2_prefix_keeps on the prefix counts with the suffix margins.
+//      screen3_prefix_keeps and by screen2_prefix_keeps on the prefix counts with the suffix margins - and by screen2c_prefix_keeps, the
+//      two-product prefix screen of a launch whose row operand is the carrier plane (CH_pre, CQ_pre), which keeps no pair the H form's drops.
 //   2. The table builder with per-tile stops (csrc/hip/ld_count_table.h) against a naive restatement: every tile's units partition
 //      [0, stop) exactly, every split tile lies in the zeroed range, a unit that holds a stopped tile's whole count says so (UNIT_WHOLE) and
 //      no other does, and with no stops - or every stop at the row's end - the packed image is the one built without them.
 //   3. The planner (csrc/hip/ld_plan.h) on the headline's law: p evenly spread over (0.05, 0.5), 1,000,000 samples, 50,000 variants in
 //      allele-count order, margins and suffix margins at their expectation: the launches of the two-product walk, the stop of every tile
 //      of every launch, the mean contracted fraction per launch and overall (two-product pairs at 0.66 of a three-product pair's cost).
+//      Then the same walk with the carrier plane as the row operand of its two-product launches (PlanEnv::carrier): a second report, every line
+//      under the prefix "carrier form:", with the cut, the steps of the walk and the count work against the first report's.
 // usage: prefix_check [--no-planner]
 #include <cinttypes>
 #include <cmath>
@@ -30,7 +33,7 @@ int g_bad_checks = 0;
 
 // ---- 1. the screens ----------------------------------------------------------------------------------------------------------
 constexpr uint32_t MAX_PART = 4;
-uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_violations = 0;
+uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_kept2cp = 0, g_violations = 0;
 std::vector<std::vector<uint32_t>> g_tables;          // every 3 x 3 table of 0 .. MAX_PART samples: c[3 a + b]
 
 void each_table(uint32_t c[9], int cell, uint32_t left) {
@@ -49,6 +52,13 @@ void check_pair(const uint32_t* p, const uint32_t* x) {
 	// the facts the bound rests on: the suffix's S is >= 0 (unsigned), and its S + HH is at most min(dA', dB')
 	const uint32_t s_suf = x[7] + x[5] + 2 * x[8], hh_suf = x[4];
 	CHECK((double)(s_suf + hh_suf) <= prefix_slack(sx), "suffix S + HH = %u above min(dA', dB') = %g", s_suf + hh_suf, prefix_slack(sx));
+	// the carrier form's interval over the prefix: e_lo is tested at CQ_pre, e_hi at CH_pre + CQ_pre + min(qa_pre, qb_pre) + min(dA', dB') - the true S and
+	// T = S + HH of the summed table lie inside
+	{
+		const uint32_t ch_pre = p[4] + p[7], cq_pre = p[5] + p[8], qa_pre = m.qA - sx.qA, qb_pre = m.qB - sx.qB;
+		CHECK(cq_pre <= s && (double)(s + hh) <= (double)ch_pre + (double)cq_pre + (double)std::min(qa_pre, qb_pre) + prefix_slack(sx),
+		      "carrier prefix: S = %u, T = %u outside [%u, %u + %u + %u + %g]", s, s + hh, cq_pre, ch_pre, cq_pre, std::min(qa_pre, qb_pre), prefix_slack(sx));
+	}
 	double cuts[3 + 6]; int n_cuts = 3;
 	cuts[0] = 0.1; cuts[1] = 0.5; cuts[2] = 0.8;
 	const double da = m.hA + 2.0 * m.qA, ra = two_n - da, db = m.hB + 2.0 * m.qB, rb = two_n - db, denom = da * ra * db * rb;
@@ -69,7 +79,14 @@ void check_pair(const uint32_t* p, const uint32_t* x) {
 			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: kept by three products on the whole rows, prefix three %d, prefix two %d",
 			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3p, (int)k2p);
 		}
-		++g_tests; g_kept3 += k3; g_kept3p += k3p; g_kept2p += k2p;
+		// the carrier form over the prefix: CH_pre = HH_pre + QH_pre, CQ_pre = HQ_pre + QQ_pre - between the whole rows' three products and the H form's prefix screen
+		const bool k2cp = screen2c_prefix_keeps(m, sx, p[4] + p[7], p[5] + p[8], two_n, cut);
+		if ((k3 && !k2cp) || (k2cp && !k2p)) {
+			++g_violations;
+			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products on the whole rows %d, carrier prefix %d, H prefix %d",
+			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3, (int)k2cp, (int)k2p);
+		}
+		++g_tests; g_kept3 += k3; g_kept3p += k3p; g_kept2p += k2p; g_kept2cp += k2cp;
 	}
 }
 int check_screens() {
@@ -87,6 +104,7 @@ int check_screens() {
 			const double cut = r2 * (1.0 - 1e-6);
 			CHECK(screen3_prefix_keeps(m, none, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut) == screen3_keeps(m, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut), "empty suffix, three");
 			CHECK(screen2_prefix_keeps(m, none, c[4], c[5], 2.0 * n, cut) == screen2_keeps(m, c[4], c[5], 2.0 * n, cut), "empty suffix, two");
+			CHECK(screen2c_prefix_keeps(m, none, c[4] + c[7], c[5] + c[8], 2.0 * n, cut) == screen2c_keeps(m, c[4] + c[7], c[5] + c[8], 2.0 * n, cut), "empty suffix, carrier");
 		}
 	}
 	return g_bad_checks != before;
@@ -160,7 +178,11 @@ int check_tables(int& n_cases) {
 }
 
 // ---- 3. the planner on the headline's law --------------------------------------------------------------------------------------
-int play_planner() {
+// carrier: the second report - the walk's two-product launches contract the carrier plane.  Its lines carry a prefix of their own and the word
+// "step" where the first report says "launch" (tests/test_prefix_cpu.py reads the first report by its lines).  -> the count work with stops, in
+// three-product tile chunks; *two_end: the cut.
+double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t h_two_end = 0) {
+	const char* tag = carrier ? "carrier form: " : "planner: ";
 	const uint32_t M = 50000, N = 1000000, nchunks = (N + 1023) / 1024;
 	const double minR2 = 0.1, cut = minR2 * (1.0 - 1e-6), two_cost = 0.66;
 	std::vector<uint32_t> het(M), hom(M), suffix((size_t)2 * M * PREFIX_GRID);
@@ -173,13 +195,14 @@ int play_planner() {
 			suffix[(size_t)(2 * v + 1) * PREFIX_GRID + g] = (uint32_t)std::llround(hom[v] * behind);
 		}
 	}
-	PlanEnv env; env.n_samples = N; env.Pmax = 2; env.nchunks = nchunks; env.minR2 = minR2; env.phased_math = false; env.het = het.data(); env.hom = hom.data();
+	PlanEnv env; env.n_samples = N; env.Pmax = 2; env.nchunks = nchunks; env.minR2 = minR2; env.phased_math = false; env.het = het.data(); env.hom = hom.data(); env.carrier = carrier;
 	const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
 	RegionPlan plan;
 	plan_region(env, g, plan);
-	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = 0.95;
-	printf("planner: %u variants x %u samples, r2 >= %g, rows of %u chunks, grid step %u chunks; two-product cut at sorted row %u (p = %.3f); %zu launches\n",
-	       M, N, minR2, nchunks, prefix_step(nchunks), plan.two_end, 0.05 + 0.45 * plan.two_end / M, plan.mine.size());
+	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = 0.95; pe.carrier = carrier;
+	*two_end = plan.two_end;
+	printf("%s%u variants x %u samples, r2 >= %g, rows of %u chunks, grid step %u chunks; two-product cut at sorted row %u (p = %.3f); %zu %s\n",
+	       tag, M, N, minR2, nchunks, prefix_step(nchunks), plan.two_end, 0.05 + 0.45 * plan.two_end / M, plan.mine.size(), carrier ? "steps" : "launches");
 	CountSettings cs;
 	double work_full = 0, work_done = 0, sum2_full = 0, sum2_done = 0, sum3_full = 0, sum3_done = 0, host_ms = 0;
 	uint64_t n_tiles = 0;
@@ -200,7 +223,8 @@ int play_planner() {
 		for (const uint32_t s : stops) { done += s; lo = std::min(lo, s); hi = std::max(hi, s); }
 		const uint64_t full = (uint64_t)tb.n_tiles() * nchunks;
 		n_tiles += tb.n_tiles();
-		printf("  launch %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n", i, two ? "two  " : "three", t.rowA0, t.nA, t.rowB0, t.nB,
+		printf(carrier ? "  carrier form: step %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n" :
+		       "  launch %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n", i, two ? "two  " : "three", t.rowA0, t.nA, t.rowB0, t.nB,
 		       tb.n_tiles(), lo, hi, full ? (double)done / (double)full : 0.0);
 		// (a two-product tile holds 128 x 64 variant pairs, a three-product tile 64 x 64: per tile and chunk twice the pairs at two_cost each)
 		const double w = two ? 2.0 * two_cost : 1.0;
@@ -208,12 +232,17 @@ int play_planner() {
 		(two ? sum2_full : sum3_full) += (double)full; (two ? sum2_done : sum3_done) += (double)done;
 	}
 	const double all_full = sum2_full * 2.0 * two_cost + sum3_full, all_pairs = 2.0 * sum2_full + sum3_full;
-	printf("planner: two-product launches %.1f %% of the pairs (%.1f %% of today's count work), mean fraction of the row contracted %.4f; three-product launches %.1f %% of the pairs (%.1f %%), mean fraction %.4f\n",
+	printf(carrier ? "carrier form: two-product steps %.1f %% of the pairs (%.1f %% of the whole rows' count work), mean fraction of the row contracted %.4f; three-product steps %.1f %% of the pairs (%.1f %%), mean fraction %.4f\n" :
+	       "planner: two-product launches %.1f %% of the pairs (%.1f %% of today's count work), mean fraction of the row contracted %.4f; three-product launches %.1f %% of the pairs (%.1f %%), mean fraction %.4f\n",
 	       100.0 * 2.0 * sum2_full / all_pairs, 100.0 * sum2_full * 2.0 * two_cost / all_full, sum2_full ? sum2_done / sum2_full : 0.0,
 	       100.0 * sum3_full / all_pairs, 100.0 * sum3_full / all_full, sum3_full ? sum3_done / sum3_full : 0.0);
-	printf("planner: count work %.4f of today's (two-product pairs at %.2f of a three-product pair); %" PRIu64 " tiles, the stops cost %.1f ms of host time a call on this machine\n",
-	       work_full ? work_done / work_full : 0.0, two_cost, n_tiles, host_ms);
-	return 0;
+	if (!carrier)
+		printf("planner: count work %.4f of today's (two-product pairs at %.2f of a three-product pair); %" PRIu64 " tiles, the stops cost %.1f ms of host time a call on this machine\n",
+		       work_full ? work_done / work_full : 0.0, two_cost, n_tiles, host_ms);
+	else
+		printf("carrier form: rows in front of the cut %u (H plane: %u); count work with stops %.4f of the H plane's with stops (two-product pairs at %.2f of a three-product pair); %" PRIu64 " tiles\n",
+		       plan.two_end, h_two_end, h_work > 0 ? work_done / h_work : 0.0, two_cost, n_tiles);
+	return work_done;
 }
 
 }  // namespace
@@ -227,7 +256,13 @@ int main(int argc, char** argv) {
 	int n_cases = 0;
 	const int bad_tables = check_tables(n_cases);
 	printf("prefix-check: table builder with stops: %d cases, %d bad\n", n_cases, bad_tables);
-	if (planner) play_planner();
+	printf("prefix-check: the two-product prefix screen on the carrier plane keeps %" PRIu64 " (three products on the whole rows %" PRIu64 " <= it <= the H plane's %" PRIu64 ")\n", g_kept2cp, g_kept3, g_kept2p);
+	if (planner) {
+		uint32_t h_end = 0, c_end = 0;
+		const double h_work = play_planner(false, &h_end);
+		const double c_work = play_planner(true, &c_end, h_work, h_end);
+		CHECK(c_end > h_end && c_work < h_work, "carrier form: cut %u against %u, work %g against %g", c_end, h_end, c_work, h_work);
+	}
 	printf("prefix-check: %s\n", (bad_screen || bad_tables || g_bad_checks) ? "FAILED" : "ok");
 	return (bad_screen || bad_tables || g_bad_checks) ? 1 : 0;
 }

@@ -1,7 +1,9 @@
 // `make two-check`: the host side of the two-product form, on the CPU under AddressSanitizer and UBSan.
 //   1. The screen (csrc/hip/ld_two_screen.h) over every 3 x 3 genotype table of up to MAX_N samples, at fixed cut-offs and at cut-offs on, one
 //      ulp below and one ulp above the values at which the three-product screen's own decision turns: the true S lies in [S_lo, S_hi], and
-//      the two-product screen keeps every pair the three-product screen keeps.
+//      the two-product screen keeps every pair the three-product screen keeps.  The carrier form (the row variant's H | Q as the row operand:
+//      CH = HH + QH, CQ = HQ + QQ): the true S and T = S + HH lie in [CQ, .] and [., CH + CQ + min(qA, qB)], and
+//      kept(three) <= kept(carrier) <= kept(H) pair by pair.
 //   2. The work table of a launch whose row axis has one plane row per variant and whose column axis two (build_count_table with PA = 1,
 //      csrc/hip/ld_count_table.h): tiles of 128 row variants x 64 column variants against a naive restatement - a tile is wanted when one of
 //      its variant pairs is (diagonal super-tiles: a pair above the diagonal) - units that partition every tile's K range, and the recorded
@@ -29,13 +31,17 @@ int g_bad_checks = 0;
 // ---- 1. the screen ---------------------------------------------------------------------------------------------------------
 // c[3 a + b]: samples with genotype a (0 ref/ref, 1 het, 2 alt/alt) at the row variant and b at the column variant
 constexpr int MAX_N = 7;
-uint64_t g_tables = 0, g_kept3 = 0, g_kept2 = 0;
+uint64_t g_tables = 0, g_kept3 = 0, g_kept2 = 0, g_kept2c = 0;
 
 void check_table(const uint32_t c[9], uint32_t n) {
 	const ScreenMargins m{c[3] + c[4] + c[5], c[6] + c[7] + c[8], c[1] + c[4] + c[7], c[2] + c[5] + c[8]};
 	const uint32_t hh = c[4], hq = c[5], qh = c[7], qq = c[8], s = qh + hq + 2 * qq;
 	const double two_n = 2.0 * n;
 	CHECK((double)hq <= (double)s && (double)s <= (double)hq + screen2_slack(m), "S = %u outside [%u, %u + %g]", s, hq, hq, screen2_slack(m));
+	// the carrier form: e_lo is tested at S_lo = CQ, e_hi at S_hi + CH = CQ + min(qA, qB) + CH - the true S and T = S + HH lie inside, and the interval inside the H form's
+	const uint32_t ch = hh + qh, cq = hq + qq;
+	CHECK(cq <= s && (double)(s + hh) <= (double)ch + (double)cq + screen2c_slack(m), "carrier: S = %u, T = %u outside [%u, %u + %u + %g]", s, s + hh, cq, ch, cq, screen2c_slack(m));
+	CHECK(cq >= hq && (double)ch + (double)cq + screen2c_slack(m) <= (double)hh + (double)hq + screen2_slack(m), "carrier interval outside the H form's");
 	// the cut-offs at which the three-product screen's decision on this very table turns: e^2 / (da ra db rb) of its two test values
 	// (without eps they are the pair's own extreme r2 values), each with its neighbours, next to fixed ones
 	std::vector<double> cuts = {1e-5, 0.01, 0.1, 0.25, 0.5, 0.9, 1.0};
@@ -50,9 +56,10 @@ void check_table(const uint32_t c[9], uint32_t n) {
 	for (const double minR2 : cuts) {
 		if (minR2 > 1.0) continue;
 		const double cut = minR2 * (1.0 - 1e-6);
-		const bool k3 = screen3_keeps(m, hh, s, two_n, cut), k2 = screen2_keeps(m, hh, hq, two_n, cut);
+		const bool k3 = screen3_keeps(m, hh, s, two_n, cut), k2 = screen2_keeps(m, hh, hq, two_n, cut), k2c = screen2c_keeps(m, ch, cq, two_n, cut);
+		CHECK((!k3 || k2c) && (!k2c || k2), "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three %d, carrier %d, H %d", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2, (int)k3, (int)k2c, (int)k2);
 		CHECK(!k3 || k2, "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products keep it, two drop it", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2);
-		++g_tables; g_kept3 += k3; g_kept2 += k2;
+		++g_tables; g_kept3 += k3; g_kept2 += k2; g_kept2c += k2c;
 	}
 }
 void each_table(uint32_t c[9], int cell, uint32_t left, uint32_t n) {
@@ -72,6 +79,11 @@ int check_screen() {
 				const uint32_t s = hq + (uint32_t)((uint64_t)slack * k / 8);
 				const double cut = minR2 * (1.0 - 1e-6);
 				CHECK(!screen3_keeps(m, hh, s, 2.0 * n, cut) || screen2_keeps(m, hh, hq, 2.0 * n, cut), "n %u pa %g pb %g S %u at %g", n, pa, pb, s, minR2);
+				// the carrier form at the same margins: QH + QQ = k / 8 of qA split evenly, so CH = HH + QH, CQ = HQ + QQ and S = CQ + QH + QQ
+				const uint32_t q_part = (uint32_t)((uint64_t)m.qA * k / 8), qq = std::min(q_part / 2, std::min(m.qA, m.qB)), qh = q_part - qq;
+				const uint32_t sc = hq + qh + 2 * qq;
+				const bool k3c = screen3_keeps(m, hh, sc, 2.0 * n, cut), k2c = screen2c_keeps(m, hh + qh, hq + qq, 2.0 * n, cut), k2h = screen2_keeps(m, hh, hq, 2.0 * n, cut);
+				CHECK((!k3c || k2c) && (!k2c || k2h), "carrier: n %u pa %g pb %g S %u at %g: three %d, carrier %d, H %d", n, pa, pb, sc, minR2, (int)k3c, (int)k2c, (int)k2h);
 			}
 		}
 	return g_bad_checks != before;
@@ -194,5 +206,7 @@ int main(int argc, char** argv) {
 	const int bad_screen = check_screen(); ++n; bad += bad_screen;
 	fprintf(record ? stderr : stdout, "two-check: %d cases, %d bad; screen: %" PRIu64 " (table, cut-off) tests, three products kept %" PRIu64 ", two %" PRIu64 "\n",
 	        n, bad, g_tables, g_kept3, g_kept2);
+	fprintf(record ? stderr : stdout, "two-check: carrier screen kept %" PRIu64 " of the same tests (three products %" PRIu64 " <= carrier <= H plane %" PRIu64 ")\n", g_kept2c, g_kept3, g_kept2);
+	if (!(g_kept3 <= g_kept2c && g_kept2c <= g_kept2)) return 1;
 	return bad != 0;
 }
