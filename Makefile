@@ -135,7 +135,8 @@ two-check:
 # The prefix contraction's host side (csrc/tools/prefix_check.cpp): its screens (csrc/hip/ld_two_screen.h) over every pair of a small prefix and a
 # small suffix genotype table, the work table with per-tile stops (csrc/hip/ld_count_table.h) against a naive restatement and against the table
 # built without stops, and the planner's stops (csrc/hip/ld_plan.h) on the headline's frequency law - once with the H plane and once with the
-# carrier plane as the two-product launches' row operand: host code only, under AddressSanitizer and UBSan
+# carrier plane as the two-product launches' row operand; the grid of 128 stops against a naive restatement for rows of 1 .. 2,000 chunks, the
+# screens at every fine stop, and the planner at four settings of grid and margin: host code only, under AddressSanitizer and UBSan
 prefix-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/prefix_check.cpp -o build/prefix_check

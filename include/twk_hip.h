@@ -810,7 +810,9 @@ int twk_hip_fisher_exact(twk_hip_ctx* ctx, const int32_t* tables, uint64_t n, do
  * closest relative is the compile-time SLAVE_DEBUG_MODE / SIMD_AVAILABLE switches, lib/ld/ld_engine.h:20-24).
  * The keys, their defaults, ranges and meaning are ONE table in the engine (TWK_HIP_OPTIONS, csrc/hip/twk_hip.hip), readable through
  * twk_hip_option_describe() below and printed as the table of INTEGRATION.md 1 (tests/test_docs_consistency.py keeps the document in
- * step with it).  In short: "fused", "three" pick the form of the contraction; "lists", "list_max", "probe", "probe_zone",
+ * step with it).  In short: "fused", "three", "two", "carrier", "prefix" pick the form of the contraction
+ * ("prefix_margin" and "prefix_sigma" are the two questions the prefix contraction's planner asks for a tile's stop on its 128-point grid,
+ * "prefix_stop" plus "prefix_substop" a test hook that puts every tile's stop on one point of it: DESIGN 3.1c); "lists", "list_max", "probe", "probe_zone",
  * "probe_lds" the carrier-list passes for rare variants; "band_*" the launches of fused runs; "patch_rows" / "patch_cols" / "seg" /
  * "xcd_queues" / "skip_pad" / "count_min_chunks" / "cand_chunk" the count kernel's work order; "fisher_*" Fisher's test;
  * "async_delivery", "deliver_buffers" the engine's delivery thread; "record_cap", "deliver_fail_*_at" are test hooks; "timeline" a log.

@@ -350,46 +350,61 @@ inline uint32_t plan_two_end(const PlanEnv& e, const PlanGeom& g) {
 // ---- the prefix contraction's stops ---------------------------------------------------------------------------
 // A tile of a two- or three-product launch of the two-product walk is contracted over the chunks [0, stop) only; the screen bounds what it did
 // not read by the rows' suffix margins (ld_two_screen.h).  The stop of a tile: for a small fixed set of its variant pairs - the four corners
-// and the middle - the smallest grid point at which the pair, at its independence expectation and with the square root of the screen's bound
-// shrunk to `margin` of it, is dropped; the largest of those, plus one grid step.  Expected prefix counts come from the real prefix margins
-// and the suffix term from the real suffix margins, so a file whose carriers crowd its last samples gets later stops by itself.  A guide
-// and no guarantee: the launch's sample decides whether the stops are taken, and what the wider screen keeps is recounted.
+// and the middle - the smallest point of the fine grid (ld_two_screen.h prefix_stop_chunks) at which the pair, at its independence
+// expectation, is dropped by either of two questions: the screen with the square root of its bound shrunk to `margin` of it
+// (prefix_expected_keeps), or the screen itself with the expected counts moved outwards by `sigma` standard deviations of theirs
+// (prefix_sigma_keeps; sigma 0: the first question alone).  The largest of those, plus one fine step.  Expected prefix counts come from the
+// real prefix margins and the suffix term from the real suffix margins, so a file whose carriers crowd its last samples gets later stops by
+// itself.  A guide and no guarantee: the launch's sample decides whether the stops are taken, and what the wider screen keeps is recounted.
 struct PrefixEnv {
 	const uint32_t* het = nullptr; const uint32_t* hom = nullptr;      // per position of the sorted set
 	const uint32_t* suffix = nullptr;                                  // [2 x position + plane][PREFIX_GRID]: suffix popcounts of the H and Q rows
 	uint32_t n_variants = 0, n_samples = 0, nchunks = 0;
-	double cut = 0, margin = 0.95;
-	uint32_t fixed_grid = 0;                                           // test hook "prefix_stop": this grid index for every tile (0: the planner's)
+	double cut = 0, margin = 0.95, sigma = 6.0;
+	uint32_t fixed_grid = 0;                                           // test hooks "prefix_stop", "prefix_substop": this fine index for every tile (0: the planner's)
 	bool carrier = false;                                              // a two-product launch's row operand is the carrier plane (PlanEnv::carrier)
-	uint64_t samples_before(uint32_t g) const { return std::min<uint64_t>((uint64_t)prefix_stop_chunks(g, nchunks) * 32u * 32u, n_samples); }
-	bool dropped(bool two, uint32_t vA, uint32_t vB, uint32_t g) const {
-		if (g >= PREFIX_GRID) return true;       // (whole rows: the screen itself decides)
+	uint64_t samples_before(uint32_t f) const { return std::min<uint64_t>((uint64_t)prefix_stop_chunks(f, nchunks) * 32u * 32u, n_samples); }
+	bool dropped(bool two, uint32_t vA, uint32_t vB, uint32_t f) const {
+		if (f >= PREFIX_GRID) return true;       // (whole rows: the screen itself decides)
 		const ScreenMargins m{het[vA], hom[vA], het[vB], hom[vB]};
-		const SuffixMargins x{suffix[(size_t)(2 * vA) * PREFIX_GRID + g], suffix[(size_t)(2 * vA + 1) * PREFIX_GRID + g],
-		                      suffix[(size_t)(2 * vB) * PREFIX_GRID + g], suffix[(size_t)(2 * vB + 1) * PREFIX_GRID + g]};
-		if (two && carrier) return !prefix_expected_keeps_carrier(m, x, (double)samples_before(g), 2.0 * (double)n_samples, cut, margin);
-		return !prefix_expected_keeps(m, x, two, (double)samples_before(g), 2.0 * (double)n_samples, cut, margin);
+		const SuffixMargins x{suffix[(size_t)(2 * vA) * PREFIX_GRID + f], suffix[(size_t)(2 * vA + 1) * PREFIX_GRID + f],
+		                      suffix[(size_t)(2 * vB) * PREFIX_GRID + f], suffix[(size_t)(2 * vB + 1) * PREFIX_GRID + f]};
+		const double n_pre = (double)samples_before(f), two_n = 2.0 * (double)n_samples;
+		if (!(two && carrier ? prefix_expected_keeps_carrier(m, x, n_pre, two_n, cut, margin) : prefix_expected_keeps(m, x, two, n_pre, two_n, cut, margin))) return true;
+		return sigma > 0 && !prefix_sigma_keeps(m, x, two, two && carrier, n_pre, two_n, cut, sigma);
 	}
-	// smallest grid index in [1, PREFIX_GRID] at which the pair is dropped, walked from `hint` (the answer of a neighbouring tile: one or two
-	// questions instead of a search - both inequalities move one way along the row)
+	// smallest fine index in [1, PREFIX_GRID] at which the pair is dropped, walked from `hint` (the answer of a neighbouring tile: two or
+	// three questions instead of a search - both inequalities move one way along the row)
 	uint32_t pair_need(bool two, uint32_t vA, uint32_t vB, uint32_t hint) const {
-		uint32_t g = std::min<uint32_t>(std::max<uint32_t>(hint, 1), PREFIX_GRID);
-		while (g > 1 && dropped(two, vA, vB, g - 1)) --g;
-		while (g < PREFIX_GRID && !dropped(two, vA, vB, g)) ++g;
-		return g;
+		uint32_t f = std::min<uint32_t>(std::max<uint32_t>(hint, 1), PREFIX_GRID);
+		while (f > 1 && dropped(two, vA, vB, f - 1)) --f;
+		while (f < PREFIX_GRID && !dropped(two, vA, vB, f)) ++f;
+		return f;
 	}
 };
-// Grid index of the stop of the tile over row variants [a_lo, a_hi] x column variants [b_lo, b_hi] (inclusive; a tile that reaches the
+// Fine index of the stop of the tile over row variants [a_lo, a_hi] x column variants [b_lo, b_hi] (inclusive; a tile that reaches the
 // diagonal holds pairs of neighbours in allele-count order and is few: whole rows).  hint[5]: the caller's, carried from tile to tile.
+// Only the largest of the five answers is used, so only one pair is walked: the one whose hint is the largest.  Each of the others is asked once,
+// at that answer - dropped there, its own answer is no larger - and walked on from it only where it is not.  Six or seven questions a tile for
+// the ten of five walks, which is what pays for the finer grid and the second question on the host.
 inline uint32_t plan_prefix_tile_grid(const PrefixEnv& e, bool two, uint32_t a_lo, uint32_t a_hi, uint32_t b_lo, uint32_t b_hi, uint32_t* hint) {
 	if (e.fixed_grid) return std::min<uint32_t>(e.fixed_grid, PREFIX_GRID);
 	if (a_hi >= e.n_variants) a_hi = e.n_variants - 1;
 	if (b_hi >= e.n_variants) b_hi = e.n_variants - 1;
 	if (a_lo > a_hi || b_lo > b_hi || b_lo <= a_hi) return PREFIX_GRID;
 	const uint32_t pa[5] = {a_lo, a_lo, a_hi, a_hi, a_lo + (a_hi - a_lo) / 2}, pb[5] = {b_lo, b_hi, b_lo, b_hi, b_lo + (b_hi - b_lo) / 2};
-	uint32_t need = 1;
-	for (int k = 0; k < 5; ++k) { hint[k] = e.pair_need(two, pa[k], pb[k], hint[k]); need = std::max(need, hint[k]); }
-	return std::min<uint32_t>(need + 1, PREFIX_GRID);
+	int first = 0;
+	for (int k = 1; k < 5; ++k) if (hint[k] > hint[first]) first = k;
+	uint32_t need = hint[first] = e.pair_need(two, pa[first], pb[first], hint[first]);
+	for (int k = 0; k < 5; ++k) {
+		if (k == first) continue;
+		if (e.dropped(two, pa[k], pb[k], need)) hint[k] = std::min(hint[k], need);      // (an upper bound of its answer: it only picks the pair walked next time)
+		else need = hint[k] = e.pair_need(two, pa[k], pb[k], need);
+	}
+	// (one fine step of chunks, not of indices: on short rows fine points coincide where a sub-step is clipped)
+	uint32_t f = std::min<uint32_t>(need + 1, PREFIX_GRID);
+	while (f < PREFIX_GRID && prefix_stop_chunks(f, e.nchunks) == prefix_stop_chunks(need, e.nchunks)) ++f;
+	return f;
 }
 
 // The stops of a launch's tiles as build_count_table (ld_count_table.h) asks for them: called with a tile's (tile row << 16 | tile column) in

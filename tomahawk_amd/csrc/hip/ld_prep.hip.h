@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "ld_two_screen.h"
 
 namespace twk {
 
@@ -99,34 +100,54 @@ __global__ void k_row_popcount(const uint32_t* __restrict__ rows, uint32_t W, ui
 	if (lane == 0) out[r] = c;
 }
 
-// Suffix popcounts of every row on a grid of 32 points (the prefix contraction's margins, ld_two_screen.h): out[r * 32 + g] = popcount of the
-// words [g * seg_words, W) of row r, zero where the grid point lies behind the row's end.  seg_words is a multiple of 4 (a grid step is whole
-// K chunks of 32 words).  One wave per row, one pass over the planes: the wave sums a segment at a time, lane g keeps segment g's count, and
-// the suffix sums are a 32-term loop per lane at the end.
-__global__ void k_row_suffix_popcount(const uint32_t* __restrict__ rows, uint32_t W, uint32_t n_rows, uint32_t seg_words,
-                                      uint32_t* __restrict__ out) {
-	const uint32_t r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-	if (r >= n_rows) return;
-	const int lane = threadIdx.x & 63;
-	const uint4* p = reinterpret_cast<const uint4*>(rows + (size_t)r * W);
-	const uint32_t W4 = W / 4, seg4 = seg_words / 4;
-	uint32_t mine = 0;                      // lane g < 32: the count of segment g
-	for (uint32_t g = 0; g < 32; ++g) {
-		const uint32_t k0 = g * seg4, k1 = k0 + seg4 < W4 ? k0 + seg4 : W4;
-		uint32_t c = 0;
-		for (uint32_t k = k0 + lane; k < k1; k += 64) {
-			const uint4 x = p[k];
-			c += __builtin_popcount(x.x) + __builtin_popcount(x.y) + __builtin_popcount(x.z) + __builtin_popcount(x.w);
+// Suffix popcounts of every row on the fine grid of stops (the prefix contraction's margins, ld_two_screen.h prefix_stop_chunks): out[r *
+// PREFIX_GRID + f] = popcount of the chunks [stop(f), W / 32) of row r, zero where the grid point lies at the row's end.  W is whole K chunks of
+// 32 words.  One wave per row, one pass over the planes: eight lanes read a chunk (8 x 16 bytes), so a wave reads eight chunks at a time, four
+// times over before it counts any; the eight lanes add up their chunk and one of them adds the sum to the count of the segment [stop(f),
+// stop(f + 1)) the chunk lies in - segments are of unequal length and may be empty, and a lane finds its chunk's by walking f up as its
+// chunks go up.  The 128 segment counts of a wave live in LDS; the suffix sums are a 128-term loop per lane at the end, two grid points a lane.
+__global__ __launch_bounds__(256)
+void k_row_suffix_popcount(const uint32_t* __restrict__ rows, uint32_t W, uint32_t n_rows, uint32_t* __restrict__ out) {
+	static_assert(PREFIX_GRID == 128, "two grid points a lane");
+	constexpr uint32_t AHEAD = 4;
+	__shared__ uint32_t seg_all[4][PREFIX_GRID];
+	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = blockIdx.x * 4 + wave;
+	uint32_t* seg = seg_all[wave];
+	seg[lane] = 0; seg[lane + 64] = 0;
+	__syncthreads();
+	if (r < n_rows) {
+		const uint4* p = reinterpret_cast<const uint4*>(rows + (size_t)r * W);
+		const uint32_t nchunks = W / 32, part = lane & 7;
+		uint32_t f = 0, next = prefix_stop_chunks(1, nchunks);      // the lane's chunk lies in segment f, which ends at `next`
+		for (uint32_t c0 = lane >> 3; c0 < nchunks; c0 += 8 * AHEAD) {
+			uint4 x[AHEAD];
+#pragma unroll
+			for (uint32_t u = 0; u < AHEAD; ++u) {
+				const uint32_t c = c0 + 8 * u;
+				x[u] = c < nchunks ? p[(size_t)c * 8 + part] : make_uint4(0, 0, 0, 0);
+			}
+#pragma unroll
+			for (uint32_t u = 0; u < AHEAD; ++u) {
+				const uint32_t c = c0 + 8 * u;
+				if (c >= nchunks) break;      // (the eight lanes of a chunk leave together)
+				while (f + 1 < PREFIX_GRID && next <= c) { ++f; next = prefix_stop_chunks(f + 1, nchunks); }
+				uint32_t n = __builtin_popcount(x[u].x) + __builtin_popcount(x[u].y) + __builtin_popcount(x[u].z) + __builtin_popcount(x[u].w);
+				n += __shfl_xor(n, 1); n += __shfl_xor(n, 2); n += __shfl_xor(n, 4);
+				if (part == 0 && n) atomicAdd(&seg[f], n);
+			}
 		}
-		for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-		if (lane == (int)g) mine = c;
 	}
-	uint32_t suffix = 0;
-	for (int g = 31; g >= 0; --g) {
-		const uint32_t s = __shfl(mine, g);
-		if (g >= lane) suffix += s;
+	__syncthreads();
+	if (r < n_rows) {
+		uint32_t lo = 0, hi = 0;              // suffix sums at the grid points lane and lane + 64
+		for (uint32_t f = PREFIX_GRID; f-- > 0;) {
+			const uint32_t s = seg[f];
+			if (f >= lane) lo += s;
+			if (f >= lane + 64) hi += s;
+		}
+		out[(size_t)r * PREFIX_GRID + lane] = lo;
+		out[(size_t)r * PREFIX_GRID + lane + 64] = hi;
 	}
-	if (lane < 32) out[(size_t)r * 32 + lane] = suffix;
 }
 
 // Carrier rows of the first n variants of an unphased plane set (the two-product form's row operand, ld_two_screen.h): out[v][k] = H | Q of

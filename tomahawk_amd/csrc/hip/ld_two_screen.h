@@ -119,13 +119,50 @@ TWK_SCREEN_FN bool prefix_expected_keeps_carrier(const ScreenMargins& m, const S
 	return screen_keeps_between(m, ch, cq, cq + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut, margin * margin);
 }
 
-// The grid of stops: PREFIX_GRID points along a row of nchunks K chunks, prefix_step chunks apart; grid index g stands for the stop
-// min(g * step, nchunks), and PREFIX_GRID (or any stop of nchunks) for the whole row.
-constexpr uint32_t PREFIX_GRID = 32;
-TWK_SCREEN_FN uint32_t prefix_step(uint32_t nchunks) { return (nchunks + PREFIX_GRID - 1) / PREFIX_GRID; }
-TWK_SCREEN_FN uint32_t prefix_stop_chunks(uint32_t g, uint32_t nchunks) {
-	const unsigned long long s = (unsigned long long)g * prefix_step(nchunks);
-	return g >= PREFIX_GRID || s >= nchunks ? nchunks : (uint32_t)s;
+// The planner's second question for a stop (ld_plan.h PrefixEnv::dropped): the screen's own bound (bound_factor 1), asked at the expected
+// prefix counts moved outwards by z standard deviations - s_lo down, s_hi + hh up.  The standard deviations are those of the prefix sums of
+// n_pre independent samples whose (gA, gB) follow the prefix margins: P(gA = 1) = ha / n_pre, P(gA = 2) = qa / n_pre, likewise gB.  Per sample
+//     S = QH + HQ + 2 QQ     mean a2 b1 + a1 b2 + 2 a2 b2,              second moment a2 b1 + a1 b2 + 4 a2 b2
+//     T = S + HH             mean a1 b1 + a1 b2 + a2 b1 + 2 a2 b2,      second moment ... + 4 a2 b2
+//     HQ, HH + HQ, CQ, CH + CQ     indicators: of (gA = 1, gB = 2), (gA = 1, gB >= 1), (gA >= 1, gB = 2), (gA >= 1, gB >= 1)
+// and a sum's variance is n_pre (second moment - mean^2).  The real counts are sums with both margins fixed, whose spread is smaller, so z
+// standard deviations of these are at least z of the real ones.  Where the 5 % of sqrt(bound) of prefix_expected_keeps is many standard
+// deviations (long rows) this question drops a pair earlier; where it is few (rows of ~ 140 k samples) the other one does.
+TWK_SCREEN_FN bool prefix_sigma_keeps(const ScreenMargins& m, const SuffixMargins& x, bool two, bool carrier, double n_pre, double two_n, double cut, double z) {
+	if (n_pre <= 0) return true;
+	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
+	const double a1 = ha / n_pre, a2 = qa / n_pre, b1 = hb / n_pre, b2 = qb / n_pre;
+	double mu_lo, m2_lo, mu_hi, m2_hi, hh, fixed;       // s_lo's sum; (s_hi + hh)'s sum; the part of it passed as hh; what the screen adds to s_hi besides
+	if (!two) {
+		mu_lo = a2 * b1 + a1 * b2 + 2.0 * a2 * b2; m2_lo = mu_lo + 2.0 * a2 * b2;
+		mu_hi = mu_lo + a1 * b1; m2_hi = m2_lo + a1 * b1;
+		hh = a1 * b1; fixed = prefix_slack(x);
+	} else if (!carrier) {
+		mu_lo = m2_lo = a1 * b2; mu_hi = m2_hi = a1 * (b1 + b2);
+		hh = a1 * b1; fixed = qa + (qa < qb ? qa : qb) + prefix_slack(x);
+	} else {
+		mu_lo = m2_lo = (a1 + a2) * b2; mu_hi = m2_hi = (a1 + a2) * (b1 + b2);
+		hh = (a1 + a2) * b1; fixed = (qa < qb ? qa : qb) + prefix_slack(x);
+	}
+	const double v_lo = n_pre * (m2_lo - mu_lo * mu_lo), v_hi = n_pre * (m2_hi - mu_hi * mu_hi);
+	const double sd_lo = v_lo > 0 ? __builtin_sqrt(v_lo) : 0.0, sd_hi = v_hi > 0 ? __builtin_sqrt(v_hi) : 0.0;
+	const double s_lo = n_pre * mu_lo - z * sd_lo, s_hi = n_pre * (mu_hi - hh) + fixed + z * sd_hi;
+	return screen_keeps_between(m, n_pre * hh, s_lo, s_hi, two_n, cut);
+}
+
+// The grid of stops: PREFIX_COARSE coarse points along a row of nchunks K chunks, prefix_step chunks apart (the option "prefix_stop" counts in
+// these), and every coarse interval divided into PREFIX_SUB sub-steps of prefix_substep chunks, clipped at the next coarse point: fine index
+// f = PREFIX_SUB g + s stands for the stop min(g step + min(s substep, step), nchunks), and PREFIX_GRID (or any stop of nchunks) for the whole
+// row.  The points are not equally spaced (137 chunks: 0, 2, 4, 5, 7, ..: step 5, sub-step 2) and may coincide; they never decrease, and every
+// coarse point is one of them.  Stated here once: the screens, the planner, the suffix table (ld_prep.hip.h) and `make prefix-check` all ask this.
+constexpr uint32_t PREFIX_COARSE = 32, PREFIX_SUB = 4, PREFIX_GRID = PREFIX_COARSE * PREFIX_SUB;
+TWK_SCREEN_FN uint32_t prefix_step(uint32_t nchunks) { return (nchunks + PREFIX_COARSE - 1) / PREFIX_COARSE; }
+TWK_SCREEN_FN uint32_t prefix_substep(uint32_t nchunks) { return (prefix_step(nchunks) + PREFIX_SUB - 1) / PREFIX_SUB; }
+TWK_SCREEN_FN uint32_t prefix_stop_chunks(uint32_t f, uint32_t nchunks) {
+	if (f >= PREFIX_GRID) return nchunks;
+	const uint32_t step = prefix_step(nchunks), sub = (f % PREFIX_SUB) * prefix_substep(nchunks);
+	const unsigned long long s = (unsigned long long)(f / PREFIX_SUB) * step + (sub < step ? sub : step);
+	return s >= nchunks ? nchunks : (uint32_t)s;
 }
 
 }  // namespace twk

@@ -218,7 +218,9 @@ namespace {
 	X(carrier, 1, 0, 1, false, "the two-product walk on rows of more than 128 K chunks: its two-product launches contract the row variant's carrier plane (H or Q, bit by bit) in the H plane's place (CH = HH + QH and CQ = HQ + QQ: S >= CQ and S + HH <= CH + CQ + min(qA, qB)), which moves the walk's cut from p ~ 0.16 to ~ 0.21 at r2 >= 0.1; one more plane row per row variant in front of the cut, built on first use and kept with the planes (DESIGN 3.1b); 0: always the H plane") \
 	X(prefix, 1, 0, 2, false, "the two-product walk on rows of more than 128 K chunks: a launch contracts each tile over a prefix of its rows, up to a stop the planner chooses per tile, and its screen bounds the unread samples by the rows' suffix margins; what it keeps is recounted over the whole rows (DESIGN 3.1c); 0: never; 1: launches whose sample with stops is poor in candidates; 2: every eligible launch whatever its sample") \
 	X(prefix_margin, 950, 1, 1000, false, "... the planner asks with the square root of the screen's bound shrunk to this many thousandths of it (950 as the two-product planner's two_margin = 0.95)") \
-	X(prefix_stop, 0, 0, 32, false, "test hook: this point of the 32-point grid of stops for every tile of a prefix launch (0: the planner's stops)") \
+	X(prefix_sigma, 60, 0, 200, false, "... and, beside it, with the screen's own bound and the expected prefix counts moved outwards by this many tenths of their standard deviation under independence; a pair counts as decided at a stop where either question drops it (60: six standard deviations, the tighter of the two on rows of about a million samples; 0: the first question alone)") \
+	X(prefix_stop, 0, 0, 32, false, "test hook: this point of the 32 coarse points of the grid of stops for every tile of a prefix launch (0: the planner's stops)") \
+	X(prefix_substop, 0, 0, 3, false, "test hook: ... moved this many of the four sub-steps of a coarse interval further, to a point of the 128-point grid that need not be a coarse one (read only where prefix_stop is set)") \
 	X(count_min_chunks, 8, 1, 1 << 20, false, "shortest K range a tile of the count kernel is split into at the end of a launch (test hook: 1 splits short rows too)") \
 	X(patch_rows, 8, 1, 4096, false, "rows of a patch of tiles in the count kernel's work order (DESIGN 3.1, profiles/r03_patch_pmc.txt)") \
 	X(patch_cols, 8, 1, 4096, false, "... and its columns") \
@@ -580,11 +582,10 @@ int ensure_suffix(twk_hip_ctx* c, int set) {
 	PlaneSet& ps = c->planes[set];
 	const size_t n = (size_t)ps.rows_alloc * PREFIX_GRID;
 	if (ps.h_suffix.size() == n && ps.suffix) return TWK_HIP_OK;
-	const uint32_t nchunks = ps.W / KC, seg_words = prefix_step(nchunks) * KC;
 	HIPCHK(c, ps.suffix.reserve(n, n, nullptr));
 	HIPCHK(c, hipMemsetAsync(ps.suffix, 0, n * 4, c->s_compute));
 	const uint32_t live_rows = c->M * (uint32_t)planes_per_variant(set_kind(set));
-	hipLaunchKernelGGL(k_row_suffix_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, live_rows, seg_words, ps.suffix.get());
+	hipLaunchKernelGGL(k_row_suffix_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, live_rows, ps.suffix.get());
 	HIPCHK(c, hipGetLastError());
 	ps.h_suffix.resize(n);
 	HIPCHK(c, hipMemcpyAsync(ps.h_suffix.data(), ps.suffix, n * 4, hipMemcpyDeviceToHost, c->s_compute));
@@ -701,7 +702,8 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		if (!(two || three) || fuse || which != 0 || P != 2 || ps.h_suffix.size() != (size_t)ps.rows_alloc * PREFIX_GRID || ps.h_het.size() != c->M) return TWK_HIP_E_STATE;
 		pe.het = ps.h_het.data(); pe.hom = ps.h_hom.data(); pe.suffix = ps.h_suffix.data();
 		pe.n_variants = c->M; pe.n_samples = c->N; pe.nchunks = nchunks;
-		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.fixed_grid = (uint32_t)c->opt.prefix_stop; pe.carrier = form.carrier;
+		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.sigma = (double)c->opt.prefix_sigma / 10.0; pe.carrier = form.carrier;
+		pe.fixed_grid = c->opt.prefix_stop ? (uint32_t)c->opt.prefix_stop * PREFIX_SUB + (uint32_t)c->opt.prefix_substop : 0;
 		pre_grid.assign((size_t)g.gy * g.gx, (uint8_t)PREFIX_GRID);
 	}
 	std::vector<uint32_t> stops;

@@ -12,6 +12,14 @@
 //      of every launch, the mean contracted fraction per launch and overall (two-product pairs at 0.66 of a three-product pair's cost).
 //      Then the same walk with the carrier plane as the row operand of its two-product launches (PlanEnv::carrier): a second report, every line
 //      under the prefix "carrier form:", with the cut, the steps of the walk and the count work against the first report's.
+//   4. The grid of stops (csrc/hip/ld_two_screen.h prefix_stop_chunks) against a naive restatement for every row length of 1 .. 2,000 chunks:
+//      the points never decrease, every coarse point is a fine point and the last point is the row's end; the suffix table's walk over segments
+//      of unequal length (csrc/hip/ld_prep.hip.h k_row_suffix_popcount, restated on the host) against plain sums; and the screens of 1. on
+//      rows of 129, 137 and 977 chunks cut at every fine stop - the prefix table in front of the stop, the suffix table behind it.
+//   5. The planner on the headline's law at four settings, carrier form, every line under the prefix "fine grid:": the grid of 32 points with
+//      margin 0.95 (the planner before the fine grid, restated here; the reports of 3. are this setting's), 128 points with 0.95, 128 points with
+//      0.95 and six standard deviations (the default), 128 points with 0.98 - count work against whole H-plane rows, against the first setting,
+//      and the host time of the stops.
 // usage: prefix_check [--no-planner]
 #include <cinttypes>
 #include <cmath>
@@ -181,7 +189,32 @@ int check_tables(int& n_cases) {
 // carrier: the second report - the walk's two-product launches contract the carrier plane.  Its lines carry a prefix of their own and the word
 // "step" where the first report says "launch" (tests/test_prefix_cpu.py reads the first report by its lines).  -> the count work with stops, in
 // three-product tile chunks; *two_end: the cut.
-double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t h_two_end = 0) {
+// The planner before the fine grid, restated: the 32 coarse points only, each pair walked from its neighbour's answer, one coarse step added.
+struct CoarseTileStops {
+	const PrefixEnv* e; bool two; uint32_t a0, b0, nA, nB; mutable uint32_t hint[5];
+	uint32_t need(uint32_t vA, uint32_t vB, uint32_t h) const {
+		uint32_t g = std::min<uint32_t>(std::max<uint32_t>(h, 1), PREFIX_COARSE);
+		while (g > 1 && e->dropped(two, vA, vB, (g - 1) * PREFIX_SUB)) --g;
+		while (g < PREFIX_COARSE && !e->dropped(two, vA, vB, g * PREFIX_SUB)) ++g;
+		return g;
+	}
+	uint32_t operator()(uint32_t yx) const {
+		const uint32_t y = yx >> 16, x = yx & 0xFFFFu, ta = two ? PLAN_TILE : PLAN_TILE / 2, tb = PLAN_TILE / 2;
+		if (!(y * ta < nA && x * tb < nB)) return e->nchunks;
+		const uint32_t a_lo = a0 + y * ta, a_hi = std::min(a0 + std::min(nA, (y + 1) * ta) - 1, e->n_variants - 1);
+		const uint32_t b_lo = b0 + x * tb, b_hi = std::min(b0 + std::min(nB, (x + 1) * tb) - 1, e->n_variants - 1);
+		if (a_lo > a_hi || b_lo > b_hi || b_lo <= a_hi) return e->nchunks;
+		const uint32_t pa[5] = {a_lo, a_lo, a_hi, a_hi, a_lo + (a_hi - a_lo) / 2}, pb[5] = {b_lo, b_hi, b_lo, b_hi, b_lo + (b_hi - b_lo) / 2};
+		uint32_t g = 1;
+		for (int k = 0; k < 5; ++k) { hint[k] = need(pa[k], pb[k], hint[k]); g = std::max(g, hint[k]); }
+		return prefix_stop_chunks(std::min<uint32_t>(g + 1, PREFIX_COARSE) * PREFIX_SUB, e->nchunks);
+	}
+};
+// fine: the planner of ld_plan.h on the grid of 128; else CoarseTileStops.  quiet: no report, only the work (section 5).
+struct Setting { bool fine; double margin, sigma; };
+constexpr Setting HEAD_SETTING{false, 0.95, 0.0};
+double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t h_two_end = 0, const Setting& st = HEAD_SETTING, bool quiet = false,
+                    double* work_whole = nullptr, double* stops_ms = nullptr, std::vector<double>* fractions = nullptr) {
 	const char* tag = carrier ? "carrier form: " : "planner: ";
 	const uint32_t M = 50000, N = 1000000, nchunks = (N + 1023) / 1024;
 	const double minR2 = 0.1, cut = minR2 * (1.0 - 1e-6), two_cost = 0.66;
@@ -199,9 +232,9 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 	const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
 	RegionPlan plan;
 	plan_region(env, g, plan);
-	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = 0.95; pe.carrier = carrier;
+	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = st.margin; pe.sigma = st.sigma; pe.carrier = carrier;
 	*two_end = plan.two_end;
-	printf("%s%u variants x %u samples, r2 >= %g, rows of %u chunks, grid step %u chunks; two-product cut at sorted row %u (p = %.3f); %zu %s\n",
+	if (!quiet) printf("%s%u variants x %u samples, r2 >= %g, rows of %u chunks, grid step %u chunks; two-product cut at sorted row %u (p = %.3f); %zu %s\n",
 	       tag, M, N, minR2, nchunks, prefix_step(nchunks), plan.two_end, 0.05 + 0.45 * plan.two_end / M, plan.mine.size(), carrier ? "steps" : "launches");
 	CountSettings cs;
 	double work_full = 0, work_done = 0, sum2_full = 0, sum2_done = 0, sum3_full = 0, sum3_done = 0, host_ms = 0;
@@ -213,8 +246,10 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		std::vector<uint8_t> grid((size_t)geo.gy * geo.gx, (uint8_t)PREFIX_GRID);
 		std::vector<uint32_t> stops;
 		const PrefixTileStops stop_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, geo.gx, &grid, {PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID}};
+		const CoarseTileStops coarse_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, {PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE}};
 		const auto t0 = std::chrono::steady_clock::now();
-		const CountTable tb = build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &stop_of, &stops);
+		const CountTable tb = st.fine ? build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &stop_of, &stops)
+		                              : build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &coarse_of, &stops);
 		const auto t1 = std::chrono::steady_clock::now();
 		const CountTable plain = build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0);
 		const auto t2 = std::chrono::steady_clock::now();
@@ -223,7 +258,8 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		for (const uint32_t s : stops) { done += s; lo = std::min(lo, s); hi = std::max(hi, s); }
 		const uint64_t full = (uint64_t)tb.n_tiles() * nchunks;
 		n_tiles += tb.n_tiles();
-		printf(carrier ? "  carrier form: step %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n" :
+		if (fractions) fractions->push_back(full ? (double)done / (double)full : 0.0);
+		if (!quiet) printf(carrier ? "  carrier form: step %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n" :
 		       "  launch %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n", i, two ? "two  " : "three", t.rowA0, t.nA, t.rowB0, t.nB,
 		       tb.n_tiles(), lo, hi, full ? (double)done / (double)full : 0.0);
 		// (a two-product tile holds 128 x 64 variant pairs, a three-product tile 64 x 64: per tile and chunk twice the pairs at two_cost each)
@@ -232,6 +268,9 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		(two ? sum2_full : sum3_full) += (double)full; (two ? sum2_done : sum3_done) += (double)done;
 	}
 	const double all_full = sum2_full * 2.0 * two_cost + sum3_full, all_pairs = 2.0 * sum2_full + sum3_full;
+	if (work_whole) *work_whole = work_full;
+	if (stops_ms) *stops_ms = host_ms;
+	if (quiet) return work_done;
 	printf(carrier ? "carrier form: two-product steps %.1f %% of the pairs (%.1f %% of the whole rows' count work), mean fraction of the row contracted %.4f; three-product steps %.1f %% of the pairs (%.1f %%), mean fraction %.4f\n" :
 	       "planner: two-product launches %.1f %% of the pairs (%.1f %% of today's count work), mean fraction of the row contracted %.4f; three-product launches %.1f %% of the pairs (%.1f %%), mean fraction %.4f\n",
 	       100.0 * 2.0 * sum2_full / all_pairs, 100.0 * sum2_full * 2.0 * two_cost / all_full, sum2_full ? sum2_done / sum2_full : 0.0,
@@ -243,6 +282,84 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		printf("carrier form: rows in front of the cut %u (H plane: %u); count work with stops %.4f of the H plane's with stops (two-product pairs at %.2f of a three-product pair); %" PRIu64 " tiles\n",
 		       plan.two_end, h_two_end, h_work > 0 ? work_done / h_work : 0.0, two_cost, n_tiles);
 	return work_done;
+}
+
+// ---- 4. the grid of stops ------------------------------------------------------------------------------------------------------
+uint32_t naive_stop(uint32_t f, uint32_t nchunks) {       // the definition in words: coarse interval g, sub-step s, clipped at the next coarse point and at the row's end
+	if (f >= 128) return nchunks;
+	const uint32_t step = (nchunks + 31) / 32, sub = (step + 3) / 4, g = f / 4, s = f % 4;
+	uint64_t at = (uint64_t)g * step + s * sub;
+	at = std::min<uint64_t>(at, (uint64_t)(g + 1) * step);
+	return (uint32_t)std::min<uint64_t>(at, nchunks);
+}
+int check_grid() {
+	const int before = g_bad_checks;
+	static_assert(PREFIX_GRID == 128 && PREFIX_COARSE == 32 && PREFIX_SUB == 4, "the grid the checks below restate");
+	for (uint32_t n = 1; n <= 2000; ++n) {
+		CHECK(prefix_stop_chunks(0, n) == 0 && prefix_stop_chunks(PREFIX_GRID, n) == n && prefix_stop_chunks(PREFIX_GRID + 7, n) == n, "%u chunks: ends", n);
+		for (uint32_t f = 0; f < PREFIX_GRID; ++f) {
+			const uint32_t at = prefix_stop_chunks(f, n);
+			CHECK(at == naive_stop(f, n), "%u chunks: point %u at %u, naive %u", n, f, at, naive_stop(f, n));
+			CHECK(at <= prefix_stop_chunks(f + 1, n) && at <= n, "%u chunks: point %u at %u, the next at %u", n, f, at, prefix_stop_chunks(f + 1, n));
+		}
+		// every coarse point (the grid of 32 before the fine one: min(g step, nchunks)) is the fine point 4 g
+		for (uint32_t g = 0; g <= PREFIX_COARSE; ++g)
+			CHECK(prefix_stop_chunks(g * PREFIX_SUB, n) == (uint32_t)std::min<uint64_t>((uint64_t)g * ((n + 31) / 32), n), "%u chunks: coarse point %u", n, g);
+		// the suffix table's walk (k_row_suffix_popcount: a lane meets the chunks c, c + 8, .. and moves its segment up), one count per chunk:
+		// segment sums -> suffix sums against plain sums
+		for (uint32_t lane8 = 0; lane8 < 8; lane8 += 7) {
+			uint32_t f = 0, next = prefix_stop_chunks(1, n);
+			for (uint32_t c = lane8; c < n; c += 8) {
+				while (f + 1 < PREFIX_GRID && next <= c) { ++f; next = prefix_stop_chunks(f + 1, n); }
+				CHECK(prefix_stop_chunks(f, n) <= c && c < prefix_stop_chunks(f + 1, n), "%u chunks: chunk %u put into segment %u = [%u, %u)", n, c, f, prefix_stop_chunks(f, n), prefix_stop_chunks(f + 1, n));
+			}
+		}
+	}
+	// the screens at every fine stop of a row: sparse random genotypes per chunk (one sample a chunk), prefix table in front of the stop, suffix table behind
+	uint64_t rng = 12345;
+	auto next_u = [&]() { rng = rng * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(rng >> 33); };
+	const uint64_t tests_before = g_tests;
+	for (const uint32_t n : {129u, 137u, 977u}) for (int rep = 0; rep < 6; ++rep) {
+		std::vector<uint8_t> cell(n);
+		for (uint32_t c = 0; c < n; ++c) {
+			const uint32_t r = next_u() % 100;
+			const bool linked = rep % 2 == 1 && c >= n / 2;      // (LD that lies in the back half of the row)
+			const uint32_t ga = r < 80 ? 0 : r < 95 ? 1 : 2, gb = linked ? ga : (next_u() % 100 < 85 ? 0 : next_u() % 3);
+			cell[c] = (uint8_t)(3 * ga + gb);
+		}
+		for (uint32_t f = 0; f <= PREFIX_GRID; ++f) {
+			uint32_t p[9] = {0}, x[9] = {0};
+			const uint32_t stop = prefix_stop_chunks(f, n);
+			for (uint32_t c = 0; c < n; ++c) ++(c < stop ? p : x)[cell[c]];
+			check_pair(p, x);
+		}
+	}
+	printf("prefix-check: grid of stops: rows of 1 .. 2000 chunks against the naive restatement, %" PRIu64 " screen tests at fine stops of rows of 129, 137, 977 chunks\n", g_tests - tests_before);
+	return g_bad_checks != before;
+}
+
+// ---- 5. the planner at four settings -----------------------------------------------------------------------------------------------
+void report_settings() {
+	struct Row { const char* name; Setting st; } rows[4] = {
+		{"32 points, margin 0.95 (before the fine grid)", {false, 0.95, 0.0}}, {"128 points, margin 0.95", {true, 0.95, 0.0}},
+		{"128 points, margin 0.95 or 6 sigma (the default)", {true, 0.95, 6.0}}, {"128 points, margin 0.98", {true, 0.98, 0.0}}};
+	double head = 0;
+	for (int k = 0; k < 4; ++k) {
+		uint32_t h_end = 0, c_end = 0;
+		double whole = 0, ms_h = 0, ms_c = 0;
+		std::vector<double> frac;
+		const double h_work = play_planner(false, &h_end, 0, 0, rows[k].st, true, &whole, &ms_h);
+		const double c_work = play_planner(true, &c_end, h_work, h_end, rows[k].st, true, nullptr, &ms_c, &frac);
+		if (k == 0) head = c_work;
+		printf("fine grid: %-50s H-form work %.4f of whole rows, x carrier form %.4f = %.4f; against the first setting %.4f; stops %.1f ms of host time a call\n",
+		       rows[k].name, h_work / whole, c_work / h_work, c_work / whole, c_work / head, ms_c);
+		if (k == 2) {
+			printf("fine grid: the default's fraction of the rows contracted, walk step by walk step:");
+			for (const double f : frac) printf(" %.4f", f);
+			printf("\nfine grid: prediction new / before %.4f\n", c_work / head);
+		}
+		if (k > 0) CHECK(c_work < head, "setting %d: work %g against %g", k, c_work, head);
+	}
 }
 
 }  // namespace
@@ -263,6 +380,8 @@ int main(int argc, char** argv) {
 		const double c_work = play_planner(true, &c_end, h_work, h_end);
 		CHECK(c_end > h_end && c_work < h_work, "carrier form: cut %u against %u, work %g against %g", c_end, h_end, c_work, h_work);
 	}
+	check_grid();
+	if (planner) report_settings();
 	printf("prefix-check: %s\n", (bad_screen || bad_tables || g_bad_checks) ? "FAILED" : "ok");
 	return (bad_screen || bad_tables || g_bad_checks) ? 1 : 0;
 }
