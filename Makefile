@@ -124,7 +124,7 @@ count-check:
 	./build/count_table_check tests/golden/count_tables.json
 
 # The two-product form's host side (csrc/tools/two_check.cpp): its screens (csrc/hip/ld_two_screen.h: the H plane or the carrier plane H | Q as the
-# row operand) over every small genotype table, and the
+# row operand, or one product of the two variants' carrier planes) over every small genotype table, plan_one_end on random sorted margins, and the
 # work table of a launch with one plane row per row variant and two per column variant against a naive restatement and the recorded order of
 # tests/golden/count_tables_two.json: host code only, under AddressSanitizer and UBSan
 two-check:

@@ -96,7 +96,8 @@ typedef struct {
 	int32_t  diag;
 	int32_t  window;   /* option bits, see TWK_HIP_OPT_*                                */
 	uint32_t l_window; /* base pairs (twk_ld_settings.l_window)                         */
-	uint32_t _pad;
+	uint32_t one;      /* set by the planner only, read by the region walk that owns the plan only (0 from every caller): a launch
+	                      in front of its rows' one_end, which may contract one product a pair                    */
 } twk_hip_tile_desc;
 
 /* Option bits for twk_hip_tile_desc.window and the `window` argument of ld_all / ld_region. */
@@ -792,6 +793,15 @@ int twk_hip_plan_region_two_operand(const twk_hip_plan_env* env, const twk_hip_v
                                     uint32_t tile_variants, int32_t window, uint32_t l_window,
                                     twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                                     uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end);
+/* ... and with the one-product launches of the carrier form (option "one"): one != 0 (read only with carrier != 0): the rows in front of the cut are
+ * walked in blocks of one_rows variants (a multiple of 128; 0: the engine's default), and a block's columns from the diagonal to its one_end - where
+ * the screen's lower test at S >= 0 stops passing for the block's last row (csrc/hip/ld_two_screen.h: screen1c_lower_ok), rounded down to 128
+ * variants - are launches with twk_hip_tile_desc::one set. */
+int twk_hip_plan_region_two_form(const twk_hip_plan_env* env, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                                 int32_t carrier, int32_t one, uint32_t one_rows, uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                                 uint32_t tile_variants, int32_t window, uint32_t l_window,
+                                 twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                                 uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end);
 
 /* Fisher's exact test on n caller-supplied 2x2 tables (tables[4*i + {0,1,2,3}] = n11, n12, n21, n22), two-sided P
  * into p_two_sided[i]: kt_fisher_exact (lib/fisher_math.cpp:231-267) as the pair math calls it
@@ -810,7 +820,7 @@ int twk_hip_fisher_exact(twk_hip_ctx* ctx, const int32_t* tables, uint64_t n, do
  * closest relative is the compile-time SLAVE_DEBUG_MODE / SIMD_AVAILABLE switches, lib/ld/ld_engine.h:20-24).
  * The keys, their defaults, ranges and meaning are ONE table in the engine (TWK_HIP_OPTIONS, csrc/hip/twk_hip.hip), readable through
  * twk_hip_option_describe() below and printed as the table of INTEGRATION.md 1 (tests/test_docs_consistency.py keeps the document in
- * step with it).  In short: "fused", "three", "two", "carrier", "prefix" pick the form of the contraction
+ * step with it).  In short: "fused", "three", "two", "carrier", "one", "prefix" pick the form of the contraction
  * ("prefix_margin" and "prefix_sigma" are the two questions the prefix contraction's planner asks for a tile's stop on its 128-point grid,
  * "prefix_stop" plus "prefix_substop" a test hook that puts every tile's stop on one point of it: DESIGN 3.1c); "lists", "list_max", "probe", "probe_zone",
  * "probe_lds" the carrier-list passes for rare variants; "band_*" the launches of fused runs; "patch_rows" / "patch_cols" / "seg" /
@@ -882,6 +892,10 @@ typedef struct {
 	uint64_t carrier_launches;    /* (appended likewise) Two-product launches whose row operand was the row variants' carrier plane H | Q
 	                                 in the H plane's place (CH and CQ for HH and HQ).  They stay part of two_launches, with
 	                                 the same row_pairs accounting: one row x two rows per variant pair                        */
+	uint64_t one_launches;        /* (appended likewise) Carrier launches that contracted one product a pair - the carrier rows of both variants,
+	                                 CC = CH + CQ - in front of their rows' one_end.  They stay part of two_launches and
+	                                 carrier_launches; their row_pairs are their variant pairs, one row x one row, in full-row equivalents
+	                                 under stops                                                                              */
 } twk_hip_timing;
 /* Progress of twk_hip_ld_all / twk_hip_ld_region: `cb` runs on the calling thread after every tile
  * with the variant pairs finished so far in the current call and the tile counts.  Replaces the
@@ -913,7 +927,7 @@ typedef struct {
 	uint64_t prefix_chunks;       /* a prefix launch: K chunks its tiles were contracted over ... (else 0)      */
 	uint64_t prefix_chunks_full;  /* ... and what whole rows would have been; row_pairs is scaled by their ratio            */
 	uint32_t carrier;             /* (appended likewise) != 0: a kind-5 launch whose row operand was the carrier plane H | Q   */
-	uint32_t _pad2;
+	uint32_t one;                 /* (in the place of padding) != 0: such a launch that contracted one product a pair, carrier rows on both axes */
 } twk_hip_launch_stat;
 /* Copies the most recent min(capacity, launches kept) entries, oldest first; *n_total: launches seen since the reset. */
 int twk_hip_launch_log(twk_hip_ctx* ctx, twk_hip_launch_stat* out, uint32_t capacity, uint32_t* n_copied, uint64_t* n_total);

@@ -24,6 +24,8 @@ struct LaunchForm {
 	                               // kernel trace's statistics of the real launches are not diluted by half-millisecond ones
 	bool carrier = false;          // a two-product launch whose row operand is the carrier plane H | Q (CH + CQ in place of HH + HQ; ld_two_screen.h): an attribute of
 	                               // `two`, never set without it
+	bool one = false;              // a carrier launch that contracts one product a pair - the carrier rows on both axes, CC = CH + CQ - and whose screen's lower test
+	                               // stands at S >= 0 (ld_two_screen.h: screen1c_*): an attribute of `two && carrier`, never set without them
 	bool prefix = false;           // a two- or three-product launch through a matrix whose tiles are contracted over a prefix of their rows (per-tile stops)
 	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
@@ -40,7 +42,8 @@ constexpr uint32_t FUSED_MAX_CHUNKS = 128;
 // What the owner of a launch allows it: `two` only where the two-product walk's owner says so for this launch (RegionRun, on the sorted set).
 // `prefix`: an attribute of such a launch's two- or three-product form, not a form of its own - stops for its tiles, where the owner's sample allows them.
 // `carrier`: the owner holds carrier rows for this launch's row variants (carrier_operand below) - the row operand of its two-product form, if it takes it.
-struct FormGrant { bool fused = true, three = true, two = false, sample = false, prefix = false, carrier = false; };
+// `one`: the walk's owner planned this launch in front of its rows' one_end (ld_plan.h) and holds carrier rows for its column variants too.
+struct FormGrant { bool fused = true, three = true, two = false, sample = false, prefix = false, carrier = false, one = false; };
 // What the tile plan, the filters and the options fix, whoever grants what.
 struct FormFacts {
 	bool two_pass = false;
@@ -49,7 +52,7 @@ struct FormFacts {
 	bool cut_screens = false;                               // an r2 cut-off a screen can use: minR2 > 1e-6 && minR2 <= 1
 	uint32_t chunks = 0;                                    // K chunks of a row (read only where a launch may fuse)
 	bool sorted_u = false;                                  // the set is PS_SORTED_U
-	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1, opt_carrier = 1;
+	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1, opt_carrier = 1, opt_one = 1;
 	uint32_t row_chunks = 0;                                // K chunks of a row (read only where a launch is granted the prefix)
 	uint32_t carrier_chunks = 0;                            // K chunks of a row (read only where a launch is granted the carrier plane)
 };
@@ -72,27 +75,30 @@ inline LaunchForm decide_form(const FormFacts& x, const FormGrant& g) {
 	lf.fused = x.opt_fused != 0 && (x.opt_fused == 2 || x.chunks <= FUSED_MAX_CHUNKS);
 	if (lf.three && !lf.fused && !lf.two_pass && x.sorted_u && g.two && x.opt_two != 0) { lf.two = true; lf.three = false; }
 	lf.carrier = lf.two && g.carrier && x.opt_carrier != 0 && x.carrier_chunks > FUSED_MAX_CHUNKS;
+	lf.one = lf.carrier && g.one && x.opt_one != 0;
 	// the prefix: only the matrix forms of the sorted walk, and only on rows the fused form never takes by policy - whatever "fused" is set to
 	lf.prefix = g.prefix && x.opt_prefix != 0 && (lf.two || lf.three_plain()) && !lf.two_pass && x.sorted_u && x.row_chunks > FUSED_MAX_CHUNKS;
 	return lf;
 }
 // The ladder: what the tile of a launch whose candidate list overflowed may be when it is redone - a two-product launch's with three products
 // (if it was granted them), a fused or three-product launch's with four products through a matrix.
-// A prefix launch's is redone over whole rows in the same product form.
+// A prefix launch's is redone over whole rows in the same product form; a one-product launch's in the carrier two-product form.
 inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
 	if (was.prefix) { given.prefix = false; return given; }
+	if (was.one) { given.one = false; return given; }
 	if (!was.two) given.fused = given.three = false;
-	given.two = given.carrier = false;
+	given.two = given.carrier = given.one = false;
 	return given;
 }
 
 // What the running call has not yet given up: a region call owns one for all its stages, the single-tile entry a fresh one.
 struct CallForms {
-	bool fused = true, three = true, two = true, prefix = true;
+	bool fused = true, three = true, two = true, prefix = true, one = true;
 	// ... and allows a launch, whose owner wants three / two products for it (and stops for its tiles)
 	// (the carrier plane is no form of the call's to give up: it goes where the two-product form goes)
-	FormGrant grant(bool want_three, bool want_two, bool want_prefix = false, bool want_carrier = false) const {
-		return FormGrant{fused, three && want_three, two && want_two, false, prefix && want_prefix, two && want_two && want_carrier};
+	// (one product is: a launch that overflows or is too rich in that form ends it for the call, and nothing else)
+	FormGrant grant(bool want_three, bool want_two, bool want_prefix = false, bool want_carrier = false, bool want_one = false) const {
+		return FormGrant{fused, three && want_three, two && want_two, false, prefix && want_prefix, two && want_two && want_carrier, one && two && want_two && want_carrier && want_one};
 	}
 	// A launch of form `was`, given `given`, is through: a list that overflowed (cand_overflow) or held more candidates than the recount is worth
 	// (too_rich) ends the form for the rest of the call - but a form the launch was not given is not taken from the call on its account.
@@ -100,6 +106,7 @@ struct CallForms {
 		// (a prefix launch's overflow - and its richness in candidates, which the wider screen of its stops makes - is the stops' doing: either ends
 		// the prefix for the call, the two-product rule, and no product form: the launches behind it are judged over whole rows again)
 		if (was.prefix) { if (cand_overflow || too_rich) prefix = false; return; }
+		if (was.one) { if (cand_overflow || too_rich) one = one && !given.one; return; }
 		if (cand_overflow && was.two) two = two && !given.two;
 		if (cand_overflow && (was.fused || was.three)) { fused = fused && !given.fused; three = three && !given.three; }
 		if (too_rich && was.three && !was.keep_three) three = three && !given.three;

@@ -36,6 +36,9 @@ struct PlanEnv {                                    // what the planner needs to
 	// ... the form of its launches' row operand: the carrier plane H | Q in the H plane's place (ld_two_screen.h: screen2c_*) - the cut is then asked of
 	// the carrier screen and lies further on (r2 >= 0.1: p ~ 0.21 for ~ 0.16)
 	bool carrier = false;
+	// ... and, in front of the cut, one product a pair where the screen's lower test is decided by the dosages alone (plan_one_tiles): only with `carrier`.
+	// one_rows: the height of those rows' blocks in variants (a multiple of 128; 0: the default, plan_one_rows)
+	bool one = false; uint32_t one_rows = 0;
 	// options
 	bool band_launch = true, band_reverse = true; long long band_work_log2 = 19, band_max_launches = 8, band_list_entries = 0;
 	const twk_hip_variant_meta& at(uint32_t i) const { return meta[ids ? ids[i] : i]; }
@@ -216,8 +219,9 @@ inline void plan_push_tile(const PlanEnv& e, const PlanGeom& g, std::vector<twk_
 // launch of B blocks takes ceil(B / resident) rounds of (equal length) blocks, so the partial last round is pure loss; with the
 // default tiling the column step is chosen, per row block, to minimise the total number of rounds (ties: fewer launches) - it matters
 // for the thin bands of a multi-GPU shard.  C stays <= 2 GiB per tile.
-inline void plan_matrix_tiles(const PlanEnv& e, const PlanGeom& g, const RegionPlan& p, uint32_t xa, uint32_t xb, std::vector<twk_hip_tile_desc>& out) {
-	const uint32_t S = p.S, nB = g.nB;
+// (S_: a super-tile edge of the caller's in the plan's place - plan_one_tiles)
+inline void plan_matrix_tiles(const PlanEnv& e, const PlanGeom& g, const RegionPlan& p, uint32_t xa, uint32_t xb, std::vector<twk_hip_tile_desc>& out, uint32_t S_ = 0) {
+	const uint32_t S = S_ ? S_ : p.S, nB = g.nB;
 	const uint64_t P = (uint64_t)e.Pmax;
 	auto rows_of = [&](uint32_t nv) -> uint64_t { return ((uint64_t)nv * P + PLAN_TILE - 1) / PLAN_TILE; };
 	auto blocks_of = [&](uint32_t h, uint32_t w, bool diag) -> uint64_t {      // a diagonal tile only runs the blocks on and above its diagonal
@@ -347,6 +351,66 @@ inline uint32_t plan_two_end(const PlanEnv& e, const PlanGeom& g) {
 	return r / PLAN_TILE * PLAN_TILE;
 }
 
+// ---- one-product launches in front of the cut -----------------------------------------------------------------
+// The one-product screen (ld_two_screen.h: screen1c_*) tests its lower value at S >= 0, where it is -(dA dB) - eps: a function of the two
+// dosages.  In allele-count order it passes for a row against every column up to some boundary and fails from there on (the ratio
+// dA dB / (rA rB) rises along the columns), and a row in front passes wherever a later row does - but for pairs of two very rare variants,
+// where eps decides.  plan_one_end: the first column (relative to b0, > row) at which the test fails for `row`, nB if there is none - a binary
+// search on the real het and hom counts; row + 1 if it fails at once.
+inline bool plan_one_lower_ok(const PlanEnv& e, const PlanGeom& g, uint32_t row, uint32_t col) {
+	const ScreenMargins m{e.het[g.a0 + row], e.hom[g.a0 + row], e.het[g.b0 + col], e.hom[g.b0 + col]};
+	return screen1c_lower_ok(m, 2.0 * (double)e.n_samples, e.minR2 * (1.0 - 1e-6));
+}
+inline uint32_t plan_one_end(const PlanEnv& e, const PlanGeom& g, uint32_t row) {
+	uint32_t lo = std::min(row + 1, g.nB), hi = g.nB;      // [lo, hi): the first failing column lies in [lo, hi]
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (plan_one_lower_ok(e, g, row, mid)) lo = mid + 1; else hi = mid;
+	}
+	return lo;
+}
+// The height of the row blocks in front of the cut: option "one_rows", else half the super-tile edge S - a block's one_end is its last row's, so
+// lower blocks reach further.  The planner predicts 0.8685 of the carrier form's count work with S / 2 against 0.8775 with S on the headline, and
+// the GPU agrees: 2598 against 2622 ms a step, one more launch a step included (profiles/one_product_ab.txt).  Never lower than 1024 rows by
+// default (or S, where that is less): below that a block is a launch of a few hundred tiles, and halving it buys a sample, a ramp-up and a tail more
+// for a boundary that moves by a tile or two.
+inline uint32_t plan_one_rows(const PlanEnv& e, uint32_t S) {
+	const uint32_t h = e.one_rows ? e.one_rows : std::max<uint32_t>(S / 2, std::min<uint32_t>(S, 1024));
+	return std::max<uint32_t>(PLAN_TILE, h / PLAN_TILE * PLAN_TILE);
+}
+// The rows [xa, xb) in front of the cut, block by block: the columns [diagonal, one_end) of a block as one-product launches (twk_hip_tile_desc::one;
+// tiles of 128 x 128 variants over the carrier rows of both axes), the columns [one_end, nB) as two-product launches as before.  one_end: the
+// block's last row's, rounded down to a whole number of 128 variants from the diagonal and never before the block's own end; a block whose own
+// pairs do not all pass the lower test (two very rare variants; a block that straddles the boundary) has no one-product launch.  A launch's
+// rectangle is one whose count matrix stays within 2 GiB also when it is redone with four products, as for every other launch.
+inline void plan_one_tiles(const PlanEnv& e, const PlanGeom& g, const RegionPlan& p, uint32_t xa, uint32_t xb, std::vector<twk_hip_tile_desc>& out) {
+	const uint32_t H = plan_one_rows(e, p.S), nB = g.nB;
+	for (uint32_t x = xa; x < xb; x += H) {
+		const uint32_t h = std::min(H, xb - x), last = x + h - 1;
+		uint32_t w = 0;      // columns of the block's one-product launches, from the diagonal
+		if (last + 1 < nB && (h < 2 || plan_one_lower_ok(e, g, x, x + 1))) {
+			const uint32_t end = plan_one_end(e, g, last);
+			if (end >= std::min(x + h, nB) && end > last + 1) w = end >= nB ? nB - x : std::max(h, (end - x) / PLAN_TILE * PLAN_TILE);
+		}
+		const uint64_t rows = plan_round_up(h, PLAN_TILE);
+		const uint32_t w_max = (uint32_t)std::max<uint64_t>(h, std::min<uint64_t>(32768, ((1ull << 27) / rows) / PLAN_TILE * PLAN_TILE));
+		uint32_t col = x;
+		for (bool diag = true; col < x + w; diag = false) {
+			const uint32_t wl = std::min(w_max, x + w - col);
+			const size_t before = out.size();
+			plan_push_tile(e, g, out, x, h, col, wl, diag ? 1 : 0);
+			if (out.size() > before) out.back().one = 1;
+			col += wl;
+		}
+		if (!w) { plan_matrix_tiles(e, g, p, x, x + h, out, h); continue; }
+		// the rest of the block's columns: two products, as few launches of equal width as that bound allows
+		if (col < nB) {
+			const uint32_t rest = nB - col, n_l = (rest + w_max - 1) / w_max, step = plan_round_up((rest + n_l - 1) / n_l, PLAN_TILE / 2);
+			for (; col < nB; col += step) plan_push_tile(e, g, out, x, h, col, std::min(step, nB - col), 0);
+		}
+	}
+}
+
 // ---- the prefix contraction's stops ---------------------------------------------------------------------------
 // A tile of a two- or three-product launch of the two-product walk is contracted over the chunks [0, stop) only; the screen bounds what it did
 // not read by the rows' suffix margins (ld_two_screen.h).  The stop of a tile: for a small fixed set of its variant pairs - the four corners
@@ -363,6 +427,7 @@ struct PrefixEnv {
 	double cut = 0, margin = 0.95, sigma = 6.0;
 	uint32_t fixed_grid = 0;                                           // test hooks "prefix_stop", "prefix_substop": this fine index for every tile (0: the planner's)
 	bool carrier = false;                                              // a two-product launch's row operand is the carrier plane (PlanEnv::carrier)
+	bool one = false;                                                  // ... and the launch contracts one product a pair (LaunchForm::one): the one-product questions
 	uint64_t samples_before(uint32_t f) const { return std::min<uint64_t>((uint64_t)prefix_stop_chunks(f, nchunks) * 32u * 32u, n_samples); }
 	bool dropped(bool two, uint32_t vA, uint32_t vB, uint32_t f) const {
 		if (f >= PREFIX_GRID) return true;       // (whole rows: the screen itself decides)
@@ -370,6 +435,10 @@ struct PrefixEnv {
 		const SuffixMargins x{suffix[(size_t)(2 * vA) * PREFIX_GRID + f], suffix[(size_t)(2 * vA + 1) * PREFIX_GRID + f],
 		                      suffix[(size_t)(2 * vB) * PREFIX_GRID + f], suffix[(size_t)(2 * vB + 1) * PREFIX_GRID + f]};
 		const double n_pre = (double)samples_before(f), two_n = 2.0 * (double)n_samples;
+		if (two && carrier && one) {
+			if (!prefix_expected_keeps_one(m, x, n_pre, two_n, cut, margin)) return true;
+			return sigma > 0 && !prefix_sigma_keeps_one(m, x, n_pre, two_n, cut, sigma);
+		}
 		if (!(two && carrier ? prefix_expected_keeps_carrier(m, x, n_pre, two_n, cut, margin) : prefix_expected_keeps(m, x, two, n_pre, two_n, cut, margin))) return true;
 		return sigma > 0 && !prefix_sigma_keeps(m, x, two, two && carrier, n_pre, two_n, cut, sigma);
 	}
@@ -409,12 +478,13 @@ inline uint32_t plan_prefix_tile_grid(const PrefixEnv& e, bool two, uint32_t a_l
 
 // The stops of a launch's tiles as build_count_table (ld_count_table.h) asks for them: called with a tile's (tile row << 16 | tile column) in
 // the order of the list, -> its stop in chunks; the grid index goes into grid[tile row * gx + tile column] for the screen.  A tile holds
-// 64 x 64 variants in the three-product form and 128 row variants x 64 column variants in the two-product form.
+// 64 x 64 variants in the three-product form, 128 row variants x 64 column variants in the two-product form and 128 x 128 in the one-product form.
 struct PrefixTileStops {
 	const PrefixEnv* e; bool two; uint32_t a0, b0, nA, nB, gx; std::vector<uint8_t>* grid; mutable uint32_t hint[5];
 	uint32_t tvA() const { return two ? PLAN_TILE : PLAN_TILE / 2; }
+	uint32_t tvB() const { return two && e->carrier && e->one ? PLAN_TILE : PLAN_TILE / 2; }
 	uint32_t operator()(uint32_t yx) const {
-		const uint32_t y = yx >> 16, x = yx & 0xFFFFu, ta = tvA(), tb = PLAN_TILE / 2;
+		const uint32_t y = yx >> 16, x = yx & 0xFFFFu, ta = tvA(), tb = tvB();
 		uint32_t g = PREFIX_GRID;
 		if (y * ta < nA && x * tb < nB)
 			g = plan_prefix_tile_grid(*e, two, a0 + y * ta, a0 + std::min(nA, (y + 1) * ta) - 1, b0 + x * tb, b0 + std::min(nB, (x + 1) * tb) - 1, hint);
@@ -435,7 +505,8 @@ inline void plan_region(const PlanEnv& e, const PlanGeom& g, RegionPlan& p) {
 	if (e.het && !p.windowed && p.bands.empty()) p.two_end = plan_two_end(e, g);
 	if (p.bands.empty()) {       // (the two-product walk: no launch straddles two_end)
 		const uint32_t cut = std::min(std::max(p.two_end, p.r0), p.r1);
-		plan_matrix_tiles(e, g, p, p.r0, cut, p.mine);
+		if (e.one && e.carrier && e.het && cut > p.r0) plan_one_tiles(e, g, p, p.r0, cut, p.mine);      // (... and a block's one-product launches end at its one_end)
+		else plan_matrix_tiles(e, g, p, p.r0, cut, p.mine);
 		plan_matrix_tiles(e, g, p, cut, p.r1, p.mine);
 	}
 	if (e.screen) p.pairs = band_pairs_before(p.r1, g.nA, g.nB, true) - band_pairs_before(p.r0, g.nA, g.nB, true);   // every pair of the band is decided

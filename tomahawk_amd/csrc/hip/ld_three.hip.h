@@ -22,8 +22,10 @@ namespace twk {
 // rows: (HH, HQ) where the three-product form leaves (HH, S), same layout), the test screen2_keeps - the same doubles with S_lo = HQ and
 // S_hi = HQ + qA + min(qA, qB) in S's place (ld_two_screen.h) - and a candidate is (A, B, HH, HQ, -, -).  ScreenWork::carrier: the row operand was
 // the carrier plane H | Q, the matrix holds (CH, CQ) in the same layout and the test is screen2c_keeps; a candidate is (A, B, CH, CQ, -, -).
+// ONE (k_screen1_pairs; ScreenWork::carrier == 2): the matrix is that of a one-product launch - k_count_list_t over the carrier rows of both axes, one
+// count CC = popc(C_A & C_B) per pair, ldc = columns, a tile 128 x 128 variants - the test screen1c_keeps and a candidate (A, B, CC, 0, stop, -).
 constexpr int SCREEN3_THREADS = 256;
-template <bool TWO>
+template <bool TWO, bool ONE = false>
 __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) {
 	const ScreenWork& s = *sp;
 	const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
@@ -39,24 +41,25 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 	}
 	uint32_t hh = 0, s_sum = 0, stop = 0;      // stop: the chunks the pair's counts cover (0: the whole rows)
 	if (ok) {
-		const uint2 hs = *reinterpret_cast<const uint2*>(C + (size_t)i * ldc + 2 * j);
-		hh = hs.x; s_sum = hs.y;
+		if (ONE) hh = C[(size_t)i * ldc + j];
+		else { const uint2 hs = *reinterpret_cast<const uint2*>(C + (size_t)i * ldc + 2 * j); hh = hs.x; s_sum = hs.y; }
 		const ScreenMargins m{s.rowpop[2 * vA], s.rowpop[2 * vA + 1], s.rowpop[2 * vB], s.rowpop[2 * vB + 1]};
 		// a prefix launch: the pair's tile was contracted over the chunks [0, stop) only - the counts are the prefix's, and the
 		// unread part of the two rows is bounded by its margins (ld_two_screen.h)
 		if (s.pre_stops) {
-			const uint32_t g = s.pre_stops[(size_t)(i / s.pre_tvA) * s.pre_gx + j / (TILE / 2)];
+			const uint32_t g = s.pre_stops[(size_t)(i / s.pre_tvA) * s.pre_gx + j / (ONE ? TILE : TILE / 2)];
 			const uint32_t st = prefix_stop_chunks(g, s.pre_nchunks);
 			if (st < s.pre_nchunks) {
 				stop = st;
 				const uint32_t* fA = s.pre_suffix + (size_t)(2 * vA) * PREFIX_GRID + g;
 				const uint32_t* fB = s.pre_suffix + (size_t)(2 * vB) * PREFIX_GRID + g;
 				const SuffixMargins x{fA[0], fA[PREFIX_GRID], fB[0], fB[PREFIX_GRID]};
-				ok = TWO ? (s.carrier ? screen2c_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut) : screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut))
+				ok = ONE ? screen1c_prefix_keeps(m, x, hh, s.two_n, s.cut)
+				   : TWO ? (s.carrier ? screen2c_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut) : screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut))
 				         : screen3_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut);
 			}
 		}
-		if (!stop) ok = TWO ? (s.carrier ? screen2c_keeps(m, hh, s_sum, s.two_n, s.cut) : screen2_keeps(m, hh, s_sum, s.two_n, s.cut)) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
+		if (!stop) ok = ONE ? screen1c_keeps(m, hh, s.two_n, s.cut) : TWO ? (s.carrier ? screen2c_keeps(m, hh, s_sum, s.two_n, s.cut) : screen2_keeps(m, hh, s_sum, s.two_n, s.cut)) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
 	}
 	__shared__ uint32_t wave_n[SCREEN3_THREADS / 64];
 	__shared__ unsigned long long block_base;
@@ -85,6 +88,8 @@ __global__ __launch_bounds__(SCREEN3_THREADS)
 void k_screen3_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) { screen_pairs_body<false>(sp, pp, C, ldc); }
 __global__ __launch_bounds__(SCREEN3_THREADS)
 void k_screen2_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) { screen_pairs_body<true>(sp, pp, C, ldc); }
+__global__ __launch_bounds__(SCREEN3_THREADS)
+void k_screen1_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) { screen_pairs_body<true, true>(sp, pp, C, ldc); }
 
 // ---- the candidates' four products --------------------------------------------------------------------------------------
 // The three-product forms hand over (A, B, HH, S); UnphasedMath needs HH, HQ, QH and QQ.  LANES lanes per candidate (64 for
@@ -96,6 +101,7 @@ void k_screen2_pairs(const ScreenWork* __restrict__ sp, const StatsParams* __res
 // own four products is counted in *mismatches, and the host fails the call on it.  two != 0: the candidates are a two-product launch's,
 // (A, B, HH, HQ) - the proof is then that both products equal their recount.  two == 2: the launch's row operand was the carrier plane, the
 // candidates are (A, B, CH, CQ), and the proof compares them with HH + QH and HQ + QQ of the recount; the records are the four products' as ever.
+// two == 3: a one-product launch's candidates (A, B, CC, 0): the proof compares CC with HH + QH + HQ + QQ over the chunks the contraction read.
 template <int LANES>
 __global__ __launch_bounds__(256)
 void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t W_live, uint32_t* __restrict__ cand,
@@ -128,7 +134,8 @@ void k_recount_unphased(const uint32_t* __restrict__ rows, uint32_t W, uint32_t 
 			const uint32_t d_qq = __popc(b.x & y.x) + __popc(b.y & y.y) + __popc(b.z & y.z) + __popc(b.w & y.w);
 			hh += d_hh; hq += d_hq; qh += d_qh; qq += d_qq;
 			if (p < pre4) {
-				if (two == 2) { p_hh += d_hh + d_qh; p_s += d_hq + d_qq; }      // the carrier plane's products: CH = HH + QH, CQ = HQ + QQ
+				if (two == 3) p_hh += d_hh + d_qh + d_hq + d_qq;                // the two carrier planes' product: CC = CH + CQ (p_s stays 0, as the candidate's)
+				else if (two == 2) { p_hh += d_hh + d_qh; p_s += d_hq + d_qq; }      // the carrier plane's products: CH = HH + QH, CQ = HQ + QQ
 				else { p_hh += d_hh; p_s += two ? d_hq : d_qh + d_hq + 2u * d_qq; }
 			}
 		}

@@ -71,6 +71,45 @@ TWK_SCREEN_FN bool screen2c_expected_keeps(const ScreenMargins& m, double n_samp
 	return screen_keeps_between(m, ch, cq, cq + screen2c_slack(m), two_n, cut, margin * margin);
 }
 
+// ---- one product: the two carrier planes against each other --------------------------------------------------------------
+// CH + CQ = popc(C_A & (H_B | Q_B)) = popc(C_A & C_B) = CC: the upper end of the carrier screen, CH + CQ + min(qA, qB), needs only the one product
+// of the two variants' carrier rows.  CQ by itself is read by the lower test alone - and there the trivial bound S >= 0 may stand in its place:
+//     T = S + HH = CC + QQ <= CC + min(qA, qB),     S >= 0,
+// and both test values rise with their argument, so the screen at (hh = CC, s_lo = 0, s_hi = min(qA, qB)) tests the same upper value as
+// screen2c_keeps and a lower value no larger than its: it keeps every pair screen2c_keeps keeps, which keeps every pair screen3_keeps keeps.
+// The lower value at s_lo = 0 reads no count at all: e_lo(0) = (ra - db) 2N - ra rb - eps = -(da db) - eps, a function of the two dosages - the
+// sort key of the sorted set - which lies inside the bound whenever, roughly, ab / ((1 - a)(1 - b)) < minR2 for allele frequencies a, b
+// (screen1c_lower_ok: the planner's exact question, ld_plan.h plan_one_end).  For such a pair the one-product screen drops what the carrier
+// screen drops wherever the latter's own lower test was not the one that kept the pair.
+TWK_SCREEN_FN bool screen1c_keeps(const ScreenMargins& m, uint32_t cc, double two_n, double cut) {
+	return screen_keeps_between(m, (double)cc, 0.0, screen2c_slack(m), two_n, cut);
+}
+// The lower half alone, at s_lo = 0 (the doubles of screen_keeps_between in the same order): true where the one-product screen's lower test
+// passes whatever the counts - the upper test then decides alone.
+TWK_SCREEN_FN bool screen1c_lower_ok(const ScreenMargins& m, double two_n, double cut) {
+	const double T2n = two_n, eps = 1e-5 * (T2n * T2n);
+	const double da = (double)(m.hA + 2u * m.qA), ra = T2n - da, fA = cut * (da * ra);
+	const double db = (double)(m.hB + 2u * m.qB), rb = T2n - db, fB = db * rb;
+	const double n11_lo = (ra - db) + 0.0;
+	const double e_lo = (n11_lo * T2n - ra * rb) - eps;
+	return e_lo * e_lo < fA * fB;
+}
+// The upper half alone, at t_hi = s_hi + hh, against the bound scaled by bound_factor.
+TWK_SCREEN_FN bool screen_upper_keeps(const ScreenMargins& m, double t_hi, double two_n, double cut, double bound_factor = 1.0) {
+	const double T2n = two_n, eps = 1e-5 * (T2n * T2n);
+	const double da = (double)(m.hA + 2u * m.qA), ra = T2n - da, fA = cut * (da * ra);
+	const double db = (double)(m.hB + 2u * m.qB), rb = T2n - db, fB = db * rb;
+	const double e_hi = (((ra - db) + t_hi) * T2n - ra * rb) + eps;
+	return !(e_hi * e_hi < fA * fB * bound_factor);
+}
+// The planner's question of the one-product form: under independence CC = cA cB / N.  The lower test has no count in it - it is asked exactly,
+// without the margin, as the plan asked it (plan_one_end) - so the margin shrinks the upper test's bound alone.
+TWK_SCREEN_FN bool screen1c_expected_keeps(const ScreenMargins& m, double n_samples, double two_n, double cut, double margin) {
+	if (!screen1c_lower_ok(m, two_n, cut)) return true;
+	const double cc = ((double)m.hA + (double)m.qA) * ((double)m.hB + (double)m.qB) / n_samples;
+	return screen_upper_keeps(m, cc + screen2c_slack(m), two_n, cut, margin * margin);
+}
+
 // ---- the prefix contraction ------------------------------------------------------------------------------------------
 // A launch may contract only the first K chunks [0, stop) of a tile's rows.  Per sample, with g = 0 / 1 / 2 alt alleles, the contribution to
 // S = QH + HQ + 2 QQ is >= 0 and the contribution to S + HH is exactly min(gA, gB); summed over the unread suffix, whose margins are the
@@ -148,6 +187,28 @@ TWK_SCREEN_FN bool prefix_sigma_keeps(const ScreenMargins& m, const SuffixMargin
 	const double sd_lo = v_lo > 0 ? __builtin_sqrt(v_lo) : 0.0, sd_hi = v_hi > 0 ? __builtin_sqrt(v_hi) : 0.0;
 	const double s_lo = n_pre * mu_lo - z * sd_lo, s_hi = n_pre * (mu_hi - hh) + fixed + z * sd_hi;
 	return screen_keeps_between(m, n_pre * hh, s_lo, s_hi, two_n, cut);
+}
+
+// The one-product form over the prefix: cc = CC_pre.  T_pre <= CC_pre + min(qa_pre, qb_pre) with the prefix margins, the unread suffix adds
+// prefix_slack(x) to the upper end, and S >= 0 as over whole rows.
+TWK_SCREEN_FN bool screen1c_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t cc, double two_n, double cut) {
+	const double qa = (double)(m.qA - x.qA), qb = (double)(m.qB - x.qB);
+	return screen_keeps_between(m, (double)cc, 0.0, (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut);
+}
+// ... and the planner's two questions for a stop of a one-product launch.  The lower sum is 0 with no spread: the lower test is the exact one,
+// outside margin and sigmas.  The upper sum CC_pre is the sum of the indicator (gA >= 1, gB >= 1), as in the carrier branch of prefix_sigma_keeps.
+TWK_SCREEN_FN bool prefix_expected_keeps_one(const ScreenMargins& m, const SuffixMargins& x, double n_pre, double two_n, double cut, double margin) {
+	if (n_pre <= 0 || !screen1c_lower_ok(m, two_n, cut)) return true;
+	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
+	const double cc = (ha + qa) * (hb + qb) / n_pre;
+	return screen_upper_keeps(m, cc + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut, margin * margin);
+}
+TWK_SCREEN_FN bool prefix_sigma_keeps_one(const ScreenMargins& m, const SuffixMargins& x, double n_pre, double two_n, double cut, double z) {
+	if (n_pre <= 0 || !screen1c_lower_ok(m, two_n, cut)) return true;
+	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
+	const double mu = ((ha + qa) / n_pre) * ((hb + qb) / n_pre), v = n_pre * (mu - mu * mu);
+	const double sd = v > 0 ? __builtin_sqrt(v) : 0.0;
+	return screen_upper_keeps(m, n_pre * mu + (qa < qb ? qa : qb) + prefix_slack(x) + z * sd, two_n, cut);
 }
 
 // The grid of stops: PREFIX_COARSE coarse points along a row of nchunks K chunks, prefix_step chunks apart (the option "prefix_stop" counts in

@@ -216,6 +216,9 @@ namespace {
 	X(three, 1, 0, 2, false, "UnphasedMath on planes without missing genotypes, r2 cut-off > 1e-6: contract three products a pair (HH and S = QH + HQ + 2 QQ: all the screen reads) and recount the four products of the pairs that pass (DESIGN 3.1a); 0: four products for every pair; 2: keep to three whatever a launch's candidate density (1 samples every launch first)") \
 	X(two, 1, 0, 2, false, "UnphasedMath, whole triangle without a window, rows too long to fuse, three = 1 and no tile edge given: walk the allele-count-sorted planes and contract two products a pair (HH and HQ of the row variant's H plane; S bounded from the margins) in the launches whose rows have few hom-alt carriers (DESIGN 3.1b); 0: never (the call walks the file order); 2: in every launch of that walk, whatever the predicate and the samples say") \
 	X(carrier, 1, 0, 1, false, "the two-product walk on rows of more than 128 K chunks: its two-product launches contract the row variant's carrier plane (H or Q, bit by bit) in the H plane's place (CH = HH + QH and CQ = HQ + QQ: S >= CQ and S + HH <= CH + CQ + min(qA, qB)), which moves the walk's cut from p ~ 0.16 to ~ 0.21 at r2 >= 0.1; one more plane row per row variant in front of the cut, built on first use and kept with the planes (DESIGN 3.1b); 0: always the H plane") \
+	X(one, 1, 0, 2, false, "the carrier form of the two-product walk: in front of the walk's cut a row block's columns up to its one_end - where the screen's lower test at S >= 0, a function of the two dosages alone, stops passing - are launches that contract one product a pair, the two variants' carrier rows (CC = CH + CQ: all the upper test reads), with carrier rows for the column variants too; the rest of the block's columns stay two-product launches (DESIGN 3.1b); 0: never; 1: launches whose sample in that form is poor in candidates; 2: every such launch whatever its sample") \
+	X(one_rows, 0, 0, 32768, false, "... the height in variants of the row blocks in front of the cut, a multiple of 128 (0: half the super-tile edge, but no less than 1024 or the edge itself; 128: the test hook)") \
+	X(cand_cap, 0, 0, 1 << 30, false, "test hook: at most this many entries in the candidate list of a two- or three-product launch through a matrix (0: the list's own size), so that a launch overflows and the ladder below it runs") \
 	X(prefix, 1, 0, 2, false, "the two-product walk on rows of more than 128 K chunks: a launch contracts each tile over a prefix of its rows, up to a stop the planner chooses per tile, and its screen bounds the unread samples by the rows' suffix margins; what it keeps is recounted over the whole rows (DESIGN 3.1c); 0: never; 1: launches whose sample with stops is poor in candidates; 2: every eligible launch whatever its sample") \
 	X(prefix_margin, 950, 1, 1000, false, "... the planner asks with the square root of the screen's bound shrunk to this many thousandths of it (950 as the two-product planner's two_margin = 0.95)") \
 	X(prefix_sigma, 60, 0, 200, false, "... and, beside it, with the screen's own bound and the expected prefix counts moved outwards by this many tenths of their standard deviation under independence; a pair counts as decided at a stop where either question drops it (60: six standard deviations, the tighter of the two on rows of about a million samples; 0: the first question alone)") \
@@ -672,17 +675,22 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	const bool fuse = form.fused, three = form.three, two = form.two, with_args = fuse || three || two;       // with_args: the parameter blocks go to the device behind the unit table
 	if (with_args != (fa != nullptr)) return TWK_HIP_E_STATE;
 	const PlaneSet& ps = c->planes[set];
-	const int P = planes_per_variant(set_kind(set));
 	// two products: one plane row - the H plane, every other row - per row variant, so tiles of 128 row variants x 64 column variants
 	// ... or, a carrier launch, consecutive rows of the set's carrier plane (ensure_carrier): same tiles, same table, rows of their own
+	// ... or, a one-product launch, such rows on both axes: one row per variant, tiles of 128 x 128 variants, the table geometry of a set with one
+	// plane per variant (P = PA = 1 from here on; the planes themselves are not read)
+	const int P_set = planes_per_variant(set_kind(set));
+	if (two && (P_set != 2 || fuse || which != 0)) return TWK_HIP_E_STATE;
+	if ((form.carrier && !two) || (form.one && !form.carrier)) return TWK_HIP_E_STATE;
+	const int P = form.one ? 1 : P_set;
 	const int PA = two ? 1 : P;
 	const uint32_t stepA = form.carrier ? 1u : (uint32_t)(P / PA);
-	if (two && (P != 2 || fuse || which != 0)) return TWK_HIP_E_STATE;
-	if (form.carrier && !two) return TWK_HIP_E_STATE;
 	const Geometry g = tile_geometry(P, t, PA);
 	if (form.carrier) {      // every row variant has its carrier row, and a tile's 128 rows end inside the zeroed pad
 		if (!ps.carrier_rows || (uint64_t)t.rowA0 + t.nA > ps.carrier_n || (uint64_t)t.rowA0 + g.rowsA > (uint64_t)round_up(ps.carrier_n, TILE) + TILE) return TWK_HIP_E_STATE;
-		if ((uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
+		if (form.one) {      // ... and so has every column variant
+			if ((uint64_t)t.rowB0 + t.nB > ps.carrier_n || (uint64_t)t.rowB0 + g.rowsB > (uint64_t)round_up(ps.carrier_n, TILE) + TILE) return TWK_HIP_E_STATE;
+		} else if ((uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
 	} else if (((uint64_t)t.rowA0 * PA + g.rowsA) * stepA > ps.rows_alloc || (uint64_t)t.rowB0 * P + g.rowsB > ps.rows_alloc) return TWK_HIP_E_INVALID;
 	if (g.gx > 0xFFFFu || g.gy > 0xFFFFu) return TWK_HIP_E_INVALID;
 	const bool diag = t.diag && t.rowA0 == t.rowB0;
@@ -699,10 +707,10 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	PrefixEnv pe;
 	PrefixTileStops stop_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, g.gx, &pre_grid, {PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID}};
 	if (form.prefix) {
-		if (!(two || three) || fuse || which != 0 || P != 2 || ps.h_suffix.size() != (size_t)ps.rows_alloc * PREFIX_GRID || ps.h_het.size() != c->M) return TWK_HIP_E_STATE;
+		if (!(two || three) || fuse || which != 0 || P_set != 2 || ps.h_suffix.size() != (size_t)ps.rows_alloc * PREFIX_GRID || ps.h_het.size() != c->M) return TWK_HIP_E_STATE;
 		pe.het = ps.h_het.data(); pe.hom = ps.h_hom.data(); pe.suffix = ps.h_suffix.data();
 		pe.n_variants = c->M; pe.n_samples = c->N; pe.nchunks = nchunks;
-		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.sigma = (double)c->opt.prefix_sigma / 10.0; pe.carrier = form.carrier;
+		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.sigma = (double)c->opt.prefix_sigma / 10.0; pe.carrier = form.carrier; pe.one = form.one;
 		pe.fixed_grid = c->opt.prefix_stop ? (uint32_t)c->opt.prefix_stop * PREFIX_SUB + (uint32_t)c->opt.prefix_substop : 0;
 		pre_grid.assign((size_t)g.gy * g.gx, (uint8_t)PREFIX_GRID);
 	}
@@ -729,7 +737,8 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	HIPCHK(c, hipEventRecord(e0, c->s_compute));
 	if (T) {
 		const uint32_t last_halves = c->opt.skip_pad ? count_last_halves(ps.W_live, ps.W) : 0;      // (measurement hook: 0 = contract the zero padding too)
-		const OperandRows op = form.carrier ? carrier_operand_rows(ps, t.rowA0, t.rowB0 * P) : OperandRows{ps.rows, t.rowA0 * PA, t.rowB0 * P};
+		const OperandRows op = form.one ? OperandRows{ps.carrier_rows, t.rowA0, t.rowB0}      // (both operands are carrier rows: their own base)
+		                     : form.carrier ? carrier_operand_rows(ps, t.rowA0, t.rowB0 * P) : OperandRows{ps.rows, t.rowA0 * PA, t.rowB0 * P};
 		const CountWork w = count_work(op.base, ps.W, op.rowA0, op.rowB0, s.d_tiles[which], tb, s.C, g.ldc,
 		                               c->tickets + ((&s - c->slot) * 2 + which) * 8, last_halves, s.n_out + 4, stepA);
 		HIPCHK(c, hipMemsetAsync(w.ticket, 0, 8 * 4, c->s_compute));
@@ -846,7 +855,7 @@ LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters
 	x.two_pass = pl.set2 >= 0; x.reduce = c->reduce.kind; x.sorted_u = pl.set1 == PS_SORTED_U;
 	x.phased_plain = pl.phased1 && k == PK_PHASED; x.unphased_plain = !pl.phased1 && k == PK_UNPHASED;
 	x.cut_screens = f.minR2 > 1e-6 && f.minR2 <= 1.0;
-	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix; x.opt_carrier = c->opt.carrier;
+	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix; x.opt_carrier = c->opt.carrier; x.opt_one = c->opt.one;
 	if (grant.carrier && c->opt.carrier != 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK && c->planes[pl.set1].carrier_rows) x.carrier_chunks = c->planes[pl.set1].W / KC;
 	// (stops are not combined with the measurement hooks that walk a tile's K range their own way)
 	if (grant.prefix && c->opt.prefix != 0 && c->opt.seg == 0 && c->opt.xcd_queues == 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK) x.row_chunks = c->planes[pl.set1].W / KC;
@@ -870,10 +879,10 @@ int launch_recount(twk_hip_ctx* c, int set, Slot& s) {
 	const PlaneSet& ps = c->planes[set];
 	if (ps.W_live <= 1024)
 		hipLaunchKernelGGL(k_recount_unphased<16>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.carrier ? 2 : s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.one ? 3 : s.l.form.carrier ? 2 : s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
 	else
 		hipLaunchKernelGGL(k_recount_unphased<64>, dim3(c->resident_blocks * 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, ps.W_live, s.l.cand,
-		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.carrier ? 2 : s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
+		                   (const unsigned long long*)(s.n_out + 2), s.l.cand_cap, s.n_out + 3, s.l.form.one ? 3 : s.l.form.carrier ? 2 : s.l.form.two ? 1 : 0, s.l.form.prefix ? 1 : 0);
 	HIPCHK(c, hipGetLastError());
 	return TWK_HIP_OK;
 }
@@ -1012,7 +1021,9 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	const auto tl0 = std::chrono::steady_clock::now();
 	auto tl = [&](const char* what) { if (c->opt.timeline) fprintf(stderr, "[timeline]     enqueue_tile: %s at +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); };
 	// (two products: the (HH, HQ) matrix has a row per row variant, whole tiles of 128 of them, and the candidate list lies behind it)
-	const size_t c_two_words = form.two ? (size_t)round_up(t.nA, TILE) * g.rowsB : 0;
+	// (one product: the CC matrix has a row per row variant and a column per column variant, whole tiles of 128 of either)
+	const uint32_t ldc_one = round_up(t.nB, TILE);
+	const size_t c_two_words = form.one ? (size_t)round_up(t.nA, TILE) * ldc_one : form.two ? (size_t)round_up(t.nA, TILE) * g.rowsB : 0;
 	const size_t two_list_words = form.two ? 6 * (size_t)std::max<unsigned long long>((unsigned long long)t.nA * t.nB / 128, 4096) : 0;
 	rc = ensure_slot(c, s, list_words ? list_words : std::max((size_t)g.rowsA * g.rowsB, c_two_words + two_list_words), capacity); if (rc) return rc;
 	tl("slot buffers");
@@ -1030,6 +1041,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		const unsigned long long pairs = (unsigned long long)t.nA * t.nB;
 		l.cand = s.C + c2_words;
 		l.cand_cap = std::min<unsigned long long>(room, form.keep_three ? room : std::max<unsigned long long>(pairs / 128, 4096));
+		if (c->opt.cand_cap > 0 && !form.sample) l.cand_cap = std::min<unsigned long long>(l.cand_cap, (unsigned long long)c->opt.cand_cap);      // (test hook: the launches, not their samples)
 	}
 	FusedArgs fa{};
 	const bool with_args = form.fused || form.three || form.two;      // the launch carries the screen's and the list math's parameter blocks
@@ -1051,7 +1063,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		sw.n_variants = c->M; sw.diag = (t.diag && t.rowA0 == t.rowB0) ? 1 : 0;
 		sw.col_hi = cr ? cr->d_hi : nullptr; sw.hi_a0 = cr ? cr->a0 : 0; sw.hi_b0 = cr ? cr->b0 : 0; sw.hi_n = cr ? cr->n_hi : 0;
 		sw.list_zone = cr ? cr->list_zone : 0; sw.probe_zone = cr ? cr->probe_zone : 0;
-		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2; sw.carrier = form.carrier ? 1u : 0u;
+		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2; sw.carrier = form.one ? 2u : form.carrier ? 1u : 0u;
 		{	// slots a wave reserves at a time: what it cannot use is lost to the list, so at most an eighth of the list's
 			// capacity may be tied up in the waves' windows (small tiles: 0, i.e. one atomic per wave and tile)
 			const unsigned long long per_wave = l.cand_cap / (8ull * c->resident_blocks * (COUNT_THREADS / 64));
@@ -1073,7 +1085,11 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	}
 	if (with_args) {
 		if (l.d_stats_dev) {      // (else: no tiles, no launch, no candidates)
-			if (form.two) {                // (HH, HQ) matrix -> screen with S bounded from the margins -> candidates -> their four products -> the list math
+			if (form.one) {                // CC matrix -> screen with S >= 0 and S + HH bounded from CC and the margins -> candidates -> their four products -> the list math
+				hipLaunchKernelGGL(k_screen1_pairs, dim3((t.nB + SCREEN3_THREADS - 1) / SCREEN3_THREADS, t.nA), dim3(SCREEN3_THREADS), 0, c->s_compute, l.d_screen_dev,
+				                   (const StatsParams*)l.d_stats_dev, (const uint32_t*)s.C, ldc_one);
+				HIPCHK(c, hipGetLastError());
+			} else if (form.two) {         // (HH, HQ) matrix -> screen with S bounded from the margins -> candidates -> their four products -> the list math
 				hipLaunchKernelGGL(k_screen2_pairs, dim3((t.nB + SCREEN3_THREADS - 1) / SCREEN3_THREADS, t.nA), dim3(SCREEN3_THREADS), 0, c->s_compute, l.d_screen_dev,
 				                   (const StatsParams*)l.d_stats_dev, (const uint32_t*)s.C, g.ldc);
 				HIPCHK(c, hipGetLastError());
@@ -1205,7 +1221,7 @@ void watch_launch(twk_hip_ctx* c, const Slot& s, float ms, const twk_hip_tile_de
 	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three || s.l.form.two) ? s.h_n_out[2] : 0;
 	st.shader_mhz = s.h_n_out[5] ? (double)s.h_n_out[4] / (double)s.h_n_out[5] * 100.0 : 0.0;
 	st.words_per_row = c->planes[s.l.plane_set].W_live;
-	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full; st.carrier = s.l.form.carrier ? 1u : 0u;
+	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full; st.carrier = s.l.form.carrier ? 1u : 0u; st.one = s.l.form.one ? 1u : 0u;
 	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.two ? 5u : s.l.form.three_plain() ? 1u : 0u);
 	unsigned long long lo = ~0ull, hi = 0;
 	for (int x = 0; x < 8; ++x) if (s.h_n_out[8 + x]) { lo = std::min(lo, s.h_n_out[8 + x]); hi = std::max(hi, s.h_n_out[8 + x]); }
@@ -1350,11 +1366,14 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) s.l.too_rich = true;      // (the launch's owner folds it into the call: CallForms::gave_up)
 	}
 	if (s.l.form.two) {
-		c->timing.two_launches += 1; c->timing.carrier_launches += s.l.form.carrier ? 1 : 0; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
+		c->timing.two_launches += 1; c->timing.carrier_launches += s.l.form.carrier ? 1 : 0; c->timing.one_launches += s.l.form.one ? 1 : 0; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
 		if (s.h_n_out[3]) {      // as above: the recount is the contraction's proof
-			snprintf(c->err, sizeof(c->err), "two-product contraction: %llu candidates whose %s differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], s.l.form.carrier ? "(CH, CQ)" : "(HH, HQ)", t.rowA0, t.nA, t.rowB0, t.nB);
+			snprintf(c->err, sizeof(c->err), "two-product contraction: %llu candidates whose %s differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], s.l.form.one ? "CC" : s.l.form.carrier ? "(CH, CQ)" : "(HH, HQ)", t.rowA0, t.nA, t.rowB0, t.nB);
 			return TWK_HIP_E_DEVICE;
 		}
+		// a one-product launch with more candidates than its sample was allowed (1 pair in 256): its list held, so its records stand, but the wider
+		// screen is not paying here - the launches behind it keep two products (CallForms::gave_up takes `one` from the call and nothing else)
+		if (s.l.form.one && c->opt.one != 2 && s.h_n_out[2] > std::max<unsigned long long>(pairs_in_tile(c, t) / 256, 4096)) s.l.too_rich = true;
 	}
 	float ms_all = 0;
 	if (s.l.form.two_pass) {
@@ -1519,7 +1538,7 @@ int run_tile_sync(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const tw
                   unsigned long long capacity, unsigned long long* n_out, const Deliver& to, const ColRange* cr = nullptr) {
 	Slot& s = c->slot[SYNC_SLOT];
 	for (;;) {
-		FormGrant grant = calls.grant(given.three, given.two, false, given.carrier);      // (a two-product tile redone over whole rows keeps its row operand)
+		FormGrant grant = calls.grant(given.three, given.two, false, given.carrier, given.one);      // (a two-product tile redone over whole rows keeps its row operand - and its one product)
 		grant.fused = grant.fused && given.fused; grant.sample = given.sample;
 		int rc = enqueue_tile(c, mode, t, f, grant, s, capacity, cr); if (rc) return rc;
 		rc = finish_tile(c, s, t, n_out, to);
@@ -2370,6 +2389,8 @@ struct RegionRun {
 	uint64_t tot_pairs = 0, tot_recs = 0;
 	std::vector<char> want_three;             // per launch: the three-product form may be used (decide_three_by_samples)
 	std::vector<char> want_two;               // ... and the two-product form (the two-product walk: launches in front of plan.two_end whose sample was poor in candidates)
+	uint32_t one_refused = 0;                 // samples in the one-product form that were too rich in candidates (the "timeline" log reports them)
+	std::vector<char> want_one;               // ... and one product a pair (the launches the planner marked: their own sample in that form, or option one = 2)
 	std::vector<char> want_prefix;            // ... and stops for its tiles (the prefix contraction, DESIGN 3.1c: the launch's sample ran with them and was poor in candidates)
 	// the prefix applies to the launches of the two-product walk on rows of more than FUSED_MAX_CHUNKS chunks (ld_form.h decide_form holds the rest)
 	bool prefix_eligible() const { return two_walk() && c->opt.prefix != 0 && calls.prefix && c->planes[PS_SORTED_U].W / KC > FUSED_MAX_CHUNKS && !c->planes[PS_SORTED_U].h_suffix.empty(); }
@@ -2380,7 +2401,8 @@ struct RegionRun {
 	// What launch i of the plan may be: the call's forms, three and two products as the launch's own sample decided.  A tile redone synchronously is not
 	// bound by a sample: it may be whatever the call still allows but two products (redo_grant).
 	// (env.carrier: the region's two-product launches contract the carrier plane - region_impl holds carrier rows for every row in front of the cut)
-	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0, want_prefix[i] != 0, env.carrier); }
+	// (want_one: the planner put the launch in front of its rows' one_end - twk_hip_tile_desc::one - and its sample in that form was poor in candidates)
+	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0, want_prefix[i] != 0, env.carrier, want_one[i] != 0); }
 	FormGrant redo_grant() const { return calls.grant(true, false); }
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, CallForms& calls_, twk_hip_record_sink sink_, void* user_)
@@ -2478,7 +2500,9 @@ struct RegionRun {
 	int decide_three_by_samples() {
 		const std::vector<twk_hip_tile_desc>& mine = plan.mine;
 		const size_t n = mine.size();
-		want_three.assign(n, 1); want_two.assign(n, 0); want_prefix.assign(n, 0);
+		want_three.assign(n, 1); want_two.assign(n, 0); want_prefix.assign(n, 0); want_one.assign(n, 0);
+		const bool one_ok = env.one && env.carrier && c->opt.one != 0 && calls.one;
+		if (one_ok) for (size_t i = 0; i < n; ++i) want_one[i] = (mine[i].one && two_eligible(mine[i])) ? 1 : 0;      // (taken back below where a launch's sample says so)
 		if (c->opt.two == 2) for (size_t i = 0; i < n; ++i) want_two[i] = two_eligible(mine[i]) ? 1 : 0;
 		const bool prefix_ok = prefix_eligible();
 		if (prefix_ok && c->opt.prefix == 2) want_prefix.assign(n, 1);
@@ -2502,13 +2526,16 @@ struct RegionRun {
 			else { const uint32_t wv = std::min<uint32_t>(384, t0.nB); st.rowB0 = t0.rowB0 + (t0.nB - wv) / 2; st.nB = wv; st.diag = 0; }
 			unsigned long long cand = 0;
 			const unsigned long long sample_pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
+			// (one: the sample of a launch the planner marked for one product runs in that form first; refused - more than 1 candidate in 256 - the launch is
+			// sampled again as any other launch in front of the cut)
+			bool one = want_one[pick] != 0;
 			auto sample = [&](bool two, bool prefix = false) -> int {
 				const twk_hip_timing keep_timing = c->timing;
 				const size_t keep_ring = c->launch_ring.size(); const uint64_t keep_seen = c->launches_seen;
 				Slot& ss = c->slot[SYNC_SLOT];
 				unsigned long long nrec = 0;
 				// (three products granted: a sample is only taken where the call allows them; and its own overflow or richness decides its launch, not the call)
-				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true, prefix && calls.prefix, two && calls.two && env.carrier}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
+				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true, prefix && calls.prefix, two && calls.two && env.carrier, one && two && calls.two && calls.one && env.carrier}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
 				if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
 				cand = ss.h_n_out[2];
 				c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
@@ -2519,21 +2546,28 @@ struct RegionRun {
 			// The prefix: the same samples, first with the stops the launch would use - at most 1 candidate in 256 and the launch takes the form with
 			// its stops; otherwise the ladder below decides without them.
 			const bool try_two = (c->opt.two == 1 && two_eligible(t0)) || (c->opt.two == 2 && want_two[pick]);
-			if (prefix_ok && c->opt.prefix == 1) {
-				const int rcp = sample(try_two, true);
-				if (rcp != TWK_HIP_OK && rcp != TWK_HIP_E_OVERFLOW) return rcp;
-				mark("prefix sample of launch: candidates", pick, cand);
-				if (rcp == TWK_HIP_OK && cand * 256 <= sample_pairs) {
-					for (size_t i = i0; i < std::min(n, i0 + step); ++i) { want_prefix[i] = 1; if (try_two && two_eligible(mine[i])) want_two[i] = 1; }
-					continue;
+			bool decided = false;
+			for (;;) {      // (at most twice: with one product where the launch is marked for it, then without)
+				if (prefix_ok && c->opt.prefix == 1) {
+					const int rcp = sample(try_two, true);
+					if (rcp != TWK_HIP_OK && rcp != TWK_HIP_E_OVERFLOW) return rcp;
+					mark(one ? "one-product prefix sample of launch: candidates" : "prefix sample of launch: candidates", pick, cand);
+					if (rcp == TWK_HIP_OK && cand * 256 <= sample_pairs) {
+						for (size_t i = i0; i < std::min(n, i0 + step); ++i) { want_prefix[i] = 1; if (try_two && two_eligible(mine[i])) want_two[i] = 1; }
+						decided = true; break;
+					}
 				}
+				if (c->opt.two == 1 && two_eligible(t0)) {
+					const int rc2 = sample(true);
+					if (rc2 != TWK_HIP_OK && rc2 != TWK_HIP_E_OVERFLOW) return rc2;
+					mark(one ? "one-product sample of launch: candidates" : "two-product sample of launch: candidates", pick, cand);
+					if (rc2 == TWK_HIP_OK && cand * 256 <= sample_pairs) { want_two[pick] = 1; decided = true; break; }      // (three products stay wanted: what a launch falls back to)
+				}
+				if (!(one && c->opt.one == 1)) break;
+				one = false; ++one_refused;
+				for (size_t i = i0; i < std::min(n, i0 + step); ++i) want_one[i] = 0;
 			}
-			if (c->opt.two == 1 && two_eligible(t0)) {
-				const int rc2 = sample(true);
-				if (rc2 != TWK_HIP_OK && rc2 != TWK_HIP_E_OVERFLOW) return rc2;
-				mark("two-product sample of launch: candidates", pick, cand);
-				if (rc2 == TWK_HIP_OK && cand * 256 <= sample_pairs) { want_two[pick] = 1; continue; }      // (three products stay wanted: what a launch falls back to)
-			}
+			if (decided) continue;
 			const int rc = sample(false);
 			const bool dense = rc == TWK_HIP_E_OVERFLOW || (rc == TWK_HIP_OK && cand * dense_one_in > sample_pairs);
 			if (rc != TWK_HIP_OK && rc != TWK_HIP_E_OVERFLOW) return rc;
@@ -2661,6 +2695,8 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, const CallF
 		env.het = ps.h_het.data(); env.hom = ps.h_hom.data();
 		// the carrier plane as the row operand: asked for here, granted by region_impl once the rows in front of the cut it gives are there
 		env.carrier = c->opt.carrier != 0 && ps.W / KC > FUSED_MAX_CHUNKS;
+		// ... and one product a pair in front of a row block's one_end: likewise, once carrier rows for those launches' columns are there too
+		env.one = env.carrier && c->opt.one != 0 && calls.one && f->minR2 > 1e-6 && f->minR2 <= 1.0; env.one_rows = (uint32_t)c->opt.one_rows;
 		// the prefix contraction: the rows' suffix margins, the first time a call may take the form (no room for the table: the call takes no stops)
 		if (c->opt.prefix != 0 && calls.prefix && f->minR2 > 1e-6 && f->minR2 <= 1.0 && ps.W / KC > FUSED_MAX_CHUNKS) {
 			const int rc = ensure_suffix(c, PS_SORTED_U);
@@ -2705,13 +2741,26 @@ static int region_impl(twk_hip_ctx* c, const RegionArgs& a, CallForms& calls) {
 		// launch of the walk), built now if they are not there.  No room for them: the plan of the H form, as before.
 		PlaneSet& ps = c->planes[PS_SORTED_U];
 		const uint32_t walk_end = c->opt.two == 2 ? g.nA : plan.two_end, need = plan.r0 < std::min(walk_end, plan.r1) ? g.a0 + std::min(walk_end, plan.r1) : 0;
+		// ... and for every column variant of this shard's one-product launches (at r2 >= 0.1 on a flat frequency law: nearly every variant of the set, one
+		// more plane row each).  No room for those: the plan without one-product launches, and the rows in front of the cut as before.
+		uint32_t need_one = 0;
+		for (const auto& t : plan.mine) if (t.one) need_one = std::max(need_one, t.rowB0 + t.nB);
+		if (need && need_one > need && !(ps.carrier_rows && ps.carrier_n >= need_one)) {
+			rc = ensure_carrier(c, PS_SORTED_U, need_one);
+			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; }
+			else if (rc) return rc;
+		}
+		if (env.one && (!need || (need_one > need && !(ps.carrier_rows && ps.carrier_n >= need_one)))) {
+			env.one = false;
+			plan_region(env, g, plan);
+		}
 		if (need) {
 			rc = ensure_carrier(c, PS_SORTED_U, need);
 			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; }
 			else if (rc) return rc;
 		}
 		if (!carrier_operand(c->opt.carrier, ps.W / KC, ps.carrier_rows ? ps.carrier_n : 0, need)) {
-			env.carrier = false;
+			env.carrier = env.one = false;
 			plan_region(env, g, plan);
 		}
 	}
@@ -2721,6 +2770,7 @@ static int region_impl(twk_hip_ctx* c, const RegionArgs& a, CallForms& calls) {
 	rc = run.run_zone_passes(); if (rc) return rc;
 	run.mark("tiles listed", plan.mine.size());
 	rc = run.decide_three_by_samples(); if (rc) return rc;
+	if (env.one) run.mark("one-product samples refused", run.one_refused);
 	rc = run.run_pipeline(); if (rc) return rc;
 	if (plan.windowed) run.tot_pairs = plan.pairs;      // screen: every pair of the band is decided; window: the pairs inside it, the ones the math evaluates
 	if (a.n_pairs) *a.n_pairs = run.tot_pairs;
@@ -3443,6 +3493,14 @@ int twk_hip_plan_region_two_operand(const twk_hip_plan_env* pe, const twk_hip_va
                                     uint32_t tile_variants, int32_t window, uint32_t l_window,
                                     twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                                     uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end) {
+	return twk_hip_plan_region_two_form(pe, meta, popc, het, hom, two_margin, carrier, 0, 0, n_variants, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window,
+	                                    tiles, capacity, n_tiles, n_band_launches, row_begin, row_end, n_pairs, lo, hi, two_end);
+}
+int twk_hip_plan_region_two_form(const twk_hip_plan_env* pe, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                                 int32_t carrier, int32_t one, uint32_t one_rows, uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                                 uint32_t tile_variants, int32_t window, uint32_t l_window,
+                                 twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                                 uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end) {
 	if ((het != nullptr) != (hom != nullptr)) return TWK_HIP_E_INVALID;
 	if (!pe || !meta || !n_tiles || (capacity && !tiles) || n_parts == 0 || part >= n_parts) return TWK_HIP_E_INVALID;
 	if (nA == 0 || nB == 0 || (uint64_t)a0 + nA > n_variants || (uint64_t)b0 + nB > n_variants) return TWK_HIP_E_INVALID;
@@ -3455,6 +3513,7 @@ int twk_hip_plan_region_two_operand(const twk_hip_plan_env* pe, const twk_hip_va
 	env.meta = meta; env.ids = nullptr; env.popc = popc;
 	env.het = het; env.hom = hom; if (two_margin > 0) env.two_margin = two_margin;
 	env.carrier = carrier != 0 && het != nullptr;
+	env.one = env.carrier && one != 0 && pe->minR2 > 1e-6 && pe->minR2 <= 1.0; env.one_rows = one_rows;
 	env.band_launch = pe->band_launch != 0; env.band_reverse = pe->band_reverse != 0; env.band_work_log2 = pe->band_work_log2; env.band_max_launches = std::max<long long>(pe->band_max_launches, 1);
 	const PlanGeom g{a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window};
 	RegionPlan plan;

@@ -179,12 +179,47 @@ void check_carrier() {
 	for (const auto& k : CASES) { ++g_cases; CHECK(carrier_operand(k.opt, k.chunks, k.have, k.need) == k.carrier, "carrier_operand(%lld, %u, %u, %u): %s", k.opt, k.chunks, k.have, k.need, k.what); }
 }
 
+// One product a pair: an attribute of a carrier launch - the carrier rows on both axes - granted by the walk's owner launch by launch.
+void check_one() {
+	// decide_form: only with the grant, the option and a launch that takes the carrier form; it changes nothing else
+	for (const FormFacts& x0 : all_facts()) for (const uint32_t cc : {FUSED_MAX_CHUNKS, FUSED_MAX_CHUNKS + 1}) for (int oo = 0; oo < 3; ++oo) for (int go = 0; go < 2; ++go) for (int gc = 0; gc < 2; ++gc)
+	for (int gt = 0; gt < 2; ++gt) for (int gp = 0; gp < 2; ++gp) {
+		FormFacts x = x0; x.carrier_chunks = cc; x.row_chunks = cc; x.opt_one = oo;
+		FormGrant g; g.two = gt != 0; g.carrier = gc != 0; g.prefix = gp != 0; g.one = go != 0;
+		const LaunchForm lf = decide_form(x, g);
+		FormGrant g0 = g; g0.one = false;
+		const LaunchForm base = decide_form(x, g0);
+		++g_cases;
+		CHECK(same(lf, base) && lf.prefix == base.prefix && lf.carrier == base.carrier, "the one-product grant changed the form");
+		CHECK(!base.one, "a one-product launch without its grant");
+		CHECK(lf.one == (go && oo != 0 && lf.carrier), "one: grant %d option %d carrier %d", go, oo, (int)lf.carrier);
+		CHECK(!lf.one || (lf.two && lf.carrier && !lf.three && !lf.fused && !lf.two_pass && x.sorted_u), "a one-product launch that is no carrier launch of the sorted walk");
+	}
+	// the ladder: a one-product launch whose list overflowed, or that was too rich, is redone in the carrier two-product form and the call gives up
+	// `one` and nothing else; with stops, the stops go first
+	FormGrant all{true, true, true, false}; all.carrier = true; all.one = true;
+	LaunchForm one; one.unphased = true; one.two = true; one.carrier = true; one.one = true;
+	{ const FormGrant g = step_down(one, all); CHECK(g.fused && g.three && g.two && g.carrier && !g.one, "below a one-product launch: the carrier two-product form"); }
+	for (int ob = 1; ob < 4; ++ob) { CallForms c; c.gave_up(one, all, (ob & 1) != 0, (ob & 2) != 0); CHECK(c.fused && c.three && c.two && c.prefix && !c.one, "a one-product launch overflowed or was too rich: the call gives up one product only");
+	                                 CHECK(c.grant(true, true, false, true, true).carrier && !c.grant(true, true, false, true, true).one, "... and grants the carrier form still"); }
+	{ CallForms c; c.gave_up(one, all, false, false); CHECK(c.one && c.grant(true, true, false, true, true).one, "a one-product launch went well"); }
+	{ FormGrant ng = all; ng.one = false; LaunchForm lf = one; CallForms c; c.gave_up(lf, ng, true, false); CHECK(c.one, "one product was not granted: not taken from the call"); }
+	{ LaunchForm lf = one; lf.prefix = true; FormGrant wp = all; wp.prefix = true; const FormGrant g = step_down(lf, wp); CHECK(!g.prefix && g.two && g.carrier && g.one, "below a one-product prefix launch: whole rows, same form");
+	  CallForms c; c.gave_up(lf, wp, true, false); CHECK(c.two && c.one && !c.prefix, "a one-product prefix launch's list overflowed: the stops go"); }
+	{ LaunchForm two = one; two.one = false; FormGrant g2 = all; g2.one = false; const FormGrant g = step_down(two, g2); CHECK(!g.two && !g.carrier && !g.one && g.three, "below a carrier launch: three products, as before");
+	  CallForms c; c.gave_up(two, all, true, false); CHECK(!c.two && !c.grant(true, true, false, true, true).one, "no two-product launches: none with one product either"); }
+	CHECK(!CallForms().grant(true, true, false, false, true).one && !CallForms().grant(true, false, false, true, true).one && !CallForms().grant(true, true, false, true).one, "one-product grants follow the carrier grant");
+	g_cases += 10;
+	printf("form-check: one-product attribute: granted with the carrier form only, given up alone\n");
+}
+
 }  // namespace
 
 int main() {
 	check_decide_form();
 	check_gave_up();
 	check_carrier();
+	check_one();
 	printf("form-check: %ld cases, %d bad\n", g_cases, g_bad_checks);
 	return g_bad_checks ? 1 : 0;
 }

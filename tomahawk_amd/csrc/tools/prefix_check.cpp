@@ -20,6 +20,11 @@
 //      margin 0.95 (the planner before the fine grid, restated here; the reports of 3. are this setting's), 128 points with 0.95, 128 points with
 //      0.95 and six standard deviations (the default), 128 points with 0.98 - count work against whole H-plane rows, against the first setting,
 //      and the host time of the stops.
+//   6. The one-product launches of the carrier form (PlanEnv::one; csrc/hip/ld_plan.h plan_one_tiles), every line under the prefix "one product:":
+//      the prefix screen of such a launch (screen1c_prefix_keeps on CC_pre) keeps every pair the carrier prefix screen keeps - part of 1. - and the
+//      planner on the headline's law with the rows in front of the cut in blocks of S and of S / 2 variants: launches by form, and the count work
+//      with stops against the carrier form's with stops at the default setting (a one-product tile costs what a two-product tile costs and holds
+//      twice the pairs).
 // usage: prefix_check [--no-planner]
 #include <cinttypes>
 #include <cmath>
@@ -41,7 +46,7 @@ int g_bad_checks = 0;
 
 // ---- 1. the screens ----------------------------------------------------------------------------------------------------------
 constexpr uint32_t MAX_PART = 4;
-uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_kept2cp = 0, g_violations = 0;
+uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_kept2cp = 0, g_kept1cp = 0, g_violations = 0;
 std::vector<std::vector<uint32_t>> g_tables;          // every 3 x 3 table of 0 .. MAX_PART samples: c[3 a + b]
 
 void each_table(uint32_t c[9], int cell, uint32_t left) {
@@ -94,7 +99,14 @@ void check_pair(const uint32_t* p, const uint32_t* x) {
 			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products on the whole rows %d, carrier prefix %d, H prefix %d",
 			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3, (int)k2cp, (int)k2p);
 		}
-		++g_tests; g_kept3 += k3; g_kept3p += k3p; g_kept2p += k2p; g_kept2cp += k2cp;
+		// one product over the prefix: CC_pre = CH_pre + CQ_pre, the lower test at S >= 0 - every pair the carrier prefix screen keeps
+		const bool k1cp = screen1c_prefix_keeps(m, sx, p[4] + p[7] + p[5] + p[8], two_n, cut);
+		if ((k3 && !k1cp) || (k2cp && !k1cp)) {
+			++g_violations;
+			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products on the whole rows %d, carrier prefix %d, one-product prefix %d",
+			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3, (int)k2cp, (int)k1cp);
+		}
+		++g_tests; g_kept3 += k3; g_kept3p += k3p; g_kept2p += k2p; g_kept2cp += k2cp; g_kept1cp += k1cp;
 	}
 }
 int check_screens() {
@@ -113,6 +125,7 @@ int check_screens() {
 			CHECK(screen3_prefix_keeps(m, none, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut) == screen3_keeps(m, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut), "empty suffix, three");
 			CHECK(screen2_prefix_keeps(m, none, c[4], c[5], 2.0 * n, cut) == screen2_keeps(m, c[4], c[5], 2.0 * n, cut), "empty suffix, two");
 			CHECK(screen2c_prefix_keeps(m, none, c[4] + c[7], c[5] + c[8], 2.0 * n, cut) == screen2c_keeps(m, c[4] + c[7], c[5] + c[8], 2.0 * n, cut), "empty suffix, carrier");
+			CHECK(screen1c_prefix_keeps(m, none, c[4] + c[7] + c[5] + c[8], 2.0 * n, cut) == screen1c_keeps(m, c[4] + c[7] + c[5] + c[8], 2.0 * n, cut), "empty suffix, one product");
 		}
 	}
 	return g_bad_checks != before;
@@ -214,7 +227,7 @@ struct CoarseTileStops {
 struct Setting { bool fine; double margin, sigma; };
 constexpr Setting HEAD_SETTING{false, 0.95, 0.0};
 double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t h_two_end = 0, const Setting& st = HEAD_SETTING, bool quiet = false,
-                    double* work_whole = nullptr, double* stops_ms = nullptr, std::vector<double>* fractions = nullptr) {
+                    double* work_whole = nullptr, double* stops_ms = nullptr, std::vector<double>* fractions = nullptr, int one_rows = -1, uint32_t* launches = nullptr) {
 	const char* tag = carrier ? "carrier form: " : "planner: ";
 	const uint32_t M = 50000, N = 1000000, nchunks = (N + 1023) / 1024;
 	const double minR2 = 0.1, cut = minR2 * (1.0 - 1e-6), two_cost = 0.66;
@@ -229,6 +242,7 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		}
 	}
 	PlanEnv env; env.n_samples = N; env.Pmax = 2; env.nchunks = nchunks; env.minR2 = minR2; env.phased_math = false; env.het = het.data(); env.hom = hom.data(); env.carrier = carrier;
+	env.one = carrier && one_rows >= 0; env.one_rows = one_rows > 0 ? (uint32_t)one_rows : 0;      // (section 6: the one-product launches of the carrier form)
 	const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
 	RegionPlan plan;
 	plan_region(env, g, plan);
@@ -242,16 +256,20 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 	for (size_t i = 0; i < plan.mine.size(); ++i) {
 		const twk_hip_tile_desc& t = plan.mine[i];
 		const bool two = t.rowA0 + t.nA <= plan.two_end, diag = t.diag && t.rowA0 == t.rowB0;
-		const Geometry geo = tile_geometry(2, t, two ? 1 : 0);
+		const bool one = two && t.one != 0;
+		const int P = one ? 1 : 2;
+		pe.one = one;
+		if (launches) { ++launches[0]; launches[1] += one ? 1 : 0; launches[2] += two ? 1 : 0; }
+		const Geometry geo = tile_geometry(P, t, two ? 1 : 0);
 		std::vector<uint8_t> grid((size_t)geo.gy * geo.gx, (uint8_t)PREFIX_GRID);
 		std::vector<uint32_t> stops;
 		const PrefixTileStops stop_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, geo.gx, &grid, {PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID}};
 		const CoarseTileStops coarse_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, {PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE}};
 		const auto t0 = std::chrono::steady_clock::now();
-		const CountTable tb = st.fine ? build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &stop_of, &stops)
+		const CountTable tb = st.fine ? build_count_table(t, P, diag, nullptr, nchunks, cs, two ? 1 : 0, &stop_of, &stops)
 		                              : build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &coarse_of, &stops);
 		const auto t1 = std::chrono::steady_clock::now();
-		const CountTable plain = build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0);
+		const CountTable plain = build_count_table(t, P, diag, nullptr, nchunks, cs, two ? 1 : 0);
 		const auto t2 = std::chrono::steady_clock::now();
 		host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count() - std::chrono::duration<double, std::milli>(t2 - t1).count();
 		uint64_t done = 0; uint32_t lo = nchunks, hi = 0;
@@ -262,7 +280,8 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		if (!quiet) printf(carrier ? "  carrier form: step %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n" :
 		       "  launch %2zu  %s  rows %5u+%-5u cols %5u+%-5u  %6u tiles  stops %3u .. %3u chunks  contracted %.4f of the rows\n", i, two ? "two  " : "three", t.rowA0, t.nA, t.rowB0, t.nB,
 		       tb.n_tiles(), lo, hi, full ? (double)done / (double)full : 0.0);
-		// (a two-product tile holds 128 x 64 variant pairs, a three-product tile 64 x 64: per tile and chunk twice the pairs at two_cost each)
+		// (a two-product tile holds 128 x 64 variant pairs, a three-product tile 64 x 64: per tile and chunk twice the pairs at two_cost each; a one-product
+		// tile holds 128 x 128 and runs the same kernel over the same 128 x 128 rows as a two-product tile: the same cost per tile and chunk)
 		const double w = two ? 2.0 * two_cost : 1.0;
 		work_full += w * (double)full; work_done += w * (double)done;
 		(two ? sum2_full : sum3_full) += (double)full; (two ? sum2_done : sum3_done) += (double)done;
@@ -362,6 +381,23 @@ void report_settings() {
 	}
 }
 
+// ---- 6. the one-product launches ---------------------------------------------------------------------------------------------------
+void report_one_product() {
+	const Setting dflt{true, 0.95, 6.0};
+	uint32_t c_end = 0;
+	const double c_work = play_planner(true, &c_end, 0, 0, dflt, true);
+	double best = 0;
+	for (const int rows : {8192, 4096}) {
+		uint32_t end = 0, n[3] = {0, 0, 0};
+		const double w = play_planner(true, &end, 0, 0, dflt, true, nullptr, nullptr, nullptr, rows, n);
+		printf("one product: rows in front of the cut %u in blocks of %d (%s): %u launches, %u of them one-product and %u two-product in front of the cut; count work with stops %.4f of the carrier form's with stops\n",
+		       end, rows, rows == 8192 ? "S" : "S / 2", n[0], n[1], n[2] - n[1], w / c_work);
+		CHECK(end == c_end && n[1] > 0 && w < c_work, "blocks of %d: cut %u against %u, %u one-product launches, work %g against %g", rows, end, c_end, n[1], w, c_work);
+		if (rows == 4096) best = w;
+	}
+	printf("one product: prediction new / parent %.4f (blocks of S / 2, the default)\n", best / c_work);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -382,6 +418,8 @@ int main(int argc, char** argv) {
 	}
 	check_grid();
 	if (planner) report_settings();
+	printf("prefix-check: the one-product prefix screen keeps %" PRIu64 " (the carrier plane's %" PRIu64 " <= it)\n", g_kept1cp, g_kept2cp);
+	if (planner) report_one_product();
 	printf("prefix-check: %s\n", (bad_screen || bad_tables || g_bad_checks) ? "FAILED" : "ok");
 	return (bad_screen || bad_tables || g_bad_checks) ? 1 : 0;
 }

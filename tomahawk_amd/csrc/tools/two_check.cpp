@@ -3,7 +3,9 @@
 //      ulp below and one ulp above the values at which the three-product screen's own decision turns: the true S lies in [S_lo, S_hi], and
 //      the two-product screen keeps every pair the three-product screen keeps.  The carrier form (the row variant's H | Q as the row operand:
 //      CH = HH + QH, CQ = HQ + QQ): the true S and T = S + HH lie in [CQ, .] and [., CH + CQ + min(qA, qB)], and
-//      kept(three) <= kept(carrier) <= kept(H) pair by pair.
+//      kept(three) <= kept(carrier) <= kept(H) pair by pair.  The one-product form (the carrier rows of both variants: CC = CH + CQ, lower test at
+//      S >= 0): kept(carrier) <= kept(one) pair by pair, and screen1c_lower_ok is the lower half of screen1c_keeps.
+//   1b. plan_one_end (csrc/hip/ld_plan.h) on random sorted margins: the exact boundary of screen1c_lower_ok along a row's columns.
 //   2. The work table of a launch whose row axis has one plane row per variant and whose column axis two (build_count_table with PA = 1,
 //      csrc/hip/ld_count_table.h): tiles of 128 row variants x 64 column variants against a naive restatement - a tile is wanted when one of
 //      its variant pairs is (diagonal super-tiles: a pair above the diagonal) - units that partition every tile's K range, and the recorded
@@ -20,6 +22,7 @@
 #include <vector>
 #include "../hip/ld_count_table.h"
 #include "../hip/ld_two_screen.h"
+#include "../hip/ld_plan.h"
 
 using namespace twk;
 
@@ -31,7 +34,7 @@ int g_bad_checks = 0;
 // ---- 1. the screen ---------------------------------------------------------------------------------------------------------
 // c[3 a + b]: samples with genotype a (0 ref/ref, 1 het, 2 alt/alt) at the row variant and b at the column variant
 constexpr int MAX_N = 7;
-uint64_t g_tables = 0, g_kept3 = 0, g_kept2 = 0, g_kept2c = 0;
+uint64_t g_tables = 0, g_kept3 = 0, g_kept2 = 0, g_kept2c = 0, g_kept1c = 0;
 
 void check_table(const uint32_t c[9], uint32_t n) {
 	const ScreenMargins m{c[3] + c[4] + c[5], c[6] + c[7] + c[8], c[1] + c[4] + c[7], c[2] + c[5] + c[8]};
@@ -59,7 +62,14 @@ void check_table(const uint32_t c[9], uint32_t n) {
 		const bool k3 = screen3_keeps(m, hh, s, two_n, cut), k2 = screen2_keeps(m, hh, hq, two_n, cut), k2c = screen2c_keeps(m, ch, cq, two_n, cut);
 		CHECK((!k3 || k2c) && (!k2c || k2), "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three %d, carrier %d, H %d", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2, (int)k3, (int)k2c, (int)k2);
 		CHECK(!k3 || k2, "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products keep it, two drop it", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2);
-		++g_tables; g_kept3 += k3; g_kept2 += k2; g_kept2c += k2c;
+		// one product: CC = CH + CQ and the lower test at S >= 0 - every pair the carrier screen keeps, hence every pair three products keep
+		const bool k1c = screen1c_keeps(m, ch + cq, two_n, cut);
+		CHECK(!k2c || k1c, "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: carrier keeps it, one product drops it", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2);
+		CHECK(!k3 || k1c, "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products keep it, one drops it", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2);
+		// the lower half alone: where it fails the screen keeps the pair whatever CC; where it holds the upper half decides
+		CHECK(screen1c_lower_ok(m, two_n, cut) || k1c, "lower test fails and the pair is dropped");
+		CHECK(!screen1c_lower_ok(m, two_n, cut) || k1c == screen_upper_keeps(m, (double)(ch + cq) + screen2c_slack(m), two_n, cut), "upper half disagrees with the screen");
+		++g_tables; g_kept3 += k3; g_kept2 += k2; g_kept2c += k2c; g_kept1c += k1c;
 	}
 }
 void each_table(uint32_t c[9], int cell, uint32_t left, uint32_t n) {
@@ -86,6 +96,40 @@ int check_screen() {
 				CHECK((!k3c || k2c) && (!k2c || k2h), "carrier: n %u pa %g pb %g S %u at %g: three %d, carrier %d, H %d", n, pa, pb, sc, minR2, (int)k3c, (int)k2c, (int)k2h);
 			}
 		}
+	return g_bad_checks != before;
+}
+
+// ---- 1b. one_end ---------------------------------------------------------------------------------------------------------------
+// Random margins in order of allele count (frequencies from a flat law, Hardy-Weinberg with binomial noise of our own making): plan_one_end of a
+// row is the first column behind it at which screen1c_lower_ok fails - every column in front of it passes, for this row and for every row before it.
+uint64_t g_one_rows = 0, g_one_pairs = 0;
+int check_one_end() {
+	const int before = g_bad_checks;
+	uint64_t rng = 0x9E3779B97F4A7C15ull;
+	auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+	for (const uint32_t n : {140000u, 1000000u}) for (const double minR2 : {0.05, 0.1, 0.3}) for (const double p_lo : {0.01, 0.05}) {
+		const uint32_t M = 900;
+		std::vector<std::pair<uint64_t, std::pair<uint32_t, uint32_t>>> v(M);
+		for (auto& x : v) {
+			const double pf = p_lo + (0.5 - p_lo) * (double)(next() % 1000003) / 1000003.0;
+			const uint32_t q = (uint32_t)(pf * pf * n * (0.98 + 0.04 * (double)(next() % 1001) / 1000.0)), h = (uint32_t)(2 * pf * (1 - pf) * n * (0.98 + 0.04 * (double)(next() % 1001) / 1000.0));
+			x = {(uint64_t)h + 2ull * q, {h, q}};
+		}
+		std::sort(v.begin(), v.end());
+		std::vector<uint32_t> het(M), hom(M);
+		for (uint32_t i = 0; i < M; ++i) { het[i] = v[i].second.first; hom[i] = v[i].second.second; }
+		PlanEnv e; e.n_samples = n; e.minR2 = minR2; e.het = het.data(); e.hom = hom.data();
+		const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
+		for (uint32_t row = 0; row + 1 < M; row += 37) {
+			const uint32_t end = plan_one_end(e, g, row);
+			CHECK(end > row && end <= M, "row %u: one_end %u", row, end);
+			// (a row whose test fails at once has no column in front of its one_end, and says nothing of the rows before it)
+			if (end > row + 1) for (uint32_t r = 0; r <= row; r += (row > 16 ? row / 16 : 1)) for (uint32_t col = r + 1; col < end; ++col) { CHECK(plan_one_lower_ok(e, g, r, col), "n %u r2 %g: pair (%u, %u) in front of one_end %u of row %u fails", n, minR2, r, col, end, row); ++g_one_pairs; }
+			for (uint32_t col = row + 1; col < end; ++col) CHECK(plan_one_lower_ok(e, g, row, col), "n %u r2 %g: pair (%u, %u) in front of one_end %u fails", n, minR2, row, col, end);
+			if (end < M) CHECK(!plan_one_lower_ok(e, g, row, end), "n %u r2 %g: pair (%u, one_end %u) passes", n, minR2, row, end);
+			++g_one_rows;
+		}
+	}
 	return g_bad_checks != before;
 }
 
@@ -208,5 +252,9 @@ int main(int argc, char** argv) {
 	        n, bad, g_tables, g_kept3, g_kept2);
 	fprintf(record ? stderr : stdout, "two-check: carrier screen kept %" PRIu64 " of the same tests (three products %" PRIu64 " <= carrier <= H plane %" PRIu64 ")\n", g_kept2c, g_kept3, g_kept2);
 	if (!(g_kept3 <= g_kept2c && g_kept2c <= g_kept2)) return 1;
+	const int bad_one = check_one_end();
+	fprintf(record ? stderr : stdout, "two-check: one-product screen kept %" PRIu64 " of the same tests (carrier %" PRIu64 " <= one product); one_end exact on %" PRIu64 " rows, %" PRIu64 " pairs in front of it, %d bad\n",
+	        g_kept1c, g_kept2c, g_one_rows, g_one_pairs, bad_one);
+	if (g_kept1c < g_kept2c || bad_one) return 1;
 	return bad != 0;
 }

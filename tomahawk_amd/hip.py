@@ -70,7 +70,7 @@ class _Timing(C.Structure):
                 ("three_launches", C.c_uint64), ("three_row_pairs", C.c_uint64), ("recount_candidates", C.c_uint64),
                 ("outlier_launches", C.c_uint64), ("finish_ms", C.c_double), ("two_launches", C.c_uint64),
                 ("prefix_launches", C.c_uint64), ("prefix_chunks", C.c_uint64), ("prefix_chunks_full", C.c_uint64),
-                ("carrier_launches", C.c_uint64)]
+                ("carrier_launches", C.c_uint64), ("one_launches", C.c_uint64)]
 
 
 class _PlanEnv(C.Structure):         # twk_hip_plan_env
@@ -80,18 +80,20 @@ class _PlanEnv(C.Structure):         # twk_hip_plan_env
 
 
 TILE_DTYPE = np.dtype([("rowA0", "<u4"), ("nA", "<u4"), ("rowB0", "<u4"), ("nB", "<u4"), ("diag", "<i4"), ("window", "<i4"),
-                       ("l_window", "<u4"), ("_pad", "<u4")])       # twk_hip_tile_desc
+                       ("l_window", "<u4"), ("one", "<u4")])       # twk_hip_tile_desc
 
 
 def plan_region(meta, n_samples, a0, nA, b0, nB, triangle=True, part=0, n_parts=1, tile_variants=0, window=0, l_window=0,
                 popc=None, screen=0, minR2=0.1, planes_per_variant=1, k_chunks=1, fused=False, phased_math=True,
                 resident_blocks=512, band_launch=True, band_reverse=True, band_work_log2=19, band_max_launches=8,
-                het=None, hom=None, two_margin=0.0, carrier=False):
+                het=None, hom=None, two_margin=0.0, carrier=False, one=False, one_rows=0):
     """The engine's planner (twk_hip_plan_region: host arithmetic, needs no GPU) -> dict(tiles=TILE_DTYPE array, n_band_launches,
     row_begin, row_end, n_pairs, lo, hi, two_end).  meta: META_DTYPE per position of the index space.  het / hom (both or neither): het and
     hom-alt carriers per position - the two-product walk of an unscreened UnphasedMath call (twk_hip_plan_region_two), whose triangle is cut
     at row two_end; two_margin 0: the engine's.  carrier: the walk's two-product launches contract the row variants' carrier planes H | Q
-    (twk_hip_plan_region_two_operand; the engine's option "carrier" on rows of more than 128 K chunks) - off: their H planes."""
+    (twk_hip_plan_region_two_operand; the engine's option "carrier" on rows of more than 128 K chunks) - off: their H planes.  one (with
+    carrier): the rows in front of the cut in blocks of one_rows variants (0: the engine's default), each block's columns up to its one_end as
+    launches with tiles["one"] set (twk_hip_plan_region_two_form; the engine's options "one" and "one_rows")."""
     lib = load_library()
     meta = np.ascontiguousarray(meta, dtype=META_DTYPE)
     env = _PlanEnv(n_samples, planes_per_variant, k_chunks, resident_blocks, screen, int(fused), int(phased_math), int(band_launch),
@@ -105,8 +107,8 @@ def plan_region(meta, n_samples, a0, nA, b0, nB, triangle=True, part=0, n_parts=
     cap = 1024
     while True:
         tiles = np.zeros(cap, dtype=TILE_DTYPE)
-        rc = lib.twk_hip_plan_region_two_operand(C.byref(env), meta.ctypes.data, None if pc is None else pc.ctypes.data,
-                                         None if ht is None else ht.ctypes.data, None if hm is None else hm.ctypes.data, float(two_margin), int(bool(carrier)), len(meta), a0, nA, b0, nB,
+        rc = lib.twk_hip_plan_region_two_form(C.byref(env), meta.ctypes.data, None if pc is None else pc.ctypes.data,
+                                         None if ht is None else ht.ctypes.data, None if hm is None else hm.ctypes.data, float(two_margin), int(bool(carrier)), int(bool(one)), int(one_rows), len(meta), a0, nA, b0, nB,
                                          int(bool(triangle)), part, n_parts, tile_variants, window, l_window, tiles.ctypes.data, cap,
                                          C.byref(n_tiles), C.byref(n_bands), C.byref(r0), C.byref(r1), C.byref(pairs), lo.ctypes.data, hi.ctypes.data, C.byref(two_end))
         if rc == -4 and n_tiles.value > cap:
@@ -143,7 +145,7 @@ class Plant(C.Structure):            # twk_hip_plant: LD planted in the syntheti
 class _LaunchStat(C.Structure):      # twk_hip_launch_stat
     _fields_ = [("ms", C.c_double), ("shader_mhz", C.c_double), ("xcd_finish_spread_us", C.c_double), ("row_pairs", C.c_uint64),
                 ("candidates", C.c_uint64), ("words_per_row", C.c_uint32), ("kind", C.c_uint32), ("outlier", C.c_uint32), ("_pad", C.c_uint32),
-                ("prefix_chunks", C.c_uint64), ("prefix_chunks_full", C.c_uint64), ("carrier", C.c_uint32), ("_pad2", C.c_uint32)]
+                ("prefix_chunks", C.c_uint64), ("prefix_chunks_full", C.c_uint64), ("carrier", C.c_uint32), ("one", C.c_uint32)]
 
 
 @dataclass
@@ -261,6 +263,8 @@ def load_library() -> C.CDLL:
                                             C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32, p, p, p, p, p, p, p, p]
     lib.twk_hip_plan_region_two_operand.argtypes = [p, p, p, p, p, C.c_double, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                                     C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32, p, p, p, p, p, p, p, p]
+    lib.twk_hip_plan_region_two_form.argtypes = [p, p, p, p, p, C.c_double, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
+                                                 C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32, p, p, p, p, p, p, p, p]
     lib.twk_hip_launch_log.argtypes = [p, p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_fisher_exact.argtypes = [p, p, C.c_uint64, p, C.c_int32, C.POINTER(C.c_float)]
     lib.twk_hip_set_device_sink.argtypes = [p, C.c_int]
