@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check varsel-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check varsel-check blocks-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -188,6 +188,15 @@ varsel-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/varsel_index_check.cpp -o build/varsel_index_check
 	./build/varsel_index_check
+
+# Haplotype blocks' host side (csrc/hip/ld_block_ci.h): the D' bounds' scan against a long double restatement (dmax == 0, a zero cell, D == 0,
+# A and B swapped, fractional counts), the byte stores of the bounds' kernel lane by lane against arrays of write counts with a border, the
+# prefix counts, the candidates' running sums and small-m rules against the contract with every pair counted, the sort key's order, and the
+# walk played with lanes running ahead (csrc/tools/blocks_check.cpp): host code only, under AddressSanitizer and UBSan
+blocks-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/blocks_check.cpp -o build/blocks_check
+	./build/blocks_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

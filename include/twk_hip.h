@@ -42,6 +42,7 @@ extern "C" {
 /*    (still 5: twk_hip_relationship / twk_hip_relationship_last - the sample relationship matrix - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_score_annot - partitioned LD scores - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_bandmat_layout / twk_hip_ld_matrix_band / twk_hip_bandmat_last - the banded LD matrix - are three entry points more; no struct and no existing entry point changed) */
+/*    (still 5: twk_hip_ld_dprime_ci_band / twk_hip_ld_blocks / twk_hip_blocks_last / twk_hip_blocks_stages - haplotype blocks - are four entry points and one struct more; nothing existing changed) */
 /*    (still 5: twk_hip_ld_topk / twk_hip_topk_last - top-k LD partners - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_select_samples / twk_hip_selection / twk_hip_get_meta / twk_hip_set_hwe / twk_hip_select_last - sample subsets - are five entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_select_variants / twk_hip_variant_selection / twk_hip_variant_map / twk_hip_select_variants_last - variant subsets - are four entry points more; no existing struct and no existing entry point changed) */
@@ -535,6 +536,54 @@ int twk_hip_ld_matrix_band(twk_hip_ctx* ctx, int mode, const twk_hip_filters* fi
                            int32_t stat, float fill, float* values, uint64_t capacity, uint32_t* first, uint64_t* row_ptr,
                            uint64_t* n_records, uint64_t* n_pairs);
 int twk_hip_bandmat_last(const twk_hip_ctx* ctx, double* copy_ms, uint64_t* band_bytes);
+
+/* Haplotype blocks by the rule of Gabriel et al. (2002) - PLINK's --blocks, Haploview's default view - in two calls, one on top of the
+ * other.  Both are windowed (l_window base pairs, always on), both take twk_hip_ld_matrix_band's mode, filters (minP >= 1), a0, n and
+ * tile_variants, and an INFORMATIVE pair is one for which twk_hip_ld_region with the same arguments would report a record.
+ *   twk_hip_ld_dprime_ci_band  the confidence bounds of D' of every informative in-band pair, in twk_hip_bandmat_layout's layout for
+ *          l_window: lo and hi, HOST arrays of `capacity` >= row_ptr[n] bytes each, hold at row_ptr[u] + (v - first[u]) the bounds of
+ *          the pair (u, v) in percent, 0 .. 100 - both orientations - and 255 / 255 where the pair has no record, and on the diagonal.
+ *          The bounds are those of a likelihood scan over 101 values of D' of the record's 2 x 2 table cnt[0..3]: the lowest and the
+ *          highest grid point that leave 5 % of the likelihood's mass outside, one step outwards (DESIGN 3.18 has the definition to the
+ *          rounding).  first, row_ptr: overwritten with the layout.  n_records: the informative pairs u < v.  Refusals: as
+ *          twk_hip_ld_matrix_band's, and l_window == 0.  Plain stores, no atomics: the same bytes for any tiling and on any repeat.
+ *   twk_hip_ld_blocks  the blocks of the slice's variants in file order.  params: NULL for the defaults
+ *          {70, 98, 90, 80, 50, 950, 20000, 30000}.  l_window is also the longest block in base pairs.
+ *          A CANDIDATE is an informative pair i < j with lo >= strong_lo and hi >= strong_hi; m = j - i + 1 is its marker count and
+ *          sep = pos[j] - pos[i].  Its cut-off is strong_lo_2 for m = 2, strong_lo_34 for m = 3 or 4, strong_lo otherwise.  Over the
+ *          informative pairs x < y inside [i, j], s counts those with lo >= cut && hi >= strong_hi and r those with hi < recomb_hi.
+ *          It QUALIFIES iff not (m == 2 && sep > max_span_2), not (m == 3 && sep > max_span_3), s + r >= 1 (m = 2), 3 (m = 3) or
+ *          6 (m >= 4), and s * 1000 > inform_permille * (s + r).  The qualifying candidates are visited in order of sep descending,
+ *          then m descending, then i ascending; one becomes a BLOCK iff neither of its ends lies in an earlier block.
+ *          block_of  HOST, one entry per uploaded variant: the index of the first variant of the variant's block, or TWK_HIP_NO_BLOCK
+ *                    (also outside the slice).
+ *          first, last, n_strong, n_recomb  HOST arrays of n / 2 entries (each may be NULL): per block, in file order, its first and
+ *                    last variant and its s and r.
+ *          n_blocks, n_candidates, n_informative, n_pairs  (each may be NULL) blocks, candidates, informative pairs, pairs looked at.
+ *          TWK_HIP_E_INVALID before any launch: a threshold above 100, recomb_hi > strong_hi, inform_permille > 1000, minP < 1,
+ *          l_window == 0, n == 0, a slice beyond the last variant or not sorted, a NULL block_of, a band row wider than 65,535
+ *          variants, a sort key (window, widest row, n) beyond 64 bits.  Device memory for the length of the call: 10 bytes per band
+ *          slot and 32 per qualifying candidate; TWK_HIP_E_NOMEM with the byte count in twk_hip_last_error.  The result is a function
+ *          of the lo / hi bytes, the positions and the parameters alone.
+ *   twk_hip_blocks_last  of the context's last twk_hip_ld_blocks call: the walk kernel's time in ms and the bytes of the lo / hi band
+ *          (either may be NULL).
+ * There is NO reference counterpart; PLINK and Haploview add a LOD filter, their own MAF rule and, unphased, a double-heterozygote term. */
+#define TWK_HIP_NO_BLOCK 0xFFFFFFFFu
+typedef struct twk_hip_block_params {
+	uint32_t strong_lo, strong_hi, recomb_hi, strong_lo_2, strong_lo_34, inform_permille, max_span_2, max_span_3;
+} twk_hip_block_params;
+int twk_hip_ld_dprime_ci_band(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                              uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
+                              uint8_t* lo, uint8_t* hi, uint64_t capacity, uint32_t* first, uint64_t* row_ptr,
+                              uint64_t* n_records, uint64_t* n_pairs);
+int twk_hip_ld_blocks(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                      uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window, const twk_hip_block_params* params,
+                      uint32_t* block_of, uint32_t* first, uint32_t* last, uint32_t* n_strong, uint32_t* n_recomb,
+                      uint64_t* n_blocks, uint64_t* n_candidates, uint64_t* n_informative, uint64_t* n_pairs);
+int twk_hip_blocks_last(const twk_hip_ctx* ctx, double* walk_ms, uint64_t* band_bytes);
+/* ... and the device time in ms of its stages between the bounds' launches and the walk: the prefix counts, the counting pass over the
+ * candidates and the scan; the emitting pass; the sort (each may be NULL; 0 for a stage that did not run). */
+int twk_hip_blocks_stages(const twk_hip_ctx* ctx, double* counts_ms, double* emit_ms, double* sort_ms);
 
 /* LD decay over the same slice of the pair space as twk_hip_ld_score, with the same arguments: r2 as a function of the distance
  * between two variants.  A pair COUNTS when twk_hip_ld_region with these arguments would report a record for it, both variants lie on

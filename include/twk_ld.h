@@ -109,6 +109,14 @@ struct twk_aggregate_settings {
 	int64_t min_count = 5;                 // a cell with fewer contributions prints 0 (the reference's -c)
 };
 
+// What Blocks takes beyond twk_ld_settings: the thresholds of Gabriel et al. (twk_hip_block_params, field for field) and the prefix of
+// the files that keep the D' bounds (empty: not written).
+struct twk_block_settings {
+	uint32_t strong_lo = 70, strong_hi = 98, recomb_hi = 90, strong_lo_2 = 80, strong_lo_34 = 50, inform_permille = 950;
+	uint32_t max_span_2 = 20000, max_span_3 = 30000;
+	std::string ci_out;         // PREFIX of PREFIX.lo.npy, .hi.npy, .indptr.npy, .first.npy and .variants.tsv
+};
+
 // What Relationship needs beyond twk_ld_settings.
 struct twk_relationship_settings {
 	int32_t stat = 2;           // TWK_HIP_REL_KING; or _IBS (0), _IBS0 (1) (include/twk_hip.h)
@@ -211,6 +219,16 @@ public:
 	// Else settings.out is a PREFIX: PREFIX.npy (NumPy format 1.0, '<f8', C order, shape (n, n)) or, with rel.text, PREFIX.tsv (the same text),
 	// and always PREFIX.samples.tsv: one sample name per row, from the header.  `tomahawk relationship` ends here.
 	bool Relationship(const twk_ld_settings& settings, const twk_relationship_settings& rel);
+	// Not in the reference: haplotype blocks by the rule of Gabriel et al. (PLINK's --blocks, Haploview's default view).  Loads the .twk
+	// exactly as Prune does (-I intervals, -p / -u, --keep, --extract ..; -c / -C are refused); the window is always on - settings.l_window
+	// bases, 200,000 where settings.window is not set - and is also the longest block.  The D' confidence bounds of every pair Compute
+	// would write a record for are formed and the blocks selected on one GPU (twk_hip_ld_blocks), no record is formed.  Writes the `##`
+	// header lines and one line per block, in file order, to settings.out: contig, first position, last position, span in bases,
+	// variants, strong pairs, recombinant pairs.  With blocks.ci_out the bounds are kept too (twk_hip_ld_dprime_ci_band, a second engine
+	// call): PREFIX.lo.npy and PREFIX.hi.npy ('|u1', shape (nnz,); 255 where a pair has no record), PREFIX.indptr.npy, PREFIX.first.npy and
+	// PREFIX.variants.tsv as Matrix writes them for a band.  Not PLINK's or Haploview's numbers: they add a LOD filter, their own MAF
+	// rule and, unphased, a double-heterozygote term.  settings.minP must be 1 (the default).  `tomahawk blocks` ends here.
+	bool Blocks(const twk_ld_settings& settings, const twk_block_settings& blocks);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

@@ -9,7 +9,7 @@ for tests, benchmarks and scripting; it contains no compute and no CPU fallback.
 from .hip import (HipLd, HipError, Filters, RECORD_DTYPE, MODE_PHASED, MODE_UNPHASED, MODE_AUTO,
                   OPT_WINDOW, OPT_KEEP_LOW_AC, OPT_REF_COMPAT, OPT_R2_SCREEN, NO_CLUMP, STAT_R, STAT_R2, STAT_D, STAT_DPRIME, REL_IBS, REL_IBS0, REL_KING, REL_COUNTS_DTYPE,
                   RLE_DESC_DTYPE, META_DTYPE,
-                  device_count, load_library, synth_bitvector, shard_rows, plan_region, TILE_DTYPE, Plant, plant_source, gather_records, gather_backend, band_to_csr, band_to_dense, NO_PARTNER, topk_merge)
+                  device_count, load_library, synth_bitvector, shard_rows, plan_region, TILE_DTYPE, Plant, plant_source, gather_records, gather_backend, band_to_csr, band_to_dense, NO_PARTNER, topk_merge, NO_BLOCK, BlockParams)
 
 __all__ = ["HipLd", "HipError", "Filters", "RECORD_DTYPE", "MODE_PHASED", "MODE_UNPHASED",
-           "MODE_AUTO", "OPT_WINDOW", "OPT_KEEP_LOW_AC", "OPT_REF_COMPAT", "OPT_R2_SCREEN", "NO_CLUMP", "STAT_R", "STAT_R2", "STAT_D", "STAT_DPRIME", "REL_IBS", "REL_IBS0", "REL_KING", "REL_COUNTS_DTYPE", "RLE_DESC_DTYPE", "META_DTYPE", "device_count", "load_library", "synth_bitvector", "shard_rows", "plan_region", "TILE_DTYPE", "Plant", "plant_source", "gather_records", "gather_backend", "band_to_csr", "band_to_dense", "NO_PARTNER", "topk_merge"]
+           "MODE_AUTO", "OPT_WINDOW", "OPT_KEEP_LOW_AC", "OPT_REF_COMPAT", "OPT_R2_SCREEN", "NO_CLUMP", "STAT_R", "STAT_R2", "STAT_D", "STAT_DPRIME", "REL_IBS", "REL_IBS0", "REL_KING", "REL_COUNTS_DTYPE", "RLE_DESC_DTYPE", "META_DTYPE", "device_count", "load_library", "synth_bitvector", "shard_rows", "plan_region", "TILE_DTYPE", "Plant", "plant_source", "gather_records", "gather_backend", "band_to_csr", "band_to_dense", "NO_PARTNER", "topk_merge", "NO_BLOCK", "BlockParams"]

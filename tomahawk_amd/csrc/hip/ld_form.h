@@ -9,8 +9,8 @@ namespace twk {
 
 // The epilogue that stands in for math, Fisher, sort and delivery while a call of twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band or _topk runs: it looks at
 // every pair of a count matrix and keeps no survivor (ld_reduce.hip.h on what the nine kernels share).
-enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot, bandmat, topk };
-constexpr int N_REDUCE = (int)Reduce::topk + 1;
+enum class Reduce { none, score, prune, clump, matrix, decay, aggregate, annot, bandmat, topk, dprime_ci, blocks };      // (dprime_ci and blocks: one epilogue, two calls)
+constexpr int N_REDUCE = (int)Reduce::blocks + 1;
 // The form of a launch, decided once (decide_form) and passed down: which count kernel, which math behind it.
 struct LaunchForm {
 	bool two_pass = false;         // a default-mode tile with missing data: a second (masked unphased) pass follows; the form describes the first

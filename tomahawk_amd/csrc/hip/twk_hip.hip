@@ -18,7 +18,9 @@
 //   topk (ld_topk.hip.h) cells -> one statistic of the pair's record -> a 64-bit key -> the k largest per variant, selected with integer atomic maxima (twk_hip_ld_topk)
 //   subset (ld_subset.hip.h) the raw rows compacted to a list of samples: a working copy beside the rows as uploaded (twk_hip_select_samples)
 //   varsel (ld_varsel.hip.h) a predicate per variant -> scan -> the rows and the metadata of the kept variants gathered beside the base (twk_hip_select_variants)
-//   (score, prune, clump, matrix, decay, aggregate, annot, bandmat and topk are the nine kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
+//   blocks (ld_blocks.hip.h) cells -> the record's 2 x 2 table -> a likelihood scan over 101 values of D' -> the bounds lo, hi as two bytes per in-window pair in band storage
+//                          (twk_hip_ld_dprime_ci_band) -> prefix counts, candidates, sort, walk: haplotype blocks (twk_hip_ld_blocks)
+//   (score, prune, clump, matrix, decay, aggregate, annot, bandmat, topk and the bounds of dprime_ci / blocks are the kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
@@ -58,6 +60,7 @@
 #include "ld_clump.hip.h"
 #include "ld_matrix.hip.h"
 #include "ld_bandmat.hip.h"
+#include "ld_blocks.hip.h"
 #include "ld_topk.hip.h"
 #include "ld_relate.hip.h"
 #include "ld_subset.hip.h"
@@ -146,7 +149,7 @@ constexpr int PIPE_SLOTS = 3, SYNC_SLOT = PIPE_SLOTS;
 // What the running call of one of them sets, for its length: ~ReduceCall puts a default-constructed one back.
 struct ReduceState {
 	Reduce kind = Reduce::none;
-	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; BandMap band; TopkMap topk; } map{};      // where the running kind's launches put their results (prune and clump: bits)
+	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; BandMap band; TopkMap topk; CiMap ci; } map{};      // where the running kind's launches put their results (prune and clump: bits)
 	uint64_t work = 0;                            // what the call's launches used up of the room of the kind's accumulators (launch_reduce holds it to the kind's limit)
 };
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
@@ -176,7 +179,7 @@ struct Launch {
 	uint64_t prefix_chunks = 0, prefix_chunks_full = 0;      // a prefix launch: chunks its tiles were contracted over, and what whole rows would have been
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
-union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; BandArgs bandmat; TopkArgs topk; };
+union ReduceArgs { ScoreArgs score; PruneArgs prune; ClumpArgs clump; MatrixArgs matrix; DecayArgs decay; AggArgs aggregate; AnnotArgs annot; BandArgs bandmat; TopkArgs topk; CiArgs ci; };
 struct Slot {                      // one in-flight tile (double buffered)
 	Launch l;
 	DevBuf<uint32_t> C;
@@ -347,6 +350,7 @@ struct twk_hip_ctx {
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
 	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
+	double blocks_stage_ms[3] = {0, 0, 0};      // of the last twk_hip_ld_blocks call: prefix counts + candidate counts + scan, the emitting pass, the sort (twk_hip_blocks_stages)
 	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
 	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last, twk_hip_bandmat_last, twk_hip_topk_last)
 	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
@@ -932,6 +936,8 @@ int launch_reduce(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, 
 	case Reduce::annot:     return run_reduce_kernel(c, t, s, which, k_ld_annot, ANNOT_THREADS, ANNOT_ROWS, AnnotArgs{{p, rs.map.annot}});      // (no work limit: ld_score_annot.hip.h)
 	case Reduce::bandmat:   return run_reduce_kernel(c, t, s, which, k_ld_bandmat_fill, BANDMAT_THREADS, BANDMAT_ROWS, BandArgs{{p, rs.map.band}});
 	case Reduce::topk:      return run_reduce_kernel(c, t, s, which, k_ld_topk, TOPK_THREADS, TOPK_BLOCK_ROWS, TopkArgs{{p, rs.map.topk}}, tk_lds_bytes(rs.map.topk.k));      // (no work limit: a selection has no headroom to use up)
+	case Reduce::dprime_ci:
+	case Reduce::blocks:    return run_reduce_kernel(c, t, s, which, k_ld_dprime_ci_band, CI_THREADS, CI_ROWS, CiArgs{{p, rs.map.ci}});
 	case Reduce::score: break;
 	case Reduce::none: return TWK_HIP_E_STATE;
 	}
@@ -2894,7 +2900,7 @@ struct ReduceCall {
 	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
 	int bad;
 	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums, the band and its map, the top-k lists.  Freed behind the destructor's body, which waits for the device.
-	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc, d_topk; DevBuf<float> d_matrix, d_band; DevBuf<double> d_annot; DevBuf<BandRow> d_band_rows;
+	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc, d_topk; DevBuf<float> d_matrix, d_band; DevBuf<double> d_annot; DevBuf<BandRow> d_band_rows; DevBuf<uint8_t> d_ci_lo, d_ci_hi;
 	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
 	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
 		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
@@ -3178,6 +3184,200 @@ int twk_hip_ld_matrix_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 }
 
 int twk_hip_bandmat_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* band_bytes) { return last_of(c, Reduce::bandmat, copy_ms, band_bytes); }
+
+// Haplotype blocks (ld_blocks.hip.h): the D' confidence bounds of the in-window pairs in band storage, and the blocks selected from them.
+extern "C++" {
+namespace {
+struct CiBand { std::vector<uint32_t> first; std::vector<uint64_t> ptr; size_t cells = 0; uint32_t widest = 0; };
+int ci_band_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, CiBand& b) {
+	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
+	b.first.resize(n); b.ptr.resize((size_t)n + 1);
+	const int rc = bandmat_layout(c, a0, n, l_window, b.first.data(), b.ptr.data()); if (rc) return rc;
+	b.cells = (size_t)b.ptr[n];
+	for (uint32_t u = 0; u < n; ++u) b.widest = std::max<uint32_t>(b.widest, (uint32_t)std::min<uint64_t>(b.ptr[u + 1] - b.ptr[u], 0xFFFFFFFFull));
+	return TWK_HIP_OK;
+}
+// The bounds of the slice into call.d_ci_lo / call.d_ci_hi: the band map, the preset 255, the launches.
+int ci_band_fill(ReduceCall& call, int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window, const CiBand& b, uint64_t* n_pairs) {
+	twk_hip_ctx* c = call.c;
+	std::vector<BandRow> rows(n);
+	for (uint32_t u = 0; u < n; ++u) rows[u] = BandRow{b.ptr[u], b.first[u], (uint32_t)(b.ptr[u + 1] - b.ptr[u])};
+	int rc = hold_for_call(c, call.d_band_rows, (size_t)n, "the band map of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	rc = hold_for_call(c, call.d_ci_hi, b.cells, "the upper D' bounds of %u variants' band need %zu bytes of device memory: %s", n); if (rc) return rc;
+	rc = call.hold(call.d_ci_lo, b.cells, "the lower D' bounds of %u variants' band need %zu bytes of device memory: %s", n); if (rc) return rc;
+	HIPCHK(c, hipMemsetAsync(call.d_ci_lo, BC_NONE, b.cells, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(call.d_ci_hi, BC_NONE, b.cells, c->s_compute));
+	// (from pageable memory: the copy has left `rows` when it returns)
+	HIPCHK(c, hipMemcpyAsync(call.d_band_rows, rows.data(), (size_t)n * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
+	c->reduce.map.ci = CiMap{call.d_ci_lo, call.d_ci_hi, call.d_band_rows, a0, n};
+	call.arm(b.cells * 2);
+	return call.dispatch(mode, a0, n, tile_variants, (int32_t)TWK_HIP_OPT_WINDOW, l_window, n_pairs);
+}
+}  // namespace
+}  // extern "C++"
+
+int twk_hip_ld_dprime_ci_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
+                              uint8_t* lo, uint8_t* hi, uint64_t capacity, uint32_t* first, uint64_t* row_ptr, uint64_t* n_records, uint64_t* n_pairs) {
+	DevBuf<uint32_t> d_inf;                  // (before `call`: freed behind its destructor, which waits for the device)
+	ReduceCall call(c, Reduce::dprime_ci, f, lo && hi && first && row_ptr && l_window > 0, mode, a0, n);
+	if (call.bad) return call.bad;
+	CiBand b;
+	int rc = ci_band_layout(c, a0, n, l_window, b); if (rc) return rc;
+	if (capacity < b.cells) {
+		snprintf(c->err, sizeof(c->err), "D' bounds: the band of %u variants holds %zu slots, the caller's arrays %llu", n, b.cells, (unsigned long long)capacity);
+		return TWK_HIP_E_INVALID;
+	}
+	rc = hold_for_call(c, d_inf, (size_t)n, "the informative counts of %u variants need %zu bytes of device memory: %s", n); if (rc) return rc;
+	rc = ci_band_fill(call, mode, a0, n, tile_variants, l_window, b, n_pairs); if (rc) return rc;
+	hipLaunchKernelGGL(k_ci_informative, dim3((n + 3) / 4), dim3(BLOCKS_THREADS), 0, c->s_compute, (const uint8_t*)call.d_ci_lo, (const BandRow*)call.d_band_rows, n, d_inf.get());
+	HIPCHK(c, hipGetLastError());
+	std::vector<uint32_t> inf(n);
+	rc = call.tail("D' bounds", [&] {
+		const hipError_t e = hipMemcpyAsync(lo, call.d_ci_lo, b.cells, hipMemcpyDeviceToHost, c->s_compute);
+		return e != hipSuccess ? e : hipMemcpyAsync(hi, call.d_ci_hi, b.cells, hipMemcpyDeviceToHost, c->s_compute);
+	}, [&] { return hipMemcpyAsync(inf.data(), d_inf, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute); });
+	if (rc) return rc;
+	memcpy(first, b.first.data(), (size_t)n * sizeof(uint32_t));
+	memcpy(row_ptr, b.ptr.data(), ((size_t)n + 1) * sizeof(uint64_t));
+	if (n_records) { uint64_t sum = 0; for (const uint32_t x : inf) sum += x; *n_records = sum; }
+	return TWK_HIP_OK;
+}
+
+int twk_hip_ld_blocks(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
+                      const twk_hip_block_params* params, uint32_t* block_of, uint32_t* first, uint32_t* last, uint32_t* n_strong, uint32_t* n_recomb,
+                      uint64_t* n_blocks, uint64_t* n_candidates, uint64_t* n_informative, uint64_t* n_pairs) {
+	static_assert(sizeof(twk_hip_block_params) == sizeof(BlockParams), "BlockParams is twk_hip_block_params, field for field");
+	BlockParams par = BLOCK_DEFAULTS;
+	if (params) memcpy(&par, params, sizeof(par));
+	// (before `call`: freed behind its destructor, which waits for the device)
+	DevBuf<uint32_t> d_pos, d_ps, d_pr, d_counts3, d_flat, d_off, d_vals, d_vals_out, d_cs, d_cr, d_block_of, d_blk;
+	DevBuf<unsigned long long> d_keys, d_keys_out, d_used;
+	DevBuf<char> d_tmp;
+	ReduceCall call(c, Reduce::blocks, f, block_of && bc_params_ok(par) && l_window > 0, mode, a0, n);
+	if (call.bad) return call.bad;
+	CiBand b;
+	int rc = ci_band_layout(c, a0, n, l_window, b); if (rc) return rc;
+	BlockKey key; uint32_t key_bits = 0;
+	if (b.widest > BLOCK_MAX_BAND || !bc_key_layout(n, b.widest, l_window, &key, &key_bits)) {
+		snprintf(c->err, sizeof(c->err), "haplotype blocks: a window of %u base pairs reaches %u variants in a row of %u (at most %u, and a sort key of at most 64 bits)",
+		         l_window, b.widest, n, BLOCK_MAX_BAND);
+		return TWK_HIP_E_INVALID;
+	}
+	const size_t M = c->M;
+	const uint32_t stride = (n + 63) / 64;
+	const bool in_lds = stride <= BLOCKS_LDS_WORDS;
+	std::vector<uint32_t> h_pos(n);
+	for (uint32_t u = 0; u < n; ++u) h_pos[u] = c->h_meta[a0 + u].pos;
+	size_t scan_tmp = 0;
+	HIPCHK(c, rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(), c->s_compute));
+	{
+		const char* what = "the prefix counts of %u variants' band need %zu bytes of device memory: %s";
+		rc = hold_for_call(c, d_ps, b.cells, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_pr, b.cells, what, n); if (rc) return rc;
+		what = "the per-variant arrays of %u variants need %zu bytes of device memory: %s";
+		rc = hold_for_call(c, d_counts3, (size_t)n * 3, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_blk, (size_t)n * 3, what, n); if (rc) return rc;
+		for (DevBuf<uint32_t>* x : {&d_pos, &d_flat, &d_off}) { rc = hold_for_call(c, *x, (size_t)n, what, n); if (rc) return rc; }
+		rc = hold_for_call(c, d_block_of, M, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_used, (size_t)stride, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_tmp, std::max<size_t>(scan_tmp, 16), "the scan of %u counts needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	}
+	rc = ci_band_fill(call, mode, a0, n, tile_variants, l_window, b, n_pairs); if (rc) return rc;
+	HIPCHK(c, hipMemcpyAsync(d_pos, h_pos.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d_block_of, 0xFF, M * sizeof(uint32_t), c->s_compute));          // TWK_HIP_NO_BLOCK
+	HIPCHK(c, hipMemsetAsync(d_blk, 0, (size_t)n * 3 * sizeof(uint32_t), c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d_used, 0, (size_t)stride * sizeof(unsigned long long), c->s_compute));
+	HIPCHK(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
+	Events ev;
+	HIPCHK(c, ev.add(5));
+	c->blocks_stage_ms[0] = c->blocks_stage_ms[1] = c->blocks_stage_ms[2] = 0;
+	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
+	const BlocksBand band{call.d_ci_lo, call.d_ci_hi, call.d_band_rows, d_pos, d_ps, d_pr, n, par, key};
+	const dim3 per_row((n + 3) / 4), per_variant((n + BLOCKS_THREADS - 1) / BLOCKS_THREADS), threads(BLOCKS_THREADS);
+	hipLaunchKernelGGL(k_blocks_prefix, per_row, threads, 0, c->s_compute, band);
+	HIPCHK(c, hipGetLastError());
+	hipLaunchKernelGGL(k_blocks_candidates<false>, per_variant, threads, 0, c->s_compute, band, d_counts3.get(), (const uint32_t*)nullptr, 0u,
+	                   (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
+	HIPCHK(c, hipGetLastError());
+	hipLaunchKernelGGL(k_blocks_flatten, per_variant, threads, 0, c->s_compute, (const uint32_t*)d_counts3, n, d_flat.get());
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, rocprim::exclusive_scan(d_tmp.get(), scan_tmp, d_flat.get(), d_off.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), c->s_compute));
+	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
+	std::vector<uint32_t> counts3((size_t)n * 3);
+	rc = call.download("haplotype blocks: the candidate counts", [&] {
+		return hipMemcpyAsync(counts3.data(), d_counts3, counts3.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
+	});
+	if (rc) return rc;
+	{ float ms = 0; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->blocks_stage_ms[0] = ms; }
+	uint64_t n_q = 0, n_c = 0, n_inf = 0;
+	for (uint32_t u = 0; u < n; ++u) { n_q += counts3[3 * (size_t)u]; n_c += counts3[3 * (size_t)u + 1]; n_inf += counts3[3 * (size_t)u + 2]; }
+	if (n_q > 0xFFFFFFFFull) {
+		snprintf(c->err, sizeof(c->err), "haplotype blocks: %llu qualifying candidates, more than 2^32 - 1; split the slice", (unsigned long long)n_q);
+		return TWK_HIP_E_INVALID;
+	}
+	std::vector<uint32_t> h_block_of(M, BLOCK_NONE), h_blk;
+	unsigned long long walked = 0;
+	if (n_q) {
+		const size_t q = (size_t)n_q;
+		const char* what = "the %u qualifying candidates need %zu bytes of device memory: %s";
+		for (DevBuf<unsigned long long>* x : {&d_keys, &d_keys_out}) { rc = hold_for_call(c, *x, q, what, (uint32_t)n_q); if (rc) return rc; }
+		for (DevBuf<uint32_t>* x : {&d_vals, &d_vals_out, &d_cs, &d_cr}) { rc = hold_for_call(c, *x, q, what, (uint32_t)n_q); if (rc) return rc; }
+		HIPCHK(c, hipMemsetAsync(d_keys, 0xFF, q * sizeof(unsigned long long), c->s_compute));      // (a slot the emitter leaves is no candidate: the walk skips it)
+		HIPCHK(c, hipMemsetAsync(d_vals, 0, q * sizeof(uint32_t), c->s_compute));
+		HIPCHK(c, hipEventRecord(ev[2], c->s_compute));
+		hipLaunchKernelGGL(k_blocks_candidates<true>, per_variant, threads, 0, c->s_compute, band, (uint32_t*)nullptr, (const uint32_t*)d_off, (uint32_t)n_q,
+		                   d_keys.get(), d_vals.get(), d_cs.get(), d_cr.get());
+		HIPCHK(c, hipGetLastError());
+		HIPCHK(c, hipEventRecord(ev[3], c->s_compute));
+		size_t sort_tmp = 0;
+		HIPCHK(c, rocprim::radix_sort_pairs(nullptr, sort_tmp, d_keys.get(), d_keys_out.get(), d_vals.get(), d_vals_out.get(), q, 0u, key_bits, c->s_compute));
+		rc = hold_for_call(c, d_tmp, std::max<size_t>(sort_tmp, 16), "the sort of %u candidates needs %zu bytes of device memory: %s", (uint32_t)n_q); if (rc) return rc;
+		sort_tmp = d_tmp.capacity();
+		HIPCHK(c, rocprim::radix_sort_pairs(d_tmp.get(), sort_tmp, d_keys.get(), d_keys_out.get(), d_vals.get(), d_vals_out.get(), q, 0u, key_bits, c->s_compute));
+		HIPCHK(c, hipEventRecord(ev[4], c->s_compute));
+		h_blk.resize((size_t)n * 3);
+		rc = call.tail("haplotype blocks: the walk", [&] {
+			hipLaunchKernelGGL(in_lds ? k_blocks_walk<true> : k_blocks_walk<false>, dim3(1), dim3(BLOCKS_WALK_THREADS), 0, c->s_compute,
+			                   (const unsigned long long*)d_keys_out, (const uint32_t*)d_vals_out, (uint32_t)n_q, key, (const uint32_t*)d_cs, (const uint32_t*)d_cr,
+			                   a0, n, stride, d_used.get(), d_block_of.get(), d_blk.get(), c->d_counts.get());
+			return hipGetLastError();
+		}, [&] {
+			hipError_t e = hipMemcpyAsync(h_block_of.data(), d_block_of, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
+			if (e == hipSuccess) e = hipMemcpyAsync(h_blk.data(), d_blk, h_blk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
+			return e != hipSuccess ? e : hipMemcpyAsync(&walked, c->d_counts, sizeof(walked), hipMemcpyDeviceToHost, c->s_compute);
+		});
+		if (rc) return rc;
+		float ms = 0;
+		if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) c->blocks_stage_ms[1] = ms;
+		if (hipEventElapsedTime(&ms, ev[3], ev[4]) == hipSuccess) c->blocks_stage_ms[2] = ms;
+	}
+	// the blocks in file order: a variant that is its own block_of begins one
+	uint64_t nb = 0;
+	for (uint32_t u = 0; u < n && n_q; ++u) {
+		if (h_block_of[a0 + u] != a0 + u) continue;
+		if (nb >= n / 2) { snprintf(c->err, sizeof(c->err), "haplotype blocks: more than %u blocks among %u variants", n / 2, n); return TWK_HIP_E_DEVICE; }
+		if (first) first[nb] = a0 + u;
+		if (last) last[nb] = h_blk[3 * (size_t)u];
+		if (n_strong) n_strong[nb] = h_blk[3 * (size_t)u + 1];
+		if (n_recomb) n_recomb[nb] = h_blk[3 * (size_t)u + 2];
+		++nb;
+	}
+	if (nb != walked) { snprintf(c->err, sizeof(c->err), "haplotype blocks: the walk made %llu blocks, block_of holds %llu", walked, (unsigned long long)nb); return TWK_HIP_E_DEVICE; }
+	memcpy(block_of, h_block_of.data(), M * sizeof(uint32_t));
+	if (n_blocks) *n_blocks = nb;
+	if (n_candidates) *n_candidates = n_c;
+	if (n_informative) *n_informative = n_inf;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_blocks_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* band_bytes) { return last_of(c, Reduce::blocks, walk_ms, band_bytes); }
+int twk_hip_blocks_stages(const twk_hip_ctx* c, double* counts_ms, double* emit_ms, double* sort_ms) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (counts_ms) *counts_ms = c->blocks_stage_ms[0];
+	if (emit_ms) *emit_ms = c->blocks_stage_ms[1];
+	if (sort_ms) *sort_ms = c->blocks_stage_ms[2];
+	return TWK_HIP_OK;
+}
 
 // Top-k LD partners: the lists' slots are zeroed in front of the launches; behind the last of them the keys are copied out and unpacked
 // on the host, a slab of variants at a time - 8 bytes per slot leave the device whoever unpacks.

@@ -482,6 +482,60 @@ static const Command<tomahawk::twk_matrix_settings> LDMATRIX = {
 	},
 	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_matrix_settings& matrix) { return ld.Matrix(settings, matrix); }};
 
+// `tomahawk blocks` (not in the reference): haplotype blocks by the rule of Gabriel et al., the D' confidence bounds formed and the blocks
+// selected on the GPU.
+static void blocks_usage() {
+	program_message();
+	std::cerr <<
+	"About:  Haplotype blocks by the rule of Gabriel et al. (2002) - PLINK's --blocks, Haploview's default\n"
+	"        view.  For every pair `calc` would report under the same options the 5 % / 95 % confidence\n"
+	"        bounds of D' come from a likelihood scan of the pair's 2 x 2 haplotype table; a pair is strong\n"
+	"        (lower bound >= 70, upper >= 98) or recombinant (upper < 90); a stretch of variants whose ends\n"
+	"        are strong and of whose informative pairs more than 95 % are strong can be a block, and the\n"
+	"        longest such stretches are taken first.  Computed and selected on the GPU (no .two is written).\n"
+	"        Not PLINK's or Haploview's numbers: they add a LOD filter, their own MAF rule and, unphased, a\n"
+	"        double-heterozygote term; here the table is the one `calc` reports.\n\n"
+	"Usage:  tomahawk blocks [options] -i <in.twk> [-o <blocks.tsv>]\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o FILE   output text file (- for stdout; default: -)\n"
+	"  -w INT    longest block, and the window of the computation, in bases (default: 200000)\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value (default: 0)\n"
+	"  -P FLOAT  accepted only as 1: blocks look at every record, Fisher's test is not run\n"
+	"  --ci-out PREFIX  also write the bounds in band storage: PREFIX.lo.npy, PREFIX.hi.npy (uint8, 255: no\n"
+	"            record), PREFIX.indptr.npy, PREFIX.first.npy and PREFIX.variants.tsv, as ldmatrix --band\n"
+	"  --keep / --remove FILE, --extract / --exclude FILE, --maf, --max-maf, --mac, --geno, --hwe: as for calc\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"  (-c / -C are refused: a block needs every pair inside it)\n"
+	"Output: '#' header lines, then per block, in file order:\n"
+	"        contig <TAB> first pos <TAB> last pos <TAB> span <TAB> variants <TAB> strong pairs <TAB> recombinant pairs\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+static const struct option BLOCKS_LONG_OPTIONS[] = {
+	{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
+	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
+	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
+	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
+	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, VARIANT_SELECTION_LONG_OPTIONS,
+	{"ci-out", required_argument, 0, 1020}, {0, 0, 0, 0}};
+static Took blocks_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_block_settings& blocks) {
+	if (c != 1020) return declined;
+	blocks.ci_out = arg;
+	return !blocks.ci_out.empty() || fail("--ci-out wants a prefix") ? took : failed;
+}
+// (Reached by its name, but not a row of ENTRIES: the list of `tomahawk` without arguments and the "Illegal command" sentence answer as
+// they always have, tests/golden/cli_transcript.json - as `ldmatrix --band` stays out of ldmatrix's usage.)
+static const Command<tomahawk::twk_block_settings> BLOCKS = {
+	"blocks", "  blocks   haplotype blocks (Gabriel et al.), D' confidence bounds and block walk on the GPU\n", blocks_usage,
+	"i:o:t:puP:r:w:I:c:C:?", BLOCKS_LONG_OPTIONS, 0, {{"cC", "Cannot find the blocks of a part of the pair space (-c / -C): a block needs every pair inside it"}},
+	"Cannot find blocks with a cutoff P-value below 1: blocks look at every record and Fisher's exact test is not run", blocks_option,
+	nullptr,
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_block_settings& blocks) { return ld.Blocks(settings, blocks); }};
+
 // `tomahawk relationship`: the sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU.  The reference's name and its -i / -I;
 // its numbers are not reproduced (include/twk_hip.h, twk_hip_relationship).
 static void relationship_usage() {
@@ -976,6 +1030,7 @@ static int run_main(int argc, char** argv) {
 	mallopt(M_TRIM_THRESHOLD, 1 << 30);
 	tomahawk::LITERAL_COMMAND_LINE = "tomahawk";
 	for (int i = 1; i < argc; ++i) tomahawk::LITERAL_COMMAND_LINE += " " + std::string(argv[i]);
+	if (strcmp(argv[1], BLOCKS.name) == 0) return engine<BLOCKS>(argc, argv);
 	for (const Entry& e : ENTRIES)
 		if (strcmp(argv[1], e.name) == 0 || (e.alias && strcmp(argv[1], e.alias) == 0) || (e.by_prefix && strncmp(argv[1], e.name, strlen(e.name)) == 0)) return e.main(argc, argv);
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }

@@ -1240,6 +1240,28 @@ struct ReduceCommand {
 		std::string nothing;
 		return finish(os, nothing, "the matrix");
 	}
+	// The band writer: 1-D arrays as NumPy files PREFIX<suffix>, and the rows' variants as PREFIX.variants.tsv ("contig <TAB> pos").
+	struct NpyArray { const char* suffix; const char* descr; uint64_t items; const void* data; size_t bytes; };
+	bool npy_files(const std::string& prefix, std::initializer_list<NpyArray> arrays) {
+		std::ofstream out;
+		for (const NpyArray& a : arrays) {
+			if (!open(out, prefix + a.suffix, std::ios::binary)) return false;
+			if (!npy(out, a.descr, a.items, 0, a.data, a.bytes)) return false;
+			out.close();
+		}
+		return true;
+	}
+	bool variant_list(const std::string& prefix) {
+		std::ofstream vfile;
+		if (!open(vfile, prefix + ".variants.tsv")) return false;
+		std::string text;
+		for (uint32_t v = 0; v < M; ++v) {
+			place(text, v);
+			text += '\n';
+			spill(vfile, text);
+		}
+		return finish(vfile, text, "the variant list");
+	}
 	void all_done() const {
 		std::cerr << stamp("LOG", "PROGRESS") << "All done..." << elapsed_string(std::chrono::duration<double>(clock::now() - t_load).count()) << "!" << std::endl;
 	}
@@ -1725,7 +1747,7 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 	const uint32_t M = cmd.M;
 	uint64_t np = 0, n_recs = 0, nnz = 0;
 	double sec = 0;
-	std::ofstream file, vfile;
+	std::ofstream file;
 	if (ms.band) {
 		// the band: its layout first, which sizes the values; then the three arrays of a CSR matrix, each a NumPy file
 		if (M > 0x7FFFFFFFu) { std::cerr << stamp("ERROR") << "Too many variants for PREFIX.first.npy (int32)..." << std::endl; return false; }
@@ -1738,15 +1760,10 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 			return twk_hip_ld_matrix_band(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, values.data(), nnz, first.data(), indptr.data(), &n_recs, &np);
 		}, &np);
 		if (sec < 0) return false;
-		const struct { const char* suffix; const char* descr; uint64_t items; const void* data; size_t bytes; } arrays[3] = {
+		if (!cmd.npy_files(settings.out, {
 			{".values.npy", "<f4", nnz, values.data(), values.size() * sizeof(float)},
 			{".indptr.npy", "<i8", (uint64_t)M + 1, indptr.data(), indptr.size() * sizeof(uint64_t)},      // (below 2^63: the same bits)
-			{".first.npy", "<i4", M, first.data(), first.size() * sizeof(uint32_t)}};                       // (below 2^31)
-		for (const auto& a : arrays) {
-			if (!cmd.open(file, settings.out + a.suffix, std::ios::binary)) return false;
-			if (!cmd.npy(file, a.descr, a.items, 0, a.data, a.bytes)) return false;
-			file.close();
-		}
+			{".first.npy", "<i4", M, first.data(), first.size() * sizeof(uint32_t)}})) return false;        // (below 2^31)
 	} else {
 		std::vector<float> m((size_t)M * M);
 		sec = cmd.call("twk_hip_ld_matrix", [&] { return twk_hip_ld_matrix(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, cmd.options, (uint32_t)settings.l_window, ms.stat, ms.fill, m.data(), M, &n_recs, &np); }, &np);
@@ -1756,16 +1773,76 @@ bool twk_ld::Matrix(const twk_ld_settings& s, const twk_matrix_settings& ms) {
 		file.close();
 	}
 	mImpl->n_records = n_recs;
-	if (!cmd.open(vfile, settings.out + ".variants.tsv")) return false;
-	std::string text;
-	for (uint32_t v = 0; v < M; ++v) {
-		cmd.place(text, v);
-		text += '\n';
-		cmd.spill(vfile, text);
-	}
-	if (!cmd.finish(vfile, text, "the variant list")) return false;
+	if (!cmd.variant_list(settings.out)) return false;
 	std::cerr << stamp("LOG") << "Matrix of " << LD_STATS.name(ms.stat) << ": " << pretty(M) << " x " << pretty(M) << (ms.band ? ", a band of " + pretty(nnz) + " entries" : std::string()) << ", " << pretty(n_recs) << " pairs with a value among "
 	          << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+	cmd.all_done();
+	return true;
+}
+
+// `tomahawk blocks`: haplotype blocks of the selection by the rule of Gabriel et al. (twk_hip_ld_blocks: the D' confidence bounds of the
+// records Compute would write, in band storage, and the blocks selected from them, all on the GPU), as text: one line per block.  With
+// bs.ci_out the bounds themselves are written through the band writer (twk_hip_ld_dprime_ci_band: a second engine call with the same
+// arguments, the same bytes).  The input is loaded exactly as Prune loads it; one GPU; the whole triangle (no -c / -C); the window is
+// always on.  Not in the reference.
+bool twk_ld::Blocks(const twk_ld_settings& s, const twk_block_settings& bs) {
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "Blocks look at every record", "Cannot find the blocks of a part of the pair space: a block needs every pair inside it")) return false;
+	if (!settings.window) { settings.window = true; settings.l_window = 200000; }
+	const twk_hip_block_params par{bs.strong_lo, bs.strong_hi, bs.recomb_hi, bs.strong_lo_2, bs.strong_lo_34, bs.inform_permille, bs.max_span_2, bs.max_span_3};
+	if (par.strong_lo > 100 || par.strong_hi > 100 || par.recomb_hi > 100 || par.strong_lo_2 > 100 || par.strong_lo_34 > 100 || par.recomb_hi > par.strong_hi || par.inform_permille > 1000) {
+		std::cerr << stamp("ERROR") << "The block thresholds are percentages up to 100 with recomb-hi <= strong-hi, and a fraction in permille up to 1000..." << std::endl;
+		return false;
+	}
+	if (settings.l_window <= 0) { std::cerr << stamp("ERROR") << "Blocks need a window of at least one base (-w): it is the longest block..." << std::endl; return false; }
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
+	const uint32_t M = cmd.M;
+	if (M > 0x7FFFFFFFu) { std::cerr << stamp("ERROR") << "Too many variants..." << std::endl; return false; }
+	std::vector<uint32_t> block_of(M, TWK_HIP_NO_BLOCK), first(M / 2 + 1), last(M / 2 + 1), n_strong(M / 2 + 1), n_recomb(M / 2 + 1);
+	uint64_t np = 0, n_blocks = 0, n_cand = 0, n_inf = 0;
+	const double sec = cmd.call("twk_hip_ld_blocks", [&] {
+		return twk_hip_ld_blocks(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, (uint32_t)settings.l_window, &par, block_of.data(), first.data(), last.data(), n_strong.data(), n_recomb.data(),
+		                         &n_blocks, &n_cand, &n_inf, &np);
+	}, &np);
+	if (sec < 0) return false;
+	mImpl->n_records = n_inf;
+	if (!bs.ci_out.empty()) {
+		std::vector<uint32_t> bfirst(M);
+		std::vector<uint64_t> indptr((size_t)M + 1);
+		if (!hip_ok(cmd.ctx, twk_hip_bandmat_layout(cmd.ctx, 0, M, (uint32_t)settings.l_window, bfirst.data(), indptr.data()), "twk_hip_bandmat_layout")) return false;
+		const uint64_t nnz = indptr[M];
+		std::vector<uint8_t> lo((size_t)nnz), hi((size_t)nnz);
+		uint64_t n_recs = 0, np2 = 0;
+		if (cmd.call("twk_hip_ld_dprime_ci_band", [&] {
+			return twk_hip_ld_dprime_ci_band(cmd.ctx, cmd.mode, &cmd.f, 0, M, 0, (uint32_t)settings.l_window, lo.data(), hi.data(), nnz, bfirst.data(), indptr.data(), &n_recs, &np2);
+		}, nullptr) < 0) return false;
+		if (!cmd.npy_files(bs.ci_out, {
+			{".lo.npy", "|u1", nnz, lo.data(), lo.size()},
+			{".hi.npy", "|u1", nnz, hi.data(), hi.size()},
+			{".indptr.npy", "<i8", (uint64_t)M + 1, indptr.data(), indptr.size() * sizeof(uint64_t)},      // (below 2^63: the same bits)
+			{".first.npy", "<i4", M, bfirst.data(), bfirst.size() * sizeof(uint32_t)}})) return false;     // (below 2^31)
+		if (!cmd.variant_list(bs.ci_out)) return false;
+	}
+	std::ostream* const os = cmd.open_text();
+	if (!os) return false;
+	cmd.header(*os, "blocks");
+	char line[256];
+	snprintf(line, sizeof(line), "##thresholds=strong_lo=%u,strong_hi=%u,recomb_hi=%u,strong_lo_2=%u,strong_lo_34=%u,inform_permille=%u,max_span_2=%u,max_span_3=%u\n",
+	         par.strong_lo, par.strong_hi, par.recomb_hi, par.strong_lo_2, par.strong_lo_34, par.inform_permille, par.max_span_2, par.max_span_3);
+	*os << line;
+	snprintf(line, sizeof(line), "##blocks=%llu,candidates=%llu,informative=%llu,total=%u\n", (unsigned long long)n_blocks, (unsigned long long)n_cand, (unsigned long long)n_inf, M);
+	*os << line << "#contig\tfirst_pos\tlast_pos\tspan\tvariants\tstrong\trecombinant\n";
+	std::string text;
+	for (uint64_t k = 0; k < n_blocks; ++k) {
+		const uint32_t a = first[k], b = last[k];
+		cmd.place(text, a);
+		snprintf(line, sizeof(line), "\t%u\t%u\t%u\t%u\t%u\n", mImpl->pos[b] + 1, mImpl->pos[b] - mImpl->pos[a], b - a + 1, n_strong[k], n_recomb[k]);
+		text += line;
+		cmd.spill(*os, text);
+	}
+	if (!cmd.finish(*os, text, "the blocks")) return false;
+	std::cerr << stamp("LOG") << "Blocks: " << pretty(n_blocks) << " among " << pretty(M) << " variants, from " << pretty(n_cand) << " candidate pairs of " << pretty(n_inf)
+	          << " informative ones among " << pretty(np) << " variant comparisons. " << elapsed_string(sec) << std::endl;
 	cmd.all_done();
 	return true;
 }

@@ -20,6 +20,7 @@ MODE_PHASED, MODE_UNPHASED, MODE_AUTO = 1, 2, 3
 OPT_WINDOW, OPT_KEEP_LOW_AC, OPT_REF_COMPAT, OPT_R2_SCREEN = 1, 2, 4, 8
 NO_CLUMP = 0xFFFFFFFF      # TWK_HIP_NO_CLUMP: ld_clump's index_of for a variant in no clump
 NO_PARTNER = 0xFFFFFFFF    # TWK_HIP_NO_PARTNER: ld_topk's idx for a slot that is not used
+NO_BLOCK = 0xFFFFFFFF      # TWK_HIP_NO_BLOCK: ld_blocks' block_of for a variant in no block
 TOPK_MAX = 32              # TWK_HIP_TOPK_MAX
 STAT_R, STAT_R2, STAT_D, STAT_DPRIME = 0, 1, 2, 3      # TWK_HIP_STAT_*: the statistic ld_matrix fills in
 REL_IBS, REL_IBS0, REL_KING = 0, 1, 2      # TWK_HIP_REL_*: the statistic relationship fills in
@@ -161,6 +162,23 @@ class Filters:
         return _Filters(self.minR2, self.maxR2, self.minDprime, self.maxDprime, self.minP)
 
 
+@dataclass
+class BlockParams:
+    """twk_hip_block_params: the thresholds of ld_blocks (percent, permille, base pairs), Gabriel et al.'s by default."""
+    strong_lo: int = 70
+    strong_hi: int = 98
+    recomb_hi: int = 90
+    strong_lo_2: int = 80
+    strong_lo_34: int = 50
+    inform_permille: int = 950
+    max_span_2: int = 20000
+    max_span_3: int = 30000
+
+    def as_tuple(self):
+        return (self.strong_lo, self.strong_hi, self.recomb_hi, self.strong_lo_2, self.strong_lo_34, self.inform_permille,
+                self.max_span_2, self.max_span_3)
+
+
 class HipError(RuntimeError):
     def __init__(self, code: int, what: str, detail: str = ""):
         super().__init__(f"{what}: error {code}" + (f" ({detail})" if detail else ""))
@@ -248,6 +266,12 @@ def load_library() -> C.CDLL:
     lib.twk_hip_ld_matrix_band.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                            C.c_int32, C.c_float, p, C.c_uint64, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_bandmat_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_dprime_ci_band.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                              p, p, C.c_uint64, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_ld_blocks.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, p,
+                                      p, p, p, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_blocks_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    lib.twk_hip_blocks_stages.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.twk_hip_ld_topk.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
                                     C.POINTER(C.c_uint64)]
@@ -874,6 +898,53 @@ class HipLd:
         ms, b = C.c_double(0), C.c_uint64(0)
         self._check(self._lib.twk_hip_bandmat_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_bandmat_last")
         return {"copy_ms": ms.value, "band_bytes": b.value}
+
+    def ld_dprime_ci_band(self, mode: int, filters: Filters, l_window: int, a0: int = 0, n: int | None = None, tile_variants: int = 0):
+        """The confidence bounds of D' in band storage (twk_hip_ld_dprime_ci_band): for every in-band (u, v) of bandmat_layout's layout
+        for l_window, lo / hi [indptr[u] + (v - first[u])] hold the bounds in percent (0 .. 100) of the pair's D' by a likelihood scan of
+        the 2 x 2 table of the record ld_region would report, and 255 / 255 where it would report none, and on the diagonal.  Both
+        orientations are stored.  filters.minP must be >= 1.
+        -> (lo uint8[indptr[n]], hi uint8[indptr[n]], first uint32[n], indptr uint64[n + 1], n_records, n_pairs)."""
+        n = self.n_variants - a0 if n is None else n
+        _, layout_ptr = self.bandmat_layout(l_window, a0, n)          # (sizes the arrays; refuses what the call would refuse about the slice)
+        nnz = int(layout_ptr[-1])
+        lo, hi = np.empty(nnz, dtype=np.uint8), np.empty(nnz, dtype=np.uint8)
+        first = np.zeros(n, dtype=np.uint32)
+        indptr = np.zeros(n + 1, dtype=np.uint64)
+        nrec, npairs = C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_dprime_ci_band(self._ctx, mode, C.byref(f), a0, n, tile_variants, l_window, lo.ctypes.data, hi.ctypes.data,
+                                                        nnz, first.ctypes.data, indptr.ctypes.data, C.byref(nrec), C.byref(npairs)),
+                    "twk_hip_ld_dprime_ci_band")
+        return lo, hi, first, indptr, nrec.value, npairs.value
+
+    def ld_blocks(self, mode: int, filters: Filters, l_window: int = 200000, params: BlockParams | None = None, a0: int = 0,
+                  n: int | None = None, tile_variants: int = 0):
+        """Haplotype blocks by the rule of Gabriel et al. (twk_hip_ld_blocks) over the variants [a0, a0 + n) in file order, from the
+        bounds of ld_dprime_ci_band with the same arguments, selected on the device.  l_window is also the longest block in base pairs;
+        params: a BlockParams (None: the defaults).  filters.minP must be >= 1.
+        -> (block_of uint32[M], first uint32[B], last uint32[B], n_strong uint32[B], n_recomb uint32[B], n_candidates,
+        n_informative, n_pairs); block_of is NO_BLOCK where a variant lies in no block, else its block's first variant."""
+        M = self.n_variants
+        n = M - a0 if n is None else n
+        block_of = np.full(M, NO_BLOCK, dtype=np.uint32)
+        per = [np.zeros(max(n // 2, 1), dtype=np.uint32) for _ in range(4)]
+        nb, nc, ni, npairs = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        par = None if params is None else np.array(params.as_tuple(), dtype=np.uint32)
+        self._check(self._lib.twk_hip_ld_blocks(self._ctx, mode, C.byref(f), a0, n, tile_variants, l_window, None if par is None else par.ctypes.data,
+                                                block_of.ctypes.data, *(x.ctypes.data for x in per), C.byref(nb), C.byref(nc), C.byref(ni),
+                                                C.byref(npairs)), "twk_hip_ld_blocks")
+        return (block_of, *(x[:nb.value].copy() for x in per), nc.value, ni.value, npairs.value)
+
+    def blocks_last(self) -> dict:
+        """Of the last ld_blocks call (twk_hip_blocks_last, twk_hip_blocks_stages): the device time of the walk kernel and of the stages
+        in front of it (prefix counts + candidate counts + scan, the emitting pass, the sort), and the size of the lo / hi band."""
+        ms, b = C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_blocks_last(self._ctx, C.byref(ms), C.byref(b)), "twk_hip_blocks_last")
+        counts, emit, sort = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._check(self._lib.twk_hip_blocks_stages(self._ctx, C.byref(counts), C.byref(emit), C.byref(sort)), "twk_hip_blocks_stages")
+        return {"walk_ms": ms.value, "band_bytes": b.value, "counts_ms": counts.value, "emit_ms": emit.value, "sort_ms": sort.value}
 
     def ld_topk(self, mode: int, filters: Filters, k: int, stat: int = STAT_R2, a0: int = 0, nA: int | None = None, b0: int = 0,
                 nB: int | None = None, triangle: bool = True, part: int = 0, n_parts: int = 1, tile_variants: int = 0, window: int = 0,
