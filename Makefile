@@ -151,7 +151,8 @@ annot-check:
 	./build/annot_term_check
 
 # Who may take which form of a count launch (csrc/hip/ld_form.h): decide_form over every combination of facts and grants, the transitions of
-# CallForms::gave_up, the ladder a redone tile descends and the choice of the two-product launches' row operand (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
+# CallForms::gave_up, the ladder a redone tile descends, the choice of the two-product launches' row operand, the thresholds and the sample ladder
+# (decide_wants) under scripted samplers (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
 form-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/form_check.cpp -o build/form_check

@@ -9,11 +9,11 @@ writes tests/golden/form_trace.json (or out.json) on an MI355X.  tests/test_gpu_
 build and compares.  The fixture is recorded from the commit BEFORE a change to how the engine decides a launch's form, never from the code
 under test; it uses nothing but the Python binding as that commit has it.
 
-Per call: the launch log as the sequence of kinds (run lengths), the launches' row_pairs and candidates, n_pairs, n_records, a SHA-256 of
-the records sorted by (idxA, idxB), and the timing's work counters.  Every scenario is run twice and only what both runs agree on is
-kept: a fused launch's candidate count may include slots a wave reserved and did not use, so it need not repeat.  The kinds, every
-*_launches counter, n_pairs, n_records and the hash must repeat - the generator stops if they do not.  What was dropped is listed in the
-fixture."""
+Per call: the launch log as the sequence of kinds (run lengths), the launches' row_pairs and candidates, their carrier, one, prefix_chunks
+and prefix_chunks_full columns, n_pairs, n_records, a SHA-256 of the records sorted by (idxA, idxB), and the timing's work counters.  Every
+scenario is run twice and only what both runs agree on is kept: a fused launch's candidate count may include slots a wave reserved and did
+not use, so it need not repeat.  The kinds, every *_launches counter, the launches' carrier, one and prefix columns, n_pairs, n_records and
+the hash must repeat - the generator stops if they do not.  What was dropped is listed in the fixture."""
 import hashlib
 import json
 import os
@@ -31,10 +31,12 @@ from tests import util                                            # noqa: E402
 
 FIXTURE = os.path.join(HERE, "form_trace.json")
 ORDER = ["idxA", "idxB"]
-# (tests/test_gpu_lists.py: WORK_FIELDS, and the two-product launches)
+# (tests/test_gpu_lists.py: WORK_FIELDS, and the two-product launches with their carrier rows, their one product and their stops)
 WORK_FIELDS = ("count_launches", "fused_launches", "three_launches", "list_launches", "probe_launches", "row_pairs", "three_row_pairs",
-               "list_pairs", "probe_pairs", "variant_pairs", "candidates", "recount_candidates", "stats_launches", "two_launches")
-MUST_REPEAT = ("kinds", "n_pairs", "n_records", "sha256")        # ... and every *_launches counter
+               "list_pairs", "probe_pairs", "variant_pairs", "candidates", "recount_candidates", "stats_launches", "two_launches",
+               "prefix_launches", "carrier_launches", "one_launches", "prefix_chunks", "prefix_chunks_full")
+LAUNCH_FORM_COLUMNS = ("carrier", "one", "prefix_chunks", "prefix_chunks_full")      # of the launch log, beside kind, row_pairs and candidates
+MUST_REPEAT = ("kinds", "n_pairs", "n_records", "sha256") + LAUNCH_FORM_COLUMNS      # ... and every *_launches counter
 LONG_LOG = 256                                                    # a longer list of row_pairs / candidates is stored as its hash
 _DATA = {}
 
@@ -66,11 +68,13 @@ def trace(hip, name, call):
             kinds[-1][1] += 1
         else:
             kinds.append([int(s["kind"]), 1])
-    return {"call": name, "kinds": kinds, "launches_seen": int(seen),
-            "row_pairs": _column([int(s["row_pairs"]) for s in stats]), "candidates": _column([int(s["candidates"]) for s in stats]),
-            "n_pairs": int(n_pairs), "n_records": int(n_records),
-            "sha256": _sha(np.sort(recs, order=ORDER).tobytes()) if recs is not None else None,
-            "work": {k: int(tm[k]) for k in WORK_FIELDS}}
+    entry = {"call": name, "kinds": kinds, "launches_seen": int(seen),
+             "row_pairs": _column([int(s["row_pairs"]) for s in stats]), "candidates": _column([int(s["candidates"]) for s in stats])}
+    entry.update({key: _column([int(s[key]) for s in stats]) for key in LAUNCH_FORM_COLUMNS})
+    entry.update({"n_pairs": int(n_pairs), "n_records": int(n_records),
+                  "sha256": _sha(np.sort(recs, order=ORDER).tobytes()) if recs is not None else None,
+                  "work": {k: int(tm[k]) for k in WORK_FIELDS}})
+    return entry
 
 
 class _Options:
@@ -171,7 +175,8 @@ def default_mode_with_missing_data(hip):
 
 def sampling(hip):
     """tests/test_gpu_three.py::test_sampling_decides_between_three_and_four_products_on_long_rows, its short rows: unlinked variants take
-    three products, a cohort rich in LD four; the samples are in neither log nor timing."""
+    three products, a cohort rich in LD four; the samples are in neither log nor timing.  tile_variants = 256 on the 3000-variant cohort:
+    78 launches, more than 64, so that every second one is sampled and its neighbour follows it."""
     from tests.test_gpu_configs import _cohort_alleles
     rng = np.random.default_rng(5)
     f, out = T.Filters(minR2=0.1), []
@@ -179,6 +184,7 @@ def sampling(hip):
     out.append(trace(hip, "unlinked", _all(hip, T.MODE_UNPHASED, f)))
     util.upload(hip, _cohort_alleles(3000, 2504, 99))
     out.append(trace(hip, "cohort", _all(hip, T.MODE_UNPHASED, f)))
+    out.append(trace(hip, "cohort, tile_variants = 256", _all(hip, T.MODE_UNPHASED, f, tile_variants=256)))
     return out
 
 
@@ -195,8 +201,25 @@ def reduce_between_record_calls(hip):
     return out
 
 
+def one_product_walk(hip):
+    """tests/test_gpu_one_product.py, its smallest shape (137 chunks with a ragged last one, one_rows = 128): rows long enough for the carrier
+    plane, one product a pair and the stops.  Each of the walk's options off or forced in turn; cand_cap = 8 floods every screened launch's
+    list, so that each is redone down the ladder; the call after that starts with everything again."""
+    from tests.test_gpu_one_product import _iid22
+    util.upload(hip, _iid22(700, 140_000, 31))
+    f, out = T.Filters(minR2=0.1), []
+    with _Options(hip, one_rows=128):
+        out.append(trace(hip, "default", _all(hip, T.MODE_UNPHASED, f)))
+        for name, kw in (("one = 0", dict(one=0)), ("one = 2", dict(one=2)), ("prefix = 0", dict(prefix=0)),
+                         ("prefix = 2, prefix_stop = 24", dict(prefix=2, prefix_stop=24)), ("two = 2", dict(two=2)), ("cand_cap = 8", dict(cand_cap=8))):
+            with _Options(hip, **kw):
+                out.append(trace(hip, name, _all(hip, T.MODE_UNPHASED, f)))
+        out.append(trace(hip, "default again", _all(hip, T.MODE_UNPHASED, f)))
+    return out
+
+
 SCENARIOS = {s.__name__: s for s in (two_product_walk, three_product_give_up, fused_give_up, band_launch_outgrown,
-                                     default_mode_with_missing_data, sampling, reduce_between_record_calls)}
+                                     default_mode_with_missing_data, sampling, reduce_between_record_calls, one_product_walk)}
 
 
 def run(hip, name):

@@ -1,8 +1,10 @@
 """Which form every launch takes, call by call: the scenarios of tests/golden/make_golden_form_trace.py - a two-product list that overflows, a
 three-product and a fused list that overflow, a band launch that outgrows its buffers, the three stages of a default-mode call, the samples'
-decision, a reduce call between two record calls - replayed on the current build and compared with tests/golden/form_trace.json, which the
-commit before the forms' permissions became values passed down (csrc/hip/ld_form.h) recorded: the kinds of the launches in order, their
-row_pairs and candidates, n_pairs, n_records, the records' hash and the timing's work counters."""
+decision (every launch's own, and every second launch's of a plan of 78), a reduce call between two record calls, the carrier, one-product
+and prefix launches of the two-product walk on long rows with each of their options off or forced - replayed on the current build and compared
+with tests/golden/form_trace.json, which the commit before the sample ladder moved into csrc/hip/ld_form.h (decide_wants) recorded: the kinds
+of the launches in order, their row_pairs and candidates, their carrier, one and prefix columns, n_pairs, n_records, the records' hash and the
+timing's work counters."""
 import pytest
 
 from tests.golden import make_golden_form_trace as trace
@@ -53,6 +55,22 @@ def test_the_fixture_holds_the_transitions_it_is_for():
     sampled = s["sampling"]
     assert _kinds(sampled["unlinked"]) == [4] and _kinds(sampled["cohort"]) == [3]
     assert sampled["unlinked"]["launches_seen"] == sampled["unlinked"]["work"]["count_launches"] == 1       # the samples are in neither
+    many = sampled["cohort, tile_variants = 256"]
+    assert many["launches_seen"] == many["work"]["count_launches"] == 78 > 64 and set(_kinds(many)) == {3, 4}      # every second launch sampled, both answers given
+    assert many["sha256"] == sampled["cohort"]["sha256"]
     between = s["reduce_between_record_calls"]
     assert set(_kinds(between["score"])) == {0} and between["score"]["work"]["fused_launches"] == 0
     assert {k: v for k, v in between["records"].items() if k != "call"} == {k: v for k, v in between["records again"].items() if k != "call"}
+    one = s["one_product_walk"]
+    assert not [name for name in fixture["dropped"] if name.startswith("one_product_walk")]                 # no fused launch: everything repeats
+    default = one["default"]
+    assert sum(default["one"]) == default["work"]["one_launches"] >= 1 and default["work"]["carrier_launches"] > default["work"]["one_launches"]
+    assert default["work"]["prefix_launches"] > 0 and 0 < default["work"]["prefix_chunks"] < default["work"]["prefix_chunks_full"]
+    assert one["one = 0"]["work"]["one_launches"] == 0 and not any(one["one = 0"]["one"])
+    assert len({e["sha256"] for e in one.values()}) == 1 and len(one) == 8
+    assert one["prefix = 0"]["work"]["prefix_launches"] == 0 and _kinds(one["two = 2"]).count(5) > _kinds(default).count(5)
+    capped = one["cand_cap = 8"]                          # the first launch's list holds 8 of its 28 candidates: redone, the next entry of the log, rung by rung
+    assert _kinds(capped)[:5] == [5, 5, 5, 1, 0] and capped["candidates"][:4] == [28] * 4 and capped["one"][:3] == [1, 1, 0] and capped["carrier"][:3] == [1, 1, 1]
+    assert capped["prefix_chunks_full"][0] > 0 == capped["prefix_chunks_full"][1]       # ... first over whole rows in the same form
+    again = one["default again"]
+    assert _kinds(again) == _kinds(default) and again["work"] == default["work"] and all(again[key] == default[key] for key in trace.LAUNCH_FORM_COLUMNS)

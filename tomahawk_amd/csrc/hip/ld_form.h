@@ -1,9 +1,15 @@
 // The form of a count launch - which contraction, which math behind it - and who may take which: what a launch is (LaunchForm), what its
 // owner allows it (FormGrant), what the plan, the filters and the options fix (FormFacts), what the running call has not yet given up
-// (CallForms).  Host-only, no HIP: twk_hip.hip's launch_form gathers the facts and calls decide_form(); csrc/tools/form_check.cpp plays every
-// combination on the host (make form-check, tests/test_form_cpu.py).
+// (CallForms), what a launch's owner wants for it (LaunchWants), the numbers that call a launch or its sample poor or rich in candidates, and the
+// samples that decide the wants of a region's launches (decide_wants).  Host-only, no HIP: twk_hip.hip's launch_form gathers the facts and calls
+// decide_form(), its RegionRun gathers the ladder's facts, runs the samples decide_wants() asks for and keeps the wants;
+// csrc/tools/form_check.cpp plays every combination on the host (make form-check, tests/test_form_cpu.py).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+#include <algorithm>
+#include <vector>
+#include "../../../include/twk_hip.h"
 
 namespace twk {
 
@@ -20,7 +26,7 @@ struct LaunchForm {
 	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
 	bool two = false;              // the two-product form (HH + HQ through a count matrix, S bounded from the margins): never fused, never with `three`
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
-	bool sample = false;           // a density sample (RegionRun::decide_three_by_samples): its count kernel runs under its own name (k_count3_list_t<.., 1>), so that a
+	bool sample = false;           // a density sample (decide_wants below): its count kernel runs under its own name (k_count3_list_t<.., 1>), so that a
 	                               // kernel trace's statistics of the real launches are not diluted by half-millisecond ones
 	bool carrier = false;          // a two-product launch whose row operand is the carrier plane H | Q (CH + CQ in place of HH + HQ; ld_two_screen.h): an attribute of
 	                               // `two`, never set without it
@@ -30,6 +36,10 @@ struct LaunchForm {
 	Reduce reduce = Reduce::none;  // the epilogue in place of math, Fisher and records (launch_reduce): always through a matrix
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
+inline bool operator==(const LaunchForm& a, const LaunchForm& b) {
+	return a.two_pass == b.two_pass && a.fused == b.fused && a.unphased == b.unphased && a.three == b.three && a.two == b.two && a.keep_three == b.keep_three &&
+	       a.sample == b.sample && a.carrier == b.carrier && a.one == b.one && a.prefix == b.prefix && a.reduce == b.reduce;
+}
 
 // Rows of at most this many K chunks (32 words each: N <= 65,536 phased, N <= 131,072 unphased) take the fused
 // count -> screen kernel.  Up to 16 chunks a tile is never worth splitting, and the C round trip plus the
@@ -44,6 +54,10 @@ constexpr uint32_t FUSED_MAX_CHUNKS = 128;
 // `carrier`: the owner holds carrier rows for this launch's row variants (carrier_operand below) - the row operand of its two-product form, if it takes it.
 // `one`: the walk's owner planned this launch in front of its rows' one_end (ld_plan.h) and holds carrier rows for its column variants too.
 struct FormGrant { bool fused = true, three = true, two = false, sample = false, prefix = false, carrier = false, one = false; };
+// What the owner of a launch wants for it, before the call has its say (CallForms::grant): three products unless the launch's sample was dense
+// in candidates; two products, stops and one product where its sample in that form was poor in them (decide_wants below), or where an option
+// forces them; `carrier` where the owner holds carrier rows for the region's two-product launches.
+struct LaunchWants { bool three = true, two = false, prefix = false, carrier = false, one = false; };
 // What the tile plan, the filters and the options fix, whoever grants what.
 struct FormFacts {
 	bool two_pass = false;
@@ -97,8 +111,22 @@ struct CallForms {
 	// ... and allows a launch, whose owner wants three / two products for it (and stops for its tiles)
 	// (the carrier plane is no form of the call's to give up: it goes where the two-product form goes)
 	// (one product is: a launch that overflows or is too rich in that form ends it for the call, and nothing else)
-	FormGrant grant(bool want_three, bool want_two, bool want_prefix = false, bool want_carrier = false, bool want_one = false) const {
-		return FormGrant{fused, three && want_three, two && want_two, false, prefix && want_prefix, two && want_two && want_carrier, one && two && want_two && want_carrier && want_one};
+	FormGrant grant(const LaunchWants& w) const {
+		FormGrant g;
+		g.fused = fused; g.three = three && w.three; g.two = two && w.two; g.sample = false; g.prefix = prefix && w.prefix;
+		g.carrier = g.two && w.carrier; g.one = one && g.carrier && w.one;
+		return g;
+	}
+	// ... a density sample in the form `w` (decide_wants): three products granted - a sample is only taken where the call allows them; and its own
+	// overflow or richness decides its launch, not the call
+	FormGrant sample_grant(const LaunchWants& w) const { FormGrant g = grant(w); g.three = true; g.sample = true; return g; }
+	// ... a tile that is redone synchronously under `given` (run_tile_sync), narrowed by what the call has given up since: over whole rows - never
+	// the prefix - and a two-product tile keeps its row operand, and its one product
+	FormGrant redo_grant(const FormGrant& given) const {
+		LaunchWants w; w.three = given.three; w.two = given.two; w.carrier = given.carrier; w.one = given.one;
+		FormGrant g = grant(w);
+		g.fused = g.fused && given.fused; g.sample = given.sample;
+		return g;
 	}
 	// A launch of form `was`, given `given`, is through: a list that overflowed (cand_overflow) or held more candidates than the recount is worth
 	// (too_rich) ends the form for the rest of the call - but a form the launch was not given is not taken from the call on its account.
@@ -112,5 +140,109 @@ struct CallForms {
 		if (too_rich && was.three && !was.keep_three) three = three && !given.three;
 	}
 };
+
+// ---- the numbers that decide a launch's fate, side by side ---------------------------------------------------------------------------------
+// A sample is poor in candidates - its launch takes the form the sample ran in - if at most 1 pair in `one_in` of it is a candidate ...
+constexpr bool sample_poor(unsigned long long cand, unsigned long long pairs, unsigned long long one_in) { return cand * one_in <= pairs; }
+// ... 1 in 256: the two- and one-product samples, the samples with stops and the three-product sample of a launch through a matrix
+constexpr unsigned long long SAMPLE_ONE_IN = 256;
+// ... 1 in 128: the three-product sample of a fused launch, whose recount reads short rows from L2.  (Fused launches - short rows - keep their
+// candidates whatever their number, but past ~1.2 % of the pairs the recount costs more than the third product saves: 2,504 samples, -u -w 1000000,
+// 2.9 % candidates: 27.4 + 30.3 ms of count kernel and math with three products in the first of two launches, 30 + 21 ms with four in both.)
+constexpr unsigned long long SAMPLE_ONE_IN_THREE_FUSED = 128;
+// The candidate list of a two- or three-product launch through a matrix (enqueue_tile): room for at most 1/128 of the tile's pairs - a candidate's
+// recount streams its four rows once more, ~25 pairs' worth of contraction, so a launch with more candidates than that is cheaper in the
+// four-product form (overflow -> CallForms::gave_up -> redone).
+inline unsigned long long cand_list_entries(unsigned long long pairs) { return std::max<unsigned long long>(pairs / 128, 4096); }
+// A three-product launch this rich in candidates pays more for their recount than the fourth product costs: the rest of the call in the
+// four-product forms (finish_tile -> Launch::too_rich -> CallForms::gave_up).  Measured at 2,504 samples, -u -w 1000000 (2.9 % of the pairs
+// candidates): count kernel 32.1 -> 27.3 ms, but 58 M recounts at 0.16 ns each (four 320-byte rows from L2 per candidate: 8 TB/s) add 9.3 ms to the
+// math; the two meet near 1.2 %.  (Against the variant pairs of the tiles the launch contracted - four plane-row pairs each - not the launch's
+// rectangle: a window launch's rectangle is mostly outside the window.)
+inline bool three_too_rich(unsigned long long cand, unsigned long long row_pairs) { return cand > std::max<unsigned long long>(row_pairs / 4 / 128, 4096); }
+// A one-product launch with more candidates than its sample was allowed (1 pair in 256): its list held, so its records stand, but the wider screen
+// is not paying here - the launches behind it keep two products (CallForms::gave_up takes `one` from the call and nothing else).
+inline bool one_too_rich(unsigned long long cand, unsigned long long pairs) { return cand > std::max<unsigned long long>(pairs / 256, 4096); }
+
+// ---- the sample ladder: what the owner of a region's launches wants for each ------------------------------------------------------------------
+// The three-product form through a count matrix (long rows) pays only where candidates are few: a launch whose list overflows is redone with four
+// products, three-product launches already in flight behind it included (1 M x 50,000 cohort run, calc -u: 977 -> 1,426 ms of count kernel with
+// three such launches wasted), and how many pairs are candidates differs from launch to launch - in allele-count order the launches over the common
+// variants hold nearly all of them.  So every launch is decided by a sample of its own, taken before the pipeline starts (ld_plan.h:
+// sample_subtile), three products unless the sample is dense in candidates.  Regions of more than 64 launches sample every k-th one; the others
+// follow their nearest sampled neighbour.
+// The two-product walk: a launch in front of the planner's cut is sampled in the two-product form first - two products if that sample is poor in
+// candidates - and only if that fails in the three-product form (those launches lead the plan and are sampled one by one: the neighbour across the
+// cut says nothing).  A launch the planner marked for one product is sampled in that form first; refused, it is sampled again as any other launch
+// in front of the cut.  The prefix: the same samples, first with the stops the launch would use - poor in candidates and the launch takes the form
+// with its stops; otherwise the rungs behind decide without them.
+struct SampleOutcome { int rc = TWK_HIP_OK; unsigned long long cand = 0, pairs = 1; };      // rc: TWK_HIP_OK, TWK_HIP_E_OVERFLOW (the sample's list), or an error that ends the call
+struct LadderFacts {
+	long long opt_two = 1, opt_three = 1, opt_prefix = 1, opt_one = 1;
+	bool prefix_ok = false;           // the region's launches may take stops (the walk's long rows, their suffix margins there, the call still allows them)
+	bool one_ok = false;              // ... and one product (the planner marked launches for it, carrier rows for their columns are there, the call still allows it)
+	bool three_possible = false;      // some launch of the region would take three products (none: nothing to sample)
+	bool fused = false;               // the region's launches fuse
+	bool carrier = false;             // the region's two-product launches contract the carrier plane: wanted for every launch, and for every sample
+};
+// two_eligible(i): launch i lies in front of the walk's cut (option two = 2: every launch of the walk); planned_one(i): the planner marked it for one
+// product; sample(pick, as) runs launch pick's sample in the form `as` (CallForms::sample_grant) -> SampleOutcome; mark(what, i, x): the timeline log.
+// -> TWK_HIP_OK with a LaunchWants per launch in `out`, or the error of the sample that ended the call.
+template <class Eligible, class PlannedOne, class Sample, class Mark>
+int decide_wants(size_t n, const LadderFacts& x, Eligible two_eligible, PlannedOne planned_one, Sample sample, Mark mark, std::vector<LaunchWants>& out, uint32_t& one_refused) {
+	LaunchWants unsampled; unsampled.carrier = x.carrier;
+	out.assign(n, unsampled);
+	if (x.one_ok) for (size_t i = 0; i < n; ++i) out[i].one = planned_one(i) && two_eligible(i);      // (taken back below where a launch's sample says so)
+	if (x.opt_two == 2) for (size_t i = 0; i < n; ++i) out[i].two = two_eligible(i);
+	if (x.prefix_ok && x.opt_prefix == 2) for (size_t i = 0; i < n; ++i) out[i].prefix = true;
+	if (n == 0 || x.opt_three != 1 || !x.three_possible) return TWK_HIP_OK;
+	const unsigned long long dense_one_in = x.fused ? SAMPLE_ONE_IN_THREE_FUSED : SAMPLE_ONE_IN;
+	size_t n_front = 0;
+	if (x.opt_two == 1) while (n_front < n && two_eligible(n_front)) ++n_front;
+	const size_t step_behind = std::max<size_t>(1, (n - n_front + 63) / 64);
+	for (size_t i0 = 0, step = 1; i0 < n; i0 += step) {
+		step = i0 < n_front ? 1 : step_behind;
+		const size_t pick = std::min(n - 1, i0 + step / 2), i1 = std::min(n, i0 + step);
+		const bool front = x.opt_two == 1 && two_eligible(pick), try_two = front || (x.opt_two == 2 && out[pick].two);
+		LaunchWants as = unsampled; as.one = out[pick].one;
+		int err = TWK_HIP_OK;
+		// one rung: the sample in the form `as` (with two products and / or stops), its line in the timeline -> poor in candidates?
+		auto poor = [&](bool two, bool prefix, const char* what, unsigned long long one_in) -> bool {
+			as.two = two; as.prefix = prefix;
+			const SampleOutcome o = sample(pick, as);
+			if (o.rc != TWK_HIP_OK && o.rc != TWK_HIP_E_OVERFLOW) { err = o.rc; return false; }
+			mark(what, pick, o.cand);
+			return o.rc == TWK_HIP_OK && sample_poor(o.cand, o.pairs, one_in);
+		};
+		// the rungs in front of the three-product one: with stops (the whole step follows), then two products (the sampled launch alone)
+		auto cheaper_form = [&]() -> bool {
+			if (x.prefix_ok && x.opt_prefix == 1) {
+				if (poor(try_two, true, as.one ? "one-product prefix sample of launch: candidates" : "prefix sample of launch: candidates", SAMPLE_ONE_IN)) {
+					for (size_t i = i0; i < i1; ++i) { out[i].prefix = true; if (try_two && two_eligible(i)) out[i].two = true; }
+					return true;
+				}
+				if (err) return false;
+			}
+			if (front && poor(true, false, as.one ? "one-product sample of launch: candidates" : "two-product sample of launch: candidates", SAMPLE_ONE_IN)) {
+				out[pick].two = true;      // (three products stay wanted: what a launch falls back to)
+				return true;
+			}
+			return false;
+		};
+		bool decided = cheaper_form();
+		if (!decided && !err && as.one && x.opt_one == 1) {      // one product refused: the step's launches without it, and the same rungs again
+			as.one = false; ++one_refused;
+			for (size_t i = i0; i < i1; ++i) out[i].one = false;
+			decided = cheaper_form();
+		}
+		if (err) return err;
+		if (decided) continue;
+		// (dense: the sample's own list overflowed, or more than 1 pair in dense_one_in is a candidate)
+		const bool dense = !poor(false, false, "three-product sample of launch: candidates", dense_one_in);
+		if (err) return err;
+		for (size_t i = i0; i < i1; ++i) out[i].three = !dense;
+	}
+	return TWK_HIP_OK;
+}
 
 }  // namespace twk

@@ -326,7 +326,7 @@ inline void plan_band_launches(const PlanEnv& e, const PlanGeom& g, RegionPlan& 
 // with the square root of its bound shrunk to two_margin of it, keeps a pair with some column behind the row.  From there on a two-product
 // launch would list a large part of its pairs as candidates (in allele-count order: rows with p above ~0.17 at r2 >= 0.1), so launches
 // behind r* keep the three-product form; the rows in front of it are cut off at the A tile edge below r*, and which form their launches
-// really take is still decided by a sample of each (RegionRun::decide_three_by_samples).  The margin keeps the rows next to the edge -
+// really take is still decided by a sample of each (ld_form.h: decide_wants).  The margin keeps the rows next to the edge -
 // where sampling noise decides - out: 0.95 moves the edge from p = 0.172 to 0.160 at r2 >= 0.1.
 // Every rank of a sharded run finds the same r*: it is a property of the region, asked from row 0 on whatever the shard.  Each row is asked
 // against at most 256 columns spread evenly over those behind it, the last one included (the predicate is no guarantee, only a guide: the
@@ -512,6 +512,17 @@ inline void plan_region(const PlanEnv& e, const PlanGeom& g, RegionPlan& p) {
 	if (e.screen) p.pairs = band_pairs_before(p.r1, g.nA, g.nB, true) - band_pairs_before(p.r0, g.nA, g.nB, true);   // every pair of the band is decided
 	else if (p.windowed) p.pairs = p.cum[p.r1] - p.cum[p.r0];       // pairs inside the window: the ones the math evaluates
 	else p.pairs = band_pairs_before(p.r1, g.nA, g.nB, g.triangle != 0) - band_pairs_before(p.r0, g.nA, g.nB, g.triangle != 0);
+}
+
+// The sub-tile a density sample of launch t runs (ld_form.h: decide_wants): at most 384 x 384 variants from the launch's middle - a diagonal
+// launch's from its diagonal, cut to the triangle's extent - through the same kernels (half a millisecond).
+inline twk_hip_tile_desc sample_subtile(const twk_hip_tile_desc& t) {
+	twk_hip_tile_desc st = t;
+	const uint32_t h = std::min<uint32_t>(384, t.nA), row_c = t.rowA0 + (t.nA - h) / 2;
+	st.rowA0 = row_c; st.nA = h;
+	if (t.diag && t.rowA0 == t.rowB0) { st.rowB0 = row_c; st.nB = std::min<uint32_t>(h, t.rowB0 + t.nB - row_c); st.diag = 1; }
+	else { const uint32_t wv = std::min<uint32_t>(384, t.nB); st.rowB0 = t.rowB0 + (t.nB - wv) / 2; st.nB = wv; st.diag = 0; }
+	return st;
 }
 
 }  // namespace twk

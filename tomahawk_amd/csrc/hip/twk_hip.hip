@@ -169,7 +169,7 @@ struct Launch {
 	uint32_t* cand = nullptr;                     // the candidate list of the launch (in C)
 	unsigned long long cand_cap = 0;              // ... of this many entries; n_out[2] counts them
 	bool cand_overflow = false;                   // set by finish_tile: the list did not hold them all
-	bool too_rich = false;                        // set by finish_tile: a three-product launch with more candidates than their recount is worth
+	bool too_rich = false;                        // set by finish_tile: a three- or one-product launch with more candidates than the form is worth (ld_form.h: three_too_rich, one_too_rich)
 	bool band_too_big = false;                    // a band launch whose candidates need more survivor / sort buffers than it may have (or could get): finish_tile reports
 	                                              // it as an overflow and the launch's rows are redone as matrix-sized tiles
 	int plane_set = 0;                            // the plane set the launch contracted
@@ -632,6 +632,13 @@ int ensure_carrier(twk_hip_ctx* c, int set, uint32_t n) {
 	ps.carrier_rows = first; ps.carrier_n = n;
 	return TWK_HIP_OK;
 }
+// A buffer a form could use and the call can do without (`rc` of its ensure_*): no room for it - the runtime's error and the context's message
+// are cleared, what there is of it is dropped (`reset`) and the call goes on without; any other failure ends the call.
+template <class Reset> int or_go_without(twk_hip_ctx* c, int rc, Reset reset) {
+	if (rc != TWK_HIP_E_NOMEM) return rc;
+	(void)hipGetLastError(); c->err[0] = 0; reset();
+	return TWK_HIP_OK;
+}
 // The two operands of a count launch whose row axis walks the carrier rows from variant rowA0 on and whose column axis the planes from plane row rowB0 on,
 // as CountWork addresses them: one base and two row numbers (ensure_carrier placed the carrier rows a whole number of rows from the planes).
 struct OperandRows { const uint32_t* base; uint32_t rowA0, rowB0; };
@@ -872,7 +879,7 @@ LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters
 // Would a launch of this mode run the fused count -> screen form and nothing else (one pass), as far as the call still allows it?  For the callers
 // that size a launch by it.
 bool fused_form_applies(twk_hip_ctx* c, int mode, const twk_hip_filters& f, const CallForms& calls) {
-	const LaunchForm lf = launch_form(c, plan_for(c, mode), f, calls.grant(true, false));
+	const LaunchForm lf = launch_form(c, plan_for(c, mode), f, calls.grant(LaunchWants()));
 	return lf.fused && !lf.two_pass;
 }
 
@@ -1030,7 +1037,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	// (one product: the CC matrix has a row per row variant and a column per column variant, whole tiles of 128 of either)
 	const uint32_t ldc_one = round_up(t.nB, TILE);
 	const size_t c_two_words = form.one ? (size_t)round_up(t.nA, TILE) * ldc_one : form.two ? (size_t)round_up(t.nA, TILE) * g.rowsB : 0;
-	const size_t two_list_words = form.two ? 6 * (size_t)std::max<unsigned long long>((unsigned long long)t.nA * t.nB / 128, 4096) : 0;
+	const size_t two_list_words = form.two ? 6 * (size_t)cand_list_entries((unsigned long long)t.nA * t.nB) : 0;
 	rc = ensure_slot(c, s, list_words ? list_words : std::max((size_t)g.rowsA * g.rowsB, c_two_words + two_list_words), capacity); if (rc) return rc;
 	tl("slot buffers");
 	Launch& l = begin_launch(s, kind1, f.minP);
@@ -1038,15 +1045,13 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 	HIPCHK(c, hipMemsetAsync(s.n_out, 0, N_SLOT_COUNTERS * sizeof(unsigned long long), c->s_compute));
 	l.cand = s.C; l.cand_cap = (list_words ? list_words : s.C.capacity()) / (form.unphased ? 6 : 3);
 	// The three-product form where the launch does not fuse (long rows: tiles are split along K): the (HH, S) matrix takes the first half of the
-	// slot's count buffer and the candidate list the room behind it - at most 1/128 of the tile's pairs: a candidate's recount streams its four
-	// rows once more, ~25 pairs' worth of contraction, so a launch with more candidates than that is cheaper in the four-product form
-	// (overflow -> CallForms::gave_up -> redone).
+	// slot's count buffer and the candidate list the room behind it, as far as the form pays (ld_form.h: cand_list_entries).
 	if (form.three_plain() || form.two) {
 		const size_t c2_words = form.two ? c_two_words : (size_t)(g.rowsA / 2) * g.rowsB;
 		const unsigned long long room = s.C.capacity() > c2_words ? (s.C.capacity() - c2_words) / 6 : 0;
 		const unsigned long long pairs = (unsigned long long)t.nA * t.nB;
 		l.cand = s.C + c2_words;
-		l.cand_cap = std::min<unsigned long long>(room, form.keep_three ? room : std::max<unsigned long long>(pairs / 128, 4096));
+		l.cand_cap = std::min<unsigned long long>(room, form.keep_three ? room : cand_list_entries(pairs));
 		if (c->opt.cand_cap > 0 && !form.sample) l.cand_cap = std::min<unsigned long long>(l.cand_cap, (unsigned long long)c->opt.cand_cap);      // (test hook: the launches, not their samples)
 	}
 	FusedArgs fa{};
@@ -1364,12 +1369,8 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 			snprintf(c->err, sizeof(c->err), "three-product contraction: %llu candidates whose (HH, S) differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], t.rowA0, t.nA, t.rowB0, t.nB);
 			return TWK_HIP_E_DEVICE;
 		}
-		// A launch this rich in candidates pays more for their recount than the fourth product costs: the rest of the call in the four-product
-		// forms.  Measured at 2,504 samples, -u -w 1000000 (2.9 % of the pairs candidates): count kernel 32.1 -> 27.3 ms, but 58 M recounts at
-		// 0.16 ns each (four 320-byte rows from L2 per candidate: 8 TB/s) add 9.3 ms to the math; the two meet near 1.2 %.
-		// (against the variant pairs of the tiles the launch contracted - four plane-row pairs each - not the launch's rectangle: a window
-		// launch's rectangle is mostly outside the window)
-		if (!s.l.form.keep_three && s.h_n_out[2] > std::max<unsigned long long>(s.l.row_pairs / 4 / 128, 4096)) s.l.too_rich = true;      // (the launch's owner folds it into the call: CallForms::gave_up)
+		// (ld_form.h on the number; the launch's owner folds it into the call: CallForms::gave_up)
+		if (!s.l.form.keep_three && three_too_rich(s.h_n_out[2], s.l.row_pairs)) s.l.too_rich = true;
 	}
 	if (s.l.form.two) {
 		c->timing.two_launches += 1; c->timing.carrier_launches += s.l.form.carrier ? 1 : 0; c->timing.one_launches += s.l.form.one ? 1 : 0; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap); c->timing.candidates += s.h_n_out[2];
@@ -1377,9 +1378,7 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 			snprintf(c->err, sizeof(c->err), "two-product contraction: %llu candidates whose %s differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], s.l.form.one ? "CC" : s.l.form.carrier ? "(CH, CQ)" : "(HH, HQ)", t.rowA0, t.nA, t.rowB0, t.nB);
 			return TWK_HIP_E_DEVICE;
 		}
-		// a one-product launch with more candidates than its sample was allowed (1 pair in 256): its list held, so its records stand, but the wider
-		// screen is not paying here - the launches behind it keep two products (CallForms::gave_up takes `one` from the call and nothing else)
-		if (s.l.form.one && c->opt.one != 2 && s.h_n_out[2] > std::max<unsigned long long>(pairs_in_tile(c, t) / 256, 4096)) s.l.too_rich = true;
+		if (s.l.form.one && c->opt.one != 2 && one_too_rich(s.h_n_out[2], pairs_in_tile(c, t))) s.l.too_rich = true;      // (ld_form.h; its list held, so its records stand)
 	}
 	float ms_all = 0;
 	if (s.l.form.two_pass) {
@@ -1544,8 +1543,7 @@ int run_tile_sync(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const tw
                   unsigned long long capacity, unsigned long long* n_out, const Deliver& to, const ColRange* cr = nullptr) {
 	Slot& s = c->slot[SYNC_SLOT];
 	for (;;) {
-		FormGrant grant = calls.grant(given.three, given.two, false, given.carrier, given.one);      // (a two-product tile redone over whole rows keeps its row operand - and its one product)
-		grant.fused = grant.fused && given.fused; grant.sample = given.sample;
+		const FormGrant grant = calls.redo_grant(given);
 		int rc = enqueue_tile(c, mode, t, f, grant, s, capacity, cr); if (rc) return rc;
 		rc = finish_tile(c, s, t, n_out, to);
 		calls.gave_up(s.l.form, grant, s.l.cand_overflow, s.l.too_rich);
@@ -2359,7 +2357,7 @@ int twk_hip_ld_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc* t, const 
 	HIPCHK(c, hipSetDevice(c->device));
 	CallForms calls;                 // (a call of its own: what a region call gave up does not reach it)
 	unsigned long long n = 0;
-	int rc = run_tile_sync(c, mode, *t, *f, calls.grant(true, false), calls, std::max<unsigned long long>(capacity, 1), &n, Deliver());      // (whole, in c->h_recs)
+	int rc = run_tile_sync(c, mode, *t, *f, calls.grant(LaunchWants()), calls, std::max<unsigned long long>(capacity, 1), &n, Deliver());      // (whole, in c->h_recs)
 	flush_graveyard(c);
 	*n_out = n;
 	if (n_pairs) *n_pairs = pairs_in_tile(c, *t);
@@ -2393,23 +2391,18 @@ struct RegionRun {
 	ColRange col_range;
 	unsigned long long cap_default = 1ull << 24;
 	uint64_t tot_pairs = 0, tot_recs = 0;
-	std::vector<char> want_three;             // per launch: the three-product form may be used (decide_three_by_samples)
-	std::vector<char> want_two;               // ... and the two-product form (the two-product walk: launches in front of plan.two_end whose sample was poor in candidates)
+	std::vector<LaunchWants> wants;           // per launch: the forms its samples allow it (decide_three_by_samples -> ld_form.h: decide_wants)
 	uint32_t one_refused = 0;                 // samples in the one-product form that were too rich in candidates (the "timeline" log reports them)
-	std::vector<char> want_one;               // ... and one product a pair (the launches the planner marked: their own sample in that form, or option one = 2)
-	std::vector<char> want_prefix;            // ... and stops for its tiles (the prefix contraction, DESIGN 3.1c: the launch's sample ran with them and was poor in candidates)
 	// the prefix applies to the launches of the two-product walk on rows of more than FUSED_MAX_CHUNKS chunks (ld_form.h decide_form holds the rest)
 	bool prefix_eligible() const { return two_walk() && c->opt.prefix != 0 && calls.prefix && c->planes[PS_SORTED_U].W / KC > FUSED_MAX_CHUNKS && !c->planes[PS_SORTED_U].h_suffix.empty(); }
 	bool two_walk() const { return mode == MODE_INT_SORTED_U_ALL; }
 	// (option two = 2, the test hook: every launch of the walk, whatever the predicate says)
 	bool two_eligible(const twk_hip_tile_desc& t) const { return two_walk() && c->opt.two != 0 && (c->opt.two == 2 || t.rowA0 + t.nA <= g.a0 + plan.two_end); }
 
-	// What launch i of the plan may be: the call's forms, three and two products as the launch's own sample decided.  A tile redone synchronously is not
-	// bound by a sample: it may be whatever the call still allows but two products (redo_grant).
-	// (env.carrier: the region's two-product launches contract the carrier plane - region_impl holds carrier rows for every row in front of the cut)
-	// (want_one: the planner put the launch in front of its rows' one_end - twk_hip_tile_desc::one - and its sample in that form was poor in candidates)
-	FormGrant grant_of(size_t i) const { return calls.grant(want_three[i] != 0, want_two[i] != 0, want_prefix[i] != 0, env.carrier, want_one[i] != 0); }
-	FormGrant redo_grant() const { return calls.grant(true, false); }
+	// What launch i of the plan may be: the call's forms, as far as the launch's own samples want them.  A tile redone synchronously is not bound by a
+	// sample: it may be whatever the call still allows but two products (redo_grant).
+	FormGrant grant_of(size_t i) const { return calls.grant(wants[i]); }
+	FormGrant redo_grant() const { return calls.grant(LaunchWants()); }
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, CallForms& calls_, twk_hip_record_sink sink_, void* user_)
 		: c(c_), mode(mode_), f(f_), g(g_), env(e_), plan(p_), calls(calls_), to{!c_->device_sink, sink_ ? sink_ : discard_records, user_} {}
@@ -2493,94 +2486,42 @@ struct RegionRun {
 		return TWK_HIP_OK;
 	}
 
-	// The three-product form through a count matrix (long rows) pays only where candidates are few: a launch whose list overflows is redone
-	// with four products, three-product launches already in flight behind it included (1 M x 50,000 cohort run, calc -u: 977 -> 1,426 ms of
-	// count kernel with three such launches wasted), and how many pairs are candidates differs from launch to launch - in allele-count order
-	// the launches over the common variants hold nearly all of them.  So every launch is decided by a sample of its own, taken before the
-	// pipeline starts: a sub-tile of at most 384 x 384 variants from its middle through the same kernels (half a millisecond), three
-	// products if at most 1 pair in 256 of the sample is a candidate (1 in 128 for fused launches, whose recount reads short rows from L2).  (Regions of more than 64 launches sample every k-th one; the others
-	// follow their nearest sampled neighbour.)
-	// The two-product walk: a launch in front of the planner's cut is sampled in the two-product form first - two products if at most 1 pair
-	// in 256 of that sample is a candidate - and only if that fails in the three-product form (those launches are sampled one by one: the
-	// neighbour across the cut says nothing).
+	// A density sample is not a launch of the run: what it leaves in the timing and in the launch log is taken back when it is through.
+	struct SampleScope {
+		twk_hip_ctx* c; const twk_hip_timing keep_timing; const size_t keep_ring; const uint64_t keep_seen;
+		explicit SampleScope(twk_hip_ctx* c_) : c(c_), keep_timing(c_->timing), keep_ring(c_->launch_ring.size()), keep_seen(c_->launches_seen) {}
+		~SampleScope() {
+			c->timing = keep_timing;
+			if (c->launch_ring.size() > keep_ring && c->launches_seen == keep_seen + 1 && keep_seen < LAUNCH_RING) c->launch_ring.pop_back();
+			c->launches_seen = keep_seen;
+		}
+	};
+	// The sample of launch `pick` in the form `as`: its sub-tile (ld_plan.h: sample_subtile) through the same kernels on the spare slot, its records dropped.
+	SampleOutcome run_sample(size_t pick, const LaunchWants& as) {
+		const twk_hip_tile_desc st = sample_subtile(plan.mine[pick]);
+		SampleOutcome o;
+		o.pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
+		SampleScope not_a_launch(c);
+		Slot& ss = c->slot[SYNC_SLOT];
+		unsigned long long nrec = 0;
+		o.rc = enqueue_tile(c, mode, st, *f, calls.sample_grant(as), ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
+		if (o.rc == TWK_HIP_OK) o.rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
+		o.cand = ss.h_n_out[2];
+		return o;
+	}
+	// What every launch of the plan may be, decided by samples taken before the pipeline starts: the facts of this region for the ladder of
+	// ld_form.h (decide_wants), which says which launch is sampled in which form and what follows from each outcome.
 	int decide_three_by_samples() {
 		const std::vector<twk_hip_tile_desc>& mine = plan.mine;
-		const size_t n = mine.size();
-		want_three.assign(n, 1); want_two.assign(n, 0); want_prefix.assign(n, 0); want_one.assign(n, 0);
-		const bool one_ok = env.one && env.carrier && c->opt.one != 0 && calls.one;
-		if (one_ok) for (size_t i = 0; i < n; ++i) want_one[i] = (mine[i].one && two_eligible(mine[i])) ? 1 : 0;      // (taken back below where a launch's sample says so)
-		if (c->opt.two == 2) for (size_t i = 0; i < n; ++i) want_two[i] = two_eligible(mine[i]) ? 1 : 0;
-		const bool prefix_ok = prefix_eligible();
-		if (prefix_ok && c->opt.prefix == 2) want_prefix.assign(n, 1);
-		if (mine.empty() || c->opt.three != 1 || !launch_form(c, plan_for(c, mode), *f, redo_grant()).three) return TWK_HIP_OK;     // (no launch of this region would take the form)
-		// (fused launches - short rows - are sampled as well: they keep their candidates whatever their number, but past ~1.2 % of the pairs
-		// the recount costs more than the third product saves: 2,504 samples, -u -w 1000000, 2.9 % candidates: 27.4 + 30.3 ms of count kernel and
-		// math with three products in the first of two launches, 30 + 21 ms with four in both)
-		const unsigned long long dense_one_in = env.fused ? 128 : 256;
-		// (the launches in front of the two-product walk's cut lead the plan and are sampled one by one; the others every k-th as ever)
-		size_t n_front = 0;
-		if (c->opt.two == 1) while (n_front < n && two_eligible(mine[n_front])) ++n_front;
-		const size_t step_behind = std::max<size_t>(1, (n - n_front + 63) / 64);
-		for (size_t i0 = 0, step = 1; i0 < n; i0 += step) {
-			step = i0 < n_front ? 1 : step_behind;
-			const size_t pick = std::min(n - 1, i0 + step / 2);
-			const twk_hip_tile_desc& t0 = mine[pick];
-			twk_hip_tile_desc st = t0;
-			const uint32_t h = std::min<uint32_t>(384, t0.nA), row_c = t0.rowA0 + (t0.nA - h) / 2;
-			st.rowA0 = row_c; st.nA = h;
-			if (t0.diag && t0.rowA0 == t0.rowB0) { st.rowB0 = row_c; st.nB = std::min<uint32_t>(h, t0.rowB0 + t0.nB - row_c); st.diag = 1; }
-			else { const uint32_t wv = std::min<uint32_t>(384, t0.nB); st.rowB0 = t0.rowB0 + (t0.nB - wv) / 2; st.nB = wv; st.diag = 0; }
-			unsigned long long cand = 0;
-			const unsigned long long sample_pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
-			// (one: the sample of a launch the planner marked for one product runs in that form first; refused - more than 1 candidate in 256 - the launch is
-			// sampled again as any other launch in front of the cut)
-			bool one = want_one[pick] != 0;
-			auto sample = [&](bool two, bool prefix = false) -> int {
-				const twk_hip_timing keep_timing = c->timing;
-				const size_t keep_ring = c->launch_ring.size(); const uint64_t keep_seen = c->launches_seen;
-				Slot& ss = c->slot[SYNC_SLOT];
-				unsigned long long nrec = 0;
-				// (three products granted: a sample is only taken where the call allows them; and its own overflow or richness decides its launch, not the call)
-				int rc = enqueue_tile(c, mode, st, *f, FormGrant{calls.fused, true, two && calls.two, true, prefix && calls.prefix, two && calls.two && env.carrier, one && two && calls.two && calls.one && env.carrier}, ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
-				if (rc == TWK_HIP_OK) rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
-				cand = ss.h_n_out[2];
-				c->timing = keep_timing;                 // (a sample is not a launch of the run: neither in the timing nor in the launch log)
-				if (c->launch_ring.size() > keep_ring && c->launches_seen == keep_seen + 1 && keep_seen < LAUNCH_RING) c->launch_ring.pop_back();
-				c->launches_seen = keep_seen;
-				return rc;
-			};
-			// The prefix: the same samples, first with the stops the launch would use - at most 1 candidate in 256 and the launch takes the form with
-			// its stops; otherwise the ladder below decides without them.
-			const bool try_two = (c->opt.two == 1 && two_eligible(t0)) || (c->opt.two == 2 && want_two[pick]);
-			bool decided = false;
-			for (;;) {      // (at most twice: with one product where the launch is marked for it, then without)
-				if (prefix_ok && c->opt.prefix == 1) {
-					const int rcp = sample(try_two, true);
-					if (rcp != TWK_HIP_OK && rcp != TWK_HIP_E_OVERFLOW) return rcp;
-					mark(one ? "one-product prefix sample of launch: candidates" : "prefix sample of launch: candidates", pick, cand);
-					if (rcp == TWK_HIP_OK && cand * 256 <= sample_pairs) {
-						for (size_t i = i0; i < std::min(n, i0 + step); ++i) { want_prefix[i] = 1; if (try_two && two_eligible(mine[i])) want_two[i] = 1; }
-						decided = true; break;
-					}
-				}
-				if (c->opt.two == 1 && two_eligible(t0)) {
-					const int rc2 = sample(true);
-					if (rc2 != TWK_HIP_OK && rc2 != TWK_HIP_E_OVERFLOW) return rc2;
-					mark(one ? "one-product sample of launch: candidates" : "two-product sample of launch: candidates", pick, cand);
-					if (rc2 == TWK_HIP_OK && cand * 256 <= sample_pairs) { want_two[pick] = 1; decided = true; break; }      // (three products stay wanted: what a launch falls back to)
-				}
-				if (!(one && c->opt.one == 1)) break;
-				one = false; ++one_refused;
-				for (size_t i = i0; i < std::min(n, i0 + step); ++i) want_one[i] = 0;
-			}
-			if (decided) continue;
-			const int rc = sample(false);
-			const bool dense = rc == TWK_HIP_E_OVERFLOW || (rc == TWK_HIP_OK && cand * dense_one_in > sample_pairs);
-			if (rc != TWK_HIP_OK && rc != TWK_HIP_E_OVERFLOW) return rc;
-			for (size_t i = i0; i < std::min(n, i0 + step); ++i) want_three[i] = dense ? 0 : 1;
-			mark("three-product sample of launch: candidates", pick, cand);
-		}
-		return TWK_HIP_OK;
+		LadderFacts x;
+		x.opt_two = c->opt.two; x.opt_three = c->opt.three; x.opt_prefix = c->opt.prefix; x.opt_one = c->opt.one;
+		x.one_ok = env.one && env.carrier && c->opt.one != 0 && calls.one;
+		x.prefix_ok = prefix_eligible();
+		x.three_possible = !mine.empty() && c->opt.three == 1 && launch_form(c, plan_for(c, mode), *f, redo_grant()).three;
+		x.fused = env.fused; x.carrier = env.carrier;      // (region_impl holds carrier rows for every row in front of the cut)
+		return decide_wants(mine.size(), x, [&](size_t i) { return two_eligible(mine[i]); }, [&](size_t i) { return mine[i].one != 0; },
+		                    [&](size_t pick, const LaunchWants& as) { return run_sample(pick, as); },
+		                    [&](const char* what, size_t i, unsigned long long n_cand) { mark(what, i, n_cand); }, wants, one_refused);
 	}
 
 	// What every tile ends with once its launch, or the ladder below it (run_tile_sync), is through with rc: more survivors than the buffer holds -> the
@@ -2705,9 +2646,8 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, const CallF
 		env.one = env.carrier && c->opt.one != 0 && calls.one && f->minR2 > 1e-6 && f->minR2 <= 1.0; env.one_rows = (uint32_t)c->opt.one_rows;
 		// the prefix contraction: the rows' suffix margins, the first time a call may take the form (no room for the table: the call takes no stops)
 		if (c->opt.prefix != 0 && calls.prefix && f->minR2 > 1e-6 && f->minR2 <= 1.0 && ps.W / KC > FUSED_MAX_CHUNKS) {
-			const int rc = ensure_suffix(c, PS_SORTED_U);
-			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.suffix = DevBuf<uint32_t>(); ps.h_suffix.clear(); }
-			else if (rc) return rc;
+			const int rc = or_go_without(c, ensure_suffix(c, PS_SORTED_U), [&] { ps.suffix = DevBuf<uint32_t>(); ps.h_suffix.clear(); });
+			if (rc) return rc;
 		}
 	}
 	// r2 screen (TWK_HIP_OPT_R2_SCREEN): the region is a triangle over the leading, missing-free part of an allele-count-sorted set
@@ -2750,20 +2690,17 @@ static int region_impl(twk_hip_ctx* c, const RegionArgs& a, CallForms& calls) {
 		// ... and for every column variant of this shard's one-product launches (at r2 >= 0.1 on a flat frequency law: nearly every variant of the set, one
 		// more plane row each).  No room for those: the plan without one-product launches, and the rows in front of the cut as before.
 		uint32_t need_one = 0;
+		auto drop_carrier = [&] { ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; };
 		for (const auto& t : plan.mine) if (t.one) need_one = std::max(need_one, t.rowB0 + t.nB);
 		if (need && need_one > need && !(ps.carrier_rows && ps.carrier_n >= need_one)) {
-			rc = ensure_carrier(c, PS_SORTED_U, need_one);
-			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; }
-			else if (rc) return rc;
+			rc = or_go_without(c, ensure_carrier(c, PS_SORTED_U, need_one), drop_carrier); if (rc) return rc;
 		}
 		if (env.one && (!need || (need_one > need && !(ps.carrier_rows && ps.carrier_n >= need_one)))) {
 			env.one = false;
 			plan_region(env, g, plan);
 		}
 		if (need) {
-			rc = ensure_carrier(c, PS_SORTED_U, need);
-			if (rc == TWK_HIP_E_NOMEM) { (void)hipGetLastError(); c->err[0] = 0; ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; }
-			else if (rc) return rc;
+			rc = or_go_without(c, ensure_carrier(c, PS_SORTED_U, need), drop_carrier); if (rc) return rc;
 		}
 		if (!carrier_operand(c->opt.carrier, ps.W / KC, ps.carrier_rows ? ps.carrier_n : 0, need)) {
 			env.carrier = env.one = false;

@@ -4,10 +4,16 @@
 //      withdrawal adds a form - but grant.two, which turns two products into three.
 //   2. CallForms::gave_up: the transitions a launch's outcome makes in what the call still allows, one by one, that a form the launch was not
 //      granted is never taken from the call, and that a second telling changes nothing; step_down, the ladder a redone tile descends.
+//   3. CallForms::grant, sample_grant and redo_grant against the expressions they replaced; the thresholds at their edges; the samples' sub-tile.
+//   4. decide_wants, the sample ladder, under scripted samplers: its invariants over every option, fact, plan length and outcome, and named scripts
+//      whose samples and wants are written out.
+#include <algorithm>
 #include <cstdio>
 #include <initializer_list>
+#include <string>
 #include <vector>
 #include "../hip/ld_form.h"
+#include "../hip/ld_plan.h"
 
 using namespace twk;
 
@@ -17,11 +23,23 @@ int g_bad_checks = 0;
 long g_cases = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { if (g_bad_checks < 40) { fprintf(stderr, "    FAILED %s: ", #cond); fprintf(stderr, __VA_ARGS__); fprintf(stderr, "\n"); } ++g_bad_checks; } } while (0)
 
-bool same(const LaunchForm& a, const LaunchForm& b) {
-	return a.two_pass == b.two_pass && a.fused == b.fused && a.unphased == b.unphased && a.three == b.three && a.two == b.two && a.keep_three == b.keep_three &&
-	       a.sample == b.sample && a.reduce == b.reduce;
+// (two forms are the same when every field of LaunchForm is: operator== in ld_form.h)
+enum { G_FUSED = 1, G_THREE = 2, G_TWO = 4, G_SAMPLE = 8, G_PREFIX = 16, G_CARRIER = 32, G_ONE = 64, G_ALL_BITS = 128 };
+FormGrant grant_of(int bits) {
+	FormGrant g;
+	g.fused = (bits & G_FUSED) != 0; g.three = (bits & G_THREE) != 0; g.two = (bits & G_TWO) != 0; g.sample = (bits & G_SAMPLE) != 0;
+	g.prefix = (bits & G_PREFIX) != 0; g.carrier = (bits & G_CARRIER) != 0; g.one = (bits & G_ONE) != 0;
+	return g;
 }
-FormGrant grant_of(int bits) { return FormGrant{(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0}; }
+enum { W_THREE = 1, W_TWO = 2, W_PREFIX = 4, W_CARRIER = 8, W_ONE = 16, W_ALL_BITS = 32 };
+LaunchWants wants_of(int bits) {
+	LaunchWants w;
+	w.three = (bits & W_THREE) != 0; w.two = (bits & W_TWO) != 0; w.prefix = (bits & W_PREFIX) != 0; w.carrier = (bits & W_CARRIER) != 0; w.one = (bits & W_ONE) != 0;
+	return w;
+}
+bool same_grant(const FormGrant& a, const FormGrant& b) {
+	return a.fused == b.fused && a.three == b.three && a.two == b.two && a.sample == b.sample && a.prefix == b.prefix && a.carrier == b.carrier && a.one == b.one;
+}
 
 std::vector<FormFacts> all_facts() {
 	std::vector<FormFacts> out;
@@ -58,11 +76,11 @@ void check_decide_form() {
 		for (int bit = 0; bit < 4; ++bit) {
 			if (!(gb & (1 << bit))) continue;
 			const LaunchForm less = decide_form(x, grant_of(gb & ~(1 << bit)));
-			if (bit == 3) { LaunchForm marked = less; marked.sample = true; CHECK(same(marked, lf), "grant.sample changed the form"); continue; }
+			if (bit == 3) { LaunchForm marked = less; marked.sample = true; CHECK(marked == lf, "grant.sample changed the form"); continue; }
 			CHECK(!(less.fused && !lf.fused), "withdrawing grant %d added the fused form", bit);
 			CHECK(!(less.two && !lf.two), "withdrawing grant %d added two products", bit);
 			if (less.three && !lf.three) CHECK(bit == 2 && lf.two && !less.two, "withdrawing grant %d added three products", bit);
-			if (bit == 2 && !same(less, lf)) CHECK(lf.two && !less.two && less.three && !lf.three && less.fused == lf.fused, "withdrawing grant.two did more than turn two products into three");
+			if (bit == 2 && !(less == lf)) CHECK(lf.two && !less.two && less.three && !lf.three && less.fused == lf.fused, "withdrawing grant.two did more than turn two products into three");
 		}
 	}
 }
@@ -71,7 +89,7 @@ LaunchForm form_of(bool fused, bool three, bool two, bool keep_three = false) { 
 bool is(const CallForms& c, bool fused, bool three, bool two) { return c.fused == fused && c.three == three && c.two == two; }
 
 void check_gave_up() {
-	const FormGrant all{true, true, true, false};
+	const FormGrant all = grant_of(G_FUSED | G_THREE | G_TWO);
 	const LaunchForm two = form_of(false, false, true), fused4 = form_of(true, false, false), fused3 = form_of(true, true, false), three = form_of(false, true, false),
 	                 four = form_of(false, false, false), kept3 = form_of(true, true, false, true);
 	{ CallForms c; c.gave_up(two, all, true, false); CHECK(is(c, true, true, false), "a two-product list overflowed"); }
@@ -95,9 +113,9 @@ void check_gave_up() {
 		again.gave_up(lf, g, (ob & 1) != 0, (ob & 2) != 0);
 		CHECK(is(again, c.fused, c.three, c.two), "not idempotent");
 		// what the call then grants a launch is no more than it still holds
-		const FormGrant next = c.grant(true, true);
+		const FormGrant next = c.grant(wants_of(W_THREE | W_TWO));
 		CHECK(next.fused == c.fused && next.three == c.three && next.two == c.two && !next.sample, "grant");
-		CHECK(!c.grant(false, true).three && !c.grant(true, false).two, "grant beyond what the owner wants");
+		CHECK(!c.grant(wants_of(W_TWO)).three && !c.grant(wants_of(W_THREE)).two, "grant beyond what the owner wants");
 	}
 	// the ladder: two -> three (if granted) -> four through the matrix; fused or three -> four through the matrix
 	{ const FormGrant g = step_down(two, all); CHECK(g.fused && g.three && !g.two, "below two products"); }
@@ -113,7 +131,7 @@ void check_gave_up() {
 		const FormGrant g = step_down(lf, with_prefix);
 		CHECK(!g.prefix && g.fused == with_prefix.fused && g.three == with_prefix.three && g.two == with_prefix.two, "below a prefix launch: the same product form over whole rows");
 		CallForms gone; gone.prefix = false;
-		CHECK(!gone.grant(true, true, true).prefix && CallForms().grant(true, true, true).prefix && !CallForms().grant(true, true).prefix, "prefix grants");
+		CHECK(!gone.grant(wants_of(W_THREE | W_TWO | W_PREFIX)).prefix && CallForms().grant(wants_of(W_THREE | W_TWO | W_PREFIX)).prefix && !CallForms().grant(wants_of(W_THREE | W_TWO)).prefix, "prefix grants");
 	}
 	{ LaunchForm lf = three; lf.prefix = true; CallForms c; c.gave_up(lf, with_prefix, false, true); CHECK(is(c, true, true, true) && !c.prefix, "a three-product prefix launch too rich in candidates: the stops go, the form stays"); }
 	{ LaunchForm lf = three; lf.prefix = true; CallForms c; c.gave_up(lf, with_prefix, true, true); CHECK(is(c, true, true, true) && !c.prefix, "a flooded prefix launch is rich by its stops: the form stays"); }
@@ -144,21 +162,22 @@ void check_carrier() {
 		FormGrant g0 = g; g0.carrier = false;
 		const LaunchForm base = decide_form(x, g0);
 		++g_cases;
-		CHECK(same(lf, base) && lf.prefix == base.prefix, "the carrier grant changed the form");
+		// (every field is compared now: the carrier grant changes `carrier`, which is its purpose, and nothing else - the check used to pass because `carrier` was not looked at)
+		{ LaunchForm but_carrier = lf; but_carrier.carrier = false; CHECK(but_carrier == base, "the carrier grant changed more than the row operand"); }
 		CHECK(!base.carrier, "a carrier launch without its grant");
 		CHECK(lf.carrier == (gc && oc != 0 && cc > FUSED_MAX_CHUNKS && lf.two), "carrier: grant %d option %d chunks %u two %d", gc, oc, cc, (int)lf.two);
 		CHECK(!lf.carrier || (lf.two && !lf.three && !lf.fused && !lf.two_pass && x.sorted_u), "a carrier launch that is no two-product launch of the sorted walk");
 	}
 	// the ladder: a carrier launch whose list overflowed is redone with three products, and the call's two-product launches end - as the H form's;
 	// a prefix launch on carrier rows is redone over whole rows on the same rows
-	FormGrant all{true, true, true, false}; all.carrier = true;
+	FormGrant all = grant_of(G_FUSED | G_THREE | G_TWO | G_CARRIER);
 	LaunchForm two; two.unphased = true; two.two = true; two.carrier = true;
 	{ const FormGrant g = step_down(two, all); CHECK(g.fused && g.three && !g.two && !g.carrier, "below a carrier launch: three products"); }
-	{ CallForms c; c.gave_up(two, all, true, false); CHECK(c.fused && c.three && !c.two && c.prefix, "a carrier launch's list overflowed: no more two-product launches"); CHECK(!c.grant(true, true, false, true).carrier && !c.grant(true, true, false, true).two, "... and none on carrier rows"); }
-	{ CallForms c; c.gave_up(two, all, false, false); CHECK(c.two && c.grant(true, true, false, true).carrier, "a carrier launch went well"); }
+	{ CallForms c; c.gave_up(two, all, true, false); CHECK(c.fused && c.three && !c.two && c.prefix, "a carrier launch's list overflowed: no more two-product launches"); CHECK(!c.grant(wants_of(W_THREE | W_TWO | W_CARRIER)).carrier && !c.grant(wants_of(W_THREE | W_TWO | W_CARRIER)).two, "... and none on carrier rows"); }
+	{ CallForms c; c.gave_up(two, all, false, false); CHECK(c.two && c.grant(wants_of(W_THREE | W_TWO | W_CARRIER)).carrier, "a carrier launch went well"); }
 	{ LaunchForm lf = two; lf.prefix = true; FormGrant wp = all; wp.prefix = true; const FormGrant g = step_down(lf, wp); CHECK(!g.prefix && g.two && g.carrier, "below a carrier prefix launch: whole rows, same operand");
 	  CallForms c; c.gave_up(lf, wp, true, false); CHECK(c.two && !c.prefix, "a carrier prefix launch's list overflowed: the stops go"); }
-	CHECK(!CallForms().grant(true, false, false, true).carrier && !CallForms().grant(true, true).carrier && CallForms().grant(true, true, false, true).carrier, "carrier grants follow the two-product grant");
+	CHECK(!CallForms().grant(wants_of(W_THREE | W_CARRIER)).carrier && !CallForms().grant(wants_of(W_THREE | W_TWO)).carrier && CallForms().grant(wants_of(W_THREE | W_TWO | W_CARRIER)).carrier, "carrier grants follow the two-product grant");
 	g_cases += 6;
 	// the row operand of a call (carrier_operand): the option, rows beyond the fused form's, and carrier rows for every row in front of the cut - rows that
 	// could not be allocated (have 0 < need) leave the H plane, and a call with nothing in front of its cut asks for none
@@ -190,27 +209,260 @@ void check_one() {
 		FormGrant g0 = g; g0.one = false;
 		const LaunchForm base = decide_form(x, g0);
 		++g_cases;
-		CHECK(same(lf, base) && lf.prefix == base.prefix && lf.carrier == base.carrier, "the one-product grant changed the form");
+		// (likewise: the one-product grant changes `one` and nothing else)
+		{ LaunchForm but_one = lf; but_one.one = false; CHECK(but_one == base, "the one-product grant changed more than the one product"); }
 		CHECK(!base.one, "a one-product launch without its grant");
 		CHECK(lf.one == (go && oo != 0 && lf.carrier), "one: grant %d option %d carrier %d", go, oo, (int)lf.carrier);
 		CHECK(!lf.one || (lf.two && lf.carrier && !lf.three && !lf.fused && !lf.two_pass && x.sorted_u), "a one-product launch that is no carrier launch of the sorted walk");
 	}
 	// the ladder: a one-product launch whose list overflowed, or that was too rich, is redone in the carrier two-product form and the call gives up
 	// `one` and nothing else; with stops, the stops go first
-	FormGrant all{true, true, true, false}; all.carrier = true; all.one = true;
+	FormGrant all = grant_of(G_FUSED | G_THREE | G_TWO | G_CARRIER | G_ONE);
 	LaunchForm one; one.unphased = true; one.two = true; one.carrier = true; one.one = true;
 	{ const FormGrant g = step_down(one, all); CHECK(g.fused && g.three && g.two && g.carrier && !g.one, "below a one-product launch: the carrier two-product form"); }
 	for (int ob = 1; ob < 4; ++ob) { CallForms c; c.gave_up(one, all, (ob & 1) != 0, (ob & 2) != 0); CHECK(c.fused && c.three && c.two && c.prefix && !c.one, "a one-product launch overflowed or was too rich: the call gives up one product only");
-	                                 CHECK(c.grant(true, true, false, true, true).carrier && !c.grant(true, true, false, true, true).one, "... and grants the carrier form still"); }
-	{ CallForms c; c.gave_up(one, all, false, false); CHECK(c.one && c.grant(true, true, false, true, true).one, "a one-product launch went well"); }
+	                                 CHECK(c.grant(wants_of(W_THREE | W_TWO | W_CARRIER | W_ONE)).carrier && !c.grant(wants_of(W_THREE | W_TWO | W_CARRIER | W_ONE)).one, "... and grants the carrier form still"); }
+	{ CallForms c; c.gave_up(one, all, false, false); CHECK(c.one && c.grant(wants_of(W_THREE | W_TWO | W_CARRIER | W_ONE)).one, "a one-product launch went well"); }
 	{ FormGrant ng = all; ng.one = false; LaunchForm lf = one; CallForms c; c.gave_up(lf, ng, true, false); CHECK(c.one, "one product was not granted: not taken from the call"); }
 	{ LaunchForm lf = one; lf.prefix = true; FormGrant wp = all; wp.prefix = true; const FormGrant g = step_down(lf, wp); CHECK(!g.prefix && g.two && g.carrier && g.one, "below a one-product prefix launch: whole rows, same form");
 	  CallForms c; c.gave_up(lf, wp, true, false); CHECK(c.two && c.one && !c.prefix, "a one-product prefix launch's list overflowed: the stops go"); }
 	{ LaunchForm two = one; two.one = false; FormGrant g2 = all; g2.one = false; const FormGrant g = step_down(two, g2); CHECK(!g.two && !g.carrier && !g.one && g.three, "below a carrier launch: three products, as before");
-	  CallForms c; c.gave_up(two, all, true, false); CHECK(!c.two && !c.grant(true, true, false, true, true).one, "no two-product launches: none with one product either"); }
-	CHECK(!CallForms().grant(true, true, false, false, true).one && !CallForms().grant(true, false, false, true, true).one && !CallForms().grant(true, true, false, true).one, "one-product grants follow the carrier grant");
+	  CallForms c; c.gave_up(two, all, true, false); CHECK(!c.two && !c.grant(wants_of(W_THREE | W_TWO | W_CARRIER | W_ONE)).one, "no two-product launches: none with one product either"); }
+	CHECK(!CallForms().grant(wants_of(W_THREE | W_TWO | W_ONE)).one && !CallForms().grant(wants_of(W_THREE | W_CARRIER | W_ONE)).one && !CallForms().grant(wants_of(W_THREE | W_TWO | W_CARRIER)).one, "one-product grants follow the carrier grant");
 	g_cases += 10;
 	printf("form-check: one-product attribute: granted with the carrier form only, given up alone\n");
+}
+
+// The three ways a grant is made - for a launch of the plan, for a sample, for a tile that is redone - against the expressions they replaced, which
+// are written out here once: every state of the call x every wants (or every grant given).
+void check_named_grants() {
+	for (int cb = 0; cb < 32; ++cb) {
+		CallForms c; c.fused = (cb & 1) != 0; c.three = (cb & 2) != 0; c.two = (cb & 4) != 0; c.prefix = (cb & 8) != 0; c.one = (cb & 16) != 0;
+		for (int wb = 0; wb < W_ALL_BITS; ++wb) {
+			const LaunchWants w = wants_of(wb);
+			FormGrant launch;      // (what the overload of five positional flags gave)
+			launch.fused = c.fused; launch.three = c.three && w.three; launch.two = c.two && w.two; launch.sample = false; launch.prefix = c.prefix && w.prefix;
+			launch.carrier = c.two && w.two && w.carrier; launch.one = c.one && c.two && w.two && w.carrier && w.one;
+			FormGrant sample;      // (the literal of the sample: three products whatever the call holds, the mark, the rest as the launch's)
+			sample.fused = c.fused; sample.three = true; sample.two = w.two && c.two; sample.sample = true; sample.prefix = w.prefix && c.prefix;
+			sample.carrier = w.two && c.two && w.carrier; sample.one = w.one && w.two && c.two && c.one && w.carrier;
+			g_cases += 2;
+			CHECK(same_grant(c.grant(w), launch), "grant(LaunchWants): call %d wants %d", cb, wb);
+			CHECK(same_grant(c.sample_grant(w), sample), "sample_grant: call %d wants %d", cb, wb);
+		}
+		for (int gb = 0; gb < G_ALL_BITS; ++gb) {
+			const FormGrant given = grant_of(gb);
+			FormGrant redo;        // (grant(given.three, given.two, false, given.carrier, given.one), then fused narrowed and the mark carried over)
+			redo.fused = c.fused && given.fused; redo.three = c.three && given.three; redo.two = c.two && given.two; redo.sample = given.sample; redo.prefix = false;
+			redo.carrier = c.two && given.two && given.carrier; redo.one = c.one && c.two && given.two && given.carrier && given.one;
+			++g_cases;
+			CHECK(same_grant(c.redo_grant(given), redo), "redo_grant: call %d given %d", cb, gb);
+		}
+	}
+	printf("form-check: grant, sample_grant and redo_grant equal the expressions they replaced\n");
+}
+
+// The numbers that call a sample poor and a launch too rich, at their edges.
+void check_thresholds() {
+	CHECK(SAMPLE_ONE_IN == 256 && SAMPLE_ONE_IN_THREE_FUSED == 128, "the samples' thresholds");
+	CHECK(sample_poor(576, 147456, SAMPLE_ONE_IN) && !sample_poor(577, 147456, SAMPLE_ONE_IN), "1 candidate in 256 is poor, one more is not");
+	CHECK(sample_poor(1152, 147456, SAMPLE_ONE_IN_THREE_FUSED) && !sample_poor(1153, 147456, SAMPLE_ONE_IN_THREE_FUSED), "1 candidate in 128 is poor for a fused launch, one more is not");
+	CHECK(sample_poor(0, 0, SAMPLE_ONE_IN) && !sample_poor(1, 0, SAMPLE_ONE_IN) && sample_poor(0, 1, SAMPLE_ONE_IN), "no pairs: only no candidates are few");
+	// three products: row_pairs / 4 / 128 crosses 4096 at row_pairs = 4096 * 512 + 512 = 2,097,664 (below it the floor of 4096 candidates stands)
+	CHECK(!three_too_rich(4096, 0) && three_too_rich(4097, 0), "three products, no pairs: the floor");
+	CHECK(!three_too_rich(4096, 2097663) && three_too_rich(4097, 2097663), "three products, just below the crossing: the floor still");
+	CHECK(!three_too_rich(4097, 2097664) && three_too_rich(4098, 2097664), "three products, just above the crossing: 1 in 512 of the row pairs");
+	CHECK(!three_too_rich(4097, 2097667) && !three_too_rich(4097, 2098175) && !three_too_rich(4098, 2098176), "three products: the division in two steps rounds down twice");
+	// one product: pairs / 256 crosses 4096 at pairs = 4096 * 256 + 256 = 1,048,832
+	CHECK(!one_too_rich(4096, 0) && one_too_rich(4097, 0) && !one_too_rich(4096, 1048831) && one_too_rich(4097, 1048831) && !one_too_rich(4097, 1048832) && one_too_rich(4098, 1048832), "one product: floor and crossing");
+	// the candidate list: pairs / 128 crosses 4096 at pairs = 4096 * 128 + 128 = 524,416
+	CHECK(cand_list_entries(0) == 4096 && cand_list_entries(524415) == 4096 && cand_list_entries(524416) == 4097 && cand_list_entries(128ull * 128 * 64 * 64) == 524288, "the candidate list's entries");
+	g_cases += 9;
+}
+
+// The sub-tile a sample runs (ld_plan.h): rows, columns and diagonal flag written out.
+void check_sample_subtile() {
+	static const struct { uint32_t rowA0, nA, rowB0, nB; int diag; uint32_t s_rowA0, s_nA, s_rowB0, s_nB; int s_diag; const char* what; } CASES[] = {
+		{100, 200, 1000, 300, 0,    100, 200, 1000, 300, 0,   "a tile smaller than the sample: itself"},
+		{0, 300, 0, 300, 1,         0, 300, 0, 300, 1,        "a diagonal tile smaller than the sample: itself"},
+		{1024, 1024, 1024, 4096, 1, 1344, 384, 1344, 384, 1,  "a diagonal tile with more columns than rows: 384 x 384 on the diagonal, from the rows' middle"},
+		{0, 1000, 0, 500, 1,        308, 384, 308, 192, 1,    "a diagonal tile whose columns end inside the sample: cut to the triangle's extent"},
+		{0, 8192, 8192, 4096, 0,    3904, 384, 10048, 384, 0, "an off-diagonal tile: the middle of both axes"},
+		{0, 1000, 512, 2000, 1,     308, 384, 1320, 384, 0,   "a tile marked diagonal whose axes start apart: as an off-diagonal one"},
+		{7, 385, 7, 385, 1,         7, 384, 7, 384, 1,        "one row more than the sample: the odd row is left at the end"},
+	};
+	for (const auto& k : CASES) {
+		twk_hip_tile_desc t{}; t.rowA0 = k.rowA0; t.nA = k.nA; t.rowB0 = k.rowB0; t.nB = k.nB; t.diag = k.diag; t.one = 1;
+		const twk_hip_tile_desc st = sample_subtile(t);
+		++g_cases;
+		CHECK(st.rowA0 == k.s_rowA0 && st.nA == k.s_nA && st.rowB0 == k.s_rowB0 && st.nB == k.s_nB && st.diag == k.s_diag && st.one == 1, "sample_subtile: %s: rows %u+%u, cols %u+%u, diag %d", k.what, st.rowA0, st.nA, st.rowB0, st.nB, (int)st.diag);
+	}
+}
+
+// ---- the sample ladder (decide_wants) under scripted samplers ---------------------------------------------------------------------------------------
+// A sample's outcome: P poor (exactly 1 candidate in 256), M middling (exactly 1 in 128), R rich (one more than that), O its list overflowed, E an
+// error that ends the call.  A script: the outcome of the rung with stops, of the two-product rung and of the three-product rung, the first two once
+// more for samples that run with one product, and one exception at (rung, pick).
+SampleOutcome outcome_of(char o) {
+	SampleOutcome r; r.pairs = 384 * 384;
+	r.rc = o == 'O' ? TWK_HIP_E_OVERFLOW : o == 'E' ? TWK_HIP_E_DEVICE : TWK_HIP_OK;
+	r.cand = o == 'P' ? 576 : o == 'M' ? 1152 : o == 'R' ? 1153 : o == 'O' ? 99999 : 7;
+	return r;
+}
+struct Script { char stops = 'R', two = 'R', three = 'P', one_stops = 'R', one_two = 'R'; char but_rung = 0; size_t but_pick = 0; char but = 'P'; };
+// A sample as the ladder asked for it: 'p' with stops, 'P' with stops and two products, '2' two products, '3' three; 'Q' and '1': 'P' and '2' with one product
+struct Asked { char rung; size_t pick; };
+char rung_of(const LaunchWants& as) { const bool one = as.one && as.two; return as.prefix ? (one ? 'Q' : as.two ? 'P' : 'p') : as.two ? (one ? '1' : '2') : '3'; }
+SampleOutcome play(const Script& s, char rung, size_t pick) {
+	if (s.but_rung == rung && s.but_pick == pick) return outcome_of(s.but);
+	return outcome_of(rung == 'p' || rung == 'P' ? s.stops : rung == 'Q' ? s.one_stops : rung == '2' ? s.two : rung == '1' ? s.one_two : s.three);
+}
+struct Played { int rc = 0; std::vector<LaunchWants> wants; uint32_t one_refused = 0; std::vector<Asked> asked; std::vector<char> outcomes; int marks = 0; bool carrier_kept = true; };
+template <class Eligible, class Planned>
+Played play_ladder(size_t n, const LadderFacts& x, const Script& s, Eligible eligible, Planned planned) {
+	Played p;
+	p.rc = decide_wants(n, x, eligible, planned,
+		[&](size_t pick, const LaunchWants& as) {
+			const char rung = rung_of(as);
+			p.asked.push_back(Asked{rung, pick}); p.carrier_kept = p.carrier_kept && as.carrier == x.carrier;
+			const SampleOutcome o = play(s, rung, pick);
+			p.outcomes.push_back(o.rc == TWK_HIP_OK ? 'k' : o.rc == TWK_HIP_E_OVERFLOW ? 'O' : 'E');
+			return o;
+		},
+		[&](const char*, size_t, unsigned long long) { ++p.marks; }, p.wants, p.one_refused);
+	return p;
+}
+
+void check_ladder_invariants() {
+	static const size_t NS[] = {0, 1, 2, 3, 64, 65, 66, 129, 200};
+	static const char OUTCOMES[] = {'P', 'R', 'O', 'E'};
+	long scripts = 0;
+	for (int o2 = 0; o2 < 3; ++o2) for (int op = 0; op < 3; ++op) for (int oo = 0; oo < 3; ++oo) for (int o3 = 0; o3 < 3; ++o3) for (int fb = 0; fb < 16; ++fb)
+	for (const size_t n : NS) for (int fi = 0; fi < 4; ++fi) {
+		const size_t n_front = fi == 0 ? 0 : fi == 1 ? 1 : fi == 2 ? n / 2 : n;
+		if (n_front > n || (fi == 1 && n_front == 0) || (fi == 2 && n_front <= 1) || (fi == 3 && n_front <= std::max<size_t>(1, n / 2))) continue;      // (each cut once)
+		LadderFacts x; x.opt_two = o2; x.opt_prefix = op; x.opt_one = oo; x.opt_three = o3;
+		x.prefix_ok = (fb & 1) != 0; x.one_ok = (fb & 2) != 0; x.three_possible = (fb & 4) != 0; x.fused = (fb & 8) != 0; x.carrier = x.one_ok;
+		// (as RegionRun's predicate: nothing with option two = 0, every launch with two = 2, the launches in front of the cut otherwise)
+		auto eligible = [&](size_t i) { return o2 != 0 && (o2 == 2 || i < n_front); };
+		auto planned = [&](size_t i) { return i % 3 != 1; };
+		const bool samples = n > 0 && o3 == 1 && x.three_possible;
+		for (const char a : OUTCOMES) for (const char b : OUTCOMES) for (const char c3 : OUTCOMES) for (int shift = 0; shift < (samples ? 2 : 1); ++shift) {
+			if (!samples && !(a == 'P' && b == 'P' && c3 == 'P')) continue;      // (no sample is taken: one script says it all)
+			Script s; s.stops = a; s.two = b; s.three = c3; s.one_stops = shift ? 'R' : a; s.one_two = shift ? 'R' : b;
+			const Played p = play_ladder(n, x, s, eligible, planned);
+			++scripts; ++g_cases;
+			CHECK(p.wants.size() == n, "a launch without its wants, or one too many");
+			if (p.wants.size() != n) continue;
+			const size_t cut = o2 == 1 ? n_front : 0, step_behind = std::max<size_t>(1, (n - cut + 63) / 64);      // (the launches sampled one by one lead the plan)
+			size_t three_behind = 0, errors = 0;
+			for (size_t k = 0; k < p.asked.size(); ++k) {
+				if (p.asked[k].rung == '3' && p.asked[k].pick >= cut) ++three_behind;
+				if (p.outcomes[k] == 'E') { ++errors; CHECK(k + 1 == p.asked.size(), "a sample was taken after one that failed"); }
+			}
+			CHECK(three_behind <= 64, "%zu three-product samples behind the cut", three_behind);
+			CHECK(p.carrier_kept, "a sample without the region's row operand");
+			CHECK(errors ? p.rc == TWK_HIP_E_DEVICE : p.rc == TWK_HIP_OK, "the sampler's error is not the ladder's");
+			CHECK(p.marks == (int)p.asked.size() - (int)errors, "a sample without its line in the timeline");
+			if (!samples) CHECK(p.asked.empty() && p.one_refused == 0, "samples where no launch would take three products");
+			for (size_t i = 0; i < n; ++i) {
+				const LaunchWants& w = p.wants[i];
+				CHECK(!w.one || (x.one_ok && planned(i) && eligible(i)), "one product for a launch the planner did not mark, or behind the cut");
+				CHECK(!w.two || eligible(i), "two products behind the cut");
+				CHECK(!w.prefix || x.prefix_ok, "stops where the region may take none");
+				CHECK(w.carrier == x.carrier, "the region's row operand");
+				if (!samples) CHECK(w.three && w.two == (o2 == 2 && eligible(i)) && w.prefix == (x.prefix_ok && op == 2) && w.one == (x.one_ok && planned(i) && eligible(i)), "no sample: the marks made in front of them");
+			}
+			if (!samples || errors) continue;
+			// a launch in front of the cut is sampled itself; one behind it follows the sample of its own step
+			std::vector<char> sampled(n, 0);
+			for (const Asked& q : p.asked) sampled[q.pick] = 1;
+			for (size_t i = 0; i < n; ++i) {
+				const size_t pick = i < cut ? i : std::min(n - 1, cut + (i - cut) / step_behind * step_behind + step_behind / 2);
+				CHECK(sampled[pick], "launch %zu: the launch it follows (%zu) was not sampled", i, pick);
+				CHECK(p.wants[i].three == p.wants[pick].three && p.wants[i].prefix == p.wants[pick].prefix, "launch %zu does not follow its step's sample", i);
+			}
+			size_t n_sampled = 0; for (const char c : sampled) n_sampled += c;
+			CHECK(n_sampled == cut + (n - cut + step_behind - 1) / step_behind, "launches sampled: %zu", n_sampled);
+		}
+	}
+	printf("form-check: the sample ladder: %ld scripted runs keep their invariants\n", scripts);
+}
+
+// Named scripts, answers written out by hand from the ladder as RegionRun::decide_three_by_samples had it: the samples in order - runs of
+// `count` steps from pick0 on, `stride` apart, each asked the rungs of `rungs` in turn - and the wants launch by launch ('3' three, '2' two, 'p'
+// stops, 'c' carrier rows, '1' one product; "a|b": launches in turn).
+struct AskedRun { const char* rungs; size_t pick0, stride, count; };
+struct WantsRun { const char* wants; size_t count; };
+struct LadderCase {
+	const char* what; size_t n; unsigned long long eligible_mask, planned_mask;      // (launches of 64 and beyond: as bit 63)
+	LadderFacts x; Script s;
+	int rc; uint32_t one_refused; std::vector<AskedRun> asked; std::vector<WantsRun> wants;
+};
+LadderFacts facts(long long two, long long prefix, long long one, bool prefix_ok, bool one_ok, bool fused = false, long long three = 1) {
+	LadderFacts x; x.opt_two = two; x.opt_prefix = prefix; x.opt_one = one; x.opt_three = three; x.prefix_ok = prefix_ok; x.one_ok = one_ok; x.carrier = one_ok; x.fused = fused; x.three_possible = true;
+	return x;
+}
+Script script(char stops, char two, char three, char one_stops = 'R', char one_two = 'R', char but_rung = 0, size_t but_pick = 0, char but = 'P') {
+	Script s; s.stops = stops; s.two = two; s.three = three; s.one_stops = one_stops; s.one_two = one_two; s.but_rung = but_rung; s.but_pick = but_pick; s.but = but;
+	return s;
+}
+std::string wants_text(const LaunchWants& w) { return std::string(w.three ? "3" : "") + (w.two ? "2" : "") + (w.prefix ? "p" : "") + (w.carrier ? "c" : "") + (w.one ? "1" : ""); }
+
+void check_ladder_table() {
+	const unsigned long long ALL = ~0ull;
+	const std::vector<LadderCase> cases = {
+		{"one product marked and its sample poor", 2, 0x1, 0x1, facts(1, 1, 1, false, true), script('R', 'R', 'P', 'R', 'P'),
+		 TWK_HIP_OK, 0, {{"1", 0, 0, 1}, {"3", 1, 0, 1}}, {{"32c1", 1}, {"3c", 1}}},
+		{"one product refused, then two products poor; the launch behind the cut dense", 2, 0x1, 0x1, facts(1, 1, 1, false, true), script('R', 'P', 'R', 'R', 'R'),
+		 TWK_HIP_OK, 1, {{"12", 0, 0, 1}, {"3", 1, 0, 1}}, {{"32c", 1}, {"c", 1}}},
+		{"one product refused, then two products refused, then three dense", 1, 0x1, 0x1, facts(1, 1, 1, false, true), script('R', 'R', 'R', 'R', 'R'),
+		 TWK_HIP_OK, 1, {{"123", 0, 0, 1}}, {{"c", 1}}},
+		{"option one = 2: a rich one-product sample takes nothing back, and the launch is left without two products", 1, 0x1, 0x1, facts(1, 1, 2, false, true), script('R', 'R', 'P', 'R', 'R'),
+		 TWK_HIP_OK, 0, {{"13", 0, 0, 1}}, {{"3c1", 1}}},
+		{"the sample with stops poor on steps of 2 behind the cut: both launches of a step get the stops", 66, 0, 0, facts(1, 1, 1, true, false), script('P', 'R', 'P'),
+		 TWK_HIP_OK, 0, {{"p", 1, 2, 33}}, {{"3p", 66}}},
+		{"... poor at one step only: its two launches and no other", 66, 0, 0, facts(1, 1, 1, true, false), script('R', 'R', 'P', 'R', 'R', 'p', 5, 'P'),
+		 TWK_HIP_OK, 0, {{"p3", 1, 2, 2}, {"p", 5, 0, 1}, {"p3", 7, 2, 30}}, {{"3", 4}, {"3p", 2}, {"3", 60}}},
+		{"the two-product sample poor in front of the cut: each launch by its own sample", 3, 0x3, 0, facts(1, 1, 1, false, false), script('R', 'P', 'R', 'R', 'R', '2', 1, 'R'),
+		 TWK_HIP_OK, 0, {{"2", 0, 0, 1}, {"23", 1, 0, 1}, {"3", 2, 0, 1}}, {{"32", 1}, {"", 2}}},
+		{"the two-product sample poor on steps of 2 (the walk's launches behind one that is not): the sampled launch alone gets two products", 66, ALL & ~1ull, 0, facts(1, 1, 1, false, false), script('R', 'P', 'P'),
+		 TWK_HIP_OK, 0, {{"2", 1, 2, 33}}, {{"3|32", 66}}},
+		{"the same with stops: the whole step gets them, and two products with them", 66, ALL & ~1ull, 0, facts(1, 1, 1, true, false), script('P', 'P', 'P'),
+		 TWK_HIP_OK, 0, {{"P", 1, 2, 33}}, {{"3p", 1}, {"32p", 65}}},
+		{"every list overflows, on every rung", 1, 0x1, 0x1, facts(1, 1, 1, true, true), script('O', 'O', 'O', 'O', 'O'),
+		 TWK_HIP_OK, 1, {{"Q1P23", 0, 0, 1}}, {{"c", 1}}},
+		{"65 launches behind the cut: steps of 2, the last step one launch, dense there alone", 65, 0, 0, facts(1, 1, 1, false, false), script('R', 'R', 'P', 'R', 'R', '3', 64, 'R'),
+		 TWK_HIP_OK, 0, {{"3", 1, 2, 32}, {"3", 64, 0, 1}}, {{"3", 64}, {"", 1}}},
+		{"option two = 2 with stops: the sample with stops runs with two products; rich, the launch keeps the two products it was marked for", 2, ALL, 0, facts(2, 1, 1, true, false), script('P', 'R', 'P', 'R', 'R', 'P', 1, 'R'),
+		 TWK_HIP_OK, 0, {{"P", 0, 0, 1}, {"P3", 1, 0, 1}}, {{"32p", 1}, {"32", 1}}},
+		{"an error on the two-product rung ends the call there", 3, 0x7, 0, facts(1, 1, 1, false, false), script('R', 'P', 'P', 'R', 'R', '2', 1, 'E'),
+		 TWK_HIP_E_DEVICE, 0, {{"2", 0, 1, 2}}, {{"32", 1}, {"3", 2}}},
+		{"option three = 2: no sample, the marks of two = 2, prefix = 2 and the planner's one product stand", 2, ALL, 0x1, facts(2, 2, 1, true, true, false, 2), script('R', 'R', 'R'),
+		 TWK_HIP_OK, 0, {}, {{"32pc1", 1}, {"32pc", 1}}},
+		{"1 candidate in 128: dense for a launch through a matrix", 1, 0, 0, facts(1, 1, 1, false, false, false), script('R', 'R', 'M'),
+		 TWK_HIP_OK, 0, {{"3", 0, 0, 1}}, {{"", 1}}},
+		{"1 candidate in 128: still three products for a fused launch", 1, 0, 0, facts(1, 1, 1, false, false, true), script('R', 'R', 'M'),
+		 TWK_HIP_OK, 0, {{"3", 0, 0, 1}}, {{"3", 1}}},
+	};
+	for (const LadderCase& k : cases) {
+		auto bit = [](unsigned long long mask, size_t i) { return ((mask >> std::min<size_t>(i, 63)) & 1) != 0; };
+		const Played p = play_ladder(k.n, k.x, k.s, [&](size_t i) { return k.x.opt_two != 0 && bit(k.eligible_mask, i); }, [&](size_t i) { return bit(k.planned_mask, i); });
+		++g_cases;
+		std::string asked, want_asked, wants, want_wants;
+		for (const Asked& q : p.asked) asked += std::string(1, q.rung) + std::to_string(q.pick) + " ";
+		for (const AskedRun& r : k.asked) for (size_t j = 0; j < r.count; ++j) for (const char* c = r.rungs; *c; ++c) want_asked += std::string(1, *c) + std::to_string(r.pick0 + j * r.stride) + " ";
+		for (const LaunchWants& w : p.wants) wants += wants_text(w) + ",";
+		for (const WantsRun& r : k.wants) {
+			std::vector<std::string> turn(1);
+			for (const char* c = r.wants; *c; ++c) { if (*c == '|') turn.emplace_back(); else turn.back() += *c; }
+			for (size_t j = 0; j < r.count; ++j) want_wants += turn[j % turn.size()] + ",";
+		}
+		CHECK(p.rc == k.rc && p.one_refused == k.one_refused, "%s: rc %d, %u samples refused", k.what, p.rc, p.one_refused);
+		CHECK(asked == want_asked, "%s: samples %s, expected %s", k.what, asked.c_str(), want_asked.c_str());
+		CHECK(wants == want_wants, "%s: wants %s expected %s", k.what, wants.c_str(), want_wants.c_str());
+	}
+	printf("form-check: the sample ladder: %zu named scripts as written out\n", cases.size());
 }
 
 }  // namespace
@@ -220,6 +472,11 @@ int main() {
 	check_gave_up();
 	check_carrier();
 	check_one();
+	check_named_grants();
+	check_thresholds();
+	check_sample_subtile();
+	check_ladder_invariants();
+	check_ladder_table();
 	printf("form-check: %ld cases, %d bad\n", g_cases, g_bad_checks);
 	return g_bad_checks ? 1 : 0;
 }
