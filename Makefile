@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check varsel-check blocks-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check varsel-check blocks-check split-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -198,6 +198,15 @@ blocks-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/blocks_check.cpp -o build/blocks_check
 	./build/blocks_check
+
+# LD splitting's host side (csrc/hip/ld_split_index.h): every lane of the prefix, block-sum, layer and backtrack kernels - the wave scan and
+# its carry, the saturation rule, the layers' ranges, the LDS windows and their bounds, the smallest-d rule - against a direct evaluation of
+# the definition with arrays that count their writes, and tiny cases against an enumeration of all partitions (csrc/tools/split_check.cpp):
+# host code only, under AddressSanitizer and UBSan
+split-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/split_check.cpp -o build/split_check
+	./build/split_check
 
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) $(ASAN_DIR) build

@@ -43,6 +43,7 @@ extern "C" {
 /*    (still 5: twk_hip_ld_score_annot - partitioned LD scores - is an entry point more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_bandmat_layout / twk_hip_ld_matrix_band / twk_hip_bandmat_last - the banded LD matrix - are three entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_dprime_ci_band / twk_hip_ld_blocks / twk_hip_blocks_last / twk_hip_blocks_stages - haplotype blocks - are four entry points and one struct more; nothing existing changed) */
+/*    (still 5: twk_hip_ld_split / twk_hip_split_last - LD splitting - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_ld_topk / twk_hip_topk_last - top-k LD partners - are two entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_select_samples / twk_hip_selection / twk_hip_get_meta / twk_hip_set_hwe / twk_hip_select_last - sample subsets - are five entry points more; no struct and no existing entry point changed) */
 /*    (still 5: twk_hip_select_variants / twk_hip_variant_selection / twk_hip_variant_map / twk_hip_select_variants_last - variant subsets - are four entry points more; no existing struct and no existing entry point changed) */
@@ -584,6 +585,44 @@ int twk_hip_blocks_last(const twk_hip_ctx* ctx, double* walk_ms, uint64_t* band_
 /* ... and the device time in ms of its stages between the bounds' launches and the walk: the prefix counts, the counting pass over the
  * candidates and the scan; the emitting pass; the sort (each may be NULL; 0 for a stage that did not run). */
 int twk_hip_blocks_stages(const twk_hip_ctx* ctx, double* counts_ms, double* emit_ms, double* sort_ms);
+
+/* LD splitting (Prive 2021, "Optimal linkage disequilibrium splitting"; bigsnpr's snp_ldsplit): where to cut a contig into K blocks of
+ * min_size .. max_size variants so that as little r2 as possible crosses a cut, for every K = 1 .. k_max, solved on the device over the
+ * banded r2 matrix, which never leaves it.
+ *   INPUT    the slice [a0, a0 + n) of the working set, sorted by position on ONE contig; mode, filters (minP >= 1), tile_variants and
+ *            l_window > 0 base pairs as for twk_hip_ld_matrix_band; min_size, max_size and k_max in variants.
+ *   THE BAND B: what twk_hip_ld_matrix_band with the same arguments, TWK_HIP_STAT_R2 and fill 0.0f writes.
+ *   WEIGHTS  for u < v (relative to the slice): q(u, v) = llrint((double)B[u][v] * 2^32) if v lies in u's band, else 0.  The product is
+ *            exact in double.  The diagonal is ignored.
+ *   OBJECTIVE  within(a, b) = the sum of q(u, v) over a <= u < v < b; T = within(0, n).  A K-partition is 0 = c_0 < c_1 < .. < c_K = n
+ *            with min_size <= c_i - c_(i-1) <= max_size; gain_K is the maximum over K-partitions of the sum of within(c_(i-1), c_i), and
+ *            cost_K = T - gain_K: the sum of r2 outside the blocks, in units of 2^-32.
+ *   RECURRENCE  G_0(0) = 0, G_0(b > 0) infeasible; G_k(b) = the maximum over d in [min_size, min(max_size, b)] with G_(k-1)(b - d)
+ *            feasible of G_(k-1)(b - d) + within(b - d, b); D_k(b) is the SMALLEST d that attains it.  The partition reported for K is
+ *            the one backtracked from (K, n) through D: among the optimal ones that whose size sequence, read from the last block, is
+ *            lexicographically smallest.  64-bit integers throughout: the result is a function of the band's bytes and the three sizes
+ *            alone, the same for any tile_variants and on any repeat.
+ *   OUTPUT   HOST arrays.  total[0] = T.  feasible[K - 1] (k_max bytes): 1 where a K-partition exists, else 0.  Where it is 1:
+ *            cost[K - 1] (k_max entries) = cost_K and cuts[(K - 1) * (k_max + 1) + i] = c_i for i = 0 .. K (k_max * (k_max + 1) entries,
+ *            relative to the slice); the entries of cost and cuts of an infeasible K, and beyond c_K in a row, are left untouched.
+ *            n_records, n_pairs (each may be NULL): as twk_hip_ld_matrix_band's.
+ *   TWK_HIP_E_INVALID before any launch, with nothing written: twk_hip_ld_matrix_band's own refusals, l_window == 0, a slice on two
+ *            contigs, min_size == 0, min_size > max_size, max_size > 65535 (D is uint16), k_max == 0 or k_max > 1024,
+ *            (uint64_t)n * max_size >= 2^32 (below it every sum of a partition stays under 2^63: at most n * max_size / 2 in-block
+ *            pairs of at most 2^32 each), 2^31 or more in-band pairs (T stays under 2^63), a NULL total, feasible, cost or cuts.
+ *   DEVICE MEMORY for the length of the call: the band (4 bytes a slot, 16 a variant), 8 bytes per (variant, offset <= min(widest upper
+ *            band, max_size - 1)) of row prefixes, 8 per (variant, d in [min_size, max_size]) of block sums - at most 16 bytes per
+ *            (variant, d <= max_size) together - 2 * k_max bytes a variant of D and 28 a variant besides;
+ *            TWK_HIP_E_NOMEM with the byte count in twk_hip_last_error.
+ *   twk_hip_split_last  of the context's last twk_hip_ld_split call: the device time in ms of the band's launches, of row prefixes +
+ *            block sums, of the layers and of the backtrack, and the bytes of device memory held (each may be NULL).
+ * NOT bigsnpr's max_r2 constraint (no cut is refused for a large r2 across it) and NOT LDetect's filtered-minimum rule.  There is NO
+ * reference counterpart. */
+int twk_hip_ld_split(twk_hip_ctx* ctx, int mode, const twk_hip_filters* filters,
+                     uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
+                     uint32_t min_size, uint32_t max_size, uint32_t k_max,
+                     uint64_t* total, uint8_t* feasible, uint64_t* cost, uint32_t* cuts, uint64_t* n_records, uint64_t* n_pairs);
+int twk_hip_split_last(const twk_hip_ctx* ctx, double* band_ms, double* sums_ms, double* layers_ms, double* backtrack_ms, uint64_t* bytes);
 
 /* LD decay over the same slice of the pair space as twk_hip_ld_score, with the same arguments: r2 as a function of the distance
  * between two variants.  A pair COUNTS when twk_hip_ld_region with these arguments would report a record for it, both variants lie on

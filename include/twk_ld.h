@@ -117,6 +117,13 @@ struct twk_block_settings {
 	std::string ci_out;         // PREFIX of PREFIX.lo.npy, .hi.npy, .indptr.npy, .first.npy and .variants.tsv
 };
 
+// What Split takes beyond twk_ld_settings: the block sizes in variants, the largest number of blocks a contig is split into, and the
+// number of blocks of the partition that is written out (0: none).
+struct twk_split_settings {
+	uint32_t min_size = 0, max_size = 0, max_blocks = 0;      // --min-size, --max-size, --max-blocks: all three required
+	uint32_t blocks = 0;                                      // -B k: PREFIX.blocks.tsv holds every contig's k-block partition
+};
+
 // What Relationship needs beyond twk_ld_settings.
 struct twk_relationship_settings {
 	int32_t stat = 2;           // TWK_HIP_REL_KING; or _IBS (0), _IBS0 (1) (include/twk_hip.h)
@@ -229,6 +236,16 @@ public:
 	// PREFIX.variants.tsv as Matrix writes them for a band.  Not PLINK's or Haploview's numbers: they add a LOD filter, their own MAF
 	// rule and, unphased, a double-heterozygote term.  settings.minP must be 1 (the default).  `tomahawk blocks` ends here.
 	bool Blocks(const twk_ld_settings& settings, const twk_block_settings& blocks);
+	// Not in the reference: LD splitting (Prive 2021; bigsnpr's snp_ldsplit) - every contig of the selection cut into K near-independent
+	// blocks of split.min_size .. split.max_size variants so that the r2 crossing a cut is smallest, for every K up to split.max_blocks.
+	// Loads the .twk exactly as Prune does (-I, -p / -u, --keep, --extract ..; -c / -C are refused); the window (settings.l_window bases)
+	// is required.  One engine call per contig (twk_hip_ld_split): the banded r2 matrix stays on the GPU and the dynamic programme runs
+	// there.  settings.out is a PREFIX: PREFIX.costs.tsv holds per contig and feasible K the cost (the r2 outside the blocks, 17
+	// digits), the cost as a fraction of the contig's total, and the sum of squared block sizes; with split.blocks = k,
+	// PREFIX.blocks.tsv holds contig, block, first position, last position and variants of every contig's k-block partition - an error
+	// if k is infeasible on some contig.  No max_r2 constraint, and not LDetect's rule.  settings.minP must be 1.  `tomahawk ldsplit`
+	// ends here.
+	bool Split(const twk_ld_settings& settings, const twk_split_settings& split);
 
 	// Not in the reference: a switch of the GPU engine by name, applied to every engine context this object creates
 	// (twk_hip_set_option, include/twk_hip.h - measurement and test switches; none changes a record), plus two of this

@@ -20,6 +20,8 @@
 //   varsel (ld_varsel.hip.h) a predicate per variant -> scan -> the rows and the metadata of the kept variants gathered beside the base (twk_hip_select_variants)
 //   blocks (ld_blocks.hip.h) cells -> the record's 2 x 2 table -> a likelihood scan over 101 values of D' -> the bounds lo, hi as two bytes per in-window pair in band storage
 //                          (twk_hip_ld_dprime_ci_band) -> prefix counts, candidates, sort, walk: haplotype blocks (twk_hip_ld_blocks)
+//   split (ld_split.hip.h) the bandmat kind's r2 band, kept on the device -> integer row prefixes -> block sums -> one max-plus layer per k -> backtrack: the optimal
+//                          split of a contig into near-independent LD blocks for every K (twk_hip_ld_split: no kind of its own, its kernels run behind the band's launches)
 //   (score, prune, clump, matrix, decay, aggregate, annot, bandmat, topk and the bounds of dprime_ci / blocks are the kinds of one reduce path - Reduce, launch_reduce, ReduceCall; ld_reduce.hip.h holds what their kernels share)
 // over super-tiles of the variant-pair triangle.  Device memory lives in the
 // ctx; nothing here falls back to the CPU.
@@ -61,6 +63,7 @@
 #include "ld_matrix.hip.h"
 #include "ld_bandmat.hip.h"
 #include "ld_blocks.hip.h"
+#include "ld_split.hip.h"
 #include "ld_topk.hip.h"
 #include "ld_relate.hip.h"
 #include "ld_subset.hip.h"
@@ -350,7 +353,9 @@ struct twk_hip_ctx {
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
 	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
-	double blocks_stage_ms[3] = {0, 0, 0};      // of the last twk_hip_ld_blocks call: prefix counts + candidate counts + scan, the emitting pass, the sort (twk_hip_blocks_stages)
+	double split_stage_ms[4] = {0, 0, 0, 0};    // of the last twk_hip_ld_split call: the band's launches, prefixes + block sums, the layers, the backtrack (twk_hip_split_last)
+	uint64_t split_bytes = 0;                   // ... and the device memory it held
+	double blocks_stage_ms[3] = {0, 0, 0};    // of the last twk_hip_ld_blocks call: prefix counts + candidate counts + scan, the emitting pass, the sort (twk_hip_blocks_stages)
 	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
 	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last, twk_hip_bandmat_last, twk_hip_topk_last)
 	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
@@ -3078,8 +3083,36 @@ int twk_hip_bandmat_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_w
 	return bandmat_layout(c, a0, n, l_window, first, row_ptr);
 }
 
-// ... and the band itself: preset to the fill in front of the launches, its diagonal behind the last of them, one contiguous copy of
-// row_ptr[n] floats; first and row_ptr are the host layout's.
+// The band of the slice on the device (call.d_band, call.d_band_rows): preset to the fill in front of the launches, its diagonal behind the
+// last of them.  h_first, h_ptr: bandmat_layout's.
+extern "C++" {
+namespace {
+int band_fill(ReduceCall& call, int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window, int32_t stat, float fill,
+              const std::vector<uint32_t>& h_first, const std::vector<uint64_t>& h_ptr, uint64_t* n_pairs) {
+	twk_hip_ctx* c = call.c;
+	const size_t cells = (size_t)h_ptr[n];
+	std::vector<BandRow> rows(n);
+	for (uint32_t u = 0; u < n; ++u) rows[u] = BandRow{h_ptr[u], h_first[u], (uint32_t)(h_ptr[u + 1] - h_ptr[u])};
+	// the band: row_ptr[n] floats, and a BandRow per variant
+	int rc = hold_for_call(c, call.d_band_rows, (size_t)n, "the band map of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	rc = call.hold(call.d_band, cells, "the banded LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
+	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
+	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)call.d_band.get(), (int)fill_bits, cells, c->s_compute));
+	// (from pageable memory: the copy has left `rows` when it returns; it lives to the end of the call anyway)
+	HIPCHK(c, hipMemcpyAsync(call.d_band_rows, rows.data(), (size_t)n * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
+	c->reduce.map.band = BandMap{call.d_band, call.d_band_rows, c->d_counts, a0, n, stat};
+	call.arm(cells * sizeof(float));
+	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
+	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
+		hipLaunchKernelGGL(k_ld_bandmat_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, call.d_band.get(), (const BandRow*)call.d_band_rows.get(), n, 1.0f);
+		HIPCHK(c, hipGetLastError());
+	}
+	return TWK_HIP_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+// ... and the band itself, in one contiguous copy of row_ptr[n] floats; first and row_ptr are the host layout's.
 int twk_hip_ld_matrix_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
                            int32_t stat, float fill, float* values, uint64_t capacity, uint32_t* first, uint64_t* row_ptr, uint64_t* n_records, uint64_t* n_pairs) {
 	ReduceCall call(c, Reduce::bandmat, f, values && first && row_ptr && valid_stat(stat) && (window & TWK_HIP_OPT_WINDOW), mode, a0, n);
@@ -3093,22 +3126,7 @@ int twk_hip_ld_matrix_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 		snprintf(c->err, sizeof(c->err), "banded LD matrix: the band of %u variants holds %zu floats, the caller's array %llu", n, cells, (unsigned long long)capacity);
 		return TWK_HIP_E_INVALID;
 	}
-	std::vector<BandRow> rows(n);
-	for (uint32_t u = 0; u < n; ++u) rows[u] = BandRow{h_ptr[u], h_first[u], (uint32_t)(h_ptr[u + 1] - h_ptr[u])};
-	// the band: row_ptr[n] floats, and a BandRow per variant
-	rc = hold_for_call(c, call.d_band_rows, (size_t)n, "the band map of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	rc = call.hold(call.d_band, cells, "the banded LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
-	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)call.d_band.get(), (int)fill_bits, cells, c->s_compute));
-	// (from pageable memory: the copy has left `rows` when it returns; it lives to the end of the call anyway)
-	HIPCHK(c, hipMemcpyAsync(call.d_band_rows, rows.data(), (size_t)n * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
-	c->reduce.map.band = BandMap{call.d_band, call.d_band_rows, c->d_counts, a0, n, stat};
-	call.arm(cells * sizeof(float));
-	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
-	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
-		hipLaunchKernelGGL(k_ld_bandmat_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, call.d_band.get(), (const BandRow*)call.d_band_rows.get(), n, 1.0f);
-		HIPCHK(c, hipGetLastError());
-	}
+	rc = band_fill(call, mode, a0, n, tile_variants, window, l_window, stat, fill, h_first, h_ptr, n_pairs); if (rc) return rc;
 	unsigned long long count = 0;
 	rc = call.tail("banded LD matrix", [&] {
 		return hipMemcpyAsync(values, call.d_band, cells * sizeof(float), hipMemcpyDeviceToHost, c->s_compute);
@@ -3313,6 +3331,130 @@ int twk_hip_blocks_stages(const twk_hip_ctx* c, double* counts_ms, double* emit_
 	if (counts_ms) *counts_ms = c->blocks_stage_ms[0];
 	if (emit_ms) *emit_ms = c->blocks_stage_ms[1];
 	if (sort_ms) *sort_ms = c->blocks_stage_ms[2];
+	return TWK_HIP_OK;
+}
+
+// LD splitting (ld_split.hip.h): the banded r2 matrix of the slice, filled by the bandmat kind and kept on the device, then row prefixes,
+// block sums, one layer launch per k and the backtrack - all of it integers.  (The bandmat kind's own twk_hip_bandmat_last keeps what the
+// last twk_hip_ld_matrix_band call left.)
+int twk_hip_ld_split(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
+                     uint32_t min_size, uint32_t max_size, uint32_t k_max, uint64_t* total, uint8_t* feasible, uint64_t* cost, uint32_t* cuts,
+                     uint64_t* n_records, uint64_t* n_pairs) {
+	// (before `call`: freed behind its destructor, which waits for the device)
+	DevBuf<long long> d_rp, d_w, d_row_total, d_g, d_gn;
+	DevBuf<unsigned long long> d_cost, d_total;
+	DevBuf<uint32_t> d_upc, d_cuts, d_broken;
+	DevBuf<uint16_t> d_dk;
+	DevBuf<uint8_t> d_feasible;
+	ReduceCall call(c, Reduce::bandmat, f, total && feasible && cost && cuts && l_window > 0 && sp_sizes_ok(n, min_size, max_size, k_max), mode, a0, n);
+	if (call.bad) return call.bad;
+	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
+	if (c->h_meta[a0].rid != c->h_meta[(size_t)a0 + n - 1].rid) {
+		snprintf(c->err, sizeof(c->err), "LD splitting: the variants [%u, %u) lie on more than one contig; split one contig a call", a0, a0 + n);
+		return TWK_HIP_E_INVALID;
+	}
+	std::vector<uint32_t> h_first(n);
+	std::vector<uint64_t> h_ptr((size_t)n + 1);
+	int rc = bandmat_layout(c, a0, n, l_window, h_first.data(), h_ptr.data()); if (rc) return rc;
+	const size_t cells = (size_t)h_ptr[n];
+	if ((cells - n) / 2 >= SPLIT_MAX_PAIRS) {
+		snprintf(c->err, sizeof(c->err), "LD splitting: the band of %u variants holds %zu pairs, 2^31 or more: their sum may pass 2^63; narrow the window or split the slice", n, (cells - n) / 2);
+		return TWK_HIP_E_INVALID;
+	}
+	std::vector<uint32_t> h_upc(n);
+	uint32_t widest = 1;                       // the offsets Rp stores: at least one row, so that no buffer is empty
+	for (uint32_t u = 0; u < n; ++u) {
+		h_upc[u] = sp_upc(sp_upper(h_first[u], (uint32_t)(h_ptr[u + 1] - h_ptr[u]), u), max_size);
+		widest = std::max(widest, h_upc[u]);
+	}
+	const SplitSizes sizes{n, min_size, max_size, k_max};
+	const size_t n1 = (size_t)n + 1, rp_items = (size_t)widest * n, w_items = (size_t)(max_size - min_size + 1) * n1, d_items = (size_t)k_max * n1;
+	const size_t cut_items = (size_t)k_max * (k_max + 1);
+	{
+		const char* what = "LD splitting: the row prefixes and block sums of %u variants need %zu bytes of device memory: %s";
+		rc = hold_for_call(c, d_rp, rp_items, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_w, w_items, what, n); if (rc) return rc;
+		what = "LD splitting: the layers of %u variants need %zu bytes of device memory: %s";
+		rc = hold_for_call(c, d_dk, d_items, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_g, 2 * n1, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_row_total, (size_t)n, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_upc, (size_t)n, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_gn, (size_t)k_max + 1, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_cost, (size_t)k_max, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_cuts, cut_items, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_feasible, (size_t)k_max, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_total, (size_t)1, what, n); if (rc) return rc;
+		rc = hold_for_call(c, d_broken, (size_t)1, what, n); if (rc) return rc;
+	}
+	const auto bandmat_last = c->reduce_last[(int)Reduce::bandmat];      // (arm() overwrites it: put back below)
+	struct Restore { twk_hip_ctx* c; decltype(bandmat_last) was; ~Restore() { c->reduce_last[(int)Reduce::bandmat] = was; } } restore{c, bandmat_last};
+	Events ev;
+	HIPCHK(c, ev.add(5));
+	for (double& x : c->split_stage_ms) x = 0;
+	c->split_bytes = cells * sizeof(float) + (size_t)n * sizeof(BandRow) + (rp_items + w_items + 2 * n1 + n + k_max + 1) * sizeof(long long) + d_items * sizeof(uint16_t) +
+	                 (size_t)n * sizeof(uint32_t) + (size_t)k_max * 9 + cut_items * sizeof(uint32_t) + 12;
+	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
+	rc = band_fill(call, mode, a0, n, tile_variants, (int32_t)TWK_HIP_OPT_WINDOW, l_window, TWK_HIP_STAT_R2, 0.0f, h_first, h_ptr, n_pairs); if (rc) return rc;
+	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
+	// (from pageable memory: the copy has left h_upc when it returns)
+	HIPCHK(c, hipMemcpyAsync(d_upc, h_upc.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d_gn, 0xFF, ((size_t)k_max + 1) * sizeof(long long), c->s_compute));      // SPLIT_INFEASIBLE
+	HIPCHK(c, hipMemsetAsync(d_g, 0, sizeof(long long), c->s_compute));                                // G_0(0) = 0, layer 0's whole range
+	const dim3 threads(SPLIT_THREADS);
+	hipLaunchKernelGGL(k_split_prefix, dim3((n + 3) / 4), threads, 0, c->s_compute, (const float*)call.d_band, (const BandRow*)call.d_band_rows, (const uint32_t*)d_upc, n,
+	                   d_rp.get(), d_row_total.get());
+	HIPCHK(c, hipGetLastError());
+	hipLaunchKernelGGL(k_split_sums, dim3((n + SPLIT_THREADS - 1) / SPLIT_THREADS), threads, 0, c->s_compute, (const long long*)d_rp, (const uint32_t*)d_upc, sizes, d_w.get());
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(ev[2], c->s_compute));
+	for (uint32_t k = 1; k <= k_max; ++k) {
+		const uint32_t lo = sp_layer_lo(k, min_size), hi = sp_layer_hi(k, max_size, n);
+		if (lo > hi) break;                    // k * min_size > n: no further layer holds a feasible b
+		long long* const g_prev = d_g.get() + ((k - 1) & 1) * n1;
+		long long* const g_cur = d_g.get() + (k & 1) * n1;
+		hipLaunchKernelGGL(k_split_layer, dim3((hi - lo) / SPLIT_THREADS + 1), threads, 0, c->s_compute, (const long long*)g_prev, (const long long*)d_w, sizes, k, lo, hi,
+		                   sp_layer_lo(k - 1, min_size), sp_layer_hi(k - 1, max_size, n), g_cur, d_dk.get(), d_gn.get());
+		HIPCHK(c, hipGetLastError());
+	}
+	HIPCHK(c, hipEventRecord(ev[3], c->s_compute));
+	hipLaunchKernelGGL(k_split_backtrack, dim3(1), dim3(SPLIT_MAX_K), 0, c->s_compute, (const long long*)d_row_total, (const long long*)d_gn, (const uint16_t*)d_dk, sizes,
+	                   d_total.get(), d_feasible.get(), d_cost.get(), d_cuts.get(), d_broken.get());
+	HIPCHK(c, hipGetLastError());
+	HIPCHK(c, hipEventRecord(ev[4], c->s_compute));
+	std::vector<uint8_t> h_feasible(k_max);
+	std::vector<unsigned long long> h_cost(k_max);
+	std::vector<uint32_t> h_cuts(cut_items);
+	unsigned long long h_total = 0, count = 0;
+	uint32_t broken = 0;
+	rc = call.download("LD splitting: the partitions", [&] {
+		hipError_t e = hipMemcpyAsync(h_feasible.data(), d_feasible, k_max, hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(h_cost.data(), d_cost, (size_t)k_max * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(h_cuts.data(), d_cuts, cut_items * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(&h_total, d_total, sizeof(h_total), hipMemcpyDeviceToHost, c->s_compute);
+		if (e == hipSuccess) e = hipMemcpyAsync(&broken, d_broken, sizeof(broken), hipMemcpyDeviceToHost, c->s_compute);
+		return e != hipSuccess ? e : hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute);
+	});
+	if (rc) return rc;
+	for (int st = 0; st < 4; ++st) { float ms = 0; if (hipEventElapsedTime(&ms, ev[st], ev[st + 1]) == hipSuccess) c->split_stage_ms[st] = ms; }
+	if (broken) { snprintf(c->err, sizeof(c->err), "LD splitting: %u of the chains through D do not end at the slice's start", broken); return TWK_HIP_E_DEVICE; }
+	*total = h_total;
+	for (uint32_t K = 1; K <= k_max; ++K) {
+		feasible[K - 1] = h_feasible[K - 1];
+		if (!h_feasible[K - 1]) continue;      // (the rows of an infeasible K stay as the caller left them)
+		cost[K - 1] = h_cost[K - 1];
+		memcpy(cuts + sp_cut_slot(K, 0, k_max), h_cuts.data() + sp_cut_slot(K, 0, k_max), ((size_t)K + 1) * sizeof(uint32_t));
+	}
+	if (n_records) *n_records = count;
+	return TWK_HIP_OK;
+}
+
+int twk_hip_split_last(const twk_hip_ctx* c, double* band_ms, double* sums_ms, double* layers_ms, double* backtrack_ms, uint64_t* bytes) {
+	if (!c) return TWK_HIP_E_INVALID;
+	if (band_ms) *band_ms = c->split_stage_ms[0];
+	if (sums_ms) *sums_ms = c->split_stage_ms[1];
+	if (layers_ms) *layers_ms = c->split_stage_ms[2];
+	if (backtrack_ms) *backtrack_ms = c->split_stage_ms[3];
+	if (bytes) *bytes = c->split_bytes;
 	return TWK_HIP_OK;
 }
 

@@ -536,6 +536,73 @@ static const Command<tomahawk::twk_block_settings> BLOCKS = {
 	nullptr,
 	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_block_settings& blocks) { return ld.Blocks(settings, blocks); }};
 
+// `tomahawk ldsplit` (not in the reference): every contig split into near-independent LD blocks, the dynamic programme solved on the GPU.
+static void ldsplit_usage() {
+	program_message();
+	std::cerr <<
+	"About:  Optimal LD splitting (Prive 2021; bigsnpr's snp_ldsplit): where to cut every contig into K blocks\n"
+	"        of --min-size to --max-size variants so that as little r2 as possible crosses a cut, for every K\n"
+	"        up to --max-blocks.  The r2 is that of every pair `calc` would report under the same options\n"
+	"        inside the window; the banded r2 matrix stays on the GPU and the dynamic programme runs there, in\n"
+	"        integers of 2^-32 (no .two is written).  Not bigsnpr's max_r2 constraint, not LDetect's rule.\n\n"
+	"Usage:  tomahawk ldsplit [options] -i <in.twk> -w <bases> --min-size m --max-size M --max-blocks K -o <PREFIX>\n\n"
+	"Options:\n"
+	"  -i FILE   input Tomahawk (required)\n"
+	"  -o PREFIX output prefix (required): PREFIX.costs.tsv, and with -B PREFIX.blocks.tsv\n"
+	"  -w INT    window in bases: pairs further apart count as r2 = 0 (required)\n"
+	"  --min-size INT    smallest block in variants (required, >= 1)\n"
+	"  --max-size INT    largest block in variants (required, <= 65535)\n"
+	"  --max-blocks INT  largest number of blocks a contig is split into (required, <= 1024)\n"
+	"  -B INT    also write every contig's partition into this many blocks\n"
+	"  -t INT    number of CPU threads used to unpack the input (default: maximum available)\n"
+	"  -I STRING filter interval <contig>:pos-pos (see manual)\n"
+	"  -p        force computations to use phased math\n"
+	"  -u        force computations to use unphased math\n"
+	"  -r FLOAT  Pearson's R-squared minimum cut-off value (default: 0)\n"
+	"  -P FLOAT  accepted only as 1: a split looks at every record, Fisher's test is not run\n"
+	"  --keep / --remove FILE, --extract / --exclude FILE, --maf, --max-maf, --mac, --geno, --hwe: as for calc\n"
+	"  --engine-option KEY=INT  a switch of the GPU engine (twk_hip_set_option, include/twk_hip.h; repeatable)\n"
+	"  (-c / -C are refused: a block sum needs every pair inside the block)\n"
+	"Output: PREFIX.costs.tsv, '#' header lines, then per contig and feasible K:\n"
+	"        contig <TAB> K <TAB> cost <TAB> cost / total <TAB> sum of squared block sizes\n"
+	"        PREFIX.blocks.tsv (-B): contig <TAB> block <TAB> first pos <TAB> last pos <TAB> variants\n"
+	"Environment: TWK_HIP_DEVICE=<n> selects the GPU (default 0).\n" << std::endl;
+}
+static const struct option LDSPLIT_LONG_OPTIONS[] = {
+	{"input", required_argument, 0, 'i'}, {"threads", optional_argument, 0, 't'}, {"output", required_argument, 0, 'o'},
+	{"interval", optional_argument, 0, 'I'}, {"parts", optional_argument, 0, 'c'}, {"partStart", optional_argument, 0, 'C'},
+	{"minP", optional_argument, 0, 'P'}, {"force-phased", no_argument, 0, 'p'}, {"force-unphased", no_argument, 0, 'u'},
+	{"minR2", optional_argument, 0, 'r'}, {"windowBases", optional_argument, 0, 'w'},
+	{"engine-option", required_argument, 0, 1000}, {"keep", required_argument, 0, 1006}, {"remove", required_argument, 0, 1007}, VARIANT_SELECTION_LONG_OPTIONS,
+	{"min-size", required_argument, 0, 1030}, {"max-size", required_argument, 0, 1031}, {"max-blocks", required_argument, 0, 1032}, {"blocks", required_argument, 0, 'B'}, {0, 0, 0, 0}};
+static Took ldsplit_option(int c, const char* arg, twk_ld_settings&, tomahawk::twk_split_settings& split) {
+	uint32_t* where = c == 1030 ? &split.min_size : c == 1031 ? &split.max_size : c == 1032 ? &split.max_blocks : c == 'B' ? &split.blocks : nullptr;
+	if (!where) return declined;
+	const char* name = c == 1030 ? "--min-size" : c == 1031 ? "--max-size" : c == 1032 ? "--max-blocks" : "-B";
+	const uint32_t top = c == 1032 || c == 'B' ? 1024 : 65535;
+	const std::string a(arg);      // an unsigned integer, digits only
+	if (a.empty() || a.size() > 6 || a.find_first_not_of("0123456789") != std::string::npos || strtoul(arg, nullptr, 10) < 1 || strtoul(arg, nullptr, 10) > top) {
+		char why[96]; snprintf(why, sizeof(why), "%s wants an integer between 1 and %u", name, top); fail(why); return failed;
+	}
+	*where = (uint32_t)strtoul(arg, nullptr, 10);
+	return took;
+}
+static bool ldsplit_check(twk_ld_settings& settings, tomahawk::twk_split_settings& split) {
+	if (!split.min_size || !split.max_size || !split.max_blocks) return fail("A split needs --min-size, --max-size and --max-blocks");
+	if (split.min_size > split.max_size) return fail("Cannot have --min-size above --max-size");
+	if (split.blocks > split.max_blocks) return fail("Cannot write a partition of more blocks (-B) than --max-blocks");
+	if (!settings.window) return fail("A split needs a window in bases (-w)");
+	if (settings.out.empty() || settings.out == "-") return fail("A split writes PREFIX.costs.tsv and PREFIX.blocks.tsv: -o wants a prefix");
+	return true;
+}
+// (Reached by its name, but not a row of ENTRIES, as `blocks`: the list of `tomahawk` without arguments answers as recorded.)
+static const Command<tomahawk::twk_split_settings> LDSPLIT = {
+	"ldsplit", "  ldsplit  optimal near-independent LD blocks (Prive 2021), the dynamic programme solved on the GPU\n", ldsplit_usage,
+	"i:o:t:puP:r:w:I:c:C:B:?", LDSPLIT_LONG_OPTIONS, 0, {{"cC", "Cannot split a part of the pair space (-c / -C): a block sum needs every pair inside the block"}},
+	"Cannot split with a cutoff P-value below 1: a split looks at every record and Fisher's exact test is not run", ldsplit_option,
+	ldsplit_check,
+	[](tomahawk::twk_ld& ld, const twk_ld_settings& settings, const tomahawk::twk_split_settings& split) { return ld.Split(settings, split); }};
+
 // `tomahawk relationship`: the sample-by-sample matrix (IBS, IBS0 or KING kinship), counted on the GPU.  The reference's name and its -i / -I;
 // its numbers are not reproduced (include/twk_hip.h, twk_hip_relationship).
 static void relationship_usage() {
@@ -1031,6 +1098,7 @@ static int run_main(int argc, char** argv) {
 	tomahawk::LITERAL_COMMAND_LINE = "tomahawk";
 	for (int i = 1; i < argc; ++i) tomahawk::LITERAL_COMMAND_LINE += " " + std::string(argv[i]);
 	if (strcmp(argv[1], BLOCKS.name) == 0) return engine<BLOCKS>(argc, argv);
+	if (strcmp(argv[1], LDSPLIT.name) == 0) return engine<LDSPLIT>(argc, argv);
 	for (const Entry& e : ENTRIES)
 		if (strcmp(argv[1], e.name) == 0 || (e.alias && strcmp(argv[1], e.alias) == 0) || (e.by_prefix && strncmp(argv[1], e.name, strlen(e.name)) == 0)) return e.main(argc, argv);
 	if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "version") == 0) { program_message(); return 0; }

@@ -1847,6 +1847,106 @@ bool twk_ld::Blocks(const twk_ld_settings& s, const twk_block_settings& bs) {
 	return true;
 }
 
+// `tomahawk ldsplit`: every contig of the selection split into K near-independent LD blocks for every K up to ss.max_blocks
+// (twk_hip_ld_split: the banded r2 matrix kept on the GPU, the dynamic programme solved there), one engine call a contig.  The input is
+// loaded exactly as Prune loads it; one GPU; the whole triangle (no -c / -C); the window is required.  Not in the reference.
+bool twk_ld::Split(const twk_ld_settings& s, const twk_split_settings& ss) {
+	ReduceCommand cmd(settings, *mImpl);
+	if (!cmd.begin(s, "A split looks at every record", "Cannot split a part of the pair space: a block sum needs every pair inside the block")) return false;
+	if (!settings.window || settings.l_window <= 0) { std::cerr << stamp("ERROR") << "A split needs a window in bases (-w): it bounds the band of r2 that is kept..." << std::endl; return false; }
+	if (ss.min_size == 0 || ss.min_size > ss.max_size || ss.max_size > 65535 || ss.max_blocks == 0 || ss.max_blocks > 1024) {
+		std::cerr << stamp("ERROR") << "A split needs 1 <= --min-size <= --max-size <= 65535 and 1 <= --max-blocks <= 1024..." << std::endl;
+		return false;
+	}
+	if (ss.blocks > ss.max_blocks) { std::cerr << stamp("ERROR") << "Cannot write a partition of more blocks (-B) than --max-blocks..." << std::endl; return false; }
+	if (cmd.to_stdout()) { std::cerr << stamp("ERROR") << "A split writes PREFIX.costs.tsv and PREFIX.blocks.tsv: -o wants a prefix..." << std::endl; return false; }
+	if (const auto l = cmd.load(); l != cmd.ready) return l == cmd.empty;
+	const uint32_t M = cmd.M, k_max = ss.max_blocks;
+	struct Contig { uint32_t a0, n; uint64_t total; std::vector<uint8_t> feasible; std::vector<uint64_t> cost; std::vector<uint32_t> cuts; };
+	std::vector<Contig> contigs;
+	for (uint32_t a = 0; a < M;) {
+		uint32_t b = a + 1;
+		while (b < M && mImpl->rid[b] == mImpl->rid[a]) ++b;
+		contigs.push_back(Contig{a, b - a, 0, std::vector<uint8_t>(k_max, 0), std::vector<uint64_t>(k_max, 0), std::vector<uint32_t>((size_t)k_max * (k_max + 1), 0)});
+		a = b;
+	}
+	uint64_t pairs = 0, records = 0;
+	double sec = 0;
+	for (Contig& c : contigs) {
+		if ((uint64_t)c.n * ss.max_size >= (1ull << 32)) {
+			std::cerr << stamp("ERROR") << "Cannot split a contig of " << pretty(c.n) << " variants into blocks of up to " << ss.max_size << ": variants x --max-size must stay below 2^32..." << std::endl;
+			return false;
+		}
+		uint64_t np = 0, nr = 0;
+		const double one = cmd.call("twk_hip_ld_split", [&] {
+			return twk_hip_ld_split(cmd.ctx, cmd.mode, &cmd.f, c.a0, c.n, 0, (uint32_t)settings.l_window, ss.min_size, ss.max_size, k_max, &c.total, c.feasible.data(), c.cost.data(), c.cuts.data(), &nr, &np);
+		}, nullptr);
+		if (one < 0) return false;
+		sec += one; pairs += np; records += nr;
+	}
+	mImpl->n_pairs = pairs;
+	mImpl->n_records = records;
+	auto cut = [&](const Contig& c, uint32_t K, uint32_t i) { return c.cuts[(size_t)(K - 1) * (k_max + 1) + i]; };
+	if (ss.blocks)
+		for (const Contig& c : contigs)
+			if (!c.feasible[ss.blocks - 1]) {
+				std::string where;
+				cmd.place(where, c.a0);
+				std::cerr << stamp("ERROR") << "Cannot split the contig of " << where.substr(0, where.find('\t')) << " (" << pretty(c.n) << " variants) into " << ss.blocks << " blocks of " << ss.min_size << " to "
+				          << ss.max_size << " variants..." << std::endl;
+				return false;
+			}
+	std::ofstream out;
+	if (!cmd.open(out, settings.out + ".costs.tsv")) return false;
+	cmd.header(out, "ldsplit");
+	char line[256];
+	snprintf(line, sizeof(line), "##sizes=min_size=%u,max_size=%u,max_blocks=%u\n", ss.min_size, ss.max_size, k_max);
+	out << line << "#contig\tK\tcost\tcost_fraction\tsum_squared_sizes\n";
+	std::string text;
+	uint64_t rows = 0;
+	for (const Contig& c : contigs) {
+		std::string where;
+		cmd.place(where, c.a0);
+		where.resize(where.find('\t'));
+		for (uint32_t K = 1; K <= k_max; ++K) {
+			if (!c.feasible[K - 1]) continue;
+			uint64_t squares = 0;
+			for (uint32_t i = 1; i <= K; ++i) { const uint64_t size = cut(c, K, i) - cut(c, K, i - 1); squares += size * size; }
+			const double cost = (double)c.cost[K - 1];
+			snprintf(line, sizeof(line), "\t%u\t%.17g\t%.17g\t%llu\n", K, cost / 4294967296.0, c.total ? cost / (double)c.total : 0.0, (unsigned long long)squares);
+			text += where; text += line;
+			cmd.spill(out, text);
+			++rows;
+		}
+	}
+	if (!cmd.finish(out, text, "the costs")) return false;
+	out.close();
+	text.clear();
+	if (ss.blocks) {
+		if (!cmd.open(out, settings.out + ".blocks.tsv")) return false;
+		cmd.header(out, "ldsplit");
+		snprintf(line, sizeof(line), "##sizes=min_size=%u,max_size=%u,max_blocks=%u,blocks=%u\n", ss.min_size, ss.max_size, k_max, ss.blocks);
+		out << line << "#contig\tblock\tfirst_pos\tlast_pos\tvariants\n";
+		for (const Contig& c : contigs)
+			for (uint32_t i = 1; i <= ss.blocks; ++i) {
+				const uint32_t a = c.a0 + cut(c, ss.blocks, i - 1), b = c.a0 + cut(c, ss.blocks, i) - 1;
+				cmd.place(text, a);
+				snprintf(line, sizeof(line), "\t%u\t%u\n", mImpl->pos[b] + 1, b - a + 1);
+				// (contig <TAB> first pos came from place(): the block's number goes between them)
+				const size_t tab = text.rfind('\t');
+				text.insert(tab, "\t" + std::to_string(i));
+				text += line;
+				cmd.spill(out, text);
+			}
+		if (!cmd.finish(out, text, "the blocks")) return false;
+		out.close();
+	}
+	std::cerr << stamp("LOG") << "Split: " << pretty(contigs.size()) << " contigs of " << pretty(M) << " variants, " << pretty(rows) << " feasible (contig, K) among K <= " << k_max << ", " << pretty(records)
+	          << " pairs with a value among " << pretty(pairs) << " variant comparisons. " << elapsed_string(sec) << std::endl;
+	cmd.all_done();
+	return true;
+}
+
 // `tomahawk relationship`: the sample-by-sample matrix over the variants of the selection (twk_hip_relationship: transposed, contracted and
 // divided on the GPU), as text on stdout or as a NumPy file or text file with the samples' names next to it.  The input is loaded exactly as
 // Prune loads it; one GPU.  The reference's command of the same name is not reproduced (include/twk_hip.h says why).

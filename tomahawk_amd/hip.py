@@ -272,6 +272,9 @@ def load_library() -> C.CDLL:
                                       p, p, p, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.twk_hip_blocks_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_blocks_stages.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.twk_hip_ld_split.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_uint32, p, p, p, p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.twk_hip_split_last.argtypes = [p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.twk_hip_ld_topk.argtypes = [p, C.c_int, C.POINTER(_Filters), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, p, p,
                                     C.POINTER(C.c_uint64)]
@@ -945,6 +948,40 @@ class HipLd:
         counts, emit, sort = C.c_double(0), C.c_double(0), C.c_double(0)
         self._check(self._lib.twk_hip_blocks_stages(self._ctx, C.byref(counts), C.byref(emit), C.byref(sort)), "twk_hip_blocks_stages")
         return {"walk_ms": ms.value, "band_bytes": b.value, "counts_ms": counts.value, "emit_ms": emit.value, "sort_ms": sort.value}
+
+    def ld_split(self, mode: int, filters: Filters, l_window: int, min_size: int, max_size: int, k_max: int, a0: int = 0,
+                 n: int | None = None, tile_variants: int = 0, out=None):
+        """LD splitting (twk_hip_ld_split): the slice [a0, a0 + n) - one contig - cut into K blocks of min_size .. max_size variants so
+        that the r2 of ld_matrix_band(STAT_R2, fill 0) with the same arguments that crosses a cut is smallest, for every K up to k_max,
+        solved on the device in integers of 2^-32.  filters.minP must be >= 1.  out: (total uint64[1], feasible uint8[k_max],
+        cost uint64[k_max], cuts uint32[k_max * (k_max + 1)]) to be filled in place - a refused call and the rows of an infeasible K leave
+        them as they are; None: fresh zeroed arrays.
+        -> {"total": T, "feasible": uint8[k_max] (entry K - 1), "cost": uint64[k_max] (entry K - 1; 0 where infeasible),
+        "cuts": [uint32[K + 1] for every feasible K, ascending], "K": the feasible K, "n_records", "n_pairs"}."""
+        n = self.n_variants - a0 if n is None else n
+        rows = int(k_max) if 1 <= int(k_max) <= 1024 else 0          # (outside 1 .. 1024 the call is refused and writes nothing)
+        if out is None:
+            out = (np.zeros(1, dtype=np.uint64), np.zeros(rows, dtype=np.uint8), np.zeros(rows, dtype=np.uint64),
+                   np.zeros(rows * (rows + 1), dtype=np.uint32))
+        total, feasible, cost, cuts = out
+        assert total.dtype == np.uint64 and feasible.dtype == np.uint8 and cost.dtype == np.uint64 and cuts.dtype == np.uint32
+        assert len(total) >= 1 and len(feasible) >= rows and len(cost) >= rows and len(cuts) >= rows * (rows + 1)
+        nrec, npairs = C.c_uint64(0), C.c_uint64(0)
+        f = filters._c()
+        self._check(self._lib.twk_hip_ld_split(self._ctx, mode, C.byref(f), a0, n, tile_variants, l_window, min_size, max_size, k_max,
+                                               total.ctypes.data, feasible.ctypes.data, cost.ctypes.data, cuts.ctypes.data,
+                                               C.byref(nrec), C.byref(npairs)), "twk_hip_ld_split")
+        ks = [K for K in range(1, rows + 1) if feasible[K - 1]]
+        return {"total": int(total[0]), "feasible": feasible[:rows].copy(), "cost": cost[:rows].copy(),
+                "cuts": [cuts[(K - 1) * (rows + 1):(K - 1) * (rows + 1) + K + 1].copy() for K in ks], "K": ks,
+                "n_records": nrec.value, "n_pairs": npairs.value}
+
+    def split_last(self) -> dict:
+        """Of the last ld_split call (twk_hip_split_last): the device time of the band's launches, of row prefixes + block sums, of the
+        layers and of the backtrack, and the device memory held."""
+        band, sums, layers, back, b = C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0), C.c_uint64(0)
+        self._check(self._lib.twk_hip_split_last(self._ctx, C.byref(band), C.byref(sums), C.byref(layers), C.byref(back), C.byref(b)), "twk_hip_split_last")
+        return {"band_ms": band.value, "sums_ms": sums.value, "layers_ms": layers.value, "backtrack_ms": back.value, "bytes": b.value}
 
     def ld_topk(self, mode: int, filters: Filters, k: int, stat: int = STAT_R2, a0: int = 0, nA: int | None = None, b0: int = 0,
                 nB: int | None = None, triangle: bool = True, part: int = 0, n_parts: int = 1, tile_variants: int = 0, window: int = 0,
