@@ -83,11 +83,13 @@ def test_count_kernels_use_no_scratch_memory():
 def test_buffer_owners_free_what_they_hold_once():
     """`make buffers-check`: the engine's buffer types (csrc/hip/twk_buffers.h) with the allocator stubbed, built with plain g++ -
     growing, parking in the graveyard and flushing it, freeing at once, out of memory with and without something to reclaim,
-    groups that share a capacity, moves, holders assigned over and destroyed.  The stub fails the run on a release of a pointer
-    that is not live, the harness on a pointer still live when a case ends."""
+    groups that share a capacity, moves, holders assigned over and destroyed; and a call's memory (CallMemory): every take
+    released once with the owner, a failure at each of four takes with either verdict, bytes(), a blocks-like call's allocation
+    count with its scratch taken again, a split-like call's bytes() against the closed form.  The stub fails the run on a release
+    of a pointer that is not live, the harness on a pointer still live when a case ends."""
     r = subprocess.run(["make", "-C", ROOT, "buffers-check"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
-    assert "7 cases, 0 bad" in r.stdout
+    assert "20 cases, 0 bad" in r.stdout          # the 7 of the buffer types and 13 of the call's memory
 
 
 def test_count_tables_keep_their_invariants_and_their_recorded_order():

@@ -19,6 +19,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
 #include "ld_matrix_index.h"
 
 namespace twk {
@@ -48,6 +49,28 @@ inline bool bm_layout(uint32_t n, Pos pos, Rid rid, uint32_t w, uint32_t* first,
 		at += hi - lo;
 	}
 	row_ptr[n] = at;
+	return true;
+}
+
+// ... and everything a call needs of it, on the host: first and row_ptr as the caller gets them, the rows as the device reads them
+// (rows[u] == {ptr[u], first[u], ptr[u + 1] - ptr[u]}), the number of slots (ptr[n]) and the longest row.  Filled once, by bm_band_layout.
+struct BandLayout {
+	std::vector<uint32_t> first;     // [n]
+	std::vector<uint64_t> ptr;       // [n + 1]
+	std::vector<BandRow> rows;       // [n]
+	size_t cells = 0;
+	uint32_t widest = 0;
+};
+template <class Pos, class Rid>
+inline bool bm_band_layout(uint32_t n, Pos pos, Rid rid, uint32_t w, BandLayout& b) {
+	b.first.assign(n, 0); b.ptr.assign((size_t)n + 1, 0); b.rows.resize(n);
+	b.cells = 0; b.widest = 0;
+	if (!bm_layout(n, pos, rid, w, b.first.data(), b.ptr.data())) return false;
+	for (uint32_t u = 0; u < n; ++u) {
+		b.rows[u] = BandRow{b.ptr[u], b.first[u], (uint32_t)(b.ptr[u + 1] - b.ptr[u])};      // (a row holds at most n columns)
+		if (b.rows[u].len > b.widest) b.widest = b.rows[u].len;
+	}
+	b.cells = (size_t)b.ptr[n];
 	return true;
 }
 

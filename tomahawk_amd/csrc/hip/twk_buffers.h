@@ -101,4 +101,45 @@ typename Ops::error reserve_together(size_t need, size_t want, Graveyard<Ops>* p
 template <class... B>
 size_t shared_capacity(const B&... b) { return std::min({b.capacity()...}); }
 
+// The device buffers that live exactly as long as one call: each request is an allocation of its own (Buffer::reserve, freed at once -
+// no graveyard: nothing reads a buffer that has not been handed out yet), all of them are released together when the owner dies, and a
+// request that fails leaves the earlier ones held until then.  The owner's place decides when that is: a member of the object whose
+// destructor waits for the device is released behind that wait.
+template <class Ops>
+class CallMemory {
+public:
+	CallMemory() = default;
+	CallMemory(const CallMemory&) = delete;
+	CallMemory& operator=(const CallMemory&) = delete;
+
+	// `items` of T, or null with the allocator's verdict in *e.  (No item: null and ok, as reserve(0, 0) - nothing is allocated.)
+	template <class T>
+	T* take(size_t items, typename Ops::error* e) {
+		held.emplace_back();
+		return grow<T>(held.back(), items, e);
+	}
+	// Room for `items` in the buffer take() returned as `p`: it stays where it is while it has the room and is replaced - freed, then
+	// allocated - when not (a scratch buffer that a later step of the call needs larger).  Contents are not kept; after a failure that
+	// buffer is empty.
+	template <class T>
+	T* retake(T* p, size_t items, typename Ops::error* e) {
+		for (Buffer<char, Ops>& b : held)
+			if (p && b.get() == reinterpret_cast<char*>(p)) return grow<T>(b, items, e);
+		return take<T>(items, e);
+	}
+	// What the requests that succeeded asked for, in bytes.
+	size_t bytes() const { return total; }
+
+private:
+	template <class T>
+	T* grow(Buffer<char, Ops>& b, size_t items, typename Ops::error* e) {
+		total -= b.capacity();
+		*e = b.reserve(items * sizeof(T), items * sizeof(T), nullptr);
+		total += b.capacity();
+		return *e == Ops::ok ? reinterpret_cast<T*>(b.get()) : nullptr;
+	}
+	std::vector<Buffer<char, Ops>> held;      // (each as many bytes as its request)
+	size_t total = 0;
+};
+
 }  // namespace twk

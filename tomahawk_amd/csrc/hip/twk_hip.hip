@@ -155,6 +155,13 @@ struct ReduceState {
 	struct { PruneMap bits; MatrixMap matrix; DecayMap decay; AggMap agg; AnnotMap annot; BandMap band; TopkMap topk; CiMap ci; } map{};      // where the running kind's launches put their results (prune and clump: bits)
 	uint64_t work = 0;                            // what the call's launches used up of the room of the kind's accumulators (launch_reduce holds it to the kind's limit)
 };
+// What twk_hip_*_last tells of an entry point's last call: the stages it timed on its stream (StageMarks; a stage it did not reach is 0)
+// and the device memory it reports.  One per entry point, not per Reduce: that says which epilogue a launch takes, and calls share those.
+struct CallReport { double stage_ms[4] = {0, 0, 0, 0}; uint64_t bytes = 0; };
+struct LastCalls {
+	CallReport prune, clump, matrix, bandmat, topk, blocks, split, relate;
+	int32_t relate_planes = 0;      // planes a sample of the last relationship call
+};
 // What a slot's current launch is.  Every launch begins with a fresh one (begin_launch); after that a field is written only by the
 // function that decides it.  (Buffers, capacities, events and counters outlive a launch: they are the Slot's.)
 struct Launch {
@@ -353,12 +360,13 @@ struct twk_hip_ctx {
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
 	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
-	double split_stage_ms[4] = {0, 0, 0, 0};    // of the last twk_hip_ld_split call: the band's launches, prefixes + block sums, the layers, the backtrack (twk_hip_split_last)
-	uint64_t split_bytes = 0;                   // ... and the device memory it held
-	double blocks_stage_ms[3] = {0, 0, 0};    // of the last twk_hip_ld_blocks call: prefix counts + candidate counts + scan, the emitting pass, the sort (twk_hip_blocks_stages)
-	struct { double ms = 0; uint64_t bytes = 0; } reduce_last[N_REDUCE];         // of the last call of each kind: the walk or the copy, the bitmap or the matrix
-	                                                                             // (twk_hip_prune_last, twk_hip_clump_last, twk_hip_matrix_last, twk_hip_bandmat_last, twk_hip_topk_last)
-	DevBuf<unsigned long long> d_counts;                                         // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
+	// What the last call of each public entry point with a twk_hip_*_last took: its own report, whichever epilogue its launches ran
+	// (ld_split's run bandmat's).  stage_ms - prune, clump: [0] the walk; matrix, bandmat: [0] the copy; topk: [0] copy and unpack;
+	// blocks: prefix counts + candidate counts + scan, the emitting pass, the sort, the walk; split: the band's launches, prefixes +
+	// block sums, the layers, the backtrack; relationship: [0] the transposition.  bytes: the bitmap, the matrix, the band, the lists,
+	// the two bounds' bands, everything the split held, the samples' planes.
+	LastCalls last;
+	DevBuf<unsigned long long> d_counts;                                        // [3] of the call: [0] edges or records; prune [1] kept; clump [1] clumps [2] members
 	// score: sums of r2 per variant (ld_score.hip.h)
 	DevBuf<double> d_score_sum; DevBuf<unsigned long long> d_score_n;            // [M] accumulators, variant ids in file order
 	// prune and clump: what their walks over the call's adjacency bitmap read and write (ld_prune.hip.h, ld_clump.hip.h; the bitmap is the ReduceCall's)
@@ -369,8 +377,7 @@ struct twk_hip_ctx {
 	DevBuf<unsigned long long> d_decay;                                          // [3][n_bins] accumulators: acc_int, acc_frac, acc_n
 	// aggregate: the two bins of every variant, packed (ld_aggregate.hip.h; the cells' accumulators are the ReduceCall's)
 	DevBuf<uint32_t> d_agg_key;                                                  // [M]
-	// relationship: of the last call (twk_hip_relationship_last) - its planes, row lists and outputs live for the length of the call
-	struct { int32_t planes = 0; double transpose_ms = 0; uint64_t plane_bytes = 0; } relate_last;
+	// (relationship: its planes, row lists and outputs live for the length of the call)
 	char err[512] = {0};
 };
 
@@ -386,6 +393,27 @@ struct Events {                    // the events of one call, destroyed on every
 		return hipSuccess;
 	}
 	hipEvent_t operator[](size_t k) const { return v[k]; }
+};
+// The stages of one call on its stream: mark(st) records the next event where stage st of the call's report begins - or, NO_STAGE, where
+// the stage in front merely ends - and once the stream has been waited for, write() puts the distance from every mark to the next one
+// into the stage it begins.  A stage that no mark began keeps what the report held: 0 from the call's start.
+struct StageMarks {
+	static constexpr int NO_STAGE = -1;
+	Events ev; std::vector<int> begins;      // begins[k]: the stage from mark k to mark k + 1
+	hipError_t mark(int stage, hipStream_t s) {
+		// (events are made eight at a time, in front of the call's first mark: making one between two marks would count as the stage's
+		// time where the device has caught up with the host, as it has in split's layers; no call here has more than seven marks)
+		hipError_t e = begins.size() < ev.v.size() ? hipSuccess : ev.add(8);
+		if (e == hipSuccess) e = hipEventRecord(ev[begins.size()], s);
+		if (e == hipSuccess) begins.push_back(stage);
+		return e;
+	}
+	void write(CallReport& r) const {
+		for (size_t k = 0; k + 1 < begins.size(); ++k) {
+			float ms = 0;
+			if (begins[k] != NO_STAGE && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess) r.stage_ms[begins[k]] = ms;
+		}
+	}
 };
 
 #define HIPCHK(ctx, call)                                                                         \
@@ -2823,29 +2851,51 @@ int twk_hip_ld_region(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 
 extern "C++" {      // (member templates)
 namespace {
-// Device memory that lives as long as one call: reserved, or the call fails with `what` - a format of `lead` (a count, or a name), the bytes
-// wanted and the runtime's reason - as TWK_HIP_E_NOMEM when the device cannot give it.
-template <class T, class Lead>
-int hold_for_call(twk_hip_ctx* c, DevBuf<T>& b, size_t items, const char* what, Lead lead) {
-	const hipError_t e = b.reserve(items, items, nullptr);
-	if (e == hipSuccess) return TWK_HIP_OK;
-	(void)hipGetLastError();
-	snprintf(c->err, sizeof(c->err), what, lead, items * sizeof(T), hipGetErrorString(e));
-	return e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+// The device memory of one call (CallMemory: a request an allocation, all released with the owner): hold() gives `items` of T, or the call
+// has failed with `what` - a format of `lead` (a count, or a name), the bytes wanted and the runtime's reason - as TWK_HIP_E_NOMEM when
+// the device cannot give it.  From the first failure on hold() gives null and asks for nothing, so an entry point holds what it needs
+// line by line and looks at `failed` once, before it uses any of it.
+struct HeldMemory : CallMemory<HipMemOps> {
+	twk_hip_ctx* c; int failed = TWK_HIP_OK;
+	explicit HeldMemory(twk_hip_ctx* c_) : c(c_) {}
+	// again: what an earlier hold gave, now needed with room for `items` (CallMemory::retake; null: a buffer of its own)
+	template <class T, class Lead>
+	T* hold(size_t items, const char* what, Lead lead, T* again = nullptr) {
+		if (failed) return nullptr;
+		hipError_t e = hipSuccess;
+		T* const p = retake(again, items, &e);
+		if (e == hipSuccess) return p;
+		(void)hipGetLastError();
+		snprintf(c->err, sizeof(c->err), what, lead, items * sizeof(T), hipGetErrorString(e));
+		failed = e == hipErrorOutOfMemory ? TWK_HIP_E_NOMEM : TWK_HIP_E_DEVICE;
+		return nullptr;
+	}
+};
+
+// "Preset n floats to this bit pattern": any pattern, NaNs included - never through a float register.
+hipError_t preset_floats(float* p, float fill, size_t n, hipStream_t s) {
+	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));
+	return hipMemsetD32Async((hipDeviceptr_t)p, (int)fill_bits, n, s);
 }
 
 // One call of twk_hip_ld_score, _prune, _clump, _matrix, _decay or _aggregate: the region call's planner and launch pipeline with the kind's epilogue in place of
 // math, Fisher, sort and delivery (launch_reduce).  Constructed at the top of the entry point, which returns `bad` if the shared checks found
 // something; whichever way the entry point then leaves, the destructor puts the context back: no kind, no map, nothing in flight, the
-// graveyard flushed - and the buffer that lived for the call, a member, is released behind it.
+// graveyard flushed - and the memory that lived for the call, a member, is released behind it.
 struct ReduceCall {
-	twk_hip_ctx* c; const twk_hip_filters* f; const Reduce kind;
+	twk_hip_ctx* c; const twk_hip_filters* f;
+	const Reduce kind;             // the epilogue the call's launches take ...
+	CallReport* const report;      // ... and the entry point's report the call writes (its own dummy: the entry point has no twk_hip_*_last)
+	CallReport unreported;
 	int bad;
-	// what lives as long as the call (hold): the bitmap, the n x n matrix, the aggregate's cells, the annotations and their sums, the band and its map, the top-k lists.  Freed behind the destructor's body, which waits for the device.
-	DevBuf<unsigned long long> d_adj, d_agg, d_annot_acc, d_topk; DevBuf<float> d_matrix, d_band; DevBuf<double> d_annot; DevBuf<BandRow> d_band_rows; DevBuf<uint8_t> d_ci_lo, d_ci_hi;
+	// What lives as long as the call - the bitmap, the n x n matrix, the aggregate's cells, the band and its map, the top-k lists, a later
+	// step's arrays: gigabytes that a record run behind this call may need, so they go back when the call ends, whichever way.  Members:
+	// released behind the destructor's body, which waits for the device.
+	HeldMemory mem;
+	StageMarks marks;
 	// own_args_ok: the entry point's own pointers and numbers; [a0, a0 + n): the rows of the call (a slice call's variants)
-	ReduceCall(twk_hip_ctx* c_, Reduce kind_, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
-		: c(c_), f(f_), kind(kind_), bad(check(own_args_ok, mode, a0, n)) {}
+	ReduceCall(twk_hip_ctx* c_, Reduce kind_, CallReport LastCalls::* which, const twk_hip_filters* f_, bool own_args_ok, int mode, uint32_t a0, uint32_t n)
+		: c(c_), f(f_), kind(kind_), report(c_ && which ? &(c_->last.*which) : &unreported), bad(check(own_args_ok, mode, a0, n)), mem(c_) {}
 	ReduceCall(const ReduceCall&) = delete;
 	int check(bool own_args_ok, int mode, uint32_t a0, uint32_t n) {
 		if (!c || !f || !own_args_ok || !(f->minP >= 1.0)) return TWK_HIP_E_INVALID;
@@ -2860,29 +2910,30 @@ struct ReduceCall {
 		(void)hipDeviceSynchronize();
 		flush_graveyard(c);                 // buffers outgrown during the call: nothing is in flight any more
 	}
-	// The buffer that lives as long as the call - gigabytes that a record run behind this call may need, so it goes back when the call ends,
-	// whichever way - or the call fails with `what`: a format of the variant count, the bytes wanted and the runtime's reason.  With it the
-	// call's three counters, zeroed.
-	template <class T>
-	int hold(DevBuf<T>& b, size_t items, const char* what, uint32_t n) {
-		const int rc = hold_for_call(c, b, items, what, n); if (rc) return rc;
+	// Memory of the call (HeldMemory::hold): null once a hold has failed - mem.failed is the call's result then.
+	template <class T, class Lead>
+	T* hold(size_t items, const char* what, Lead lead) { return mem.hold<T>(items, what, lead); }
+	// The call's three counters, zeroed.
+	int zero_counts() {
 		HIPCHK(c, c->d_counts.reserve(3, 3, nullptr));
 		HIPCHK(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
 		return TWK_HIP_OK;
 	}
 	// prune, clump: the adjacency bitmap of the slice [a0, a0 + n), n * ceil(n / 64) words whatever the window (ld_prune.hip.h), held, cleared
-	// and armed
+	// and armed.  Where it lies is what the launches were told: c->reduce.map.bits.adj, for the rest of the call.
 	int bitmap(uint32_t a0, uint32_t n, const char* what) {
 		const uint32_t stride = (n + 63) / 64;
 		const size_t words = (size_t)n * stride;
-		const int rc = hold(d_adj, words, what, n); if (rc) return rc;
-		HIPCHK(c, hipMemsetAsync(d_adj, 0, words * sizeof(unsigned long long), c->s_compute));
-		c->reduce.map.bits = PruneMap{d_adj, c->d_counts, a0, n, stride};
+		unsigned long long* const adj = hold<unsigned long long>(words, what, n);
+		if (mem.failed) return mem.failed;
+		const int rc = zero_counts(); if (rc) return rc;
+		HIPCHK(c, hipMemsetAsync(adj, 0, words * sizeof(unsigned long long), c->s_compute));
+		c->reduce.map.bits = PruneMap{adj, c->d_counts, a0, n, stride};
 		arm(words * sizeof(unsigned long long));
 		return TWK_HIP_OK;
 	}
-	// From here on the call's launches take the kind's epilogue.  bytes: what twk_hip_*_last reports of this call.
-	void arm(uint64_t bytes) { c->reduce_last[(int)kind].ms = 0; c->reduce_last[(int)kind].bytes = bytes; c->reduce.work = 0; c->reduce.kind = kind; }
+	// From here on the call's launches take the kind's epilogue, and its report is this call's.  bytes: what twk_hip_*_last reports of it.
+	void arm(uint64_t bytes) { *report = CallReport(); report->bytes = bytes; c->reduce.work = 0; c->reduce.kind = kind; }
 	// The region call's geometry.  (The r2 band and the carrier-list zones exist to avoid looking at pairs: never for a reduce call.)
 	int dispatch(int mode, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts, uint32_t tile_variants,
 	             int32_t window, uint32_t l_window, uint64_t* n_pairs) {
@@ -2902,30 +2953,44 @@ struct ReduceCall {
 		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
 		return TWK_HIP_OK;
 	}
-	// What follows the call's last launch on its stream: `timed` between two events - their distance is the call's `ms` of twk_hip_*_last -
-	// then `rest`, then one wait for the stream.  Both enqueue and return the runtime's verdict.
+	// ... of `items` items of `words` words each at `d`, a slab of items at a time: each(at, m, w) behind each wait - items [at, at + m), their words at w.
+	template <class Each>
+	int download_slabs(const char* what, const unsigned long long* d, size_t items, size_t words, size_t slab, Each&& each) {
+		std::vector<unsigned long long> w(slab * words);
+		for (size_t at = 0; at < items; at += slab) {
+			const size_t m = std::min(slab, items - at);
+			const int rc = download(what, [&] { return hipMemcpyAsync(w.data(), d + at * words, m * words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute); });
+			if (rc) return rc;
+			each(at, m, (const unsigned long long*)w.data());
+		}
+		return TWK_HIP_OK;
+	}
+	// A stage of the call's report begins here on its stream (StageMarks::mark).
+	hipError_t mark(int stage) { return marks.mark(stage, c->s_compute); }
+	// What follows the call's last launch on its stream: `timed` between two marks - stage `stage` of the call's report, the `ms` of
+	// twk_hip_*_last - then `rest`, then one wait for the stream, behind which every stage marked so far is written.  Both enqueue and
+	// return the runtime's verdict.
 	template <class Timed, class Rest>
-	int tail(const char* what, Timed&& timed, Rest&& rest) {
-		Events w;
-		hipError_t e = w.add(2);
-		if (e == hipSuccess) e = hipEventRecord(w[0], c->s_compute);
+	int tail(const char* what, Timed&& timed, Rest&& rest, int stage = 0) {
+		hipError_t e = mark(stage);
 		if (e == hipSuccess) e = timed();
-		if (e == hipSuccess) e = hipEventRecord(w[1], c->s_compute);
+		if (e == hipSuccess) e = mark(StageMarks::NO_STAGE);
 		if (e == hipSuccess) e = rest();
 		if (e == hipSuccess) e = hipStreamSynchronize(c->s_compute);
 		if (e != hipSuccess) { snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e)); return TWK_HIP_E_DEVICE; }
-		float ms = 0;
-		if (hipEventElapsedTime(&ms, w[0], w[1]) == hipSuccess) c->reduce_last[(int)kind].ms = ms;
+		marks.write(*report);
 		return TWK_HIP_OK;
 	}
 };
 
 bool valid_stat(int32_t stat) { return stat == TWK_HIP_STAT_R || stat == TWK_HIP_STAT_R2 || stat == TWK_HIP_STAT_D || stat == TWK_HIP_STAT_DPRIME; }
 
-int last_of(const twk_hip_ctx* c, Reduce kind, double* ms, uint64_t* bytes) {
+// twk_hip_*_last: stage k of the entry point's report to ms[k], where the caller asks for it.
+int last_of(const twk_hip_ctx* c, CallReport LastCalls::* which, std::initializer_list<double*> ms, uint64_t* bytes) {
 	if (!c) return TWK_HIP_E_INVALID;
-	if (ms) *ms = c->reduce_last[(int)kind].ms;
-	if (bytes) *bytes = c->reduce_last[(int)kind].bytes;
+	const double* stage = (c->last.*which).stage_ms;
+	for (double* m : ms) { if (m) *m = *stage; ++stage; }
+	if (bytes) *bytes = (c->last.*which).bytes;
 	return TWK_HIP_OK;
 }
 
@@ -2936,7 +3001,7 @@ int last_of(const twk_hip_ctx* c, Reduce kind, double* ms, uint64_t* bytes) {
 int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
                      uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
                      uint64_t* n_partners, double* sum_r2, uint64_t* n_pairs) {
-	ReduceCall call(c, Reduce::score, f, n_partners && sum_r2, mode, a0, nA);
+	ReduceCall call(c, Reduce::score, nullptr, f, n_partners && sum_r2, mode, a0, nA);
 	if (call.bad) return call.bad;
 	const size_t M = c->M;
 	HIPCHK(c, c->d_score_sum.reserve(M, M, nullptr));
@@ -2955,7 +3020,7 @@ int twk_hip_ld_score(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 // LD pruning: the greedy walk over the bitmap the launches filled.
 int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
                      int32_t window, uint32_t l_window, uint8_t* keep, uint64_t* n_kept, uint64_t* n_edges, uint64_t* n_pairs) {
-	ReduceCall call(c, Reduce::prune, f, keep != nullptr, mode, a0, n);
+	ReduceCall call(c, Reduce::prune, &LastCalls::prune, f, keep != nullptr, mode, a0, n);
 	if (call.bad) return call.bad;
 	const size_t M = c->M;
 	const uint32_t stride = (n + 63) / 64;
@@ -2968,7 +3033,7 @@ int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
 	unsigned long long counts[2] = {0, 0};
 	rc = call.tail("prune walk", [&] {
-		hipLaunchKernelGGL(in_lds ? k_ld_prune_walk<true> : k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)call.d_adj,
+		hipLaunchKernelGGL(in_lds ? k_ld_prune_walk<true> : k_ld_prune_walk<false>, dim3(1), dim3(WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->reduce.map.bits.adj,
 		                   a0, n, stride, in_lds ? nullptr : c->d_walk.get(), c->d_prune_keep.get(), c->d_counts + 1);
 		return hipGetLastError();
 	}, [&] {
@@ -2981,13 +3046,13 @@ int twk_hip_ld_prune(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	return TWK_HIP_OK;
 }
 
-int twk_hip_prune_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) { return last_of(c, Reduce::prune, walk_ms, bitmap_bytes); }
+int twk_hip_prune_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) { return last_of(c, &LastCalls::prune, {walk_ms}, bitmap_bytes); }
 
 // LD clumping: the walk in P order over the bitmap the launches filled from both ends of a pair.
 int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants,
                      int32_t window, uint32_t l_window, const double* p, double p1, double p2,
                      uint32_t* index_of, uint64_t* n_clumps, uint64_t* n_members, uint64_t* n_edges, uint64_t* n_pairs) {
-	ReduceCall call(c, Reduce::clump, f, p && index_of && p1 >= 0.0 && p1 <= p2 && p2 <= 1.0, mode, a0, n);      // (a NaN fails every comparison)
+	ReduceCall call(c, Reduce::clump, &LastCalls::clump, f, p && index_of && p1 >= 0.0 && p1 <= p2 && p2 <= 1.0, mode, a0, n);      // (a NaN fails every comparison)
 	if (call.bad) return call.bad;
 	const size_t M = c->M;
 	const uint32_t stride = (n + 63) / 64;
@@ -3018,7 +3083,7 @@ int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
 	unsigned long long counts[3] = {0, 0, 0};
 	rc = call.tail("clump walk", [&] {
-		hipLaunchKernelGGL(in_lds ? k_ld_clump_walk<true> : k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)call.d_adj,
+		hipLaunchKernelGGL(in_lds ? k_ld_clump_walk<true> : k_ld_clump_walk<false>, dim3(1), dim3(CLUMP_WALK_THREADS), 0, c->s_compute, (const unsigned long long*)c->reduce.map.bits.adj,
 		                   a0, n, stride, (const uint32_t*)c->d_clump_order, m, c->d_walk.get(), c->d_clump_index.get(), c->d_counts + 1);
 		return hipGetLastError();
 	}, [&] {
@@ -3032,46 +3097,101 @@ int twk_hip_ld_clump(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 	return TWK_HIP_OK;
 }
 
-int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) { return last_of(c, Reduce::clump, walk_ms, bitmap_bytes); }
+int twk_hip_clump_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* bitmap_bytes) { return last_of(c, &LastCalls::clump, {walk_ms}, bitmap_bytes); }
 
 // LD matrix: the matrix is preset to the fill in front of the launches, gets its diagonal behind the last of them and leaves in one 2-D
 // copy that honours the caller's row pitch.
 int twk_hip_ld_matrix(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
                       int32_t stat, float fill, float* out, uint64_t ld, uint64_t* n_records, uint64_t* n_pairs) {
-	ReduceCall call(c, Reduce::matrix, f, out && valid_stat(stat), mode, a0, n);
+	ReduceCall call(c, Reduce::matrix, &LastCalls::matrix, f, out && valid_stat(stat), mode, a0, n);
 	if (call.bad) return call.bad;
 	if (ld < n) return TWK_HIP_E_INVALID;
 	const size_t cells = (size_t)n * n;
 	// the dense matrix: n * n floats, whatever the window
-	int rc = call.hold(call.d_matrix, cells, "the LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
-	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)call.d_matrix.get(), (int)fill_bits, cells, c->s_compute));
-	c->reduce.map.matrix = MatrixMap{call.d_matrix, c->d_counts, a0, n, stat};
+	float* const d_matrix = call.hold<float>(cells, "the LD matrix of %u variants needs %zu bytes of device memory: %s", n);
+	if (call.mem.failed) return call.mem.failed;
+	int rc = call.zero_counts(); if (rc) return rc;
+	HIPCHK(c, preset_floats(d_matrix, fill, cells, c->s_compute));
+	c->reduce.map.matrix = MatrixMap{d_matrix, c->d_counts, a0, n, stat};
 	call.arm(cells * sizeof(float));
 	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
 	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
-		hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, call.d_matrix.get(), n, 1.0f);
+		hipLaunchKernelGGL(k_ld_matrix_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, d_matrix, n, 1.0f);
 		HIPCHK(c, hipGetLastError());
 	}
 	unsigned long long count = 0;
 	rc = call.tail("LD matrix", [&] {
-		return hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), call.d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
+		return hipMemcpy2DAsync(out, (size_t)ld * sizeof(float), d_matrix, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, c->s_compute);
 	}, [&] { return hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute); });
 	if (rc) return rc;
 	if (n_records) *n_records = count;
 	return TWK_HIP_OK;
 }
 
-int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) { return last_of(c, Reduce::matrix, copy_ms, matrix_bytes); }
+int twk_hip_matrix_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* matrix_bytes) { return last_of(c, &LastCalls::matrix, {copy_ms}, matrix_bytes); }
 
-// Banded LD matrix: the band's layout of the slice [a0, a0 + n) from the uploaded metadata (ld_bandmat_index.h), on the host.
+// The banded kinds (banded matrix, D' bounds, haplotype blocks, LD splitting): the band's layout of the slice [a0, a0 + n) from the uploaded
+// metadata (ld_bandmat_index.h), on the host, and what the kinds do with it.
 extern "C++" {
 namespace {
-int bandmat_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, uint32_t* first, uint64_t* row_ptr) {
+// (the caller has checked [a0, a0 + n) against M)
+int band_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, BandLayout& b) {
+	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
 	const twk_hip_variant_meta* meta = c->h_meta.data() + a0;
-	if (bm_layout(n, [&](uint32_t k) { return meta[k].pos; }, [&](uint32_t k) { return meta[k].rid; }, l_window, first, row_ptr)) return TWK_HIP_OK;
+	if (bm_band_layout(n, [&](uint32_t k) { return meta[k].pos; }, [&](uint32_t k) { return meta[k].rid; }, l_window, b)) return TWK_HIP_OK;
 	snprintf(c->err, sizeof(c->err), "banded LD matrix: the variants [%u, %u) are not sorted by (contig, position): a row's window is then no contiguous band", a0, a0 + n);
 	return TWK_HIP_E_INVALID;
+}
+// first[n] and row_ptr[n + 1] as the caller of an entry point gets them.
+void give_layout(const BandLayout& b, uint32_t* first, uint64_t* row_ptr) {
+	memcpy(first, b.first.data(), b.first.size() * sizeof(uint32_t));
+	memcpy(row_ptr, b.ptr.data(), b.ptr.size() * sizeof(uint64_t));
+}
+// The band map on the device, a BandRow per variant: held by the call and uploaded.
+int band_rows(ReduceCall& call, const BandLayout& b, const BandRow** d_rows) {
+	twk_hip_ctx* c = call.c;
+	BandRow* const rows = call.hold<BandRow>(b.rows.size(), "the band map of %u variants needs %zu bytes of device memory: %s", (uint32_t)b.rows.size());
+	if (call.mem.failed) return call.mem.failed;
+	// (from pageable memory: the copy has left the layout's rows when it returns; they live to the end of the call anyway)
+	HIPCHK(c, hipMemcpyAsync(rows, b.rows.data(), b.rows.size() * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
+	*d_rows = rows;
+	return TWK_HIP_OK;
+}
+// The band of the slice on the device, row_ptr[n] floats and the band map: preset to the fill in front of the launches, its diagonal behind
+// the last of them.  Where it lies is what the launches were told: c->reduce.map.band, for the rest of the call.
+int band_fill(ReduceCall& call, int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window, int32_t stat, float fill,
+              const BandLayout& b, uint64_t* n_pairs) {
+	twk_hip_ctx* c = call.c;
+	BandMap& d = c->reduce.map.band;
+	d = BandMap{call.hold<float>(b.cells, "the banded LD matrix of %u variants needs %zu bytes of device memory: %s", n), nullptr, nullptr, a0, n, stat};
+	if (call.mem.failed) return call.mem.failed;
+	int rc = call.zero_counts(); if (rc) return rc;
+	d.n_records = c->d_counts;
+	HIPCHK(c, preset_floats(d.values, fill, b.cells, c->s_compute));
+	rc = band_rows(call, b, &d.rows); if (rc) return rc;
+	call.arm(b.cells * sizeof(float));
+	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
+	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
+		hipLaunchKernelGGL(k_ld_bandmat_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, d.values, d.rows, n, 1.0f);
+		HIPCHK(c, hipGetLastError());
+	}
+	return TWK_HIP_OK;
+}
+// The D' bounds of the slice on the device, a byte a slot each, and the band map: the preset 255, the launches.  Where they lie:
+// c->reduce.map.ci, for the rest of the call.
+int ci_band_fill(ReduceCall& call, int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window, const BandLayout& b, uint64_t* n_pairs) {
+	twk_hip_ctx* c = call.c;
+	CiMap& d = c->reduce.map.ci;
+	d = CiMap{nullptr, nullptr, nullptr, a0, n};
+	d.hi = call.hold<uint8_t>(b.cells, "the upper D' bounds of %u variants' band need %zu bytes of device memory: %s", n);
+	d.lo = call.hold<uint8_t>(b.cells, "the lower D' bounds of %u variants' band need %zu bytes of device memory: %s", n);
+	if (call.mem.failed) return call.mem.failed;
+	int rc = call.zero_counts(); if (rc) return rc;
+	HIPCHK(c, hipMemsetAsync(d.lo, BC_NONE, b.cells, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d.hi, BC_NONE, b.cells, c->s_compute));
+	rc = band_rows(call, b, &d.rows); if (rc) return rc;
+	call.arm(b.cells * 2);
+	return call.dispatch(mode, a0, n, tile_variants, (int32_t)TWK_HIP_OPT_WINDOW, l_window, n_pairs);
 }
 }  // namespace
 }  // extern "C++"
@@ -3079,121 +3199,62 @@ int bandmat_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, u
 int twk_hip_bandmat_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, uint32_t* first, uint64_t* row_ptr) {
 	if (!c || !first || !row_ptr) return TWK_HIP_E_INVALID;
 	if (!c->raw) return TWK_HIP_E_STATE;
-	if (n == 0 || (uint64_t)a0 + n > c->M || c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
-	return bandmat_layout(c, a0, n, l_window, first, row_ptr);
-}
-
-// The band of the slice on the device (call.d_band, call.d_band_rows): preset to the fill in front of the launches, its diagonal behind the
-// last of them.  h_first, h_ptr: bandmat_layout's.
-extern "C++" {
-namespace {
-int band_fill(ReduceCall& call, int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window, int32_t stat, float fill,
-              const std::vector<uint32_t>& h_first, const std::vector<uint64_t>& h_ptr, uint64_t* n_pairs) {
-	twk_hip_ctx* c = call.c;
-	const size_t cells = (size_t)h_ptr[n];
-	std::vector<BandRow> rows(n);
-	for (uint32_t u = 0; u < n; ++u) rows[u] = BandRow{h_ptr[u], h_first[u], (uint32_t)(h_ptr[u + 1] - h_ptr[u])};
-	// the band: row_ptr[n] floats, and a BandRow per variant
-	int rc = hold_for_call(c, call.d_band_rows, (size_t)n, "the band map of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	rc = call.hold(call.d_band, cells, "the banded LD matrix of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	uint32_t fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));              // any pattern, NaNs included: never through a float register
-	HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)call.d_band.get(), (int)fill_bits, cells, c->s_compute));
-	// (from pageable memory: the copy has left `rows` when it returns; it lives to the end of the call anyway)
-	HIPCHK(c, hipMemcpyAsync(call.d_band_rows, rows.data(), (size_t)n * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
-	c->reduce.map.band = BandMap{call.d_band, call.d_band_rows, c->d_counts, a0, n, stat};
-	call.arm(cells * sizeof(float));
-	rc = call.dispatch(mode, a0, n, tile_variants, window, l_window, n_pairs); if (rc) return rc;
-	if (stat != TWK_HIP_STAT_D) {      // (D: the diagonal keeps the preset fill - no launch stores on it)
-		hipLaunchKernelGGL(k_ld_bandmat_diag, dim3((n + 255) / 256), dim3(256), 0, c->s_compute, call.d_band.get(), (const BandRow*)call.d_band_rows.get(), n, 1.0f);
-		HIPCHK(c, hipGetLastError());
-	}
+	if (n == 0 || (uint64_t)a0 + n > c->M) return TWK_HIP_E_INVALID;
+	BandLayout b;
+	const int rc = band_layout(c, a0, n, l_window, b); if (rc) return rc;
+	give_layout(b, first, row_ptr);
 	return TWK_HIP_OK;
 }
-}  // namespace
-}  // extern "C++"
 
 // ... and the band itself, in one contiguous copy of row_ptr[n] floats; first and row_ptr are the host layout's.
 int twk_hip_ld_matrix_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, int32_t window, uint32_t l_window,
                            int32_t stat, float fill, float* values, uint64_t capacity, uint32_t* first, uint64_t* row_ptr, uint64_t* n_records, uint64_t* n_pairs) {
-	ReduceCall call(c, Reduce::bandmat, f, values && first && row_ptr && valid_stat(stat) && (window & TWK_HIP_OPT_WINDOW), mode, a0, n);
+	ReduceCall call(c, Reduce::bandmat, &LastCalls::bandmat, f, values && first && row_ptr && valid_stat(stat) && (window & TWK_HIP_OPT_WINDOW), mode, a0, n);
 	if (call.bad) return call.bad;
-	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
-	std::vector<uint32_t> h_first(n);
-	std::vector<uint64_t> h_ptr((size_t)n + 1);
-	int rc = bandmat_layout(c, a0, n, l_window, h_first.data(), h_ptr.data()); if (rc) return rc;
-	const size_t cells = (size_t)h_ptr[n];
-	if (capacity < cells) {
-		snprintf(c->err, sizeof(c->err), "banded LD matrix: the band of %u variants holds %zu floats, the caller's array %llu", n, cells, (unsigned long long)capacity);
+	BandLayout b;
+	int rc = band_layout(c, a0, n, l_window, b); if (rc) return rc;
+	if (capacity < b.cells) {
+		snprintf(c->err, sizeof(c->err), "banded LD matrix: the band of %u variants holds %zu floats, the caller's array %llu", n, b.cells, (unsigned long long)capacity);
 		return TWK_HIP_E_INVALID;
 	}
-	rc = band_fill(call, mode, a0, n, tile_variants, window, l_window, stat, fill, h_first, h_ptr, n_pairs); if (rc) return rc;
+	rc = band_fill(call, mode, a0, n, tile_variants, window, l_window, stat, fill, b, n_pairs); if (rc) return rc;
+	const BandMap& d = c->reduce.map.band;
 	unsigned long long count = 0;
 	rc = call.tail("banded LD matrix", [&] {
-		return hipMemcpyAsync(values, call.d_band, cells * sizeof(float), hipMemcpyDeviceToHost, c->s_compute);
+		return hipMemcpyAsync(values, d.values, b.cells * sizeof(float), hipMemcpyDeviceToHost, c->s_compute);
 	}, [&] { return hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute); });
 	if (rc) return rc;
-	memcpy(first, h_first.data(), (size_t)n * sizeof(uint32_t));
-	memcpy(row_ptr, h_ptr.data(), ((size_t)n + 1) * sizeof(uint64_t));
+	give_layout(b, first, row_ptr);
 	if (n_records) *n_records = count;
 	return TWK_HIP_OK;
 }
 
-int twk_hip_bandmat_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* band_bytes) { return last_of(c, Reduce::bandmat, copy_ms, band_bytes); }
+int twk_hip_bandmat_last(const twk_hip_ctx* c, double* copy_ms, uint64_t* band_bytes) { return last_of(c, &LastCalls::bandmat, {copy_ms}, band_bytes); }
 
 // Haplotype blocks (ld_blocks.hip.h): the D' confidence bounds of the in-window pairs in band storage, and the blocks selected from them.
-extern "C++" {
-namespace {
-struct CiBand { std::vector<uint32_t> first; std::vector<uint64_t> ptr; size_t cells = 0; uint32_t widest = 0; };
-int ci_band_layout(twk_hip_ctx* c, uint32_t a0, uint32_t n, uint32_t l_window, CiBand& b) {
-	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
-	b.first.resize(n); b.ptr.resize((size_t)n + 1);
-	const int rc = bandmat_layout(c, a0, n, l_window, b.first.data(), b.ptr.data()); if (rc) return rc;
-	b.cells = (size_t)b.ptr[n];
-	for (uint32_t u = 0; u < n; ++u) b.widest = std::max<uint32_t>(b.widest, (uint32_t)std::min<uint64_t>(b.ptr[u + 1] - b.ptr[u], 0xFFFFFFFFull));
-	return TWK_HIP_OK;
-}
-// The bounds of the slice into call.d_ci_lo / call.d_ci_hi: the band map, the preset 255, the launches.
-int ci_band_fill(ReduceCall& call, int mode, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window, const CiBand& b, uint64_t* n_pairs) {
-	twk_hip_ctx* c = call.c;
-	std::vector<BandRow> rows(n);
-	for (uint32_t u = 0; u < n; ++u) rows[u] = BandRow{b.ptr[u], b.first[u], (uint32_t)(b.ptr[u + 1] - b.ptr[u])};
-	int rc = hold_for_call(c, call.d_band_rows, (size_t)n, "the band map of %u variants needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	rc = hold_for_call(c, call.d_ci_hi, b.cells, "the upper D' bounds of %u variants' band need %zu bytes of device memory: %s", n); if (rc) return rc;
-	rc = call.hold(call.d_ci_lo, b.cells, "the lower D' bounds of %u variants' band need %zu bytes of device memory: %s", n); if (rc) return rc;
-	HIPCHK(c, hipMemsetAsync(call.d_ci_lo, BC_NONE, b.cells, c->s_compute));
-	HIPCHK(c, hipMemsetAsync(call.d_ci_hi, BC_NONE, b.cells, c->s_compute));
-	// (from pageable memory: the copy has left `rows` when it returns)
-	HIPCHK(c, hipMemcpyAsync(call.d_band_rows, rows.data(), (size_t)n * sizeof(BandRow), hipMemcpyHostToDevice, c->s_compute));
-	c->reduce.map.ci = CiMap{call.d_ci_lo, call.d_ci_hi, call.d_band_rows, a0, n};
-	call.arm(b.cells * 2);
-	return call.dispatch(mode, a0, n, tile_variants, (int32_t)TWK_HIP_OPT_WINDOW, l_window, n_pairs);
-}
-}  // namespace
-}  // extern "C++"
-
 int twk_hip_ld_dprime_ci_band(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
                               uint8_t* lo, uint8_t* hi, uint64_t capacity, uint32_t* first, uint64_t* row_ptr, uint64_t* n_records, uint64_t* n_pairs) {
-	DevBuf<uint32_t> d_inf;                  // (before `call`: freed behind its destructor, which waits for the device)
-	ReduceCall call(c, Reduce::dprime_ci, f, lo && hi && first && row_ptr && l_window > 0, mode, a0, n);
+	ReduceCall call(c, Reduce::dprime_ci, nullptr, f, lo && hi && first && row_ptr && l_window > 0, mode, a0, n);
 	if (call.bad) return call.bad;
-	CiBand b;
-	int rc = ci_band_layout(c, a0, n, l_window, b); if (rc) return rc;
+	BandLayout b;
+	int rc = band_layout(c, a0, n, l_window, b); if (rc) return rc;
 	if (capacity < b.cells) {
 		snprintf(c->err, sizeof(c->err), "D' bounds: the band of %u variants holds %zu slots, the caller's arrays %llu", n, b.cells, (unsigned long long)capacity);
 		return TWK_HIP_E_INVALID;
 	}
-	rc = hold_for_call(c, d_inf, (size_t)n, "the informative counts of %u variants need %zu bytes of device memory: %s", n); if (rc) return rc;
+	uint32_t* const d_inf = call.hold<uint32_t>((size_t)n, "the informative counts of %u variants need %zu bytes of device memory: %s", n);
+	if (call.mem.failed) return call.mem.failed;
 	rc = ci_band_fill(call, mode, a0, n, tile_variants, l_window, b, n_pairs); if (rc) return rc;
-	hipLaunchKernelGGL(k_ci_informative, dim3((n + 3) / 4), dim3(BLOCKS_THREADS), 0, c->s_compute, (const uint8_t*)call.d_ci_lo, (const BandRow*)call.d_band_rows, n, d_inf.get());
+	const CiMap& d = c->reduce.map.ci;
+	hipLaunchKernelGGL(k_ci_informative, dim3((n + 3) / 4), dim3(BLOCKS_THREADS), 0, c->s_compute, (const uint8_t*)d.lo, d.rows, n, d_inf);
 	HIPCHK(c, hipGetLastError());
 	std::vector<uint32_t> inf(n);
 	rc = call.tail("D' bounds", [&] {
-		const hipError_t e = hipMemcpyAsync(lo, call.d_ci_lo, b.cells, hipMemcpyDeviceToHost, c->s_compute);
-		return e != hipSuccess ? e : hipMemcpyAsync(hi, call.d_ci_hi, b.cells, hipMemcpyDeviceToHost, c->s_compute);
+		const hipError_t e = hipMemcpyAsync(lo, d.lo, b.cells, hipMemcpyDeviceToHost, c->s_compute);
+		return e != hipSuccess ? e : hipMemcpyAsync(hi, d.hi, b.cells, hipMemcpyDeviceToHost, c->s_compute);
 	}, [&] { return hipMemcpyAsync(inf.data(), d_inf, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute); });
 	if (rc) return rc;
-	memcpy(first, b.first.data(), (size_t)n * sizeof(uint32_t));
-	memcpy(row_ptr, b.ptr.data(), ((size_t)n + 1) * sizeof(uint64_t));
+	give_layout(b, first, row_ptr);
 	if (n_records) { uint64_t sum = 0; for (const uint32_t x : inf) sum += x; *n_records = sum; }
 	return TWK_HIP_OK;
 }
@@ -3204,14 +3265,11 @@ int twk_hip_ld_blocks(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 	static_assert(sizeof(twk_hip_block_params) == sizeof(BlockParams), "BlockParams is twk_hip_block_params, field for field");
 	BlockParams par = BLOCK_DEFAULTS;
 	if (params) memcpy(&par, params, sizeof(par));
-	// (before `call`: freed behind its destructor, which waits for the device)
-	DevBuf<uint32_t> d_pos, d_ps, d_pr, d_counts3, d_flat, d_off, d_vals, d_vals_out, d_cs, d_cr, d_block_of, d_blk;
-	DevBuf<unsigned long long> d_keys, d_keys_out, d_used;
-	DevBuf<char> d_tmp;
-	ReduceCall call(c, Reduce::blocks, f, block_of && bc_params_ok(par) && l_window > 0, mode, a0, n);
+	ReduceCall call(c, Reduce::blocks, &LastCalls::blocks, f, block_of && bc_params_ok(par) && l_window > 0, mode, a0, n);
 	if (call.bad) return call.bad;
-	CiBand b;
-	int rc = ci_band_layout(c, a0, n, l_window, b); if (rc) return rc;
+	enum { COUNTS, EMIT, SORT, WALK };      // the stages of the call's report (twk_hip_blocks_stages; twk_hip_blocks_last: the walk)
+	BandLayout b;
+	int rc = band_layout(c, a0, n, l_window, b); if (rc) return rc;
 	BlockKey key; uint32_t key_bits = 0;
 	if (b.widest > BLOCK_MAX_BAND || !bc_key_layout(n, b.widest, l_window, &key, &key_bits)) {
 		snprintf(c->err, sizeof(c->err), "haplotype blocks: a window of %u base pairs reaches %u variants in a row of %u (at most %u, and a sort key of at most 64 bits)",
@@ -3225,45 +3283,44 @@ int twk_hip_ld_blocks(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 	for (uint32_t u = 0; u < n; ++u) h_pos[u] = c->h_meta[a0 + u].pos;
 	size_t scan_tmp = 0;
 	HIPCHK(c, rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(), c->s_compute));
-	{
-		const char* what = "the prefix counts of %u variants' band need %zu bytes of device memory: %s";
-		rc = hold_for_call(c, d_ps, b.cells, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_pr, b.cells, what, n); if (rc) return rc;
-		what = "the per-variant arrays of %u variants need %zu bytes of device memory: %s";
-		rc = hold_for_call(c, d_counts3, (size_t)n * 3, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_blk, (size_t)n * 3, what, n); if (rc) return rc;
-		for (DevBuf<uint32_t>* x : {&d_pos, &d_flat, &d_off}) { rc = hold_for_call(c, *x, (size_t)n, what, n); if (rc) return rc; }
-		rc = hold_for_call(c, d_block_of, M, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_used, (size_t)stride, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_tmp, std::max<size_t>(scan_tmp, 16), "the scan of %u counts needs %zu bytes of device memory: %s", n); if (rc) return rc;
-	}
+	const char* const band_what = "the prefix counts of %u variants' band need %zu bytes of device memory: %s";
+	const char* const variant_what = "the per-variant arrays of %u variants need %zu bytes of device memory: %s";
+	uint32_t* const d_ps = call.hold<uint32_t>(b.cells, band_what, n);
+	uint32_t* const d_pr = call.hold<uint32_t>(b.cells, band_what, n);
+	uint32_t* const d_counts3 = call.hold<uint32_t>((size_t)n * 3, variant_what, n);
+	uint32_t* const d_blk = call.hold<uint32_t>((size_t)n * 3, variant_what, n);
+	uint32_t *d_pos, *d_flat, *d_off;
+	for (uint32_t** x : {&d_pos, &d_flat, &d_off}) *x = call.hold<uint32_t>((size_t)n, variant_what, n);
+	uint32_t* const d_block_of = call.hold<uint32_t>(M, variant_what, n);
+	unsigned long long* const d_used = call.hold<unsigned long long>((size_t)stride, variant_what, n);
+	size_t tmp_bytes = std::max<size_t>(scan_tmp, 16);      // the scan's scratch, then the sort's: one buffer, grown for the sort if that needs more
+	char* d_tmp = call.hold<char>(tmp_bytes, "the scan of %u counts needs %zu bytes of device memory: %s", n);
+	if (call.mem.failed) return call.mem.failed;
 	rc = ci_band_fill(call, mode, a0, n, tile_variants, l_window, b, n_pairs); if (rc) return rc;
+	const CiMap& ci = c->reduce.map.ci;
 	HIPCHK(c, hipMemcpyAsync(d_pos, h_pos.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_block_of, 0xFF, M * sizeof(uint32_t), c->s_compute));          // TWK_HIP_NO_BLOCK
 	HIPCHK(c, hipMemsetAsync(d_blk, 0, (size_t)n * 3 * sizeof(uint32_t), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_used, 0, (size_t)stride * sizeof(unsigned long long), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(c->d_counts, 0, 3 * sizeof(unsigned long long), c->s_compute));
-	Events ev;
-	HIPCHK(c, ev.add(5));
-	c->blocks_stage_ms[0] = c->blocks_stage_ms[1] = c->blocks_stage_ms[2] = 0;
-	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
-	const BlocksBand band{call.d_ci_lo, call.d_ci_hi, call.d_band_rows, d_pos, d_ps, d_pr, n, par, key};
+	HIPCHK(c, call.mark(COUNTS));
+	const BlocksBand band{ci.lo, ci.hi, ci.rows, d_pos, d_ps, d_pr, n, par, key};
 	const dim3 per_row((n + 3) / 4), per_variant((n + BLOCKS_THREADS - 1) / BLOCKS_THREADS), threads(BLOCKS_THREADS);
 	hipLaunchKernelGGL(k_blocks_prefix, per_row, threads, 0, c->s_compute, band);
 	HIPCHK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_blocks_candidates<false>, per_variant, threads, 0, c->s_compute, band, d_counts3.get(), (const uint32_t*)nullptr, 0u,
+	hipLaunchKernelGGL(k_blocks_candidates<false>, per_variant, threads, 0, c->s_compute, band, d_counts3, (const uint32_t*)nullptr, 0u,
 	                   (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
 	HIPCHK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_blocks_flatten, per_variant, threads, 0, c->s_compute, (const uint32_t*)d_counts3, n, d_flat.get());
+	hipLaunchKernelGGL(k_blocks_flatten, per_variant, threads, 0, c->s_compute, (const uint32_t*)d_counts3, n, d_flat);
 	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, rocprim::exclusive_scan(d_tmp.get(), scan_tmp, d_flat.get(), d_off.get(), 0u, (size_t)n, rocprim::plus<uint32_t>(), c->s_compute));
-	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
+	HIPCHK(c, rocprim::exclusive_scan(d_tmp, scan_tmp, d_flat, d_off, 0u, (size_t)n, rocprim::plus<uint32_t>(), c->s_compute));
+	HIPCHK(c, call.mark(StageMarks::NO_STAGE));
 	std::vector<uint32_t> counts3((size_t)n * 3);
 	rc = call.download("haplotype blocks: the candidate counts", [&] {
 		return hipMemcpyAsync(counts3.data(), d_counts3, counts3.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
 	});
 	if (rc) return rc;
-	{ float ms = 0; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) c->blocks_stage_ms[0] = ms; }
+	call.marks.write(*call.report);            // (the counts: a call that ends here, or without a candidate, has no other stage)
 	uint64_t n_q = 0, n_c = 0, n_inf = 0;
 	for (uint32_t u = 0; u < n; ++u) { n_q += counts3[3 * (size_t)u]; n_c += counts3[3 * (size_t)u + 1]; n_inf += counts3[3 * (size_t)u + 2]; }
 	if (n_q > 0xFFFFFFFFull) {
@@ -3275,36 +3332,37 @@ int twk_hip_ld_blocks(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 	if (n_q) {
 		const size_t q = (size_t)n_q;
 		const char* what = "the %u qualifying candidates need %zu bytes of device memory: %s";
-		for (DevBuf<unsigned long long>* x : {&d_keys, &d_keys_out}) { rc = hold_for_call(c, *x, q, what, (uint32_t)n_q); if (rc) return rc; }
-		for (DevBuf<uint32_t>* x : {&d_vals, &d_vals_out, &d_cs, &d_cr}) { rc = hold_for_call(c, *x, q, what, (uint32_t)n_q); if (rc) return rc; }
+		unsigned long long *d_keys, *d_keys_out;
+		uint32_t *d_vals, *d_vals_out, *d_cs, *d_cr;
+		for (unsigned long long** x : {&d_keys, &d_keys_out}) *x = call.hold<unsigned long long>(q, what, (uint32_t)n_q);
+		for (uint32_t** x : {&d_vals, &d_vals_out, &d_cs, &d_cr}) *x = call.hold<uint32_t>(q, what, (uint32_t)n_q);
+		if (call.mem.failed) return call.mem.failed;
 		HIPCHK(c, hipMemsetAsync(d_keys, 0xFF, q * sizeof(unsigned long long), c->s_compute));      // (a slot the emitter leaves is no candidate: the walk skips it)
 		HIPCHK(c, hipMemsetAsync(d_vals, 0, q * sizeof(uint32_t), c->s_compute));
-		HIPCHK(c, hipEventRecord(ev[2], c->s_compute));
+		HIPCHK(c, call.mark(EMIT));
 		hipLaunchKernelGGL(k_blocks_candidates<true>, per_variant, threads, 0, c->s_compute, band, (uint32_t*)nullptr, (const uint32_t*)d_off, (uint32_t)n_q,
-		                   d_keys.get(), d_vals.get(), d_cs.get(), d_cr.get());
+		                   d_keys, d_vals, d_cs, d_cr);
 		HIPCHK(c, hipGetLastError());
-		HIPCHK(c, hipEventRecord(ev[3], c->s_compute));
+		HIPCHK(c, call.mark(SORT));
 		size_t sort_tmp = 0;
-		HIPCHK(c, rocprim::radix_sort_pairs(nullptr, sort_tmp, d_keys.get(), d_keys_out.get(), d_vals.get(), d_vals_out.get(), q, 0u, key_bits, c->s_compute));
-		rc = hold_for_call(c, d_tmp, std::max<size_t>(sort_tmp, 16), "the sort of %u candidates needs %zu bytes of device memory: %s", (uint32_t)n_q); if (rc) return rc;
-		sort_tmp = d_tmp.capacity();
-		HIPCHK(c, rocprim::radix_sort_pairs(d_tmp.get(), sort_tmp, d_keys.get(), d_keys_out.get(), d_vals.get(), d_vals_out.get(), q, 0u, key_bits, c->s_compute));
-		HIPCHK(c, hipEventRecord(ev[4], c->s_compute));
+		HIPCHK(c, rocprim::radix_sort_pairs(nullptr, sort_tmp, d_keys, d_keys_out, d_vals, d_vals_out, q, 0u, key_bits, c->s_compute));
+		tmp_bytes = std::max(tmp_bytes, sort_tmp);
+		d_tmp = call.mem.hold(tmp_bytes, "the sort of %u candidates needs %zu bytes of device memory: %s", (uint32_t)n_q, d_tmp);
+		if (call.mem.failed) return call.mem.failed;
+		HIPCHK(c, rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys_out, d_vals, d_vals_out, q, 0u, key_bits, c->s_compute));
+		HIPCHK(c, call.mark(StageMarks::NO_STAGE));
 		h_blk.resize((size_t)n * 3);
 		rc = call.tail("haplotype blocks: the walk", [&] {
 			hipLaunchKernelGGL(in_lds ? k_blocks_walk<true> : k_blocks_walk<false>, dim3(1), dim3(BLOCKS_WALK_THREADS), 0, c->s_compute,
 			                   (const unsigned long long*)d_keys_out, (const uint32_t*)d_vals_out, (uint32_t)n_q, key, (const uint32_t*)d_cs, (const uint32_t*)d_cr,
-			                   a0, n, stride, d_used.get(), d_block_of.get(), d_blk.get(), c->d_counts.get());
+			                   a0, n, stride, d_used, d_block_of, d_blk, c->d_counts.get());
 			return hipGetLastError();
 		}, [&] {
 			hipError_t e = hipMemcpyAsync(h_block_of.data(), d_block_of, M * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
 			if (e == hipSuccess) e = hipMemcpyAsync(h_blk.data(), d_blk, h_blk.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->s_compute);
 			return e != hipSuccess ? e : hipMemcpyAsync(&walked, c->d_counts, sizeof(walked), hipMemcpyDeviceToHost, c->s_compute);
-		});
+		}, WALK);
 		if (rc) return rc;
-		float ms = 0;
-		if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) c->blocks_stage_ms[1] = ms;
-		if (hipEventElapsedTime(&ms, ev[3], ev[4]) == hipSuccess) c->blocks_stage_ms[2] = ms;
 	}
 	// the blocks in file order: a variant that is its own block_of begins one
 	uint64_t nb = 0;
@@ -3325,102 +3383,82 @@ int twk_hip_ld_blocks(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32
 	return TWK_HIP_OK;
 }
 
-int twk_hip_blocks_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* band_bytes) { return last_of(c, Reduce::blocks, walk_ms, band_bytes); }
-int twk_hip_blocks_stages(const twk_hip_ctx* c, double* counts_ms, double* emit_ms, double* sort_ms) {
-	if (!c) return TWK_HIP_E_INVALID;
-	if (counts_ms) *counts_ms = c->blocks_stage_ms[0];
-	if (emit_ms) *emit_ms = c->blocks_stage_ms[1];
-	if (sort_ms) *sort_ms = c->blocks_stage_ms[2];
-	return TWK_HIP_OK;
-}
+// (the report's stages: COUNTS, EMIT, SORT, WALK)
+int twk_hip_blocks_last(const twk_hip_ctx* c, double* walk_ms, uint64_t* band_bytes) { return last_of(c, &LastCalls::blocks, {nullptr, nullptr, nullptr, walk_ms}, band_bytes); }
+int twk_hip_blocks_stages(const twk_hip_ctx* c, double* counts_ms, double* emit_ms, double* sort_ms) { return last_of(c, &LastCalls::blocks, {counts_ms, emit_ms, sort_ms}, nullptr); }
 
 // LD splitting (ld_split.hip.h): the banded r2 matrix of the slice, filled by the bandmat kind and kept on the device, then row prefixes,
-// block sums, one layer launch per k and the backtrack - all of it integers.  (The bandmat kind's own twk_hip_bandmat_last keeps what the
+// block sums, one layer launch per k and the backtrack - all of it integers.  (The call writes its own report: twk_hip_bandmat_last keeps what the
 // last twk_hip_ld_matrix_band call left.)
 int twk_hip_ld_split(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t n, uint32_t tile_variants, uint32_t l_window,
                      uint32_t min_size, uint32_t max_size, uint32_t k_max, uint64_t* total, uint8_t* feasible, uint64_t* cost, uint32_t* cuts,
                      uint64_t* n_records, uint64_t* n_pairs) {
-	// (before `call`: freed behind its destructor, which waits for the device)
-	DevBuf<long long> d_rp, d_w, d_row_total, d_g, d_gn;
-	DevBuf<unsigned long long> d_cost, d_total;
-	DevBuf<uint32_t> d_upc, d_cuts, d_broken;
-	DevBuf<uint16_t> d_dk;
-	DevBuf<uint8_t> d_feasible;
-	ReduceCall call(c, Reduce::bandmat, f, total && feasible && cost && cuts && l_window > 0 && sp_sizes_ok(n, min_size, max_size, k_max), mode, a0, n);
+	ReduceCall call(c, Reduce::bandmat, &LastCalls::split, f, total && feasible && cost && cuts && l_window > 0 && sp_sizes_ok(n, min_size, max_size, k_max), mode, a0, n);
 	if (call.bad) return call.bad;
-	if (c->h_meta.size() < (size_t)a0 + n) return TWK_HIP_E_INVALID;
+	enum { BAND, SUMS, LAYERS, BACKTRACK };      // the stages of the call's report (twk_hip_split_last)
+	BandLayout b;
+	int rc = band_layout(c, a0, n, l_window, b); if (rc) return rc;
 	if (c->h_meta[a0].rid != c->h_meta[(size_t)a0 + n - 1].rid) {
 		snprintf(c->err, sizeof(c->err), "LD splitting: the variants [%u, %u) lie on more than one contig; split one contig a call", a0, a0 + n);
 		return TWK_HIP_E_INVALID;
 	}
-	std::vector<uint32_t> h_first(n);
-	std::vector<uint64_t> h_ptr((size_t)n + 1);
-	int rc = bandmat_layout(c, a0, n, l_window, h_first.data(), h_ptr.data()); if (rc) return rc;
-	const size_t cells = (size_t)h_ptr[n];
-	if ((cells - n) / 2 >= SPLIT_MAX_PAIRS) {
-		snprintf(c->err, sizeof(c->err), "LD splitting: the band of %u variants holds %zu pairs, 2^31 or more: their sum may pass 2^63; narrow the window or split the slice", n, (cells - n) / 2);
+	if ((b.cells - n) / 2 >= SPLIT_MAX_PAIRS) {
+		snprintf(c->err, sizeof(c->err), "LD splitting: the band of %u variants holds %zu pairs, 2^31 or more: their sum may pass 2^63; narrow the window or split the slice", n, (b.cells - n) / 2);
 		return TWK_HIP_E_INVALID;
 	}
 	std::vector<uint32_t> h_upc(n);
 	uint32_t widest = 1;                       // the offsets Rp stores: at least one row, so that no buffer is empty
 	for (uint32_t u = 0; u < n; ++u) {
-		h_upc[u] = sp_upc(sp_upper(h_first[u], (uint32_t)(h_ptr[u + 1] - h_ptr[u]), u), max_size);
+		h_upc[u] = sp_upc(sp_upper(b.rows[u].first, b.rows[u].len, u), max_size);
 		widest = std::max(widest, h_upc[u]);
 	}
 	const SplitSizes sizes{n, min_size, max_size, k_max};
 	const size_t n1 = (size_t)n + 1, rp_items = (size_t)widest * n, w_items = (size_t)(max_size - min_size + 1) * n1, d_items = (size_t)k_max * n1;
 	const size_t cut_items = (size_t)k_max * (k_max + 1);
-	{
-		const char* what = "LD splitting: the row prefixes and block sums of %u variants need %zu bytes of device memory: %s";
-		rc = hold_for_call(c, d_rp, rp_items, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_w, w_items, what, n); if (rc) return rc;
-		what = "LD splitting: the layers of %u variants need %zu bytes of device memory: %s";
-		rc = hold_for_call(c, d_dk, d_items, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_g, 2 * n1, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_row_total, (size_t)n, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_upc, (size_t)n, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_gn, (size_t)k_max + 1, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_cost, (size_t)k_max, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_cuts, cut_items, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_feasible, (size_t)k_max, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_total, (size_t)1, what, n); if (rc) return rc;
-		rc = hold_for_call(c, d_broken, (size_t)1, what, n); if (rc) return rc;
-	}
-	const auto bandmat_last = c->reduce_last[(int)Reduce::bandmat];      // (arm() overwrites it: put back below)
-	struct Restore { twk_hip_ctx* c; decltype(bandmat_last) was; ~Restore() { c->reduce_last[(int)Reduce::bandmat] = was; } } restore{c, bandmat_last};
-	Events ev;
-	HIPCHK(c, ev.add(5));
-	for (double& x : c->split_stage_ms) x = 0;
-	c->split_bytes = cells * sizeof(float) + (size_t)n * sizeof(BandRow) + (rp_items + w_items + 2 * n1 + n + k_max + 1) * sizeof(long long) + d_items * sizeof(uint16_t) +
-	                 (size_t)n * sizeof(uint32_t) + (size_t)k_max * 9 + cut_items * sizeof(uint32_t) + 12;
-	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
-	rc = band_fill(call, mode, a0, n, tile_variants, (int32_t)TWK_HIP_OPT_WINDOW, l_window, TWK_HIP_STAT_R2, 0.0f, h_first, h_ptr, n_pairs); if (rc) return rc;
-	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
+	const char* const sums_what = "LD splitting: the row prefixes and block sums of %u variants need %zu bytes of device memory: %s";
+	const char* const layers_what = "LD splitting: the layers of %u variants need %zu bytes of device memory: %s";
+	long long* const d_rp = call.hold<long long>(rp_items, sums_what, n);
+	long long* const d_w = call.hold<long long>(w_items, sums_what, n);
+	uint16_t* const d_dk = call.hold<uint16_t>(d_items, layers_what, n);
+	long long* const d_g = call.hold<long long>(2 * n1, layers_what, n);
+	long long* const d_row_total = call.hold<long long>((size_t)n, layers_what, n);
+	uint32_t* const d_upc = call.hold<uint32_t>((size_t)n, layers_what, n);
+	long long* const d_gn = call.hold<long long>((size_t)k_max + 1, layers_what, n);
+	unsigned long long* const d_cost = call.hold<unsigned long long>((size_t)k_max, layers_what, n);
+	uint32_t* const d_cuts = call.hold<uint32_t>(cut_items, layers_what, n);
+	uint8_t* const d_feasible = call.hold<uint8_t>((size_t)k_max, layers_what, n);
+	unsigned long long* const d_total = call.hold<unsigned long long>((size_t)1, layers_what, n);
+	uint32_t* const d_broken = call.hold<uint32_t>((size_t)1, layers_what, n);
+	if (call.mem.failed) return call.mem.failed;
+	HIPCHK(c, call.mark(BAND));
+	rc = band_fill(call, mode, a0, n, tile_variants, (int32_t)TWK_HIP_OPT_WINDOW, l_window, TWK_HIP_STAT_R2, 0.0f, b, n_pairs); if (rc) return rc;
+	const BandMap& band = c->reduce.map.band;
+	call.report->bytes = call.mem.bytes();      // (everything the call holds, not the band alone: nothing is held behind this line)
+	HIPCHK(c, call.mark(SUMS));
 	// (from pageable memory: the copy has left h_upc when it returns)
 	HIPCHK(c, hipMemcpyAsync(d_upc, h_upc.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_gn, 0xFF, ((size_t)k_max + 1) * sizeof(long long), c->s_compute));      // SPLIT_INFEASIBLE
 	HIPCHK(c, hipMemsetAsync(d_g, 0, sizeof(long long), c->s_compute));                                // G_0(0) = 0, layer 0's whole range
 	const dim3 threads(SPLIT_THREADS);
-	hipLaunchKernelGGL(k_split_prefix, dim3((n + 3) / 4), threads, 0, c->s_compute, (const float*)call.d_band, (const BandRow*)call.d_band_rows, (const uint32_t*)d_upc, n,
-	                   d_rp.get(), d_row_total.get());
+	hipLaunchKernelGGL(k_split_prefix, dim3((n + 3) / 4), threads, 0, c->s_compute, (const float*)band.values, band.rows, (const uint32_t*)d_upc, n, d_rp, d_row_total);
 	HIPCHK(c, hipGetLastError());
-	hipLaunchKernelGGL(k_split_sums, dim3((n + SPLIT_THREADS - 1) / SPLIT_THREADS), threads, 0, c->s_compute, (const long long*)d_rp, (const uint32_t*)d_upc, sizes, d_w.get());
+	hipLaunchKernelGGL(k_split_sums, dim3((n + SPLIT_THREADS - 1) / SPLIT_THREADS), threads, 0, c->s_compute, (const long long*)d_rp, (const uint32_t*)d_upc, sizes, d_w);
 	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipEventRecord(ev[2], c->s_compute));
+	HIPCHK(c, call.mark(LAYERS));
 	for (uint32_t k = 1; k <= k_max; ++k) {
 		const uint32_t lo = sp_layer_lo(k, min_size), hi = sp_layer_hi(k, max_size, n);
 		if (lo > hi) break;                    // k * min_size > n: no further layer holds a feasible b
-		long long* const g_prev = d_g.get() + ((k - 1) & 1) * n1;
-		long long* const g_cur = d_g.get() + (k & 1) * n1;
+		long long* const g_prev = d_g + ((k - 1) & 1) * n1;
+		long long* const g_cur = d_g + (k & 1) * n1;
 		hipLaunchKernelGGL(k_split_layer, dim3((hi - lo) / SPLIT_THREADS + 1), threads, 0, c->s_compute, (const long long*)g_prev, (const long long*)d_w, sizes, k, lo, hi,
-		                   sp_layer_lo(k - 1, min_size), sp_layer_hi(k - 1, max_size, n), g_cur, d_dk.get(), d_gn.get());
+		                   sp_layer_lo(k - 1, min_size), sp_layer_hi(k - 1, max_size, n), g_cur, d_dk, d_gn);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipEventRecord(ev[3], c->s_compute));
+	HIPCHK(c, call.mark(BACKTRACK));
 	hipLaunchKernelGGL(k_split_backtrack, dim3(1), dim3(SPLIT_MAX_K), 0, c->s_compute, (const long long*)d_row_total, (const long long*)d_gn, (const uint16_t*)d_dk, sizes,
-	                   d_total.get(), d_feasible.get(), d_cost.get(), d_cuts.get(), d_broken.get());
+	                   d_total, d_feasible, d_cost, d_cuts, d_broken);
 	HIPCHK(c, hipGetLastError());
-	HIPCHK(c, hipEventRecord(ev[4], c->s_compute));
+	HIPCHK(c, call.mark(StageMarks::NO_STAGE));
 	std::vector<uint8_t> h_feasible(k_max);
 	std::vector<unsigned long long> h_cost(k_max);
 	std::vector<uint32_t> h_cuts(cut_items);
@@ -3435,7 +3473,7 @@ int twk_hip_ld_split(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 		return e != hipSuccess ? e : hipMemcpyAsync(&count, c->d_counts, sizeof(count), hipMemcpyDeviceToHost, c->s_compute);
 	});
 	if (rc) return rc;
-	for (int st = 0; st < 4; ++st) { float ms = 0; if (hipEventElapsedTime(&ms, ev[st], ev[st + 1]) == hipSuccess) c->split_stage_ms[st] = ms; }
+	call.marks.write(*call.report);
 	if (broken) { snprintf(c->err, sizeof(c->err), "LD splitting: %u of the chains through D do not end at the slice's start", broken); return TWK_HIP_E_DEVICE; }
 	*total = h_total;
 	for (uint32_t K = 1; K <= k_max; ++K) {
@@ -3449,13 +3487,7 @@ int twk_hip_ld_split(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_
 }
 
 int twk_hip_split_last(const twk_hip_ctx* c, double* band_ms, double* sums_ms, double* layers_ms, double* backtrack_ms, uint64_t* bytes) {
-	if (!c) return TWK_HIP_E_INVALID;
-	if (band_ms) *band_ms = c->split_stage_ms[0];
-	if (sums_ms) *sums_ms = c->split_stage_ms[1];
-	if (layers_ms) *layers_ms = c->split_stage_ms[2];
-	if (backtrack_ms) *backtrack_ms = c->split_stage_ms[3];
-	if (bytes) *bytes = c->split_bytes;
-	return TWK_HIP_OK;
+	return last_of(c, &LastCalls::split, {band_ms, sums_ms, layers_ms, backtrack_ms}, bytes);
 }
 
 // Top-k LD partners: the lists' slots are zeroed in front of the launches; behind the last of them the keys are copied out and unpacked
@@ -3463,38 +3495,34 @@ int twk_hip_split_last(const twk_hip_ctx* c, double* band_ms, double* sums_ms, d
 int twk_hip_ld_topk(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
                     uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
                     int32_t stat, uint32_t k, uint32_t* idx, float* val, uint64_t* n_pairs) {
-	ReduceCall call(c, Reduce::topk, f, idx && val && k >= 1 && k <= TOPK_MAX && valid_stat(stat), mode, a0, nA);
+	ReduceCall call(c, Reduce::topk, &LastCalls::topk, f, idx && val && k >= 1 && k <= TOPK_MAX && valid_stat(stat), mode, a0, nA);
 	if (call.bad) return call.bad;
 	const size_t M = c->M, slots = M * k;
-	int rc = hold_for_call(c, call.d_topk, slots, "the top-k lists of %u variants need %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	unsigned long long* const d_topk = call.hold<unsigned long long>(slots, "the top-k lists of %u variants need %zu bytes of device memory: %s", (uint32_t)M);
+	if (call.mem.failed) return call.mem.failed;
 	// (beyond 64 KiB of dynamic LDS a kernel has to be told so; k = 32 asks for 72 KiB)
 	HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_ld_topk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tk_lds_bytes(TOPK_MAX)));
-	HIPCHK(c, hipMemsetAsync(call.d_topk, 0, slots * sizeof(unsigned long long), c->s_compute));
-	c->reduce.map.topk = TopkMap{call.d_topk, k, stat};
+	HIPCHK(c, hipMemsetAsync(d_topk, 0, slots * sizeof(unsigned long long), c->s_compute));
+	c->reduce.map.topk = TopkMap{d_topk, k, stat};
 	call.arm(slots * sizeof(unsigned long long));
 	if (triangle && nA < 2) { if (n_pairs) *n_pairs = 0; }      // (a single variant has no pair)
-	else { rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs); if (rc) return rc; }
+	else { const int rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs); if (rc) return rc; }
 	const auto t0 = std::chrono::steady_clock::now();
-	const size_t slab = std::min<size_t>(slots, (size_t)1 << 21);      // 16 MiB of keys at a time
-	std::vector<unsigned long long> keys(slab);
-	for (size_t at = 0; at < slots; at += slab) {
-		const size_t m = std::min(slab, slots - at);
-		rc = call.download("top-k lists", [&] { return hipMemcpyAsync(keys.data(), call.d_topk + at, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute); });
-		if (rc) return rc;
-		for (size_t e = 0; e < m; ++e) tk_unpack(keys[e], idx + at + e, val + at + e);
-	}
-	c->reduce_last[(int)Reduce::topk].ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+	const int rc = call.download_slabs("top-k lists", d_topk, slots, 1, std::min<size_t>(slots, (size_t)1 << 21),      // 16 MiB of keys at a time
+		[&](size_t at, size_t m, const unsigned long long* keys) { for (size_t e = 0; e < m; ++e) tk_unpack(keys[e], idx + at + e, val + at + e); });
+	if (rc) return rc;
+	call.report->stage_ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();      // (the host's clock: the unpacking is the host's)
 	return TWK_HIP_OK;
 }
 
-int twk_hip_topk_last(const twk_hip_ctx* c, double* unpack_ms, uint64_t* list_bytes) { return last_of(c, Reduce::topk, unpack_ms, list_bytes); }
+int twk_hip_topk_last(const twk_hip_ctx* c, double* unpack_ms, uint64_t* list_bytes) { return last_of(c, &LastCalls::topk, {unpack_ms}, list_bytes); }
 
 // LD decay: the bins' integer accumulators are zeroed in front of the launches and converted behind the last of them.
 int twk_hip_ld_decay(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle,
                      uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
                      uint32_t range_bp, uint32_t n_bins, uint64_t* n, double* sum_r2, uint64_t* n_pairs) {
 	const bool bins_ok = n_bins >= 1 && n_bins <= DECAY_MAX_BINS && range_bp >= n_bins;      // (range_bp < n_bins: a width of 0)
-	ReduceCall call(c, Reduce::decay, f, n && sum_r2 && bins_ok, mode, a0, nA);
+	ReduceCall call(c, Reduce::decay, nullptr, f, n && sum_r2 && bins_ok, mode, a0, nA);
 	if (call.bad) return call.bad;
 	const size_t B = n_bins;
 	HIPCHK(c, c->d_decay.reserve(3 * B, 3 * B, nullptr));
@@ -3520,7 +3548,7 @@ int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uin
                          int32_t stat, const uint16_t* bin_x, const uint16_t* bin_y, uint32_t x_bins, uint32_t y_bins,
                          uint64_t* n, double* sum, double* sum_sq, double* min, double* max, uint64_t* n_pairs) {
 	const bool bins_ok = x_bins >= 1 && x_bins <= AGG_MAX_BINS && y_bins >= 1 && y_bins <= AGG_MAX_BINS;
-	ReduceCall call(c, Reduce::aggregate, f, bin_x && bin_y && n && sum && sum_sq && min && max && valid_stat(stat) && bins_ok, mode, a0, nA);
+	ReduceCall call(c, Reduce::aggregate, nullptr, f, bin_x && bin_y && n && sum && sum_sq && min && max && valid_stat(stat) && bins_ok, mode, a0, nA);
 	if (call.bad) return call.bad;
 	const size_t M = c->M, cells = (size_t)x_bins * y_bins, words = cells * AGG_CELL_WORDS;
 	std::vector<uint32_t> key(M);
@@ -3529,33 +3557,28 @@ int twk_hip_ld_aggregate(twk_hip_ctx* c, int mode, const twk_hip_filters* f, uin
 		key[v] = ag_pack(bin_x[v], bin_y[v]);
 	}
 	HIPCHK(c, c->d_agg_key.reserve(M, M, nullptr));
-	int rc = call.hold(call.d_agg, words, "the LD aggregate of %u variants needs %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	unsigned long long* const d_agg = call.hold<unsigned long long>(words, "the LD aggregate of %u variants needs %zu bytes of device memory: %s", (uint32_t)M);
+	if (call.mem.failed) return call.mem.failed;
+	int rc = call.zero_counts(); if (rc) return rc;
 	// (from pageable memory: the copy has left `key` when it returns)
 	HIPCHK(c, hipMemcpyAsync(c->d_agg_key, key.data(), M * sizeof(uint32_t), hipMemcpyHostToDevice, c->s_compute));
-	hipLaunchKernelGGL(k_ld_aggregate_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, call.d_agg.get(), (unsigned long long)words);
+	hipLaunchKernelGGL(k_ld_aggregate_init, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->s_compute, d_agg, (unsigned long long)words);
 	HIPCHK(c, hipGetLastError());
-	c->reduce.map.agg = AggMap{c->d_agg_key, call.d_agg, x_bins, y_bins, stat};
+	c->reduce.map.agg = AggMap{c->d_agg_key, d_agg, x_bins, y_bins, stat};
 	call.arm(words * sizeof(unsigned long long));
 	rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
 	if (rc) return rc;
-	const size_t slab = std::min<size_t>(cells, (size_t)1 << 18);      // 16 MiB of accumulators at a time
-	std::vector<unsigned long long> acc(slab * AGG_CELL_WORDS);
-	for (size_t at = 0; at < cells; at += slab) {
-		const size_t m = std::min(slab, cells - at);
-		rc = call.download("aggregate arrays", [&] {
-			return hipMemcpyAsync(acc.data(), call.d_agg + at * AGG_CELL_WORDS, m * AGG_CELL_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+	return call.download_slabs("aggregate arrays", d_agg, cells, AGG_CELL_WORDS, std::min<size_t>(cells, (size_t)1 << 18),      // 16 MiB of accumulators at a time
+		[&](size_t at, size_t m, const unsigned long long* acc) {
+			for (size_t k = 0; k < m; ++k) {
+				const unsigned long long* w = acc + k * AGG_CELL_WORDS;
+				n[at + k] = w[AGG_W_N];
+				sum[at + k] = xs_sum_to_double_signed<AGG_SPLIT>(w[AGG_W_Q_HI], w[AGG_W_Q_LO]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
+				sum_sq[at + k] = xs_sum_to_double_unsigned<AGG_SPLIT>(w[AGG_W_Q2_HI], w[AGG_W_Q2_LO]);
+				min[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MIN]) : 0.0;
+				max[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
+			}
 		});
-		if (rc) return rc;
-		for (size_t k = 0; k < m; ++k) {
-			const unsigned long long* w = acc.data() + k * AGG_CELL_WORDS;
-			n[at + k] = w[AGG_W_N];
-			sum[at + k] = xs_sum_to_double_signed<AGG_SPLIT>(w[AGG_W_Q_HI], w[AGG_W_Q_LO]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
-			sum_sq[at + k] = xs_sum_to_double_unsigned<AGG_SPLIT>(w[AGG_W_Q2_HI], w[AGG_W_Q2_LO]);
-			min[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MIN]) : 0.0;
-			max[at + k] = w[AGG_W_N] ? xs_value_to_double((long long)w[AGG_W_MAX]) : 0.0;
-		}
-	}
-	return TWK_HIP_OK;
 }
 
 // Partitioned LD scores: the annotations are checked, packed to n_annot columns and uploaded, the integer accumulators of every
@@ -3564,7 +3587,7 @@ int twk_hip_ld_score_annot(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
                            uint32_t part, uint32_t n_parts, uint32_t tile_variants, int32_t window, uint32_t l_window,
                            const double* annot, uint32_t n_annot, uint64_t ld_annot, uint64_t* n_partners, double* score, uint64_t* n_pairs) {
 	const bool shape_ok = n_annot >= 1 && n_annot <= ANNOT_MAX_CATEGORIES && ld_annot >= n_annot;
-	ReduceCall call(c, Reduce::annot, f, annot && n_partners && score && shape_ok, mode, a0, nA);
+	ReduceCall call(c, Reduce::annot, nullptr, f, annot && n_partners && score && shape_ok, mode, a0, nA);
 	if (call.bad) return call.bad;
 	const size_t M = c->M, C = n_annot, cells = M * C;
 	std::vector<double> packed(cells);
@@ -3577,42 +3600,30 @@ int twk_hip_ld_score_annot(twk_hip_ctx* c, int mode, const twk_hip_filters* f, u
 			}
 			packed[v * C + k] = a;
 		}
-	int rc = hold_for_call(c, call.d_annot, cells, "the annotations of %u variants need %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
-	rc = hold_for_call(c, call.d_annot_acc, 2 * cells, "the partitioned LD scores of %u variants need %zu bytes of device memory: %s", (uint32_t)M); if (rc) return rc;
+	double* const d_annot = call.hold<double>(cells, "the annotations of %u variants need %zu bytes of device memory: %s", (uint32_t)M);
+	unsigned long long* const d_annot_acc = call.hold<unsigned long long>(2 * cells, "the partitioned LD scores of %u variants need %zu bytes of device memory: %s", (uint32_t)M);
+	if (call.mem.failed) return call.mem.failed;
 	HIPCHK(c, c->d_score_n.reserve(M, M, nullptr));
 	// (from pageable memory: the copy has left `packed` when it returns)
-	HIPCHK(c, hipMemcpyAsync(call.d_annot, packed.data(), cells * sizeof(double), hipMemcpyHostToDevice, c->s_compute));
-	HIPCHK(c, hipMemsetAsync(call.d_annot_acc, 0, 2 * cells * sizeof(unsigned long long), c->s_compute));
+	HIPCHK(c, hipMemcpyAsync(d_annot, packed.data(), cells * sizeof(double), hipMemcpyHostToDevice, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(d_annot_acc, 0, 2 * cells * sizeof(unsigned long long), c->s_compute));
 	HIPCHK(c, hipMemsetAsync(c->d_score_n, 0, M * sizeof(unsigned long long), c->s_compute));
-	c->reduce.map.annot = AnnotMap{call.d_annot, call.d_annot_acc, c->d_score_n, n_annot};
+	c->reduce.map.annot = AnnotMap{d_annot, d_annot_acc, c->d_score_n, n_annot};
 	call.arm(2 * cells * sizeof(unsigned long long));
-	rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
+	int rc = call.dispatch(mode, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window, n_pairs);
 	if (rc) return rc;
 	rc = call.download("partner counts", [&] { return hipMemcpyAsync(n_partners, c->d_score_n, M * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute); });
 	if (rc) return rc;
-	const size_t slab = std::min<size_t>(cells, (size_t)1 << 20);      // 16 MiB of accumulators at a time
-	std::vector<unsigned long long> acc(2 * slab);
-	for (size_t at = 0; at < cells; at += slab) {
-		const size_t m = std::min(slab, cells - at);
-		rc = call.download("partitioned score arrays", [&] {
-			return hipMemcpyAsync(acc.data(), call.d_annot_acc + 2 * at, 2 * m * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->s_compute);
+	return call.download_slabs("partitioned score arrays", d_annot_acc, cells, 2, std::min<size_t>(cells, (size_t)1 << 20),      // 16 MiB of accumulators at a time
+		[&](size_t at, size_t m, const unsigned long long* acc) {
+			for (size_t k = 0; k < m; ++k) score[at + k] = xs_sum_to_double_signed<ANNOT_SPLIT>(acc[2 * k], acc[2 * k + 1]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
 		});
-		if (rc) return rc;
-		for (size_t k = 0; k < m; ++k) score[at + k] = xs_sum_to_double_signed<ANNOT_SPLIT>(acc[2 * k], acc[2 * k + 1]);      // (exact in 128 bits, one conversion: ld_exact_sum.h)
-	}
-	return TWK_HIP_OK;
 }
 
 // ---- sample relationship (ld_relate.hip.h): its own plane set, tile lists, count launches and epilogue, beside the variant launch path ----
 extern "C++" {
 namespace {
 static_assert(sizeof(RelCounts) == sizeof(twk_hip_rel_counts) && sizeof(RelCounts) == 24, "the epilogue stores twk_hip_rel_counts");
-
-// Device memory of the call (hold_for_call), named in the error text.
-template <class T>
-int relate_hold(twk_hip_ctx* c, DevBuf<T>& buf, size_t items, const char* what) {
-	return hold_for_call(c, buf, items, "sample relationship: %s needs %zu bytes of device memory: %s", what);
-}
 
 struct RelateSuper { uint32_t sa, na, sb, nb; bool diag; CountTable table; size_t table_at = 0; };      // table_at: where the packed table lies in the call's one copy
 }  // namespace
@@ -3637,30 +3648,28 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 	// the plane set: P rows a sample over the variants in use (ld_relate_index.h)
 	const uint32_t P = rl_planes(any_missing), W = rl_words(n_use), N = c->N;
 	const uint64_t rows_alloc = rl_rows_alloc(N, P), live_rows = (uint64_t)N * P;
-	DevBuf<uint32_t> d_rows, d_rowpop, d_ids, d_C, d_lists, d_tickets;
-	DevBuf<unsigned long long> d_out;
-	DevBuf<RelCounts> d_counts;
-	DevBuf<RelateArgs> d_args;
-	int rc = relate_hold(c, d_rows, (size_t)rows_alloc * W, "the planes of the samples"); if (rc) return rc;
-	rc = relate_hold(c, d_rowpop, (size_t)rows_alloc, "the planes' popcounts"); if (rc) return rc;
-	if (variants) {
-		rc = relate_hold(c, d_ids, n_use, "the variant list"); if (rc) return rc;
-		HIPCHK(c, hipMemcpyAsync(d_ids, variants, (size_t)n_use * 4, hipMemcpyHostToDevice, c->s_compute));
-	}
+	// the call's memory: released when the entry point leaves, behind the wait for its stream - or, on a failure's way out, by frees that
+	// wait for the device themselves
+	HeldMemory mem(c);
+	const char* const what = "sample relationship: %s needs %zu bytes of device memory: %s";
+	uint32_t* const d_rows = mem.hold<uint32_t>((size_t)rows_alloc * W, what, "the planes of the samples");
+	uint32_t* const d_rowpop = mem.hold<uint32_t>((size_t)rows_alloc, what, "the planes' popcounts");
+	uint32_t* const d_ids = variants ? mem.hold<uint32_t>(n_use, what, "the variant list") : nullptr;
+	if (mem.failed) return mem.failed;
+	if (variants) HIPCHK(c, hipMemcpyAsync(d_ids, variants, (size_t)n_use * 4, hipMemcpyHostToDevice, c->s_compute));
 	// (the transposition writes every word of the live rows; the zero rows behind them are set here)
 	HIPCHK(c, hipMemsetAsync(d_rows + live_rows * W, 0, (size_t)(rows_alloc - live_rows) * W * 4, c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_rowpop, 0, (size_t)rows_alloc * 4, c->s_compute));
-	Events ev;
-	HIPCHK(c, ev.add(2));
-	HIPCHK(c, hipEventRecord(ev[0], c->s_compute));
+	StageMarks marks;
+	HIPCHK(c, marks.mark(0, c->s_compute));      // the report's one stage: the transposition
 	{
 		const dim3 grid((N + RL_BLOCK_SAMPLES - 1) / RL_BLOCK_SAMPLES, std::min<uint32_t>(W / RL_KC, 65535u)), block(RL_THREADS);
 		hipLaunchKernelGGL(k_relate_transpose, grid, block, 0, c->s_compute, (const uint32_t*)c->raw, (const uint32_t*)(any_missing ? c->rawmask.get() : nullptr), c->Wp,
-		                   (const uint32_t*)(variants ? d_ids.get() : nullptr), n_use, N, P, d_rows.get(), W);
+		                   (const uint32_t*)d_ids, n_use, N, P, d_rows, W);
 		HIPCHK(c, hipGetLastError());
 	}
-	HIPCHK(c, hipEventRecord(ev[1], c->s_compute));
-	hipLaunchKernelGGL(k_row_popcount, dim3((unsigned)((live_rows + 3) / 4)), dim3(256), 0, c->s_compute, (const uint32_t*)d_rows, W, (uint32_t)live_rows, d_rowpop.get());
+	HIPCHK(c, marks.mark(StageMarks::NO_STAGE, c->s_compute));
+	hipLaunchKernelGGL(k_row_popcount, dim3((unsigned)((live_rows + 3) / 4)), dim3(256), 0, c->s_compute, (const uint32_t*)d_rows, W, (uint32_t)live_rows, d_rowpop);
 	HIPCHK(c, hipGetLastError());
 
 	// the super-tiles of the sample-pair space, each with its tile list and unit table (one copy to the device for all of them)
@@ -3684,12 +3693,13 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 			supers.push_back(std::move(st));
 		}
 	const size_t cells = (size_t)nSA * nSB;
-	rc = relate_hold(c, d_C, c_words, "the count matrix of a super-tile"); if (rc) return rc;
-	rc = relate_hold(c, d_lists, blob.size(), "the tile lists"); if (rc) return rc;
-	rc = relate_hold(c, d_tickets, supers.size() * 8, "the work tickets"); if (rc) return rc;
-	rc = relate_hold(c, d_args, supers.size(), "the epilogue's parameter blocks"); if (rc) return rc;
-	if (out) { rc = relate_hold(c, d_out, cells, "the matrix"); if (rc) return rc; }
-	if (counts) { rc = relate_hold(c, d_counts, cells, "the counts"); if (rc) return rc; }
+	uint32_t* const d_C = mem.hold<uint32_t>(c_words, what, "the count matrix of a super-tile");
+	uint32_t* const d_lists = mem.hold<uint32_t>(blob.size(), what, "the tile lists");
+	uint32_t* const d_tickets = mem.hold<uint32_t>(supers.size() * 8, what, "the work tickets");
+	RelateArgs* const d_args = mem.hold<RelateArgs>(supers.size(), what, "the epilogue's parameter blocks");
+	unsigned long long* const d_out = out ? mem.hold<unsigned long long>(cells, what, "the matrix") : nullptr;
+	RelCounts* const d_counts = counts ? mem.hold<RelCounts>(cells, what, "the counts") : nullptr;
+	if (mem.failed) return mem.failed;
 	unsigned long long fill_bits; memcpy(&fill_bits, &fill, sizeof(fill_bits));          // any pattern, NaNs included
 	std::vector<RelateArgs> args(supers.size());
 	for (size_t k = 0; k < supers.size(); ++k) {
@@ -3699,32 +3709,35 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 		a.sa = st.sa; a.na = st.na; a.sb = st.sb; a.nb = st.nb;
 		a.out_a0 = sA0; a.out_b0 = sB0; a.out_ld = nSB;
 		a.diag = st.diag ? 1 : 0; a.mirror = square ? 1 : 0; a.stat = stat; a.fill_bits = fill_bits;
-		a.out = out ? d_out.get() : nullptr; a.counts = counts ? d_counts.get() : nullptr;
+		a.out = d_out; a.counts = d_counts;
 	}
 	// (from pageable memory: the copies have left `blob` and `args` when they return)
 	HIPCHK(c, hipMemcpyAsync(d_lists, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, c->s_compute));
 	HIPCHK(c, hipMemcpyAsync(d_args, args.data(), args.size() * sizeof(RelateArgs), hipMemcpyHostToDevice, c->s_compute));
 	HIPCHK(c, hipMemsetAsync(d_tickets, 0, supers.size() * 8 * 4, c->s_compute));
+	Events ev;                                // per super-tile: the count's begin, its end, the epilogue's end
 	HIPCHK(c, ev.add(3 * supers.size()));
 	const uint32_t last_halves = c->opt.skip_pad ? count_last_halves(rl_words_live(n_use), W) : 0;
 	for (size_t k = 0; k < supers.size(); ++k) {
 		const RelateSuper& st = supers[k];
 		const CountWork w = count_work(d_rows, W, st.sa * P, st.sb * P, d_lists + st.table_at, st.table, d_C, st.table.g.ldc, d_tickets + k * 8, last_halves, nullptr);
-		HIPCHK(c, enqueue_count(c->s_compute, w, st.table, n_blocks, (uint32_t)TILE, ev[2 + 3 * k], k_count_list_t<COUNT_NW>));      // (the count's time starts behind the zeroing)
-		HIPCHK(c, hipEventRecord(ev[3 + 3 * k], c->s_compute));
+		HIPCHK(c, enqueue_count(c->s_compute, w, st.table, n_blocks, (uint32_t)TILE, ev[3 * k], k_count_list_t<COUNT_NW>));      // (the count's time starts behind the zeroing)
+		HIPCHK(c, hipEventRecord(ev[3 * k + 1], c->s_compute));
 		hipLaunchKernelGGL(k_relate_epilogue, dim3((st.nb + RL_EP - 1) / RL_EP, (st.na + RL_EP - 1) / RL_EP), dim3(RL_THREADS), 0, c->s_compute, (const RelateArgs*)(d_args + k));
 		HIPCHK(c, hipGetLastError());
-		HIPCHK(c, hipEventRecord(ev[4 + 3 * k], c->s_compute));
+		HIPCHK(c, hipEventRecord(ev[3 * k + 2], c->s_compute));
 	}
 	if (out) HIPCHK(c, hipMemcpy2DAsync(out, (size_t)ld * sizeof(double), d_out, (size_t)nSB * sizeof(double), (size_t)nSB * sizeof(double), nSA, hipMemcpyDeviceToHost, c->s_compute));
 	if (counts) HIPCHK(c, hipMemcpy2DAsync(counts, (size_t)ld_counts * sizeof(RelCounts), d_counts, (size_t)nSB * sizeof(RelCounts), (size_t)nSB * sizeof(RelCounts), nSA, hipMemcpyDeviceToHost, c->s_compute));
 	HIPCHK(c, hipStreamSynchronize(c->s_compute));
+	c->last.relate = CallReport();
+	c->last.relate.bytes = (uint64_t)rows_alloc * W * 4;
+	c->last.relate_planes = (int32_t)P;
+	marks.write(c->last.relate);
 	float ms = 0;
-	c->relate_last.planes = (int32_t)P; c->relate_last.plane_bytes = (uint64_t)rows_alloc * W * 4;
-	c->relate_last.transpose_ms = hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess ? ms : 0.0;
 	for (size_t k = 0; k < supers.size(); ++k) {
-		if (hipEventElapsedTime(&ms, ev[2 + 3 * k], ev[3 + 3 * k]) == hipSuccess) c->timing.count_ms += ms;
-		if (hipEventElapsedTime(&ms, ev[3 + 3 * k], ev[4 + 3 * k]) == hipSuccess) c->timing.stats_ms += ms;
+		if (hipEventElapsedTime(&ms, ev[3 * k], ev[3 * k + 1]) == hipSuccess) c->timing.count_ms += ms;
+		if (hipEventElapsedTime(&ms, ev[3 * k + 1], ev[3 * k + 2]) == hipSuccess) c->timing.stats_ms += ms;
 		c->timing.count_launches += 1; c->timing.stats_launches += 1;
 		c->timing.row_pairs += (uint64_t)supers[k].table.n_tiles() * TILE * TILE;
 	}
@@ -3733,11 +3746,8 @@ int twk_hip_relationship(twk_hip_ctx* c, const uint32_t* variants, uint32_t n_us
 }
 
 int twk_hip_relationship_last(const twk_hip_ctx* c, int32_t* planes_per_sample, double* transpose_ms, uint64_t* plane_bytes) {
-	if (!c) return TWK_HIP_E_INVALID;
-	if (planes_per_sample) *planes_per_sample = c->relate_last.planes;
-	if (transpose_ms) *transpose_ms = c->relate_last.transpose_ms;
-	if (plane_bytes) *plane_bytes = c->relate_last.plane_bytes;
-	return TWK_HIP_OK;
+	if (c && planes_per_sample) *planes_per_sample = c->last.relate_planes;
+	return last_of(c, &LastCalls::relate, {transpose_ms}, plane_bytes);
 }
 
 int twk_hip_shard_rows(uint32_t n_rows, uint32_t n_cols, int32_t triangle, uint32_t part, uint32_t n_parts,

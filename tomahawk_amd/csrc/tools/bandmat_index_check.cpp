@@ -1,7 +1,8 @@
 // The banded LD matrix's layout and index arithmetic (csrc/hip/ld_bandmat_index.h) played on the host: `make bandmat-check` builds this
 // file with g++ under AddressSanitizer and UBSan and runs it.  Per case
-//   the layout (bm_layout: two forward-moving pointers) is checked against its O(n^2) definition - the band of row u is exactly the set of
-//   variants on u's contig within the window, a contiguous range that holds u, symmetric, its ends never decreasing, row_ptr its prefix sums;
+//   the layout (bm_band_layout over bm_layout: two forward-moving pointers) is checked against its O(n^2) definition - the band of row u is
+//   exactly the set of variants on u's contig within the window, a contiguous range that holds u, symmetric, its ends never decreasing,
+//   row_ptr its prefix sums, rows[u] == {ptr[u], first[u], ptr[u + 1] - ptr[u]}, cells == ptr[n], widest the longest row;
 //   every lane of every block of every launch then goes through the kernel's own steps - live lane, the two dead-block tests, the pair
 //   rules, the slice guards, the in-band guard, direct slot, staging index, transposed write-out, mirrored slot - against an array of
 //   write counts of row_ptr[n] slots with a border on either side.
@@ -65,28 +66,29 @@ struct Board {
 };
 uint32_t pair_value(uint32_t u, uint32_t v) { if (u > v) std::swap(u, v); return u * 65536u + v + 1; }
 
-struct Layout { std::vector<uint32_t> first; std::vector<uint64_t> ptr; std::vector<BandRow> rows; };
+typedef BandLayout Layout;      // what the engine's calls lay a band out into
 
 bool window_ok(const Case& cs, uint32_t A, uint32_t B) {
 	const int64_t d = (int64_t)cs.pos[A] - (int64_t)cs.pos[B];
 	return cs.rid[A] == cs.rid[B] && (d < 0 ? -d : d) <= (int64_t)cs.w;
 }
 
-// bm_layout against the definition, in O(n^2)
+// bm_band_layout (bm_layout, and the rows, slot count and longest row made of it) against the definition, in O(n^2)
 long check_layout(const Case& cs, Layout& L) {
 	long bad = 0;
 	const uint32_t n = cs.n;
-	L.first.assign(n, 0); L.ptr.assign((size_t)n + 1, 0);
 	const uint32_t* pos = cs.pos.data() + cs.slice_a0; const uint32_t* rid = cs.rid.data() + cs.slice_a0;
-	if (!bm_layout(n, [&](uint32_t k) { return pos[k]; }, [&](uint32_t k) { return rid[k]; }, cs.w, L.first.data(), L.ptr.data())) return 1;
-	L.rows.resize(n);
+	if (!bm_band_layout(n, [&](uint32_t k) { return pos[k]; }, [&](uint32_t k) { return rid[k]; }, cs.w, L)) return 1;
+	if (L.first.size() != n || L.ptr.size() != (size_t)n + 1 || L.rows.size() != n) return 1;
 	uint64_t at = 0;
+	uint32_t longest = 0;
 	for (uint32_t u = 0; u < n; ++u) {
 		if (L.ptr[u] != at || L.ptr[u + 1] < L.ptr[u]) { ++bad; break; }
 		const uint64_t len64 = L.ptr[u + 1] - L.ptr[u];
 		if (len64 == 0 || len64 > n) { ++bad; break; }
 		const uint32_t first = L.first[u], len = (uint32_t)len64;
-		L.rows[u] = BandRow{L.ptr[u], first, len};
+		if (L.rows[u].base != L.ptr[u] || L.rows[u].first != first || L.rows[u].len != len) ++bad;      // rows[u] == {ptr[u], first[u], ptr[u + 1] - ptr[u]}
+		longest = std::max(longest, len);
 		if ((uint64_t)first + len > n || !bm_in_band(u, first, len)) ++bad;
 		for (uint32_t v = 0; v < n; ++v) {
 			const bool in = bm_in_band(v, first, len);
@@ -97,7 +99,7 @@ long check_layout(const Case& cs, Layout& L) {
 		if (u && (first < L.first[u - 1] || first + len < L.first[u - 1] + (uint32_t)(L.ptr[u] - L.ptr[u - 1]))) ++bad;      // the ends never decrease
 		at += len;
 	}
-	if (L.ptr[n] != at) ++bad;
+	if (L.ptr[n] != at || L.cells != L.ptr[n] || L.widest != longest) ++bad;
 	// symmetric
 	if (!bad) for (uint32_t u = 0; u < n; ++u) for (uint32_t v = L.first[u]; v < L.first[u] + L.rows[u].len; ++v)
 		if (!bm_in_band(u, L.rows[v].first, L.rows[v].len)) ++bad;
@@ -326,8 +328,11 @@ int main() {
 		const bool sorted = bm_layout(3, [&](uint32_t k) { return pos[k]; }, [&](uint32_t k) { return rid[k]; }, 50, first, ptr);
 		uint32_t rid2[3] = {1, 0, 0}, pos2[3] = {1, 2, 3};
 		const bool sorted2 = bm_layout(3, [&](uint32_t k) { return pos2[k]; }, [&](uint32_t k) { return rid2[k]; }, 50, first, ptr);
-		std::printf("  %-66s %s\n", "unsorted positions and contigs are refused", (sorted || sorted2) ? "BAD" : "ok");
-		if (sorted || sorted2) { std::printf("bandmat-check: layout accepted unsorted variants\n"); return 1; }
+		BandLayout L;
+		const bool sorted3 = bm_band_layout(3, [&](uint32_t k) { return pos[k]; }, [&](uint32_t k) { return rid[k]; }, 50, L);
+		const bool sorted4 = bm_band_layout(3, [&](uint32_t k) { return pos2[k]; }, [&](uint32_t k) { return rid2[k]; }, 50, L);
+		std::printf("  %-66s %s\n", "unsorted positions and contigs are refused", (sorted || sorted2 || sorted3 || sorted4) ? "BAD" : "ok");
+		if (sorted || sorted2 || sorted3 || sorted4) { std::printf("bandmat-check: layout accepted unsorted variants\n"); return 1; }
 	}
 	long bad = 0;
 	for (const Case& c : cases) bad += run_case(c) ? 1 : 0;

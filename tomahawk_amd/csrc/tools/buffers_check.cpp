@@ -2,7 +2,8 @@
 // builds this file with plain g++ and runs it.  The stub keeps the set of live pointers: releasing a pointer that is not live (a double
 // free, a free through the wrong call) fails the run at once, and so does a case that ends with a pointer still live (a leak).  The cases
 // walk what the engine does with its buffers: growing, parking, flushing, freeing at once, running out of memory with and without
-// something to reclaim, groups that share a capacity, moves, holders that are assigned over and destroyed.
+// something to reclaim, groups that share a capacity, moves, holders that are assigned over and destroyed; and a call's memory
+// (CallMemory): takes released once with the owner, a take that fails in the middle, its bytes(), a scratch buffer taken again.
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -52,6 +53,7 @@ size_t StubOps::budget = 0, StubOps::live_bytes = 0;
 template <class T> using Dev = twk::Buffer<T, StubOps>;
 template <class T> using Pinned = twk::Buffer<T, StubOps, true>;
 typedef twk::Graveyard<StubOps> Yard;
+typedef twk::CallMemory<StubOps> Call;
 
 static int n_cases = 0, n_bad = 0;
 static const char* current = "";
@@ -173,6 +175,101 @@ int main() {
 			CHECK(StubOps::live.size() == 2 && !h.a.get() && !h.b.get() && !h.h.get() && !h.alias && h.n == 0);
 		}      // the graveyard goes with two buffers still parked
 		CHECK(StubOps::live.empty());
+	});
+	run("call memory: every take released once, when the owner dies", [] {
+		const long allocs = StubOps::n_alloc, releases = StubOps::n_release;
+		{
+			Call mem;
+			int e = StubOps::broken;
+			int* a = mem.take<int>(10, &e);
+			CHECK(e == StubOps::ok && is_live(a) && StubOps::bytes_of[a] == 40);
+			double* b = mem.take<double>(7, &e);
+			CHECK(e == StubOps::ok && is_live(b) && StubOps::bytes_of[b] == 56);
+			char* z = mem.take<char>(0, &e);                                       // as reserve(0, 0): nothing wanted, nothing allocated
+			CHECK(e == StubOps::ok && !z && StubOps::n_alloc == allocs + 2);
+			Dev<char> plain;
+			CHECK(plain.reserve(0, 0, nullptr) == StubOps::ok && !plain.get() && StubOps::n_alloc == allocs + 2);
+			short* s = mem.take<short>(3, &e);
+			CHECK(e == StubOps::ok && is_live(s) && is_live(a) && is_live(b));      // (the owner's bookkeeping grew: what it handed out stays put)
+			CHECK(mem.bytes() == 40 + 56 + 0 + 6 && StubOps::live_bytes == mem.bytes());
+			CHECK(StubOps::n_alloc == allocs + 3 && StubOps::n_release == releases && StubOps::live.size() == 3);
+		}
+		CHECK(StubOps::live.empty() && StubOps::n_release == releases + 3);
+	});
+	for (const int verdict : {StubOps::out_of_memory, StubOps::broken})
+		for (int k = 1; k <= 4; ++k) run("call memory: the k-th take fails, the earlier ones stay held", [=] {
+			const long releases = StubOps::n_release;
+			{
+				Call mem;
+				void* got[4] = {nullptr, nullptr, nullptr, nullptr};
+				size_t want = 0;
+				StubOps::fail_at = k; StubOps::fail_with = verdict;
+				for (int t = 1; t <= 4; ++t) {
+					int e = StubOps::ok;
+					got[t - 1] = mem.take<long>(100 * t, &e);
+					if (t == k) { CHECK(e == verdict && !got[t - 1]); break; }
+					CHECK(e == StubOps::ok && got[t - 1]);
+					want += 100 * t * sizeof(long);
+				}
+				for (int t = 1; t < k; ++t) CHECK(is_live(got[t - 1]));
+				CHECK(StubOps::live.size() == (size_t)(k - 1) && StubOps::n_release == releases && mem.bytes() == want);
+				int e = StubOps::broken;                                                // the owner is still good for a request that can be met
+				CHECK(mem.take<char>(5, &e) && e == StubOps::ok && mem.bytes() == want + 5);
+			}
+			CHECK(StubOps::live.empty() && StubOps::n_release == releases + k);
+		});
+	// twk_hip_ld_blocks as the source before CallMemory allocated (twk_hip.hip, `hold_for_call` lines of that entry point): ten buffers in
+	// front of the launches - two prefix-count bands, counts3, blk, pos, flat, off, block_of, used, the scan's scratch -, the bounds' three
+	// (band map, upper, lower), six for the candidates (keys, keys_out, vals, vals_out, cs, cr), and the scratch once more where the sort
+	// needs more of it than the scan did: 20 allocations (the outgrown scratch freed at once, so 19 live), 19 where it does not
+	for (const bool sort_needs_more : {true, false}) run("call memory: a blocks-like call, scan scratch then sort scratch", [=] {
+		const long allocs = StubOps::n_alloc, releases = StubOps::n_release;
+		{
+			Call mem;
+			int e = StubOps::ok;
+			const size_t n = 300, cells = 9000, M = 400, q = 1234, scan_tmp = 2048, sort_tmp = sort_needs_more ? 40000 : 1024;
+			for (int t = 0; t < 2; ++t) CHECK(mem.take<unsigned>(cells, &e) && e == StubOps::ok);
+			for (int t = 0; t < 2; ++t) CHECK(mem.take<unsigned>(n * 3, &e) && e == StubOps::ok);
+			for (int t = 0; t < 3; ++t) CHECK(mem.take<unsigned>(n, &e) && e == StubOps::ok);
+			CHECK(mem.take<unsigned>(M, &e) && e == StubOps::ok);
+			CHECK(mem.take<unsigned long long>((n + 63) / 64, &e) && e == StubOps::ok);
+			char* tmp = mem.take<char>(scan_tmp, &e);
+			CHECK(tmp && e == StubOps::ok && StubOps::n_alloc == allocs + 10);
+			CHECK(mem.take<long>(n, &e) && e == StubOps::ok);                       // the band map (a BandRow is 16 bytes; the size is not the point)
+			for (int t = 0; t < 2; ++t) CHECK(mem.take<unsigned char>(cells, &e) && e == StubOps::ok);
+			for (int t = 0; t < 2; ++t) CHECK(mem.take<unsigned long long>(q, &e) && e == StubOps::ok);
+			for (int t = 0; t < 4; ++t) CHECK(mem.take<unsigned>(q, &e) && e == StubOps::ok);
+			const size_t before = mem.bytes();
+			char* tmp2 = mem.retake(tmp, std::max(scan_tmp, sort_tmp), &e);
+			CHECK(tmp2 && e == StubOps::ok && is_live(tmp2));
+			if (sort_needs_more) CHECK(StubOps::bytes_of[tmp2] == sort_tmp && mem.bytes() == before + sort_tmp - scan_tmp && StubOps::n_release == releases + 1);
+			else CHECK(tmp2 == tmp && mem.bytes() == before && StubOps::n_release == releases);
+			CHECK(StubOps::n_alloc == allocs + (sort_needs_more ? 20 : 19) && StubOps::live.size() == 19 && StubOps::live_bytes == mem.bytes());
+		}
+		CHECK(StubOps::live.empty() && StubOps::n_release == releases + (sort_needs_more ? 20 : 19));
+	});
+	run("call memory: a retake that fails leaves its buffer empty and the others held", [] {
+		Call mem;
+		int e = StubOps::ok;
+		int* a = mem.take<int>(4, &e); char* tmp = mem.take<char>(100, &e);
+		StubOps::fail_at = 1;
+		CHECK(!mem.retake(tmp, (size_t)500, &e) && e == StubOps::out_of_memory);
+		CHECK(is_live(a) && StubOps::live.size() == 1 && mem.bytes() == 16);
+	});
+	// twk_hip_ld_split: bytes() of its takes against the closed form twk_hip_split_last has reported since the call exists
+	run("call memory: a split-like call's bytes() is the closed form", [] {
+		Call mem;
+		int e = StubOps::ok;
+		const size_t n = 300, cells = 9000, widest = 17, min_size = 5, max_size = 40, k_max = 12, n1 = n + 1;
+		const size_t rp = widest * n, w = (max_size - min_size + 1) * n1, d = k_max * n1, cut = k_max * (k_max + 1);
+		mem.take<long long>(rp, &e); mem.take<long long>(w, &e); mem.take<unsigned short>(d, &e); mem.take<long long>(2 * n1, &e);
+		mem.take<long long>(n, &e); mem.take<unsigned>(n, &e); mem.take<long long>(k_max + 1, &e); mem.take<unsigned long long>(k_max, &e);
+		mem.take<unsigned>(cut, &e); mem.take<unsigned char>(k_max, &e); mem.take<unsigned long long>(1, &e); mem.take<unsigned>(1, &e);
+		mem.take<float>(cells, &e);
+		struct Row16 { unsigned long long base; unsigned first, len; };
+		mem.take<Row16>(n, &e);
+		CHECK(e == StubOps::ok);
+		CHECK(mem.bytes() == cells * 4 + n * 16 + (rp + w + 2 * n1 + n + k_max + 1) * 8 + d * 2 + n * 4 + k_max * 9 + cut * 4 + 12);
 	});
 	std::printf("%d cases, %d bad\n", n_cases, n_bad);
 	return n_bad ? 1 : 0;
