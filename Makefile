@@ -126,7 +126,8 @@ count-check:
 # The two-product form's host side (csrc/tools/two_check.cpp): its screens (csrc/hip/ld_two_screen.h: the H plane or the carrier plane H | Q as the
 # row operand, or one product of the two variants' carrier planes) over every small genotype table, plan_one_end on random sorted margins, and the
 # work table of a launch with one plane row per row variant and two per column variant against a naive restatement and the recorded order of
-# tests/golden/count_tables_two.json: host code only, under AddressSanitizer and UBSan
+# tests/golden/count_tables_two.json; the fine walk's carrier screen (QQ <= min(qA, qB, CQ)) between three products and the carrier screen:
+# host code only, under AddressSanitizer and UBSan
 two-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/two_check.cpp -o build/two_check
@@ -136,7 +137,9 @@ two-check:
 # small suffix genotype table, the work table with per-tile stops (csrc/hip/ld_count_table.h) against a naive restatement and against the table
 # built without stops, and the planner's stops (csrc/hip/ld_plan.h) on the headline's frequency law - once with the H plane and once with the
 # carrier plane as the two-product launches' row operand; the grid of 128 stops against a naive restatement for rows of 1 .. 2,000 chunks, the
-# screens at every fine stop, and the planner at four settings of grid and margin: host code only, under AddressSanitizer and UBSan
+# screens at every fine stop, and the planner at four settings of grid and margin; the fine walk (option "walk_fine"): its carrier prefix screen
+# between three products and the carrier screen, the planner's report with and without it, and its plans on random margins - every pair in exactly
+# one launch and on its side of the staircase: host code only, under AddressSanitizer and UBSan
 prefix-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/prefix_check.cpp -o build/prefix_check

@@ -891,6 +891,19 @@ int twk_hip_plan_region_two_form(const twk_hip_plan_env* env, const twk_hip_vari
                                  twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                                  uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end);
 
+/* ... and with the fine walk (option "walk_fine"; read only with carrier != 0): fine != 0: the cut is asked of the carrier screen that holds QQ to
+ * min(qA, qB, CQ), a block in front of the cut has its one_end per tile row of 128 variants - a staircase: its one-product launches list the tiles in
+ * front of it, its two-product launches the tiles behind it - and the blocks of the rows [*two_end, *two_last) take a two-product launch from the
+ * diagonal to their rows' two_reach and three products behind it.  notes (may be NULL; `capacity` entries): per launch, bits 0-1: 0 the whole
+ * rectangle, 1 the columns in front of its rows' staircase border, 2 those from it on; bit 2: a two-product launch behind the cut.  stair (may be
+ * NULL; nA entries): the border of row a0 + r, relative to b0 (0: none).  fine == 0: twk_hip_plan_region_two_form. */
+int twk_hip_plan_region_walk(const twk_hip_plan_env* env, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                             int32_t carrier, int32_t one, uint32_t one_rows, int32_t fine, uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                             uint32_t tile_variants, int32_t window, uint32_t l_window,
+                             twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                             uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end,
+                             uint32_t* two_last, uint8_t* notes, uint32_t* stair);
+
 /* Fisher's exact test on n caller-supplied 2x2 tables (tables[4*i + {0,1,2,3}] = n11, n12, n21, n22), two-sided P
  * into p_two_sided[i]: kt_fisher_exact (lib/fisher_math.cpp:231-267) as the pair math calls it
  * (ld_engine.cpp:1222-1226, :1656-1658), through the engine's own Fisher kernels: the reference's walk, one table per

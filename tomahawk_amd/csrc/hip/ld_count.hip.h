@@ -860,10 +860,14 @@ struct ScreenWork {
 	float slack;                       // 0.5 + T 2^-20 counts: four times the worst rounding of the prefilter's left side
 	// A prefix launch (the matrix screens of ld_three.hip.h only): pre_stops[ty * pre_gx + tx] = the grid index (ld_two_screen.h
 	// prefix_stop_chunks) of the stop of the tile that holds row variant i = ty * pre_tvA + .. and column variant j = tx * 64 + ..; pre_suffix
-	// [plane row][PREFIX_GRID]: the rows' suffix popcounts (k_row_suffix_popcount).  pre_stops == null: every tile over its whole rows.
+	// [grid point][plane row of pre_rows]: the rows' suffix popcounts, grid-major (k_row_suffix_popcount, k_suffix_grid_major) - the 64 column variants of a
+	// tile share its grid point, so a wave reads its 128 column margins from 512 consecutive bytes.  pre_stops == null: every tile over its whole rows.
 	const uint8_t* pre_stops; const uint32_t* pre_suffix;
 	uint32_t pre_gx, pre_tvA, pre_nchunks;
 	uint32_t carrier;                  // k_screen2_pairs: the matrix is (CH, CQ) of a launch whose row operand was the carrier plane (ld_two_screen.h: screen2c_*)
+	uint32_t pre_rows;                 // plane rows of pre_suffix (the set's rows_alloc)
+	const uint32_t* col_lo;            // the matrix screens of ld_three.hip.h only: row at set position a holds the columns >= hi_b0 + col_lo[a - hi_a0] (hi_n entries; null: no limit)
+	uint32_t fine;                     // ... and its screen holds QQ to min(qA, qB, CQ) (the fine walk; ld_two_screen.h: screen2c_slack_cq)
 };
 // -> terms[] of ScreenWork for n_pos set positions (P = 1: rowpop[pos]; P = 2: rowpop[2 pos] + 2 rowpop[2 pos + 1])
 __global__ void k_screen_terms(const uint32_t* __restrict__ rowpop, uint32_t n_pos, int P, double two_n, double cut, float4* __restrict__ terms) {

@@ -91,6 +91,8 @@ inline void fill_unit_tiles(Vec& units, const uint32_t* tiles) { for (auto& u : 
 // Window mode: row variant a0 + r of a region reaches the columns [b0 + lo[r], b0 + hi[r]).
 struct ColRange { const uint32_t* lo = nullptr; const uint32_t* hi = nullptr; uint32_t a0 = 0, b0 = 0;
                   const uint32_t* d_hi = nullptr; uint32_t n_hi = 0;      // d_hi: device copy of hi, n_hi entries (r2 screen: the math kernel skips what was not contracted)
+                  const uint32_t* d_lo = nullptr;      // ... of lo, n_hi entries (the fine walk's launches behind a staircase: the screens skip what was not contracted)
+                  bool falling = false;                // the ranges fall along the rows of a block (a staircase of the fine walk) instead of rising (window, band)
                   uint32_t list_zone = 0;              // pairs with both set positions below it are intersected as carrier lists (ld_list.hip.h), not contracted
                   uint32_t probe_zone = 0; };          // <= list_zone: every other pair of a row below it is decided by probing the column's row with the row's carriers (k_probe_screen)
 
@@ -121,7 +123,10 @@ inline void build_tile_list(const twk_hip_tile_desc& t, int P, const Geometry& g
 			const uint32_t v0 = t.rowA0 + (by * TILE) / PA;
 			const uint32_t v1 = std::min<uint64_t>((uint64_t)t.rowA0 + t.nA, (uint64_t)t.rowA0 + ((uint64_t)(by + 1) * TILE + PA - 1) / PA);   // exclusive
 			if (v0 >= v1) { x1[by] = x0[by]; continue; }
-			const uint64_t c_lo = (uint64_t)cr->b0 + cr->lo[v0 - cr->a0], c_hi = (uint64_t)cr->b0 + cr->hi[v1 - 1 - cr->a0];   // variants [c_lo, c_hi)
+			// (window and band mode: the ranges rise along the rows.  Down a staircase of the fine walk they fall - ColRange::falling - and a sample or a
+			// strip of such a launch starts anywhere in a step: the tile row's last row then holds the smallest lo and its first row the largest hi)
+			const uint64_t c_lo = (uint64_t)cr->b0 + cr->lo[(cr->falling ? v1 - 1 : v0) - cr->a0];
+			const uint64_t c_hi = (uint64_t)cr->b0 + cr->hi[(cr->falling ? v0 : v1 - 1) - cr->a0];   // variants [c_lo, c_hi)
 			const uint64_t lo = std::max<uint64_t>(c_lo, t.rowB0), hi = std::min<uint64_t>(c_hi, (uint64_t)t.rowB0 + t.nB);
 			if (hi <= lo) { x1[by] = x0[by]; continue; }
 			x0[by] = std::max<uint32_t>(x0[by], (uint32_t)(((lo - t.rowB0) * P) / TILE));

@@ -108,6 +108,16 @@ inline FormGrant step_down(const LaunchForm& was, FormGrant given) {
 // What the running call has not yet given up: a region call owns one for all its stages, the single-tile entry a fresh one.
 struct CallForms {
 	bool fused = true, three = true, two = true, prefix = true, one = true;
+	bool two_behind = true;      // the two-product launches behind the walk's cut (below: behind_wants, behind_overflowed)
+	// ... what a launch behind the cut may still want
+	LaunchWants behind_wants(LaunchWants w) const { if (!two_behind) w.two = w.one = false; return w; }
+	// ... such a launch, of form `was` under `given`, whose candidate list overflowed: the call gives up those launches and no other form, and the tile is
+	// redone with three products over whole rows -> the grant of that
+	FormGrant behind_overflowed(FormGrant given) {
+		two_behind = false;
+		given.two = given.carrier = given.one = given.prefix = false;
+		return given;
+	}
 	// ... and allows a launch, whose owner wants three / two products for it (and stops for its tiles)
 	// (the carrier plane is no form of the call's to give up: it goes where the two-product form goes)
 	// (one product is: a launch that overflows or is too rich in that form ends it for the call, and nothing else)
@@ -140,6 +150,16 @@ struct CallForms {
 		if (too_rich && was.three && !was.keep_three) three = three && !given.three;
 	}
 };
+
+// ---- the two-product launches behind the walk's cut (the fine walk; ld_plan.h LaunchNote::behind) --------------------------------------------------
+// A form of the call's of its own: a refused sample or an overflowing list of such a launch ends them for the rest of the call, and nothing else - the
+// launches in front of the cut keep their two products.  CallForms::two_behind holds it; behind(i): launch i is one of them.
+// ... after the samples (decide_wants, option two = 1): a launch behind the cut whose own sample did not leave it two products -> true: none of them takes it
+template <class Behind>
+bool behind_refused(const std::vector<LaunchWants>& wants, Behind behind) {
+	for (size_t i = 0; i < wants.size(); ++i) if (behind(i) && !wants[i].two) return true;
+	return false;
+}
 
 // ---- the numbers that decide a launch's fate, side by side ---------------------------------------------------------------------------------
 // A sample is poor in candidates - its launch takes the form the sample ran in - if at most 1 pair in `one_in` of it is a candidate ...
@@ -184,6 +204,9 @@ struct LadderFacts {
 	bool three_possible = false;      // some launch of the region would take three products (none: nothing to sample)
 	bool fused = false;               // the region's launches fuse
 	bool carrier = false;             // the region's two-product launches contract the carrier plane: wanted for every launch, and for every sample
+	// The fine walk's plan (ld_plan.h plan_two_stairs) has two-eligible launches behind the cut, between three-product ones: such a launch is sampled by
+	// itself wherever it lies - a step of several launches ends in front of it - so that none is left to follow a neighbour in another form.
+	bool eligible_interleaved = false;
 };
 // two_eligible(i): launch i lies in front of the walk's cut (option two = 2: every launch of the walk); planned_one(i): the planner marked it for one
 // product; sample(pick, as) runs launch pick's sample in the form `as` (CallForms::sample_grant) -> SampleOutcome; mark(what, i, x): the timeline log.
@@ -200,8 +223,10 @@ int decide_wants(size_t n, const LadderFacts& x, Eligible two_eligible, PlannedO
 	size_t n_front = 0;
 	if (x.opt_two == 1) while (n_front < n && two_eligible(n_front)) ++n_front;
 	const size_t step_behind = std::max<size_t>(1, (n - n_front + 63) / 64);
+	auto own_sample = [&](size_t i) { return x.eligible_interleaved && x.opt_two == 1 && two_eligible(i); };
 	for (size_t i0 = 0, step = 1; i0 < n; i0 += step) {
-		step = i0 < n_front ? 1 : step_behind;
+		step = (i0 < n_front || own_sample(i0)) ? 1 : step_behind;
+		for (size_t k = i0 + 1; k < i0 + step && k < n; ++k) if (own_sample(k)) { step = k - i0; break; }
 		const size_t pick = std::min(n - 1, i0 + step / 2), i1 = std::min(n, i0 + step);
 		const bool front = x.opt_two == 1 && two_eligible(pick), try_two = front || (x.opt_two == 2 && out[pick].two);
 		LaunchWants as = unsampled; as.one = out[pick].one;

@@ -9,6 +9,7 @@
 #include <vector>
 #include "../../../include/twk_hip.h"
 #include "ld_two_screen.h"
+#include "ld_count_table.h"
 
 namespace twk {
 
@@ -39,11 +40,21 @@ struct PlanEnv {                                    // what the planner needs to
 	// ... and, in front of the cut, one product a pair where the screen's lower test is decided by the dosages alone (plan_one_tiles): only with `carrier`.
 	// one_rows: the height of those rows' blocks in variants (a multiple of 128; 0: the default, plan_one_rows)
 	bool one = false; uint32_t one_rows = 0;
+	// ... the fine walk (option "walk_fine", twk_hip.hip walk_fine_applies): the carrier screen's upper value with the counted CQ in its min
+	// (ld_two_screen.h screen2c_slack_cq) - the cut is asked of that screen - and stops without the spare grid step (plan_prefix_tile_grid)
+	bool fine = false;
+	// ... and staircase borders inside a row block (plan_one_tiles, plan_two_stairs): only with `fine`, `carrier` and launches through a matrix.
+	// stair_behind: also behind the cut (the caller takes it back where it has no carrier rows for those row variants)
+	bool stair_behind = true;
 	// options
 	bool band_launch = true, band_reverse = true; long long band_work_log2 = 19, band_max_launches = 8, band_list_entries = 0;
 	const twk_hip_variant_meta& at(uint32_t i) const { return meta[ids ? ids[i] : i]; }
 };
 struct BandLaunch { uint32_t xa, xb; size_t list_words; size_t tile_index; };
+// What the plan says of a launch besides its rectangle.  side: the launch holds, of each of its rows, the columns on one side of the row's staircase
+// border RegionPlan::stair - 1: [.., stair), 2: [stair, ..) - and no tile outside it is contracted or screened (0: the whole rectangle).
+// behind: a two-product launch over rows behind the cut, from the diagonal to the rows' two_reach (plan_two_stairs).
+struct LaunchNote { uint8_t side = 0, behind = 0; };
 struct RegionPlan {
 	bool windowed = false;
 	std::vector<uint32_t> lo, hi;                   // windowed: row a0 + r reaches the columns [b0 + lo[r], b0 + hi[r])
@@ -54,6 +65,39 @@ struct RegionPlan {
 	std::vector<BandLaunch> bands;
 	uint64_t pairs = 0;                             // pairs the shard decides
 	uint32_t two_end = 0;                           // the two-product walk: launches over rows below it (a multiple of the tile edge) lie wholly in front of r*
+	// the fine walk's staircases: the border of row a0 + r is the column b0 + stair[r], the same for the 128 rows of a tile row counted from their
+	// block's first row, and never rises along the rows of a block (empty: no launch has a side; 0: a row without one)
+	std::vector<uint32_t> stair;
+	std::vector<LaunchNote> notes;                  // per launch of `mine`
+	uint32_t two_last = 0;                          // ... rows [two_end, two_last) have a two-product launch from the diagonal to their two_reach (two_end: none)
+	void note_last(uint8_t side, uint8_t behind) { notes.resize(mine.size()); if (!notes.empty()) { notes.back().side = side; notes.back().behind = behind; } }
+	// the columns [lo, hi) (set positions) of launch i that row `row` (a set position inside it) holds
+	void launch_cols(const PlanGeom& g, size_t i, uint32_t row, uint32_t& lo, uint32_t& hi) const {
+		const twk_hip_tile_desc& t = mine[i];
+		lo = t.rowB0; hi = t.rowB0 + t.nB;
+		if (t.diag && t.rowA0 == t.rowB0) lo = std::max(lo, row + 1);
+		const uint8_t side = i < notes.size() ? notes[i].side : 0;
+		if (side == 1) hi = std::min(hi, g.b0 + stair[row - g.a0]);
+		if (side == 2) lo = std::max(lo, g.b0 + stair[row - g.a0]);
+		if (hi < lo) hi = lo;
+	}
+};
+
+// The column ranges of a plan's staircase launches as build_tile_list and the screens take them (ld_count_table.h ColRange): in front of the border
+// [0, stair), behind it [stair, nB).  d_stair: the device copy of RegionPlan::stair for the screens (null: host only - the planner's tools).
+struct StairRanges {
+	std::vector<uint32_t> zero, end; ColRange left, right;
+	void set(const RegionPlan& p, const PlanGeom& g, const uint32_t* d_stair) {
+		if (p.stair.size() != g.nA) return;
+		zero.assign(g.nA, 0); end.assign(g.nA, g.nB);
+		left.lo = zero.data(); left.hi = p.stair.data(); left.d_hi = d_stair;
+		right.lo = p.stair.data(); right.hi = end.data(); right.d_lo = d_stair;
+		left.a0 = right.a0 = g.a0; left.b0 = right.b0 = g.b0; left.n_hi = right.n_hi = g.nA; left.falling = right.falling = true;
+	}
+	const ColRange* of(const RegionPlan& p, size_t i, const ColRange* other = nullptr) const {
+		const uint8_t side = i < p.notes.size() ? p.notes[i].side : 0;
+		return side == 1 ? &left : side == 2 ? &right : other;
+	}
 };
 
 inline uint32_t plan_round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
@@ -343,7 +387,7 @@ inline uint32_t plan_two_end(const PlanEnv& e, const PlanGeom& g) {
 		for (uint32_t k = 0; k < n_ask && !kept; ++k) {
 			const uint32_t j = first + (uint32_t)(((uint64_t)(k + 1) * n_behind) / n_ask) - 1;
 			const ScreenMargins m{e.het[g.a0 + r], e.hom[g.a0 + r], e.het[g.b0 + j], e.hom[g.b0 + j]};
-			kept = e.carrier ? screen2c_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin)
+			kept = e.carrier ? screen2c_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin, e.fine)
 			                 : screen2_expected_keeps(m, (double)e.n_samples, two_n, cut, e.two_margin);
 		}
 		if (kept) break;
@@ -383,7 +427,14 @@ inline uint32_t plan_one_rows(const PlanEnv& e, uint32_t S) {
 // block's last row's, rounded down to a whole number of 128 variants from the diagonal and never before the block's own end; a block whose own
 // pairs do not all pass the lower test (two very rare variants; a block that straddles the boundary) has no one-product launch.  A launch's
 // rectangle is one whose count matrix stays within 2 GiB also when it is redone with four products, as for every other launch.
-inline void plan_one_tiles(const PlanEnv& e, const PlanGeom& g, const RegionPlan& p, uint32_t xa, uint32_t xb, std::vector<twk_hip_tile_desc>& out) {
+// The fine walk (PlanEnv::fine): the border is asked once per tile row of 128 variants, at that tile row's last row, and rounded down to 128 variants
+// from the block's first column - a staircase that never rises along the block's rows and ends at the block's own border of before.  The one-product
+// launches are then the rectangle [diagonal, the first tile row's border) and list, per tile row, the tiles in front of that tile row's border; the
+// two-product launches are the rectangle [the last tile row's border, nB) and list the tiles behind it (RegionPlan::stair, LaunchNote::side).  A block
+// whose tile rows' answers would rise (two very rare variants) keeps the one border.
+inline void plan_block_launches(const PlanEnv& e, const PlanGeom& g, RegionPlan& p, uint32_t x, uint32_t h, uint32_t col_first, uint32_t col_last, bool left_one, uint8_t behind);
+inline void plan_one_tiles(const PlanEnv& e, const PlanGeom& g, RegionPlan& p, uint32_t xa, uint32_t xb) {
+	std::vector<twk_hip_tile_desc>& out = p.mine;
 	const uint32_t H = plan_one_rows(e, p.S), nB = g.nB;
 	for (uint32_t x = xa; x < xb; x += H) {
 		const uint32_t h = std::min(H, xb - x), last = x + h - 1;
@@ -391,6 +442,23 @@ inline void plan_one_tiles(const PlanEnv& e, const PlanGeom& g, const RegionPlan
 		if (last + 1 < nB && (h < 2 || plan_one_lower_ok(e, g, x, x + 1))) {
 			const uint32_t end = plan_one_end(e, g, last);
 			if (end >= std::min(x + h, nB) && end > last + 1) w = end >= nB ? nB - x : std::max(h, (end - x) / PLAN_TILE * PLAN_TILE);
+		}
+		if (w && e.fine && !e.fused && h > PLAN_TILE && x + w < nB) {      // (a block of one tile row, or one that reaches the last column, has no staircase)
+			const uint32_t n_ty = (h + PLAN_TILE - 1) / PLAN_TILE;
+			std::vector<uint32_t> s(n_ty, x + w);
+			bool ok = true;
+			for (uint32_t ty = 0; ty + 1 < n_ty && ok; ++ty) {
+				const uint32_t end = plan_one_end(e, g, x + (ty + 1) * PLAN_TILE - 1);
+				s[ty] = end >= nB ? nB : x + (end - x) / PLAN_TILE * PLAN_TILE;
+				if (ty) s[ty] = std::min(s[ty], s[ty - 1]);
+				ok = s[ty] >= x + w;
+			}
+			if (ok && s[0] > x + w) {
+				p.stair.resize(g.nA, 0);
+				for (uint32_t r = 0; r < h; ++r) p.stair[x + r] = s[r / PLAN_TILE];
+				plan_block_launches(e, g, p, x, h, s[0], x + w, true, 0);
+				continue;
+			}
 		}
 		const uint64_t rows = plan_round_up(h, PLAN_TILE);
 		const uint32_t w_max = (uint32_t)std::max<uint64_t>(h, std::min<uint64_t>(32768, ((1ull << 27) / rows) / PLAN_TILE * PLAN_TILE));
@@ -411,13 +479,91 @@ inline void plan_one_tiles(const PlanEnv& e, const PlanGeom& g, const RegionPlan
 	}
 }
 
+// The launches of a block of rows [x, x + h) with a staircase (RegionPlan::stair filled for its rows): the rectangle [x, col_first) - col_first the
+// first tile row's border, the largest - as launches of side 1, the first of them on the diagonal, and the rectangle [col_last, nB) - col_last the last
+// tile row's border - as launches of side 2; each rectangle one whose count matrix stays within 2 GiB also when it is redone with four products.
+// left_one: the left launches are planned for one product (in front of the cut); behind: they are the two-product launches behind the cut.
+inline void plan_block_launches(const PlanEnv& e, const PlanGeom& g, RegionPlan& p, uint32_t x, uint32_t h, uint32_t col_first, uint32_t col_last, bool left_one, uint8_t behind) {
+	const uint32_t nB = g.nB;
+	const uint64_t rows = plan_round_up(h, PLAN_TILE);
+	const uint32_t w_max = (uint32_t)std::max<uint64_t>(h, std::min<uint64_t>(32768, ((1ull << 27) / rows) / PLAN_TILE * PLAN_TILE));
+	uint32_t col = x;
+	for (bool diag = true; col < col_first; diag = false) {
+		uint32_t wl = std::min(w_max, col_first - col);
+		if (diag && wl < h) wl = std::min(h, nB - col);      // (the diagonal launch spans its own rows)
+		const size_t before = p.mine.size();
+		plan_push_tile(e, g, p.mine, x, h, col, wl, diag ? 1 : 0);
+		if (p.mine.size() > before) { p.mine.back().one = left_one ? 1 : 0; p.note_last(1, behind); }
+		col += wl;
+	}
+	if (col_last < nB) {
+		const uint32_t rest = nB - col_last, n_l = (rest + w_max - 1) / w_max, step = plan_round_up((rest + n_l - 1) / n_l, PLAN_TILE / 2);
+		for (col = col_last; col < nB; col += step) {
+			const size_t before = p.mine.size();
+			plan_push_tile(e, g, p.mine, x, h, col, std::min(step, nB - col), 0);
+			if (p.mine.size() > before) p.note_last(2, 0);
+		}
+	}
+}
+
+// ---- two products behind the cut -------------------------------------------------------------------------------
+// Behind two_end a row fails the planner's question against *some* column - the commonest - and still passes against the columns next to it: with
+// QQ <= min(qA, qB, CQ) a row at p = 0.25 passes against columns near 0.25 and fails against 0.5.  two_reach(row): the first column behind the row at
+// which the carrier screen, asked as plan_two_end asks it, keeps the pair (nB: none; row + 1: at once) - a binary search, the answer moving one way
+// along the columns.
+inline bool plan_two_keeps(const PlanEnv& e, const PlanGeom& g, uint32_t row, uint32_t col) {
+	const ScreenMargins m{e.het[g.a0 + row], e.hom[g.a0 + row], e.het[g.b0 + col], e.hom[g.b0 + col]};
+	return screen2c_expected_keeps(m, (double)e.n_samples, 2.0 * (double)e.n_samples, e.minR2 * (1.0 - 1e-6), e.two_margin, e.fine);
+}
+inline uint32_t plan_two_reach(const PlanEnv& e, const PlanGeom& g, uint32_t row) {
+	uint32_t lo = std::min(row + 1, g.nB), hi = g.nB;
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (!plan_two_keeps(e, g, row, mid)) lo = mid + 1; else hi = mid;
+	}
+	return lo;
+}
+// The rows [xa, xb) behind the cut, in blocks of S (option "one_rows" set: of that many rows, 256 at least - the test hook): per tile row of 128 variants the border is the smaller of its first and its last row's two_reach,
+// rounded down to 128 variants from the block's first column and never rising along the block.  While every tile row's border lies behind the tile
+// row's own columns, and its last row still passes against the column next to it, the block takes a two-product launch over [diagonal, border) - carrier rows as the row operand - and three products behind it; the
+// first block in which some tile row's does not ends that: two_last is its first such row, and the rows from there on are planned as before.  A guide like
+// the cut itself: every launch is sampled in its form, and a two-product launch that is refused or overflows is redone with three products.
+inline uint32_t plan_two_stairs(const PlanEnv& e, const PlanGeom& g, RegionPlan& p, uint32_t xa, uint32_t xb) {
+	uint32_t x = xa;
+	const uint32_t H = e.one_rows ? plan_round_up(std::max<uint32_t>(e.one_rows, 2 * PLAN_TILE), PLAN_TILE) : p.S, h_min = e.one_rows ? PLAN_TILE : 4 * PLAN_TILE;
+	for (; x < xb; x += H) {
+		const uint32_t h = std::min(H, xb - x), n_ty = (h + PLAN_TILE - 1) / PLAN_TILE;
+		if (x + PLAN_TILE >= g.nB) break;
+		std::vector<uint32_t> s(n_ty);
+		uint32_t n_ok = 0;      // tile rows whose border lies behind their own columns
+		for (uint32_t ty = 0; ty < n_ty; ++ty, ++n_ok) {
+			const uint32_t first = x + ty * PLAN_TILE, end_row = std::min(x + h, first + PLAN_TILE);
+			const uint32_t reach = std::min(plan_two_reach(e, g, first), plan_two_reach(e, g, end_row - 1));
+			s[ty] = reach >= g.nB ? g.nB : x + (reach > x ? (reach - x) / PLAN_TILE * PLAN_TILE : 0);
+			if (ty) s[ty] = std::min(s[ty], s[ty - 1]);
+			if (s[ty] < first + PLAN_TILE) break;
+			// ... and the tile row's last row passes against its own first column: a border that only equals the tile row's end says nothing of the
+			// pairs inside its diagonal tile, of which that one is the hardest (two_last: the first row whose own first column fails)
+			if (end_row < g.nB && plan_two_keeps(e, g, end_row - 1, end_row)) break;
+		}
+		// (a block is cut where its tile rows stop reaching: the rows in front keep their staircase, if they are worth a launch of their own)
+		const uint32_t h_ok = n_ok == n_ty ? h : n_ok * PLAN_TILE;
+		if (h_ok < std::min<uint32_t>(h, h_min) || h_ok == 0) break;
+		p.stair.resize(g.nA, 0);
+		for (uint32_t r = 0; r < h_ok; ++r) p.stair[x + r] = s[r / PLAN_TILE];
+		plan_block_launches(e, g, p, x, h_ok, s[0], s[(h_ok - 1) / PLAN_TILE], false, 1);
+		if (h_ok < h) { x += h_ok; break; }
+	}
+	return std::min(x, xb);
+}
+
 // ---- the prefix contraction's stops ---------------------------------------------------------------------------
 // A tile of a two- or three-product launch of the two-product walk is contracted over the chunks [0, stop) only; the screen bounds what it did
 // not read by the rows' suffix margins (ld_two_screen.h).  The stop of a tile: for a small fixed set of its variant pairs - the four corners
 // and the middle - the smallest point of the fine grid (ld_two_screen.h prefix_stop_chunks) at which the pair, at its independence
 // expectation, is dropped by either of two questions: the screen with the square root of its bound shrunk to `margin` of it
 // (prefix_expected_keeps), or the screen itself with the expected counts moved outwards by `sigma` standard deviations of theirs
-// (prefix_sigma_keeps; sigma 0: the first question alone).  The largest of those, plus one fine step.  Expected prefix counts come from the
+// (prefix_sigma_keeps; sigma 0: the first question alone).  The largest of those, plus one fine step (none on the fine walk with sigma > 0).  Expected prefix counts come from the
 // real prefix margins and the suffix term from the real suffix margins, so a file whose carriers crowd its last samples gets later stops by
 // itself.  A guide and no guarantee: the launch's sample decides whether the stops are taken, and what the wider screen keeps is recounted.
 struct PrefixEnv {
@@ -428,6 +574,7 @@ struct PrefixEnv {
 	uint32_t fixed_grid = 0;                                           // test hooks "prefix_stop", "prefix_substop": this fine index for every tile (0: the planner's)
 	bool carrier = false;                                              // a two-product launch's row operand is the carrier plane (PlanEnv::carrier)
 	bool one = false;                                                  // ... and the launch contracts one product a pair (LaunchForm::one): the one-product questions
+	bool fine = false;                                                 // the fine walk (PlanEnv::fine): the carrier questions with CQ in the min, and no spare step behind a sigma answer
 	uint64_t samples_before(uint32_t f) const { return std::min<uint64_t>((uint64_t)prefix_stop_chunks(f, nchunks) * 32u * 32u, n_samples); }
 	bool dropped(bool two, uint32_t vA, uint32_t vB, uint32_t f) const {
 		if (f >= PREFIX_GRID) return true;       // (whole rows: the screen itself decides)
@@ -439,8 +586,8 @@ struct PrefixEnv {
 			if (!prefix_expected_keeps_one(m, x, n_pre, two_n, cut, margin)) return true;
 			return sigma > 0 && !prefix_sigma_keeps_one(m, x, n_pre, two_n, cut, sigma);
 		}
-		if (!(two && carrier ? prefix_expected_keeps_carrier(m, x, n_pre, two_n, cut, margin) : prefix_expected_keeps(m, x, two, n_pre, two_n, cut, margin))) return true;
-		return sigma > 0 && !prefix_sigma_keeps(m, x, two, two && carrier, n_pre, two_n, cut, sigma);
+		if (!(two && carrier ? prefix_expected_keeps_carrier(m, x, n_pre, two_n, cut, margin, fine) : prefix_expected_keeps(m, x, two, n_pre, two_n, cut, margin))) return true;
+		return sigma > 0 && !prefix_sigma_keeps(m, x, two, two && carrier, n_pre, two_n, cut, sigma, fine);
 	}
 	// smallest fine index in [1, PREFIX_GRID] at which the pair is dropped, walked from `hint` (the answer of a neighbouring tile: two or
 	// three questions instead of a search - both inequalities move one way along the row)
@@ -470,6 +617,9 @@ inline uint32_t plan_prefix_tile_grid(const PrefixEnv& e, bool two, uint32_t a_l
 		if (e.dropped(two, pa[k], pb[k], need)) hint[k] = std::min(hint[k], need);      // (an upper bound of its answer: it only picks the pair walked next time)
 		else need = hint[k] = e.pair_need(two, pa[k], pb[k], need);
 	}
+	// The fine walk with the sigma question on: the answer itself.  The spare step dates from the margin question alone; behind six standard deviations
+	// it is about five more (1 / 128 of a row of a million samples: ~2,900 counts of S against sigma ~550), and a miss costs one recount.
+	if (e.fine && e.sigma > 0) return std::min<uint32_t>(need, PREFIX_GRID);
 	// (one fine step of chunks, not of indices: on short rows fine points coincide where a sub-step is clipped)
 	uint32_t f = std::min<uint32_t>(need + 1, PREFIX_GRID);
 	while (f < PREFIX_GRID && prefix_stop_chunks(f, e.nchunks) == prefix_stop_chunks(need, e.nchunks)) ++f;
@@ -505,10 +655,15 @@ inline void plan_region(const PlanEnv& e, const PlanGeom& g, RegionPlan& p) {
 	if (e.het && !p.windowed && p.bands.empty()) p.two_end = plan_two_end(e, g);
 	if (p.bands.empty()) {       // (the two-product walk: no launch straddles two_end)
 		const uint32_t cut = std::min(std::max(p.two_end, p.r0), p.r1);
-		if (e.one && e.carrier && e.het && cut > p.r0) plan_one_tiles(e, g, p, p.r0, cut, p.mine);      // (... and a block's one-product launches end at its one_end)
+		if (e.one && e.carrier && e.het && cut > p.r0) plan_one_tiles(e, g, p, p.r0, cut);      // (... and a block's one-product launches end at its one_end)
 		else plan_matrix_tiles(e, g, p, p.r0, cut, p.mine);
-		plan_matrix_tiles(e, g, p, cut, p.r1, p.mine);
+		// (the fine walk: two products from the diagonal to the rows' two_reach in the blocks behind the cut that have one)
+		p.two_last = p.two_end;
+		uint32_t behind = cut;
+		if (e.fine && e.stair_behind && e.carrier && e.het && !e.fused && !g.tile_variants && g.triangle && p.two_end == cut && cut < p.r1) behind = p.two_last = plan_two_stairs(e, g, p, cut, p.r1);
+		plan_matrix_tiles(e, g, p, behind, p.r1, p.mine);
 	}
+	p.notes.resize(p.mine.size());
 	if (e.screen) p.pairs = band_pairs_before(p.r1, g.nA, g.nB, true) - band_pairs_before(p.r0, g.nA, g.nB, true);   // every pair of the band is decided
 	else if (p.windowed) p.pairs = p.cum[p.r1] - p.cum[p.r0];       // pairs inside the window: the ones the math evaluates
 	else p.pairs = band_pairs_before(p.r1, g.nA, g.nB, g.triangle != 0) - band_pairs_before(p.r0, g.nA, g.nB, g.triangle != 0);
@@ -522,6 +677,29 @@ inline twk_hip_tile_desc sample_subtile(const twk_hip_tile_desc& t) {
 	st.rowA0 = row_c; st.nA = h;
 	if (t.diag && t.rowA0 == t.rowB0) { st.rowB0 = row_c; st.nB = std::min<uint32_t>(h, t.rowB0 + t.nB - row_c); st.diag = 1; }
 	else { const uint32_t wv = std::min<uint32_t>(384, t.nB); st.rowB0 = t.rowB0 + (t.nB - wv) / 2; st.nB = wv; st.diag = 0; }
+	return st;
+}
+
+// ... of launch i of a plan: a launch on one side of a staircase (LaunchNote::side) takes its sample where it has pairs - a launch that lies beside the
+// diagonal launch may have none in its rectangle's middle rows, whose border lies in front of it: then from its first rows, whose border is the furthest -
+// with the columns from the middle of what the sample's middle row holds.  *pairs: the pairs of the sub-tile that are the launch's.
+inline twk_hip_tile_desc sample_subtile_of(const RegionPlan& p, const PlanGeom& g, size_t i, uint64_t* pairs) {
+	const twk_hip_tile_desc& t = p.mine[i];
+	twk_hip_tile_desc st = sample_subtile(t);
+	const bool sided = i < p.notes.size() && p.notes[i].side != 0;
+	if (sided && !st.diag) {
+		uint32_t lo, hi; p.launch_cols(g, i, st.rowA0 + st.nA / 2, lo, hi);
+		if (hi <= lo) { st.rowA0 = t.rowA0; p.launch_cols(g, i, st.rowA0 + st.nA / 2, lo, hi); }
+		if (hi > lo) { const uint32_t w = std::min<uint32_t>(384, hi - lo); st.rowB0 = lo + (hi - lo - w) / 2; st.nB = w; }
+	}
+	uint64_t n = 0;
+	for (uint32_t r = st.rowA0; r < st.rowA0 + st.nA; ++r) {
+		uint32_t lo = st.rowB0, hi = st.rowB0 + st.nB;
+		if (sided) { uint32_t l2, h2; p.launch_cols(g, i, r, l2, h2); lo = std::max(lo, l2); hi = std::min(hi, h2); }
+		else if (st.diag) lo = std::max(lo, r + 1);
+		if (hi > lo) n += hi - lo;
+	}
+	if (pairs) *pairs = n;
 	return st;
 }
 

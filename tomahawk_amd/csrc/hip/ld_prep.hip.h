@@ -150,6 +150,18 @@ void k_row_suffix_popcount(const uint32_t* __restrict__ rows, uint32_t W, uint32
 	}
 }
 
+// The suffix table turned grid-major for the screens (ld_three.hip.h screen_pairs_body): in[r * PREFIX_GRID + f] -> out[f * n_rows + r].  A block turns
+// 32 rows x 32 grid points through LDS, so that both sides move whole 128-byte lines.  grid: (ceil(n_rows / 32), PREFIX_GRID / 32) - the rows on x,
+// which has no limit a plane set can meet - 32 x 8 threads.
+__global__ __launch_bounds__(256)
+void k_suffix_grid_major(const uint32_t* __restrict__ in, uint32_t n_rows, uint32_t* __restrict__ out) {
+	__shared__ uint32_t t[32][33];
+	const uint32_t f0 = blockIdx.y * 32, r0 = blockIdx.x * 32;
+	for (uint32_t k = threadIdx.y; k < 32; k += 8) { const uint32_t r = r0 + k; t[k][threadIdx.x] = r < n_rows ? in[(size_t)r * PREFIX_GRID + f0 + threadIdx.x] : 0u; }
+	__syncthreads();
+	for (uint32_t k = threadIdx.y; k < 32; k += 8) { const uint32_t r = r0 + threadIdx.x; if (r < n_rows) out[(size_t)(f0 + k) * n_rows + r] = t[threadIdx.x][k]; }
+}
+
 // Carrier rows of the first n variants of an unphased plane set (the two-product form's row operand, ld_two_screen.h): out[v][k] = H | Q of
 // variant v - plane rows 2v and 2v + 1 - one row of W words per variant.  W is a multiple of 4; grid.y walks the variants, 16 bytes per thread:
 // one streaming pass.  Rows behind n are the caller's to zero.

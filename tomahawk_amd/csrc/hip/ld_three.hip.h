@@ -32,6 +32,7 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 	const uint32_t vA = s.a0 + i, vB = s.b0 + j;
 	bool ok = i < s.nA && j < s.nB && vA < s.n_variants && vB < s.n_variants && (!s.diag || vB > vA);
 	if (ok && s.col_hi) { const uint32_t k = vA - s.hi_a0; ok = vB < s.hi_b0 + s.col_hi[k < s.hi_n ? k : s.hi_n - 1]; }
+	if (ok && s.col_lo) { const uint32_t k = vA - s.hi_a0; ok = vB >= s.hi_b0 + s.col_lo[k < s.hi_n ? k : s.hi_n - 1]; }      // (a launch behind a staircase: nothing in front of it was contracted)
 	if (ok && ((vA < s.list_zone && vB < s.list_zone) || vA < s.probe_zone)) ok = false;
 	if (ok && (pp->window & TWK_HIP_OPT_WINDOW)) {      // window mode: only the tiles some row can reach were contracted - the exact test of d_pair, so that
 		const StatsParams& p = *pp;                     // nothing is read from a tile that holds no counts
@@ -51,15 +52,16 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 			const uint32_t st = prefix_stop_chunks(g, s.pre_nchunks);
 			if (st < s.pre_nchunks) {
 				stop = st;
-				const uint32_t* fA = s.pre_suffix + (size_t)(2 * vA) * PREFIX_GRID + g;
-				const uint32_t* fB = s.pre_suffix + (size_t)(2 * vB) * PREFIX_GRID + g;
-				const SuffixMargins x{fA[0], fA[PREFIX_GRID], fB[0], fB[PREFIX_GRID]};
+				// (grid-major: the row variant's two margins are one address a wave, the column variants' two a lane lie side by side)
+				const uint32_t* fG = s.pre_suffix + (size_t)g * s.pre_rows;
+				const uint2 xA = *reinterpret_cast<const uint2*>(fG + 2 * (size_t)vA), xB = *reinterpret_cast<const uint2*>(fG + 2 * (size_t)vB);
+				const SuffixMargins x{xA.x, xA.y, xB.x, xB.y};
 				ok = ONE ? screen1c_prefix_keeps(m, x, hh, s.two_n, s.cut)
-				   : TWO ? (s.carrier ? screen2c_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut) : screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut))
+				   : TWO ? (s.carrier ? screen2c_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut, s.fine != 0) : screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut))
 				         : screen3_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut);
 			}
 		}
-		if (!stop) ok = ONE ? screen1c_keeps(m, hh, s.two_n, s.cut) : TWO ? (s.carrier ? screen2c_keeps(m, hh, s_sum, s.two_n, s.cut) : screen2_keeps(m, hh, s_sum, s.two_n, s.cut)) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
+		if (!stop) ok = ONE ? screen1c_keeps(m, hh, s.two_n, s.cut) : TWO ? (s.carrier ? screen2c_keeps(m, hh, s_sum, s.two_n, s.cut, s.fine != 0) : screen2_keeps(m, hh, s_sum, s.two_n, s.cut)) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
 	}
 	__shared__ uint32_t wave_n[SCREEN3_THREADS / 64];
 	__shared__ unsigned long long block_base;

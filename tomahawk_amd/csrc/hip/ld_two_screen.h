@@ -62,13 +62,17 @@ TWK_SCREEN_FN bool screen2_expected_keeps(const ScreenMargins& m, double n_sampl
 // Both ends lie inside the H form's - CQ >= HQ, and CH + CQ + min = HH + HQ + (QH + QQ) + min <= HH + HQ + qA + min - so screen2c_keeps keeps
 // every pair screen3_keeps keeps and none that screen2_keeps drops; the gap above T falls from about 2 qA to min(qA, qB).
 TWK_SCREEN_FN double screen2c_slack(const ScreenMargins& m) { return (double)(m.qA < m.qB ? m.qA : m.qB); }       // (T's upper end) - CH - CQ
-TWK_SCREEN_FN bool screen2c_keeps(const ScreenMargins& m, uint32_t ch, uint32_t cq, double two_n, double cut) {
-	return screen_keeps_between(m, (double)ch, (double)cq, (double)cq + screen2c_slack(m), two_n, cut);
+// The launch has counted CQ = HQ + QQ >= QQ itself, so QQ <= min(qA, qB, CQ) costs nothing: the gap above T is never more than CQ (the fine
+// walk, option "walk_fine"; `fine` false: the bound by the margins alone).  At a = b = 0.25 under independence the term falls from 0.0625 N to
+// 0.027 N, less than the room the screen has above T there.  The one-product form counts no CQ and keeps screen2c_slack.
+TWK_SCREEN_FN double screen2c_slack_cq(const ScreenMargins& m, double cq, bool fine) { const double s = screen2c_slack(m); return fine && cq < s ? cq : s; }
+TWK_SCREEN_FN bool screen2c_keeps(const ScreenMargins& m, uint32_t ch, uint32_t cq, double two_n, double cut, bool fine = false) {
+	return screen_keeps_between(m, (double)ch, (double)cq, (double)cq + screen2c_slack_cq(m, (double)cq, fine), two_n, cut);
 }
-// The planner's question of the carrier form: under independence CH = cA hB / N and CQ = cA qB / N with cA = hA + qA.
-TWK_SCREEN_FN bool screen2c_expected_keeps(const ScreenMargins& m, double n_samples, double two_n, double cut, double margin) {
+// The planner's question of the carrier form: under independence CH = cA hB / N and CQ = cA qB / N with cA = hA + qA (fine: the expected CQ in the min).
+TWK_SCREEN_FN bool screen2c_expected_keeps(const ScreenMargins& m, double n_samples, double two_n, double cut, double margin, bool fine = false) {
 	const double ca = (double)m.hA + (double)m.qA, ch = ca * (double)m.hB / n_samples, cq = ca * (double)m.qB / n_samples;
-	return screen_keeps_between(m, ch, cq, cq + screen2c_slack(m), two_n, cut, margin * margin);
+	return screen_keeps_between(m, ch, cq, cq + screen2c_slack_cq(m, cq, fine), two_n, cut, margin * margin);
 }
 
 // ---- one product: the two carrier planes against each other --------------------------------------------------------------
@@ -146,16 +150,18 @@ TWK_SCREEN_FN bool prefix_expected_keeps(const ScreenMargins& m, const SuffixMar
 
 // The carrier form over the prefix: ch = CH_pre, cq = CQ_pre.  S_pre >= CQ_pre and T_pre <= CH_pre + CQ_pre + min(qa_pre, qb_pre) as over whole
 // rows, with the prefix margins (total minus suffix); the unread suffix adds prefix_slack(x) to the upper end as in the other prefix screens.
-TWK_SCREEN_FN bool screen2c_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t ch, uint32_t cq, double two_n, double cut) {
+// fine: QQ_pre <= CQ_pre too - what the launch counted over the prefix is itself such a bound, so it is sound over a prefix as it stands.
+TWK_SCREEN_FN double prefix_slack_cq(double qa, double qb, double cq, bool fine) { const double s = qa < qb ? qa : qb; return fine && cq < s ? cq : s; }
+TWK_SCREEN_FN bool screen2c_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t ch, uint32_t cq, double two_n, double cut, bool fine = false) {
 	const double qa = (double)(m.qA - x.qA), qb = (double)(m.qB - x.qB);
-	return screen_keeps_between(m, (double)ch, (double)cq, (double)cq + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut);
+	return screen_keeps_between(m, (double)ch, (double)cq, (double)cq + prefix_slack_cq(qa, qb, (double)cq, fine) + prefix_slack(x), two_n, cut);
 }
 // ... and the planner's question for a stop of a carrier launch (prefix_expected_keeps with two = true, in the carrier form).
-TWK_SCREEN_FN bool prefix_expected_keeps_carrier(const ScreenMargins& m, const SuffixMargins& x, double n_pre, double two_n, double cut, double margin) {
+TWK_SCREEN_FN bool prefix_expected_keeps_carrier(const ScreenMargins& m, const SuffixMargins& x, double n_pre, double two_n, double cut, double margin, bool fine = false) {
 	if (n_pre <= 0) return true;
 	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
 	const double ch = (ha + qa) * hb / n_pre, cq = (ha + qa) * qb / n_pre;
-	return screen_keeps_between(m, ch, cq, cq + (qa < qb ? qa : qb) + prefix_slack(x), two_n, cut, margin * margin);
+	return screen_keeps_between(m, ch, cq, cq + prefix_slack_cq(qa, qb, cq, fine) + prefix_slack(x), two_n, cut, margin * margin);
 }
 
 // The planner's second question for a stop (ld_plan.h PrefixEnv::dropped): the screen's own bound (bound_factor 1), asked at the expected
@@ -167,7 +173,8 @@ TWK_SCREEN_FN bool prefix_expected_keeps_carrier(const ScreenMargins& m, const S
 // and a sum's variance is n_pre (second moment - mean^2).  The real counts are sums with both margins fixed, whose spread is smaller, so z
 // standard deviations of these are at least z of the real ones.  Where the 5 % of sqrt(bound) of prefix_expected_keeps is many standard
 // deviations (long rows) this question drops a pair earlier; where it is few (rows of ~ 140 k samples) the other one does.
-TWK_SCREEN_FN bool prefix_sigma_keeps(const ScreenMargins& m, const SuffixMargins& x, bool two, bool carrier, double n_pre, double two_n, double cut, double z) {
+// (fine: the carrier form's fixed term with the expected CQ_pre in its min, as the screen of the fine walk has the counted one)
+TWK_SCREEN_FN bool prefix_sigma_keeps(const ScreenMargins& m, const SuffixMargins& x, bool two, bool carrier, double n_pre, double two_n, double cut, double z, bool fine = false) {
 	if (n_pre <= 0) return true;
 	const double ha = (double)(m.hA - x.hA), qa = (double)(m.qA - x.qA), hb = (double)(m.hB - x.hB), qb = (double)(m.qB - x.qB);
 	const double a1 = ha / n_pre, a2 = qa / n_pre, b1 = hb / n_pre, b2 = qb / n_pre;
@@ -181,7 +188,7 @@ TWK_SCREEN_FN bool prefix_sigma_keeps(const ScreenMargins& m, const SuffixMargin
 		hh = a1 * b1; fixed = qa + (qa < qb ? qa : qb) + prefix_slack(x);
 	} else {
 		mu_lo = m2_lo = (a1 + a2) * b2; mu_hi = m2_hi = (a1 + a2) * (b1 + b2);
-		hh = (a1 + a2) * b1; fixed = (qa < qb ? qa : qb) + prefix_slack(x);
+		hh = (a1 + a2) * b1; fixed = prefix_slack_cq(qa, qb, n_pre * mu_lo, fine) + prefix_slack(x);
 	}
 	const double v_lo = n_pre * (m2_lo - mu_lo * mu_lo), v_hi = n_pre * (m2_hi - mu_hi * mu_hi);
 	const double sd_lo = v_lo > 0 ? __builtin_sqrt(v_lo) : 0.0, sd_hi = v_hi > 0 ? __builtin_sqrt(v_hi) : 0.0;

@@ -113,8 +113,9 @@ struct PlaneSet {
 	DevBuf<float4> terms; double terms_cut = -1.0;
 	// the two-product walk's planner (ld_plan.h plan_two_end): het and hom-alt carriers per position, copied from rowpop when first asked for
 	std::vector<uint32_t> h_het, h_hom;
-	// the prefix contraction: suffix popcounts of every plane row on the grid of stops, [rows_alloc][PREFIX_GRID], built the first time a
-	// call may take the form (ensure_suffix) and kept with the set - on the device for the screens, on the host for the planner
+	// the prefix contraction: suffix popcounts of every plane row on the grid of stops, built the first time a call may take the form
+	// (ensure_suffix) and kept with the set - on the host for the planner, [rows_alloc][PREFIX_GRID], and on the device for the screens, grid-major:
+	// [PREFIX_GRID][rows_alloc]
 	DevBuf<uint32_t> suffix; std::vector<uint32_t> h_suffix;
 	// the carrier plane: H | Q of the variants [0, carrier_n) of the sorted unphased set, one row of W words each and a zeroed pad of one
 	// tile of rows behind them (a tile stages 128 rows from its first) - the row operand of the two-product launches on long rows.  Built the first
@@ -235,6 +236,8 @@ namespace {
 	X(prefix, 1, 0, 2, false, "the two-product walk on rows of more than 128 K chunks: a launch contracts each tile over a prefix of its rows, up to a stop the planner chooses per tile, and its screen bounds the unread samples by the rows' suffix margins; what it keeps is recounted over the whole rows (DESIGN 3.1c); 0: never; 1: launches whose sample with stops is poor in candidates; 2: every eligible launch whatever its sample") \
 	X(prefix_margin, 950, 1, 1000, false, "... the planner asks with the square root of the screen's bound shrunk to this many thousandths of it (950 as the two-product planner's two_margin = 0.95)") \
 	X(prefix_sigma, 60, 0, 200, false, "... and, beside it, with the screen's own bound and the expected prefix counts moved outwards by this many tenths of their standard deviation under independence; a pair counts as decided at a stop where either question drops it (60: six standard deviations, the tighter of the two on rows of about a million samples; 0: the first question alone)") \
+	X(walk_fine, 1, 0, 2, false, "the two-product walk's finer rounding (DESIGN 3.1b, 3.1c): a row block's borders are staircases - a block in front of the cut has its one_end per tile row of 128 variants, its one-product launches listing the tiles in front of it and its two-product launches those behind it, and the blocks behind the cut take a two-product launch from the diagonal to their rows' two_reach, up to two_last, with three products behind it; the carrier screens hold QQ to min(qA, qB, CQ) - the launch counted CQ itself - in the launches, their samples and the planner's questions; and a tile's stop is the planner's answer without the spare grid step wherever prefix_sigma is on; 0: never; 1: rows of at least 256 K chunks; 2: every row length the carrier and prefix forms take (more than 128 chunks: the test hook)") \
+	X(walk_fine_sigma, 45, 0, 200, false, "... and where it applies prefix_sigma is this many tenths (45: the smallest of 60, 50 and 45 at which the headline recounts under 1 ms of candidates a step, no sample is refused and no launch redone - profiles/walk_fine_ab.txt; 0: prefix_sigma itself)") \
 	X(prefix_stop, 0, 0, 32, false, "test hook: this point of the 32 coarse points of the grid of stops for every tile of a prefix launch (0: the planner's stops)") \
 	X(prefix_substop, 0, 0, 3, false, "test hook: ... moved this many of the four sub-steps of a coarse interval further, to a point of the 128-point grid that need not be a coarse one (read only where prefix_stop is set)") \
 	X(count_min_chunks, 8, 1, 1 << 20, false, "shortest K range a tile of the count kernel is split into at the end of a launch (test hook: 1 splits short rows too)") \
@@ -358,6 +361,7 @@ struct twk_hip_ctx {
 	DevBuf<uint8_t> d_rle, d_rle_desc;
 	DevBuf<int> d_status;
 	DevBuf<uint32_t> d_col_hi;        // r2 screen: per-row column limit of the current region
+	DevBuf<uint32_t> d_stair;         // the fine walk: per-row staircase border of the current region (RegionPlan::stair)
 	// twk_hip_ld_score, _prune, _clump, _matrix, _decay, _aggregate, _score_annot, _matrix_band: the launches of the running call reduce their count matrices (launch_reduce) instead of keeping records
 	ReduceState reduce;                                                          // which way and where to, for the length of the call (ReduceCall)
 	// What the last call of each public entry point with a twk_hip_*_last took: its own report, whichever epilogue its launches ran
@@ -622,13 +626,17 @@ int ensure_suffix(twk_hip_ctx* c, int set) {
 	PlaneSet& ps = c->planes[set];
 	const size_t n = (size_t)ps.rows_alloc * PREFIX_GRID;
 	if (ps.h_suffix.size() == n && ps.suffix) return TWK_HIP_OK;
+	DevBuf<uint32_t> by_row;      // the kernel's own layout, which the host keeps; the device keeps its transpose
+	HIPCHK(c, by_row.reserve(n, n, nullptr));
 	HIPCHK(c, ps.suffix.reserve(n, n, nullptr));
-	HIPCHK(c, hipMemsetAsync(ps.suffix, 0, n * 4, c->s_compute));
+	HIPCHK(c, hipMemsetAsync(by_row, 0, n * 4, c->s_compute));
 	const uint32_t live_rows = c->M * (uint32_t)planes_per_variant(set_kind(set));
-	hipLaunchKernelGGL(k_row_suffix_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, live_rows, ps.suffix.get());
+	hipLaunchKernelGGL(k_row_suffix_popcount, dim3((live_rows + 3) / 4), dim3(256), 0, c->s_compute, (const uint32_t*)ps.rows, ps.W, live_rows, by_row.get());
+	HIPCHK(c, hipGetLastError());
+	hipLaunchKernelGGL(k_suffix_grid_major, dim3((ps.rows_alloc + 31) / 32, PREFIX_GRID / 32), dim3(32, 8), 0, c->s_compute, (const uint32_t*)by_row.get(), ps.rows_alloc, ps.suffix.get());
 	HIPCHK(c, hipGetLastError());
 	ps.h_suffix.resize(n);
-	HIPCHK(c, hipMemcpyAsync(ps.h_suffix.data(), ps.suffix, n * 4, hipMemcpyDeviceToHost, c->s_compute));
+	HIPCHK(c, hipMemcpyAsync(ps.h_suffix.data(), by_row, n * 4, hipMemcpyDeviceToHost, c->s_compute));
 	HIPCHK(c, hipStreamSynchronize(c->s_compute));
 	return TWK_HIP_OK;
 }
@@ -700,6 +708,12 @@ int ensure_slot(twk_hip_ctx* c, Slot& s, size_t C_words, unsigned long long capa
 		}                                                                                         \
 	} while (0)
 
+// The fine walk (option "walk_fine"; ld_plan.h PlanEnv::fine, PrefixEnv::fine; ScreenWork::fine) on rows of this many K chunks.  By default from 256
+// chunks on: the carrier and prefix forms begin behind 128, and up to 256 the grid of 128 stops coincides with the chunks.
+bool walk_fine_applies(const twk_hip_ctx* c, uint32_t row_chunks) {
+	return c->opt.walk_fine == 2 ? row_chunks > FUSED_MAX_CHUNKS : c->opt.walk_fine == 1 && row_chunks >= 256;
+}
+
 int ensure_host_records(twk_hip_ctx* c, unsigned long long n, char* err = nullptr, size_t err_len = 0) {
 	if (!err) { err = c->err; err_len = sizeof(c->err); }
 	HIPCHK_E(err, err_len, c->h_recs.reserve(n, std::max<unsigned long long>(n, 1ull << 16), nullptr));      // (freed at once: also called on the delivery thread)
@@ -755,6 +769,8 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		pe.het = ps.h_het.data(); pe.hom = ps.h_hom.data(); pe.suffix = ps.h_suffix.data();
 		pe.n_variants = c->M; pe.n_samples = c->N; pe.nchunks = nchunks;
 		pe.cut = fa->screen.cut; pe.margin = (double)c->opt.prefix_margin / 1000.0; pe.sigma = (double)c->opt.prefix_sigma / 10.0; pe.carrier = form.carrier; pe.one = form.one;
+		pe.fine = walk_fine_applies(c, nchunks);
+		if (pe.fine && c->opt.walk_fine_sigma > 0 && c->opt.prefix_sigma > 0) pe.sigma = (double)c->opt.walk_fine_sigma / 10.0;
 		pe.fixed_grid = c->opt.prefix_stop ? (uint32_t)c->opt.prefix_stop * PREFIX_SUB + (uint32_t)c->opt.prefix_substop : 0;
 		pre_grid.assign((size_t)g.gy * g.gx, (uint8_t)PREFIX_GRID);
 	}
@@ -774,7 +790,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 			std::memcpy(at, pre_grid.data(), pre_grid.size());
 			ScreenWork& sw = reinterpret_cast<FusedArgs*>(s.h_tiles[which] + words_units)->screen;
 			sw.pre_stops = reinterpret_cast<const uint8_t*>(s.d_tiles[which] + words_units + fa_words); sw.pre_suffix = ps.suffix;
-			sw.pre_gx = g.gx; sw.pre_tvA = stop_of.tvA(); sw.pre_nchunks = nchunks;
+			sw.pre_gx = g.gx; sw.pre_tvA = stop_of.tvA(); sw.pre_nchunks = nchunks; sw.pre_rows = ps.rows_alloc;
 		}
 		HIPCHK(c, hipMemcpyAsync(s.d_tiles[which], s.h_tiles[which], words * 4, hipMemcpyHostToDevice, c->s_compute));
 	}
@@ -823,7 +839,7 @@ StatsParams make_stats(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, cons
 	p.tv.n_samples = c->N; p.tv.a0 = t.rowA0; p.tv.b0 = t.rowB0; p.tv.ids = ps.ids;
 	p.vm = VariantMeta{c->d_ac, c->d_an, c->d_pos, c->d_rid, c->d_missing, c->d_hwe};
 	p.raw = c->raw; p.rawmask = c->rawmask; p.Wp = c->Wp;
-	p.col_hi = cr ? cr->d_hi : nullptr; p.hi_a0 = cr ? cr->a0 : 0; p.hi_b0 = cr ? cr->b0 : 0;
+	p.col_hi = cr ? cr->d_hi : nullptr; p.hi_a0 = cr ? cr->a0 : 0; p.hi_b0 = cr ? cr->b0 : 0; p.col_lo = cr ? cr->d_lo : nullptr;
 	p.list_zone = cr ? cr->list_zone : 0; p.probe_zone = cr ? cr->probe_zone : 0;
 	p.nA = t.nA; p.nB = t.nB; p.n_variants = c->M;
 	p.diag = (t.diag && t.rowA0 == t.rowB0) ? 1 : 0;
@@ -1105,9 +1121,10 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		fa.stats = make_stats(c, kind1, t, s, pl.phased1, pl.select1, f, cr);
 		sw.rowpop = ps.rowpop; sw.a0 = t.rowA0; sw.b0 = t.rowB0; sw.nA = t.nA; sw.nB = t.nB;
 		sw.n_variants = c->M; sw.diag = (t.diag && t.rowA0 == t.rowB0) ? 1 : 0;
-		sw.col_hi = cr ? cr->d_hi : nullptr; sw.hi_a0 = cr ? cr->a0 : 0; sw.hi_b0 = cr ? cr->b0 : 0; sw.hi_n = cr ? cr->n_hi : 0;
+		sw.col_hi = cr ? cr->d_hi : nullptr; sw.hi_a0 = cr ? cr->a0 : 0; sw.hi_b0 = cr ? cr->b0 : 0; sw.hi_n = cr ? cr->n_hi : 0; sw.col_lo = cr ? cr->d_lo : nullptr;
 		sw.list_zone = cr ? cr->list_zone : 0; sw.probe_zone = cr ? cr->probe_zone : 0;
 		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2; sw.carrier = form.one ? 2u : form.carrier ? 1u : 0u;
+		sw.fine = form.carrier && !form.one && walk_fine_applies(c, ps.W / KC) ? 1u : 0u;
 		{	// slots a wave reserves at a time: what it cannot use is lost to the list, so at most an eighth of the list's
 			// capacity may be tied up in the waves' windows (small tiles: 0, i.e. one atomic per wave and tile)
 			const unsigned long long per_wave = l.cand_cap / (8ull * c->resident_blocks * (COUNT_THREADS / 64));
@@ -2422,6 +2439,8 @@ struct RegionRun {
 	Deliver to;                               // every launch of the region: the device sink, or the caller's sink (none: records are counted and dropped)
 	std::chrono::steady_clock::time_point t_origin = std::chrono::steady_clock::now();
 	ColRange col_range;
+	// the fine walk's staircases (RegionPlan::stair): the column ranges of the launches in front of a border (LaunchNote::side 1) and behind one (2)
+	StairRanges stairs;
 	unsigned long long cap_default = 1ull << 24;
 	uint64_t tot_pairs = 0, tot_recs = 0;
 	std::vector<LaunchWants> wants;           // per launch: the forms its samples allow it (decide_three_by_samples -> ld_form.h: decide_wants)
@@ -2431,10 +2450,24 @@ struct RegionRun {
 	bool two_walk() const { return mode == MODE_INT_SORTED_U_ALL; }
 	// (option two = 2, the test hook: every launch of the walk, whatever the predicate says)
 	bool two_eligible(const twk_hip_tile_desc& t) const { return two_walk() && c->opt.two != 0 && (c->opt.two == 2 || t.rowA0 + t.nA <= g.a0 + plan.two_end); }
+	bool behind(size_t i) const { return i < plan.notes.size() && plan.notes[i].behind != 0; }
+	// ... or a launch the planner gave two products behind the cut, while the call still has them
+	bool two_eligible(size_t i) const { return two_eligible(plan.mine[i]) || (behind(i) && calls.two_behind && two_walk() && c->opt.two != 0); }
+	const ColRange* cr_of(size_t i) const { return stairs.of(plan, i, cr()); }
+	// the pairs launch i decides: its rectangle's, or what lies on its side of the staircase
+	uint64_t pairs_of(size_t i) const {
+		if (!(i < plan.notes.size() && plan.notes[i].side)) return pairs_in_tile(c, plan.mine[i]);
+		const twk_hip_tile_desc& t = plan.mine[i];
+		uint64_t n = 0;
+		for (uint32_t r = t.rowA0; r < t.rowA0 + t.nA; ++r) { uint32_t lo, hi; plan.launch_cols(g, i, r, lo, hi); n += hi - lo; }
+		return n;
+	}
 
 	// What launch i of the plan may be: the call's forms, as far as the launch's own samples want them.  A tile redone synchronously is not bound by a
 	// sample: it may be whatever the call still allows but two products (redo_grant).
-	FormGrant grant_of(size_t i) const { return calls.grant(wants[i]); }
+	FormGrant grant_of(size_t i) const {
+		return calls.grant(behind(i) ? calls.behind_wants(wants[i]) : wants[i]);
+	}
 	FormGrant redo_grant() const { return calls.grant(LaunchWants()); }
 
 	RegionRun(twk_hip_ctx* c_, int mode_, const twk_hip_filters* f_, const PlanGeom& g_, const PlanEnv& e_, RegionPlan& p_, CallForms& calls_, twk_hip_record_sink sink_, void* user_)
@@ -2453,6 +2486,11 @@ struct RegionRun {
 		cap_default = std::min<unsigned long long>(worst ? worst : 1, 1ull << 24);
 		if (c->opt.record_cap > 0) cap_default = std::min<unsigned long long>(cap_default, (unsigned long long)c->opt.record_cap);   // test hook: force the overflow / strip path
 		if (plan.windowed) { col_range.lo = plan.lo.data(); col_range.hi = plan.hi.data(); col_range.a0 = g.a0; col_range.b0 = g.b0; }
+		if (!plan.stair.empty() && plan.stair.size() == g.nA) {      // (rows of no staircase are in no launch that has a side)
+			HIPCHK(c, c->d_stair.reserve(g.nA, g.nA, nullptr));
+			HIPCHK(c, hipMemcpy(c->d_stair, plan.stair.data(), (size_t)g.nA * 4, hipMemcpyHostToDevice));
+			stairs.set(plan, g, c->d_stair);
+		}
 		if (env.screen && g.nA) {
 			HIPCHK(c, c->d_col_hi.reserve(g.nA, g.nA, nullptr));
 			HIPCHK(c, hipMemcpy(c->d_col_hi, plan.hi.data(), (size_t)g.nA * 4, hipMemcpyHostToDevice));
@@ -2531,13 +2569,14 @@ struct RegionRun {
 	};
 	// The sample of launch `pick` in the form `as`: its sub-tile (ld_plan.h: sample_subtile) through the same kernels on the spare slot, its records dropped.
 	SampleOutcome run_sample(size_t pick, const LaunchWants& as) {
-		const twk_hip_tile_desc st = sample_subtile(plan.mine[pick]);
+		uint64_t sided_pairs = 0;
+		const twk_hip_tile_desc st = sample_subtile_of(plan, g, pick, &sided_pairs);      // (a launch on one side of a staircase: where it has pairs, and those alone counted)
 		SampleOutcome o;
-		o.pairs = std::max<uint64_t>(pairs_in_tile(c, st), 1);
+		o.pairs = std::max<uint64_t>(pick < plan.notes.size() && plan.notes[pick].side ? sided_pairs : pairs_in_tile(c, st), 1);
 		SampleScope not_a_launch(c);
 		Slot& ss = c->slot[SYNC_SLOT];
 		unsigned long long nrec = 0;
-		o.rc = enqueue_tile(c, mode, st, *f, calls.sample_grant(as), ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr());
+		o.rc = enqueue_tile(c, mode, st, *f, calls.sample_grant(as), ss, std::max<unsigned long long>((unsigned long long)st.nA * st.nB, 1), cr_of(pick));
 		if (o.rc == TWK_HIP_OK) o.rc = finish_tile(c, ss, st, &nrec, Deliver{true, discard_records, nullptr});
 		o.cand = ss.h_n_out[2];
 		return o;
@@ -2552,17 +2591,21 @@ struct RegionRun {
 		x.prefix_ok = prefix_eligible();
 		x.three_possible = !mine.empty() && c->opt.three == 1 && launch_form(c, plan_for(c, mode), *f, redo_grant()).three;
 		x.fused = env.fused; x.carrier = env.carrier;      // (region_impl holds carrier rows for every row in front of the cut)
-		return decide_wants(mine.size(), x, [&](size_t i) { return two_eligible(mine[i]); }, [&](size_t i) { return mine[i].one != 0; },
-		                    [&](size_t pick, const LaunchWants& as) { return run_sample(pick, as); },
-		                    [&](const char* what, size_t i, unsigned long long n_cand) { mark(what, i, n_cand); }, wants, one_refused);
+		for (size_t i = 0; i < mine.size(); ++i) x.eligible_interleaved = x.eligible_interleaved || behind(i);
+		const int rc = decide_wants(mine.size(), x, [&](size_t i) { return two_eligible(i); }, [&](size_t i) { return mine[i].one != 0; },
+		                            [&](size_t pick, const LaunchWants& as) { return run_sample(pick, as); },
+		                            [&](const char* what, size_t i, unsigned long long n_cand) { mark(what, i, n_cand); }, wants, one_refused);
+		// (a two-product launch behind the cut whose sample refused the form: none of them takes it)
+		if (rc == TWK_HIP_OK && c->opt.two == 1 && calls.two_behind && behind_refused(wants, [&](size_t i) { return behind(i); })) { mark("two-product sample behind the cut refused: launches behind it", mine.size()); calls.two_behind = false; }
+		return rc;
 	}
 
 	// What every tile ends with once its launch, or the ladder below it (run_tile_sync), is through with rc: more survivors than the buffer holds -> the
 	// tile again in row strips that cannot overflow; its records into the total.
-	int strips_if_overflowed(int rc, const twk_hip_tile_desc& t, unsigned long long nrec) {
+	int strips_if_overflowed(int rc, const twk_hip_tile_desc& t, unsigned long long nrec, const ColRange* range) {
 		if (rc == TWK_HIP_E_OVERFLOW) {
 			uint64_t nr = 0;
-			rc = redo_tile_in_strips(c, mode, t, *f, redo_grant(), calls, cap_default, to, &nr, cr());
+			rc = redo_tile_in_strips(c, mode, t, *f, redo_grant(), calls, cap_default, to, &nr, range);
 			nrec = nr;
 		}
 		if (rc == TWK_HIP_OK) tot_recs += nrec;
@@ -2572,7 +2615,7 @@ struct RegionRun {
 	int run_tile_with_fallbacks(const twk_hip_tile_desc& t) {
 		unsigned long long nrec = 0;
 		const int rc = run_tile_sync(c, mode, t, *f, redo_grant(), calls, cap_default, &nrec, to, cr());
-		return strips_if_overflowed(rc, t, nrec);
+		return strips_if_overflowed(rc, t, nrec, cr());
 	}
 	// a band launch that cannot run (or has overflowed) as the matrix-sized tiles of its rows
 	int run_band_as_matrix_tiles(const BandLaunch& b) {
@@ -2611,10 +2654,13 @@ struct RegionRun {
 			return rc;
 		}
 		rc = finish_tile(c, s, mine[done], &nrec, to);
-		calls.gave_up(s.l.form, s.l.given, s.l.cand_overflow, s.l.too_rich);      // (the launches not yet enqueued see it; those in flight keep their grant)
+		// (a two-product launch behind the cut whose list overflowed ends those launches, and takes no form from the call: the ladder below is the same)
+		const bool behind_overflow = behind(done) && s.l.form.two && s.l.cand_overflow;
+		if (!behind_overflow) calls.gave_up(s.l.form, s.l.given, s.l.cand_overflow, s.l.too_rich);      // (the launches not yet enqueued see it; those in flight keep their grant)
+		const FormGrant down = behind_overflow ? calls.behind_overflowed(s.l.given) : step_down(s.l.form, s.l.given);      // (ld_form.h: ... redone with three products over whole rows)
 		if (rc == TWK_HIP_E_OVERFLOW && s.l.cand_overflow)                        // the candidate list overflowed: this tile again, one step down the ladder
-			rc = run_tile_sync(c, mode, mine[done], *f, step_down(s.l.form, s.l.given), calls, cap_default, &nrec, to, cr());
-		rc = strips_if_overflowed(rc, mine[done], nrec);
+			rc = run_tile_sync(c, mode, mine[done], *f, down, calls, cap_default, &nrec, to, cr_of(done));
+		rc = strips_if_overflowed(rc, mine[done], nrec, cr_of(done));
 		if (rc == TWK_HIP_OK) mark("finished (records delivered) launch", done, tot_recs);
 		return rc;
 	}
@@ -2633,7 +2679,7 @@ struct RegionRun {
 			if (b && !calls.fused) skipped[issued] = 1;                 // an earlier launch gave the fused form up: this one goes the matrix way when its turn comes
 			else {
 				mark("enqueue launch", issued);
-				const int r = enqueue_tile(c, mode, mine[issued], *f, grant_of(issued), c->slot[issued % PIPE_SLOTS], b ? 1 : cap_default, cr(), b ? b->list_words : 0);
+				const int r = enqueue_tile(c, mode, mine[issued], *f, grant_of(issued), c->slot[issued % PIPE_SLOTS], b ? 1 : cap_default, cr_of(issued), b ? b->list_words : 0);
 				if (r) return r;
 				mark("enqueued launch", issued);
 			}
@@ -2648,7 +2694,7 @@ struct RegionRun {
 			while (math_issued <= done && math_issued < issued) { rc = band_math(math_issued, skipped); if (rc) return rc; ++math_issued; }
 			rc = finish_launch(done, skipped);
 			if (rc) return rc;
-			tot_pairs += pairs_in_tile(c, mine[done]);
+			tot_pairs += pairs_of(done);
 			++done;
 			if (c->progress_cb && !c->progress_muted) c->progress_cb(c->progress_user, tot_pairs, (uint32_t)done, (uint32_t)n);
 		}
@@ -2677,6 +2723,7 @@ int plan_env_for(twk_hip_ctx* c, int mode, const twk_hip_filters* f, const CallF
 		env.carrier = c->opt.carrier != 0 && ps.W / KC > FUSED_MAX_CHUNKS;
 		// ... and one product a pair in front of a row block's one_end: likewise, once carrier rows for those launches' columns are there too
 		env.one = env.carrier && c->opt.one != 0 && calls.one && f->minR2 > 1e-6 && f->minR2 <= 1.0; env.one_rows = (uint32_t)c->opt.one_rows;
+		env.fine = walk_fine_applies(c, ps.W / KC);
 		// the prefix contraction: the rows' suffix margins, the first time a call may take the form (no room for the table: the call takes no stops)
 		if (c->opt.prefix != 0 && calls.prefix && f->minR2 > 1e-6 && f->minR2 <= 1.0 && ps.W / KC > FUSED_MAX_CHUNKS) {
 			const int rc = or_go_without(c, ensure_suffix(c, PS_SORTED_U), [&] { ps.suffix = DevBuf<uint32_t>(); ps.h_suffix.clear(); });
@@ -2719,11 +2766,22 @@ static int region_impl(twk_hip_ctx* c, const RegionArgs& a, CallForms& calls) {
 		// The carrier form's cut lies behind the H form's: carrier rows for every row variant of this shard's two-product launches (option two = 2: every
 		// launch of the walk), built now if they are not there.  No room for them: the plan of the H form, as before.
 		PlaneSet& ps = c->planes[PS_SORTED_U];
-		const uint32_t walk_end = c->opt.two == 2 ? g.nA : plan.two_end, need = plan.r0 < std::min(walk_end, plan.r1) ? g.a0 + std::min(walk_end, plan.r1) : 0;
+		auto drop_carrier = [&] { ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; };
+		auto have_carrier = [&](uint32_t n) { return ps.carrier_rows && ps.carrier_n >= n; };
+		// The rows are built once, for the largest need of this plan: the column variants of its one-product launches, or - the fine walk's two-product
+		// launches behind the cut - the row variants up to two_last.  No room for the latter: those blocks stay three-product.
+		{
+			uint32_t largest = plan.two_last > plan.two_end && c->opt.two != 2 ? g.a0 + plan.two_last : 0;
+			const uint32_t behind_need = largest;
+			for (const auto& t : plan.mine) if (t.one) largest = std::max(largest, t.rowB0 + t.nB);
+			if (behind_need && !have_carrier(largest)) { rc = or_go_without(c, ensure_carrier(c, PS_SORTED_U, largest), drop_carrier); if (rc) return rc; }
+			if (behind_need && !have_carrier(behind_need)) { rc = or_go_without(c, ensure_carrier(c, PS_SORTED_U, behind_need), drop_carrier); if (rc) return rc; }
+			if (behind_need && !have_carrier(behind_need)) { env.stair_behind = false; plan_region(env, g, plan); }
+		}
+		const uint32_t walk_end = c->opt.two == 2 ? g.nA : std::max(plan.two_end, plan.two_last), need = plan.r0 < std::min(walk_end, plan.r1) ? g.a0 + std::min(walk_end, plan.r1) : 0;
 		// ... and for every column variant of this shard's one-product launches (at r2 >= 0.1 on a flat frequency law: nearly every variant of the set, one
 		// more plane row each).  No room for those: the plan without one-product launches, and the rows in front of the cut as before.
 		uint32_t need_one = 0;
-		auto drop_carrier = [&] { ps.carrier_buf.reset(); ps.carrier_rows = nullptr; ps.carrier_n = 0; };
 		for (const auto& t : plan.mine) if (t.one) need_one = std::max(need_one, t.rowB0 + t.nB);
 		if (need && need_one > need && !(ps.carrier_rows && ps.carrier_n >= need_one)) {
 			rc = or_go_without(c, ensure_carrier(c, PS_SORTED_U, need_one), drop_carrier); if (rc) return rc;
@@ -3790,6 +3848,15 @@ int twk_hip_plan_region_two_form(const twk_hip_plan_env* pe, const twk_hip_varia
                                  uint32_t tile_variants, int32_t window, uint32_t l_window,
                                  twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
                                  uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end) {
+	return twk_hip_plan_region_walk(pe, meta, popc, het, hom, two_margin, carrier, one, one_rows, 0, n_variants, a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window,
+	                                tiles, capacity, n_tiles, n_band_launches, row_begin, row_end, n_pairs, lo, hi, two_end, nullptr, nullptr, nullptr);
+}
+int twk_hip_plan_region_walk(const twk_hip_plan_env* pe, const twk_hip_variant_meta* meta, const uint32_t* popc, const uint32_t* het, const uint32_t* hom, double two_margin,
+                             int32_t carrier, int32_t one, uint32_t one_rows, int32_t fine, uint32_t n_variants, uint32_t a0, uint32_t nA, uint32_t b0, uint32_t nB, int32_t triangle, uint32_t part, uint32_t n_parts,
+                             uint32_t tile_variants, int32_t window, uint32_t l_window,
+                             twk_hip_tile_desc* tiles, uint32_t capacity, uint32_t* n_tiles, uint32_t* n_band_launches,
+                             uint32_t* row_begin, uint32_t* row_end, uint64_t* n_pairs, uint32_t* lo, uint32_t* hi, uint32_t* two_end,
+                             uint32_t* two_last, uint8_t* notes, uint32_t* stair) {
 	if ((het != nullptr) != (hom != nullptr)) return TWK_HIP_E_INVALID;
 	if (!pe || !meta || !n_tiles || (capacity && !tiles) || n_parts == 0 || part >= n_parts) return TWK_HIP_E_INVALID;
 	if (nA == 0 || nB == 0 || (uint64_t)a0 + nA > n_variants || (uint64_t)b0 + nB > n_variants) return TWK_HIP_E_INVALID;
@@ -3803,6 +3870,7 @@ int twk_hip_plan_region_two_form(const twk_hip_plan_env* pe, const twk_hip_varia
 	env.het = het; env.hom = hom; if (two_margin > 0) env.two_margin = two_margin;
 	env.carrier = carrier != 0 && het != nullptr;
 	env.one = env.carrier && one != 0 && pe->minR2 > 1e-6 && pe->minR2 <= 1.0; env.one_rows = one_rows;
+	env.fine = fine != 0 && env.carrier;
 	env.band_launch = pe->band_launch != 0; env.band_reverse = pe->band_reverse != 0; env.band_work_log2 = pe->band_work_log2; env.band_max_launches = std::max<long long>(pe->band_max_launches, 1);
 	const PlanGeom g{a0, nA, b0, nB, triangle, part, n_parts, tile_variants, window, l_window};
 	RegionPlan plan;
@@ -3813,6 +3881,9 @@ int twk_hip_plan_region_two_form(const twk_hip_plan_env* pe, const twk_hip_varia
 	if (row_end) *row_end = plan.r1;
 	if (n_pairs) *n_pairs = plan.pairs;
 	if (two_end) *two_end = plan.two_end;
+	if (two_last) *two_last = plan.two_last;
+	if (stair) for (uint32_t r = 0; r < nA; ++r) stair[r] = r < plan.stair.size() ? plan.stair[r] : 0;
+	if (notes) for (size_t i = 0; i < plan.mine.size() && i < capacity; ++i) notes[i] = (uint8_t)(plan.notes[i].side | (plan.notes[i].behind ? 4 : 0));
 	if (plan.windowed) {
 		if (lo) std::copy(plan.lo.begin(), plan.lo.end(), lo);
 		if (hi) std::copy(plan.hi.begin(), plan.hi.end(), hi);

@@ -407,6 +407,7 @@ Script script(char stops, char two, char three, char one_stops = 'R', char one_t
 	Script s; s.stops = stops; s.two = two; s.three = three; s.one_stops = one_stops; s.one_two = one_two; s.but_rung = but_rung; s.but_pick = but_pick; s.but = but;
 	return s;
 }
+LadderFacts interleaved(LadderFacts x) { x.eligible_interleaved = true; return x; }      // (the fine walk's plan: two-eligible launches behind the cut too)
 std::string wants_text(const LaunchWants& w) { return std::string(w.three ? "3" : "") + (w.two ? "2" : "") + (w.prefix ? "p" : "") + (w.carrier ? "c" : "") + (w.one ? "1" : ""); }
 
 void check_ladder_table() {
@@ -442,6 +443,12 @@ void check_ladder_table() {
 		 TWK_HIP_OK, 0, {}, {{"32pc1", 1}, {"32pc", 1}}},
 		{"1 candidate in 128: dense for a launch through a matrix", 1, 0, 0, facts(1, 1, 1, false, false, false), script('R', 'R', 'M'),
 		 TWK_HIP_OK, 0, {{"3", 0, 0, 1}}, {{"", 1}}},
+		{"two-eligible launches between three-product ones (the fine walk): each sampled by itself, and the steps of 4 end in front of them", 200, 0x223, 0, interleaved(facts(1, 1, 1, false, false)), script('R', 'P', 'P'),
+		 TWK_HIP_OK, 0, {{"2", 0, 1, 2}, {"3", 3, 0, 1}, {"2", 5, 0, 1}, {"3", 7, 0, 1}, {"2", 9, 0, 1}, {"3", 12, 4, 47}, {"3", 199, 0, 1}}, {{"32", 2}, {"3", 3}, {"32", 1}, {"3", 3}, {"32", 1}, {"3", 190}}},
+		{"... one of them refused: it alone is left without two products by the ladder (the call then ends them all: behind_refused)", 200, 0x223, 0, interleaved(facts(1, 1, 1, false, false)), script('R', 'P', 'P', 'R', 'R', '2', 9, 'R'),
+		 TWK_HIP_OK, 0, {{"2", 0, 1, 2}, {"3", 3, 0, 1}, {"2", 5, 0, 1}, {"3", 7, 0, 1}, {"23", 9, 0, 1}, {"3", 12, 4, 47}, {"3", 199, 0, 1}}, {{"32", 2}, {"3", 3}, {"32", 1}, {"3", 3}, {"3", 1}, {"3", 190}}},
+		{"... without the fact the same plan is sampled in steps, as before: launch 5 follows launch 4", 200, 0x223, 0, facts(1, 1, 1, false, false), script('R', 'P', 'P'),
+		 TWK_HIP_OK, 0, {{"2", 0, 1, 2}, {"3", 4, 4, 49}, {"3", 199, 0, 1}}, {{"32", 2}, {"3", 198}}},
 		{"1 candidate in 128: still three products for a fused launch", 1, 0, 0, facts(1, 1, 1, false, false, true), script('R', 'R', 'M'),
 		 TWK_HIP_OK, 0, {{"3", 0, 0, 1}}, {{"3", 1}}},
 	};
@@ -465,6 +472,29 @@ void check_ladder_table() {
 	printf("form-check: the sample ladder: %zu named scripts as written out\n", cases.size());
 }
 
+// ---- the two-product launches behind the walk's cut ----------------------------------------------------------------------------------------------
+void check_behind() {
+	CallForms c;
+	LaunchWants w; w.two = true; w.carrier = true; w.one = true; w.prefix = true;
+	++g_cases;
+	CHECK(c.two_behind && c.behind_wants(w).two && c.behind_wants(w).one, "a fresh call has the launches behind the cut");
+	const FormGrant given = c.grant(w);
+	const FormGrant down = c.behind_overflowed(given);
+	CHECK(!c.two_behind && c.two && c.three && c.fused && c.prefix && c.one, "an overflowing launch behind the cut takes another form from the call");
+	CHECK(!down.two && !down.carrier && !down.one && !down.prefix && down.three == given.three && down.fused == given.fused && down.three, "redone with three products over whole rows");
+	CHECK(!c.behind_wants(w).two && !c.behind_wants(w).one && c.behind_wants(w).three && c.behind_wants(w).prefix, "the launches behind the cut keep two products");
+	CHECK(c.grant(w).two && c.grant(w).one && c.grant(w).prefix, "the launches in front of the cut lose theirs");
+	CHECK(!c.grant(c.behind_wants(w)).two && c.grant(c.behind_wants(w)).three, "the grant of a launch behind the cut");
+	std::vector<LaunchWants> wants(5);
+	for (size_t i : {0, 1, 3}) wants[i].two = true;
+	auto behind = [](size_t i) { return i == 3 || i == 4; };
+	++g_cases;
+	CHECK(behind_refused(wants, behind), "launch 4 behind the cut was refused two products");
+	wants[4].two = true;
+	CHECK(!behind_refused(wants, behind), "no launch behind the cut was refused (launch 2 in front of it says nothing)");
+	printf("form-check: the launches behind the cut: sampled by themselves, given up alone\n");
+}
+
 }  // namespace
 
 int main() {
@@ -477,6 +507,7 @@ int main() {
 	check_sample_subtile();
 	check_ladder_invariants();
 	check_ladder_table();
+	check_behind();
 	printf("form-check: %ld cases, %d bad\n", g_cases, g_bad_checks);
 	return g_bad_checks ? 1 : 0;
 }

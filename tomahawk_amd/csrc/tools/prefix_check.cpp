@@ -25,6 +25,13 @@
 //      planner on the headline's law with the rows in front of the cut in blocks of S and of S / 2 variants: launches by form, and the count work
 //      with stops against the carrier form's with stops at the default setting (a one-product tile costs what a two-product tile costs and holds
 //      twice the pairs).
+//   7. The fine walk (option "walk_fine"; PlanEnv::fine, PrefixEnv::fine), every line under the prefix "walk fine:": the carrier prefix screen with
+//      QQ_pre <= min(qa_pre, qb_pre, CQ_pre) keeps every pair three products keep on the whole rows and none the carrier prefix screen drops - part
+//      of 1. - and the planner on the headline's law, one-product blocks of S / 2, with walk_fine 0 and 1 and six, five and four and a half standard
+//      deviations: the cut, two_last, the launches by form, the count work, and the ratio new / parent expected of a step.
+//   8. The fine walk's plan on random het / hom tables of 300 .. 3,000 variants with p up to 0.5: every pair of the triangle lies in exactly one
+//      launch's listed tiles and on that launch's side of its staircase, both staircases never rise along a block and move in steps of 128 variants,
+//      and with PlanEnv::fine off the launches are the parent's - restated here from plan_one_end and plan_matrix_tiles - tile list by tile list.
 // usage: prefix_check [--no-planner]
 #include <cinttypes>
 #include <cmath>
@@ -46,7 +53,7 @@ int g_bad_checks = 0;
 
 // ---- 1. the screens ----------------------------------------------------------------------------------------------------------
 constexpr uint32_t MAX_PART = 4;
-uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_kept2cp = 0, g_kept1cp = 0, g_violations = 0;
+uint64_t g_tests = 0, g_kept3 = 0, g_kept3p = 0, g_kept2p = 0, g_kept2cp = 0, g_kept1cp = 0, g_kept2cfp = 0, g_violations = 0;
 std::vector<std::vector<uint32_t>> g_tables;          // every 3 x 3 table of 0 .. MAX_PART samples: c[3 a + b]
 
 void each_table(uint32_t c[9], int cell, uint32_t left) {
@@ -99,6 +106,14 @@ void check_pair(const uint32_t* p, const uint32_t* x) {
 			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products on the whole rows %d, carrier prefix %d, H prefix %d",
 			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3, (int)k2cp, (int)k2p);
 		}
+		// the fine walk's carrier prefix screen: QQ_pre <= CQ_pre as well - between the whole rows' three products and the carrier prefix screen
+		const bool k2cfp = screen2c_prefix_keeps(m, sx, p[4] + p[7], p[5] + p[8], two_n, cut, true);
+		if ((k3 && !k2cfp) || (k2cfp && !k2cp)) {
+			++g_violations;
+			CHECK(false, "prefix %u %u %u / %u %u %u / %u %u %u + suffix %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products on the whole rows %d, fine carrier prefix %d, carrier prefix %d",
+			      p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], x[8], cuts[k], (int)k3, (int)k2cfp, (int)k2cp);
+		}
+		g_kept2cfp += k2cfp;
 		// one product over the prefix: CC_pre = CH_pre + CQ_pre, the lower test at S >= 0 - every pair the carrier prefix screen keeps
 		const bool k1cp = screen1c_prefix_keeps(m, sx, p[4] + p[7] + p[5] + p[8], two_n, cut);
 		if ((k3 && !k1cp) || (k2cp && !k1cp)) {
@@ -125,6 +140,7 @@ int check_screens() {
 			CHECK(screen3_prefix_keeps(m, none, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut) == screen3_keeps(m, c[4], c[7] + c[5] + 2 * c[8], 2.0 * n, cut), "empty suffix, three");
 			CHECK(screen2_prefix_keeps(m, none, c[4], c[5], 2.0 * n, cut) == screen2_keeps(m, c[4], c[5], 2.0 * n, cut), "empty suffix, two");
 			CHECK(screen2c_prefix_keeps(m, none, c[4] + c[7], c[5] + c[8], 2.0 * n, cut) == screen2c_keeps(m, c[4] + c[7], c[5] + c[8], 2.0 * n, cut), "empty suffix, carrier");
+			CHECK(screen2c_prefix_keeps(m, none, c[4] + c[7], c[5] + c[8], 2.0 * n, cut, true) == screen2c_keeps(m, c[4] + c[7], c[5] + c[8], 2.0 * n, cut, true), "empty suffix, fine carrier");
 			CHECK(screen1c_prefix_keeps(m, none, c[4] + c[7] + c[5] + c[8], 2.0 * n, cut) == screen1c_keeps(m, c[4] + c[7] + c[5] + c[8], 2.0 * n, cut), "empty suffix, one product");
 		}
 	}
@@ -224,10 +240,11 @@ struct CoarseTileStops {
 	}
 };
 // fine: the planner of ld_plan.h on the grid of 128; else CoarseTileStops.  quiet: no report, only the work (section 5).
-struct Setting { bool fine; double margin, sigma; };
+// walk: the fine walk (PlanEnv::fine, PrefixEnv::fine) - section 7.
+struct Setting { bool fine; double margin, sigma; bool walk = false; };
 constexpr Setting HEAD_SETTING{false, 0.95, 0.0};
 double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t h_two_end = 0, const Setting& st = HEAD_SETTING, bool quiet = false,
-                    double* work_whole = nullptr, double* stops_ms = nullptr, std::vector<double>* fractions = nullptr, int one_rows = -1, uint32_t* launches = nullptr) {
+                    double* work_whole = nullptr, double* stops_ms = nullptr, std::vector<double>* fractions = nullptr, int one_rows = -1, uint32_t* launches = nullptr, uint32_t* two_last = nullptr) {
 	const char* tag = carrier ? "carrier form: " : "planner: ";
 	const uint32_t M = 50000, N = 1000000, nchunks = (N + 1023) / 1024;
 	const double minR2 = 0.1, cut = minR2 * (1.0 - 1e-6), two_cost = 0.66;
@@ -242,12 +259,15 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		}
 	}
 	PlanEnv env; env.n_samples = N; env.Pmax = 2; env.nchunks = nchunks; env.minR2 = minR2; env.phased_math = false; env.het = het.data(); env.hom = hom.data(); env.carrier = carrier;
+	env.fine = st.walk;
 	env.one = carrier && one_rows >= 0; env.one_rows = one_rows > 0 ? (uint32_t)one_rows : 0;      // (section 6: the one-product launches of the carrier form)
 	const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
 	RegionPlan plan;
 	plan_region(env, g, plan);
-	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = st.margin; pe.sigma = st.sigma; pe.carrier = carrier;
+	PrefixEnv pe; pe.het = het.data(); pe.hom = hom.data(); pe.suffix = suffix.data(); pe.n_variants = M; pe.n_samples = N; pe.nchunks = nchunks; pe.cut = cut; pe.margin = st.margin; pe.sigma = st.sigma; pe.carrier = carrier; pe.fine = st.walk;
 	*two_end = plan.two_end;
+	if (two_last) *two_last = plan.two_last;
+	StairRanges stairs; stairs.set(plan, g, nullptr);
 	if (!quiet) printf("%s%u variants x %u samples, r2 >= %g, rows of %u chunks, grid step %u chunks; two-product cut at sorted row %u (p = %.3f); %zu %s\n",
 	       tag, M, N, minR2, nchunks, prefix_step(nchunks), plan.two_end, 0.05 + 0.45 * plan.two_end / M, plan.mine.size(), carrier ? "steps" : "launches");
 	CountSettings cs;
@@ -255,7 +275,8 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 	uint64_t n_tiles = 0;
 	for (size_t i = 0; i < plan.mine.size(); ++i) {
 		const twk_hip_tile_desc& t = plan.mine[i];
-		const bool two = t.rowA0 + t.nA <= plan.two_end, diag = t.diag && t.rowA0 == t.rowB0;
+		const bool two = t.rowA0 + t.nA <= plan.two_end || plan.notes[i].behind, diag = t.diag && t.rowA0 == t.rowB0;
+		const ColRange* cr = stairs.of(plan, i);
 		const bool one = two && t.one != 0;
 		const int P = one ? 1 : 2;
 		pe.one = one;
@@ -266,10 +287,10 @@ double play_planner(bool carrier, uint32_t* two_end, double h_work = 0, uint32_t
 		const PrefixTileStops stop_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, geo.gx, &grid, {PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID, PREFIX_GRID}};
 		const CoarseTileStops coarse_of{&pe, two, t.rowA0, t.rowB0, t.nA, t.nB, {PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE, PREFIX_COARSE}};
 		const auto t0 = std::chrono::steady_clock::now();
-		const CountTable tb = st.fine ? build_count_table(t, P, diag, nullptr, nchunks, cs, two ? 1 : 0, &stop_of, &stops)
-		                              : build_count_table(t, 2, diag, nullptr, nchunks, cs, two ? 1 : 0, &coarse_of, &stops);
+		const CountTable tb = st.fine ? build_count_table(t, P, diag, cr, nchunks, cs, two ? 1 : 0, &stop_of, &stops)
+		                              : build_count_table(t, 2, diag, cr, nchunks, cs, two ? 1 : 0, &coarse_of, &stops);
 		const auto t1 = std::chrono::steady_clock::now();
-		const CountTable plain = build_count_table(t, P, diag, nullptr, nchunks, cs, two ? 1 : 0);
+		const CountTable plain = build_count_table(t, P, diag, cr, nchunks, cs, two ? 1 : 0);
 		const auto t2 = std::chrono::steady_clock::now();
 		host_ms += std::chrono::duration<double, std::milli>(t1 - t0).count() - std::chrono::duration<double, std::milli>(t2 - t1).count();
 		uint64_t done = 0; uint32_t lo = nchunks, hi = 0;
@@ -398,6 +419,159 @@ void report_one_product() {
 	printf("one product: prediction new / parent %.4f (blocks of S / 2, the default)\n", best / c_work);
 }
 
+// ---- 7. the fine walk ----------------------------------------------------------------------------------------------------------------
+// The step's time outside the two count kernels (screens, recount, math, sort, delivery: profiles/sample_ladder_ab.txt) and inside them, in ms.
+constexpr double STEP_OTHER_MS = 31.0, STEP_COUNT_MS = 2563.0;
+void report_walk_fine() {
+	struct Row { const char* name; Setting st; } rows[4] = {
+		{"walk_fine 0, 6 sigma (the parent's plan)", {true, 0.95, 6.0, false}}, {"walk_fine 1, 6 sigma", {true, 0.95, 6.0, true}},
+		{"walk_fine 1, 5 sigma", {true, 0.95, 5.0, true}}, {"walk_fine 1, 4.5 sigma", {true, 0.95, 4.5, true}}};
+	double parent = 0;
+	for (int k = 0; k < 4; ++k) {
+		uint32_t end = 0, last = 0, n[3] = {0, 0, 0};
+		double whole = 0;
+		const double w = play_planner(true, &end, 0, 0, rows[k].st, true, &whole, nullptr, nullptr, 4096, n, &last);
+		if (k == 0) parent = w;
+		printf("walk fine: %-42s two_end %u (p = %.4f), two_last %u (p = %.4f); %u launches: %u one-product, %u two-product, %u three-product; count work %.4f of whole rows in these forms, %.4f of the parent's; a step %.4f of the parent's\n",
+		       rows[k].name, end, 0.05 + 0.45 * end / 50000.0, last, 0.05 + 0.45 * last / 50000.0, n[0], n[1], n[2] - n[1], n[0] - n[2], w / whole, w / parent,
+		       (STEP_COUNT_MS * w / parent + STEP_OTHER_MS) / (STEP_COUNT_MS + STEP_OTHER_MS));
+		if (k > 0) CHECK(w < parent, "setting %d: work %g against the parent's %g", k, w, parent);
+	}
+}
+
+// ---- 8. the fine walk's plan: exact cover ------------------------------------------------------------------------------------------
+struct CoverStats { uint64_t plans = 0, pairs = 0, side_launches = 0, behind_launches = 0, stair_steps = 0, parent_equal = 0; };
+// The parent's launches of the rows in front of the cut, restated: one border a block, from the block's last row.
+void parent_front(const PlanEnv& e, const PlanGeom& g, const RegionPlan& p, uint32_t xa, uint32_t xb, std::vector<twk_hip_tile_desc>& out) {
+	const uint32_t H = plan_one_rows(e, p.S), nB = g.nB;
+	for (uint32_t x = xa; x < xb; x += H) {
+		const uint32_t h = std::min(H, xb - x), last = x + h - 1;
+		uint32_t w = 0;
+		if (last + 1 < nB && (h < 2 || plan_one_lower_ok(e, g, x, x + 1))) {
+			const uint32_t end = plan_one_end(e, g, last);
+			if (end >= std::min(x + h, nB) && end > last + 1) w = end >= nB ? nB - x : std::max(h, (end - x) / PLAN_TILE * PLAN_TILE);
+		}
+		const uint64_t rows = plan_round_up(h, PLAN_TILE);
+		const uint32_t w_max = (uint32_t)std::max<uint64_t>(h, std::min<uint64_t>(32768, ((1ull << 27) / rows) / PLAN_TILE * PLAN_TILE));
+		uint32_t col = x;
+		for (bool diag = true; col < x + w; diag = false) {
+			const uint32_t wl = std::min(w_max, x + w - col);
+			plan_push_tile(e, g, out, x, h, col, wl, diag ? 1 : 0);
+			out.back().one = 1;
+			col += wl;
+		}
+		if (!w) { plan_matrix_tiles(e, g, p, x, x + h, out, h); continue; }
+		if (col < nB) {
+			const uint32_t rest = nB - col, n_l = (rest + w_max - 1) / w_max, step = plan_round_up((rest + n_l - 1) / n_l, PLAN_TILE / 2);
+			for (; col < nB; col += step) plan_push_tile(e, g, out, x, h, col, std::min(step, nB - col), 0);
+		}
+	}
+}
+void check_cover_case(uint32_t M, uint32_t N, double p_lo, double minR2, uint32_t one_rows, uint64_t seed, CoverStats& cs) {
+	uint64_t rng = seed * 0x9E3779B97F4A7C15ull + 1;
+	auto next = [&]() { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return rng; };
+	std::vector<std::pair<uint64_t, std::pair<uint32_t, uint32_t>>> v(M);
+	for (auto& x : v) {
+		const double pf = p_lo + (0.5 - p_lo) * (double)(next() % 1000003) / 1000003.0;
+		const uint32_t q = (uint32_t)(pf * pf * N * (0.98 + 0.04 * (double)(next() % 1001) / 1000.0)), h = (uint32_t)(2 * pf * (1 - pf) * N * (0.98 + 0.04 * (double)(next() % 1001) / 1000.0));
+		x = {(uint64_t)h + 2ull * q, {h, q}};
+	}
+	std::sort(v.begin(), v.end());
+	std::vector<uint32_t> het(M), hom(M);
+	for (uint32_t i = 0; i < M; ++i) { het[i] = v[i].second.first; hom[i] = v[i].second.second; }
+	PlanEnv env; env.n_samples = N; env.Pmax = 2; env.nchunks = (N + 1023) / 1024; env.minR2 = minR2; env.phased_math = false; env.het = het.data(); env.hom = hom.data();
+	env.carrier = true; env.one = true; env.one_rows = one_rows;
+	const PlanGeom g{0, M, 0, M, 1, 0, 1, 0, 0, 0};
+	// fine off: the parent's launches, tile list by tile list
+	{
+		RegionPlan p0; env.fine = false; plan_region(env, g, p0);
+		std::vector<twk_hip_tile_desc> want;
+		const uint32_t cut = std::min(p0.two_end, p0.r1);
+		if (cut > p0.r0) parent_front(env, g, p0, p0.r0, cut, want); else plan_matrix_tiles(env, g, p0, p0.r0, cut, want);
+		plan_matrix_tiles(env, g, p0, cut, p0.r1, want);
+		bool same = want.size() == p0.mine.size() && p0.stair.empty() && p0.two_last == p0.two_end;
+		for (size_t i = 0; same && i < want.size(); ++i) {
+			same = std::memcmp(&want[i], &p0.mine[i], sizeof(twk_hip_tile_desc)) == 0 && p0.notes[i].side == 0 && p0.notes[i].behind == 0;
+			if (same) {
+				const bool one = want[i].one != 0, two = want[i].rowA0 + want[i].nA <= p0.two_end, diag = want[i].diag && want[i].rowA0 == want[i].rowB0;
+				std::vector<uint32_t> a, b;
+				build_tile_list(want[i], one ? 1 : 2, tile_geometry(one ? 1 : 2, want[i], two ? 1 : 0), diag, nullptr, a, nullptr, 8, 8, two ? 1 : 0);
+				build_tile_list(p0.mine[i], one ? 1 : 2, tile_geometry(one ? 1 : 2, p0.mine[i], two ? 1 : 0), diag, StairRanges().of(p0, i), b, nullptr, 8, 8, two ? 1 : 0);
+				same = a == b;
+			}
+		}
+		CHECK(same, "M %u N %u r2 %g one_rows %u: walk_fine 0 does not reproduce the parent's launches", M, N, minR2, one_rows);
+		cs.parent_equal += same;
+	}
+	RegionPlan p; env.fine = true; plan_region(env, g, p);
+	StairRanges stairs; stairs.set(p, g, nullptr);
+	CHECK(p.notes.size() == p.mine.size() && p.two_last >= p.two_end && p.two_last <= M, "notes %zu launches %zu two_end %u two_last %u", p.notes.size(), p.mine.size(), p.two_end, p.two_last);
+	std::vector<uint8_t> seen((size_t)M * M, 0);
+	for (size_t i = 0; i < p.mine.size(); ++i) {
+		const twk_hip_tile_desc& t = p.mine[i];
+		const LaunchNote nt = p.notes[i];
+		const bool one = t.one != 0, two = t.rowA0 + t.nA <= p.two_end || nt.behind, diag = t.diag && t.rowA0 == t.rowB0;
+		cs.side_launches += nt.side != 0; cs.behind_launches += nt.behind;
+		if (nt.behind) CHECK(nt.side == 1 && diag && t.rowA0 >= p.two_end && t.rowA0 + t.nA <= p.two_last && !one, "launch %zu behind the cut: rows %u+%u, cut %u .. %u", i, t.rowA0, t.nA, p.two_end, p.two_last);
+		if (nt.side) CHECK(p.stair.size() == M, "launch %zu has a side and the plan no staircase", i);
+		{	// the launch's sample lies inside it and holds pairs of its own - all of the sub-tile's for a launch without a side
+			uint64_t sp = 0;
+			const twk_hip_tile_desc st = sample_subtile_of(p, g, i, &sp);
+			CHECK(st.rowA0 >= t.rowA0 && st.rowA0 + st.nA <= t.rowA0 + t.nA && st.rowB0 >= t.rowB0 && st.rowB0 + st.nB <= t.rowB0 + t.nB && st.nA && st.nB, "launch %zu: sample %u+%u x %u+%u outside it", i, st.rowA0, st.nA, st.rowB0, st.nB);
+			uint64_t have = 0; for (uint32_t a = t.rowA0; a < t.rowA0 + t.nA; ++a) { uint32_t lo, hi; p.launch_cols(g, i, a, lo, hi); have += hi - lo; }
+			CHECK(sp > 0 || have == 0, "launch %zu side %u: its sample holds none of its %" PRIu64 " pairs", i, nt.side, have);
+			if (!nt.side) CHECK(sp == (st.diag ? (uint64_t)st.nA * (st.nA - 1) / 2 + (uint64_t)st.nA * (st.nB - st.nA) : (uint64_t)st.nA * st.nB), "launch %zu: %" PRIu64 " pairs in a sample of %u x %u", i, sp, st.nA, st.nB);
+		}
+		const int P = one ? 1 : 2, PA = two ? 1 : 0;
+		const uint32_t tvA = two ? TILE : TILE / 2, tvB = one ? TILE : TILE / 2;      // variants a tile holds on either axis
+		const Geometry geo = tile_geometry(P, t, PA);
+		std::vector<uint32_t> tiles;
+		build_tile_list(t, P, geo, diag, stairs.of(p, i), tiles, nullptr, 8, 8, PA);
+		for (const uint32_t yx : tiles) {
+			const uint32_t y = yx >> 16, x = yx & 0xFFFFu;
+			bool any = false;
+			for (uint32_t a = t.rowA0 + y * tvA; a < std::min(t.rowA0 + t.nA, t.rowA0 + (y + 1) * tvA); ++a) {
+				uint32_t lo, hi; p.launch_cols(g, i, a, lo, hi);      // what the screens' threads keep of the row: the rectangle, the diagonal, the launch's side
+				for (uint32_t b = std::max(lo, t.rowB0 + x * tvB); b < std::min(hi, t.rowB0 + (x + 1) * tvB); ++b) { ++seen[(size_t)a * M + b]; any = true; }
+			}
+			// the tile is on the launch's side of the staircase: some pair of it is the launch's (no tile is contracted for nothing but the diagonal's rounding)
+			CHECK(any || diag, "launch %zu side %u: tile (%u, %u) holds no pair of the launch", i, nt.side, y, x);
+		}
+		// every pair the launch is to decide lies in a listed tile
+		std::vector<uint8_t> listed((size_t)geo.gy * geo.gx, 0);
+		for (const uint32_t yx : tiles) listed[(size_t)(yx >> 16) * geo.gx + (yx & 0xFFFFu)] = 1;
+		for (uint32_t a = t.rowA0; a < t.rowA0 + t.nA; ++a) {
+			uint32_t lo, hi; p.launch_cols(g, i, a, lo, hi);
+			for (uint32_t b = lo; b < hi; b += tvB) CHECK(listed[(size_t)((a - t.rowA0) / tvA) * geo.gx + (b - t.rowB0) / tvB], "launch %zu: pair (%u, %u) in no listed tile", i, a, b);
+			if (hi > lo) CHECK(listed[(size_t)((a - t.rowA0) / tvA) * geo.gx + (hi - 1 - t.rowB0) / tvB], "launch %zu: pair (%u, %u) in no listed tile", i, a, hi - 1);
+		}
+		// the staircase of the launch's rows: constant over a tile row of 128 counted from the block's first row, in steps of 128 from its first column, never rising
+		if (nt.side) for (uint32_t a = t.rowA0; a < t.rowA0 + t.nA; ++a) {
+			const uint32_t s = p.stair[a];
+			CHECK(s > a && s <= M && (s == M || (s - t.rowA0) % PLAN_TILE == 0), "row %u of block %u: border %u", a, t.rowA0, s);
+			if (a > t.rowA0) { CHECK(s <= p.stair[a - 1] && ((a - t.rowA0) % PLAN_TILE == 0 || s == p.stair[a - 1]), "row %u: border %u after %u", a, s, p.stair[a - 1]); cs.stair_steps += s != p.stair[a - 1] && i + 1 < p.mine.size() && nt.side == 1 && diag; }
+			// the right side of it: in front of the cut the lower test passes for the row against every column in front of the border
+			if (one && s > a + 1) CHECK(plan_one_lower_ok(env, g, a, s - 1), "row %u: the lower test fails in front of its border %u", a, s);
+			// (behind the cut the border is a guide asked at two rows of a tile row - with noise in the margins the question's answer need not move one way -
+			// but every tile row's last row passes against its own first column: no row from two_last on is in such a launch)
+			if (nt.behind && ((a + 1 - t.rowA0) % PLAN_TILE == 0 || a + 1 == t.rowA0 + t.nA) && a + 1 < M) CHECK(!plan_two_keeps(env, g, a, a + 1), "row %u, the last of its tile row: the planner's question keeps the pair with its first column", a);
+		}
+	}
+	uint64_t bad = 0;
+	for (uint32_t a = 0; a < M; ++a) for (uint32_t b = 0; b < M; ++b) bad += seen[(size_t)a * M + b] != (b > a ? 1 : 0);
+	CHECK(bad == 0, "M %u N %u r2 %g one_rows %u: %" PRIu64 " pairs not in exactly one launch", M, N, minR2, one_rows, bad);
+	++cs.plans; cs.pairs += (uint64_t)M * (M - 1) / 2;
+}
+void check_cover() {
+	CoverStats cs;
+	uint64_t seed = 1;
+	for (const uint32_t M : {300u, 777u, 1400u, 3000u}) for (const uint32_t N : {140000u, 262184u, 1000000u}) for (const double minR2 : {0.05, 0.1})
+		for (const uint32_t one_rows : {0u, 128u, 384u}) check_cover_case(M, N, M == 777 ? 0.01 : 0.05, minR2, one_rows, seed++, cs);
+	printf("walk fine: plan cover: %" PRIu64 " plans, %" PRIu64 " pairs each in exactly one launch and on its side of the staircase; %" PRIu64 " launches with a side, %" PRIu64 " two-product launches behind the cut, %" PRIu64
+	       " steps of a staircase; walk_fine 0 equals the parent's launches in %" PRIu64 " plans\n", cs.plans, cs.pairs, cs.side_launches, cs.behind_launches, cs.stair_steps, cs.parent_equal);
+	CHECK(cs.side_launches > 0 && cs.behind_launches > 0 && cs.stair_steps > 0 && cs.parent_equal == cs.plans, "the cases hold no staircase");
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -420,6 +594,9 @@ int main(int argc, char** argv) {
 	if (planner) report_settings();
 	printf("prefix-check: the one-product prefix screen keeps %" PRIu64 " (the carrier plane's %" PRIu64 " <= it)\n", g_kept1cp, g_kept2cp);
 	if (planner) report_one_product();
+	printf("prefix-check: the fine carrier prefix screen (QQ_pre <= min(qa_pre, qb_pre, CQ_pre)) keeps %" PRIu64 " (three products on the whole rows %" PRIu64 " <= it <= the carrier plane's %" PRIu64 "), pair by pair\n", g_kept2cfp, g_kept3, g_kept2cp);
+	if (planner) report_walk_fine();
+	check_cover();
 	printf("prefix-check: %s\n", (bad_screen || bad_tables || g_bad_checks) ? "FAILED" : "ok");
 	return (bad_screen || bad_tables || g_bad_checks) ? 1 : 0;
 }

@@ -4,7 +4,9 @@
 //      the two-product screen keeps every pair the three-product screen keeps.  The carrier form (the row variant's H | Q as the row operand:
 //      CH = HH + QH, CQ = HQ + QQ): the true S and T = S + HH lie in [CQ, .] and [., CH + CQ + min(qA, qB)], and
 //      kept(three) <= kept(carrier) <= kept(H) pair by pair.  The one-product form (the carrier rows of both variants: CC = CH + CQ, lower test at
-//      S >= 0): kept(carrier) <= kept(one) pair by pair, and screen1c_lower_ok is the lower half of screen1c_keeps.
+//      S >= 0): kept(carrier) <= kept(one) pair by pair, and screen1c_lower_ok is the lower half of screen1c_keeps.  The fine walk's carrier screen
+//      (QQ <= min(qA, qB, CQ): screen2c_keeps with fine = true): T still lies under its upper end, and kept(three) <= kept(carrier, fine) <= kept(carrier)
+//      pair by pair.
 //   1b. plan_one_end (csrc/hip/ld_plan.h) on random sorted margins: the exact boundary of screen1c_lower_ok along a row's columns.
 //   2. The work table of a launch whose row axis has one plane row per variant and whose column axis two (build_count_table with PA = 1,
 //      csrc/hip/ld_count_table.h): tiles of 128 row variants x 64 column variants against a naive restatement - a tile is wanted when one of
@@ -34,7 +36,7 @@ int g_bad_checks = 0;
 // ---- 1. the screen ---------------------------------------------------------------------------------------------------------
 // c[3 a + b]: samples with genotype a (0 ref/ref, 1 het, 2 alt/alt) at the row variant and b at the column variant
 constexpr int MAX_N = 7;
-uint64_t g_tables = 0, g_kept3 = 0, g_kept2 = 0, g_kept2c = 0, g_kept1c = 0;
+uint64_t g_tables = 0, g_kept3 = 0, g_kept2 = 0, g_kept2c = 0, g_kept1c = 0, g_kept2cf = 0;
 
 void check_table(const uint32_t c[9], uint32_t n) {
 	const ScreenMargins m{c[3] + c[4] + c[5], c[6] + c[7] + c[8], c[1] + c[4] + c[7], c[2] + c[5] + c[8]};
@@ -45,6 +47,9 @@ void check_table(const uint32_t c[9], uint32_t n) {
 	const uint32_t ch = hh + qh, cq = hq + qq;
 	CHECK(cq <= s && (double)(s + hh) <= (double)ch + (double)cq + screen2c_slack(m), "carrier: S = %u, T = %u outside [%u, %u + %u + %g]", s, s + hh, cq, ch, cq, screen2c_slack(m));
 	CHECK(cq >= hq && (double)ch + (double)cq + screen2c_slack(m) <= (double)hh + (double)hq + screen2_slack(m), "carrier interval outside the H form's");
+	// ... and the fine walk's: QQ <= CQ, so T <= CH + CQ + min(qA, qB, CQ), an upper end no higher than the other
+	CHECK((double)(s + hh) <= (double)ch + (double)cq + screen2c_slack_cq(m, (double)cq, true) && screen2c_slack_cq(m, (double)cq, true) <= screen2c_slack(m) && screen2c_slack_cq(m, (double)cq, false) == screen2c_slack(m),
+	      "fine carrier: T = %u above %u + %u + %g", s + hh, ch, cq, screen2c_slack_cq(m, (double)cq, true));
 	// the cut-offs at which the three-product screen's decision on this very table turns: e^2 / (da ra db rb) of its two test values
 	// (without eps they are the pair's own extreme r2 values), each with its neighbours, next to fixed ones
 	std::vector<double> cuts = {1e-5, 0.01, 0.1, 0.25, 0.5, 0.9, 1.0};
@@ -61,6 +66,9 @@ void check_table(const uint32_t c[9], uint32_t n) {
 		const double cut = minR2 * (1.0 - 1e-6);
 		const bool k3 = screen3_keeps(m, hh, s, two_n, cut), k2 = screen2_keeps(m, hh, hq, two_n, cut), k2c = screen2c_keeps(m, ch, cq, two_n, cut);
 		CHECK((!k3 || k2c) && (!k2c || k2), "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three %d, carrier %d, H %d", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2, (int)k3, (int)k2c, (int)k2);
+		const bool k2cf = screen2c_keeps(m, ch, cq, two_n, cut, true);
+		CHECK((!k3 || k2cf) && (!k2cf || k2c), "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three %d, fine carrier %d, carrier %d", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2, (int)k3, (int)k2cf, (int)k2c);
+		g_kept2cf += k2cf;
 		CHECK(!k3 || k2, "n %u table %u %u %u / %u %u %u / %u %u %u at r2 >= %.17g: three products keep it, two drop it", n, c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], minR2);
 		// one product: CC = CH + CQ and the lower test at S >= 0 - every pair the carrier screen keeps, hence every pair three products keep
 		const bool k1c = screen1c_keeps(m, ch + cq, two_n, cut);
@@ -94,6 +102,8 @@ int check_screen() {
 				const uint32_t sc = hq + qh + 2 * qq;
 				const bool k3c = screen3_keeps(m, hh, sc, 2.0 * n, cut), k2c = screen2c_keeps(m, hh + qh, hq + qq, 2.0 * n, cut), k2h = screen2_keeps(m, hh, hq, 2.0 * n, cut);
 				CHECK((!k3c || k2c) && (!k2c || k2h), "carrier: n %u pa %g pb %g S %u at %g: three %d, carrier %d, H %d", n, pa, pb, sc, minR2, (int)k3c, (int)k2c, (int)k2h);
+				const bool k2cf = screen2c_keeps(m, hh + qh, hq + qq, 2.0 * n, cut, true);
+				CHECK((!k3c || k2cf) && (!k2cf || k2c), "fine carrier: n %u pa %g pb %g S %u at %g: three %d, fine carrier %d, carrier %d", n, pa, pb, sc, minR2, (int)k3c, (int)k2cf, (int)k2c);
 			}
 		}
 	return g_bad_checks != before;
@@ -256,5 +266,7 @@ int main(int argc, char** argv) {
 	fprintf(record ? stderr : stdout, "two-check: one-product screen kept %" PRIu64 " of the same tests (carrier %" PRIu64 " <= one product); one_end exact on %" PRIu64 " rows, %" PRIu64 " pairs in front of it, %d bad\n",
 	        g_kept1c, g_kept2c, g_one_rows, g_one_pairs, bad_one);
 	if (g_kept1c < g_kept2c || bad_one) return 1;
+	fprintf(record ? stderr : stdout, "two-check: fine carrier screen (QQ <= min(qA, qB, CQ)) kept %" PRIu64 " of the same tests (three products %" PRIu64 " <= fine carrier <= carrier %" PRIu64 "), pair by pair\n", g_kept2cf, g_kept3, g_kept2c);
+	if (!(g_kept3 <= g_kept2cf && g_kept2cf <= g_kept2c)) return 1;
 	return bad != 0;
 }

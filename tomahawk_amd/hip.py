@@ -87,14 +87,17 @@ TILE_DTYPE = np.dtype([("rowA0", "<u4"), ("nA", "<u4"), ("rowB0", "<u4"), ("nB",
 def plan_region(meta, n_samples, a0, nA, b0, nB, triangle=True, part=0, n_parts=1, tile_variants=0, window=0, l_window=0,
                 popc=None, screen=0, minR2=0.1, planes_per_variant=1, k_chunks=1, fused=False, phased_math=True,
                 resident_blocks=512, band_launch=True, band_reverse=True, band_work_log2=19, band_max_launches=8,
-                het=None, hom=None, two_margin=0.0, carrier=False, one=False, one_rows=0):
+                het=None, hom=None, two_margin=0.0, carrier=False, one=False, one_rows=0, walk_fine=False):
     """The engine's planner (twk_hip_plan_region: host arithmetic, needs no GPU) -> dict(tiles=TILE_DTYPE array, n_band_launches,
     row_begin, row_end, n_pairs, lo, hi, two_end).  meta: META_DTYPE per position of the index space.  het / hom (both or neither): het and
     hom-alt carriers per position - the two-product walk of an unscreened UnphasedMath call (twk_hip_plan_region_two), whose triangle is cut
     at row two_end; two_margin 0: the engine's.  carrier: the walk's two-product launches contract the row variants' carrier planes H | Q
     (twk_hip_plan_region_two_operand; the engine's option "carrier" on rows of more than 128 K chunks) - off: their H planes.  one (with
     carrier): the rows in front of the cut in blocks of one_rows variants (0: the engine's default), each block's columns up to its one_end as
-    launches with tiles["one"] set (twk_hip_plan_region_two_form; the engine's options "one" and "one_rows")."""
+    launches with tiles["one"] set (twk_hip_plan_region_two_form; the engine's options "one" and "one_rows").  walk_fine (with carrier): the fine
+    walk's plan (twk_hip_plan_region_walk; the engine's option "walk_fine" where it applies) - staircase borders inside a row block: also
+    two_last, side (per launch: 0 the whole rectangle, 1 the columns in front of its rows' borders, 2 those from them on), behind (per launch: a
+    two-product launch behind the cut) and stair (per row: its border, 0: none)."""
     lib = load_library()
     meta = np.ascontiguousarray(meta, dtype=META_DTYPE)
     env = _PlanEnv(n_samples, planes_per_variant, k_chunks, resident_blocks, screen, int(fused), int(phased_math), int(band_launch),
@@ -102,16 +105,20 @@ def plan_region(meta, n_samples, a0, nA, b0, nB, triangle=True, part=0, n_parts=
     pc = None if popc is None else np.ascontiguousarray(popc, dtype=np.uint32)
     lo = np.zeros(nA, dtype=np.uint32); hi = np.zeros(nA, dtype=np.uint32)
     n_tiles, n_bands, r0, r1, pairs = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
-    two_end = C.c_uint32(0)
+    two_end, two_last = C.c_uint32(0), C.c_uint32(0)
+    stair = np.zeros(nA, dtype=np.uint32)
     ht = None if het is None else np.ascontiguousarray(het, dtype=np.uint32)
     hm = None if hom is None else np.ascontiguousarray(hom, dtype=np.uint32)
     cap = 1024
     while True:
         tiles = np.zeros(cap, dtype=TILE_DTYPE)
-        rc = lib.twk_hip_plan_region_two_form(C.byref(env), meta.ctypes.data, None if pc is None else pc.ctypes.data,
-                                         None if ht is None else ht.ctypes.data, None if hm is None else hm.ctypes.data, float(two_margin), int(bool(carrier)), int(bool(one)), int(one_rows), len(meta), a0, nA, b0, nB,
-                                         int(bool(triangle)), part, n_parts, tile_variants, window, l_window, tiles.ctypes.data, cap,
-                                         C.byref(n_tiles), C.byref(n_bands), C.byref(r0), C.byref(r1), C.byref(pairs), lo.ctypes.data, hi.ctypes.data, C.byref(two_end))
+        notes = np.zeros(cap, dtype=np.uint8)
+        rc = lib.twk_hip_plan_region_walk(C.byref(env), meta.ctypes.data, None if pc is None else pc.ctypes.data,
+                                          None if ht is None else ht.ctypes.data, None if hm is None else hm.ctypes.data, float(two_margin), int(bool(carrier)), int(bool(one)), int(one_rows),
+                                          int(bool(walk_fine)), len(meta), a0, nA, b0, nB,
+                                          int(bool(triangle)), part, n_parts, tile_variants, window, l_window, tiles.ctypes.data, cap,
+                                          C.byref(n_tiles), C.byref(n_bands), C.byref(r0), C.byref(r1), C.byref(pairs), lo.ctypes.data, hi.ctypes.data, C.byref(two_end),
+                                          C.byref(two_last), notes.ctypes.data, stair.ctypes.data)
         if rc == -4 and n_tiles.value > cap:
             cap = n_tiles.value
             continue
@@ -119,7 +126,7 @@ def plan_region(meta, n_samples, a0, nA, b0, nB, triangle=True, part=0, n_parts=
             raise HipError(rc, "twk_hip_plan_region", lib.twk_hip_strerror(rc).decode())
         break
     return dict(tiles=tiles[:n_tiles.value], n_band_launches=n_bands.value, row_begin=r0.value, row_end=r1.value, n_pairs=pairs.value, lo=lo, hi=hi,
-                two_end=two_end.value)
+                two_end=two_end.value, two_last=two_last.value, side=notes[:n_tiles.value] & 3, behind=(notes[:n_tiles.value] >> 2) & 1, stair=stair)
 
 
 class Plant(C.Structure):            # twk_hip_plant: LD planted in the synthetic input (include/twk_hip.h)
@@ -292,6 +299,8 @@ def load_library() -> C.CDLL:
                                                     C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32, p, p, p, p, p, p, p, p]
     lib.twk_hip_plan_region_two_form.argtypes = [p, p, p, p, p, C.c_double, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
                                                  C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32, p, p, p, p, p, p, p, p]
+    lib.twk_hip_plan_region_walk.argtypes = [p, p, p, p, p, C.c_double, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32,
+                                             C.c_uint32, C.c_uint32, C.c_int32, C.c_uint32, p, C.c_uint32, p, p, p, p, p, p, p, p, p, p, p]
     lib.twk_hip_launch_log.argtypes = [p, p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.twk_hip_fisher_exact.argtypes = [p, p, C.c_uint64, p, C.c_int32, C.POINTER(C.c_float)]
     lib.twk_hip_set_device_sink.argtypes = [p, C.c_int]
