@@ -22,7 +22,7 @@ HOST_LIB_SRC := $(filter-out %/calc_main.cpp,$(HOST_SRC))
 HOST_DEPS := $(wildcard $(PKG)/csrc/host/*.h) include/twk_hip.h
 CXXFLAGS := -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude -I$(PKG)/csrc/host
 
-.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check bandmat-check topk-check subset-check varsel-check blocks-check split-check
+.PHONY: all hip host cli oracle tools clean asan asan-test tsan buffers-check matrix-check decay-check aggregate-check relate-check count-check two-check prefix-check annot-check form-check uz-check bandmat-check topk-check subset-check varsel-check blocks-check split-check
 all: hip host cli oracle
 
 hip: $(LIBDIR)/libtwk_hip.so
@@ -44,13 +44,17 @@ $(BINDIR)/tomahawk: $(PKG)/csrc/host/calc_main.cpp $(LIBDIR)/libtomahawk_amd.so
 oracle:
 	$(MAKE) -C oracle all
 
-tools: build/count_microbench build/valu_rate build/hbm_read_bw build/issue_test2 build/fisher_probe build/bank_test2 build/list_vs_dense build/probe_vs_dense build/shift64_probe build/issue_test3 build/lds_dma3_probe build/bitop3_probe build/sgpr_probe
+tools: build/count_microbench build/valu_rate build/hbm_read_bw build/issue_test2 build/fisher_probe build/bank_test2 build/list_vs_dense build/probe_vs_dense build/shift64_probe build/issue_test3 build/lds_dma3_probe build/bitop3_probe build/sgpr_probe build/uz_probe
 build/%: $(PKG)/csrc/tools/%.hip $(HIP_DEPS)
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -Ibuild $< -o $@
 # (the probe's instruction streams with every register fixed by hand are written by a script)
 build/bitop3_probe: build/bitop3_probe_gen.h
 build/bitop3_probe_gen.h: $(PKG)/csrc/tools/bitop3_probe_gen.py
+	@mkdir -p build
+	python3 $< > $@
+build/uz_probe: build/uz_probe_gen.h
+build/uz_probe_gen.h: $(PKG)/csrc/tools/uz_probe_gen.py
 	@mkdir -p build
 	python3 $< > $@
 build/sgpr_probe: build/sgpr_probe_gen.h
@@ -155,11 +159,21 @@ annot-check:
 
 # Who may take which form of a count launch (csrc/hip/ld_form.h): decide_form over every combination of facts and grants, the transitions of
 # CallForms::gave_up, the ladder a redone tile descends, the choice of the two-product launches' row operand, the thresholds and the sample ladder
-# (decide_wants) under scripted samplers (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
+# (decide_wants) under scripted samplers, and the (U, Z) attribute of a three-product launch through a matrix (option "uz")
+# (csrc/tools/form_check.cpp): host code only, under AddressSanitizer and UBSan
 form-check:
 	@mkdir -p build
 	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/form_check.cpp -o build/form_check
 	./build/form_check
+
+# The (U, Z) form of the three-product contraction (csrc/hip/ld_count_uz.hip.h) on the host: the conversion its screen runs (csrc/hip/ld_two_screen.h:
+# uz_to_hh_s, uz_prefix_to_hh_s) against the products - every 3 x 3 table of up to 7 samples, every prefix and suffix table of up to 4 + 4 samples with
+# screen3_keeps / screen3_prefix_keeps on both, and zero-padded bit-plane rows word by word over every prefix (csrc/tools/uz_check.cpp): host code only,
+# under AddressSanitizer and UBSan
+uz-check:
+	@mkdir -p build
+	$(CXX) -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PKG)/csrc/tools/uz_check.cpp -o build/uz_check
+	./build/uz_check
 
 # The banded LD matrix's layout against its O(n^2) definition, and the fill's slot arithmetic, guards and dead-block test
 # (csrc/hip/ld_bandmat_index.h) played lane by lane against an array of write counts with a border (csrc/tools/bandmat_index_check.cpp):

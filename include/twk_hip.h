@@ -921,7 +921,7 @@ int twk_hip_fisher_exact(twk_hip_ctx* ctx, const int32_t* tables, uint64_t n, do
  * closest relative is the compile-time SLAVE_DEBUG_MODE / SIMD_AVAILABLE switches, lib/ld/ld_engine.h:20-24).
  * The keys, their defaults, ranges and meaning are ONE table in the engine (TWK_HIP_OPTIONS, csrc/hip/twk_hip.hip), readable through
  * twk_hip_option_describe() below and printed as the table of INTEGRATION.md 1 (tests/test_docs_consistency.py keeps the document in
- * step with it).  In short: "fused", "three", "two", "carrier", "one", "prefix" pick the form of the contraction
+ * step with it).  In short: "fused", "three", "uz", "two", "carrier", "one", "prefix" pick the form of the contraction
  * ("prefix_margin" and "prefix_sigma" are the two questions the prefix contraction's planner asks for a tile's stop on its 128-point grid,
  * "prefix_stop" plus "prefix_substop" a test hook that puts every tile's stop on one point of it: DESIGN 3.1c); "lists", "list_max", "probe", "probe_zone",
  * "probe_lds" the carrier-list passes for rare variants; "band_*" the launches of fused runs; "patch_rows" / "patch_cols" / "seg" /
@@ -997,6 +997,13 @@ typedef struct {
 	                                 CC = CH + CQ - in front of their rows' one_end.  They stay part of two_launches and
 	                                 carrier_launches; their row_pairs are their variant pairs, one row x one row, in full-row equivalents
 	                                 under stops                                                                              */
+	uint64_t uz_launches;         /* (appended likewise) Three-product launches through a matrix that contracted U = popc(H_A | H_B) and
+	                                 Z = popc((Q_A ^ Q_B) & ~(H_A | H_B)) in the place of HH and S (option "uz"): two popcounts a
+	                                 word of a variant pair where the products are three.  They stay part of three_launches ...           */
+	uint64_t uz_row_pairs;        /* ... and their plane-row pairs part of three_row_pairs and row_pairs, counted as theirs; a word of them
+	                                 issued v_or + v_bcnt + v_bitop3 + v_bcnt, 12 SIMD cycles a variant pair where three products are 18   */
+	uint64_t uz_split_units;      /* ... and their units of work beyond one a tile: the parts of tiles cut along K at the end of a launch,
+	                                 whose U and Z are added into the matrix with atomics (0: every tile was contracted by one block)      */
 } twk_hip_timing;
 /* Progress of twk_hip_ld_all / twk_hip_ld_region: `cb` runs on the calling thread after every tile
  * with the variant pairs finished so far in the current call and the tile counts.  Replaces the
@@ -1021,7 +1028,7 @@ typedef struct {
 	                                 3 fused UnphasedMath four products, 4 fused UnphasedMath three products,
 	                                 5 two products -> matrix (row variants' H planes x column variants' H, Q) */
 	uint32_t outlier;             /* != 0: flagged by the watch                                                */
-	uint32_t _pad;
+	uint32_t uz;                  /* (in the place of padding) != 0: a kind-1 launch in the (U, Z) form (option "uz")          */
 	/* Appended behind the ABI 5 layout with TWK_HIP_ABI_VERSION still 5 (existing callers' checks pin it): the entry grew, so the stride of the
 	 * array twk_hip_launch_log fills changed - a caller compiled against the older header would misread every entry after the first and must be
 	 * rebuilt; the version check does not catch it (only this library's own binding, built with it, reads the log). */

@@ -431,6 +431,10 @@ __device__ __forceinline__ void contract3_slot(uint32_t (&acc)[8][4], uint32_t a
 	             : "memory", TWK_CLOBBER_P, TWK_CLOBBER_B);
 }
 
+}      // namespace twk
+#include "ld_count_uz.hip.h"      // contract_uz_chunk / _slot: the same launch with (U, Z) in the accumulators, two popcounts a word
+namespace twk {
+
 // ---- persistent work-list form of the same contraction ------------------------------------
 // One launch = a list of 128 x 128 tiles of one super-tile (only the tiles that hold wanted pairs:
 // on/above the diagonal, inside the window band, ...) run by P persistent blocks, P = the number
@@ -487,6 +491,7 @@ struct StoreCounts {
 	static constexpr int META_WORDS = 0;       // nothing to stage for the epilogue
 	static constexpr bool PAIRED_ROWS = false; // a lane's rows are li + 8t (see read_half)
 	static constexpr bool THREE_PRODUCTS = false;
+	static constexpr bool UZ_COUNTS = false;
 	static constexpr bool QUEUED = false;
 	uint32_t* C; uint32_t ldc;
 	__device__ __forceinline__ const uint32_t* meta_src(uint32_t, uint32_t) const { return nullptr; }
@@ -515,6 +520,7 @@ struct StoreCounts3 {
 	static constexpr int META_WORDS = 0;
 	static constexpr bool PAIRED_ROWS = true;
 	static constexpr bool THREE_PRODUCTS = true;
+	static constexpr bool UZ_COUNTS = false;    // (StoreCountsUZ: the accumulators hold (U, Z), ld_count_uz.hip.h)
 	static constexpr bool QUEUED = false;
 	uint32_t* C; uint32_t ldc;
 	__device__ __forceinline__ const uint32_t* meta_src(uint32_t, uint32_t) const { return nullptr; }
@@ -533,6 +539,12 @@ struct StoreCounts3 {
 				acc[2 * s][2 * v] = 0; acc[2 * s + 1][2 * v + 1] = 0;
 			}
 	}
+};
+
+// ... and the (U, Z) form's: the same matrix, (U, Z) where StoreCounts3 leaves (HH, S); the screens convert (ld_two_screen.h: uz_to_hh_s)
+template <int TB>
+struct StoreCountsUZ : StoreCounts3<TB> {
+	static constexpr bool UZ_COUNTS = true;
 };
 
 template <int NW, int EXPERIMENT, class Epilogue>      // EXPERIMENT == 5: the dev tool's finish-time probe (overwrites C)
@@ -719,10 +731,14 @@ __device__ __forceinline__ void count_list_body(const CountWork& w, const Epilog
 		if constexpr (THREE) {
 			// (operand registers placed by hand, see contract3_chunk; a row's last, partly filled chunk slot by slot - the half-slot of padding that may
 			// come with it is zeros)
-			if (h_end == 16) contract3_chunk(acc, bufbase + offA, bufbase + offB);
+			constexpr bool UZ = Epilogue::UZ_COUNTS;
+			if (h_end == 16) { if constexpr (UZ) contract_uz_chunk(acc, bufbase + offA, bufbase + offB); else contract3_chunk(acc, bufbase + offA, bufbase + offB); }
 			else {
 #pragma unroll 1
-				for (uint32_t q = 0; q < (uint32_t)(h_end + 1) >> 1; ++q) contract3_slot(acc, bufbase + (offA ^ (q << 4)), bufbase + (offB ^ (q << 4)));
+				for (uint32_t q = 0; q < (uint32_t)(h_end + 1) >> 1; ++q) {
+					if constexpr (UZ) contract_uz_slot(acc, bufbase + (offA ^ (q << 4)), bufbase + (offB ^ (q << 4)));
+					else contract3_slot(acc, bufbase + (offA ^ (q << 4)), bufbase + (offB ^ (q << 4)));
+				}
 			}
 		} else if (h_end == 16) {
 			uint2 ra[2][8], rb[2][TB];
@@ -810,6 +826,12 @@ void k_count3_list_t(const CountWork w) {
 	count_list_body<NW, EXPERIMENT>(w, StoreCounts3<16 / (NW / 2)>{w.C, w.ldc});
 }
 
+template <int NW, int EXPERIMENT = 0>
+__global__ __launch_bounds__(NW * 64, NW / 2)
+void k_count3_uz_list_t(const CountWork w) {
+	count_list_body<NW, EXPERIMENT>(w, StoreCountsUZ<16 / (NW / 2)>{{w.C, w.ldc}});
+}
+
 // Inclusive prefix sum over the 64 lanes of a wave (all active) without LDS: Hillis-Steele inside each row of 16 lanes
 // (row_shr 1, 2, 4, 8; lanes shifted in from outside a row contribute 0), then row 0's total into row 1 and row 2's into row
 // 3 (row_bcast:15), then lane 31's into rows 2 and 3 (row_bcast:31).  __shfl_up goes through ds_bpermute: six dependent LDS
@@ -868,6 +890,7 @@ struct ScreenWork {
 	uint32_t pre_rows;                 // plane rows of pre_suffix (the set's rows_alloc)
 	const uint32_t* col_lo;            // the matrix screens of ld_three.hip.h only: row at set position a holds the columns >= hi_b0 + col_lo[a - hi_a0] (hi_n entries; null: no limit)
 	uint32_t fine;                     // ... and its screen holds QQ to min(qA, qB, CQ) (the fine walk; ld_two_screen.h: screen2c_slack_cq)
+	uint32_t uz;                       // k_screen3_pairs: the matrix is (U, Z) of a launch in that form (ld_count_uz.hip.h); (HH, S) from the margins before any test (ld_two_screen.h: uz_to_hh_s)
 };
 // -> terms[] of ScreenWork for n_pos set positions (P = 1: rowpop[pos]; P = 2: rowpop[2 pos] + 2 rowpop[2 pos + 1])
 __global__ void k_screen_terms(const uint32_t* __restrict__ rowpop, uint32_t n_pos, int P, double two_n, double cut, float4* __restrict__ terms) {
@@ -931,6 +954,7 @@ template <int TB>
 struct ScreenCounts {
 	static constexpr bool PAIRED_ROWS = false;
 	static constexpr bool THREE_PRODUCTS = false;
+	static constexpr bool UZ_COUNTS = false;
 	static constexpr bool QUEUED = true;       // the wave's queue of prefilter-passing pairs (SlotWindow::q)
 	// staged per tile: [0, 2 TILE) the prefilter's (a / T, sA) of its 128 rows, [2 TILE, 4 TILE) (b, sB) of its 128 columns (ScreenWork::terms),
 	// then - for the exact test - the allele counts of the rows, of the columns, and the rows' band limits
@@ -1125,6 +1149,7 @@ template <int TB, bool THREE = false>
 struct ScreenCountsUnphased {
 	static constexpr bool PAIRED_ROWS = true;
 	static constexpr bool THREE_PRODUCTS = THREE;
+	static constexpr bool UZ_COUNTS = false;
 	static constexpr bool QUEUED = false;
 	// staged per tile: the prefilter's (da / T, sA) of its 64 row variants and (db, sB) of its 64 column variants (ScreenWork::terms), then - for the
 	// exact test - the H / Q counts of its 128 plane rows and of its 128 plane columns, and the band limits of its 64 row variants

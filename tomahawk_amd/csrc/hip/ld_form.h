@@ -24,6 +24,8 @@ struct LaunchForm {
 	bool unphased = false;         // plain unphased planes with UnphasedMath: the list math, if there is one, is the unphased kernel
 	bool three = false;            // the three-product form (HH + S; the candidates' four products are recounted): fused, or ...
 	bool three_plain() const { return three && !fused; }      // ... through a count matrix (long rows): C holds the (HH, S) matrix and, behind it, the candidate list
+	bool uz = false;               // a three_plain() launch whose matrix holds (U, Z) = (popc(H_A | H_B), popc((Q_A ^ Q_B) & ~(H_A | H_B))) in (HH, S)'s place - two popcounts a
+	                               // word for three (ld_count_uz.hip.h); its screen converts (ld_two_screen.h: uz_to_hh_s).  An attribute of three_plain(), never set with `fused`
 	bool two = false;              // the two-product form (HH + HQ through a count matrix, S bounded from the margins): never fused, never with `three`
 	bool keep_three = false;       // option three = 2: whatever a launch's candidate density
 	bool sample = false;           // a density sample (decide_wants below): its count kernel runs under its own name (k_count3_list_t<.., 1>), so that a
@@ -37,7 +39,7 @@ struct LaunchForm {
 	bool reduces() const { return reduce != Reduce::none; }      // ... the launch looks at every pair and keeps no survivor: no screen, no Fisher test, no sort
 };
 inline bool operator==(const LaunchForm& a, const LaunchForm& b) {
-	return a.two_pass == b.two_pass && a.fused == b.fused && a.unphased == b.unphased && a.three == b.three && a.two == b.two && a.keep_three == b.keep_three &&
+	return a.two_pass == b.two_pass && a.fused == b.fused && a.unphased == b.unphased && a.three == b.three && a.uz == b.uz && a.two == b.two && a.keep_three == b.keep_three &&
 	       a.sample == b.sample && a.carrier == b.carrier && a.one == b.one && a.prefix == b.prefix && a.reduce == b.reduce;
 }
 
@@ -66,7 +68,7 @@ struct FormFacts {
 	bool cut_screens = false;                               // an r2 cut-off a screen can use: minR2 > 1e-6 && minR2 <= 1
 	uint32_t chunks = 0;                                    // K chunks of a row (read only where a launch may fuse)
 	bool sorted_u = false;                                  // the set is PS_SORTED_U
-	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1, opt_carrier = 1, opt_one = 1;
+	long long opt_fused = 1, opt_three = 1, opt_two = 1, opt_prefix = 1, opt_carrier = 1, opt_one = 1, opt_uz = 1;
 	uint32_t row_chunks = 0;                                // K chunks of a row (read only where a launch is granted the prefix)
 	uint32_t carrier_chunks = 0;                            // K chunks of a row (read only where a launch is granted the carrier plane)
 };
@@ -88,6 +90,7 @@ inline LaunchForm decide_form(const FormFacts& x, const FormGrant& g) {
 	lf.three = lf.unphased && g.three && x.opt_three != 0;
 	lf.fused = x.opt_fused != 0 && (x.opt_fused == 2 || x.chunks <= FUSED_MAX_CHUNKS);
 	if (lf.three && !lf.fused && !lf.two_pass && x.sorted_u && g.two && x.opt_two != 0) { lf.two = true; lf.three = false; }
+	lf.uz = lf.three_plain() && x.opt_uz != 0;      // (the same launch, samples included: what it costs, not what it keeps)
 	lf.carrier = lf.two && g.carrier && x.opt_carrier != 0 && x.carrier_chunks > FUSED_MAX_CHUNKS;
 	lf.one = lf.carrier && g.one && x.opt_one != 0;
 	// the prefix: only the matrix forms of the sorted walk, and only on rows the fused form never takes by policy - whatever "fused" is set to

@@ -24,6 +24,8 @@ namespace twk {
 // the carrier plane H | Q, the matrix holds (CH, CQ) in the same layout and the test is screen2c_keeps; a candidate is (A, B, CH, CQ, -, -).
 // ONE (k_screen1_pairs; ScreenWork::carrier == 2): the matrix is that of a one-product launch - k_count_list_t over the carrier rows of both axes, one
 // count CC = popc(C_A & C_B) per pair, ldc = columns, a tile 128 x 128 variants - the test screen1c_keeps and a candidate (A, B, CC, 0, stop, -).
+// ScreenWork::uz (three products only): the launch ran in the (U, Z) form (ld_count_uz.hip.h) - (HH, S) from (U, Z) and the margins of the range the
+// tile was contracted over, in integers, before any test (ld_two_screen.h: uz_to_hh_s); candidates, recount and list math see no difference.
 constexpr int SCREEN3_THREADS = 256;
 template <bool TWO, bool ONE = false>
 __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__ sp, const StatsParams* __restrict__ pp, const uint32_t* __restrict__ C, uint32_t ldc) {
@@ -45,6 +47,7 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 		if (ONE) hh = C[(size_t)i * ldc + j];
 		else { const uint2 hs = *reinterpret_cast<const uint2*>(C + (size_t)i * ldc + 2 * j); hh = hs.x; s_sum = hs.y; }
 		const ScreenMargins m{s.rowpop[2 * vA], s.rowpop[2 * vA + 1], s.rowpop[2 * vB], s.rowpop[2 * vB + 1]};
+		bool uz = !TWO && s.uz != 0;      // the counts read are (U, Z): converted once, below, with the margins of the range they cover
 		// a prefix launch: the pair's tile was contracted over the chunks [0, stop) only - the counts are the prefix's, and the
 		// unread part of the two rows is bounded by its margins (ld_two_screen.h)
 		if (s.pre_stops) {
@@ -56,11 +59,13 @@ __device__ __forceinline__ void screen_pairs_body(const ScreenWork* __restrict__
 				const uint32_t* fG = s.pre_suffix + (size_t)g * s.pre_rows;
 				const uint2 xA = *reinterpret_cast<const uint2*>(fG + 2 * (size_t)vA), xB = *reinterpret_cast<const uint2*>(fG + 2 * (size_t)vB);
 				const SuffixMargins x{xA.x, xA.y, xB.x, xB.y};
+				if (uz) { const CountsHS hs = uz_prefix_to_hh_s(m, x, hh, s_sum); hh = hs.hh; s_sum = hs.s; uz = false; }      // (U, Z) of the prefix -> its (HH, S)
 				ok = ONE ? screen1c_prefix_keeps(m, x, hh, s.two_n, s.cut)
 				   : TWO ? (s.carrier ? screen2c_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut, s.fine != 0) : screen2_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut))
 				         : screen3_prefix_keeps(m, x, hh, s_sum, s.two_n, s.cut);
 			}
 		}
+		if (uz) { const CountsHS hs = uz_to_hh_s(m, hh, s_sum); hh = hs.hh; s_sum = hs.s; }      // (U, Z) of the whole rows -> (HH, S)
 		if (!stop) ok = ONE ? screen1c_keeps(m, hh, s.two_n, s.cut) : TWO ? (s.carrier ? screen2c_keeps(m, hh, s_sum, s.two_n, s.cut, s.fine != 0) : screen2_keeps(m, hh, s_sum, s.two_n, s.cut)) : screen3_keeps(m, hh, s_sum, s.two_n, s.cut);
 	}
 	__shared__ uint32_t wave_n[SCREEN3_THREADS / 64];

@@ -131,6 +131,18 @@ TWK_SCREEN_FN double prefix_slack(const SuffixMargins& x) {
 TWK_SCREEN_FN bool screen3_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t hh, uint32_t s_sum, double two_n, double cut) {
 	return screen_keeps_between(m, (double)hh, (double)s_sum, (double)s_sum + prefix_slack(x), two_n, cut);
 }
+// ---- the (U, Z) form of the three-product contraction (ld_count_uz.hip.h) ------------------------------------------------------------
+// Such a launch leaves U = popc(H_A | H_B) and Z = popc((Q_A ^ Q_B) & ~(H_A | H_B)) where the product form leaves HH and S.  H and Q of a variant
+// are disjoint and no genotype is missing, so per sample - and over any range of samples, with the margins counted over the same range -
+//     HH = hA + hB - U                                  (inclusion - exclusion),
+//     S  = QH + HQ + 2 QQ = qA + qB - Z                 (qA + qB counts the cells 20 21 22 02 12 22; Z the opposite homozygotes 20 and 02).
+// In integers and exact: the screens behind it test the numbers the product form would have counted.  m: the margins over the range the
+// counts cover - the rows' popcounts, or (uz_prefix_to_hh_s) those minus the suffix margins at the tile's stop.
+struct CountsHS { uint32_t hh, s; };
+TWK_SCREEN_FN CountsHS uz_to_hh_s(const ScreenMargins& m, uint32_t u, uint32_t z) { return CountsHS{m.hA + m.hB - u, m.qA + m.qB - z}; }
+TWK_SCREEN_FN CountsHS uz_prefix_to_hh_s(const ScreenMargins& m, const SuffixMargins& x, uint32_t u, uint32_t z) {
+	return uz_to_hh_s(ScreenMargins{m.hA - x.hA, m.qA - x.qA, m.hB - x.hB, m.qB - x.qB}, u, z);
+}
 // Two products over the prefix: hh = HH_pre, hq = HQ_pre; the prefix's own S is bounded by the prefix margins (total minus suffix).
 TWK_SCREEN_FN bool screen2_prefix_keeps(const ScreenMargins& m, const SuffixMargins& x, uint32_t hh, uint32_t hq, double two_n, double cut) {
 	const double qa = (double)(m.qA - x.qA), qb = (double)(m.qB - x.qB);

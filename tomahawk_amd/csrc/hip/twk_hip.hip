@@ -187,6 +187,7 @@ struct Launch {
 	double minP = 1.0;
 	uint64_t row_pairs = 0, row_pairs_b = 0;      // plane-row pairs of the tiles its (up to two) count kernels contracted - a prefix launch's in full-row
 	                                              // equivalents: x chunks contracted / chunks per row, summed over its tiles and rounded down once
+	uint64_t extra_units = 0;                                // units of the (first) count launch beyond one a tile: parts of tiles cut along K, added into the matrix with atomics
 	uint64_t prefix_chunks = 0, prefix_chunks_full = 0;      // a prefix launch: chunks its tiles were contracted over, and what whole rows would have been
 };
 // Room for the parameter block of a reduce launch of any kind (send_reduce_args): never read as a union, only sized and aligned as one.
@@ -228,6 +229,7 @@ namespace {
 #define TWK_HIP_OPTIONS(X) \
 	X(fused, 1, 0, 2, false, "fused count -> r2 screen kernel (no count matrix; DESIGN 3.2a): 0 never, 1 rows of <= 128 K chunks, 2 always") \
 	X(three, 1, 0, 2, false, "UnphasedMath on planes without missing genotypes, r2 cut-off > 1e-6: contract three products a pair (HH and S = QH + HQ + 2 QQ: all the screen reads) and recount the four products of the pairs that pass (DESIGN 3.1a); 0: four products for every pair; 2: keep to three whatever a launch's candidate density (1 samples every launch first)") \
+	X(uz, 1, 0, 1, false, "the three-product form through a count matrix (rows too long to fuse): contract U = popc(H_A | H_B) and Z = popc((Q_A ^ Q_B) & ~(H_A | H_B)) - two popcounts a word - in the place of HH and S, which the screen derives from them and the margins in integers (HH = hA + hB - U, S = qA + qB - Z; DESIGN 3.1a); candidates, recount and records are unchanged; 0: the three products themselves") \
 	X(two, 1, 0, 2, false, "UnphasedMath, whole triangle without a window, rows too long to fuse, three = 1 and no tile edge given: walk the allele-count-sorted planes and contract two products a pair (HH and HQ of the row variant's H plane; S bounded from the margins) in the launches whose rows have few hom-alt carriers (DESIGN 3.1b); 0: never (the call walks the file order); 2: in every launch of that walk, whatever the predicate and the samples say") \
 	X(carrier, 1, 0, 1, false, "the two-product walk on rows of more than 128 K chunks: its two-product launches contract the row variant's carrier plane (H or Q, bit by bit) in the H plane's place (CH = HH + QH and CQ = HQ + QQ: S >= CQ and S + HH <= CH + CQ + min(qA, qB)), which moves the walk's cut from p ~ 0.16 to ~ 0.21 at r2 >= 0.1; one more plane row per row variant in front of the cut, built on first use and kept with the planes (DESIGN 3.1b); 0: always the H plane") \
 	X(one, 1, 0, 2, false, "the carrier form of the two-product walk: in front of the walk's cut a row block's columns up to its one_end - where the screen's lower test at S >= 0, a function of the two dosages alone, stops passing - are launches that contract one product a pair, the two variants' carrier rows (CC = CH + CQ: all the upper test reads), with carrier rows for the column variants too; the rest of the block's columns stay two-product launches (DESIGN 3.1b); 0: never; 1: launches whose sample in that form is poor in candidates; 2: every such launch whatever its sample") \
@@ -739,7 +741,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	// plane per variant (P = PA = 1 from here on; the planes themselves are not read)
 	const int P_set = planes_per_variant(set_kind(set));
 	if (two && (P_set != 2 || fuse || which != 0)) return TWK_HIP_E_STATE;
-	if ((form.carrier && !two) || (form.one && !form.carrier)) return TWK_HIP_E_STATE;
+	if ((form.carrier && !two) || (form.one && !form.carrier) || (form.uz && !form.three_plain())) return TWK_HIP_E_STATE;
 	const int P = form.one ? 1 : P_set;
 	const int PA = two ? 1 : P;
 	const uint32_t stepA = form.carrier ? 1u : (uint32_t)(P / PA);
@@ -808,6 +810,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 		void (*k_list)(CountWork, const ScreenWork*) = nullptr;
 		void (*k_matrix)(CountWork) = nullptr;
 		if (fuse && three) k_list = form.sample ? k_count3_screen_unphased_t<COUNT_NW, 1> : k_count3_screen_unphased_t<COUNT_NW>;
+		else if (form.uz) k_matrix = form.sample ? k_count3_uz_list_t<COUNT_NW, 1> : k_count3_uz_list_t<COUNT_NW>;
 		else if (three) k_matrix = form.sample ? k_count3_list_t<COUNT_NW, 1> : k_count3_list_t<COUNT_NW>;
 		else if (fuse) k_list = form.unphased ? k_count_screen_unphased_t<COUNT_NW> : k_count_screen_t<COUNT_NW>;
 		else k_matrix = (two && form.sample) ? k_count_list_t<COUNT_NW, 1> : k_count_list_t<COUNT_NW>;
@@ -817,6 +820,7 @@ int launch_count(twk_hip_ctx* c, int set, const twk_hip_tile_desc& t, Slot& s, i
 	}
 	HIPCHK(c, hipEventRecord(e1, c->s_compute));
 	(which ? s.l.row_pairs_b : s.l.row_pairs) = (uint64_t)T * TILE * TILE;
+	if (!which) s.l.extra_units = tb.n_units() > T ? tb.n_units() - T : 0;
 	if (form.prefix) {      // full-row equivalents: what the launch's time is set against (bench.py's roofline, the outlier watch)
 		uint64_t done = 0;
 		for (uint32_t st : stops) done += st;
@@ -915,7 +919,7 @@ LaunchForm launch_form(twk_hip_ctx* c, const TilePlan& pl, const twk_hip_filters
 	x.two_pass = pl.set2 >= 0; x.reduce = c->reduce.kind; x.sorted_u = pl.set1 == PS_SORTED_U;
 	x.phased_plain = pl.phased1 && k == PK_PHASED; x.unphased_plain = !pl.phased1 && k == PK_UNPHASED;
 	x.cut_screens = f.minR2 > 1e-6 && f.minR2 <= 1.0;
-	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix; x.opt_carrier = c->opt.carrier; x.opt_one = c->opt.one;
+	x.opt_fused = c->opt.fused; x.opt_three = c->opt.three; x.opt_two = c->opt.two; x.opt_prefix = c->opt.prefix; x.opt_carrier = c->opt.carrier; x.opt_one = c->opt.one; x.opt_uz = c->opt.uz;
 	if (grant.carrier && c->opt.carrier != 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK && c->planes[pl.set1].carrier_rows) x.carrier_chunks = c->planes[pl.set1].W / KC;
 	// (stops are not combined with the measurement hooks that walk a tile's K range their own way)
 	if (grant.prefix && c->opt.prefix != 0 && c->opt.seg == 0 && c->opt.xcd_queues == 0 && ensure_planes(c, pl.set1) == TWK_HIP_OK) x.row_chunks = c->planes[pl.set1].W / KC;
@@ -1125,6 +1129,7 @@ int enqueue_tile(twk_hip_ctx* c, int mode, const twk_hip_tile_desc& t, const twk
 		sw.list_zone = cr ? cr->list_zone : 0; sw.probe_zone = cr ? cr->probe_zone : 0;
 		sw.cand = l.cand; sw.cap = l.cand_cap; sw.n_cand = s.n_out + 2; sw.carrier = form.one ? 2u : form.carrier ? 1u : 0u;
 		sw.fine = form.carrier && !form.one && walk_fine_applies(c, ps.W / KC) ? 1u : 0u;
+		sw.uz = form.uz ? 1u : 0u;
 		{	// slots a wave reserves at a time: what it cannot use is lost to the list, so at most an eighth of the list's
 			// capacity may be tied up in the waves' windows (small tiles: 0, i.e. one atomic per wave and tile)
 			const unsigned long long per_wave = l.cand_cap / (8ull * c->resident_blocks * (COUNT_THREADS / 64));
@@ -1282,16 +1287,16 @@ void watch_launch(twk_hip_ctx* c, const Slot& s, float ms, const twk_hip_tile_de
 	st.ms = ms; st.row_pairs = s.l.row_pairs; st.candidates = (s.l.form.fused || s.l.form.three || s.l.form.two) ? s.h_n_out[2] : 0;
 	st.shader_mhz = s.h_n_out[5] ? (double)s.h_n_out[4] / (double)s.h_n_out[5] * 100.0 : 0.0;
 	st.words_per_row = c->planes[s.l.plane_set].W_live;
-	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full; st.carrier = s.l.form.carrier ? 1u : 0u; st.one = s.l.form.one ? 1u : 0u;
+	st.prefix_chunks = s.l.prefix_chunks; st.prefix_chunks_full = s.l.prefix_chunks_full; st.carrier = s.l.form.carrier ? 1u : 0u; st.one = s.l.form.one ? 1u : 0u; st.uz = s.l.form.uz ? 1u : 0u;
 	st.kind = s.l.form.fused ? (s.l.form.three ? 4u : (c->planes[s.l.plane_set].rows && set_kind(s.l.plane_set) == PK_UNPHASED ? 3u : 2u)) : (s.l.form.two ? 5u : s.l.form.three_plain() ? 1u : 0u);
 	unsigned long long lo = ~0ull, hi = 0;
 	for (int x = 0; x < 8; ++x) if (s.h_n_out[8 + x]) { lo = std::min(lo, s.h_n_out[8 + x]); hi = std::max(hi, s.h_n_out[8 + x]); }
 	st.xcd_finish_spread_us = hi ? (double)(hi - lo) / 100.0 : 0.0;
-	auto cost = [](const twk_hip_launch_stat& x) { return x.row_pairs ? x.ms / ((double)x.row_pairs * (double)x.words_per_row * ((x.kind == 1 || x.kind == 4) ? 0.75 : 1.0)) : 0.0; };
+	auto cost = [](const twk_hip_launch_stat& x) { return x.row_pairs ? x.ms / ((double)x.row_pairs * (double)x.words_per_row * (x.uz ? 0.5 : (x.kind == 1 || x.kind == 4) ? 0.75 : 1.0)) : 0.0; };
 	if (st.ms >= 0.3 && st.row_pairs) {
 		std::vector<double> peers;
 		for (const auto& x : c->launch_ring)
-			if (x.kind == st.kind && x.words_per_row == st.words_per_row && x.ms >= 0.3 && !x.outlier) peers.push_back(cost(x));
+			if (x.kind == st.kind && x.uz == st.uz && x.words_per_row == st.words_per_row && x.ms >= 0.3 && !x.outlier) peers.push_back(cost(x));
 		if (peers.size() >= 8) {
 			std::nth_element(peers.begin(), peers.begin() + peers.size() / 2, peers.end());
 			const double med = peers[peers.size() / 2];
@@ -1413,7 +1418,13 @@ int finish_tile(twk_hip_ctx* c, Slot& s, const twk_hip_tile_desc& t, unsigned lo
 	       c->timing.count_shader_cycles += s.h_n_out[4]; c->timing.count_wall_ticks += s.h_n_out[5]; }
 	if (s.l.form.fused) { c->timing.fused_launches += 1; c->timing.candidates += s.h_n_out[2]; }
 	if (s.l.form.three) {
-		c->timing.three_launches += 1; c->timing.three_row_pairs += s.l.row_pairs; c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap);
+		c->timing.three_launches += 1; c->timing.three_row_pairs += s.l.row_pairs;
+		c->timing.recount_candidates += std::min<unsigned long long>(s.h_n_out[2], s.l.cand_cap);
+		if (s.l.form.uz) {
+			c->timing.uz_launches += 1;
+			c->timing.uz_row_pairs += s.l.row_pairs;
+			c->timing.uz_split_units += s.l.extra_units;
+		}
 		if (s.l.form.three_plain()) c->timing.candidates += s.h_n_out[2];
 		if (s.h_n_out[3]) {      // the recount disagrees with the contraction: never to be papered over
 			snprintf(c->err, sizeof(c->err), "three-product contraction: %llu candidates whose (HH, S) differ from their recounted products (tile rows %u+%u, cols %u+%u)", s.h_n_out[3], t.rowA0, t.nA, t.rowB0, t.nB);

@@ -871,13 +871,15 @@ bool twk_ld::twk_ld_impl::run(twk_ld_settings& settings, const Header& hdr, cons
 			std::cerr << stamp("LOG", "HIP") << (n_gpus > 1 ? "GPU " + std::to_string(g) + ": " : std::string()) << "count kernel " << tm.count_ms << " ms in "
 			          << tm.count_launches << " launches ("
 			          // what the launches issued: one AND+popcount (6 cycles per wave) per word of a plane-row pair - three for every four of them in
-			          // the three-product form (v_and / v_bitop3 + v_bcnt: no other instruction since round 6)
-			          << (tm.count_ms > 0 ? ((double)(tm.row_pairs - tm.three_row_pairs) + (double)tm.three_row_pairs * 0.75) * (double)tm.words_per_row / (tm.count_ms * 1e-3) / 2.62e13 * 100.0 : 0.0)
+			          // the three-product form (v_and / v_bitop3 + v_bcnt: no other instruction since round 6), and two popcounts behind a v_or and a
+			          // v_bitop3 - 12 cycles for the 24 of four products - in its (U, Z) form
+			          << (tm.count_ms > 0 ? ((double)(tm.row_pairs - tm.three_row_pairs) + (double)(tm.three_row_pairs - tm.uz_row_pairs) * 0.75 + (double)tm.uz_row_pairs * 0.5) * (double)tm.words_per_row / (tm.count_ms * 1e-3) / 2.62e13 * 100.0 : 0.0)
 			          << " % of the and+bcnt issue ceiling over the tiles it contracted"
 			          << (tm.count_wall_ticks ? "; its blocks ran at " + std::to_string((int)((double)tm.count_shader_cycles / (double)tm.count_wall_ticks * 100.0 + 0.5)) + " MHz" : std::string())
 			          << "), math kernels " << tm.stats_ms << " ms"
 			          << (tm.fused_launches ? "; " + std::to_string(tm.fused_launches) + " launches fused count -> r2 screen, " + pretty(tm.candidates) + " candidate slots" : std::string())
 			          << (tm.three_launches ? "; " + std::to_string(tm.three_launches) + " launches in the three-product form (HH + S), " + pretty(tm.recount_candidates) + " candidates recounted" : std::string())
+			          << (tm.uz_launches ? "; " + std::to_string(tm.uz_launches) + " of them counted (U, Z), two popcounts a word" : std::string())
 			          << (tm.prefix_launches && tm.prefix_chunks_full ? "; " + std::to_string(tm.prefix_launches) + " launches contracted a prefix of their rows, " +
 			              std::to_string((int)(100.0 * (double)tm.prefix_chunks / (double)tm.prefix_chunks_full + 0.5)) + " % of them" : std::string())
 			          << (tm.list_launches ? "; carrier-list kernel " + std::to_string(tm.list_ms) + " ms in " + std::to_string(tm.list_launches) + " launches over " + pretty(tm.list_pairs) + " rare pairs" : std::string())

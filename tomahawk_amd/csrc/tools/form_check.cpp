@@ -198,6 +198,35 @@ void check_carrier() {
 	for (const auto& k : CASES) { ++g_cases; CHECK(carrier_operand(k.opt, k.chunks, k.have, k.need) == k.carrier, "carrier_operand(%lld, %u, %u, %u): %s", k.opt, k.chunks, k.have, k.need, k.what); }
 }
 
+// The (U, Z) form: an attribute of a three-product launch through a matrix - what the launch counts, not what it keeps - chosen by option
+// "uz" alone: no grant, no sample and no rung of the ladder knows it.
+void check_uz() {
+	for (const FormFacts& x0 : all_facts()) for (const uint32_t cc : {1u, FUSED_MAX_CHUNKS, FUSED_MAX_CHUNKS + 1}) for (int ou = 0; ou < 2; ++ou) for (int gbits = 0; gbits < 128; ++gbits) {
+		FormFacts x = x0; x.chunks = cc; x.carrier_chunks = cc; x.row_chunks = cc; x.opt_uz = ou;
+		FormGrant g; g.fused = (gbits & 1) != 0; g.three = (gbits & 2) != 0; g.two = (gbits & 4) != 0; g.sample = (gbits & 8) != 0; g.prefix = (gbits & 16) != 0; g.carrier = (gbits & 32) != 0; g.one = (gbits & 64) != 0;
+		const LaunchForm lf = decide_form(x, g);
+		FormFacts x_off = x; x_off.opt_uz = 0;
+		const LaunchForm base = decide_form(x_off, g);
+		++g_cases;
+		{ LaunchForm but_uz = lf; but_uz.uz = false; CHECK(but_uz == base, "option uz changed more than what a three-product launch counts"); }
+		CHECK(!base.uz, "a (U, Z) launch with option uz = 0");
+		CHECK(lf.uz == (ou != 0 && lf.three && !lf.fused), "uz: option %d three %d fused %d", ou, (int)lf.three, (int)lf.fused);
+		CHECK(!lf.uz || (lf.three_plain() && lf.unphased && !lf.two && !lf.carrier && !lf.one && !lf.reduces()), "a (U, Z) launch that is no three-product launch through a matrix");
+		{ LaunchForm other = lf; other.uz = !other.uz; CHECK(!(other == lf), "operator== does not look at uz"); }
+	}
+	// the ladder does not know the form: what a flooded or rich (U, Z) launch gives up and steps down to is the three-product launch's
+	FormGrant all = grant_of(G_FUSED | G_THREE | G_TWO);
+	LaunchForm three; three.unphased = true; three.three = true;
+	LaunchForm uz = three; uz.uz = true;
+	for (int ob = 0; ob < 4; ++ob) {
+		CallForms a, b; a.gave_up(three, all, (ob & 1) != 0, (ob & 2) != 0); b.gave_up(uz, all, (ob & 1) != 0, (ob & 2) != 0);
+		CHECK(a.fused == b.fused && a.three == b.three && a.two == b.two && a.prefix == b.prefix && a.one == b.one, "a (U, Z) launch gave up something else than a three-product launch");
+		++g_cases;
+	}
+	printf("form-check: (U, Z) attribute: three-product launches through a matrix only, by option uz alone; the ladder does not know it\n");
+	{ const FormGrant a = step_down(three, all), b = step_down(uz, all); CHECK(a.fused == b.fused && a.three == b.three && a.two == b.two && a.prefix == b.prefix, "below a (U, Z) launch: what lies below a three-product launch"); ++g_cases; }
+}
+
 // One product a pair: an attribute of a carrier launch - the carrier rows on both axes - granted by the walk's owner launch by launch.
 void check_one() {
 	// decide_form: only with the grant, the option and a launch that takes the carrier form; it changes nothing else
@@ -502,6 +531,7 @@ int main() {
 	check_gave_up();
 	check_carrier();
 	check_one();
+	check_uz();
 	check_named_grants();
 	check_thresholds();
 	check_sample_subtile();

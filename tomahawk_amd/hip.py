@@ -71,7 +71,7 @@ class _Timing(C.Structure):
                 ("three_launches", C.c_uint64), ("three_row_pairs", C.c_uint64), ("recount_candidates", C.c_uint64),
                 ("outlier_launches", C.c_uint64), ("finish_ms", C.c_double), ("two_launches", C.c_uint64),
                 ("prefix_launches", C.c_uint64), ("prefix_chunks", C.c_uint64), ("prefix_chunks_full", C.c_uint64),
-                ("carrier_launches", C.c_uint64), ("one_launches", C.c_uint64)]
+                ("carrier_launches", C.c_uint64), ("one_launches", C.c_uint64), ("uz_launches", C.c_uint64), ("uz_row_pairs", C.c_uint64), ("uz_split_units", C.c_uint64)]
 
 
 class _PlanEnv(C.Structure):         # twk_hip_plan_env
@@ -152,7 +152,7 @@ class Plant(C.Structure):            # twk_hip_plant: LD planted in the syntheti
 
 class _LaunchStat(C.Structure):      # twk_hip_launch_stat
     _fields_ = [("ms", C.c_double), ("shader_mhz", C.c_double), ("xcd_finish_spread_us", C.c_double), ("row_pairs", C.c_uint64),
-                ("candidates", C.c_uint64), ("words_per_row", C.c_uint32), ("kind", C.c_uint32), ("outlier", C.c_uint32), ("_pad", C.c_uint32),
+                ("candidates", C.c_uint64), ("words_per_row", C.c_uint32), ("kind", C.c_uint32), ("outlier", C.c_uint32), ("uz", C.c_uint32),
                 ("prefix_chunks", C.c_uint64), ("prefix_chunks_full", C.c_uint64), ("carrier", C.c_uint32), ("one", C.c_uint32)]
 
 
